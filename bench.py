@@ -14,6 +14,11 @@ Schedule (default `--schedule rotate --pipeline 2`): two passes are in flight pe
 with registration objects, stream and result block of its own -- the few slow-converging pairs of one pass (59 GN
 iterations where the mean is 12) finish under the bulk of the next.  The timed region is EXACTLY `--steps` passes.
 
+A plain run sets up, warms up, times the steps and prints the headline.  `--full` adds what takes passes or legs of its own:
+the vector-issue roofline of the search kernel (HIP events on the timed launches, a single-stream pass, a counters pass), the
+check of the gathered poses (N>1), the CPU baseline and the full-size parity against the oracle.  `--dump-outputs DIR` writes
+the results of the last timed pass as DIR/<field>.npy (float32 / float64), so that two builds can be compared output for output.
+
 Prints ONE JSON line (rank 0).  Launch for N>1 with torch.distributed.run.
 """
 from __future__ import annotations
@@ -132,6 +137,18 @@ def full_size_parity(gpu_results, oracle_results):
             "parity_ok": bool(n > 0 and max_dt < 1e-4 and max_dr < 1e-4)}
 
 
+RESULT_FIELDS = {"T": np.float32, "T64": np.float64, "H": np.float64, "cost": np.float64, "iterations": np.float64, "converged": np.float64,
+                 "num_linearize": np.float64, "num_compute_error": np.float64, "num_inliers": np.float64, "status": np.float64}
+
+
+def dump_outputs(out_dir, results):
+    """What align_batch handed back in the last timed pass, one array per pcm_result field over the pairs in pair order
+    (T (n,4,4), T64 (n,4,4), H (n,6,6), the scalars (n,); counts and flags as float64), as out_dir/<field>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, dtype in RESULT_FIELDS.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.stack([np.asarray(getattr(r, name), dtype) for r in results]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -151,7 +168,11 @@ def main():
     ap.add_argument("--optimizer", default="GN", choices=["GN", "LM"])
     ap.add_argument("--max-iterations", type=int, default=64)
     ap.add_argument("--sort-source", type=int, default=1)
-    ap.add_argument("--cpu-seconds", type=float, default=40.0, help="budget of the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=40.0, help="budget of the cpu_baseline leg of --full (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what needs passes or legs of its own: roofline, gathered-pose check, cpu_baseline, full-size parity")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the results of the last timed pass (rank 0's pairs) as DIR/<field>.npy in float32 / float64")
     ap.add_argument("--gen-workers", type=int, default=0)
     ap.add_argument("--pairs-cache", default="", help="load the rank-0 pairs from an .npz written by tools/gen_cache.py (profiling runs: the program behind "
                     "rocprofv3 must not fork, and generating 64 pairs in-process takes minutes)")
@@ -164,6 +185,8 @@ def main():
     ap.add_argument("--collectives-at-one", type=int, default=0,
                     help="1: at N=1 still create the process group and run the per-pass all-gather (world size 1): executes the RCCL path of N>1 on one GPU")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -346,106 +369,113 @@ def main():
     fence()
     t_warm = (time.perf_counter() - t0) / (max(1, args.warmup - 1) * per)
 
-    for j in range(S):
-        lead[j].reset_stats()
-        # HIP events around every 4th residual launch, on the launch stream (bit3: sampled, the phase rotating from batch to batch:
-        # bracketing EVERY launch costs 16 % of the headline -- three events on the critical path of every round)
-        lead[j].set_profiling(int(os.environ.get("PCM_BENCH_LAUNCH_EVENTS", "9")))
+    if args.full:
+        for j in range(S):
+            lead[j].reset_stats()
+            # HIP events around every 4th residual launch, on the launch stream (bit3: sampled, the phase rotating from batch to batch:
+            # bracketing EVERY launch costs 16 % of the headline -- three events on the critical path of every round)
+            lead[j].set_profiling(int(os.environ.get("PCM_BENCH_LAUNCH_EVENTS", "9")))
     fence()
     t0 = time.perf_counter()
     res = run_steps(args.steps, stagger_s=args.stagger * t_warm if S > 1 else 0.0)
     fence()
     elapsed = time.perf_counter() - t0
-    sts = [lead[j].stats() for j in range(S)]
-    st = {k: sum(x[k] for x in sts) for k in sts[0]}
-    for j in range(S):
-        lead[j].set_profiling(0)
+    if args.full:
+        sts = [lead[j].stats() for j in range(S)]
+        st = {k: sum(x[k] for x in sts) for k in sts[0]}
+        for j in range(S):
+            lead[j].set_profiling(0)
 
     t = torch.tensor([elapsed, t_cold], dtype=torch.float64, device=dev)
     if use_dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed, t_cold = float(t[0]), float(t[1])
 
-    # single-stream pass (untimed): the dominant kernel alone on the device, HIP events around EVERY launch on the launch stream
-    # -- the two-slot figure above includes the time a launch shares the CUs with the other slot's grid
-    lead[0].reset_stats()
-    lead[0].set_profiling(1)
-    n_single = max(2, min(10, args.steps))
-    if rotate:
-        sharding.run_rotating_steps(n_single, 1, sub_step, None, 0.0, on_thread_start=lambda: torch.cuda.set_device(dev_index))
-    else:
-        sharding.run_pipelined_steps(n_single, 1, sub_step, None, 0.0, on_thread_start=lambda: torch.cuda.set_device(dev_index))
-    torch.cuda.synchronize()
-    s1 = lead[0].stats()
-    lead[0].set_profiling(0)
-
-    # counters pass (untimed): candidates / probes per point for the algorithmic-byte model
-    for j in range(S):
-        lead[j].reset_stats()
-        lead[j].set_profiling(3)
-    run_steps(S if rotate else 1)
-    scs = [lead[j].stats() for j in range(S)]
-    sc = {k: sum(x[k] for x in scs) for k in scs[0]}
-    for j in range(S):
-        lead[j].set_profiling(0)
-    kbar = sc["candidates"] / max(1, sc["point_passes"])
-    probes = sc["slots_probed"] / max(1, sc["point_passes"])
-
-    gathered_ok = None
-    if use_dist:   # untimed check of the exchange: own block round-trips, every rank's poses arrived
-        allrec = d_gather.view(n_sets, world, n_local * rec)[0]
-        if not torch.equal(allrec[rank], d_results[:n_local * rec]):
-            raise SystemExit("rank %d: gathered block differs from the local results" % rank)
-        gathered_ok = sum(int(r["status"] == 0) for r in sharding.records_to_results(allrec.reshape(-1)))
-
     total_regs = args.steps * n_local * world
     value = total_regs / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
 
-    # ---- roofline of the dominant kernel (k_linearize) ------------------------------------------------------------
-    # The kernel is a gather + reduction served from LDS: its physical HBM traffic is a few percent of the peak, and the
-    # SURVEY §8(d) byte model ("no reuse assumed": query + 27 slots + K-bar candidates per point pass) prices bytes the LDS staging
-    # never moves -- round 2's fraction against it exceeded 1.  What bounds it is vector-instruction issue: the roofline is
-    # wave-instructions per second against 1024 SIMDs x 2.4 GHz / 2 cycles.  Instructions per wave come from a committed
-    # SQ_INSTS_VALU / SQ_WAVES pass of the same sources (profiles/pmc_valu.json, tools/r03_counters.sh); time is the step's wall time.
-    workload_key = "%d_%d_%d_%s" % (args.scan_points, args.map_points, n_local, args.optimizer)
-    launches = max(1, st["linearize_launches"])
-    timed = max(1, st["timed_launches"])
-    share = st["timed_pair_slots"] / max(1, st["launched_pair_slots"])   # the timed launches' share of the point passes: by the length of their pair lists
-    pp_per_step = st["point_passes"] / args.steps                         # point passes of this rank per step
-    waves_per_step = pp_per_step / 64.0
-    avg_launch_ms = st["linearize_ms"] / timed                            # two slots: sampled launches, other slot's grid sharing the device
-    pp_per_timed_launch = st["point_passes"] * share / timed
-    single_launch_ms = s1["linearize_ms"] / max(1, s1["timed_launches"])  # the kernel alone on the device
-    pp_per_single_launch = s1["point_passes"] / max(1, s1["timed_launches"])
-    valu, valu_ok = load_profile("pmc_valu.json", workload_key)
-    traffic_p, traffic_ok = load_profile("pmc_traffic.json", workload_key)
-    valu_per_wave = float(valu["valu_per_wave"]) if valu else None
-    b_pi = POINT_BYTES + cfg["num_neighbors"] * SLOT_BYTES + kbar * POINT_BYTES
     # the kernel the timed passes run (pcm_amd.h PCM_FLAG_*): candidate lists by default from a target's second registration on
     search_kernel = "k_linearize_counted" if (args.flags & 8) else ("k_linearize" if (args.flags & (64 | 32 | 2 | 1)) else "k_linearize_lists")
-    roof = {"bound": "valu_issue", "unit": "G wave-instructions/s", "peak": VALU_PEAK_GIPS, "kernel": search_kernel,
-            "achieved": None, "frac": None, "traffic": None}
-    if valu_per_wave:
-        ach = valu_per_wave * waves_per_step / (ms_per_step * 1e-3) / 1e9
-        alone = valu_per_wave * (pp_per_single_launch / 64.0) / (single_launch_ms * 1e-3) / 1e9 if single_launch_ms > 0 else None
-        roof.update({"achieved": ach, "frac": ach / VALU_PEAK_GIPS,
-                     "valu_instructions_per_wave": valu_per_wave, "counters_match_binary": valu_ok, "counters_file": "profiles/pmc_valu.json",
-                     "wave_cycles_waiting_frac": valu.get("wait_any_frac"), "wave_cycles_issue_stalled_frac": valu.get("wait_inst_any_frac"),
-                     "kernel_alone_achieved": alone, "kernel_alone_frac": (alone / VALU_PEAK_GIPS) if alone else None})
-    if traffic_p:
-        hb = float(traffic_p["hbm_bytes_per_launch"])   # FETCH_SIZE x 2 + WRITE_SIZE of one launch of the profiled run (its launches carry the same mean pair count)
-        roof.update({"traffic": hb, "traffic_match_binary": traffic_ok,
-                     "hbm_GBps_physical": hb / (single_launch_ms * 1e-3) / 1e9 if single_launch_ms > 0 else None,
-                     "hbm_frac_physical": hb / (single_launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if single_launch_ms > 0 else None})
-    roof.update({"avg_launch_ms_two_slots": avg_launch_ms, "point_passes_per_launch_two_slots": pp_per_timed_launch,
-                 "avg_launch_ms_single_stream": single_launch_ms, "point_passes_per_launch_single_stream": pp_per_single_launch,
-                 "launches_per_step": launches / args.steps,
-                 # reconciliation: sum of the dominant kernel's launch times per step over the step's wall time; > 1 = the two slots' grids overlap
-                 "sum_launch_ms_over_step_ms": (launches / args.steps) * avg_launch_ms / ms_per_step,
-                 "algorithmic_bytes_per_point_pass": b_pi, "algorithmic_GBps_informational": pp_per_step * b_pi / (ms_per_step * 1e-3) / 1e9,
-                 "candidates_per_point": kbar, "slots_probed_per_point": probes,
-                 "tiles_on_lds_grid": sc["tiles_lds_grid"] / max(1, sc["tiles"]), "tiles_staged_through_lds": sc["tiles_lds_points"] / max(1, sc["tiles"])})
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
+
+    roof, gathered_ok = None, None
+    if args.full:
+        # single-stream pass (untimed): the dominant kernel alone on the device, HIP events around EVERY launch on the launch stream
+        # -- the two-slot figure above includes the time a launch shares the CUs with the other slot's grid
+        lead[0].reset_stats()
+        lead[0].set_profiling(1)
+        n_single = max(2, min(10, args.steps))
+        if rotate:
+            sharding.run_rotating_steps(n_single, 1, sub_step, None, 0.0, on_thread_start=lambda: torch.cuda.set_device(dev_index))
+        else:
+            sharding.run_pipelined_steps(n_single, 1, sub_step, None, 0.0, on_thread_start=lambda: torch.cuda.set_device(dev_index))
+        torch.cuda.synchronize()
+        s1 = lead[0].stats()
+        lead[0].set_profiling(0)
+
+        # counters pass (untimed): candidates / probes per point for the algorithmic-byte model
+        for j in range(S):
+            lead[j].reset_stats()
+            lead[j].set_profiling(3)
+        run_steps(S if rotate else 1)
+        scs = [lead[j].stats() for j in range(S)]
+        sc = {k: sum(x[k] for x in scs) for k in scs[0]}
+        for j in range(S):
+            lead[j].set_profiling(0)
+        kbar = sc["candidates"] / max(1, sc["point_passes"])
+        probes = sc["slots_probed"] / max(1, sc["point_passes"])
+
+        if use_dist:   # untimed check of the exchange: own block round-trips, every rank's poses arrived
+            allrec = d_gather.view(n_sets, world, n_local * rec)[0]
+            if not torch.equal(allrec[rank], d_results[:n_local * rec]):
+                raise SystemExit("rank %d: gathered block differs from the local results" % rank)
+            gathered_ok = sum(int(r["status"] == 0) for r in sharding.records_to_results(allrec.reshape(-1)))
+
+        # ---- roofline of the dominant kernel (k_linearize) ------------------------------------------------------------
+        # The kernel is a gather + reduction served from LDS: its physical HBM traffic is a few percent of the peak, and the
+        # SURVEY §8(d) byte model ("no reuse assumed": query + 27 slots + K-bar candidates per point pass) prices bytes the LDS staging
+        # never moves -- round 2's fraction against it exceeded 1.  What bounds it is vector-instruction issue: the roofline is
+        # wave-instructions per second against 1024 SIMDs x 2.4 GHz / 2 cycles.  Instructions per wave come from a committed
+        # SQ_INSTS_VALU / SQ_WAVES pass of the same sources (profiles/pmc_valu.json, tools/r03_counters.sh); time is the step's wall time.
+        workload_key = "%d_%d_%d_%s" % (args.scan_points, args.map_points, n_local, args.optimizer)
+        launches = max(1, st["linearize_launches"])
+        timed = max(1, st["timed_launches"])
+        share = st["timed_pair_slots"] / max(1, st["launched_pair_slots"])   # the timed launches' share of the point passes: by the length of their pair lists
+        pp_per_step = st["point_passes"] / args.steps                         # point passes of this rank per step
+        waves_per_step = pp_per_step / 64.0
+        avg_launch_ms = st["linearize_ms"] / timed                            # two slots: sampled launches, other slot's grid sharing the device
+        pp_per_timed_launch = st["point_passes"] * share / timed
+        single_launch_ms = s1["linearize_ms"] / max(1, s1["timed_launches"])  # the kernel alone on the device
+        pp_per_single_launch = s1["point_passes"] / max(1, s1["timed_launches"])
+        valu, valu_ok = load_profile("pmc_valu.json", workload_key)
+        traffic_p, traffic_ok = load_profile("pmc_traffic.json", workload_key)
+        valu_per_wave = float(valu["valu_per_wave"]) if valu else None
+        b_pi = POINT_BYTES + cfg["num_neighbors"] * SLOT_BYTES + kbar * POINT_BYTES
+        roof = {"bound": "valu_issue", "unit": "G wave-instructions/s", "peak": VALU_PEAK_GIPS, "kernel": search_kernel,
+                "achieved": None, "frac": None, "traffic": None}
+        if valu_per_wave:
+            ach = valu_per_wave * waves_per_step / (ms_per_step * 1e-3) / 1e9
+            alone = valu_per_wave * (pp_per_single_launch / 64.0) / (single_launch_ms * 1e-3) / 1e9 if single_launch_ms > 0 else None
+            roof.update({"achieved": ach, "frac": ach / VALU_PEAK_GIPS,
+                         "valu_instructions_per_wave": valu_per_wave, "counters_match_binary": valu_ok, "counters_file": "profiles/pmc_valu.json",
+                         "wave_cycles_waiting_frac": valu.get("wait_any_frac"), "wave_cycles_issue_stalled_frac": valu.get("wait_inst_any_frac"),
+                         "kernel_alone_achieved": alone, "kernel_alone_frac": (alone / VALU_PEAK_GIPS) if alone else None})
+        if traffic_p:
+            hb = float(traffic_p["hbm_bytes_per_launch"])   # FETCH_SIZE x 2 + WRITE_SIZE of one launch of the profiled run (its launches carry the same mean pair count)
+            roof.update({"traffic": hb, "traffic_match_binary": traffic_ok,
+                         "hbm_GBps_physical": hb / (single_launch_ms * 1e-3) / 1e9 if single_launch_ms > 0 else None,
+                         "hbm_frac_physical": hb / (single_launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if single_launch_ms > 0 else None})
+        roof.update({"avg_launch_ms_two_slots": avg_launch_ms, "point_passes_per_launch_two_slots": pp_per_timed_launch,
+                     "avg_launch_ms_single_stream": single_launch_ms, "point_passes_per_launch_single_stream": pp_per_single_launch,
+                     "launches_per_step": launches / args.steps,
+                     # reconciliation: sum of the dominant kernel's launch times per step over the step's wall time; > 1 = the two slots' grids overlap
+                     "sum_launch_ms_over_step_ms": (launches / args.steps) * avg_launch_ms / ms_per_step,
+                     "algorithmic_bytes_per_point_pass": b_pi, "algorithmic_GBps_informational": pp_per_step * b_pi / (ms_per_step * 1e-3) / 1e9,
+                     "candidates_per_point": kbar, "slots_probed_per_point": probes,
+                     "tiles_on_lds_grid": sc["tiles_lds_grid"] / max(1, sc["tiles"]), "tiles_staged_through_lds": sc["tiles_lds_points"] / max(1, sc["tiles"])})
 
     out = None
     if rank == 0:
@@ -468,9 +498,9 @@ def main():
                        "cold_registrations_per_s": n_local * world / t_cold, "gen_s": t_gen, "gathered_ok": gathered_ok},
             "roofline": roof,
         }
-        # the CPU leg is timed on rank 0 of the single-GPU run only (the other ranks would idle behind it)
+        # the CPU leg (--full) is timed on rank 0 of the single-GPU run only (the other ranks would idle behind it)
         out["cpu_baseline"] = None
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full and args.cpu_seconds > 0 and world == 1:
             out["cpu_baseline"], oracle_results = cpu_baseline(pairs, cfg, args.cpu_seconds)
             out["config"].update(full_size_parity(res, oracle_results))   # untimed: the timed GPU poses against the oracle's, full size
             one, _ = cpu_baseline(pairs[:3], cfg, min(15.0, args.cpu_seconds), threads=1)

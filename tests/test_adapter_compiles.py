@@ -58,12 +58,12 @@ int main() {
 '''
 
 
-def test_adapter_header_compiles_against_stub_pcl_and_links_against_the_c_abi():
+def test_adapter_header_compiles_against_stub_pcl_and_links_against_the_c_abi(tmp_path):
     inc = ["-I", os.path.join(ROOT, "tests", "stubs"), "-I", os.path.join(ROOT, "include")]
     subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-Wno-unused-parameter", "-fsyntax-only", "-x", "c++", "-"] + inc, input=SRC.encode(), check=True)
     lib = os.path.join(ROOT, "pointcloud-slam_amd", "libpcm_amd.so")
     if os.path.exists(lib):   # every pcm_* symbol the adapter calls exists in the library (no GPU needed to link)
-        subprocess.run(["g++", "-std=c++17", "-x", "c++", "-", "-o", "/tmp/pcm_adapter_link_check"] + inc +
+        subprocess.run(["g++", "-std=c++17", "-x", "c++", "-", "-o", str(tmp_path / "pcm_adapter_link_check")] + inc +
                        ["-L", os.path.dirname(lib), "-lpcm_amd", "-Wl,-rpath," + os.path.dirname(lib), "-Wl,--unresolved-symbols=ignore-in-shared-libs"],
                        input=SRC.encode(), check=True)
 

@@ -28,7 +28,7 @@ def test_library_exports_every_declared_symbol(pcm):
     assert L.pcm_abi_version() == 3
 
 
-def test_struct_layouts_match_header(pcm):
+def test_struct_layouts_match_header(pcm, tmp_path):
     from pointcloud_slam_amd import capi
     src = r'''
     #include <stdio.h>
@@ -39,7 +39,7 @@ def test_struct_layouts_match_header(pcm):
              offsetof(pcm_config, voxel_resolution), offsetof(pcm_config, flags), offsetof(pcm_result, H), offsetof(pcm_result, status));
       return 0;
     }'''
-    exe = "/tmp/pcm_layout_check"
+    exe = str(tmp_path / "pcm_layout_check")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src.encode(), check=True)
     got = [int(x) for x in subprocess.check_output([exe]).split()]
     want = [C.sizeof(capi.PcmConfig), C.sizeof(capi.PcmResult), C.sizeof(capi.PcmStats), capi.PcmConfig.voxel_resolution.offset,
@@ -98,7 +98,7 @@ def test_product_never_imports_the_oracle():
             assert "oracle" not in open(p).read()
 
 
-def test_plane_fit_host_math_equals_oracle_bitwise():
+def test_plane_fit_host_math_equals_oracle_bitwise(tmp_path):
     """csrc/plane_fit.h (the kernel's plane fit, compiled here for the host with g++)
     against the oracle's restatement on 60k random neighbourhoods, m = 3, 4, 5."""
     from oracle import build
@@ -131,14 +131,14 @@ def test_plane_fit_host_math_equals_oracle_bitwise():
       printf("%d\n", nbad);
       return 0;
     }'''
-    exe = "/tmp/pcm_planefit_check"
+    exe = str(tmp_path / "pcm_planefit_check")
     subprocess.run(["g++", "-O2", "-ffp-contract=off", "-x", "c++", "-", "-I", os.path.join(ROOT, "pointcloud-slam_amd", "csrc"),
                     "-L", os.path.join(ROOT, "oracle"), "-lpcm_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-o", exe],
                    input=src.encode(), check=True)
     assert int(subprocess.check_output([exe]).strip()) == 0
 
 
-def test_lsq_step_host_matches_oracle(synth):
+def test_lsq_step_host_matches_oracle(synth, tmp_path):
     """csrc/lsq_step.h (the GN / LM state machine the device runs: left-looking pivoted LDL^T, so3_exp, convergence test,
     LM rho / lambda / nu bookkeeping) is compiled for the HOST with g++ and fed the oracle's trace of an align() -- every
     linearize (cost, H, b) and every trial cost in order: the replay must end in the oracle's pose bit for bit, with the same
@@ -174,7 +174,7 @@ def test_lsq_step_host_matches_oracle(synth):
       printf("%a %a\n", s.lambda, s.nu);
       return 0;
     }'''
-    exe = "/tmp/pcm_lsq_step_check"
+    exe = str(tmp_path / "pcm_lsq_step_check")
     subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-x", "c++", "-", "-I", os.path.join(ROOT, "pointcloud-slam_amd", "csrc"), "-o", exe],
                    input=src.encode(), check=True)
     p = synth.make_pair(5, 3000, 40000)

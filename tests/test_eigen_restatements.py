@@ -22,12 +22,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _DEV = None
 
 
-def _device_twins():
+def _device_twins(tmp_path_factory):
     """The DEVICE twins (csrc/dev_linalg.h, lsq_step.h, plane_fit.h) compiled for the host behind the same hook names
     (tests/dev_linalg_hooks.cpp), -ffp-contract=off like the kernels."""
     global _DEV
     if _DEV is None:
-        so = "/tmp/pcm_dev_linalg_hooks.so"
+        so = str(tmp_path_factory.mktemp("dev_linalg") / "pcm_dev_linalg_hooks.so")
         subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I", os.path.join(ROOT, "pointcloud-slam_amd", "csrc"),
                         os.path.join(ROOT, "tests", "dev_linalg_hooks.cpp"), "-o", so], check=True)
         _DEV = C.CDLL(so)
@@ -35,9 +35,9 @@ def _device_twins():
 
 
 @pytest.fixture(params=["oracle", "device_twin"])
-def L(request):
+def L(request, tmp_path_factory):
     """Every check below runs twice: on oracle/orc_eigen.h and on the code the kernels run."""
-    return lib() if request.param == "oracle" else _device_twins()
+    return lib() if request.param == "oracle" else _device_twins(tmp_path_factory)
 EPS64 = np.finfo(np.float64).eps
 EPS32 = np.finfo(np.float32).eps
 

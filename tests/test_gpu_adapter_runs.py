@@ -81,10 +81,9 @@ int main(int argc, char** argv) {
 '''
 
 
-def test_adapter_program_runs_and_matches_ctypes(pcm, synth):
+def test_adapter_program_runs_and_matches_ctypes(pcm, synth, tmp_path):
     p = synth.make_pair(5, 8000, 80000)
-    d = "/tmp/pcm_adapter_run"
-    os.makedirs(d, exist_ok=True)
+    d = str(tmp_path)
     p.submap.astype(np.float32).tofile(os.path.join(d, "map.bin"))
     p.scan.astype(np.float32).tofile(os.path.join(d, "scan.bin"))
     p.guess.astype(np.float32).tofile(os.path.join(d, "guess.bin"))

@@ -80,13 +80,13 @@ def test_pose_spread_of_the_two_orders_on_config1(optimizer):
     assert abs(res["ascending"].num_inliers - res["libstdcxx"].num_inliers) <= 20
 
 
-def test_device_nth_element_restatement_equals_libstdcxx():
+def test_device_nth_element_restatement_equals_libstdcxx(tmp_path):
     """pointcloud-slam_amd/csrc/nth_select.h (what PCM_FLAG_REFERENCE_KNN_ORDER runs on the device) against std::nth_element of the
     container's libstdc++: the same permutation on every one of 200 000 arrays, the heap-select fallback included."""
     import os
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = "/tmp/pcm_nth_select_check"
+    exe = str(tmp_path / "pcm_nth_select_check")
     subprocess.run(["g++", "-O2", "-std=c++17", "-I", os.path.join(root, "pointcloud-slam_amd", "csrc"), os.path.join(root, "tests", "nth_select_check.cpp"), "-o", exe], check=True)
     out = subprocess.check_output([exe]).decode()
     assert out.startswith("ok 200000 cases"), out
