@@ -389,7 +389,7 @@ __global__ void __launch_bounds__(256) k_linearize_lists(const PairDesc* __restr
               px[j] = mp.x; py[j] = mp.y; pz[j] = mp.z;
             }
             float4 fit;
-            if (esti_plane(px, py, pz, best.m, kp.plane_threshold, &fit)) pl = fit;
+            if (esti_plane<true>(px, py, pz, best.m, kp.plane_threshold, &fit)) pl = fit;
           }
         }
       }

@@ -34,6 +34,40 @@ PCM_HD_FN inline float pcm_divf_rn(float a, float b) {
 #endif
 }
 
+#if defined(__HIP_DEVICE_COMPILE__)
+// ---- device-only shortcuts of the two correctly rounded sequences above, bit-identical to them inside a window -------------
+// sqrtf() is lowered to: x' = x < 2^-96 ? x * 2^32 : x;  s = v_sqrt_f32(x');  s-, s+ = s -+ 1 ulp (integer add);
+// s = fma(-s-, s, x') <= 0 ? s- : s;  s = fma(-s+, s, x') > 0 ? s+ : s;  s = x < 2^-96 ? s * 2^-16 : s;  x is +-0 or +inf ? x : s.
+// For 2^-96 <= x < +inf every select takes its pass-through operand, so fsqrt_fast() below -- the same instructions without
+// the scaling and the class test -- returns the same bits.  Outside the window (0, denormals, tiny, inf, NaN, negatives) the
+// callers take the full sequence.
+__device__ inline bool fsqrt_in_window(float x) { return x >= 0x1p-96f && x < __builtin_inff(); }   // false for NaN
+__device__ inline float fsqrt_fast(float x) {
+  const float s = __builtin_amdgcn_sqrtf(x);
+  const float sd = __uint_as_float(__float_as_uint(s) - 1u), su = __uint_as_float(__float_as_uint(s) + 1u);
+  const float rd = __builtin_fmaf(-sd, s, x), ru = __builtin_fmaf(-su, s, x);
+  const float r = rd <= 0.f ? sd : s;
+  return ru > 0.f ? su : r;
+}
+// __fdiv_rn(a, b) is lowered to: b' = v_div_scale(b), a' = v_div_scale(a);  y0 = v_rcp(b');  y = fma(fma(-b', y0, 1), y0, y0);
+// q0 = a' y;  q1 = fma(fma(-b', q0, a'), y, q0);  q = v_div_fmas(fma(-b', q1, a'), y, q1);  v_div_fixup(q, b, a).
+// With 2^-40 <= |a|, |b| < 2^40 (biased exponents 87..166) v_div_scale leaves both operands as they are and clears VCC
+// (exponent difference < 96, neither 1/b nor a/b denormal, exponent of a > 23), so v_div_fmas is a plain fma, and
+// v_div_fixup returns q with the sign of a xor b, which q already has (|a/b| >= 2^-80: no zero, inf or NaN to fix).  The
+// reciprocal y depends on b alone, so divisions by one denominator share it: fdiv_recip() once, fdiv_fast() per numerator
+// (5 instructions in place of 11).  Outside the window the callers take __fdiv_rn.
+__device__ inline bool fdiv_in_window(float x) { return fabsf(x) >= 0x1p-40f && fabsf(x) < 0x1p40f; }   // false for NaN
+__device__ inline float fdiv_recip(float b) {
+  const float y0 = __builtin_amdgcn_rcpf(b);
+  return __builtin_fmaf(__builtin_fmaf(-b, y0, 1.0f), y0, y0);
+}
+__device__ inline float fdiv_fast(float a, float b, float y) {
+  const float q0 = a * y;
+  const float q1 = __builtin_fmaf(__builtin_fmaf(-b, q0, a), y, q0);
+  return __builtin_fmaf(__builtin_fmaf(-b, q1, a), y, q1);
+}
+#endif
+
 // ---------------------------------------------------------------------------
 // Eigen::ColPivHouseholderQR<Matrix<T,R,3>>(A).solve(-ones)  (common_lib.h:199-208, 210-226), restated from the Eigen
 // sources in the reference tree (E = /root/reference/src/pointcloud_match/fast_gicp/thirdparty/Eigen/Eigen/src):
@@ -62,6 +96,38 @@ template <> struct Num<double> {
   static PCM_HD_FN double sqrt_(double v) { return sqrt(v); }
   static PCM_HD_FN double div_(double a, double b) { return a / b; }
 };
+
+// FAST (device, float): the window sequences above with no branch; `ok` clears when an operand leaves its window, and the
+// caller then repeats the whole fit with the full sequences (sqrt: 11 instructions in place of 15; a division by a shared
+// denominator: 7 in place of 11)
+template <typename T, bool FAST>
+PCM_HD_FN inline T qr_sqrt(T v, bool& ok) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (FAST) {
+    ok &= fsqrt_in_window(v);
+    return fsqrt_fast(v);
+  }
+#endif
+  return Num<T>::sqrt_(v);
+}
+// v[I0 .. R) /= b
+template <typename T, bool FAST, int R, int I0>
+PCM_HD_FN inline void qr_div_tail(T (&v)[R], T b, bool& ok) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (FAST) {
+    ok &= fdiv_in_window(b);
+    const float y = fdiv_recip(b);
+#pragma unroll
+    for (int i = I0; i < R; i++) {
+      ok &= fdiv_in_window(v[i]);
+      v[i] = fdiv_fast(v[i], b, y);
+    }
+    return;
+  }
+#endif
+#pragma unroll
+  for (int i = I0; i < R; i++) v[i] = Num<T>::div_(v[i], b);
+}
 
 // sum of N (<= 2 packets) contiguous scalars in the order Eigen's vectorised reduction adds them
 template <typename T, int N>
@@ -106,8 +172,8 @@ PCM_HD_FN inline T eig_tail_dot(const T (&x)[R], const T (&y)[R]) {
   }
 }
 
-template <typename T, int R, int K0>
-PCM_HD_FN inline void colpiv_qr_step(T (&A)[3][R], T (&nu)[3], T (&nd)[3], int (&perm)[3], T (&hc)[3], int& nonzero, T thr_helper, T downdate_thr) {
+template <typename T, int R, int K0, bool FAST>
+PCM_HD_FN inline void colpiv_qr_step(T (&A)[3][R], T (&nu)[3], T (&nd)[3], int (&perm)[3], T (&hc)[3], int& nonzero, T thr_helper, T downdate_thr, bool& ok) {
   constexpr int k = K0;
   int big = k;
   T bign = nu[k];
@@ -116,9 +182,14 @@ PCM_HD_FN inline void colpiv_qr_step(T (&A)[3][R], T (&nu)[3], T (&nd)[3], int (
     if (nu[j] > bign) { bign = nu[j]; big = j; }
   }
   if (nonzero == 3 && bign * bign < thr_helper * (T)(R - k)) nonzero = k;
+  bool keep_all = false;
+#if defined(__HIP_DEVICE_COMPILE__)
+  // wave-uniform: no lane of the wave moves a column (the per-lane swaps below would all select their own operand)
+  if constexpr (FAST) keep_all = __all(big == k);
+#endif
 #pragma unroll
   for (int j = k + 1; j < 3; j++) {
-    if (big == j) {
+    if (!keep_all && big == j) {
 #pragma unroll
       for (int i = 0; i < R; i++) { const T t = A[k][i]; A[k][i] = A[j][i]; A[j][i] = t; }
       T t = nu[k]; nu[k] = nu[j]; nu[j] = t;
@@ -136,11 +207,10 @@ PCM_HD_FN inline void colpiv_qr_step(T (&A)[3][R], T (&nu)[3], T (&nd)[3], int (
 #pragma unroll
     for (int i = k + 1; i < R; i++) A[k][i] = 0;
   } else {
-    beta = Num<T>::sqrt_(c0 * c0 + tail_sq);
+    beta = qr_sqrt<T, FAST>(c0 * c0 + tail_sq, ok);
     if (c0 >= 0) beta = -beta;
     const T den = c0 - beta;
-#pragma unroll
-    for (int i = k + 1; i < R; i++) A[k][i] = Num<T>::div_(A[k][i], den);
+    qr_div_tail<T, FAST, R, k + 1>(A[k], den, ok);
     tau = Num<T>::div_(beta - c0, beta);
   }
   A[k][k] = beta;
@@ -163,12 +233,18 @@ PCM_HD_FN inline void colpiv_qr_step(T (&A)[3][R], T (&nu)[3], T (&nd)[3], int (
       T temp = Num<T>::div_(fabs(A[j][k]), nu[j]);
       temp = ((T)1 + temp) * ((T)1 - temp);
       temp = temp < 0 ? (T)0 : temp;
+#if defined(__HIP_DEVICE_COMPILE__)
+      // step 0: nd[j] == nu[j] (both the column's norm, swapped together), != 0, so nu / nd is 1 -- or NaN when nu is inf / NaN,
+      // which (nu - nu) + 1 gives as well, and a NaN r only ever meets the comparison below
+      const T r = (FAST && k == 0) ? (nu[j] - nu[j]) + (T)1 : Num<T>::div_(nu[j], nd[j]);
+#else
       const T r = Num<T>::div_(nu[j], nd[j]);
+#endif
       const T temp2 = temp * (r * r);
       if (temp2 <= downdate_thr) {
-        nd[j] = nu[j] = Num<T>::sqrt_(eig_tail_dot<T, R, k>(A[j], A[j]));
+        nd[j] = nu[j] = qr_sqrt<T, FAST>(eig_tail_dot<T, R, k>(A[j], A[j]), ok);
       } else {
-        nu[j] *= Num<T>::sqrt_(temp);
+        nu[j] *= qr_sqrt<T, FAST>(temp, ok);
       }
     }
   }
@@ -191,8 +267,10 @@ PCM_HD_FN inline void colpiv_qr_reflect_rhs(const T (&A)[3][R], const T (&hc)[3]
   }
 }
 
-template <typename T, int R>
-PCM_HD_FN inline void colpiv_qr_solve(T (&A)[3][R], T (&x)[3]) {
+template <typename T, int R, bool FAST = false>
+PCM_HD_FN inline void colpiv_qr_solve(T (&A)[3][R], T (&x)[3], bool* fast_ok = nullptr) {
+  bool ok_local = true;
+  bool& ok = fast_ok ? *fast_ok : ok_local;
   T nu[3], nd[3];
   int perm[3] = {0, 1, 2};
   T hc[3] = {0, 0, 0};
@@ -203,15 +281,15 @@ PCM_HD_FN inline void colpiv_qr_solve(T (&A)[3][R], T (&x)[3]) {
     T prod[R];
 #pragma unroll
     for (int i = 0; i < R; i++) prod[i] = A[j][i] * A[j][i];
-    nu[j] = nd[j] = Num<T>::sqrt_(eig_redux<T, R>(prod));
+    nu[j] = nd[j] = qr_sqrt<T, FAST>(eig_redux<T, R>(prod), ok);
     maxnorm = nu[j] > maxnorm ? nu[j] : maxnorm;
   }
   const T thr_helper = Num<T>::div_((maxnorm * Num<T>::eps()) * (maxnorm * Num<T>::eps()), (T)R);
   const T downdate_thr = Num<T>::sqrt_(Num<T>::eps());
   int nonzero = 3;
-  colpiv_qr_step<T, R, 0>(A, nu, nd, perm, hc, nonzero, thr_helper, downdate_thr);
-  colpiv_qr_step<T, R, 1>(A, nu, nd, perm, hc, nonzero, thr_helper, downdate_thr);
-  colpiv_qr_step<T, R, 2>(A, nu, nd, perm, hc, nonzero, thr_helper, downdate_thr);
+  colpiv_qr_step<T, R, 0, FAST>(A, nu, nd, perm, hc, nonzero, thr_helper, downdate_thr, ok);
+  colpiv_qr_step<T, R, 1, FAST>(A, nu, nd, perm, hc, nonzero, thr_helper, downdate_thr, ok);
+  colpiv_qr_step<T, R, 2, FAST>(A, nu, nd, perm, hc, nonzero, thr_helper, downdate_thr, ok);
 #pragma unroll
   for (int i = 0; i < R; i++) c[i] = (T)-1;
   colpiv_qr_reflect_rhs<T, R, 0>(A, hc, nonzero, c);
@@ -237,14 +315,59 @@ PCM_HD_FN inline void colpiv_qr_solve(T (&A)[3][R], T (&x)[3]) {
   }
 }
 
-// common::esti_plane (common_lib.h:186-243) on m (3..5) neighbours held in registers.
+// n = x / |x|, d = 1 / |x| of the solution x (common_lib.h:230-233)
+template <bool FAST>
+PCM_HD_FN inline float4 plane_of_solution(const float (&nv)[3], bool& ok) {
+  const float n2 = nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2];
+  float4 pl;
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (FAST) {
+    // (float)(1.0 / (double)n) rounds twice; with 53 >= 2 * 24 + 2 bits that equals the correctly rounded float 1 / n for a
+    // normal quotient (double rounding is innocuous for +, -, *, / and sqrt under that condition), so inside the window of
+    // fdiv_fast 1 / n is one more numerator over the shared reciprocal
+    const float n = qr_sqrt<float, true>(n2, ok);
+    float v[4] = {nv[0], nv[1], nv[2], 1.0f};
+    qr_div_tail<float, true, 4, 0>(v, n, ok);
+    pl.x = v[0]; pl.y = v[1]; pl.z = v[2]; pl.w = v[3];
+    return pl;
+  }
+#endif
+  const float n = pcm_sqrtf_rn(n2);
+  pl.x = pcm_divf_rn(nv[0], n);
+  pl.y = pcm_divf_rn(nv[1], n);
+  pl.z = pcm_divf_rn(nv[2], n);
+  pl.w = (float)(1.0 / (double)n);
+  return pl;
+}
+
+// common::esti_plane (common_lib.h:186-243) on m (3..5) neighbours held in registers.  FAST_FIT (device): the m == 5 fit runs the
+// window sequences and falls back per lane; it keeps about a dozen more values live, so only kernels with registers to spare
+// (k_linearize_lists) ask for it -- the tile and counted kernels already spill at their 96-VGPR bound.
+template <bool FAST_FIT = false>
 PCM_HD_FN inline bool esti_plane(const float (&px)[K], const float (&py)[K], const float (&pz)[K], int m, float threshold, float4* plane) {
   float nv[3];
+  float4 pl;
+  bool ok = true, fast_done = false;
   if (m == K) {
     float A[3][K];
 #pragma unroll
     for (int j = 0; j < K; j++) { A[0][j] = px[j]; A[1][j] = py[j]; A[2][j] = pz[j]; }
-    colpiv_qr_solve<float, K>(A, nv);
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (FAST_FIT) {
+      // the window sequences throughout; a lane that left a window anywhere repeats the fit with the full ones
+      colpiv_qr_solve<float, K, true>(A, nv, &ok);
+      pl = plane_of_solution<true>(nv, ok);
+      fast_done = ok;
+      if (!ok) {
+#pragma unroll
+        for (int j = 0; j < K; j++) { A[0][j] = px[j]; A[1][j] = py[j]; A[2][j] = pz[j]; }
+        colpiv_qr_solve<float, K>(A, nv);
+      }
+    } else
+#endif
+    {
+      colpiv_qr_solve<float, K>(A, nv);
+    }
   } else if (m == 4) {  // dynamic-size path: solved in double (common_lib.h:210-226)
     double A[3][4], xd[3];
 #pragma unroll
@@ -258,13 +381,8 @@ PCM_HD_FN inline bool esti_plane(const float (&px)[K], const float (&py)[K], con
     colpiv_qr_solve<double, 3>(A, xd);
     nv[0] = (float)xd[0]; nv[1] = (float)xd[1]; nv[2] = (float)xd[2];
   }
-  const float n = pcm_sqrtf_rn(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2]);
-  float4 pl;
-  pl.x = pcm_divf_rn(nv[0], n);
-  pl.y = pcm_divf_rn(nv[1], n);
-  pl.z = pcm_divf_rn(nv[2], n);
-  pl.w = (float)(1.0 / (double)n);
-  bool ok = true;
+  if (!fast_done) pl = plane_of_solution<false>(nv, ok);
+  ok = true;
 #pragma unroll
   for (int j = 0; j < K; j++) {
     if (j < m) {
