@@ -40,7 +40,9 @@ typedef enum pcm_status {
   PCM_ERR_UNSUPPORTED = -4,
   PCM_ERR_OUT_OF_RANGE = -5,   /* voxel coordinate outside +-2^20 cells */
   PCM_ERR_NOT_CONVERGED = -6,  /* "lm not converged!!"  impl/lsq_registration_impl.hpp:69-72 (result still written) */
-  PCM_ERR_INTERNAL = -7        /* a pair of a batch was not driven to the end of its loop (library bug); its pose is not a result */
+  PCM_ERR_INTERNAL = -7,       /* a pair of a batch was not driven to the end of its loop (library bug); its pose is not a result */
+  PCM_ERR_TOO_FEW_FEATURES = -8 /* LOAM: not more than edge_min_valid corner / surf_min_valid surf features; pose left as given
+                                 * (the "Not enough features!" branch of scan2MapOptimization, jueying_slam/src/mapOptmization.cpp:1584-1585) */
 } pcm_status;
 
 /* residual models */
@@ -52,6 +54,7 @@ typedef enum pcm_model {
   PCM_MODEL_NDT_D2D = 4, /* src/fast_gicp/cuda/ndt_compute_derivatives.cu:104-175 */
   PCM_MODEL_VGICP_CUDA = 6, /* FastVGICPCuda's float core: src/fast_gicp/cuda/{covariance_estimation,covariance_regularization,gaussian_voxelmap,
                              * find_voxel_correspondences,compute_derivatives}.cu (resolution 1.0, DIRECT1, PLANE: impl/fast_vgicp_cuda_impl.hpp:24-27) */
+  PCM_MODEL_LOAM = 7,    /* jueying_slam LOAM edge / plane scan-to-map optimisation (mapOptmization.cpp:1255-1586): pcm_loam_* entry points only */
   PCM_MODEL_NDT_OMP = 5  /* pclomp::NormalDistributionsTransform: pointcloud_match/ndt_omp/include/pclomp/ndt_omp_impl.hpp:69-880
                           * (Newton step + More-Thuente line search; max_iterations 35, translation_eps 0.1 = transformation_epsilon_,
                           *  voxel_resolution 1.0, num_neighbors 7 = DIRECT7 are that class's defaults) */
@@ -381,6 +384,60 @@ int pcm_get_source(pcm_ctx *ctx, float *out_xyz, size_t capacity_points, size_t 
  * `host_out` (n results) and/or `device_out` (device pointer to n packed
  * pcm_result records, e.g. the buffer handed to an RCCL all_gather) may be NULL. */
 int pcm_align_batch(pcm_ctx *const *ctxs, int n, const float *guesses, pcm_result *host_out, void *device_out);
+
+/*
+ * LOAM (LIO-SAM style) scan-to-map registration of jueying_slam: scan2MapOptimization
+ * (jueying_slam/src/mapOptmization.cpp:1560-1586; cornerOptimization :1255-1347, surfOptimization :1349-1419,
+ * combineOptimizationCoeffs :1421-1440, LMOptimization :1442-1558) and the fitness scores of its localisation variant
+ * (jueying_slam/src/localization.cpp:674-1031).  A context created with PCM_MODEL_LOAM holds two maps (corner, surf) and one
+ * scan of two feature clouds; the whole iteration loop runs on the device.  The pose is transformTobeMapped:
+ * (roll, pitch, yaw, x, y, z), floats.  transformUpdate (IMU blending and clamps) stays with the caller.  DESIGN.md section 9.
+ */
+typedef struct pcm_loam_params {
+  int32_t iter_num;              /* 30   utility.h:253 (iter_num) */
+  int32_t edge_min_valid;        /* 10   utility.h:267 edgeFeatureMinValidNum: run only if corner features > this ... */
+  int32_t surf_min_valid;        /* 100  utility.h:268 surfFeatureMinValidNum: ... and surf features > this */
+  int32_t reserved0;
+  double rot_conv_deg;           /* 0.01 deltaR threshold (mapOptmization.cpp:1551); the localisation nodes use 0.05 (localization.cpp:985) */
+  double trans_conv_cm;          /* 0.05 deltaT threshold */
+  double degeneracy_threshold;   /* 100  eignThre (mapOptmization.cpp:1524) */
+  float search_cell;             /* 1.0  cell size [m] of the maps' search grid, >= 1.0; speed only (results do not depend on it) */
+  int32_t reserved[7];
+} pcm_loam_params;
+
+typedef struct pcm_loam_result {
+  float x[6];                    /* transformTobeMapped after the loop */
+  int32_t iterations;            /* loop iterations run (iter_num when it did not converge; 0 when it did not run) */
+  int32_t converged;             /* LMOptimization returned true */
+  int32_t degenerate;            /* isDegenerate of iteration 0 */
+  int32_t status;                /* PCM_OK or PCM_ERR_TOO_FEW_FEATURES */
+  double eigenvalues[6];         /* of A^T A at iteration 0, descending (0 when iteration 0 had < 50 rows) */
+  int32_t num_corner;            /* selected corner rows of the last iteration */
+  int32_t num_surf;              /* selected surf rows of the last iteration */
+  double corner_fitness;         /* Corner_fitness_score / Surf_fitness_score of the last iteration: mean sqDis[0] over the features */
+  double surf_fitness;           /*   with sqDis[0] <= 1, the largest double when at most one (localization.cpp:1012-1021) */
+  int32_t maps_built;            /* 1: this call (re)built the search grids of the two maps */
+  int32_t reserved;
+} pcm_loam_result;
+
+void pcm_loam_default_params(pcm_loam_params *params);
+/* laserCloudCornerFromMapDS / laserCloudSurfFromMapDS (records of stride_bytes, x y z first).  An equal non-zero tag makes the call a
+ * no-op (the maps and their search grids are kept). */
+int pcm_loam_set_target(pcm_ctx *ctx, const void *corner, size_t n_corner, const void *surf, size_t n_surf, size_t stride_bytes, int memory, uint64_t tag);
+/* laserCloudCornerLastDS / laserCloudSurfLastDS: the scan's features in the body frame; same tag rule */
+int pcm_loam_set_source(pcm_ctx *ctx, const void *corner, size_t n_corner, const void *surf, size_t n_surf, size_t stride_bytes, int memory, uint64_t tag);
+/* scan2MapOptimization from x6_in; params NULL = defaults */
+int pcm_loam_align(pcm_ctx *ctx, const pcm_loam_params *params, const float x6_in[6], pcm_loam_result *result);
+/* n independent contexts on one device in lock-step launches; x6_in = n x 6 floats, results = n records.  Returns the first
+ * non-OK status of a context (each record carries its own). */
+int pcm_loam_align_batch(pcm_ctx *const *ctxs, int n, const pcm_loam_params *params, const float *x6_in, pcm_loam_result *results);
+/* parity hook: one correspondence pass at the fixed pose x6.  corner_out / surf_out: (coeff.x, coeff.y, coeff.z, coeff.intensity)
+ * per feature, NaN when the feature is not selected (4 floats each).  AtA (36, row-major), AtB (6): the normal equations as the
+ * step reads them.  counts: selected corner rows, selected surf rows, corner / surf features with sqDis[0] <= 1.  Any may be NULL. */
+int pcm_loam_coefficients(pcm_ctx *ctx, const float x6[6], float *corner_out, float *surf_out, double AtA[36], double AtB[6], int32_t counts[4]);
+/* parity hook: the 5 nearest map points (caller indices, ascending (d^2, index)) of every feature at x6 among those with d^2 <= 1,
+ * -1 where there are fewer; 5 int32 per feature.  Either may be NULL. */
+int pcm_loam_neighbours(pcm_ctx *ctx, const float x6[6], int32_t *corner_nn, int32_t *surf_nn);
 
 /* profiling flags: bit0 = bracket every residual launch with HIP events on the
  * launch stream (pcm_stats.linearize_ms); bit1 = collect the kNN candidate /

@@ -318,6 +318,68 @@ protected:
   double trans_probability_ = 0.0;
 };
 
+// jueying_slam's LOAM edge / plane scan-to-map optimisation with the call shape of mapOptmization.cpp:1560-1586:
+//     loam.setInputMaps(laserCloudCornerFromMapDS, laserCloudSurfFromMapDS);   // replaces the two kdtree setInputCloud calls
+//     loam.setInputFeatures(laserCloudCornerLastDS, laserCloudSurfLastDS);
+//     if (loam.scan2MapOptimization(transformTobeMapped)) transformUpdate();  // false: "Not enough features!" (pose untouched)
+// The mapping node refills its map clouds in place every frame, so the maps are uploaded at every call unless the caller passes a
+// non-zero tag that changes with the content (a localisation node's fixed global map: any constant).  setLocalizationThresholds()
+// selects the 0.05 deg rotation threshold of localization.cpp:985; the fitness scores are those of localization.cpp:1003-1022.
+template <typename PointT>
+class LoamScanToMap {
+public:
+  using Cloud = pcl::PointCloud<PointT>;
+  using CloudConstPtr = typename Cloud::ConstPtr;
+
+  explicit LoamScanToMap(int device = 0) {
+    pcm_config cfg;
+    pcm_default_config(&cfg);
+    cfg.model = PCM_MODEL_LOAM;
+    ctx_ = pcm_create(device, &cfg);
+    if (!ctx_) throw std::runtime_error("pcm_create failed");
+    pcm_loam_default_params(&params_);
+  }
+  ~LoamScanToMap() { pcm_destroy(ctx_); }
+  LoamScanToMap(const LoamScanToMap&) = delete;
+  LoamScanToMap& operator=(const LoamScanToMap&) = delete;
+
+  void setIterNum(int n) { params_.iter_num = n; }                                     // utility.h:253
+  void setFeatureMinValidNum(int edge, int surf) { params_.edge_min_valid = edge; params_.surf_min_valid = surf; }   // utility.h:267-268
+  void setLocalizationThresholds() { params_.rot_conv_deg = 0.05; }                    // localization.cpp:985
+  pcm_loam_params& params() { return params_; }
+
+  void setInputMaps(const CloudConstPtr& corner, const CloudConstPtr& surf, uint64_t tag = 0) {
+    check(pcm_loam_set_target(ctx_, corner->points.data(), corner->size(), surf->points.data(), surf->size(), sizeof(PointT), PCM_MEM_HOST, tag),
+          "pcm_loam_set_target");
+  }
+  void setInputFeatures(const CloudConstPtr& corner, const CloudConstPtr& surf) {
+    check(pcm_loam_set_source(ctx_, corner->points.data(), corner->size(), surf->points.data(), surf->size(), sizeof(PointT), PCM_MEM_HOST, 0),
+          "pcm_loam_set_source");
+  }
+
+  // the loop of scan2MapOptimization; transformTobeMapped is updated in place.  false: too few features (left as it was).
+  bool scan2MapOptimization(float transformTobeMapped[6]) {
+    const int rc = pcm_loam_align(ctx_, &params_, transformTobeMapped, &last_);
+    if (rc == PCM_ERR_TOO_FEW_FEATURES) return false;
+    check(rc, "pcm_loam_align");
+    for (int k = 0; k < 6; k++) transformTobeMapped[k] = last_.x[k];
+    return true;
+  }
+  bool isDegenerate() const { return last_.degenerate != 0; }
+  double cornerFitnessScore() const { return last_.corner_fitness; }   // Corner_fitness_score
+  double surfFitnessScore() const { return last_.surf_fitness; }       // Surf_fitness_score
+  int iterations() const { return last_.iterations; }
+  const pcm_loam_result& result() const { return last_; }
+
+private:
+  void check(int rc, const char* what) const {
+    if (rc != PCM_OK) throw std::runtime_error(std::string(what) + ": " + pcm_last_error(ctx_));
+  }
+  pcm_ctx* ctx_ = nullptr;
+  pcm_loam_params params_;
+  pcm_loam_result last_{};
+};
+
 }  // namespace pcm_amd
 
 // The call sites spell the pclomp enumerators unqualified inside namespace pclomp (jueying_slam/src/localization.cpp:169-186:

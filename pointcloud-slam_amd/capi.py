@@ -15,6 +15,8 @@ SYMBOLS = [
     "pcm_swap_source_and_target", "pcm_clear_source", "pcm_clear_target", "pcm_align",
     "pcm_linearize", "pcm_compute_error", "pcm_get_planes", "pcm_get_lio_members", "pcm_obs_model", "pcm_target_insert", "pcm_map_incremental", "pcm_get_target", "pcm_get_covariances", "pcm_set_covariances", "pcm_ndt_derivatives", "pcm_ndt_score", "pcm_fitness_score", "pcm_undistort", "pcm_voxel_downsample", "pcm_livox_filter", "pcm_gicp_bfgs_set_correspondences", "pcm_gicp_bfgs_fdf", "pcm_gicp_bfgs_update_correspondences", "pcm_gicp_bfgs_get_correspondences", "pcm_align_batch", "pcm_set_profiling", "pcm_debug_phase_cycles",
     "pcm_get_stats", "pcm_reset_stats", "pcm_lio_frame_begin", "pcm_lio_frame_end", "pcm_get_source",
+    "pcm_loam_default_params", "pcm_loam_set_target", "pcm_loam_set_source", "pcm_loam_align", "pcm_loam_align_batch",
+    "pcm_loam_coefficients", "pcm_loam_neighbours",
 ]
 
 PCM_ABI_VERSION = 3   # include/pcm_amd.h
@@ -28,8 +30,9 @@ PCM_FLAG_REFERENCE_KNN_ORDER = 32      # neighbours in the order of libstdc++'s 
 PCM_FLAG_LIO_REFERENCE_SEMANTICS = 4   # pcm_obs_model keeps LaserMapping's per-point members across calls and scans
 PCM_ERR_NOT_CONVERGED = -6
 PCM_ERR_INTERNAL = -7
+PCM_ERR_TOO_FEW_FEATURES = -8          # LOAM: not enough corner / surf features, pose left as given
 MEM_HOST, MEM_DEVICE = 0, 1
-MODEL = {"P2PLANE": 0, "GICP": 1, "VGICP": 2, "NDT_P2D": 3, "NDT_D2D": 4, "NDT_OMP": 5, "VGICP_CUDA": 6}
+MODEL = {"P2PLANE": 0, "GICP": 1, "VGICP": 2, "NDT_P2D": 3, "NDT_D2D": 4, "NDT_OMP": 5, "VGICP_CUDA": 6, "LOAM": 7}
 OPTIMIZER = {"GN": 0, "LM": 1}
 REGULARIZATION = {"NONE": 0, "MIN_EIG": 1, "NORMALIZED_MIN_EIG": 2, "PLANE": 3, "FROBENIUS": 4, "PCLOMP": 5}
 
@@ -79,6 +82,18 @@ class PcmStats(C.Structure):
                 ("tiles_lds_grid", C.c_uint64), ("tiles_lds_points", C.c_uint64), ("residual_ms", C.c_double),
                 ("timed_launches", C.c_uint64), ("timed_pair_slots", C.c_uint64), ("launched_pair_slots", C.c_uint64),
                 ("lru_batch_hazards", C.c_uint64)]
+
+
+class PcmLoamParams(C.Structure):
+    _fields_ = [("iter_num", C.c_int32), ("edge_min_valid", C.c_int32), ("surf_min_valid", C.c_int32), ("reserved0", C.c_int32),
+                ("rot_conv_deg", C.c_double), ("trans_conv_cm", C.c_double), ("degeneracy_threshold", C.c_double),
+                ("search_cell", C.c_float), ("reserved", C.c_int32 * 7)]
+
+
+class PcmLoamResult(C.Structure):
+    _fields_ = [("x", C.c_float * 6), ("iterations", C.c_int32), ("converged", C.c_int32), ("degenerate", C.c_int32),
+                ("status", C.c_int32), ("eigenvalues", C.c_double * 6), ("num_corner", C.c_int32), ("num_surf", C.c_int32),
+                ("corner_fitness", C.c_double), ("surf_fitness", C.c_double), ("maps_built", C.c_int32), ("reserved", C.c_int32)]
 
 
 def library_path() -> str:
@@ -160,5 +175,13 @@ def load_library():
     L.pcm_lio_frame_begin.argtypes = [vp, vp, sz, C.c_int, C.POINTER(PcmLioFrameParams), vp, C.c_int, C.POINTER(PcmLioState), C.POINTER(sz)]
     L.pcm_lio_frame_end.argtypes = [vp, C.POINTER(PcmLioState), C.c_float, i32, C.POINTER(sz)]
     L.pcm_get_source.argtypes = [vp, vp, sz, C.POINTER(sz)]
+    L.pcm_loam_default_params.argtypes = [C.POINTER(PcmLoamParams)]
+    L.pcm_loam_default_params.restype = None
+    for f in (L.pcm_loam_set_target, L.pcm_loam_set_source):
+        f.argtypes = [vp, vp, sz, vp, sz, sz, i32, u64]
+    L.pcm_loam_align.argtypes = [vp, C.POINTER(PcmLoamParams), vp, C.POINTER(PcmLoamResult)]
+    L.pcm_loam_align_batch.argtypes = [C.POINTER(vp), i32, C.POINTER(PcmLoamParams), vp, C.POINTER(PcmLoamResult)]
+    L.pcm_loam_coefficients.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.pcm_loam_neighbours.argtypes = [vp, vp, vp, vp]
     _LIB = L
     return L

@@ -171,6 +171,7 @@ size_t neighbor_slots(const pcm_config& g) {
 int ndt_kind(int model) { return model == PCM_MODEL_NDT_D2D ? 1 : (model == PCM_MODEL_VGICP_CUDA ? 2 : 0); }
 
 int validate_config(pcm_ctx* c, const pcm_config& g) {
+  if (g.model == PCM_MODEL_LOAM) { c->err = "PCM_MODEL_LOAM contexts run through the pcm_loam_* entry points"; return PCM_ERR_UNSUPPORTED; }
   if (g.model != PCM_MODEL_P2PLANE && !is_ndt(g.model) && !is_gicp(g.model) && g.model != PCM_MODEL_NDT_OMP) { c->err = "unknown registration model"; return PCM_ERR_UNSUPPORTED; }
   if (g.model == PCM_MODEL_NDT_OMP) {
     if (g.num_neighbors == 19) { c->err = "pclomp NDT neighbourhoods are KDTREE / DIRECT1 / DIRECT7 / DIRECT26 (num_neighbors 0, 1, 7, 27)"; return PCM_ERR_INVALID_ARGUMENT; }
@@ -1162,6 +1163,7 @@ void pcm_destroy(pcm_ctx* c) {
     if (c->counter) hipFree(c->counter);
     if (c->nn) hipFree(c->nn);
     free_ws(c);
+    loam_release(c);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
   }
   delete c;

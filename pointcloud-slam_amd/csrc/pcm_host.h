@@ -172,6 +172,8 @@ void launch_pclndt_pass(hipStream_t stream, const TargetMap& map, const PclLeaf*
                         double gauss_d3 = 0.0);   // pass 3: calculateScore (needs gauss_d3)
 void launch_init_states(hipStream_t stream, PairState* d_states, const float* d_guesses, int npairs, int max_iterations, int window, unsigned int* d_queue);
 void launch_pack_results(hipStream_t stream, const PairState* d_states, pcm_result* d_results, int npairs);
+// loam_api.hip: the maps, scan and device state of a PCM_MODEL_LOAM context (pcm_ctx::loam)
+void loam_release(pcm_ctx* c);
 
 }  // namespace pcm
 
@@ -237,5 +239,6 @@ struct pcm_ctx {
   int32_t* bfgs_idx = nullptr; // [2][bfgs_idx_cap] source / target index of every packed pair (device-side correspondence step)
   size_t bfgs_idx_cap = 0;
   double* bfgs_host = nullptr; // pinned, device-visible: the 14 sums land here without a copy command
+  void* loam = nullptr;   // PCM_MODEL_LOAM: maps, features and device state (loam_api.hip)
   int profiling = 0;  // bit0: HIP-event timing of residual launches, bit1: kNN counters
 };

@@ -454,3 +454,131 @@ def align_batch(regs, guesses, device_out=None):
     for r, x in zip(regs, res):
         r._last = x
     return res
+
+
+# ---- LOAM scan-to-map (jueying_slam mapOptmization.cpp:1560-1586) -------------------------------------------------------------
+
+@dataclasses.dataclass
+class LoamResult:
+    x: np.ndarray             # (6,) float32 transformTobeMapped: roll, pitch, yaw, x, y, z
+    iterations: int
+    converged: bool
+    degenerate: bool
+    status: int               # PCM_OK or PCM_ERR_TOO_FEW_FEATURES (pose left as given)
+    eigenvalues: np.ndarray   # (6,) of A^T A at iteration 0, descending
+    num_corner: int
+    num_surf: int
+    corner_fitness: float
+    surf_fitness: float
+    maps_built: bool
+
+
+def _loam_result(r: capi.PcmLoamResult) -> LoamResult:
+    return LoamResult(np.array(r.x[:], np.float32), r.iterations, bool(r.converged), bool(r.degenerate), r.status,
+                      np.array(r.eigenvalues[:]), r.num_corner, r.num_surf, r.corner_fitness, r.surf_fitness, bool(r.maps_built))
+
+
+def _loam_params(L, params: dict) -> capi.PcmLoamParams:
+    p = capi.PcmLoamParams()
+    L.pcm_loam_default_params(C.byref(p))
+    for k, v in params.items():
+        if k.startswith("reserved") or not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _feature_pair(corner, surf):
+    """Both clouds as (N,4) float32 host arrays (one stride for the two)."""
+    out = []
+    for a in (corner, surf):
+        a = np.asarray(a, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] < 3:
+            raise ValueError("expected (N,>=3) float32 arrays")
+        b = np.zeros((a.shape[0], 4), np.float32)
+        b[:, :3] = a[:, :3]
+        out.append(b)
+    return out
+
+
+class LoamRegistration:
+    """jueying_slam's LOAM edge / plane scan-to-map optimisation on one HIP device (a PCM_MODEL_LOAM ``pcm_ctx``).
+
+    ``set_input_target(corner_map, surf_map)`` = laserCloudCornerFromMapDS / laserCloudSurfFromMapDS,
+    ``set_input_source(corner, surf)`` = laserCloudCornerLastDS / laserCloudSurfLastDS (body frame),
+    ``scan2map(x6)`` = scan2MapOptimization from transformTobeMapped = x6 (roll, pitch, yaw, x, y, z)."""
+
+    def __init__(self, device: int = 0, **params):
+        self._L = capi.load_library()
+        cfg = capi.PcmConfig()
+        self._L.pcm_default_config(C.byref(cfg))
+        cfg.model = capi.MODEL["LOAM"]
+        self._h = self._L.pcm_create(device, C.byref(cfg))
+        if not self._h:
+            raise capi.PcmError(-3, "pcm_create failed")
+        self.params = dict(params)
+        _loam_params(self._L, self.params)   # unknown names fail here
+        self.n_corner = self.n_surf = 0
+
+    def _check(self, rc, allow=(capi.PCM_OK,)):
+        if rc not in allow:
+            raise capi.PcmError(rc, (self._L.pcm_last_error(self._h) or b"").decode())
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._L.pcm_destroy(h)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def set_input_target(self, corner, surf, tag: int = 0):
+        c, s = _feature_pair(corner, surf)
+        self._check(self._L.pcm_loam_set_target(self._h, c.ctypes.data, c.shape[0], s.ctypes.data, s.shape[0], 16, capi.MEM_HOST, tag))
+
+    def set_input_source(self, corner, surf, tag: int = 0):
+        c, s = _feature_pair(corner, surf)
+        self._check(self._L.pcm_loam_set_source(self._h, c.ctypes.data, c.shape[0], s.ctypes.data, s.shape[0], 16, capi.MEM_HOST, tag))
+        self.n_corner, self.n_surf = c.shape[0], s.shape[0]
+
+    def scan2map(self, x6, **params) -> LoamResult:
+        p = _loam_params(self._L, {**self.params, **params})
+        x = np.ascontiguousarray(x6, dtype=np.float32).reshape(6)
+        r = capi.PcmLoamResult()
+        self._check(self._L.pcm_loam_align(self._h, C.byref(p), x.ctypes.data, C.byref(r)), (capi.PCM_OK, capi.PCM_ERR_TOO_FEW_FEATURES))
+        return _loam_result(r)
+
+    def coefficients(self, x6):
+        """Parity hook at a fixed pose: (corner (Nc,4), surf (Ns,4)) coefficients (coeff.xyz, intensity; NaN = not selected),
+        A^T A (6,6), A^T b (6,), counts (selected corner, selected surf, corner / surf features with sqDis[0] <= 1)."""
+        x = np.ascontiguousarray(x6, dtype=np.float32).reshape(6)
+        co = np.zeros((self.n_corner, 4), np.float32)
+        su = np.zeros((self.n_surf, 4), np.float32)
+        AtA = np.zeros((6, 6))
+        AtB = np.zeros(6)
+        cnt = np.zeros(4, np.int32)
+        self._check(self._L.pcm_loam_coefficients(self._h, x.ctypes.data, co.ctypes.data, su.ctypes.data, AtA.ctypes.data, AtB.ctypes.data, cnt.ctypes.data))
+        return co, su, AtA, AtB, cnt
+
+    def neighbours(self, x6):
+        """Parity hook: the 5 nearest map indices with d^2 <= 1 (ascending (d^2, index), -1 pads) of every corner / surf feature."""
+        x = np.ascontiguousarray(x6, dtype=np.float32).reshape(6)
+        cn = np.zeros((self.n_corner, 5), np.int32)
+        sn = np.zeros((self.n_surf, 5), np.int32)
+        self._check(self._L.pcm_loam_neighbours(self._h, x.ctypes.data, cn.ctypes.data, sn.ctypes.data))
+        return cn, sn
+
+
+def loam_align_batch(regs, x6s, **params):
+    """scan2MapOptimization of independent LoamRegistration objects in lock-step launches (pcm_loam_align_batch)."""
+    L = capi.load_library()
+    n = len(regs)
+    p = _loam_params(L, {**regs[0].params, **params})
+    x = np.ascontiguousarray(x6s, dtype=np.float32).reshape(n, 6)
+    arr = (C.c_void_p * n)(*[r.handle for r in regs])
+    out = (capi.PcmLoamResult * n)()
+    rc = L.pcm_loam_align_batch(arr, n, C.byref(p), x.ctypes.data, out)
+    if rc not in (capi.PCM_OK, capi.PCM_ERR_TOO_FEW_FEATURES):
+        raise capi.PcmError(rc, (L.pcm_last_error(regs[0].handle) or b"").decode())
+    return [_loam_result(out[i]) for i in range(n)]
