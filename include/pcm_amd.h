@@ -439,6 +439,69 @@ int pcm_loam_coefficients(pcm_ctx *ctx, const float x6[6], float *corner_out, fl
  * -1 where there are fewer; 5 int32 per feature.  Either may be NULL. */
 int pcm_loam_neighbours(pcm_ctx *ctx, const float x6[6], int32_t *corner_nn, int32_t *surf_nn);
 
+/*
+ * LOAM front end of jueying_slam: imageProjection (projectPointCloud / cloudExtraction, imageProjection.cpp:736-823),
+ * featureExtraction (calculateSmoothness / markOccludedPoints / extractFeatures with one pcl::VoxelGrid per ring,
+ * featureExtraction.cpp:84-247) and downsampleCurrentScan's two mapping VoxelGrids (mapOptmization.cpp:1232-1247), on the device.
+ * Input: ring-tagged records (PointXYZIRT, imageProjection.cpp:7-19: x y z floats at 0, uint8 intensity, uint16 ring; 48 / 16 / 32
+ * by default); a point with a non-finite coordinate is skipped; the timestamp is never read (the reference's deskew is the
+ * identity as written).  The context keeps the nodes' cross-frame arrays (zero at creation), so a stream of
+ * frames through one context reproduces the nodes frame for frame.  Needs a PCM_MODEL_LOAM context.
+ */
+#define PCM_LOAM_FEATURES_FORCE_SERIAL_SORT 1u   /* flags: every sector through the serial std::sort restatement (tests) */
+
+typedef struct pcm_loam_feature_params {
+  int32_t n_scan;                /* 16    utility.h:241 N_SCAN (<= 256) */
+  int32_t horizon_scan;          /* 1800  :242 Horizon_SCAN (<= 4096) */
+  int32_t downsample_rate;       /* 1     :244 downsampleRate (rows with ring % rate != 0 are skipped; the row is the ring) */
+  int32_t area_num;              /* 6     :252 sectors per ring, >= 1 (every value within these caps runs, area_num 1 at
+                                  *       horizon_scan 4096 included: one sector sorts in LDS up to 4096 entries) */
+  float min_range;               /* 1.0   :223 */
+  float max_range;               /* 150.0 :224 */
+  float edge_threshold;          /* 0.1   :265 (the configs use 1.0) */
+  float surf_threshold;          /* 0.1   :266 */
+  float odometry_surf_leaf;      /* 0.2   :270 per-ring VoxelGrid of the surf scan, > 0 */
+  float mapping_corner_leaf;     /* 0.2   :271 downsampleCurrentScan; 0 = no down-sampling */
+  float mapping_surf_leaf;       /* 0.2   :272 same; the localisation node passes 1.5 x (localization.cpp:160) */
+  uint32_t flags;                /* PCM_LOAM_FEATURES_* */
+  int32_t reserved[8];
+} pcm_loam_feature_params;
+
+typedef struct pcm_loam_features_result {
+  int32_t num_extracted;         /* extractedCloud */
+  int32_t num_corner_scan;       /* cornerCloud (before the mapping VoxelGrid) */
+  int32_t num_surf_scan;         /* surfaceCloud (rings after their own VoxelGrid, before the mapping one) */
+  int32_t num_corner;            /* laserCloudCornerLastDS */
+  int32_t num_surf;              /* laserCloudSurfLastDS */
+  int32_t sectors;               /* sectors sorted */
+  int32_t sectors_serial;        /* of which through the serial std::sort restatement: ties that could change the selection,
+                                  * a tie group of more than 256 entries, or a tied minimum in the sector that holds slot 4 */
+  int32_t status;                /* PCM_OK, PCM_ERR_OUT_OF_RANGE (VoxelGrid index overflow) */
+  int32_t reserved[8];
+} pcm_loam_features_result;
+
+void pcm_loam_default_feature_params(pcm_loam_feature_params *params);
+/* one frame to host PointXYZI records (x, y, z, intensity): corner = laserCloudCornerLastDS, surf = laserCloudSurfLastDS.  The
+ * context's LOAM source is not touched.  params NULL = defaults.  Capacities in points; when too small the counts are in *res,
+ * the frame has advanced the cross-frame state and PCM_ERR_INVALID_ARGUMENT is returned. */
+int pcm_loam_extract_features(pcm_ctx *ctx, const void *points, size_t n, size_t stride_bytes, size_t intensity_offset_bytes, size_t ring_offset_bytes,
+                              int memory, const pcm_loam_feature_params *params, float *corner, size_t cap_corner, float *surf, size_t cap_surf,
+                              pcm_loam_features_result *res);
+/* the same frame's features become the context's LOAM source without leaving the device (pcm_loam_set_source's state; then
+ * pcm_loam_align as before) */
+int pcm_loam_frame_begin(pcm_ctx *ctx, const void *points, size_t n, size_t stride_bytes, size_t intensity_offset_bytes, size_t ring_offset_bytes,
+                         int memory, const pcm_loam_feature_params *params, pcm_loam_features_result *res);
+/* n frames of n distinct contexts on one device in one set of launches; each context keeps its own cross-frame state */
+int pcm_loam_frame_begin_batch(pcm_ctx *const *ctxs, int n, const void *const *points, const size_t *n_points, size_t stride_bytes,
+                               size_t intensity_offset_bytes, size_t ring_offset_bytes, int memory, const pcm_loam_feature_params *params,
+                               pcm_loam_features_result *results);
+/* parity hook: the last frame's intermediate arrays.  counts: extracted points n, cornerCloud, surfaceCloud, n_scan.
+ * start_ring / end_ring: n_scan int32; col_ind, range, curvature, neighbor_picked (after markOccludedPoints), label (final):
+ * n entries of the context's arrays; cloud: n x 4 floats; corner_scan / surf_scan: cornerCloud in pick order / surfaceCloud,
+ * 4 floats per point.  Any pointer may be NULL. */
+int pcm_loam_feature_info(pcm_ctx *ctx, int32_t counts[4], int32_t *start_ring, int32_t *end_ring, int32_t *col_ind, float *range, float *cloud,
+                          float *curvature, int32_t *neighbor_picked, int32_t *label, float *corner_scan, float *surf_scan);
+
 /* profiling flags: bit0 = bracket every residual launch with HIP events on the
  * launch stream (pcm_stats.linearize_ms); bit1 = collect the kNN candidate /
  * probe counters (slower kernel variant; use in an untimed pass); bit2 = in-kernel

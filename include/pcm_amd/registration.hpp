@@ -24,6 +24,7 @@
 #include <Eigen/Geometry>
 #include <cfloat>
 #include <iostream>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -356,6 +357,18 @@ public:
     check(pcm_loam_set_source(ctx_, corner->points.data(), corner->size(), surf->points.data(), surf->size(), sizeof(PointT), PCM_MEM_HOST, 0),
           "pcm_loam_set_source");
   }
+  // imageProjection + featureExtraction + downsampleCurrentScan of one ring-tagged scan (PointXYZIRT-like: x y z, intensity, ring
+  // members) into the features on the device (pcm_loam_frame_begin).  The context keeps the nodes'
+  // cross-frame state.  fp: the feature parameters (default: utility.h's), e.g. LoamFeatureExtraction::params().
+  template <typename PointIn>
+  void setInputScan(const std::shared_ptr<const pcl::PointCloud<PointIn>>& scan, const pcm_loam_feature_params* fp = nullptr) {
+    const PointIn probe{};
+    const char* base = reinterpret_cast<const char*>(&probe);
+    const size_t ioff = (size_t)(reinterpret_cast<const char*>(&probe.intensity) - base), roff = (size_t)(reinterpret_cast<const char*>(&probe.ring) - base);
+    check(pcm_loam_frame_begin(ctx_, scan->points.data(), scan->size(), sizeof(PointIn), ioff, roff, PCM_MEM_HOST, fp, &features_),
+          "pcm_loam_frame_begin");
+  }
+  const pcm_loam_features_result& featuresResult() const { return features_; }
 
   // the loop of scan2MapOptimization; transformTobeMapped is updated in place.  false: too few features (left as it was).
   bool scan2MapOptimization(float transformTobeMapped[6]) {
@@ -378,6 +391,72 @@ private:
   pcm_ctx* ctx_ = nullptr;
   pcm_loam_params params_;
   pcm_loam_result last_{};
+  pcm_loam_features_result features_{};
+};
+
+// jueying_slam's LOAM front end (imageProjection.cpp:736-823, featureExtraction.cpp:84-247, mapOptmization.cpp:1232-1247) on the
+// device, for callers that want the features on the host.  PointIn: the driver's ring-tagged point (members x y z, intensity as
+// uint8, ring as uint16, e.g. imageProjection.cpp's PointXYZIRT); PointOut: PointType (x y z intensity).  One object per node: it
+// holds the nodes' cross-frame arrays.  The setters are named after ParamServer's members (utility.h:223-272).
+template <typename PointIn, typename PointOut = pcl::PointXYZI>
+class LoamFeatureExtraction {
+public:
+  using CloudIn = pcl::PointCloud<PointIn>;
+  using CloudOut = pcl::PointCloud<PointOut>;
+
+  explicit LoamFeatureExtraction(int device = 0) {
+    pcm_config cfg;
+    pcm_default_config(&cfg);
+    cfg.model = PCM_MODEL_LOAM;
+    ctx_ = pcm_create(device, &cfg);
+    if (!ctx_) throw std::runtime_error("pcm_create failed");
+    pcm_loam_default_feature_params(&params_);
+  }
+  ~LoamFeatureExtraction() { pcm_destroy(ctx_); }
+  LoamFeatureExtraction(const LoamFeatureExtraction&) = delete;
+  LoamFeatureExtraction& operator=(const LoamFeatureExtraction&) = delete;
+
+  void setNScan(int v) { params_.n_scan = v; }                         // N_SCAN
+  void setHorizonScan(int v) { params_.horizon_scan = v; }             // Horizon_SCAN
+  void setDownsampleRate(int v) { params_.downsample_rate = v; }       // downsampleRate
+  void setAreaNum(int v) { params_.area_num = v; }                     // area_num
+  void setMinRange(float v) { params_.min_range = v; }                 // min_range
+  void setMaxRange(float v) { params_.max_range = v; }                 // max_range
+  void setEdgeThreshold(float v) { params_.edge_threshold = v; }       // edgeThreshold
+  void setSurfThreshold(float v) { params_.surf_threshold = v; }       // surfThreshold
+  void setOdometrySurfLeafSize(float v) { params_.odometry_surf_leaf = v; }     // odometrySurfLeafSize
+  void setMappingCornerLeafSize(float v) { params_.mapping_corner_leaf = v; }   // mappingCornerLeafSize (0: no down-sampling)
+  void setMappingSurfLeafSize(float v) { params_.mapping_surf_leaf = v; }       // mappingSurfLeafSize (localisation: x 1.5)
+  const pcm_loam_feature_params& params() const { return params_; }
+  const pcm_loam_features_result& result() const { return last_; }
+
+  // laserCloudCornerLastDS / laserCloudSurfLastDS of one scan (pcm_loam_extract_features)
+  void extract(const std::shared_ptr<const CloudIn>& scan, CloudOut& cornerOut, CloudOut& surfOut) {
+    const PointIn probe{};
+    const char* base = reinterpret_cast<const char*>(&probe);
+    const size_t ioff = (size_t)(reinterpret_cast<const char*>(&probe.intensity) - base), roff = (size_t)(reinterpret_cast<const char*>(&probe.ring) - base);
+    const size_t cap = scan->size() ? scan->size() : 1;   // both outputs hold at most one feature per input point
+    corner_.resize(4 * cap);
+    surf_.resize(4 * cap);
+    const int rc = pcm_loam_extract_features(ctx_, scan->points.data(), scan->size(), sizeof(PointIn), ioff, roff, PCM_MEM_HOST, &params_,
+                                             corner_.data(), cap, surf_.data(), cap, &last_);
+    if (rc != PCM_OK) throw std::runtime_error(std::string("pcm_loam_extract_features: ") + pcm_last_error(ctx_));
+    fill(corner_, (size_t)last_.num_corner, cornerOut);
+    fill(surf_, (size_t)last_.num_surf, surfOut);
+  }
+
+private:
+  static void fill(const std::vector<float>& v, size_t n, CloudOut& out) {
+    out.points.resize(n);
+    for (size_t i = 0; i < n; i++) {
+      PointOut& q = out.points[i];
+      q.x = v[4 * i]; q.y = v[4 * i + 1]; q.z = v[4 * i + 2]; q.intensity = v[4 * i + 3];
+    }
+  }
+  pcm_ctx* ctx_ = nullptr;
+  pcm_loam_feature_params params_;
+  pcm_loam_features_result last_{};
+  std::vector<float> corner_, surf_;
 };
 
 }  // namespace pcm_amd

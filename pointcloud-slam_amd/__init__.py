@@ -12,3 +12,4 @@ from . import sharding  # noqa: F401
 from .registration import (GicpRegistration, NdtRegistration, P2PlaneRegistration, PclNdtRegistration, Registration, VgicpCudaRegistration, VgicpRegistration,  # noqa: F401
                            RegistrationResult, align_batch)
 from .registration import LoamRegistration, LoamResult, loam_align_batch  # noqa: F401
+from .registration import loam_extract_features, loam_frame_begin_batch, pack_xyzirt  # noqa: F401

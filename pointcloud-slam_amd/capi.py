@@ -17,6 +17,8 @@ SYMBOLS = [
     "pcm_get_stats", "pcm_reset_stats", "pcm_lio_frame_begin", "pcm_lio_frame_end", "pcm_get_source",
     "pcm_loam_default_params", "pcm_loam_set_target", "pcm_loam_set_source", "pcm_loam_align", "pcm_loam_align_batch",
     "pcm_loam_coefficients", "pcm_loam_neighbours",
+    "pcm_loam_default_feature_params", "pcm_loam_extract_features", "pcm_loam_frame_begin", "pcm_loam_frame_begin_batch",
+    "pcm_loam_feature_info",
 ]
 
 PCM_ABI_VERSION = 3   # include/pcm_amd.h
@@ -94,6 +96,22 @@ class PcmLoamResult(C.Structure):
     _fields_ = [("x", C.c_float * 6), ("iterations", C.c_int32), ("converged", C.c_int32), ("degenerate", C.c_int32),
                 ("status", C.c_int32), ("eigenvalues", C.c_double * 6), ("num_corner", C.c_int32), ("num_surf", C.c_int32),
                 ("corner_fitness", C.c_double), ("surf_fitness", C.c_double), ("maps_built", C.c_int32), ("reserved", C.c_int32)]
+
+
+PCM_LOAM_FEATURES_FORCE_SERIAL_SORT = 1
+
+
+class PcmLoamFeatureParams(C.Structure):
+    _fields_ = [("n_scan", C.c_int32), ("horizon_scan", C.c_int32), ("downsample_rate", C.c_int32), ("area_num", C.c_int32),
+                ("min_range", C.c_float), ("max_range", C.c_float), ("edge_threshold", C.c_float), ("surf_threshold", C.c_float),
+                ("odometry_surf_leaf", C.c_float), ("mapping_corner_leaf", C.c_float), ("mapping_surf_leaf", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_int32 * 8)]
+
+
+class PcmLoamFeaturesResult(C.Structure):
+    _fields_ = [("num_extracted", C.c_int32), ("num_corner_scan", C.c_int32), ("num_surf_scan", C.c_int32), ("num_corner", C.c_int32),
+                ("num_surf", C.c_int32), ("sectors", C.c_int32), ("sectors_serial", C.c_int32), ("status", C.c_int32),
+                ("reserved", C.c_int32 * 8)]
 
 
 def library_path() -> str:
@@ -183,5 +201,12 @@ def load_library():
     L.pcm_loam_align_batch.argtypes = [C.POINTER(vp), i32, C.POINTER(PcmLoamParams), vp, C.POINTER(PcmLoamResult)]
     L.pcm_loam_coefficients.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.pcm_loam_neighbours.argtypes = [vp, vp, vp, vp]
+    L.pcm_loam_default_feature_params.argtypes = [C.POINTER(PcmLoamFeatureParams)]
+    L.pcm_loam_default_feature_params.restype = None
+    L.pcm_loam_extract_features.argtypes = [vp, vp, sz, sz, sz, sz, i32, C.POINTER(PcmLoamFeatureParams), vp, sz, vp, sz, C.POINTER(PcmLoamFeaturesResult)]
+    L.pcm_loam_frame_begin.argtypes = [vp, vp, sz, sz, sz, sz, i32, C.POINTER(PcmLoamFeatureParams), C.POINTER(PcmLoamFeaturesResult)]
+    L.pcm_loam_frame_begin_batch.argtypes = [C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(sz), sz, sz, sz, i32, C.POINTER(PcmLoamFeatureParams),
+                                             C.POINTER(PcmLoamFeaturesResult)]
+    L.pcm_loam_feature_info.argtypes = [vp] * 12
     _LIB = L
     return L

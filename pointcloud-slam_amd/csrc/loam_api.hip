@@ -343,6 +343,7 @@ int probe(pcm_ctx* c, const float* x6, float* corner_out, float* surf_out, doubl
 
 namespace pcm {
 void loam_release(pcm_ctx* c) {
+  loam_features_release(c);
   LoamCtx* L = static_cast<LoamCtx*>(c->loam);
   if (!L) return;
   for (int m = 0; m < 2; m++) { L->map_cloud[m].release(); L->map[m].release(); }
@@ -355,6 +356,25 @@ void loam_release(pcm_ctx* c) {
   delete L;
   c->loam = nullptr;
 }
+namespace loam {
+int loam_source_reserve(pcm_ctx* c, size_t n, float4** feats) {
+  int rc = check_ctx(c);
+  if (rc != PCM_OK) return rc;
+  LoamCtx* L = loam_of(c);
+  L->have_src = false;
+  if ((rc = grow_f4(c, &L->feats, &L->feats_cap, n)) != PCM_OK) return rc;
+  *feats = L->feats;
+  return PCM_OK;
+}
+
+void loam_source_commit(pcm_ctx* c, uint32_t n_c, uint32_t n_s) {
+  LoamCtx* L = loam_of(c);
+  L->n_c = n_c;
+  L->n_s = n_s;
+  L->src_tag = 0;
+  L->have_src = true;
+}
+}  // namespace loam
 }  // namespace pcm
 
 extern "C" {

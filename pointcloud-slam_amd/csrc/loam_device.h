@@ -4,6 +4,8 @@
 #include "loam_step.h"
 #include "pcm_device.h"
 
+struct pcm_ctx;
+
 namespace pcm {
 namespace loam {
 
@@ -28,6 +30,11 @@ void launch_tag_input_index(hipStream_t stream, float4* pts, const uint32_t* ord
 void launch_init(hipStream_t stream, const LoamDesc* d_descs, int n);
 // one iteration of every context still running: the correspondence pass, then the step kernel
 void launch_round(hipStream_t stream, const LoamDesc* d_descs, int n, uint32_t max_blocks, const StepParams& p);
+
+// loam_api.hip: the front end (loam_features.hip) writes the context's source features in place: room for n features, then
+// the counts once they are on the device (the same state pcm_loam_set_source leaves)
+int loam_source_reserve(pcm_ctx* c, size_t n, float4** feats);
+void loam_source_commit(pcm_ctx* c, uint32_t n_c, uint32_t n_s);
 
 }  // namespace loam
 }  // namespace pcm

@@ -1,0 +1,1133 @@
+// loam_features.hip -- the LOAM front end on the device: jueying_slam's imageProjection (projectPointCloud, cloudExtraction),
+// featureExtraction (calculateSmoothness, markOccludedPoints, extractFeatures with its per-ring VoxelGrid) and the two mapping
+// VoxelGrids of downsampleCurrentScan, from one ring-tagged scan to the LOAM source of a PCM_MODEL_LOAM context
+// (include/pcm_amd.h, pcm_loam_extract_features / pcm_loam_frame_begin[_batch]).
+//
+// Reference: jueying_slam/src/imageProjection.cpp:736-823, featureExtraction.cpp:84-247,
+// mapOptmization.cpp:1232-1247.  Deskew (imageProjection.cpp:704-733) is the identity as written (relative point time compared
+// against absolute IMU / odometry stamps, :535/:548/:624/:632/:777): no IMU input, the timestamp field is never read.
+//
+// Launches of one batch (grid.y = frame), all on the stream of the first context, one read-back at the end:
+//   k_lf_clear, k_lf_project (atomicMin cell owner = first point wins), k_lf_rowcount, k_lf_rings (ring prefix, start/end),
+//   k_lf_extract (pointColInd, pointRange, extracted cloud), k_lf_smooth, k_lf_occlude, k_lf_snapshot (marks for the hook),
+//   k_lf_select<first ring> then k_lf_select<other rings> (sort, invariance check / serial std::sort, greedy passes),
+//   k_lf_corner_compact, segmented VoxelGrid stage 1 (per ring, odometry leaf), stage 2 (corner / surf, mapping leaves), k_lf_finish.
+#include "intro_sort.h"
+#include "loam_device.h"
+#include "pcm_host.h"
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <vector>
+
+using namespace pcm;
+
+namespace {
+
+constexpr int kMaxPicks = 20;   // largestPickedNum <= 20 (featureExtraction.cpp:177)
+
+#define LFCK(ctx, x)                                                                 \
+  do {                                                                               \
+    hipError_t e_ = (x);                                                             \
+    if (e_ != hipSuccess) {                                                          \
+      (ctx)->err = std::string(#x) + ": " + hipGetErrorString(e_);                   \
+      return PCM_ERR_HIP;                                                            \
+    }                                                                                \
+  } while (0)
+
+// per-frame counters, read back once per batch
+struct LfInfo {
+  uint32_t count;          // extracted points
+  int32_t first_ring;      // first ring with points (-1: none)
+  uint32_t n_corner_scan;  // cornerCloud
+  uint32_t n_surf_scan;    // surfaceCloud (rings concatenated after the odometry VoxelGrid)
+  uint32_t n_corner;       // after the mapping VoxelGrids
+  uint32_t n_surf;
+  uint32_t sectors, sectors_serial;
+  uint32_t overflow;       // a VoxelGrid index overflowed
+  uint32_t bad_sector;     // a sector was larger than the sort buffer (library bug)
+  uint32_t first1;         // first stage-1 cell of the frame
+  uint32_t first2;         // first stage-2 cell of the frame
+};
+
+struct LfFrame {
+  const char* pts;         // input records (device)
+  uint32_t n, stride, ioff, roff;
+  uint32_t cap1;           // min(n, n_scan * horizon_scan): extracted-point bound
+  uint32_t base1, base2;   // offsets of the frame's elements in the stage-1 / stage-2 arrays
+  // context state (persists between frames)
+  int32_t* col_ind; float* range; float4* cloud; float* curv; int32_t* picked; int32_t* label; DistId* smooth;
+  // last-frame outputs of the context (parity hook)
+  int32_t* start; int32_t* end; int32_t* picked_occ; float4* corner_scan; float4* surf_scan; float4* out;
+  float4* src;             // pcm_loam_frame_begin: the context's LOAM source (w = index), else nullptr
+  // batch scratch
+  uint32_t* owner; uint32_t* rowcnt; uint32_t* roff_arr; int32_t* member; int32_t* cpick; int32_t* ccnt;
+  LfInfo* info;
+};
+
+struct LfParams {
+  int n_scan, H, rate, A;
+  float min_range, max_range, edge, surf, ang_res_x;
+  float leaf_odo, leaf_corner, leaf_surf;
+  int force_serial;
+  int ppr;                 // corner picks per ring = A * 20
+  int P;                   // sort buffer entries (power of two >= the largest sector + 1)
+};
+
+__device__ inline uint32_t cap_of(const LfParams& p) { return (uint32_t)p.n_scan * (uint32_t)p.H; }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// projection (imageProjection.cpp:736-797)
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ void k_lf_clear(const LfFrame* __restrict__ fr, LfParams p) {
+  const LfFrame& F = fr[blockIdx.y];
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < cap_of(p)) F.owner[i] = 0xffffffffu;
+  if (i < (uint32_t)p.n_scan) { F.rowcnt[i] = 0u; F.ccnt[i] = 0; }
+  if (i == 0) {
+    LfInfo z;
+    memset(&z, 0, sizeof(z));
+    z.first_ring = -1;
+    *F.info = z;
+  }
+}
+
+struct Proj { int row, col; float range; };
+
+// false: the point is skipped.  Keeps the C++ types and evaluation order of :753-776 (atan2f pinned to float(atan2(double, double)))
+__device__ inline bool project_point(const LfFrame& F, const LfParams& p, uint32_t i, Proj* o, float4* pt) {
+  const char* r = F.pts + (size_t)i * F.stride;
+  const float x = *reinterpret_cast<const float*>(r), y = *reinterpret_cast<const float*>(r + 4), z = *reinterpret_cast<const float*>(r + 8);
+  if (!(isfinite(x) && isfinite(y) && isfinite(z))) return false;
+  const int row = (int)*reinterpret_cast<const uint16_t*>(r + F.roff);
+  if (row < 0 || row >= p.n_scan) return false;
+  if (row % p.rate != 0) return false;
+  const float a = (float)atan2((double)x, (double)y);
+  const float horizonAngle = (float)((double)(a * 180.0f) / M_PI);
+  int col = (int)(-round(((double)horizonAngle - 90.0) / (double)p.ang_res_x) + (double)(p.H / 2));
+  if (col >= p.H) col -= p.H;
+  if (col < 0 || col >= p.H) return false;
+  const float range = sqrtf((x * x + y * y) + z * z);
+  if (range < p.min_range || range > p.max_range) return false;
+  o->row = row; o->col = col; o->range = range;
+  if (pt) *pt = make_float4(x, y, z, (float)*reinterpret_cast<const uint8_t*>(r + F.ioff));
+  return true;
+}
+
+__global__ void k_lf_project(const LfFrame* __restrict__ fr, LfParams p) {
+  const LfFrame& F = fr[blockIdx.y];
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= F.n) return;
+  Proj q;
+  if (!project_point(F, p, i, &q, nullptr)) return;
+  atomicMin(&F.owner[(uint32_t)q.row * (uint32_t)p.H + (uint32_t)q.col], i);   // rangeMat != FLT_MAX -> skip (:774): first point wins
+}
+
+// one block of 256 per (row, frame): occupied cells of the row
+__global__ void __launch_bounds__(256) k_lf_rowcount(const LfFrame* __restrict__ fr, LfParams p) {
+  const LfFrame& F = fr[blockIdx.y];
+  const uint32_t row = blockIdx.x;
+  __shared__ uint32_t s_cnt;
+  if (threadIdx.x == 0) s_cnt = 0;
+  __syncthreads();
+  uint32_t c = 0;
+  for (int j = threadIdx.x; j < p.H; j += 256) c += F.owner[row * (uint32_t)p.H + j] != 0xffffffffu ? 1u : 0u;
+  for (int off = 32; off >= 1; off >>= 1) c += (uint32_t)__shfl_xor((int)c, off, 64);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_cnt, c);
+  __syncthreads();
+  if (threadIdx.x == 0) F.rowcnt[row] = s_cnt;
+}
+
+// one block of 256 per frame: ring prefix, startRingIndex / endRingIndex (cloudExtraction :803-821)
+__global__ void __launch_bounds__(256) k_lf_rings(const LfFrame* __restrict__ fr, LfParams p) {
+  const LfFrame& F = fr[blockIdx.x];
+  __shared__ uint32_t s[256];
+  const int r = threadIdx.x;
+  const uint32_t v = r < p.n_scan ? F.rowcnt[r] : 0u;
+  s[r] = v;
+  __syncthreads();
+  for (int off = 1; off < 256; off <<= 1) {   // inclusive Hillis-Steele scan
+    const uint32_t t = r >= off ? s[r - off] : 0u;
+    __syncthreads();
+    s[r] += t;
+    __syncthreads();
+  }
+  if (r < p.n_scan) {
+    const int before = (int)(s[r] - v), after = (int)s[r];
+    F.roff_arr[r] = (uint32_t)before;
+    F.start[r] = before - 1 + 5;
+    F.end[r] = after - 1 - 5;
+    if (r == p.n_scan - 1) {
+      F.roff_arr[p.n_scan] = (uint32_t)after;
+      F.info->count = (uint32_t)after;
+    }
+    if (v && (r == 0 || s[r - 1] == 0)) F.info->first_ring = r;
+  }
+}
+
+// one block of 256 per (row, frame): the row's occupied cells in column order
+__global__ void __launch_bounds__(256) k_lf_extract(const LfFrame* __restrict__ fr, LfParams p) {
+  const LfFrame& F = fr[blockIdx.y];
+  const uint32_t row = blockIdx.x;
+  if (F.rowcnt[row] == 0) return;
+  const int per = (p.H + 255) / 256;   // <= 16 columns per thread
+  const int j0 = threadIdx.x * per;
+  uint32_t own = 0;
+  for (int k = 0; k < per; k++) {
+    const int j = j0 + k;
+    if (j < p.H && F.owner[row * (uint32_t)p.H + j] != 0xffffffffu) own++;
+  }
+  __shared__ uint32_t s[256];
+  s[threadIdx.x] = own;
+  __syncthreads();
+  for (int off = 1; off < 256; off <<= 1) {
+    const uint32_t t = (int)threadIdx.x >= off ? s[threadIdx.x - off] : 0u;
+    __syncthreads();
+    s[threadIdx.x] += t;
+    __syncthreads();
+  }
+  uint32_t pos = F.roff_arr[row] + s[threadIdx.x] - own;
+  for (int k = 0; k < per; k++) {
+    const int j = j0 + k;
+    if (j >= p.H) break;
+    const uint32_t i = F.owner[row * (uint32_t)p.H + j];
+    if (i == 0xffffffffu) continue;
+    Proj q;
+    float4 pt;
+    project_point(F, p, i, &q, &pt);   // the owner passed every test in k_lf_project
+    F.col_ind[pos] = j;
+    F.range[pos] = q.range;
+    F.cloud[pos] = pt;
+    pos++;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// calculateSmoothness (featureExtraction.cpp:84-105) and markOccludedPoints (:107-145)
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ void k_lf_smooth(const LfFrame* __restrict__ fr, LfParams p) {
+  const LfFrame& F = fr[blockIdx.y];
+  const int n = (int)F.info->count;
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i < 5 || i >= n - 5) return;
+  const float* r = F.range;
+  // strictly left to right, no contraction (-ffp-contract=off)
+  float d = r[i - 5] + r[i - 4];
+  d = d + r[i - 3];
+  d = d + r[i - 2];
+  d = d + r[i - 1];
+  d = d - r[i] * 10.0f;
+  d = d + r[i + 1];
+  d = d + r[i + 2];
+  d = d + r[i + 3];
+  d = d + r[i + 4];
+  d = d + r[i + 5];
+  const float c = d * d;
+  F.curv[i] = c;
+  F.picked[i] = 0;
+  F.label[i] = 0;
+  F.smooth[i] = DistId{c, (uint32_t)i};
+}
+
+// every mark is a store of 1, so concurrent marks commute; they follow every reset (separate launch)
+__global__ void k_lf_occlude(const LfFrame* __restrict__ fr, LfParams p) {
+  const LfFrame& F = fr[blockIdx.y];
+  const int n = (int)F.info->count;
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i < 5 || i >= n - 6) return;
+  const float depth1 = F.range[i], depth2 = F.range[i + 1];
+  const int columnDiff = abs(F.col_ind[i + 1] - F.col_ind[i]);
+  if (columnDiff < 10) {
+    if ((double)(depth1 - depth2) > 0.3) {
+      for (int l = -5; l <= 0; l++) F.picked[i + l] = 1;
+    } else if ((double)(depth2 - depth1) > 0.3) {
+      for (int l = 1; l <= 6; l++) F.picked[i + l] = 1;
+    }
+  }
+  const float ri = F.range[i];
+  const float diff1 = fabsf(F.range[i - 1] - ri), diff2 = fabsf(F.range[i + 1] - ri);
+  if ((double)diff1 > 0.02 * (double)ri && (double)diff2 > 0.02 * (double)ri) F.picked[i] = 1;
+}
+
+__global__ void k_lf_snapshot(const LfFrame* __restrict__ fr, LfParams p) {
+  const LfFrame& F = fr[blockIdx.y];
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < F.info->count) F.picked_occ[i] = F.picked[i];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// extractFeatures (:147-247): one wave per (ring, frame).  The ring's pointColInd, cloudNeighborPicked and cloudLabel with a +-5
+// halo live in LDS; any other position (only the stale slot 4 of the first ring can name one) is read and written in global
+// memory, which is why the first ring runs in a launch of its own before the others.
+// ---------------------------------------------------------------------------------------------------------------------------
+struct Ring {
+  int wlo, whi, cap;
+  int16_t* col; uint8_t* pick; int8_t* lab;
+  const LfFrame* F;
+  __device__ bool in(int i) const { return i >= wlo && i < whi; }
+  // outside [0, cap) the reference reads beyond its vectors (only the initial stale entry {0, 0} can get there): a column jump
+  __device__ int col_at(int i) const { return in(i) ? (int)col[i - wlo] : (i < 0 || i >= cap) ? -100000 : F->col_ind[i]; }
+  __device__ int pick_at(int i) const { return in(i) ? (int)pick[i - wlo] : F->picked[i]; }
+  __device__ int lab_at(int i) const { return in(i) ? (int)lab[i - wlo] : F->label[i]; }
+  // every lane of the wave stores the same value (each then reads its own store back: no cross-lane ordering needed)
+  __device__ void set_pick(int i) const { if (in(i)) pick[i - wlo] = 1; else F->picked[i] = 1; }
+  __device__ void set_lab(int i, int v) const { if (in(i)) lab[i - wlo] = (int8_t)v; else F->label[i] = v; }
+  __device__ void suppress(int ind) const {   // :186-201 / :213-230
+    for (int l = 1; l <= 5; l++) {
+      if (abs(col_at(ind + l) - col_at(ind + l - 1)) > 10) break;
+      set_pick(ind + l);
+    }
+    for (int l = -1; l >= -5; l--) {
+      if (abs(col_at(ind + l) - col_at(ind + l + 1)) > 10) break;
+      set_pick(ind + l);
+    }
+  }
+};
+
+// one greedy pass over the visit order (corner: ent[S], ent[S-1], ..., ent[0]; surf: ent[0], ..., ent[S]) by ballot: the first
+// eligible lane of a 64-entry window is taken, its marks are made, the lanes behind it are evaluated again
+template <bool kCorner>
+__device__ void greedy_pass(const Ring& R, const DistId* ent, int S, float thr, int32_t* cpick, int* ccount) {
+  const int lane = threadIdx.x;
+  int picks = 0;
+  for (int base = 0; base <= S; base += 64) {
+    const int v = base + lane;
+    int ind = 0;
+    bool cand = false;
+    if (v <= S) {
+      ind = (int)ent[kCorner ? S - v : v].id;
+      const float c = R.F->curv[ind];
+      cand = kCorner ? (c > thr) : (c < thr);
+    }
+    for (;;) {
+      const bool elig = cand && R.pick_at(ind) == 0;
+      const uint64_t m = __ballot(elig);
+      if (m == 0) break;
+      const int l = __ffsll((unsigned long long)m) - 1;
+      const int pind = __shfl(ind, l, 64);
+      if (kCorner) {
+        if (++picks > kMaxPicks) return;   // the 21st eligible candidate breaks the loop before it is marked (:178-183)
+        R.set_lab(pind, 1);
+        if (lane == 0) cpick[*ccount] = pind;
+        ++*ccount;
+      } else {
+        R.set_lab(pind, -1);
+      }
+      R.set_pick(pind);
+      R.suppress(pind);
+      cand = cand && lane > l;
+    }
+  }
+}
+
+// the bitonic order of (value, position) equals std::sort's order as far as the passes can tell
+__device__ bool order_invariant(const Ring& R, const DistId* ent, int S, int sp, const LfParams& p) {
+  bool bad = false;
+  for (int t = threadIdx.x; t < S && !bad; t += 64) {
+    const float v = ent[t].d;
+    const int ia = (int)ent[t].id;
+    const float ca = R.F->curv[ia];
+    const bool cc = ca > p.edge, cs = ca < p.surf;
+    if (!cc && !cs) continue;
+    for (int u = t + 1; u < S && ent[u].d == v; u++) {
+      if (u - t > 256) { bad = true; break; }   // very large tie group: serial
+      const int ib = (int)ent[u].id;
+      const float cb = R.F->curv[ib];
+      if (cc && cb > p.edge) { bad = true; break; }   // two corner candidates in one tie group
+      if (cs && cb < p.surf && abs(ia - ib) <= 5) { bad = true; break; }
+    }
+  }
+  // std::sort leaves one of the minimum's ties in slot sp; slot 4 outlives the frame (the stale entry of the next one)
+  if (sp == 4 && S >= 2 && ent[0].d == ent[1].d) bad = true;
+  return __ballot(bad) == 0;
+}
+
+template <bool kFirst>
+__global__ void __launch_bounds__(64) k_lf_select(const LfFrame* __restrict__ fr, LfParams p) {
+  const LfFrame& F = fr[blockIdx.y];
+  const int first = F.info->first_ring;
+  if (first < 0) return;
+  const int r = kFirst ? first : (int)blockIdx.x;
+  if (!kFirst && r == first) return;
+  const int c = (int)F.roff_arr[r], n = (int)F.roff_arr[r + 1] - c;
+  if (n == 0) return;
+  const int cap = p.n_scan * p.H;
+  extern __shared__ char smem[];
+  DistId* ent = reinterpret_cast<DistId*>(smem);
+  uint64_t* key = reinterpret_cast<uint64_t*>(smem);   // the same bytes: keys first, entries after the sort
+  const int W = p.H + 10;
+  int16_t* s_col = reinterpret_cast<int16_t*>(smem + (size_t)p.P * 8);
+  uint8_t* s_pick = reinterpret_cast<uint8_t*>(s_col + W);
+  int8_t* s_lab = reinterpret_cast<int8_t*>(s_pick + W);
+  Ring R;
+  R.wlo = max(0, c - 5);
+  R.whi = min(cap, c + n + 5);
+  R.cap = cap;
+  R.col = s_col; R.pick = s_pick; R.lab = s_lab; R.F = &F;
+  const int lane = threadIdx.x;
+  for (int k = lane; k < R.whi - R.wlo; k += 64) {
+    s_col[k] = (int16_t)F.col_ind[R.wlo + k];
+    s_pick[k] = (uint8_t)F.picked[R.wlo + k];
+    s_lab[k] = (int8_t)F.label[R.wlo + k];
+  }
+  for (int k = c + lane; k < c + n; k += 64) F.member[k] = -1;
+  __syncthreads();
+  const int start = c - 1 + 5, end = c + n - 1 - 5, A = p.A;
+  int32_t* cpick = F.cpick + (size_t)r * p.ppr;
+  int ccount = 0, sectors = 0, serial = 0, bad_sector = 0;
+  for (int j = 0; j < A; j++) {
+    const int sp = (start * (A - j) + end * j) / A;            // C++ int division truncates toward zero
+    const int ep = (start * (A - 1 - j) + end * (j + 1)) / A - 1;
+    if (sp >= ep) continue;
+    const int S = ep - sp;                                      // std::sort covers [sp, ep); the entry at ep stays
+    if (S + 1 > p.P) { bad_sector = 1; continue; }
+    sectors++;
+    bool ok = false;
+    if (!p.force_serial) {
+      for (int t = lane; t < p.P; t += 64)
+        key[t] = t < S ? (((uint64_t)__float_as_uint(F.smooth[sp + t].d) << 32) | (uint32_t)t) : ~0ull;   // curvatures are >= 0
+      __syncthreads();
+      int P2 = 1;
+      while (P2 < S) P2 <<= 1;
+      for (int k = 2; k <= P2; k <<= 1)
+        for (int jj = k >> 1; jj > 0; jj >>= 1) {
+          for (int t = lane; t < P2; t += 64) {
+            const int u = t ^ jj;
+            if (u > t) {
+              const uint64_t a = key[t], b = key[u];
+              if ((a > b) == ((t & k) == 0)) { key[t] = b; key[u] = a; }
+            }
+          }
+          __syncthreads();
+        }
+      // keys -> entries in place: slot t's key and entry share the same 8 bytes and one lane owns the slot
+      for (int t = lane; t < S; t += 64) {
+        const uint32_t pos = (uint32_t)(key[t] & 0xffffffffu);
+        ent[t] = F.smooth[sp + pos];
+      }
+      if (lane == 0) ent[S] = F.smooth[ep];
+      __syncthreads();
+      ok = order_invariant(R, ent, S, sp, p);
+    }
+    if (!ok) {   // std::sort itself on the array order
+      for (int t = lane; t <= S; t += 64) ent[t] = F.smooth[sp + t];
+      __syncthreads();
+      if (lane == 0) intro_sort_libstdcxx(ent, S);
+      __syncthreads();
+      serial++;
+    }
+    for (int t = lane; t < S; t += 64) F.smooth[sp + t] = ent[t];   // the sorted sector persists (slot 4 feeds the next frame)
+    greedy_pass<true>(R, ent, S, p.edge, cpick, &ccount);
+    greedy_pass<false>(R, ent, S, p.surf, nullptr, nullptr);
+    for (int k = sp + lane; k <= ep; k += 64)                   // surfaceCloudScan (:234-240): labels -1 and 0
+      if (R.lab_at(k) <= 0) F.member[k] = r;
+    __syncthreads();
+  }
+  // write back: labels of the ring's own positions, marks (stores of 1 commute with the neighbouring rings' ones)
+  for (int k = lane; k < R.whi - R.wlo; k += 64) {
+    const int i = R.wlo + k;
+    if (i >= c && i < c + n) F.label[i] = s_lab[k];
+    if (s_pick[k]) F.picked[i] = 1;
+  }
+  if (lane == 0) {
+    F.ccnt[r] = ccount;
+    atomicAdd(&F.info->sectors, (uint32_t)sectors);
+    atomicAdd(&F.info->sectors_serial, (uint32_t)serial);
+    if (bad_sector) F.info->bad_sector = 1u;
+  }
+}
+
+// cornerCloud in pick order: rings concatenated (one block of 256 per frame)
+__global__ void __launch_bounds__(256) k_lf_corner_compact(const LfFrame* __restrict__ fr, LfParams p) {
+  const LfFrame& F = fr[blockIdx.x];
+  __shared__ uint32_t s[256];
+  const int r = threadIdx.x;
+  const uint32_t v = r < p.n_scan ? (uint32_t)F.ccnt[r] : 0u;
+  s[r] = v;
+  __syncthreads();
+  for (int off = 1; off < 256; off <<= 1) {
+    const uint32_t t = r >= off ? s[r - off] : 0u;
+    __syncthreads();
+    s[r] += t;
+    __syncthreads();
+  }
+  if (r == 255) F.info->n_corner_scan = s[255];
+  if (r < p.n_scan) {
+    const uint32_t o = s[r] - v;
+    for (uint32_t t = 0; t < v; t++) F.corner_scan[o + t] = F.cloud[F.cpick[(size_t)r * p.ppr + t]];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// segmented pcl::VoxelGrid (same arithmetic as preprocess.hip's voxel_downsample_device, one box per segment):
+//   stage 1: segment = frame * n_scan + ring, the ring's surfaceCloudScan, leaf odometrySurfLeafSize (:243-245)
+//   stage 2: segment = 2 frame (corner) / 2 frame + 1 (surf), leaf mappingCornerLeafSize / mappingSurfLeafSize
+//            (downsampleCurrentScan, mapOptmization.cpp:1238-1246); leaf 0 = no down-sampling (one cell per element, in order)
+// keys (segment << 32 | cell index) are radix-sorted once for all segments of all frames; double centroid sums.
+// ---------------------------------------------------------------------------------------------------------------------------
+struct Elem { bool valid; uint32_t seg, ord; float4 pt; };
+
+template <int kStage>
+__device__ inline Elem elem_of(const LfFrame& F, const LfParams& p, uint32_t f, uint32_t j, const float4* cells1) {
+  Elem e{false, 0u, 0u, make_float4(0.f, 0.f, 0.f, 0.f)};
+  if (kStage == 1) {
+    if (j < F.info->count && F.member[j] >= 0) {
+      e.valid = true; e.seg = f * (uint32_t)p.n_scan + (uint32_t)F.member[j]; e.ord = j; e.pt = F.cloud[j];
+    }
+  } else {
+    const uint32_t nc = (uint32_t)p.n_scan * (uint32_t)p.ppr;
+    if (j < nc) {
+      const uint32_t r = j / (uint32_t)p.ppr, t = j % (uint32_t)p.ppr;
+      if (t < (uint32_t)F.ccnt[r]) { e.valid = true; e.seg = 2u * f; e.ord = j; e.pt = F.cloud[F.cpick[j]]; }
+    } else if (j - nc < F.info->n_surf_scan) {
+      e.valid = true; e.seg = 2u * f + 1u; e.ord = j; e.pt = cells1[F.info->first1 + (j - nc)];
+    }
+  }
+  return e;
+}
+
+__device__ inline float seg_leaf(int stage, const LfParams& p, uint32_t seg) {
+  return stage == 1 ? p.leaf_odo : ((seg & 1u) ? p.leaf_surf : p.leaf_corner);
+}
+
+__device__ inline unsigned int f2ord(float f) { const unsigned int u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+// inverse of f2ord, branch-free (the select form crashes this compiler's instruction selection when followed by float arithmetic)
+__device__ inline float ord2f(unsigned int o) { const unsigned int m = (unsigned int)((int)o >> 31); return __uint_as_float(o ^ (~m | 0x80000000u)); }
+
+__global__ void k_sv_clear(unsigned int* __restrict__ mm, uint32_t* __restrict__ scnt, uint32_t nseg) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nseg) return;
+  for (int a = 0; a < 3; a++) { mm[6 * s + a] = 0xffffffffu; mm[6 * s + 3 + a] = 0u; }
+  scnt[s] = 0u;
+}
+
+template <int kStage>
+__global__ void k_sv_minmax(const LfFrame* __restrict__ fr, LfParams p, uint32_t size_per_frame, const float4* __restrict__ cells1, unsigned int* __restrict__ mm) {
+  const uint32_t f = blockIdx.y;
+  const LfFrame& F = fr[f];
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  const Elem e = j < size_per_frame ? elem_of<kStage>(F, p, f, j, cells1) : Elem{false, 0u, 0u, make_float4(0.f, 0.f, 0.f, 0.f)};
+  unsigned int lo[3], hi[3];
+  const float c[3] = {e.pt.x, e.pt.y, e.pt.z};
+  for (int a = 0; a < 3; a++) { lo[a] = e.valid ? f2ord(c[a]) : 0xffffffffu; hi[a] = e.valid ? f2ord(c[a]) : 0u; }
+  // one atomic per wave when every valid lane shares the segment
+  const uint64_t vm = __ballot(e.valid);
+  if (vm == 0) return;
+  const int l0 = __ffsll((unsigned long long)vm) - 1;
+  const uint32_t s0 = (uint32_t)__shfl((int)e.seg, l0, 64);
+  const bool same = __ballot(e.valid && e.seg != s0) == 0;
+  if (same) {
+    for (int off = 32; off >= 1; off >>= 1)
+      for (int a = 0; a < 3; a++) { lo[a] = min(lo[a], (unsigned int)__shfl_xor((int)lo[a], off, 64)); hi[a] = max(hi[a], (unsigned int)__shfl_xor((int)hi[a], off, 64)); }
+    if ((threadIdx.x & 63) == 0)
+      for (int a = 0; a < 3; a++) { atomicMin(&mm[6 * s0 + a], lo[a]); atomicMax(&mm[6 * s0 + 3 + a], hi[a]); }
+  } else if (e.valid) {
+    for (int a = 0; a < 3; a++) { atomicMin(&mm[6 * e.seg + a], lo[a]); atomicMax(&mm[6 * e.seg + 3 + a], hi[a]); }
+  }
+}
+
+// per segment: the box of pcl::VoxelGrid from the segment's min / max: box = {min_b x, y, z, divb_mul[1], divb_mul[2], state}
+// (state 0: empty or no leaf, 1: index overflow, 2: valid).  The products are formed in double: exact, as a valid box has fewer
+// than 2^31 cells.
+__global__ void k_sv_boxes(const LfFrame* __restrict__ fr, const unsigned int* __restrict__ mm, uint32_t nseg, int stage, LfParams p, long long* __restrict__ box) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nseg) return;
+  long long* b = box + 6 * (size_t)s;
+  b[5] = 0;
+  if (mm[6 * s] == 0xffffffffu) return;   // empty segment
+  const float leaf = seg_leaf(stage, p, s);
+  if (!(leaf > 0.f)) return;
+  const float inv = 1.0f / leaf;
+  float mn[3], mx[3];
+  for (int a = 0; a < 3; a++) { mn[a] = ord2f(mm[6 * s + a]); mx[a] = ord2f(mm[6 * s + 3 + a]); }
+  double cells = 1.0;
+  for (int a = 0; a < 3; a++) cells *= trunc((double)((mx[a] - mn[a]) * inv)) + 1.0;   // int64_t((max - min) * inv) + 1, max >= min
+  const bool over = cells > 2147483647.0;
+  int mb[3], xb[3];
+  for (int a = 0; a < 3; a++) { mb[a] = (int)floorf(mn[a] * inv); xb[a] = (int)floorf(mx[a] * inv); }
+  const double div0 = (double)xb[0] - (double)mb[0] + 1.0, div1 = (double)xb[1] - (double)mb[1] + 1.0;
+  b[0] = mb[0]; b[1] = mb[1]; b[2] = mb[2];
+  b[3] = over ? 0 : (long long)div0;
+  b[4] = over ? 0 : (long long)(div0 * div1);
+  b[5] = over ? 1 : 2;
+  if (over) fr[s / (stage == 1 ? (uint32_t)p.n_scan : 2u)].info->overflow = 1u;   // every writer stores 1
+}
+
+template <int kStage>
+__global__ void k_sv_keys(const LfFrame* __restrict__ fr, LfParams p, uint32_t size_per_frame, const float4* __restrict__ cells1, const long long* __restrict__ box,
+                          uint32_t nseg, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+  const uint32_t f = blockIdx.y;
+  const LfFrame& F = fr[f];
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  // the frame's own element range (size_per_frame is the largest of the batch)
+  const uint32_t own = kStage == 1 ? F.cap1 : (uint32_t)p.n_scan * (uint32_t)p.ppr + F.cap1;
+  if (j >= size_per_frame || j >= own) return;
+  const uint32_t g = (kStage == 1 ? F.base1 : F.base2) + j;
+  const Elem e = elem_of<kStage>(F, p, f, j, cells1);
+  uint64_t key = (uint64_t)nseg << 32;   // invalid: behind every segment
+  if (e.valid) {
+    const float leaf = seg_leaf(kStage, p, e.seg);
+    const long long* b = box + 6 * (size_t)e.seg;
+    if (!(leaf > 0.f)) {
+      key = ((uint64_t)e.seg << 32) | e.ord;
+    } else if (b[5] == 2) {
+      const float inv = 1.0f / leaf;
+      const int mb0 = (int)b[0], mb1 = (int)b[1], mb2 = (int)b[2];
+      const long long i0 = (long long)(floorf(e.pt.x * inv) - (float)mb0), i1 = (long long)(floorf(e.pt.y * inv) - (float)mb1),
+                      i2 = (long long)(floorf(e.pt.z * inv) - (float)mb2);
+      key = ((uint64_t)e.seg << 32) | (uint64_t)(i0 + i1 * b[3] + i2 * b[4]);
+    }
+  }
+  keys[g] = key;
+  vals[g] = g;
+}
+
+__global__ void k_sv_heads(const uint64_t* __restrict__ keys, uint32_t n, uint32_t nseg, uint32_t* __restrict__ head, uint32_t* __restrict__ scnt) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t k = keys[i];
+  const bool h = (k >> 32) < nseg && (i == 0 || keys[i - 1] != k);
+  head[i] = h ? 1u : 0u;
+  if (h) atomicAdd(&scnt[k >> 32], 1u);
+}
+
+// cell c starts at sorted element pos[c]; the first cell of every segment -> sfirst[segment]
+__global__ void k_sv_head_pos(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ head, const uint32_t* __restrict__ slot, uint32_t n,
+                              uint32_t* __restrict__ pos, uint32_t* __restrict__ sfirst) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || !head[i]) return;
+  pos[slot[i]] = i;
+  const uint32_t s = (uint32_t)(keys[i] >> 32);
+  if (i == 0 || (uint32_t)(keys[i - 1] >> 32) != s) sfirst[s] = slot[i];
+}
+
+// the last valid element: valid count and cell count
+__global__ void k_sv_count(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ head, const uint32_t* __restrict__ slot, uint32_t n, uint32_t nseg,
+                           uint32_t* __restrict__ nc) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || (keys[i] >> 32) >= nseg) return;
+  if (i + 1 == n || (keys[i + 1] >> 32) >= nseg) { nc[0] = slot[i] + head[i]; nc[1] = i + 1; }
+}
+
+// one wave per cell (grid-stride): double sums of x, y, z, intensity over the cell's run (k_vg_average's scheme)
+template <int kStage>
+__global__ void __launch_bounds__(256) k_sv_average(const LfFrame* __restrict__ fr, LfParams p, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                    const uint32_t* __restrict__ pos, const uint32_t* __restrict__ ncells_p, const uint32_t* __restrict__ nvalid_p,
+                                                    const float4* __restrict__ cells1, float4* __restrict__ out) {
+  const uint32_t ncells = *ncells_p, nvalid = *nvalid_p;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t spf = kStage == 1 ? (uint32_t)p.n_scan : 2u;
+  for (uint32_t cell = blockIdx.x * 4 + (threadIdx.x >> 6); cell < ncells; cell += gridDim.x * 4) {
+    const uint32_t b = pos[cell], e = cell + 1 < ncells ? pos[cell + 1] : nvalid;
+    const uint32_t seg = (uint32_t)(keys[b] >> 32), f = seg / spf;
+    const LfFrame& F = fr[f];
+    const uint32_t base = kStage == 1 ? F.base1 : F.base2;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (uint32_t j = b + lane; j < e; j += 64) {
+      const float4 q = elem_of<kStage>(F, p, f, vals[j] - base, cells1).pt;
+      acc[0] += (double)q.x; acc[1] += (double)q.y; acc[2] += (double)q.z; acc[3] += (double)q.w;
+    }
+    for (int k = 0; k < 4; k++)
+      for (int off = 32; off >= 1; off >>= 1) acc[k] += __shfl_xor(acc[k], off, 64);
+    if (lane == 0) {
+      const double m = (double)(e - b);
+      out[cell] = make_float4((float)(acc[0] / m), (float)(acc[1] / m), (float)(acc[2] / m), (float)(acc[3] / m));
+    }
+  }
+}
+
+// per-frame totals of a stage from the segment counts (one block of 256 per frame)
+template <int kStage>
+__global__ void __launch_bounds__(256) k_sv_frames(const LfFrame* __restrict__ fr, LfParams p, const uint32_t* __restrict__ scnt, const uint32_t* __restrict__ sfirst) {
+  const uint32_t f = blockIdx.x;
+  const LfFrame& F = fr[f];
+  const uint32_t spf = kStage == 1 ? (uint32_t)p.n_scan : 2u;
+  __shared__ uint32_t s_tot, s_first;
+  if (threadIdx.x == 0) { s_tot = 0; s_first = 0xffffffffu; }
+  __syncthreads();
+  for (uint32_t r = threadIdx.x; r < spf; r += 256) {
+    const uint32_t c = scnt[f * spf + r];
+    if (c) { atomicAdd(&s_tot, c); atomicMin(&s_first, sfirst[f * spf + r]); }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (kStage == 1) { F.info->n_surf_scan = s_tot; F.info->first1 = s_first == 0xffffffffu ? 0u : s_first; }
+    else {
+      F.info->n_corner = scnt[2 * f]; F.info->n_surf = scnt[2 * f + 1];
+      F.info->first2 = s_first == 0xffffffffu ? 0u : s_first;
+    }
+  }
+}
+
+// the frame's outputs: surfaceCloud (stage 1) and the mapping-down-sampled features (stage 2), corner first, then surf
+__global__ void k_lf_finish(const LfFrame* __restrict__ fr, LfParams p, const float4* __restrict__ cells1, const float4* __restrict__ cells2) {
+  const LfFrame& F = fr[blockIdx.y];
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const LfInfo& I = *F.info;
+  if (i < I.n_surf_scan) F.surf_scan[i] = cells1[I.first1 + i];
+  const uint32_t nf = I.n_corner + I.n_surf;
+  if (i < nf) {
+    const float4 q = cells2[I.first2 + i];
+    F.out[i] = q;
+    if (F.src) {   // k_load_points' layout: w = the index within its own cloud
+      const uint32_t w = i < I.n_corner ? i : i - I.n_corner;
+      F.src[i] = make_float4(q.x, q.y, q.z, __uint_as_float(w));
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------------------
+template <typename T>
+int grow(pcm_ctx* c, T** p, size_t* cap, size_t n, bool zero = false) {
+  if (n <= *cap && *p) return PCM_OK;
+  if (*p) { (void)hipStreamSynchronize(c->stream); hipFree(*p); }
+  *p = nullptr; *cap = 0;
+  const size_t bytes = sizeof(T) * (n ? n : 1);
+  LFCK(c, hipMalloc(reinterpret_cast<void**>(p), bytes));
+  if (zero) LFCK(c, hipMemset(*p, 0, bytes));
+  *cap = n;
+  return PCM_OK;
+}
+
+// the cross-frame state of one context (the reference node's members) and its last frame's outputs
+struct FeatState {
+  int n_scan = 0, H = 0, A = 0;
+  size_t cap = 0, sz_state = 0;
+  int32_t* col_ind = nullptr; float* range = nullptr; float4* cloud = nullptr; float* curv = nullptr;
+  int32_t* picked = nullptr; int32_t* label = nullptr; DistId* smooth = nullptr;
+  int32_t* picked_occ = nullptr; int32_t* start = nullptr; int32_t* end = nullptr;   // end = start + n_scan (one allocation)
+  size_t cap_occ = 0, cap_se = 0;
+  float4* corner_scan = nullptr; size_t cap_cs = 0;
+  float4* surf_scan = nullptr; size_t cap_ss = 0;
+  float4* out = nullptr; size_t cap_out = 0;
+  LfInfo last{};
+  bool have_last = false;
+  // batch workspace (used when this context leads a batch)
+  LfFrame* d_fr = nullptr; LfFrame* h_fr = nullptr; int fr_cap = 0;
+  LfInfo* d_info = nullptr; LfInfo* h_info = nullptr; int info_cap = 0;
+  char* ws = nullptr; size_t ws_cap = 0;
+
+  void release_state() {
+    for (void* q : {(void*)col_ind, (void*)range, (void*)cloud, (void*)curv, (void*)picked, (void*)label, (void*)smooth}) if (q) hipFree(q);
+    col_ind = nullptr; range = nullptr; cloud = nullptr; curv = nullptr; picked = nullptr; label = nullptr; smooth = nullptr;
+    sz_state = 0;
+  }
+  void release() {
+    release_state();
+    for (void* q : {(void*)picked_occ, (void*)start, (void*)corner_scan, (void*)surf_scan, (void*)out, (void*)d_fr, (void*)d_info, (void*)ws}) if (q) hipFree(q);
+    if (h_fr) hipHostFree(h_fr);
+    if (h_info) hipHostFree(h_info);
+  }
+};
+
+FeatState* fe_of(pcm_ctx* c) {
+  if (!c->loam_fe) c->loam_fe = new (std::nothrow) FeatState();
+  return static_cast<FeatState*>(c->loam_fe);
+}
+
+int check_fparams(pcm_ctx* c, const pcm_loam_feature_params& p) {
+  if (p.n_scan < 1 || p.horizon_scan < 2) { c->err = "n_scan must be >= 1 and horizon_scan >= 2"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (p.n_scan > 256 || p.horizon_scan > 4096) { c->err = "n_scan > 256 or horizon_scan > 4096 is not supported"; return PCM_ERR_UNSUPPORTED; }
+  if (p.downsample_rate < 1 || p.area_num < 1 || p.area_num > 4096) { c->err = "downsample_rate must be >= 1 and area_num in [1, 4096]"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!(p.min_range >= 0.f) || !(p.max_range <= 1e30f) || !(p.edge_threshold == p.edge_threshold) || !(p.surf_threshold == p.surf_threshold)) {
+    c->err = "ranges must be in [0, 1e30] and the thresholds numbers"; return PCM_ERR_INVALID_ARGUMENT;
+  }
+  if (!(p.odometry_surf_leaf > 0.f) || !(p.mapping_corner_leaf >= 0.f) || !(p.mapping_surf_leaf >= 0.f)) {
+    c->err = "odometry_surf_leaf must be > 0, the mapping leaves >= 0 (0: no down-sampling)"; return PCM_ERR_INVALID_ARGUMENT;
+  }
+  return PCM_OK;
+}
+
+// the context's state arrays for (n_scan, horizon_scan): zero at creation (cloudSmoothness is value-initialised; the three
+// new T[] arrays of featureExtraction are taken as zero) and again whenever the shape changes
+int ensure_state(pcm_ctx* c, FeatState* S, const pcm_loam_feature_params& p) {
+  const size_t cap = (size_t)p.n_scan * (size_t)p.horizon_scan;
+  if (S->col_ind && S->n_scan == p.n_scan && S->H == p.horizon_scan) return PCM_OK;
+  (void)hipStreamSynchronize(c->stream);
+  S->release_state();
+  size_t k = 0;
+  int rc;
+  if ((rc = grow(c, &S->col_ind, &k, cap, true)) != PCM_OK) return rc; k = 0;
+  if ((rc = grow(c, &S->range, &k, cap, true)) != PCM_OK) return rc; k = 0;
+  if ((rc = grow(c, &S->cloud, &k, cap, true)) != PCM_OK) return rc; k = 0;
+  if ((rc = grow(c, &S->curv, &k, cap, true)) != PCM_OK) return rc; k = 0;
+  if ((rc = grow(c, &S->picked, &k, cap, true)) != PCM_OK) return rc; k = 0;
+  if ((rc = grow(c, &S->label, &k, cap, true)) != PCM_OK) return rc; k = 0;
+  if ((rc = grow(c, &S->smooth, &k, cap, true)) != PCM_OK) return rc;
+  S->n_scan = p.n_scan; S->H = p.horizon_scan; S->cap = cap;
+  S->have_last = false;
+  return PCM_OK;
+}
+
+size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+int next_pow2(int x) { int p = 1; while (p < x) p <<= 1; return p; }
+int bit_len(uint64_t x) { int b = 0; while (x) { b++; x >>= 1; } return b; }
+
+struct BatchLayout {
+  size_t o_in, o_owner, o_rowcnt, o_roff, o_member, o_cpick, o_ccnt;
+  size_t o_k1, o_k1s, o_v1, o_v1s, o_head1, o_slot1, o_cells1;
+  size_t o_k2, o_k2s, o_v2, o_v2s, o_head2, o_slot2, o_cells2;
+  size_t o_mm, o_box, o_scnt, o_sfirst, o_nc, o_tmp, o_tmp2, total;
+  size_t tmp_bytes, tmp2_bytes;
+};
+
+BatchLayout layout(int B, size_t in_bytes, size_t cap, int n_scan, int ppr, size_t N1, size_t N2, size_t nseg_max) {
+  BatchLayout L{};
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t r = o; o += up256(bytes); return r; };
+  L.o_in = take(in_bytes);
+  L.o_owner = take(4 * cap * B);
+  L.o_rowcnt = take(4 * (size_t)n_scan * B);
+  L.o_roff = take(4 * (size_t)(n_scan + 1) * B);
+  L.o_member = take(4 * cap * B);
+  L.o_cpick = take(4 * (size_t)n_scan * ppr * B);
+  L.o_ccnt = take(4 * (size_t)n_scan * B);
+  const size_t NM = std::max(N1, N2);
+  L.o_k1 = take(8 * NM); L.o_k1s = take(8 * NM); L.o_v1 = take(4 * NM); L.o_v1s = take(4 * NM);
+  L.o_head1 = take(4 * NM); L.o_slot1 = take(4 * NM);
+  L.o_cells1 = take(16 * N1);
+  L.o_cells2 = take(16 * N2);
+  L.o_mm = take(4 * 6 * nseg_max); L.o_box = take(8 * 6 * nseg_max); L.o_scnt = take(4 * nseg_max); L.o_sfirst = take(4 * nseg_max);
+  L.o_nc = take(16);
+  size_t t1 = 0, t2 = 0;
+  {
+    uint64_t* k = nullptr; uint32_t* v = nullptr;
+    (void)rocprim::radix_sort_pairs(nullptr, t1, k, k, v, v, NM, 0, 64, nullptr);
+    (void)rocprim::exclusive_scan(nullptr, t2, v, v, 0u, NM, rocprim::plus<uint32_t>(), nullptr);
+  }
+  L.tmp_bytes = t1; L.tmp2_bytes = t2;
+  L.o_tmp = take(t1);
+  L.o_tmp2 = take(t2);
+  L.total = o;
+  return L;
+}
+
+int run_vg(pcm_ctx* c0, hipStream_t st, int stage, const LfFrame* d_fr, const LfParams& P, int B, uint32_t size_per_frame, uint32_t N, uint32_t nseg,
+           char* ws, const BatchLayout& Lw, const float4* cells1, float4* cells_out) {
+  uint64_t* keys = reinterpret_cast<uint64_t*>(ws + Lw.o_k1);
+  uint64_t* keys_s = reinterpret_cast<uint64_t*>(ws + Lw.o_k1s);
+  uint32_t* vals = reinterpret_cast<uint32_t*>(ws + Lw.o_v1);
+  uint32_t* vals_s = reinterpret_cast<uint32_t*>(ws + Lw.o_v1s);
+  uint32_t* head = reinterpret_cast<uint32_t*>(ws + Lw.o_head1);
+  uint32_t* slot = reinterpret_cast<uint32_t*>(ws + Lw.o_slot1);
+  unsigned int* mm = reinterpret_cast<unsigned int*>(ws + Lw.o_mm);
+  uint32_t* scnt = reinterpret_cast<uint32_t*>(ws + Lw.o_scnt);
+  uint32_t* sfirst = reinterpret_cast<uint32_t*>(ws + Lw.o_sfirst);
+  uint32_t* nc = reinterpret_cast<uint32_t*>(ws + Lw.o_nc);   // [0] cells, [1] valid elements
+  long long* box = reinterpret_cast<long long*>(ws + Lw.o_box);
+  if (N == 0 || size_per_frame == 0) return PCM_OK;
+  const dim3 g((size_per_frame + 255) / 256, (unsigned)B);
+  k_sv_clear<<<(nseg + 255) / 256, 256, 0, st>>>(mm, scnt, nseg);
+  LFCK(c0, hipMemsetAsync(nc, 0, 16, st));
+  if (stage == 1) {
+    k_sv_minmax<1><<<g, 256, 0, st>>>(d_fr, P, size_per_frame, cells1, mm);
+    k_sv_boxes<<<(nseg + 255) / 256, 256, 0, st>>>(d_fr, mm, nseg, 1, P, box);
+    k_sv_keys<1><<<g, 256, 0, st>>>(d_fr, P, size_per_frame, cells1, box, nseg, keys, vals);
+  } else {
+    k_sv_minmax<2><<<g, 256, 0, st>>>(d_fr, P, size_per_frame, cells1, mm);
+    k_sv_boxes<<<(nseg + 255) / 256, 256, 0, st>>>(d_fr, mm, nseg, 2, P, box);
+    k_sv_keys<2><<<g, 256, 0, st>>>(d_fr, P, size_per_frame, cells1, box, nseg, keys, vals);
+  }
+  LFCK(c0, hipGetLastError());
+  size_t tb = Lw.tmp_bytes, tb2 = Lw.tmp2_bytes;
+  const int end_bit = 32 + bit_len(nseg);
+  LFCK(c0, rocprim::radix_sort_pairs(ws + Lw.o_tmp, tb, keys, keys_s, vals, vals_s, (size_t)N, 0, end_bit, st));
+  const unsigned nb = (N + 255) / 256;
+  k_sv_heads<<<nb, 256, 0, st>>>(keys_s, N, nseg, head, scnt);
+  LFCK(c0, hipGetLastError());
+  LFCK(c0, rocprim::exclusive_scan(ws + Lw.o_tmp2, tb2, head, slot, 0u, (size_t)N, rocprim::plus<uint32_t>(), st));
+  uint32_t* pos = vals;   // free after the sort
+  k_sv_head_pos<<<nb, 256, 0, st>>>(keys_s, head, slot, N, pos, sfirst);
+  k_sv_count<<<nb, 256, 0, st>>>(keys_s, head, slot, N, nseg, nc);   // invalid keys sort behind every valid one
+  const unsigned gb = std::min<unsigned>(1024u, (N + 3) / 4);
+  if (stage == 1) {
+    k_sv_average<1><<<gb, 256, 0, st>>>(d_fr, P, keys_s, vals_s, pos, nc, nc + 1, cells1, cells_out);
+    k_sv_frames<1><<<B, 256, 0, st>>>(d_fr, P, scnt, sfirst);
+  } else {
+    k_sv_average<2><<<gb, 256, 0, st>>>(d_fr, P, keys_s, vals_s, pos, nc, nc + 1, cells1, cells_out);
+    k_sv_frames<2><<<B, 256, 0, st>>>(d_fr, P, scnt, sfirst);
+  }
+  LFCK(c0, hipGetLastError());
+  return PCM_OK;
+}
+
+}  // namespace
+
+namespace {
+
+pcm_loam_feature_params params_or_default(const pcm_loam_feature_params* params) {
+  pcm_loam_feature_params p;
+  if (params) p = *params; else pcm_loam_default_feature_params(&p);
+  return p;
+}
+
+LfParams dev_params(const pcm_loam_feature_params& q) {
+  LfParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.n_scan = q.n_scan; p.H = q.horizon_scan; p.rate = q.downsample_rate; p.A = q.area_num;
+  p.min_range = q.min_range; p.max_range = q.max_range; p.edge = q.edge_threshold; p.surf = q.surf_threshold;
+  p.ang_res_x = (float)(360.0 / (double)(float)q.horizon_scan);   // static float ang_res_x = 360.0/float(Horizon_SCAN) (:741)
+  p.leaf_odo = q.odometry_surf_leaf; p.leaf_corner = q.mapping_corner_leaf; p.leaf_surf = q.mapping_surf_leaf;
+  p.force_serial = (q.flags & PCM_LOAM_FEATURES_FORCE_SERIAL_SORT) ? 1 : 0;
+  p.ppr = q.area_num * kMaxPicks;
+  const int smax = (q.horizon_scan - 10) / q.area_num;   // ep - sp <= (end - start) / area_num, end - start = points - 10
+  p.P = next_pow2(std::max(1, smax + 1));
+  return p;
+}
+
+int check_ctx_fe(pcm_ctx* c) {
+  if (!c) return PCM_ERR_INVALID_ARGUMENT;
+  if (c->device < 0) return PCM_ERR_HIP;
+  if (c->cfg.model != PCM_MODEL_LOAM) { c->err = "pcm_loam_* needs a context created with PCM_MODEL_LOAM"; return PCM_ERR_UNSUPPORTED; }
+  if (!fe_of(c)) { c->err = "out of host memory"; return PCM_ERR_INTERNAL; }
+  return PCM_OK;
+}
+
+// the whole front end for n frames (one context each) in one set of launches on the first context's stream
+int run_frames(pcm_ctx* const* ctxs, int B, const void* const* points, const size_t* n_points, size_t stride, size_t ioff, size_t roff, int memory,
+               const pcm_loam_feature_params* params, bool to_source, pcm_loam_features_result* results) {
+  if (!ctxs || B <= 0 || !points || !n_points || !results) return PCM_ERR_INVALID_ARGUMENT;
+  pcm_ctx* c0 = ctxs[0];
+  int rc = check_ctx_fe(c0);
+  if (rc != PCM_OK) return rc;
+  const pcm_loam_feature_params q = params_or_default(params);
+  if ((rc = check_fparams(c0, q)) != PCM_OK) return rc;
+  if (stride < 12 || ioff + 1 > stride || roff + 2 > stride || (stride % 4) != 0 || (roff % 2) != 0) {
+    c0->err = "stride must be a multiple of 4 >= 12 holding the 1-byte intensity and the 2-byte aligned ring";
+    return PCM_ERR_INVALID_ARGUMENT;
+  }
+  if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c0->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  for (int i = 0; i < B; i++) {
+    if ((rc = check_ctx_fe(ctxs[i])) != PCM_OK) { if (ctxs[i] && ctxs[i] != c0) c0->err = ctxs[i]->err; return rc; }
+    if (ctxs[i]->device != c0->device) { c0->err = "all contexts of a batch must live on one device"; return PCM_ERR_INVALID_ARGUMENT; }
+    for (int j = 0; j < i; j++) if (ctxs[j] == ctxs[i]) { c0->err = "a context appears twice in the batch"; return PCM_ERR_INVALID_ARGUMENT; }
+    if (!points[i] && n_points[i]) { c0->err = "null point buffer"; return PCM_ERR_INVALID_ARGUMENT; }
+    if (n_points[i] > 0x3fffffffull) { c0->err = "cloud too large"; return PCM_ERR_INVALID_ARGUMENT; }
+  }
+  LFCK(c0, hipSetDevice(c0->device));
+  const LfParams P = dev_params(q);
+  const size_t cap = (size_t)q.n_scan * q.horizon_scan;
+  const size_t ncs = (size_t)q.n_scan * P.ppr;   // corner picks per frame
+  // LDS of k_lf_select: the sort buffer (<= 4096 entries of 8 bytes: a sector holds at most (horizon_scan - 10) / area_num + 1
+  // entries) and the ring window (horizon_scan + 10 positions of 4 bytes): at most 48.1 KiB within the caps checked above
+  const size_t lds = (size_t)P.P * 8 + (size_t)(q.horizon_scan + 10) * 4;
+  if (lds > 65536) { c0->err = "k_lf_select's LDS exceeds 64 KiB (library bug: the caps keep it below 48.1 KiB)"; return PCM_ERR_INTERNAL; }
+  // per-context state and outputs
+  std::vector<size_t> cap1((size_t)B), base1((size_t)B), base2((size_t)B);
+  size_t N1 = 0, N2 = 0, in_bytes = 0;
+  uint32_t max1 = 1;
+  for (int i = 0; i < B; i++) {
+    pcm_ctx* c = ctxs[i];
+    FeatState* S = fe_of(c);
+    if ((rc = ensure_state(c, S, q)) != PCM_OK) { if (c != c0) c0->err = c->err; return rc; }
+    cap1[(size_t)i] = std::min(n_points[i], cap);
+    base1[(size_t)i] = N1; N1 += cap1[(size_t)i];
+    base2[(size_t)i] = N2; N2 += ncs + cap1[(size_t)i];
+    max1 = std::max<uint32_t>(max1, (uint32_t)cap1[(size_t)i]);
+    if ((rc = grow(c, &S->picked_occ, &S->cap_occ, cap)) != PCM_OK || (rc = grow(c, &S->start, &S->cap_se, 2 * (size_t)q.n_scan)) != PCM_OK ||
+        (rc = grow(c, &S->corner_scan, &S->cap_cs, ncs)) != PCM_OK || (rc = grow(c, &S->surf_scan, &S->cap_ss, cap1[(size_t)i])) != PCM_OK ||
+        (rc = grow(c, &S->out, &S->cap_out, ncs + cap1[(size_t)i])) != PCM_OK) {
+      if (c != c0) c0->err = c->err;
+      return rc;
+    }
+    S->end = S->start + q.n_scan;
+    S->A = q.area_num;
+    if (memory == PCM_MEM_HOST) in_bytes += up256(n_points[i] * stride);
+  }
+  std::vector<float4*> src((size_t)B, nullptr);
+  if (to_source)
+    for (int i = 0; i < B; i++)
+      if ((rc = loam::loam_source_reserve(ctxs[i], ncs + cap1[(size_t)i], &src[(size_t)i])) != PCM_OK) { if (ctxs[i] != c0) c0->err = ctxs[i]->err; return rc; }
+  // batch workspace of the leading context
+  FeatState* S0 = fe_of(c0);
+  const size_t nseg_max = std::max<size_t>((size_t)B * q.n_scan, 2 * (size_t)B);
+  const BatchLayout Lw = layout(B, in_bytes, cap, q.n_scan, P.ppr, N1, N2, nseg_max);
+  hipStream_t st = c0->stream;
+  LFCK(c0, hipStreamSynchronize(st));   // the pinned staging of an earlier batch is free again
+  if ((rc = grow(c0, &S0->ws, &S0->ws_cap, Lw.total)) != PCM_OK) return rc;
+  if (B > S0->fr_cap) {
+    if (S0->d_fr) hipFree(S0->d_fr);
+    if (S0->h_fr) hipHostFree(S0->h_fr);
+    if (S0->d_info) hipFree(S0->d_info);
+    if (S0->h_info) hipHostFree(S0->h_info);
+    S0->d_fr = nullptr; S0->h_fr = nullptr; S0->d_info = nullptr; S0->h_info = nullptr; S0->fr_cap = 0;
+    LFCK(c0, hipMalloc(reinterpret_cast<void**>(&S0->d_fr), sizeof(LfFrame) * (size_t)B));
+    LFCK(c0, hipHostMalloc(reinterpret_cast<void**>(&S0->h_fr), sizeof(LfFrame) * (size_t)B));
+    LFCK(c0, hipMalloc(reinterpret_cast<void**>(&S0->d_info), sizeof(LfInfo) * (size_t)B));
+    LFCK(c0, hipHostMalloc(reinterpret_cast<void**>(&S0->h_info), sizeof(LfInfo) * (size_t)B));
+    S0->fr_cap = B;
+  }
+  char* ws = S0->ws;
+  size_t in_off = Lw.o_in;
+  uint32_t maxn = 1;
+  for (int i = 0; i < B; i++) {
+    FeatState* S = fe_of(ctxs[i]);
+    LfFrame& F = S0->h_fr[i];
+    std::memset(&F, 0, sizeof(F));
+    if (memory == PCM_MEM_HOST) {
+      F.pts = ws + in_off;
+      if (n_points[i]) LFCK(c0, hipMemcpyAsync(ws + in_off, points[i], n_points[i] * stride, hipMemcpyHostToDevice, st));
+      in_off += up256(n_points[i] * stride);
+    } else {
+      F.pts = static_cast<const char*>(points[i]);
+    }
+    F.n = (uint32_t)n_points[i]; F.stride = (uint32_t)stride; F.ioff = (uint32_t)ioff; F.roff = (uint32_t)roff;
+    F.cap1 = (uint32_t)cap1[(size_t)i]; F.base1 = (uint32_t)base1[(size_t)i]; F.base2 = (uint32_t)base2[(size_t)i];
+    F.col_ind = S->col_ind; F.range = S->range; F.cloud = S->cloud; F.curv = S->curv; F.picked = S->picked; F.label = S->label; F.smooth = S->smooth;
+    F.start = S->start; F.end = S->end; F.picked_occ = S->picked_occ; F.corner_scan = S->corner_scan; F.surf_scan = S->surf_scan; F.out = S->out;
+    F.src = src[(size_t)i];
+    F.owner = reinterpret_cast<uint32_t*>(ws + Lw.o_owner) + (size_t)i * cap;
+    F.rowcnt = reinterpret_cast<uint32_t*>(ws + Lw.o_rowcnt) + (size_t)i * q.n_scan;
+    F.roff_arr = reinterpret_cast<uint32_t*>(ws + Lw.o_roff) + (size_t)i * (q.n_scan + 1);
+    F.member = reinterpret_cast<int32_t*>(ws + Lw.o_member) + (size_t)i * cap;
+    F.cpick = reinterpret_cast<int32_t*>(ws + Lw.o_cpick) + (size_t)i * ncs;
+    F.ccnt = reinterpret_cast<int32_t*>(ws + Lw.o_ccnt) + (size_t)i * q.n_scan;
+    F.info = S0->d_info + i;
+    maxn = std::max<uint32_t>(maxn, F.n);
+  }
+  LFCK(c0, hipMemcpyAsync(S0->d_fr, S0->h_fr, sizeof(LfFrame) * (size_t)B, hipMemcpyHostToDevice, st));
+  const LfFrame* d_fr = S0->d_fr;
+  const unsigned gcap = (unsigned)((std::max<size_t>(cap, (size_t)q.n_scan) + 255) / 256);
+  k_lf_clear<<<dim3(gcap, B), 256, 0, st>>>(d_fr, P);
+  k_lf_project<<<dim3((maxn + 255) / 256, B), 256, 0, st>>>(d_fr, P);
+  k_lf_rowcount<<<dim3(q.n_scan, B), 256, 0, st>>>(d_fr, P);
+  k_lf_rings<<<B, 256, 0, st>>>(d_fr, P);
+  k_lf_extract<<<dim3(q.n_scan, B), 256, 0, st>>>(d_fr, P);
+  const unsigned g1 = (max1 + 255) / 256;
+  k_lf_smooth<<<dim3(g1, B), 256, 0, st>>>(d_fr, P);
+  k_lf_occlude<<<dim3(g1, B), 256, 0, st>>>(d_fr, P);
+  k_lf_snapshot<<<dim3(g1, B), 256, 0, st>>>(d_fr, P);
+  k_lf_select<true><<<dim3(1, B), 64, lds, st>>>(d_fr, P);
+  k_lf_select<false><<<dim3(q.n_scan, B), 64, lds, st>>>(d_fr, P);
+  k_lf_corner_compact<<<B, 256, 0, st>>>(d_fr, P);
+  LFCK(c0, hipGetLastError());
+  float4* cells1 = reinterpret_cast<float4*>(ws + Lw.o_cells1);
+  float4* cells2 = reinterpret_cast<float4*>(ws + Lw.o_cells2);
+  if ((rc = run_vg(c0, st, 1, d_fr, P, B, max1, (uint32_t)N1, (uint32_t)(B * q.n_scan), ws, Lw, cells1, cells1)) != PCM_OK) return rc;
+  const uint32_t size2 = (uint32_t)(ncs + max1);
+  if ((rc = run_vg(c0, st, 2, d_fr, P, B, size2, (uint32_t)N2, (uint32_t)(2 * B), ws, Lw, cells1, cells2)) != PCM_OK) return rc;
+  k_lf_finish<<<dim3((size2 + 255) / 256, B), 256, 0, st>>>(d_fr, P, cells1, cells2);
+  LFCK(c0, hipGetLastError());
+  LFCK(c0, hipMemcpyAsync(S0->h_info, S0->d_info, sizeof(LfInfo) * (size_t)B, hipMemcpyDeviceToHost, st));
+  LFCK(c0, hipStreamSynchronize(st));
+  int worst = PCM_OK;
+  for (int i = 0; i < B; i++) {
+    const LfInfo& I = S0->h_info[i];
+    FeatState* S = fe_of(ctxs[i]);
+    S->last = I;
+    S->have_last = true;
+    pcm_loam_features_result& r = results[i];
+    std::memset(&r, 0, sizeof(r));
+    r.num_extracted = (int32_t)I.count;
+    r.num_corner_scan = (int32_t)I.n_corner_scan;
+    r.num_surf_scan = (int32_t)I.n_surf_scan;
+    r.num_corner = (int32_t)I.n_corner;
+    r.num_surf = (int32_t)I.n_surf;
+    r.sectors = (int32_t)I.sectors;
+    r.sectors_serial = (int32_t)I.sectors_serial;
+    r.status = PCM_OK;
+    if (I.bad_sector) { r.status = PCM_ERR_INTERNAL; ctxs[i]->err = "a sector exceeded the sort buffer"; }
+    else if (I.overflow) { r.status = PCM_ERR_OUT_OF_RANGE; ctxs[i]->err = "leaf size too small for the extent of the cloud (index overflow)"; }
+    if (r.status == PCM_OK && to_source) loam::loam_source_commit(ctxs[i], I.n_corner, I.n_surf);
+    if (r.status != PCM_OK && worst == PCM_OK) { worst = r.status; if (ctxs[i] != c0) c0->err = ctxs[i]->err; }
+  }
+  return worst;
+}
+
+void copy_xyzi(const float4* d, size_t n, float* host) { for (size_t i = 0; i < n; i++) { host[4 * i] = d[i].x; host[4 * i + 1] = d[i].y; host[4 * i + 2] = d[i].z; host[4 * i + 3] = d[i].w; } }
+
+}  // namespace
+
+namespace pcm {
+void loam_features_release(pcm_ctx* c) {
+  FeatState* S = static_cast<FeatState*>(c->loam_fe);
+  if (!S) return;
+  S->release();
+  delete S;
+  c->loam_fe = nullptr;
+}
+}  // namespace pcm
+
+extern "C" {
+
+void pcm_loam_default_feature_params(pcm_loam_feature_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->n_scan = 16;                 // utility.h:241
+  p->horizon_scan = 1800;         // :242
+  p->downsample_rate = 1;         // :244
+  p->area_num = 6;                // :252
+  p->min_range = 1.0f;            // :223
+  p->max_range = 150.0f;          // :224
+  p->edge_threshold = 0.1f;       // :265
+  p->surf_threshold = 0.1f;       // :266
+  p->odometry_surf_leaf = 0.2f;   // :270
+  p->mapping_corner_leaf = 0.2f;  // :271
+  p->mapping_surf_leaf = 0.2f;    // :272
+}
+
+int pcm_loam_extract_features(pcm_ctx* c, const void* points, size_t n, size_t stride_bytes, size_t intensity_offset_bytes, size_t ring_offset_bytes, int memory,
+                              const pcm_loam_feature_params* params, float* corner, size_t cap_corner, float* surf, size_t cap_surf, pcm_loam_features_result* res) {
+  if (!c || !res) return PCM_ERR_INVALID_ARGUMENT;
+  pcm_ctx* arr[1] = {c};
+  const void* pts[1] = {points};
+  size_t ns[1] = {n};
+  int rc = run_frames(arr, 1, pts, ns, stride_bytes, intensity_offset_bytes, ring_offset_bytes, memory, params, false, res);
+  if (rc != PCM_OK) return rc;
+  const size_t nc = (size_t)res->num_corner, nsf = (size_t)res->num_surf;
+  if ((nc && !corner) || (nsf && !surf) || nc > cap_corner || nsf > cap_surf) { c->err = "output capacity too small (counts are in the result)"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (nc + nsf == 0) return PCM_OK;
+  std::vector<float4> h(nc + nsf);
+  FeatState* S = fe_of(c);
+  LFCK(c, hipMemcpyAsync(h.data(), S->out, sizeof(float4) * h.size(), hipMemcpyDeviceToHost, c->stream));
+  LFCK(c, hipStreamSynchronize(c->stream));
+  copy_xyzi(h.data(), nc, corner);
+  copy_xyzi(h.data() + nc, nsf, surf);
+  return PCM_OK;
+}
+
+int pcm_loam_frame_begin(pcm_ctx* c, const void* points, size_t n, size_t stride_bytes, size_t intensity_offset_bytes, size_t ring_offset_bytes, int memory,
+                         const pcm_loam_feature_params* params, pcm_loam_features_result* res) {
+  pcm_ctx* arr[1] = {c};
+  const void* pts[1] = {points};
+  size_t ns[1] = {n};
+  return run_frames(arr, 1, pts, ns, stride_bytes, intensity_offset_bytes, ring_offset_bytes, memory, params, true, res);
+}
+
+int pcm_loam_frame_begin_batch(pcm_ctx* const* ctxs, int n, const void* const* points, const size_t* n_points, size_t stride_bytes, size_t intensity_offset_bytes,
+                               size_t ring_offset_bytes, int memory, const pcm_loam_feature_params* params, pcm_loam_features_result* results) {
+  return run_frames(ctxs, n, points, n_points, stride_bytes, intensity_offset_bytes, ring_offset_bytes, memory, params, true, results);
+}
+
+int pcm_loam_feature_info(pcm_ctx* c, int32_t counts[4], int32_t* start_ring, int32_t* end_ring, int32_t* col_ind, float* range, float* cloud, float* curvature,
+                          int32_t* neighbor_picked, int32_t* label, float* corner_scan, float* surf_scan) {
+  int rc = check_ctx_fe(c);
+  if (rc != PCM_OK) return rc;
+  FeatState* S = fe_of(c);
+  if (!S->have_last) { c->err = "no frame has run through the front end of this context"; return PCM_ERR_NO_INPUT; }
+  LFCK(c, hipSetDevice(c->device));
+  const size_t n = S->last.count, ns = (size_t)S->n_scan, nc = S->last.n_corner_scan, nss = S->last.n_surf_scan;
+  if (counts) { counts[0] = (int32_t)n; counts[1] = (int32_t)nc; counts[2] = (int32_t)nss; counts[3] = (int32_t)ns; }
+  LFCK(c, hipStreamSynchronize(c->stream));
+  if (start_ring) LFCK(c, hipMemcpy(start_ring, S->start, 4 * ns, hipMemcpyDeviceToHost));
+  if (end_ring) LFCK(c, hipMemcpy(end_ring, S->end, 4 * ns, hipMemcpyDeviceToHost));
+  if (col_ind && n) LFCK(c, hipMemcpy(col_ind, S->col_ind, 4 * n, hipMemcpyDeviceToHost));
+  if (range && n) LFCK(c, hipMemcpy(range, S->range, 4 * n, hipMemcpyDeviceToHost));
+  if (cloud && n) LFCK(c, hipMemcpy(cloud, S->cloud, 16 * n, hipMemcpyDeviceToHost));
+  if (curvature && n) LFCK(c, hipMemcpy(curvature, S->curv, 4 * n, hipMemcpyDeviceToHost));
+  if (neighbor_picked && n) LFCK(c, hipMemcpy(neighbor_picked, S->picked_occ, 4 * n, hipMemcpyDeviceToHost));
+  if (label && n) LFCK(c, hipMemcpy(label, S->label, 4 * n, hipMemcpyDeviceToHost));
+  if (corner_scan && nc) LFCK(c, hipMemcpy(corner_scan, S->corner_scan, 16 * nc, hipMemcpyDeviceToHost));
+  if (surf_scan && nss) LFCK(c, hipMemcpy(surf_scan, S->surf_scan, 16 * nss, hipMemcpyDeviceToHost));
+  return PCM_OK;
+}
+
+}  // extern "C"

@@ -174,6 +174,8 @@ void launch_init_states(hipStream_t stream, PairState* d_states, const float* d_
 void launch_pack_results(hipStream_t stream, const PairState* d_states, pcm_result* d_results, int npairs);
 // loam_api.hip: the maps, scan and device state of a PCM_MODEL_LOAM context (pcm_ctx::loam)
 void loam_release(pcm_ctx* c);
+// loam_features.hip: the front end's cross-frame state of a PCM_MODEL_LOAM context (pcm_ctx::loam_fe)
+void loam_features_release(pcm_ctx* c);
 
 }  // namespace pcm
 
@@ -240,5 +242,6 @@ struct pcm_ctx {
   size_t bfgs_idx_cap = 0;
   double* bfgs_host = nullptr; // pinned, device-visible: the 14 sums land here without a copy command
   void* loam = nullptr;   // PCM_MODEL_LOAM: maps, features and device state (loam_api.hip)
+  void* loam_fe = nullptr;   // PCM_MODEL_LOAM: the front end's cross-frame state and last-frame outputs (loam_features.hip)
   int profiling = 0;  // bit0: HIP-event timing of residual launches, bit1: kNN counters
 };

@@ -582,3 +582,137 @@ def loam_align_batch(regs, x6s, **params):
     if rc not in (capi.PCM_OK, capi.PCM_ERR_TOO_FEW_FEATURES):
         raise capi.PcmError(rc, (L.pcm_last_error(regs[0].handle) or b"").decode())
     return [_loam_result(out[i]) for i in range(n)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# LOAM front end: imageProjection + featureExtraction + downsampleCurrentScan on the device
+# ---------------------------------------------------------------------------------------------------------------------------
+XYZIRT_STRIDE, XYZIRT_INTENSITY, XYZIRT_RING = 48, 16, 32   # PointXYZIRT (imageProjection.cpp:7-19)
+
+
+def pack_xyzirt(xyz, intensity=None, ring=None, timestamp=None) -> np.ndarray:
+    """48-byte PointXYZIRT records as an (N, 48) uint8 array: x y z floats at 0, uint8 intensity at 16, double timestamp at 24
+    (never read), uint16 ring at 32."""
+    xyz = np.asarray(xyz, dtype=np.float32).reshape(-1, 3)
+    n = xyz.shape[0]
+    rec = np.zeros((n, XYZIRT_STRIDE), np.uint8)
+    rec[:, 0:12] = np.ascontiguousarray(xyz).view(np.uint8).reshape(n, 12)
+    if intensity is not None:
+        rec[:, XYZIRT_INTENSITY] = np.asarray(intensity).astype(np.uint8).reshape(n)
+    if timestamp is not None:
+        rec[:, 24:32] = np.ascontiguousarray(np.asarray(timestamp, np.float64).reshape(n)).view(np.uint8).reshape(n, 8)
+    if ring is not None:
+        rec[:, XYZIRT_RING:XYZIRT_RING + 2] = np.ascontiguousarray(np.asarray(ring).astype(np.uint16).reshape(n)).view(np.uint8).reshape(n, 2)
+    return rec
+
+
+def _scan_arg(cloud, stride):
+    """(pointer, n, memory, keep-alive) of ring-tagged records: a host array or a device tensor of n x stride bytes."""
+    if hasattr(cloud, "data_ptr") and getattr(cloud, "is_cuda", False):
+        if not cloud.is_contiguous():
+            raise ValueError("device scans must be contiguous")
+        nbytes = cloud.numel() * cloud.element_size()
+        if nbytes % stride:
+            raise ValueError("device scan size is not a multiple of the record stride")
+        return cloud.data_ptr(), nbytes // stride, capi.MEM_DEVICE, cloud
+    a = np.ascontiguousarray(cloud)
+    if a.nbytes % stride:
+        raise ValueError("scan size is not a multiple of the record stride")
+    return a.ctypes.data, a.nbytes // stride, capi.MEM_HOST, a
+
+
+def _feature_params(L, params: dict) -> capi.PcmLoamFeatureParams:
+    p = capi.PcmLoamFeatureParams()
+    L.pcm_loam_default_feature_params(C.byref(p))
+    for k, v in params.items():
+        if k == "force_serial_sort":
+            p.flags = (p.flags | capi.PCM_LOAM_FEATURES_FORCE_SERIAL_SORT) if v else (p.flags & ~capi.PCM_LOAM_FEATURES_FORCE_SERIAL_SORT)
+            continue
+        if k.startswith("reserved") or not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+_FEATURE_LAYOUT = ("stride", "intensity_offset", "ring_offset")
+
+
+def _split_layout(params: dict):
+    lay = (params.pop("stride", XYZIRT_STRIDE), params.pop("intensity_offset", XYZIRT_INTENSITY), params.pop("ring_offset", XYZIRT_RING))
+    return lay, params
+
+
+def _features_result(r: capi.PcmLoamFeaturesResult) -> dict:
+    return {k: getattr(r, k) for k, _ in r._fields_ if k != "reserved"}
+
+
+def _loam_set_input_scan(self, cloud, **feature_params) -> dict:
+    """featureExtraction + downsampleCurrentScan of one ring-tagged scan into this context's LOAM source, on the device
+    (pcm_loam_frame_begin).  Then ``scan2map`` as after ``set_input_source``."""
+    (stride, ioff, roff), fp = _split_layout(dict(feature_params))
+    p = _feature_params(self._L, fp)
+    ptr, n, mem, keep = _scan_arg(cloud, stride)
+    r = capi.PcmLoamFeaturesResult()
+    self._check(self._L.pcm_loam_frame_begin(self._h, ptr, n, stride, ioff, roff, mem, C.byref(p), C.byref(r)))
+    del keep
+    self.n_corner, self.n_surf = r.num_corner, r.num_surf
+    return _features_result(r)
+
+
+def _loam_feature_info(self) -> dict:
+    """Parity hook: the last frame's intermediate arrays (pcm_loam_feature_info)."""
+    cnt = np.zeros(4, np.int32)
+    self._check(self._L.pcm_loam_feature_info(self._h, cnt.ctypes.data, *([None] * 10)))
+    n, nc, ns, nsc = (int(v) for v in cnt)
+    out = {"start": np.zeros(nsc, np.int32), "end": np.zeros(nsc, np.int32), "col_ind": np.zeros(n, np.int32), "range": np.zeros(n, np.float32),
+           "cloud": np.zeros((n, 4), np.float32), "curvature": np.zeros(n, np.float32), "neighbor_picked": np.zeros(n, np.int32),
+           "label": np.zeros(n, np.int32), "corner_scan": np.zeros((nc, 4), np.float32), "surf_scan": np.zeros((ns, 4), np.float32)}
+    self._check(self._L.pcm_loam_feature_info(self._h, cnt.ctypes.data, *(out[k].ctypes.data for k in
+                                              ("start", "end", "col_ind", "range", "cloud", "curvature", "neighbor_picked", "label", "corner_scan", "surf_scan"))))
+    return out
+
+
+LoamRegistration.set_input_scan = _loam_set_input_scan
+LoamRegistration.feature_info = _loam_feature_info
+
+
+def loam_extract_features(reg: LoamRegistration, cloud, **feature_params):
+    """One scan to (corner (Nc,4), surf (Ns,4), info): laserCloudCornerLastDS / laserCloudSurfLastDS as (x, y, z, intensity) on
+    the host (pcm_loam_extract_features; the context's LOAM source is left as it is, its cross-frame state advances)."""
+    (stride, ioff, roff), fp = _split_layout(dict(feature_params))
+    p = _feature_params(reg._L, fp)
+    ptr, n, mem, keep = _scan_arg(cloud, stride)
+    r = capi.PcmLoamFeaturesResult()
+    cap = max(1, n)
+    corner = np.zeros((cap, 4), np.float32)
+    surf = np.zeros((cap, 4), np.float32)
+    reg._check(reg._L.pcm_loam_extract_features(reg.handle, ptr, n, stride, ioff, roff, mem, C.byref(p), corner.ctypes.data, cap,
+                                                surf.ctypes.data, cap, C.byref(r)))
+    del keep
+    info = _features_result(r)
+    return corner[:r.num_corner].copy(), surf[:r.num_surf].copy(), info
+
+
+def loam_frame_begin_batch(regs, clouds, **feature_params):
+    """pcm_loam_frame_begin of n scans into n LoamRegistration contexts in one set of launches; returns n result dicts."""
+    (stride, ioff, roff), fp = _split_layout(dict(feature_params))
+    L = capi.load_library()
+    p = _feature_params(L, fp)
+    n = len(regs)
+    if len(clouds) != n:
+        raise ValueError("one scan per context")
+    args = [_scan_arg(c, stride) for c in clouds]
+    mems = {a[2] for a in args}
+    if len(mems) != 1:
+        raise ValueError("all scans of a batch must be host arrays or all device tensors")
+    hs = (C.c_void_p * n)(*[r.handle for r in regs])
+    ptrs = (C.c_void_p * n)(*[a[0] for a in args])
+    ns = (C.c_size_t * n)(*[a[1] for a in args])
+    out = (capi.PcmLoamFeaturesResult * n)()
+    rc = L.pcm_loam_frame_begin_batch(hs, n, ptrs, ns, stride, ioff, roff, mems.pop(), C.byref(p), out)
+    if rc != capi.PCM_OK:
+        raise capi.PcmError(rc, (L.pcm_last_error(regs[0].handle) or b"").decode())
+    res = [_features_result(out[i]) for i in range(n)]
+    for reg, r in zip(regs, res):
+        reg.n_corner, reg.n_surf = r["num_corner"], r["num_surf"]
+    return res
