@@ -502,6 +502,68 @@ int pcm_loam_frame_begin_batch(pcm_ctx *const *ctxs, int n, const void *const *p
 int pcm_loam_feature_info(pcm_ctx *ctx, int32_t counts[4], int32_t *start_ring, int32_t *end_ring, int32_t *col_ind, float *range, float *cloud,
                           float *curvature, int32_t *neighbor_picked, int32_t *label, float *corner_scan, float *surf_scan);
 
+/*
+ * LOAM key-frame store and surrounding-key-frame submap of jueying_slam on the device: saveKeyFramesAndFactor's clouds
+ * (mapOptmization.cpp:1779-1846), correctPoses (:1886-1917), extractSurroundingKeyFrames (:1153-1230) and loopFindNearKeyframes
+ * (:972-1018).  A PCM_MODEL_LOAM context keeps every key frame's corner / surf cloud (body frame, PointXYZI) and pose on the
+ * device; pcm_loam_submap_update selects the key frames as the reference does, transforms, concatenates and down-samples their
+ * clouds and makes the result the context's LOAM target, so a mapping frame is
+ *   pcm_loam_frame_begin -> pcm_loam_submap_update -> pcm_loam_align -> pcm_loam_keyframe_add
+ * with the scan as the only bulk upload.  DESIGN.md section 11.
+ */
+typedef struct pcm_loam_submap_params {
+  float search_radius;           /* 50.0  utility.h:282 surroundingKeyframeSearchRadius */
+  float keypose_density;         /* 1.0   utility.h:283 surroundingKeyframeDensity: leaf of the VoxelGrid over the key poses, > 0 */
+  float corner_leaf;             /* 0.2   utility.h:271 mappingCornerLeafSize; 0 = no down-sampling */
+  float surf_leaf;               /* 0.2   utility.h:272 mappingSurfLeafSize; 0 = no down-sampling */
+  double recent_window_s;        /* 10.0  mapOptmization.cpp:1174: key frames younger than this are always taken */
+  int32_t reserved[8];
+} pcm_loam_submap_params;
+
+typedef struct pcm_loam_submap_result {
+  int32_t num_keyframes;         /* K */
+  int32_t num_near;              /* key poses inside the radius of the last one */
+  int32_t num_pose_leaves;       /* leaves of the VoxelGrid over them */
+  int32_t num_selected;          /* list entries used (a key frame may be used more than once) */
+  int32_t num_skipped;           /* list entries farther than the radius from the last key pose */
+  int32_t num_corner_in;         /* points of the concatenated clouds, before the VoxelGrids */
+  int32_t num_surf_in;
+  int32_t num_corner_map;        /* laserCloudCornerFromMapDS / laserCloudSurfFromMapDS */
+  int32_t num_surf_map;
+  int32_t rebuilt;               /* 0: selection, poses and leaves equal those of the last update: nothing done on the device */
+  int32_t status;                /* PCM_OK, PCM_ERR_OUT_OF_RANGE (VoxelGrid index overflow) */
+  int32_t reserved[5];
+} pcm_loam_submap_result;
+
+void pcm_loam_default_submap_params(pcm_loam_submap_params *params);
+/* saveKeyFramesAndFactor: key frame K gets pose6 (roll, pitch, yaw, x, y, z, as pcm_loam_align), time and the two clouds (records
+ * of stride_bytes, x y z first, intensity the fourth float when stride_bytes >= 16, else 0).  corner == NULL and surf == NULL:
+ * the context's current LOAM source is copied on the device (after pcm_loam_frame_begin with the features' averaged intensity,
+ * after pcm_loam_set_source with the records' fourth float).  Returns PCM_OK; pcm_loam_keyframe_count gives the new K.
+ * The fourth float is read as it lies in memory: a pcl::PointXYZI buffer must NOT be passed as it is (its fourth float is the
+ * padding of the xyz block, the intensity sits at byte 16 of 32); repack to (x, y, z, intensity) records first, as
+ * pcm_amd::LoamKeyFrameMap and LoamScanToMap::setInputFeatures do.  The same holds for pcm_loam_set_source when key frames are
+ * to be taken from the source. */
+int pcm_loam_keyframe_add(pcm_ctx *ctx, const float pose6[6], double time, const void *corner, size_t n_corner, const void *surf, size_t n_surf,
+                          size_t stride_bytes, int memory);
+/* correctPoses: key frames first .. first + n - 1 get new poses (n x 6 floats); their times and clouds stay */
+int pcm_loam_keyframe_set_poses(pcm_ctx *ctx, int first, int n, const float *pose6);
+int pcm_loam_keyframe_count(pcm_ctx *ctx);   /* K, or a negative pcm_status */
+int pcm_loam_keyframe_clear(pcm_ctx *ctx);
+/* one stored key frame as host PointXYZI records (body frame); capacities in points; the counts are always set, and
+ * PCM_ERR_INVALID_ARGUMENT is returned when a capacity is too small (corner / surf may be NULL with capacity 0 to ask for them) */
+int pcm_loam_keyframe_get(pcm_ctx *ctx, int key, float *corner, size_t cap_corner, float *surf, size_t cap_surf, size_t *n_corner, size_t *n_surf);
+/* extractSurroundingKeyFrames at timeLaserInfoCur = time_cur: the result becomes the context's LOAM target (the caller index of a
+ * map point is its position in the down-sampled cloud).  params NULL = defaults.  No key frame yet: PCM_OK, nothing done. */
+int pcm_loam_submap_update(pcm_ctx *ctx, const pcm_loam_submap_params *params, double time_cur, pcm_loam_submap_result *result);
+/* loopFindNearKeyframes (wrt_key < 0: every key frame under its own pose) / loopFindNearKeyframesWithRespectTo (all under the pose
+ * of wrt_key): key frames key - search_num .. key + search_num inside [0, K), corner then surf of each, one VoxelGrid(leaf)
+ * (0 = none); host PointXYZI out, capacity in points, *n_out always set.  The context's target is not touched. */
+int pcm_loam_submap_near(pcm_ctx *ctx, int key, int search_num, int wrt_key, float leaf, float *out, size_t cap, size_t *n_out);
+/* parity hook: the last update's selection (key frame per used entry: num_selected int32) and its clouds before (concatenated,
+ * transformed: num_*_in x 4 floats) and after the VoxelGrids (num_*_map x 4 floats).  Any pointer may be NULL. */
+int pcm_loam_submap_info(pcm_ctx *ctx, int32_t *keys, float *corner_in, float *surf_in, float *corner_map, float *surf_map);
+
 /* profiling flags: bit0 = bracket every residual launch with HIP events on the
  * launch stream (pcm_stats.linearize_ms); bit1 = collect the kNN candidate /
  * probe counters (slower kernel variant; use in an untimed pass); bit2 = in-kernel

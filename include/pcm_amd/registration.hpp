@@ -319,6 +319,23 @@ protected:
   double trans_probability_ = 0.0;
 };
 
+namespace detail {
+// A PCL point is not a packed (x, y, z, intensity) record: pcl::PointXYZI keeps the padding of its xyz block as the fourth float
+// and the intensity at byte 16.  The LOAM feature and key-frame calls read the fourth float of a record as its intensity, so the
+// adapters repack member by member; a point type without an intensity member packs 0.
+template <typename P> auto intensity_of(const P& p, int) -> decltype(static_cast<float>(p.intensity)) { return static_cast<float>(p.intensity); }
+template <typename P> float intensity_of(const P&, long) { return 0.0f; }
+template <typename CloudT>
+void pack_xyzi(const CloudT& cloud, std::vector<float>& buf) {
+  const size_t n = cloud.points.size();
+  buf.resize(4 * n);
+  for (size_t i = 0; i < n; i++) {
+    const auto& q = cloud.points[i];
+    buf[4 * i] = q.x; buf[4 * i + 1] = q.y; buf[4 * i + 2] = q.z; buf[4 * i + 3] = intensity_of(q, 0);
+  }
+}
+}  // namespace detail
+
 // jueying_slam's LOAM edge / plane scan-to-map optimisation with the call shape of mapOptmization.cpp:1560-1586:
 //     loam.setInputMaps(laserCloudCornerFromMapDS, laserCloudSurfFromMapDS);   // replaces the two kdtree setInputCloud calls
 //     loam.setInputFeatures(laserCloudCornerLastDS, laserCloudSurfLastDS);
@@ -353,8 +370,11 @@ public:
     check(pcm_loam_set_target(ctx_, corner->points.data(), corner->size(), surf->points.data(), surf->size(), sizeof(PointT), PCM_MEM_HOST, tag),
           "pcm_loam_set_target");
   }
+  // packed member by member (x, y, z, intensity): a key frame saved from this source keeps the points' intensity
   void setInputFeatures(const CloudConstPtr& corner, const CloudConstPtr& surf) {
-    check(pcm_loam_set_source(ctx_, corner->points.data(), corner->size(), surf->points.data(), surf->size(), sizeof(PointT), PCM_MEM_HOST, 0),
+    detail::pack_xyzi(*corner, corner_xyzi_);
+    detail::pack_xyzi(*surf, surf_xyzi_);
+    check(pcm_loam_set_source(ctx_, corner_xyzi_.data(), corner->size(), surf_xyzi_.data(), surf->size(), 4 * sizeof(float), PCM_MEM_HOST, 0),
           "pcm_loam_set_source");
   }
   // imageProjection + featureExtraction + downsampleCurrentScan of one ring-tagged scan (PointXYZIRT-like: x y z, intensity, ring
@@ -383,6 +403,7 @@ public:
   double surfFitnessScore() const { return last_.surf_fitness; }       // Surf_fitness_score
   int iterations() const { return last_.iterations; }
   const pcm_loam_result& result() const { return last_; }
+  pcm_ctx* context() const { return ctx_; }   // for LoamKeyFrameMap, which works on the same context
 
 private:
   void check(int rc, const char* what) const {
@@ -392,6 +413,90 @@ private:
   pcm_loam_params params_;
   pcm_loam_result last_{};
   pcm_loam_features_result features_{};
+  std::vector<float> corner_xyzi_, surf_xyzi_;
+};
+
+// jueying_slam's key-frame clouds and surrounding-key-frame submap on the device, on the context of a LoamScanToMap, with the
+// call shape of mapOptmization.cpp:
+//     pcm_amd::LoamKeyFrameMap<PointType> keyframes(loam);                   // cornerCloudKeyFrames / surfCloudKeyFrames / cloudKeyPoses6D
+//     keyframes.extractSurroundingKeyFrames(timeLaserInfoCur);               // :1224; the result is loam's maps (no setInputMaps)
+//     if (loam.scan2MapOptimization(transformTobeMapped)) transformUpdate();
+//     keyframes.saveKeyFrame(transformTobeMapped, timeLaserInfoCur);         // :1839-1840 after setInputScan: the features stay on the device
+//     keyframes.correctPoses(poses, n);                                      // :1886-1917 after a loop closure
+//     keyframes.loopFindNearKeyframes(cureKeyframeCloud, loopKeyCur, 0);     // :972
+//     keyframes.loopFindNearKeyframesWithRespectTo(prevKeyframeCloud, loopKeyPre, historyKeyframeSearchNum, loopKeyCur);
+// Poses are transformTobeMapped vectors (roll, pitch, yaw, x, y, z).  The object does not own the context: it must not outlive `loam`.
+template <typename PointT>
+class LoamKeyFrameMap {
+public:
+  using Cloud = pcl::PointCloud<PointT>;
+  using CloudConstPtr = typename Cloud::ConstPtr;
+
+  explicit LoamKeyFrameMap(LoamScanToMap<PointT>& loam) : ctx_(loam.context()) { pcm_loam_default_submap_params(&params_); }
+
+  void setSurroundingKeyframeSearchRadius(float v) { params_.search_radius = v; }   // surroundingKeyframeSearchRadius
+  void setSurroundingKeyframeDensity(float v) { params_.keypose_density = v; }      // surroundingKeyframeDensity
+  void setMappingCornerLeafSize(float v) { params_.corner_leaf = v; }               // mappingCornerLeafSize
+  void setMappingSurfLeafSize(float v) { params_.surf_leaf = v; }                   // mappingSurfLeafSize
+  void setLoopLeafSize(float v) { loop_leaf_ = v; }                                 // downSizeFilterICP (mappingSurfLeafSize)
+  pcm_loam_submap_params& params() { return params_; }
+  const pcm_loam_submap_result& result() const { return last_; }
+  int size() const { return pcm_loam_keyframe_count(ctx_); }                        // cloudKeyPoses3D->size()
+
+  // the scan the context holds (LoamScanToMap::setInputScan / setInputFeatures) becomes key frame size()
+  void saveKeyFrame(const float pose[6], double time) {
+    check(pcm_loam_keyframe_add(ctx_, pose, time, nullptr, 0, nullptr, 0, sizeof(PointT), PCM_MEM_HOST), "pcm_loam_keyframe_add");
+  }
+  void saveKeyFrame(const float pose[6], double time, const CloudConstPtr& corner, const CloudConstPtr& surf) {
+    detail::pack_xyzi(*corner, buf_);
+    detail::pack_xyzi(*surf, buf2_);
+    check(pcm_loam_keyframe_add(ctx_, pose, time, buf_.data(), corner->size(), buf2_.data(), surf->size(), 4 * sizeof(float), PCM_MEM_HOST),
+          "pcm_loam_keyframe_add");
+  }
+  // n x 6 floats for key frames 0 .. n - 1
+  void correctPoses(const float* poses, int n) { check(pcm_loam_keyframe_set_poses(ctx_, 0, n, poses), "pcm_loam_keyframe_set_poses"); }
+  void clear() { check(pcm_loam_keyframe_clear(ctx_), "pcm_loam_keyframe_clear"); }
+
+  // true: the maps were rebuilt; false: nothing changed since the last call (or there is no key frame yet)
+  bool extractSurroundingKeyFrames(double timeLaserInfoCur) {
+    check(pcm_loam_submap_update(ctx_, &params_, timeLaserInfoCur, &last_), "pcm_loam_submap_update");
+    return last_.rebuilt != 0;
+  }
+  int laserCloudCornerFromMapDSNum() const { return last_.num_corner_map; }
+  int laserCloudSurfFromMapDSNum() const { return last_.num_surf_map; }
+
+  void loopFindNearKeyframes(Cloud& nearKeyframes, int key, int searchNum) { near(nearKeyframes, key, searchNum, -1); }
+  void loopFindNearKeyframesWithRespectTo(Cloud& nearKeyframes, int key, int searchNum, int wrtKey) { near(nearKeyframes, key, searchNum, wrtKey); }
+
+private:
+  void near(Cloud& out, int key, int searchNum, int wrt) {
+    // room for every point of the key frames in the window (the VoxelGrid can only shrink it), from the stored counts
+    const int K = size();
+    size_t total = 0;
+    for (long long k = (long long)key - searchNum; k <= (long long)key + searchNum; ++k) {
+      if (k < 0 || k >= K) continue;
+      size_t nc = 0, ns = 0;
+      check(pcm_loam_keyframe_get(ctx_, (int)k, nullptr, 0, nullptr, 0, &nc, &ns), "pcm_loam_keyframe_get");
+      total += nc + ns;
+    }
+    if (buf_.size() < 4 * total) buf_.resize(4 * total);
+    size_t n = 0;
+    const int rc = pcm_loam_submap_near(ctx_, key, searchNum, wrt, loop_leaf_, buf_.data(), buf_.size() / 4, &n);
+    check(rc, "pcm_loam_submap_near");
+    out.points.resize(n);
+    for (size_t i = 0; i < n; i++) {
+      PointT& q = out.points[i];
+      q.x = buf_[4 * i]; q.y = buf_[4 * i + 1]; q.z = buf_[4 * i + 2]; q.intensity = buf_[4 * i + 3];
+    }
+  }
+  void check(int rc, const char* what) const {
+    if (rc != PCM_OK) throw std::runtime_error(std::string(what) + ": " + pcm_last_error(ctx_));
+  }
+  pcm_ctx* ctx_ = nullptr;
+  pcm_loam_submap_params params_;
+  pcm_loam_submap_result last_{};
+  float loop_leaf_ = 0.2f;
+  std::vector<float> buf_, buf2_;
 };
 
 // jueying_slam's LOAM front end (imageProjection.cpp:736-823, featureExtraction.cpp:84-247, mapOptmization.cpp:1232-1247) on the

@@ -19,6 +19,8 @@ SYMBOLS = [
     "pcm_loam_coefficients", "pcm_loam_neighbours",
     "pcm_loam_default_feature_params", "pcm_loam_extract_features", "pcm_loam_frame_begin", "pcm_loam_frame_begin_batch",
     "pcm_loam_feature_info",
+    "pcm_loam_default_submap_params", "pcm_loam_keyframe_add", "pcm_loam_keyframe_set_poses", "pcm_loam_keyframe_count", "pcm_loam_keyframe_clear",
+    "pcm_loam_keyframe_get", "pcm_loam_submap_update", "pcm_loam_submap_near", "pcm_loam_submap_info",
 ]
 
 PCM_ABI_VERSION = 3   # include/pcm_amd.h
@@ -112,6 +114,17 @@ class PcmLoamFeaturesResult(C.Structure):
     _fields_ = [("num_extracted", C.c_int32), ("num_corner_scan", C.c_int32), ("num_surf_scan", C.c_int32), ("num_corner", C.c_int32),
                 ("num_surf", C.c_int32), ("sectors", C.c_int32), ("sectors_serial", C.c_int32), ("status", C.c_int32),
                 ("reserved", C.c_int32 * 8)]
+
+
+class PcmLoamSubmapParams(C.Structure):
+    _fields_ = [("search_radius", C.c_float), ("keypose_density", C.c_float), ("corner_leaf", C.c_float), ("surf_leaf", C.c_float),
+                ("recent_window_s", C.c_double), ("reserved", C.c_int32 * 8)]
+
+
+class PcmLoamSubmapResult(C.Structure):
+    _fields_ = [("num_keyframes", C.c_int32), ("num_near", C.c_int32), ("num_pose_leaves", C.c_int32), ("num_selected", C.c_int32),
+                ("num_skipped", C.c_int32), ("num_corner_in", C.c_int32), ("num_surf_in", C.c_int32), ("num_corner_map", C.c_int32),
+                ("num_surf_map", C.c_int32), ("rebuilt", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
 def library_path() -> str:
@@ -208,5 +221,15 @@ def load_library():
     L.pcm_loam_frame_begin_batch.argtypes = [C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(sz), sz, sz, sz, i32, C.POINTER(PcmLoamFeatureParams),
                                              C.POINTER(PcmLoamFeaturesResult)]
     L.pcm_loam_feature_info.argtypes = [vp] * 12
+    L.pcm_loam_default_submap_params.argtypes = [C.POINTER(PcmLoamSubmapParams)]
+    L.pcm_loam_default_submap_params.restype = None
+    L.pcm_loam_keyframe_add.argtypes = [vp, vp, C.c_double, vp, sz, vp, sz, sz, i32]
+    L.pcm_loam_keyframe_set_poses.argtypes = [vp, i32, i32, vp]
+    L.pcm_loam_keyframe_count.argtypes = [vp]
+    L.pcm_loam_keyframe_clear.argtypes = [vp]
+    L.pcm_loam_keyframe_get.argtypes = [vp, i32, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(sz)]
+    L.pcm_loam_submap_update.argtypes = [vp, C.POINTER(PcmLoamSubmapParams), C.c_double, C.POINTER(PcmLoamSubmapResult)]
+    L.pcm_loam_submap_near.argtypes = [vp, i32, i32, i32, C.c_float, vp, sz, C.POINTER(sz)]
+    L.pcm_loam_submap_info.argtypes = [vp] * 6
     _LIB = L
     return L

@@ -35,6 +35,13 @@ struct LoamCtx {
   bool have_tgt = false, have_src = false;
   float4* feats = nullptr;     // corner features, then surf features (body frame)
   size_t feats_cap = 0;
+  float* src_int = nullptr;    // pcm_loam_set_source with records of >= 16 bytes: their fourth float (a key frame keeps it)
+  size_t src_int_cap = 0;
+  bool src_has_int = false;    // src_int is current
+  bool src_from_fe = false;    // the source came from the front end (its intensity lives in loam_features.hip's output)
+  uint64_t src_fe_gen = 0;     // generation of that output when the source was committed
+  bool tgt_from_submap = false;   // the target clouds are what loam_target_commit left
+  void* keystore = nullptr;    // key frames and submap workspace (loam_submap.hip)
   uint32_t n_c = 0, n_s = 0;
   double* partials = nullptr;
   size_t partials_cap = 0;     // doubles
@@ -78,6 +85,33 @@ int grow_f4(pcm_ctx* c, float4** p, size_t* cap, size_t n) {
   *p = nullptr; *cap = 0;
   LCK(c, hipMalloc(reinterpret_cast<void**>(p), sizeof(float4) * (n ? n : 1)));
   *cap = n;
+  return PCM_OK;
+}
+
+// records of >= 16 bytes -> features (x, y, z, w = index: k_load_points' layout) and their fourth float, one float per record.
+// base may be `out` itself (rows staged in place): every lane reads its own row before it writes it.
+__global__ void k_load_feats(const char* base, size_t stride, uint32_t n, float4* out, float* __restrict__ inten) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* p = reinterpret_cast<const float*>(base + (size_t)i * stride);
+  const float x = p[0], y = p[1], z = p[2], w = p[3];
+  inten[i] = w;
+  out[i] = make_float4(x, y, z, __uint_as_float(i));
+}
+
+// load_points_to_device for records that carry a fourth float: the same single transfer (16 instead of 12 bytes per row) and one
+// kernel, which also keeps the fourth float
+int load_feats_xyzw(pcm_ctx* c, const void* pts, size_t n, size_t stride, int memory, float4* out, float* inten) {
+  if (n == 0) return PCM_OK;
+  const char* base = static_cast<const char*>(pts);
+  size_t st = stride;
+  if (memory != PCM_MEM_DEVICE) {
+    LCK(c, hipMemcpy2DAsync(out, sizeof(float4), pts, stride, sizeof(float4), n, hipMemcpyHostToDevice, c->stream));
+    base = reinterpret_cast<const char*>(out);
+    st = sizeof(float4);
+  }
+  k_load_feats<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(base, st, (uint32_t)n, out, inten);
+  LCK(c, hipGetLastError());
   return PCM_OK;
 }
 
@@ -347,7 +381,9 @@ void loam_release(pcm_ctx* c) {
   LoamCtx* L = static_cast<LoamCtx*>(c->loam);
   if (!L) return;
   for (int m = 0; m < 2; m++) { L->map_cloud[m].release(); L->map[m].release(); }
+  if (L->keystore) loam::loam_keystore_release(L->keystore);
   if (L->feats) hipFree(L->feats);
+  if (L->src_int) hipFree(L->src_int);
   if (L->partials) hipFree(L->partials);
   if (L->st) hipFree(L->st);
   if (L->h_st) hipHostFree(L->h_st);
@@ -372,7 +408,67 @@ void loam_source_commit(pcm_ctx* c, uint32_t n_c, uint32_t n_s) {
   L->n_c = n_c;
   L->n_s = n_s;
   L->src_tag = 0;
+  L->src_from_fe = true;
+  L->src_fe_gen = 0;
+  const float4* out = nullptr;
+  uint32_t fc = 0, fs = 0;
+  (void)loam_features_last_out(c, &out, &fc, &fs, &L->src_fe_gen);
+  L->src_has_int = false;
   L->have_src = true;
+}
+
+int loam_target_reserve(pcm_ctx* c, size_t n_corner, size_t n_surf, float4** corner, float4** surf) {
+  int rc = check_ctx(c);
+  if (rc != PCM_OK) return rc;
+  LoamCtx* L = loam_of(c);
+  L->have_tgt = false;
+  L->tgt_from_submap = false;
+  L->built_cell = 0.f;
+  L->map[0].valid = L->map[1].valid = false;
+  L->map_cloud[0].n = L->map_cloud[1].n = 0;
+  if ((rc = grow_f4(c, &L->map_cloud[0].d_pts, &L->map_cloud[0].cap, n_corner)) != PCM_OK) return rc;
+  if ((rc = grow_f4(c, &L->map_cloud[1].d_pts, &L->map_cloud[1].cap, n_surf)) != PCM_OK) return rc;
+  *corner = L->map_cloud[0].d_pts;
+  *surf = L->map_cloud[1].d_pts;
+  return PCM_OK;
+}
+
+void loam_target_commit(pcm_ctx* c, uint32_t n_corner, uint32_t n_surf) {
+  LoamCtx* L = loam_of(c);
+  L->map_cloud[0].n = n_corner;
+  L->map_cloud[1].n = n_surf;
+  L->tgt_tag = 0;
+  L->have_tgt = true;
+  L->tgt_from_submap = true;
+}
+
+bool loam_target_view(pcm_ctx* c, const float4** corner, uint32_t* n_corner, const float4** surf, uint32_t* n_surf) {
+  LoamCtx* L = loam_of(c);
+  if (!L || !L->have_tgt || !L->tgt_from_submap) return false;
+  *corner = L->map_cloud[0].d_pts; *n_corner = (uint32_t)L->map_cloud[0].n;
+  *surf = L->map_cloud[1].d_pts; *n_surf = (uint32_t)L->map_cloud[1].n;
+  return true;
+}
+
+int loam_source_view(pcm_ctx* c, const float4** feats, uint32_t* n_c, uint32_t* n_s, const float4** xyzi, const float** inten) {
+  LoamCtx* L = loam_of(c);
+  if (!L || !L->have_src) return 1;
+  *feats = L->feats; *n_c = L->n_c; *n_s = L->n_s; *xyzi = nullptr; *inten = nullptr;
+  if (L->src_from_fe) {
+    // the front end's output must still be the frame that became the source: pcm_loam_extract_features, a failed frame or
+    // a batch led by another context rewrites it without touching the source
+    uint32_t fc = 0, fs = 0;
+    uint64_t gen = 0;
+    if (!loam_features_last_out(c, xyzi, &fc, &fs, &gen) || gen != L->src_fe_gen || fc != L->n_c || fs != L->n_s) return 2;
+  } else if (L->src_has_int) {
+    *inten = L->src_int;
+  }
+  return 0;
+}
+
+void** loam_keystore_slot(pcm_ctx* c) {
+  LoamCtx* L = loam_of(c);
+  return L ? &L->keystore : nullptr;
 }
 }  // namespace loam
 }  // namespace pcm
@@ -399,6 +495,7 @@ int pcm_loam_set_target(pcm_ctx* c, const void* corner, size_t n_c, const void* 
   if ((rc = check_cloud(c, corner, n_c, stride)) != PCM_OK || (rc = check_cloud(c, surf, n_s, stride)) != PCM_OK) return rc;
   LCK(c, hipSetDevice(c->device));
   L->have_tgt = false;
+  L->tgt_from_submap = false;
   L->built_cell = 0.f;
   L->map[0].valid = L->map[1].valid = false;
   if ((rc = load_cloud(c, &L->map_cloud[0], corner, n_c, stride, memory)) != PCM_OK) return rc;
@@ -418,8 +515,22 @@ int pcm_loam_set_source(pcm_ctx* c, const void* corner, size_t n_c, const void* 
   LCK(c, hipSetDevice(c->device));
   L->have_src = false;
   if ((rc = grow_f4(c, &L->feats, &L->feats_cap, n_c + n_s)) != PCM_OK) return rc;
-  if ((rc = load_points_to_device(c->stream, corner, n_c, stride, memory, 0u, L->feats, &c->err)) != PCM_OK) return rc;
-  if ((rc = load_points_to_device(c->stream, surf, n_s, stride, memory, 0u, L->feats + n_c, &c->err)) != PCM_OK) return rc;
+  L->src_from_fe = false;
+  L->src_has_int = false;
+  if (stride >= 4 * sizeof(float)) {   // the records carry a fourth float (PointXYZI's intensity): a key frame keeps it
+    if (n_c + n_s > L->src_int_cap || !L->src_int) {
+      if (L->src_int) { (void)hipStreamSynchronize(c->stream); hipFree(L->src_int); }
+      L->src_int = nullptr; L->src_int_cap = 0;
+      LCK(c, hipMalloc(reinterpret_cast<void**>(&L->src_int), sizeof(float) * (n_c + n_s ? n_c + n_s : 1)));
+      L->src_int_cap = n_c + n_s;
+    }
+    if ((rc = load_feats_xyzw(c, corner, n_c, stride, memory, L->feats, L->src_int)) != PCM_OK) return rc;
+    if ((rc = load_feats_xyzw(c, surf, n_s, stride, memory, L->feats + n_c, L->src_int + n_c)) != PCM_OK) return rc;
+    L->src_has_int = true;
+  } else {
+    if ((rc = load_points_to_device(c->stream, corner, n_c, stride, memory, 0u, L->feats, &c->err)) != PCM_OK) return rc;
+    if ((rc = load_points_to_device(c->stream, surf, n_s, stride, memory, 0u, L->feats + n_c, &c->err)) != PCM_OK) return rc;
+  }
   LCK(c, hipStreamSynchronize(c->stream));
   L->n_c = (uint32_t)n_c;
   L->n_s = (uint32_t)n_s;

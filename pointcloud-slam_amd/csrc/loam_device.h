@@ -36,5 +36,94 @@ void launch_round(hipStream_t stream, const LoamDesc* d_descs, int n, uint32_t m
 int loam_source_reserve(pcm_ctx* c, size_t n, float4** feats);
 void loam_source_commit(pcm_ctx* c, uint32_t n_c, uint32_t n_s);
 
+
+// loam_api.hip: the key-frame submap (loam_submap.hip) writes the context's two target clouds in place: room for the clouds, then
+// their sizes once they are known (the state pcm_loam_set_target leaves, grids not built yet: the next align builds them)
+int loam_target_reserve(pcm_ctx* c, size_t n_corner, size_t n_surf, float4** corner, float4** surf);
+void loam_target_commit(pcm_ctx* c, uint32_t n_corner, uint32_t n_surf);
+// the target clouds in caller order, and whether they are still what the last loam_target_commit left
+bool loam_target_view(pcm_ctx* c, const float4** corner, uint32_t* n_corner, const float4** surf, uint32_t* n_surf);
+// the current source as PointXYZI pieces: feats (xyz, w = index), and the intensity either as whole records (xyzi, the front
+// end's output) or as one float per feature (inten); both null: intensity 0.  Returns 0, 1 without a source, 2 when the source
+// came from the front end and its output has been rewritten since (pcm_loam_extract_features on the same context, a failed frame).
+int loam_source_view(pcm_ctx* c, const float4** feats, uint32_t* n_c, uint32_t* n_s, const float4** xyzi, const float** inten);
+// the key-frame store of a context (pcm_ctx::loam owns the pointer, loam_submap.hip the type)
+void** loam_keystore_slot(pcm_ctx* c);
+void loam_keystore_release(void* store);
+
+// loam_features.hip: pieces of the segmented VoxelGrid that do not depend on where the elements live
+struct SvWork {
+  uint64_t* keys; uint64_t* keys_s; uint32_t* vals; uint32_t* vals_s;   // [N]; after sv_sort_cells vals holds the first sorted element of every cell
+  uint32_t* head; uint32_t* slot;                                      // [N]
+  uint32_t* scnt; uint32_t* sfirst;                                    // [nseg] cells per segment, first cell of the segment
+  uint32_t* nc;                                                        // [0] cells, [1] valid elements (zeroed by the caller)
+  void* tmp; size_t tmp_bytes; void* tmp2; size_t tmp2_bytes;          // rocprim scratch (sv_temp_bytes)
+};
+void sv_temp_bytes(size_t n, size_t* sort_bytes, size_t* scan_bytes);
+void sv_clear(hipStream_t st, unsigned int* mm, uint32_t* scnt, uint32_t nseg);
+int sv_sort_cells(pcm_ctx* c0, hipStream_t st, const SvWork& W, uint32_t N, uint32_t nseg);
+// gen: bumps whenever the output array is rewritten
+bool loam_features_last_out(pcm_ctx* c, const float4** out, uint32_t* n_c, uint32_t* n_s, uint64_t* gen);
+
+#if defined(__HIPCC__)
+// floats as unsigned integers of the same order (atomicMin / atomicMax on bounding boxes)
+__device__ inline unsigned int f2ord(float f) { const unsigned int u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+// inverse of f2ord, branch-free (the select form crashes this compiler's instruction selection when followed by float arithmetic)
+__device__ inline float ord2f(unsigned int o) { const unsigned int m = (unsigned int)((int)o >> 31); return __uint_as_float(o ^ (~m | 0x80000000u)); }
+
+// a lane's point into the bounding box of its segment (mm: 6 ordered-int words per segment, min then max)
+__device__ inline void sv_wave_minmax(bool valid, uint32_t seg, const float4& pt, unsigned int* __restrict__ mm) {
+  unsigned int lo[3], hi[3];
+  const float c[3] = {pt.x, pt.y, pt.z};
+  for (int a = 0; a < 3; a++) { lo[a] = valid ? f2ord(c[a]) : 0xffffffffu; hi[a] = valid ? f2ord(c[a]) : 0u; }
+  // one atomic per wave when every valid lane shares the segment
+  const uint64_t vm = __ballot(valid);
+  if (vm == 0) return;
+  const int l0 = __ffsll((unsigned long long)vm) - 1;
+  const uint32_t s0 = (uint32_t)__shfl((int)seg, l0, 64);
+  const bool same = __ballot(valid && seg != s0) == 0;
+  if (same) {
+    for (int off = 32; off >= 1; off >>= 1)
+      for (int a = 0; a < 3; a++) { lo[a] = min(lo[a], (unsigned int)__shfl_xor((int)lo[a], off, 64)); hi[a] = max(hi[a], (unsigned int)__shfl_xor((int)hi[a], off, 64)); }
+    if ((threadIdx.x & 63) == 0)
+      for (int a = 0; a < 3; a++) { atomicMin(&mm[6 * s0 + a], lo[a]); atomicMax(&mm[6 * s0 + 3 + a], hi[a]); }
+  } else if (valid) {
+    for (int a = 0; a < 3; a++) { atomicMin(&mm[6 * seg + a], lo[a]); atomicMax(&mm[6 * seg + 3 + a], hi[a]); }
+  }
+}
+
+// the box of pcl::VoxelGrid from a segment's min / max: b = {min_b x, y, z, divb_mul[1], divb_mul[2], state} (state 0: empty or no
+// leaf, 1: index overflow, 2: valid).  The products are formed in double: exact, as a valid box has fewer than 2^31 cells.
+// Returns whether the index overflows.
+__device__ inline bool sv_box(const unsigned int* __restrict__ mm, float leaf, long long* __restrict__ b) {
+  b[5] = 0;
+  if (mm[0] == 0xffffffffu) return false;   // empty segment
+  if (!(leaf > 0.f)) return false;
+  const float inv = 1.0f / leaf;
+  float mn[3], mx[3];
+  for (int a = 0; a < 3; a++) { mn[a] = ord2f(mm[a]); mx[a] = ord2f(mm[3 + a]); }
+  double cells = 1.0;
+  for (int a = 0; a < 3; a++) cells *= trunc((double)((mx[a] - mn[a]) * inv)) + 1.0;   // int64_t((max - min) * inv) + 1, max >= min
+  const bool over = cells > 2147483647.0;
+  int mb[3], xb[3];
+  for (int a = 0; a < 3; a++) { mb[a] = (int)floorf(mn[a] * inv); xb[a] = (int)floorf(mx[a] * inv); }
+  const double div0 = (double)xb[0] - (double)mb[0] + 1.0, div1 = (double)xb[1] - (double)mb[1] + 1.0;
+  b[0] = mb[0]; b[1] = mb[1]; b[2] = mb[2];
+  b[3] = over ? 0 : (long long)div0;
+  b[4] = over ? 0 : (long long)(div0 * div1);
+  b[5] = over ? 1 : 2;
+  return over;
+}
+
+// linear leaf index of a point in a valid box
+__device__ inline uint64_t sv_cell(const float4& pt, float leaf, const long long* __restrict__ b) {
+  const float inv = 1.0f / leaf;
+  const int mb0 = (int)b[0], mb1 = (int)b[1], mb2 = (int)b[2];
+  const long long i0 = (long long)(floorf(pt.x * inv) - (float)mb0), i1 = (long long)(floorf(pt.y * inv) - (float)mb1),
+                  i2 = (long long)(floorf(pt.z * inv) - (float)mb2);
+  return (uint64_t)(i0 + i1 * b[3] + i2 * b[4]);
+}
+#endif
+
 }  // namespace loam
 }  // namespace pcm

@@ -495,10 +495,6 @@ __device__ inline float seg_leaf(int stage, const LfParams& p, uint32_t seg) {
   return stage == 1 ? p.leaf_odo : ((seg & 1u) ? p.leaf_surf : p.leaf_corner);
 }
 
-__device__ inline unsigned int f2ord(float f) { const unsigned int u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-// inverse of f2ord, branch-free (the select form crashes this compiler's instruction selection when followed by float arithmetic)
-__device__ inline float ord2f(unsigned int o) { const unsigned int m = (unsigned int)((int)o >> 31); return __uint_as_float(o ^ (~m | 0x80000000u)); }
-
 __global__ void k_sv_clear(unsigned int* __restrict__ mm, uint32_t* __restrict__ scnt, uint32_t nseg) {
   const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= nseg) return;
@@ -512,23 +508,7 @@ __global__ void k_sv_minmax(const LfFrame* __restrict__ fr, LfParams p, uint32_t
   const LfFrame& F = fr[f];
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   const Elem e = j < size_per_frame ? elem_of<kStage>(F, p, f, j, cells1) : Elem{false, 0u, 0u, make_float4(0.f, 0.f, 0.f, 0.f)};
-  unsigned int lo[3], hi[3];
-  const float c[3] = {e.pt.x, e.pt.y, e.pt.z};
-  for (int a = 0; a < 3; a++) { lo[a] = e.valid ? f2ord(c[a]) : 0xffffffffu; hi[a] = e.valid ? f2ord(c[a]) : 0u; }
-  // one atomic per wave when every valid lane shares the segment
-  const uint64_t vm = __ballot(e.valid);
-  if (vm == 0) return;
-  const int l0 = __ffsll((unsigned long long)vm) - 1;
-  const uint32_t s0 = (uint32_t)__shfl((int)e.seg, l0, 64);
-  const bool same = __ballot(e.valid && e.seg != s0) == 0;
-  if (same) {
-    for (int off = 32; off >= 1; off >>= 1)
-      for (int a = 0; a < 3; a++) { lo[a] = min(lo[a], (unsigned int)__shfl_xor((int)lo[a], off, 64)); hi[a] = max(hi[a], (unsigned int)__shfl_xor((int)hi[a], off, 64)); }
-    if ((threadIdx.x & 63) == 0)
-      for (int a = 0; a < 3; a++) { atomicMin(&mm[6 * s0 + a], lo[a]); atomicMax(&mm[6 * s0 + 3 + a], hi[a]); }
-  } else if (e.valid) {
-    for (int a = 0; a < 3; a++) { atomicMin(&mm[6 * e.seg + a], lo[a]); atomicMax(&mm[6 * e.seg + 3 + a], hi[a]); }
-  }
+  loam::sv_wave_minmax(e.valid, e.seg, e.pt, mm);
 }
 
 // per segment: the box of pcl::VoxelGrid from the segment's min / max: box = {min_b x, y, z, divb_mul[1], divb_mul[2], state}
@@ -537,24 +517,7 @@ __global__ void k_sv_minmax(const LfFrame* __restrict__ fr, LfParams p, uint32_t
 __global__ void k_sv_boxes(const LfFrame* __restrict__ fr, const unsigned int* __restrict__ mm, uint32_t nseg, int stage, LfParams p, long long* __restrict__ box) {
   const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= nseg) return;
-  long long* b = box + 6 * (size_t)s;
-  b[5] = 0;
-  if (mm[6 * s] == 0xffffffffu) return;   // empty segment
-  const float leaf = seg_leaf(stage, p, s);
-  if (!(leaf > 0.f)) return;
-  const float inv = 1.0f / leaf;
-  float mn[3], mx[3];
-  for (int a = 0; a < 3; a++) { mn[a] = ord2f(mm[6 * s + a]); mx[a] = ord2f(mm[6 * s + 3 + a]); }
-  double cells = 1.0;
-  for (int a = 0; a < 3; a++) cells *= trunc((double)((mx[a] - mn[a]) * inv)) + 1.0;   // int64_t((max - min) * inv) + 1, max >= min
-  const bool over = cells > 2147483647.0;
-  int mb[3], xb[3];
-  for (int a = 0; a < 3; a++) { mb[a] = (int)floorf(mn[a] * inv); xb[a] = (int)floorf(mx[a] * inv); }
-  const double div0 = (double)xb[0] - (double)mb[0] + 1.0, div1 = (double)xb[1] - (double)mb[1] + 1.0;
-  b[0] = mb[0]; b[1] = mb[1]; b[2] = mb[2];
-  b[3] = over ? 0 : (long long)div0;
-  b[4] = over ? 0 : (long long)(div0 * div1);
-  b[5] = over ? 1 : 2;
+  const bool over = loam::sv_box(mm + 6 * (size_t)s, seg_leaf(stage, p, s), box + 6 * (size_t)s);
   if (over) fr[s / (stage == 1 ? (uint32_t)p.n_scan : 2u)].info->overflow = 1u;   // every writer stores 1
 }
 
@@ -573,15 +536,8 @@ __global__ void k_sv_keys(const LfFrame* __restrict__ fr, LfParams p, uint32_t s
   if (e.valid) {
     const float leaf = seg_leaf(kStage, p, e.seg);
     const long long* b = box + 6 * (size_t)e.seg;
-    if (!(leaf > 0.f)) {
-      key = ((uint64_t)e.seg << 32) | e.ord;
-    } else if (b[5] == 2) {
-      const float inv = 1.0f / leaf;
-      const int mb0 = (int)b[0], mb1 = (int)b[1], mb2 = (int)b[2];
-      const long long i0 = (long long)(floorf(e.pt.x * inv) - (float)mb0), i1 = (long long)(floorf(e.pt.y * inv) - (float)mb1),
-                      i2 = (long long)(floorf(e.pt.z * inv) - (float)mb2);
-      key = ((uint64_t)e.seg << 32) | (uint64_t)(i0 + i1 * b[3] + i2 * b[4]);
-    }
+    if (!(leaf > 0.f)) key = ((uint64_t)e.seg << 32) | e.ord;
+    else if (b[5] == 2) key = ((uint64_t)e.seg << 32) | loam::sv_cell(e.pt, leaf, b);
   }
   keys[g] = key;
   vals[g] = g;
@@ -707,6 +663,7 @@ struct FeatState {
   float4* corner_scan = nullptr; size_t cap_cs = 0;
   float4* surf_scan = nullptr; size_t cap_ss = 0;
   float4* out = nullptr; size_t cap_out = 0;
+  uint64_t out_gen = 0;   // bumps with every frame that rewrites `out` (the key-frame store checks it, loam_source_view)
   LfInfo last{};
   bool have_last = false;
   // batch workspace (used when this context leads a batch)
@@ -837,16 +794,12 @@ int run_vg(pcm_ctx* c0, hipStream_t st, int stage, const LfFrame* d_fr, const Lf
     k_sv_keys<2><<<g, 256, 0, st>>>(d_fr, P, size_per_frame, cells1, box, nseg, keys, vals);
   }
   LFCK(c0, hipGetLastError());
-  size_t tb = Lw.tmp_bytes, tb2 = Lw.tmp2_bytes;
-  const int end_bit = 32 + bit_len(nseg);
-  LFCK(c0, rocprim::radix_sort_pairs(ws + Lw.o_tmp, tb, keys, keys_s, vals, vals_s, (size_t)N, 0, end_bit, st));
-  const unsigned nb = (N + 255) / 256;
-  k_sv_heads<<<nb, 256, 0, st>>>(keys_s, N, nseg, head, scnt);
-  LFCK(c0, hipGetLastError());
-  LFCK(c0, rocprim::exclusive_scan(ws + Lw.o_tmp2, tb2, head, slot, 0u, (size_t)N, rocprim::plus<uint32_t>(), st));
+  loam::SvWork W;
+  W.keys = keys; W.keys_s = keys_s; W.vals = vals; W.vals_s = vals_s; W.head = head; W.slot = slot; W.scnt = scnt; W.sfirst = sfirst; W.nc = nc;
+  W.tmp = ws + Lw.o_tmp; W.tmp_bytes = Lw.tmp_bytes; W.tmp2 = ws + Lw.o_tmp2; W.tmp2_bytes = Lw.tmp2_bytes;
+  int rc = loam::sv_sort_cells(c0, st, W, N, nseg);
+  if (rc != PCM_OK) return rc;
   uint32_t* pos = vals;   // free after the sort
-  k_sv_head_pos<<<nb, 256, 0, st>>>(keys_s, head, slot, N, pos, sfirst);
-  k_sv_count<<<nb, 256, 0, st>>>(keys_s, head, slot, N, nseg, nc);   // invalid keys sort behind every valid one
   const unsigned gb = std::min<unsigned>(1024u, (N + 3) / 4);
   if (stage == 1) {
     k_sv_average<1><<<gb, 256, 0, st>>>(d_fr, P, keys_s, vals_s, pos, nc, nc + 1, cells1, cells_out);
@@ -860,6 +813,43 @@ int run_vg(pcm_ctx* c0, hipStream_t st, int stage, const LfFrame* d_fr, const Lf
 }
 
 }  // namespace
+
+namespace pcm {
+namespace loam {
+// the middle of the segmented VoxelGrid, independent of where the elements live: keys -> sorted keys, cell heads, the start of
+// every cell in W.vals (free after the sort), per-segment cell counts and first cells, totals in W.nc
+int sv_sort_cells(pcm_ctx* c0, hipStream_t st, const SvWork& W, uint32_t N, uint32_t nseg) {
+  size_t tb = W.tmp_bytes, tb2 = W.tmp2_bytes;
+  const int end_bit = 32 + bit_len(nseg);
+  LFCK(c0, rocprim::radix_sort_pairs(W.tmp, tb, W.keys, W.keys_s, W.vals, W.vals_s, (size_t)N, 0, end_bit, st));
+  const unsigned nb = (N + 255) / 256;
+  k_sv_heads<<<nb, 256, 0, st>>>(W.keys_s, N, nseg, W.head, W.scnt);
+  LFCK(c0, hipGetLastError());
+  LFCK(c0, rocprim::exclusive_scan(W.tmp2, tb2, W.head, W.slot, 0u, (size_t)N, rocprim::plus<uint32_t>(), st));
+  k_sv_head_pos<<<nb, 256, 0, st>>>(W.keys_s, W.head, W.slot, N, W.vals, W.sfirst);
+  k_sv_count<<<nb, 256, 0, st>>>(W.keys_s, W.head, W.slot, N, nseg, W.nc);   // invalid keys sort behind every valid one
+  LFCK(c0, hipGetLastError());
+  return PCM_OK;
+}
+
+void sv_clear(hipStream_t st, unsigned int* mm, uint32_t* scnt, uint32_t nseg) { k_sv_clear<<<(nseg + 255) / 256, 256, 0, st>>>(mm, scnt, nseg); }
+
+void sv_temp_bytes(size_t n, size_t* sort_bytes, size_t* scan_bytes) {
+  uint64_t* k = nullptr; uint32_t* v = nullptr;
+  (void)rocprim::radix_sort_pairs(nullptr, *sort_bytes, k, k, v, v, n, 0, 64, nullptr);
+  (void)rocprim::exclusive_scan(nullptr, *scan_bytes, v, v, 0u, n, rocprim::plus<uint32_t>(), nullptr);
+}
+
+// the context's last front-end features with their averaged intensity (k_lf_finish's F.out), alive until the next frame
+bool loam_features_last_out(pcm_ctx* c, const float4** out, uint32_t* n_c, uint32_t* n_s, uint64_t* gen) {
+  FeatState* S = static_cast<FeatState*>(c->loam_fe);
+  if (!S || !S->have_last || !S->out) return false;
+  *gen = S->out_gen;
+  *out = S->out; *n_c = S->last.n_corner; *n_s = S->last.n_surf;
+  return true;
+}
+}  // namespace loam
+}  // namespace pcm
 
 namespace {
 
@@ -940,6 +930,7 @@ int run_frames(pcm_ctx* const* ctxs, int B, const void* const* points, const siz
     }
     S->end = S->start + q.n_scan;
     S->A = q.area_num;
+    S->out_gen++;
     if (memory == PCM_MEM_HOST) in_bytes += up256(n_points[i] * stride);
   }
   std::vector<float4*> src((size_t)B, nullptr);

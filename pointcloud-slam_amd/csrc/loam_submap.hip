@@ -1,0 +1,620 @@
+// loam_submap.hip -- LOAM key-frame store and surrounding-key-frame submap on the device (include/pcm_amd.h, pcm_loam_keyframe_*
+// and pcm_loam_submap_*): jueying_slam's saveKeyFramesAndFactor clouds (mapOptmization.cpp:1779-1846), correctPoses (:1886-1917),
+// extractSurroundingKeyFrames (:1153-1230), transformPointCloud (:447-470) and loopFindNearKeyframes (:972-1018).
+//
+// Store: one growing float4 arena (x, y, z, intensity; body frame) for the corner clouds of all key frames and one for the surf
+// clouds, per-key-frame offsets and counts on the host, the 3 x 4 float pose matrices on the device.  A matrix is loam_step.h's
+// pose_matrix evaluated on the HOST when a pose is added or replaced (48 bytes uploaded): the device transform is then
+// contraction-free float arithmetic that a test can check bit for bit, whereas the device library's sin / cos need not agree with
+// libm in the last bit.
+// Submap: the selection runs on the host (loam_submap.h; microseconds); its entry table (arena offset, first output position,
+// matrix) is uploaded, k_sm_gather transforms and concatenates the selected clouds and reduces their bounding boxes, and the two
+// VoxelGrids run as one segmented pass (segment 0 corner, 1 surf) through the (segment, leaf) key -> radix sort -> heads ->
+// average chain of loam_features.hip (sv_sort_cells and the sv_* device helpers of loam_device.h).  The averaged cells are written
+// straight into the context's two target clouds (loam_target_reserve / loam_target_commit); no float atomics anywhere, so two
+// updates of the same state give the same bits.
+// laserCloudMapContainer (the reference's cache of transformed clouds) never changes a result and is not kept: when the selection,
+// the poses and the leaves equal those of the previous update the call does nothing at all, which is the common case at LiDAR rate.
+#include "loam_device.h"
+#include "loam_submap.h"
+#include "pcm_host.h"
+
+#include <cstring>
+#include <new>
+#include <vector>
+
+using namespace pcm;
+using namespace pcm::loam;
+
+namespace {
+
+#define SMCK(ctx, x)                                                                 \
+  do {                                                                               \
+    hipError_t e_ = (x);                                                             \
+    if (e_ != hipSuccess) {                                                          \
+      (ctx)->err = std::string(#x) + ": " + hipGetErrorString(e_);                   \
+      return PCM_ERR_HIP;                                                            \
+    }                                                                                \
+  } while (0)
+
+// one cloud of one selected key frame: points [src, src + count) of an arena go to output positions [first, first + count)
+struct SmEntry {
+  uint32_t src;     // first point in its arena
+  uint32_t first;   // first output position (ascending over the table; an empty entry shares it with its successor)
+  uint32_t mat;     // key frame whose pose matrix applies
+  uint32_t flags;   // bit 0: surf arena, bit 1: VoxelGrid segment 1
+};
+
+// One lane per point of the concatenated selection.  The lane finds its entry by a binary search over the first positions: the
+// trip count is the same in every lane (it depends on the table size only) and a key frame's cloud holds thousands of points, so
+// nearly every wave reads one entry and one matrix (wave-uniform addresses, served by one cache line); the arena read and the
+// output write are contiguous 16-byte accesses per lane.  transformPointCloud :462-466: T(r,0) x + T(r,1) y + T(r,2) z + T(r,3),
+// left to right in float (built with -ffp-contract=off), intensity copied.
+__global__ void __launch_bounds__(256) k_sm_gather(const float4* __restrict__ corner_arena, const float4* __restrict__ surf_arena, const float* __restrict__ mats,
+                                                   const SmEntry* __restrict__ ent, uint32_t n_ent, uint32_t N, float4* __restrict__ out,
+                                                   unsigned int* __restrict__ mm) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = g < N;
+  const uint32_t gg = valid ? g : N - 1;
+  uint32_t lo = 0, hi = n_ent;   // ent[lo].first <= gg < ent[hi].first (ent[n_ent].first taken as N)
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (ent[mid].first <= gg) lo = mid; else hi = mid;
+  }
+  const SmEntry e = ent[lo];
+  const float4* __restrict__ arena = (e.flags & 1u) ? surf_arena : corner_arena;
+  const float4 p = arena[(size_t)e.src + (gg - e.first)];
+  const float* __restrict__ T = mats + 12 * (size_t)e.mat;
+  float4 q;
+  q.x = T[0] * p.x + T[1] * p.y + T[2] * p.z + T[3];
+  q.y = T[4] * p.x + T[5] * p.y + T[6] * p.z + T[7];
+  q.z = T[8] * p.x + T[9] * p.y + T[10] * p.z + T[11];
+  q.w = p.w;
+  if (valid) out[g] = q;
+  sv_wave_minmax(valid, (e.flags >> 1) & 1u, q, mm);
+}
+
+// small: [0..1] cells per segment, [2..3] first cell, [4..7] totals (sv_sort_cells' nc), [8] index overflow
+constexpr int kSmallWords = 9;
+
+__global__ void k_sm_boxes(const unsigned int* __restrict__ mm, float leaf0, float leaf1, long long* __restrict__ box, uint32_t* __restrict__ small) {
+  const uint32_t s = threadIdx.x;
+  if (s >= 2) return;
+  if (sv_box(mm + 6 * s, s ? leaf1 : leaf0, box + 6 * s)) small[8] = 1u;   // every writer stores 1
+}
+
+__global__ void k_sm_keys(const float4* __restrict__ in, uint32_t N, uint32_t n0, float leaf0, float leaf1, const long long* __restrict__ box,
+                          uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= N) return;
+  const uint32_t seg = g >= n0 ? 1u : 0u;
+  const float leaf = seg ? leaf1 : leaf0;
+  const long long* b = box + 6 * seg;
+  uint64_t key = 2ull << 32;   // invalid (index overflow): behind both segments
+  if (!(leaf > 0.f)) key = ((uint64_t)seg << 32) | g;   // no down-sampling: one cell per point, in order
+  else if (b[5] == 2) key = ((uint64_t)seg << 32) | sv_cell(in[g], leaf, b);
+  keys[g] = key;
+  vals[g] = g;
+}
+
+// one wave per cell (grid-stride): double sums of x, y, z, intensity over the cell's run (k_sv_average's scheme); the cells of
+// segment 0 go to out0, those of segment 1 to out1, each in leaf-index order
+__global__ void __launch_bounds__(256) k_sm_average(const float4* __restrict__ in, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ pos,
+                                                    const uint32_t* __restrict__ small, float4* __restrict__ out0, float4* __restrict__ out1) {
+  const uint32_t ncells = small[4], nvalid = small[5], n_seg0 = small[0];
+  const uint32_t lane = threadIdx.x & 63;
+  for (uint32_t cell = blockIdx.x * 4 + (threadIdx.x >> 6); cell < ncells; cell += gridDim.x * 4) {
+    const uint32_t b = pos[cell], e = cell + 1 < ncells ? pos[cell + 1] : nvalid;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (uint32_t j = b + lane; j < e; j += 64) {
+      const float4 q = in[vals[j]];
+      acc[0] += (double)q.x; acc[1] += (double)q.y; acc[2] += (double)q.z; acc[3] += (double)q.w;
+    }
+    for (int k = 0; k < 4; k++)
+      for (int off = 32; off >= 1; off >>= 1) acc[k] += __shfl_xor(acc[k], off, 64);
+    if (lane == 0) {
+      const double m = (double)(e - b);
+      const float4 r = make_float4((float)(acc[0] / m), (float)(acc[1] / m), (float)(acc[2] / m), (float)(acc[3] / m));
+      if (cell < n_seg0) out0[cell] = r; else out1[cell - n_seg0] = r;
+    }
+  }
+}
+
+// the context's LOAM source as PointXYZI: corner features to dst_c, surf features to dst_s
+__global__ void k_sm_store_source(const float4* __restrict__ feats, const float4* __restrict__ xyzi, const float* __restrict__ inten, uint32_t n_c, uint32_t n_s,
+                                  float4* __restrict__ dst_c, float4* __restrict__ dst_s) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_c + n_s) return;
+  float4 p;
+  if (xyzi) p = xyzi[i];
+  else { p = feats[i]; p.w = inten ? inten[i] : 0.f; }
+  if (i < n_c) dst_c[i] = p; else dst_s[i - n_c] = p;
+}
+
+// strided device records -> PointXYZI rows
+__global__ void k_sm_load(const char* __restrict__ base, size_t stride, uint32_t n, int has_w, float4* __restrict__ dst) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* p = reinterpret_cast<const float*>(base + (size_t)i * stride);
+  dst[i] = make_float4(p[0], p[1], p[2], has_w ? p[3] : 0.f);
+}
+
+size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// device workspace of one gather + VoxelGrid pass
+struct SmWork {
+  char* buf = nullptr;
+  size_t n_cap = 0, ent_cap = 0;
+  size_t o_in = 0, o_cells = 0, o_keys = 0, o_keys_s = 0, o_vals = 0, o_vals_s = 0, o_head = 0, o_slot = 0, o_mm = 0, o_box = 0, o_small = 0, o_ent = 0,
+         o_tmp = 0, o_tmp2 = 0, tmp_bytes = 0, tmp2_bytes = 0;
+  uint32_t* h_small = nullptr;   // pinned
+  SmEntry* h_ent = nullptr;      // pinned staging of the entry table
+  size_t h_ent_cap = 0;
+
+  float4* in() const { return reinterpret_cast<float4*>(buf + o_in); }
+  float4* cells() const { return reinterpret_cast<float4*>(buf + o_cells); }
+  uint32_t* small() const { return reinterpret_cast<uint32_t*>(buf + o_small); }
+
+  void release() {
+    if (buf) hipFree(buf);
+    if (h_small) hipHostFree(h_small);
+    if (h_ent) hipHostFree(h_ent);
+    buf = nullptr; h_small = nullptr; h_ent = nullptr; n_cap = ent_cap = h_ent_cap = 0;
+  }
+};
+
+int ensure_work(pcm_ctx* c, SmWork* W, size_t N, size_t n_ent, bool want_cells) {
+  if (!W->h_small) SMCK(c, hipHostMalloc(reinterpret_cast<void**>(&W->h_small), sizeof(uint32_t) * kSmallWords));
+  if (n_ent > W->h_ent_cap) {
+    SMCK(c, hipStreamSynchronize(c->stream));
+    if (W->h_ent) hipHostFree(W->h_ent);
+    W->h_ent = nullptr; W->h_ent_cap = 0;
+    const size_t cap = n_ent + n_ent / 2 + 16;
+    SMCK(c, hipHostMalloc(reinterpret_cast<void**>(&W->h_ent), sizeof(SmEntry) * cap));
+    W->h_ent_cap = cap;
+  }
+  if (W->buf && N <= W->n_cap && n_ent <= W->ent_cap) return PCM_OK;
+  SMCK(c, hipStreamSynchronize(c->stream));
+  if (W->buf) hipFree(W->buf);
+  W->buf = nullptr; W->n_cap = W->ent_cap = 0;
+  const size_t nc = N + N / 4 + 1024, ec = W->h_ent_cap;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t r = o; o += up256(bytes); return r; };
+  W->o_in = take(16 * nc);
+  W->o_cells = take(want_cells ? 16 * nc : 16);
+  W->o_keys = take(8 * nc); W->o_keys_s = take(8 * nc);
+  W->o_vals = take(4 * nc); W->o_vals_s = take(4 * nc); W->o_head = take(4 * nc); W->o_slot = take(4 * nc);
+  W->o_mm = take(4 * 12); W->o_box = take(8 * 12); W->o_small = take(4 * kSmallWords);
+  W->o_ent = take(sizeof(SmEntry) * ec);
+  sv_temp_bytes(nc, &W->tmp_bytes, &W->tmp2_bytes);
+  W->o_tmp = take(W->tmp_bytes); W->o_tmp2 = take(W->tmp2_bytes);
+  SMCK(c, hipMalloc(reinterpret_cast<void**>(&W->buf), o));
+  W->n_cap = nc; W->ent_cap = ec;
+  return PCM_OK;
+}
+
+struct Arena {
+  float4* d = nullptr;
+  size_t n = 0, cap = 0;
+  // room for `extra` more points; growth copies device to device
+  int reserve(pcm_ctx* c, size_t extra) {
+    if (d && n + extra <= cap) return PCM_OK;
+    const size_t want = std::max<size_t>(n + extra, cap + cap / 2 + 65536);
+    float4* nd = nullptr;
+    SMCK(c, hipMalloc(reinterpret_cast<void**>(&nd), sizeof(float4) * want));
+    if (d) {
+      hipError_t e = n ? hipMemcpyAsync(nd, d, sizeof(float4) * n, hipMemcpyDeviceToDevice, c->stream) : hipSuccess;
+      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+      if (e != hipSuccess) { hipFree(nd); c->err = std::string("key-frame arena growth: ") + hipGetErrorString(e); return PCM_ERR_HIP; }
+      hipFree(d);
+    }
+    d = nd; cap = want;
+    return PCM_OK;
+  }
+};
+
+struct KeyFrame {
+  float pose[6];   // roll, pitch, yaw, x, y, z
+  double time;
+  size_t off_c, off_s;
+  uint32_t n_c, n_s;
+};
+
+struct KeyStore {
+  std::vector<KeyFrame> kf;
+  std::vector<KeyPose> kp;   // what the selection reads
+  Arena arena[2];            // corner, surf
+  float* mats = nullptr;     // [K][12]
+  size_t mats_cap = 0;       // key frames
+  uint64_t gen = 1;          // bumps whenever a key frame or a pose changes
+  SmWork upd, near;
+  // the last update
+  bool last_valid = false;
+  uint64_t last_gen = 0;
+  float last_leaf[2] = {0.f, 0.f};
+  std::vector<int32_t> last_keys;
+  pcm_loam_submap_result last{};
+};
+
+int check_ctx_sm(pcm_ctx* c, KeyStore** ks) {
+  if (!c) return PCM_ERR_INVALID_ARGUMENT;
+  if (c->device < 0) return PCM_ERR_HIP;
+  if (c->cfg.model != PCM_MODEL_LOAM) { c->err = "pcm_loam_keyframe_* / pcm_loam_submap_* need a context created with PCM_MODEL_LOAM"; return PCM_ERR_INVALID_ARGUMENT; }
+  void** slot = loam_keystore_slot(c);
+  if (!slot) { c->err = "out of host memory"; return PCM_ERR_INTERNAL; }
+  if (!*slot) *slot = new (std::nothrow) KeyStore();
+  if (!*slot) { c->err = "out of host memory"; return PCM_ERR_INTERNAL; }
+  *ks = static_cast<KeyStore*>(*slot);
+  return PCM_OK;
+}
+
+void host_matrix(const float* pose6, float* T12) {
+  float x[6], T[12], trig[6];
+  for (int k = 0; k < 6; k++) x[k] = pose6[k];
+  pose_matrix(x, T, trig);
+  for (int k = 0; k < 12; k++) T12[k] = T[k];
+}
+
+int upload_matrices(pcm_ctx* c, KeyStore* S, size_t first, size_t n) {
+  const size_t K = S->kf.size();
+  if (K > S->mats_cap || !S->mats) {
+    const size_t cap = K + K / 2 + 256;
+    float* nm = nullptr;
+    SMCK(c, hipMalloc(reinterpret_cast<void**>(&nm), sizeof(float) * 12 * cap));
+    SMCK(c, hipStreamSynchronize(c->stream));
+    if (S->mats) hipFree(S->mats);
+    S->mats = nm; S->mats_cap = cap;
+    first = 0; n = K;   // a fresh array gets every matrix
+  }
+  if (n == 0) return PCM_OK;
+  std::vector<float> T(12 * n);
+  for (size_t i = 0; i < n; i++) host_matrix(S->kf[first + i].pose, T.data() + 12 * i);
+  SMCK(c, hipMemcpyAsync(S->mats + 12 * first, T.data(), sizeof(float) * 12 * n, hipMemcpyHostToDevice, c->stream));
+  SMCK(c, hipStreamSynchronize(c->stream));
+  return PCM_OK;
+}
+
+int load_cloud_xyzi(pcm_ctx* c, const void* pts, size_t n, size_t stride, int memory, float4* dst) {
+  if (n == 0) return PCM_OK;
+  const int has_w = stride >= 4 * sizeof(float) ? 1 : 0;
+  if (memory == PCM_MEM_DEVICE) {
+    k_sm_load<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(static_cast<const char*>(pts), stride, (uint32_t)n, has_w, dst);
+    SMCK(c, hipGetLastError());
+    return PCM_OK;
+  }
+  if (!has_w) SMCK(c, hipMemsetAsync(dst, 0, sizeof(float4) * n, c->stream));
+  SMCK(c, hipMemcpy2DAsync(dst, sizeof(float4), pts, stride, has_w ? sizeof(float4) : 3 * sizeof(float), n, hipMemcpyHostToDevice, c->stream));
+  return PCM_OK;
+}
+
+// gather + segmented VoxelGrid of W->h_ent[0..n_ent): N points, the first n0 of them segment 0.  Cells of segment 0 -> out0, of
+// segment 1 -> out1; the counts and the overflow flag come back through W->h_small.
+int run_pass(pcm_ctx* c, KeyStore* S, SmWork* W, size_t n_ent, uint32_t N, uint32_t n0, float leaf0, float leaf1, float4* out0, float4* out1) {
+  hipStream_t st = c->stream;
+  char* b = W->buf;
+  SmEntry* d_ent = reinterpret_cast<SmEntry*>(b + W->o_ent);
+  unsigned int* mm = reinterpret_cast<unsigned int*>(b + W->o_mm);
+  long long* box = reinterpret_cast<long long*>(b + W->o_box);
+  uint32_t* small = W->small();
+  SvWork V;
+  V.keys = reinterpret_cast<uint64_t*>(b + W->o_keys); V.keys_s = reinterpret_cast<uint64_t*>(b + W->o_keys_s);
+  V.vals = reinterpret_cast<uint32_t*>(b + W->o_vals); V.vals_s = reinterpret_cast<uint32_t*>(b + W->o_vals_s);
+  V.head = reinterpret_cast<uint32_t*>(b + W->o_head); V.slot = reinterpret_cast<uint32_t*>(b + W->o_slot);
+  V.scnt = small; V.sfirst = small + 2; V.nc = small + 4;
+  V.tmp = b + W->o_tmp; V.tmp_bytes = W->tmp_bytes; V.tmp2 = b + W->o_tmp2; V.tmp2_bytes = W->tmp2_bytes;
+  SMCK(c, hipMemcpyAsync(d_ent, W->h_ent, sizeof(SmEntry) * n_ent, hipMemcpyHostToDevice, st));
+  SMCK(c, hipMemsetAsync(small, 0, sizeof(uint32_t) * kSmallWords, st));
+  sv_clear(st, mm, small, 2);
+  const unsigned nb = (N + 255) / 256;
+  k_sm_gather<<<nb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, d_ent, (uint32_t)n_ent, N, W->in(), mm);
+  k_sm_boxes<<<1, 64, 0, st>>>(mm, leaf0, leaf1, box, small);
+  k_sm_keys<<<nb, 256, 0, st>>>(W->in(), N, n0, leaf0, leaf1, box, V.keys, V.vals);
+  SMCK(c, hipGetLastError());
+  int rc = sv_sort_cells(c, st, V, N, 2);
+  if (rc != PCM_OK) return rc;
+  const unsigned gb = std::min<unsigned>(1024u, (N + 3) / 4);
+  k_sm_average<<<gb, 256, 0, st>>>(W->in(), V.vals_s, V.vals, small, out0, out1);
+  SMCK(c, hipGetLastError());
+  SMCK(c, hipMemcpyAsync(W->h_small, small, sizeof(uint32_t) * kSmallWords, hipMemcpyDeviceToHost, st));
+  SMCK(c, hipStreamSynchronize(st));
+  return PCM_OK;
+}
+
+bool finite_f(float v) { return v == v && v <= 3.0e38f && v >= -3.0e38f; }
+
+int check_sparams(pcm_ctx* c, const pcm_loam_submap_params& p) {
+  if (!(p.search_radius > 0.f) || !finite_f(p.search_radius)) { c->err = "search_radius must be a positive number"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!(p.keypose_density > 0.f) || !finite_f(p.keypose_density)) { c->err = "keypose_density must be a positive number"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!(p.corner_leaf >= 0.f) || !(p.surf_leaf >= 0.f) || !finite_f(p.corner_leaf) || !finite_f(p.surf_leaf)) {
+    c->err = "corner_leaf and surf_leaf must be >= 0 (0: no down-sampling)"; return PCM_ERR_INVALID_ARGUMENT;
+  }
+  if (!(p.recent_window_s == p.recent_window_s)) { c->err = "recent_window_s must be a number"; return PCM_ERR_INVALID_ARGUMENT; }
+  return PCM_OK;
+}
+
+}  // namespace
+
+namespace pcm {
+namespace loam {
+void loam_keystore_release(void* store) {
+  KeyStore* S = static_cast<KeyStore*>(store);
+  if (!S) return;
+  for (int a = 0; a < 2; a++) if (S->arena[a].d) hipFree(S->arena[a].d);
+  if (S->mats) hipFree(S->mats);
+  S->upd.release();
+  S->near.release();
+  delete S;
+}
+}  // namespace loam
+}  // namespace pcm
+
+extern "C" {
+
+void pcm_loam_default_submap_params(pcm_loam_submap_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->search_radius = 50.0f;     // utility.h:282
+  p->keypose_density = 1.0f;    // utility.h:283
+  p->corner_leaf = 0.2f;        // utility.h:271
+  p->surf_leaf = 0.2f;          // utility.h:272
+  p->recent_window_s = 10.0;    // mapOptmization.cpp:1174
+}
+
+int pcm_loam_keyframe_add(pcm_ctx* c, const float pose6[6], double time, const void* corner, size_t n_corner, const void* surf, size_t n_surf, size_t stride,
+                          int memory) {
+  KeyStore* S = nullptr;
+  int rc = check_ctx_sm(c, &S);
+  if (rc != PCM_OK) return rc;
+  if (!pose6) { c->err = "null pose"; return PCM_ERR_INVALID_ARGUMENT; }
+  for (int k = 0; k < 6; k++) if (!finite_f(pose6[k])) { c->err = "the pose must be finite"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!(time == time)) { c->err = "the time must be a number"; return PCM_ERR_INVALID_ARGUMENT; }
+  const bool from_source = !corner && !surf;
+  const float4* feats = nullptr; const float4* xyzi = nullptr; const float* inten = nullptr;
+  uint32_t sc = 0, ss = 0;
+  if (from_source) {
+    const int sv = loam_source_view(c, &feats, &sc, &ss, &xyzi, &inten);
+    if (sv == 1) { c->err = "pcm_loam_keyframe_add without clouds needs a LOAM source (pcm_loam_frame_begin / pcm_loam_set_source)"; return PCM_ERR_NO_INPUT; }
+    if (sv != 0) {
+      c->err = "pcm_loam_keyframe_add without clouds: the front end has processed another frame on this context since pcm_loam_frame_begin "
+               "(pcm_loam_extract_features or a failed frame), so the source's intensities are gone; add the key frame before that, or pass the clouds";
+      return PCM_ERR_NO_INPUT;
+    }
+    n_corner = sc; n_surf = ss;
+  } else {
+    if ((!corner && n_corner) || (!surf && n_surf)) { c->err = "null point buffer"; return PCM_ERR_INVALID_ARGUMENT; }
+    if (stride < 3 * sizeof(float) || (stride % sizeof(float)) != 0) { c->err = "stride must be a multiple of 4 and >= 12 bytes"; return PCM_ERR_INVALID_ARGUMENT; }
+    if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  }
+  if (n_corner > 0x3fffffffull || n_surf > 0x3fffffffull || S->arena[0].n + n_corner > 0xffffffffull || S->arena[1].n + n_surf > 0xffffffffull) {
+    c->err = "key-frame store too large"; return PCM_ERR_INVALID_ARGUMENT;
+  }
+  SMCK(c, hipSetDevice(c->device));
+  if ((rc = S->arena[0].reserve(c, n_corner)) != PCM_OK || (rc = S->arena[1].reserve(c, n_surf)) != PCM_OK) return rc;
+  float4* dc = S->arena[0].d + S->arena[0].n;
+  float4* ds = S->arena[1].d + S->arena[1].n;
+  if (from_source) {
+    const uint32_t n = (uint32_t)(n_corner + n_surf);
+    if (n) {
+      k_sm_store_source<<<(n + 255) / 256, 256, 0, c->stream>>>(feats, xyzi, inten, (uint32_t)n_corner, (uint32_t)n_surf, dc, ds);
+      SMCK(c, hipGetLastError());
+    }
+  } else {
+    if ((rc = load_cloud_xyzi(c, corner, n_corner, stride, memory, dc)) != PCM_OK) return rc;
+    if ((rc = load_cloud_xyzi(c, surf, n_surf, stride, memory, ds)) != PCM_OK) return rc;
+  }
+  KeyFrame k{};
+  for (int a = 0; a < 6; a++) k.pose[a] = pose6[a];
+  k.time = time;
+  k.off_c = S->arena[0].n; k.off_s = S->arena[1].n;
+  k.n_c = (uint32_t)n_corner; k.n_s = (uint32_t)n_surf;
+  S->kf.push_back(k);
+  S->kp.push_back(KeyPose{pose6[3], pose6[4], pose6[5], time});
+  rc = upload_matrices(c, S, S->kf.size() - 1, 1);   // synchronises: the caller may reuse its buffers on return
+  if (rc != PCM_OK) { S->kf.pop_back(); S->kp.pop_back(); return rc; }
+  S->arena[0].n += n_corner;
+  S->arena[1].n += n_surf;
+  S->gen++;
+  return PCM_OK;
+}
+
+int pcm_loam_keyframe_set_poses(pcm_ctx* c, int first, int n, const float* pose6) {
+  KeyStore* S = nullptr;
+  int rc = check_ctx_sm(c, &S);
+  if (rc != PCM_OK) return rc;
+  const long long K = (long long)S->kf.size();
+  if (first < 0 || n < 0 || (long long)first + n > K) { c->err = "pcm_loam_keyframe_set_poses: first + n exceeds the number of key frames"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (n == 0) return PCM_OK;
+  if (!pose6) { c->err = "null poses"; return PCM_ERR_INVALID_ARGUMENT; }
+  for (int i = 0; i < 6 * n; i++) if (!finite_f(pose6[i])) { c->err = "the poses must be finite"; return PCM_ERR_INVALID_ARGUMENT; }
+  SMCK(c, hipSetDevice(c->device));
+  for (int i = 0; i < n; i++) {
+    KeyFrame& k = S->kf[(size_t)(first + i)];
+    for (int a = 0; a < 6; a++) k.pose[a] = pose6[6 * i + a];
+    KeyPose& q = S->kp[(size_t)(first + i)];
+    q.x = k.pose[3]; q.y = k.pose[4]; q.z = k.pose[5];
+  }
+  S->gen++;
+  return upload_matrices(c, S, (size_t)first, (size_t)n);
+}
+
+int pcm_loam_keyframe_count(pcm_ctx* c) {
+  KeyStore* S = nullptr;
+  int rc = check_ctx_sm(c, &S);
+  if (rc != PCM_OK) return rc;
+  return (int)S->kf.size();
+}
+
+int pcm_loam_keyframe_clear(pcm_ctx* c) {
+  KeyStore* S = nullptr;
+  int rc = check_ctx_sm(c, &S);
+  if (rc != PCM_OK) return rc;
+  S->kf.clear(); S->kp.clear();
+  S->arena[0].n = S->arena[1].n = 0;   // the arenas keep their memory
+  S->gen++;
+  S->last_valid = false;
+  return PCM_OK;
+}
+
+int pcm_loam_keyframe_get(pcm_ctx* c, int key, float* corner, size_t cap_corner, float* surf, size_t cap_surf, size_t* n_corner, size_t* n_surf) {
+  KeyStore* S = nullptr;
+  int rc = check_ctx_sm(c, &S);
+  if (rc != PCM_OK) return rc;
+  if (n_corner) *n_corner = 0;
+  if (n_surf) *n_surf = 0;
+  if (key < 0 || (size_t)key >= S->kf.size()) { c->err = "pcm_loam_keyframe_get: key outside [0, K)"; return PCM_ERR_INVALID_ARGUMENT; }
+  const KeyFrame& k = S->kf[(size_t)key];
+  if (n_corner) *n_corner = k.n_c;
+  if (n_surf) *n_surf = k.n_s;
+  if ((corner && cap_corner < k.n_c) || (surf && cap_surf < k.n_s)) { c->err = "pcm_loam_keyframe_get: capacity too small (the counts are set)"; return PCM_ERR_INVALID_ARGUMENT; }
+  SMCK(c, hipSetDevice(c->device));
+  if (corner && k.n_c) SMCK(c, hipMemcpyAsync(corner, S->arena[0].d + k.off_c, sizeof(float4) * k.n_c, hipMemcpyDeviceToHost, c->stream));
+  if (surf && k.n_s) SMCK(c, hipMemcpyAsync(surf, S->arena[1].d + k.off_s, sizeof(float4) * k.n_s, hipMemcpyDeviceToHost, c->stream));
+  SMCK(c, hipStreamSynchronize(c->stream));
+  return PCM_OK;
+}
+
+int pcm_loam_submap_update(pcm_ctx* c, const pcm_loam_submap_params* params, double time_cur, pcm_loam_submap_result* result) {
+  KeyStore* S = nullptr;
+  int rc = check_ctx_sm(c, &S);
+  if (rc != PCM_OK) return rc;
+  if (!result) { c->err = "null result"; return PCM_ERR_INVALID_ARGUMENT; }
+  pcm_loam_submap_params p;
+  if (params) p = *params; else pcm_loam_default_submap_params(&p);
+  if ((rc = check_sparams(c, p)) != PCM_OK) return rc;
+  if (!(time_cur == time_cur)) { c->err = "time_cur must be a number"; return PCM_ERR_INVALID_ARGUMENT; }
+  std::memset(result, 0, sizeof(*result));
+  const int K = (int)S->kf.size();
+  if (K == 0) return PCM_OK;   // extractSurroundingKeyFrames :1226
+  SubmapSelection sel = select_surrounding(S->kp.data(), K, p.search_radius, p.keypose_density, time_cur, p.recent_window_s);
+  pcm_loam_submap_result r{};
+  r.num_keyframes = K;
+  r.num_near = sel.num_near;
+  if (sel.status != 0) {
+    r.status = PCM_ERR_OUT_OF_RANGE;
+    *result = r;
+    c->err = "keypose_density too small for the extent of the key poses (index overflow)";
+    return PCM_ERR_OUT_OF_RANGE;
+  }
+  r.num_pose_leaves = sel.num_pose_leaves;
+  r.num_selected = (int32_t)sel.keys.size();
+  r.num_skipped = sel.num_skipped;
+  const float4 *tc = nullptr, *ts = nullptr;
+  uint32_t tnc = 0, tns = 0;
+  if (S->last_valid && S->last_gen == S->gen && S->last_leaf[0] == p.corner_leaf && S->last_leaf[1] == p.surf_leaf && S->last_keys == sel.keys &&
+      loam_target_view(c, &tc, &tnc, &ts, &tns)) {
+    // same key frames in the same order under the same poses and leaves: the maps are the ones the context already holds
+    r.num_corner_in = S->last.num_corner_in; r.num_surf_in = S->last.num_surf_in;
+    r.num_corner_map = S->last.num_corner_map; r.num_surf_map = S->last.num_surf_map;
+    r.rebuilt = 0;
+    r.status = PCM_OK;
+    *result = r;
+    return PCM_OK;
+  }
+  SMCK(c, hipSetDevice(c->device));
+  S->last_valid = false;
+  const size_t E = sel.keys.size();
+  uint64_t n_c = 0, n_s = 0;
+  for (int32_t k : sel.keys) { n_c += S->kf[(size_t)k].n_c; n_s += S->kf[(size_t)k].n_s; }
+  if (n_c + n_s > 0x7fffffffull) { c->err = "the selected key frames hold more than 2^31 points"; return PCM_ERR_OUT_OF_RANGE; }
+  float4 *out_c = nullptr, *out_s = nullptr;
+  if ((rc = loam_target_reserve(c, (size_t)n_c, (size_t)n_s, &out_c, &out_s)) != PCM_OK) return rc;
+  r.num_corner_in = (int32_t)n_c; r.num_surf_in = (int32_t)n_s;
+  const uint32_t N = (uint32_t)(n_c + n_s);
+  if ((rc = ensure_work(c, &S->upd, N, 2 * E, false)) != PCM_OK) return rc;
+  if (N > 0) {
+    SMCK(c, hipStreamSynchronize(c->stream));   // the pinned staging of an earlier pass is free again
+    uint32_t first = 0;
+    for (size_t i = 0; i < E; i++) {
+      const KeyFrame& k = S->kf[(size_t)sel.keys[i]];
+      S->upd.h_ent[i] = SmEntry{(uint32_t)k.off_c, first, (uint32_t)sel.keys[i], 0u};
+      first += k.n_c;
+    }
+    for (size_t i = 0; i < E; i++) {
+      const KeyFrame& k = S->kf[(size_t)sel.keys[i]];
+      S->upd.h_ent[E + i] = SmEntry{(uint32_t)k.off_s, first, (uint32_t)sel.keys[i], 3u};
+      first += k.n_s;
+    }
+    if ((rc = run_pass(c, S, &S->upd, 2 * E, N, (uint32_t)n_c, p.corner_leaf, p.surf_leaf, out_c, out_s)) != PCM_OK) return rc;
+    if (S->upd.h_small[8]) {
+      r.status = PCM_ERR_OUT_OF_RANGE;
+      *result = r;
+      c->err = "leaf size too small for the extent of the submap (index overflow)";
+      return PCM_ERR_OUT_OF_RANGE;
+    }
+    r.num_corner_map = (int32_t)S->upd.h_small[0];
+    r.num_surf_map = (int32_t)S->upd.h_small[1];
+  }
+  loam_target_commit(c, (uint32_t)r.num_corner_map, (uint32_t)r.num_surf_map);
+  r.rebuilt = 1;
+  r.status = PCM_OK;
+  S->last_valid = true;
+  S->last_gen = S->gen;
+  S->last_leaf[0] = p.corner_leaf; S->last_leaf[1] = p.surf_leaf;
+  S->last_keys = std::move(sel.keys);
+  S->last = r;
+  *result = r;
+  return PCM_OK;
+}
+
+int pcm_loam_submap_near(pcm_ctx* c, int key, int search_num, int wrt_key, float leaf, float* out, size_t cap, size_t* n_out) {
+  KeyStore* S = nullptr;
+  int rc = check_ctx_sm(c, &S);
+  if (rc != PCM_OK) return rc;
+  if (n_out) *n_out = 0;
+  const int K = (int)S->kf.size();
+  if (search_num < 0) { c->err = "search_num must be >= 0"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!(leaf >= 0.f) || !finite_f(leaf)) { c->err = "leaf must be >= 0 (0: no down-sampling)"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (K == 0) return PCM_OK;   // nothing to assemble
+  if (key < 0 || key >= K) { c->err = "pcm_loam_submap_near: key outside [0, K)"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (wrt_key >= K) { c->err = "pcm_loam_submap_near: wrt_key outside [0, K)"; return PCM_ERR_INVALID_ARGUMENT; }
+  const std::vector<int32_t> keys = select_near(K, key, search_num);
+  uint64_t N64 = 0;
+  for (int32_t k : keys) N64 += (uint64_t)S->kf[(size_t)k].n_c + S->kf[(size_t)k].n_s;
+  if (N64 > 0x7fffffffull) { c->err = "the selected key frames hold more than 2^31 points"; return PCM_ERR_OUT_OF_RANGE; }
+  if (N64 == 0) return PCM_OK;
+  const uint32_t N = (uint32_t)N64;
+  SMCK(c, hipSetDevice(c->device));
+  const size_t E = 2 * keys.size();
+  if ((rc = ensure_work(c, &S->near, N, E, true)) != PCM_OK) return rc;
+  SMCK(c, hipStreamSynchronize(c->stream));
+  uint32_t first = 0;
+  for (size_t i = 0; i < keys.size(); i++) {
+    const KeyFrame& k = S->kf[(size_t)keys[i]];
+    const uint32_t mat = wrt_key < 0 ? (uint32_t)keys[i] : (uint32_t)wrt_key;
+    S->near.h_ent[2 * i] = SmEntry{(uint32_t)k.off_c, first, mat, 0u};
+    first += k.n_c;
+    S->near.h_ent[2 * i + 1] = SmEntry{(uint32_t)k.off_s, first, mat, 1u};
+    first += k.n_s;
+  }
+  float4* cells = S->near.cells();
+  if ((rc = run_pass(c, S, &S->near, E, N, N, leaf, leaf, cells, cells)) != PCM_OK) return rc;
+  if (S->near.h_small[8]) { c->err = "leaf size too small for the extent of the cloud (index overflow)"; return PCM_ERR_OUT_OF_RANGE; }
+  const size_t m = S->near.h_small[0];
+  if (n_out) *n_out = m;
+  if (m > cap || (!out && m)) { c->err = "pcm_loam_submap_near: capacity too small (the count is set)"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (m) {
+    SMCK(c, hipMemcpyAsync(out, cells, sizeof(float4) * m, hipMemcpyDeviceToHost, c->stream));
+    SMCK(c, hipStreamSynchronize(c->stream));
+  }
+  return PCM_OK;
+}
+
+int pcm_loam_submap_info(pcm_ctx* c, int32_t* keys, float* corner_in, float* surf_in, float* corner_map, float* surf_map) {
+  KeyStore* S = nullptr;
+  int rc = check_ctx_sm(c, &S);
+  if (rc != PCM_OK) return rc;
+  const float4 *tc = nullptr, *ts = nullptr;
+  uint32_t tnc = 0, tns = 0;
+  if (!S->last_valid || !loam_target_view(c, &tc, &tnc, &ts, &tns)) { c->err = "pcm_loam_submap_info: the context's target is not the result of pcm_loam_submap_update"; return PCM_ERR_NO_INPUT; }
+  SMCK(c, hipSetDevice(c->device));
+  if (keys && !S->last_keys.empty()) std::memcpy(keys, S->last_keys.data(), sizeof(int32_t) * S->last_keys.size());
+  const size_t n_c = (size_t)S->last.num_corner_in, n_s = (size_t)S->last.num_surf_in;
+  if (corner_in && n_c) SMCK(c, hipMemcpyAsync(corner_in, S->upd.in(), sizeof(float4) * n_c, hipMemcpyDeviceToHost, c->stream));
+  if (surf_in && n_s) SMCK(c, hipMemcpyAsync(surf_in, S->upd.in() + n_c, sizeof(float4) * n_s, hipMemcpyDeviceToHost, c->stream));
+  if (corner_map && tnc) SMCK(c, hipMemcpyAsync(corner_map, tc, sizeof(float4) * tnc, hipMemcpyDeviceToHost, c->stream));
+  if (surf_map && tns) SMCK(c, hipMemcpyAsync(surf_map, ts, sizeof(float4) * tns, hipMemcpyDeviceToHost, c->stream));
+  SMCK(c, hipStreamSynchronize(c->stream));
+  return PCM_OK;
+}
+
+}  // extern "C"

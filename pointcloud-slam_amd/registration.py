@@ -676,6 +676,131 @@ LoamRegistration.set_input_scan = _loam_set_input_scan
 LoamRegistration.feature_info = _loam_feature_info
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# LOAM key-frame store and surrounding-key-frame submap on the device
+# ---------------------------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class LoamSubmapResult:
+    num_keyframes: int
+    num_near: int
+    num_pose_leaves: int
+    num_selected: int
+    num_skipped: int
+    num_corner_in: int
+    num_surf_in: int
+    num_corner_map: int
+    num_surf_map: int
+    rebuilt: bool
+    status: int
+
+
+def _submap_params(L, params: dict) -> capi.PcmLoamSubmapParams:
+    p = capi.PcmLoamSubmapParams()
+    L.pcm_loam_default_submap_params(C.byref(p))
+    for k, v in params.items():
+        if k.startswith("reserved") or not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _xyzi(a):
+    a = np.asarray(a, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] < 3:
+        raise ValueError("expected an (N,>=3) float32 array")
+    b = np.zeros((a.shape[0], 4), np.float32)
+    b[:, :min(4, a.shape[1])] = a[:, :4]
+    return b
+
+
+def _loam_add_keyframe(self, pose6, time, corner=None, surf=None) -> int:
+    """saveKeyFramesAndFactor: a key frame with pose6 (roll, pitch, yaw, x, y, z), its time and its (N,4) x y z intensity clouds in
+    the body frame.  Without clouds the context's current LOAM source is copied on the device.  Returns the key frame's index."""
+    x = np.ascontiguousarray(pose6, dtype=np.float32).reshape(6)
+    if (corner is None) != (surf is None):
+        raise ValueError("pass both clouds or neither")
+    if corner is None:
+        self._check(self._L.pcm_loam_keyframe_add(self._h, x.ctypes.data, float(time), None, 0, None, 0, 16, capi.MEM_HOST))
+    else:
+        c, s = _xyzi(corner), _xyzi(surf)
+        self._check(self._L.pcm_loam_keyframe_add(self._h, x.ctypes.data, float(time), c.ctypes.data, c.shape[0], s.ctypes.data, s.shape[0], 16, capi.MEM_HOST))
+    return self.num_keyframes - 1
+
+
+def _loam_set_keyframe_poses(self, poses, first: int = 0):
+    """correctPoses: new (n,6) poses for key frames first .. first + n - 1."""
+    x = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 6)
+    self._check(self._L.pcm_loam_keyframe_set_poses(self._h, int(first), x.shape[0], x.ctypes.data))
+
+
+def _loam_num_keyframes(self) -> int:
+    n = self._L.pcm_loam_keyframe_count(self._h)
+    if n < 0:
+        self._check(n)
+    return n
+
+
+def _loam_clear_keyframes(self):
+    self._check(self._L.pcm_loam_keyframe_clear(self._h))
+
+
+def _loam_get_keyframe(self, key: int):
+    """(corner (Nc,4), surf (Ns,4)) of one stored key frame: body frame, x y z intensity."""
+    nc, ns = C.c_size_t(0), C.c_size_t(0)
+    self._check(self._L.pcm_loam_keyframe_get(self._h, int(key), None, 0, None, 0, C.byref(nc), C.byref(ns)))
+    co = np.zeros((nc.value, 4), np.float32)
+    su = np.zeros((ns.value, 4), np.float32)
+    self._check(self._L.pcm_loam_keyframe_get(self._h, int(key), co.ctypes.data, nc.value, su.ctypes.data, ns.value, C.byref(nc), C.byref(ns)))
+    return co, su
+
+
+def _loam_update_submap(self, time_cur, **params) -> LoamSubmapResult:
+    """extractSurroundingKeyFrames at timeLaserInfoCur = time_cur: the down-sampled corner / surf submap of the surrounding key
+    frames becomes this context's target (pcm_loam_submap_update)."""
+    p = _submap_params(self._L, params)
+    r = capi.PcmLoamSubmapResult()
+    self._check(self._L.pcm_loam_submap_update(self._h, C.byref(p), float(time_cur), C.byref(r)))
+    self._submap = r
+    return LoamSubmapResult(r.num_keyframes, r.num_near, r.num_pose_leaves, r.num_selected, r.num_skipped, r.num_corner_in, r.num_surf_in,
+                            r.num_corner_map, r.num_surf_map, bool(r.rebuilt), r.status)
+
+
+def _loam_near_keyframes(self, key: int, search_num: int, wrt_key: int = -1, leaf: float = 0.2) -> np.ndarray:
+    """loopFindNearKeyframes (wrt_key < 0) / loopFindNearKeyframesWithRespectTo: (M,4) x y z intensity on the host."""
+    n = C.c_size_t(0)
+    total = 0
+    K = self.num_keyframes
+    for k in range(max(0, key - search_num), min(K, key + search_num + 1)):
+        a, b = C.c_size_t(0), C.c_size_t(0)
+        self._check(self._L.pcm_loam_keyframe_get(self._h, k, None, 0, None, 0, C.byref(a), C.byref(b)))
+        total += a.value + b.value
+    out = np.zeros((max(1, total), 4), np.float32)
+    self._check(self._L.pcm_loam_submap_near(self._h, int(key), int(search_num), int(wrt_key), float(leaf), out.ctypes.data, out.shape[0], C.byref(n)))
+    return out[:n.value].copy()
+
+
+def _loam_submap_info(self) -> dict:
+    """Parity hook: the last update's selection and its clouds before and after the VoxelGrids (pcm_loam_submap_info)."""
+    r = getattr(self, "_submap", None)
+    if r is None:
+        raise capi.PcmError(-2, "submap_info before update_submap")
+    out = {"keys": np.zeros(r.num_selected, np.int32), "corner_in": np.zeros((r.num_corner_in, 4), np.float32),
+           "surf_in": np.zeros((r.num_surf_in, 4), np.float32), "corner_map": np.zeros((r.num_corner_map, 4), np.float32),
+           "surf_map": np.zeros((r.num_surf_map, 4), np.float32)}
+    self._check(self._L.pcm_loam_submap_info(self._h, *(out[k].ctypes.data for k in ("keys", "corner_in", "surf_in", "corner_map", "surf_map"))))
+    return out
+
+
+LoamRegistration.add_keyframe = _loam_add_keyframe
+LoamRegistration.set_keyframe_poses = _loam_set_keyframe_poses
+LoamRegistration.num_keyframes = property(_loam_num_keyframes)
+LoamRegistration.clear_keyframes = _loam_clear_keyframes
+LoamRegistration.get_keyframe = _loam_get_keyframe
+LoamRegistration.update_submap = _loam_update_submap
+LoamRegistration.near_keyframes = _loam_near_keyframes
+LoamRegistration.submap_info = _loam_submap_info
+
+
 def loam_extract_features(reg: LoamRegistration, cloud, **feature_params):
     """One scan to (corner (Nc,4), surf (Ns,4), info): laserCloudCornerLastDS / laserCloudSurfLastDS as (x, y, z, intensity) on
     the host (pcm_loam_extract_features; the context's LOAM source is left as it is, its cross-frame state advances)."""

@@ -1,0 +1,150 @@
+"""CPU checks of the surrounding-key-frame selection (pointcloud-slam_amd/csrc/loam_submap.h, compiled with g++ through
+tests/loam_submap_hooks.cpp) against the numpy restatement (tests/loam_submap_ref.py), of the synthetic trajectories (they must
+exercise the reference's quirks: asserted on the restatement alone), hand-made known answers, and the layouts of the two
+pcm_loam_submap_* structs against the ctypes binding.  No GPU."""
+import ctypes as C
+import importlib
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import loam_submap_ref as R  # noqa: E402
+
+synth_keyframes = importlib.import_module("pointcloud-slam_amd.synth_keyframes")
+F = np.float32
+
+
+@pytest.fixture(scope="module")
+def H(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("submap_hooks") / "loam_submap_hooks.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I", os.path.join(ROOT, "pointcloud-slam_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "loam_submap_hooks.cpp"), "-o", so], check=True)
+    L = C.CDLL(so)
+    L.submap_hook_select.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_float, C.c_double, C.c_double, C.c_void_p, C.c_long, C.c_void_p]
+    L.submap_hook_select.restype = C.c_long
+    L.submap_hook_near.argtypes = [C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_long]
+    L.submap_hook_near.restype = C.c_long
+    L.submap_hook_layout.argtypes = [C.c_void_p]
+    return L
+
+
+def hook_select(H, poses, times, time_cur, radius, density=1.0, window=10.0):
+    poses = np.ascontiguousarray(poses, F)
+    times = np.ascontiguousarray(times, np.float64)
+    K = poses.shape[0]
+    keys = np.zeros(4 * K + 16, np.int32)
+    cnt = np.zeros(3, np.int32)
+    n = H.submap_hook_select(poses.ctypes.data, times.ctypes.data, K, radius, density, time_cur, window, keys.ctypes.data, keys.size, cnt.ctypes.data)
+    assert n >= 0, n
+    return keys[:n].copy(), tuple(int(v) for v in cnt)
+
+
+def quirks(sel):
+    """(leaves whose truncated mean index is not a member, duplicated entries, key frames outside the radius, skipped entries)"""
+    odd = sum(1 for leaf, mem in zip(sel.leaves, sel.leaf_members) if int(leaf[3]) not in set(int(m) for m in mem))
+    dup = len(sel.keys) - len(set(int(k) for k in sel.keys))
+    return odd, dup, None, sel.num_skipped
+
+
+CASES = [(K, seed, radius) for K in (40, 120, 200) for seed in (0, 1, 2) for radius in (15.0, 5.0)]
+
+
+@pytest.mark.parametrize("K,seed,radius", CASES)
+def test_selection_matches_restatement(H, K, seed, radius):
+    poses, times = synth_keyframes.make_trajectory(seed, K)
+    time_cur = float(times[-1] + 0.1)
+    ref = R.select(poses, times, time_cur, radius, 1.0)
+    keys, (near, leaves, skipped) = hook_select(H, poses, times, time_cur, radius)
+    assert np.array_equal(keys, ref.keys)
+    assert (near, leaves, skipped) == (ref.num_near, ref.num_pose_leaves, ref.num_skipped)
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_trajectories_exercise_the_quirks(seed):
+    """On the restatement alone: a test of the selection cannot pass by skipping what makes it odd."""
+    for K in (120, 200):
+        poses, times = synth_keyframes.make_trajectory(seed, K)
+        sel = R.select(poses, times, float(times[-1] + 0.1), 15.0, 1.0)
+        odd, dup, _, _ = quirks(sel)
+        outside = K - sel.num_near
+        print("K=%d seed=%d radius=15: truncated-mean leaves %d, duplicated entries %d, outside %d, skipped %d" % (K, seed, odd, dup, outside, sel.num_skipped))
+        assert odd >= 1 and dup >= 1 and outside >= 1
+        sel5 = R.select(poses, times, float(times[-1] + 0.1), 5.0, 1.0)
+        print("K=%d seed=%d radius=5: skipped %d" % (K, seed, sel5.num_skipped))
+        assert sel5.num_skipped >= 1
+    poses, times = synth_keyframes.make_trajectory(seed, 40)
+    sel = R.select(poses, times, float(times[-1] + 0.1), 15.0, 1.0)
+    assert quirks(sel)[0] == 0   # one lane: every leaf holds consecutive keys, the truncated mean is one of them
+
+
+def _poses(xyz):
+    p = np.zeros((len(xyz), 6), F)
+    p[:, 3:] = np.asarray(xyz, F)
+    return p
+
+
+def test_known_answers(H):
+    # one key frame: once from its leaf, once from the window
+    for fn in (lambda *a: hook_select(H, *a)[0], lambda *a: R.select(*a).keys):
+        assert list(fn(_poses([[1, 2, 3]]), [5.0], 5.1, 50.0)) == [0, 0]
+        # time_cur so late that the window is empty
+        assert list(fn(_poses([[1, 2, 3]]), [5.0], 15.0, 50.0)) == [0]
+        assert list(fn(_poses([[1, 2, 3]]), [5.0], 14.9, 50.0)) == [0, 0]
+        # two key frames in one pose leaf with indices {0, 3}: mean 1.5 -> key frame 1 is used, wherever it is
+        xyz = [[0.2, 0.2, 0.2], [30.0, 0.5, 0.5], [31.5, 0.5, 0.5], [0.6, 0.6, 0.6]]
+        assert list(fn(_poses(xyz), [0.0, 1.0, 2.0, 3.0], 100.0, 10.0)) == [1]
+        # a pose exactly at distance `radius` is outside (d2 < r2), so only the last one and the window remain
+        xyz = [[0.5, 0.5, 0.5], [3.5, 4.5, 0.5]]
+        assert list(fn(_poses(xyz), [0.0, 1.0], 100.0, 5.0)) == [1]
+        assert list(fn(_poses(xyz), [0.0, 1.0], 100.0, float(np.nextafter(F(5.0), F(6.0))))) == [0, 1]
+    keys, cnt = hook_select(H, _poses([[0.5, 0.5, 0.5], [3.5, 4.5, 0.5]]), [0.0, 1.0], 100.0, 5.0)
+    assert cnt == (1, 1, 0)
+
+
+def test_pose_grid_overflow_is_reported(H):
+    """A density so small, or poses so far apart, that the leaf index leaves int32 (or the float product is infinite): status -1,
+    decided before any float is converted to an integer."""
+    poses = np.ascontiguousarray(_poses([[0, 0, 0], [1, 1, 1]]))
+    times = np.array([0.0, 1.0])
+    keys = np.zeros(16, np.int32); cnt = np.zeros(3, np.int32)
+
+    def run(p, radius, density):
+        p = np.ascontiguousarray(p, F)
+        return H.submap_hook_select(p.ctypes.data, times.ctypes.data, 2, radius, density, 1.5, 10.0, keys.ctypes.data, keys.size, cnt.ctypes.data)
+
+    assert run(poses, 50.0, 1.0) == 4        # two leaves, two window entries
+    assert run(poses, 50.0, 1e-30) == -1
+    assert run(poses, 50.0, 1e-45) == -1      # 1 / density is infinite
+    assert run(poses, 50.0, 1e-4) == -1       # 10^4 cells per axis
+    far = _poses([[3e37, 0, 0], [3e37, 0, 0]])
+    assert run(far, 50.0, 1e-3) == -1         # one cell, but its coordinate does not fit an int
+    assert run(_poses([[-3e38, 0, 0], [3e38, 0, 0]]), 3e38, 1.0) == -1   # infinite extent
+
+
+def test_near_window(H):
+    def near(K, key, s):
+        out = np.zeros(2 * s + 1, np.int32)
+        n = H.submap_hook_near(K, key, s, out.ctypes.data, out.size)
+        return list(out[:n])
+    assert near(10, 0, 2) == [0, 1, 2]
+    assert near(10, 9, 2) == [7, 8, 9]
+    assert near(10, 5, 1) == [4, 5, 6]
+    assert near(2, 1, 25) == [0, 1]
+    assert near(0, 0, 3) == []
+
+
+def test_struct_layouts(H, pcm):
+    capi = pcm.capi
+    got = np.zeros(15, np.int64)
+    H.submap_hook_layout(got.ctypes.data)
+    P, Rs = capi.PcmLoamSubmapParams, capi.PcmLoamSubmapResult
+    want = [C.sizeof(P), P.keypose_density.offset, P.corner_leaf.offset, P.surf_leaf.offset, P.recent_window_s.offset, P.reserved.offset,
+            C.sizeof(Rs), Rs.num_pose_leaves.offset, Rs.num_skipped.offset, Rs.num_corner_in.offset, Rs.num_surf_map.offset, Rs.rebuilt.offset,
+            Rs.status.offset, Rs.reserved.offset, capi.PCM_ABI_VERSION]
+    assert list(got) == want
+    assert C.sizeof(P) == 56 and C.sizeof(Rs) == 64 and capi.PCM_ABI_VERSION == 3
