@@ -564,6 +564,88 @@ int pcm_loam_submap_near(pcm_ctx *ctx, int key, int search_num, int wrt_key, flo
  * transformed: num_*_in x 4 floats) and after the VoxelGrids (num_*_map x 4 floats).  Any pointer may be NULL. */
 int pcm_loam_submap_info(pcm_ctx *ctx, int32_t *keys, float *corner_in, float *surf_in, float *corner_map, float *surf_map);
 
+/*
+ * Scan Context descriptors and loop detection of jueying_slam on the device: SCManager::makeAndSaveScancontextAndKeys
+ * (Scancontext.cpp:151-250, called from saveKeyFramesAndFactor, mapOptmization.cpp:1848-1866), detectLoopClosureID (:253-344)
+ * and detectLoopClosureDistance (mapOptmization.cpp:843-880).  A PCM_MODEL_LOAM context keeps one descriptor (num_ring x
+ * num_sector, stored as float), its ring key, sector key and column norms per call of pcm_loam_sc_add / pcm_loam_sc_put; the
+ * loop thread is
+ *   pcm_loam_sc_add (per key frame) ... pcm_loam_sc_detect (per tick) -> pcm_loam_submap_near x 2 -> the caller's verification.
+ * DESIGN.md section 12.
+ */
+#define PCM_LOAM_SC_POINTS 0          /* the given cloud (SINGLE_SCAN_FULL), through the VoxelGrid of `leaf` */
+#define PCM_LOAM_SC_KEYFRAME_SURF 1   /* the stored surf cloud of key frame `key`, no VoxelGrid (SINGLE_SCAN_FEAT) */
+#define PCM_LOAM_SC_KEYFRAME_NEAR 2   /* MULTI_SCAN_FEAT: not built, PCM_ERR_UNSUPPORTED */
+
+typedef struct pcm_loam_sc_params {
+  double lidar_height;           /* 0.3   Scancontext.h:80 LIDAR_HEIGHT */
+  double max_radius;             /* 80.0  :84 PC_MAX_RADIUS, > 0 */
+  double search_ratio;           /* 0.1   :93 SEARCH_RATIO, in [0, 1] */
+  double dist_threshold;         /* 0.3   :95 SC_DIST_THRES */
+  int32_t num_ring;              /* 20    :82 PC_NUM_RING, 1..64; fixed by the first descriptor of a store */
+  int32_t num_sector;            /* 60    :83 PC_NUM_SECTOR, 1..360; fixed by the first descriptor of a store */
+  int32_t num_exclude_recent;    /* 30    :89 NUM_EXCLUDE_RECENT */
+  int32_t num_candidates;        /* 3     :90 NUM_CANDIDATES_FROM_TREE, 1..64; 0 = every entry of the search set (extension) */
+  int32_t tree_making_period;    /* 10    :99 TREE_MAKING_PERIOD_, >= 1 */
+  float leaf;                    /* 0.5   mapOptmization.cpp:239 kSCFilterSize (PCM_LOAM_SC_POINTS only); 0 = no down-sampling */
+  int32_t reserved[8];
+} pcm_loam_sc_params;
+
+typedef struct pcm_loam_sc_add_result {
+  int32_t index;                 /* of the new descriptor */
+  int32_t num_points_in;         /* points of the cloud */
+  int32_t num_points;            /* points the descriptor was built from (after the VoxelGrid) */
+  int32_t status;
+  int32_t reserved[4];
+} pcm_loam_sc_add_result;
+
+typedef struct pcm_loam_sc_result {
+  int32_t loop_id;               /* nn_idx when min_dist < dist_threshold, else -1 */
+  float yaw_diff_rad;            /* deg2rad(nn_align * 360 / num_sector), returned in both cases as the reference does */
+  double min_dist;               /* 10000000 when no candidate had a distance (all-empty descriptors) */
+  int32_t nn_idx;
+  int32_t nn_align;
+  int32_t num_descriptors;
+  int32_t tree_size;             /* entries of the (possibly stale) search set */
+  int32_t tree_rebuilt;          /* 1: this call took the search set anew */
+  int32_t num_evaluated;         /* candidates through distanceBtnScanContext */
+  int32_t status;
+  int32_t reserved0;
+  /* parity hooks: the first 64 candidates in candidate order (ascending (d2, index); with num_candidates 0, in index order) */
+  int32_t cand_index[64];
+  float cand_d2[64];             /* nanoflann's squared ring-key distance */
+  double cand_dist[64];          /* distanceBtnScanContext().first (10000000: no shift had an effective column) */
+  int32_t cand_shift[64];        /* .second */
+  int32_t reserved[8];
+} pcm_loam_sc_result;
+
+void pcm_loam_default_sc_params(pcm_loam_sc_params *params);
+/* makeAndSaveScancontextAndKeys of one cloud; `input` = PCM_LOAM_SC_*.  POINTS: n records of stride_bytes (x y z first) in host or
+ * device memory; KEYFRAME_SURF: key frame `key` of the context's key-frame store (points / n / stride_bytes / memory unused).
+ * A point with a non-finite coordinate is skipped.  params NULL = defaults; result may be NULL. */
+int pcm_loam_sc_add(pcm_ctx *ctx, const pcm_loam_sc_params *params, int input, int key, const void *points, size_t n, size_t stride_bytes, int memory,
+                    pcm_loam_sc_add_result *result);
+/* a ready descriptor (column-major doubles, ring fastest: the reference's Eigen::MatrixXd; every value must be representable as a
+ * float): the keys are derived on the device.  This is how the descriptors of a saved map are loaded. */
+int pcm_loam_sc_put(pcm_ctx *ctx, const double *desc, int num_ring, int num_sector);
+/* descriptor `index`: desc num_ring x num_sector doubles column-major, ring_key num_ring floats, sector_key num_sector doubles;
+ * any may be NULL */
+int pcm_loam_sc_get(pcm_ctx *ctx, int index, double *desc, float *ring_key, double *sector_key);
+int pcm_loam_sc_count(pcm_ctx *ctx);   /* descriptors, or a negative pcm_status */
+int pcm_loam_sc_shape(pcm_ctx *ctx, int *num_ring, int *num_sector);   /* of the stored descriptors; 0, 0 for an empty store */
+int pcm_loam_sc_clear(pcm_ctx *ctx);   /* also resets the tree counter */
+/* detectLoopClosureID: the last descriptor against the search set [0, count - num_exclude_recent) as of the last call whose
+ * counter was a multiple of tree_making_period.  Everything runs on the device; `result` is read back once.  The shape is the
+ * store's: num_ring / num_sector of params are not read here or in pcm_loam_sc_distance. */
+int pcm_loam_sc_detect(pcm_ctx *ctx, const pcm_loam_sc_params *params, pcm_loam_sc_result *result);
+/* distanceBtnScanContext(descriptor i, descriptor j) on the kernel of pcm_loam_sc_detect; params NULL = defaults (search_ratio) */
+int pcm_loam_sc_distance(pcm_ctx *ctx, const pcm_loam_sc_params *params, int i, int j, double *dist, int32_t *shift);
+/* detectLoopClosureDistance on the host mirror of the key poses (z replaced by 1.1f): the nearest key pose inside `radius`
+ * (10.0, historyKeyframeSearchRadius), in ascending (d2, index), whose |time - time_cur| > time_diff_s (30.0) and that lies more
+ * than 10 key frames back.  Returns 1 (found: *key_cur = K - 1, *key_pre), 0, or a negative pcm_status.  The loopIndexContainer
+ * test stays with the caller. */
+int pcm_loam_loop_detect_distance(pcm_ctx *ctx, float radius, double time_diff_s, double time_cur, int32_t *key_cur, int32_t *key_pre);
+
 /* profiling flags: bit0 = bracket every residual launch with HIP events on the
  * launch stream (pcm_stats.linearize_ms); bit1 = collect the kNN candidate /
  * probe counters (slower kernel variant; use in an untimed pass); bit2 = in-kernel

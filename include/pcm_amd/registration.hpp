@@ -499,6 +499,74 @@ private:
   std::vector<float> buf_, buf2_;
 };
 
+// jueying_slam's SCManager (include/Scancontext.h) on the context of a LoamScanToMap, with SCManager's user-side names:
+//     scManager.makeAndSaveScancontextAndKeys(*thisRawCloudKeyFrame);           // saveKeyFramesAndFactor, mapOptmization.cpp:1857
+//     auto detectResult = scManager.detectLoopClosureID();                      // :741: (nearest node or -1, relative yaw)
+// The descriptors live on the device (pcm_loam_sc_*).  Free of Eigen: getConstRefRecentSCD returns the last
+// descriptor as column-major doubles (num_ring x num_sector, the memory of the reference's MatrixXd).
+template <typename PointT>
+class LoamScanContext {
+public:
+  using Cloud = pcl::PointCloud<PointT>;
+
+  explicit LoamScanContext(LoamScanToMap<PointT>& loam) : ctx_(loam.context()) { pcm_loam_default_sc_params(&params_); }
+  pcm_loam_sc_params& params() { return params_; }
+  const pcm_loam_sc_result& result() const { return last_; }
+  int size() const { return pcm_loam_sc_count(ctx_); }                              // polarcontexts_.size()
+  void clear() { check(pcm_loam_sc_clear(ctx_), "pcm_loam_sc_clear"); }
+
+  // SINGLE_SCAN_FULL: the cloud goes through the VoxelGrid of params().leaf on the device (downSizeFilterSC)
+  void makeAndSaveScancontextAndKeys(const Cloud& scan) {
+    detail::pack_xyzi(scan, buf_);
+    check(pcm_loam_sc_add(ctx_, &params_, PCM_LOAM_SC_POINTS, -1, buf_.data(), scan.points.size(), 4 * sizeof(float), PCM_MEM_HOST, nullptr), "pcm_loam_sc_add");
+  }
+  // SINGLE_SCAN_FEAT: the stored surf cloud of a key frame of LoamKeyFrameMap, without leaving the device
+  void makeAndSaveScancontextAndKeysOfKeyFrame(int key) {
+    check(pcm_loam_sc_add(ctx_, &params_, PCM_LOAM_SC_KEYFRAME_SURF, key, nullptr, 0, 0, PCM_MEM_HOST, nullptr), "pcm_loam_sc_add");
+  }
+  // a descriptor of a saved map: column-major doubles
+  void putScancontext(const std::vector<double>& desc) { check(pcm_loam_sc_put(ctx_, desc.data(), params_.num_ring, params_.num_sector), "pcm_loam_sc_put"); }
+
+  std::pair<int, float> detectLoopClosureID() {
+    check(pcm_loam_sc_detect(ctx_, &params_, &last_), "pcm_loam_sc_detect");
+    return std::pair<int, float>(last_.loop_id, last_.yaw_diff_rad);
+  }
+  std::pair<double, int> distanceBtnScanContext(int i, int j) {
+    double d = 0.0;
+    int32_t s = 0;
+    check(pcm_loam_sc_distance(ctx_, &params_, i, j, &d, &s), "pcm_loam_sc_distance");
+    return std::pair<double, int>(d, (int)s);
+  }
+  const std::vector<double>& getConstRefRecentSCD() {
+    int R = 0, S = 0;
+    check(pcm_loam_sc_shape(ctx_, &R, &S), "pcm_loam_sc_shape");
+    recent_.assign((size_t)R * (size_t)S, 0.0);
+    if (size() > 0) check(pcm_loam_sc_get(ctx_, size() - 1, recent_.data(), nullptr, nullptr), "pcm_loam_sc_get");
+    return recent_;
+  }
+  // detectLoopClosureDistance (mapOptmization.cpp:843-880) on LoamKeyFrameMap's key poses; the loopIndexContainer test stays with
+  // the caller
+  bool detectLoopClosureDistance(int* latestID, int* closestID, double timeLaserInfoCur, float historyKeyframeSearchRadius = 10.0f,
+                                 double historyKeyframeSearchTimeDiff = 30.0) {
+    int32_t cur = -1, pre = -1;
+    const int rc = pcm_loam_loop_detect_distance(ctx_, historyKeyframeSearchRadius, historyKeyframeSearchTimeDiff, timeLaserInfoCur, &cur, &pre);
+    if (rc < 0) check(rc, "pcm_loam_loop_detect_distance");
+    if (rc != 1) return false;
+    *latestID = cur; *closestID = pre;
+    return true;
+  }
+
+private:
+  void check(int rc, const char* what) const {
+    if (rc != PCM_OK) throw std::runtime_error(std::string(what) + ": " + pcm_last_error(ctx_));
+  }
+  pcm_ctx* ctx_ = nullptr;
+  pcm_loam_sc_params params_;
+  pcm_loam_sc_result last_{};
+  std::vector<float> buf_;
+  std::vector<double> recent_;
+};
+
 // jueying_slam's LOAM front end (imageProjection.cpp:736-823, featureExtraction.cpp:84-247, mapOptmization.cpp:1232-1247) on the
 // device, for callers that want the features on the host.  PointIn: the driver's ring-tagged point (members x y z, intensity as
 // uint8, ring as uint16, e.g. imageProjection.cpp's PointXYZIRT); PointOut: PointType (x y z intensity).  One object per node: it

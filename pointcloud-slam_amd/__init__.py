@@ -11,5 +11,5 @@ from .capi import PcmError, build_library, library_path, load_library  # noqa: F
 from . import sharding  # noqa: F401
 from .registration import (GicpRegistration, NdtRegistration, P2PlaneRegistration, PclNdtRegistration, Registration, VgicpCudaRegistration, VgicpRegistration,  # noqa: F401
                            RegistrationResult, align_batch)
-from .registration import LoamRegistration, LoamResult, LoamSubmapResult, loam_align_batch  # noqa: F401
+from .registration import LoamRegistration, LoamResult, LoamSubmapResult, LoamLoopResult, loam_align_batch  # noqa: F401
 from .registration import loam_extract_features, loam_frame_begin_batch, pack_xyzirt  # noqa: F401

@@ -21,6 +21,8 @@ SYMBOLS = [
     "pcm_loam_feature_info",
     "pcm_loam_default_submap_params", "pcm_loam_keyframe_add", "pcm_loam_keyframe_set_poses", "pcm_loam_keyframe_count", "pcm_loam_keyframe_clear",
     "pcm_loam_keyframe_get", "pcm_loam_submap_update", "pcm_loam_submap_near", "pcm_loam_submap_info",
+    "pcm_loam_default_sc_params", "pcm_loam_sc_add", "pcm_loam_sc_put", "pcm_loam_sc_get", "pcm_loam_sc_count", "pcm_loam_sc_shape", "pcm_loam_sc_clear",
+    "pcm_loam_sc_detect", "pcm_loam_sc_distance", "pcm_loam_loop_detect_distance",
 ]
 
 PCM_ABI_VERSION = 3   # include/pcm_amd.h
@@ -127,6 +129,26 @@ class PcmLoamSubmapResult(C.Structure):
                 ("num_surf_map", C.c_int32), ("rebuilt", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
+PCM_LOAM_SC_POINTS, PCM_LOAM_SC_KEYFRAME_SURF, PCM_LOAM_SC_KEYFRAME_NEAR = 0, 1, 2
+
+
+class PcmLoamScParams(C.Structure):
+    _fields_ = [("lidar_height", C.c_double), ("max_radius", C.c_double), ("search_ratio", C.c_double), ("dist_threshold", C.c_double),
+                ("num_ring", C.c_int32), ("num_sector", C.c_int32), ("num_exclude_recent", C.c_int32), ("num_candidates", C.c_int32),
+                ("tree_making_period", C.c_int32), ("leaf", C.c_float), ("reserved", C.c_int32 * 8)]
+
+
+class PcmLoamScAddResult(C.Structure):
+    _fields_ = [("index", C.c_int32), ("num_points_in", C.c_int32), ("num_points", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class PcmLoamScResult(C.Structure):
+    _fields_ = [("loop_id", C.c_int32), ("yaw_diff_rad", C.c_float), ("min_dist", C.c_double), ("nn_idx", C.c_int32), ("nn_align", C.c_int32),
+                ("num_descriptors", C.c_int32), ("tree_size", C.c_int32), ("tree_rebuilt", C.c_int32), ("num_evaluated", C.c_int32),
+                ("status", C.c_int32), ("reserved0", C.c_int32), ("cand_index", C.c_int32 * 64), ("cand_d2", C.c_float * 64),
+                ("cand_dist", C.c_double * 64), ("cand_shift", C.c_int32 * 64), ("reserved", C.c_int32 * 8)]
+
+
 def library_path() -> str:
     """The in-tree build; PCM_AMD_LIBRARY names another build of the same ABI (A/B measurements of two builds on one box)."""
     return os.environ.get("PCM_AMD_LIBRARY") or os.path.join(_HERE, "libpcm_amd.so")
@@ -231,5 +253,16 @@ def load_library():
     L.pcm_loam_submap_update.argtypes = [vp, C.POINTER(PcmLoamSubmapParams), C.c_double, C.POINTER(PcmLoamSubmapResult)]
     L.pcm_loam_submap_near.argtypes = [vp, i32, i32, i32, C.c_float, vp, sz, C.POINTER(sz)]
     L.pcm_loam_submap_info.argtypes = [vp] * 6
+    L.pcm_loam_default_sc_params.argtypes = [C.POINTER(PcmLoamScParams)]
+    L.pcm_loam_default_sc_params.restype = None
+    L.pcm_loam_sc_add.argtypes = [vp, C.POINTER(PcmLoamScParams), i32, i32, vp, sz, sz, i32, C.POINTER(PcmLoamScAddResult)]
+    L.pcm_loam_sc_put.argtypes = [vp, vp, i32, i32]
+    L.pcm_loam_sc_get.argtypes = [vp, i32, vp, vp, vp]
+    L.pcm_loam_sc_count.argtypes = [vp]
+    L.pcm_loam_sc_shape.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.pcm_loam_sc_clear.argtypes = [vp]
+    L.pcm_loam_sc_detect.argtypes = [vp, C.POINTER(PcmLoamScParams), C.POINTER(PcmLoamScResult)]
+    L.pcm_loam_sc_distance.argtypes = [vp, C.POINTER(PcmLoamScParams), i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+    L.pcm_loam_loop_detect_distance.argtypes = [vp, C.c_float, C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     _LIB = L
     return L

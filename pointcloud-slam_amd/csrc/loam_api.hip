@@ -42,6 +42,7 @@ struct LoamCtx {
   uint64_t src_fe_gen = 0;     // generation of that output when the source was committed
   bool tgt_from_submap = false;   // the target clouds are what loam_target_commit left
   void* keystore = nullptr;    // key frames and submap workspace (loam_submap.hip)
+  void* scstore = nullptr;     // Scan Context descriptors and loop-detection workspace (loam_sc.hip)
   uint32_t n_c = 0, n_s = 0;
   double* partials = nullptr;
   size_t partials_cap = 0;     // doubles
@@ -382,6 +383,7 @@ void loam_release(pcm_ctx* c) {
   if (!L) return;
   for (int m = 0; m < 2; m++) { L->map_cloud[m].release(); L->map[m].release(); }
   if (L->keystore) loam::loam_keystore_release(L->keystore);
+  if (L->scstore) loam::loam_scstore_release(L->scstore);
   if (L->feats) hipFree(L->feats);
   if (L->src_int) hipFree(L->src_int);
   if (L->partials) hipFree(L->partials);
@@ -469,6 +471,11 @@ int loam_source_view(pcm_ctx* c, const float4** feats, uint32_t* n_c, uint32_t* 
 void** loam_keystore_slot(pcm_ctx* c) {
   LoamCtx* L = loam_of(c);
   return L ? &L->keystore : nullptr;
+}
+
+void** loam_scstore_slot(pcm_ctx* c) {
+  LoamCtx* L = loam_of(c);
+  return L ? &L->scstore : nullptr;
 }
 }  // namespace loam
 }  // namespace pcm

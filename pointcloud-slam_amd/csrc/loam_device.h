@@ -50,6 +50,14 @@ int loam_source_view(pcm_ctx* c, const float4** feats, uint32_t* n_c, uint32_t* 
 // the key-frame store of a context (pcm_ctx::loam owns the pointer, loam_submap.hip the type)
 void** loam_keystore_slot(pcm_ctx* c);
 void loam_keystore_release(void* store);
+// loam_submap.hip: one stored cloud of a key frame on the device (which: 0 corner, 1 surf; false: no such key frame), and the host
+// mirror of the key poses (returns K)
+bool loam_keyframe_cloud(pcm_ctx* c, int key, int which, const float4** pts, uint32_t* n);
+struct KeyPose;
+int loam_keyposes(pcm_ctx* c, const KeyPose** kp);
+// the Scan Context store of a context (pcm_ctx::loam owns the pointer, loam_sc.hip the type)
+void** loam_scstore_slot(pcm_ctx* c);
+void loam_scstore_release(void* store);
 
 // loam_features.hip: pieces of the segmented VoxelGrid that do not depend on where the elements live
 struct SvWork {

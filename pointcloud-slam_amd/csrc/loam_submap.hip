@@ -345,6 +345,23 @@ void loam_keystore_release(void* store) {
   S->near.release();
   delete S;
 }
+
+bool loam_keyframe_cloud(pcm_ctx* c, int key, int which, const float4** pts, uint32_t* n) {
+  void** slot = loam_keystore_slot(c);
+  const KeyStore* S = slot ? static_cast<const KeyStore*>(*slot) : nullptr;
+  if (!S || key < 0 || (size_t)key >= S->kf.size()) return false;
+  const KeyFrame& k = S->kf[(size_t)key];
+  *pts = S->arena[which ? 1 : 0].d + (which ? k.off_s : k.off_c);
+  *n = which ? k.n_s : k.n_c;
+  return true;
+}
+
+int loam_keyposes(pcm_ctx* c, const KeyPose** kp) {
+  void** slot = loam_keystore_slot(c);
+  const KeyStore* S = slot ? static_cast<const KeyStore*>(*slot) : nullptr;
+  *kp = S ? S->kp.data() : nullptr;
+  return S ? (int)S->kf.size() : 0;
+}
 }  // namespace loam
 }  // namespace pcm
 

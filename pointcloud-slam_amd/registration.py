@@ -801,6 +801,127 @@ LoamRegistration.near_keyframes = _loam_near_keyframes
 LoamRegistration.submap_info = _loam_submap_info
 
 
+@dataclasses.dataclass
+class LoamLoopResult:
+    """pcm_loam_sc_detect: detectLoopClosureID's pair (loop_id, yaw_diff_rad) and what led to it; ``candidates`` = one
+    (index, ring-key d2, distance, shift) per evaluated candidate (the first 64), in candidate order."""
+    loop_id: int
+    yaw_diff_rad: float
+    min_dist: float
+    nn_idx: int
+    nn_align: int
+    num_descriptors: int
+    tree_size: int
+    tree_rebuilt: bool
+    num_evaluated: int
+    candidates: list
+    status: int
+
+
+def _sc_params(L, params: dict) -> capi.PcmLoamScParams:
+    p = capi.PcmLoamScParams()
+    L.pcm_loam_default_sc_params(C.byref(p))
+    for k, v in params.items():
+        if k.startswith("reserved") or not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _loam_sc_add(self, points=None, keyframe=None, near=None, **params) -> int:
+    """makeAndSaveScancontextAndKeys of one cloud: ``points`` (an (N,>=3) float32 host array or a contiguous (N,C) float32 device
+    tensor; VoxelGrid of ``leaf`` first), or the stored surf cloud of key frame ``keyframe``.  Returns the descriptor's index."""
+    if sum(a is not None for a in (points, keyframe, near)) != 1:
+        raise ValueError("pass exactly one of points, keyframe, near")
+    p = _sc_params(self._L, params)
+    r = capi.PcmLoamScAddResult()
+    if near is not None:
+        self._check(self._L.pcm_loam_sc_add(self._h, C.byref(p), capi.PCM_LOAM_SC_KEYFRAME_NEAR, int(near), None, 0, 16, capi.MEM_HOST, C.byref(r)))
+    elif keyframe is not None:
+        self._check(self._L.pcm_loam_sc_add(self._h, C.byref(p), capi.PCM_LOAM_SC_KEYFRAME_SURF, int(keyframe), None, 0, 16, capi.MEM_HOST, C.byref(r)))
+    elif hasattr(points, "data_ptr") and getattr(points, "is_cuda", False):
+        if points.dim() != 2 or points.shape[1] < 3 or not points.is_contiguous() or points.element_size() != 4:
+            raise ValueError("expected a contiguous (N,>=3) float32 device tensor")
+        self._check(self._L.pcm_loam_sc_add(self._h, C.byref(p), capi.PCM_LOAM_SC_POINTS, -1, points.data_ptr(), points.shape[0], 4 * points.shape[1],
+                                            capi.MEM_DEVICE, C.byref(r)))
+    else:
+        a = np.ascontiguousarray(points, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] < 3:
+            raise ValueError("expected an (N,>=3) float32 array")
+        self._check(self._L.pcm_loam_sc_add(self._h, C.byref(p), capi.PCM_LOAM_SC_POINTS, -1, a.ctypes.data, a.shape[0], 4 * a.shape[1], capi.MEM_HOST, C.byref(r)))
+    self._sc_last_add = r
+    return r.index
+
+
+def _loam_sc_put(self, desc):
+    """A ready (num_ring, num_sector) descriptor (e.g. of a saved map); its keys are derived on the device."""
+    d = np.asarray(desc, dtype=np.float64)
+    if d.ndim != 2:
+        raise ValueError("expected a (num_ring, num_sector) array")
+    col = np.ascontiguousarray(d.T)   # column-major, ring fastest
+    self._check(self._L.pcm_loam_sc_put(self._h, col.ctypes.data, d.shape[0], d.shape[1]))
+
+
+def _loam_sc_count(self) -> int:
+    n = self._L.pcm_loam_sc_count(self._h)
+    if n < 0:
+        self._check(n)
+    return n
+
+
+def _loam_sc_get(self, i: int):
+    """(descriptor (num_ring, num_sector) float64, ring key (num_ring,) float32, sector key (num_sector,) float64)."""
+    R, S = C.c_int(0), C.c_int(0)
+    self._check(self._L.pcm_loam_sc_shape(self._h, C.byref(R), C.byref(S)))
+    col = np.zeros((max(1, S.value), max(1, R.value)))
+    rk = np.zeros(max(1, R.value), np.float32)
+    sk = np.zeros(max(1, S.value))
+    self._check(self._L.pcm_loam_sc_get(self._h, int(i), col.ctypes.data, rk.ctypes.data, sk.ctypes.data))
+    return np.ascontiguousarray(col.T), rk, sk
+
+
+def _loam_sc_clear(self):
+    self._check(self._L.pcm_loam_sc_clear(self._h))
+
+
+def _loam_sc_detect(self, **params) -> LoamLoopResult:
+    """detectLoopClosureID of the last descriptor (pcm_loam_sc_detect); num_candidates=0 compares against the whole search set."""
+    p = _sc_params(self._L, params)
+    r = capi.PcmLoamScResult()
+    self._check(self._L.pcm_loam_sc_detect(self._h, C.byref(p), C.byref(r)))
+    m = min(64, r.num_evaluated)
+    cands = [(r.cand_index[t], float(np.float32(r.cand_d2[t])), r.cand_dist[t], r.cand_shift[t]) for t in range(m)]
+    return LoamLoopResult(r.loop_id, r.yaw_diff_rad, r.min_dist, r.nn_idx, r.nn_align, r.num_descriptors, r.tree_size, bool(r.tree_rebuilt),
+                          r.num_evaluated, cands, r.status)
+
+
+def _loam_sc_distance(self, i: int, j: int, **params):
+    """distanceBtnScanContext(descriptor i, descriptor j) -> (distance, shift)."""
+    p = _sc_params(self._L, params)
+    d, s = C.c_double(0.0), C.c_int32(0)
+    self._check(self._L.pcm_loam_sc_distance(self._h, C.byref(p), int(i), int(j), C.byref(d), C.byref(s)))
+    return d.value, s.value
+
+
+def _loam_detect_loop_distance(self, time_cur, radius: float = 10.0, time_diff_s: float = 30.0):
+    """detectLoopClosureDistance on the stored key poses: (key_cur, key_pre) or None."""
+    a, b = C.c_int32(-1), C.c_int32(-1)
+    rc = self._L.pcm_loam_loop_detect_distance(self._h, float(radius), float(time_diff_s), float(time_cur), C.byref(a), C.byref(b))
+    if rc < 0:
+        self._check(rc)
+    return (a.value, b.value) if rc == 1 else None
+
+
+LoamRegistration.sc_add = _loam_sc_add
+LoamRegistration.sc_put = _loam_sc_put
+LoamRegistration.sc_get = _loam_sc_get
+LoamRegistration.sc_count = property(_loam_sc_count)
+LoamRegistration.sc_clear = _loam_sc_clear
+LoamRegistration.sc_detect = _loam_sc_detect
+LoamRegistration.sc_distance = _loam_sc_distance
+LoamRegistration.detect_loop_distance = _loam_detect_loop_distance
+
+
 def loam_extract_features(reg: LoamRegistration, cloud, **feature_params):
     """One scan to (corner (Nc,4), surf (Ns,4), info): laserCloudCornerLastDS / laserCloudSurfLastDS as (x, y, z, intensity) on
     the host (pcm_loam_extract_features; the context's LOAM source is left as it is, its cross-frame state advances)."""
