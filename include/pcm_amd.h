@@ -646,6 +646,60 @@ int pcm_loam_sc_distance(pcm_ctx *ctx, const pcm_loam_sc_params *params, int i, 
  * test stays with the caller. */
 int pcm_loam_loop_detect_distance(pcm_ctx *ctx, float radius, double time_diff_s, double time_cur, int32_t *key_cur, int32_t *key_pre);
 
+/*
+ * 2D occupancy grid mapping of jueying_slam's map tool (src/tool/occupancy_mapping) on the device: getScan (cloud -> virtual
+ * laser scan), processScan + TraceLine (rays into the grid), getGridMap (crop, -1 / 0 / 100) and saveMap's PGM bytes.  The map
+ * belongs to a context of any model; a PCM_MODEL_LOAM context can also feed it from its key-frame store in place.  Offline
+ * (OccupancyServerFromFile, use_file_num 2) and after a loop closure:
+ *   pcm_occ_reset -> pcm_occ_insert_keyframes [0, K) -> pcm_occ_info / pcm_occ_get_map;
+ * online (OccupancyServerRealTime): pcm_occ_insert_scans per cloud.  A cell holds two uint32 counters (end-point hits, ray
+ * passes; they wrap after 2^32 updates of one cell) and its value is defined from them:
+ *   logit = (double)n_occ * log_occ + (double)n_free * log_free, occupied when 1 / (1 + exp(-logit)) * 100 >= 50
+ * (the reference adds the updates in visit order, which is not associative).  The grid is a dense rectangle of at most 2^28
+ * cells that grows with the poses; a batch that would exceed it returns PCM_ERR_INVALID_ARGUMENT.  DESIGN.md section 13.
+ */
+typedef struct pcm_occ_params {
+  double min_z;                  /* -0.15  config/rslidar.yaml: points with min_z <= z <= max_z (sensor frame) make the scan */
+  double max_z;                  /* 1.5 */
+  double angle_increment;        /* 0.006  beam width in rad: ceil(2 * 3.1415927 / angle_increment) beams, at most 2^20 */
+  double min_range;              /* 0.5    a beam keeps the smallest range in [min_range, max_range] */
+  double max_range;              /* 200 */
+  double log_occ;                /* 0.1    update of the end cell */
+  double log_free;               /* -0.01  update of a cell a ray passes */
+  double resolution;             /* 0.1    metres per cell */
+  double max_radius;             /* 20     longer beams are clipped to max_radius + 0.1 and hit nothing */
+  int32_t fill_with_white;       /* 1      trace clipped beams as free space */
+  int32_t use_nan;               /* 0      empty beams count as clipped beams */
+  int32_t reserved[8];
+} pcm_occ_params;
+
+void pcm_occ_default_params(pcm_occ_params *params);
+/* an empty map with these parameters (NULL = defaults); they hold until the next reset.  Device memory is kept. */
+int pcm_occ_reset(pcm_ctx *ctx, const pcm_occ_params *params);
+/* num_scans clouds in the sensor frame, one after the other in `points` (records of stride_bytes, x y z first; host or device
+ * memory), n_points[s] records and poses6 + 6 s (roll, pitch, yaw, x, y, z as pcm_loam_align; yaw, x, y are used) for scan s, in one
+ * set of launches.  The first scan after a reset also initialises the map at its cell (initializeMap).  A point with a
+ * non-finite coordinate is skipped.  The counters do not depend on how scans are split into calls. */
+int pcm_occ_insert_scans(pcm_ctx *ctx, const void *points, const size_t *n_points, const float *poses6, int num_scans, size_t stride_bytes, int memory);
+/* PCM_MODEL_LOAM: key frames first .. first + n - 1 of the context's store, each one virtual scan from its corner and surf
+ * cloud together under its stored pose, read where they lie on the device */
+int pcm_occ_insert_keyframes(pcm_ctx *ctx, int first, int n);
+/* parity hook: virtual scan s of the last call (of its last 2^24 / beams scans): beam_size ranges (NaN = empty beam) and angles;
+ * either may be NULL */
+int pcm_occ_get_scan(pcm_ctx *ctx, int s, float *ranges, double *angles);
+/* beam_size, scans inserted since the reset, updates dropped outside the allocation (always 0; an insert that drops one returns
+ * PCM_ERR_INTERNAL) and the allocated rectangle {x0, y0, width, height} in cells; any pointer may be NULL */
+int pcm_occ_status(pcm_ctx *ctx, int32_t *beam_size, uint64_t *n_scans, uint64_t *overflow, int64_t rect[4]);
+/* the map cropped to the bounding box of its known cells, as nav_msgs/OccupancyGrid: origin = first cell index * resolution;
+ * width = height = 0 for an empty map; any pointer may be NULL */
+int pcm_occ_info(pcm_ctx *ctx, int32_t *width, int32_t *height, double *origin_x, double *origin_y, double *resolution, int64_t *n_known);
+/* width x height values, row-major (i + j * width): -1 unknown, 0 free, 100 occupied; capacity in cells */
+int pcm_occ_get_map(pcm_ctx *ctx, int8_t *data, size_t capacity);
+/* the body of saveMap's P5 image: width x height bytes, rows top-down (205 unknown, 254 free, 0 occupied) */
+int pcm_occ_get_pgm(pcm_ctx *ctx, uint8_t *data, size_t capacity);
+/* the counters of the same rectangle (either may be NULL): what a caller needs to apply a threshold of its own */
+int pcm_occ_get_counts(pcm_ctx *ctx, uint32_t *n_occ, uint32_t *n_free, size_t capacity);
+
 /* profiling flags: bit0 = bracket every residual launch with HIP events on the
  * launch stream (pcm_stats.linearize_ms); bit1 = collect the kNN candidate /
  * probe counters (slower kernel variant; use in an untimed pass); bit2 = in-kernel

@@ -567,6 +567,62 @@ private:
   std::vector<double> recent_;
 };
 
+// jueying_slam's 2D occupancy mapping tool (src/tool/occupancy_mapping) on the device: OccupancyServer's getScan + processScan per
+// cloud, getGridMap and saveMap's image.  Constructed alone it owns a context (the online node, OccupancyServerRealTime: tf lookups
+// and the sensor-tilt pre-rotation stay with the caller); constructed over a LoamScanToMap it maps that context's key frames in
+// place (the offline node with two files per frame, and the rebuild after a loop closure).  File writing stays with the caller.
+template <typename PointT>
+class OccupancyMap2D {
+public:
+  using Cloud = pcl::PointCloud<PointT>;
+
+  explicit OccupancyMap2D(int device = 0) : ctx_(pcm_create(device, nullptr)), own_(true) {
+    if (!ctx_) throw std::runtime_error("pcm_create failed");
+    pcm_occ_default_params(&params_);
+  }
+  explicit OccupancyMap2D(LoamScanToMap<PointT>& loam) : ctx_(loam.context()), own_(false) { pcm_occ_default_params(&params_); }
+  ~OccupancyMap2D() { if (own_ && ctx_) pcm_destroy(ctx_); }
+  OccupancyMap2D(const OccupancyMap2D&) = delete;
+  OccupancyMap2D& operator=(const OccupancyMap2D&) = delete;
+
+  pcm_occ_params& params() { return params_; }             // read by the next initializeMap()
+  void initializeMap() { check(pcm_occ_reset(ctx_, &params_), "pcm_occ_reset"); }
+  // getScan + processScan; robot_pose = roll, pitch, yaw, x, y, z
+  void processCloud(const Cloud& cloud, const std::vector<double>& robot_pose) {
+    detail::pack_xyzi(cloud, buf_);
+    float pose[6];
+    for (int k = 0; k < 6; k++) pose[k] = (float)robot_pose[(size_t)k];
+    const size_t n = cloud.points.size();
+    check(pcm_occ_insert_scans(ctx_, buf_.data(), &n, pose, 1, 4 * sizeof(float), PCM_MEM_HOST), "pcm_occ_insert_scans");
+  }
+  // key frames first .. first + n - 1 of LoamKeyFrameMap, corner and surf cloud as one scan, without leaving the device
+  void processKeyFrames(int first, int n) { check(pcm_occ_insert_keyframes(ctx_, first, n), "pcm_occ_insert_keyframes"); }
+  // nav_msgs/OccupancyGrid: info.width / height / resolution / origin.position and data
+  void getGridMap(std::vector<int8_t>* data, int* width, int* height, double* origin_x, double* origin_y, double* resolution) {
+    int32_t w = 0, h = 0;
+    check(pcm_occ_info(ctx_, &w, &h, origin_x, origin_y, resolution, nullptr), "pcm_occ_info");
+    data->assign((size_t)w * (size_t)h, (int8_t)-1);
+    check(pcm_occ_get_map(ctx_, data->data(), data->size()), "pcm_occ_get_map");
+    *width = w; *height = h;
+  }
+  // the body of saveMap's P5 image (after the "P5 ... 255" header), rows top-down
+  void getPgm(std::vector<uint8_t>* bytes) {
+    int32_t w = 0, h = 0;
+    check(pcm_occ_info(ctx_, &w, &h, nullptr, nullptr, nullptr, nullptr), "pcm_occ_info");
+    bytes->assign((size_t)w * (size_t)h, (uint8_t)205);
+    check(pcm_occ_get_pgm(ctx_, bytes->data(), bytes->size()), "pcm_occ_get_pgm");
+  }
+
+private:
+  void check(int rc, const char* what) const {
+    if (rc != PCM_OK) throw std::runtime_error(std::string(what) + ": " + pcm_last_error(ctx_));
+  }
+  pcm_ctx* ctx_ = nullptr;
+  bool own_ = false;
+  pcm_occ_params params_;
+  std::vector<float> buf_;
+};
+
 // jueying_slam's LOAM front end (imageProjection.cpp:736-823, featureExtraction.cpp:84-247, mapOptmization.cpp:1232-1247) on the
 // device, for callers that want the features on the host.  PointIn: the driver's ring-tagged point (members x y z, intensity as
 // uint8, ring as uint16, e.g. imageProjection.cpp's PointXYZIRT); PointOut: PointType (x y z intensity).  One object per node: it

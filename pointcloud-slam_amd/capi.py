@@ -23,6 +23,8 @@ SYMBOLS = [
     "pcm_loam_keyframe_get", "pcm_loam_submap_update", "pcm_loam_submap_near", "pcm_loam_submap_info",
     "pcm_loam_default_sc_params", "pcm_loam_sc_add", "pcm_loam_sc_put", "pcm_loam_sc_get", "pcm_loam_sc_count", "pcm_loam_sc_shape", "pcm_loam_sc_clear",
     "pcm_loam_sc_detect", "pcm_loam_sc_distance", "pcm_loam_loop_detect_distance",
+    "pcm_occ_default_params", "pcm_occ_reset", "pcm_occ_insert_scans", "pcm_occ_insert_keyframes", "pcm_occ_get_scan", "pcm_occ_status",
+    "pcm_occ_info", "pcm_occ_get_map", "pcm_occ_get_pgm", "pcm_occ_get_counts",
 ]
 
 PCM_ABI_VERSION = 3   # include/pcm_amd.h
@@ -149,6 +151,12 @@ class PcmLoamScResult(C.Structure):
                 ("cand_dist", C.c_double * 64), ("cand_shift", C.c_int32 * 64), ("reserved", C.c_int32 * 8)]
 
 
+class PcmOccParams(C.Structure):
+    _fields_ = [("min_z", C.c_double), ("max_z", C.c_double), ("angle_increment", C.c_double), ("min_range", C.c_double),
+                ("max_range", C.c_double), ("log_occ", C.c_double), ("log_free", C.c_double), ("resolution", C.c_double),
+                ("max_radius", C.c_double), ("fill_with_white", C.c_int32), ("use_nan", C.c_int32), ("reserved", C.c_int32 * 8)]
+
+
 def library_path() -> str:
     """The in-tree build; PCM_AMD_LIBRARY names another build of the same ABI (A/B measurements of two builds on one box)."""
     return os.environ.get("PCM_AMD_LIBRARY") or os.path.join(_HERE, "libpcm_amd.so")
@@ -264,5 +272,17 @@ def load_library():
     L.pcm_loam_sc_detect.argtypes = [vp, C.POINTER(PcmLoamScParams), C.POINTER(PcmLoamScResult)]
     L.pcm_loam_sc_distance.argtypes = [vp, C.POINTER(PcmLoamScParams), i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     L.pcm_loam_loop_detect_distance.argtypes = [vp, C.c_float, C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.pcm_occ_default_params.argtypes = [C.POINTER(PcmOccParams)]
+    L.pcm_occ_default_params.restype = None
+    L.pcm_occ_reset.argtypes = [vp, C.POINTER(PcmOccParams)]
+    L.pcm_occ_insert_scans.argtypes = [vp, vp, vp, vp, i32, sz, i32]
+    L.pcm_occ_insert_keyframes.argtypes = [vp, i32, i32]
+    L.pcm_occ_get_scan.argtypes = [vp, i32, vp, vp]
+    L.pcm_occ_status.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_int64)]
+    L.pcm_occ_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                               C.POINTER(C.c_int64)]
+    L.pcm_occ_get_map.argtypes = [vp, vp, sz]
+    L.pcm_occ_get_pgm.argtypes = [vp, vp, sz]
+    L.pcm_occ_get_counts.argtypes = [vp, vp, vp, sz]
     _LIB = L
     return L

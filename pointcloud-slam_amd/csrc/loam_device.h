@@ -53,6 +53,7 @@ void loam_keystore_release(void* store);
 // loam_submap.hip: one stored cloud of a key frame on the device (which: 0 corner, 1 surf; false: no such key frame), and the host
 // mirror of the key poses (returns K)
 bool loam_keyframe_cloud(pcm_ctx* c, int key, int which, const float4** pts, uint32_t* n);
+bool loam_keyframe_pose(pcm_ctx* c, int key, float pose6[6]);   // roll, pitch, yaw, x, y, z as stored
 struct KeyPose;
 int loam_keyposes(pcm_ctx* c, const KeyPose** kp);
 // the Scan Context store of a context (pcm_ctx::loam owns the pointer, loam_sc.hip the type)

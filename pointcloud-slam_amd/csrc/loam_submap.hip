@@ -356,6 +356,14 @@ bool loam_keyframe_cloud(pcm_ctx* c, int key, int which, const float4** pts, uin
   return true;
 }
 
+bool loam_keyframe_pose(pcm_ctx* c, int key, float pose6[6]) {
+  void** slot = loam_keystore_slot(c);
+  const KeyStore* S = slot ? static_cast<const KeyStore*>(*slot) : nullptr;
+  if (!S || key < 0 || (size_t)key >= S->kf.size()) return false;
+  for (int a = 0; a < 6; a++) pose6[a] = S->kf[(size_t)key].pose[a];
+  return true;
+}
+
 int loam_keyposes(pcm_ctx* c, const KeyPose** kp) {
   void** slot = loam_keystore_slot(c);
   const KeyStore* S = slot ? static_cast<const KeyStore*>(*slot) : nullptr;

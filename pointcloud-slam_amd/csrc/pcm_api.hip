@@ -1164,6 +1164,7 @@ void pcm_destroy(pcm_ctx* c) {
     if (c->nn) hipFree(c->nn);
     free_ws(c);
     loam_release(c);
+    occ_release(c);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
   }
   delete c;

@@ -176,6 +176,8 @@ void launch_pack_results(hipStream_t stream, const PairState* d_states, pcm_resu
 void loam_release(pcm_ctx* c);
 // loam_features.hip: the front end's cross-frame state of a PCM_MODEL_LOAM context (pcm_ctx::loam_fe)
 void loam_features_release(pcm_ctx* c);
+// occ_map.hip: the 2D occupancy map of a context (pcm_ctx::occ)
+void occ_release(pcm_ctx* c);
 
 }  // namespace pcm
 
@@ -243,5 +245,6 @@ struct pcm_ctx {
   double* bfgs_host = nullptr; // pinned, device-visible: the 14 sums land here without a copy command
   void* loam = nullptr;   // PCM_MODEL_LOAM: maps, features and device state (loam_api.hip)
   void* loam_fe = nullptr;   // PCM_MODEL_LOAM: the front end's cross-frame state and last-frame outputs (loam_features.hip)
+  void* occ = nullptr;   // any model: the 2D occupancy map (occ_map.hip)
   int profiling = 0;  // bit0: HIP-event timing of residual launches, bit1: kNN counters
 };
