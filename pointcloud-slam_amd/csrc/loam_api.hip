@@ -4,8 +4,8 @@
 // Host side of jueying_slam's scan2MapOptimization (mapOptmization.cpp:1560-1586): the reference builds two FLANN kd-trees
 // (:1569-1570) and runs every iteration on the host; here the two maps become brick-hashed grids (build_target_map) built
 // once per map (the tag rule keeps them across frames) and all iterations are queued without a host round trip.
+#include "host_util.h"
 #include "loam_device.h"
-#include "pcm_host.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -18,25 +18,15 @@ using namespace pcm::loam;
 
 namespace {
 
-#define LCK(ctx, x)                                                                  \
-  do {                                                                               \
-    hipError_t e_ = (x);                                                             \
-    if (e_ != hipSuccess) {                                                          \
-      (ctx)->err = std::string(#x) + ": " + hipGetErrorString(e_);                   \
-      return PCM_ERR_HIP;                                                            \
-    }                                                                                \
-  } while (0)
-
 struct LoamCtx {
-  Cloud map_cloud[2];          // corner / surf map, caller order (float4)
+  DevBuf<float4> map_pts[2];   // corner / surf map, caller order
+  size_t map_n[2] = {0, 0};
   TargetMap map[2];
   float built_cell = 0.f;      // cell of the grids in map[] (0: not built)
   uint64_t tgt_tag = 0, src_tag = 0;
   bool have_tgt = false, have_src = false;
-  float4* feats = nullptr;     // corner features, then surf features (body frame)
-  size_t feats_cap = 0;
-  float* src_int = nullptr;    // pcm_loam_set_source with records of >= 16 bytes: their fourth float (a key frame keeps it)
-  size_t src_int_cap = 0;
+  DevBuf<float4> feats;        // corner features, then surf features (body frame)
+  DevBuf<float> src_int;       // pcm_loam_set_source with records of >= 16 bytes: their fourth float (a key frame keeps it)
   bool src_has_int = false;    // src_int is current
   bool src_from_fe = false;    // the source came from the front end (its intensity lives in loam_features.hip's output)
   uint64_t src_fe_gen = 0;     // generation of that output when the source was committed
@@ -44,13 +34,11 @@ struct LoamCtx {
   void* keystore = nullptr;    // key frames and submap workspace (loam_submap.hip)
   void* scstore = nullptr;     // Scan Context descriptors and loop-detection workspace (loam_sc.hip)
   uint32_t n_c = 0, n_s = 0;
-  double* partials = nullptr;
-  size_t partials_cap = 0;     // doubles
-  LoamState* st = nullptr;     // device
-  LoamState* h_st = nullptr;   // pinned read-back
-  LoamDesc* d_desc = nullptr;  // descriptors of the batches this context leads
-  LoamDesc* h_desc = nullptr;  // pinned staging of the same
-  int desc_cap = 0;
+  DevBuf<double> partials;
+  DevBuf<LoamState> st;
+  PinnedBuf<LoamState> h_st;   // read-back
+  DevBuf<LoamDesc> d_desc;     // descriptors of the batches this context leads
+  PinnedBuf<LoamDesc> h_desc;  // staging of the same
 };
 
 LoamCtx* loam_of(pcm_ctx* c) {
@@ -73,21 +61,7 @@ int check_params(pcm_ctx* c, const pcm_loam_params& p) {
   return PCM_OK;
 }
 
-int check_cloud(pcm_ctx* c, const void* pts, size_t n, size_t stride) {
-  if (!pts && n) { c->err = "null point buffer"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (stride < 3 * sizeof(float) || (stride % sizeof(float)) != 0) { c->err = "stride must be a multiple of 4 and >= 12 bytes"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (n > 0x3fffffffull) { c->err = "cloud too large"; return PCM_ERR_INVALID_ARGUMENT; }
-  return PCM_OK;
-}
-
-int grow_f4(pcm_ctx* c, float4** p, size_t* cap, size_t n) {
-  if (n <= *cap && *p) return PCM_OK;
-  if (*p) { (void)hipStreamSynchronize(c->stream); hipFree(*p); }
-  *p = nullptr; *cap = 0;
-  LCK(c, hipMalloc(reinterpret_cast<void**>(p), sizeof(float4) * (n ? n : 1)));
-  *cap = n;
-  return PCM_OK;
-}
+int check_cloud(pcm_ctx* c, const void* pts, size_t n, size_t stride) { return check_point_records(c, pts, n, stride, PCM_MEM_HOST, 0x3fffffffull, false); }
 
 // records of >= 16 bytes -> features (x, y, z, w = index: k_load_points' layout) and their fourth float, one float per record.
 // base may be `out` itself (rows staged in place): every lane reads its own row before it writes it.
@@ -107,20 +81,20 @@ int load_feats_xyzw(pcm_ctx* c, const void* pts, size_t n, size_t stride, int me
   const char* base = static_cast<const char*>(pts);
   size_t st = stride;
   if (memory != PCM_MEM_DEVICE) {
-    LCK(c, hipMemcpy2DAsync(out, sizeof(float4), pts, stride, sizeof(float4), n, hipMemcpyHostToDevice, c->stream));
+    PCM_HIPCK(c, hipMemcpy2DAsync(out, sizeof(float4), pts, stride, sizeof(float4), n, hipMemcpyHostToDevice, c->stream));
     base = reinterpret_cast<const char*>(out);
     st = sizeof(float4);
   }
   k_load_feats<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(base, st, (uint32_t)n, out, inten);
-  LCK(c, hipGetLastError());
+  PCM_HIPCK(c, hipGetLastError());
   return PCM_OK;
 }
 
-int load_cloud(pcm_ctx* c, Cloud* cl, const void* pts, size_t n, size_t stride, int memory) {
-  int rc = grow_f4(c, &cl->d_pts, &cl->cap, n);
+int load_cloud(pcm_ctx* c, LoamCtx* L, int m, const void* pts, size_t n, size_t stride, int memory) {
+  int rc = L->map_pts[m].reserve(c, n, n);
   if (rc != PCM_OK) return rc;
-  cl->n = n;
-  return load_points_to_device(c->stream, pts, n, stride, memory, 0u, cl->d_pts, &c->err);
+  L->map_n[m] = n;
+  return load_points_to_device(c->stream, pts, n, stride, memory, 0u, L->map_pts[m], &c->err);
 }
 
 // the search grids of both maps at `cell`; the map points' w then carries the caller index
@@ -130,16 +104,16 @@ int ensure_maps(pcm_ctx* c, LoamCtx* L, float cell, int* built) {
   if (L->built_cell == cell) return PCM_OK;
   L->built_cell = 0.f;
   for (int m = 0; m < 2; m++) {
-    uint32_t n = (uint32_t)L->map_cloud[m].n;
+    uint32_t n = (uint32_t)L->map_n[m];
     if (n == 0) { L->map[m].release(); continue; }
-    int rc = build_target_map(c->stream, L->map_cloud[m].d_pts, &n, cell, COORD_FLOOR_MUL, false, 0u, &L->map[m], &c->err, true);
+    int rc = build_target_map(c->stream, L->map_pts[m], &n, cell, COORD_FLOOR_MUL, false, 0u, &L->map[m], &c->err, true);
     if (rc != PCM_OK) return rc;
     launch_tag_input_index(c->stream, L->map[m].pts, L->map[m].order, n);
-    LCK(c, hipGetLastError());
+    PCM_HIPCK(c, hipGetLastError());
   }
   // the grids are read by launches on other streams too (a batch runs on the stream of its first context): they are
   // complete, index tags included, before this returns
-  LCK(c, hipStreamSynchronize(c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   L->built_cell = cell;
   *built = 1;
   return PCM_OK;
@@ -155,26 +129,15 @@ TargetView view_of_loam_map(const TargetMap& m) {
 
 int ensure_state(pcm_ctx* c, LoamCtx* L) {
   const size_t need = (size_t)num_blocks(L->n_c + L->n_s) * kSums;
-  if (need > L->partials_cap || !L->partials) {
-    if (L->partials) { (void)hipStreamSynchronize(c->stream); hipFree(L->partials); }
-    L->partials = nullptr; L->partials_cap = 0;
-    LCK(c, hipMalloc(reinterpret_cast<void**>(&L->partials), sizeof(double) * (need ? need : 1)));
-    L->partials_cap = need;
-  }
-  if (!L->st) LCK(c, hipMalloc(reinterpret_cast<void**>(&L->st), sizeof(LoamState)));
-  if (!L->h_st) LCK(c, hipHostMalloc(reinterpret_cast<void**>(&L->h_st), sizeof(LoamState)));
-  return PCM_OK;
+  int rc;
+  if ((rc = L->partials.reserve(c, need, need)) != PCM_OK || (rc = L->st.reserve(c, 1, 1)) != PCM_OK) return rc;
+  return L->h_st.reserve(c, 1, 1);
 }
 
 int ensure_descs(pcm_ctx* c, LoamCtx* L, int n) {
-  if (n <= L->desc_cap) return PCM_OK;
-  if (L->d_desc) { (void)hipStreamSynchronize(c->stream); hipFree(L->d_desc); }
-  if (L->h_desc) hipHostFree(L->h_desc);
-  L->d_desc = nullptr; L->h_desc = nullptr; L->desc_cap = 0;
-  LCK(c, hipMalloc(reinterpret_cast<void**>(&L->d_desc), sizeof(LoamDesc) * (size_t)n));
-  LCK(c, hipHostMalloc(reinterpret_cast<void**>(&L->h_desc), sizeof(LoamDesc) * (size_t)n));
-  L->desc_cap = n;
-  return PCM_OK;
+  int rc = L->d_desc.reserve(c, (size_t)n, (size_t)n);
+  if (rc != PCM_OK) return rc;
+  return L->h_desc.reserve(c, (size_t)n, (size_t)n);
 }
 
 LoamDesc make_desc(const LoamCtx* L, const float* x6) {
@@ -212,7 +175,7 @@ int prepare_one(pcm_ctx* c, const pcm_loam_params& p, const float* x6, pcm_loam_
   if (rc != PCM_OK) return rc;
   LoamCtx* L = loam_of(c);
   if (!L->have_tgt || !L->have_src) { c->err = "pcm_loam_align before pcm_loam_set_target / pcm_loam_set_source"; return PCM_ERR_NO_INPUT; }
-  LCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   // scan2MapOptimization :1563: laserCloudCornerLastDSNum > edgeFeatureMinValidNum && laserCloudSurfLastDSNum > surfFeatureMinValidNum
   if (!((int64_t)L->n_c > (int64_t)p.edge_min_valid && (int64_t)L->n_s > (int64_t)p.surf_min_valid)) {
     unchanged_result(x6, PCM_ERR_TOO_FEW_FEATURES, r);
@@ -264,8 +227,8 @@ int align_batch(pcm_ctx* const* ctxs, int n, const pcm_loam_params* params, cons
   rc = ensure_descs(c0, L0, m);
   if (rc != PCM_OK) return rc;
   hipStream_t st = c0->stream;
-  LCK(c0, hipSetDevice(c0->device));
-  LCK(c0, hipStreamSynchronize(st));   // the pinned staging of an earlier batch is free again
+  PCM_HIPCK(c0, hipSetDevice(c0->device));
+  PCM_HIPCK(c0, hipStreamSynchronize(st));   // the pinned staging of an earlier batch is free again
   uint32_t max_blocks = 1;
   for (int k = 0; k < m; k++) {
     const int i = live[(size_t)k];
@@ -273,17 +236,17 @@ int align_batch(pcm_ctx* const* ctxs, int n, const pcm_loam_params* params, cons
     L0->h_desc[k] = make_desc(L, x6_in + 6 * i);
     max_blocks = std::max(max_blocks, num_blocks(L->n_c + L->n_s));
   }
-  LCK(c0, hipMemcpyAsync(L0->d_desc, L0->h_desc, sizeof(LoamDesc) * (size_t)m, hipMemcpyHostToDevice, st));
+  PCM_HIPCK(c0, hipMemcpyAsync(L0->d_desc, L0->h_desc, sizeof(LoamDesc) * (size_t)m, hipMemcpyHostToDevice, st));
   launch_init(st, L0->d_desc, m);
-  LCK(c0, hipGetLastError());
+  PCM_HIPCK(c0, hipGetLastError());
   const StepParams sp = step_params(p);
   for (int it = 0; it < p.iter_num; it++) launch_round(st, L0->d_desc, m, max_blocks, sp);
-  LCK(c0, hipGetLastError());
+  PCM_HIPCK(c0, hipGetLastError());
   for (int k = 0; k < m; k++) {
     const LoamCtx* L = loam_of(ctxs[live[(size_t)k]]);
-    LCK(c0, hipMemcpyAsync(L->h_st, L->st, sizeof(LoamState), hipMemcpyDeviceToHost, st));
+    PCM_HIPCK(c0, hipMemcpyAsync(L->h_st, L->st, sizeof(LoamState), hipMemcpyDeviceToHost, st));
   }
-  LCK(c0, hipStreamSynchronize(st));
+  PCM_HIPCK(c0, hipStreamSynchronize(st));
   for (int k = 0; k < m; k++) {
     const int i = live[(size_t)k];
     const LoamState& s = *loam_of(ctxs[i])->h_st;
@@ -310,7 +273,7 @@ int probe(pcm_ctx* c, const float* x6, float* corner_out, float* surf_out, doubl
   LoamCtx* L = loam_of(c);
   if (!L->have_tgt || !L->have_src) { c->err = "parity hook before pcm_loam_set_target / pcm_loam_set_source"; return PCM_ERR_NO_INPUT; }
   if (L->n_c + L->n_s == 0) { c->err = "no features"; return PCM_ERR_NO_INPUT; }
-  LCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   pcm_loam_params p;
   pcm_loam_default_params(&p);
   int built = 0;
@@ -321,21 +284,14 @@ int probe(pcm_ctx* c, const float* x6, float* corner_out, float* surf_out, doubl
   rc = ensure_descs(c, L, 1);
   if (rc != PCM_OK) return rc;
   const size_t nf = (size_t)L->n_c + L->n_s;
-  char* buf = nullptr;
+  DevBuf<char> buf;
   const size_t b_coeff = sizeof(float4) * nf, b_nn = sizeof(int32_t) * 5 * nf, b_sums = sizeof(double) * kSums;
-  LCK(c, hipMalloc(reinterpret_cast<void**>(&buf), b_coeff + b_nn + b_sums));
-  {
-    const hipError_t e0 = hipStreamSynchronize(c->stream);
-    if (e0 != hipSuccess) {
-      hipFree(buf);
-      c->err = std::string("hipStreamSynchronize: ") + hipGetErrorString(e0);
-      return PCM_ERR_HIP;
-    }
-  }
+  if ((rc = buf.reserve(c, b_coeff + b_nn + b_sums, b_coeff + b_nn + b_sums)) != PCM_OK) return rc;
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   LoamDesc d = make_desc(L, x6);
-  d.coeff_out = reinterpret_cast<float4*>(buf);
-  d.nn_out = reinterpret_cast<int32_t*>(buf + b_coeff);
-  d.sums_out = reinterpret_cast<double*>(buf + b_coeff + b_nn);
+  d.coeff_out = reinterpret_cast<float4*>(buf.p);
+  d.nn_out = reinterpret_cast<int32_t*>(buf.p + b_coeff);
+  d.sums_out = reinterpret_cast<double*>(buf.p + b_coeff + b_nn);
   L->h_desc[0] = d;
   std::vector<float4> co(nf);
   std::vector<int32_t> nn(5 * nf);
@@ -353,7 +309,7 @@ int probe(pcm_ctx* c, const float* x6, float* corner_out, float* surf_out, doubl
   if (e == hipSuccess) e = hipMemcpyAsync(sums, d.sums_out, b_sums, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   (void)hipStreamSynchronize(c->stream);
-  hipFree(buf);
+  buf.release();
   if (e != hipSuccess) { c->err = std::string("LOAM parity pass: ") + hipGetErrorString(e); return PCM_ERR_HIP; }
   if (corner_out) std::memcpy(corner_out, co.data(), sizeof(float4) * L->n_c);
   if (surf_out) std::memcpy(surf_out, co.data() + L->n_c, sizeof(float4) * L->n_s);
@@ -381,16 +337,9 @@ void loam_release(pcm_ctx* c) {
   loam_features_release(c);
   LoamCtx* L = static_cast<LoamCtx*>(c->loam);
   if (!L) return;
-  for (int m = 0; m < 2; m++) { L->map_cloud[m].release(); L->map[m].release(); }
+  for (int m = 0; m < 2; m++) L->map[m].release();
   if (L->keystore) loam::loam_keystore_release(L->keystore);
   if (L->scstore) loam::loam_scstore_release(L->scstore);
-  if (L->feats) hipFree(L->feats);
-  if (L->src_int) hipFree(L->src_int);
-  if (L->partials) hipFree(L->partials);
-  if (L->st) hipFree(L->st);
-  if (L->h_st) hipHostFree(L->h_st);
-  if (L->d_desc) hipFree(L->d_desc);
-  if (L->h_desc) hipHostFree(L->h_desc);
   delete L;
   c->loam = nullptr;
 }
@@ -400,7 +349,7 @@ int loam_source_reserve(pcm_ctx* c, size_t n, float4** feats) {
   if (rc != PCM_OK) return rc;
   LoamCtx* L = loam_of(c);
   L->have_src = false;
-  if ((rc = grow_f4(c, &L->feats, &L->feats_cap, n)) != PCM_OK) return rc;
+  if ((rc = L->feats.reserve(c, n, n)) != PCM_OK) return rc;
   *feats = L->feats;
   return PCM_OK;
 }
@@ -427,18 +376,18 @@ int loam_target_reserve(pcm_ctx* c, size_t n_corner, size_t n_surf, float4** cor
   L->tgt_from_submap = false;
   L->built_cell = 0.f;
   L->map[0].valid = L->map[1].valid = false;
-  L->map_cloud[0].n = L->map_cloud[1].n = 0;
-  if ((rc = grow_f4(c, &L->map_cloud[0].d_pts, &L->map_cloud[0].cap, n_corner)) != PCM_OK) return rc;
-  if ((rc = grow_f4(c, &L->map_cloud[1].d_pts, &L->map_cloud[1].cap, n_surf)) != PCM_OK) return rc;
-  *corner = L->map_cloud[0].d_pts;
-  *surf = L->map_cloud[1].d_pts;
+  L->map_n[0] = L->map_n[1] = 0;
+  if ((rc = L->map_pts[0].reserve(c, n_corner, n_corner)) != PCM_OK) return rc;
+  if ((rc = L->map_pts[1].reserve(c, n_surf, n_surf)) != PCM_OK) return rc;
+  *corner = L->map_pts[0];
+  *surf = L->map_pts[1];
   return PCM_OK;
 }
 
 void loam_target_commit(pcm_ctx* c, uint32_t n_corner, uint32_t n_surf) {
   LoamCtx* L = loam_of(c);
-  L->map_cloud[0].n = n_corner;
-  L->map_cloud[1].n = n_surf;
+  L->map_n[0] = n_corner;
+  L->map_n[1] = n_surf;
   L->tgt_tag = 0;
   L->have_tgt = true;
   L->tgt_from_submap = true;
@@ -447,8 +396,8 @@ void loam_target_commit(pcm_ctx* c, uint32_t n_corner, uint32_t n_surf) {
 bool loam_target_view(pcm_ctx* c, const float4** corner, uint32_t* n_corner, const float4** surf, uint32_t* n_surf) {
   LoamCtx* L = loam_of(c);
   if (!L || !L->have_tgt || !L->tgt_from_submap) return false;
-  *corner = L->map_cloud[0].d_pts; *n_corner = (uint32_t)L->map_cloud[0].n;
-  *surf = L->map_cloud[1].d_pts; *n_surf = (uint32_t)L->map_cloud[1].n;
+  *corner = L->map_pts[0]; *n_corner = (uint32_t)L->map_n[0];
+  *surf = L->map_pts[1]; *n_surf = (uint32_t)L->map_n[1];
   return true;
 }
 
@@ -498,16 +447,16 @@ int pcm_loam_set_target(pcm_ctx* c, const void* corner, size_t n_c, const void* 
   int rc = check_ctx(c);
   if (rc != PCM_OK) return rc;
   LoamCtx* L = loam_of(c);
-  if (tag != 0 && tag == L->tgt_tag && L->have_tgt && L->map_cloud[0].n == n_c && L->map_cloud[1].n == n_s) return PCM_OK;
+  if (tag != 0 && tag == L->tgt_tag && L->have_tgt && L->map_n[0] == n_c && L->map_n[1] == n_s) return PCM_OK;
   if ((rc = check_cloud(c, corner, n_c, stride)) != PCM_OK || (rc = check_cloud(c, surf, n_s, stride)) != PCM_OK) return rc;
-  LCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   L->have_tgt = false;
   L->tgt_from_submap = false;
   L->built_cell = 0.f;
   L->map[0].valid = L->map[1].valid = false;
-  if ((rc = load_cloud(c, &L->map_cloud[0], corner, n_c, stride, memory)) != PCM_OK) return rc;
-  if ((rc = load_cloud(c, &L->map_cloud[1], surf, n_s, stride, memory)) != PCM_OK) return rc;
-  LCK(c, hipStreamSynchronize(c->stream));   // the caller may reuse its buffers on return
+  if ((rc = load_cloud(c, L, 0, corner, n_c, stride, memory)) != PCM_OK) return rc;
+  if ((rc = load_cloud(c, L, 1, surf, n_s, stride, memory)) != PCM_OK) return rc;
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));   // the caller may reuse its buffers on return
   L->tgt_tag = tag;
   L->have_tgt = true;
   return PCM_OK;
@@ -519,18 +468,13 @@ int pcm_loam_set_source(pcm_ctx* c, const void* corner, size_t n_c, const void* 
   LoamCtx* L = loam_of(c);
   if (tag != 0 && tag == L->src_tag && L->have_src && L->n_c == n_c && L->n_s == n_s) return PCM_OK;
   if ((rc = check_cloud(c, corner, n_c, stride)) != PCM_OK || (rc = check_cloud(c, surf, n_s, stride)) != PCM_OK) return rc;
-  LCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   L->have_src = false;
-  if ((rc = grow_f4(c, &L->feats, &L->feats_cap, n_c + n_s)) != PCM_OK) return rc;
+  if ((rc = L->feats.reserve(c, n_c + n_s, n_c + n_s)) != PCM_OK) return rc;
   L->src_from_fe = false;
   L->src_has_int = false;
   if (stride >= 4 * sizeof(float)) {   // the records carry a fourth float (PointXYZI's intensity): a key frame keeps it
-    if (n_c + n_s > L->src_int_cap || !L->src_int) {
-      if (L->src_int) { (void)hipStreamSynchronize(c->stream); hipFree(L->src_int); }
-      L->src_int = nullptr; L->src_int_cap = 0;
-      LCK(c, hipMalloc(reinterpret_cast<void**>(&L->src_int), sizeof(float) * (n_c + n_s ? n_c + n_s : 1)));
-      L->src_int_cap = n_c + n_s;
-    }
+    if ((rc = L->src_int.reserve(c, n_c + n_s, n_c + n_s)) != PCM_OK) return rc;
     if ((rc = load_feats_xyzw(c, corner, n_c, stride, memory, L->feats, L->src_int)) != PCM_OK) return rc;
     if ((rc = load_feats_xyzw(c, surf, n_s, stride, memory, L->feats + n_c, L->src_int + n_c)) != PCM_OK) return rc;
     L->src_has_int = true;
@@ -538,7 +482,7 @@ int pcm_loam_set_source(pcm_ctx* c, const void* corner, size_t n_c, const void* 
     if ((rc = load_points_to_device(c->stream, corner, n_c, stride, memory, 0u, L->feats, &c->err)) != PCM_OK) return rc;
     if ((rc = load_points_to_device(c->stream, surf, n_s, stride, memory, 0u, L->feats + n_c, &c->err)) != PCM_OK) return rc;
   }
-  LCK(c, hipStreamSynchronize(c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   L->n_c = (uint32_t)n_c;
   L->n_s = (uint32_t)n_s;
   L->src_tag = tag;

@@ -80,6 +80,33 @@ __device__ inline unsigned int f2ord(float f) { const unsigned int u = __float_a
 // inverse of f2ord, branch-free (the select form crashes this compiler's instruction selection when followed by float arithmetic)
 __device__ inline float ord2f(unsigned int o) { const unsigned int m = (unsigned int)((int)o >> 31); return __uint_as_float(o ^ (~m | 0x80000000u)); }
 
+// 64-lane butterfly reductions (every lane ends with the result).  The double sum adds in this fixed order, so its bits do not
+// depend on the schedule; linearize_common.h's DPP reductions are another order and stay apart.
+__device__ inline uint32_t wave_min_u32(uint32_t v) {
+  for (int off = 32; off >= 1; off >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, off, 64));
+  return v;
+}
+__device__ inline uint32_t wave_max_u32(uint32_t v) {
+  for (int off = 32; off >= 1; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off, 64));
+  return v;
+}
+__device__ inline uint32_t wave_sum_u32(uint32_t v) {
+  for (int off = 32; off >= 1; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, 64);
+  return v;
+}
+__device__ inline uint64_t wave_min_u64(uint64_t v) {
+  for (int off = 32; off >= 1; off >>= 1) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off, 64);
+    const uint64_t o = ((uint64_t)hi << 32) | lo;
+    v = o < v ? o : v;
+  }
+  return v;
+}
+__device__ inline double wave_sum_f64(double v) {
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
 // a lane's point into the bounding box of its segment (mm: 6 ordered-int words per segment, min then max)
 __device__ inline void sv_wave_minmax(bool valid, uint32_t seg, const float4& pt, unsigned int* __restrict__ mm) {
   unsigned int lo[3], hi[3];

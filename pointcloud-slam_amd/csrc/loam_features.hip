@@ -12,9 +12,9 @@
 //   k_lf_extract (pointColInd, pointRange, extracted cloud), k_lf_smooth, k_lf_occlude, k_lf_snapshot (marks for the hook),
 //   k_lf_select<first ring> then k_lf_select<other rings> (sort, invariance check / serial std::sort, greedy passes),
 //   k_lf_corner_compact, segmented VoxelGrid stage 1 (per ring, odometry leaf), stage 2 (corner / surf, mapping leaves), k_lf_finish.
+#include "host_util.h"
 #include "intro_sort.h"
 #include "loam_device.h"
-#include "pcm_host.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -30,15 +30,6 @@ using namespace pcm;
 namespace {
 
 constexpr int kMaxPicks = 20;   // largestPickedNum <= 20 (featureExtraction.cpp:177)
-
-#define LFCK(ctx, x)                                                                 \
-  do {                                                                               \
-    hipError_t e_ = (x);                                                             \
-    if (e_ != hipSuccess) {                                                          \
-      (ctx)->err = std::string(#x) + ": " + hipGetErrorString(e_);                   \
-      return PCM_ERR_HIP;                                                            \
-    }                                                                                \
-  } while (0)
 
 // per-frame counters, read back once per batch
 struct LfInfo {
@@ -640,48 +631,21 @@ __global__ void k_lf_finish(const LfFrame* __restrict__ fr, LfParams p, const fl
 // ---------------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------
-template <typename T>
-int grow(pcm_ctx* c, T** p, size_t* cap, size_t n, bool zero = false) {
-  if (n <= *cap && *p) return PCM_OK;
-  if (*p) { (void)hipStreamSynchronize(c->stream); hipFree(*p); }
-  *p = nullptr; *cap = 0;
-  const size_t bytes = sizeof(T) * (n ? n : 1);
-  LFCK(c, hipMalloc(reinterpret_cast<void**>(p), bytes));
-  if (zero) LFCK(c, hipMemset(*p, 0, bytes));
-  *cap = n;
-  return PCM_OK;
-}
-
 // the cross-frame state of one context (the reference node's members) and its last frame's outputs
 struct FeatState {
   int n_scan = 0, H = 0, A = 0;
-  size_t cap = 0, sz_state = 0;
-  int32_t* col_ind = nullptr; float* range = nullptr; float4* cloud = nullptr; float* curv = nullptr;
-  int32_t* picked = nullptr; int32_t* label = nullptr; DistId* smooth = nullptr;
-  int32_t* picked_occ = nullptr; int32_t* start = nullptr; int32_t* end = nullptr;   // end = start + n_scan (one allocation)
-  size_t cap_occ = 0, cap_se = 0;
-  float4* corner_scan = nullptr; size_t cap_cs = 0;
-  float4* surf_scan = nullptr; size_t cap_ss = 0;
-  float4* out = nullptr; size_t cap_out = 0;
+  DevBuf<int32_t> col_ind; DevBuf<float> range; DevBuf<float4> cloud; DevBuf<float> curv;
+  DevBuf<int32_t> picked; DevBuf<int32_t> label; DevBuf<DistId> smooth;
+  DevBuf<int32_t> picked_occ; DevBuf<int32_t> start;
+  int32_t* end = nullptr;   // end = start + n_scan (one allocation)
+  DevBuf<float4> corner_scan, surf_scan, out;
   uint64_t out_gen = 0;   // bumps with every frame that rewrites `out` (the key-frame store checks it, loam_source_view)
   LfInfo last{};
   bool have_last = false;
   // batch workspace (used when this context leads a batch)
-  LfFrame* d_fr = nullptr; LfFrame* h_fr = nullptr; int fr_cap = 0;
-  LfInfo* d_info = nullptr; LfInfo* h_info = nullptr; int info_cap = 0;
-  char* ws = nullptr; size_t ws_cap = 0;
-
-  void release_state() {
-    for (void* q : {(void*)col_ind, (void*)range, (void*)cloud, (void*)curv, (void*)picked, (void*)label, (void*)smooth}) if (q) hipFree(q);
-    col_ind = nullptr; range = nullptr; cloud = nullptr; curv = nullptr; picked = nullptr; label = nullptr; smooth = nullptr;
-    sz_state = 0;
-  }
-  void release() {
-    release_state();
-    for (void* q : {(void*)picked_occ, (void*)start, (void*)corner_scan, (void*)surf_scan, (void*)out, (void*)d_fr, (void*)d_info, (void*)ws}) if (q) hipFree(q);
-    if (h_fr) hipHostFree(h_fr);
-    if (h_info) hipHostFree(h_info);
-  }
+  DevBuf<LfFrame> d_fr; PinnedBuf<LfFrame> h_fr;
+  DevBuf<LfInfo> d_info; PinnedBuf<LfInfo> h_info;
+  DevBuf<char> ws;
 };
 
 FeatState* fe_of(pcm_ctx* c) {
@@ -708,22 +672,17 @@ int ensure_state(pcm_ctx* c, FeatState* S, const pcm_loam_feature_params& p) {
   const size_t cap = (size_t)p.n_scan * (size_t)p.horizon_scan;
   if (S->col_ind && S->n_scan == p.n_scan && S->H == p.horizon_scan) return PCM_OK;
   (void)hipStreamSynchronize(c->stream);
-  S->release_state();
-  size_t k = 0;
-  int rc;
-  if ((rc = grow(c, &S->col_ind, &k, cap, true)) != PCM_OK) return rc; k = 0;
-  if ((rc = grow(c, &S->range, &k, cap, true)) != PCM_OK) return rc; k = 0;
-  if ((rc = grow(c, &S->cloud, &k, cap, true)) != PCM_OK) return rc; k = 0;
-  if ((rc = grow(c, &S->curv, &k, cap, true)) != PCM_OK) return rc; k = 0;
-  if ((rc = grow(c, &S->picked, &k, cap, true)) != PCM_OK) return rc; k = 0;
-  if ((rc = grow(c, &S->label, &k, cap, true)) != PCM_OK) return rc; k = 0;
-  if ((rc = grow(c, &S->smooth, &k, cap, true)) != PCM_OK) return rc;
-  S->n_scan = p.n_scan; S->H = p.horizon_scan; S->cap = cap;
+  S->n_scan = S->H = 0;   // until every array below has the new shape
   S->have_last = false;
+  S->col_ind.release(); S->range.release(); S->cloud.release(); S->curv.release(); S->picked.release(); S->label.release(); S->smooth.release();
+  auto fresh = [&](auto& b) { return b.reserve(c, cap, cap, true); };
+  int rc;
+  if ((rc = fresh(S->col_ind)) != PCM_OK || (rc = fresh(S->range)) != PCM_OK || (rc = fresh(S->cloud)) != PCM_OK || (rc = fresh(S->curv)) != PCM_OK ||
+      (rc = fresh(S->picked)) != PCM_OK || (rc = fresh(S->label)) != PCM_OK || (rc = fresh(S->smooth)) != PCM_OK)
+    return rc;
+  S->n_scan = p.n_scan; S->H = p.horizon_scan;
   return PCM_OK;
 }
-
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 int next_pow2(int x) { int p = 1; while (p < x) p <<= 1; return p; }
 int bit_len(uint64_t x) { int b = 0; while (x) { b++; x >>= 1; } return b; }
@@ -783,7 +742,7 @@ int run_vg(pcm_ctx* c0, hipStream_t st, int stage, const LfFrame* d_fr, const Lf
   if (N == 0 || size_per_frame == 0) return PCM_OK;
   const dim3 g((size_per_frame + 255) / 256, (unsigned)B);
   k_sv_clear<<<(nseg + 255) / 256, 256, 0, st>>>(mm, scnt, nseg);
-  LFCK(c0, hipMemsetAsync(nc, 0, 16, st));
+  PCM_HIPCK(c0, hipMemsetAsync(nc, 0, 16, st));
   if (stage == 1) {
     k_sv_minmax<1><<<g, 256, 0, st>>>(d_fr, P, size_per_frame, cells1, mm);
     k_sv_boxes<<<(nseg + 255) / 256, 256, 0, st>>>(d_fr, mm, nseg, 1, P, box);
@@ -793,7 +752,7 @@ int run_vg(pcm_ctx* c0, hipStream_t st, int stage, const LfFrame* d_fr, const Lf
     k_sv_boxes<<<(nseg + 255) / 256, 256, 0, st>>>(d_fr, mm, nseg, 2, P, box);
     k_sv_keys<2><<<g, 256, 0, st>>>(d_fr, P, size_per_frame, cells1, box, nseg, keys, vals);
   }
-  LFCK(c0, hipGetLastError());
+  PCM_HIPCK(c0, hipGetLastError());
   loam::SvWork W;
   W.keys = keys; W.keys_s = keys_s; W.vals = vals; W.vals_s = vals_s; W.head = head; W.slot = slot; W.scnt = scnt; W.sfirst = sfirst; W.nc = nc;
   W.tmp = ws + Lw.o_tmp; W.tmp_bytes = Lw.tmp_bytes; W.tmp2 = ws + Lw.o_tmp2; W.tmp2_bytes = Lw.tmp2_bytes;
@@ -808,7 +767,7 @@ int run_vg(pcm_ctx* c0, hipStream_t st, int stage, const LfFrame* d_fr, const Lf
     k_sv_average<2><<<gb, 256, 0, st>>>(d_fr, P, keys_s, vals_s, pos, nc, nc + 1, cells1, cells_out);
     k_sv_frames<2><<<B, 256, 0, st>>>(d_fr, P, scnt, sfirst);
   }
-  LFCK(c0, hipGetLastError());
+  PCM_HIPCK(c0, hipGetLastError());
   return PCM_OK;
 }
 
@@ -821,14 +780,14 @@ namespace loam {
 int sv_sort_cells(pcm_ctx* c0, hipStream_t st, const SvWork& W, uint32_t N, uint32_t nseg) {
   size_t tb = W.tmp_bytes, tb2 = W.tmp2_bytes;
   const int end_bit = 32 + bit_len(nseg);
-  LFCK(c0, rocprim::radix_sort_pairs(W.tmp, tb, W.keys, W.keys_s, W.vals, W.vals_s, (size_t)N, 0, end_bit, st));
+  PCM_HIPCK(c0, rocprim::radix_sort_pairs(W.tmp, tb, W.keys, W.keys_s, W.vals, W.vals_s, (size_t)N, 0, end_bit, st));
   const unsigned nb = (N + 255) / 256;
   k_sv_heads<<<nb, 256, 0, st>>>(W.keys_s, N, nseg, W.head, W.scnt);
-  LFCK(c0, hipGetLastError());
-  LFCK(c0, rocprim::exclusive_scan(W.tmp2, tb2, W.head, W.slot, 0u, (size_t)N, rocprim::plus<uint32_t>(), st));
+  PCM_HIPCK(c0, hipGetLastError());
+  PCM_HIPCK(c0, rocprim::exclusive_scan(W.tmp2, tb2, W.head, W.slot, 0u, (size_t)N, rocprim::plus<uint32_t>(), st));
   k_sv_head_pos<<<nb, 256, 0, st>>>(W.keys_s, W.head, W.slot, N, W.vals, W.sfirst);
   k_sv_count<<<nb, 256, 0, st>>>(W.keys_s, W.head, W.slot, N, nseg, W.nc);   // invalid keys sort behind every valid one
-  LFCK(c0, hipGetLastError());
+  PCM_HIPCK(c0, hipGetLastError());
   return PCM_OK;
 }
 
@@ -902,7 +861,7 @@ int run_frames(pcm_ctx* const* ctxs, int B, const void* const* points, const siz
     if (!points[i] && n_points[i]) { c0->err = "null point buffer"; return PCM_ERR_INVALID_ARGUMENT; }
     if (n_points[i] > 0x3fffffffull) { c0->err = "cloud too large"; return PCM_ERR_INVALID_ARGUMENT; }
   }
-  LFCK(c0, hipSetDevice(c0->device));
+  PCM_HIPCK(c0, hipSetDevice(c0->device));
   const LfParams P = dev_params(q);
   const size_t cap = (size_t)q.n_scan * q.horizon_scan;
   const size_t ncs = (size_t)q.n_scan * P.ppr;   // corner picks per frame
@@ -922,9 +881,10 @@ int run_frames(pcm_ctx* const* ctxs, int B, const void* const* points, const siz
     base1[(size_t)i] = N1; N1 += cap1[(size_t)i];
     base2[(size_t)i] = N2; N2 += ncs + cap1[(size_t)i];
     max1 = std::max<uint32_t>(max1, (uint32_t)cap1[(size_t)i]);
-    if ((rc = grow(c, &S->picked_occ, &S->cap_occ, cap)) != PCM_OK || (rc = grow(c, &S->start, &S->cap_se, 2 * (size_t)q.n_scan)) != PCM_OK ||
-        (rc = grow(c, &S->corner_scan, &S->cap_cs, ncs)) != PCM_OK || (rc = grow(c, &S->surf_scan, &S->cap_ss, cap1[(size_t)i])) != PCM_OK ||
-        (rc = grow(c, &S->out, &S->cap_out, ncs + cap1[(size_t)i])) != PCM_OK) {
+    const size_t n_ring = 2 * (size_t)q.n_scan, n_surf = cap1[(size_t)i];
+    if ((rc = S->picked_occ.reserve(c, cap, cap)) != PCM_OK || (rc = S->start.reserve(c, n_ring, n_ring)) != PCM_OK ||
+        (rc = S->corner_scan.reserve(c, ncs, ncs)) != PCM_OK || (rc = S->surf_scan.reserve(c, n_surf, n_surf)) != PCM_OK ||
+        (rc = S->out.reserve(c, ncs + n_surf, ncs + n_surf)) != PCM_OK) {
       if (c != c0) c0->err = c->err;
       return rc;
     }
@@ -942,20 +902,11 @@ int run_frames(pcm_ctx* const* ctxs, int B, const void* const* points, const siz
   const size_t nseg_max = std::max<size_t>((size_t)B * q.n_scan, 2 * (size_t)B);
   const BatchLayout Lw = layout(B, in_bytes, cap, q.n_scan, P.ppr, N1, N2, nseg_max);
   hipStream_t st = c0->stream;
-  LFCK(c0, hipStreamSynchronize(st));   // the pinned staging of an earlier batch is free again
-  if ((rc = grow(c0, &S0->ws, &S0->ws_cap, Lw.total)) != PCM_OK) return rc;
-  if (B > S0->fr_cap) {
-    if (S0->d_fr) hipFree(S0->d_fr);
-    if (S0->h_fr) hipHostFree(S0->h_fr);
-    if (S0->d_info) hipFree(S0->d_info);
-    if (S0->h_info) hipHostFree(S0->h_info);
-    S0->d_fr = nullptr; S0->h_fr = nullptr; S0->d_info = nullptr; S0->h_info = nullptr; S0->fr_cap = 0;
-    LFCK(c0, hipMalloc(reinterpret_cast<void**>(&S0->d_fr), sizeof(LfFrame) * (size_t)B));
-    LFCK(c0, hipHostMalloc(reinterpret_cast<void**>(&S0->h_fr), sizeof(LfFrame) * (size_t)B));
-    LFCK(c0, hipMalloc(reinterpret_cast<void**>(&S0->d_info), sizeof(LfInfo) * (size_t)B));
-    LFCK(c0, hipHostMalloc(reinterpret_cast<void**>(&S0->h_info), sizeof(LfInfo) * (size_t)B));
-    S0->fr_cap = B;
-  }
+  PCM_HIPCK(c0, hipStreamSynchronize(st));   // the pinned staging of an earlier batch is free again
+  if ((rc = S0->ws.reserve(c0, Lw.total, Lw.total)) != PCM_OK) return rc;
+  if ((rc = S0->d_fr.reserve(c0, (size_t)B, (size_t)B)) != PCM_OK || (rc = S0->h_fr.reserve(c0, (size_t)B, (size_t)B)) != PCM_OK ||
+      (rc = S0->d_info.reserve(c0, (size_t)B, (size_t)B)) != PCM_OK || (rc = S0->h_info.reserve(c0, (size_t)B, (size_t)B)) != PCM_OK)
+    return rc;
   char* ws = S0->ws;
   size_t in_off = Lw.o_in;
   uint32_t maxn = 1;
@@ -965,7 +916,7 @@ int run_frames(pcm_ctx* const* ctxs, int B, const void* const* points, const siz
     std::memset(&F, 0, sizeof(F));
     if (memory == PCM_MEM_HOST) {
       F.pts = ws + in_off;
-      if (n_points[i]) LFCK(c0, hipMemcpyAsync(ws + in_off, points[i], n_points[i] * stride, hipMemcpyHostToDevice, st));
+      if (n_points[i]) PCM_HIPCK(c0, hipMemcpyAsync(ws + in_off, points[i], n_points[i] * stride, hipMemcpyHostToDevice, st));
       in_off += up256(n_points[i] * stride);
     } else {
       F.pts = static_cast<const char*>(points[i]);
@@ -984,7 +935,7 @@ int run_frames(pcm_ctx* const* ctxs, int B, const void* const* points, const siz
     F.info = S0->d_info + i;
     maxn = std::max<uint32_t>(maxn, F.n);
   }
-  LFCK(c0, hipMemcpyAsync(S0->d_fr, S0->h_fr, sizeof(LfFrame) * (size_t)B, hipMemcpyHostToDevice, st));
+  PCM_HIPCK(c0, hipMemcpyAsync(S0->d_fr, S0->h_fr, sizeof(LfFrame) * (size_t)B, hipMemcpyHostToDevice, st));
   const LfFrame* d_fr = S0->d_fr;
   const unsigned gcap = (unsigned)((std::max<size_t>(cap, (size_t)q.n_scan) + 255) / 256);
   k_lf_clear<<<dim3(gcap, B), 256, 0, st>>>(d_fr, P);
@@ -999,16 +950,16 @@ int run_frames(pcm_ctx* const* ctxs, int B, const void* const* points, const siz
   k_lf_select<true><<<dim3(1, B), 64, lds, st>>>(d_fr, P);
   k_lf_select<false><<<dim3(q.n_scan, B), 64, lds, st>>>(d_fr, P);
   k_lf_corner_compact<<<B, 256, 0, st>>>(d_fr, P);
-  LFCK(c0, hipGetLastError());
+  PCM_HIPCK(c0, hipGetLastError());
   float4* cells1 = reinterpret_cast<float4*>(ws + Lw.o_cells1);
   float4* cells2 = reinterpret_cast<float4*>(ws + Lw.o_cells2);
   if ((rc = run_vg(c0, st, 1, d_fr, P, B, max1, (uint32_t)N1, (uint32_t)(B * q.n_scan), ws, Lw, cells1, cells1)) != PCM_OK) return rc;
   const uint32_t size2 = (uint32_t)(ncs + max1);
   if ((rc = run_vg(c0, st, 2, d_fr, P, B, size2, (uint32_t)N2, (uint32_t)(2 * B), ws, Lw, cells1, cells2)) != PCM_OK) return rc;
   k_lf_finish<<<dim3((size2 + 255) / 256, B), 256, 0, st>>>(d_fr, P, cells1, cells2);
-  LFCK(c0, hipGetLastError());
-  LFCK(c0, hipMemcpyAsync(S0->h_info, S0->d_info, sizeof(LfInfo) * (size_t)B, hipMemcpyDeviceToHost, st));
-  LFCK(c0, hipStreamSynchronize(st));
+  PCM_HIPCK(c0, hipGetLastError());
+  PCM_HIPCK(c0, hipMemcpyAsync(S0->h_info, S0->d_info, sizeof(LfInfo) * (size_t)B, hipMemcpyDeviceToHost, st));
+  PCM_HIPCK(c0, hipStreamSynchronize(st));
   int worst = PCM_OK;
   for (int i = 0; i < B; i++) {
     const LfInfo& I = S0->h_info[i];
@@ -1041,7 +992,6 @@ namespace pcm {
 void loam_features_release(pcm_ctx* c) {
   FeatState* S = static_cast<FeatState*>(c->loam_fe);
   if (!S) return;
-  S->release();
   delete S;
   c->loam_fe = nullptr;
 }
@@ -1078,8 +1028,8 @@ int pcm_loam_extract_features(pcm_ctx* c, const void* points, size_t n, size_t s
   if (nc + nsf == 0) return PCM_OK;
   std::vector<float4> h(nc + nsf);
   FeatState* S = fe_of(c);
-  LFCK(c, hipMemcpyAsync(h.data(), S->out, sizeof(float4) * h.size(), hipMemcpyDeviceToHost, c->stream));
-  LFCK(c, hipStreamSynchronize(c->stream));
+  PCM_HIPCK(c, hipMemcpyAsync(h.data(), S->out, sizeof(float4) * h.size(), hipMemcpyDeviceToHost, c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   copy_xyzi(h.data(), nc, corner);
   copy_xyzi(h.data() + nc, nsf, surf);
   return PCM_OK;
@@ -1104,20 +1054,20 @@ int pcm_loam_feature_info(pcm_ctx* c, int32_t counts[4], int32_t* start_ring, in
   if (rc != PCM_OK) return rc;
   FeatState* S = fe_of(c);
   if (!S->have_last) { c->err = "no frame has run through the front end of this context"; return PCM_ERR_NO_INPUT; }
-  LFCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   const size_t n = S->last.count, ns = (size_t)S->n_scan, nc = S->last.n_corner_scan, nss = S->last.n_surf_scan;
   if (counts) { counts[0] = (int32_t)n; counts[1] = (int32_t)nc; counts[2] = (int32_t)nss; counts[3] = (int32_t)ns; }
-  LFCK(c, hipStreamSynchronize(c->stream));
-  if (start_ring) LFCK(c, hipMemcpy(start_ring, S->start, 4 * ns, hipMemcpyDeviceToHost));
-  if (end_ring) LFCK(c, hipMemcpy(end_ring, S->end, 4 * ns, hipMemcpyDeviceToHost));
-  if (col_ind && n) LFCK(c, hipMemcpy(col_ind, S->col_ind, 4 * n, hipMemcpyDeviceToHost));
-  if (range && n) LFCK(c, hipMemcpy(range, S->range, 4 * n, hipMemcpyDeviceToHost));
-  if (cloud && n) LFCK(c, hipMemcpy(cloud, S->cloud, 16 * n, hipMemcpyDeviceToHost));
-  if (curvature && n) LFCK(c, hipMemcpy(curvature, S->curv, 4 * n, hipMemcpyDeviceToHost));
-  if (neighbor_picked && n) LFCK(c, hipMemcpy(neighbor_picked, S->picked_occ, 4 * n, hipMemcpyDeviceToHost));
-  if (label && n) LFCK(c, hipMemcpy(label, S->label, 4 * n, hipMemcpyDeviceToHost));
-  if (corner_scan && nc) LFCK(c, hipMemcpy(corner_scan, S->corner_scan, 16 * nc, hipMemcpyDeviceToHost));
-  if (surf_scan && nss) LFCK(c, hipMemcpy(surf_scan, S->surf_scan, 16 * nss, hipMemcpyDeviceToHost));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
+  if (start_ring) PCM_HIPCK(c, hipMemcpy(start_ring, S->start, 4 * ns, hipMemcpyDeviceToHost));
+  if (end_ring) PCM_HIPCK(c, hipMemcpy(end_ring, S->end, 4 * ns, hipMemcpyDeviceToHost));
+  if (col_ind && n) PCM_HIPCK(c, hipMemcpy(col_ind, S->col_ind, 4 * n, hipMemcpyDeviceToHost));
+  if (range && n) PCM_HIPCK(c, hipMemcpy(range, S->range, 4 * n, hipMemcpyDeviceToHost));
+  if (cloud && n) PCM_HIPCK(c, hipMemcpy(cloud, S->cloud, 16 * n, hipMemcpyDeviceToHost));
+  if (curvature && n) PCM_HIPCK(c, hipMemcpy(curvature, S->curv, 4 * n, hipMemcpyDeviceToHost));
+  if (neighbor_picked && n) PCM_HIPCK(c, hipMemcpy(neighbor_picked, S->picked_occ, 4 * n, hipMemcpyDeviceToHost));
+  if (label && n) PCM_HIPCK(c, hipMemcpy(label, S->label, 4 * n, hipMemcpyDeviceToHost));
+  if (corner_scan && nc) PCM_HIPCK(c, hipMemcpy(corner_scan, S->corner_scan, 16 * nc, hipMemcpyDeviceToHost));
+  if (surf_scan && nss) PCM_HIPCK(c, hipMemcpy(surf_scan, S->surf_scan, 16 * nss, hipMemcpyDeviceToHost));
   return PCM_OK;
 }
 

@@ -11,9 +11,9 @@
 // one lane per column; the column sums of a shift are added by one lane in column order, as loam_sc.h's host composition does)
 // and k_sc_fold (minimum by (distance, candidate position); NaN never wins).  The result record is read back once at the end.
 // No float atomics anywhere, so two runs over the same store give the same bits.
+#include "host_util.h"
 #include "loam_device.h"
 #include "loam_sc.h"
-#include "pcm_host.h"
 
 #include <algorithm>
 #include <cstring>
@@ -25,15 +25,6 @@ using namespace pcm::loam;
 
 namespace {
 
-#define SCCK(ctx, x)                                                                 \
-  do {                                                                               \
-    hipError_t e_ = (x);                                                             \
-    if (e_ != hipSuccess) {                                                          \
-      (ctx)->err = std::string(#x) + ": " + hipGetErrorString(e_);                   \
-      return PCM_ERR_HIP;                                                            \
-    }                                                                                \
-  } while (0)
-
 constexpr double kScLarge = 10000000;   // the reference's initial minimum
 constexpr int kShiftChunk = 8;          // shifts evaluated side by side in k_sc_distance
 constexpr uint32_t kScLdsWords = 8192;  // largest bin table k_sc_bins keeps in LDS (32 KB; 20 x 60 is 1 200 words)
@@ -41,14 +32,6 @@ constexpr uint32_t kScLdsWords = 8192;  // largest bin table k_sc_bins keeps in 
 __global__ void k_sc_table_init(uint32_t* __restrict__ table, uint32_t n) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) table[i] = f2ord(kScNoPoint);
-}
-
-// strided device records -> float4 rows (the fourth float when the record has one)
-__global__ void k_sc_load(const char* __restrict__ base, size_t stride, uint32_t n, int has_w, float4* __restrict__ dst) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float* p = reinterpret_cast<const float*>(base + (size_t)i * stride);
-  dst[i] = make_float4(p[0], p[1], p[2], has_w ? p[3] : 0.f);
 }
 
 // One lane per point (grid-stride): the workgroup's maxima in a table of num_ring * num_sector words of dynamic LDS, flushed with
@@ -101,15 +84,6 @@ __global__ void __launch_bounds__(256) k_sc_ringkeys(const float* __restrict__ r
   if (i >= n) return;
   const float d2 = sc_ring_d2(rkeys + (size_t)q * R, rkeys + (size_t)i * R, R);
   keys[i] = ((uint64_t)__float_as_uint(d2) << 32) | i;
-}
-
-__device__ inline uint64_t wave_min_u64(uint64_t v) {
-  for (int off = 32; off >= 1; off >>= 1) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off, 64);
-    const uint64_t o = ((uint64_t)hi << 32) | lo;
-    v = o < v ? o : v;
-  }
-  return v;
 }
 
 // one workgroup: the k smallest keys in ascending order (round t takes the smallest key above that of round t - 1; the keys are
@@ -247,38 +221,25 @@ __global__ void __launch_bounds__(1024) k_sc_fold(const double* __restrict__ dis
 struct ScStore {
   int R = 0, S = 0;
   size_t count = 0, cap = 0;        // descriptors
-  float* desc = nullptr;            // [cap][R * S]
-  float* rkey = nullptr;            // [cap][R]
-  double* skey = nullptr;           // [cap][S]
-  double* norm = nullptr;           // [cap][S]
-  uint32_t* table = nullptr;        // [R * S] ordered-int maxima of the descriptor being built
-  double* ready = nullptr;          // [R * S] staging of pcm_loam_sc_put
-  float4* pts = nullptr;            // staged input cloud, then room for its VoxelGrid cells
-  size_t pts_cap = 0;
-  char* vg = nullptr;               // VoxelGrid scratch
-  size_t vg_cap = 0;
-  uint64_t* keys = nullptr;         // [set] ring-key sort keys
-  double* dist = nullptr;           // [set] candidate distances
-  int32_t* shift = nullptr;         // [set]
-  size_t set_cap = 0;
-  int32_t* cand = nullptr;          // [kScMaxCandidates]
-  pcm_loam_sc_result* d_res = nullptr;
-  pcm_loam_sc_result* h_res = nullptr;   // pinned
+  DevBuf<float> desc{"scan-context store"};    // [cap][R * S]
+  DevBuf<float> rkey{"scan-context store"};    // [cap][R]
+  DevBuf<double> skey{"scan-context store"};   // [cap][S]
+  DevBuf<double> norm{"scan-context store"};   // [cap][S]
+  DevBuf<uint32_t> table;           // [R * S] ordered-int maxima of the descriptor being built
+  DevBuf<double> ready;             // [R * S] staging of pcm_loam_sc_put
+  DevBuf<float4> pts;               // staged input cloud, then room for its VoxelGrid cells
+  DevBuf<char> vg;                  // VoxelGrid scratch
+  DevBuf<uint64_t> keys;            // [set] ring-key sort keys
+  DevBuf<double> dist;              // [set] candidate distances
+  DevBuf<int32_t> shift;            // [set]
+  DevBuf<int32_t> cand;             // [kScMaxCandidates]
+  DevBuf<pcm_loam_sc_result> d_res;
+  PinnedBuf<pcm_loam_sc_result> h_res;
   // the reference's stale tree
   uint64_t counter = 0;
   size_t tree_size = 0;
   bool have_tree = false;
-
-  void release() {
-    for (void* p : {(void*)desc, (void*)rkey, (void*)skey, (void*)norm, (void*)table, (void*)ready, (void*)pts, (void*)vg, (void*)keys, (void*)dist, (void*)shift,
-                    (void*)cand, (void*)d_res})
-      if (p) hipFree(p);
-    if (h_res) hipHostFree(h_res);
-  }
 };
-
-bool finite_f(float v) { return sc_finite(v); }
-bool finite_d(double v) { return v == v && v <= 1.7976931348623157e308 && v >= -1.7976931348623157e308; }
 
 // create = false (queries): *out stays null when the context has no store yet, and none is made
 int check_ctx_sc(pcm_ctx* c, ScStore** out, bool create = true) {
@@ -313,61 +274,34 @@ int check_scparams(pcm_ctx* c, const ScStore* S, const pcm_loam_sc_params& p) {
   return PCM_OK;
 }
 
-template <typename T>
-int regrow(pcm_ctx* c, T** p, size_t old_n, size_t new_n) {
-  T* np = nullptr;
-  SCCK(c, hipMalloc(reinterpret_cast<void**>(&np), sizeof(T) * new_n));
-  if (*p) {
-    hipError_t e = old_n ? hipMemcpyAsync(np, *p, sizeof(T) * old_n, hipMemcpyDeviceToDevice, c->stream) : hipSuccess;
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { hipFree(np); c->err = std::string("scan-context store growth: ") + hipGetErrorString(e); return PCM_ERR_HIP; }
-    hipFree(*p);
-  }
-  *p = np;
-  return PCM_OK;
-}
-
 // the shape of an empty store, its fixed-size buffers, and room for one more descriptor
 int ensure_store(pcm_ctx* c, ScStore* S, int R, int Sec) {
   if (S->count == 0 && (S->R != R || S->S != Sec)) {
-    SCCK(c, hipStreamSynchronize(c->stream));
-    for (void* p : {(void*)S->desc, (void*)S->rkey, (void*)S->skey, (void*)S->norm, (void*)S->table, (void*)S->ready})
-      if (p) hipFree(p);
-    S->desc = nullptr; S->rkey = nullptr; S->skey = nullptr; S->norm = nullptr; S->table = nullptr; S->ready = nullptr;
+    PCM_HIPCK(c, hipStreamSynchronize(c->stream));
+    S->desc.release(); S->rkey.release(); S->skey.release(); S->norm.release(); S->table.release(); S->ready.release();
     S->cap = 0;
     S->R = R; S->S = Sec;
   }
-  const size_t nb = (size_t)S->R * S->S;
-  if (!S->table) SCCK(c, hipMalloc(reinterpret_cast<void**>(&S->table), sizeof(uint32_t) * nb));
-  if (!S->ready) SCCK(c, hipMalloc(reinterpret_cast<void**>(&S->ready), sizeof(double) * nb));
-  if (!S->cand) SCCK(c, hipMalloc(reinterpret_cast<void**>(&S->cand), sizeof(int32_t) * kScMaxCandidates));
-  if (!S->d_res) SCCK(c, hipMalloc(reinterpret_cast<void**>(&S->d_res), sizeof(pcm_loam_sc_result)));
-  if (!S->h_res) SCCK(c, hipHostMalloc(reinterpret_cast<void**>(&S->h_res), sizeof(pcm_loam_sc_result)));
-  if (S->count + 1 > S->cap) {
-    const size_t cap = S->cap + S->cap / 2 + 256;
-    int rc;
-    if ((rc = regrow(c, &S->desc, S->count * nb, cap * nb)) != PCM_OK) return rc;
-    if ((rc = regrow(c, &S->rkey, S->count * S->R, cap * S->R)) != PCM_OK) return rc;
-    if ((rc = regrow(c, &S->skey, S->count * S->S, cap * S->S)) != PCM_OK) return rc;
-    if ((rc = regrow(c, &S->norm, S->count * S->S, cap * S->S)) != PCM_OK) return rc;
+  const size_t nb = (size_t)S->R * S->S, nr = (size_t)S->R, ns = (size_t)S->S;
+  int rc;
+  if ((rc = S->table.reserve(c, nb, nb)) != PCM_OK || (rc = S->ready.reserve(c, nb, nb)) != PCM_OK || (rc = S->cand.reserve(c, kScMaxCandidates, kScMaxCandidates)) != PCM_OK ||
+      (rc = S->d_res.reserve(c, 1, 1)) != PCM_OK || (rc = S->h_res.reserve(c, 1, 1)) != PCM_OK)
+    return rc;
+  if (S->count + 1 > S->cap) {   // the stored rows move to the larger arrays
+    const size_t cap = S->cap + S->cap / 2 + 256, n = S->count;
+    if ((rc = S->desc.reserve_keep(c, cap * nb, cap * nb, n * nb)) != PCM_OK || (rc = S->rkey.reserve_keep(c, cap * nr, cap * nr, n * nr)) != PCM_OK ||
+        (rc = S->skey.reserve_keep(c, cap * ns, cap * ns, n * ns)) != PCM_OK || (rc = S->norm.reserve_keep(c, cap * ns, cap * ns, n * ns)) != PCM_OK)
+      return rc;
     S->cap = cap;
   }
   return PCM_OK;
 }
 
 int ensure_set(pcm_ctx* c, ScStore* S, size_t n) {
-  if (n <= S->set_cap && S->keys) return PCM_OK;
-  SCCK(c, hipStreamSynchronize(c->stream));
-  if (S->keys) hipFree(S->keys);
-  if (S->dist) hipFree(S->dist);
-  if (S->shift) hipFree(S->shift);
-  S->keys = nullptr; S->dist = nullptr; S->shift = nullptr; S->set_cap = 0;
   const size_t cap = n + n / 2 + 256;
-  SCCK(c, hipMalloc(reinterpret_cast<void**>(&S->keys), sizeof(uint64_t) * cap));
-  SCCK(c, hipMalloc(reinterpret_cast<void**>(&S->dist), sizeof(double) * cap));
-  SCCK(c, hipMalloc(reinterpret_cast<void**>(&S->shift), sizeof(int32_t) * cap));
-  S->set_cap = cap;
-  return PCM_OK;
+  int rc;
+  if ((rc = S->keys.reserve(c, n, cap)) != PCM_OK || (rc = S->dist.reserve(c, n, cap)) != PCM_OK) return rc;
+  return S->shift.reserve(c, n, cap);
 }
 
 // table (or S->ready) -> row S->count of the store; the caller bumps the count
@@ -390,7 +324,6 @@ namespace loam {
 void loam_scstore_release(void* store) {
   ScStore* S = static_cast<ScStore*>(store);
   if (!S) return;
-  S->release();
   delete S;
 }
 }  // namespace loam
@@ -433,52 +366,29 @@ int pcm_loam_sc_add(pcm_ctx* c, const pcm_loam_sc_params* params, int input, int
     if (!loam_keyframe_cloud(c, key, 1, &cloud, &n_cloud)) { c->err = "pcm_loam_sc_add: key outside [0, K)"; return PCM_ERR_INVALID_ARGUMENT; }
     n_in = n_cloud;
   } else if (input == PCM_LOAM_SC_POINTS) {
-    if (!points && n) { c->err = "null point buffer"; return PCM_ERR_INVALID_ARGUMENT; }
-    if (stride < 3 * sizeof(float) || (stride % sizeof(float)) != 0) { c->err = "stride must be a multiple of 4 and >= 12 bytes"; return PCM_ERR_INVALID_ARGUMENT; }
-    if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
-    if (n > 0x3fffffffull) { c->err = "cloud too large"; return PCM_ERR_INVALID_ARGUMENT; }
+    if ((rc = check_point_records(c, points, n, stride, memory, 0x3fffffffull)) != PCM_OK) return rc;
     n_in = n;
   } else {
     c->err = "input must be PCM_LOAM_SC_POINTS, PCM_LOAM_SC_KEYFRAME_SURF or PCM_LOAM_SC_KEYFRAME_NEAR";
     return PCM_ERR_INVALID_ARGUMENT;
   }
-  SCCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   if ((rc = ensure_store(c, S, p.num_ring, p.num_sector)) != PCM_OK) return rc;
   hipStream_t st = c->stream;
   if (input == PCM_LOAM_SC_POINTS && n > 0) {
     const bool vg = p.leaf > 0.f;
     const size_t need = vg ? 2 * n : n;   // the staged cloud, then its cells
-    if (need > S->pts_cap || !S->pts) {
-      SCCK(c, hipStreamSynchronize(st));
-      if (S->pts) hipFree(S->pts);
-      S->pts = nullptr; S->pts_cap = 0;
-      const size_t cap = need + need / 4 + 1024;
-      SCCK(c, hipMalloc(reinterpret_cast<void**>(&S->pts), sizeof(float4) * cap));
-      S->pts_cap = cap;
-    }
-    const int has_w = stride >= 4 * sizeof(float) ? 1 : 0;
-    if (memory == PCM_MEM_DEVICE) {
-      k_sc_load<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(static_cast<const char*>(points), stride, (uint32_t)n, has_w, S->pts);
-      SCCK(c, hipGetLastError());
-    } else {
-      if (!has_w) SCCK(c, hipMemsetAsync(S->pts, 0, sizeof(float4) * n, st));
-      SCCK(c, hipMemcpy2DAsync(S->pts, sizeof(float4), points, stride, has_w ? sizeof(float4) : 3 * sizeof(float), n, hipMemcpyHostToDevice, st));
-    }
+    if ((rc = S->pts.reserve(c, need, need + need / 4 + 1024)) != PCM_OK) return rc;
+    if ((rc = load_xyzw_rows(c, points, n, stride, memory, true, S->pts)) != PCM_OK) return rc;
     cloud = S->pts;
     n_cloud = (uint32_t)n;
     if (vg) {
       // downSizeFilterSC: the VoxelGrid of pcm_voxel_downsample (one implementation, so the cells are the same bits)
       const size_t sb = voxel_downsample_scratch_bytes(n);
-      if (sb > S->vg_cap || !S->vg) {
-        SCCK(c, hipStreamSynchronize(st));
-        if (S->vg) hipFree(S->vg);
-        S->vg = nullptr; S->vg_cap = 0;
-        SCCK(c, hipMalloc(reinterpret_cast<void**>(&S->vg), sb + sb / 4));
-        S->vg_cap = sb + sb / 4;
-      }
+      if ((rc = S->vg.reserve(c, sb, sb + sb / 4)) != PCM_OK) return rc;
       size_t m = 0;
       float4* cells = S->pts + n;
-      if ((rc = voxel_downsample_device(st, S->pts, n, sizeof(float4), p.leaf, reinterpret_cast<float*>(cells), &m, S->vg, &c->err)) != PCM_OK) return rc;
+      if ((rc = voxel_downsample_device(st, S->pts, n, sizeof(float4), p.leaf, reinterpret_cast<float*>(cells), &m, S->vg.p, &c->err)) != PCM_OK) return rc;
       cloud = cells;
       n_cloud = (uint32_t)m;
     }
@@ -492,8 +402,8 @@ int pcm_loam_sc_add(pcm_ctx* c, const pcm_loam_sc_params* params, int input, int
     k_sc_bins<<<grid, 256, use_lds ? sizeof(uint32_t) * nb : 0, st>>>(cloud, n_cloud, sh, S->table, use_lds);
   }
   launch_finish(c, S, true);
-  SCCK(c, hipGetLastError());
-  SCCK(c, hipStreamSynchronize(st));   // the caller may reuse its buffers on return
+  PCM_HIPCK(c, hipGetLastError());
+  PCM_HIPCK(c, hipStreamSynchronize(st));   // the caller may reuse its buffers on return
   S->count++;
   if (result) {
     result->index = (int32_t)(S->count - 1);
@@ -516,12 +426,12 @@ int pcm_loam_sc_put(pcm_ctx* c, const double* desc, int num_ring, int num_sector
   const size_t nb = (size_t)num_ring * num_sector;
   for (size_t i = 0; i < nb; i++)
     if (!finite_d(desc[i]) || (double)(float)desc[i] != desc[i]) { c->err = "pcm_loam_sc_put: every entry must be representable as a float"; return PCM_ERR_INVALID_ARGUMENT; }
-  SCCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   if ((rc = ensure_store(c, S, num_ring, num_sector)) != PCM_OK) return rc;
-  SCCK(c, hipMemcpyAsync(S->ready, desc, sizeof(double) * nb, hipMemcpyHostToDevice, c->stream));
+  PCM_HIPCK(c, hipMemcpyAsync(S->ready, desc, sizeof(double) * nb, hipMemcpyHostToDevice, c->stream));
   launch_finish(c, S, false);
-  SCCK(c, hipGetLastError());
-  SCCK(c, hipStreamSynchronize(c->stream));
+  PCM_HIPCK(c, hipGetLastError());
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   S->count++;
   return PCM_OK;
 }
@@ -531,13 +441,13 @@ int pcm_loam_sc_get(pcm_ctx* c, int index, double* desc, float* ring_key, double
   int rc = check_ctx_sc(c, &S);
   if (rc != PCM_OK) return rc;
   if (index < 0 || (size_t)index >= S->count) { c->err = "pcm_loam_sc_get: index outside [0, count)"; return PCM_ERR_INVALID_ARGUMENT; }
-  SCCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   const size_t nb = (size_t)S->R * S->S, i = (size_t)index;
   std::vector<float> h(desc ? nb : 0);
-  if (desc) SCCK(c, hipMemcpyAsync(h.data(), S->desc + i * nb, sizeof(float) * nb, hipMemcpyDeviceToHost, c->stream));
-  if (ring_key) SCCK(c, hipMemcpyAsync(ring_key, S->rkey + i * S->R, sizeof(float) * S->R, hipMemcpyDeviceToHost, c->stream));
-  if (sector_key) SCCK(c, hipMemcpyAsync(sector_key, S->skey + i * S->S, sizeof(double) * S->S, hipMemcpyDeviceToHost, c->stream));
-  SCCK(c, hipStreamSynchronize(c->stream));
+  if (desc) PCM_HIPCK(c, hipMemcpyAsync(h.data(), S->desc + i * nb, sizeof(float) * nb, hipMemcpyDeviceToHost, c->stream));
+  if (ring_key) PCM_HIPCK(c, hipMemcpyAsync(ring_key, S->rkey + i * S->R, sizeof(float) * S->R, hipMemcpyDeviceToHost, c->stream));
+  if (sector_key) PCM_HIPCK(c, hipMemcpyAsync(sector_key, S->skey + i * S->S, sizeof(double) * S->S, hipMemcpyDeviceToHost, c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   if (desc) for (size_t k = 0; k < nb; k++) desc[k] = (double)h[k];
   return PCM_OK;
 }
@@ -593,10 +503,10 @@ int pcm_loam_sc_detect(pcm_ctx* c, const pcm_loam_sc_params* params, pcm_loam_sc
   S->counter++;
   const uint32_t T = (uint32_t)S->tree_size, q = (uint32_t)(S->count - 1);
   const uint32_t n_eval = p.num_candidates == 0 ? T : std::min<uint32_t>((uint32_t)p.num_candidates, T);
-  SCCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   if ((rc = ensure_set(c, S, T)) != PCM_OK) return rc;
   hipStream_t st = c->stream;
-  SCCK(c, hipMemsetAsync(S->d_res, 0, sizeof(pcm_loam_sc_result), st));
+  PCM_HIPCK(c, hipMemsetAsync(S->d_res, 0, sizeof(pcm_loam_sc_result), st));
   k_sc_ringkeys<<<(T + 255) / 256, 256, 0, st>>>(S->rkey, S->R, q, T, S->keys);
   const int32_t* cand = nullptr;
   if (p.num_candidates > 0) {
@@ -605,9 +515,9 @@ int pcm_loam_sc_detect(pcm_ctx* c, const pcm_loam_sc_params* params, pcm_loam_sc
   }
   launch_distance(c, S, q, cand, 0u, n_eval, p.search_ratio);
   k_sc_fold<<<1, 1024, 0, st>>>(S->dist, S->shift, cand, n_eval, S->keys, p.dist_threshold, S->d_res);
-  SCCK(c, hipGetLastError());
-  SCCK(c, hipMemcpyAsync(S->h_res, S->d_res, sizeof(pcm_loam_sc_result), hipMemcpyDeviceToHost, st));
-  SCCK(c, hipStreamSynchronize(st));
+  PCM_HIPCK(c, hipGetLastError());
+  PCM_HIPCK(c, hipMemcpyAsync(S->h_res, S->d_res, sizeof(pcm_loam_sc_result), hipMemcpyDeviceToHost, st));
+  PCM_HIPCK(c, hipStreamSynchronize(st));
   *result = *S->h_res;
   result->yaw_diff_rad = sc_yaw(result->nn_align, S->S);
   result->num_descriptors = (int32_t)S->count;
@@ -627,15 +537,15 @@ int pcm_loam_sc_distance(pcm_ctx* c, const pcm_loam_sc_params* params, int i, in
   if (S->count > 0) { p.num_ring = S->R; p.num_sector = S->S; }   // as pcm_loam_sc_detect
   if ((rc = check_scparams(c, S, p)) != PCM_OK) return rc;
   if (i < 0 || j < 0 || (size_t)i >= S->count || (size_t)j >= S->count) { c->err = "pcm_loam_sc_distance: index outside [0, count)"; return PCM_ERR_INVALID_ARGUMENT; }
-  SCCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   if ((rc = ensure_set(c, S, 1)) != PCM_OK) return rc;
   launch_distance(c, S, (uint32_t)i, nullptr, (uint32_t)j, 1u, p.search_ratio);
-  SCCK(c, hipGetLastError());
+  PCM_HIPCK(c, hipGetLastError());
   double d = 0.0;
   int32_t s = 0;
-  SCCK(c, hipMemcpyAsync(&d, S->dist, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  SCCK(c, hipMemcpyAsync(&s, S->shift, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  SCCK(c, hipStreamSynchronize(c->stream));
+  PCM_HIPCK(c, hipMemcpyAsync(&d, S->dist, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  PCM_HIPCK(c, hipMemcpyAsync(&s, S->shift, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   if (dist) *dist = d;
   if (shift) *shift = s;
   return PCM_OK;

@@ -15,9 +15,9 @@
 // updates of the same state give the same bits.
 // laserCloudMapContainer (the reference's cache of transformed clouds) never changes a result and is not kept: when the selection,
 // the poses and the leaves equal those of the previous update the call does nothing at all, which is the common case at LiDAR rate.
+#include "host_util.h"
 #include "loam_device.h"
 #include "loam_submap.h"
-#include "pcm_host.h"
 
 #include <cstring>
 #include <new>
@@ -27,15 +27,6 @@ using namespace pcm;
 using namespace pcm::loam;
 
 namespace {
-
-#define SMCK(ctx, x)                                                                 \
-  do {                                                                               \
-    hipError_t e_ = (x);                                                             \
-    if (e_ != hipSuccess) {                                                          \
-      (ctx)->err = std::string(#x) + ": " + hipGetErrorString(e_);                   \
-      return PCM_ERR_HIP;                                                            \
-    }                                                                                \
-  } while (0)
 
 // one cloud of one selected key frame: points [src, src + count) of an arena go to output positions [first, first + count)
 struct SmEntry {
@@ -110,8 +101,7 @@ __global__ void __launch_bounds__(256) k_sm_average(const float4* __restrict__ i
       const float4 q = in[vals[j]];
       acc[0] += (double)q.x; acc[1] += (double)q.y; acc[2] += (double)q.z; acc[3] += (double)q.w;
     }
-    for (int k = 0; k < 4; k++)
-      for (int off = 32; off >= 1; off >>= 1) acc[k] += __shfl_xor(acc[k], off, 64);
+    for (int k = 0; k < 4; k++) acc[k] = wave_sum_f64(acc[k]);
     if (lane == 0) {
       const double m = (double)(e - b);
       const float4 r = make_float4((float)(acc[0] / m), (float)(acc[1] / m), (float)(acc[2] / m), (float)(acc[3] / m));
@@ -131,53 +121,29 @@ __global__ void k_sm_store_source(const float4* __restrict__ feats, const float4
   if (i < n_c) dst_c[i] = p; else dst_s[i - n_c] = p;
 }
 
-// strided device records -> PointXYZI rows
-__global__ void k_sm_load(const char* __restrict__ base, size_t stride, uint32_t n, int has_w, float4* __restrict__ dst) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float* p = reinterpret_cast<const float*>(base + (size_t)i * stride);
-  dst[i] = make_float4(p[0], p[1], p[2], has_w ? p[3] : 0.f);
-}
-
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // device workspace of one gather + VoxelGrid pass
 struct SmWork {
-  char* buf = nullptr;
+  DevBuf<char> buf;
   size_t n_cap = 0, ent_cap = 0;
   size_t o_in = 0, o_cells = 0, o_keys = 0, o_keys_s = 0, o_vals = 0, o_vals_s = 0, o_head = 0, o_slot = 0, o_mm = 0, o_box = 0, o_small = 0, o_ent = 0,
          o_tmp = 0, o_tmp2 = 0, tmp_bytes = 0, tmp2_bytes = 0;
-  uint32_t* h_small = nullptr;   // pinned
-  SmEntry* h_ent = nullptr;      // pinned staging of the entry table
-  size_t h_ent_cap = 0;
+  PinnedBuf<uint32_t> h_small;
+  PinnedBuf<SmEntry> h_ent;      // staging of the entry table
 
-  float4* in() const { return reinterpret_cast<float4*>(buf + o_in); }
-  float4* cells() const { return reinterpret_cast<float4*>(buf + o_cells); }
-  uint32_t* small() const { return reinterpret_cast<uint32_t*>(buf + o_small); }
-
-  void release() {
-    if (buf) hipFree(buf);
-    if (h_small) hipHostFree(h_small);
-    if (h_ent) hipHostFree(h_ent);
-    buf = nullptr; h_small = nullptr; h_ent = nullptr; n_cap = ent_cap = h_ent_cap = 0;
-  }
+  float4* in() const { return reinterpret_cast<float4*>(buf.p + o_in); }
+  float4* cells() const { return reinterpret_cast<float4*>(buf.p + o_cells); }
+  uint32_t* small() const { return reinterpret_cast<uint32_t*>(buf.p + o_small); }
 };
 
 int ensure_work(pcm_ctx* c, SmWork* W, size_t N, size_t n_ent, bool want_cells) {
-  if (!W->h_small) SMCK(c, hipHostMalloc(reinterpret_cast<void**>(&W->h_small), sizeof(uint32_t) * kSmallWords));
-  if (n_ent > W->h_ent_cap) {
-    SMCK(c, hipStreamSynchronize(c->stream));
-    if (W->h_ent) hipHostFree(W->h_ent);
-    W->h_ent = nullptr; W->h_ent_cap = 0;
-    const size_t cap = n_ent + n_ent / 2 + 16;
-    SMCK(c, hipHostMalloc(reinterpret_cast<void**>(&W->h_ent), sizeof(SmEntry) * cap));
-    W->h_ent_cap = cap;
-  }
+  int rc = W->h_small.reserve(c, kSmallWords, kSmallWords);
+  if (rc != PCM_OK) return rc;
+  if (n_ent > W->h_ent.cap && (rc = W->h_ent.reserve(c, n_ent, n_ent + n_ent / 2 + 16)) != PCM_OK) return rc;
   if (W->buf && N <= W->n_cap && n_ent <= W->ent_cap) return PCM_OK;
-  SMCK(c, hipStreamSynchronize(c->stream));
-  if (W->buf) hipFree(W->buf);
-  W->buf = nullptr; W->n_cap = W->ent_cap = 0;
-  const size_t nc = N + N / 4 + 1024, ec = W->h_ent_cap;
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
+  W->buf.release();   // the layout below is for the new sizes alone
+  W->n_cap = W->ent_cap = 0;
+  const size_t nc = N + N / 4 + 1024, ec = W->h_ent.cap;
   size_t o = 0;
   auto take = [&](size_t bytes) { const size_t r = o; o += up256(bytes); return r; };
   W->o_in = take(16 * nc);
@@ -188,29 +154,16 @@ int ensure_work(pcm_ctx* c, SmWork* W, size_t N, size_t n_ent, bool want_cells) 
   W->o_ent = take(sizeof(SmEntry) * ec);
   sv_temp_bytes(nc, &W->tmp_bytes, &W->tmp2_bytes);
   W->o_tmp = take(W->tmp_bytes); W->o_tmp2 = take(W->tmp2_bytes);
-  SMCK(c, hipMalloc(reinterpret_cast<void**>(&W->buf), o));
+  if ((rc = W->buf.reserve(c, o, o)) != PCM_OK) return rc;
   W->n_cap = nc; W->ent_cap = ec;
   return PCM_OK;
 }
 
 struct Arena {
-  float4* d = nullptr;
-  size_t n = 0, cap = 0;
+  DevBuf<float4> d{"key-frame arena"};
+  size_t n = 0;
   // room for `extra` more points; growth copies device to device
-  int reserve(pcm_ctx* c, size_t extra) {
-    if (d && n + extra <= cap) return PCM_OK;
-    const size_t want = std::max<size_t>(n + extra, cap + cap / 2 + 65536);
-    float4* nd = nullptr;
-    SMCK(c, hipMalloc(reinterpret_cast<void**>(&nd), sizeof(float4) * want));
-    if (d) {
-      hipError_t e = n ? hipMemcpyAsync(nd, d, sizeof(float4) * n, hipMemcpyDeviceToDevice, c->stream) : hipSuccess;
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      if (e != hipSuccess) { hipFree(nd); c->err = std::string("key-frame arena growth: ") + hipGetErrorString(e); return PCM_ERR_HIP; }
-      hipFree(d);
-    }
-    d = nd; cap = want;
-    return PCM_OK;
-  }
+  int reserve(pcm_ctx* c, size_t extra) { return d.reserve_keep(c, n + extra, std::max<size_t>(n + extra, d.cap + d.cap / 2 + 65536), n); }
 };
 
 struct KeyFrame {
@@ -224,8 +177,7 @@ struct KeyStore {
   std::vector<KeyFrame> kf;
   std::vector<KeyPose> kp;   // what the selection reads
   Arena arena[2];            // corner, surf
-  float* mats = nullptr;     // [K][12]
-  size_t mats_cap = 0;       // key frames
+  DevBuf<float> mats{"key-frame matrices"};   // [K][12]
   uint64_t gen = 1;          // bumps whenever a key frame or a pose changes
   SmWork upd, near;
   // the last update
@@ -257,33 +209,16 @@ void host_matrix(const float* pose6, float* T12) {
 
 int upload_matrices(pcm_ctx* c, KeyStore* S, size_t first, size_t n) {
   const size_t K = S->kf.size();
-  if (K > S->mats_cap || !S->mats) {
-    const size_t cap = K + K / 2 + 256;
-    float* nm = nullptr;
-    SMCK(c, hipMalloc(reinterpret_cast<void**>(&nm), sizeof(float) * 12 * cap));
-    SMCK(c, hipStreamSynchronize(c->stream));
-    if (S->mats) hipFree(S->mats);
-    S->mats = nm; S->mats_cap = cap;
+  if (12 * K > S->mats.cap || !S->mats) {
+    int rc = S->mats.reserve_keep(c, 12 * K, 12 * (K + K / 2 + 256), 0);
+    if (rc != PCM_OK) return rc;
     first = 0; n = K;   // a fresh array gets every matrix
   }
   if (n == 0) return PCM_OK;
   std::vector<float> T(12 * n);
   for (size_t i = 0; i < n; i++) host_matrix(S->kf[first + i].pose, T.data() + 12 * i);
-  SMCK(c, hipMemcpyAsync(S->mats + 12 * first, T.data(), sizeof(float) * 12 * n, hipMemcpyHostToDevice, c->stream));
-  SMCK(c, hipStreamSynchronize(c->stream));
-  return PCM_OK;
-}
-
-int load_cloud_xyzi(pcm_ctx* c, const void* pts, size_t n, size_t stride, int memory, float4* dst) {
-  if (n == 0) return PCM_OK;
-  const int has_w = stride >= 4 * sizeof(float) ? 1 : 0;
-  if (memory == PCM_MEM_DEVICE) {
-    k_sm_load<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(static_cast<const char*>(pts), stride, (uint32_t)n, has_w, dst);
-    SMCK(c, hipGetLastError());
-    return PCM_OK;
-  }
-  if (!has_w) SMCK(c, hipMemsetAsync(dst, 0, sizeof(float4) * n, c->stream));
-  SMCK(c, hipMemcpy2DAsync(dst, sizeof(float4), pts, stride, has_w ? sizeof(float4) : 3 * sizeof(float), n, hipMemcpyHostToDevice, c->stream));
+  PCM_HIPCK(c, hipMemcpyAsync(S->mats + 12 * first, T.data(), sizeof(float) * 12 * n, hipMemcpyHostToDevice, c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   return PCM_OK;
 }
 
@@ -291,7 +226,7 @@ int load_cloud_xyzi(pcm_ctx* c, const void* pts, size_t n, size_t stride, int me
 // segment 1 -> out1; the counts and the overflow flag come back through W->h_small.
 int run_pass(pcm_ctx* c, KeyStore* S, SmWork* W, size_t n_ent, uint32_t N, uint32_t n0, float leaf0, float leaf1, float4* out0, float4* out1) {
   hipStream_t st = c->stream;
-  char* b = W->buf;
+  char* b = W->buf.p;
   SmEntry* d_ent = reinterpret_cast<SmEntry*>(b + W->o_ent);
   unsigned int* mm = reinterpret_cast<unsigned int*>(b + W->o_mm);
   long long* box = reinterpret_cast<long long*>(b + W->o_box);
@@ -302,30 +237,28 @@ int run_pass(pcm_ctx* c, KeyStore* S, SmWork* W, size_t n_ent, uint32_t N, uint3
   V.head = reinterpret_cast<uint32_t*>(b + W->o_head); V.slot = reinterpret_cast<uint32_t*>(b + W->o_slot);
   V.scnt = small; V.sfirst = small + 2; V.nc = small + 4;
   V.tmp = b + W->o_tmp; V.tmp_bytes = W->tmp_bytes; V.tmp2 = b + W->o_tmp2; V.tmp2_bytes = W->tmp2_bytes;
-  SMCK(c, hipMemcpyAsync(d_ent, W->h_ent, sizeof(SmEntry) * n_ent, hipMemcpyHostToDevice, st));
-  SMCK(c, hipMemsetAsync(small, 0, sizeof(uint32_t) * kSmallWords, st));
+  PCM_HIPCK(c, hipMemcpyAsync(d_ent, W->h_ent, sizeof(SmEntry) * n_ent, hipMemcpyHostToDevice, st));
+  PCM_HIPCK(c, hipMemsetAsync(small, 0, sizeof(uint32_t) * kSmallWords, st));
   sv_clear(st, mm, small, 2);
   const unsigned nb = (N + 255) / 256;
   k_sm_gather<<<nb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, d_ent, (uint32_t)n_ent, N, W->in(), mm);
   k_sm_boxes<<<1, 64, 0, st>>>(mm, leaf0, leaf1, box, small);
   k_sm_keys<<<nb, 256, 0, st>>>(W->in(), N, n0, leaf0, leaf1, box, V.keys, V.vals);
-  SMCK(c, hipGetLastError());
+  PCM_HIPCK(c, hipGetLastError());
   int rc = sv_sort_cells(c, st, V, N, 2);
   if (rc != PCM_OK) return rc;
   const unsigned gb = std::min<unsigned>(1024u, (N + 3) / 4);
   k_sm_average<<<gb, 256, 0, st>>>(W->in(), V.vals_s, V.vals, small, out0, out1);
-  SMCK(c, hipGetLastError());
-  SMCK(c, hipMemcpyAsync(W->h_small, small, sizeof(uint32_t) * kSmallWords, hipMemcpyDeviceToHost, st));
-  SMCK(c, hipStreamSynchronize(st));
+  PCM_HIPCK(c, hipGetLastError());
+  PCM_HIPCK(c, hipMemcpyAsync(W->h_small, small, sizeof(uint32_t) * kSmallWords, hipMemcpyDeviceToHost, st));
+  PCM_HIPCK(c, hipStreamSynchronize(st));
   return PCM_OK;
 }
 
-bool finite_f(float v) { return v == v && v <= 3.0e38f && v >= -3.0e38f; }
-
 int check_sparams(pcm_ctx* c, const pcm_loam_submap_params& p) {
-  if (!(p.search_radius > 0.f) || !finite_f(p.search_radius)) { c->err = "search_radius must be a positive number"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (!(p.keypose_density > 0.f) || !finite_f(p.keypose_density)) { c->err = "keypose_density must be a positive number"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (!(p.corner_leaf >= 0.f) || !(p.surf_leaf >= 0.f) || !finite_f(p.corner_leaf) || !finite_f(p.surf_leaf)) {
+  if (!(p.search_radius > 0.f) || !finite_f_3e38(p.search_radius)) { c->err = "search_radius must be a positive number"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!(p.keypose_density > 0.f) || !finite_f_3e38(p.keypose_density)) { c->err = "keypose_density must be a positive number"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!(p.corner_leaf >= 0.f) || !(p.surf_leaf >= 0.f) || !finite_f_3e38(p.corner_leaf) || !finite_f_3e38(p.surf_leaf)) {
     c->err = "corner_leaf and surf_leaf must be >= 0 (0: no down-sampling)"; return PCM_ERR_INVALID_ARGUMENT;
   }
   if (!(p.recent_window_s == p.recent_window_s)) { c->err = "recent_window_s must be a number"; return PCM_ERR_INVALID_ARGUMENT; }
@@ -339,10 +272,6 @@ namespace loam {
 void loam_keystore_release(void* store) {
   KeyStore* S = static_cast<KeyStore*>(store);
   if (!S) return;
-  for (int a = 0; a < 2; a++) if (S->arena[a].d) hipFree(S->arena[a].d);
-  if (S->mats) hipFree(S->mats);
-  S->upd.release();
-  S->near.release();
   delete S;
 }
 
@@ -391,7 +320,7 @@ int pcm_loam_keyframe_add(pcm_ctx* c, const float pose6[6], double time, const v
   int rc = check_ctx_sm(c, &S);
   if (rc != PCM_OK) return rc;
   if (!pose6) { c->err = "null pose"; return PCM_ERR_INVALID_ARGUMENT; }
-  for (int k = 0; k < 6; k++) if (!finite_f(pose6[k])) { c->err = "the pose must be finite"; return PCM_ERR_INVALID_ARGUMENT; }
+  for (int k = 0; k < 6; k++) if (!finite_f_3e38(pose6[k])) { c->err = "the pose must be finite"; return PCM_ERR_INVALID_ARGUMENT; }
   if (!(time == time)) { c->err = "the time must be a number"; return PCM_ERR_INVALID_ARGUMENT; }
   const bool from_source = !corner && !surf;
   const float4* feats = nullptr; const float4* xyzi = nullptr; const float* inten = nullptr;
@@ -413,7 +342,7 @@ int pcm_loam_keyframe_add(pcm_ctx* c, const float pose6[6], double time, const v
   if (n_corner > 0x3fffffffull || n_surf > 0x3fffffffull || S->arena[0].n + n_corner > 0xffffffffull || S->arena[1].n + n_surf > 0xffffffffull) {
     c->err = "key-frame store too large"; return PCM_ERR_INVALID_ARGUMENT;
   }
-  SMCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   if ((rc = S->arena[0].reserve(c, n_corner)) != PCM_OK || (rc = S->arena[1].reserve(c, n_surf)) != PCM_OK) return rc;
   float4* dc = S->arena[0].d + S->arena[0].n;
   float4* ds = S->arena[1].d + S->arena[1].n;
@@ -421,11 +350,11 @@ int pcm_loam_keyframe_add(pcm_ctx* c, const float pose6[6], double time, const v
     const uint32_t n = (uint32_t)(n_corner + n_surf);
     if (n) {
       k_sm_store_source<<<(n + 255) / 256, 256, 0, c->stream>>>(feats, xyzi, inten, (uint32_t)n_corner, (uint32_t)n_surf, dc, ds);
-      SMCK(c, hipGetLastError());
+      PCM_HIPCK(c, hipGetLastError());
     }
   } else {
-    if ((rc = load_cloud_xyzi(c, corner, n_corner, stride, memory, dc)) != PCM_OK) return rc;
-    if ((rc = load_cloud_xyzi(c, surf, n_surf, stride, memory, ds)) != PCM_OK) return rc;
+    if ((rc = load_xyzw_rows(c, corner, n_corner, stride, memory, true, dc)) != PCM_OK) return rc;
+    if ((rc = load_xyzw_rows(c, surf, n_surf, stride, memory, true, ds)) != PCM_OK) return rc;
   }
   KeyFrame k{};
   for (int a = 0; a < 6; a++) k.pose[a] = pose6[a];
@@ -450,8 +379,8 @@ int pcm_loam_keyframe_set_poses(pcm_ctx* c, int first, int n, const float* pose6
   if (first < 0 || n < 0 || (long long)first + n > K) { c->err = "pcm_loam_keyframe_set_poses: first + n exceeds the number of key frames"; return PCM_ERR_INVALID_ARGUMENT; }
   if (n == 0) return PCM_OK;
   if (!pose6) { c->err = "null poses"; return PCM_ERR_INVALID_ARGUMENT; }
-  for (int i = 0; i < 6 * n; i++) if (!finite_f(pose6[i])) { c->err = "the poses must be finite"; return PCM_ERR_INVALID_ARGUMENT; }
-  SMCK(c, hipSetDevice(c->device));
+  for (int i = 0; i < 6 * n; i++) if (!finite_f_3e38(pose6[i])) { c->err = "the poses must be finite"; return PCM_ERR_INVALID_ARGUMENT; }
+  PCM_HIPCK(c, hipSetDevice(c->device));
   for (int i = 0; i < n; i++) {
     KeyFrame& k = S->kf[(size_t)(first + i)];
     for (int a = 0; a < 6; a++) k.pose[a] = pose6[6 * i + a];
@@ -491,10 +420,10 @@ int pcm_loam_keyframe_get(pcm_ctx* c, int key, float* corner, size_t cap_corner,
   if (n_corner) *n_corner = k.n_c;
   if (n_surf) *n_surf = k.n_s;
   if ((corner && cap_corner < k.n_c) || (surf && cap_surf < k.n_s)) { c->err = "pcm_loam_keyframe_get: capacity too small (the counts are set)"; return PCM_ERR_INVALID_ARGUMENT; }
-  SMCK(c, hipSetDevice(c->device));
-  if (corner && k.n_c) SMCK(c, hipMemcpyAsync(corner, S->arena[0].d + k.off_c, sizeof(float4) * k.n_c, hipMemcpyDeviceToHost, c->stream));
-  if (surf && k.n_s) SMCK(c, hipMemcpyAsync(surf, S->arena[1].d + k.off_s, sizeof(float4) * k.n_s, hipMemcpyDeviceToHost, c->stream));
-  SMCK(c, hipStreamSynchronize(c->stream));
+  PCM_HIPCK(c, hipSetDevice(c->device));
+  if (corner && k.n_c) PCM_HIPCK(c, hipMemcpyAsync(corner, S->arena[0].d + k.off_c, sizeof(float4) * k.n_c, hipMemcpyDeviceToHost, c->stream));
+  if (surf && k.n_s) PCM_HIPCK(c, hipMemcpyAsync(surf, S->arena[1].d + k.off_s, sizeof(float4) * k.n_s, hipMemcpyDeviceToHost, c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   return PCM_OK;
 }
 
@@ -535,7 +464,7 @@ int pcm_loam_submap_update(pcm_ctx* c, const pcm_loam_submap_params* params, dou
     *result = r;
     return PCM_OK;
   }
-  SMCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   S->last_valid = false;
   const size_t E = sel.keys.size();
   uint64_t n_c = 0, n_s = 0;
@@ -547,7 +476,7 @@ int pcm_loam_submap_update(pcm_ctx* c, const pcm_loam_submap_params* params, dou
   const uint32_t N = (uint32_t)(n_c + n_s);
   if ((rc = ensure_work(c, &S->upd, N, 2 * E, false)) != PCM_OK) return rc;
   if (N > 0) {
-    SMCK(c, hipStreamSynchronize(c->stream));   // the pinned staging of an earlier pass is free again
+    PCM_HIPCK(c, hipStreamSynchronize(c->stream));   // the pinned staging of an earlier pass is free again
     uint32_t first = 0;
     for (size_t i = 0; i < E; i++) {
       const KeyFrame& k = S->kf[(size_t)sel.keys[i]];
@@ -588,7 +517,7 @@ int pcm_loam_submap_near(pcm_ctx* c, int key, int search_num, int wrt_key, float
   if (n_out) *n_out = 0;
   const int K = (int)S->kf.size();
   if (search_num < 0) { c->err = "search_num must be >= 0"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (!(leaf >= 0.f) || !finite_f(leaf)) { c->err = "leaf must be >= 0 (0: no down-sampling)"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!(leaf >= 0.f) || !finite_f_3e38(leaf)) { c->err = "leaf must be >= 0 (0: no down-sampling)"; return PCM_ERR_INVALID_ARGUMENT; }
   if (K == 0) return PCM_OK;   // nothing to assemble
   if (key < 0 || key >= K) { c->err = "pcm_loam_submap_near: key outside [0, K)"; return PCM_ERR_INVALID_ARGUMENT; }
   if (wrt_key >= K) { c->err = "pcm_loam_submap_near: wrt_key outside [0, K)"; return PCM_ERR_INVALID_ARGUMENT; }
@@ -598,10 +527,10 @@ int pcm_loam_submap_near(pcm_ctx* c, int key, int search_num, int wrt_key, float
   if (N64 > 0x7fffffffull) { c->err = "the selected key frames hold more than 2^31 points"; return PCM_ERR_OUT_OF_RANGE; }
   if (N64 == 0) return PCM_OK;
   const uint32_t N = (uint32_t)N64;
-  SMCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   const size_t E = 2 * keys.size();
   if ((rc = ensure_work(c, &S->near, N, E, true)) != PCM_OK) return rc;
-  SMCK(c, hipStreamSynchronize(c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   uint32_t first = 0;
   for (size_t i = 0; i < keys.size(); i++) {
     const KeyFrame& k = S->kf[(size_t)keys[i]];
@@ -618,8 +547,8 @@ int pcm_loam_submap_near(pcm_ctx* c, int key, int search_num, int wrt_key, float
   if (n_out) *n_out = m;
   if (m > cap || (!out && m)) { c->err = "pcm_loam_submap_near: capacity too small (the count is set)"; return PCM_ERR_INVALID_ARGUMENT; }
   if (m) {
-    SMCK(c, hipMemcpyAsync(out, cells, sizeof(float4) * m, hipMemcpyDeviceToHost, c->stream));
-    SMCK(c, hipStreamSynchronize(c->stream));
+    PCM_HIPCK(c, hipMemcpyAsync(out, cells, sizeof(float4) * m, hipMemcpyDeviceToHost, c->stream));
+    PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   }
   return PCM_OK;
 }
@@ -631,14 +560,14 @@ int pcm_loam_submap_info(pcm_ctx* c, int32_t* keys, float* corner_in, float* sur
   const float4 *tc = nullptr, *ts = nullptr;
   uint32_t tnc = 0, tns = 0;
   if (!S->last_valid || !loam_target_view(c, &tc, &tnc, &ts, &tns)) { c->err = "pcm_loam_submap_info: the context's target is not the result of pcm_loam_submap_update"; return PCM_ERR_NO_INPUT; }
-  SMCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   if (keys && !S->last_keys.empty()) std::memcpy(keys, S->last_keys.data(), sizeof(int32_t) * S->last_keys.size());
   const size_t n_c = (size_t)S->last.num_corner_in, n_s = (size_t)S->last.num_surf_in;
-  if (corner_in && n_c) SMCK(c, hipMemcpyAsync(corner_in, S->upd.in(), sizeof(float4) * n_c, hipMemcpyDeviceToHost, c->stream));
-  if (surf_in && n_s) SMCK(c, hipMemcpyAsync(surf_in, S->upd.in() + n_c, sizeof(float4) * n_s, hipMemcpyDeviceToHost, c->stream));
-  if (corner_map && tnc) SMCK(c, hipMemcpyAsync(corner_map, tc, sizeof(float4) * tnc, hipMemcpyDeviceToHost, c->stream));
-  if (surf_map && tns) SMCK(c, hipMemcpyAsync(surf_map, ts, sizeof(float4) * tns, hipMemcpyDeviceToHost, c->stream));
-  SMCK(c, hipStreamSynchronize(c->stream));
+  if (corner_in && n_c) PCM_HIPCK(c, hipMemcpyAsync(corner_in, S->upd.in(), sizeof(float4) * n_c, hipMemcpyDeviceToHost, c->stream));
+  if (surf_in && n_s) PCM_HIPCK(c, hipMemcpyAsync(surf_in, S->upd.in() + n_c, sizeof(float4) * n_s, hipMemcpyDeviceToHost, c->stream));
+  if (corner_map && tnc) PCM_HIPCK(c, hipMemcpyAsync(corner_map, tc, sizeof(float4) * tnc, hipMemcpyDeviceToHost, c->stream));
+  if (surf_map && tns) PCM_HIPCK(c, hipMemcpyAsync(surf_map, ts, sizeof(float4) * tns, hipMemcpyDeviceToHost, c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   return PCM_OK;
 }
 

@@ -9,9 +9,9 @@
 // the S x beam_size table.  k_occ_trace: one lane per (scan, beam), atomicAdd of 1 on the end cell and along the Bresenham walk.
 // Integer minima and integer sums do not depend on the schedule or on how scans are batched.
 // k_occ_bounds: bounding box and number of the known cells; k_occ_render: the cropped int8 grid, its PGM bytes and the counters.
+#include "host_util.h"
 #include "loam_device.h"
 #include "occ_map.h"
-#include "pcm_host.h"
 
 #include <algorithm>
 #include <cstring>
@@ -22,15 +22,6 @@ using namespace pcm;
 using namespace pcm::occ;
 
 namespace {
-
-#define OCCK(ctx, x)                                                                 \
-  do {                                                                               \
-    hipError_t e_ = (x);                                                             \
-    if (e_ != hipSuccess) {                                                          \
-      (ctx)->err = std::string(#x) + ": " + hipGetErrorString(e_);                   \
-      return PCM_ERR_HIP;                                                            \
-    }                                                                                \
-  } while (0)
 
 constexpr uint32_t kChunkBeams = 1u << 24;    // entries of the beam table of one set of launches
 constexpr uint64_t kChunkPoints = 1ull << 30; // points of one set of launches
@@ -47,14 +38,6 @@ struct OccPose { double yaw, x, y; };
 __global__ void k_occ_fill(uint32_t* __restrict__ p, uint32_t n, uint32_t v) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
-}
-
-// strided device records -> float4 rows
-__global__ void k_occ_load(const char* __restrict__ base, size_t stride, uint32_t n, float4* __restrict__ dst) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float* p = reinterpret_cast<const float*>(base + (size_t)i * stride);
-  dst[i] = make_float4(p[0], p[1], p[2], 0.f);
 }
 
 // old rectangle -> its place in the new one (the new one covers it)
@@ -109,19 +92,6 @@ __global__ void __launch_bounds__(256) k_occ_trace(const uint32_t* __restrict__ 
   if (trace) occ_trace_line(rx, ry, cx, cy, [&](int x, int y) { occ_add(cells, R, x, y, 1, small); });
 }
 
-__device__ inline uint32_t wave_min_u32(uint32_t v) {
-  for (int off = 32; off >= 1; off >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, off, 64));
-  return v;
-}
-__device__ inline uint32_t wave_max_u32(uint32_t v) {
-  for (int off = 32; off >= 1; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off, 64));
-  return v;
-}
-__device__ inline uint32_t wave_sum_u32(uint32_t v) {
-  for (int off = 32; off >= 1; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, 64);
-  return v;
-}
-
 // bounding box (offsets inside the rectangle) and number of the known cells; init_slot: the cell the map was initialised at, or -1
 __global__ void __launch_bounds__(256) k_occ_bounds(const uint2* __restrict__ cells, OccRect R, long long init_slot, uint32_t* __restrict__ small) {
   const long long n = R.w * R.h;
@@ -134,9 +104,9 @@ __global__ void __launch_bounds__(256) k_occ_bounds(const uint2* __restrict__ ce
     mny = min(mny, (uint32_t)cy); mxy = max(mxy, (uint32_t)cy);
     cnt++;
   }
-  cnt = wave_sum_u32(cnt);
+  cnt = loam::wave_sum_u32(cnt);
   if (cnt == 0u) return;   // the same in every lane of the wave
-  mnx = wave_min_u32(mnx); mxx = wave_max_u32(mxx); mny = wave_min_u32(mny); mxy = wave_max_u32(mxy);
+  mnx = loam::wave_min_u32(mnx); mxx = loam::wave_max_u32(mxx); mny = loam::wave_min_u32(mny); mxy = loam::wave_max_u32(mxy);
   if ((threadIdx.x & 63) == 0) {
     atomicMin(&small[kMinX], mnx); atomicMax(&small[kMaxX], mxx);
     atomicMin(&small[kMinY], mny); atomicMax(&small[kMaxY], mxy);
@@ -165,40 +135,27 @@ struct OccMap {
   OccParams P{};
   uint32_t beams = 0;
   OccRect R{0, 0, 0, 0};
-  uint2* cells = nullptr;
-  size_t cells_cap = 0;          // cells of the allocation (a reset keeps it)
+  DevBuf<uint2> cells;           // cap: cells of the allocation (a reset keeps it)
   bool have_init = false;
   int init_x = 0, init_y = 0;
   uint64_t n_scans = 0, overflow = 0;
   // the last set of launches
-  uint32_t* table = nullptr;
-  size_t table_cap = 0;
+  DevBuf<uint32_t> table;
   uint32_t last_scans = 0;
-  OccSeg* d_seg = nullptr;
-  uint32_t* d_off = nullptr;
-  OccPose* d_pose = nullptr;
-  size_t seg_cap = 0, off_cap = 0, pose_cap = 0;
-  float4* stage = nullptr;
-  size_t stage_cap = 0;
-  uint32_t* d_small = nullptr;
-  uint32_t* h_small = nullptr;   // pinned
+  DevBuf<OccSeg> d_seg;
+  DevBuf<uint32_t> d_off;
+  DevBuf<OccPose> d_pose;
+  DevBuf<float4> stage;
+  DevBuf<uint32_t> d_small;
+  PinnedBuf<uint32_t> h_small;
   // the last render
   bool rendered = false;
   uint32_t cw = 0, ch = 0, n_known = 0;
   long long cx0 = 0, cy0 = 0;    // cell index of the crop's first cell
-  int8_t* d_grid = nullptr;
-  unsigned char* d_pgm = nullptr;
-  uint32_t* d_cnt = nullptr;     // [2][cw * ch]
-  size_t out_cap = 0;
-
-  void release() {
-    for (void* p : {(void*)cells, (void*)table, (void*)d_seg, (void*)d_off, (void*)d_pose, (void*)stage, (void*)d_small, (void*)d_grid, (void*)d_pgm, (void*)d_cnt})
-      if (p) hipFree(p);
-    if (h_small) hipHostFree(h_small);
-  }
+  DevBuf<int8_t> d_grid;
+  DevBuf<unsigned char> d_pgm;
+  DevBuf<uint32_t> d_cnt;        // [2][cw * ch]
 };
-
-bool finite_d(double v) { return v == v && v <= 1.7976931348623157e308 && v >= -1.7976931348623157e308; }
 
 int check_ctx_occ(pcm_ctx* c, OccMap** out, bool need_params) {
   *out = nullptr;
@@ -252,13 +209,13 @@ int ensure_rect(pcm_ctx* c, OccMap* M, long long lx, long long hx, long long ly,
   }
   const OccRect N{gx0, gy0, gx1 - gx0 + 1, gy1 - gy0 + 1};
   const size_t n = (size_t)(N.w * N.h);
-  if (empty && M->cells && n <= M->cells_cap) {   // after a reset: the allocation is reused
-    OCCK(c, hipMemsetAsync(M->cells, 0, sizeof(uint2) * n, c->stream));
+  if (empty && M->cells && n <= M->cells.cap) {   // after a reset: the allocation is reused
+    PCM_HIPCK(c, hipMemsetAsync(M->cells, 0, sizeof(uint2) * n, c->stream));
     M->R = N;
     return PCM_OK;
   }
   uint2* nc = nullptr;
-  OCCK(c, hipMalloc(reinterpret_cast<void**>(&nc), sizeof(uint2) * n));
+  PCM_HIPCK(c, hipMalloc(reinterpret_cast<void**>(&nc), sizeof(uint2) * n));
   hipError_t e = hipMemsetAsync(nc, 0, sizeof(uint2) * n, c->stream);
   if (e == hipSuccess && !empty) {
     const unsigned grid = (unsigned)std::min<long long>(4096, (R.w * R.h + 255) / 256);
@@ -267,32 +224,22 @@ int ensure_rect(pcm_ctx* c, OccMap* M, long long lx, long long hx, long long ly,
   }
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) { hipFree(nc); c->err = std::string("occupancy map growth: ") + hipGetErrorString(e); return PCM_ERR_HIP; }
-  if (M->cells) hipFree(M->cells);
-  M->cells = nc;
-  M->cells_cap = n;
+  M->cells.adopt(nc, n);   // synchronised above
   M->R = N;
   return PCM_OK;
 }
 
+// the scratch of a set of launches and the staging rows grow by half
 template <typename T>
-int ensure_buf(pcm_ctx* c, T** p, size_t* cap, size_t n) {
-  if (*p && n <= *cap) return PCM_OK;
-  OCCK(c, hipStreamSynchronize(c->stream));
-  if (*p) hipFree(*p);
-  *p = nullptr; *cap = 0;
-  const size_t nc = n + n / 2 + 64;
-  OCCK(c, hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * nc));
-  *cap = nc;
-  return PCM_OK;
-}
+int reserve_half(pcm_ctx* c, DevBuf<T>* b, size_t n) { return b->reserve(c, n, n + n / 2 + 64); }
 
 int ensure_small(pcm_ctx* c, OccMap* M) {
   if (!M->d_small) {
-    OCCK(c, hipMalloc(reinterpret_cast<void**>(&M->d_small), sizeof(uint32_t) * kSmallWords));
-    OCCK(c, hipMemsetAsync(M->d_small, 0, sizeof(uint32_t) * kSmallWords, c->stream));
+    int rc = M->d_small.reserve(c, kSmallWords, kSmallWords);
+    if (rc != PCM_OK) return rc;
+    PCM_HIPCK(c, hipMemsetAsync(M->d_small, 0, sizeof(uint32_t) * kSmallWords, c->stream));
   }
-  if (!M->h_small) OCCK(c, hipHostMalloc(reinterpret_cast<void**>(&M->h_small), sizeof(uint32_t) * kSmallWords));
-  return PCM_OK;
+  return M->h_small.reserve(c, kSmallWords, kSmallWords);
 }
 
 struct HostScan {
@@ -314,7 +261,7 @@ int insert_scans(pcm_ctx* c, OccMap* M, const std::vector<HostScan>& scans) {
     if (first) { lx = a; hx = b; ly = d; hy = e; first = false; }
     else { lx = std::min(lx, a); hx = std::max(hx, b); ly = std::min(ly, d); hy = std::max(hy, e); }
   }
-  OCCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   int rc;
   if ((rc = ensure_rect(c, M, lx, hx, ly, hy)) != PCM_OK) return rc;
   if ((rc = ensure_small(c, M)) != PCM_OK) return rc;
@@ -349,29 +296,29 @@ int insert_scans(pcm_ctx* c, OccMap* M, const std::vector<HostScan>& scans) {
     if (total > 0xfffffff0ull) { c->err = "a scan has too many points"; return PCM_ERR_INVALID_ARGUMENT; }
     const uint32_t S = (uint32_t)(s1 - s0), nseg = (uint32_t)segs.size();
     const uint32_t nt = S * beams;
-    if ((rc = ensure_buf(c, &M->table, &M->table_cap, (size_t)nt)) != PCM_OK) return rc;
-    if ((rc = ensure_buf(c, &M->d_pose, &M->pose_cap, (size_t)S)) != PCM_OK) return rc;
-    if ((rc = ensure_buf(c, &M->d_seg, &M->seg_cap, (size_t)nseg + 1)) != PCM_OK) return rc;
-    if ((rc = ensure_buf(c, &M->d_off, &M->off_cap, (size_t)nseg + 1)) != PCM_OK) return rc;
-    OCCK(c, hipMemcpyAsync(M->d_pose, poses.data(), sizeof(OccPose) * S, hipMemcpyHostToDevice, st));
+    if ((rc = reserve_half(c, &M->table, (size_t)nt)) != PCM_OK) return rc;
+    if ((rc = reserve_half(c, &M->d_pose, (size_t)S)) != PCM_OK) return rc;
+    if ((rc = reserve_half(c, &M->d_seg, (size_t)nseg + 1)) != PCM_OK) return rc;
+    if ((rc = reserve_half(c, &M->d_off, (size_t)nseg + 1)) != PCM_OK) return rc;
+    PCM_HIPCK(c, hipMemcpyAsync(M->d_pose, poses.data(), sizeof(OccPose) * S, hipMemcpyHostToDevice, st));
     if (nseg) {
-      OCCK(c, hipMemcpyAsync(M->d_seg, segs.data(), sizeof(OccSeg) * nseg, hipMemcpyHostToDevice, st));
-      OCCK(c, hipMemcpyAsync(M->d_off, off.data(), sizeof(uint32_t) * nseg, hipMemcpyHostToDevice, st));
+      PCM_HIPCK(c, hipMemcpyAsync(M->d_seg, segs.data(), sizeof(OccSeg) * nseg, hipMemcpyHostToDevice, st));
+      PCM_HIPCK(c, hipMemcpyAsync(M->d_off, off.data(), sizeof(uint32_t) * nseg, hipMemcpyHostToDevice, st));
     }
     k_occ_fill<<<(nt + 255) / 256, 256, 0, st>>>(M->table, nt, __builtin_bit_cast(uint32_t, occ_range_init(P.max_range)));
     if (total > 0) {
       const unsigned grid = (unsigned)std::min<uint64_t>(8192, (total + 255) / 256);
       k_occ_scan<<<grid, 256, 0, st>>>(M->d_seg, M->d_off, nseg, (uint32_t)total, P, beams, M->table);
     }
-    k_occ_trace<<<(nt + 255) / 256, 256, 0, st>>>(M->table, M->d_pose, S, beams, P, reinterpret_cast<uint32_t*>(M->cells), M->R, M->d_small);
-    OCCK(c, hipGetLastError());
-    OCCK(c, hipMemcpyAsync(M->h_small, M->d_small, sizeof(uint32_t) * kSmallWords, hipMemcpyDeviceToHost, st));
-    OCCK(c, hipStreamSynchronize(st));   // the vectors above and the caller's buffers are free again
+    k_occ_trace<<<(nt + 255) / 256, 256, 0, st>>>(M->table, M->d_pose, S, beams, P, reinterpret_cast<uint32_t*>(M->cells.p), M->R, M->d_small);
+    PCM_HIPCK(c, hipGetLastError());
+    PCM_HIPCK(c, hipMemcpyAsync(M->h_small, M->d_small, sizeof(uint32_t) * kSmallWords, hipMemcpyDeviceToHost, st));
+    PCM_HIPCK(c, hipStreamSynchronize(st));   // the vectors above and the caller's buffers are free again
     M->last_scans = S;
     M->n_scans += S;
     if (M->h_small[kOverflow] != 0) {
       M->overflow += M->h_small[kOverflow];
-      OCCK(c, hipMemsetAsync(M->d_small, 0, sizeof(uint32_t), st));
+      PCM_HIPCK(c, hipMemsetAsync(M->d_small, 0, sizeof(uint32_t), st));
       c->err = "occupancy map: cells outside the allocated rectangle were dropped (internal error: the host bound did not cover a ray)";
       return PCM_ERR_INTERNAL;
     }
@@ -384,19 +331,19 @@ int ensure_render(pcm_ctx* c, OccMap* M) {
   if (M->rendered) return PCM_OK;
   M->cw = M->ch = 0; M->n_known = 0; M->cx0 = M->cy0 = 0;
   if (!M->cells || M->R.w == 0) { M->rendered = true; return PCM_OK; }
-  OCCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   int rc;
   if ((rc = ensure_small(c, M)) != PCM_OK) return rc;
   hipStream_t st = c->stream;
   const uint32_t init_words[kSmallWords] = {0u, 0xffffffffu, 0u, 0xffffffffu, 0u, 0u, 0u, 0u};
-  OCCK(c, hipMemcpyAsync(M->d_small, init_words, sizeof(init_words), hipMemcpyHostToDevice, st));
+  PCM_HIPCK(c, hipMemcpyAsync(M->d_small, init_words, sizeof(init_words), hipMemcpyHostToDevice, st));
   const long long init_slot = M->have_init ? occ_slot(M->init_x, M->init_y, M->R) : -1;
   const long long n = M->R.w * M->R.h;
   const unsigned grid = (unsigned)std::min<long long>(8192, (n + 255) / 256);
   k_occ_bounds<<<grid, 256, 0, st>>>(M->cells, M->R, init_slot, M->d_small);
-  OCCK(c, hipGetLastError());
-  OCCK(c, hipMemcpyAsync(M->h_small, M->d_small, sizeof(uint32_t) * kSmallWords, hipMemcpyDeviceToHost, st));
-  OCCK(c, hipStreamSynchronize(st));
+  PCM_HIPCK(c, hipGetLastError());
+  PCM_HIPCK(c, hipMemcpyAsync(M->h_small, M->d_small, sizeof(uint32_t) * kSmallWords, hipMemcpyDeviceToHost, st));
+  PCM_HIPCK(c, hipStreamSynchronize(st));
   const uint32_t* h = M->h_small;
   if (h[kKnown] == 0) { M->rendered = true; return PCM_OK; }
   if (h[kMaxX] >= (uint64_t)M->R.w || h[kMaxY] >= (uint64_t)M->R.h || h[kMinX] > h[kMaxX] || h[kMinY] > h[kMaxY]) {
@@ -404,19 +351,12 @@ int ensure_render(pcm_ctx* c, OccMap* M) {
   }
   const uint32_t w = h[kMaxX] - h[kMinX] + 1, hh = h[kMaxY] - h[kMinY] + 1;
   const size_t m = (size_t)w * hh;
-  if (m > M->out_cap || !M->d_grid) {
-    for (void* p : {(void*)M->d_grid, (void*)M->d_pgm, (void*)M->d_cnt}) if (p) hipFree(p);
-    M->d_grid = nullptr; M->d_pgm = nullptr; M->d_cnt = nullptr; M->out_cap = 0;
-    const size_t cap = m + m / 4 + 256;
-    OCCK(c, hipMalloc(reinterpret_cast<void**>(&M->d_grid), cap));
-    OCCK(c, hipMalloc(reinterpret_cast<void**>(&M->d_pgm), cap));
-    OCCK(c, hipMalloc(reinterpret_cast<void**>(&M->d_cnt), sizeof(uint32_t) * 2 * cap));
-    M->out_cap = cap;
-  }
+  const size_t cap = m + m / 4 + 256;
+  if ((rc = M->d_grid.reserve(c, m, cap)) != PCM_OK || (rc = M->d_pgm.reserve(c, m, cap)) != PCM_OK || (rc = M->d_cnt.reserve(c, 2 * m, 2 * cap)) != PCM_OK) return rc;
   const unsigned rgrid = (unsigned)std::min<size_t>(8192, (m + 255) / 256);
   k_occ_render<<<rgrid, 256, 0, st>>>(M->cells, M->R, init_slot, h[kMinX], h[kMinY], w, hh, M->P.log_occ, M->P.log_free, M->d_grid, M->d_pgm, M->d_cnt, M->d_cnt + m);
-  OCCK(c, hipGetLastError());
-  OCCK(c, hipStreamSynchronize(st));
+  PCM_HIPCK(c, hipGetLastError());
+  PCM_HIPCK(c, hipStreamSynchronize(st));
   M->cw = w; M->ch = hh; M->n_known = h[kKnown];
   M->cx0 = M->R.x0 + h[kMinX]; M->cy0 = M->R.y0 + h[kMinY];
   M->rendered = true;
@@ -427,8 +367,8 @@ int read_back(pcm_ctx* c, OccMap* M, void* dst, const void* src, size_t bytes, s
   if (elems == 0) return PCM_OK;
   if (!dst) { c->err = "null output buffer"; return PCM_ERR_INVALID_ARGUMENT; }
   if (capacity < elems) { c->err = "capacity too small (pcm_occ_info gives width x height)"; return PCM_ERR_INVALID_ARGUMENT; }
-  OCCK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-  OCCK(c, hipStreamSynchronize(c->stream));
+  PCM_HIPCK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   return PCM_OK;
 }
 
@@ -438,7 +378,6 @@ namespace pcm {
 void occ_release(pcm_ctx* c) {
   OccMap* M = static_cast<OccMap*>(c->occ);
   if (!M) return;
-  M->release();
   delete M;
   c->occ = nullptr;
 }
@@ -469,13 +408,13 @@ int pcm_occ_reset(pcm_ctx* c, const pcm_occ_params* params) {
   pcm_occ_params p;
   if (params) p = *params; else pcm_occ_default_params(&p);
   if ((rc = check_oparams(c, p)) != PCM_OK) return rc;
-  OCCK(c, hipSetDevice(c->device));
-  OCCK(c, hipStreamSynchronize(c->stream));
+  PCM_HIPCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   M->P = OccParams{p.min_z, p.max_z, p.angle_increment, p.min_range, p.max_range, p.log_occ, p.log_free, p.resolution, p.max_radius, p.fill_with_white ? 1 : 0, p.use_nan ? 1 : 0};
   M->beams = occ_beam_size(p.angle_increment);
   M->R = OccRect{0, 0, 0, 0};   // the allocation stays for the next rectangle
-  if (M->d_small) OCCK(c, hipMemsetAsync(M->d_small, 0, sizeof(uint32_t) * kSmallWords, c->stream));
-  OCCK(c, hipStreamSynchronize(c->stream));
+  if (M->d_small) PCM_HIPCK(c, hipMemsetAsync(M->d_small, 0, sizeof(uint32_t) * kSmallWords, c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   M->have_init = false;
   M->n_scans = 0; M->overflow = 0; M->last_scans = 0;
   M->rendered = false;
@@ -489,8 +428,7 @@ int pcm_occ_insert_scans(pcm_ctx* c, const void* points, const size_t* n_points,
   if (num_scans < 0) { c->err = "num_scans must be >= 0"; return PCM_ERR_INVALID_ARGUMENT; }
   if (num_scans == 0) return PCM_OK;
   if (!n_points || !poses6) { c->err = "null n_points / poses"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (stride < 3 * sizeof(float) || (stride % sizeof(float)) != 0) { c->err = "stride must be a multiple of 4 and >= 12 bytes"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  if ((rc = check_point_records(c, points, 0, stride, memory, 0x3fffffffull)) != PCM_OK) return rc;   // stride and memory kind; sizes and the buffer below
   size_t total = 0;
   for (int s = 0; s < num_scans; s++) {
     if (n_points[s] > 0x3fffffffull) { c->err = "cloud too large"; return PCM_ERR_INVALID_ARGUMENT; }
@@ -498,19 +436,14 @@ int pcm_occ_insert_scans(pcm_ctx* c, const void* points, const size_t* n_points,
   }
   if (total > 0xfffffff0ull) { c->err = "batch too large (split it)"; return PCM_ERR_INVALID_ARGUMENT; }
   if (total && !points) { c->err = "null point buffer"; return PCM_ERR_INVALID_ARGUMENT; }
-  OCCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   const float4* base = nullptr;
   if (total) {
     if (memory == PCM_MEM_DEVICE && stride == sizeof(float4) && (reinterpret_cast<uintptr_t>(points) % sizeof(float4)) == 0) {
       base = static_cast<const float4*>(points);   // in place
     } else {
-      if ((rc = ensure_buf(c, &M->stage, &M->stage_cap, total)) != PCM_OK) return rc;
-      if (memory == PCM_MEM_DEVICE) {
-        k_occ_load<<<(unsigned)((total + 255) / 256), 256, 0, c->stream>>>(static_cast<const char*>(points), stride, (uint32_t)total, M->stage);
-        OCCK(c, hipGetLastError());
-      } else {
-        OCCK(c, hipMemcpy2DAsync(M->stage, sizeof(float4), points, stride, 3 * sizeof(float), total, hipMemcpyHostToDevice, c->stream));   // w is never read
-      }
+      if ((rc = reserve_half(c, &M->stage, total)) != PCM_OK) return rc;
+      if ((rc = load_xyzw_rows(c, points, total, stride, memory, false, M->stage)) != PCM_OK) return rc;   // w is never read
       base = M->stage;
     }
   }
@@ -551,9 +484,9 @@ int pcm_occ_get_scan(pcm_ctx* c, int s, float* ranges, double* angles) {
   if (s < 0 || (uint32_t)s >= M->last_scans) { c->err = "pcm_occ_get_scan: scan outside the last set of launches"; return PCM_ERR_INVALID_ARGUMENT; }
   const uint32_t B = M->beams;
   if (ranges) {
-    OCCK(c, hipSetDevice(c->device));
-    OCCK(c, hipMemcpyAsync(ranges, M->table + (size_t)s * B, sizeof(float) * B, hipMemcpyDeviceToHost, c->stream));
-    OCCK(c, hipStreamSynchronize(c->stream));
+    PCM_HIPCK(c, hipSetDevice(c->device));
+    PCM_HIPCK(c, hipMemcpyAsync(ranges, M->table + (size_t)s * B, sizeof(float) * B, hipMemcpyDeviceToHost, c->stream));
+    PCM_HIPCK(c, hipStreamSynchronize(c->stream));
     for (uint32_t i = 0; i < B; i++) ranges[i] = occ_beam_range(ranges[i], M->P);
   }
   if (angles) for (uint32_t i = 0; i < B; i++) angles[i] = occ_beam_angle(i, M->P.angle_increment);

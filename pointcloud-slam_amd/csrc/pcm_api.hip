@@ -7,7 +7,7 @@
 // The reference crosses host<->device >= 4 times per Gauss-Newton iteration
 // (SURVEY.md §2.3); here the loop state lives on the device and the host only
 // polls a per-round "pairs still active" counter one round behind the GPU.
-#include "pcm_host.h"
+#include "host_util.h"
 #include "pclndt_host.h"
 
 #include <algorithm>
@@ -22,15 +22,6 @@
 using namespace pcm;
 
 namespace {
-
-#define HIPCK(ctx, x)                                                                \
-  do {                                                                               \
-    hipError_t e_ = (x);                                                             \
-    if (e_ != hipSuccess) {                                                          \
-      (ctx)->err = std::string(#x) + ": " + hipGetErrorString(e_);                   \
-      return PCM_ERR_HIP;                                                            \
-    }                                                                                \
-  } while (0)
 
 // grow-only device workspace shared by the batch launches of one device
 struct Workspace {
@@ -85,22 +76,22 @@ int ensure_ws(pcm_ctx* c, Workspace** out, int npairs, size_t partial_doubles, i
   w.device = c->device;
   if (npairs > w.cap_pairs) {
     if (w.d_descs) { hipFree(w.d_descs); hipFree(w.d_states); hipFree(w.d_guesses); hipFree(w.d_results); hipFree(w.d_sums); hipFree(w.d_jobs); }
-    // a failed hipMalloc below returns at once (HIPCK): nothing freed here may stay reachable, or a retry / pcm_destroy frees it twice
+    // a failed hipMalloc below returns at once (PCM_HIPCK): nothing freed here may stay reachable, or a retry / pcm_destroy frees it twice
     w.d_descs = nullptr; w.d_states = nullptr; w.d_guesses = nullptr; w.d_results = nullptr; w.d_sums = nullptr; w.d_jobs = nullptr;
     w.cap_pairs = 0;
     const int cap = std::max(npairs, 64);
-    HIPCK(c, hipMalloc(&w.d_descs, sizeof(PairDesc) * cap));
-    HIPCK(c, hipMalloc(&w.d_states, sizeof(PairState) * cap));
-    HIPCK(c, hipMalloc(&w.d_guesses, sizeof(float) * 16 * cap));
-    HIPCK(c, hipMalloc(&w.d_results, sizeof(pcm_result) * cap));
-    HIPCK(c, hipMalloc(&w.d_sums, sizeof(double) * kPartialStride * cap));
-    HIPCK(c, hipMalloc(&w.d_jobs, sizeof(SortJob) * cap));
+    PCM_HIPCK(c, hipMalloc(&w.d_descs, sizeof(PairDesc) * cap));
+    PCM_HIPCK(c, hipMalloc(&w.d_states, sizeof(PairState) * cap));
+    PCM_HIPCK(c, hipMalloc(&w.d_guesses, sizeof(float) * 16 * cap));
+    PCM_HIPCK(c, hipMalloc(&w.d_results, sizeof(pcm_result) * cap));
+    PCM_HIPCK(c, hipMalloc(&w.d_sums, sizeof(double) * kPartialStride * cap));
+    PCM_HIPCK(c, hipMalloc(&w.d_jobs, sizeof(SortJob) * cap));
     w.cap_pairs = cap;
   }
   if (partial_doubles > w.cap_partials) {
     if (w.d_partials) hipFree(w.d_partials);
     w.d_partials = nullptr; w.cap_partials = 0;
-    HIPCK(c, hipMalloc(&w.d_partials, sizeof(double) * partial_doubles));
+    PCM_HIPCK(c, hipMalloc(&w.d_partials, sizeof(double) * partial_doubles));
     w.cap_partials = partial_doubles;
   }
   if ((size_t)rounds * (size_t)std::max(npairs, 64) > w.cap_flags) {
@@ -109,15 +100,15 @@ int ensure_ws(pcm_ctx* c, Workspace** out, int npairs, size_t partial_doubles, i
     const size_t bytes = (size_t)rounds * (size_t)std::max(npairs, 64);
     // per-round status bytes of every pair live in mapped pinned host memory: k_finish_round
     // stores them directly (posted writes); the host polls them, no event / copy per round
-    HIPCK(c, hipHostMalloc(reinterpret_cast<void**>(&w.h_flags), bytes, hipHostMallocMapped));
-    HIPCK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&w.d_flags), w.h_flags, 0));
+    PCM_HIPCK(c, hipHostMalloc(reinterpret_cast<void**>(&w.h_flags), bytes, hipHostMallocMapped));
+    PCM_HIPCK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&w.d_flags), w.h_flags, 0));
     w.cap_flags = bytes;
   }
-  if (!w.d_stats) HIPCK(c, hipMalloc(&w.d_stats, sizeof(unsigned long long) * 16));
-  if (!w.d_queue) HIPCK(c, hipMalloc(&w.d_queue, sizeof(unsigned int)));
+  if (!w.d_stats) PCM_HIPCK(c, hipMalloc(&w.d_stats, sizeof(unsigned long long) * 16));
+  if (!w.d_queue) PCM_HIPCK(c, hipMalloc(&w.d_queue, sizeof(unsigned int)));
   while ((int)w.ev_round.size() < 2) {
     hipEvent_t e;
-    HIPCK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    PCM_HIPCK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     w.ev_round.push_back(e);
   }
   *out = &w;
@@ -205,10 +196,9 @@ int validate_config(pcm_ctx* c, const pcm_config& g) {
 }
 
 int set_cloud(pcm_ctx* c, Cloud* cl, const void* points, size_t n, size_t stride, int memory, uint64_t tag, bool allow_borrow) {
-  if (!points && n) { c->err = "null point buffer"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (stride < 3 * sizeof(float) || (stride % sizeof(float)) != 0) { c->err = "stride must be a multiple of 4 and >= 12 bytes"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (n > 0x7fffffffull) { c->err = "cloud too large"; return PCM_ERR_INVALID_ARGUMENT; }
-  HIPCK(c, hipSetDevice(c->device));
+  int rc = check_point_records(c, points, n, stride, memory, 0x7fffffffull, false);
+  if (rc != PCM_OK) return rc;
+  PCM_HIPCK(c, hipSetDevice(c->device));
   if (allow_borrow && memory == PCM_MEM_DEVICE && stride == sizeof(float4) && (reinterpret_cast<uintptr_t>(points) & 15u) == 0) {
     // a device-resident PointXYZ-layout scan is used in place (the kernels only read x,y,z):
     // like the reference's shared_ptr input, the caller keeps it alive and unchanged until align() returns
@@ -223,14 +213,14 @@ int set_cloud(pcm_ctx* c, Cloud* cl, const void* points, size_t n, size_t stride
   if (n > cl->cap) {
     if (cl->d_pts) hipFree(cl->d_pts);
     cl->d_pts = nullptr; cl->cap = 0;
-    HIPCK(c, hipMalloc(&cl->d_pts, sizeof(float4) * n));
+    PCM_HIPCK(c, hipMalloc(&cl->d_pts, sizeof(float4) * n));
     cl->cap = n;
   }
   cl->n = n;
   cl->tag = tag;
-  int rc = load_points_to_device(c->stream, points, n, stride, memory, 0u, cl->d_pts, &c->err);
+  rc = load_points_to_device(c->stream, points, n, stride, memory, 0u, cl->d_pts, &c->err);
   if (rc != PCM_OK) return rc;
-  HIPCK(c, hipStreamSynchronize(c->stream));  // the caller may free/reuse its buffer on return
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));  // the caller may free/reuse its buffer on return
   return PCM_OK;
 }
 
@@ -263,7 +253,7 @@ TargetView ndt_lists_view(const pcm_ctx* c) {
 // lazy (re)build of everything the residual kernel needs
 int prepare(pcm_ctx* c) {
   if (c->src.n == 0 || c->tgt.n == 0) { c->err = "align before setInputSource/setInputTarget"; return PCM_ERR_NO_INPUT; }
-  HIPCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   const int mode = coord_mode_for(c->cfg.model);
   const bool gauss = is_ndt(c->cfg.model);
   const bool gicp = is_gicp(c->cfg.model);
@@ -316,8 +306,8 @@ int prepare(pcm_ctx* c) {
         if (c->pleaf) hipFree(c->pleaf);
         if (c->pleaf_f) hipFree(c->pleaf_f);
         c->pleaf = nullptr; c->pleaf_f = nullptr; c->pleaf_cap = 0;
-        HIPCK(c, hipMalloc(&c->pleaf, sizeof(PclLeaf) * (size_t)c->map.num_voxels));
-        HIPCK(c, hipMalloc(&c->pleaf_f, sizeof(PclLeafF) * (size_t)c->map.num_voxels));
+        PCM_HIPCK(c, hipMalloc(&c->pleaf, sizeof(PclLeaf) * (size_t)c->map.num_voxels));
+        PCM_HIPCK(c, hipMalloc(&c->pleaf_f, sizeof(PclLeafF) * (size_t)c->map.num_voxels));
         c->pleaf_cap = c->map.num_voxels;
       }
       int rc = build_pclndt_leaves(c->stream, c->map, c->pleaf, c->pleaf_f, &c->err);
@@ -343,12 +333,12 @@ int prepare(pcm_ctx* c) {
     if (c->ndt_partials_cap < need) {
       if (c->ndt_partials) hipFree(c->ndt_partials);
       c->ndt_partials = nullptr; c->ndt_partials_cap = 0;
-      HIPCK(c, hipMalloc(&c->ndt_partials, sizeof(double) * need));
-      HIPCK(c, hipMemsetAsync(c->ndt_partials, 0, sizeof(double) * need, c->stream));
+      PCM_HIPCK(c, hipMalloc(&c->ndt_partials, sizeof(double) * need));
+      PCM_HIPCK(c, hipMemsetAsync(c->ndt_partials, 0, sizeof(double) * need, c->stream));
       c->ndt_partials_cap = need;
     }
-    if (!c->ndt_out) HIPCK(c, hipMalloc(&c->ndt_out, sizeof(double) * 48));
-    if (!c->ndt_out_host) HIPCK(c, hipHostMalloc(&c->ndt_out_host, sizeof(double) * 48));
+    if (!c->ndt_out) PCM_HIPCK(c, hipMalloc(&c->ndt_out, sizeof(double) * 48));
+    if (!c->ndt_out_host) PCM_HIPCK(c, hipHostMalloc(&c->ndt_out_host, sizeof(double) * 48));
     return PCM_OK;
   }
   if (gicp) {
@@ -376,7 +366,7 @@ int prepare(pcm_ctx* c) {
       if (c->tgt_cov_cap < c->map.num_points) {
         if (c->tgt_cov) hipFree(c->tgt_cov);
         c->tgt_cov = nullptr; c->tgt_cov_cap = 0;
-        HIPCK(c, hipMalloc(&c->tgt_cov, sizeof(double) * 6 * (size_t)c->map.num_points));
+        PCM_HIPCK(c, hipMalloc(&c->tgt_cov, sizeof(double) * 6 * (size_t)c->map.num_points));
         c->tgt_cov_cap = c->map.num_points;
       }
       const int reg_code = c->cfg.regularization + (c->cfg.model == PCM_MODEL_VGICP_CUDA ? 16 : 0);   // + 16: float CUDA-core semantics
@@ -396,7 +386,7 @@ int prepare(pcm_ctx* c) {
         if (c->cvox_cap < c->map.num_voxels) {
           if (c->cvox) hipFree(c->cvox);
           c->cvox = nullptr; c->cvox_cap = 0;
-          HIPCK(c, hipMalloc(&c->cvox, sizeof(VgcVoxel) * (size_t)c->map.num_voxels));
+          PCM_HIPCK(c, hipMalloc(&c->cvox, sizeof(VgcVoxel) * (size_t)c->map.num_voxels));
           c->cvox_cap = c->map.num_voxels;
         }
         rc = build_vgc_voxels(c->stream, c->map, c->tgt_cov, c->cvox, &c->err);
@@ -406,7 +396,7 @@ int prepare(pcm_ctx* c) {
         if (c->vvox_cap < c->map.num_voxels) {
           if (c->vvox) hipFree(c->vvox);
           c->vvox = nullptr; c->vvox_cap = 0;
-          HIPCK(c, hipMalloc(&c->vvox, sizeof(VgVoxel) * (size_t)c->map.num_voxels));
+          PCM_HIPCK(c, hipMalloc(&c->vvox, sizeof(VgVoxel) * (size_t)c->map.num_voxels));
           c->vvox_cap = c->map.num_voxels;
         }
         rc = build_vgicp_voxels(c->stream, c->map, c->tgt_cov, c->cfg.voxel_mode, c->vvox, &c->err);
@@ -418,7 +408,7 @@ int prepare(pcm_ctx* c) {
       if (c->src_cov_cap < c->srcmap.num_points) {
         if (c->src_cov) hipFree(c->src_cov);
         c->src_cov = nullptr; c->src_cov_cap = 0;
-        HIPCK(c, hipMalloc(&c->src_cov, sizeof(double) * 6 * (size_t)c->srcmap.num_points));
+        PCM_HIPCK(c, hipMalloc(&c->src_cov, sizeof(double) * 6 * (size_t)c->srcmap.num_points));
         c->src_cov_cap = c->srcmap.num_points;
       }
       const bool given = c->cfg.model != PCM_MODEL_VGICP_CUDA && c->user_cov[0].size() == (size_t)c->srcmap.num_points * 6 && c->srcmap.num_points == c->src.n;   // :104-106
@@ -440,7 +430,7 @@ int prepare(pcm_ctx* c) {
     if (c->maha_cap < ncorr) {
       if (c->maha) hipFree(c->maha);
       c->maha = nullptr; c->maha_cap = 0;
-      HIPCK(c, hipMalloc(&c->maha, sizeof(double) * 6 * ncorr));
+      PCM_HIPCK(c, hipMalloc(&c->maha, sizeof(double) * 6 * ncorr));
       c->maha_cap = ncorr;
     }
   }
@@ -455,31 +445,31 @@ int prepare(pcm_ctx* c) {
     if (c->corr_cap < need) {
       if (c->corr) hipFree(c->corr);
       c->corr = nullptr; c->corr_cap = 0;
-      HIPCK(c, hipMalloc(&c->corr, sizeof(int32_t) * need));
+      PCM_HIPCK(c, hipMalloc(&c->corr, sizeof(int32_t) * need));
       c->corr_cap = need;
     }
   }
   if (c->cfg.sort_source && c->src_order_cap < c->src.n) {
     if (c->src_order) hipFree(c->src_order);
     c->src_order = nullptr; c->src_order_cap = 0; c->src_sorted = false;
-    HIPCK(c, hipMalloc(&c->src_order, sizeof(float4) * c->src.n));
+    PCM_HIPCK(c, hipMalloc(&c->src_order, sizeof(float4) * c->src.n));
     c->src_order_cap = c->src.n;
   }
   if (!c->counter) {
-    HIPCK(c, hipMalloc(&c->counter, sizeof(unsigned int)));
-    HIPCK(c, hipMemsetAsync(c->counter, 0, sizeof(unsigned int), c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
+    PCM_HIPCK(c, hipMalloc(&c->counter, sizeof(unsigned int)));
+    PCM_HIPCK(c, hipMemsetAsync(c->counter, 0, sizeof(unsigned int), c->stream));
+    PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   }
   if (c->nn_cap < c->src.n) {
     if (c->nn) hipFree(c->nn);
     c->nn = nullptr; c->nn_cap = 0;
-    HIPCK(c, hipMalloc(&c->nn, sizeof(uint32_t) * 5 * c->src.n));
+    PCM_HIPCK(c, hipMalloc(&c->nn, sizeof(uint32_t) * 5 * c->src.n));
     c->nn_cap = c->src.n;
   }
   if (c->planes_cap < c->src.n) {
     if (c->planes) hipFree(c->planes);
     c->planes = nullptr; c->planes_cap = 0;
-    HIPCK(c, hipMalloc(&c->planes, sizeof(float4) * c->src.n));
+    PCM_HIPCK(c, hipMalloc(&c->planes, sizeof(float4) * c->src.n));
     c->planes_cap = c->src.n;
   }
   return PCM_OK;
@@ -625,7 +615,7 @@ int align_batch_impl(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_resu
   // GICP / VGICP: the covariance kernels of the contexts were queued on their own streams without a host
   // sync (they overlap on the device); the batch kernels below run on c0's stream and read their output
   if (is_gicp(c0->cfg.model)) {
-    for (int i = 0; i < n; i++) HIPCK(c0, hipStreamSynchronize(ctxs[i]->stream));
+    for (int i = 0; i < n; i++) PCM_HIPCK(c0, hipStreamSynchronize(ctxs[i]->stream));
   }
   const pcm_config& g = c0->cfg;
   const bool ndt = is_ndt(g.model) || g.model == PCM_MODEL_VGICP_CUDA;   // residual kernel of the Gaussian-voxel family
@@ -656,7 +646,7 @@ int align_batch_impl(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_resu
   if (rc != PCM_OK) return rc;
   hipStream_t st = c0->stream;
 
-  HIPCK(c0, hipMemcpyAsync(w->d_guesses, guesses, sizeof(float) * 16 * n, hipMemcpyHostToDevice, st));
+  PCM_HIPCK(c0, hipMemcpyAsync(w->d_guesses, guesses, sizeof(float) * 16 * n, hipMemcpyHostToDevice, st));
   {  // new scans are re-ordered along the world grid (at their initial guess) in one batched pass
     std::vector<SortJob> jobs;
     uint32_t total = 0, jmax = 0;
@@ -669,7 +659,7 @@ int align_batch_impl(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_resu
       jmax = std::max(jmax, j.n);
     }
     if (!jobs.empty()) {
-      HIPCK(c0, hipMemcpyAsync(w->d_jobs, jobs.data(), sizeof(SortJob) * jobs.size(), hipMemcpyHostToDevice, st));
+      PCM_HIPCK(c0, hipMemcpyAsync(w->d_jobs, jobs.data(), sizeof(SortJob) * jobs.size(), hipMemcpyHostToDevice, st));
       rc = sort_sources_batched(st, w->d_jobs, (int)jobs.size(), jmax, total, w->d_guesses, g.voxel_resolution, &w->sort, &c0->err);
       if (rc != PCM_OK) return rc;
       for (const SortJob& j : jobs) ctxs[j.guess_index]->src_sorted = true;
@@ -677,7 +667,7 @@ int align_batch_impl(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_resu
   }
   std::vector<PairDesc> descs(n);
   for (int i = 0; i < n; i++) fill_desc(ctxs[i], &descs[i], w->d_partials + per_pair_partials * i);
-  HIPCK(c0, hipMemcpyAsync(w->d_descs, descs.data(), sizeof(PairDesc) * n, hipMemcpyHostToDevice, st));
+  PCM_HIPCK(c0, hipMemcpyAsync(w->d_descs, descs.data(), sizeof(PairDesc) * n, hipMemcpyHostToDevice, st));
   std::memset(w->h_flags, 0, (size_t)max_rounds * n);
   launch_init_states(st, w->d_states, w->d_guesses, n, g.max_iterations, host_window ? n : window, w->d_queue);
   const bool stats_on = (c0->profiling & 1) != 0;      // HIP events around the residual launches
@@ -686,7 +676,7 @@ int align_batch_impl(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_resu
   uint64_t timed_launches = 0, timed_slots = 0, launched_slots = 0;
   const bool timing_on = (c0->profiling & 4) != 0;     // diagnostic: in-kernel phase stamps (stats.phase_cycles)
   const bool counters_on = (c0->profiling & 2) != 0 || timing_on;   // kNN candidate / probe counters (slower kernel variant)
-  if (counters_on) HIPCK(c0, hipMemsetAsync(w->d_stats, 0, sizeof(unsigned long long) * 16, st));
+  if (counters_on) PCM_HIPCK(c0, hipMemsetAsync(w->d_stats, 0, sizeof(unsigned long long) * 16, st));
   const bool is_lm = g.optimizer == PCM_OPT_LEVENBERG_MARQUARDT;
   const bool write_sel = is_lm;  // trial passes re-use the planes of the selected set
   const bool counted_search = (g.flags & PCM_FLAG_COUNTED_SEARCH) != 0;   // k_linearize_counted (A/B)
@@ -722,8 +712,8 @@ int align_batch_impl(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_resu
     const bool timed = stats_on && (!stats_sampled || (((unsigned)r + prof_phase) & 3u) == 0u);
     launched_slots += (uint64_t)nl;
     if (timed) {
-      while (w->ev_prof.size() < prof_used + 3) { hipEvent_t e; HIPCK(c0, hipEventCreate(&e)); w->ev_prof.push_back(e); }
-      HIPCK(c0, hipEventRecord(w->ev_prof[prof_used], st));
+      while (w->ev_prof.size() < prof_used + 3) { hipEvent_t e; PCM_HIPCK(c0, hipEventCreate(&e)); w->ev_prof.push_back(e); }
+      PCM_HIPCK(c0, hipEventRecord(w->ev_prof[prof_used], st));
       timed_launches++;
       timed_slots += (uint64_t)nl;
     }
@@ -740,7 +730,7 @@ int align_batch_impl(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_resu
     else if (lists && !counters_on && !timing_on) launch_linearize_lists(st, w->d_descs, w->d_states, kpr, nl, write_sel);
     else if (counted_search) launch_linearize_counted(st, w->d_descs, w->d_states, kpr, nl, write_sel, counters_on ? w->d_stats : nullptr, timing_on);
     else launch_linearize(st, w->d_descs, w->d_states, kpr, nl, write_sel, counters_on ? w->d_stats : nullptr, timing_on);
-    if (timed) HIPCK(c0, hipEventRecord(w->ev_prof[prof_used + 1], st));
+    if (timed) PCM_HIPCK(c0, hipEventRecord(w->ev_prof[prof_used + 1], st));
     if (!fuse) launch_finish_round(st, w->d_descs, w->d_states, kpr, lp, nl, false, !is_lm, w->d_flags + (size_t)r * n, w->d_sums, use_list ? nullptr : w->d_queue, n);
     if (is_lm) {
       if (ndt) launch_ndt(st, w->d_descs, w->d_states, kpr, nl, ndt_kind(g.model), true);
@@ -749,7 +739,7 @@ int align_batch_impl(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_resu
       launch_finish_round(st, w->d_descs, w->d_states, kpr, lp, nl, true, true, w->d_flags + (size_t)r * n, w->d_sums, use_list ? nullptr : w->d_queue, n);
     }
     if (timed) {
-      if (!stats_sampled) HIPCK(c0, hipEventRecord(w->ev_prof[prof_used + 2], st));
+      if (!stats_sampled) PCM_HIPCK(c0, hipEventRecord(w->ev_prof[prof_used + 2], st));
       prof_used += 3;
     }
     rounds_done = r + 1;
@@ -780,18 +770,18 @@ int align_batch_impl(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_resu
     }
     prev_list.swap(this_list);
   }
-  HIPCK(c0, hipGetLastError());
+  PCM_HIPCK(c0, hipGetLastError());
   pcm_result* d_res = device_out ? static_cast<pcm_result*>(device_out) : w->d_results;
   launch_pack_results(st, w->d_states, d_res, n);
   std::vector<pcm_result> tmp;
   pcm_result* h_res = host_out;
   if (!h_res) { tmp.resize(n); h_res = tmp.data(); }
-  HIPCK(c0, hipMemcpyAsync(h_res, d_res, sizeof(pcm_result) * n, hipMemcpyDeviceToHost, st));
-  HIPCK(c0, hipStreamSynchronize(st));
+  PCM_HIPCK(c0, hipMemcpyAsync(h_res, d_res, sizeof(pcm_result) * n, hipMemcpyDeviceToHost, st));
+  PCM_HIPCK(c0, hipStreamSynchronize(st));
 
   if (counters_on) {
     unsigned long long hs[16];
-    HIPCK(c0, hipMemcpy(hs, w->d_stats, sizeof(hs), hipMemcpyDeviceToHost));
+    PCM_HIPCK(c0, hipMemcpy(hs, w->d_stats, sizeof(hs), hipMemcpyDeviceToHost));
     for (int k = 0; k < 8; k++) c0->phase_cycles[k] += hs[8 + k];
     c0->stats.candidates += hs[0];
     c0->stats.slots_probed += hs[1];
@@ -843,8 +833,8 @@ int single_pass(pcm_ctx* c, const double T[16], bool linearize, double sums[kPar
   init_state(s, ident);
   for (int i = 0; i < 16; i++) { s.x0[i] = T[i]; s.xi[i] = T[i]; }
   s.mode = linearize ? MODE_LINEARIZE : MODE_TRIAL;
-  HIPCK(c, hipMemcpyAsync(w->d_descs, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
-  HIPCK(c, hipMemcpyAsync(w->d_states, &s, sizeof(s), hipMemcpyHostToDevice, c->stream));
+  PCM_HIPCK(c, hipMemcpyAsync(w->d_descs, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
+  PCM_HIPCK(c, hipMemcpyAsync(w->d_states, &s, sizeof(s), hipMemcpyHostToDevice, c->stream));
   KernelParams kp1 = kp;
   kp1.do_step = 0;   // the last workgroup exports the sums instead of stepping
   if (ndt) launch_ndt(c->stream, w->d_descs, w->d_states, kp1, 1, ndt_kind(c->cfg.model), !linearize);
@@ -858,18 +848,18 @@ int single_pass(pcm_ctx* c, const double T[16], bool linearize, double sums[kPar
   else if (linearize) launch_linearize(c->stream, w->d_descs, w->d_states, kp1, 1, true, nullptr, false);
   else launch_trial(c->stream, w->d_descs, w->d_states, kp1, 1);
   launch_finish_round(c->stream, w->d_descs, w->d_states, kp1, lsq_params(c->cfg), 1, !linearize, false, w->d_flags, w->d_sums);
-  HIPCK(c, hipGetLastError());
-  HIPCK(c, hipMemcpyAsync(sums, w->d_sums, sizeof(double) * kPartialStride, hipMemcpyDeviceToHost, c->stream));
-  HIPCK(c, hipStreamSynchronize(c->stream));
+  PCM_HIPCK(c, hipGetLastError());
+  PCM_HIPCK(c, hipMemcpyAsync(sums, w->d_sums, sizeof(double) * kPartialStride, hipMemcpyDeviceToHost, c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   return PCM_OK;
 }
 
 // one pclomp NDT pass on the device: launch, read the 48-double row back (pass 0/1: H, g, score; pass 2: H)
 int pclndt_eval(pcm_ctx* c, int pass, const NdtOmpParams& P, ndtomp::Eval* e, double gauss_d3 = 0.0) {
   launch_pclndt_pass(c->stream, c->map, c->pleaf, c->pleaf_f, ndt_lists_view(c), c->src.d_pts, (uint32_t)c->src.n, P, pass, c->ndt_partials, c->ndt_out, gauss_d3);
-  HIPCK(c, hipGetLastError());
-  HIPCK(c, hipMemcpyAsync(c->ndt_out_host, c->ndt_out, sizeof(double) * 48, hipMemcpyDeviceToHost, c->stream));
-  HIPCK(c, hipStreamSynchronize(c->stream));
+  PCM_HIPCK(c, hipGetLastError());
+  PCM_HIPCK(c, hipMemcpyAsync(c->ndt_out_host, c->ndt_out, sizeof(double) * 48, hipMemcpyDeviceToHost, c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   std::memcpy(e->H, c->ndt_out_host, sizeof(double) * 36);
   if (pass == 3) e->score = c->ndt_out_host[0];
   else if (pass != 2) {
@@ -925,7 +915,7 @@ int pclndt_align_batch(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_re
   for (int i = 0; i < n; i++) {
     int rc = prepare(ctxs[i]);
     if (rc != PCM_OK) { if (i) c0->err = ctxs[i]->err; return rc; }
-    if (ctxs[i]->stream != c0->stream) HIPCK(c0, hipStreamSynchronize(ctxs[i]->stream));   // its map / leaves were built on its own stream
+    if (ctxs[i]->stream != c0->stream) PCM_HIPCK(c0, hipStreamSynchronize(ctxs[i]->stream));   // its map / leaves were built on its own stream
   }
   if (!c0->ndt_ws) c0->ndt_ws = new (std::nothrow) NdtBatchWs();
   if (!c0->ndt_ws) { c0->err = "out of host memory"; return PCM_ERR_HIP; }
@@ -937,10 +927,10 @@ int pclndt_align_batch(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_re
     if (w.h_ms) hipHostFree(w.h_ms);
     w.d_objs = nullptr; w.d_ms = nullptr; w.h_objs = nullptr; w.h_ms = nullptr; w.cap = 0;
     const int cap = std::max(n, 16);
-    HIPCK(c0, hipMalloc(&w.d_objs, sizeof(NdtObject) * cap));
-    HIPCK(c0, hipMalloc(&w.d_ms, sizeof(ndtomp::NdtMachine) * cap));
-    HIPCK(c0, hipHostMalloc(reinterpret_cast<void**>(&w.h_objs), sizeof(NdtObject) * cap, hipHostMallocDefault));
-    HIPCK(c0, hipHostMalloc(reinterpret_cast<void**>(&w.h_ms), sizeof(ndtomp::NdtMachine) * cap, hipHostMallocDefault));
+    PCM_HIPCK(c0, hipMalloc(&w.d_objs, sizeof(NdtObject) * cap));
+    PCM_HIPCK(c0, hipMalloc(&w.d_ms, sizeof(ndtomp::NdtMachine) * cap));
+    PCM_HIPCK(c0, hipHostMalloc(reinterpret_cast<void**>(&w.h_objs), sizeof(NdtObject) * cap, hipHostMallocDefault));
+    PCM_HIPCK(c0, hipHostMalloc(reinterpret_cast<void**>(&w.h_ms), sizeof(ndtomp::NdtMachine) * cap, hipHostMallocDefault));
     w.cap = cap;
   }
   // an object asks for at most 12 evaluations per Newton iteration (1 + 10 trials + the Hessian pass) and runs max_iterations + 2 of them
@@ -959,15 +949,15 @@ int pclndt_align_batch(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_re
     if (w.h_flags) hipHostFree(w.h_flags);
     w.h_flags = nullptr; w.d_flags = nullptr; w.cap_flags = 0;
     const size_t bytes = std::max<size_t>(flag_bytes, 65536);
-    HIPCK(c0, hipHostMalloc(reinterpret_cast<void**>(&w.h_flags), bytes, hipHostMallocMapped));
-    HIPCK(c0, hipHostGetDevicePointer(reinterpret_cast<void**>(&w.d_flags), w.h_flags, 0));
+    PCM_HIPCK(c0, hipHostMalloc(reinterpret_cast<void**>(&w.h_flags), bytes, hipHostMallocMapped));
+    PCM_HIPCK(c0, hipHostGetDevicePointer(reinterpret_cast<void**>(&w.d_flags), w.h_flags, 0));
     w.cap_flags = bytes;
   }
   std::memset(w.h_flags, 0, flag_bytes);
   hipStream_t st = c0->stream;
-  HIPCK(c0, hipMemcpyAsync(w.d_objs, w.h_objs, sizeof(NdtObject) * n, hipMemcpyHostToDevice, st));
-  HIPCK(c0, hipMemcpyAsync(w.d_ms, w.h_ms, sizeof(ndtomp::NdtMachine) * n, hipMemcpyHostToDevice, st));
-  HIPCK(c0, hipStreamSynchronize(st));   // the groups below run on their own streams
+  PCM_HIPCK(c0, hipMemcpyAsync(w.d_objs, w.h_objs, sizeof(NdtObject) * n, hipMemcpyHostToDevice, st));
+  PCM_HIPCK(c0, hipMemcpyAsync(w.d_ms, w.h_ms, sizeof(ndtomp::NdtMachine) * n, hipMemcpyHostToDevice, st));
+  PCM_HIPCK(c0, hipStreamSynchronize(st));   // the groups below run on their own streams
   // The objects advance in up to four groups, each in lock-step on the stream of its first object: registrations need 6 ... 37
   // Newton iterations on the same map, and a single lock-step batch runs every round at the pace of its largest kernel while most
   // objects have finished.  At most two rounds of a group are in flight (the host confirms a round's status bytes before it queues
@@ -993,7 +983,7 @@ int pclndt_align_batch(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_re
     // ran at 3 225 registrations/s and a second batch of objects created later in the same process at 2 016, or the other way round.)
     if (ngroups == 1) G.st = ctxs[G.lo]->stream;
     else {
-      if (!w.gst[g]) HIPCK(c0, hipStreamCreateWithFlags(&w.gst[g], hipStreamNonBlocking));
+      if (!w.gst[g]) PCM_HIPCK(c0, hipStreamCreateWithFlags(&w.gst[g], hipStreamNonBlocking));
       G.st = w.gst[g];
     }
     for (int i = G.lo; i < G.hi; i++) G.max_blocks = std::max(G.max_blocks, (int)w.h_objs[i].nblocks);
@@ -1038,10 +1028,10 @@ int pclndt_align_batch(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_re
         }
     }
   }
-  HIPCK(c0, hipGetLastError());
-  for (Group& G : groups) HIPCK(c0, hipStreamSynchronize(G.st));
-  HIPCK(c0, hipMemcpyAsync(w.h_ms, w.d_ms, sizeof(ndtomp::NdtMachine) * n, hipMemcpyDeviceToHost, st));
-  HIPCK(c0, hipStreamSynchronize(st));
+  PCM_HIPCK(c0, hipGetLastError());
+  for (Group& G : groups) PCM_HIPCK(c0, hipStreamSynchronize(G.st));
+  PCM_HIPCK(c0, hipMemcpyAsync(w.h_ms, w.d_ms, sizeof(ndtomp::NdtMachine) * n, hipMemcpyDeviceToHost, st));
+  PCM_HIPCK(c0, hipStreamSynchronize(st));
   int worst = PCM_OK;
   for (int i = 0; i < n; i++) {
     const ndtomp::NdtMachine& m = w.h_ms[i];
@@ -1222,9 +1212,9 @@ static int lio_members_resize(pcm_ctx* c, size_t n) {
   if (n > c->lio_aux_cap) {
     const size_t cap = n + n / 2 + 1024;
     float2* nb = nullptr;
-    HIPCK(c, hipMalloc(&nb, sizeof(float2) * cap));
-    if (c->lio_aux_n) HIPCK(c, hipMemcpyAsync(nb, c->lio_aux, sizeof(float2) * c->lio_aux_n, hipMemcpyDeviceToDevice, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
+    PCM_HIPCK(c, hipMalloc(&nb, sizeof(float2) * cap));
+    if (c->lio_aux_n) PCM_HIPCK(c, hipMemcpyAsync(nb, c->lio_aux, sizeof(float2) * c->lio_aux_n, hipMemcpyDeviceToDevice, c->stream));
+    PCM_HIPCK(c, hipStreamSynchronize(c->stream));
     if (c->lio_aux) hipFree(c->lio_aux);
     c->lio_aux = nb;
     c->lio_aux_cap = cap;
@@ -1249,7 +1239,7 @@ int pcm_set_source(pcm_ctx* c, const void* points, size_t n, size_t stride_bytes
 
 int pcm_swap_source_and_target(pcm_ctx* c) {
   CHECK_CTX(c);
-  HIPCK(c, hipStreamSynchronize(c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   std::swap(c->src, c->tgt);
   std::swap(c->user_cov[0], c->user_cov[1]);   // source_covs_.swap(target_covs_)  fast_gicp_impl.hpp:55
   c->map.valid = false;
@@ -1309,10 +1299,10 @@ int pcm_fitness_score(pcm_ctx* c, const float T[16], double max_range, double* s
   rc = ensure_ws(c, &w, 1, (size_t)std::max<uint32_t>(2u * nblocks, kPartialStride), 2);
   if (rc != PCM_OK) return rc;
   launch_fitness(c->stream, d.tgt, coord_mode_for(c->cfg.model), c->src.d_pts, n, T, max_range, w->d_partials);
-  HIPCK(c, hipGetLastError());
+  PCM_HIPCK(c, hipGetLastError());
   std::vector<double> rows(2 * (size_t)nblocks);
-  HIPCK(c, hipMemcpyAsync(rows.data(), w->d_partials, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, c->stream));
-  HIPCK(c, hipStreamSynchronize(c->stream));
+  PCM_HIPCK(c, hipMemcpyAsync(rows.data(), w->d_partials, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   double sum = 0.0, cnt = 0.0;
   for (uint32_t b = 0; b < nblocks; b++) { sum += rows[2 * b]; cnt += rows[2 * b + 1]; }
   *score = cnt > 0.0 ? sum / cnt : DBL_MAX;
@@ -1325,7 +1315,7 @@ int pcm_undistort(pcm_ctx* c, void* points, size_t n, size_t stride, size_t time
   if ((!points && n) || !poses || !st || npose < 0) return PCM_ERR_INVALID_ARGUMENT;
   if (stride < 16 || (stride % 4) != 0 || time_off + 4 > stride || (time_off % 4) != 0) { c->err = "bad record layout"; return PCM_ERR_INVALID_ARGUMENT; }
   if (n == 0 || npose < 2) return PCM_OK;
-  HIPCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   LioStateD s;
   for (int a = 0; a < 4; a++) { s.rot[a] = st->rot[a]; s.off_R[a] = st->off_R[a]; }
   for (int a = 0; a < 3; a++) { s.pos[a] = st->pos[a]; s.off_T[a] = st->off_T[a]; }
@@ -1334,20 +1324,20 @@ int pcm_undistort(pcm_ctx* c, void* points, size_t n, size_t stride, size_t time
   if (c->pre_arena_cap < need) {   // grow-only arena shared with pcm_voxel_downsample
     if (c->pre_arena) hipFree(c->pre_arena);
     c->pre_arena = nullptr; c->pre_arena_cap = 0;
-    HIPCK(c, hipMalloc(&c->pre_arena, need + need / 4));
+    PCM_HIPCK(c, hipMalloc(&c->pre_arena, need + need / 4));
     c->pre_arena_cap = need + need / 4;
   }
   pcm_imu_pose* d_poses = reinterpret_cast<pcm_imu_pose*>(c->pre_arena);
-  HIPCK(c, hipMemcpyAsync(d_poses, poses, sizeof(pcm_imu_pose) * (size_t)npose, hipMemcpyHostToDevice, c->stream));
+  PCM_HIPCK(c, hipMemcpyAsync(d_poses, poses, sizeof(pcm_imu_pose) * (size_t)npose, hipMemcpyHostToDevice, c->stream));
   void* d_pts = points;
   if (memory == PCM_MEM_HOST) {
     d_pts = c->pre_arena + up(sizeof(pcm_imu_pose) * (size_t)npose);
-    HIPCK(c, hipMemcpyAsync(d_pts, points, n * stride, hipMemcpyHostToDevice, c->stream));
+    PCM_HIPCK(c, hipMemcpyAsync(d_pts, points, n * stride, hipMemcpyHostToDevice, c->stream));
   }
   const int rc = undistort_device(c->stream, d_pts, n, stride, time_off, d_poses, npose, s, &c->err);
   if (rc != PCM_OK) return rc;
-  if (memory == PCM_MEM_HOST) HIPCK(c, hipMemcpyAsync(points, d_pts, n * stride, hipMemcpyDeviceToHost, c->stream));
-  HIPCK(c, hipStreamSynchronize(c->stream));
+  if (memory == PCM_MEM_HOST) PCM_HIPCK(c, hipMemcpyAsync(points, d_pts, n * stride, hipMemcpyDeviceToHost, c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   return PCM_OK;
 }
 
@@ -1401,13 +1391,13 @@ int pcm_gicp_bfgs_set_correspondences(pcm_ctx* c, const void* src, size_t n_src,
   if (memory == PCM_MEM_HOST)
     for (size_t i = 0; i < m; i++)
       if (idx_src[i] < 0 || (size_t)idx_src[i] >= n_src || idx_tgt[i] < 0 || (size_t)idx_tgt[i] >= n_tgt) { c->err = "correspondence index out of range"; return PCM_ERR_INVALID_ARGUMENT; }
-  HIPCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   c->bfgs_m = 0;
   const size_t need = gicp_bfgs_scratch_bytes(m);
   if (c->bfgs_cap < need) {
     if (c->bfgs) hipFree(c->bfgs);
     c->bfgs = nullptr; c->bfgs_cap = 0;
-    HIPCK(c, hipMalloc(&c->bfgs, need + need / 4));
+    PCM_HIPCK(c, hipMalloc(&c->bfgs, need + need / 4));
     c->bfgs_cap = need + need / 4;
   }
   if (m == 0) return PCM_OK;
@@ -1418,18 +1408,18 @@ int pcm_gicp_bfgs_set_correspondences(pcm_ctx* c, const void* src, size_t n_src,
   if (memory == PCM_MEM_HOST) {   // staged once per correspondence set; the evaluations then read the packed records only
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t b_src = up(n_src * stride), b_tgt = up(n_tgt * stride), b_idx = up(m * 4), b_maha = up(n_src * 64);
-    HIPCK(c, hipMallocAsync(reinterpret_cast<void**>(&tmp), b_src + b_tgt + 2 * b_idx + b_maha, c->stream));
+    PCM_HIPCK(c, hipMallocAsync(reinterpret_cast<void**>(&tmp), b_src + b_tgt + 2 * b_idx + b_maha, c->stream));
     char* q = tmp;
-    HIPCK(c, hipMemcpyAsync(q, src, n_src * stride, hipMemcpyHostToDevice, c->stream)); d_src = q; q += b_src;
-    HIPCK(c, hipMemcpyAsync(q, tgt, n_tgt * stride, hipMemcpyHostToDevice, c->stream)); d_tgt = q; q += b_tgt;
-    HIPCK(c, hipMemcpyAsync(q, idx_src, m * 4, hipMemcpyHostToDevice, c->stream)); d_is = reinterpret_cast<const int32_t*>(q); q += b_idx;
-    HIPCK(c, hipMemcpyAsync(q, idx_tgt, m * 4, hipMemcpyHostToDevice, c->stream)); d_it = reinterpret_cast<const int32_t*>(q); q += b_idx;
-    HIPCK(c, hipMemcpyAsync(q, maha, n_src * 64, hipMemcpyHostToDevice, c->stream)); d_maha = reinterpret_cast<const float*>(q);
+    PCM_HIPCK(c, hipMemcpyAsync(q, src, n_src * stride, hipMemcpyHostToDevice, c->stream)); d_src = q; q += b_src;
+    PCM_HIPCK(c, hipMemcpyAsync(q, tgt, n_tgt * stride, hipMemcpyHostToDevice, c->stream)); d_tgt = q; q += b_tgt;
+    PCM_HIPCK(c, hipMemcpyAsync(q, idx_src, m * 4, hipMemcpyHostToDevice, c->stream)); d_is = reinterpret_cast<const int32_t*>(q); q += b_idx;
+    PCM_HIPCK(c, hipMemcpyAsync(q, idx_tgt, m * 4, hipMemcpyHostToDevice, c->stream)); d_it = reinterpret_cast<const int32_t*>(q); q += b_idx;
+    PCM_HIPCK(c, hipMemcpyAsync(q, maha, n_src * 64, hipMemcpyHostToDevice, c->stream)); d_maha = reinterpret_cast<const float*>(q);
   }
   const int rc = gicp_bfgs_pack_device(c->stream, d_src, d_tgt, stride, d_is, d_it, d_maha, m, c->bfgs, &c->err);
-  if (tmp) HIPCK(c, hipFreeAsync(tmp, c->stream));
+  if (tmp) PCM_HIPCK(c, hipFreeAsync(tmp, c->stream));
   if (rc != PCM_OK) return rc;
-  HIPCK(c, hipStreamSynchronize(c->stream));   // the caller's buffers are free again
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));   // the caller's buffers are free again
   c->bfgs_m = m;
   return PCM_OK;
 }
@@ -1438,15 +1428,15 @@ int pcm_gicp_bfgs_fdf(pcm_ctx* c, const float* base_T, const double* x, int mode
   CHECK_CTX(c);
   if (!base_T || !x || mode < 0 || mode > 2 || (mode != 1 && !f) || (mode != 0 && !g)) return PCM_ERR_INVALID_ARGUMENT;
   if (c->bfgs_m == 0) { c->err = "no correspondences (pcm_gicp_bfgs_set_correspondences)"; return PCM_ERR_NO_INPUT; }
-  HIPCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   float T[16];
   bfgs_apply_state(base_T, x, T);
   const size_t m = c->bfgs_m;
   double* d_partials = reinterpret_cast<double*>(c->bfgs + ((64 * m + 255) & ~(size_t)255));
-  if (!c->bfgs_host) HIPCK(c, hipHostMalloc(reinterpret_cast<void**>(&c->bfgs_host), 16 * sizeof(double), hipHostMallocDefault));
+  if (!c->bfgs_host) PCM_HIPCK(c, hipHostMalloc(reinterpret_cast<void**>(&c->bfgs_host), 16 * sizeof(double), hipHostMallocDefault));
   const int rc = gicp_bfgs_fdf_device(c->stream, c->bfgs, m, T, base_T, d_partials, c->bfgs_host, &c->err);   // the finish kernel stores to host memory
   if (rc != PCM_OK) return rc;
-  HIPCK(c, hipStreamSynchronize(c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   const double* s = c->bfgs_host;
   const double dm = (double)m;
   if (f && mode != 1) *f = (mode == 0 ? s[0] : s[1]) / dm;
@@ -1474,20 +1464,20 @@ int pcm_gicp_bfgs_update_correspondences(pcm_ctx* c, const float* transformation
   if (c->bfgs_cap < need) {
     if (c->bfgs) hipFree(c->bfgs);
     c->bfgs = nullptr; c->bfgs_cap = 0;
-    HIPCK(c, hipMalloc(&c->bfgs, need + need / 4));
+    PCM_HIPCK(c, hipMalloc(&c->bfgs, need + need / 4));
     c->bfgs_cap = need + need / 4;
   }
   if (c->bfgs_idx_cap < n) {
     if (c->bfgs_idx) hipFree(c->bfgs_idx);
     c->bfgs_idx = nullptr; c->bfgs_idx_cap = 0;
-    HIPCK(c, hipMalloc(&c->bfgs_idx, sizeof(int32_t) * 2 * (n + n / 4 + 64)));
+    PCM_HIPCK(c, hipMalloc(&c->bfgs_idx, sizeof(int32_t) * 2 * (n + n / 4 + 64)));
     c->bfgs_idx_cap = n + n / 4 + 64;
   }
   uint32_t m = 0;
   rc = gicp_bfgs_correspond_device(c->stream, c->map, coord_mode_for(c->cfg.model), c->srcmap, c->src_cov, c->tgt_cov, guess, transformation, (double)c->cfg.max_corr_dist,
                                    reinterpret_cast<float4*>(c->bfgs), c->bfgs_idx, c->bfgs_idx + c->bfgs_idx_cap, &m, &c->err);
   if (rc != PCM_OK) return rc;
-  HIPCK(c, hipStreamSynchronize(c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   c->bfgs_m = m;
   *m_out = m;
   return PCM_OK;
@@ -1498,11 +1488,11 @@ int pcm_gicp_bfgs_get_correspondences(pcm_ctx* c, int32_t* idx_src, int32_t* idx
   const size_t m = c->bfgs_m;
   if (!c->bfgs_idx || capacity < m) { c->err = "pcm_gicp_bfgs_get_correspondences: no device-side correspondence set, or the buffers are too small"; return PCM_ERR_INVALID_ARGUMENT; }
   if (m == 0) return PCM_OK;
-  if (idx_src) HIPCK(c, hipMemcpy(idx_src, c->bfgs_idx, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
-  if (idx_tgt) HIPCK(c, hipMemcpy(idx_tgt, c->bfgs_idx + c->bfgs_idx_cap, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
+  if (idx_src) PCM_HIPCK(c, hipMemcpy(idx_src, c->bfgs_idx, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
+  if (idx_tgt) PCM_HIPCK(c, hipMemcpy(idx_tgt, c->bfgs_idx + c->bfgs_idx_cap, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
   if (maha9) {
     std::vector<float4> r(3 * m);   // planes 1..3 of the records hold M
-    HIPCK(c, hipMemcpy(r.data(), reinterpret_cast<const float4*>(c->bfgs) + m, sizeof(float4) * 3 * m, hipMemcpyDeviceToHost));
+    PCM_HIPCK(c, hipMemcpy(r.data(), reinterpret_cast<const float4*>(c->bfgs) + m, sizeof(float4) * 3 * m, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < m; i++) {
       const float4 a = r[i], b = r[m + i], d = r[2 * m + i];
       float* o = maha9 + 9 * i;
@@ -1519,14 +1509,14 @@ int pcm_voxel_downsample(pcm_ctx* c, const void* points, size_t n, size_t stride
   if (capacity_points < n) { c->err = "the output buffer must hold as many records as the input"; return PCM_ERR_INVALID_ARGUMENT; }
   *n_out = 0;
   if (n == 0) return PCM_OK;
-  HIPCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t io = memory == PCM_MEM_HOST ? 2 * up(n * stride) : 0;
   const size_t need = voxel_downsample_scratch_bytes(n) + io;
   if (c->pre_arena_cap < need) {   // grow-only arena: no allocation per frame in the steady state
     if (c->pre_arena) hipFree(c->pre_arena);
     c->pre_arena = nullptr; c->pre_arena_cap = 0;
-    HIPCK(c, hipMalloc(&c->pre_arena, need + need / 4));
+    PCM_HIPCK(c, hipMalloc(&c->pre_arena, need + need / 4));
     c->pre_arena_cap = need + need / 4;
   }
   const void* src = points;
@@ -1536,14 +1526,14 @@ int pcm_voxel_downsample(pcm_ctx* c, const void* points, size_t n, size_t stride
     char* d_in = c->pre_arena;
     char* d_out = c->pre_arena + up(n * stride);
     scratch = c->pre_arena + io;
-    HIPCK(c, hipMemcpyAsync(d_in, points, n * stride, hipMemcpyHostToDevice, c->stream));
+    PCM_HIPCK(c, hipMemcpyAsync(d_in, points, n * stride, hipMemcpyHostToDevice, c->stream));
     src = d_in; dst = d_out;
   }
   int rc = voxel_downsample_device(c->stream, src, n, stride, leaf, static_cast<float*>(dst), n_out, scratch, &c->err);
   if (rc != PCM_OK) return rc;
   if (memory == PCM_MEM_HOST && *n_out) {
-    HIPCK(c, hipMemcpyAsync(out, dst, *n_out * stride, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
+    PCM_HIPCK(c, hipMemcpyAsync(out, dst, *n_out * stride, hipMemcpyDeviceToHost, c->stream));
+    PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   }
   return PCM_OK;
 }
@@ -1574,14 +1564,14 @@ int pcm_livox_filter(pcm_ctx* c, const void* custom_points, size_t n, int memory
   if (n > 0xffffffffull) { c->err = "too many points"; return PCM_ERR_INVALID_ARGUMENT; }
   *n_out = 0;
   if (n == 0) return PCM_OK;
-  HIPCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t io = memory == PCM_MEM_HOST ? up(n * 20) + up(n * 48) : 0;
   const size_t need = livox_filter_scratch_bytes(n) + io;
   if (c->pre_arena_cap < need) {   // grow-only arena shared with the other pre-processing operators
     if (c->pre_arena) hipFree(c->pre_arena);
     c->pre_arena = nullptr; c->pre_arena_cap = 0;
-    HIPCK(c, hipMalloc(&c->pre_arena, need + need / 4));
+    PCM_HIPCK(c, hipMalloc(&c->pre_arena, need + need / 4));
     c->pre_arena_cap = need + need / 4;
   }
   const void* src = custom_points;
@@ -1591,13 +1581,13 @@ int pcm_livox_filter(pcm_ctx* c, const void* custom_points, size_t n, int memory
     char* d_in = c->pre_arena;
     char* d_out = c->pre_arena + up(n * 20);
     scratch = c->pre_arena + io;
-    HIPCK(c, hipMemcpyAsync(d_in, custom_points, n * 20, hipMemcpyHostToDevice, c->stream));
+    PCM_HIPCK(c, hipMemcpyAsync(d_in, custom_points, n * 20, hipMemcpyHostToDevice, c->stream));
     src = d_in; dst = d_out;
   }
   const int rc = livox_filter_device(c->stream, src, n, num_scans, point_filter_num, blind, dst, n_out, scratch, &c->err);
   if (rc != PCM_OK) return rc;
-  if (memory == PCM_MEM_HOST && *n_out) HIPCK(c, hipMemcpyAsync(out, dst, *n_out * 48, hipMemcpyDeviceToHost, c->stream));
-  HIPCK(c, hipStreamSynchronize(c->stream));
+  if (memory == PCM_MEM_HOST && *n_out) PCM_HIPCK(c, hipMemcpyAsync(out, dst, *n_out * 48, hipMemcpyDeviceToHost, c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   return PCM_OK;
 }
 
@@ -1616,9 +1606,9 @@ int pcm_get_covariances(pcm_ctx* c, int target, double* out, size_t capacity_poi
   if (capacity_points < m.num_points) { c->err = "output buffer too small"; return PCM_ERR_INVALID_ARGUMENT; }
   std::vector<double> h6((size_t)m.num_points * 6);
   std::vector<uint32_t> ord(m.num_points);
-  HIPCK(c, hipMemcpyAsync(h6.data(), d_cov, sizeof(double) * h6.size(), hipMemcpyDeviceToHost, c->stream));
-  HIPCK(c, hipMemcpyAsync(ord.data(), m.order, sizeof(uint32_t) * ord.size(), hipMemcpyDeviceToHost, c->stream));
-  HIPCK(c, hipStreamSynchronize(c->stream));
+  PCM_HIPCK(c, hipMemcpyAsync(h6.data(), d_cov, sizeof(double) * h6.size(), hipMemcpyDeviceToHost, c->stream));
+  PCM_HIPCK(c, hipMemcpyAsync(ord.data(), m.order, sizeof(uint32_t) * ord.size(), hipMemcpyDeviceToHost, c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   for (size_t i = 0; i < ord.size(); i++) {
     const double* s = &h6[i * 6];
     double* o = out + (size_t)ord[i] * 9;
@@ -1777,8 +1767,8 @@ int pcm_obs_model(pcm_ctx* c, const pcm_lio_state* s, int extrinsic_est_en, int 
     float g[16] = {(float)Rwl[0], (float)Rwl[1], (float)Rwl[2], L.t_wl[0], (float)Rwl[3], (float)Rwl[4], (float)Rwl[5], L.t_wl[1],
                    (float)Rwl[6], (float)Rwl[7], (float)Rwl[8], L.t_wl[2], 0.f, 0.f, 0.f, 1.f};
     SortJob j{c->src.d_pts, c->src_order, n, 0, 0, 0};
-    HIPCK(c, hipMemcpyAsync(w->d_guesses, g, sizeof(g), hipMemcpyHostToDevice, st));
-    HIPCK(c, hipMemcpyAsync(w->d_jobs, &j, sizeof(j), hipMemcpyHostToDevice, st));
+    PCM_HIPCK(c, hipMemcpyAsync(w->d_guesses, g, sizeof(g), hipMemcpyHostToDevice, st));
+    PCM_HIPCK(c, hipMemcpyAsync(w->d_jobs, &j, sizeof(j), hipMemcpyHostToDevice, st));
     rc = sort_sources_batched(st, w->d_jobs, 1, n, n, w->d_guesses, c->cfg.voxel_resolution, &w->sort, &c->err);
     if (rc != PCM_OK) return rc;
     c->src_sorted = true;
@@ -1802,14 +1792,14 @@ int pcm_obs_model(pcm_ctx* c, const pcm_lio_state* s, int extrinsic_est_en, int 
   PairState ps;
   const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   init_state(ps, ident);
-  HIPCK(c, hipMemcpyAsync(w->d_descs, &d, sizeof(d), hipMemcpyHostToDevice, st));
-  HIPCK(c, hipMemcpyAsync(w->d_states, &ps, sizeof(ps), hipMemcpyHostToDevice, st));
+  PCM_HIPCK(c, hipMemcpyAsync(w->d_descs, &d, sizeof(d), hipMemcpyHostToDevice, st));
+  PCM_HIPCK(c, hipMemcpyAsync(w->d_states, &ps, sizeof(ps), hipMemcpyHostToDevice, st));
   launch_lio_obs(st, w->d_descs, w->d_states, kp);
   launch_lio_finish(st, w->d_partials, tiles, w->d_sums);
-  HIPCK(c, hipGetLastError());
+  PCM_HIPCK(c, hipGetLastError());
   double sums[kLioStride];
-  HIPCK(c, hipMemcpyAsync(sums, w->d_sums, sizeof(double) * kLioStride, hipMemcpyDeviceToHost, st));
-  HIPCK(c, hipStreamSynchronize(st));
+  PCM_HIPCK(c, hipMemcpyAsync(sums, w->d_sums, sizeof(double) * kLioStride, hipMemcpyDeviceToHost, st));
+  PCM_HIPCK(c, hipStreamSynchronize(st));
   if (rematch) c->lio_planes_valid = true;
   int t = 0;
   for (int a = 0; a < 12; a++) for (int b = a; b < 12; b++) { out->HTH[a * 12 + b] = sums[t]; out->HTH[b * 12 + a] = sums[t]; t++; }
@@ -1828,9 +1818,9 @@ int reserve_target(pcm_ctx* c, size_t need) {
   if (need <= c->tgt.cap && !c->tgt.borrowed) return PCM_OK;
   const size_t cap = std::max(need, c->tgt.cap + c->tgt.cap / 2 + 1024);
   float4* nb = nullptr;
-  HIPCK(c, hipMalloc(&nb, sizeof(float4) * cap));
-  if (c->tgt.n) HIPCK(c, hipMemcpyAsync(nb, c->tgt.d_pts, sizeof(float4) * c->tgt.n, hipMemcpyDeviceToDevice, c->stream));
-  HIPCK(c, hipStreamSynchronize(c->stream));
+  PCM_HIPCK(c, hipMalloc(&nb, sizeof(float4) * cap));
+  if (c->tgt.n) PCM_HIPCK(c, hipMemcpyAsync(nb, c->tgt.d_pts, sizeof(float4) * c->tgt.n, hipMemcpyDeviceToDevice, c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   const size_t n = c->tgt.n;
   const uint64_t tag = c->tgt.tag;
   c->tgt.drop_buffer();
@@ -1844,12 +1834,12 @@ int pcm_target_insert(pcm_ctx* c, const void* points, size_t n, size_t stride_by
   if (!points && n) { c->err = "null point buffer"; return PCM_ERR_INVALID_ARGUMENT; }
   if (stride_bytes < 3 * sizeof(float) || (stride_bytes % sizeof(float)) != 0) { c->err = "stride must be a multiple of 4 and >= 12 bytes"; return PCM_ERR_INVALID_ARGUMENT; }
   if (n == 0) return PCM_OK;
-  HIPCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   int rc = reserve_target(c, c->tgt.n + n);
   if (rc != PCM_OK) return rc;
   rc = load_points_to_device(c->stream, points, n, stride_bytes, memory, c->next_seq, c->tgt.d_pts + c->tgt.n, &c->err);
   if (rc != PCM_OK) return rc;
-  HIPCK(c, hipStreamSynchronize(c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   c->tgt.n += n;
   c->next_seq += (uint32_t)n;
   c->tgt.tag = 0;
@@ -1862,7 +1852,7 @@ int pcm_map_incremental(pcm_ctx* c, const pcm_lio_state* s, float filter_size_ma
   CHECK_CTX(c);
   if (!s) return PCM_ERR_INVALID_ARGUMENT;
   if (c->src.n == 0) { c->err = "pcm_map_incremental without a source scan"; return PCM_ERR_NO_INPUT; }
-  HIPCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   const uint32_t n = (uint32_t)c->src.n;
   int rc = reserve_target(c, c->tgt.n + n);
   if (rc != PCM_OK) return rc;
@@ -1895,7 +1885,7 @@ int pcm_lio_frame_begin(pcm_ctx* c, const void* custom_points, size_t n, int mem
   if (!(prm->leaf_size >= 0.f)) { c->err = "leaf_size must be >= 0"; return PCM_ERR_INVALID_ARGUMENT; }
   *n_scan = 0;
   if (n == 0) { c->err = "empty frame"; return PCM_ERR_NO_INPUT; }
-  HIPCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   // frame arena: [raw message | filtered records | down-sampled records | IMU poses | scratch of the operators]; grow-only, so the
@@ -1906,13 +1896,13 @@ int pcm_lio_frame_begin(pcm_ctx* c, const void* custom_points, size_t n, int mem
   if (c->pre_arena_cap < need) {
     if (c->pre_arena) hipFree(c->pre_arena);
     c->pre_arena = nullptr; c->pre_arena_cap = 0;
-    HIPCK(c, hipMalloc(&c->pre_arena, need + need / 4));
+    PCM_HIPCK(c, hipMalloc(&c->pre_arena, need + need / 4));
     c->pre_arena_cap = need + need / 4;
   }
   char* A = c->pre_arena;
   const void* d_raw = custom_points;
   if (memory == PCM_MEM_HOST) {
-    HIPCK(c, hipMemcpyAsync(A + o_raw, custom_points, n * 20, hipMemcpyHostToDevice, st));
+    PCM_HIPCK(c, hipMemcpyAsync(A + o_raw, custom_points, n * 20, hipMemcpyHostToDevice, st));
     d_raw = A + o_raw;
   }
   // 1. PointCloudPreprocess::AviaHandler  (pointcloud_preprocess.cc:44-88)
@@ -1927,7 +1917,7 @@ int pcm_lio_frame_begin(pcm_ctx* c, const void* custom_points, size_t n, int mem
     LioStateD s;
     for (int a = 0; a < 4; a++) { s.rot[a] = end_state->rot[a]; s.off_R[a] = end_state->off_R[a]; }
     for (int a = 0; a < 3; a++) { s.pos[a] = end_state->pos[a]; s.off_T[a] = end_state->off_T[a]; }
-    HIPCK(c, hipMemcpyAsync(A + o_pose, poses, sizeof(pcm_imu_pose) * (size_t)npose, hipMemcpyHostToDevice, st));
+    PCM_HIPCK(c, hipMemcpyAsync(A + o_pose, poses, sizeof(pcm_imu_pose) * (size_t)npose, hipMemcpyHostToDevice, st));
     rc = undistort_device(st, A + o_flt, n_flt, 48, 36, reinterpret_cast<const pcm_imu_pose*>(A + o_pose), npose, s, &c->err);   // PointXYZINormal::curvature: byte 36
     if (rc != PCM_OK) return rc;
   }
@@ -1965,8 +1955,8 @@ int pcm_get_source(pcm_ctx* c, float* out_xyz, size_t capacity_points, size_t* n
   if (!out_xyz) return PCM_OK;
   if (capacity_points < c->src.n) { c->err = "pcm_get_source: buffer too small"; return PCM_ERR_INVALID_ARGUMENT; }
   std::vector<float4> tmp(c->src.n);
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  HIPCK(c, hipMemcpy(tmp.data(), c->src.d_pts, sizeof(float4) * c->src.n, hipMemcpyDeviceToHost));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
+  PCM_HIPCK(c, hipMemcpy(tmp.data(), c->src.d_pts, sizeof(float4) * c->src.n, hipMemcpyDeviceToHost));
   for (size_t i = 0; i < c->src.n; i++) { out_xyz[3 * i] = tmp[i].x; out_xyz[3 * i + 1] = tmp[i].y; out_xyz[3 * i + 2] = tmp[i].z; }
   return PCM_OK;
 }
@@ -1982,7 +1972,7 @@ int pcm_get_target(pcm_ctx* c, float* out_xyz, size_t capacity_points, size_t* n
   if (!out_xyz) return PCM_OK;
   if (capacity_points < c->tgt.n) { c->err = "pcm_get_target: buffer too small"; return PCM_ERR_INVALID_ARGUMENT; }
   std::vector<float4> tmp(c->tgt.n);
-  HIPCK(c, hipMemcpy(tmp.data(), c->tgt.d_pts, sizeof(float4) * c->tgt.n, hipMemcpyDeviceToHost));
+  PCM_HIPCK(c, hipMemcpy(tmp.data(), c->tgt.d_pts, sizeof(float4) * c->tgt.n, hipMemcpyDeviceToHost));
   for (size_t i = 0; i < c->tgt.n; i++) { out_xyz[3 * i] = tmp[i].x; out_xyz[3 * i + 1] = tmp[i].y; out_xyz[3 * i + 2] = tmp[i].z; }
   return PCM_OK;
 }
@@ -1990,7 +1980,7 @@ int pcm_get_target(pcm_ctx* c, float* out_xyz, size_t capacity_points, size_t* n
 int pcm_get_planes(pcm_ctx* c, float* out, size_t n) {
   CHECK_CTX(c);
   if (!out || n != c->src.n || !c->planes) { c->err = "pcm_get_planes: call pcm_linearize first; n must equal the source size"; return PCM_ERR_INVALID_ARGUMENT; }
-  HIPCK(c, hipMemcpy(out, c->planes, sizeof(float4) * n, hipMemcpyDeviceToHost));
+  PCM_HIPCK(c, hipMemcpy(out, c->planes, sizeof(float4) * n, hipMemcpyDeviceToHost));
   return PCM_OK;
 }
 
@@ -2001,8 +1991,8 @@ int pcm_get_lio_members(pcm_ctx* c, float* residuals, uint8_t* selected, size_t 
     return PCM_ERR_INVALID_ARGUMENT;
   }
   std::vector<float2> tmp(n);
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  if (n) HIPCK(c, hipMemcpy(tmp.data(), c->lio_aux, sizeof(float2) * n, hipMemcpyDeviceToHost));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
+  if (n) PCM_HIPCK(c, hipMemcpy(tmp.data(), c->lio_aux, sizeof(float2) * n, hipMemcpyDeviceToHost));
   for (size_t i = 0; i < n; i++) {
     if (residuals) residuals[i] = tmp[i].x;
     if (selected) selected[i] = tmp[i].y != 0.f ? 1 : 0;

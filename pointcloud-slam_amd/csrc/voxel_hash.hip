@@ -14,7 +14,7 @@
 // are laid out brick-major so everything under a search tile is a few contiguous
 // runs (layout: pcm_device.h).
 #include "pcm_device.h"
-#include "pcm_host.h"
+#include "host_util.h"
 #include "dev_linalg.h"
 
 #include <cstring>
@@ -380,20 +380,10 @@ struct BuildScratch {
   }
 };
 
+// grow-only arrays of a TargetMap: a quarter of headroom, the first keep_elems elements stay
 template <typename T>
 static int grow(T** p, size_t* cap, size_t need, size_t keep_elems, hipStream_t stream, std::string* err, const char* what) {
-  if (need <= *cap) return PCM_OK;
-  const size_t nc = need + need / 4 + 1024;
-  T* q = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&q), sizeof(T) * nc) != hipSuccess) { *err = std::string("hipMalloc(") + what + ")"; return PCM_ERR_HIP; }
-  if (*p && keep_elems) {
-    if (hipMemcpyAsync(q, *p, sizeof(T) * keep_elems, hipMemcpyDeviceToDevice, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { hipFree(q); *err = std::string("copy(") + what + ")"; return PCM_ERR_HIP; }
-  } else if (*p) {
-    (void)hipStreamSynchronize(stream);   // queued kernels may still read the old array
-  }
-  if (*p) hipFree(*p);
-  *p = q; *cap = nc;
-  return PCM_OK;
+  return dev_reserve_keep(p, cap, need, need + need / 4 + 1024, keep_elems, stream, err, what);
 }
 
 // Build the voxel hash of the point log `d_pts` into `map`, or -- `n_indexed` > 0: the first n_indexed log points are what
@@ -892,6 +882,27 @@ int load_points_to_device(hipStream_t stream, const void* points, size_t n, size
   k_load_points<<<cdiv((uint32_t)n, 256), 256, 0, stream>>>(reinterpret_cast<const char*>(d_out), sizeof(float4), (uint32_t)n, seq0, d_out);
   e = hipGetLastError();
   if (e != hipSuccess) { *err = std::string("k_load_points: ") + hipGetErrorString(e); return PCM_ERR_HIP; }
+  return PCM_OK;
+}
+
+// strided xyz(w) records -> float4 rows; w = the record's fourth float, or 0
+__global__ void k_load_xyzw_rows(const char* __restrict__ base, size_t stride, uint32_t n, int has_w, float4* __restrict__ dst) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* p = reinterpret_cast<const float*>(base + (size_t)i * stride);
+  dst[i] = make_float4(p[0], p[1], p[2], has_w ? p[3] : 0.f);
+}
+
+int load_xyzw_rows(pcm_ctx* c, const void* pts, size_t n, size_t stride, int memory, bool want_w, float4* dst) {
+  if (n == 0) return PCM_OK;
+  const int has_w = want_w && stride >= 4 * sizeof(float) ? 1 : 0;
+  if (memory == PCM_MEM_DEVICE) {
+    k_load_xyzw_rows<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(static_cast<const char*>(pts), stride, (uint32_t)n, has_w, dst);
+    PCM_HIPCK(c, hipGetLastError());
+    return PCM_OK;
+  }
+  if (!has_w) PCM_HIPCK(c, hipMemsetAsync(dst, 0, sizeof(float4) * n, c->stream));
+  PCM_HIPCK(c, hipMemcpy2DAsync(dst, sizeof(float4), pts, stride, has_w ? sizeof(float4) : 3 * sizeof(float), n, hipMemcpyHostToDevice, c->stream));
   return PCM_OK;
 }
 

@@ -198,6 +198,26 @@ def test_put_clear_and_repeatability(pcm):
     assert (r.loop_id, r.nn_idx, r.nn_align, r.min_dist) == (-1, 0, 0, 1e7) and r.candidates[0][2] == 1e7
 
 
+def test_growth_of_the_store_keeps_the_descriptors(pcm):
+    """700 descriptors: the store's arrays (room for 256 rows at first) are replaced at the 257th and again at the 641st.  Every
+    row, the rows stored before a growth included, reads back as the restatement's bits, and a distance between two early rows
+    (descriptor, sector key and column norms of both) is the restatement's after the growths as before them."""
+    L = loop()
+    P = R.Params()
+    descs = [R.make_scancontext(c, P) for c in L.clouds[:8]]
+    g = pcm.LoamRegistration(0)
+    for i in range(200):
+        g.sc_put(descs[i % 8])
+    before = g.sc_distance(3, 6)
+    assert before == R.distance(descs[3], descs[6])
+    for i in range(200, 700):
+        g.sc_put(descs[i % 8])
+    assert g.sc_count == 700
+    for i in list(range(0, 700, 7)) + [255, 256, 257, 639, 640, 641, 699]:
+        check_entry(g, i, descs[i % 8])
+    assert g.sc_distance(3, 6) == before and g.sc_distance(3, 694) == before
+
+
 def dataclass_tuple(r):
     return (r.loop_id, r.yaw_diff_rad, r.min_dist, r.nn_idx, r.nn_align, r.num_descriptors, r.tree_size, r.tree_rebuilt, r.num_evaluated,
             [tuple(None if isinstance(v, float) and math.isnan(v) else v for v in row) for row in r.candidates])
@@ -257,3 +277,14 @@ def test_errors_are_readable(pcm):
         g.sc_add(near=0)
     assert e.value.code == -4
     assert g.sc_count == 1
+
+
+def test_memory_kind_is_checked(pcm):
+    """Any memory kind other than PCM_MEM_HOST (0) and PCM_MEM_DEVICE (1) is refused before the buffer is touched."""
+    L = pcm.capi.load_library()
+    g = pcm.LoamRegistration(0)
+    pts = np.zeros((4, 3), F)
+    for mem in (-1, 2):
+        assert L.pcm_loam_sc_add(g._h, None, 0, -1, pts.ctypes.data, 4, 12, mem, None) == -1
+        assert b"memory must be" in L.pcm_last_error(g._h)
+    assert g.sc_count == 0

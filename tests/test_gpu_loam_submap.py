@@ -59,6 +59,20 @@ def test_update_matches_restatement(pcm, K, seed, radius):
     assert r.rebuilt
 
 
+def test_growth_of_the_matrices_keeps_the_earlier_key_frames(pcm):
+    """300 key frames: the pose-matrix array (room for 257 key frames at first) is replaced at the 258th and the surf arena
+    (65 536 points at first) grows twice.  The submap selected afterwards reaches back before the growth and is compared with the
+    restatement bit for bit (its input clouds are the stored clouds under the stored matrices); the stored clouds are read back
+    as they went in."""
+    kf = keyframes(0, 300)
+    g = filled(pcm, kf)
+    _, info, _ = check_update(g, kf, 15.0)
+    assert info["keys"].min() < 200 and info["keys"].max() > 257
+    for k in (0, 100, 256, 257, 299):
+        kc, ks = g.get_keyframe(k)
+        assert np.array_equal(bits(kc), bits(kf.corner[k])) and np.array_equal(bits(ks), bits(kf.surf[k]))
+
+
 def test_update_without_downsampling_and_known_answers(pcm):
     kf = keyframes(0, 40)
     g = filled(pcm, kf)
