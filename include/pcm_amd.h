@@ -647,6 +647,79 @@ int pcm_loam_sc_distance(pcm_ctx *ctx, const pcm_loam_sc_params *params, int i, 
 int pcm_loam_loop_detect_distance(pcm_ctx *ctx, float radius, double time_diff_s, double time_cur, int32_t *key_cur, int32_t *key_pre);
 
 /*
+ * Localisation map of jueying_slam on the device: the saved global map cut into area tiles (include/dynamic_map.h:16-156), the
+ * reload of the tiles around the robot (dynamic_load_map_run, localization.cpp:281-315) and the per-frame crop of the loaded
+ * tiles (dynamic_load_map, :256-280).  A PCM_MODEL_LOAM context keeps every tile of the corner list and of the surf list (map
+ * frame, PointXYZI) on the device; pcm_loam_dynmap_load selects tiles on the host and moves no points; pcm_loam_dynmap_crop
+ * compacts the selected tiles through the frame's window, in order, straight into the context's LOAM target
+ * (laserCloudCornerFromMapDS / laserCloudSurfFromMapDS), so a localisation frame is
+ *   pcm_loam_frame_begin -> pcm_loam_dynmap_crop -> pcm_loam_align
+ * with the scan as the only bulk upload.  DESIGN.md section 14.
+ */
+typedef struct pcm_loam_dynmap_params {
+  float max_range;               /* 150.0 utility.h:224: the window is pose -/+ max_range * 1.1 */
+  int32_t margin;                /* -1    utility.h:186: a tile is loaded when the pose lies in its box grown by margin; < 0: every
+                                  *       tile is selected and the crop keeps every (finite) point: the whole map is the target */
+  int32_t area_size;             /* -1    utility.h:185: reload after moving farther than this from the last load */
+  int32_t crop_x;                /* 0     0: only the y window has an effect, as localization.cpp:259-273 behaves (its x filters are
+                                  *       overwritten); 1: x and y windows both */
+  int32_t reserved[8];
+} pcm_loam_dynmap_params;
+
+typedef struct pcm_loam_dynmap_load_result {
+  int32_t num_corner_tiles;      /* tiles stored per list */
+  int32_t num_surf_tiles;
+  int32_t num_corner_selected;   /* tiles selected per list (empty tiles included) */
+  int32_t num_surf_selected;
+  int64_t num_corner_points;     /* points of the selected tiles */
+  int64_t num_surf_points;
+  uint64_t generation;           /* of the selection: changes only when a selected index list differs from the last load's */
+  int32_t changed;               /* 1: this load changed the selection */
+  int32_t reserved[5];
+} pcm_loam_dynmap_load_result;
+
+typedef struct pcm_loam_dynmap_crop_result {
+  int32_t num_corner_in;         /* points of the selected tiles */
+  int32_t num_surf_in;
+  int32_t num_corner;            /* points kept: laserCloudCornerFromMapDS / laserCloudSurfFromMapDS */
+  int32_t num_surf;
+  int32_t num_nonfinite;         /* points of both lists dropped for a non-finite x, y or z */
+  int32_t rebuilt;               /* 0: selection, limits and crop_x equal those of the last crop and the target is still its
+                                  * result: nothing done on the device */
+  float x_lo, x_hi, y_lo, y_hi;  /* the float limits (x_* are computed even where crop_x = 0 does not apply them) */
+  int32_t status;                /* PCM_OK */
+  int32_t reserved[5];
+} pcm_loam_dynmap_crop_result;
+
+void pcm_loam_default_dynmap_params(pcm_loam_dynmap_params *params);
+/* one area tile of list `which` (0 corner, 1 surf): box = x_min, y_min, z_min, x_max, y_max, z_max (the CSV area list's columns)
+ * and its n points (records of stride_bytes, x y z first, intensity the fourth float when stride_bytes >= 16, else 0; n may be 0).
+ * The intensity rule of pcm_loam_keyframe_add holds: a pcl::PointXYZI buffer must be repacked to (x, y, z, intensity) first, as
+ * pcm_amd::LoamDynamicMap does.  Returns the tile's index in its list (>= 0) or a negative pcm_status. */
+int pcm_loam_tile_add(pcm_ctx *ctx, int which, const double box[6], const void *points, size_t n, size_t stride_bytes, int memory);
+int pcm_loam_tile_count(pcm_ctx *ctx, int which);   /* tiles of the list, or a negative pcm_status */
+int pcm_loam_tile_clear(pcm_ctx *ctx);              /* both lists and the selection; device memory is kept */
+/* the trigger of dynamic_load_map_run: 1 when pose6 (roll, pitch, yaw, x, y, z) is farther than area_size from the pose of the
+ * last pcm_loam_dynmap_load (before the first one the last pose is -999999 on every axis, as last_loadMap starts), else 0; or a
+ * negative pcm_status.  The comparison is the reference's float arithmetic (localization.cpp:295-300).  params NULL = defaults. */
+int pcm_loam_dynmap_need_load(pcm_ctx *ctx, const pcm_loam_dynmap_params *params, const float pose6[6]);
+/* create_pcd for both lists at pose6: selects the tiles whose grown boxes hold (x, y), in list order, and records the pose as
+ * the last load.  No bulk data moves.  result may be NULL. */
+int pcm_loam_dynmap_load(pcm_ctx *ctx, const pcm_loam_dynmap_params *params, const float pose6[6], pcm_loam_dynmap_load_result *result);
+/* dynamic_load_map(pose6): the selected tiles, concatenated in list order, through the window; the result becomes the context's
+ * LOAM target (the caller index of a map point is its position in the cropped cloud) and the next pcm_loam_align builds the
+ * search grids.  PCM_ERR_NO_INPUT before a load. */
+int pcm_loam_dynmap_crop(pcm_ctx *ctx, const pcm_loam_dynmap_params *params, const float pose6[6], pcm_loam_dynmap_crop_result *result);
+/* parity hook: the selected tile indices of both lists (num_*_selected int32 each) and the two cropped clouds (num_corner /
+ * num_surf x 4 floats, to the host).  Any pointer may be NULL.  PCM_ERR_NO_INPUT when the context's target is not the result
+ * of pcm_loam_dynmap_crop (the clouds; the indices need only a load). */
+int pcm_loam_dynmap_info(pcm_ctx *ctx, int32_t *corner_tiles, int32_t *surf_tiles, float *corner, float *surf);
+/* globalMap (localization.cpp:274): the cropped corner cloud, then the cropped surf cloud, as (x, y, z, intensity) records into
+ * a host buffer or a caller's device buffer (memory) of `capacity` points; *n is always set, PCM_ERR_INVALID_ARGUMENT when the
+ * capacity is too small.  The Matching_method == "ndt" branch feeds it to an NDT context with PCM_MEM_DEVICE. */
+int pcm_loam_dynmap_global(pcm_ctx *ctx, void *out, size_t capacity, size_t *n, int memory);
+
+/*
  * 2D occupancy grid mapping of jueying_slam's map tool (src/tool/occupancy_mapping) on the device: getScan (cloud -> virtual
  * laser scan), processScan + TraceLine (rays into the grid), getGridMap (crop, -1 / 0 / 100) and saveMap's PGM bytes.  The map
  * belongs to a context of any model; a PCM_MODEL_LOAM context can also feed it from its key-frame store in place.  Offline

@@ -499,6 +499,93 @@ private:
   std::vector<float> buf_, buf2_;
 };
 
+// jueying_slam's localisation map on the device, on the context of a LoamScanToMap, with the call shape of localization.cpp
+// (DESIGN.md section 14):
+//     pcm_amd::LoamDynamicMap<PointType> dynmap(loam);
+//     for (const Area& a : all_Corner_areas) dynmap.addCornerArea(box_of(a), *cloud_of(a));     // once, instead of create_pcd per reload
+//     for (const Area& a : all_Surf_areas) dynmap.addSurfArea(box_of(a), *cloud_of(a));
+//     if (dynmap.needLoad(transformTobeMapped)) dynmap.load(transformTobeMapped);              // dynamic_load_map_run :295-311
+//     dynmap.dynamic_load_map(transformTobeMapped);                                            // :256; the result is loam's maps
+//     if (loam.scan2MapOptimization(transformTobeMapped)) transformUpdate();
+//     dynmap.globalMap(ndt_target_device_buffer, capacity);                                    // :274-277, the "ndt" branch
+// Tile clouds are repacked member by member (the PointXYZI rule of detail::pack_xyzi).  The object does not own the context.
+template <typename PointT>
+class LoamDynamicMap {
+public:
+  using Cloud = pcl::PointCloud<PointT>;
+
+  explicit LoamDynamicMap(LoamScanToMap<PointT>& loam) : ctx_(loam.context()) { pcm_loam_default_dynmap_params(&params_); }
+
+  void setMaxRange(float v) { params_.max_range = v; }     // max_range
+  void setMargin(int v) { params_.margin = v; }            // globalmap_server/margin
+  void setAreaSize(int v) { params_.area_size = v; }       // globalmap_server/area_size
+  void setCropX(bool v) { params_.crop_x = v ? 1 : 0; }    // false: only the y window has an effect, as the reference behaves
+  pcm_loam_dynmap_params& params() { return params_; }
+  const pcm_loam_dynmap_load_result& loadResult() const { return load_; }
+  const pcm_loam_dynmap_crop_result& result() const { return crop_; }
+
+  // box: x_min, y_min, z_min, x_max, y_max, z_max of the area list; returns the tile's index in its list
+  int addCornerArea(const double box[6], const Cloud& cloud) { return add(0, box, cloud); }
+  int addSurfArea(const double box[6], const Cloud& cloud) { return add(1, box, cloud); }
+  int cornerAreas() const { return pcm_loam_tile_count(ctx_, 0); }
+  int surfAreas() const { return pcm_loam_tile_count(ctx_, 1); }
+  void clear() { check(pcm_loam_tile_clear(ctx_), "pcm_loam_tile_clear"); }
+
+  bool needLoad(const float transformTobeMapped[6]) {
+    const int rc = pcm_loam_dynmap_need_load(ctx_, &params_, transformTobeMapped);
+    if (rc < 0) check(rc, "pcm_loam_dynmap_need_load");
+    return rc == 1;
+  }
+  // true: the selection changed
+  bool load(const float transformTobeMapped[6]) {
+    check(pcm_loam_dynmap_load(ctx_, &params_, transformTobeMapped, &load_), "pcm_loam_dynmap_load");
+    return load_.changed != 0;
+  }
+  // true: the maps were rebuilt; false: same tiles through the same window as the last call
+  bool dynamic_load_map(const float pose[6]) {
+    check(pcm_loam_dynmap_crop(ctx_, &params_, pose, &crop_), "pcm_loam_dynmap_crop");
+    return crop_.rebuilt != 0;
+  }
+  int laserCloudCornerFromMapDSNum() const { return crop_.num_corner; }
+  int laserCloudSurfFromMapDSNum() const { return crop_.num_surf; }
+
+  // globalMap as (x, y, z, intensity) records into a device buffer of `capacity` points (e.g. the target of an NDT context,
+  // then pcm_set_target with PCM_MEM_DEVICE and a stride of 16); returns the number of points
+  size_t globalMap(void* device_out, size_t capacity) {
+    size_t n = 0;
+    check(pcm_loam_dynmap_global(ctx_, device_out, capacity, &n, PCM_MEM_DEVICE), "pcm_loam_dynmap_global");
+    return n;
+  }
+  // globalMap as a PCL cloud on the host (publishCloud)
+  void globalMap(Cloud& out) {
+    const size_t cap = (size_t)crop_.num_corner + (size_t)crop_.num_surf;
+    if (buf_.size() < 4 * cap) buf_.resize(4 * cap);
+    size_t n = 0;
+    check(pcm_loam_dynmap_global(ctx_, buf_.data(), buf_.size() / 4, &n, PCM_MEM_HOST), "pcm_loam_dynmap_global");
+    out.points.resize(n);
+    for (size_t i = 0; i < n; i++) {
+      PointT& q = out.points[i];
+      q.x = buf_[4 * i]; q.y = buf_[4 * i + 1]; q.z = buf_[4 * i + 2]; q.intensity = buf_[4 * i + 3];
+    }
+  }
+
+private:
+  int add(int which, const double box[6], const Cloud& cloud) {
+    detail::pack_xyzi(cloud, buf_);
+    const int rc = pcm_loam_tile_add(ctx_, which, box, buf_.data(), cloud.points.size(), 4 * sizeof(float), PCM_MEM_HOST);
+    if (rc < 0) check(rc, "pcm_loam_tile_add");
+    return rc;
+  }
+  void check(int rc, const char* what) const {
+    if (rc != PCM_OK) throw std::runtime_error(std::string(what) + ": " + pcm_last_error(ctx_));
+  }
+  pcm_ctx* ctx_ = nullptr;
+  pcm_loam_dynmap_params params_;
+  pcm_loam_dynmap_load_result load_{};
+  pcm_loam_dynmap_crop_result crop_{};
+  std::vector<float> buf_;
+};
+
 // jueying_slam's SCManager (include/Scancontext.h) on the context of a LoamScanToMap, with SCManager's user-side names:
 //     scManager.makeAndSaveScancontextAndKeys(*thisRawCloudKeyFrame);           // saveKeyFramesAndFactor, mapOptmization.cpp:1857
 //     auto detectResult = scManager.detectLoopClosureID();                      // :741: (nearest node or -1, relative yaw)

@@ -14,3 +14,4 @@ from .registration import (GicpRegistration, NdtRegistration, P2PlaneRegistratio
 from .registration import LoamRegistration, LoamResult, LoamSubmapResult, LoamLoopResult, loam_align_batch  # noqa: F401
 from .registration import loam_extract_features, loam_frame_begin_batch, pack_xyzirt  # noqa: F401
 from .registration import OccupancyGrid, OccupancyMap2D, save_map  # noqa: F401
+from .registration import LoamMapLoadResult, LoamMapCropResult, read_arealist, write_arealist  # noqa: F401

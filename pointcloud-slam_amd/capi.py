@@ -23,6 +23,8 @@ SYMBOLS = [
     "pcm_loam_keyframe_get", "pcm_loam_submap_update", "pcm_loam_submap_near", "pcm_loam_submap_info",
     "pcm_loam_default_sc_params", "pcm_loam_sc_add", "pcm_loam_sc_put", "pcm_loam_sc_get", "pcm_loam_sc_count", "pcm_loam_sc_shape", "pcm_loam_sc_clear",
     "pcm_loam_sc_detect", "pcm_loam_sc_distance", "pcm_loam_loop_detect_distance",
+    "pcm_loam_default_dynmap_params", "pcm_loam_tile_add", "pcm_loam_tile_count", "pcm_loam_tile_clear", "pcm_loam_dynmap_need_load",
+    "pcm_loam_dynmap_load", "pcm_loam_dynmap_crop", "pcm_loam_dynmap_info", "pcm_loam_dynmap_global",
     "pcm_occ_default_params", "pcm_occ_reset", "pcm_occ_insert_scans", "pcm_occ_insert_keyframes", "pcm_occ_get_scan", "pcm_occ_status",
     "pcm_occ_info", "pcm_occ_get_map", "pcm_occ_get_pgm", "pcm_occ_get_counts",
 ]
@@ -151,6 +153,22 @@ class PcmLoamScResult(C.Structure):
                 ("cand_dist", C.c_double * 64), ("cand_shift", C.c_int32 * 64), ("reserved", C.c_int32 * 8)]
 
 
+class PcmLoamDynmapParams(C.Structure):
+    _fields_ = [("max_range", C.c_float), ("margin", C.c_int32), ("area_size", C.c_int32), ("crop_x", C.c_int32), ("reserved", C.c_int32 * 8)]
+
+
+class PcmLoamDynmapLoadResult(C.Structure):
+    _fields_ = [("num_corner_tiles", C.c_int32), ("num_surf_tiles", C.c_int32), ("num_corner_selected", C.c_int32), ("num_surf_selected", C.c_int32),
+                ("num_corner_points", C.c_int64), ("num_surf_points", C.c_int64), ("generation", C.c_uint64), ("changed", C.c_int32),
+                ("reserved", C.c_int32 * 5)]
+
+
+class PcmLoamDynmapCropResult(C.Structure):
+    _fields_ = [("num_corner_in", C.c_int32), ("num_surf_in", C.c_int32), ("num_corner", C.c_int32), ("num_surf", C.c_int32),
+                ("num_nonfinite", C.c_int32), ("rebuilt", C.c_int32), ("x_lo", C.c_float), ("x_hi", C.c_float), ("y_lo", C.c_float),
+                ("y_hi", C.c_float), ("status", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
 class PcmOccParams(C.Structure):
     _fields_ = [("min_z", C.c_double), ("max_z", C.c_double), ("angle_increment", C.c_double), ("min_range", C.c_double),
                 ("max_range", C.c_double), ("log_occ", C.c_double), ("log_free", C.c_double), ("resolution", C.c_double),
@@ -272,6 +290,16 @@ def load_library():
     L.pcm_loam_sc_detect.argtypes = [vp, C.POINTER(PcmLoamScParams), C.POINTER(PcmLoamScResult)]
     L.pcm_loam_sc_distance.argtypes = [vp, C.POINTER(PcmLoamScParams), i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     L.pcm_loam_loop_detect_distance.argtypes = [vp, C.c_float, C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.pcm_loam_default_dynmap_params.argtypes = [C.POINTER(PcmLoamDynmapParams)]
+    L.pcm_loam_default_dynmap_params.restype = None
+    L.pcm_loam_tile_add.argtypes = [vp, i32, vp, vp, sz, sz, i32]
+    L.pcm_loam_tile_count.argtypes = [vp, i32]
+    L.pcm_loam_tile_clear.argtypes = [vp]
+    L.pcm_loam_dynmap_need_load.argtypes = [vp, C.POINTER(PcmLoamDynmapParams), vp]
+    L.pcm_loam_dynmap_load.argtypes = [vp, C.POINTER(PcmLoamDynmapParams), vp, C.POINTER(PcmLoamDynmapLoadResult)]
+    L.pcm_loam_dynmap_crop.argtypes = [vp, C.POINTER(PcmLoamDynmapParams), vp, C.POINTER(PcmLoamDynmapCropResult)]
+    L.pcm_loam_dynmap_info.argtypes = [vp] * 5
+    L.pcm_loam_dynmap_global.argtypes = [vp, vp, sz, C.POINTER(sz), i32]
     L.pcm_occ_default_params.argtypes = [C.POINTER(PcmOccParams)]
     L.pcm_occ_default_params.restype = None
     L.pcm_occ_reset.argtypes = [vp, C.POINTER(PcmOccParams)]

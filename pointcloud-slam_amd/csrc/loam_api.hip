@@ -33,6 +33,8 @@ struct LoamCtx {
   bool tgt_from_submap = false;   // the target clouds are what loam_target_commit left
   void* keystore = nullptr;    // key frames and submap workspace (loam_submap.hip)
   void* scstore = nullptr;     // Scan Context descriptors and loop-detection workspace (loam_sc.hip)
+  bool tgt_from_dynmap = false;   // the target clouds are what loam_target_commit_dynmap left
+  void* dynstore = nullptr;    // localisation map tiles and crop workspace (loam_dynmap.hip)
   uint32_t n_c = 0, n_s = 0;
   DevBuf<double> partials;
   DevBuf<LoamState> st;
@@ -340,6 +342,7 @@ void loam_release(pcm_ctx* c) {
   for (int m = 0; m < 2; m++) L->map[m].release();
   if (L->keystore) loam::loam_keystore_release(L->keystore);
   if (L->scstore) loam::loam_scstore_release(L->scstore);
+  if (L->dynstore) loam::loam_dynstore_release(L->dynstore);
   delete L;
   c->loam = nullptr;
 }
@@ -374,6 +377,7 @@ int loam_target_reserve(pcm_ctx* c, size_t n_corner, size_t n_surf, float4** cor
   LoamCtx* L = loam_of(c);
   L->have_tgt = false;
   L->tgt_from_submap = false;
+  L->tgt_from_dynmap = false;
   L->built_cell = 0.f;
   L->map[0].valid = L->map[1].valid = false;
   L->map_n[0] = L->map_n[1] = 0;
@@ -426,6 +430,26 @@ void** loam_scstore_slot(pcm_ctx* c) {
   LoamCtx* L = loam_of(c);
   return L ? &L->scstore : nullptr;
 }
+
+void loam_target_commit_dynmap(pcm_ctx* c, uint32_t n_corner, uint32_t n_surf) {
+  loam_target_commit(c, n_corner, n_surf);
+  LoamCtx* L = loam_of(c);
+  L->tgt_from_submap = false;   // not the submap's: pcm_loam_submap_update must rebuild
+  L->tgt_from_dynmap = true;
+}
+
+bool loam_target_view_dynmap(pcm_ctx* c, const float4** corner, uint32_t* n_corner, const float4** surf, uint32_t* n_surf) {
+  LoamCtx* L = loam_of(c);
+  if (!L || !L->have_tgt || !L->tgt_from_dynmap) return false;
+  *corner = L->map_pts[0]; *n_corner = (uint32_t)L->map_n[0];
+  *surf = L->map_pts[1]; *n_surf = (uint32_t)L->map_n[1];
+  return true;
+}
+
+void** loam_dynstore_slot(pcm_ctx* c) {
+  LoamCtx* L = loam_of(c);
+  return L ? &L->dynstore : nullptr;
+}
 }  // namespace loam
 }  // namespace pcm
 
@@ -452,6 +476,7 @@ int pcm_loam_set_target(pcm_ctx* c, const void* corner, size_t n_c, const void* 
   PCM_HIPCK(c, hipSetDevice(c->device));
   L->have_tgt = false;
   L->tgt_from_submap = false;
+  L->tgt_from_dynmap = false;
   L->built_cell = 0.f;
   L->map[0].valid = L->map[1].valid = false;
   if ((rc = load_cloud(c, L, 0, corner, n_c, stride, memory)) != PCM_OK) return rc;

@@ -59,6 +59,13 @@ int loam_keyposes(pcm_ctx* c, const KeyPose** kp);
 // the Scan Context store of a context (pcm_ctx::loam owns the pointer, loam_sc.hip the type)
 void** loam_scstore_slot(pcm_ctx* c);
 void loam_scstore_release(void* store);
+// the localisation map tiles of a context (pcm_ctx::loam owns the pointer, loam_dynmap.hip the type); its crop writes the target
+// in place through loam_target_reserve and commits it as its own, so that neither it nor the submap mistakes the other's target
+// for the one it left
+void** loam_dynstore_slot(pcm_ctx* c);
+void loam_dynstore_release(void* store);
+void loam_target_commit_dynmap(pcm_ctx* c, uint32_t n_corner, uint32_t n_surf);
+bool loam_target_view_dynmap(pcm_ctx* c, const float4** corner, uint32_t* n_corner, const float4** surf, uint32_t* n_surf);
 
 // loam_features.hip: pieces of the segmented VoxelGrid that do not depend on where the elements live
 struct SvWork {

@@ -1120,3 +1120,171 @@ def _loam_occ_insert_keyframes(self, first: int = 0, n: int = None):
 for _name in ("occ_reset", "occ_insert_scans", "occ_scan", "occ_status", "_occ_info", "occ_map", "occ_pgm", "occ_counts", "occ_save_map"):
     setattr(LoamRegistration, _name, getattr(_OccMixin, _name))
 LoamRegistration.occ_insert_keyframes = _loam_occ_insert_keyframes
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# LOAM localisation map: area tiles and the per-frame crop on the device
+# ---------------------------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class LoamMapLoadResult:
+    num_corner_tiles: int
+    num_surf_tiles: int
+    num_corner_selected: int
+    num_surf_selected: int
+    num_corner_points: int
+    num_surf_points: int
+    generation: int
+    changed: bool
+
+
+@dataclasses.dataclass
+class LoamMapCropResult:
+    num_corner_in: int
+    num_surf_in: int
+    num_corner: int
+    num_surf: int
+    num_nonfinite: int
+    rebuilt: bool
+    x_lo: np.float32
+    x_hi: np.float32
+    y_lo: np.float32
+    y_hi: np.float32
+    status: int
+
+
+def _dynmap_params(L, params: dict) -> capi.PcmLoamDynmapParams:
+    p = capi.PcmLoamDynmapParams()
+    L.pcm_loam_default_dynmap_params(C.byref(p))
+    for k, v in params.items():
+        if k.startswith("reserved") or not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+_TILE_LIST = {0: 0, 1: 1, "corner": 0, "surf": 1}
+
+
+def _loam_add_tile(self, which, box, points) -> int:
+    """One area tile of the corner (0, "corner") or surf (1, "surf") list: box = (x_min, y_min, z_min, x_max, y_max, z_max) as in the
+    CSV area list, points an (N,>=3) array of x y z [intensity] in the map frame (N may be 0).  Returns the tile's index."""
+    b = np.ascontiguousarray(box, dtype=np.float64).reshape(6)
+    a = np.asarray(points, np.float32)
+    pts = _xyzi(a.reshape(0, 4) if a.size == 0 else a)
+    idx = self._L.pcm_loam_tile_add(self._h, _TILE_LIST[which], b.ctypes.data, pts.ctypes.data, pts.shape[0], 16, capi.MEM_HOST)
+    if idx < 0:
+        self._check(idx)
+    return idx
+
+
+def _loam_num_tiles(self, which) -> int:
+    n = self._L.pcm_loam_tile_count(self._h, _TILE_LIST[which])
+    if n < 0:
+        self._check(n)
+    return n
+
+
+def _loam_clear_tiles(self):
+    self._check(self._L.pcm_loam_tile_clear(self._h))
+    self._dm_load = self._dm_crop = None
+
+
+def _pose6(pose6):
+    return np.ascontiguousarray(pose6, dtype=np.float32).reshape(6)
+
+
+def _loam_need_map_load(self, pose6, **params) -> bool:
+    """dynamic_load_map_run's trigger: has the pose moved farther than area_size from the last load_map (pcm_loam_dynmap_need_load)."""
+    p = _dynmap_params(self._L, params)
+    x = _pose6(pose6)
+    rc = self._L.pcm_loam_dynmap_need_load(self._h, C.byref(p), x.ctypes.data)
+    if rc < 0:
+        self._check(rc)
+    return bool(rc)
+
+
+def _loam_load_map(self, pose6, **params) -> LoamMapLoadResult:
+    """create_pcd for both lists: selects the tiles around pose6 (margin) and records the pose; no points move (pcm_loam_dynmap_load)."""
+    p = _dynmap_params(self._L, params)
+    x = _pose6(pose6)
+    r = capi.PcmLoamDynmapLoadResult()
+    self._check(self._L.pcm_loam_dynmap_load(self._h, C.byref(p), x.ctypes.data, C.byref(r)))
+    self._dm_load = r
+    return LoamMapLoadResult(r.num_corner_tiles, r.num_surf_tiles, r.num_corner_selected, r.num_surf_selected, r.num_corner_points,
+                             r.num_surf_points, r.generation, bool(r.changed))
+
+
+def _loam_crop_map(self, pose6, **params) -> LoamMapCropResult:
+    """dynamic_load_map(pose6): the selected tiles through the frame's window become this context's target (pcm_loam_dynmap_crop)."""
+    p = _dynmap_params(self._L, params)
+    x = _pose6(pose6)
+    r = capi.PcmLoamDynmapCropResult()
+    self._check(self._L.pcm_loam_dynmap_crop(self._h, C.byref(p), x.ctypes.data, C.byref(r)))
+    self._dm_crop = r
+    return LoamMapCropResult(r.num_corner_in, r.num_surf_in, r.num_corner, r.num_surf, r.num_nonfinite, bool(r.rebuilt), np.float32(r.x_lo),
+                             np.float32(r.x_hi), np.float32(r.y_lo), np.float32(r.y_hi), r.status)
+
+
+def _loam_dynmap_info(self) -> dict:
+    """Parity hook: the selected tile indices of both lists and, after crop_map, the two cropped clouds (pcm_loam_dynmap_info)."""
+    ld, cr = getattr(self, "_dm_load", None), getattr(self, "_dm_crop", None)
+    if ld is None:
+        raise capi.PcmError(-2, "dynmap_info before load_map")
+    out = {"corner_tiles": np.zeros(ld.num_corner_selected, np.int32), "surf_tiles": np.zeros(ld.num_surf_selected, np.int32)}
+    ptrs = [out["corner_tiles"].ctypes.data, out["surf_tiles"].ctypes.data, None, None]
+    if cr is not None:
+        out["corner"] = np.zeros((cr.num_corner, 4), np.float32)
+        out["surf"] = np.zeros((cr.num_surf, 4), np.float32)
+        ptrs[2:] = [out["corner"].ctypes.data, out["surf"].ctypes.data]
+    self._check(self._L.pcm_loam_dynmap_info(self._h, *ptrs))
+    return out
+
+
+def _loam_global_map(self, out=None):
+    """globalMap = cropped corner ++ cropped surf as (M,4) x y z intensity.  Without ``out``: a host array.  With a contiguous (cap,4)
+    float32 CUDA tensor: written there without leaving the device, returns the number of points M (the NDT branch then passes
+    ``out[:M]`` to ``PclNdtRegistration.set_input_target``)."""
+    n = C.c_size_t(0)
+    if out is not None:
+        if not (hasattr(out, "data_ptr") and getattr(out, "is_cuda", False)) or str(out.dtype) != "torch.float32" or out.dim() != 2 or out.shape[1] != 4 \
+                or not out.is_contiguous():
+            raise ValueError("expected a contiguous (cap,4) float32 CUDA tensor")
+        self._check(self._L.pcm_loam_dynmap_global(self._h, out.data_ptr(), out.shape[0], C.byref(n), capi.MEM_DEVICE))
+        return n.value
+    cr = getattr(self, "_dm_crop", None)
+    if cr is None:
+        raise capi.PcmError(-2, "global_map before crop_map")
+    a = np.zeros((cr.num_corner + cr.num_surf, 4), np.float32)
+    self._check(self._L.pcm_loam_dynmap_global(self._h, a.ctypes.data, a.shape[0], C.byref(n), capi.MEM_HOST))
+    return a[:n.value]
+
+
+def write_arealist(path, areas):
+    """dynamic_map.h:90-106: one line per area, ``path,x_min,y_min,z_min,x_max,y_max,z_max``, the numbers as std::to_string writes
+    doubles (``%f``: 6 decimals).  areas: (path, (6 numbers)) pairs."""
+    with open(path, "w") as f:
+        for name, box in areas:
+            f.write(",".join([str(name)] + ["%f" % float(v) for v in box]) + "\n")
+
+
+def read_arealist(path):
+    """dynamic_map.h:37-88: lines split at commas, column 0 the PCD path, columns 1..6 through std::stod.  Returns a list of
+    (path, float64 array of 6) pairs in file order."""
+    areas = []
+    with open(path) as f:
+        for line in f.read().split("\n"):
+            if line == "":
+                continue
+            cols = line.split(",")
+            areas.append((cols[0], np.array([float(c) for c in cols[1:7]], np.float64)))
+    return areas
+
+
+LoamRegistration.add_tile = _loam_add_tile
+LoamRegistration.num_tiles = _loam_num_tiles
+LoamRegistration.clear_tiles = _loam_clear_tiles
+LoamRegistration.need_map_load = _loam_need_map_load
+LoamRegistration.load_map = _loam_load_map
+LoamRegistration.crop_map = _loam_crop_map
+LoamRegistration.dynmap_info = _loam_dynmap_info
+LoamRegistration.global_map = _loam_global_map

@@ -1,0 +1,258 @@
+"""CPU checks of the localisation map's host logic (pointcloud-slam_amd/csrc/loam_dynmap.h, compiled with g++ through
+tests/loam_dynmap_hooks.cpp) against the numpy restatement (tests/loam_dynmap_ref.py): tile selection, reload trigger, window
+limits and the crop predicate; of the synthetic tile layouts (asserted on the restatement alone); of read_arealist /
+write_arealist; and of the pcm_loam_dynmap_* struct layouts against the ctypes binding.  No GPU."""
+import ctypes as C
+import importlib
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import loam_dynmap_ref as R  # noqa: E402
+
+synth_tiles = importlib.import_module("pointcloud-slam_amd.synth_tiles")
+F = np.float32
+_TS = {}
+
+
+def tileset(seed):
+    if seed not in _TS:
+        _TS[seed] = synth_tiles.make_tiles(seed)
+    return _TS[seed]
+
+
+@pytest.fixture(scope="module")
+def H(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("dynmap_hooks") / "loam_dynmap_hooks.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I", os.path.join(ROOT, "pointcloud-slam_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "loam_dynmap_hooks.cpp"), "-o", so], check=True)
+    L = C.CDLL(so)
+    L.dynmap_hook_select.argtypes = [C.c_void_p, C.c_long, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_long]
+    L.dynmap_hook_select.restype = C.c_long
+    L.dynmap_hook_need_load.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.dynmap_hook_never_loaded.restype = C.c_float
+    L.dynmap_hook_limits.argtypes = [C.c_float, C.c_float, C.c_void_p]
+    L.dynmap_hook_window.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_void_p]
+    L.dynmap_hook_classes.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p]
+    L.dynmap_hook_layout.argtypes = [C.c_void_p]
+    return L
+
+
+def hook_select(H, boxes, p_x, p_y, margin):
+    boxes = np.ascontiguousarray(boxes, np.float64).reshape(-1, 6)
+    out = np.zeros(len(boxes) + 1, np.int32)
+    n = H.dynmap_hook_select(boxes.ctypes.data, len(boxes), float(F(p_x)), float(F(p_y)), float(margin), out.ctypes.data, out.size)
+    assert n >= 0
+    return out[:n].copy()
+
+
+def hook_need_load(H, pose, last, area_size):
+    pose = np.ascontiguousarray(pose, F); last = np.ascontiguousarray(last, F)
+    return bool(H.dynmap_hook_need_load(pose.ctypes.data, last.ctypes.data, int(area_size)))
+
+
+def bits(a):
+    return np.ascontiguousarray(a, F).view(np.uint32)
+
+
+def sample_poses(ts, seed):
+    """Poses over the map and a little outside it, some exactly on tile boxes."""
+    rng = np.random.default_rng(seed + 11)
+    span = ts.hi - ts.lo
+    xy = [ts.lo + rng.uniform(-0.2, 1.2, 2) * span for _ in range(12)]
+    for boxes in (ts.corner_boxes, ts.surf_boxes):
+        b = boxes[int(rng.integers(len(boxes)))]
+        xy += [np.array([b[3], b[1]]), np.array([b[0], b[4]])]
+    return [(F(p[0]), F(p[1])) for p in xy]
+
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2])
+@pytest.mark.parametrize("margin", [0, 10, 100, -1])
+def test_selection_matches_restatement(H, seed, margin):
+    ts = tileset(seed)
+    some = full = 0
+    for boxes in (ts.corner_boxes, ts.surf_boxes):
+        for p_x, p_y in sample_poses(ts, seed):
+            ref = R.select(boxes, p_x, p_y, margin)
+            got = hook_select(H, boxes, p_x, p_y, margin)
+            assert np.array_equal(got, ref)
+            assert np.all(np.diff(ref) > 0)   # list order
+            some += 0 < len(ref) < len(boxes)
+            full += len(ref) == len(boxes)
+    if margin in (0, 10):
+        assert some >= 4      # the layouts discriminate: neither nothing nor everything
+    if margin in (100, -1):
+        assert full >= 4
+    if margin < 0:
+        assert some == 0
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_layouts_have_what_the_tests_need(seed):
+    """On the generator alone: empty tiles, points exactly on their tile's box, two different lists."""
+    ts = tileset(seed)
+    for boxes, tiles in ts.lists():
+        assert sum(1 for t in tiles if len(t) == 0) >= 1 and sum(1 for t in tiles if len(t) > 0) >= 4
+        on_box = 0
+        for b, t in zip(boxes, tiles):
+            if len(t):
+                q = t[:, :3].astype(np.float64)
+                assert np.all(q >= b[:3]) and np.all(q <= b[3:])
+                on_box += int((q[:, 0] == b[3]).sum() + (q[:, 1] == b[1]).sum())
+        assert on_box >= 4
+    assert len(ts.corner_tiles) != len(ts.surf_tiles)
+    assert not np.array_equal(ts.corner_boxes[:4], ts.surf_boxes[:4])
+    # the surf list is not sorted by position: list order is not spatial order
+    assert np.any(np.diff(ts.surf_boxes[:, 1] * 1e3 + ts.surf_boxes[:, 0]) < 0)
+
+
+def test_box_edges_are_inside(H):
+    """is_in_area is inclusive in double: a pose exactly on x_max + m or on y_min - m is inside, one float ulp beyond is outside."""
+    box = np.array([[-3.0, 3.25, 0.0, 12.5, 9.0, 2.0]])
+    for fn in (lambda *a: list(hook_select(H, *a)), lambda *a: list(R.select(*a))):
+        for m in (0, 10, 100):
+            xe, ye = F(12.5 + m), F(3.25 - m)   # both exact in float
+            assert float(xe) == 12.5 + m and float(ye) == 3.25 - m
+            assert fn(box, xe, F(5.0), m) == [0]
+            assert fn(box, np.nextafter(xe, F(np.inf)), F(5.0), m) == []
+            assert fn(box, F(0.0), ye, m) == [0]
+            assert fn(box, F(0.0), np.nextafter(ye, F(-np.inf)), m) == []
+            assert fn(box, xe, ye, m) == [0]
+        # z is never tested, and a negative margin takes everything
+        assert fn(np.array([[0.0, 0.0, 50.0, 1.0, 1.0, 60.0]]), F(0.5), F(0.5), 0) == [0]
+        assert fn(box, F(1e6), F(-1e6), -1) == [0]
+    # the true box of a synthetic tile: the float coordinate of its extreme point is on the box
+    ts = tileset(0)
+    k = next(i for i, t in enumerate(ts.corner_tiles) if len(t))
+    b = ts.corner_boxes[k]
+    xe, ym = F(b[3]), F(0.5 * (b[1] + b[4]))
+    assert float(xe) == b[3]
+    assert k in hook_select(H, ts.corner_boxes, xe, ym, 0) and k in R.select(ts.corner_boxes, xe, ym, 0)
+    beyond = np.nextafter(xe, F(np.inf))
+    assert k not in hook_select(H, ts.corner_boxes, beyond, ym, 0) and k not in R.select(ts.corner_boxes, beyond, ym, 0)
+
+
+def test_list_order_with_empty_tiles(H):
+    """Overlapping boxes in a scrambled list: the indices come in list order, empty tiles among them."""
+    boxes = np.array([[5, 0, 0, 9, 4, 1], [0, 0, 0, 6, 4, 1], [20, 0, 0, 30, 4, 1], [4, 1, 0, 7, 3, 1], [0, 0, 0, 10, 10, 1]], np.float64)
+    for fn in (lambda *a: list(hook_select(H, *a)), lambda *a: list(R.select(*a))):
+        assert fn(boxes, F(5.5), F(2.0), 0) == [0, 1, 3, 4]
+        assert fn(boxes, F(15.0), F(2.0), 5) == [2, 4]
+        assert fn(boxes, F(15.0), F(2.0), 0) == []
+    tiles = [np.full((2, 4), k, F) for k in range(5)]
+    tiles[1] = np.zeros((0, 4), F)
+    got = R.concat(tiles, R.select(boxes, F(5.5), F(2.0), 0))
+    assert list(got[:, 0]) == [0, 0, 3, 3, 4, 4]
+
+
+def test_reload_trigger(H):
+    never = H.dynmap_hook_never_loaded()
+    assert F(never) == R.NEVER == F(-999999.0)
+    last = np.zeros(6, F)
+    for fn in (lambda *a: hook_need_load(H, *a), R.need_load):
+        # load_distance == area_size: no load (3-4-5 and a single axis)
+        assert fn([0, 0, 0, 3, 4, 0], last, 5) is False
+        assert fn([9, 9, 9, 0, 0, 5], last, 5) is False   # the angles do not count
+        up = np.nextafter(F(5.0), F(np.inf))
+        assert fn([0, 0, 0, 0, 0, up], last, 5) is True    # sqrt(fl(z * z)) == z: one float ulp above
+        assert fn([0, 0, 0, up, 0, 0], last, 5) is True
+        assert fn([0, 0, 0, np.nextafter(F(5.0), F(0.0)), 0, 0], last, 5) is False
+        # the first call always loads
+        first = np.full(6, never, F)
+        for area_size in (-1, 0, 50, 1000):
+            assert fn([0, 0, 0, 0, 0, 0], first, area_size) is True
+            assert fn([0, 0, 0, 812.5, -40.25, 3.0], first, area_size) is True
+        # area_size -1 (the default): every later call loads too, even without moving (0 > -1)
+        assert fn([0, 0, 0, 1, 2, 3], [0, 0, 0, 1, 2, 3], -1) is True
+        assert fn([0, 0, 0, 1, 2, 3], [0, 0, 0, 1, 2, 3], 0) is False
+    rng = np.random.default_rng(3)
+    for _ in range(200):
+        pose = rng.uniform(-60, 60, 6).astype(F); lastp = rng.uniform(-60, 60, 6).astype(F)
+        a = int(rng.integers(0, 120))
+        assert hook_need_load(H, pose, lastp, a) == R.need_load(pose, lastp, a)
+
+
+def test_limit_arithmetic(H):
+    out = np.zeros(2, F)
+    H.dynmap_hook_limits(float(F(0.1)), 80.0, out.ctypes.data)
+    # the float nearest to the double expression, computed here from the definition
+    lo = F(float(F(0.1)) - 80.0 * 1.1)
+    hi = F(float(F(0.1)) + 80.0 * 1.1)
+    assert bits(out)[0] == bits(lo)[0] and bits(out)[1] == bits(hi)[0]
+    assert (bits(R.limits(F(0.1), 80.0)[0])[0], bits(R.limits(F(0.1), 80.0)[1])[0]) == (bits(lo)[0], bits(hi)[0])
+    rng = np.random.default_rng(4)
+    for _ in range(300):
+        v, mr = F(rng.uniform(-500, 500)), F(rng.uniform(1, 200))
+        H.dynmap_hook_limits(float(v), float(mr), out.ctypes.data)
+        assert np.array_equal(bits(out), bits(np.array(R.limits(v, mr))))
+    pose = np.array([0, 0, 0, 12.25, -7.5, 1.0], F)
+    w = np.zeros(4, F)
+    H.dynmap_hook_window(pose.ctypes.data, 150.0, 10, 0, w.ctypes.data)
+    assert np.array_equal(bits(w), bits(np.array(R.window(pose, 150.0, 10))))
+    H.dynmap_hook_window(pose.ctypes.data, 150.0, -1, 0, w.ctypes.data)
+    assert list(w) == [-np.inf, np.inf, -np.inf, np.inf] and list(R.window(pose, 150.0, -1)) == list(w)
+
+
+@pytest.mark.parametrize("crop_x", [0, 1])
+def test_predicate(H, crop_x):
+    win = np.array(R.limits(F(3.0), 20.0) + R.limits(F(0.1), 20.0), F)
+    x_lo, x_hi, y_lo, y_hi = win
+    rng = np.random.default_rng(5)
+    pts = np.zeros((400, 4), F)
+    pts[:, 0] = rng.uniform(-60, 60, 400); pts[:, 1] = rng.uniform(-60, 60, 400); pts[:, 2] = rng.uniform(-5, 5, 400)
+    edge = [(F(3.0), y_lo), (F(3.0), y_hi), (F(3.0), np.nextafter(y_lo, F(-np.inf))), (F(3.0), np.nextafter(y_hi, F(np.inf))),
+            (x_lo, F(0.0)), (x_hi, F(0.0)), (np.nextafter(x_lo, F(-np.inf)), F(0.0)), (np.nextafter(x_hi, F(np.inf)), F(0.0))]
+    for k, (x, y) in enumerate(edge):
+        pts[k, 0], pts[k, 1] = x, y
+    for k, (col, v) in enumerate([(c, v) for c in (0, 1, 2) for v in (np.nan, np.inf, -np.inf)]):
+        pts[20 + k, col] = v
+    pts[30, 3] = np.nan   # the intensity is not a coordinate
+    cls = np.zeros(len(pts), np.int32)
+    H.dynmap_hook_classes(pts.ctypes.data, len(pts), win.ctypes.data, crop_x, cls.ctypes.data)
+    kept, nonfinite = R.crop_cloud(pts, tuple(win), crop_x)
+    assert np.array_equal(bits(pts[cls == 1]), bits(kept)) and int((cls == 2).sum()) == nonfinite == 9
+    assert list(cls[:4]) == [1, 1, 0, 0]
+    assert list(cls[4:8]) == ([1, 1, 0, 0] if crop_x else [1, 1, 1, 1])
+    assert cls[30] == (1 if (y_lo <= pts[30, 1] <= y_hi and (not crop_x or x_lo <= pts[30, 0] <= x_hi)) else 0)
+
+
+def test_arealist_round_trip(tmp_path, pcm):
+    ts = tileset(1)
+    areas = [("tile_%03d.pcd" % k, b) for k, b in enumerate(ts.surf_boxes)]
+    areas.append(("sub dir/odd name.pcd", np.array([-1234567.125, 0.0000004, 1e-7, 2.5, 1e6 + 0.1234567, -0.0])))
+    path = str(tmp_path / "arealist.csv")
+    pcm.write_arealist(path, areas)
+    lines = open(path).read().split("\n")
+    assert lines[-1] == "" and len(lines) == len(areas) + 1
+    assert lines[0] == ",".join(["tile_000.pcd"] + ["%.6f" % v for v in ts.surf_boxes[0]])   # std::to_string(double): %f
+    assert lines[-2] == "sub dir/odd name.pcd,-1234567.125000,0.000000,0.000000,2.500000,1000000.123457,-0.000000"
+    back = pcm.read_arealist(path)
+    assert [n for n, _ in back] == [n for n, _ in areas]
+    for (_, b), (_, a) in zip(back, areas):
+        assert b.dtype == np.float64 and np.array_equal(b, np.array([float("%.6f" % v) for v in a]))
+    # written again, the file is the same: the text is a fixed point
+    path2 = str(tmp_path / "again.csv")
+    pcm.write_arealist(path2, back)
+    assert open(path2).read() == open(path).read()
+
+
+def test_struct_layouts(H, pcm):
+    capi = pcm.capi
+    got = np.zeros(22, np.int64)
+    H.dynmap_hook_layout(got.ctypes.data)
+    P, Ld, Cr = capi.PcmLoamDynmapParams, capi.PcmLoamDynmapLoadResult, capi.PcmLoamDynmapCropResult
+    want = [C.sizeof(P), P.margin.offset, P.area_size.offset, P.crop_x.offset, P.reserved.offset,
+            C.sizeof(Ld), Ld.num_surf_selected.offset, Ld.num_corner_points.offset, Ld.num_surf_points.offset, Ld.generation.offset, Ld.changed.offset,
+            Ld.reserved.offset, C.sizeof(Cr), Cr.num_surf.offset, Cr.num_nonfinite.offset, Cr.rebuilt.offset, Cr.x_lo.offset, Cr.y_hi.offset,
+            Cr.status.offset, Cr.reserved.offset, 48, capi.PCM_ABI_VERSION]
+    assert list(got) == want
+    assert C.sizeof(P) == 48 and C.sizeof(Ld) == 64 and C.sizeof(Cr) == 64
+    for name in ("pcm_loam_default_dynmap_params", "pcm_loam_tile_add", "pcm_loam_tile_count", "pcm_loam_tile_clear", "pcm_loam_dynmap_need_load",
+                 "pcm_loam_dynmap_load", "pcm_loam_dynmap_crop", "pcm_loam_dynmap_info", "pcm_loam_dynmap_global"):
+        assert name in capi.SYMBOLS
