@@ -1277,43 +1277,36 @@ int gicp_bfgs_correspond_device(hipStream_t stream, const TargetMap& tmap, int c
   char* tmp = nullptr;
   void* scan_tmp = nullptr;
   size_t scan_bytes = 0;
-  int rc = PCM_OK;
   uint32_t tails[2] = {0, 0};
   TargetView tg{};
   tg.pts = tmap.pts; tg.vox_start = tmap.vox_start; tg.bricks = tmap.bricks; tg.bmask = tmap.bmask; tg.bpref = tmap.bpref; tg.gvox = tmap.gvox;
   tg.mask = tmap.cap - 1; tg.num_points = tmap.num_points; tg.inv_res = tmap.inv_res; tg.res = tmap.res;
-#define CK(x)                                                                    \
-  do {                                                                           \
-    hipError_t e_ = (x);                                                         \
-    if (e_ != hipSuccess) { *err = std::string(#x) + ": " + hipGetErrorString(e_); rc = PCM_ERR_HIP; goto done; } \
-  } while (0)
-  {
+  const int rc = [&]() -> int {
     const size_t b_flag = ((size_t)n * 4 + 255) & ~(size_t)255, b_rec = (size_t)n * 64, b_idx = b_flag;
-    CK(hipMallocAsync(reinterpret_cast<void**>(&tmp), 2 * b_flag + b_rec + b_idx, stream));
+    PCM_HIPCK_ERR(err, hipMallocAsync(reinterpret_cast<void**>(&tmp), 2 * b_flag + b_rec + b_idx, stream));
     uint32_t* flag = reinterpret_cast<uint32_t*>(tmp);
     uint32_t* pos = reinterpret_cast<uint32_t*>(tmp + b_flag);
     float4* rec = reinterpret_cast<float4*>(tmp + 2 * b_flag);
     int32_t* tidx = reinterpret_cast<int32_t*>(tmp + 2 * b_flag + b_rec);
     k_bfgs_correspond<<<(n + 255u) / 256u, 256, 0, stream>>>(tg, coord_mode, smap.pts, smap.order, n, src_cov, tgt_cov, tmap.order, X, flag, rec, tidx);
-    CK(hipGetLastError());
-    CK(rocprim::exclusive_scan(nullptr, scan_bytes, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-    CK(hipMallocAsync(&scan_tmp, scan_bytes, stream));
-    CK(rocprim::exclusive_scan(scan_tmp, scan_bytes, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-    CK(hipMemcpyAsync(&tails[0], flag + (n - 1), 4, hipMemcpyDeviceToHost, stream));
-    CK(hipMemcpyAsync(&tails[1], pos + (n - 1), 4, hipMemcpyDeviceToHost, stream));
-    CK(hipStreamSynchronize(stream));
+    PCM_HIPCK_ERR(err, hipGetLastError());
+    PCM_HIPCK_ERR(err, rocprim::exclusive_scan(nullptr, scan_bytes, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
+    PCM_HIPCK_ERR(err, hipMallocAsync(&scan_tmp, scan_bytes, stream));
+    PCM_HIPCK_ERR(err, rocprim::exclusive_scan(scan_tmp, scan_bytes, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
+    PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[0], flag + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+    PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[1], pos + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+    PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
     const uint32_t m = tails[0] + tails[1];
     if (m) {
       k_bfgs_compact<<<(n + 255u) / 256u, 256, 0, stream>>>(flag, pos, rec, tidx, n, m, d_records, d_idx_src, d_idx_tgt);
-      CK(hipGetLastError());
+      PCM_HIPCK_ERR(err, hipGetLastError());
     }
     *m_out = m;
-  }
-done:
+    return PCM_OK;
+  }();
   if (tmp) (void)hipFreeAsync(tmp, stream);
   if (scan_tmp) (void)hipFreeAsync(scan_tmp, stream);
   return rc;
-#undef CK
 }
 
 void launch_fitness(hipStream_t stream, const TargetView& tg, int coord_mode, const float4* src, uint32_t n, const float* T, double max_range, double* d_out) {

@@ -183,13 +183,6 @@ TargetView view_of_map(const TargetMap& m) {
 
 }  // namespace
 
-void NeighbourLists::release() {
-  index.release();
-  if (start) hipFree(start);
-  if (pts) hipFree(pts);
-  start = nullptr; pts = nullptr; start_cap = 0; pts_cap = 0; num_lists = 0; num_candidates = 0; num_neighbors = 0; valid = false; kind = 0;
-}
-
 TargetView view_of_lists(const NeighbourLists& l) {
   TargetView v = view_of_map(l.index);
   v.pts = l.pts;
@@ -225,94 +218,75 @@ int build_neighbour_lists(hipStream_t stream, const TargetMap& map, int nn, Neig
   void *tmp = nullptr, *tmp2 = nullptr, *tmp3 = nullptr;
   size_t tmp_bytes = 0, tmp2_bytes = 0, tmp3_bytes = 0;
   uint32_t h_cnt[2] = {0, 0};
-  int rc = PCM_OK;
-#define CK(x)                                                                    \
-  do {                                                                           \
-    hipError_t e_ = (x);                                                         \
-    if (e_ != hipSuccess) { *err = std::string(#x) + ": " + hipGetErrorString(e_); rc = PCM_ERR_HIP; goto done; } \
-  } while (0)
-  {
+  // the build proper; its temporaries go back to the stream's pool behind it
+  const int rc = [&]() -> int {
     const unsigned nb = (unsigned)((nk + 255) / 256);
-    CK(hipMallocAsync(reinterpret_cast<void**>(&keys), sizeof(uint64_t) * nk, stream));
-    CK(hipMallocAsync(reinterpret_cast<void**>(&keys_s), sizeof(uint64_t) * nk, stream));
-    CK(hipMallocAsync(reinterpret_cast<void**>(&flag), sizeof(uint32_t) * nk, stream));
-    CK(hipMallocAsync(reinterpret_cast<void**>(&pos), sizeof(uint32_t) * nk, stream));
-    CK(hipMallocAsync(reinterpret_cast<void**>(&d_cnt), sizeof(uint32_t) * 2, stream));
+    PCM_HIPCK_ERR(err, hipMallocAsync(reinterpret_cast<void**>(&keys), sizeof(uint64_t) * nk, stream));
+    PCM_HIPCK_ERR(err, hipMallocAsync(reinterpret_cast<void**>(&keys_s), sizeof(uint64_t) * nk, stream));
+    PCM_HIPCK_ERR(err, hipMallocAsync(reinterpret_cast<void**>(&flag), sizeof(uint32_t) * nk, stream));
+    PCM_HIPCK_ERR(err, hipMallocAsync(reinterpret_cast<void**>(&pos), sizeof(uint32_t) * nk, stream));
+    PCM_HIPCK_ERR(err, hipMallocAsync(reinterpret_cast<void**>(&d_cnt), sizeof(uint32_t) * 2, stream));
     k_nl_keys<<<(nvox + 255) / 256, 256, 0, stream>>>(map.pts, map.vox_start, nvox, map.res, map.inv_res, mode, nset, keys);
-    CK(hipGetLastError());
-    CK(rocprim::radix_sort_keys(nullptr, tmp_bytes, keys, keys_s, nk, 0, 64, stream));
-    CK(hipMallocAsync(&tmp, tmp_bytes, stream));
-    CK(rocprim::radix_sort_keys(tmp, tmp_bytes, keys, keys_s, nk, 0, 64, stream));
+    PCM_HIPCK_ERR(err, hipGetLastError());
+    PCM_HIPCK_ERR(err, rocprim::radix_sort_keys(nullptr, tmp_bytes, keys, keys_s, nk, 0, 64, stream));
+    PCM_HIPCK_ERR(err, hipMallocAsync(&tmp, tmp_bytes, stream));
+    PCM_HIPCK_ERR(err, rocprim::radix_sort_keys(tmp, tmp_bytes, keys, keys_s, nk, 0, 64, stream));
     k_nl_flags<<<nb, 256, 0, stream>>>(keys_s, (uint32_t)nk, flag);
-    CK(hipGetLastError());
-    CK(rocprim::exclusive_scan(nullptr, tmp2_bytes, flag, pos, 0u, nk, rocprim::plus<uint32_t>(), stream));
-    CK(hipMallocAsync(&tmp2, tmp2_bytes, stream));
-    CK(rocprim::exclusive_scan(tmp2, tmp2_bytes, flag, pos, 0u, nk, rocprim::plus<uint32_t>(), stream));
-    CK(hipMallocAsync(reinterpret_cast<void**>(&centres), sizeof(float4) * nk, stream));   // at most one per key
+    PCM_HIPCK_ERR(err, hipGetLastError());
+    PCM_HIPCK_ERR(err, rocprim::exclusive_scan(nullptr, tmp2_bytes, flag, pos, 0u, nk, rocprim::plus<uint32_t>(), stream));
+    PCM_HIPCK_ERR(err, hipMallocAsync(&tmp2, tmp2_bytes, stream));
+    PCM_HIPCK_ERR(err, rocprim::exclusive_scan(tmp2, tmp2_bytes, flag, pos, 0u, nk, rocprim::plus<uint32_t>(), stream));
+    PCM_HIPCK_ERR(err, hipMallocAsync(reinterpret_cast<void**>(&centres), sizeof(float4) * nk, stream));   // at most one per key
     k_nl_centres<<<nb, 256, 0, stream>>>(keys_s, flag, pos, (uint32_t)nk, map.res, mode == COORD_ROUND ? 0.f : mode == COORD_FLOOR_MUL ? 0.5f : 1.0f, centres, d_cnt);
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(&h_cnt[0], d_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    CK(hipStreamSynchronize(stream));
+    PCM_HIPCK_ERR(err, hipGetLastError());
+    PCM_HIPCK_ERR(err, hipMemcpyAsync(&h_cnt[0], d_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
     uint32_t nd = h_cnt[0];
-    if (nd == 0) { *err = "neighbour lists: empty map"; rc = PCM_ERR_NO_INPUT; goto done; }
+    if (nd == 0) { *err = "neighbour lists: empty map"; return PCM_ERR_NO_INPUT; }
     // the list index: a brick hash over the stand-in points (one per dilated voxel)
-    rc = build_target_map(stream, centres, &nd, map.res, mode, false, 0u, &out->index, err);
-    if (rc != PCM_OK) goto done;
-    if (out->index.num_voxels != nd || out->index.num_points != nd) { *err = "neighbour lists: index does not hold one voxel per list"; rc = PCM_ERR_INTERNAL; goto done; }
+    int rc = build_target_map(stream, centres, &nd, map.res, mode, false, 0u, &out->index, err);
+    if (rc != PCM_OK) return rc;
+    if (out->index.num_voxels != nd || out->index.num_points != nd) { *err = "neighbour lists: index does not hold one voxel per list"; return PCM_ERR_INTERNAL; }
     if (voxel_slots) {   // a fixed row of nn voxel indices per list voxel, kept in the `pts` allocation
       const size_t words = (size_t)nd * nn, cells = (words + 3) / 4 + 4;
-      if (out->pts_cap < cells) {
-        if (out->pts) hipFree(out->pts);
-        out->pts = nullptr; out->pts_cap = 0;
-        CK(hipMalloc(reinterpret_cast<void**>(&out->pts), sizeof(float4) * cells));
-        out->pts_cap = cells;
-      }
-      k_nl_voxel_slots<<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of_map(map), mode, nn, reinterpret_cast<int32_t*>(out->pts));
-      CK(hipGetLastError());
-      CK(hipStreamSynchronize(stream));
+      if ((rc = out->pts.reserve(stream, err, cells, cells)) != PCM_OK) return rc;
+      k_nl_voxel_slots<<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of_map(map), mode, nn, reinterpret_cast<int32_t*>(out->pts.p));
+      PCM_HIPCK_ERR(err, hipGetLastError());
+      PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
       out->num_lists = nd;
       out->num_candidates = words;
       out->num_neighbors = nn;
       out->kind = 2;
       out->valid = true;
-      goto done;
+      return PCM_OK;
     }
     // list lengths -> starts -> candidates
-    if (out->start_cap < (size_t)nd + 1) {
-      if (out->start) hipFree(out->start);
-      out->start = nullptr; out->start_cap = 0;
-      CK(hipMalloc(reinterpret_cast<void**>(&out->start), sizeof(uint32_t) * ((size_t)nd + 1)));
-      out->start_cap = (size_t)nd + 1;
-    }
-    CK(hipMallocAsync(reinterpret_cast<void**>(&len), sizeof(uint32_t) * ((size_t)nd + 1), stream));
-    CK(hipMemsetAsync(len, 0, sizeof(uint32_t) * ((size_t)nd + 1), stream));
+    if ((rc = out->start.reserve(stream, err, (size_t)nd + 1, (size_t)nd + 1)) != PCM_OK) return rc;
+    PCM_HIPCK_ERR(err, hipMallocAsync(reinterpret_cast<void**>(&len), sizeof(uint32_t) * ((size_t)nd + 1), stream));
+    PCM_HIPCK_ERR(err, hipMemsetAsync(len, 0, sizeof(uint32_t) * ((size_t)nd + 1), stream));
     if (ndt_leaves) k_nl_leaf_lists<false><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of_map(map), mode, ndt_leaves, nn, len, nullptr, nullptr);
     else k_nl_lists<false><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of_map(map), nn, len, nullptr, nullptr);
-    CK(hipGetLastError());
-    CK(rocprim::exclusive_scan(nullptr, tmp3_bytes, len, out->start, 0u, (size_t)nd + 1, rocprim::plus<uint32_t>(), stream));
-    CK(hipMallocAsync(&tmp3, tmp3_bytes, stream));
-    CK(rocprim::exclusive_scan(tmp3, tmp3_bytes, len, out->start, 0u, (size_t)nd + 1, rocprim::plus<uint32_t>(), stream));
-    CK(hipMemcpyAsync(&h_cnt[1], out->start + nd, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    CK(hipStreamSynchronize(stream));
+    PCM_HIPCK_ERR(err, hipGetLastError());
+    PCM_HIPCK_ERR(err, rocprim::exclusive_scan(nullptr, tmp3_bytes, len, out->start.p, 0u, (size_t)nd + 1, rocprim::plus<uint32_t>(), stream));
+    PCM_HIPCK_ERR(err, hipMallocAsync(&tmp3, tmp3_bytes, stream));
+    PCM_HIPCK_ERR(err, rocprim::exclusive_scan(tmp3, tmp3_bytes, len, out->start.p, 0u, (size_t)nd + 1, rocprim::plus<uint32_t>(), stream));
+    PCM_HIPCK_ERR(err, hipMemcpyAsync(&h_cnt[1], out->start + nd, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
     const size_t total = h_cnt[1];
-    if (out->pts_cap < total + 4) {   // + 4: the walk of k_linearize_lists reads (never uses) up to three entries past a run
-      if (out->pts) hipFree(out->pts);
-      out->pts = nullptr; out->pts_cap = 0;
-      CK(hipMalloc(reinterpret_cast<void**>(&out->pts), sizeof(float4) * (total + 4)));
-      out->pts_cap = total + 4;
-    }
-    CK(hipMemsetAsync(out->pts + total, 0, sizeof(float4) * 4, stream));
+    // + 4: the walk of k_linearize_lists reads (never uses) up to three entries past a run
+    if ((rc = out->pts.reserve(stream, err, total + 4, total + 4)) != PCM_OK) return rc;
+    PCM_HIPCK_ERR(err, hipMemsetAsync(out->pts + total, 0, sizeof(float4) * 4, stream));
     if (ndt_leaves) k_nl_leaf_lists<true><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of_map(map), mode, ndt_leaves, nn, nullptr, out->start, out->pts);
     else k_nl_lists<true><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of_map(map), nn, nullptr, out->start, out->pts);
-    CK(hipGetLastError());
-    CK(hipStreamSynchronize(stream));
+    PCM_HIPCK_ERR(err, hipGetLastError());
+    PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
     out->num_lists = nd;
     out->num_candidates = total;
     out->num_neighbors = nn;
     out->kind = ndt_leaves ? 1 : 0;
     out->valid = true;
-  }
-done:
+    return PCM_OK;
+  }();
   if (keys) (void)hipFreeAsync(keys, stream);
   if (keys_s) (void)hipFreeAsync(keys_s, stream);
   if (flag) (void)hipFreeAsync(flag, stream);
@@ -325,7 +299,6 @@ done:
   if (tmp3) (void)hipFreeAsync(tmp3, stream);
   if (rc != PCM_OK) out->valid = false;
   return rc;
-#undef CK
 }
 
 // ---------------------------------------------------------------------------

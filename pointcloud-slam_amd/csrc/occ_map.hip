@@ -214,6 +214,7 @@ int ensure_rect(pcm_ctx* c, OccMap* M, long long lx, long long hx, long long ly,
     M->R = N;
     return PCM_OK;
   }
+  // a growth that is more than a copy (the old rectangle moves into its place in the new one): allocated here, adopted below
   uint2* nc = nullptr;
   PCM_HIPCK(c, hipMalloc(reinterpret_cast<void**>(&nc), sizeof(uint2) * n));
   hipError_t e = hipMemsetAsync(nc, 0, sizeof(uint2) * n, c->stream);

@@ -26,22 +26,18 @@ namespace {
 // grow-only device workspace shared by the batch launches of one device
 struct Workspace {
   int device = -1;
-  PairDesc* d_descs = nullptr;
-  PairState* d_states = nullptr;
-  float* d_guesses = nullptr;
-  pcm_result* d_results = nullptr;
-  double* d_partials = nullptr;
-  double* d_sums = nullptr;
-  unsigned char* d_flags = nullptr;  // device view of h_flags
-  unsigned char* h_flags = nullptr;  // mapped pinned host memory: [round][pair] status bytes written by k_finish_round
-  size_t cap_flags = 0;
-  unsigned long long* d_stats = nullptr;
-  unsigned int* d_queue = nullptr;   // batch window: index of the next queued pair
-  SortJob* d_jobs = nullptr;
+  DevBuf<PairDesc> d_descs{"d_descs"};      // the per-pair arrays grow together (ensure_ws)
+  DevBuf<PairState> d_states{"d_states"};
+  DevBuf<float> d_guesses{"d_guesses"};     // 16 per pair
+  DevBuf<pcm_result> d_results{"d_results"};
+  DevBuf<double> d_partials{"d_partials"};
+  DevBuf<double> d_sums{"d_sums"};          // kPartialStride per pair
+  PinnedBuf<unsigned char> h_flags{"h_flags"};   // mapped pinned host memory: [round][pair] status bytes written by k_finish_round
+  unsigned char* d_flags = nullptr;              // device view of h_flags
+  DevBuf<unsigned long long> d_stats{"d_stats"};
+  DevBuf<unsigned int> d_queue{"d_queue"};   // batch window: index of the next queued pair
+  DevBuf<SortJob> d_jobs{"d_jobs"};
   SortScratch sort;
-  int cap_pairs = 0;
-  size_t cap_partials = 0;
-  int cap_rounds = 0;
   std::vector<hipEvent_t> ev_round;
   std::vector<hipEvent_t> ev_prof;
 };
@@ -74,38 +70,27 @@ int ensure_ws(pcm_ctx* c, Workspace** out, int npairs, size_t partial_doubles, i
   if (!c->ws) { c->err = "out of host memory"; return PCM_ERR_HIP; }
   Workspace& w = *static_cast<Workspace*>(c->ws);
   w.device = c->device;
-  if (npairs > w.cap_pairs) {
-    if (w.d_descs) { hipFree(w.d_descs); hipFree(w.d_states); hipFree(w.d_guesses); hipFree(w.d_results); hipFree(w.d_sums); hipFree(w.d_jobs); }
-    // a failed hipMalloc below returns at once (PCM_HIPCK): nothing freed here may stay reachable, or a retry / pcm_destroy frees it twice
-    w.d_descs = nullptr; w.d_states = nullptr; w.d_guesses = nullptr; w.d_results = nullptr; w.d_sums = nullptr; w.d_jobs = nullptr;
-    w.cap_pairs = 0;
-    const int cap = std::max(npairs, 64);
-    PCM_HIPCK(c, hipMalloc(&w.d_descs, sizeof(PairDesc) * cap));
-    PCM_HIPCK(c, hipMalloc(&w.d_states, sizeof(PairState) * cap));
-    PCM_HIPCK(c, hipMalloc(&w.d_guesses, sizeof(float) * 16 * cap));
-    PCM_HIPCK(c, hipMalloc(&w.d_results, sizeof(pcm_result) * cap));
-    PCM_HIPCK(c, hipMalloc(&w.d_sums, sizeof(double) * kPartialStride * cap));
-    PCM_HIPCK(c, hipMalloc(&w.d_jobs, sizeof(SortJob) * cap));
-    w.cap_pairs = cap;
-  }
-  if (partial_doubles > w.cap_partials) {
-    if (w.d_partials) hipFree(w.d_partials);
-    w.d_partials = nullptr; w.cap_partials = 0;
-    PCM_HIPCK(c, hipMalloc(&w.d_partials, sizeof(double) * partial_doubles));
-    w.cap_partials = partial_doubles;
-  }
-  if ((size_t)rounds * (size_t)std::max(npairs, 64) > w.cap_flags) {
-    if (w.h_flags) hipHostFree(w.h_flags);
-    w.h_flags = nullptr; w.cap_flags = 0;
-    const size_t bytes = (size_t)rounds * (size_t)std::max(npairs, 64);
+  const size_t np = (size_t)npairs, cap = (size_t)std::max(npairs, 64);
+  int rc = w.d_descs.reserve(c, np, cap);
+  if (rc == PCM_OK) rc = w.d_states.reserve(c, np, cap);
+  if (rc == PCM_OK) rc = w.d_guesses.reserve(c, 16 * np, 16 * cap);
+  if (rc == PCM_OK) rc = w.d_results.reserve(c, np, cap);
+  if (rc == PCM_OK) rc = w.d_sums.reserve(c, kPartialStride * np, kPartialStride * cap);
+  if (rc == PCM_OK) rc = w.d_jobs.reserve(c, np, cap);
+  if (rc == PCM_OK && partial_doubles) rc = w.d_partials.reserve(c, partial_doubles, partial_doubles);
+  if (rc != PCM_OK) return rc;
+  {
     // per-round status bytes of every pair live in mapped pinned host memory: k_finish_round
     // stores them directly (posted writes); the host polls them, no event / copy per round
-    PCM_HIPCK(c, hipHostMalloc(reinterpret_cast<void**>(&w.h_flags), bytes, hipHostMallocMapped));
-    PCM_HIPCK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&w.d_flags), w.h_flags, 0));
-    w.cap_flags = bytes;
+    const size_t bytes = (size_t)rounds * cap;
+    if (!w.h_flags || bytes > w.h_flags.cap) w.d_flags = nullptr;
+    rc = w.h_flags.reserve(c, bytes, bytes, hipHostMallocMapped);
+    if (rc != PCM_OK) return rc;
+    if (!w.d_flags) PCM_HIPCK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&w.d_flags), w.h_flags.p, 0));
   }
-  if (!w.d_stats) PCM_HIPCK(c, hipMalloc(&w.d_stats, sizeof(unsigned long long) * 16));
-  if (!w.d_queue) PCM_HIPCK(c, hipMalloc(&w.d_queue, sizeof(unsigned int)));
+  rc = w.d_stats.reserve(c, 16, 16);
+  if (rc == PCM_OK) rc = w.d_queue.reserve(c, 1, 1);
+  if (rc != PCM_OK) return rc;
   while ((int)w.ev_round.size() < 2) {
     hipEvent_t e;
     PCM_HIPCK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -118,13 +103,20 @@ int ensure_ws(pcm_ctx* c, Workspace** out, int npairs, size_t partial_doubles, i
 void free_ws(pcm_ctx* c) {
   Workspace* w = static_cast<Workspace*>(c->ws);
   if (!w) return;
-  hipFree(w->d_descs); hipFree(w->d_states); hipFree(w->d_guesses); hipFree(w->d_results); hipFree(w->d_partials); hipFree(w->d_sums);
-  hipFree(w->d_stats); hipFree(w->d_queue); hipFree(w->d_jobs); hipFree(w->sort.keys); hipFree(w->sort.vals); hipFree(w->sort.tmp);
-  if (w->h_flags) hipHostFree(w->h_flags);
   for (hipEvent_t e : w->ev_round) hipEventDestroy(e);
   for (hipEvent_t e : w->ev_prof) hipEventDestroy(e);
   delete w;
   c->ws = nullptr;
+}
+
+// room for `bytes` in the grow-only device scratch the pre-processing operators share (a quarter of headroom: no allocation per
+// frame in the steady state); the contents do not survive a growth
+int pre_scratch(pcm_ctx* c, size_t bytes) { return c->pre_arena.reserve(c, bytes, bytes + bytes / 4); }
+
+// the same for the records + partial sums of a GICP-BFGS correspondence set of m pairs
+int bfgs_scratch(pcm_ctx* c, size_t m) {
+  const size_t need = gicp_bfgs_scratch_bytes(m);
+  return c->bfgs.reserve(c, need, need + need / 4);
 }
 
 int coord_mode_for(int model) {
@@ -210,12 +202,9 @@ int set_cloud(pcm_ctx* c, Cloud* cl, const void* points, size_t n, size_t stride
     return PCM_OK;
   }
   if (cl->borrowed) cl->drop_buffer();
-  if (n > cl->cap) {
-    if (cl->d_pts) hipFree(cl->d_pts);
-    cl->d_pts = nullptr; cl->cap = 0;
-    PCM_HIPCK(c, hipMalloc(&cl->d_pts, sizeof(float4) * n));
-    cl->cap = n;
-  }
+  if (n) rc = cl->own.reserve(c, n, n);
+  cl->d_pts = cl->own;
+  if (rc != PCM_OK) return rc;
   cl->n = n;
   cl->tag = tag;
   rc = load_points_to_device(c->stream, points, n, stride, memory, 0u, cl->d_pts, &c->err);
@@ -302,15 +291,10 @@ int prepare(pcm_ctx* c) {
   if (c->cfg.model == PCM_MODEL_NDT_OMP) {
     // VoxelGridCovariance leaves (NormalDistributionsTransform::init, ndt_omp.h:300-306) + pass buffers
     if (!c->pleaf_valid) {
-      if (c->pleaf_cap < c->map.num_voxels) {
-        if (c->pleaf) hipFree(c->pleaf);
-        if (c->pleaf_f) hipFree(c->pleaf_f);
-        c->pleaf = nullptr; c->pleaf_f = nullptr; c->pleaf_cap = 0;
-        PCM_HIPCK(c, hipMalloc(&c->pleaf, sizeof(PclLeaf) * (size_t)c->map.num_voxels));
-        PCM_HIPCK(c, hipMalloc(&c->pleaf_f, sizeof(PclLeafF) * (size_t)c->map.num_voxels));
-        c->pleaf_cap = c->map.num_voxels;
-      }
-      int rc = build_pclndt_leaves(c->stream, c->map, c->pleaf, c->pleaf_f, &c->err);
+      int rc = c->pleaf.reserve(c, c->map.num_voxels, c->map.num_voxels);
+      if (rc == PCM_OK) rc = c->pleaf_f.reserve(c, c->map.num_voxels, c->map.num_voxels);
+      if (rc != PCM_OK) return rc;
+      rc = build_pclndt_leaves(c->stream, c->map, c->pleaf, c->pleaf_f, &c->err);
       if (rc != PCM_OK) return rc;
       c->pleaf_valid = true;
       c->nlists.valid = false;
@@ -330,16 +314,10 @@ int prepare(pcm_ctx* c) {
     }
     uint32_t per = 0;
     const size_t need = (size_t)pclndt_workgroups((uint32_t)c->src.n, &per) * 48;
-    if (c->ndt_partials_cap < need) {
-      if (c->ndt_partials) hipFree(c->ndt_partials);
-      c->ndt_partials = nullptr; c->ndt_partials_cap = 0;
-      PCM_HIPCK(c, hipMalloc(&c->ndt_partials, sizeof(double) * need));
-      PCM_HIPCK(c, hipMemsetAsync(c->ndt_partials, 0, sizeof(double) * need, c->stream));
-      c->ndt_partials_cap = need;
-    }
-    if (!c->ndt_out) PCM_HIPCK(c, hipMalloc(&c->ndt_out, sizeof(double) * 48));
-    if (!c->ndt_out_host) PCM_HIPCK(c, hipHostMalloc(&c->ndt_out_host, sizeof(double) * 48));
-    return PCM_OK;
+    int rc = c->ndt_partials.reserve(c, need, need, true);
+    if (rc == PCM_OK) rc = c->ndt_out.reserve(c, 48, 48);
+    if (rc == PCM_OK) rc = c->ndt_out_host.reserve(c, 48, 48);
+    return rc;
   }
   if (gicp) {
     // FastGICP::computeTransformation: covariances of both clouds, lazily   fast_gicp_impl.hpp:102-110
@@ -363,16 +341,11 @@ int prepare(pcm_ctx* c) {
       c->src_cov_valid = false;
     }
     if (!c->tgt_cov_valid) {
-      if (c->tgt_cov_cap < c->map.num_points) {
-        if (c->tgt_cov) hipFree(c->tgt_cov);
-        c->tgt_cov = nullptr; c->tgt_cov_cap = 0;
-        PCM_HIPCK(c, hipMalloc(&c->tgt_cov, sizeof(double) * 6 * (size_t)c->map.num_points));
-        c->tgt_cov_cap = c->map.num_points;
-      }
+      int rc = c->tgt_cov.reserve(c, 6 * (size_t)c->map.num_points, 6 * (size_t)c->map.num_points);
+      if (rc != PCM_OK) return rc;
       const int reg_code = c->cfg.regularization + (c->cfg.model == PCM_MODEL_VGICP_CUDA ? 16 : 0);   // + 16: float CUDA-core semantics
       // `if (target_covs_.size() != target_->size()) calculate_covariances(...)`  fast_gicp_impl.hpp:107-109
       const bool given = c->cfg.model != PCM_MODEL_VGICP_CUDA && c->user_cov[1].size() == (size_t)c->map.num_points * 6 && c->map.num_points == c->tgt.n;
-      int rc = PCM_OK;
       if (given) rc = upload_covariances(c->stream, c->map, c->user_cov[1].data(), c->tgt_cov, &c->err);
       else if (rbf) rc = compute_covariances_rbf(c->stream, c->map, c->tgt.d_pts, (uint32_t)c->tgt.n, c->cfg.rbf_kernel_width, c->cfg.rbf_max_dist, c->cfg.regularization, c->tgt_cov, &c->err);
       else {
@@ -383,36 +356,23 @@ int prepare(pcm_ctx* c) {
       }
       if (rc != PCM_OK) return rc;
       if (c->cfg.model == PCM_MODEL_VGICP_CUDA) {
-        if (c->cvox_cap < c->map.num_voxels) {
-          if (c->cvox) hipFree(c->cvox);
-          c->cvox = nullptr; c->cvox_cap = 0;
-          PCM_HIPCK(c, hipMalloc(&c->cvox, sizeof(VgcVoxel) * (size_t)c->map.num_voxels));
-          c->cvox_cap = c->map.num_voxels;
-        }
+        rc = c->cvox.reserve(c, c->map.num_voxels, c->map.num_voxels);
+        if (rc != PCM_OK) return rc;
         rc = build_vgc_voxels(c->stream, c->map, c->tgt_cov, c->cvox, &c->err);
         if (rc != PCM_OK) return rc;
       }
       if (c->cfg.model == PCM_MODEL_VGICP) {
-        if (c->vvox_cap < c->map.num_voxels) {
-          if (c->vvox) hipFree(c->vvox);
-          c->vvox = nullptr; c->vvox_cap = 0;
-          PCM_HIPCK(c, hipMalloc(&c->vvox, sizeof(VgVoxel) * (size_t)c->map.num_voxels));
-          c->vvox_cap = c->map.num_voxels;
-        }
+        rc = c->vvox.reserve(c, c->map.num_voxels, c->map.num_voxels);
+        if (rc != PCM_OK) return rc;
         rc = build_vgicp_voxels(c->stream, c->map, c->tgt_cov, c->cfg.voxel_mode, c->vvox, &c->err);
         if (rc != PCM_OK) return rc;
       }
       c->tgt_cov_valid = true;
     }
     if (!c->src_cov_valid) {
-      if (c->src_cov_cap < c->srcmap.num_points) {
-        if (c->src_cov) hipFree(c->src_cov);
-        c->src_cov = nullptr; c->src_cov_cap = 0;
-        PCM_HIPCK(c, hipMalloc(&c->src_cov, sizeof(double) * 6 * (size_t)c->srcmap.num_points));
-        c->src_cov_cap = c->srcmap.num_points;
-      }
+      int rc = c->src_cov.reserve(c, 6 * (size_t)c->srcmap.num_points, 6 * (size_t)c->srcmap.num_points);
+      if (rc != PCM_OK) return rc;
       const bool given = c->cfg.model != PCM_MODEL_VGICP_CUDA && c->user_cov[0].size() == (size_t)c->srcmap.num_points * 6 && c->srcmap.num_points == c->src.n;   // :104-106
-      int rc = PCM_OK;
       if (given) rc = upload_covariances(c->stream, c->srcmap, c->user_cov[0].data(), c->src_cov, &c->err);
       else if (rbf) rc = compute_covariances_rbf(c->stream, c->srcmap, c->src.d_pts, (uint32_t)c->src.n, c->cfg.rbf_kernel_width, c->cfg.rbf_max_dist, c->cfg.regularization, c->src_cov, &c->err);
       else {
@@ -427,11 +387,9 @@ int prepare(pcm_ctx* c) {
       c->src_cov_valid = true;
     }
     const size_t ncorr = c->cfg.model == PCM_MODEL_VGICP_CUDA ? 0 : c->src.n * (size_t)(c->cfg.model == PCM_MODEL_VGICP ? c->cfg.num_neighbors : 1);
-    if (c->maha_cap < ncorr) {
-      if (c->maha) hipFree(c->maha);
-      c->maha = nullptr; c->maha_cap = 0;
-      PCM_HIPCK(c, hipMalloc(&c->maha, sizeof(double) * 6 * ncorr));
-      c->maha_cap = ncorr;
+    if (ncorr) {   // VGICP_CUDA keeps no cache
+      const int rc = c->maha.reserve(c, 6 * ncorr, 6 * ncorr);
+      if (rc != PCM_OK) return rc;
     }
   }
   if (c->cfg.model == PCM_MODEL_NDT_D2D && (!c->srcmap.valid || c->srcmap.res != c->cfg.voxel_resolution)) {
@@ -442,37 +400,18 @@ int prepare(pcm_ctx* c) {
   }
   if (gauss || gicp) {
     const size_t need = num_elements(c) * (c->cfg.model == PCM_MODEL_GICP ? (size_t)1 : neighbor_slots(c->cfg));
-    if (c->corr_cap < need) {
-      if (c->corr) hipFree(c->corr);
-      c->corr = nullptr; c->corr_cap = 0;
-      PCM_HIPCK(c, hipMalloc(&c->corr, sizeof(int32_t) * need));
-      c->corr_cap = need;
-    }
+    const int rc = c->corr.reserve(c, need, need);
+    if (rc != PCM_OK) return rc;
   }
-  if (c->cfg.sort_source && c->src_order_cap < c->src.n) {
-    if (c->src_order) hipFree(c->src_order);
-    c->src_order = nullptr; c->src_order_cap = 0; c->src_sorted = false;
-    PCM_HIPCK(c, hipMalloc(&c->src_order, sizeof(float4) * c->src.n));
-    c->src_order_cap = c->src.n;
+  if (c->cfg.sort_source && c->src_order.cap < c->src.n) {
+    c->src_sorted = false;
+    const int rc = c->src_order.reserve(c, c->src.n, c->src.n);
+    if (rc != PCM_OK) return rc;
   }
-  if (!c->counter) {
-    PCM_HIPCK(c, hipMalloc(&c->counter, sizeof(unsigned int)));
-    PCM_HIPCK(c, hipMemsetAsync(c->counter, 0, sizeof(unsigned int), c->stream));
-    PCM_HIPCK(c, hipStreamSynchronize(c->stream));
-  }
-  if (c->nn_cap < c->src.n) {
-    if (c->nn) hipFree(c->nn);
-    c->nn = nullptr; c->nn_cap = 0;
-    PCM_HIPCK(c, hipMalloc(&c->nn, sizeof(uint32_t) * 5 * c->src.n));
-    c->nn_cap = c->src.n;
-  }
-  if (c->planes_cap < c->src.n) {
-    if (c->planes) hipFree(c->planes);
-    c->planes = nullptr; c->planes_cap = 0;
-    PCM_HIPCK(c, hipMalloc(&c->planes, sizeof(float4) * c->src.n));
-    c->planes_cap = c->src.n;
-  }
-  return PCM_OK;
+  int rc = c->counter.reserve(c, 1, 1, true);
+  if (rc == PCM_OK) rc = c->nn.reserve(c, 5 * c->src.n, 5 * c->src.n);
+  if (rc == PCM_OK) rc = c->planes.reserve(c, c->src.n, c->src.n);
+  return rc;
 }
 
 struct Geom {
@@ -885,14 +824,12 @@ auto make_ndt_solver(pcm_ctx* c) {
 
 // buffers of a batched pclomp NDT registration, owned by the first context of the batch
 struct NdtBatchWs {
-  NdtObject* d_objs = nullptr;
-  ndtomp::NdtMachine* d_ms = nullptr;
-  NdtObject* h_objs = nullptr;            // pinned
-  ndtomp::NdtMachine* h_ms = nullptr;     // pinned
-  unsigned char* h_flags = nullptr;       // mapped pinned: [round][object] status bytes of k_pclndt_batch_step
-  unsigned char* d_flags = nullptr;
-  int cap = 0;
-  size_t cap_flags = 0;
+  DevBuf<NdtObject> d_objs{"d_objs"};
+  DevBuf<ndtomp::NdtMachine> d_ms{"d_ms"};
+  PinnedBuf<NdtObject> h_objs{"h_objs"};
+  PinnedBuf<ndtomp::NdtMachine> h_ms{"h_ms"};
+  PinnedBuf<unsigned char> h_flags{"h_flags"};   // mapped pinned: [round][object] status bytes of k_pclndt_batch_step
+  unsigned char* d_flags = nullptr;              // device view of h_flags
   hipStream_t gst[4] = {nullptr, nullptr, nullptr, nullptr};   // streams of the lock-step groups, created back to back
 };
 
@@ -900,11 +837,6 @@ void free_ndt_batch_ws(void* p) {
   NdtBatchWs* w = static_cast<NdtBatchWs*>(p);
   if (!w) return;
   for (hipStream_t st : w->gst) if (st) (void)hipStreamDestroy(st);
-  if (w->d_objs) hipFree(w->d_objs);
-  if (w->d_ms) hipFree(w->d_ms);
-  if (w->h_objs) hipHostFree(w->h_objs);
-  if (w->h_ms) hipHostFree(w->h_ms);
-  if (w->h_flags) hipHostFree(w->h_flags);
   delete w;
 }
 
@@ -920,18 +852,13 @@ int pclndt_align_batch(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_re
   if (!c0->ndt_ws) c0->ndt_ws = new (std::nothrow) NdtBatchWs();
   if (!c0->ndt_ws) { c0->err = "out of host memory"; return PCM_ERR_HIP; }
   NdtBatchWs& w = *static_cast<NdtBatchWs*>(c0->ndt_ws);
-  if (n > w.cap) {
-    if (w.d_objs) hipFree(w.d_objs);
-    if (w.d_ms) hipFree(w.d_ms);
-    if (w.h_objs) hipHostFree(w.h_objs);
-    if (w.h_ms) hipHostFree(w.h_ms);
-    w.d_objs = nullptr; w.d_ms = nullptr; w.h_objs = nullptr; w.h_ms = nullptr; w.cap = 0;
-    const int cap = std::max(n, 16);
-    PCM_HIPCK(c0, hipMalloc(&w.d_objs, sizeof(NdtObject) * cap));
-    PCM_HIPCK(c0, hipMalloc(&w.d_ms, sizeof(ndtomp::NdtMachine) * cap));
-    PCM_HIPCK(c0, hipHostMalloc(reinterpret_cast<void**>(&w.h_objs), sizeof(NdtObject) * cap, hipHostMallocDefault));
-    PCM_HIPCK(c0, hipHostMalloc(reinterpret_cast<void**>(&w.h_ms), sizeof(ndtomp::NdtMachine) * cap, hipHostMallocDefault));
-    w.cap = cap;
+  {
+    const size_t cap = (size_t)std::max(n, 16);
+    int rc = w.d_objs.reserve(c0, (size_t)n, cap);
+    if (rc == PCM_OK) rc = w.d_ms.reserve(c0, (size_t)n, cap);
+    if (rc == PCM_OK) rc = w.h_objs.reserve(c0, (size_t)n, cap);
+    if (rc == PCM_OK) rc = w.h_ms.reserve(c0, (size_t)n, cap);
+    if (rc != PCM_OK) return rc;
   }
   // an object asks for at most 12 evaluations per Newton iteration (1 + 10 trials + the Hessian pass) and runs max_iterations + 2 of them
   int max_rounds = 2;
@@ -945,13 +872,11 @@ int pclndt_align_batch(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_re
     max_rounds = std::max(max_rounds, (c->cfg.max_iterations + 3) * 12 + 2);
   }
   const size_t flag_bytes = (size_t)max_rounds * (size_t)n;
-  if (flag_bytes > w.cap_flags) {
-    if (w.h_flags) hipHostFree(w.h_flags);
-    w.h_flags = nullptr; w.d_flags = nullptr; w.cap_flags = 0;
-    const size_t bytes = std::max<size_t>(flag_bytes, 65536);
-    PCM_HIPCK(c0, hipHostMalloc(reinterpret_cast<void**>(&w.h_flags), bytes, hipHostMallocMapped));
-    PCM_HIPCK(c0, hipHostGetDevicePointer(reinterpret_cast<void**>(&w.d_flags), w.h_flags, 0));
-    w.cap_flags = bytes;
+  {
+    if (!w.h_flags || flag_bytes > w.h_flags.cap) w.d_flags = nullptr;
+    const int rc = w.h_flags.reserve(c0, flag_bytes, std::max<size_t>(flag_bytes, 65536), hipHostMallocMapped);
+    if (rc != PCM_OK) return rc;
+    if (!w.d_flags) PCM_HIPCK(c0, hipHostGetDevicePointer(reinterpret_cast<void**>(&w.d_flags), w.h_flags.p, 0));
   }
   std::memset(w.h_flags, 0, flag_bytes);
   hipStream_t st = c0->stream;
@@ -1124,40 +1049,17 @@ void pcm_destroy(pcm_ctx* c) {
   if (c->device >= 0) {
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
-    c->src.release();
-    c->tgt.release();
-    if (c->src_order) hipFree(c->src_order);
-    if (c->lio_aux) hipFree(c->lio_aux);
     free_ndt_batch_ws(c->ndt_ws);
     c->ndt_ws = nullptr;
-    c->map.release();
-    c->srcmap.release();
-    c->covfine.release();
-    c->nlists.release();
-    if (c->corr) hipFree(c->corr);
-    if (c->src_cov) hipFree(c->src_cov);
-    if (c->tgt_cov) hipFree(c->tgt_cov);
-    if (c->vvox) hipFree(c->vvox);
-    if (c->cvox) hipFree(c->cvox);
-    if (c->maha) hipFree(c->maha);
-    if (c->pleaf) hipFree(c->pleaf);
-    if (c->pleaf_f) hipFree(c->pleaf_f);
-    if (c->pre_arena) hipFree(c->pre_arena);
-    if (c->bfgs) hipFree(c->bfgs);
-    if (c->bfgs_idx) hipFree(c->bfgs_idx);
-    if (c->bfgs_host) hipHostFree(c->bfgs_host);
-    if (c->ndt_partials) hipFree(c->ndt_partials);
-    if (c->ndt_out) hipFree(c->ndt_out);
-    if (c->ndt_out_host) hipHostFree(c->ndt_out_host);
-    if (c->planes) hipFree(c->planes);
-    if (c->counter) hipFree(c->counter);
-    if (c->nn) hipFree(c->nn);
     free_ws(c);
     loam_release(c);
     occ_release(c);
-    if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
   }
+  // The context's own buffers (the DevBuf / PinnedBuf members of pcm_ctx, its clouds, maps and lists) free themselves here:
+  // `delete c` runs with the device current and before the context's stream is destroyed.
+  hipStream_t own = (c->device >= 0 && c->own_stream) ? c->stream : nullptr;
   delete c;
+  if (own) hipStreamDestroy(own);
 }
 
 const char* pcm_last_error(const pcm_ctx* c) { return c ? c->err.c_str() : "null context"; }
@@ -1209,15 +1111,9 @@ namespace {
 // min(old, new) entries survive a new scan, appended ones take the default.  plane_coef_ (:339) needs no such care: the
 // IEKF's first ObsModel call of a frame always matches (esekfom.hpp:1529) and rewrites every plane it may read later.
 static int lio_members_resize(pcm_ctx* c, size_t n) {
-  if (n > c->lio_aux_cap) {
-    const size_t cap = n + n / 2 + 1024;
-    float2* nb = nullptr;
-    PCM_HIPCK(c, hipMalloc(&nb, sizeof(float2) * cap));
-    if (c->lio_aux_n) PCM_HIPCK(c, hipMemcpyAsync(nb, c->lio_aux, sizeof(float2) * c->lio_aux_n, hipMemcpyDeviceToDevice, c->stream));
-    PCM_HIPCK(c, hipStreamSynchronize(c->stream));
-    if (c->lio_aux) hipFree(c->lio_aux);
-    c->lio_aux = nb;
-    c->lio_aux_cap = cap;
+  if (n > c->lio_aux.cap) {
+    const int rc = c->lio_aux.reserve_keep(c, n, n + n / 2 + 1024, c->lio_aux_n);
+    if (rc != PCM_OK) return rc;
   }
   if (n > c->lio_aux_n) launch_lio_members_init(c->stream, c->lio_aux, (uint32_t)c->lio_aux_n, (uint32_t)n);
   c->lio_aux_n = n;
@@ -1240,7 +1136,7 @@ int pcm_set_source(pcm_ctx* c, const void* points, size_t n, size_t stride_bytes
 int pcm_swap_source_and_target(pcm_ctx* c) {
   CHECK_CTX(c);
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));
-  std::swap(c->src, c->tgt);
+  c->src.swap(c->tgt);
   std::swap(c->user_cov[0], c->user_cov[1]);   // source_covs_.swap(target_covs_)  fast_gicp_impl.hpp:55
   c->map.valid = false;
   c->srcmap.valid = false;
@@ -1319,22 +1215,17 @@ int pcm_undistort(pcm_ctx* c, void* points, size_t n, size_t stride, size_t time
   LioStateD s;
   for (int a = 0; a < 4; a++) { s.rot[a] = st->rot[a]; s.off_R[a] = st->off_R[a]; }
   for (int a = 0; a < 3; a++) { s.pos[a] = st->pos[a]; s.off_T[a] = st->off_T[a]; }
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t need = up(sizeof(pcm_imu_pose) * (size_t)npose) + (memory == PCM_MEM_HOST ? up(n * stride) : 0);
-  if (c->pre_arena_cap < need) {   // grow-only arena shared with pcm_voxel_downsample
-    if (c->pre_arena) hipFree(c->pre_arena);
-    c->pre_arena = nullptr; c->pre_arena_cap = 0;
-    PCM_HIPCK(c, hipMalloc(&c->pre_arena, need + need / 4));
-    c->pre_arena_cap = need + need / 4;
-  }
-  pcm_imu_pose* d_poses = reinterpret_cast<pcm_imu_pose*>(c->pre_arena);
+  const size_t need = up256(sizeof(pcm_imu_pose) * (size_t)npose) + (memory == PCM_MEM_HOST ? up256(n * stride) : 0);
+  int rc = pre_scratch(c, need);
+  if (rc != PCM_OK) return rc;
+  pcm_imu_pose* d_poses = reinterpret_cast<pcm_imu_pose*>(c->pre_arena.p);
   PCM_HIPCK(c, hipMemcpyAsync(d_poses, poses, sizeof(pcm_imu_pose) * (size_t)npose, hipMemcpyHostToDevice, c->stream));
   void* d_pts = points;
   if (memory == PCM_MEM_HOST) {
-    d_pts = c->pre_arena + up(sizeof(pcm_imu_pose) * (size_t)npose);
+    d_pts = c->pre_arena + up256(sizeof(pcm_imu_pose) * (size_t)npose);
     PCM_HIPCK(c, hipMemcpyAsync(d_pts, points, n * stride, hipMemcpyHostToDevice, c->stream));
   }
-  const int rc = undistort_device(c->stream, d_pts, n, stride, time_off, d_poses, npose, s, &c->err);
+  rc = undistort_device(c->stream, d_pts, n, stride, time_off, d_poses, npose, s, &c->err);
   if (rc != PCM_OK) return rc;
   if (memory == PCM_MEM_HOST) PCM_HIPCK(c, hipMemcpyAsync(points, d_pts, n * stride, hipMemcpyDeviceToHost, c->stream));
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));
@@ -1393,21 +1284,15 @@ int pcm_gicp_bfgs_set_correspondences(pcm_ctx* c, const void* src, size_t n_src,
       if (idx_src[i] < 0 || (size_t)idx_src[i] >= n_src || idx_tgt[i] < 0 || (size_t)idx_tgt[i] >= n_tgt) { c->err = "correspondence index out of range"; return PCM_ERR_INVALID_ARGUMENT; }
   PCM_HIPCK(c, hipSetDevice(c->device));
   c->bfgs_m = 0;
-  const size_t need = gicp_bfgs_scratch_bytes(m);
-  if (c->bfgs_cap < need) {
-    if (c->bfgs) hipFree(c->bfgs);
-    c->bfgs = nullptr; c->bfgs_cap = 0;
-    PCM_HIPCK(c, hipMalloc(&c->bfgs, need + need / 4));
-    c->bfgs_cap = need + need / 4;
-  }
+  int rc = bfgs_scratch(c, m);
+  if (rc != PCM_OK) return rc;
   if (m == 0) return PCM_OK;
   const void *d_src = src, *d_tgt = tgt;
   const int32_t *d_is = idx_src, *d_it = idx_tgt;
   const float* d_maha = maha;
   char* tmp = nullptr;
   if (memory == PCM_MEM_HOST) {   // staged once per correspondence set; the evaluations then read the packed records only
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t b_src = up(n_src * stride), b_tgt = up(n_tgt * stride), b_idx = up(m * 4), b_maha = up(n_src * 64);
+    const size_t b_src = up256(n_src * stride), b_tgt = up256(n_tgt * stride), b_idx = up256(m * 4), b_maha = up256(n_src * 64);
     PCM_HIPCK(c, hipMallocAsync(reinterpret_cast<void**>(&tmp), b_src + b_tgt + 2 * b_idx + b_maha, c->stream));
     char* q = tmp;
     PCM_HIPCK(c, hipMemcpyAsync(q, src, n_src * stride, hipMemcpyHostToDevice, c->stream)); d_src = q; q += b_src;
@@ -1416,7 +1301,7 @@ int pcm_gicp_bfgs_set_correspondences(pcm_ctx* c, const void* src, size_t n_src,
     PCM_HIPCK(c, hipMemcpyAsync(q, idx_tgt, m * 4, hipMemcpyHostToDevice, c->stream)); d_it = reinterpret_cast<const int32_t*>(q); q += b_idx;
     PCM_HIPCK(c, hipMemcpyAsync(q, maha, n_src * 64, hipMemcpyHostToDevice, c->stream)); d_maha = reinterpret_cast<const float*>(q);
   }
-  const int rc = gicp_bfgs_pack_device(c->stream, d_src, d_tgt, stride, d_is, d_it, d_maha, m, c->bfgs, &c->err);
+  rc = gicp_bfgs_pack_device(c->stream, d_src, d_tgt, stride, d_is, d_it, d_maha, m, c->bfgs, &c->err);
   if (tmp) PCM_HIPCK(c, hipFreeAsync(tmp, c->stream));
   if (rc != PCM_OK) return rc;
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));   // the caller's buffers are free again
@@ -1433,8 +1318,9 @@ int pcm_gicp_bfgs_fdf(pcm_ctx* c, const float* base_T, const double* x, int mode
   bfgs_apply_state(base_T, x, T);
   const size_t m = c->bfgs_m;
   double* d_partials = reinterpret_cast<double*>(c->bfgs + ((64 * m + 255) & ~(size_t)255));
-  if (!c->bfgs_host) PCM_HIPCK(c, hipHostMalloc(reinterpret_cast<void**>(&c->bfgs_host), 16 * sizeof(double), hipHostMallocDefault));
-  const int rc = gicp_bfgs_fdf_device(c->stream, c->bfgs, m, T, base_T, d_partials, c->bfgs_host, &c->err);   // the finish kernel stores to host memory
+  int rc = c->bfgs_host.reserve(c, 16, 16);
+  if (rc != PCM_OK) return rc;
+  rc = gicp_bfgs_fdf_device(c->stream, c->bfgs, m, T, base_T, d_partials, c->bfgs_host, &c->err);   // the finish kernel stores to host memory
   if (rc != PCM_OK) return rc;
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   const double* s = c->bfgs_host;
@@ -1460,22 +1346,12 @@ int pcm_gicp_bfgs_update_correspondences(pcm_ctx* c, const float* transformation
   if (rc != PCM_OK) return rc;
   const size_t n = c->srcmap.num_points;
   c->bfgs_m = 0;
-  const size_t need = gicp_bfgs_scratch_bytes(n);
-  if (c->bfgs_cap < need) {
-    if (c->bfgs) hipFree(c->bfgs);
-    c->bfgs = nullptr; c->bfgs_cap = 0;
-    PCM_HIPCK(c, hipMalloc(&c->bfgs, need + need / 4));
-    c->bfgs_cap = need + need / 4;
-  }
-  if (c->bfgs_idx_cap < n) {
-    if (c->bfgs_idx) hipFree(c->bfgs_idx);
-    c->bfgs_idx = nullptr; c->bfgs_idx_cap = 0;
-    PCM_HIPCK(c, hipMalloc(&c->bfgs_idx, sizeof(int32_t) * 2 * (n + n / 4 + 64)));
-    c->bfgs_idx_cap = n + n / 4 + 64;
-  }
+  rc = bfgs_scratch(c, n);
+  if (rc == PCM_OK) rc = c->bfgs_idx.reserve(c, 2 * n, 2 * (n + n / 4 + 64));
+  if (rc != PCM_OK) return rc;
   uint32_t m = 0;
   rc = gicp_bfgs_correspond_device(c->stream, c->map, coord_mode_for(c->cfg.model), c->srcmap, c->src_cov, c->tgt_cov, guess, transformation, (double)c->cfg.max_corr_dist,
-                                   reinterpret_cast<float4*>(c->bfgs), c->bfgs_idx, c->bfgs_idx + c->bfgs_idx_cap, &m, &c->err);
+                                   reinterpret_cast<float4*>(c->bfgs.p), c->bfgs_idx, c->bfgs_idx + c->bfgs_idx.cap / 2, &m, &c->err);
   if (rc != PCM_OK) return rc;
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   c->bfgs_m = m;
@@ -1489,10 +1365,10 @@ int pcm_gicp_bfgs_get_correspondences(pcm_ctx* c, int32_t* idx_src, int32_t* idx
   if (!c->bfgs_idx || capacity < m) { c->err = "pcm_gicp_bfgs_get_correspondences: no device-side correspondence set, or the buffers are too small"; return PCM_ERR_INVALID_ARGUMENT; }
   if (m == 0) return PCM_OK;
   if (idx_src) PCM_HIPCK(c, hipMemcpy(idx_src, c->bfgs_idx, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
-  if (idx_tgt) PCM_HIPCK(c, hipMemcpy(idx_tgt, c->bfgs_idx + c->bfgs_idx_cap, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
+  if (idx_tgt) PCM_HIPCK(c, hipMemcpy(idx_tgt, c->bfgs_idx + c->bfgs_idx.cap / 2, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
   if (maha9) {
     std::vector<float4> r(3 * m);   // planes 1..3 of the records hold M
-    PCM_HIPCK(c, hipMemcpy(r.data(), reinterpret_cast<const float4*>(c->bfgs) + m, sizeof(float4) * 3 * m, hipMemcpyDeviceToHost));
+    PCM_HIPCK(c, hipMemcpy(r.data(), reinterpret_cast<const float4*>(c->bfgs.p) + m, sizeof(float4) * 3 * m, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < m; i++) {
       const float4 a = r[i], b = r[m + i], d = r[2 * m + i];
       float* o = maha9 + 9 * i;
@@ -1510,26 +1386,20 @@ int pcm_voxel_downsample(pcm_ctx* c, const void* points, size_t n, size_t stride
   *n_out = 0;
   if (n == 0) return PCM_OK;
   PCM_HIPCK(c, hipSetDevice(c->device));
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t io = memory == PCM_MEM_HOST ? 2 * up(n * stride) : 0;
-  const size_t need = voxel_downsample_scratch_bytes(n) + io;
-  if (c->pre_arena_cap < need) {   // grow-only arena: no allocation per frame in the steady state
-    if (c->pre_arena) hipFree(c->pre_arena);
-    c->pre_arena = nullptr; c->pre_arena_cap = 0;
-    PCM_HIPCK(c, hipMalloc(&c->pre_arena, need + need / 4));
-    c->pre_arena_cap = need + need / 4;
-  }
+  const size_t io = memory == PCM_MEM_HOST ? 2 * up256(n * stride) : 0;
+  int rc = pre_scratch(c, voxel_downsample_scratch_bytes(n) + io);
+  if (rc != PCM_OK) return rc;
   const void* src = points;
   void* dst = out;
   char* scratch = c->pre_arena;
   if (memory == PCM_MEM_HOST) {
     char* d_in = c->pre_arena;
-    char* d_out = c->pre_arena + up(n * stride);
+    char* d_out = c->pre_arena + up256(n * stride);
     scratch = c->pre_arena + io;
     PCM_HIPCK(c, hipMemcpyAsync(d_in, points, n * stride, hipMemcpyHostToDevice, c->stream));
     src = d_in; dst = d_out;
   }
-  int rc = voxel_downsample_device(c->stream, src, n, stride, leaf, static_cast<float*>(dst), n_out, scratch, &c->err);
+  rc = voxel_downsample_device(c->stream, src, n, stride, leaf, static_cast<float*>(dst), n_out, scratch, &c->err);
   if (rc != PCM_OK) return rc;
   if (memory == PCM_MEM_HOST && *n_out) {
     PCM_HIPCK(c, hipMemcpyAsync(out, dst, *n_out * stride, hipMemcpyDeviceToHost, c->stream));
@@ -1565,26 +1435,20 @@ int pcm_livox_filter(pcm_ctx* c, const void* custom_points, size_t n, int memory
   *n_out = 0;
   if (n == 0) return PCM_OK;
   PCM_HIPCK(c, hipSetDevice(c->device));
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t io = memory == PCM_MEM_HOST ? up(n * 20) + up(n * 48) : 0;
-  const size_t need = livox_filter_scratch_bytes(n) + io;
-  if (c->pre_arena_cap < need) {   // grow-only arena shared with the other pre-processing operators
-    if (c->pre_arena) hipFree(c->pre_arena);
-    c->pre_arena = nullptr; c->pre_arena_cap = 0;
-    PCM_HIPCK(c, hipMalloc(&c->pre_arena, need + need / 4));
-    c->pre_arena_cap = need + need / 4;
-  }
+  const size_t io = memory == PCM_MEM_HOST ? up256(n * 20) + up256(n * 48) : 0;
+  int rc = pre_scratch(c, livox_filter_scratch_bytes(n) + io);
+  if (rc != PCM_OK) return rc;
   const void* src = custom_points;
   void* dst = out;
   char* scratch = c->pre_arena;
   if (memory == PCM_MEM_HOST) {
     char* d_in = c->pre_arena;
-    char* d_out = c->pre_arena + up(n * 20);
+    char* d_out = c->pre_arena + up256(n * 20);
     scratch = c->pre_arena + io;
     PCM_HIPCK(c, hipMemcpyAsync(d_in, custom_points, n * 20, hipMemcpyHostToDevice, c->stream));
     src = d_in; dst = d_out;
   }
-  const int rc = livox_filter_device(c->stream, src, n, num_scans, point_filter_num, blind, dst, n_out, scratch, &c->err);
+  rc = livox_filter_device(c->stream, src, n, num_scans, point_filter_num, blind, dst, n_out, scratch, &c->err);
   if (rc != PCM_OK) return rc;
   if (memory == PCM_MEM_HOST && *n_out) PCM_HIPCK(c, hipMemcpyAsync(out, dst, *n_out * 48, hipMemcpyDeviceToHost, c->stream));
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));
@@ -1815,16 +1679,21 @@ int pcm_obs_model(pcm_ctx* c, const pcm_lio_state* s, int extrinsic_est_en, int 
 namespace {
 // grow the target point log to hold `need` points (keeps the content)
 int reserve_target(pcm_ctx* c, size_t need) {
-  if (need <= c->tgt.cap && !c->tgt.borrowed) return PCM_OK;
-  const size_t cap = std::max(need, c->tgt.cap + c->tgt.cap / 2 + 1024);
-  float4* nb = nullptr;
-  PCM_HIPCK(c, hipMalloc(&nb, sizeof(float4) * cap));
-  if (c->tgt.n) PCM_HIPCK(c, hipMemcpyAsync(nb, c->tgt.d_pts, sizeof(float4) * c->tgt.n, hipMemcpyDeviceToDevice, c->stream));
-  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
-  const size_t n = c->tgt.n;
-  const uint64_t tag = c->tgt.tag;
-  c->tgt.drop_buffer();
-  c->tgt.d_pts = nb; c->tgt.cap = cap; c->tgt.n = n; c->tgt.tag = tag;
+  Cloud& t = c->tgt;
+  if (need <= t.own.cap && !t.borrowed) return PCM_OK;
+  const size_t cap = std::max(need, t.own.cap + t.own.cap / 2 + 1024);
+  if (t.borrowed) {   // the caller's buffer is copied into an owned log on the first insert (own is empty until then)
+    const int rc = t.own.reserve(c, need, cap);
+    if (rc != PCM_OK) return rc;
+    hipError_t e = t.n ? hipMemcpyAsync(t.own, t.d_pts, sizeof(float4) * t.n, hipMemcpyDeviceToDevice, c->stream) : hipSuccess;
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { t.own.release(); return hip_failure(&c->err, "copy", t.own.what, e); }
+    t.borrowed = false;
+  } else {
+    const int rc = t.own.reserve_keep(c, need, cap, t.n);
+    if (rc != PCM_OK) return rc;
+  }
+  t.d_pts = t.own;
   return PCM_OK;
 }
 }  // namespace
@@ -1887,18 +1756,12 @@ int pcm_lio_frame_begin(pcm_ctx* c, const void* custom_points, size_t n, int mem
   if (n == 0) { c->err = "empty frame"; return PCM_ERR_NO_INPUT; }
   PCM_HIPCK(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   // frame arena: [raw message | filtered records | down-sampled records | IMU poses | scratch of the operators]; grow-only, so the
   // steady state makes no allocation.  The raw message is the only host -> device copy of the frame.
-  const size_t o_raw = 0, o_flt = o_raw + up(n * 20), o_ds = o_flt + up(n * 48), o_pose = o_ds + up(n * 48);
-  const size_t o_scr = o_pose + up(sizeof(pcm_imu_pose) * (size_t)std::max(npose, 1));
-  const size_t need = o_scr + std::max(livox_filter_scratch_bytes(n), voxel_downsample_scratch_bytes(n));
-  if (c->pre_arena_cap < need) {
-    if (c->pre_arena) hipFree(c->pre_arena);
-    c->pre_arena = nullptr; c->pre_arena_cap = 0;
-    PCM_HIPCK(c, hipMalloc(&c->pre_arena, need + need / 4));
-    c->pre_arena_cap = need + need / 4;
-  }
+  const size_t o_raw = 0, o_flt = o_raw + up256(n * 20), o_ds = o_flt + up256(n * 48), o_pose = o_ds + up256(n * 48);
+  const size_t o_scr = o_pose + up256(sizeof(pcm_imu_pose) * (size_t)std::max(npose, 1));
+  int rc = pre_scratch(c, o_scr + std::max(livox_filter_scratch_bytes(n), voxel_downsample_scratch_bytes(n)));
+  if (rc != PCM_OK) return rc;
   char* A = c->pre_arena;
   const void* d_raw = custom_points;
   if (memory == PCM_MEM_HOST) {
@@ -1907,7 +1770,7 @@ int pcm_lio_frame_begin(pcm_ctx* c, const void* custom_points, size_t n, int mem
   }
   // 1. PointCloudPreprocess::AviaHandler  (pointcloud_preprocess.cc:44-88)
   size_t n_flt = 0;
-  int rc = livox_filter_device(st, d_raw, n, prm->num_scans, prm->point_filter_num, prm->blind, A + o_flt, &n_flt, A + o_scr, &c->err);
+  rc = livox_filter_device(st, d_raw, n, prm->num_scans, prm->point_filter_num, prm->blind, A + o_flt, &n_flt, A + o_scr, &c->err);
   if (rc != PCM_OK) return rc;
   if (n_flt == 0) { c->err = "no point of the frame passed the driver-message filter"; return PCM_ERR_NO_INPUT; }
   // 2. ImuProcess::UndistortPcl backward loop  (imu_processing.hpp:245-285): in place on the filtered records (time stamp = curvature).

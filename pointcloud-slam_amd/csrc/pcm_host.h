@@ -3,76 +3,60 @@
 
 #include <hip/hip_runtime.h>
 
+#include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/pcm_amd.h"
+#include "dev_buf.h"
 #include "lsq_step.h"
 #include "pcm_device.h"
 
 namespace pcm {
 
 struct Cloud {
-  float4* d_pts = nullptr;  // compact float4 points, input order (device copy, or the caller's own device buffer)
+  float4* d_pts = nullptr;  // compact float4 points, input order: what the kernels read (own, or the caller's own device buffer)
+  DevBuf<float4> own{"point cloud"};   // the device copy; empty while borrowed
   size_t n = 0;
-  size_t cap = 0;           // capacity of an owned buffer
   uint64_t tag = 0;
   bool borrowed = false;    // d_pts aliases a caller-owned 16-byte-stride device buffer (zero copy)
   void drop_buffer() {
-    if (d_pts && !borrowed) hipFree(d_pts);
-    d_pts = nullptr; cap = 0; borrowed = false;
+    own.release();
+    d_pts = nullptr; borrowed = false;
   }
   void release() {
     drop_buffer();
     n = 0; tag = 0;
   }
+  void swap(Cloud& o) {
+    own.swap(o.own);
+    std::swap(d_pts, o.d_pts); std::swap(n, o.n); std::swap(tag, o.tag); std::swap(borrowed, o.borrowed);
+  }
 };
 
 struct TargetMap {   // layout: pcm_device.h
-  BrickSlot* bricks = nullptr;
-  uint32_t* bmask = nullptr;
-  uint16_t* bpref = nullptr;
-  uint32_t* vox_start = nullptr;
-  float4* pts = nullptr;
-  GaussVoxel* gvox = nullptr;   // NDT models
-  uint32_t* order = nullptr;    // input index of every map point (kept on request: GICP covariances are reported in input order)
-  size_t order_cap = 0;
+  // the table in use is the first `cap` slots of bricks / bmask (x 16) / bpref (x 16); the allocations only grow
+  DevBuf<BrickSlot> bricks{"bricks"};
+  DevBuf<uint32_t> bmask{"bmask"};
+  DevBuf<uint16_t> bpref{"bpref"};
+  DevBuf<uint32_t> vox_start{"vox_start"};
+  DevBuf<float4> pts{"pts"};
+  DevBuf<GaussVoxel> gvox{"gvox"};   // NDT models
+  DevBuf<uint32_t> order{"order"};   // input index of every map point (kept on request: GICP covariances are reported in input order)
   // the sorted index of the point log the tables were built from (key, log position), kept for the next batch of a sliding map
   // (voxel_hash.hip: merged, not re-sorted), and its double buffer
-  uint64_t *keys_s = nullptr, *keys_t = nullptr;
-  uint32_t *idx_s = nullptr, *idx_t = nullptr;
-  size_t keys_cap = 0, keys_t_cap = 0, idx_cap = 0, idx_t_cap = 0, vox_cap = 0, pts_cap = 0;
-  uint32_t bricks_cap = 0;      // allocated slots of bricks / bmask / bpref (cap <= bricks_cap is the table in use)
+  DevBuf<uint64_t> keys_s{"keys_s"}, keys_t{"keys_t"};
+  DevBuf<uint32_t> idx_s{"idx_s"}, idx_t{"idx_t"};
   uint32_t index_n = 0;         // log points keys_s / idx_s cover (0: no usable index)
-  char* arena = nullptr;        // scratch of the incremental updates (grow-only; voxel_hash.hip BuildScratch)
-  size_t arena_cap = 0;
-  int* h_ctr = nullptr;         // pinned host copy of the build's counter record (one read-back per synchronisation point)
+  DevBuf<char> arena{"map update arena"};   // scratch of the incremental updates (grow-only; voxel_hash.hip BuildScratch)
+  PinnedBuf<int> h_ctr{"counters"};         // pinned host copy of the build's counter record (one read-back per synchronisation point)
   uint32_t cap = 0, num_voxels = 0, num_bricks = 0, num_points = 0;
   uint32_t max_voxel_points = 0;   // most points in one voxel
   float res = 0.f, inv_res = 0.f;
   int coord_mode = 0;
   bool valid = false;
-  void release() {
-    if (bricks) hipFree(bricks);
-    if (bmask) hipFree(bmask);
-    if (bpref) hipFree(bpref);
-    if (vox_start) hipFree(vox_start);
-    if (pts) hipFree(pts);
-    if (gvox) hipFree(gvox);
-    if (order) hipFree(order);
-    if (keys_s) hipFree(keys_s);
-    if (keys_t) hipFree(keys_t);
-    if (idx_s) hipFree(idx_s);
-    if (idx_t) hipFree(idx_t);
-    if (h_ctr) hipHostFree(h_ctr);
-    if (arena) hipFree(arena);
-    arena = nullptr; arena_cap = 0;
-    h_ctr = nullptr;
-    gvox = nullptr; order = nullptr; keys_s = keys_t = nullptr; idx_s = idx_t = nullptr;
-    bricks = nullptr; bmask = nullptr; bpref = nullptr; vox_start = nullptr; pts = nullptr;
-    keys_cap = keys_t_cap = idx_cap = idx_t_cap = vox_cap = pts_cap = order_cap = 0; bricks_cap = 0; index_n = 0;
-    cap = num_voxels = num_bricks = num_points = 0; max_voxel_points = 0; valid = false;
-  }
+  // back to the empty map: the members free themselves, the scalars take their initial values (nothing to keep in step here)
+  void release() { this->~TargetMap(); new (this) TargetMap(); }
 };
 
 // n_indexed > 0: the first n_indexed points of the log are what map->keys_s / idx_s index; only the points behind them are new
@@ -89,10 +73,10 @@ struct SortJob {
   uint32_t pad;
 };
 struct SortScratch {
-  uint64_t* keys = nullptr;   // 2 x cap
-  uint32_t* vals = nullptr;   // 2 x cap
-  void* tmp = nullptr;
-  size_t cap = 0, tmp_bytes = 0;
+  DevBuf<uint64_t> keys{"sort keys"};    // 2 x cap
+  DevBuf<uint32_t> vals{"sort values"};  // 2 x cap
+  DevBuf<char> tmp{"sort temporary"};
+  size_t cap = 0;                        // points the key / value arrays hold
 };
 // MapIncremental on the device (voxel_hash.hip)
 struct LioStateD { double rot[4], pos[3], off_R[4], off_T[3]; };
@@ -131,14 +115,14 @@ void launch_linearize_counted(hipStream_t stream, const PairDesc* d_descs, const
 // per-voxel candidate lists of a static point-to-plane map (neighbour_lists.hip)
 struct NeighbourLists {
   TargetMap index;            // brick hash over one stand-in point per voxel of the dilated occupied set: voxel -> list rank
-  uint32_t* start = nullptr;  // [num_lists + 1] first candidate of every list
-  float4* pts = nullptr;      // candidates, a list after the other, in the reference's visit order; w = index in the map's point array
-  size_t start_cap = 0, pts_cap = 0, num_candidates = 0;
+  DevBuf<uint32_t> start{"list starts"};  // [num_lists + 1] first candidate of every list
+  DevBuf<float4> pts{"list candidates"};  // candidates, a list after the other, in the reference's visit order; w = index in the map's point array
+  size_t num_candidates = 0;
   uint32_t num_lists = 0;
   int num_neighbors = 0;      // the neighbourhood the lists were built for
   int kind = 0;               // 0: candidate points (P2PLANE); 1: neighbour leaves of a pclomp NDT grid (centroid, leaf index); 2: rows of neighbour voxel indices (k_ndt)
   bool valid = false;
-  void release();
+  void release() { this->~NeighbourLists(); new (this) NeighbourLists(); }   // as TargetMap::release
 };
 int build_neighbour_lists(hipStream_t stream, const TargetMap& map, int num_neighbors, NeighbourLists* out, std::string* err, const PclLeaf* ndt_leaves = nullptr, bool voxel_slots = false);
 TargetView view_of_lists(const NeighbourLists& l);
@@ -181,6 +165,8 @@ void occ_release(pcm_ctx* c);
 
 }  // namespace pcm
 
+// A device array of the context is a DevBuf member (pinned host memory: a PinnedBuf): it frees itself when pcm_destroy deletes the
+// context, with the device current and before the stream goes.  Nothing is added to pcm_destroy for it.
 struct pcm_ctx {
   int device = 0;
   pcm_config cfg{};
@@ -194,57 +180,50 @@ struct pcm_ctx {
   int map_uses = 0;               // prepare() calls since the map was (re)built
   pcm::NeighbourLists nlists;     // P2PLANE, PCM_FLAG_NEIGHBOUR_LISTS: candidate lists of `map` (static targets)
   pcm::TargetMap covfine;         // GICP: the cloud whose covariances are being computed, on a grid 8x finer (kNN index of dense neighbourhoods only)
-  int32_t* corr = nullptr;        // NDT: matched voxel per (element, offset) of the last linearize
-  size_t corr_cap = 0;
+  pcm::DevBuf<int32_t> corr{"corr"};   // NDT: matched voxel per (element, offset) of the last linearize
   // GICP / VGICP: per-point covariances in MAP order (the source elements are srcmap.pts), voxel distributions, Mahalanobis cache
-  double* src_cov = nullptr;
-  double* tgt_cov = nullptr;
-  size_t src_cov_cap = 0, tgt_cov_cap = 0;
+  pcm::DevBuf<double> src_cov{"src_cov"}, tgt_cov{"tgt_cov"};   // 6 doubles per point
   bool src_cov_valid = false, tgt_cov_valid = false;
   int cov_k = 0, cov_reg = -1, cov_vmode = -1;
   float cov_rbf_w = -1.f, cov_rbf_d = -1.f;   // RBF parameters the cached covariances were computed with (-1: kNN covariances)
-  pcm::VgVoxel* vvox = nullptr;
-  size_t vvox_cap = 0;
-  pcm::VgcVoxel* cvox = nullptr;   // VGICP_CUDA
-  size_t cvox_cap = 0;
-  double* maha = nullptr;
-  size_t maha_cap = 0;
+  pcm::DevBuf<pcm::VgVoxel> vvox{"vvox"};
+  pcm::DevBuf<pcm::VgcVoxel> cvox{"cvox"};   // VGICP_CUDA
+  pcm::DevBuf<double> maha{"maha"};          // 6 doubles per correspondence
   // pclomp NDT: leaf payload of the map, partial rows, result row (device + pinned host)
-  pcm::PclLeaf* pleaf = nullptr;
-  pcm::PclLeafF* pleaf_f = nullptr;   // the float passes' 64-byte view of the same leaves
-  size_t pleaf_cap = 0;
+  pcm::DevBuf<pcm::PclLeaf> pleaf{"pleaf"};
+  pcm::DevBuf<pcm::PclLeafF> pleaf_f{"pleaf_f"};   // the float passes' 64-byte view of the same leaves
   bool pleaf_valid = false;
-  double* ndt_partials = nullptr;
-  size_t ndt_partials_cap = 0;
-  double* ndt_out = nullptr;
-  double* ndt_out_host = nullptr;
-  float4* src_order = nullptr;   // the scan re-ordered along the world-grid Morton curve (speed only)
-  size_t src_order_cap = 0;
+  pcm::DevBuf<double> ndt_partials{"ndt_partials"};
+  pcm::DevBuf<double> ndt_out{"ndt_out"};
+  pcm::PinnedBuf<double> ndt_out_host{"ndt_out_host"};
+  pcm::DevBuf<float4> src_order{"src_order"};   // the scan re-ordered along the world-grid Morton curve (speed only)
   bool src_sorted = false;       // src_order holds the current source
-  float4* planes = nullptr;
-  unsigned int* counter = nullptr;   // round tickets (device, one word)
-  size_t planes_cap = 0;
+  pcm::DevBuf<float4> planes{"planes"};
+  pcm::DevBuf<unsigned int> counter{"counter"};   // round tickets (device, one word)
   std::string err;
   pcm_stats stats{};
   uint64_t phase_cycles[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // diagnostic (profiling bit2)
-  uint32_t* nn = nullptr;          // LIO: the <= 5 neighbours (indices into map.pts) of every scan point from the last matching call
-  size_t nn_cap = 0;
+  pcm::DevBuf<uint32_t> nn{"nn"};  // LIO: the <= 5 neighbours (indices into map.pts) of every scan point from the last matching call
   uint32_t next_seq = 0;           // next insertion sequence number of the target point log
   bool lio_planes_valid = false;   // planes of the last pcm_obs_model(rematch=1) belong to the current scan
-  float2* lio_aux = nullptr;       // PCM_FLAG_LIO_REFERENCE_SEMANTICS: residuals_ / point_selected_surf_ of LaserMapping, in the caller's scan order;
-  size_t lio_aux_n = 0, lio_aux_cap = 0;   // they outlive the scan (std::vector::resize semantics, laser_mapping.cc:337-338)
+  pcm::DevBuf<float2> lio_aux{"lio_aux"};   // PCM_FLAG_LIO_REFERENCE_SEMANTICS: residuals_ / point_selected_surf_ of LaserMapping, in the caller's scan order;
+  size_t lio_aux_n = 0;                     // they outlive the scan (std::vector::resize semantics, laser_mapping.cc:337-338)
   void* ws = nullptr;   // batch workspace owned by this context (pcm_api.hip)
   void* ndt_ws = nullptr;   // pclomp NDT: objects + solver machines of a batch (pcm_api.hip)
-  char* pre_arena = nullptr;   // grow-only device scratch of the pre-processing operators
-  size_t pre_arena_cap = 0;
-  char* bfgs = nullptr;        // GICP-BFGS functor: packed correspondence records + partial sums (gicp_bfgs.hip)
-  size_t bfgs_cap = 0, bfgs_m = 0;
+  pcm::DevBuf<char> pre_arena{"pre_arena"};   // grow-only device scratch of the pre-processing operators
+  pcm::DevBuf<char> bfgs{"bfgs"};             // GICP-BFGS functor: packed correspondence records + partial sums (gicp_bfgs.hip)
+  size_t bfgs_m = 0;
   std::vector<double> user_cov[2];   // [0] source, [1] target: covariances handed in by the caller (6 per point, input order); empty = compute
-  int32_t* bfgs_idx = nullptr; // [2][bfgs_idx_cap] source / target index of every packed pair (device-side correspondence step)
-  size_t bfgs_idx_cap = 0;
-  double* bfgs_host = nullptr; // pinned, device-visible: the 14 sums land here without a copy command
+  pcm::DevBuf<int32_t> bfgs_idx{"bfgs_idx"};   // source indices of the packed pairs in the first half, target indices in the second (device-side correspondence step)
+  pcm::PinnedBuf<double> bfgs_host{"bfgs_host"};   // pinned, device-visible: the 14 sums land here without a copy command
   void* loam = nullptr;   // PCM_MODEL_LOAM: maps, features and device state (loam_api.hip)
   void* loam_fe = nullptr;   // PCM_MODEL_LOAM: the front end's cross-frame state and last-frame outputs (loam_features.hip)
   void* occ = nullptr;   // any model: the 2D occupancy map (occ_map.hip)
   int profiling = 0;  // bit0: HIP-event timing of residual launches, bit1: kNN counters
 };
+
+namespace pcm {
+template <typename T> int DevBuf<T>::reserve(pcm_ctx* c, size_t need, size_t new_cap, bool zero) { return reserve(c->stream, &c->err, need, new_cap, zero); }
+template <typename T> int DevBuf<T>::reserve_keep(pcm_ctx* c, size_t need, size_t new_cap, size_t keep) { return reserve_keep(c->stream, &c->err, need, new_cap, keep); }
+template <typename T> int PinnedBuf<T>::reserve(pcm_ctx* c, size_t need, size_t new_cap, unsigned flags) { return reserve(c->stream, &c->err, need, new_cap, flags); }
+}  // namespace pcm

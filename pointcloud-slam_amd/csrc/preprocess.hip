@@ -189,8 +189,7 @@ size_t voxel_downsample_scratch_bytes(size_t n) {
   uint64_t* k = nullptr; uint32_t* v = nullptr;
   (void)rocprim::radix_sort_pairs(nullptr, t1, k, k, v, v, n, 0, 33, nullptr);
   (void)rocprim::exclusive_scan(nullptr, t2, v, v, 0u, n, rocprim::plus<uint32_t>(), nullptr);
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  return up(64) + 2 * up(8 * n) + 4 * up(4 * n) + up(t1) + up(t2);
+  return up256(64) + 2 * up256(8 * n) + 4 * up256(4 * n) + up256(t1) + up256(t2);
 }
 
 // d_in: n records of `stride` bytes (nfields = stride / 4 floats, x y z first); d_out: room for n records.  *n_out receives
@@ -202,7 +201,6 @@ int voxel_downsample_device(hipStream_t stream, const void* d_in, size_t n, size
   if (nfields < 3 || nfields > 16 || (stride % 4) != 0) { *err = "records must be 3..16 floats"; return PCM_ERR_INVALID_ARGUMENT; }
   if (!(leaf > 0.f)) { *err = "leaf size must be > 0"; return PCM_ERR_INVALID_ARGUMENT; }
   const float inv = 1.0f / leaf;
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   size_t tmp_bytes = 0, tmp2_bytes = 0;
   {
     uint64_t* k = nullptr; uint32_t* v = nullptr;
@@ -210,28 +208,23 @@ int voxel_downsample_device(hipStream_t stream, const void* d_in, size_t n, size
     (void)rocprim::exclusive_scan(nullptr, tmp2_bytes, v, v, 0u, n, rocprim::plus<uint32_t>(), stream);
   }
   char* cur = static_cast<char*>(scratch);
-  unsigned int* d_mm = reinterpret_cast<unsigned int*>(cur); cur += up(64);
-  uint64_t* keys = reinterpret_cast<uint64_t*>(cur); cur += up(8 * n);
-  uint64_t* keys_s = reinterpret_cast<uint64_t*>(cur); cur += up(8 * n);
-  uint32_t* vals = reinterpret_cast<uint32_t*>(cur); cur += up(4 * n);
-  uint32_t* vals_s = reinterpret_cast<uint32_t*>(cur); cur += up(4 * n);
-  uint32_t* head = reinterpret_cast<uint32_t*>(cur); cur += up(4 * n);
-  uint32_t* slot = reinterpret_cast<uint32_t*>(cur); cur += up(4 * n);
-  void* tmp = cur; cur += up(tmp_bytes);
+  unsigned int* d_mm = reinterpret_cast<unsigned int*>(cur); cur += up256(64);
+  uint64_t* keys = reinterpret_cast<uint64_t*>(cur); cur += up256(8 * n);
+  uint64_t* keys_s = reinterpret_cast<uint64_t*>(cur); cur += up256(8 * n);
+  uint32_t* vals = reinterpret_cast<uint32_t*>(cur); cur += up256(4 * n);
+  uint32_t* vals_s = reinterpret_cast<uint32_t*>(cur); cur += up256(4 * n);
+  uint32_t* head = reinterpret_cast<uint32_t*>(cur); cur += up256(4 * n);
+  uint32_t* slot = reinterpret_cast<uint32_t*>(cur); cur += up256(4 * n);
+  void* tmp = cur; cur += up256(tmp_bytes);
   void* tmp2 = cur;
   int rc = PCM_OK;
   const unsigned nb = (unsigned)((n + 255) / 256);
   const char* base = static_cast<const char*>(d_in);
-#define CK(x)                                                                    \
-  do {                                                                           \
-    hipError_t e_ = (x);                                                         \
-    if (e_ != hipSuccess) { *err = std::string(#x) + ": " + hipGetErrorString(e_); return PCM_ERR_HIP; } \
-  } while (0)
   unsigned int h_mm[7] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u};
-  CK(hipMemcpyAsync(d_mm, h_mm, sizeof(h_mm), hipMemcpyHostToDevice, stream));
+  PCM_HIPCK_ERR(err, hipMemcpyAsync(d_mm, h_mm, sizeof(h_mm), hipMemcpyHostToDevice, stream));
   k_vg_minmax<<<nb, 256, 0, stream>>>(base, stride, (uint32_t)n, d_mm);
-  CK(hipMemcpyAsync(h_mm, d_mm, sizeof(h_mm), hipMemcpyDeviceToHost, stream));
-  CK(hipStreamSynchronize(stream));
+  PCM_HIPCK_ERR(err, hipMemcpyAsync(h_mm, d_mm, sizeof(h_mm), hipMemcpyDeviceToHost, stream));
+  PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
   if (h_mm[6] == 0) return PCM_OK;   // no finite point
   float mn[3], mx[3];
   for (int a = 0; a < 3; a++) { mn[a] = ord2f(h_mm[a]); mx[a] = ord2f(h_mm[3 + a]); }
@@ -241,24 +234,23 @@ int voxel_downsample_device(hipStream_t stream, const void* d_in, size_t n, size
   for (int a = 0; a < 3; a++) { min_b[a] = (int)floorf(mn[a] * inv); max_b[a] = (int)floorf(mx[a] * inv); }
   const long long div0 = (long long)max_b[0] - min_b[0] + 1, div1 = (long long)max_b[1] - min_b[1] + 1;
   k_vg_keys<<<nb, 256, 0, stream>>>(base, stride, (uint32_t)n, inv, min_b[0], min_b[1], min_b[2], div0, div0 * div1, keys, vals);
-  CK(hipGetLastError());
-  CK(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_s, vals, vals_s, n, 0, 33, stream));
+  PCM_HIPCK_ERR(err, hipGetLastError());
+  PCM_HIPCK_ERR(err, rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_s, vals, vals_s, n, 0, 33, stream));
   k_vg_heads<<<nb, 256, 0, stream>>>(keys_s, (uint32_t)n, head);
-  CK(hipGetLastError());
-  CK(rocprim::exclusive_scan(tmp2, tmp2_bytes, head, slot, 0u, n, rocprim::plus<uint32_t>(), stream));
+  PCM_HIPCK_ERR(err, hipGetLastError());
+  PCM_HIPCK_ERR(err, rocprim::exclusive_scan(tmp2, tmp2_bytes, head, slot, 0u, n, rocprim::plus<uint32_t>(), stream));
   uint32_t last[2];
-  CK(hipMemcpyAsync(&last[0], slot + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  CK(hipMemcpyAsync(&last[1], head + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  CK(hipStreamSynchronize(stream));
+  PCM_HIPCK_ERR(err, hipMemcpyAsync(&last[0], slot + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  PCM_HIPCK_ERR(err, hipMemcpyAsync(&last[1], head + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
   const uint32_t ncells = last[0] + last[1];
   uint32_t* pos = vals;   // the unsorted value array is free after the sort
   k_vg_head_pos<<<nb, 256, 0, stream>>>(head, slot, (uint32_t)n, pos);
   k_vg_average<<<(ncells + 3) / 4, 256, 0, stream>>>(base, stride, nfields, vals_s, pos, ncells, h_mm[6], d_out);
-  CK(hipGetLastError());
-  CK(hipStreamSynchronize(stream));
+  PCM_HIPCK_ERR(err, hipGetLastError());
+  PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
   *n_out = (size_t)ncells;
   return rc;
-#undef CK
 }
 
 // ---------------------------------------------------------------------------
@@ -309,43 +301,35 @@ size_t livox_filter_scratch_bytes(size_t n) {
   size_t t = 0;
   uint32_t* v = nullptr;
   (void)rocprim::exclusive_scan(nullptr, t, v, v, 0u, n, rocprim::plus<uint32_t>(), nullptr);
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  return 2 * up(4 * n) + up(t);
+  return 2 * up256(4 * n) + up256(t);
 }
 
 int livox_filter_device(hipStream_t stream, const void* d_msg, size_t n, int num_scans, int point_filter_num, double blind, void* d_out, size_t* n_out, void* scratch, std::string* err) {
   *n_out = 0;
   if (n < 2) return PCM_OK;
   if (point_filter_num < 1 || num_scans < 0) { *err = "point_filter_num must be >= 1"; return PCM_ERR_INVALID_ARGUMENT; }
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   char* cur = static_cast<char*>(scratch);
-  uint32_t* flag = reinterpret_cast<uint32_t*>(cur); cur += up(4 * n);
-  uint32_t* pos = reinterpret_cast<uint32_t*>(cur); cur += up(4 * n);
+  uint32_t* flag = reinterpret_cast<uint32_t*>(cur); cur += up256(4 * n);
+  uint32_t* pos = reinterpret_cast<uint32_t*>(cur); cur += up256(4 * n);
   void* tmp = cur;
   size_t tmp_bytes = 0;
   (void)rocprim::exclusive_scan(nullptr, tmp_bytes, flag, pos, 0u, n, rocprim::plus<uint32_t>(), stream);
   const unsigned nb = (unsigned)((n + 255) / 256);
   const LivoxRaw* msg = static_cast<const LivoxRaw*>(d_msg);
-#define CK(x)                                                                    \
-  do {                                                                           \
-    hipError_t e_ = (x);                                                         \
-    if (e_ != hipSuccess) { *err = std::string(#x) + ": " + hipGetErrorString(e_); return PCM_ERR_HIP; } \
-  } while (0)
   k_livox_flags<<<nb, 256, 0, stream>>>(msg, (uint32_t)n, num_scans, (uint32_t)point_filter_num, blind * blind, flag);
-  CK(hipGetLastError());
-  CK(rocprim::exclusive_scan(tmp, tmp_bytes, flag, pos, 0u, n, rocprim::plus<uint32_t>(), stream));
+  PCM_HIPCK_ERR(err, hipGetLastError());
+  PCM_HIPCK_ERR(err, rocprim::exclusive_scan(tmp, tmp_bytes, flag, pos, 0u, n, rocprim::plus<uint32_t>(), stream));
   uint32_t tails[2] = {0, 0};
-  CK(hipMemcpyAsync(&tails[0], flag + (n - 1), 4, hipMemcpyDeviceToHost, stream));
-  CK(hipMemcpyAsync(&tails[1], pos + (n - 1), 4, hipMemcpyDeviceToHost, stream));
-  CK(hipStreamSynchronize(stream));
+  PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[0], flag + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+  PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[1], pos + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+  PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
   const size_t m = (size_t)tails[0] + tails[1];
   if (m) {
     k_livox_write<<<nb, 256, 0, stream>>>(msg, (uint32_t)n, flag, pos, static_cast<float4*>(d_out));
-    CK(hipGetLastError());
+    PCM_HIPCK_ERR(err, hipGetLastError());
   }
   *n_out = m;
   return PCM_OK;
-#undef CK
 }
 
 }  // namespace pcm

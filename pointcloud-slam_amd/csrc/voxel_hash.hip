@@ -380,11 +380,8 @@ struct BuildScratch {
   }
 };
 
-// grow-only arrays of a TargetMap: a quarter of headroom, the first keep_elems elements stay
-template <typename T>
-static int grow(T** p, size_t* cap, size_t need, size_t keep_elems, hipStream_t stream, std::string* err, const char* what) {
-  return dev_reserve_keep(p, cap, need, need + need / 4 + 1024, keep_elems, stream, err, what);
-}
+// capacity of a grow-only array of a TargetMap that must hold `need` elements: a quarter of headroom
+static inline size_t headroom(size_t need) { return need + need / 4 + 1024; }
 
 // Build the voxel hash of the point log `d_pts` into `map`, or -- `n_indexed` > 0: the first n_indexed log points are what
 // map->keys_s / idx_s index -- merge the points appended since.  Host syncs: voxel / brick counts (array sizes), once more after
@@ -399,87 +396,73 @@ int build_target_map(hipStream_t stream, float4* d_pts, uint32_t* n_inout, float
   int* d_flags = nullptr;  // [0] out-of-range flag, [1] brick count, [2] most points in one voxel, [3] LRU hazards, [4] voxels, [5] log points alive
   void *tmp = nullptr, *tmp2 = nullptr;
   size_t tmp_bytes = 0, tmp2_bytes = 0;
-  int rc = PCM_OK;
   uint32_t hazards = 0;
   BuildScratch sc;
   // ivox3d.h:67  inv_resolution_ = 1.0 / resolution_ (float);  pcl::VoxelGrid: inverse_leaf_size_ = 1 / leaf_size_ in float
   const float inv_res = coord_mode == COORD_FLOOR_MUL ? 1.0f / res : (float)(1.0 / res);
-#define CK(x)                                                                    \
-  do {                                                                           \
-    hipError_t e_ = (x);                                                         \
-    if (e_ != hipSuccess) { *err = std::string(#x) + ": " + hipGetErrorString(e_); rc = PCM_ERR_HIP; goto done; } \
-  } while (0)
-#define RC(x) do { rc = (x); if (rc != PCM_OK) goto done; } while (0)
+#define RC(x) do { const int rc_ = (x); if (rc_ != PCM_OK) return rc_; } while (0)
   map->valid = false;
-  if (!map->h_ctr && hipHostMalloc(reinterpret_cast<void**>(&map->h_ctr), kCtrInts * sizeof(int)) != hipSuccess) { *err = "hipHostMalloc(counters)"; return PCM_ERR_HIP; }
-  if (incremental) {   // everything an update with eviction takes, rounded up: 24 B per new point, 52 B per log point, sort / scan temporaries
-    const size_t need = 24 * (size_t)(n - n_indexed) + 56 * (size_t)n + ((size_t)16 << 20);
-    if (need > map->arena_cap) {
-      (void)hipStreamSynchronize(stream);
-      if (map->arena) hipFree(map->arena);
-      map->arena = nullptr; map->arena_cap = 0;
-      const size_t nc = need + need / 4;
-      CK(hipMalloc(reinterpret_cast<void**>(&map->arena), nc));
-      map->arena_cap = nc;
+  if (map->h_ctr.reserve(stream, err, kCtrInts, kCtrInts) != PCM_OK) return PCM_ERR_HIP;
+  // the build proper; its scratch and, after a failure, the map are released behind it
+  const int rc = [&]() -> int {
+    if (incremental) {   // everything an update with eviction takes, rounded up: 24 B per new point, 52 B per log point, sort / scan temporaries
+      const size_t need = 24 * (size_t)(n - n_indexed) + 56 * (size_t)n + ((size_t)16 << 20);
+      RC(map->arena.reserve(stream, err, need, need + need / 4));
+      sc.base = map->arena; sc.cap = map->arena.cap;
     }
-    sc.base = map->arena; sc.cap = map->arena_cap;
-  }
-  CK(sc.get(reinterpret_cast<void**>(&d_flags), kCtrInts * sizeof(int), stream));
-  CK(hipMemsetAsync(d_flags, 0, kCtrInts * sizeof(int), stream));
-  {
+    PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&d_flags), kCtrInts * sizeof(int), stream));
+    PCM_HIPCK_ERR(err, hipMemsetAsync(d_flags, 0, kCtrInts * sizeof(int), stream));
     // ---- 1. the sorted index (key, log position) of all n log points in map->keys_s / idx_s ------------------------------
     const uint32_t first = incremental ? n_indexed : 0u, m = n - first;
-    RC(grow(&map->keys_s, &map->keys_cap, n, incremental ? n_indexed : 0, stream, err, "keys_s"));
-    RC(grow(&map->idx_s, &map->idx_cap, n, incremental ? n_indexed : 0, stream, err, "idx_s"));
-    RC(grow(&map->keys_t, &map->keys_t_cap, n, 0, stream, err, "keys_t"));
-    RC(grow(&map->idx_t, &map->idx_t_cap, n, 0, stream, err, "idx_t"));
+    RC(map->keys_s.reserve_keep(stream, err, n, headroom(n), first));   // an update keeps the index it merges into
+    RC(map->idx_s.reserve_keep(stream, err, n, headroom(n), first));
+    RC(map->keys_t.reserve_keep(stream, err, n, headroom(n), 0));
+    RC(map->idx_t.reserve_keep(stream, err, n, headroom(n), 0));
     if (m > 0) {
-      CK(sc.get(reinterpret_cast<void**>(&keys_b), sizeof(uint64_t) * m, stream));
-      CK(sc.get(reinterpret_cast<void**>(&keys_bs), sizeof(uint64_t) * m, stream));
-      CK(sc.get(reinterpret_cast<void**>(&idx_b), sizeof(uint32_t) * m, stream));
-      CK(sc.get(reinterpret_cast<void**>(&idx_bs), sizeof(uint32_t) * m, stream));
+      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&keys_b), sizeof(uint64_t) * m, stream));
+      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&keys_bs), sizeof(uint64_t) * m, stream));
+      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&idx_b), sizeof(uint32_t) * m, stream));
+      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&idx_bs), sizeof(uint32_t) * m, stream));
       k_point_keys_at<<<cdiv(m, 256), 256, 0, stream>>>(d_pts, first, m, res, inv_res, coord_mode, keys_b, idx_b, d_flags);
-      CK(hipGetLastError());
+      PCM_HIPCK_ERR(err, hipGetLastError());
       uint64_t* ks = incremental ? keys_bs : map->keys_s;   // a full build sorts straight into the persistent index
       uint32_t* is = incremental ? idx_bs : map->idx_s;
-      CK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys_b, ks, idx_b, is, m, 0, 63, stream));
-      CK(sc.get(reinterpret_cast<void**>(&tmp), tmp_bytes, stream));
-      CK(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys_b, ks, idx_b, is, m, 0, 63, stream));
+      PCM_HIPCK_ERR(err, rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys_b, ks, idx_b, is, m, 0, 63, stream));
+      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&tmp), tmp_bytes, stream));
+      PCM_HIPCK_ERR(err, rocprim::radix_sort_pairs(tmp, tmp_bytes, keys_b, ks, idx_b, is, m, 0, 63, stream));
       if (incremental) {
         k_merge_old<<<cdiv(n_indexed, 256), 256, 0, stream>>>(map->keys_s, map->idx_s, n_indexed, keys_bs, m, map->keys_t, map->idx_t);
         k_merge_new<<<cdiv(m, 256), 256, 0, stream>>>(map->keys_s, n_indexed, keys_bs, idx_bs, m, map->keys_t, map->idx_t);
-        CK(hipGetLastError());
-        std::swap(map->keys_s, map->keys_t); std::swap(map->keys_cap, map->keys_t_cap);
-        std::swap(map->idx_s, map->idx_t); std::swap(map->idx_cap, map->idx_t_cap);
+        PCM_HIPCK_ERR(err, hipGetLastError());
+        map->keys_s.swap(map->keys_t);
+        map->idx_s.swap(map->idx_t);
       }
     }
     map->index_n = 0;   // until this build is through
     // ---- 2. voxel heads, ranks; counts to the host -----------------------------------------------------------------------
-    CK(sc.get(reinterpret_cast<void**>(&vflag), sizeof(uint32_t) * n, stream));
-    CK(sc.get(reinterpret_cast<void**>(&vrank), sizeof(uint32_t) * n, stream));
+    PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&vflag), sizeof(uint32_t) * n, stream));
+    PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&vrank), sizeof(uint32_t) * n, stream));
     uint32_t nvox = 0, nbricks = 0;
     auto heads = [&](uint32_t cnt) -> int {
-      CK(hipMemsetAsync(d_flags + 8, 0, kBrickCountShards * sizeof(int), stream));
+      PCM_HIPCK_ERR(err, hipMemsetAsync(d_flags + 8, 0, kBrickCountShards * sizeof(int), stream));
       k_head_flags<<<cdiv(cnt, 256), 256, 0, stream>>>(map->keys_s, cnt, vflag, reinterpret_cast<unsigned int*>(d_flags + 8));
-      CK(hipGetLastError());
+      PCM_HIPCK_ERR(err, hipGetLastError());
       if (!tmp2) {
-        CK(rocprim::exclusive_scan(nullptr, tmp2_bytes, vflag, vrank, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-        CK(sc.get(reinterpret_cast<void**>(&tmp2), tmp2_bytes, stream));
+        PCM_HIPCK_ERR(err, rocprim::exclusive_scan(nullptr, tmp2_bytes, vflag, vrank, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
+        PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&tmp2), tmp2_bytes, stream));
       }
       {
         size_t tb = tmp2_bytes;
-        CK(rocprim::exclusive_scan(tmp2, tb, vflag, vrank, 0u, (size_t)cnt, rocprim::plus<uint32_t>(), stream));
+        PCM_HIPCK_ERR(err, rocprim::exclusive_scan(tmp2, tb, vflag, vrank, 0u, (size_t)cnt, rocprim::plus<uint32_t>(), stream));
       }
       k_count_voxels<<<1, 1, 0, stream>>>(vflag, vrank, cnt, d_flags);
-      CK(hipMemcpyAsync(map->h_ctr, d_flags, kCtrInts * sizeof(int), hipMemcpyDeviceToHost, stream));   // one copy into pinned memory
-      CK(hipStreamSynchronize(stream));
-      if (map->h_ctr[0]) { *err = "target point outside the +-2^20 voxel range (or not finite)"; rc = PCM_ERR_OUT_OF_RANGE; goto done; }
+      PCM_HIPCK_ERR(err, hipMemcpyAsync(map->h_ctr, d_flags, kCtrInts * sizeof(int), hipMemcpyDeviceToHost, stream));   // one copy into pinned memory
+      PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
+      if (map->h_ctr[0]) { *err = "target point outside the +-2^20 voxel range (or not finite)"; return PCM_ERR_OUT_OF_RANGE; }
       nvox = (uint32_t)map->h_ctr[4];
       nbricks = 0;
       for (int k = 0; k < kBrickCountShards; k++) nbricks += (uint32_t)map->h_ctr[8 + k];
       return PCM_OK;
-    done:
-      return rc;
     };
     RC(heads(n));
     if (subsort && !incremental) {   // permute the index inside the voxels (the heads and ranks above stay valid: same keys at the same places)
@@ -488,14 +471,14 @@ int build_target_map(hipStream_t stream, float4* d_pts, uint32_t* n_inout, float
       size_t tmp5_bytes = 0;
       int bits = 9;
       while (bits < 41 && (1ull << (bits - 9)) < (unsigned long long)nvox) bits++;
-      CK(sc.get(reinterpret_cast<void**>(&k2), sizeof(uint64_t) * n, stream));
-      CK(sc.get(reinterpret_cast<void**>(&k2s), sizeof(uint64_t) * n, stream));
+      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&k2), sizeof(uint64_t) * n, stream));
+      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&k2s), sizeof(uint64_t) * n, stream));
       k_subvoxel_keys<<<cdiv(n, 256), 256, 0, stream>>>(d_pts, map->idx_s, vflag, vrank, n, inv_res, k2);
-      CK(hipGetLastError());
-      CK(rocprim::radix_sort_pairs(nullptr, tmp5_bytes, k2, k2s, map->idx_s, map->idx_t, n, 0, bits, stream));
-      CK(sc.get(&tmp5, tmp5_bytes, stream));
-      CK(rocprim::radix_sort_pairs(tmp5, tmp5_bytes, k2, k2s, map->idx_s, map->idx_t, n, 0, bits, stream));
-      std::swap(map->idx_s, map->idx_t); std::swap(map->idx_cap, map->idx_t_cap);
+      PCM_HIPCK_ERR(err, hipGetLastError());
+      PCM_HIPCK_ERR(err, rocprim::radix_sort_pairs(nullptr, tmp5_bytes, k2, k2s, map->idx_s.p, map->idx_t.p, n, 0, bits, stream));
+      PCM_HIPCK_ERR(err, sc.get(&tmp5, tmp5_bytes, stream));
+      PCM_HIPCK_ERR(err, rocprim::radix_sort_pairs(tmp5, tmp5_bytes, k2, k2s, map->idx_s.p, map->idx_t.p, n, 0, bits, stream));
+      map->idx_s.swap(map->idx_t);
     }
     if (capacity_voxels > 1 && nvox > capacity_voxels - 1) {
       // ---- 3. LRU eviction: keep the (capacity - 1) most recently touched voxels; log and index are compacted in place ------
@@ -505,98 +488,82 @@ int build_target_map(hipStream_t stream, float4* d_pts, uint32_t* n_inout, float
       void *tmp3 = nullptr, *tmp4 = nullptr;
       size_t tmp3_bytes = 0, tmp4_bytes = 0;
       const uint32_t* d_cutoff = nullptr;
-      int rc2 = PCM_OK;
-#define CK2(x)                                                                   \
-  do {                                                                           \
-    hipError_t e_ = (x);                                                         \
-    if (e_ != hipSuccess) { *err = std::string(#x) + ": " + hipGetErrorString(e_); rc2 = PCM_ERR_HIP; goto evict_done; } \
-  } while (0)
-      CK2(sc.get(reinterpret_cast<void**>(&vlast), sizeof(uint32_t) * nvox, stream));
-      CK2(sc.get(reinterpret_cast<void**>(&vsorted), sizeof(uint32_t) * nvox, stream));
-      CK2(sc.get(reinterpret_cast<void**>(&vfirst), sizeof(uint32_t) * nvox, stream));
-      CK2(sc.get(reinterpret_cast<void**>(&alive), sizeof(uint32_t) * n, stream));
-      CK2(sc.get(reinterpret_cast<void**>(&pos), sizeof(uint32_t) * n, stream));
-      CK2(sc.get(reinterpret_cast<void**>(&alive_s), sizeof(uint32_t) * n, stream));
-      CK2(sc.get(reinterpret_cast<void**>(&pos_s), sizeof(uint32_t) * n, stream));
-      CK2(sc.get(reinterpret_cast<void**>(&tmp_log), sizeof(float4) * n, stream));
+      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&vlast), sizeof(uint32_t) * nvox, stream));
+      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&vsorted), sizeof(uint32_t) * nvox, stream));
+      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&vfirst), sizeof(uint32_t) * nvox, stream));
+      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&alive), sizeof(uint32_t) * n, stream));
+      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&pos), sizeof(uint32_t) * n, stream));
+      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&alive_s), sizeof(uint32_t) * n, stream));
+      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&pos_s), sizeof(uint32_t) * n, stream));
+      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&tmp_log), sizeof(float4) * n, stream));
       k_voxel_firsts<<<cdiv(n, 256), 256, 0, stream>>>(vflag, vrank, n, vfirst);
       k_voxel_last_from_firsts<<<cdiv(nvox, 256), 256, 0, stream>>>(d_pts, map->idx_s, vfirst, nvox, n, vlast);
-      CK2(hipGetLastError());
-      CK2(rocprim::radix_sort_keys(nullptr, tmp3_bytes, vlast, vsorted, nvox, 0, 32, stream));
-      CK2(sc.get(reinterpret_cast<void**>(&tmp3), tmp3_bytes, stream));
-      CK2(rocprim::radix_sort_keys(tmp3, tmp3_bytes, vlast, vsorted, nvox, 0, 32, stream));
+      PCM_HIPCK_ERR(err, hipGetLastError());
+      PCM_HIPCK_ERR(err, rocprim::radix_sort_keys(nullptr, tmp3_bytes, vlast, vsorted, nvox, 0, 32, stream));
+      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&tmp3), tmp3_bytes, stream));
+      PCM_HIPCK_ERR(err, rocprim::radix_sort_keys(tmp3, tmp3_bytes, vlast, vsorted, nvox, 0, 32, stream));
       d_cutoff = vsorted + (nvox - keep);   // the smallest surviving last-touch stamp, read on the device
       if (incremental && n_indexed < n) {   // the batch = the log points from n_indexed on
         k_lru_hazards<<<cdiv(nvox, 256), 256, 0, stream>>>(d_pts, map->idx_s, vfirst, vlast, nvox, n, d_pts + n_indexed, d_cutoff, reinterpret_cast<unsigned int*>(d_flags + 3));
-        CK2(hipGetLastError());
+        PCM_HIPCK_ERR(err, hipGetLastError());
       }
       k_mark_alive_dev<<<cdiv(n, 256), 256, 0, stream>>>(map->idx_s, vflag, vrank, vlast, d_cutoff, n, alive);
-      CK2(hipGetLastError());
-      CK2(rocprim::exclusive_scan(nullptr, tmp4_bytes, alive, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-      CK2(sc.get(reinterpret_cast<void**>(&tmp4), tmp4_bytes, stream));
-      { size_t tb = tmp4_bytes; CK2(rocprim::exclusive_scan(tmp4, tb, alive, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream)); }
+      PCM_HIPCK_ERR(err, hipGetLastError());
+      PCM_HIPCK_ERR(err, rocprim::exclusive_scan(nullptr, tmp4_bytes, alive, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
+      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&tmp4), tmp4_bytes, stream));
+      { size_t tb = tmp4_bytes; PCM_HIPCK_ERR(err, rocprim::exclusive_scan(tmp4, tb, alive, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream)); }
       k_alive_sorted<<<cdiv(n, 256), 256, 0, stream>>>(map->idx_s, alive, n, alive_s);
-      { size_t tb = tmp4_bytes; CK2(rocprim::exclusive_scan(tmp4, tb, alive_s, pos_s, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream)); }
+      { size_t tb = tmp4_bytes; PCM_HIPCK_ERR(err, rocprim::exclusive_scan(tmp4, tb, alive_s, pos_s, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream)); }
       k_compact_log<<<cdiv(n, 256), 256, 0, stream>>>(d_pts, alive, pos, n, tmp_log);
       k_compact_index<<<cdiv(n, 256), 256, 0, stream>>>(map->keys_s, map->idx_s, alive, pos, pos_s, n, map->keys_t, map->idx_t);
       k_count_alive<<<1, 1, 0, stream>>>(alive, pos, n, d_flags);
-      CK2(hipGetLastError());
-      CK2(hipMemcpyAsync(map->h_ctr, d_flags, kCtrInts * sizeof(int), hipMemcpyDeviceToHost, stream));
-      CK2(hipStreamSynchronize(stream));
+      PCM_HIPCK_ERR(err, hipGetLastError());
+      PCM_HIPCK_ERR(err, hipMemcpyAsync(map->h_ctr, d_flags, kCtrInts * sizeof(int), hipMemcpyDeviceToHost, stream));
+      PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
       n = (uint32_t)map->h_ctr[5];
       hazards = (uint32_t)map->h_ctr[3];
-      CK2(hipMemcpyAsync(d_pts, tmp_log, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, stream));
-      std::swap(map->keys_s, map->keys_t); std::swap(map->keys_cap, map->keys_t_cap);
-      std::swap(map->idx_s, map->idx_t); std::swap(map->idx_cap, map->idx_t_cap);
+      PCM_HIPCK_ERR(err, hipMemcpyAsync(d_pts, tmp_log, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, stream));
+      map->keys_s.swap(map->keys_t);
+      map->idx_s.swap(map->idx_t);
       *n_inout = n;
-    evict_done:
-#undef CK2
-      if (rc2 != PCM_OK) { rc = rc2; goto done; }
       RC(heads(n));   // the survivors' voxel heads and ranks
     }
     // ---- 4. tables from the sorted index (capacity-managed arrays: a sliding map allocates nothing in the steady state) ----
     uint32_t cap = 1024;
     while (cap < 4ull * nbricks) cap <<= 1;
-    if (cap > kMaxBrickSlots) { *err = "too many occupied bricks"; rc = PCM_ERR_OUT_OF_RANGE; goto done; }
-    if (cap > map->bricks_cap) {   // the table only grows; a smaller table uses the front of the allocation
-      (void)hipStreamSynchronize(stream);
-      if (map->bricks) hipFree(map->bricks);
-      if (map->bmask) hipFree(map->bmask);
-      if (map->bpref) hipFree(map->bpref);
-      map->bricks = nullptr; map->bmask = nullptr; map->bpref = nullptr; map->bricks_cap = 0;
-      CK(hipMalloc(&map->bricks, sizeof(BrickSlot) * (size_t)cap));
-      CK(hipMalloc(&map->bmask, sizeof(uint32_t) * 16 * (size_t)cap));
-      CK(hipMalloc(&map->bpref, sizeof(uint16_t) * 16 * (size_t)cap));
-      map->bricks_cap = cap;
-    }
-    RC(grow(&map->vox_start, &map->vox_cap, (size_t)nvox + 1, 0, stream, err, "vox_start"));
-    RC(grow(&map->pts, &map->pts_cap, (size_t)n, 0, stream, err, "pts"));
-    CK(hipMemsetAsync(map->bricks, 0xFF, sizeof(BrickSlot) * (size_t)cap, stream));
-    CK(hipMemsetAsync(map->bmask, 0, sizeof(uint32_t) * 16 * (size_t)cap, stream));
-    CK(hipMemsetAsync(map->bpref, 0, sizeof(uint16_t) * 16 * (size_t)cap, stream));
+    if (cap > kMaxBrickSlots) { *err = "too many occupied bricks"; return PCM_ERR_OUT_OF_RANGE; }
+    // the table only grows; a smaller table uses the front of the allocations
+    RC(map->bricks.reserve(stream, err, cap, cap));
+    RC(map->bmask.reserve(stream, err, 16 * (size_t)cap, 16 * (size_t)cap));
+    RC(map->bpref.reserve(stream, err, 16 * (size_t)cap, 16 * (size_t)cap));
+    RC(map->vox_start.reserve_keep(stream, err, (size_t)nvox + 1, headroom((size_t)nvox + 1), 0));
+    RC(map->pts.reserve_keep(stream, err, (size_t)n, headroom((size_t)n), 0));
+    PCM_HIPCK_ERR(err, hipMemsetAsync(map->bricks, 0xFF, sizeof(BrickSlot) * (size_t)cap, stream));
+    PCM_HIPCK_ERR(err, hipMemsetAsync(map->bmask, 0, sizeof(uint32_t) * 16 * (size_t)cap, stream));
+    PCM_HIPCK_ERR(err, hipMemsetAsync(map->bpref, 0, sizeof(uint16_t) * 16 * (size_t)cap, stream));
     k_insert_bricks<<<cdiv(n, 256), 256, 0, stream>>>(map->keys_s, vrank, n, map->bricks, cap - 1);
-    CK(hipGetLastError());
+    PCM_HIPCK_ERR(err, hipGetLastError());
     k_fill_voxels<<<cdiv(n, 256), 256, 0, stream>>>(map->keys_s, vflag, vrank, n, nvox, map->vox_start, map->bricks, map->bmask, cap - 1);
-    CK(hipGetLastError());
+    PCM_HIPCK_ERR(err, hipGetLastError());
     k_finalize_bricks<<<cdiv(cap, 256), 256, 0, stream>>>(map->bricks, map->bmask, map->bpref, map->vox_start, cap);
-    CK(hipGetLastError());
+    PCM_HIPCK_ERR(err, hipGetLastError());
     k_gather_points<<<cdiv(n, 256), 256, 0, stream>>>(d_pts, map->idx_s, map->keys_s, vrank, map->vox_start, n, map->pts);
-    CK(hipGetLastError());
+    PCM_HIPCK_ERR(err, hipGetLastError());
     k_max_voxel_points<<<cdiv(nvox, 1024), 256, 0, stream>>>(map->vox_start, nvox, reinterpret_cast<unsigned int*>(d_flags + 2));
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(map->h_ctr, d_flags, kCtrInts * sizeof(int), hipMemcpyDeviceToHost, stream));   // complete at the synchronize below
-    if (map->gvox) { (void)hipStreamSynchronize(stream); hipFree(map->gvox); map->gvox = nullptr; }
-    if (map->order && !keep_order) { (void)hipStreamSynchronize(stream); hipFree(map->order); map->order = nullptr; map->order_cap = 0; }
+    PCM_HIPCK_ERR(err, hipGetLastError());
+    PCM_HIPCK_ERR(err, hipMemcpyAsync(map->h_ctr, d_flags, kCtrInts * sizeof(int), hipMemcpyDeviceToHost, stream));   // complete at the synchronize below
+    if (map->gvox) { (void)hipStreamSynchronize(stream); map->gvox.release(); }   // rebuilt at its exact size below, when asked for
+    if (map->order && !keep_order) { (void)hipStreamSynchronize(stream); map->order.release(); }
     if (keep_order) {   // a persistent copy of the input index of every map point (capacity-managed: a scan per registration re-uses it)
-      RC(grow(&map->order, &map->order_cap, (size_t)n, 0, stream, err, "order"));
-      CK(hipMemcpyAsync(map->order, map->idx_s, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice, stream));
+      RC(map->order.reserve_keep(stream, err, (size_t)n, headroom((size_t)n), 0));
+      PCM_HIPCK_ERR(err, hipMemcpyAsync(map->order, map->idx_s, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice, stream));
     }
     if (want_gauss) {
-      CK(hipMalloc(&map->gvox, sizeof(GaussVoxel) * ((size_t)nvox + 1)));
+      RC(map->gvox.reserve(stream, err, (size_t)nvox + 1, (size_t)nvox + 1));
       k_gauss_voxels<<<cdiv(nvox, 128), 128, 0, stream>>>(map->pts, map->vox_start, nvox, map->gvox);
-      CK(hipGetLastError());
+      PCM_HIPCK_ERR(err, hipGetLastError());
     }
-    CK(hipStreamSynchronize(stream));
+    PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
     map->max_voxel_points = (uint32_t)map->h_ctr[2];
     map->cap = cap;
     map->num_voxels = nvox;
@@ -607,13 +574,12 @@ int build_target_map(hipStream_t stream, float4* d_pts, uint32_t* n_inout, float
     map->coord_mode = coord_mode;
     map->index_n = n;
     map->valid = true;
-  }
-done:
+    return PCM_OK;
+  }();
   sc.release(stream);
   if (lru_hazards) *lru_hazards = hazards;
   if (rc != PCM_OK) map->release();
   return rc;
-#undef CK
 #undef RC
 }
 
@@ -708,61 +674,44 @@ __global__ void k_batch_gather32(const SortJob* __restrict__ jobs, const uint32_
 int sort_sources_batched(hipStream_t stream, const SortJob* d_jobs, int njobs, uint32_t max_n, uint32_t total, const float* d_guesses, float res,
                          SortScratch* ws, std::string* err) {
   if (total == 0 || njobs == 0) return PCM_OK;
-  int rc = PCM_OK;
-#define CK(x)                                                                    \
-  do {                                                                           \
-    hipError_t e_ = (x);                                                         \
-    if (e_ != hipSuccess) { *err = std::string(#x) + ": " + hipGetErrorString(e_); rc = PCM_ERR_HIP; goto done; } \
-  } while (0)
   {
     int pair_bits = 1;
     while ((1 << pair_bits) < njobs) pair_bits++;
     size_t need = 0;
     if (total > ws->cap) {
-      hipFree(ws->keys); hipFree(ws->vals); hipFree(ws->tmp);
-      ws->keys = nullptr; ws->vals = nullptr; ws->tmp = nullptr; ws->cap = 0; ws->tmp_bytes = 0;
-      CK(hipMalloc(&ws->keys, sizeof(uint64_t) * 2 * (size_t)total));
-      CK(hipMalloc(&ws->vals, sizeof(uint32_t) * 2 * (size_t)total));
+      ws->cap = 0;
+      int rc = ws->keys.reserve(stream, err, 2 * (size_t)total, 2 * (size_t)total);
+      if (rc == PCM_OK) rc = ws->vals.reserve(stream, err, 2 * (size_t)total, 2 * (size_t)total);
+      if (rc != PCM_OK) return rc;
+      ws->tmp.release();   // sized anew below (the stream is idle: the arrays above were just replaced)
       ws->cap = total;
     }
-    uint64_t* keys_s = ws->keys + ws->cap;
-    uint32_t* vals_s = ws->vals + ws->cap;
+    uint64_t* keys_s = ws->keys.p + ws->cap;
+    uint32_t* vals_s = ws->vals.p + ws->cap;
     if (pair_bits <= 8) {   // one 32-bit word per point (the key buffers are re-used as 32-bit arrays)
       const int mb = 32 - pair_bits;
-      uint32_t* k32 = reinterpret_cast<uint32_t*>(ws->keys);
+      uint32_t* k32 = reinterpret_cast<uint32_t*>(ws->keys.p);
       uint32_t* k32_s = k32 + ws->cap;
-      CK(rocprim::radix_sort_pairs(nullptr, need, k32, k32_s, ws->vals, vals_s, total, 0, 32, stream));
-      if (need > ws->tmp_bytes) {
-        hipFree(ws->tmp);
-        ws->tmp = nullptr; ws->tmp_bytes = 0;
-        CK(hipMalloc(&ws->tmp, need));
-        ws->tmp_bytes = need;
-      }
+      PCM_HIPCK_ERR(err, rocprim::radix_sort_pairs(nullptr, need, k32, k32_s, ws->vals.p, vals_s, total, 0, 32, stream));
+      if (need > ws->tmp.cap && ws->tmp.reserve(stream, err, need, need) != PCM_OK) return PCM_ERR_HIP;
       k_batch_morton_keys32<<<dim3(cdiv(max_n, 256), (unsigned)njobs), 256, 0, stream>>>(d_jobs, d_guesses, (float)(1.0 / res), mb, k32, ws->vals);
-      CK(hipGetLastError());
-      need = ws->tmp_bytes;
-      CK(rocprim::radix_sort_pairs(ws->tmp, need, k32, k32_s, ws->vals, vals_s, total, 0, 32, stream));
+      PCM_HIPCK_ERR(err, hipGetLastError());
+      need = ws->tmp.cap;
+      PCM_HIPCK_ERR(err, rocprim::radix_sort_pairs(ws->tmp.p, need, k32, k32_s, ws->vals.p, vals_s, total, 0, 32, stream));
       k_batch_gather32<<<cdiv(total, 256), 256, 0, stream>>>(d_jobs, k32_s, vals_s, total, mb);
-      CK(hipGetLastError());
-      goto done;
+      PCM_HIPCK_ERR(err, hipGetLastError());
+      return PCM_OK;
     }
-    CK(rocprim::radix_sort_pairs(nullptr, need, ws->keys, keys_s, ws->vals, vals_s, total, 0, 32 + pair_bits, stream));
-    if (need > ws->tmp_bytes) {
-      hipFree(ws->tmp);
-      ws->tmp = nullptr; ws->tmp_bytes = 0;
-      CK(hipMalloc(&ws->tmp, need));
-      ws->tmp_bytes = need;
-    }
+    PCM_HIPCK_ERR(err, rocprim::radix_sort_pairs(nullptr, need, ws->keys.p, keys_s, ws->vals.p, vals_s, total, 0, 32 + pair_bits, stream));
+    if (need > ws->tmp.cap && ws->tmp.reserve(stream, err, need, need) != PCM_OK) return PCM_ERR_HIP;
     k_batch_morton_keys<<<dim3(cdiv(max_n, 256), (unsigned)njobs), 256, 0, stream>>>(d_jobs, d_guesses, (float)(1.0 / res), ws->keys, ws->vals);
-    CK(hipGetLastError());
-    need = ws->tmp_bytes;
-    CK(rocprim::radix_sort_pairs(ws->tmp, need, ws->keys, keys_s, ws->vals, vals_s, total, 0, 32 + pair_bits, stream));
+    PCM_HIPCK_ERR(err, hipGetLastError());
+    need = ws->tmp.cap;
+    PCM_HIPCK_ERR(err, rocprim::radix_sort_pairs(ws->tmp.p, need, ws->keys.p, keys_s, ws->vals.p, vals_s, total, 0, 32 + pair_bits, stream));
     k_batch_gather<<<cdiv(total, 256), 256, 0, stream>>>(d_jobs, keys_s, vals_s, total);
-    CK(hipGetLastError());
+    PCM_HIPCK_ERR(err, hipGetLastError());
   }
-done:
-  return rc;
-#undef CK
+  return PCM_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -833,38 +782,31 @@ int map_incremental_device(hipStream_t stream, const float4* scan, bool scan_reo
   uint32_t* buf = nullptr;   // f1, f2, p1, p2
   void* tmp = nullptr;
   size_t tmp_bytes = 0;
-  int rc = PCM_OK;
   uint32_t tails[4] = {0, 0, 0, 0};
-#define CK(x)                                                                    \
-  do {                                                                           \
-    hipError_t e_ = (x);                                                         \
-    if (e_ != hipSuccess) { *err = std::string(#x) + ": " + hipGetErrorString(e_); rc = PCM_ERR_HIP; goto done; } \
-  } while (0)
-  CK(hipMallocAsync(&world, sizeof(float4) * n, stream));
-  CK(hipMallocAsync(&buf, sizeof(uint32_t) * 4 * (size_t)n, stream));
-  {
+  const int rc = [&]() -> int {
+    PCM_HIPCK_ERR(err, hipMallocAsync(&world, sizeof(float4) * n, stream));
+    PCM_HIPCK_ERR(err, hipMallocAsync(&buf, sizeof(uint32_t) * 4 * (size_t)n, stream));
     uint32_t *f1 = buf, *f2 = buf + n, *p1 = buf + 2 * (size_t)n, *p2 = buf + 3 * (size_t)n;
     k_map_filter<<<cdiv(n, 256), 256, 0, stream>>>(scan, n, s, filter_size_map, nn, map_pts, world, f1, f2, scan_reordered ? 1 : 0);
-    CK(hipGetLastError());
-    CK(rocprim::exclusive_scan(nullptr, tmp_bytes, f1, p1, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-    CK(hipMallocAsync(&tmp, tmp_bytes, stream));
-    CK(rocprim::exclusive_scan(tmp, tmp_bytes, f1, p1, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-    CK(rocprim::exclusive_scan(tmp, tmp_bytes, f2, p2, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-    CK(hipMemcpyAsync(&tails[0], f1 + (n - 1), 4, hipMemcpyDeviceToHost, stream));
-    CK(hipMemcpyAsync(&tails[1], p1 + (n - 1), 4, hipMemcpyDeviceToHost, stream));
-    CK(hipMemcpyAsync(&tails[2], f2 + (n - 1), 4, hipMemcpyDeviceToHost, stream));
-    CK(hipMemcpyAsync(&tails[3], p2 + (n - 1), 4, hipMemcpyDeviceToHost, stream));
-    CK(hipStreamSynchronize(stream));
+    PCM_HIPCK_ERR(err, hipGetLastError());
+    PCM_HIPCK_ERR(err, rocprim::exclusive_scan(nullptr, tmp_bytes, f1, p1, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
+    PCM_HIPCK_ERR(err, hipMallocAsync(&tmp, tmp_bytes, stream));
+    PCM_HIPCK_ERR(err, rocprim::exclusive_scan(tmp, tmp_bytes, f1, p1, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
+    PCM_HIPCK_ERR(err, rocprim::exclusive_scan(tmp, tmp_bytes, f2, p2, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
+    PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[0], f1 + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+    PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[1], p1 + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+    PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[2], f2 + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+    PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[3], p2 + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+    PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
     const uint32_t n1 = tails[0] + tails[1], n2 = tails[2] + tails[3];
     k_map_append<<<cdiv(n, 256), 256, 0, stream>>>(world, f1, f2, p1, p2, n, n1, seq0, out_append);
-    CK(hipGetLastError());
-    CK(hipStreamSynchronize(stream));
+    PCM_HIPCK_ERR(err, hipGetLastError());
+    PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
     *num_added = n1 + n2;
-  }
-done:
+    return PCM_OK;
+  }();
   sfree(stream, world); sfree(stream, buf); sfree(stream, tmp);
   return rc;
-#undef CK
 }
 
 int load_points_to_device(hipStream_t stream, const void* points, size_t n, size_t stride, int memory, uint32_t seq0, float4* d_out, std::string* err) {
