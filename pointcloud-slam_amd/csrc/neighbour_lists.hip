@@ -6,7 +6,8 @@
 // The tile kernel (kernels.hip) re-derives it per pass -- tile box, brick probes by one wave, the bricks' points staged through LDS,
 // a cell grid, 27 per-cell walks in lock-step, five barriers in front of the plane fit -- and its waves spend four fifths of their
 // life waiting (the search over a ready-made flat list is 12x cheaper than the cell walk).  For a submap that is
-// registered against many times (the reference's own protocol: fast_gicp/src/align.cpp:51-104 reuses the target) the sequences are
+// registered against many times (jueying_slam's localization against one global map; fast_gicp/src/align.cpp:51-104 is no such
+// protocol: it clears the target on every iteration and its reuse loop swaps source and target) the sequences are
 // built ONCE, with the map: for every voxel of the occupied set dilated by the neighbourhood, the points of its <= 27 neighbour
 // voxels in the reference's visit order, contiguous in HBM (27 x 16 B per map point).  The pass is then: voxel of the query ->
 // one probe of the list index -> a flat walk of one contiguous run (lanes of a wave mostly share it) -> plane fit -> the shared

@@ -1,20 +1,10 @@
-// pcm_api.hip -- the C ABI of include/pcm_amd.h: registration objects, the batched
-// device-resident GN/LM loop and the parity hooks (linearize / compute_error).
-//
-// Host-side counterpart of the reference's wrappers
-//   FastVGICPCuda / NDTCuda host classes   /root/reference/src/pointcloud_match/fast_gicp/include/fast_gicp/gicp/impl/fast_vgicp_cuda_impl.hpp:21-180
-//   LsqRegistration::computeTransformation  .../impl/lsq_registration_impl.hpp:52-79
-// The reference crosses host<->device >= 4 times per Gauss-Newton iteration
-// (SURVEY.md §2.3); here the loop state lives on the device and the host only
-// polls a per-round "pairs still active" counter one round behind the GPU.
-#include "host_util.h"
-#include "pclndt_host.h"
+// pcm_api.hip -- the C ABI of include/pcm_amd.h: the extern "C" entry points of the registration objects and their small helpers
+// (configuration check, cloud upload, the GICP-BFGS functor, the LIO frame).  What a registration reads is built in prepare.hip;
+// the batched device-resident GN/LM loop and the parity hooks (linearize / compute_error) run in align_batch.hip.
+#include "pcm_core.h"
 
 #include <algorithm>
-#include <atomic>
-#include <thread>
 #include <cfloat>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -22,92 +12,6 @@
 using namespace pcm;
 
 namespace {
-
-// grow-only device workspace shared by the batch launches of one device
-struct Workspace {
-  int device = -1;
-  DevBuf<PairDesc> d_descs{"d_descs"};      // the per-pair arrays grow together (ensure_ws)
-  DevBuf<PairState> d_states{"d_states"};
-  DevBuf<float> d_guesses{"d_guesses"};     // 16 per pair
-  DevBuf<pcm_result> d_results{"d_results"};
-  DevBuf<double> d_partials{"d_partials"};
-  DevBuf<double> d_sums{"d_sums"};          // kPartialStride per pair
-  PinnedBuf<unsigned char> h_flags{"h_flags"};   // mapped pinned host memory: [round][pair] status bytes written by k_finish_round
-  unsigned char* d_flags = nullptr;              // device view of h_flags
-  DevBuf<unsigned long long> d_stats{"d_stats"};
-  DevBuf<unsigned int> d_queue{"d_queue"};   // batch window: index of the next queued pair
-  DevBuf<SortJob> d_jobs{"d_jobs"};
-  SortScratch sort;
-  std::vector<hipEvent_t> ev_round;
-  std::vector<hipEvent_t> ev_prof;
-};
-
-// Spin until a round's status byte (mapped pinned host memory, stored by the step kernel) is non-zero.  On both error returns
-// the queued kernels may still be writing into the workspace and the flags: the stream is drained first, so that the caller can
-// destroy the context safely.  The runtime is asked (hipStreamQuery: has the stream died?) only after a wait far beyond any
-// round -- a query takes the locks the other slots' launches need; polled every few microseconds by several waiting threads it
-// throttled every launch of the process.
-int wait_status_byte(pcm_ctx* c0, hipStream_t st, volatile unsigned char* p, std::chrono::steady_clock::time_point t_start) {
-  unsigned spins = 0;
-  auto next_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(5);
-  while (*p == 0) {
-    if ((++spins & 0xfff) != 0) continue;
-    const auto now = std::chrono::steady_clock::now();
-    if (now - t_start > std::chrono::seconds(20)) { (void)hipStreamSynchronize(st); c0->err = "timeout waiting for the GPU round status"; return PCM_ERR_HIP; }
-    if (now >= next_query) {
-      next_query = now + std::chrono::milliseconds(5);
-      if (hipStreamQuery(st) == hipSuccess && *p == 0) { c0->err = "stream drained without a round status (kernel fault?)"; return PCM_ERR_HIP; }
-    }
-  }
-  return PCM_OK;
-}
-
-// The workspace belongs to the first context of a batch (contexts are single-threaded
-// objects), so independent batches may run concurrently from different host threads
-// on their own streams -- e.g. the stragglers of one batch under the bulk of the next.
-int ensure_ws(pcm_ctx* c, Workspace** out, int npairs, size_t partial_doubles, int rounds) {
-  if (!c->ws) c->ws = new (std::nothrow) Workspace();
-  if (!c->ws) { c->err = "out of host memory"; return PCM_ERR_HIP; }
-  Workspace& w = *static_cast<Workspace*>(c->ws);
-  w.device = c->device;
-  const size_t np = (size_t)npairs, cap = (size_t)std::max(npairs, 64);
-  int rc = w.d_descs.reserve(c, np, cap);
-  if (rc == PCM_OK) rc = w.d_states.reserve(c, np, cap);
-  if (rc == PCM_OK) rc = w.d_guesses.reserve(c, 16 * np, 16 * cap);
-  if (rc == PCM_OK) rc = w.d_results.reserve(c, np, cap);
-  if (rc == PCM_OK) rc = w.d_sums.reserve(c, kPartialStride * np, kPartialStride * cap);
-  if (rc == PCM_OK) rc = w.d_jobs.reserve(c, np, cap);
-  if (rc == PCM_OK && partial_doubles) rc = w.d_partials.reserve(c, partial_doubles, partial_doubles);
-  if (rc != PCM_OK) return rc;
-  {
-    // per-round status bytes of every pair live in mapped pinned host memory: k_finish_round
-    // stores them directly (posted writes); the host polls them, no event / copy per round
-    const size_t bytes = (size_t)rounds * cap;
-    if (!w.h_flags || bytes > w.h_flags.cap) w.d_flags = nullptr;
-    rc = w.h_flags.reserve(c, bytes, bytes, hipHostMallocMapped);
-    if (rc != PCM_OK) return rc;
-    if (!w.d_flags) PCM_HIPCK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&w.d_flags), w.h_flags.p, 0));
-  }
-  rc = w.d_stats.reserve(c, 16, 16);
-  if (rc == PCM_OK) rc = w.d_queue.reserve(c, 1, 1);
-  if (rc != PCM_OK) return rc;
-  while ((int)w.ev_round.size() < 2) {
-    hipEvent_t e;
-    PCM_HIPCK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    w.ev_round.push_back(e);
-  }
-  *out = &w;
-  return PCM_OK;
-}
-
-void free_ws(pcm_ctx* c) {
-  Workspace* w = static_cast<Workspace*>(c->ws);
-  if (!w) return;
-  for (hipEvent_t e : w->ev_round) hipEventDestroy(e);
-  for (hipEvent_t e : w->ev_prof) hipEventDestroy(e);
-  delete w;
-  c->ws = nullptr;
-}
 
 // room for `bytes` in the grow-only device scratch the pre-processing operators share (a quarter of headroom: no allocation per
 // frame in the steady state); the contents do not survive a growth
@@ -118,40 +22,6 @@ int bfgs_scratch(pcm_ctx* c, size_t m) {
   const size_t need = gicp_bfgs_scratch_bytes(m);
   return c->bfgs.reserve(c, need, need + need / 4);
 }
-
-int coord_mode_for(int model) {
-  if (model == PCM_MODEL_P2PLANE || model == PCM_MODEL_GICP) return COORD_ROUND;   // GICP: the grid is only the kNN index, any convention serves
-  if (model == PCM_MODEL_NDT_OMP) return COORD_FLOOR_MUL;
-  return model == PCM_MODEL_VGICP ? COORD_FLOOR_HALF_D : COORD_FLOOR_HALF;
-}
-
-// PCM_COV_FINE_INDEX=1 switches the fine kNN index of the covariance pass on (measured: fewer candidates, but the second index
-// build and its query order cost more than they save on the bench scans -- DESIGN section 3)
-bool cov_fine_index_enabled() {
-  static const bool on = [] { const char* e = getenv("PCM_COV_FINE_INDEX"); return e && e[0] == '1'; }();
-  return on;
-}
-
-// PCM_COV_SUBSORT=0: the scan's kNN index keeps input order inside its voxels (A/B measurements)
-bool cov_subsort_enabled() {
-  static const bool on = [] { const char* e = getenv("PCM_COV_SUBSORT"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
-size_t num_elements(const pcm_ctx* c) { return c->cfg.model == PCM_MODEL_NDT_D2D ? (size_t)c->srcmap.num_voxels : c->src.n; }
-
-bool is_ndt(int model) { return model == PCM_MODEL_NDT_P2D || model == PCM_MODEL_NDT_D2D; }
-bool is_gicp(int model) { return model == PCM_MODEL_GICP || model == PCM_MODEL_VGICP || model == PCM_MODEL_VGICP_CUDA; }   // models with per-point covariances
-bool radius_model(int model) { return is_ndt(model) || model == PCM_MODEL_VGICP_CUDA; }
-// offsets examined per element: DIRECT_RADIUS walks the cube around the voxel (the list is its subset), else the table
-size_t neighbor_slots(const pcm_config& g) {
-  if (radius_model(g.model) && g.neighbor_search_radius > 0.f) {
-    const size_t D = 2 * (size_t)std::ceil((double)g.neighbor_search_radius) + 1;
-    return D * D * D;
-  }
-  return (size_t)g.num_neighbors;
-}
-int ndt_kind(int model) { return model == PCM_MODEL_NDT_D2D ? 1 : (model == PCM_MODEL_VGICP_CUDA ? 2 : 0); }
 
 int validate_config(pcm_ctx* c, const pcm_config& g) {
   if (g.model == PCM_MODEL_LOAM) { c->err = "PCM_MODEL_LOAM contexts run through the pcm_loam_* entry points"; return PCM_ERR_UNSUPPORTED; }
@@ -213,603 +83,6 @@ int set_cloud(pcm_ctx* c, Cloud* cl, const void* points, size_t n, size_t stride
   return PCM_OK;
 }
 
-// P2PLANE against a static target: the linearize pass runs on per-voxel candidate lists (neighbour_lists.hip).  The lists cost a
-// build (several ms and 27 x 16 B per map point), so by default they are made when a target is registered against the SECOND time
-// (the reference's own protocols re-use a target: fast_gicp/src/align.cpp:51-104, jueying_slam's localization against one global map);
-// PCM_FLAG_NEIGHBOUR_LISTS builds them with the map, PCM_FLAG_NO_NEIGHBOUR_LISTS never.  A target that grows through
-// pcm_target_insert / pcm_map_incremental would rebuild them with every batch: it keeps the tile kernel.
-bool uses_neighbour_lists(const pcm_ctx* c) {
-  if (c->cfg.model != PCM_MODEL_P2PLANE || c->tgt_dynamic || c->nlists_failed || (c->cfg.flags & PCM_FLAG_NO_NEIGHBOUR_LISTS)) return false;
-  if (c->cfg.flags & (PCM_FLAG_REFERENCE_KNN_ORDER | PCM_FLAG_COUNTED_SEARCH | PCM_FLAG_NO_LDS_STAGING | PCM_FLAG_FUSED_STEP)) return false;   // another kernel was asked for
-  return (c->cfg.flags & PCM_FLAG_NEIGHBOUR_LISTS) != 0 || c->map_uses >= 2;
-}
-
-// fast_gicp NDTCuda (P2D / D2D) and VGICP of the CUDA core with a DIRECT neighbourhood: k_ndt reads rows of neighbour voxel indices
-bool uses_voxel_slot_lists(const pcm_ctx* c) {
-  const int m = c->cfg.model;
-  if (!(m == PCM_MODEL_NDT_P2D || m == PCM_MODEL_NDT_D2D || m == PCM_MODEL_VGICP_CUDA) || c->cfg.neighbor_search_radius > 0.f) return false;
-  if (c->nlists_failed || (c->cfg.flags & PCM_FLAG_NO_NEIGHBOUR_LISTS) || c->map.coord_mode != COORD_FLOOR_HALF) return false;
-  return (c->cfg.flags & PCM_FLAG_NEIGHBOUR_LISTS) != 0 || c->map_uses >= 2;
-}
-
-// pclomp NDT: the neighbour-leaf lists of the context's grid, or an empty view (the cells are then looked up one by one)
-TargetView ndt_lists_view(const pcm_ctx* c) {
-  const bool on = c->cfg.model == PCM_MODEL_NDT_OMP && c->nlists.valid && c->nlists.kind == 1 && c->nlists.num_neighbors == c->cfg.num_neighbors &&
-                  !(c->cfg.flags & PCM_FLAG_NO_NEIGHBOUR_LISTS);
-  return on ? view_of_lists(c->nlists) : TargetView{};
-}
-
-// lazy (re)build of everything the residual kernel needs
-int prepare(pcm_ctx* c) {
-  if (c->src.n == 0 || c->tgt.n == 0) { c->err = "align before setInputSource/setInputTarget"; return PCM_ERR_NO_INPUT; }
-  PCM_HIPCK(c, hipSetDevice(c->device));
-  const int mode = coord_mode_for(c->cfg.model);
-  const bool gauss = is_ndt(c->cfg.model);
-  const bool gicp = is_gicp(c->cfg.model);
-  if (!c->map.valid || c->map.res != c->cfg.voxel_resolution || c->map.coord_mode != mode || (gauss && !c->map.gvox) || (gicp && !c->map.order)) {
-    uint32_t n_log = (uint32_t)c->tgt.n;
-    // the sliding-map capacity belongs to the iVox of the P2PLANE / LIO path; fast_gicp keeps every target point
-    const uint32_t capacity = c->cfg.model == PCM_MODEL_P2PLANE ? (uint32_t)std::max(0, c->cfg.map_capacity) : 0u;
-    // a map whose log only grew since its last build (pcm_target_insert / pcm_map_incremental) is updated: the new points are merged
-    // into the sorted index it kept (voxel_hash.hip); anything else is built from scratch
-    uint32_t hazards = 0;
-    int rc = build_target_map(c->stream, c->tgt.d_pts, &n_log, c->cfg.voxel_resolution, mode, gauss, capacity, &c->map, &c->err, gicp, c->map.index_n, &hazards);
-    c->stats.lru_batch_hazards += hazards;
-    c->tgt.n = n_log;   // LRU eviction compacts the point log
-    if (rc != PCM_OK) return rc;
-    c->stats.target_voxels = c->map.num_voxels;
-    c->stats.target_slots = c->map.cap;
-    c->tgt_cov_valid = false;
-    c->pleaf_valid = false;
-    c->nlists.valid = false;
-    c->nlists_failed = false;
-    c->map_uses = 0;
-  }
-  if (c->map_uses < 1000000) c->map_uses++;
-  if (uses_neighbour_lists(c) && (!c->nlists.valid || c->nlists.kind != 0 || c->nlists.num_neighbors != c->cfg.num_neighbors)) {
-    // the candidate list of every voxel a query can fall into, built once per (static) target
-    int rc = build_neighbour_lists(c->stream, c->map, c->cfg.num_neighbors, &c->nlists, &c->err);
-    if (rc != PCM_OK) {
-      if (c->cfg.flags & PCM_FLAG_NEIGHBOUR_LISTS) return rc;   // asked for explicitly
-      c->nlists_failed = true;                                   // e.g. no memory for them: the tile kernel serves this target
-      c->nlists.release();
-      c->err.clear();
-      (void)hipGetLastError();
-    }
-  }
-  if (uses_voxel_slot_lists(c) && (!c->nlists.valid || c->nlists.kind != 2 || c->nlists.num_neighbors != c->cfg.num_neighbors)) {
-    // fast_gicp NDTCuda / VGICP_CUDA with DIRECT1 / 7 / 27: rows of neighbour voxel indices, same policy as the candidate lists
-    int rc = build_neighbour_lists(c->stream, c->map, c->cfg.num_neighbors, &c->nlists, &c->err, nullptr, true);
-    if (rc != PCM_OK) {
-      if (c->cfg.flags & PCM_FLAG_NEIGHBOUR_LISTS) return rc;
-      c->nlists_failed = true;
-      c->nlists.release();
-      c->err.clear();
-      (void)hipGetLastError();
-    }
-  }
-  if (c->cfg.model == PCM_MODEL_NDT_OMP) {
-    // VoxelGridCovariance leaves (NormalDistributionsTransform::init, ndt_omp.h:300-306) + pass buffers
-    if (!c->pleaf_valid) {
-      int rc = c->pleaf.reserve(c, c->map.num_voxels, c->map.num_voxels);
-      if (rc == PCM_OK) rc = c->pleaf_f.reserve(c, c->map.num_voxels, c->map.num_voxels);
-      if (rc != PCM_OK) return rc;
-      rc = build_pclndt_leaves(c->stream, c->map, c->pleaf, c->pleaf_f, &c->err);
-      if (rc != PCM_OK) return rc;
-      c->pleaf_valid = true;
-      c->nlists.valid = false;
-    }
-    // neighbour-leaf lists of the grid (neighbour_lists.hip): same policy as the point-to-plane candidate lists -- from the second
-    // registration against the target on, or with the grid when PCM_FLAG_NEIGHBOUR_LISTS asks for it
-    const bool want_lists = !c->nlists_failed && !(c->cfg.flags & PCM_FLAG_NO_NEIGHBOUR_LISTS) && ((c->cfg.flags & PCM_FLAG_NEIGHBOUR_LISTS) || c->map_uses >= 2);
-    if (want_lists && (!c->nlists.valid || c->nlists.kind != 1 || c->nlists.num_neighbors != c->cfg.num_neighbors)) {
-      int rc = build_neighbour_lists(c->stream, c->map, c->cfg.num_neighbors, &c->nlists, &c->err, c->pleaf);
-      if (rc != PCM_OK) {
-        if (c->cfg.flags & PCM_FLAG_NEIGHBOUR_LISTS) return rc;
-        c->nlists_failed = true;
-        c->nlists.release();
-        c->err.clear();
-        (void)hipGetLastError();
-      }
-    }
-    uint32_t per = 0;
-    const size_t need = (size_t)pclndt_workgroups((uint32_t)c->src.n, &per) * 48;
-    int rc = c->ndt_partials.reserve(c, need, need, true);
-    if (rc == PCM_OK) rc = c->ndt_out.reserve(c, 48, 48);
-    if (rc == PCM_OK) rc = c->ndt_out_host.reserve(c, 48, 48);
-    return rc;
-  }
-  if (gicp) {
-    // FastGICP::computeTransformation: covariances of both clouds, lazily   fast_gicp_impl.hpp:102-110
-    const bool rbf = c->cfg.model == PCM_MODEL_VGICP_CUDA && c->cfg.covariance_method == PCM_COV_RBF_KERNEL;   // NearestNeighborMethod::GPU_RBF_KERNEL
-    const float rbf_w = rbf ? c->cfg.rbf_kernel_width : -1.f, rbf_d = rbf ? c->cfg.rbf_max_dist : -1.f;
-    if (c->cov_k != c->cfg.k_correspondences || c->cov_reg != c->cfg.regularization + 100 * c->cfg.model || c->cov_vmode != c->cfg.voxel_mode || c->cov_rbf_w != rbf_w ||
-        c->cov_rbf_d != rbf_d) {
-      c->src_cov_valid = false; c->tgt_cov_valid = false;
-      c->cov_k = c->cfg.k_correspondences; c->cov_reg = c->cfg.regularization + 100 * c->cfg.model; c->cov_vmode = c->cfg.voxel_mode;
-      c->cov_rbf_w = rbf_w; c->cov_rbf_d = rbf_d;
-    }
-    // the scan's own grid is only the index of its kNN search: a finer cell keeps the candidate lists short where a
-    // LiDAR scan is dense (near the sensor one 0.5 m voxel holds thousands of points)
-    // (measured on Livox-shaped 100 k-point scans: 0.5 m cells are the optimum; 1.0 m costs 25 %, 0.25 m 15-40 %)
-    const float src_res = std::min(c->cfg.voxel_resolution, 0.5f);
-    if (!c->srcmap.valid || c->srcmap.res != src_res || c->srcmap.coord_mode != mode) {
-      uint32_t n_src = (uint32_t)c->src.n;
-      // sub-voxel order: 64 consecutive points of the brick-major scan are one patch (k_covariances; k_gicp reads it point by point)
-      int rc = build_target_map(c->stream, c->src.d_pts, &n_src, src_res, mode, false, 0u, &c->srcmap, &c->err, true, 0u, nullptr, cov_subsort_enabled());
-      if (rc != PCM_OK) return rc;
-      c->src_cov_valid = false;
-    }
-    if (!c->tgt_cov_valid) {
-      int rc = c->tgt_cov.reserve(c, 6 * (size_t)c->map.num_points, 6 * (size_t)c->map.num_points);
-      if (rc != PCM_OK) return rc;
-      const int reg_code = c->cfg.regularization + (c->cfg.model == PCM_MODEL_VGICP_CUDA ? 16 : 0);   // + 16: float CUDA-core semantics
-      // `if (target_covs_.size() != target_->size()) calculate_covariances(...)`  fast_gicp_impl.hpp:107-109
-      const bool given = c->cfg.model != PCM_MODEL_VGICP_CUDA && c->user_cov[1].size() == (size_t)c->map.num_points * 6 && c->map.num_points == c->tgt.n;
-      if (given) rc = upload_covariances(c->stream, c->map, c->user_cov[1].data(), c->tgt_cov, &c->err);
-      else if (rbf) rc = compute_covariances_rbf(c->stream, c->map, c->tgt.d_pts, (uint32_t)c->tgt.n, c->cfg.rbf_kernel_width, c->cfg.rbf_max_dist, c->cfg.regularization, c->tgt_cov, &c->err);
-      else {
-        uint32_t n_fine = (uint32_t)c->tgt.n;   // the fine kNN index (see the source cloud below); only when the map holds the whole log
-        const bool fine = cov_fine_index_enabled() && c->map.num_points == c->tgt.n &&
-                          build_target_map(c->stream, c->tgt.d_pts, &n_fine, std::min(c->cfg.voxel_resolution, 0.5f) * 0.125f, mode, false, 0u, &c->covfine, &c->err, true) == PCM_OK;
-        rc = compute_covariances(c->stream, c->map, c->cfg.k_correspondences, reg_code, c->tgt_cov, &c->err, fine ? &c->covfine : nullptr);
-      }
-      if (rc != PCM_OK) return rc;
-      if (c->cfg.model == PCM_MODEL_VGICP_CUDA) {
-        rc = c->cvox.reserve(c, c->map.num_voxels, c->map.num_voxels);
-        if (rc != PCM_OK) return rc;
-        rc = build_vgc_voxels(c->stream, c->map, c->tgt_cov, c->cvox, &c->err);
-        if (rc != PCM_OK) return rc;
-      }
-      if (c->cfg.model == PCM_MODEL_VGICP) {
-        rc = c->vvox.reserve(c, c->map.num_voxels, c->map.num_voxels);
-        if (rc != PCM_OK) return rc;
-        rc = build_vgicp_voxels(c->stream, c->map, c->tgt_cov, c->cfg.voxel_mode, c->vvox, &c->err);
-        if (rc != PCM_OK) return rc;
-      }
-      c->tgt_cov_valid = true;
-    }
-    if (!c->src_cov_valid) {
-      int rc = c->src_cov.reserve(c, 6 * (size_t)c->srcmap.num_points, 6 * (size_t)c->srcmap.num_points);
-      if (rc != PCM_OK) return rc;
-      const bool given = c->cfg.model != PCM_MODEL_VGICP_CUDA && c->user_cov[0].size() == (size_t)c->srcmap.num_points * 6 && c->srcmap.num_points == c->src.n;   // :104-106
-      if (given) rc = upload_covariances(c->stream, c->srcmap, c->user_cov[0].data(), c->src_cov, &c->err);
-      else if (rbf) rc = compute_covariances_rbf(c->stream, c->srcmap, c->src.d_pts, (uint32_t)c->src.n, c->cfg.rbf_kernel_width, c->cfg.rbf_max_dist, c->cfg.regularization, c->src_cov, &c->err);
-      else {
-        // a second index of the scan on a grid 8x finer: where one voxel of the search grid holds hundreds of points (a LiDAR's near
-        // field) the 20 nearest lie within a few centimetres, and a candidate box made of 0.5 m voxels is thousands of points
-        uint32_t n_fine = (uint32_t)c->src.n;
-        const bool fine = cov_fine_index_enabled() && build_target_map(c->stream, c->src.d_pts, &n_fine, src_res * 0.125f, mode, false, 0u, &c->covfine, &c->err, true) == PCM_OK;
-        rc = compute_covariances(c->stream, c->srcmap, c->cfg.k_correspondences, c->cfg.regularization + (c->cfg.model == PCM_MODEL_VGICP_CUDA ? 16 : 0), c->src_cov, &c->err,
-                                 fine ? &c->covfine : nullptr);
-      }
-      if (rc != PCM_OK) return rc;
-      c->src_cov_valid = true;
-    }
-    const size_t ncorr = c->cfg.model == PCM_MODEL_VGICP_CUDA ? 0 : c->src.n * (size_t)(c->cfg.model == PCM_MODEL_VGICP ? c->cfg.num_neighbors : 1);
-    if (ncorr) {   // VGICP_CUDA keeps no cache
-      const int rc = c->maha.reserve(c, 6 * ncorr, 6 * ncorr);
-      if (rc != PCM_OK) return rc;
-    }
-  }
-  if (c->cfg.model == PCM_MODEL_NDT_D2D && (!c->srcmap.valid || c->srcmap.res != c->cfg.voxel_resolution)) {
-    // D2D: the source elements are the source-voxel distributions (ndt_cuda.cu:120-129,156-158)
-    uint32_t n_src = (uint32_t)c->src.n;
-    int rc = build_target_map(c->stream, c->src.d_pts, &n_src, c->cfg.voxel_resolution, mode, true, 0u, &c->srcmap, &c->err);
-    if (rc != PCM_OK) return rc;
-  }
-  if (gauss || gicp) {
-    const size_t need = num_elements(c) * (c->cfg.model == PCM_MODEL_GICP ? (size_t)1 : neighbor_slots(c->cfg));
-    const int rc = c->corr.reserve(c, need, need);
-    if (rc != PCM_OK) return rc;
-  }
-  if (c->cfg.sort_source && c->src_order.cap < c->src.n) {
-    c->src_sorted = false;
-    const int rc = c->src_order.reserve(c, c->src.n, c->src.n);
-    if (rc != PCM_OK) return rc;
-  }
-  int rc = c->counter.reserve(c, 1, 1, true);
-  if (rc == PCM_OK) rc = c->nn.reserve(c, 5 * c->src.n, 5 * c->src.n);
-  if (rc == PCM_OK) rc = c->planes.reserve(c, c->src.n, c->src.n);
-  return rc;
-}
-
-struct Geom {
-  int blocks_per_pair;   // residual/reduction kernel
-  int points_per_block;
-  int tiles_per_pair;    // correspondence-search kernel (256-point tiles)
-};
-
-Geom pick_geom(size_t max_n, int npairs, bool ndt = false) {
-  // residual kernel: streaming 32 B/point; each lane amortises the 29-value wave
-  // reduction over several points, but keep >= ~1024 workgroups in flight
-  size_t total = max_n * (size_t)npairs;
-  size_t ppb = (total / 1024 + 255) / 256 * 256;
-  ppb = std::min<size_t>(std::max<size_t>(ppb, 256), 2048);
-  Geom g;
-  g.points_per_block = (int)ppb;
-  g.blocks_per_pair = (int)((max_n + ppb - 1) / ppb);
-  g.tiles_per_pair = ndt ? g.blocks_per_pair : (int)((max_n + 255) / 256);   // NDT linearize uses the streaming geometry
-  return g;
-}
-
-void fill_desc(const pcm_ctx* c, PairDesc* d, double* partials) {
-  d->tgt.pts = c->map.pts;
-  d->tgt.vox_start = c->map.vox_start;
-  d->tgt.bricks = c->map.bricks;
-  d->tgt.bmask = c->map.bmask;
-  d->tgt.bpref = c->map.bpref;
-  d->tgt.mask = c->map.cap - 1;
-  d->tgt.num_points = c->map.num_points;
-  d->tgt.inv_res = c->map.inv_res;
-  d->tgt.res = c->map.res;
-  d->tgt.gvox = c->map.gvox;
-  d->nl = TargetView{};
-  if (c->nlists.valid && c->nlists.num_neighbors == c->cfg.num_neighbors &&
-      ((uses_neighbour_lists(c) && c->nlists.kind == 0) || (uses_voxel_slot_lists(c) && c->nlists.kind == 2)))
-    d->nl = view_of_lists(c->nlists);
-  d->src.pts = (c->cfg.sort_source && c->src_sorted) ? c->src_order : c->src.d_pts;
-  if (is_gicp(c->cfg.model)) d->src.pts = c->srcmap.pts;   // brick-major copy of the scan: its covariances are in that order
-  d->src_cov = c->src_cov;
-  d->tgt_cov = c->tgt_cov;
-  d->vvox = c->vvox;
-  d->cvox = c->cvox;
-  d->maha = c->maha;
-  d->src.gvox = c->srcmap.gvox;
-  d->src.num_points = (uint32_t)num_elements(c);
-  d->corr = c->corr;
-  d->nn = c->nn;
-  d->planes = c->planes;
-  d->partials = partials;
-  d->counter = c->counter;
-}
-
-KernelParams kernel_params(const pcm_config& g, const Geom& geom) {
-  KernelParams kp{};
-  kp.num_neighbors = g.num_neighbors;
-  if (radius_model(g.model) && g.neighbor_search_radius > 0.f) {
-    kp.nb_range = (int32_t)std::ceil((double)g.neighbor_search_radius);
-    kp.nb_radius = (double)g.neighbor_search_radius;
-  }
-  kp.knn = g.knn;
-  kp.min_knn = g.min_knn;
-  {  // d2 < fl  <=>  double(d2) < max_range^2  when fl is the smallest float >= max_range^2
-    const double m2 = (double)g.max_range * (double)g.max_range;
-    float fl = (float)m2;
-    if ((double)fl < m2) fl = nextafterf(fl, INFINITY);
-    kp.max_range_sq = fl;
-  }
-  kp.plane_threshold = g.plane_threshold;
-  kp.blocks_per_pair = geom.blocks_per_pair;
-  kp.points_per_block = geom.points_per_block;
-  kp.tiles_per_pair = geom.tiles_per_pair;
-  kp.use_lds = (g.flags & PCM_FLAG_NO_LDS_STAGING) ? 0 : 1;
-  kp.do_step = 1;
-  kp.lin_points_per_block = (is_ndt(g.model) || g.model == PCM_MODEL_VGICP_CUDA) ? geom.points_per_block : 256;
-  kp.coord_mode = coord_mode_for(g.model);
-  kp.max_corr_sq = (double)g.max_corr_dist * (double)g.max_corr_dist;
-  return kp;
-}
-
-LsqParams lsq_params(const pcm_config& g) {
-  LsqParams lp{};
-  lp.optimizer = g.optimizer;
-  lp.max_iterations = g.max_iterations;
-  lp.lm_max_iterations = g.lm_max_iterations;
-  lp.rotation_eps = g.rotation_eps;
-  lp.translation_eps = g.translation_eps;
-  lp.lm_init_lambda_factor = g.lm_init_lambda_factor;
-  return lp;
-}
-
-bool same_solver_config(const pcm_config& a, const pcm_config& b) {
-  return a.model == b.model && a.optimizer == b.optimizer && a.max_iterations == b.max_iterations && a.lm_max_iterations == b.lm_max_iterations &&
-         a.rotation_eps == b.rotation_eps && a.translation_eps == b.translation_eps && a.lm_init_lambda_factor == b.lm_init_lambda_factor &&
-         a.num_neighbors == b.num_neighbors && a.neighbor_search_radius == b.neighbor_search_radius && a.max_range == b.max_range && a.plane_threshold == b.plane_threshold && a.flags == b.flags &&
-         (a.model == PCM_MODEL_P2PLANE || a.voxel_resolution == b.voxel_resolution) && (!is_gicp(a.model) || a.max_corr_dist == b.max_corr_dist);
-}
-
-int align_batch_impl(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_result* host_out, void* device_out) {
-  if (!ctxs || n <= 0 || !guesses) return PCM_ERR_INVALID_ARGUMENT;
-  pcm_ctx* c0 = ctxs[0];
-  if (!c0) return PCM_ERR_INVALID_ARGUMENT;
-  size_t max_n = 0;
-  for (int i = 0; i < n; i++) {
-    pcm_ctx* c = ctxs[i];
-    if (!c) { c0->err = "null context in batch"; return PCM_ERR_INVALID_ARGUMENT; }
-    if (c->device != c0->device) { c0->err = "all contexts of a batch must live on one device"; return PCM_ERR_INVALID_ARGUMENT; }
-    if (!same_solver_config(c->cfg, c0->cfg)) { c0->err = "all contexts of a batch must share the solver configuration"; return PCM_ERR_INVALID_ARGUMENT; }
-    if (c->stream != c0->stream) {
-      // inputs of the other contexts were produced on their own streams, which are idle after set_*()
-    }
-  }
-  {
-    // per-object preparation (the scan's kNN index and covariances of the GICP family are the heavy part: a radix sort with
-    // host syncs per object): the objects are independent and own their streams, so up to 8 host threads prepare them side
-    // by side; nothing is shared but the device
-    std::vector<int> rcs((size_t)n, PCM_OK);
-    const int nthreads = (is_gicp(c0->cfg.model) && n > 1) ? std::min(n, 8) : 1;
-    bool distinct = true;
-    for (int i = 0; i < n && distinct; i++) for (int j = 0; j < i; j++) if (ctxs[j] == ctxs[i]) { distinct = false; break; }
-    if (nthreads <= 1 || !distinct) {
-      for (int i = 0; i < n; i++) rcs[(size_t)i] = prepare(ctxs[i]);
-    } else {
-      std::atomic<int> next{0};
-      auto worker = [&]() {
-        for (;;) {
-          const int i = next.fetch_add(1);
-          if (i >= n) break;
-          rcs[(size_t)i] = prepare(ctxs[i]);
-        }
-      };
-      std::vector<std::thread> th;
-      for (int t = 0; t < nthreads; t++) th.emplace_back(worker);
-      for (auto& t : th) t.join();
-    }
-    for (int i = 0; i < n; i++) {
-      if (rcs[(size_t)i] != PCM_OK) { if (ctxs[i] != c0) c0->err = ctxs[i]->err; return rcs[(size_t)i]; }
-      max_n = std::max(max_n, num_elements(ctxs[i]));
-    }
-  }
-  // GICP / VGICP: the covariance kernels of the contexts were queued on their own streams without a host
-  // sync (they overlap on the device); the batch kernels below run on c0's stream and read their output
-  if (is_gicp(c0->cfg.model)) {
-    for (int i = 0; i < n; i++) PCM_HIPCK(c0, hipStreamSynchronize(ctxs[i]->stream));
-  }
-  const pcm_config& g = c0->cfg;
-  const bool ndt = is_ndt(g.model) || g.model == PCM_MODEL_VGICP_CUDA;   // residual kernel of the Gaussian-voxel family
-  const bool gicp = is_gicp(g.model);                                     // per-point covariances, source elements = brick-major copy
-  const Geom geom = pick_geom(max_n, n, ndt);
-  const LsqParams lp = lsq_params(g);
-  const KernelParams kp = kernel_params(g, geom);
-  // worst case: every outer iteration = 1 linearize + lm_max_iterations trials
-  // batch window: at most `window` pairs iterate at a time, a finished pair's slot goes to the next queued one on the
-  // device (k_finish_round) -- the late rounds of a slow pair then overlap the early rounds of its successors
-  const int window = (g.batch_window > 0 && g.max_iterations > 0) ? std::min(n, g.batch_window) : n;
-  const int per_pair_rounds = std::max(1, g.max_iterations) * (g.optimizer == PCM_OPT_LEVENBERG_MARQUARDT ? 1 + std::max(1, g.lm_max_iterations) : 1);
-  // Up to 256 pairs with a window of at most 64: the window is kept by the HOST.  Only the pairs of the launch list run; when the
-  // status byte of a pair says "done" the next queued pair takes its place in the list (it was initialised with the others and
-  // simply never launched before).  Every round then carries about `window` live pairs, so the fixed cost of a round (two launches,
-  // their boundaries) is shared by that many registrations for the whole batch, not only in its first rounds.  No device-side hand-off.
-  const bool host_window = window < n && n <= 256 && window <= kMaxListedPairs;
-  // Round budget.  Host window: a slot serves its pairs one after the other, and every hand-over costs one extra round because the
-  // status bytes are read one round behind; with every pair running to max_iterations a slot needs ceil(n / window) * (rounds + 1)
-  // rounds, one more pair's worth covers an uneven hand-out (round-2 advisor finding: the old bound ran out for 256 pairs at a
-  // window of 8 and 10 GN iterations and returned unfinished pairs as PCM_OK).  A pair the loop leaves unfinished is reported
-  // with PCM_ERR_INTERNAL by k_pack_results, never silently.
-  const int max_rounds = host_window ? ((n + window - 1) / window + 1) * (per_pair_rounds + 1) + 2
-                                     : per_pair_rounds * (n - window + 1) + 1 + 2 * (n - window);   // + the rounds a handed-over pair spends PENDING
-  const size_t per_pair_partials = (size_t)std::max(geom.blocks_per_pair, geom.tiles_per_pair) * kPartialStride;
-  Workspace* w = nullptr;
-  int rc = ensure_ws(c0, &w, n, per_pair_partials * n, max_rounds);
-  if (rc != PCM_OK) return rc;
-  hipStream_t st = c0->stream;
-
-  PCM_HIPCK(c0, hipMemcpyAsync(w->d_guesses, guesses, sizeof(float) * 16 * n, hipMemcpyHostToDevice, st));
-  {  // new scans are re-ordered along the world grid (at their initial guess) in one batched pass
-    std::vector<SortJob> jobs;
-    uint32_t total = 0, jmax = 0;
-    for (int i = 0; i < n; i++) {
-      pcm_ctx* c = ctxs[i];
-      if (!c->cfg.sort_source || c->src_sorted || c->cfg.model == PCM_MODEL_NDT_D2D || gicp) continue;
-      SortJob j{c->src.d_pts, c->src_order, (uint32_t)c->src.n, total, (uint32_t)i, 0};
-      jobs.push_back(j);
-      total += j.n;
-      jmax = std::max(jmax, j.n);
-    }
-    if (!jobs.empty()) {
-      PCM_HIPCK(c0, hipMemcpyAsync(w->d_jobs, jobs.data(), sizeof(SortJob) * jobs.size(), hipMemcpyHostToDevice, st));
-      rc = sort_sources_batched(st, w->d_jobs, (int)jobs.size(), jmax, total, w->d_guesses, g.voxel_resolution, &w->sort, &c0->err);
-      if (rc != PCM_OK) return rc;
-      for (const SortJob& j : jobs) ctxs[j.guess_index]->src_sorted = true;
-    }
-  }
-  std::vector<PairDesc> descs(n);
-  for (int i = 0; i < n; i++) fill_desc(ctxs[i], &descs[i], w->d_partials + per_pair_partials * i);
-  PCM_HIPCK(c0, hipMemcpyAsync(w->d_descs, descs.data(), sizeof(PairDesc) * n, hipMemcpyHostToDevice, st));
-  std::memset(w->h_flags, 0, (size_t)max_rounds * n);
-  launch_init_states(st, w->d_states, w->d_guesses, n, g.max_iterations, host_window ? n : window, w->d_queue);
-  const bool stats_on = (c0->profiling & 1) != 0;      // HIP events around the residual launches
-  const bool stats_sampled = stats_on && (c0->profiling & 8) != 0;   // ... every 4th launch only; the phase moves from batch to batch
-  const unsigned prof_phase = stats_sampled ? (unsigned)(c0->stats.linearize_launches & 3u) : 0u;
-  uint64_t timed_launches = 0, timed_slots = 0, launched_slots = 0;
-  const bool timing_on = (c0->profiling & 4) != 0;     // diagnostic: in-kernel phase stamps (stats.phase_cycles)
-  const bool counters_on = (c0->profiling & 2) != 0 || timing_on;   // kNN candidate / probe counters (slower kernel variant)
-  if (counters_on) PCM_HIPCK(c0, hipMemsetAsync(w->d_stats, 0, sizeof(unsigned long long) * 16, st));
-  const bool is_lm = g.optimizer == PCM_OPT_LEVENBERG_MARQUARDT;
-  const bool write_sel = is_lm;  // trial passes re-use the planes of the selected set
-  const bool counted_search = (g.flags & PCM_FLAG_COUNTED_SEARCH) != 0;   // k_linearize_counted (A/B)
-  const bool ref_order = g.model == PCM_MODEL_P2PLANE && (g.flags & PCM_FLAG_REFERENCE_KNN_ORDER) != 0;   // neighbours in libstdc++'s nth_element order
-  bool lists = g.model == PCM_MODEL_P2PLANE && !ref_order;   // k_linearize_lists: every context of the batch holds its map's candidate lists
-  for (int i = 0; i < n && lists; i++) lists = uses_neighbour_lists(ctxs[i]) && ctxs[i]->nlists.valid && ctxs[i]->nlists.kind == 0;
-  if (ref_order) {
-    for (int i = 0; i < n; i++) {
-      if (ctxs[i]->map.max_voxel_points > (uint32_t)kRefMaxVoxelPoints) {
-        c0->err = "PCM_FLAG_REFERENCE_KNN_ORDER supports at most " + std::to_string(kRefMaxVoxelPoints) + " points per voxel (this map: " + std::to_string(ctxs[i]->map.max_voxel_points) + ")";
-        return PCM_ERR_UNSUPPORTED;
-      }
-    }
-  }
-
-  int rounds_done = 0;
-  size_t prof_used = 0;
-  // Only the pairs the host still believes active are launched (the list rides in the kernel arguments, batches of
-  // <= kMaxListedPairs pairs): an early-exit workgroup is not free, and the late rounds of a batch have one or two live pairs.
-  // The list lags one round (the status bytes are read one round behind); a stale entry exits at once.
-  const bool use_list = (n <= kMaxListedPairs && window == n) || host_window;
-  std::vector<uint8_t> act((size_t)(host_window ? window : n));
-  for (size_t i = 0; i < act.size(); i++) act[i] = (uint8_t)i;
-  int next_queued = host_window ? window : n;   // host window: first pair that has not been launched yet
-  std::vector<uint8_t> prev_list;
-  KernelParams kpr = kp;
-  for (int r = 0; r < max_rounds; r++) {
-    const int nl = use_list ? (int)act.size() : n;
-    if (use_list) {
-      kpr.use_list = 1;
-      std::memcpy(kpr.active, act.data(), act.size());
-    }
-    const bool timed = stats_on && (!stats_sampled || (((unsigned)r + prof_phase) & 3u) == 0u);
-    launched_slots += (uint64_t)nl;
-    if (timed) {
-      while (w->ev_prof.size() < prof_used + 3) { hipEvent_t e; PCM_HIPCK(c0, hipEventCreate(&e)); w->ev_prof.push_back(e); }
-      PCM_HIPCK(c0, hipEventRecord(w->ev_prof[prof_used], st));
-      timed_launches++;
-      timed_slots += (uint64_t)nl;
-    }
-    // per round: correspondence search + residual/Jacobian + reduction in one launch, then the tiny
-    // per-pair sum + GN/LM step launch.  LM adds the (cheap) trial-cost launch + its step.
-    // PCM_FLAG_FUSED_STEP (off by default): the last workgroup of a pair's search launch takes the GN step (write-through hand-off of
-    // the partial rows, kernels.hip).  Measured slower than the second launch at every round size, the single-pair rounds
-    // included (profiles/r02_fused_step_threshold_sweep.txt): every workgroup pays a store drain and a returned atomic.
-    const bool fuse = use_list && !is_lm && !ndt && !gicp && !counters_on && !timing_on && kp.do_step && (g.flags & PCM_FLAG_FUSED_STEP);
-    if (ndt) launch_ndt(st, w->d_descs, w->d_states, kpr, nl, ndt_kind(g.model), false);
-    else if (gicp) launch_gicp(st, w->d_descs, w->d_states, kpr, nl, g.model == PCM_MODEL_VGICP, false);
-    else if (fuse) launch_linearize_fused(st, w->d_descs, w->d_states, kpr, lp, nl, w->d_flags + (size_t)r * n);
-    else if (ref_order) launch_linearize_reforder(st, w->d_descs, w->d_states, kpr, nl, write_sel);
-    else if (lists && !counters_on && !timing_on) launch_linearize_lists(st, w->d_descs, w->d_states, kpr, nl, write_sel);
-    else if (counted_search) launch_linearize_counted(st, w->d_descs, w->d_states, kpr, nl, write_sel, counters_on ? w->d_stats : nullptr, timing_on);
-    else launch_linearize(st, w->d_descs, w->d_states, kpr, nl, write_sel, counters_on ? w->d_stats : nullptr, timing_on);
-    if (timed) PCM_HIPCK(c0, hipEventRecord(w->ev_prof[prof_used + 1], st));
-    if (!fuse) launch_finish_round(st, w->d_descs, w->d_states, kpr, lp, nl, false, !is_lm, w->d_flags + (size_t)r * n, w->d_sums, use_list ? nullptr : w->d_queue, n);
-    if (is_lm) {
-      if (ndt) launch_ndt(st, w->d_descs, w->d_states, kpr, nl, ndt_kind(g.model), true);
-      else if (gicp) launch_gicp(st, w->d_descs, w->d_states, kpr, nl, g.model == PCM_MODEL_VGICP, true);
-      else launch_trial(st, w->d_descs, w->d_states, kpr, nl);
-      launch_finish_round(st, w->d_descs, w->d_states, kpr, lp, nl, true, true, w->d_flags + (size_t)r * n, w->d_sums, use_list ? nullptr : w->d_queue, n);
-    }
-    if (timed) {
-      if (!stats_sampled) PCM_HIPCK(c0, hipEventRecord(w->ev_prof[prof_used + 2], st));
-      prof_used += 3;
-    }
-    rounds_done = r + 1;
-    std::vector<uint8_t> this_list = act;   // pairs launched in round r
-    if (r >= 1) {  // look one round behind so the GPU always has the next round queued
-      volatile unsigned char* row = w->h_flags + (size_t)(r - 1) * n;
-      bool any_active = false;
-      const auto t_start = std::chrono::steady_clock::now();
-      std::vector<uint8_t> alive;
-      const int np = use_list ? (int)prev_list.size() : n;
-      for (int k = 0; k < np; k++) {
-        const int i = use_list ? (int)prev_list[(size_t)k] : k;
-        if (int wrc = wait_status_byte(c0, st, row + i, t_start)) return wrc;
-        any_active |= row[i] == 1;
-        if (row[i] == 1 && use_list) alive.push_back((uint8_t)i);
-      }
-      if (host_window) {
-        // pairs launched in round r (this_list) but not in round r - 1 have no status byte yet: they stay
-        for (uint8_t i : this_list) {
-          bool seen = false;
-          for (uint8_t q : prev_list) if (q == i) { seen = true; break; }
-          if (!seen) { alive.push_back(i); any_active = true; }
-        }
-        while ((int)alive.size() < window && next_queued < n) { alive.push_back((uint8_t)next_queued++); any_active = true; }
-      }
-      if (!any_active) break;
-      if (use_list) act.swap(alive);
-    }
-    prev_list.swap(this_list);
-  }
-  PCM_HIPCK(c0, hipGetLastError());
-  pcm_result* d_res = device_out ? static_cast<pcm_result*>(device_out) : w->d_results;
-  launch_pack_results(st, w->d_states, d_res, n);
-  std::vector<pcm_result> tmp;
-  pcm_result* h_res = host_out;
-  if (!h_res) { tmp.resize(n); h_res = tmp.data(); }
-  PCM_HIPCK(c0, hipMemcpyAsync(h_res, d_res, sizeof(pcm_result) * n, hipMemcpyDeviceToHost, st));
-  PCM_HIPCK(c0, hipStreamSynchronize(st));
-
-  if (counters_on) {
-    unsigned long long hs[16];
-    PCM_HIPCK(c0, hipMemcpy(hs, w->d_stats, sizeof(hs), hipMemcpyDeviceToHost));
-    for (int k = 0; k < 8; k++) c0->phase_cycles[k] += hs[8 + k];
-    c0->stats.candidates += hs[0];
-    c0->stats.slots_probed += hs[1];
-    c0->stats.tiles += hs[3];
-    c0->stats.tiles_lds_grid += hs[4];
-    c0->stats.tiles_lds_points += hs[2];
-  }
-  if (stats_on) {
-    double ms = 0.0, ms2 = 0.0;
-    for (size_t k = 0; k + 2 < prof_used + 1; k += 3) {
-      float t = 0.f;
-      if (hipEventElapsedTime(&t, w->ev_prof[k], w->ev_prof[k + 1]) == hipSuccess) ms += t;
-      if (!stats_sampled && hipEventElapsedTime(&t, w->ev_prof[k + 1], w->ev_prof[k + 2]) == hipSuccess) ms2 += t;
-    }
-    c0->stats.linearize_ms += ms;
-    c0->stats.residual_ms += ms2;
-    c0->stats.timed_launches += timed_launches;
-    c0->stats.timed_pair_slots += timed_slots;
-  }
-  c0->stats.launched_pair_slots += launched_slots;
-  c0->stats.linearize_launches += (uint64_t)rounds_done;
-  uint64_t passes = 0;
-  int worst = PCM_OK;
-  for (int i = 0; i < n; i++) {
-    passes += (uint64_t)(h_res[i].num_linearize + h_res[i].num_compute_error) * num_elements(ctxs[i]);
-    if (h_res[i].status != PCM_OK && worst != PCM_ERR_INTERNAL) worst = h_res[i].status;
-  }
-  c0->stats.point_passes += passes;
-  if (worst == PCM_ERR_INTERNAL) c0->err = "the round budget of the batch ran out before every pair finished (library bug): unfinished pairs carry PCM_ERR_INTERNAL";
-  else if (worst != PCM_OK) c0->err = "lm not converged!!";
-  return worst;
-}
-
-// one LINEARIZE or TRIAL pass at a caller-supplied pose (parity hook)
-int single_pass(pcm_ctx* c, const double T[16], bool linearize, double sums[kPartialStride]) {
-  if (c->cfg.model == PCM_MODEL_NDT_OMP) { c->err = "the pclomp NDT model is evaluated through pcm_ndt_derivatives"; return PCM_ERR_UNSUPPORTED; }
-  int rc = prepare(c);
-  if (rc != PCM_OK) return rc;
-  const bool ndt = is_ndt(c->cfg.model) || c->cfg.model == PCM_MODEL_VGICP_CUDA;
-  const Geom geom = pick_geom(num_elements(c), 1, ndt);
-  const KernelParams kp = kernel_params(c->cfg, geom);
-  Workspace* w = nullptr;
-  rc = ensure_ws(c, &w, 1, (size_t)std::max(geom.blocks_per_pair, geom.tiles_per_pair) * kPartialStride, 2);
-  if (rc != PCM_OK) return rc;
-  PairDesc d;
-  fill_desc(c, &d, w->d_partials);
-  PairState s;
-  float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  init_state(s, ident);
-  for (int i = 0; i < 16; i++) { s.x0[i] = T[i]; s.xi[i] = T[i]; }
-  s.mode = linearize ? MODE_LINEARIZE : MODE_TRIAL;
-  PCM_HIPCK(c, hipMemcpyAsync(w->d_descs, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
-  PCM_HIPCK(c, hipMemcpyAsync(w->d_states, &s, sizeof(s), hipMemcpyHostToDevice, c->stream));
-  KernelParams kp1 = kp;
-  kp1.do_step = 0;   // the last workgroup exports the sums instead of stepping
-  if (ndt) launch_ndt(c->stream, w->d_descs, w->d_states, kp1, 1, ndt_kind(c->cfg.model), !linearize);
-  else if (is_gicp(c->cfg.model)) launch_gicp(c->stream, w->d_descs, w->d_states, kp1, 1, c->cfg.model == PCM_MODEL_VGICP, !linearize);
-  else if (linearize && (c->cfg.flags & PCM_FLAG_REFERENCE_KNN_ORDER)) {
-    if (c->map.max_voxel_points > (uint32_t)kRefMaxVoxelPoints) { c->err = "PCM_FLAG_REFERENCE_KNN_ORDER supports at most " + std::to_string(kRefMaxVoxelPoints) + " points per voxel"; return PCM_ERR_UNSUPPORTED; }
-    launch_linearize_reforder(c->stream, w->d_descs, w->d_states, kp1, 1, true);
-  }
-  else if (linearize && uses_neighbour_lists(c) && c->nlists.valid && c->nlists.kind == 0) launch_linearize_lists(c->stream, w->d_descs, w->d_states, kp1, 1, true);
-  else if (linearize && (c->cfg.flags & PCM_FLAG_COUNTED_SEARCH)) launch_linearize_counted(c->stream, w->d_descs, w->d_states, kp1, 1, true, nullptr);
-  else if (linearize) launch_linearize(c->stream, w->d_descs, w->d_states, kp1, 1, true, nullptr, false);
-  else launch_trial(c->stream, w->d_descs, w->d_states, kp1, 1);
-  launch_finish_round(c->stream, w->d_descs, w->d_states, kp1, lsq_params(c->cfg), 1, !linearize, false, w->d_flags, w->d_sums);
-  PCM_HIPCK(c, hipGetLastError());
-  PCM_HIPCK(c, hipMemcpyAsync(sums, w->d_sums, sizeof(double) * kPartialStride, hipMemcpyDeviceToHost, c->stream));
-  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
-  return PCM_OK;
-}
-
-// one pclomp NDT pass on the device: launch, read the 48-double row back (pass 0/1: H, g, score; pass 2: H)
-int pclndt_eval(pcm_ctx* c, int pass, const NdtOmpParams& P, ndtomp::Eval* e, double gauss_d3 = 0.0) {
-  launch_pclndt_pass(c->stream, c->map, c->pleaf, c->pleaf_f, ndt_lists_view(c), c->src.d_pts, (uint32_t)c->src.n, P, pass, c->ndt_partials, c->ndt_out, gauss_d3);
-  PCM_HIPCK(c, hipGetLastError());
-  PCM_HIPCK(c, hipMemcpyAsync(c->ndt_out_host, c->ndt_out, sizeof(double) * 48, hipMemcpyDeviceToHost, c->stream));
-  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
-  std::memcpy(e->H, c->ndt_out_host, sizeof(double) * 36);
-  if (pass == 3) e->score = c->ndt_out_host[0];
-  else if (pass != 2) {
-    std::memcpy(e->g, c->ndt_out_host + 36, sizeof(double) * 6);
-    e->score = c->ndt_out_host[42];
-  }
-  c->stats.linearize_launches += 1;
-  c->stats.point_passes += c->src.n;
-  return PCM_OK;
-}
-
 auto make_ndt_solver(pcm_ctx* c) {
   auto ev = [c](int pass, const NdtOmpParams& P, ndtomp::Eval* e) { return pclndt_eval(c, pass, P, e); };
   ndtomp::Solver<decltype(ev)> s{ev};
@@ -820,166 +93,6 @@ auto make_ndt_solver(pcm_ctx* c) {
   s.max_iterations = c->cfg.max_iterations;
   s.num_neighbors = c->cfg.num_neighbors;
   return s;
-}
-
-// buffers of a batched pclomp NDT registration, owned by the first context of the batch
-struct NdtBatchWs {
-  DevBuf<NdtObject> d_objs{"d_objs"};
-  DevBuf<ndtomp::NdtMachine> d_ms{"d_ms"};
-  PinnedBuf<NdtObject> h_objs{"h_objs"};
-  PinnedBuf<ndtomp::NdtMachine> h_ms{"h_ms"};
-  PinnedBuf<unsigned char> h_flags{"h_flags"};   // mapped pinned: [round][object] status bytes of k_pclndt_batch_step
-  unsigned char* d_flags = nullptr;              // device view of h_flags
-  hipStream_t gst[4] = {nullptr, nullptr, nullptr, nullptr};   // streams of the lock-step groups, created back to back
-};
-
-void free_ndt_batch_ws(void* p) {
-  NdtBatchWs* w = static_cast<NdtBatchWs*>(p);
-  if (!w) return;
-  for (hipStream_t st : w->gst) if (st) (void)hipStreamDestroy(st);
-  delete w;
-}
-
-// pclomp::NormalDistributionsTransform::computeTransformation (ndt_omp_impl.hpp:69-156) for n objects: their solvers run on the
-// device (ndtomp::NdtMachine, pclndt_host.h), one derivatives launch + one step launch per round for all of them
-int pclndt_align_batch(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_result* res) {
-  pcm_ctx* c0 = ctxs[0];
-  for (int i = 0; i < n; i++) {
-    int rc = prepare(ctxs[i]);
-    if (rc != PCM_OK) { if (i) c0->err = ctxs[i]->err; return rc; }
-    if (ctxs[i]->stream != c0->stream) PCM_HIPCK(c0, hipStreamSynchronize(ctxs[i]->stream));   // its map / leaves were built on its own stream
-  }
-  if (!c0->ndt_ws) c0->ndt_ws = new (std::nothrow) NdtBatchWs();
-  if (!c0->ndt_ws) { c0->err = "out of host memory"; return PCM_ERR_HIP; }
-  NdtBatchWs& w = *static_cast<NdtBatchWs*>(c0->ndt_ws);
-  {
-    const size_t cap = (size_t)std::max(n, 16);
-    int rc = w.d_objs.reserve(c0, (size_t)n, cap);
-    if (rc == PCM_OK) rc = w.d_ms.reserve(c0, (size_t)n, cap);
-    if (rc == PCM_OK) rc = w.h_objs.reserve(c0, (size_t)n, cap);
-    if (rc == PCM_OK) rc = w.h_ms.reserve(c0, (size_t)n, cap);
-    if (rc != PCM_OK) return rc;
-  }
-  // an object asks for at most 12 evaluations per Newton iteration (1 + 10 trials + the Hessian pass) and runs max_iterations + 2 of them
-  int max_rounds = 2;
-  int max_blocks = 1;
-  for (int i = 0; i < n; i++) {
-    pcm_ctx* c = ctxs[i];
-    w.h_objs[i] = make_ndt_object(c->map, c->pleaf, c->pleaf_f, ndt_lists_view(c), c->src.d_pts, (uint32_t)c->src.n, c->ndt_partials);
-    max_blocks = std::max(max_blocks, (int)w.h_objs[i].nblocks);
-    ndtomp::ndt_machine_start(w.h_ms[i], guesses + 16 * (size_t)i, (double)c->cfg.ndt_step_size, c->cfg.translation_eps, (double)c->cfg.ndt_outlier_ratio,
-                              c->cfg.voxel_resolution, c->cfg.max_iterations, c->cfg.num_neighbors);
-    max_rounds = std::max(max_rounds, (c->cfg.max_iterations + 3) * 12 + 2);
-  }
-  const size_t flag_bytes = (size_t)max_rounds * (size_t)n;
-  {
-    if (!w.h_flags || flag_bytes > w.h_flags.cap) w.d_flags = nullptr;
-    const int rc = w.h_flags.reserve(c0, flag_bytes, std::max<size_t>(flag_bytes, 65536), hipHostMallocMapped);
-    if (rc != PCM_OK) return rc;
-    if (!w.d_flags) PCM_HIPCK(c0, hipHostGetDevicePointer(reinterpret_cast<void**>(&w.d_flags), w.h_flags.p, 0));
-  }
-  std::memset(w.h_flags, 0, flag_bytes);
-  hipStream_t st = c0->stream;
-  PCM_HIPCK(c0, hipMemcpyAsync(w.d_objs, w.h_objs, sizeof(NdtObject) * n, hipMemcpyHostToDevice, st));
-  PCM_HIPCK(c0, hipMemcpyAsync(w.d_ms, w.h_ms, sizeof(ndtomp::NdtMachine) * n, hipMemcpyHostToDevice, st));
-  PCM_HIPCK(c0, hipStreamSynchronize(st));   // the groups below run on their own streams
-  // The objects advance in up to four groups, each in lock-step on the stream of its first object: registrations need 6 ... 37
-  // Newton iterations on the same map, and a single lock-step batch runs every round at the pace of its largest kernel while most
-  // objects have finished.  At most two rounds of a group are in flight (the host confirms a round's status bytes before it queues
-  // the one after the next); a group whose objects have all finished sees that one round late and stops.
-  struct Group { int lo, hi, max_blocks, launched, confirmed; bool done; hipStream_t st; };
-  // Measured at config 4 (100k-point scans, tools/r03_scaling.sh): 8 objects -- four groups 1 175 registrations/s, two 1 122; 16 objects --
-  // one group 1 548, two 1 781, four 953; 32 objects -- one 2 340, two 2 753, three 2 217, four 1 990: one group's solver step and the
-  // ragged end of its pass overlap the other's pass; more groups only add launches and host-side waiting.
-  size_t total_points = 0;
-  for (int i = 0; i < n; i++) total_points += ctxs[i]->src.n;
-  // (the 27-cell searches -- KDTREE, DIRECT26 -- lose with two groups while they look their cells up one by one: 1 570 -> 1 213 at 32
-  // scans, their pass keeps the device busy alone; on the grid's neighbour-leaf lists they gain like the others: 2 760 -> 3 203)
-  const bool wide = (c0->cfg.num_neighbors == 0 || c0->cfg.num_neighbors > 7) && ndt_lists_view(c0).pts == nullptr;
-  int ngroups = total_points <= 1000000 ? std::min(n, 4) : (wide ? 1 : std::min(n, 2));
-  if (const char* e = getenv("PCM_NDT_GROUPS")) ngroups = std::max(1, std::min(std::min(n, 4), atoi(e)));   // measurements only
-  std::vector<Group> groups((size_t)ngroups);
-  for (int g = 0; g < ngroups; g++) {
-    Group& G = groups[(size_t)g];
-    G.lo = (int)((long long)n * g / ngroups); G.hi = (int)((long long)n * (g + 1) / ngroups);
-    G.launched = 0; G.confirmed = 0; G.done = false; G.max_blocks = 1;
-    // Streams of the groups' own, created back to back: HIP deals streams onto a handful of hardware queues in creation order, and two
-    // groups whose streams share a queue do not overlap.  (With the streams of the groups' first objects the first batch of a process
-    // ran at 3 225 registrations/s and a second batch of objects created later in the same process at 2 016, or the other way round.)
-    if (ngroups == 1) G.st = ctxs[G.lo]->stream;
-    else {
-      if (!w.gst[g]) PCM_HIPCK(c0, hipStreamCreateWithFlags(&w.gst[g], hipStreamNonBlocking));
-      G.st = w.gst[g];
-    }
-    for (int i = G.lo; i < G.hi; i++) G.max_blocks = std::max(G.max_blocks, (int)w.h_objs[i].nblocks);
-  }
-  const auto t_start = std::chrono::steady_clock::now();
-  auto next_query = t_start + std::chrono::milliseconds(5);
-  int live = ngroups;
-  unsigned idle_spins = 0;
-  while (live > 0) {
-    bool progress = false;
-    for (Group& G : groups) {
-      if (G.done) continue;
-      if (G.confirmed < G.launched) {   // status bytes of the oldest unconfirmed round of this group: all landed?
-        volatile unsigned char* row = w.h_flags + (size_t)G.confirmed * n;
-        bool ready = true, any_active = false;
-        for (int i = G.lo; i < G.hi; i++) { const unsigned char f = row[i]; ready &= f != 0; any_active |= f == 1; }
-        if (ready) {
-          G.confirmed++;
-          progress = true;
-          if (!any_active || G.confirmed >= max_rounds) { G.done = true; live--; continue; }
-        }
-      }
-      if (G.launched - G.confirmed < 2 && G.launched < max_rounds) {
-        launch_pclndt_batch_round(G.st, w.d_objs + G.lo, w.d_ms + G.lo, G.hi - G.lo, G.max_blocks, w.d_flags + (size_t)G.launched * n + G.lo);
-        G.launched++;
-        progress = true;
-      }
-    }
-    if (progress) { idle_spins = 0; continue; }
-    if ((++idle_spins & 0xfff) != 0) continue;
-    const auto now = std::chrono::steady_clock::now();
-    auto drain = [&]() { for (Group& G : groups) (void)hipStreamSynchronize(G.st); };
-    if (now - t_start > std::chrono::seconds(20)) { drain(); c0->err = "timeout waiting for the GPU round status"; return PCM_ERR_HIP; }
-    if (now >= next_query) {   // a dead stream never writes its status bytes (see wait_status_byte for why this is asked rarely)
-      next_query = now + std::chrono::milliseconds(5);
-      for (Group& G : groups)
-        if (!G.done && G.confirmed < G.launched && hipStreamQuery(G.st) == hipSuccess) {
-          volatile unsigned char* row = w.h_flags + (size_t)G.confirmed * n;
-          bool ready = true;
-          for (int i = G.lo; i < G.hi; i++) ready &= row[i] != 0;
-          if (!ready) { drain(); c0->err = "stream drained without a round status (kernel fault?)"; return PCM_ERR_HIP; }
-        }
-    }
-  }
-  PCM_HIPCK(c0, hipGetLastError());
-  for (Group& G : groups) PCM_HIPCK(c0, hipStreamSynchronize(G.st));
-  PCM_HIPCK(c0, hipMemcpyAsync(w.h_ms, w.d_ms, sizeof(ndtomp::NdtMachine) * n, hipMemcpyDeviceToHost, st));
-  PCM_HIPCK(c0, hipStreamSynchronize(st));
-  int worst = PCM_OK;
-  for (int i = 0; i < n; i++) {
-    const ndtomp::NdtMachine& m = w.h_ms[i];
-    pcm_result* out = &res[i];
-    std::memset(out, 0, sizeof(*out));
-    for (int k = 0; k < 16; k++) { out->T[k] = m.P.T[k]; out->T64[k] = (double)m.P.T[k]; }
-    std::memcpy(out->H, m.cur.H, sizeof(out->H));   // hessian_eigen_
-    out->cost = m.cur.score;                        // trans_probability_ * N
-    out->iterations = m.nr;
-    out->converged = m.converged;
-    out->num_linearize = m.n_deriv;
-    out->num_compute_error = m.n_hess;
-    out->status = m.request < 0 ? PCM_OK : PCM_ERR_HIP;   // a machine still asking after max_rounds cannot happen (bounded loops)
-    if (out->status != PCM_OK) { worst = out->status; c0->err = "pclomp NDT solver did not finish within its round budget"; }
-    ctxs[i]->stats.linearize_launches += (uint64_t)(m.n_deriv + m.n_hess);
-    ctxs[i]->stats.point_passes += (uint64_t)(m.n_deriv + m.n_hess) * ctxs[i]->src.n;
-  }
-  return worst;
-}
-
-int pclndt_align(pcm_ctx* c, const float guess[16], pcm_result* out) {
-  pcm_ctx* one[1] = {c};
-  return pclndt_align_batch(one, 1, guess, out);
 }
 
 }  // namespace
@@ -1491,8 +604,8 @@ int pcm_align(pcm_ctx* c, const float guess[16], pcm_result* out) {
   if (!guess || !out) return PCM_ERR_INVALID_ARGUMENT;
   int rc = validate_config(c, c->cfg);
   if (rc != PCM_OK) return rc;
-  if (c->cfg.model == PCM_MODEL_NDT_OMP) return pclndt_align(c, guess, out);
   pcm_ctx* arr[1] = {c};
+  if (c->cfg.model == PCM_MODEL_NDT_OMP) return pclndt_align_batch(arr, 1, guess, out);
   return align_batch_impl(arr, 1, guess, out, nullptr);
 }
 

@@ -208,8 +208,8 @@ struct pcm_ctx {
   bool lio_planes_valid = false;   // planes of the last pcm_obs_model(rematch=1) belong to the current scan
   pcm::DevBuf<float2> lio_aux{"lio_aux"};   // PCM_FLAG_LIO_REFERENCE_SEMANTICS: residuals_ / point_selected_surf_ of LaserMapping, in the caller's scan order;
   size_t lio_aux_n = 0;                     // they outlive the scan (std::vector::resize semantics, laser_mapping.cc:337-338)
-  void* ws = nullptr;   // batch workspace owned by this context (pcm_api.hip)
-  void* ndt_ws = nullptr;   // pclomp NDT: objects + solver machines of a batch (pcm_api.hip)
+  void* ws = nullptr;   // batch workspace owned by this context (align_batch.hip)
+  void* ndt_ws = nullptr;   // pclomp NDT: objects + solver machines of a batch (align_batch.hip)
   pcm::DevBuf<char> pre_arena{"pre_arena"};   // grow-only device scratch of the pre-processing operators
   pcm::DevBuf<char> bfgs{"bfgs"};             // GICP-BFGS functor: packed correspondence records + partial sums (gicp_bfgs.hip)
   size_t bfgs_m = 0;
