@@ -773,6 +773,89 @@ int pcm_occ_get_pgm(pcm_ctx *ctx, uint8_t *data, size_t capacity);
 /* the counters of the same rectangle (either may be NULL): what a caller needs to apply a threshold of its own */
 int pcm_occ_get_counts(pcm_ctx *ctx, uint32_t *n_occ, uint32_t *n_free, size_t capacity);
 
+/*
+ * The ring-tagged scan the LOAM front end reads, made on the device from the sensors' own buffers: jueying_slam's
+ * fusion_lidar_camera node (src/tool/integrate_points/src/fusion_lidar_camera.cpp: the LiDAR cloud, then 1-3 depth-camera clouds
+ * moved into the LiDAR frame with a ring from their pitch angle) and its rs_to_velodyne / hesai_to_velodyne converters
+ * (src/tool/rs_to_velodyne, src/tool/hesai_to_velodyne), which are the one-segment case.  The output is the kept points of the segments in segment
+ * order, each segment in input order, as 32-byte records:
+ *   PCM_SCAN_OUT_XYZIRT  x y z 1.0f | float intensity @16 | uint16 ring @20, 2 zero bytes | float time @24 | 4 zero bytes
+ *   PCM_SCAN_OUT_XYZIR   the same, time bytes zero          PCM_SCAN_OUT_XYZI   x y z 1.0f | intensity | 12 zero bytes
+ * i.e. stride 32, intensity offset 16, ring offset 20 for the front end.  Ring tables are the caller's (the node's own `int`
+ * arrays); the library embeds none.  A context of any model.  DESIGN.md section 15.
+ */
+#define PCM_SCAN_MAX_SEGMENTS 8
+#define PCM_SCAN_LIDAR_XYZIRT 0 /* vendor XYZIRT records: ring and double timestamp read from the record (handle_pc_msg) */
+#define PCM_SCAN_LIDAR_XYZI 1   /* organised XYZI cloud: ring from the point's position through ring_table, time 0 */
+#define PCM_SCAN_DEPTH 2        /* depth-camera cloud (pcl::PointXYZRGB, x y z first): convert_depth */
+#define PCM_SCAN_INTENSITY_FLOAT 0
+#define PCM_SCAN_INTENSITY_UINT8 1 /* converted to float by value */
+#define PCM_SCAN_RING_BY_HEIGHT 0  /* the reference's rule: height 16 -> table[id / width], height 128 -> table[id % height], else an error */
+#define PCM_SCAN_RING_DIV_WIDTH 1  /* table[id / width] whatever the height */
+#define PCM_SCAN_RING_MOD_HEIGHT 2 /* table[id % height] whatever the height */
+#define PCM_SCAN_OUT_XYZI 0        /* the converters' output_type */
+#define PCM_SCAN_OUT_XYZIR 1
+#define PCM_SCAN_OUT_XYZIRT 2
+
+typedef struct pcm_scan_segment {
+  int32_t kind;                  /* PCM_SCAN_LIDAR_XYZIRT / PCM_SCAN_LIDAR_XYZI / PCM_SCAN_DEPTH */
+  int32_t memory;                /* PCM_MEM_HOST (staged in one upload) or PCM_MEM_DEVICE (read in place) */
+  const void *points;            /* n records of stride_bytes, three floats x y z first; 4-byte aligned */
+  size_t n;
+  size_t stride_bytes;
+  size_t intensity_offset_bytes; /* LiDAR kinds */
+  size_t ring_offset_bytes;      /* LIDAR_XYZIRT: a uint16 */
+  size_t timestamp_offset_bytes; /* LIDAR_XYZIRT: a double (4-byte aligned); time = float(timestamp[i] - timestamp[0]) */
+  int32_t intensity_type;        /* PCM_SCAN_INTENSITY_* */
+  int32_t ring_rule;             /* LIDAR_XYZI: PCM_SCAN_RING_* */
+  int32_t width, height;         /* LIDAR_XYZI: the organised cloud's */
+  const int *ring_table;         /* LIDAR_XYZI: host memory; every index the rule can reach must lie inside it */
+  int32_t ring_table_len;
+  int32_t dt_sec, dt_nsec;       /* DEPTH: camera stamp - LiDAR stamp; time = float(dt_sec * 1.0 + dt_nsec / 1000000000.0) */
+  int32_t reserved;
+  double T[16];                  /* DEPTH: camera_T of the node (the transposed 4x4): out.x = x T[0] + y T[4] + z T[8] + T[12], ... */
+} pcm_scan_segment;
+
+typedef struct pcm_scan_fuse_params {
+  double depth_filter;           /* 1.8  config/fusion_param.yaml: a camera point with z > depth_filter is dropped; < 0 = off */
+  double pitch_scale;            /* 28.6478897565  pitch = asin(z / dist) * pitch_scale */
+  double pitch_min;              /* -40  pitch_min <= pitch < pitch_max: ring = table[int(round(pitch + pitch_offset))] */
+  double pitch_max;              /* 12 */
+  double pitch_offset;           /* 40 */
+  const int *pitch_ring_table;   /* host memory (the node's RING_MAP_16); NULL only without DEPTH segments */
+  int32_t pitch_ring_table_len;  /* an index outside the table gives ring_otherwise and is counted (n_pitch_index_clamped) */
+  int32_t ring_below;            /* 47  pitch < pitch_min */
+  int32_t ring_otherwise;        /* 51  pitch >= pitch_max or NaN */
+  float depth_intensity;         /* 100 */
+  int32_t output_layout;         /* PCM_SCAN_OUT_XYZIRT */
+  int32_t reserved[9];
+} pcm_scan_fuse_params;
+
+typedef struct pcm_scan_segment_counts {
+  uint32_t n_in, n_nan, n_depth_filtered, n_kept;
+  uint32_t out_offset;           /* first record of this segment in the output */
+  uint32_t reserved[3];
+} pcm_scan_segment_counts;
+
+typedef struct pcm_scan_fuse_result {
+  pcm_scan_segment_counts seg[PCM_SCAN_MAX_SEGMENTS];
+  uint32_t n_out;
+  uint32_t n_pitch_index_clamped;
+  int32_t status;
+  int32_t reserved[5];
+} pcm_scan_fuse_result;
+
+/* the reference's scalars; no table */
+void pcm_scan_default_fuse_params(pcm_scan_fuse_params *params);
+/* 1..8 segments of any kinds in any order, at most 2^27 points together.  params NULL = defaults (no DEPTH segment then).
+ * out NULL: the records stay in a buffer of the context (pcm_scan_fused), nothing but the counters returns to the host.
+ * Else `out` (out_memory: host or device) holds capacity_points records; when that is too small the counts are set, no
+ * record past the capacity is written and PCM_ERR_INVALID_ARGUMENT returns. */
+int pcm_scan_fuse(pcm_ctx *ctx, const pcm_scan_segment *segs, int n_segs, const pcm_scan_fuse_params *params, void *out, size_t capacity_points, int out_memory,
+                  pcm_scan_fuse_result *res);
+/* the last pcm_scan_fuse with out = NULL: device memory of the context, valid until the next call of it */
+int pcm_scan_fused(pcm_ctx *ctx, const void **device_points, size_t *n);
+
 /* profiling flags: bit0 = bracket every residual launch with HIP events on the
  * launch stream (pcm_stats.linearize_ms); bit1 = collect the kNN candidate /
  * probe counters (slower kernel variant; use in an untimed pass); bit2 = in-kernel

@@ -388,6 +388,10 @@ public:
     check(pcm_loam_frame_begin(ctx_, scan->points.data(), scan->size(), sizeof(PointIn), ioff, roff, PCM_MEM_HOST, fp, &features_),
           "pcm_loam_frame_begin");
   }
+  // the same for ring-tagged records that already lie in device memory (ScanFusion::fuseToFrontEnd)
+  void setInputScanDevice(const void* device_points, size_t n, size_t stride, size_t intensity_offset, size_t ring_offset, const pcm_loam_feature_params* fp = nullptr) {
+    check(pcm_loam_frame_begin(ctx_, device_points, n, stride, intensity_offset, ring_offset, PCM_MEM_DEVICE, fp, &features_), "pcm_loam_frame_begin");
+  }
   const pcm_loam_features_result& featuresResult() const { return features_; }
 
   // the loop of scan2MapOptimization; transformTobeMapped is updated in place.  false: too few features (left as it was).
@@ -773,6 +777,112 @@ private:
   pcm_loam_feature_params params_;
   pcm_loam_features_result last_{};
   std::vector<float> corner_, surf_;
+};
+
+// jueying_slam's fusion_lidar_camera node (src/tool/integrate_points/src/fusion_lidar_camera.cpp) on the device: the node's
+// parameters (camera_T, depth_filter) and its own ring tables in, its callback's clouds in, the fused VelodynePointXYZIRT scan
+// born in device memory and handed to the front end of a LoamScanToMap without a host copy.  Message
+// synchronisation and fromROSMsg stay with the caller.  Over a LoamScanToMap it shares that context; alone it owns one.
+//     pcm_amd::ScanFusion<PointType> fusion(loam);
+//     fusion.setCameraT(camera_T); fusion.setDepthFilter(depth_filter); fusion.setPitchRingTable(RING_MAP_16, 52);
+//     // callback(lidar_msg, depth_0_msg, ...):
+//     fusion.begin();
+//     fusion.addLidar(*pc_lidar);                                   // RsPointXYZIRT: members intensity, ring, timestamp
+//     fusion.addDepth(*pc_depth_0, camera_fusion_index[0], time_0_sec, time_0_nsec);
+//     fusion.fuseToFrontEnd(&feature_params);                       // replaces publish + imageProjection + featureExtraction
+template <typename PointT>
+class ScanFusion {
+public:
+  explicit ScanFusion(int device = 0) : ctx_(pcm_create(device, nullptr)), own_(true) {
+    if (!ctx_) throw std::runtime_error("pcm_create failed");
+    pcm_scan_default_fuse_params(&params_);
+  }
+  explicit ScanFusion(LoamScanToMap<PointT>& loam) : ctx_(loam.context()), loam_(&loam), own_(false) { pcm_scan_default_fuse_params(&params_); }
+  ~ScanFusion() { if (own_ && ctx_) pcm_destroy(ctx_); }
+  ScanFusion(const ScanFusion&) = delete;
+  ScanFusion& operator=(const ScanFusion&) = delete;
+
+  pcm_scan_fuse_params& params() { return params_; }
+  void setCameraT(const std::vector<std::vector<double>>& camera_T) { camera_T_ = camera_T; }          // camera_T0 .. camera_T2
+  void setDepthFilter(double v) { params_.depth_filter = v; }                                           // depth_filter
+  // the node's own arrays (they must outlive this object's calls)
+  void setPitchRingTable(const int* table, int n) { params_.pitch_ring_table = table; params_.pitch_ring_table_len = n; }   // RING_MAP_16
+  void setOutputType(int output_type) { params_.output_layout = output_type; }                          // the converters' output_type
+
+  void begin() { n_segs_ = 0; }
+  // handle_pc_msg: a vendor XYZIRT cloud (members intensity -- float or uint8_t --, ring, timestamp)
+  template <typename PointIn>
+  void addLidar(const pcl::PointCloud<PointIn>& cloud) {
+    pcm_scan_segment& g = next(PCM_SCAN_LIDAR_XYZIRT, cloud.points.data(), cloud.points.size(), sizeof(PointIn));
+    const PointIn probe{};
+    const char* base = reinterpret_cast<const char*>(&probe);
+    g.intensity_offset_bytes = (size_t)(reinterpret_cast<const char*>(&probe.intensity) - base);
+    g.ring_offset_bytes = (size_t)(reinterpret_cast<const char*>(&probe.ring) - base);
+    g.timestamp_offset_bytes = (size_t)(reinterpret_cast<const char*>(&probe.timestamp) - base);
+    g.intensity_type = sizeof(probe.intensity) == 1 ? PCM_SCAN_INTENSITY_UINT8 : PCM_SCAN_INTENSITY_FLOAT;
+  }
+  // the XYZI branch: an organised cloud and the node's row -> ring table for its height (RING_MAP_16 / RING_ID_MAP_RUBY)
+  template <typename PointIn>
+  void addLidarOrganised(const pcl::PointCloud<PointIn>& cloud, int width, int height, const int* ring_table, int ring_table_len) {
+    pcm_scan_segment& g = next(PCM_SCAN_LIDAR_XYZI, cloud.points.data(), cloud.points.size(), sizeof(PointIn));
+    const PointIn probe{};
+    g.intensity_offset_bytes = (size_t)(reinterpret_cast<const char*>(&probe.intensity) - reinterpret_cast<const char*>(&probe));
+    g.intensity_type = PCM_SCAN_INTENSITY_FLOAT;
+    g.ring_rule = PCM_SCAN_RING_BY_HEIGHT;
+    g.width = width; g.height = height; g.ring_table = ring_table; g.ring_table_len = ring_table_len;
+  }
+  // convert_depth(pc_depth, ..., camera, time_depth_sec, time_depth_nsec)
+  template <typename PointIn>
+  void addDepth(const pcl::PointCloud<PointIn>& cloud, int camera, int time_depth_sec, int time_depth_nsec) {
+    if (camera < 0 || (size_t)camera >= camera_T_.size() || camera_T_[(size_t)camera].size() < 16) throw std::runtime_error("ScanFusion: no camera_T for this camera");
+    pcm_scan_segment& g = next(PCM_SCAN_DEPTH, cloud.points.data(), cloud.points.size(), sizeof(PointIn));
+    for (int k = 0; k < 16; k++) g.T[k] = camera_T_[(size_t)camera][(size_t)k];
+    g.dt_sec = time_depth_sec; g.dt_nsec = time_depth_nsec;
+  }
+  // the fused scan stays on the device (pcm_scan_fused)
+  const pcm_scan_fuse_result& fuse() {
+    check(pcm_scan_fuse(ctx_, segs_, n_segs_, &params_, nullptr, 0, PCM_MEM_DEVICE, &last_), "pcm_scan_fuse");
+    return last_;
+  }
+  // ... and becomes the LOAM source of the LoamScanToMap this object was made over
+  const pcm_scan_fuse_result& fuseToFrontEnd(const pcm_loam_feature_params* fp = nullptr) {
+    if (!loam_) throw std::runtime_error("ScanFusion: not constructed over a LoamScanToMap");
+    fuse();
+    const void* d = nullptr;
+    size_t n = 0;
+    check(pcm_scan_fused(ctx_, &d, &n), "pcm_scan_fused");
+    loam_->setInputScanDevice(d, n, 32, 16, 20, fp);
+    return last_;
+  }
+  // the published cloud on the host, for a node that still publishes it: 32-byte VelodynePointXYZIRT records
+  const pcm_scan_fuse_result& fuseToHost(std::vector<unsigned char>* records) {
+    size_t total = 0;
+    for (int s = 0; s < n_segs_; s++) total += segs_[s].n;
+    records->resize(32 * (total ? total : 1));
+    check(pcm_scan_fuse(ctx_, segs_, n_segs_, &params_, records->data(), total ? total : 1, PCM_MEM_HOST, &last_), "pcm_scan_fuse");
+    records->resize(32 * (size_t)last_.n_out);
+    return last_;
+  }
+
+private:
+  pcm_scan_segment& next(int kind, const void* points, size_t n, size_t stride) {
+    if (n_segs_ >= PCM_SCAN_MAX_SEGMENTS) throw std::runtime_error("ScanFusion: too many clouds");
+    pcm_scan_segment& g = segs_[n_segs_++];
+    g = pcm_scan_segment{};
+    g.kind = kind; g.memory = PCM_MEM_HOST; g.points = points; g.n = n; g.stride_bytes = stride;
+    return g;
+  }
+  void check(int rc, const char* what) const {
+    if (rc != PCM_OK) throw std::runtime_error(std::string(what) + ": " + pcm_last_error(ctx_));
+  }
+  pcm_ctx* ctx_ = nullptr;
+  LoamScanToMap<PointT>* loam_ = nullptr;
+  bool own_ = false;
+  pcm_scan_fuse_params params_;
+  pcm_scan_fuse_result last_{};
+  pcm_scan_segment segs_[PCM_SCAN_MAX_SEGMENTS];
+  int n_segs_ = 0;
+  std::vector<std::vector<double>> camera_T_;
 };
 
 }  // namespace pcm_amd

@@ -27,6 +27,7 @@ SYMBOLS = [
     "pcm_loam_dynmap_load", "pcm_loam_dynmap_crop", "pcm_loam_dynmap_info", "pcm_loam_dynmap_global",
     "pcm_occ_default_params", "pcm_occ_reset", "pcm_occ_insert_scans", "pcm_occ_insert_keyframes", "pcm_occ_get_scan", "pcm_occ_status",
     "pcm_occ_info", "pcm_occ_get_map", "pcm_occ_get_pgm", "pcm_occ_get_counts",
+    "pcm_scan_default_fuse_params", "pcm_scan_fuse", "pcm_scan_fused",
 ]
 
 PCM_ABI_VERSION = 3   # include/pcm_amd.h
@@ -175,6 +176,38 @@ class PcmOccParams(C.Structure):
                 ("max_radius", C.c_double), ("fill_with_white", C.c_int32), ("use_nan", C.c_int32), ("reserved", C.c_int32 * 8)]
 
 
+PCM_SCAN_MAX_SEGMENTS = 8
+PCM_SCAN_LIDAR_XYZIRT, PCM_SCAN_LIDAR_XYZI, PCM_SCAN_DEPTH = 0, 1, 2
+PCM_SCAN_INTENSITY_FLOAT, PCM_SCAN_INTENSITY_UINT8 = 0, 1
+PCM_SCAN_RING_BY_HEIGHT, PCM_SCAN_RING_DIV_WIDTH, PCM_SCAN_RING_MOD_HEIGHT = 0, 1, 2
+PCM_SCAN_OUT_XYZI, PCM_SCAN_OUT_XYZIR, PCM_SCAN_OUT_XYZIRT = 0, 1, 2
+
+
+class PcmScanSegment(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("memory", C.c_int32), ("points", C.c_void_p), ("n", C.c_size_t), ("stride_bytes", C.c_size_t),
+                ("intensity_offset_bytes", C.c_size_t), ("ring_offset_bytes", C.c_size_t), ("timestamp_offset_bytes", C.c_size_t),
+                ("intensity_type", C.c_int32), ("ring_rule", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("ring_table", C.c_void_p), ("ring_table_len", C.c_int32), ("dt_sec", C.c_int32), ("dt_nsec", C.c_int32),
+                ("reserved", C.c_int32), ("T", C.c_double * 16)]
+
+
+class PcmScanFuseParams(C.Structure):
+    _fields_ = [("depth_filter", C.c_double), ("pitch_scale", C.c_double), ("pitch_min", C.c_double), ("pitch_max", C.c_double),
+                ("pitch_offset", C.c_double), ("pitch_ring_table", C.c_void_p), ("pitch_ring_table_len", C.c_int32),
+                ("ring_below", C.c_int32), ("ring_otherwise", C.c_int32), ("depth_intensity", C.c_float), ("output_layout", C.c_int32),
+                ("reserved", C.c_int32 * 9)]
+
+
+class PcmScanSegmentCounts(C.Structure):
+    _fields_ = [("n_in", C.c_uint32), ("n_nan", C.c_uint32), ("n_depth_filtered", C.c_uint32), ("n_kept", C.c_uint32),
+                ("out_offset", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class PcmScanFuseResult(C.Structure):
+    _fields_ = [("seg", PcmScanSegmentCounts * PCM_SCAN_MAX_SEGMENTS), ("n_out", C.c_uint32), ("n_pitch_index_clamped", C.c_uint32),
+                ("status", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
 def library_path() -> str:
     """The in-tree build; PCM_AMD_LIBRARY names another build of the same ABI (A/B measurements of two builds on one box)."""
     return os.environ.get("PCM_AMD_LIBRARY") or os.path.join(_HERE, "libpcm_amd.so")
@@ -312,5 +345,9 @@ def load_library():
     L.pcm_occ_get_map.argtypes = [vp, vp, sz]
     L.pcm_occ_get_pgm.argtypes = [vp, vp, sz]
     L.pcm_occ_get_counts.argtypes = [vp, vp, vp, sz]
+    L.pcm_scan_default_fuse_params.argtypes = [C.POINTER(PcmScanFuseParams)]
+    L.pcm_scan_default_fuse_params.restype = None
+    L.pcm_scan_fuse.argtypes = [vp, C.POINTER(PcmScanSegment), i32, C.POINTER(PcmScanFuseParams), vp, sz, i32, C.POINTER(PcmScanFuseResult)]
+    L.pcm_scan_fused.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
     _LIB = L
     return L

@@ -219,6 +219,9 @@ struct pcm_ctx {
   void* loam = nullptr;   // PCM_MODEL_LOAM: maps, features and device state (loam_api.hip)
   void* loam_fe = nullptr;   // PCM_MODEL_LOAM: the front end's cross-frame state and last-frame outputs (loam_features.hip)
   void* occ = nullptr;   // any model: the 2D occupancy map (occ_map.hip)
+  // any model: scan fusion (scan_fuse.hip): staged host segments, the fused records (pcm_scan_fused), counters + tables + scan scratch
+  pcm::DevBuf<char> scan_in{"scan_in"}, scan_out{"scan_out"}, scan_tmp{"scan_tmp"};
+  size_t scan_n = 0;     // records of the last pcm_scan_fuse with out = NULL that scan_out still holds
   int profiling = 0;  // bit0: HIP-event timing of residual launches, bit1: kNN counters
 };
 

@@ -1288,3 +1288,169 @@ LoamRegistration.load_map = _loam_load_map
 LoamRegistration.crop_map = _loam_crop_map
 LoamRegistration.dynmap_info = _loam_dynmap_info
 LoamRegistration.global_map = _loam_global_map
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Scan fusion and ring converters on the device: fusion_lidar_camera / rs_to_velodyne / hesai_to_velodyne
+# ---------------------------------------------------------------------------------------------------------------------------
+FUSED_STRIDE, FUSED_INTENSITY, FUSED_RING, FUSED_TIME = 32, 16, 20, 24   # the output records (VelodynePointXYZIRT)
+_SCAN_LAYOUT = {"XYZI": capi.PCM_SCAN_OUT_XYZI, "XYZIR": capi.PCM_SCAN_OUT_XYZIR, "XYZIRT": capi.PCM_SCAN_OUT_XYZIRT, 0: 0, 1: 1, 2: 2}
+_SCAN_ITYPE = {"f32": capi.PCM_SCAN_INTENSITY_FLOAT, "u8": capi.PCM_SCAN_INTENSITY_UINT8}
+_SCAN_RULE = {"height": capi.PCM_SCAN_RING_BY_HEIGHT, "div_width": capi.PCM_SCAN_RING_DIV_WIDTH, "mod_height": capi.PCM_SCAN_RING_MOD_HEIGHT}
+
+
+@dataclasses.dataclass
+class ScanSegment:
+    """One input of fuse_scans.  points: a host array or a device tensor of n x stride bytes."""
+    kind: int
+    points: object
+    stride: int
+    intensity_offset: int = 16
+    ring_offset: int = 0
+    timestamp_offset: int = 0
+    intensity_type: str = "f32"
+    ring_rule: str = "height"
+    width: int = 0
+    height: int = 0
+    ring_table: object = None
+    T: object = None
+    dt_sec: int = 0
+    dt_nsec: int = 0
+
+
+def lidar_xyzirt_segment(points, stride=32, intensity_offset=16, ring_offset=20, timestamp_offset=24, intensity_type="f32") -> ScanSegment:
+    """Vendor XYZIRT records (default layout: rs_to_velodyne.cpp's RsPointXYZIRT)."""
+    return ScanSegment(capi.PCM_SCAN_LIDAR_XYZIRT, points, stride, intensity_offset, ring_offset, timestamp_offset, intensity_type)
+
+
+def lidar_xyzi_segment(points, width, height, ring_table, stride=32, intensity_offset=16, intensity_type="f32", ring_rule="height") -> ScanSegment:
+    """An organised pcl::PointXYZI cloud; ring_table is the node's own row -> ring array."""
+    return ScanSegment(capi.PCM_SCAN_LIDAR_XYZI, points, stride, intensity_offset, intensity_type=intensity_type, ring_rule=ring_rule, width=width,
+                       height=height, ring_table=ring_table)
+
+
+def depth_segment(points, T, dt_sec=0, dt_nsec=0, stride=32) -> ScanSegment:
+    """A depth-camera cloud (pcl::PointXYZRGB records); T: the node's camera_T entry, 16 doubles."""
+    return ScanSegment(capi.PCM_SCAN_DEPTH, points, stride, T=T, dt_sec=dt_sec, dt_nsec=dt_nsec)
+
+
+def scan_segments(segments):
+    """(ctypes array of pcm_scan_segment, objects to keep alive while it is in use)."""
+    arr = (capi.PcmScanSegment * max(len(segments), 1))()
+    keep = []
+    for k, s in enumerate(segments):
+        ptr, n, mem, ka = _scan_arg(s.points, s.stride)
+        keep.append(ka)
+        g = arr[k]
+        g.kind, g.memory, g.points, g.n, g.stride_bytes = s.kind, mem, ptr if n else None, n, s.stride
+        g.intensity_offset_bytes, g.ring_offset_bytes, g.timestamp_offset_bytes = s.intensity_offset, s.ring_offset, s.timestamp_offset
+        g.intensity_type, g.ring_rule, g.width, g.height = _SCAN_ITYPE[s.intensity_type], _SCAN_RULE[s.ring_rule], int(s.width), int(s.height)
+        if s.ring_table is not None:
+            t = np.ascontiguousarray(s.ring_table, np.int32)
+            keep.append(t)
+            g.ring_table, g.ring_table_len = t.ctypes.data, t.size
+        g.dt_sec, g.dt_nsec = int(s.dt_sec), int(s.dt_nsec)
+        if s.T is not None:
+            g.T[:] = [float(v) for v in np.asarray(s.T, np.float64).reshape(16)]
+    return arr, keep
+
+
+def scan_fuse_params(defaults, params: dict):
+    """pcm_scan_fuse_params from the defaults `defaults(p)` fills and keyword overrides (pitch_ring_table: an int array; layout)."""
+    p = capi.PcmScanFuseParams()
+    defaults(C.byref(p))
+    keep = []
+    for k, v in (params or {}).items():
+        if k == "pitch_ring_table":
+            if v is not None:
+                t = np.ascontiguousarray(v, np.int32)
+                keep.append(t)
+                p.pitch_ring_table, p.pitch_ring_table_len = t.ctypes.data, t.size
+        elif k in ("layout", "output_layout"):
+            p.output_layout = _SCAN_LAYOUT[v]
+        elif k.startswith("reserved") or not hasattr(p, k):
+            raise KeyError(k)
+        else:
+            setattr(p, k, v)
+    return p, keep
+
+
+def scan_result(r: capi.PcmScanFuseResult, n_segs: int) -> dict:
+    d = {k: [getattr(r.seg[s], k) for s in range(n_segs)] for k in ("n_in", "n_nan", "n_depth_filtered", "n_kept", "out_offset")}
+    d.update(n_out=r.n_out, n_pitch_index_clamped=r.n_pitch_index_clamped, status=r.status)
+    return d
+
+
+def _fuse_scans(self, segments, params=None, out=None):
+    """pcm_scan_fuse.  out None: the records stay on the device in the context's buffer -> (None, counts); out "host": -> ((n_out, 32)
+    uint8 array, counts); out a device tensor or a host array of capacity x 32 bytes: filled -> (out, counts)."""
+    arr, keep = scan_segments(segments)
+    p, keep_p = scan_fuse_params(self._L.pcm_scan_default_fuse_params, params)
+    r = capi.PcmScanFuseResult()
+    ptr, cap, mem, ret = None, 0, capi.MEM_HOST, None
+    if isinstance(out, str) and out == "host":
+        ret = np.zeros((max(sum(a.n for a in arr[:len(segments)]), 1), FUSED_STRIDE), np.uint8)
+        ptr, cap = ret.ctypes.data, ret.shape[0]
+    elif out is not None:
+        ptr, cap, mem, ret = _scan_arg(out, FUSED_STRIDE)
+        if mem == capi.MEM_HOST and ret is not out:
+            raise ValueError("a host output buffer must be a contiguous array")
+    rc = self._L.pcm_scan_fuse(self._h, arr, len(segments), C.byref(p), ptr, cap, mem, C.byref(r))
+    counts = scan_result(r, len(segments))
+    del keep, keep_p
+    if rc != capi.PCM_OK:
+        e = capi.PcmError(rc, (self._L.pcm_last_error(self._h) or b"").decode())
+        e.counts = counts
+        raise e
+    if isinstance(out, str):
+        ret = ret[:r.n_out]
+    return ret, counts
+
+
+def _fused_scan(self):
+    """(device pointer, n) of the records the last fuse_scans(out=None) left in the context."""
+    ptr, n = C.c_void_p(), C.c_size_t()
+    self._check(self._L.pcm_scan_fused(self._h, C.byref(ptr), C.byref(n)))
+    return ptr.value or 0, n.value
+
+
+def rs_to_velodyne(reg, points, output_type="XYZIRT", organised=None, **layout):
+    """rs_to_velodyne.cpp: rsHandler_XYZIRT (vendor XYZIRT records; `layout`: lidar_xyzirt_segment's offsets) or, with
+    organised = (width, height, ring_table), rsHandler_XYZI.  -> ((n, 32) uint8 records, counts)."""
+    if organised is not None:
+        w, h, table = organised
+        seg = lidar_xyzi_segment(points, w, h, table, **layout)
+        output_type = "XYZIR" if output_type == "XYZIRT" else output_type   # rsHandler_XYZI publishes VelodynePointXYZIR
+    else:
+        seg = lidar_xyzirt_segment(points, **layout)
+    return reg.fuse_scans([seg], {"layout": output_type}, out="host")
+
+
+def hesai_to_velodyne(reg, points, output_type="XYZIRT", organised=None, **layout):
+    """hesai_to_velodyne.cpp: the same loops over HesaiPointXYZIRT (48 bytes: uint8 intensity @16, double timestamp @24, uint16 ring @32)."""
+    if organised is None:
+        layout = {**dict(stride=48, intensity_offset=16, ring_offset=32, timestamp_offset=24, intensity_type="u8"), **layout}
+    return rs_to_velodyne(reg, points, output_type, organised, **layout)
+
+
+def fuse_lidar_cameras(reg, lidar: ScanSegment, cameras, out=None, **params):
+    """fusion_lidar_camera.cpp's callback: the LiDAR segment, then one depth segment per (points, T, dt_sec, dt_nsec) of `cameras`."""
+    return reg.fuse_scans([lidar] + [depth_segment(*c) for c in cameras], params, out=out)
+
+
+def _loam_frame_begin_fused(self, segments, fuse_params=None, **feature_params):
+    """fuse_scans into the context's device buffer, then pcm_loam_frame_begin on it where it lies -> (features result, counts)."""
+    _, counts = self.fuse_scans(segments, fuse_params, out=None)
+    ptr, n = self.fused_scan()
+    fp = {k: v for k, v in feature_params.items() if k not in _FEATURE_LAYOUT}
+    p = _feature_params(self._L, fp)
+    r = capi.PcmLoamFeaturesResult()
+    self._check(self._L.pcm_loam_frame_begin(self._h, ptr, n, FUSED_STRIDE, FUSED_INTENSITY, FUSED_RING, capi.MEM_DEVICE, C.byref(p), C.byref(r)))
+    self.n_corner, self.n_surf = r.num_corner, r.num_surf
+    return _features_result(r), counts
+
+
+for _cls in (Registration, LoamRegistration, OccupancyMap2D):
+    _cls.fuse_scans = _fuse_scans
+    _cls.fused_scan = _fused_scan
+LoamRegistration.frame_begin_fused = _loam_frame_begin_fused
