@@ -856,6 +856,58 @@ int pcm_scan_fuse(pcm_ctx *ctx, const pcm_scan_segment *segs, int n_segs, const 
 /* the last pcm_scan_fuse with out = NULL: device memory of the context, valid until the next call of it */
 int pcm_scan_fused(pcm_ctx *ctx, const void **device_points, size_t *n);
 
+/* ---- spinning-LiDAR handlers of jueying_lio's PointCloudPreprocess on sensor_msgs::PointCloud2 records ------------------------------
+ * VelodyneHandler (jueying_lio/src/pointcloud_preprocess.cc:151-227), RslidarHandler (:229-305), Oust64Handler (:120-149) and
+ * LivoxHandler (:89-118): n records of msg->data.data() -> the kept points, in input order, as pcl::PointXYZINormal records (48
+ * bytes: x y z 1, 0 0 0 0, intensity, curvature [ms], 0 0), exactly what pcm_livox_filter writes.  The record is described by a
+ * stride and byte offsets (x, with y and z behind it, intensity: floats; the time and ring fields by their kinds); every offset
+ * but the ring's is a multiple of 4 and the buffer is 4-byte aligned.  Velodyne and RoboSense clouds whose last point's time is
+ * not > 0 get their offset times from the yaw of each point and per-ring state carried through the cloud; on the device that
+ * serial chain runs as an exact scan over composed functions.  A context of any model.  DESIGN.md section 16. */
+#define PCM_LIDAR_VELODYNE 2   /* the reference's LidarType values (pointcloud_preprocess.h) */
+#define PCM_LIDAR_OUSTER 3
+#define PCM_LIDAR_RSLIDAR 4
+#define PCM_LIDAR_LIVOX_STD 5  /* livox in PointCloud2 form */
+#define PCM_LIDAR_TIME_FLOAT 0
+#define PCM_LIDAR_TIME_DOUBLE 1
+#define PCM_LIDAR_TIME_UINT32 2
+#define PCM_LIDAR_RING_UINT8 0
+#define PCM_LIDAR_RING_UINT16 1
+#define PCM_LIDAR_MAX_SCANS 256
+
+typedef struct pcm_lidar_desc {
+  int32_t type;                  /* PCM_LIDAR_* */
+  int32_t time_kind;             /* PCM_LIDAR_TIME_* of the field at time_offset_bytes */
+  int32_t ring_kind;             /* PCM_LIDAR_RING_* of the field at ring_offset_bytes (Velodyne / RoboSense without times only) */
+  int32_t num_scans;             /* scan_line: rings are 0 .. num_scans - 1, at most PCM_LIDAR_MAX_SCANS */
+  int32_t point_filter_num;      /* point i is a candidate iff i % point_filter_num == 0 */
+  float time_scale;              /* Velodyne, RoboSense, Livox: time unit -> ms */
+  size_t stride_bytes;
+  size_t xyz_offset_bytes;
+  size_t intensity_offset_bytes;
+  size_t time_offset_bytes;
+  size_t ring_offset_bytes;
+  double blind;                  /* compared squared: kept when r^2 > blind^2 (Velodyne, RoboSense), when !(r^2 < blind^2) (Ouster, Livox) */
+  int32_t reserved[8];
+} pcm_lidar_desc;
+
+/* the reference's PCL struct of the type (velodyne_ros / rslidar_ros / ouster_ros / livox_ros ::Point, pointcloud_preprocess.h:12-88)
+ * and blind, scan_line, point_filter_num, time_scale of its config file (velodyne / ouster64 / rslidar / livox .yaml) */
+int pcm_lidar_default_desc(int type, pcm_lidar_desc *desc);
+/* points: n records in host or device memory; out: capacity_points 48-byte records in host or device memory (out_memory).  *n_out is
+ * the number of kept points; when it exceeds the capacity no record past the capacity is written and PCM_ERR_INVALID_ARGUMENT
+ * returns.  *given_offset_time (may be NULL): 0 when a Velodyne / RoboSense cloud took the yaw path, else 1.  n = 0 gives *n_out = 0.
+ * A ring >= num_scans on the yaw path, num_scans > PCM_LIDAR_MAX_SCANS, point_filter_num < 1 or a record too short for its
+ * offsets: PCM_ERR_INVALID_ARGUMENT. */
+int pcm_lidar_filter(pcm_ctx *ctx, const void *points, size_t n, int memory, const pcm_lidar_desc *desc, void *out, size_t capacity_points, int out_memory,
+                     size_t *n_out, int *given_offset_time);
+/* pcm_lio_frame_begin for a PointCloud2 cloud: the handler above -> stable sort by (curvature, input index) (the reference's
+ * std::sort by curvature, imu_processing.hpp:177-178, made definite) -> motion compensation (skipped when num_poses < 2) ->
+ * voxel-grid down-sampling (leaf_size 0: none, the sorted order stays) -> the SOURCE of this object.  The raw cloud is the only
+ * bulk upload.  pcm_obs_model and pcm_lio_frame_end follow as after pcm_lio_frame_begin. */
+int pcm_lio_frame_begin_cloud(pcm_ctx *ctx, const void *points, size_t n, int memory, const pcm_lidar_desc *desc, float leaf_size, const pcm_imu_pose *poses,
+                              int num_poses, const pcm_lio_state *end_state, size_t *n_scan);
+
 /* profiling flags: bit0 = bracket every residual launch with HIP events on the
  * launch stream (pcm_stats.linearize_ms); bit1 = collect the kNN candidate /
  * probe counters (slower kernel variant; use in an untimed pass); bit2 = in-kernel

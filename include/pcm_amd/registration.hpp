@@ -885,6 +885,62 @@ private:
   std::vector<std::vector<double>> camera_T_;
 };
 
+// jueying_lio's PointCloudPreprocess for sensor_msgs::PointCloud2 clouds (pointcloud_preprocess.cc: Velodyne, RoboSense, Ouster and
+// Livox-PointCloud2 handlers) on the device.  No ROS type enters: the callback hands msg->data.data(), the point count and, when the
+// driver's fields are not the reference's PCL struct, their offsets.
+//     pcm_amd::LidarPreprocess pre(PCM_LIDAR_RSLIDAR);              // lidar_type of the config; layout and config defaults
+//     pre.Blind() = blind; pre.NumScans() = scan_line; pre.PointFilterNum() = point_filter_num; pre.TimeScale() = time_scale;
+//     pre.Process(msg->data.data(), msg->width * msg->height, &cloud_out);   // 12 floats per kept point (pcl::PointXYZINormal)
+// or, over the pcm_ctx that registers the scan, the whole front end of a frame (pcm_lio_frame_begin_cloud):
+//     pcm_amd::LidarPreprocess pre(PCM_LIDAR_RSLIDAR, ctx);
+//     pre.FrameBegin(msg->data.data(), n, filter_size_surf, IMUpose.data(), IMUpose.size(), &end_state);
+class LidarPreprocess {
+public:
+  explicit LidarPreprocess(int lidar_type, int device = 0) : ctx_(pcm_create(device, nullptr)), own_(true) {
+    if (!ctx_) throw std::runtime_error("pcm_create failed");
+    init(lidar_type);
+  }
+  LidarPreprocess(int lidar_type, pcm_ctx* ctx) : ctx_(ctx), own_(false) { init(lidar_type); }
+  ~LidarPreprocess() { if (own_ && ctx_) pcm_destroy(ctx_); }
+  LidarPreprocess(const LidarPreprocess&) = delete;
+  LidarPreprocess& operator=(const LidarPreprocess&) = delete;
+
+  // PointCloudPreprocess's accessors (pointcloud_preprocess.h)
+  double& Blind() { return desc_.blind; }
+  int32_t& NumScans() { return desc_.num_scans; }
+  int32_t& PointFilterNum() { return desc_.point_filter_num; }
+  float& TimeScale() { return desc_.time_scale; }
+  pcm_lidar_desc& desc() { return desc_; }   // stride, offsets and kinds of a driver whose fields differ from the reference's struct
+  bool GivenOffsetTime() const { return given_ != 0; }
+
+  // the handler: `records` in host memory -> the kept points, 12 floats each, in input order; returns their number
+  size_t Process(const void* records, size_t n, std::vector<float>* cloud_out) {
+    cloud_out->resize(12 * (n ? n : 1));
+    size_t m = 0;
+    check(pcm_lidar_filter(ctx_, records, n, PCM_MEM_HOST, &desc_, cloud_out->data(), n ? n : 1, PCM_MEM_HOST, &m, &given_), "pcm_lidar_filter");
+    cloud_out->resize(12 * m);
+    return m;
+  }
+  // handler -> time sort -> motion compensation -> voxel grid -> source of the context; returns the scan's size
+  size_t FrameBegin(const void* records, size_t n, float leaf_size, const pcm_imu_pose* poses, int num_poses, const pcm_lio_state* end_state, int memory = PCM_MEM_HOST) {
+    size_t m = 0;
+    check(pcm_lio_frame_begin_cloud(ctx_, records, n, memory, &desc_, leaf_size, poses, num_poses, end_state, &m), "pcm_lio_frame_begin_cloud");
+    return m;
+  }
+
+private:
+  void init(int lidar_type) {
+    if (pcm_lidar_default_desc(lidar_type, &desc_) != PCM_OK) throw std::runtime_error("LidarPreprocess: unknown lidar type");
+  }
+  void check(int rc, const char* what) const {
+    if (rc != PCM_OK) throw std::runtime_error(std::string(what) + ": " + pcm_last_error(ctx_));
+  }
+  pcm_ctx* ctx_ = nullptr;
+  bool own_ = false;
+  pcm_lidar_desc desc_;
+  int given_ = 1;
+};
+
 }  // namespace pcm_amd
 
 // The call sites spell the pclomp enumerators unqualified inside namespace pclomp (jueying_slam/src/localization.cpp:169-186:

@@ -28,6 +28,7 @@ SYMBOLS = [
     "pcm_occ_default_params", "pcm_occ_reset", "pcm_occ_insert_scans", "pcm_occ_insert_keyframes", "pcm_occ_get_scan", "pcm_occ_status",
     "pcm_occ_info", "pcm_occ_get_map", "pcm_occ_get_pgm", "pcm_occ_get_counts",
     "pcm_scan_default_fuse_params", "pcm_scan_fuse", "pcm_scan_fused",
+    "pcm_lidar_default_desc", "pcm_lidar_filter", "pcm_lio_frame_begin_cloud",
 ]
 
 PCM_ABI_VERSION = 3   # include/pcm_amd.h
@@ -208,6 +209,18 @@ class PcmScanFuseResult(C.Structure):
                 ("status", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
+PCM_LIDAR_VELODYNE, PCM_LIDAR_OUSTER, PCM_LIDAR_RSLIDAR, PCM_LIDAR_LIVOX_STD = 2, 3, 4, 5   # the reference's LidarType values
+PCM_LIDAR_TIME_FLOAT, PCM_LIDAR_TIME_DOUBLE, PCM_LIDAR_TIME_UINT32 = 0, 1, 2
+PCM_LIDAR_RING_UINT8, PCM_LIDAR_RING_UINT16 = 0, 1
+PCM_LIDAR_MAX_SCANS = 256
+
+
+class PcmLidarDesc(C.Structure):
+    _fields_ = [("type", C.c_int32), ("time_kind", C.c_int32), ("ring_kind", C.c_int32), ("num_scans", C.c_int32), ("point_filter_num", C.c_int32),
+                ("time_scale", C.c_float), ("stride_bytes", C.c_size_t), ("xyz_offset_bytes", C.c_size_t), ("intensity_offset_bytes", C.c_size_t),
+                ("time_offset_bytes", C.c_size_t), ("ring_offset_bytes", C.c_size_t), ("blind", C.c_double), ("reserved", C.c_int32 * 8)]
+
+
 def library_path() -> str:
     """The in-tree build; PCM_AMD_LIBRARY names another build of the same ABI (A/B measurements of two builds on one box)."""
     return os.environ.get("PCM_AMD_LIBRARY") or os.path.join(_HERE, "libpcm_amd.so")
@@ -349,5 +362,8 @@ def load_library():
     L.pcm_scan_default_fuse_params.restype = None
     L.pcm_scan_fuse.argtypes = [vp, C.POINTER(PcmScanSegment), i32, C.POINTER(PcmScanFuseParams), vp, sz, i32, C.POINTER(PcmScanFuseResult)]
     L.pcm_scan_fused.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
+    L.pcm_lidar_default_desc.argtypes = [i32, C.POINTER(PcmLidarDesc)]
+    L.pcm_lidar_filter.argtypes = [vp, vp, sz, i32, C.POINTER(PcmLidarDesc), vp, sz, i32, C.POINTER(sz), C.POINTER(C.c_int)]
+    L.pcm_lio_frame_begin_cloud.argtypes = [vp, vp, sz, i32, C.POINTER(PcmLidarDesc), C.c_float, vp, i32, C.POINTER(PcmLioState), C.POINTER(sz)]
     _LIB = L
     return L

@@ -922,6 +922,75 @@ int pcm_lio_frame_begin(pcm_ctx* c, const void* custom_points, size_t n, int mem
   return PCM_OK;
 }
 
+// The same frame for a sensor_msgs::PointCloud2 cloud: the handler of its LiDAR type (pointcloud_preprocess.cc:89-305) in front, and
+// the time sort of ImuProcess::UndistortPcl (imu_processing.hpp:177-178) made definite: (curvature, input index).
+int pcm_lio_frame_begin_cloud(pcm_ctx* c, const void* points, size_t n, int memory, const pcm_lidar_desc* desc, float leaf_size, const pcm_imu_pose* poses, int npose,
+                              const pcm_lio_state* end_state, size_t* n_scan) {
+  CHECK_CTX(c);
+  if (!n_scan || (npose >= 2 && (!poses || !end_state))) return PCM_ERR_INVALID_ARGUMENT;
+  *n_scan = 0;
+  int rc = lidar_check_cloud(c, points, n, memory, desc);
+  if (rc != PCM_OK) return rc;
+  if (!(leaf_size >= 0.f)) { c->err = "leaf_size must be >= 0"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (n == 0) { c->err = "empty frame"; return PCM_ERR_NO_INPUT; }
+  PCM_HIPCK(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  // frame arena: [raw cloud | filtered records, later the down-sampled ones | time-sorted records | IMU poses | scratch of the operators]
+  const size_t o_raw = 0, o_flt = o_raw + (memory == PCM_MEM_HOST ? up256(n * desc->stride_bytes) : 0), o_srt = o_flt + up256(n * 48), o_pose = o_srt + up256(n * 48);
+  const size_t o_scr = o_pose + up256(sizeof(pcm_imu_pose) * (size_t)std::max(npose, 1));
+  rc = pre_scratch(c, o_scr + std::max({lidar_filter_scratch_bytes(n), lidar_time_sort_scratch_bytes(n), voxel_downsample_scratch_bytes(n)}));
+  if (rc != PCM_OK) return rc;
+  char* A = c->pre_arena;
+  const void* d_raw = points;
+  int hint = -1;
+  if (memory == PCM_MEM_HOST) {
+    PCM_HIPCK(c, hipMemcpyAsync(A + o_raw, points, n * desc->stride_bytes, hipMemcpyHostToDevice, st));
+    d_raw = A + o_raw;
+    hint = lidar_given_on_host(points, n, *desc);
+  }
+  // 1. the handler: kept points in input order
+  size_t n_flt = 0;
+  int given = 1;
+  rc = lidar_filter_device(st, d_raw, n, *desc, hint, A + o_flt, n, &n_flt, &given, A + o_scr, &c->err);
+  if (rc != PCM_OK) return rc;
+  if (n_flt == 0) { c->err = "no point of the frame passed the handler"; return PCM_ERR_NO_INPUT; }
+  // 2. sort by time; the radix sort is stable, so equal stamps keep their input order
+  rc = lidar_time_sort_device(st, A + o_flt, n_flt, A + o_srt, A + o_scr, &c->err);
+  if (rc != PCM_OK) return rc;
+  // 3. ImuProcess::UndistortPcl backward loop, in place on the sorted records
+  if (npose >= 2) {
+    LioStateD s;
+    for (int a = 0; a < 4; a++) { s.rot[a] = end_state->rot[a]; s.off_R[a] = end_state->off_R[a]; }
+    for (int a = 0; a < 3; a++) { s.pos[a] = end_state->pos[a]; s.off_T[a] = end_state->off_T[a]; }
+    PCM_HIPCK(c, hipMemcpyAsync(A + o_pose, poses, sizeof(pcm_imu_pose) * (size_t)npose, hipMemcpyHostToDevice, st));
+    rc = undistort_device(st, A + o_srt, n_flt, 48, 36, reinterpret_cast<const pcm_imu_pose*>(A + o_pose), npose, s, &c->err);
+    if (rc != PCM_OK) return rc;
+  }
+  // 4. voxel_scan_.filter(); leaf 0 = the sorted scan as it is.  The filtered records are free again: the centroids go there.
+  const char* d_scan = A + o_srt;
+  size_t n_ds = n_flt;
+  if (leaf_size > 0.f) {
+    rc = voxel_downsample_device(st, A + o_srt, n_flt, 48, leaf_size, reinterpret_cast<float*>(A + o_flt), &n_ds, A + o_scr, &c->err);
+    if (rc != PCM_OK) return rc;
+    d_scan = A + o_flt;
+  }
+  if (n_ds == 0) { c->err = "empty scan after down-sampling"; return PCM_ERR_NO_INPUT; }
+  // 5. the scan becomes the source of this object: device -> device
+  if (c->cfg.flags & PCM_FLAG_LIO_REFERENCE_SEMANTICS) {
+    rc = lio_members_resize(c, n_ds);
+    if (rc != PCM_OK) return rc;
+  }
+  rc = set_cloud(c, &c->src, d_scan, n_ds, 48, PCM_MEM_DEVICE, 0, false);
+  if (rc != PCM_OK) return rc;
+  c->src_sorted = false;
+  c->lio_planes_valid = false;
+  c->srcmap.valid = false;
+  c->src_cov_valid = false;
+  c->user_cov[0].clear();
+  *n_scan = n_ds;
+  return PCM_OK;
+}
+
 int pcm_lio_frame_end(pcm_ctx* c, const pcm_lio_state* s, float filter_size_map, int ekf_inited, size_t* num_added) { return pcm_map_incremental(c, s, filter_size_map, ekf_inited, num_added); }
 
 int pcm_get_source(pcm_ctx* c, float* out_xyz, size_t capacity_points, size_t* n) {

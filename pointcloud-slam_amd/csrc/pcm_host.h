@@ -88,6 +88,14 @@ size_t voxel_downsample_scratch_bytes(size_t n);
 size_t livox_filter_scratch_bytes(size_t n);
 int livox_filter_device(hipStream_t stream, const void* d_msg, size_t n, int num_scans, int point_filter_num, double blind, void* d_out, size_t* n_out, void* scratch, std::string* err);
 int voxel_downsample_device(hipStream_t stream, const void* d_in, size_t n, size_t stride, float leaf, float* d_out, size_t* n_out, void* scratch, std::string* err);
+// lidar_handlers.hip: the PointCloud2 handlers (the descriptor has passed lidar_check_cloud; n >= 1) and the stable time sort
+size_t lidar_filter_scratch_bytes(size_t n);
+int lidar_check_cloud(pcm_ctx* c, const void* points, size_t n, int memory, const pcm_lidar_desc* desc);
+int lidar_given_on_host(const void* points, size_t n, const pcm_lidar_desc& D);
+int lidar_filter_device(hipStream_t stream, const void* d_pts, size_t n, const pcm_lidar_desc& D, int given_hint, void* d_out, size_t capacity, size_t* n_out, int* given_out,
+                        void* scratch, std::string* err);
+size_t lidar_time_sort_scratch_bytes(size_t m);
+int lidar_time_sort_device(hipStream_t stream, const void* d_in, size_t m, void* d_out, void* scratch, std::string* err);
 // gicp_bfgs.hip
 constexpr int kGicpBfgsMaxBlocks = 512;   // rows of the partial-sum table
 size_t gicp_bfgs_scratch_bytes(size_t m);

@@ -1454,3 +1454,69 @@ for _cls in (Registration, LoamRegistration, OccupancyMap2D):
     _cls.fuse_scans = _fuse_scans
     _cls.fused_scan = _fused_scan
 LoamRegistration.frame_begin_fused = _loam_frame_begin_fused
+
+
+# ---- PointCloud2 handlers of jueying_lio's PointCloudPreprocess (pcm_lidar_filter) -----------------------------
+LIDAR_TYPE = {"velodyne": capi.PCM_LIDAR_VELODYNE, "ouster": capi.PCM_LIDAR_OUSTER, "rslidar": capi.PCM_LIDAR_RSLIDAR, "livox": capi.PCM_LIDAR_LIVOX_STD}
+LIDAR_TIME_KIND = {"f32": capi.PCM_LIDAR_TIME_FLOAT, "f64": capi.PCM_LIDAR_TIME_DOUBLE, "u32": capi.PCM_LIDAR_TIME_UINT32}
+LIDAR_RING_KIND = {"u8": capi.PCM_LIDAR_RING_UINT8, "u16": capi.PCM_LIDAR_RING_UINT16}
+NORMAL_STRIDE = 48   # pcl::PointXYZINormal
+
+
+def lidar_desc(type, **overrides) -> capi.PcmLidarDesc:
+    """The reference's PCL struct layout and config values of a LiDAR type ("velodyne" | "ouster" | "rslidar" | "livox", or the
+    reference's LidarType number), with any field of pcm_lidar_desc overridden (time_kind / ring_kind also by name: "f32" "f64" "u32",
+    "u8" "u16")."""
+    d = capi.PcmLidarDesc()
+    capi.load_library().pcm_lidar_default_desc(LIDAR_TYPE.get(type, type) if isinstance(type, str) else int(type), C.byref(d))
+    for k, v in overrides.items():
+        if k == "time_kind" and isinstance(v, str):
+            v = LIDAR_TIME_KIND[v]
+        if k == "ring_kind" and isinstance(v, str):
+            v = LIDAR_RING_KIND[v]
+        if k == "reserved" or not hasattr(d, k):
+            raise KeyError(k)
+        setattr(d, k, v)
+    return d
+
+
+def _lidar_filter(self, points, desc, out=None):
+    """The handler of desc.type on n records of desc.stride_bytes (a host array or a device tensor): -> ((m, 12) float32
+    pcl::PointXYZINormal records in input order, given_offset_time).  out: a device tensor of at least n x 48 bytes to fill instead
+    (-> (m, given_offset_time))."""
+    ptr, n, mem, keep = _scan_arg(points, desc.stride_bytes)
+    m, given = C.c_size_t(), C.c_int()
+    if out is None:
+        ret = np.zeros((max(n, 1), 12), np.float32)
+        rc = self._L.pcm_lidar_filter(self._h, ptr, n, mem, C.byref(desc), ret.ctypes.data, n, capi.MEM_HOST, C.byref(m), C.byref(given))
+    else:
+        optr, cap, omem, okeep = _scan_arg(out, NORMAL_STRIDE)
+        rc = self._L.pcm_lidar_filter(self._h, ptr, n, mem, C.byref(desc), optr, cap, omem, C.byref(m), C.byref(given))
+    del keep
+    self._check(rc)
+    return (ret[:m.value].copy() if out is None else m.value), bool(given.value)
+
+
+def _lio_frame_begin_cloud(self, points, desc, poses=None, rot_xyzw=(0, 0, 0, 1.0), pos=(0, 0, 0), off_R_xyzw=(0, 0, 0, 1.0), off_T=(0, 0, 0),
+                           leaf_size: float = 0.5) -> int:
+    """lio_frame_begin for a sensor_msgs::PointCloud2 cloud (pcm_lio_frame_begin_cloud): the records of msg.data (a host array or a
+    device tensor) -> handler of desc.type -> stable sort by time -> motion compensation (poses: (K,22) Pose6D rows, None = none) ->
+    voxel-grid down-sampling -> source of this object.  Returns the number of scan points."""
+    ptr, n, mem, keep = _scan_arg(points, desc.stride_bytes)
+    st = capi.PcmLioState()
+    st.rot[:] = list(map(float, rot_xyzw)); st.pos[:] = list(map(float, pos)); st.off_R[:] = list(map(float, off_R_xyzw)); st.off_T[:] = list(map(float, off_T))
+    pp, npose = None, 0
+    if poses is not None:
+        pa = np.ascontiguousarray(poses, dtype=np.float64)
+        assert pa.ndim == 2 and pa.shape[1] == 22
+        pp, npose = pa.ctypes.data, pa.shape[0]
+    m = C.c_size_t()
+    rc = self._L.pcm_lio_frame_begin_cloud(self._h, ptr, n, mem, C.byref(desc), C.c_float(leaf_size), C.c_void_p(pp), int(npose), C.byref(st), C.byref(m))
+    del keep
+    self._check(rc)
+    return m.value
+
+
+for _cls in (Registration, LoamRegistration, OccupancyMap2D):
+    _cls.lidar_filter = _lidar_filter
+Registration.lio_frame_begin_cloud = _lio_frame_begin_cloud
