@@ -362,7 +362,9 @@ int pcm_gicp_bfgs_get_correspondences(pcm_ctx *ctx, int32_t *idx_src, int32_t *i
  *                         this object; *n_scan = its size.  The reference sorts the scan by time before compensating it
  *                         (imu_processing.hpp:177-178); the message order is kept here (a point's compensation depends on its own
  *                         stamp only and a Livox message is time-ordered).
- *   pcm_obs_model x k     the IEKF of the caller between the calls (esekfom.hpp:1685-1735), as before
+ *   pcm_lio_update        the whole iterated Kalman update (esekfom.hpp:1526-1834) on the device: k ObsModel calls and the 23 x 23
+ *                         algebra between them behind one synchronisation -- or pcm_obs_model x k with the caller's own filter
+ *                         between the calls, as before
  *   pcm_lio_frame_end     = pcm_map_incremental with the updated state: add-filter + AddPoints, the map stays on the device
  * Target = the map (pcm_set_target once, then it slides by itself). */
 typedef struct pcm_lio_frame_params {
@@ -377,6 +379,42 @@ int pcm_lio_frame_begin(pcm_ctx *ctx, const void *custom_points, size_t n, int m
 int pcm_lio_frame_end(pcm_ctx *ctx, const pcm_lio_state *state, float filter_size_map, int ekf_inited, size_t *num_added);
 /* the current source scan, x y z per point in its stored order (tests: the scan pcm_lio_frame_begin produced); out may be NULL */
 int pcm_get_source(pcm_ctx *ctx, float *out_xyz, size_t capacity_points, size_t *n);
+
+/* esekf::update_iterated_dyn_share_modified of jueying_lio (IKFoM_toolkit/esekfom/esekfom.hpp:1526-1834, called at
+ * laser_mapping.cc:347) for state_ikfom, on the device: every ObsModel call of the loop, the manifold algebra (SO3 / S2 boxplus and
+ * boxminus, A_matrix, S2_Nx_yy, S2_Mx), the two 23 x 23 inverses per iteration and the closing covariance re-projection.  One call per
+ * frame between pcm_lio_frame_begin and pcm_lio_frame_end (or after pcm_set_source); the context requirements are those of
+ * pcm_obs_model (P2PLANE, source and target set).  One upload (state, P, parameters), max_iter + 1 rounds of kernels queued up front,
+ * one download, one stream synchronisation; a round after the loop's exit returns at once.  The gain is the information form
+ * (esekfom.hpp:1685-1713) for every n_eff >= 1: the dense form the reference takes for fewer than 23 effective points needs the rows
+ * of h_x (equal in exact arithmetic).  DESIGN.md section 17. */
+typedef struct pcm_lio_filter_state {   /* state_ikfom, use-ikfom.hpp:14-15; DOF 23 in this order; quaternions x, y, z, w */
+  double pos[3], rot[4], off_R[4], off_T[3], vel[3], bg[3], ba[3], grav[3];
+} pcm_lio_filter_state;
+typedef struct pcm_lio_update_params {
+  double R;                  /* 0.001  options.h:12 LASER_POINT_COV */
+  int32_t max_iter;          /* 4      laser_mapping.cc:89 (livox.yaml: 3-4); 1 .. 15 */
+  int32_t extrinsic_est_en;
+  double limit[23];          /* 0.001 each, laser_mapping.cc:19 */
+  int32_t reserved[8];
+} pcm_lio_update_params;
+typedef struct pcm_lio_update_result {
+  int32_t iterations;        /* ObsModel calls made (<= max_iter + 1) */
+  int32_t rematches;         /* of those, with converge = true */
+  int32_t valid_calls;       /* calls with n_eff >= 1 */
+  int32_t t;                 /* the loop's converge counter at exit */
+  int32_t n_eff_last;
+  int32_t status;            /* PCM_OK, or PCM_ERR_INTERNAL when the updated state or covariance is not finite */
+  double sum_h2_last;
+  int32_t reserved[8];
+} pcm_lio_update_result;
+void pcm_lio_default_update_params(pcm_lio_update_params *params);
+/* x: in the propagated state x_, out the updated one; P: 23 x 23 row-major, in P_ propagated, out updated (as the reference leaves its
+ * member: untouched when no call was valid) */
+int pcm_lio_update(pcm_ctx *ctx, const pcm_lio_update_params *params, pcm_lio_filter_state *x, double *P, pcm_lio_update_result *result);
+/* parity hook: ObsModel call `call` (0-based) of the last pcm_lio_update -- the state it was evaluated at, its converge flag, n_eff,
+ * HTH upper triangle (78) + HTh (12), and dx_ (23; zeros for an invalid call).  Any pointer may be NULL. */
+int pcm_lio_update_trace(pcm_ctx *ctx, int call, pcm_lio_filter_state *x, int32_t *converge, int32_t *n_eff, double *sums90, double *dx23);
 
 /* Batch of independent registration objects on one device (BASELINE config 3:
  * independent scan/submap pairs): all GN/LM loops advance in lock-step kernel

@@ -941,6 +941,36 @@ private:
   int given_ = 1;
 };
 
+// jueying_lio's iterated Kalman update over the pcm_ctx that holds the frame's scan and the map (pcm_lio_update): the replacement of
+// kf_.update_iterated_dyn_share_modified(options::LASER_POINT_COV, solve_H_time)  (laser_mapping.cc:347).
+//     pcm_amd::LioFilter kf(ctx);                       // R 0.001, max_iter 4, limit 0.001 (options.h:12, laser_mapping.cc:19,89)
+//     kf.ExtrinsicEstEn() = extrinsic_est_en_;
+//     kf.Update(&x, P_row_major);                       // x: propagated -> updated state_ikfom, P: 23 x 23 row-major in / out
+class LioFilter {
+public:
+  explicit LioFilter(pcm_ctx* ctx) : ctx_(ctx) { pcm_lio_default_update_params(&params_); }
+  double& R() { return params_.R; }
+  int32_t& MaxIter() { return params_.max_iter; }
+  int32_t& ExtrinsicEstEn() { return params_.extrinsic_est_en; }
+  double* Limit() { return params_.limit; }
+  // update_iterated_dyn_share_modified: every ObsModel call and the filter algebra on the device, one synchronisation
+  const pcm_lio_update_result& Update(pcm_lio_filter_state* x, double* P) {
+    const int rc = pcm_lio_update(ctx_, &params_, x, P, &last_);
+    if (rc != PCM_OK) throw std::runtime_error(std::string("pcm_lio_update: ") + pcm_last_error(ctx_));
+    return last_;
+  }
+  const pcm_lio_update_result& last() const { return last_; }
+  // the state ObsModel call `call` of the last update was evaluated at, its converge flag and n_eff
+  bool Trace(int call, pcm_lio_filter_state* x, int32_t* converge, int32_t* n_eff, double* dx23 = nullptr) const {
+    return pcm_lio_update_trace(ctx_, call, x, converge, n_eff, nullptr, dx23) == PCM_OK;
+  }
+
+private:
+  pcm_ctx* ctx_ = nullptr;
+  pcm_lio_update_params params_;
+  pcm_lio_update_result last_{};
+};
+
 }  // namespace pcm_amd
 
 // The call sites spell the pclomp enumerators unqualified inside namespace pclomp (jueying_slam/src/localization.cpp:169-186:

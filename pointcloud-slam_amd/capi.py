@@ -29,6 +29,7 @@ SYMBOLS = [
     "pcm_occ_info", "pcm_occ_get_map", "pcm_occ_get_pgm", "pcm_occ_get_counts",
     "pcm_scan_default_fuse_params", "pcm_scan_fuse", "pcm_scan_fused",
     "pcm_lidar_default_desc", "pcm_lidar_filter", "pcm_lio_frame_begin_cloud",
+    "pcm_lio_default_update_params", "pcm_lio_update", "pcm_lio_update_trace",
 ]
 
 PCM_ABI_VERSION = 3   # include/pcm_amd.h
@@ -81,6 +82,20 @@ class PcmLioState(C.Structure):
 
 class PcmObsResult(C.Structure):
     _fields_ = [("HTH", C.c_double * 144), ("HTh", C.c_double * 12), ("sum_h2", C.c_double), ("n_eff", C.c_int32), ("valid", C.c_int32)]
+
+
+class PcmLioFilterState(C.Structure):   # state_ikfom, DOF 23 in this order
+    _fields_ = [("pos", C.c_double * 3), ("rot", C.c_double * 4), ("off_R", C.c_double * 4), ("off_T", C.c_double * 3), ("vel", C.c_double * 3),
+                ("bg", C.c_double * 3), ("ba", C.c_double * 3), ("grav", C.c_double * 3)]
+
+
+class PcmLioUpdateParams(C.Structure):
+    _fields_ = [("R", C.c_double), ("max_iter", C.c_int32), ("extrinsic_est_en", C.c_int32), ("limit", C.c_double * 23), ("reserved", C.c_int32 * 8)]
+
+
+class PcmLioUpdateResult(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("rematches", C.c_int32), ("valid_calls", C.c_int32), ("t", C.c_int32), ("n_eff_last", C.c_int32),
+                ("status", C.c_int32), ("sum_h2_last", C.c_double), ("reserved", C.c_int32 * 8)]
 
 
 class PcmLioFrameParams(C.Structure):
@@ -365,5 +380,9 @@ def load_library():
     L.pcm_lidar_default_desc.argtypes = [i32, C.POINTER(PcmLidarDesc)]
     L.pcm_lidar_filter.argtypes = [vp, vp, sz, i32, C.POINTER(PcmLidarDesc), vp, sz, i32, C.POINTER(sz), C.POINTER(C.c_int)]
     L.pcm_lio_frame_begin_cloud.argtypes = [vp, vp, sz, i32, C.POINTER(PcmLidarDesc), C.c_float, vp, i32, C.POINTER(PcmLioState), C.POINTER(sz)]
+    L.pcm_lio_default_update_params.argtypes = [C.POINTER(PcmLioUpdateParams)]
+    L.pcm_lio_default_update_params.restype = None
+    L.pcm_lio_update.argtypes = [vp, C.POINTER(PcmLioUpdateParams), C.POINTER(PcmLioFilterState), vp, C.POINTER(PcmLioUpdateResult)]
+    L.pcm_lio_update_trace.argtypes = [vp, i32, C.POINTER(PcmLioFilterState), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp]
     _LIB = L
     return L

@@ -244,7 +244,7 @@ constexpr uint16_t kNoCell = 0xffffu;
     t_prev = t_now;                                                            \
   }
 
-template <bool STATS, bool TIMING, bool WRITE_PLANES, bool LIO, bool FUSED = false>
+template <bool STATS, bool TIMING, bool WRITE_PLANES, bool LIO, bool FUSED = false, bool LIO_DEV = false>
 __global__ void __launch_bounds__(256, 5) k_linearize(const PairDesc* __restrict__ descs, const PairState* __restrict__ states, KernelParams kp,
                                                       unsigned long long* __restrict__ stats, LsqParams lp = LsqParams{}, unsigned char* __restrict__ flags_row = nullptr) {
   // XCD-aware placement, balanced: workgroups are dealt round-robin over the 8 XCDs (each with its own L2).  Inside every run of 64
@@ -271,7 +271,8 @@ __global__ void __launch_bounds__(256, 5) k_linearize(const PairDesc* __restrict
   const bool live = i < d.src.num_points;
   const PoseF P = load_pose(states[pair].x0);
   const TargetView tg = d.tgt;
-  const bool do_search = !LIO || kp.lio_rematch != 0;   // LIO with converge == false re-uses the stored planes (laser_mapping.cc:616)
+  // LIO with converge == false re-uses the stored planes (laser_mapping.cc:616); LIO_DEV: the flag k_iekf_step left in the descriptor
+  const bool do_search = !LIO || (LIO_DEV ? d.lio.rematch != 0 : kp.lio_rematch != 0);
 
   __shared__ int s_red[4][6];
   __shared__ int s_box[8];                 // origin xyz, dims xyz, ncell, dense flag
@@ -795,6 +796,13 @@ void launch_linearize(hipStream_t stream, const PairDesc* d_descs, const PairSta
 void launch_lio_obs(hipStream_t stream, const PairDesc* d_descs, const PairState* d_states, const KernelParams& kp) {
   dim3 grid((unsigned)kp.tiles_per_pair, 1u);
   k_linearize<false, false, true, true><<<grid, 256, 0, stream>>>(d_descs, d_states, kp, nullptr);
+}
+
+// the same for a round of pcm_lio_update: the pose and the converge flag are the ones the step kernel of the round before wrote into
+// the descriptor, and a round queued behind the loop's exit (state MODE_DONE) returns at once
+void launch_lio_obs_dev(hipStream_t stream, const PairDesc* d_descs, const PairState* d_states, const KernelParams& kp) {
+  dim3 grid((unsigned)kp.tiles_per_pair, 1u);
+  k_linearize<false, false, true, true, false, true><<<grid, 256, 0, stream>>>(d_descs, d_states, kp, nullptr);
 }
 
 // fixed-order sum of the LIO partial rows -> 96 doubles (78 HTH, 12 HTh, sum h^2, count)

@@ -789,6 +789,136 @@ int pcm_obs_model(pcm_ctx* c, const pcm_lio_state* s, int extrinsic_est_en, int 
   return PCM_OK;
 }
 
+void pcm_lio_default_update_params(pcm_lio_update_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->R = 0.001;        // options.h:12 LASER_POINT_COV
+  p->max_iter = 4;     // laser_mapping.cc:89
+  for (int k = 0; k < 23; k++) p->limit[k] = 0.001;   // laser_mapping.cc:19
+}
+
+// esekf::update_iterated_dyn_share_modified on the device (lio_iekf.h, lio_iekf.hip): the rounds are queued up front, the host waits once
+int pcm_lio_update(pcm_ctx* c, const pcm_lio_update_params* prm, pcm_lio_filter_state* x, double* P, pcm_lio_update_result* res) {
+  CHECK_CTX(c);
+  if (!prm || !x || !P || !res) { c->err = "pcm_lio_update: null argument"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (c->cfg.model != PCM_MODEL_P2PLANE) { c->err = "pcm_lio_update needs the P2PLANE model"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (prm->max_iter < 1 || prm->max_iter + 1 > iekf::kMaxCalls) { c->err = "pcm_lio_update: max_iter must be in 1 .. 15"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!(prm->R > 0.0) || !std::isfinite(prm->R)) { c->err = "pcm_lio_update: R must be positive and finite"; return PCM_ERR_INVALID_ARGUMENT; }
+  for (int k = 0; k < iekf::N; k++)
+    if (!(prm->limit[k] >= 0.0)) { c->err = "pcm_lio_update: limit must not be negative or NaN"; return PCM_ERR_INVALID_ARGUMENT; }
+  for (int k = 0; k < iekf::NN; k++)
+    if (!std::isfinite(P[k])) { c->err = "pcm_lio_update: P is not finite"; return PCM_ERR_INVALID_ARGUMENT; }
+  {
+    const double* xs = reinterpret_cast<const double*>(x);
+    for (size_t k = 0; k < sizeof(*x) / sizeof(double); k++)
+      if (!std::isfinite(xs[k])) { c->err = "pcm_lio_update: the state is not finite"; return PCM_ERR_INVALID_ARGUMENT; }
+  }
+  int rc = validate_config(c, c->cfg);
+  if (rc != PCM_OK) return rc;
+  rc = prepare(c);
+  if (rc != PCM_OK) return rc;
+  const uint32_t n = (uint32_t)c->src.n;
+  const int tiles = (int)((n + 255u) / 256u);
+  Workspace* w = nullptr;
+  rc = ensure_ws(c, &w, 1, (size_t)tiles * kLioStride, 2);
+  if (rc != PCM_OK) return rc;
+  rc = c->lio_upd.reserve(c, sizeof(LioUpdateRecord), sizeof(LioUpdateRecord));
+  if (rc != PCM_OK) return rc;
+  rc = c->lio_upd_host.reserve(c, sizeof(LioUpdateRecord), sizeof(LioUpdateRecord));
+  if (rc != PCM_OK) return rc;
+  c->lio_upd_calls = 0;
+  LioUpdateRecord* h = reinterpret_cast<LioUpdateRecord*>(c->lio_upd_host.p);
+  LioUpdateRecord* dv = reinterpret_cast<LioUpdateRecord*>(c->lio_upd.p);
+  std::memcpy(&h->b.x_prop, x, sizeof(iekf::State));
+  std::memcpy(h->b.P_prop, P, sizeof(double) * iekf::NN);
+  h->b.prm.R = prm->R;
+  h->b.prm.max_iter = prm->max_iter;
+  h->b.prm.extrinsic = prm->extrinsic_est_en ? 1 : 0;
+  for (int k = 0; k < iekf::N; k++) h->b.prm.limit[k] = prm->limit[k];
+  iekf::begin(h->b);
+  iekf::PoseF L0{};
+  iekf::pose_of(h->b.x, &L0);
+  L0.rematch = 1;   // dyn_share.converge = true  esekfom.hpp:1529
+  hipStream_t st = c->stream;
+  if (c->cfg.sort_source && !c->src_sorted) {   // new scan: order it along the world grid at the propagated state's pose (as pcm_obs_model)
+    double qwl[4], Rwl[9];
+    quat_mul_d(x->rot, x->off_R, qwl);
+    quat_to_rot_d(qwl, Rwl);
+    float g[16] = {(float)Rwl[0], (float)Rwl[1], (float)Rwl[2], L0.t_wl[0], (float)Rwl[3], (float)Rwl[4], (float)Rwl[5], L0.t_wl[1],
+                   (float)Rwl[6], (float)Rwl[7], (float)Rwl[8], L0.t_wl[2], 0.f, 0.f, 0.f, 1.f};
+    SortJob j{c->src.d_pts, c->src_order, n, 0, 0, 0};
+    PCM_HIPCK(c, hipMemcpyAsync(w->d_guesses, g, sizeof(g), hipMemcpyHostToDevice, st));
+    PCM_HIPCK(c, hipMemcpyAsync(w->d_jobs, &j, sizeof(j), hipMemcpyHostToDevice, st));
+    rc = sort_sources_batched(st, w->d_jobs, 1, n, n, w->d_guesses, c->cfg.voxel_resolution, &w->sort, &c->err);
+    if (rc != PCM_OK) return rc;
+    c->src_sorted = true;
+  }
+  c->lio_planes_valid = false;
+  const bool ref = (c->cfg.flags & PCM_FLAG_LIO_REFERENCE_SEMANTICS) != 0;
+  if (ref) {
+    rc = lio_members_resize(c, n);
+    if (rc != PCM_OK) return rc;
+  }
+  Geom geom = pick_geom(n, 1);
+  KernelParams kp = kernel_params(c->cfg, geom);
+  kp.lio_rematch = 1;   // not read by the device-flag instance
+  kp.lio_extrinsic = prm->extrinsic_est_en ? 1 : 0;
+  kp.lio_ref = !ref ? 0 : ((c->cfg.sort_source && c->src_sorted) ? 2 : 1);
+  fill_desc(c, &h->desc, w->d_partials);
+  std::memcpy(&h->desc.lio, &L0, sizeof(L0));
+  h->desc.lio_aux = c->lio_aux;
+  const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  init_state(h->ps, ident);
+  const int rounds = prm->max_iter + 1;
+  PCM_HIPCK(c, hipMemcpyAsync(dv, h, offsetof(LioUpdateRecord, b) + offsetof(iekf::Block, tr), hipMemcpyHostToDevice, st));
+  for (int r = 0; r < rounds; r++) {
+    launch_lio_obs_dev(st, &dv->desc, &dv->ps, kp);
+    launch_lio_finish_gated(st, dv, w->d_partials, tiles, w->d_sums);
+    launch_iekf_step(st, dv, w->d_sums);
+  }
+  PCM_HIPCK(c, hipGetLastError());
+  const size_t back0 = offsetof(LioUpdateRecord, b) + offsetof(iekf::Block, x);
+  const size_t back1 = offsetof(LioUpdateRecord, b) + offsetof(iekf::Block, tr) + sizeof(iekf::Trace) * (size_t)rounds;
+  PCM_HIPCK(c, hipMemcpyAsync(reinterpret_cast<char*>(h) + back0, reinterpret_cast<const char*>(dv) + back0, back1 - back0, hipMemcpyDeviceToHost, st));
+  PCM_HIPCK(c, hipStreamSynchronize(st));
+  const iekf::Ctl& ctl = h->b.ctl;
+  c->lio_planes_valid = true;   // the first call of the loop always matches
+  c->lio_upd_calls = ctl.iterations;
+  std::memcpy(x, &h->b.x, sizeof(iekf::State));
+  std::memcpy(P, h->b.P, sizeof(double) * iekf::NN);
+  std::memset(res, 0, sizeof(*res));
+  res->iterations = ctl.iterations;
+  res->rematches = ctl.rematches;
+  res->valid_calls = ctl.valid_calls;
+  res->t = ctl.t;
+  res->n_eff_last = ctl.n_eff_last;
+  res->sum_h2_last = ctl.sum_h2_last;
+  res->status = PCM_OK;
+  c->stats.linearize_launches += (uint64_t)ctl.iterations;
+  c->stats.point_passes += (uint64_t)n * (uint64_t)ctl.iterations;
+  bool finite = true;
+  for (int k = 0; k < iekf::NN; k++) finite = finite && std::isfinite(P[k]);
+  for (size_t k = 0; k < sizeof(*x) / sizeof(double); k++) finite = finite && std::isfinite(reinterpret_cast<const double*>(x)[k]);
+  if (!finite || !ctl.done) {
+    c->err = !ctl.done ? "pcm_lio_update: the loop did not reach its end" : "pcm_lio_update: the updated state or covariance is not finite";
+    res->status = PCM_ERR_INTERNAL;
+    return PCM_ERR_INTERNAL;
+  }
+  return PCM_OK;
+}
+
+int pcm_lio_update_trace(pcm_ctx* c, int call, pcm_lio_filter_state* x, int32_t* converge, int32_t* n_eff, double* sums90, double* dx23) {
+  CHECK_CTX(c);
+  if (call < 0 || call >= c->lio_upd_calls || !c->lio_upd_host.p) { c->err = "pcm_lio_update_trace: no such call of the last pcm_lio_update"; return PCM_ERR_INVALID_ARGUMENT; }
+  const iekf::Trace& t = reinterpret_cast<const LioUpdateRecord*>(c->lio_upd_host.p)->b.tr[call];
+  if (x) std::memcpy(x, &t.x, sizeof(iekf::State));
+  if (converge) *converge = t.converge;
+  if (n_eff) *n_eff = t.n_eff;
+  if (sums90) std::memcpy(sums90, t.sums, sizeof(t.sums));
+  if (dx23) std::memcpy(dx23, t.dx, sizeof(t.dx));
+  return PCM_OK;
+}
+
 namespace {
 // grow the target point log to hold `need` points (keeps the content)
 int reserve_target(pcm_ctx* c, size_t need) {

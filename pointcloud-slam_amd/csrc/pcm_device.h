@@ -196,7 +196,8 @@ struct LioPose {
   float off_t[3];    // s.offset_T_L_I
   float off_R[9];    // s.offset_R_L_I.toRotationMatrix()      (row-major)
   float Rt[9];       // s.rot.toRotationMatrix().transpose()
-  float pad[2];
+  int32_t rematch;   // pcm_lio_update rounds only: ekfom_data.converge of the call, written by k_iekf_step (lio_iekf.hip)
+  int32_t pad;
 };
 
 // per-pair descriptor read by the residual kernels

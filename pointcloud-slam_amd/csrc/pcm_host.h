@@ -9,6 +9,7 @@
 
 #include "../../include/pcm_amd.h"
 #include "dev_buf.h"
+#include "lio_iekf.h"
 #include "lsq_step.h"
 #include "pcm_device.h"
 
@@ -139,6 +140,15 @@ void launch_linearize_reforder(hipStream_t stream, const PairDesc* d_descs, cons
 void launch_linearize_fused(hipStream_t stream, const PairDesc* d_descs, PairState* d_states, const KernelParams& kp, const LsqParams& lp, int npairs, unsigned char* d_flags_row);
 void launch_lio_obs(hipStream_t stream, const PairDesc* d_descs, const PairState* d_states, const KernelParams& kp);
 void launch_lio_finish(hipStream_t stream, const double* d_partials, int nblocks, double* d_out);
+// pcm_lio_update (lio_iekf.hip): a round = launch_lio_obs_dev + launch_lio_finish_gated + launch_iekf_step on the record `blk`
+void launch_lio_obs_dev(hipStream_t stream, const PairDesc* d_descs, const PairState* d_states, const KernelParams& kp);
+struct LioUpdateRecord {   // device-resident for the whole update; the host image is uploaded up to b.tr and read back from b.x on
+  PairDesc desc;           // desc.lio: the float pose + converge flag of the next ObsModel call
+  PairState ps;            // mode: MODE_LINEARIZE while the loop runs, MODE_DONE after its exit
+  iekf::Block b;
+};
+void launch_lio_finish_gated(hipStream_t stream, const LioUpdateRecord* rec, const double* d_partials, int nblocks, double* d_out);
+void launch_iekf_step(hipStream_t stream, LioUpdateRecord* rec, const double* d_sums);
 void launch_lio_members_init(hipStream_t stream, float2* aux, uint32_t first, uint32_t last);   // entries [first, last) = (residual 0, selected)
 void launch_trial(hipStream_t stream, const PairDesc* d_descs, const PairState* d_states, const KernelParams& kp, int npairs);
 void launch_finish_round(hipStream_t stream, const PairDesc* d_descs, PairState* d_states, const KernelParams& kp, const LsqParams& lp, int npairs, bool trial_round,
@@ -216,6 +226,9 @@ struct pcm_ctx {
   bool lio_planes_valid = false;   // planes of the last pcm_obs_model(rematch=1) belong to the current scan
   pcm::DevBuf<float2> lio_aux{"lio_aux"};   // PCM_FLAG_LIO_REFERENCE_SEMANTICS: residuals_ / point_selected_surf_ of LaserMapping, in the caller's scan order;
   size_t lio_aux_n = 0;                     // they outlive the scan (std::vector::resize semantics, laser_mapping.cc:337-338)
+  pcm::DevBuf<char> lio_upd{"lio_upd"};      // pcm_lio_update: descriptor, pair state, filter record and trace of the last update (lio_iekf.hip)
+  pcm::PinnedBuf<char> lio_upd_host{"lio_upd_host"};   // its pinned host image (one upload, one download)
+  int lio_upd_calls = 0;                    // ObsModel calls the trace of the last update holds
   void* ws = nullptr;   // batch workspace owned by this context (align_batch.hip)
   void* ndt_ws = nullptr;   // pclomp NDT: objects + solver machines of a batch (align_batch.hip)
   pcm::DevBuf<char> pre_arena{"pre_arena"};   // grow-only device scratch of the pre-processing operators

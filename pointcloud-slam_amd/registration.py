@@ -51,6 +51,20 @@ def _points(a):
     return arr.ctypes.data, arr.shape[0], arr.shape[1] * 4, capi.MEM_HOST, arr
 
 
+@dataclasses.dataclass
+class LioUpdateResult:
+    """Result of Registration.lio_update: the updated state (dict as given) and covariance, and the loop's counters."""
+    x: dict
+    P: np.ndarray
+    iterations: int       # ObsModel calls made (<= max_iter + 1)
+    rematches: int        # of those, with converge = true
+    valid_calls: int      # calls with n_eff >= 1
+    t: int                # the loop's converge counter at exit
+    n_eff_last: int
+    sum_h2_last: float
+    status: int
+
+
 class Registration:
     """One registration object bound to a HIP device (= one ``pcm_ctx``)."""
 
@@ -222,6 +236,49 @@ class Registration:
     def lio_frame_end(self, rot_xyzw, pos, off_R_xyzw, off_T, filter_size_map: float, ekf_inited: bool = True) -> int:
         """Back end of the frame (pcm_lio_frame_end = MapIncremental with the updated state); returns the points inserted."""
         return self.map_incremental(rot_xyzw, pos, off_R_xyzw, off_T, filter_size_map, ekf_inited)
+
+    LIO_STATE_FIELDS = (("pos", 3), ("rot", 4), ("off_R", 4), ("off_T", 3), ("vel", 3), ("bg", 3), ("ba", 3), ("grav", 3))
+
+    def lio_update(self, x, P, R: float = None, max_iter: int = None, extrinsic_est_en: bool = False, limit=None) -> "LioUpdateResult":
+        """jueying_lio's iterated Kalman update (esekf::update_iterated_dyn_share_modified) on the device: pcm_lio_update.
+        x: the propagated state_ikfom as a dict of pos(3) rot(4: x,y,z,w) off_R(4) off_T(3) vel(3) bg(3) ba(3) grav(3), or the 26 numbers
+        in that order; P: 23 x 23 covariance.  One call per frame between lio_frame_begin and lio_frame_end; the inputs are not changed.
+        Parameters default to the reference's (R 0.001, max_iter 4, limit 0.001 each)."""
+        st = capi.PcmLioFilterState()
+        if isinstance(x, dict):
+            for k, _ in self.LIO_STATE_FIELDS:
+                getattr(st, k)[:] = [float(v) for v in x[k]]
+        else:
+            v = np.ascontiguousarray(x, np.float64).reshape(26)
+            C.memmove(C.byref(st), v.ctypes.data, 26 * 8)
+        Pm = np.array(P, np.float64).reshape(23, 23).copy()
+        prm = capi.PcmLioUpdateParams()
+        self._L.pcm_lio_default_update_params(C.byref(prm))
+        if R is not None:
+            prm.R = float(R)
+        if max_iter is not None:
+            prm.max_iter = int(max_iter)
+        prm.extrinsic_est_en = int(bool(extrinsic_est_en))
+        if limit is not None:
+            prm.limit[:] = [float(v) for v in np.broadcast_to(np.asarray(limit, np.float64), (23,))]
+        res = capi.PcmLioUpdateResult()
+        self._check(self._L.pcm_lio_update(self._h, C.byref(prm), C.byref(st), Pm.ctypes.data, C.byref(res)))
+        xo = {k: np.array(getattr(st, k)[:]) for k, _ in self.LIO_STATE_FIELDS}
+        return LioUpdateResult(x=xo, P=Pm, iterations=res.iterations, rematches=res.rematches, valid_calls=res.valid_calls, t=res.t,
+                               n_eff_last=res.n_eff_last, sum_h2_last=res.sum_h2_last, status=res.status)
+
+    def lio_update_trace(self, call: int):
+        """ObsModel call `call` of the last lio_update: dict(x, converge, n_eff, HTH (12x12), HTh (12), dx_ (23))."""
+        st = capi.PcmLioFilterState()
+        cv, ne = C.c_int32(), C.c_int32()
+        sums = np.zeros(90); dx = np.zeros(23)
+        self._check(self._L.pcm_lio_update_trace(self._h, int(call), C.byref(st), C.byref(cv), C.byref(ne), sums.ctypes.data, dx.ctypes.data))
+        HTH = np.zeros((12, 12))
+        iu = np.triu_indices(12)
+        HTH[iu] = sums[:78]
+        HTH = HTH + np.triu(HTH, 1).T
+        return dict(x={k: np.array(getattr(st, k)[:]) for k, _ in self.LIO_STATE_FIELDS}, converge=bool(cv.value), n_eff=ne.value, HTH=HTH,
+                    HTh=sums[78:90].copy(), dx_=dx)
 
     def get_source(self) -> np.ndarray:
         n = C.c_size_t()
