@@ -416,6 +416,32 @@ int pcm_lio_update(pcm_ctx *ctx, const pcm_lio_update_params *params, pcm_lio_fi
  * HTH upper triangle (78) + HTh (12), and dx_ (23; zeros for an invalid call).  Any pointer may be NULL. */
 int pcm_lio_update_trace(pcm_ctx *ctx, int call, pcm_lio_filter_state *x, int32_t *converge, int32_t *n_eff, double *sums90, double *dx23);
 
+/* What ImuProcess::Process does before the frame (jueying_lio/include/imu_processing.hpp:287-318): IMUInit and the init branch
+ * (:113-163, :295-315; host arithmetic, no context), and for every later frame the forward loop of UndistortPcl with esekf::predict
+ * per IMU sample and the closing predict (:167-243, esekfom.hpp:269-374) on the device -- one upload, one launch of one wave that
+ * runs the whole sample loop, one download, one stream synchronisation.  The members of ImuProcess live in the caller's
+ * pcm_lio_imu_state.  Outputs feed the calls above with no other glue: poses / *num_poses (IMUpose_) and the pose part of x go to
+ * pcm_lio_frame_begin, pcm_lio_frame_begin_cloud or pcm_undistort, x and P (x_, P_) to pcm_lio_update.  DESIGN.md section 18. */
+typedef struct pcm_imu_sample { double t, acc[3], gyr[3]; } pcm_imu_sample;   /* sensor_msgs::Imu: stamp, linear_acceleration, angular_velocity */
+typedef struct pcm_lio_imu_state {                                            /* the members of ImuProcess, owned by the caller */
+  double mean_acc[3], mean_gyr[3], cov_acc[3], cov_gyr[3], cov_bias_gyr[3], cov_bias_acc[3];
+  double cov_acc_scale[3], cov_gyr_scale[3];                                  /* SetAccCov / SetGyrCov */
+  double lidar_T_wrt_imu[3], lidar_R_wrt_imu[4];                              /* SetExtrinsic; quaternion x y z w */
+  double angvel_last[3], acc_s_last[3], last_lidar_end_time;
+  pcm_imu_sample last_imu;
+  int32_t init_iter_num, first_frame, need_init, reserved[5];
+} pcm_lio_imu_state;
+/* the constructor's values (:71-84); acc_s_last, which the reference never initialises, is zero; the two scales are 0.1 (laser_mapping.cc:97-98) */
+void pcm_lio_default_imu_state(pcm_lio_imu_state *s);
+/* one frame of the init branch over the n >= 1 samples of the frame: running mean / covariance, then grav, bg, the extrinsics and
+ * the initial P (23 x 23 row-major) into x and P; s->need_init drops to 0 once init_iter_num exceeds MAX_INI_COUNT (20) */
+int pcm_lio_imu_init(pcm_lio_imu_state *s, const pcm_imu_sample *imu, int n, pcm_lio_filter_state *x, double *P);
+/* one frame of forward propagation on any context (its device and stream are all it uses).  1 <= n <= 1024 samples
+ * (PCM_ERR_OUT_OF_RANGE beyond), capacity >= n + 1 poses, s->need_init == 0.  x, P: in the filter's x_, P_; out the propagated ones.
+ * Updates s->last_imu, last_lidar_end_time, angvel_last, acc_s_last as the reference does; a bad argument leaves s, x and P untouched. */
+int pcm_lio_propagate(pcm_ctx *ctx, pcm_lio_imu_state *s, const pcm_imu_sample *imu, int n, double pcl_beg_time, double pcl_end_time, pcm_lio_filter_state *x,
+                      double *P, pcm_imu_pose *poses, int capacity, int *num_poses);
+
 /* Batch of independent registration objects on one device (BASELINE config 3:
  * independent scan/submap pairs): all GN/LM loops advance in lock-step kernel
  * launches, no host round trip per iteration.  `guesses` = n x 16 floats.

@@ -965,10 +965,71 @@ public:
     return pcm_lio_update_trace(ctx_, call, x, converge, n_eff, nullptr, dx23) == PCM_OK;
   }
 
+  // ---- p_imu_->Process(measures_, kf_, scan_undistort_) (laser_mapping.cc:307) and the frame around the update -----------------------
+  // the members of ImuProcess (SetExtrinsic / SetGyrCov / SetAccCov / SetGyrBiasCov / SetAccBiasCov write into it)
+  pcm_lio_imu_state& Imu() { return imu_; }
+  // the init branch of Process: one frame of IMUInit; true once the IMU is initialised (imu_need_init_ == false)
+  bool imuInit(const pcm_imu_sample* imu, int n, pcm_lio_filter_state* x, double* P) {
+    if (pcm_lio_imu_init(&imu_, imu, n, x, P) != PCM_OK) throw std::runtime_error("pcm_lio_imu_init: bad argument");
+    return imu_.need_init == 0;
+  }
+  // the forward loop of UndistortPcl + esekf::predict on the device; the IMUpose_ list is kept for the frame entry
+  const std::vector<pcm_imu_pose>& propagate(const pcm_imu_sample* imu, int n, double pcl_beg_time, double pcl_end_time, pcm_lio_filter_state* x, double* P) {
+    poses_.resize((size_t)(n > 0 ? n : 0) + 1);
+    int k = 0;
+    const int rc = pcm_lio_propagate(ctx_, &imu_, imu, n, pcl_beg_time, pcl_end_time, x, P, poses_.data(), (int)poses_.size(), &k);
+    if (rc != PCM_OK) throw std::runtime_error(std::string("pcm_lio_propagate: ") + pcm_last_error(ctx_));
+    poses_.resize((size_t)k);
+    return poses_;
+  }
+  enum class Frame { NoImu, Init, NoPoints, FirstScan, TooFewPoints, Updated };
+  // LaserMapping::Run (laser_mapping.cc:301-356) for one synchronised package: a livox_ros_driver::CustomMsg (msg->points.data(),
+  // n_points records), its IMU samples, lidar_bag_time_ and lidar_end_time_.  x, P: the filter's state and covariance, in / out.
+  Frame processFrame(const void* custom_points, size_t n_points, const pcm_imu_sample* imu, int n_imu, double pcl_beg_time, double pcl_end_time,
+                     const pcm_lio_frame_params& frame, float filter_size_map, pcm_lio_filter_state* x, double* P) {
+    if (n_imu <= 0) return Frame::NoImu;
+    if (imu_.need_init) { imuInit(imu, n_imu, x, P); return Frame::Init; }
+    propagate(imu, n_imu, pcl_beg_time, pcl_end_time, x, P);
+    pcm_lio_state st = poseOf(*x);
+    pcm_lio_frame_params fp = frame;
+    if (first_scan_) fp.leaf_size = 0.f;
+    size_t n_scan = 0;
+    int rc = pcm_lio_frame_begin(ctx_, custom_points, n_points, PCM_MEM_HOST, &fp, poses_.data(), (int)poses_.size(), &st, &n_scan);
+    if (rc == PCM_ERR_NO_INPUT) return Frame::NoPoints;                       // "No point, skip this scan!"
+    if (rc != PCM_OK) throw std::runtime_error(std::string("pcm_lio_frame_begin: ") + pcm_last_error(ctx_));
+    if (first_scan_) {                                                        // ivox_->AddPoints(scan_undistort_->points)
+      std::vector<float> xyz(3 * n_scan);
+      if (pcm_get_source(ctx_, xyz.data(), n_scan, &n_scan) != PCM_OK || pcm_target_insert(ctx_, xyz.data(), n_scan, 12, PCM_MEM_HOST) != PCM_OK)
+        throw std::runtime_error(std::string("first scan: ") + pcm_last_error(ctx_));
+      first_lidar_time_ = pcl_beg_time;
+      first_scan_ = false;
+      return Frame::FirstScan;
+    }
+    ekf_inited_ = (pcl_beg_time - first_lidar_time_) >= 0.1;                  // options::INIT_TIME
+    if (n_scan < 5) return Frame::TooFewPoints;
+    Update(x, P);
+    st = poseOf(*x);
+    size_t added = 0;
+    rc = pcm_lio_frame_end(ctx_, &st, filter_size_map, ekf_inited_ ? 1 : 0, &added);
+    if (rc != PCM_OK) throw std::runtime_error(std::string("pcm_lio_frame_end: ") + pcm_last_error(ctx_));
+    return Frame::Updated;
+  }
+  bool EkfInited() const { return ekf_inited_; }
+
 private:
+  static pcm_lio_state poseOf(const pcm_lio_filter_state& x) {
+    pcm_lio_state st{};
+    for (int a = 0; a < 4; a++) { st.rot[a] = x.rot[a]; st.off_R[a] = x.off_R[a]; }
+    for (int a = 0; a < 3; a++) { st.pos[a] = x.pos[a]; st.off_T[a] = x.off_T[a]; }
+    return st;
+  }
   pcm_ctx* ctx_ = nullptr;
   pcm_lio_update_params params_;
   pcm_lio_update_result last_{};
+  pcm_lio_imu_state imu_ = [] { pcm_lio_imu_state s; pcm_lio_default_imu_state(&s); return s; }();
+  std::vector<pcm_imu_pose> poses_;
+  bool first_scan_ = true, ekf_inited_ = false;
+  double first_lidar_time_ = 0.0;
 };
 
 }  // namespace pcm_amd

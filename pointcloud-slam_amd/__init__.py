@@ -18,3 +18,4 @@ from .registration import LoamMapLoadResult, LoamMapCropResult, read_arealist, w
 from .registration import (ScanSegment, lidar_xyzirt_segment, lidar_xyzi_segment, depth_segment, rs_to_velodyne, hesai_to_velodyne,  # noqa: F401
                            fuse_lidar_cameras)
 from .registration import lidar_desc  # noqa: F401
+from .registration import LioOdometry, lio_imu_state  # noqa: F401

@@ -30,6 +30,7 @@ SYMBOLS = [
     "pcm_scan_default_fuse_params", "pcm_scan_fuse", "pcm_scan_fused",
     "pcm_lidar_default_desc", "pcm_lidar_filter", "pcm_lio_frame_begin_cloud",
     "pcm_lio_default_update_params", "pcm_lio_update", "pcm_lio_update_trace",
+    "pcm_lio_default_imu_state", "pcm_lio_imu_init", "pcm_lio_propagate",
 ]
 
 PCM_ABI_VERSION = 3   # include/pcm_amd.h
@@ -96,6 +97,18 @@ class PcmLioUpdateParams(C.Structure):
 class PcmLioUpdateResult(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("rematches", C.c_int32), ("valid_calls", C.c_int32), ("t", C.c_int32), ("n_eff_last", C.c_int32),
                 ("status", C.c_int32), ("sum_h2_last", C.c_double), ("reserved", C.c_int32 * 8)]
+
+
+class PcmImuSample(C.Structure):   # sensor_msgs::Imu: stamp, linear_acceleration, angular_velocity
+    _fields_ = [("t", C.c_double), ("acc", C.c_double * 3), ("gyr", C.c_double * 3)]
+
+
+class PcmLioImuState(C.Structure):   # the members of ImuProcess
+    _fields_ = [("mean_acc", C.c_double * 3), ("mean_gyr", C.c_double * 3), ("cov_acc", C.c_double * 3), ("cov_gyr", C.c_double * 3),
+                ("cov_bias_gyr", C.c_double * 3), ("cov_bias_acc", C.c_double * 3), ("cov_acc_scale", C.c_double * 3), ("cov_gyr_scale", C.c_double * 3),
+                ("lidar_T_wrt_imu", C.c_double * 3), ("lidar_R_wrt_imu", C.c_double * 4), ("angvel_last", C.c_double * 3), ("acc_s_last", C.c_double * 3),
+                ("last_lidar_end_time", C.c_double), ("last_imu", PcmImuSample), ("init_iter_num", C.c_int32), ("first_frame", C.c_int32),
+                ("need_init", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
 class PcmLioFrameParams(C.Structure):
@@ -384,5 +397,9 @@ def load_library():
     L.pcm_lio_default_update_params.restype = None
     L.pcm_lio_update.argtypes = [vp, C.POINTER(PcmLioUpdateParams), C.POINTER(PcmLioFilterState), vp, C.POINTER(PcmLioUpdateResult)]
     L.pcm_lio_update_trace.argtypes = [vp, i32, C.POINTER(PcmLioFilterState), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp]
+    L.pcm_lio_default_imu_state.argtypes = [C.POINTER(PcmLioImuState)]
+    L.pcm_lio_default_imu_state.restype = None
+    L.pcm_lio_imu_init.argtypes = [C.POINTER(PcmLioImuState), vp, i32, C.POINTER(PcmLioFilterState), vp]
+    L.pcm_lio_propagate.argtypes = [vp, C.POINTER(PcmLioImuState), vp, i32, C.c_double, C.c_double, C.POINTER(PcmLioFilterState), vp, vp, i32, C.POINTER(C.c_int32)]
     _LIB = L
     return L

@@ -229,6 +229,8 @@ struct pcm_ctx {
   pcm::DevBuf<char> lio_upd{"lio_upd"};      // pcm_lio_update: descriptor, pair state, filter record and trace of the last update (lio_iekf.hip)
   pcm::PinnedBuf<char> lio_upd_host{"lio_upd_host"};   // its pinned host image (one upload, one download)
   int lio_upd_calls = 0;                    // ObsModel calls the trace of the last update holds
+  pcm::DevBuf<char> lio_prop{"lio_prop"};    // pcm_lio_propagate: the uploaded frame block and the downloaded result block (lio_predict.hip)
+  pcm::PinnedBuf<char> lio_prop_host{"lio_prop_host"};   // their pinned host image
   void* ws = nullptr;   // batch workspace owned by this context (align_batch.hip)
   void* ndt_ws = nullptr;   // pclomp NDT: objects + solver machines of a batch (align_batch.hip)
   pcm::DevBuf<char> pre_arena{"pre_arena"};   // grow-only device scratch of the pre-processing operators

@@ -1577,3 +1577,144 @@ def _lio_frame_begin_cloud(self, points, desc, poses=None, rot_xyzw=(0, 0, 0, 1.
 for _cls in (Registration, LoamRegistration, OccupancyMap2D):
     _cls.lidar_filter = _lidar_filter
 Registration.lio_frame_begin_cloud = _lio_frame_begin_cloud
+
+
+# ---- ImuProcess::Process of jueying_lio: the init frames and the forward propagation (pcm_lio_imu_init, pcm_lio_propagate;
+# ---- DESIGN.md section 18), and LaserMapping::Run composed from the existing frame calls ---------------------------------------------
+IMU_STATE_VECTORS = ("mean_acc", "mean_gyr", "cov_acc", "cov_gyr", "cov_bias_gyr", "cov_bias_acc", "cov_acc_scale", "cov_gyr_scale", "lidar_T_wrt_imu",
+                     "lidar_R_wrt_imu", "angvel_last", "acc_s_last")
+IMU_STATE_SCALARS = ("last_lidar_end_time", "init_iter_num", "first_frame", "need_init")
+
+
+def lio_imu_state(**overrides) -> capi.PcmLioImuState:
+    """The members of ImuProcess with the constructor's values (pcm_lio_default_imu_state), any of them overridden: the vectors by a
+    sequence, last_imu by the 7 numbers t, acc, gyr, the scalars by a number."""
+    s = capi.PcmLioImuState()
+    capi.load_library().pcm_lio_default_imu_state(C.byref(s))
+    for k, v in overrides.items():
+        if k in IMU_STATE_VECTORS:
+            getattr(s, k)[:] = [float(t) for t in v]
+        elif k == "last_imu":
+            v = [float(t) for t in v]
+            s.last_imu.t = v[0]; s.last_imu.acc[:] = v[1:4]; s.last_imu.gyr[:] = v[4:7]
+        elif k in IMU_STATE_SCALARS:
+            setattr(s, k, v)
+        else:
+            raise KeyError(k)
+    return s
+
+
+def _filter_state(x) -> capi.PcmLioFilterState:
+    st = capi.PcmLioFilterState()
+    if isinstance(x, dict):
+        for k, _ in Registration.LIO_STATE_FIELDS:
+            getattr(st, k)[:] = [float(v) for v in x[k]]
+    else:
+        v = np.ascontiguousarray(x, np.float64).reshape(26)
+        C.memmove(C.byref(st), v.ctypes.data, 26 * 8)
+    return st
+
+
+def _filter_dict(st) -> dict:
+    return {k: np.array(getattr(st, k)[:]) for k, _ in Registration.LIO_STATE_FIELDS}
+
+
+def _imu_rows(imu) -> np.ndarray:
+    a = np.ascontiguousarray(imu, np.float64)
+    if a.ndim != 2 or a.shape[1] != 7:
+        raise ValueError("expected (n, 7) IMU rows: t, acc, gyr")
+    return a
+
+
+def _lio_imu_init(self, imu_state: capi.PcmLioImuState, imu, x, P):
+    """One init frame of ImuProcess::Process (pcm_lio_imu_init; host arithmetic): imu_state is advanced in place, -> (x, P) with grav,
+    bg, the extrinsics and the initial covariance set.  imu: (n, 7) rows t, acc, gyr; x as for lio_update."""
+    a = _imu_rows(imu)
+    st = _filter_state(x)
+    Pm = np.array(P, np.float64).reshape(23, 23).copy()
+    rc = self._L.pcm_lio_imu_init(C.byref(imu_state), a.ctypes.data, a.shape[0], C.byref(st), Pm.ctypes.data)
+    if rc != capi.PCM_OK:
+        raise capi.PcmError(rc, "pcm_lio_imu_init: no sample, a sample that is not finite, or an IMU state that is already initialised")
+    return _filter_dict(st), Pm
+
+
+def _lio_propagate(self, imu_state: capi.PcmLioImuState, imu, t_beg: float, t_end: float, x, P, capacity: int = None):
+    """The forward propagation of one frame on the device (pcm_lio_propagate): esekf::predict per IMU sample and the closing one.
+    imu_state is advanced in place; -> (x, P, poses) with the propagated state and covariance for lio_update and the (k, 22) Pose6D
+    rows for lio_frame_begin / lio_frame_begin_cloud / undistort.  The inputs x and P are not changed."""
+    a = _imu_rows(imu)
+    st = _filter_state(x)
+    Pm = np.array(P, np.float64).reshape(23, 23).copy()
+    cap = a.shape[0] + 1 if capacity is None else int(capacity)
+    poses = np.zeros((max(cap, 1), 22))
+    k = C.c_int32()
+    self._check(self._L.pcm_lio_propagate(self._h, C.byref(imu_state), a.ctypes.data, a.shape[0], float(t_beg), float(t_end), C.byref(st), Pm.ctypes.data,
+                                          poses.ctypes.data, cap, C.byref(k)))
+    return _filter_dict(st), Pm, poses[:k.value].copy()
+
+
+Registration.lio_imu_init = _lio_imu_init
+Registration.lio_propagate = _lio_propagate
+
+
+class LioOdometry:
+    """LaserMapping::Run (laser_mapping.cc:301-356) over one Registration (P2PLANE): ImuProcess::Process, the first-scan branch, the
+    down-sampled frame, the iterated Kalman update and the map update, every step one of the object's existing calls.
+    `propagate(imu_state, imu, t_beg, t_end, x, P) -> (x, P, poses)` defaults to the object's lio_propagate (tests hand in a host
+    restatement of the same step)."""
+    INIT_TIME = 0.1          # options.h:11
+    MIN_POINTS = 5           # laser_mapping.cc:331
+
+    def __init__(self, reg: Registration, imu_state: capi.PcmLioImuState = None, x=None, P=None, filter_size_map: float = 0.5, propagate=None,
+                 update_params: dict = None, **frame_params):
+        self.reg = reg
+        self.imu_state = imu_state if imu_state is not None else lio_imu_state()
+        self.x = _filter_dict(_filter_state(x)) if x is not None else _filter_dict(_filter_state([0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 1] + [0] * 12 + [9.809, 0, 0]))
+        self.P = np.eye(23) if P is None else np.array(P, np.float64).reshape(23, 23).copy()
+        self.filter_size_map = float(filter_size_map)
+        self.frame_params = dict(frame_params)
+        self.update_params = dict(update_params or {})
+        self.propagate = propagate if propagate is not None else reg.lio_propagate
+        self.first_scan = True
+        self.first_lidar_time = 0.0
+        self.ekf_inited = False
+        self.last_update = None
+
+    def _pose_args(self):
+        return self.x["rot"], self.x["pos"], self.x["off_R"], self.x["off_T"]
+
+    def _frame_begin(self, msg_points, poses, kw) -> int:
+        try:
+            return self.reg.lio_frame_begin(msg_points, poses, *self._pose_args(), **kw)
+        except capi.PcmError as e:
+            if e.code != -2:                                   # PCM_ERR_NO_INPUT: "No point, skip this scan!"
+                raise
+            return 0
+
+    def process(self, msg_points, imu, t_beg: float, t_end: float) -> str:
+        """One synchronised package (measures_): the frame's driver message, its IMU samples, lidar_bag_time_ and lidar_end_time_.
+        -> what became of it: "no_imu" | "init" | "no_points" | "first_scan" | "too_few_points" | "updated"."""
+        if len(imu) == 0:
+            return "no_imu"                                    # Process returns on an empty queue; scan_undistort_ stays empty
+        if self.imu_state.need_init:
+            self.x, self.P = self.reg.lio_imu_init(self.imu_state, imu, self.x, self.P)
+            return "init"
+        self.x, self.P, poses = self.propagate(self.imu_state, imu, t_beg, t_end, self.x, self.P)
+        if self.first_scan:                                    # ivox_->AddPoints(scan_undistort_->points)
+            kw = dict(self.frame_params); kw["leaf_size"] = 0.0
+            if self._frame_begin(msg_points, poses, kw) == 0:
+                return "no_points"
+            self.reg.target_insert(self.reg.get_source())
+            self.first_lidar_time = float(t_beg)
+            self.first_scan = False
+            return "first_scan"
+        self.ekf_inited = (float(t_beg) - self.first_lidar_time) >= self.INIT_TIME
+        n = self._frame_begin(msg_points, poses, self.frame_params)
+        if n == 0:
+            return "no_points"
+        if n < self.MIN_POINTS:
+            return "too_few_points"
+        self.last_update = self.reg.lio_update(self.x, self.P, **self.update_params)
+        self.x, self.P = self.last_update.x, self.last_update.P
+        self.reg.lio_frame_end(*self._pose_args(), self.filter_size_map, self.ekf_inited)
+        return "updated"
