@@ -711,6 +711,74 @@ int pcm_loam_sc_distance(pcm_ctx *ctx, const pcm_loam_sc_params *params, int i, 
 int pcm_loam_loop_detect_distance(pcm_ctx *ctx, float radius, double time_diff_s, double time_cur, int32_t *key_cur, int32_t *key_pre);
 
 /*
+ * Loop verification of jueying_slam on the device: performLoopClosure (mapOptmization.cpp:619-733) from a detected pair to the
+ * loop factor, with the key frames never leaving the device.  The live verifier of that function is
+ * pclomp::NormalDistributionsTransform (:683-697; the PCL ICP block above it is commented out).  DESIGN.md section 19.
+ *
+ * pcm_loam_submap_near_dev: pcm_loam_submap_near -- same selection, transform, order and VoxelGrid, the same bits -- with the
+ * (x, y, z, intensity) float4 records written to a host or a DEVICE buffer (`memory`; capacity in points; *n_out always set,
+ * PCM_ERR_INVALID_ARGUMENT when the capacity is too small).  It waits for the stream only when the count has to come back
+ * (leaf > 0) or the result goes to host memory: with leaf == 0 and a device buffer the call returns with the work queued on the
+ * context's stream.  A device buffer with room for every input point of the window is written in place.
+ */
+int pcm_loam_submap_near_dev(pcm_ctx *ctx, int key, int search_num, int wrt_key, float leaf, void *out, size_t cap, int memory, size_t *n_out);
+
+#define PCM_LOAM_LOOP_ACCEPTED 0
+#define PCM_LOAM_LOOP_REJECTED_SIZE 1            /* :652 a cloud below its gate; NDT did not run */
+#define PCM_LOAM_LOOP_REJECTED_NOT_CONVERGED 2   /* :693 hasConverged() == false */
+#define PCM_LOAM_LOOP_REJECTED_FITNESS 3         /* :693 getFitnessScore() > historyKeyframeFitnessScore */
+#define PCM_LOAM_LOOP_NONE 4                     /* pcm_loam_loop_closure: detectLoopClosureDistance found no pair */
+
+typedef struct pcm_loam_loop_params {
+  int32_t history_search_num;    /* 25    utility.h:290 historyKeyframeSearchNum: the previous cloud spans key_pre -/+ this */
+  int32_t min_cur_points;        /* 300   mapOptmization.cpp:652 */
+  int32_t min_prev_points;       /* 1000  mapOptmization.cpp:652 */
+  int32_t wrt_key;               /* -1    every key frame under its own pose, as performLoopClosure (:650-651).  >= 0: both clouds
+                                  *       under the pose of that key frame (loopFindNearKeyframesWithRespectTo) -- an option of this
+                                  *       library, NOT performSCLoopClosure, which verifies with PCL ICP and stays with the caller */
+  float fitness_threshold;       /* 0.3   utility.h:291 historyKeyframeFitnessScore */
+  float near_leaf;               /* 0.2   mapOptmization.cpp:243 downSizeFilterICP = mappingSurfLeafSize (utility.h:272); 0 = none */
+  double ndt_epsilon;            /* 0.01  mapOptmization.cpp:684 setTransformationEpsilon */
+  float ndt_resolution;          /* 1.0   mapOptmization.cpp:685 setResolution */
+  int32_t ndt_num_neighbors;     /* 7     mapOptmization.cpp:686 DIRECT7 (0 KDTREE, 1, 7, 27 as pcm_config::num_neighbors) */
+  int32_t reserved[8];
+} pcm_loam_loop_params;
+
+typedef struct pcm_loam_loop_result {
+  int32_t status;                /* PCM_LOAM_LOOP_* */
+  int32_t key_cur, key_pre;      /* the pair (pcm_loam_loop_closure: as detected; -1, -1 without one) */
+  int32_t num_cur_points;        /* cureKeyframeCloud->size() */
+  int32_t num_prev_points;       /* prevKeyframeCloud->size() */
+  int32_t ndt_iterations;        /* 0 when NDT did not run */
+  int32_t ndt_converged;
+  float noise_variance;          /* :719 float noiseScore = getFitnessScore(): the six variances of the loop's noise model */
+  double fitness;                /* ndt->getFitnessScore() (PCL's default max_range); 0 when NDT did not run */
+  float correction[16];          /* ndt->getFinalTransformation(), row-major; identity when NDT did not run */
+  /* the loop factor, written when the status is ACCEPTED (zero otherwise); poses as (roll, pitch, yaw, x, y, z) */
+  double pose_from[6];           /* :715 poseFrom: getTranslationAndEulerAngles(correction * tWrong), floats promoted */
+  double pose_to[6];             /* :716 poseTo = pose of key_pre */
+  double between[16];            /* :725 poseFrom.between(poseTo), row-major 4 x 4 */
+  double between6[6];            /* the same as (roll, pitch, yaw, x, y, z) */
+  int32_t reserved[8];
+} pcm_loam_loop_result;
+
+void pcm_loam_default_loop_params(pcm_loam_loop_params *params);
+/* performLoopClosure :645-731 for the pair (key_cur, key_pre): both near clouds are built in device memory (one wait, for their
+ * two counts), the size gates, pclomp NDT from the identity in a verifier context the LOAM context owns (created by the first
+ * verification that passes the gates, released with the context), its fitness score, the acceptance test and -- on the host -- the
+ * pose algebra of :706-725.  Returns PCM_OK with the outcome in result->status.  The context's target, source, key frames and Scan
+ * Context store are not touched.  An empty store, a key outside [0, K) and bad parameters: PCM_ERR_INVALID_ARGUMENT, nothing
+ * changed.  params NULL = defaults.  GTSAM's factor and the loopIndexContainer bookkeeping (:730) stay with the caller. */
+int pcm_loam_loop_verify(pcm_ctx *ctx, const pcm_loam_loop_params *params, int key_cur, int key_pre, pcm_loam_loop_result *result);
+/* detectLoopClosureDistance (pcm_loam_loop_detect_distance with the same radius / time_diff_s / time_cur) followed by
+ * pcm_loam_loop_verify of the pair it finds.  No pair: PCM_OK with status PCM_LOAM_LOOP_NONE, at the cost of the host search alone
+ * (no device work, no verifier).  The loopIndexContainer test and insert (:730, :848) stay with the caller: a pair the caller has
+ * already closed is verified again unless the caller filters it. */
+int pcm_loam_loop_closure(pcm_ctx *ctx, const pcm_loam_loop_params *params, float radius, double time_diff_s, double time_cur, pcm_loam_loop_result *result);
+/* 1 when the context holds a verifier context, 0 when none has been created yet, or a negative pcm_status */
+int pcm_loam_loop_verifier_exists(pcm_ctx *ctx);
+
+/*
  * Localisation map of jueying_slam on the device: the saved global map cut into area tiles (include/dynamic_map.h:16-156), the
  * reload of the tiles around the robot (dynamic_load_map_run, localization.cpp:281-315) and the per-frame crop of the loaded
  * tiles (dynamic_load_map, :256-280).  A PCM_MODEL_LOAM context keeps every tile of the corner list and of the surf list (map

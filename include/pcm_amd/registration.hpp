@@ -27,6 +27,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../pcm_amd.h"
@@ -429,6 +430,7 @@ private:
 //     keyframes.correctPoses(poses, n);                                      // :1886-1917 after a loop closure
 //     keyframes.loopFindNearKeyframes(cureKeyframeCloud, loopKeyCur, 0);     // :972
 //     keyframes.loopFindNearKeyframesWithRespectTo(prevKeyframeCloud, loopKeyPre, historyKeyframeSearchNum, loopKeyCur);
+//     if (keyframes.performLoopClosure(timeLaserInfoCur, &factor)) { ... }   // :619-733 on the device
 // Poses are transformTobeMapped vectors (roll, pitch, yaw, x, y, z).  The object does not own the context: it must not outlive `loam`.
 template <typename PointT>
 class LoamKeyFrameMap {
@@ -442,7 +444,14 @@ public:
   void setSurroundingKeyframeDensity(float v) { params_.keypose_density = v; }      // surroundingKeyframeDensity
   void setMappingCornerLeafSize(float v) { params_.corner_leaf = v; }               // mappingCornerLeafSize
   void setMappingSurfLeafSize(float v) { params_.surf_leaf = v; }                   // mappingSurfLeafSize
-  void setLoopLeafSize(float v) { loop_leaf_ = v; }                                 // downSizeFilterICP (mappingSurfLeafSize)
+  void setLoopLeafSize(float v) { loop_leaf_ = v; }                                 // downSizeFilterICP (mappingSurfLeafSize); also performLoopClosure's leaf
+  void setHistoryKeyframeSearchNum(int v) { loopParams().history_search_num = v; }  // historyKeyframeSearchNum
+  void setHistoryKeyframeFitnessScore(float v) { loopParams().fitness_threshold = v; }   // historyKeyframeFitnessScore
+  // the reference's values on first use; near_leaf is taken from setLoopLeafSize at every call
+  pcm_loam_loop_params& loopParams() {
+    if (!loop_params_set_) { pcm_loam_default_loop_params(&loop_params_); loop_params_set_ = true; }
+    return loop_params_;
+  }
   pcm_loam_submap_params& params() { return params_; }
   const pcm_loam_submap_result& result() const { return last_; }
   int size() const { return pcm_loam_keyframe_count(ctx_); }                        // cloudKeyPoses3D->size()
@@ -472,7 +481,42 @@ public:
   void loopFindNearKeyframes(Cloud& nearKeyframes, int key, int searchNum) { near(nearKeyframes, key, searchNum, -1); }
   void loopFindNearKeyframesWithRespectTo(Cloud& nearKeyframes, int key, int searchNum, int wrtKey) { near(nearKeyframes, key, searchNum, wrtKey); }
 
+  // What performLoopClosure pushes on its three queues (mapOptmization.cpp:724-726): loopIndexQueue's pair, loopPoseQueue's
+  // poseFrom.between(poseTo) -- row-major 4 x 4 and (roll, pitch, yaw, x, y, z), for gtsam::Pose3(Rot3::RzRyRx(...), Point3(...)) --
+  // and the variance that fills loopNoiseQueue's noiseModel::Diagonal::Variances.
+  struct LoopFactor {
+    std::pair<int, int> index{-1, -1};
+    double between[16] = {};
+    double between6[6] = {};
+    float noise = 0.f;
+  };
+  const pcm_loam_loop_result& loopResult() const { return loop_last_; }
+  // performLoopClosure :645-731 for a given pair, on the device (pcm_loam_loop_verify): true = the factor is in *out.  The
+  // loopIndexContainer bookkeeping (:730) stays with the caller.
+  bool performLoopClosure(int loopKeyCur, int loopKeyPre, LoopFactor* out) {
+    loopParams().near_leaf = loop_leaf_;
+    check(pcm_loam_loop_verify(ctx_, &loop_params_, loopKeyCur, loopKeyPre, &loop_last_), "pcm_loam_loop_verify");
+    return take_factor(out);
+  }
+  // detectLoopClosureDistance (:638) and the verification in one call (pcm_loam_loop_closure); false also when there is no pair
+  bool performLoopClosure(double timeLaserInfoCur, LoopFactor* out, float historyKeyframeSearchRadius = 10.0f, double historyKeyframeSearchTimeDiff = 30.0) {
+    loopParams().near_leaf = loop_leaf_;
+    check(pcm_loam_loop_closure(ctx_, &loop_params_, historyKeyframeSearchRadius, historyKeyframeSearchTimeDiff, timeLaserInfoCur, &loop_last_),
+          "pcm_loam_loop_closure");
+    return take_factor(out);
+  }
+
 private:
+  bool take_factor(LoopFactor* out) const {
+    if (loop_last_.status != PCM_LOAM_LOOP_ACCEPTED) return false;
+    if (out) {
+      out->index = std::make_pair((int)loop_last_.key_cur, (int)loop_last_.key_pre);
+      for (int k = 0; k < 16; k++) out->between[k] = loop_last_.between[k];
+      for (int k = 0; k < 6; k++) out->between6[k] = loop_last_.between6[k];
+      out->noise = loop_last_.noise_variance;
+    }
+    return true;
+  }
   void near(Cloud& out, int key, int searchNum, int wrt) {
     // room for every point of the key frames in the window (the VoxelGrid can only shrink it), from the stored counts
     const int K = size();
@@ -499,6 +543,9 @@ private:
   pcm_ctx* ctx_ = nullptr;
   pcm_loam_submap_params params_;
   pcm_loam_submap_result last_{};
+  pcm_loam_loop_params loop_params_{};
+  bool loop_params_set_ = false;
+  pcm_loam_loop_result loop_last_{};
   float loop_leaf_ = 0.2f;
   std::vector<float> buf_, buf2_;
 };

@@ -23,6 +23,7 @@ SYMBOLS = [
     "pcm_loam_keyframe_get", "pcm_loam_submap_update", "pcm_loam_submap_near", "pcm_loam_submap_info",
     "pcm_loam_default_sc_params", "pcm_loam_sc_add", "pcm_loam_sc_put", "pcm_loam_sc_get", "pcm_loam_sc_count", "pcm_loam_sc_shape", "pcm_loam_sc_clear",
     "pcm_loam_sc_detect", "pcm_loam_sc_distance", "pcm_loam_loop_detect_distance",
+    "pcm_loam_submap_near_dev", "pcm_loam_default_loop_params", "pcm_loam_loop_verify", "pcm_loam_loop_closure", "pcm_loam_loop_verifier_exists",
     "pcm_loam_default_dynmap_params", "pcm_loam_tile_add", "pcm_loam_tile_count", "pcm_loam_tile_clear", "pcm_loam_dynmap_need_load",
     "pcm_loam_dynmap_load", "pcm_loam_dynmap_crop", "pcm_loam_dynmap_info", "pcm_loam_dynmap_global",
     "pcm_occ_default_params", "pcm_occ_reset", "pcm_occ_insert_scans", "pcm_occ_insert_keyframes", "pcm_occ_get_scan", "pcm_occ_status",
@@ -181,6 +182,22 @@ class PcmLoamScResult(C.Structure):
                 ("num_descriptors", C.c_int32), ("tree_size", C.c_int32), ("tree_rebuilt", C.c_int32), ("num_evaluated", C.c_int32),
                 ("status", C.c_int32), ("reserved0", C.c_int32), ("cand_index", C.c_int32 * 64), ("cand_d2", C.c_float * 64),
                 ("cand_dist", C.c_double * 64), ("cand_shift", C.c_int32 * 64), ("reserved", C.c_int32 * 8)]
+
+
+PCM_LOAM_LOOP_ACCEPTED, PCM_LOAM_LOOP_REJECTED_SIZE, PCM_LOAM_LOOP_REJECTED_NOT_CONVERGED, PCM_LOAM_LOOP_REJECTED_FITNESS, PCM_LOAM_LOOP_NONE = 0, 1, 2, 3, 4
+
+
+class PcmLoamLoopParams(C.Structure):
+    _fields_ = [("history_search_num", C.c_int32), ("min_cur_points", C.c_int32), ("min_prev_points", C.c_int32), ("wrt_key", C.c_int32),
+                ("fitness_threshold", C.c_float), ("near_leaf", C.c_float), ("ndt_epsilon", C.c_double), ("ndt_resolution", C.c_float),
+                ("ndt_num_neighbors", C.c_int32), ("reserved", C.c_int32 * 8)]
+
+
+class PcmLoamLoopResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("key_cur", C.c_int32), ("key_pre", C.c_int32), ("num_cur_points", C.c_int32), ("num_prev_points", C.c_int32),
+                ("ndt_iterations", C.c_int32), ("ndt_converged", C.c_int32), ("noise_variance", C.c_float), ("fitness", C.c_double),
+                ("correction", C.c_float * 16), ("pose_from", C.c_double * 6), ("pose_to", C.c_double * 6), ("between", C.c_double * 16),
+                ("between6", C.c_double * 6), ("reserved", C.c_int32 * 8)]
 
 
 class PcmLoamDynmapParams(C.Structure):
@@ -364,6 +381,12 @@ def load_library():
     L.pcm_loam_sc_detect.argtypes = [vp, C.POINTER(PcmLoamScParams), C.POINTER(PcmLoamScResult)]
     L.pcm_loam_sc_distance.argtypes = [vp, C.POINTER(PcmLoamScParams), i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     L.pcm_loam_loop_detect_distance.argtypes = [vp, C.c_float, C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.pcm_loam_submap_near_dev.argtypes = [vp, i32, i32, i32, C.c_float, vp, sz, i32, C.POINTER(sz)]
+    L.pcm_loam_default_loop_params.argtypes = [C.POINTER(PcmLoamLoopParams)]
+    L.pcm_loam_default_loop_params.restype = None
+    L.pcm_loam_loop_verify.argtypes = [vp, C.POINTER(PcmLoamLoopParams), i32, i32, C.POINTER(PcmLoamLoopResult)]
+    L.pcm_loam_loop_closure.argtypes = [vp, C.POINTER(PcmLoamLoopParams), C.c_float, C.c_double, C.c_double, C.POINTER(PcmLoamLoopResult)]
+    L.pcm_loam_loop_verifier_exists.argtypes = [vp]
     L.pcm_loam_default_dynmap_params.argtypes = [C.POINTER(PcmLoamDynmapParams)]
     L.pcm_loam_default_dynmap_params.restype = None
     L.pcm_loam_tile_add.argtypes = [vp, i32, vp, vp, sz, sz, i32]

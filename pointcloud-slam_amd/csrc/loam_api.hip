@@ -35,6 +35,7 @@ struct LoamCtx {
   void* scstore = nullptr;     // Scan Context descriptors and loop-detection workspace (loam_sc.hip)
   bool tgt_from_dynmap = false;   // the target clouds are what loam_target_commit_dynmap left
   void* dynstore = nullptr;    // localisation map tiles and crop workspace (loam_dynmap.hip)
+  void* loopstore = nullptr;   // loop verifier: the pclomp NDT context of pcm_loam_loop_verify (loam_loop.hip)
   uint32_t n_c = 0, n_s = 0;
   DevBuf<double> partials;
   DevBuf<LoamState> st;
@@ -343,6 +344,7 @@ void loam_release(pcm_ctx* c) {
   if (L->keystore) loam::loam_keystore_release(L->keystore);
   if (L->scstore) loam::loam_scstore_release(L->scstore);
   if (L->dynstore) loam::loam_dynstore_release(L->dynstore);
+  if (L->loopstore) loam::loam_loopstore_release(L->loopstore);
   delete L;
   c->loam = nullptr;
 }
@@ -449,6 +451,11 @@ bool loam_target_view_dynmap(pcm_ctx* c, const float4** corner, uint32_t* n_corn
 void** loam_dynstore_slot(pcm_ctx* c) {
   LoamCtx* L = loam_of(c);
   return L ? &L->dynstore : nullptr;
+}
+
+void** loam_loopstore_slot(pcm_ctx* c) {
+  LoamCtx* L = loam_of(c);
+  return L ? &L->loopstore : nullptr;
 }
 }  // namespace loam
 }  // namespace pcm

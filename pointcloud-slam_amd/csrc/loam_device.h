@@ -56,6 +56,16 @@ bool loam_keyframe_cloud(pcm_ctx* c, int key, int which, const float4** pts, uin
 bool loam_keyframe_pose(pcm_ctx* c, int key, float pose6[6]);   // roll, pitch, yaw, x, y, z as stored
 struct KeyPose;
 int loam_keyposes(pcm_ctx* c, const KeyPose** kp);
+// loam_submap.hip: queues the near-key-frame cloud of (key, search_num, wrt_key, leaf) -- pcm_loam_submap_near's cloud, bit for
+// bit -- on the context's stream into workspace `slot` (0 or 1) and does not wait.  Once the stream has drained, h_small[0] is
+// the number of points at pts and h_small[2] says whether the leaf index overflowed; pts == nullptr: the selected clouds are
+// empty.  An empty store and bad arguments: PCM_ERR_INVALID_ARGUMENT.  loam_near_waited: the caller has drained the stream.
+struct NearCloud { const float4* pts; uint32_t n_in; const uint32_t* h_small; };
+int loam_near_queue(pcm_ctx* c, int slot, int key, int search_num, int wrt_key, float leaf, NearCloud* out);
+void loam_near_waited(pcm_ctx* c);
+// the loop verifier of a context (pcm_ctx::loam owns the pointer, loam_loop.hip the type)
+void** loam_loopstore_slot(pcm_ctx* c);
+void loam_loopstore_release(void* store);
 // the Scan Context store of a context (pcm_ctx::loam owns the pointer, loam_sc.hip the type)
 void** loam_scstore_slot(pcm_ctx* c);
 void loam_scstore_release(void* store);

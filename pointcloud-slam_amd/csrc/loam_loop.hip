@@ -1,0 +1,218 @@
+// loam_loop.hip -- loop verification on the device (include/pcm_amd.h, pcm_loam_loop_*): jueying_slam's performLoopClosure
+// (mapOptmization.cpp:619-733) from a detected pair of key frames to the loop factor.
+//
+// The live verifier of that function is pclomp::NormalDistributionsTransform (:683-697; the PCL ICP block is commented out), an
+// operator this library has (pclndt.hip and its solver), so a verification is a composition: the two near-key-frame clouds are
+// queued on the context's stream into device memory (loam_submap.hip's k_nd_* pass: pcm_loam_submap_near's clouds, bit for bit),
+// ONE wait brings their two counts back for the size gates (:652), and the clouds go as PCM_MEM_DEVICE buffers to a verifier
+// context -- a PCM_MODEL_NDT_OMP pcm_ctx the LOAM context owns, created by the first verification that gets this far, run on the
+// LOAM context's stream and released with it -- through the public pcm_set_target / pcm_set_source / pcm_align /
+// pcm_fitness_score, whose code is unchanged.  What the caller used to write by hand, the acceptance test (:693) and the
+// Eigen / GTSAM pose algebra of :706-725, is loam_loop.h, evaluated on the host.  Nothing of the LOAM context's own target, source,
+// key-frame store or Scan Context store is written.
+#include "host_util.h"
+#include "loam_device.h"
+#include "loam_loop.h"
+#include "loam_submap.h"
+
+#include <cfloat>
+#include <cstring>
+#include <new>
+
+using namespace pcm;
+using namespace pcm::loam;
+
+namespace {
+
+struct LoopStore {
+  pcm_ctx* verifier = nullptr;
+};
+
+int check_ctx_loop(pcm_ctx* c, LoopStore** ls) {
+  if (!c) return PCM_ERR_INVALID_ARGUMENT;
+  if (c->device < 0) return PCM_ERR_HIP;
+  if (c->cfg.model != PCM_MODEL_LOAM) { c->err = "pcm_loam_loop_* needs a context created with PCM_MODEL_LOAM"; return PCM_ERR_INVALID_ARGUMENT; }
+  void** slot = loam_loopstore_slot(c);
+  if (!slot) { c->err = "out of host memory"; return PCM_ERR_INTERNAL; }
+  if (!*slot) *slot = new (std::nothrow) LoopStore();
+  if (!*slot) { c->err = "out of host memory"; return PCM_ERR_INTERNAL; }
+  *ls = static_cast<LoopStore*>(*slot);
+  return PCM_OK;
+}
+
+int check_lparams(pcm_ctx* c, const pcm_loam_loop_params& p) {
+  if (p.history_search_num < 0) { c->err = "history_search_num must be >= 0"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (p.min_cur_points < 0 || p.min_prev_points < 0) { c->err = "min_cur_points and min_prev_points must be >= 0"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!(p.near_leaf >= 0.f) || !finite_f_3e38(p.near_leaf)) { c->err = "near_leaf must be >= 0 (0: no down-sampling)"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!(p.fitness_threshold == p.fitness_threshold)) { c->err = "fitness_threshold must be a number"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!(p.ndt_epsilon > 0.0) || !finite_d(p.ndt_epsilon)) { c->err = "ndt_epsilon must be > 0"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!(p.ndt_resolution > 0.f) || !finite_f(p.ndt_resolution)) { c->err = "ndt_resolution must be > 0"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (p.ndt_num_neighbors != 0 && p.ndt_num_neighbors != 1 && p.ndt_num_neighbors != 7 && p.ndt_num_neighbors != 27) {
+    c->err = "ndt_num_neighbors must be 0 (KDTREE), 1, 7 or 27"; return PCM_ERR_INVALID_ARGUMENT;
+  }
+  return PCM_OK;
+}
+
+// the verifier's settings: pclomp NDT's own defaults (35 iterations, step 0.1, outlier ratio 0.55: ndt_omp_impl.hpp:48,60-63)
+// under the three setters of :684-686
+void verifier_config(const pcm_loam_loop_params& p, pcm_config* g) {
+  pcm_default_config(g);
+  g->model = PCM_MODEL_NDT_OMP;
+  g->max_iterations = 35;
+  g->translation_eps = p.ndt_epsilon;
+  g->voxel_resolution = p.ndt_resolution;
+  g->num_neighbors = p.ndt_num_neighbors;
+}
+
+int ensure_verifier(pcm_ctx* c, LoopStore* S, const pcm_loam_loop_params& p) {
+  pcm_config g;
+  verifier_config(p, &g);
+  if (!S->verifier) {
+    pcm_ctx* v = pcm_create(c->device, &g);
+    if (!v) { c->err = "out of host memory"; return PCM_ERR_INTERNAL; }
+    if (v->device < 0) { c->err = "loop verifier: " + v->err; pcm_destroy(v); return PCM_ERR_HIP; }
+    S->verifier = v;
+  }
+  pcm_ctx* v = S->verifier;
+  if (v->stream != c->stream) {   // every step of a verification runs on the LOAM context's stream
+    const int rc = pcm_set_stream(v, c->stream);
+    if (rc != PCM_OK) { c->err = "loop verifier: " + v->err; return rc; }
+  }
+  if (std::memcmp(&v->cfg, &g, sizeof(g)) != 0) {
+    const int rc = pcm_set_config(v, &g);
+    if (rc != PCM_OK) { c->err = "loop verifier: " + v->err; return rc; }
+  }
+  return PCM_OK;
+}
+
+void clear_result(pcm_loam_loop_result* r, int key_cur, int key_pre) {
+  std::memset(r, 0, sizeof(*r));
+  r->key_cur = key_cur; r->key_pre = key_pre;
+  r->correction[0] = r->correction[5] = r->correction[10] = r->correction[15] = 1.f;
+}
+
+int verify(pcm_ctx* c, LoopStore* S, const pcm_loam_loop_params& p, int key_cur, int key_pre, pcm_loam_loop_result* out) {
+  const KeyPose* kp = nullptr;
+  const int K = loam_keyposes(c, &kp);
+  if (K <= 0) { c->err = "pcm_loam_loop_verify: the key-frame store is empty"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (key_cur < 0 || key_cur >= K || key_pre < 0 || key_pre >= K) { c->err = "pcm_loam_loop_verify: key outside [0, K)"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (p.wrt_key >= K) { c->err = "pcm_loam_loop_verify: wrt_key outside [0, K)"; return PCM_ERR_INVALID_ARGUMENT; }
+  float pose_cur[6], pose_pre[6];
+  if (!loam_keyframe_pose(c, key_cur, pose_cur) || !loam_keyframe_pose(c, key_pre, pose_pre)) { c->err = "pcm_loam_loop_verify: no such key frame"; return PCM_ERR_INTERNAL; }
+  pcm_loam_loop_result r;
+  clear_result(&r, key_cur, key_pre);
+  // :650-651 loopFindNearKeyframes(cure, loopKeyCur, 0) and (prev, loopKeyPre, historyKeyframeSearchNum), both queued, one wait
+  NearCloud cur{}, prev{};
+  int rc = loam_near_queue(c, 0, key_cur, 0, p.wrt_key, p.near_leaf, &cur);
+  if (rc != PCM_OK) return rc;
+  if ((rc = loam_near_queue(c, 1, key_pre, p.history_search_num, p.wrt_key, p.near_leaf, &prev)) != PCM_OK) return rc;
+  if (cur.pts || prev.pts) {
+    PCM_HIPCK(c, hipStreamSynchronize(c->stream));
+    loam_near_waited(c);
+  }
+  if ((cur.pts && cur.h_small[2]) || (prev.pts && prev.h_small[2])) { c->err = "near_leaf too small for the extent of the cloud (index overflow)"; return PCM_ERR_OUT_OF_RANGE; }
+  const uint32_t n_cur = cur.pts ? cur.h_small[0] : 0u, n_prev = prev.pts ? prev.h_small[0] : 0u;
+  r.num_cur_points = (int32_t)n_cur;
+  r.num_prev_points = (int32_t)n_prev;
+  if (!loop::size_gate(n_cur, n_prev, p.min_cur_points, p.min_prev_points) || n_cur == 0 || n_prev == 0) {   // :652 (an empty cloud cannot be registered)
+    r.status = PCM_LOAM_LOOP_REJECTED_SIZE;
+    *out = r;
+    return PCM_OK;
+  }
+  if ((rc = ensure_verifier(c, S, p)) != PCM_OK) return rc;
+  pcm_ctx* v = S->verifier;
+  // :688-691 setInputSource(cure), setInputTarget(prev), align(*unused): no guess = the identity
+  const float I[16] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f};
+  pcm_result ar;
+  std::memset(&ar, 0, sizeof(ar));
+  double fitness = 0.0;
+  rc = pcm_set_target(v, prev.pts, n_prev, sizeof(float4), PCM_MEM_DEVICE, 0);
+  if (rc == PCM_OK) rc = pcm_set_source(v, cur.pts, n_cur, sizeof(float4), PCM_MEM_DEVICE, 0);   // used in place: the workspace outlives the call
+  if (rc == PCM_OK) { rc = pcm_align(v, I, &ar); if (rc == PCM_ERR_NOT_CONVERGED) rc = PCM_OK; }
+  if (rc == PCM_OK) rc = pcm_fitness_score(v, ar.T, DBL_MAX, &fitness);   // :693 getFitnessScore(): max_range = the largest double
+  (void)pcm_clear_source(v);   // the verifier keeps no pointer into the workspace
+  if (rc != PCM_OK) { c->err = "loop verifier: " + v->err; return rc; }
+  r.ndt_iterations = ar.iterations;
+  r.ndt_converged = ar.converged;
+  r.fitness = fitness;
+  r.noise_variance = (float)fitness;   // :719
+  std::memcpy(r.correction, ar.T, sizeof(r.correction));
+  r.status = loop::accept_status(ar.converged, fitness, p.fitness_threshold);
+  if (r.status == PCM_LOAM_LOOP_ACCEPTED) loop::loop_factor(r.correction, pose_cur, pose_pre, r.pose_from, r.pose_to, r.between, r.between6);
+  *out = r;
+  return PCM_OK;
+}
+
+static_assert(PCM_LOAM_LOOP_ACCEPTED == loop::kAccepted && PCM_LOAM_LOOP_REJECTED_SIZE == loop::kRejectedSize && PCM_LOAM_LOOP_REJECTED_NOT_CONVERGED == loop::kRejectedNotConverged &&
+                  PCM_LOAM_LOOP_REJECTED_FITNESS == loop::kRejectedFitness && PCM_LOAM_LOOP_NONE == loop::kNoLoop,
+              "status codes");
+
+}  // namespace
+
+namespace pcm {
+namespace loam {
+void loam_loopstore_release(void* store) {
+  LoopStore* S = static_cast<LoopStore*>(store);
+  if (!S) return;
+  if (S->verifier) pcm_destroy(S->verifier);
+  delete S;
+}
+}  // namespace loam
+}  // namespace pcm
+
+extern "C" {
+
+void pcm_loam_default_loop_params(pcm_loam_loop_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->history_search_num = 25;    // utility.h:290
+  p->min_cur_points = 300;       // mapOptmization.cpp:652
+  p->min_prev_points = 1000;     // mapOptmization.cpp:652
+  p->wrt_key = -1;               // :650-651 loopFindNearKeyframes
+  p->fitness_threshold = 0.3f;   // utility.h:291
+  p->near_leaf = 0.2f;           // mapOptmization.cpp:243 (utility.h:272)
+  p->ndt_epsilon = 0.01;         // mapOptmization.cpp:684
+  p->ndt_resolution = 1.0f;      // mapOptmization.cpp:685
+  p->ndt_num_neighbors = 7;      // mapOptmization.cpp:686 DIRECT7
+}
+
+int pcm_loam_loop_verify(pcm_ctx* c, const pcm_loam_loop_params* params, int key_cur, int key_pre, pcm_loam_loop_result* result) {
+  LoopStore* S = nullptr;
+  int rc = check_ctx_loop(c, &S);
+  if (rc != PCM_OK) return rc;
+  if (!result) { c->err = "null result"; return PCM_ERR_INVALID_ARGUMENT; }
+  pcm_loam_loop_params p;
+  if (params) p = *params; else pcm_loam_default_loop_params(&p);
+  if ((rc = check_lparams(c, p)) != PCM_OK) return rc;
+  PCM_HIPCK(c, hipSetDevice(c->device));
+  return verify(c, S, p, key_cur, key_pre, result);
+}
+
+int pcm_loam_loop_closure(pcm_ctx* c, const pcm_loam_loop_params* params, float radius, double time_diff_s, double time_cur, pcm_loam_loop_result* result) {
+  LoopStore* S = nullptr;
+  int rc = check_ctx_loop(c, &S);
+  if (rc != PCM_OK) return rc;
+  if (!result) { c->err = "null result"; return PCM_ERR_INVALID_ARGUMENT; }
+  pcm_loam_loop_params p;
+  if (params) p = *params; else pcm_loam_default_loop_params(&p);
+  if ((rc = check_lparams(c, p)) != PCM_OK) return rc;
+  int32_t key_cur = -1, key_pre = -1;
+  rc = pcm_loam_loop_detect_distance(c, radius, time_diff_s, time_cur, &key_cur, &key_pre);   // :638
+  if (rc < 0) return rc;
+  if (rc == 0) {   // :641-643
+    clear_result(result, -1, -1);
+    result->status = PCM_LOAM_LOOP_NONE;
+    return PCM_OK;
+  }
+  PCM_HIPCK(c, hipSetDevice(c->device));
+  return verify(c, S, p, key_cur, key_pre, result);
+}
+
+int pcm_loam_loop_verifier_exists(pcm_ctx* c) {
+  LoopStore* S = nullptr;
+  int rc = check_ctx_loop(c, &S);
+  if (rc != PCM_OK) return rc;
+  return S->verifier ? 1 : 0;
+}
+
+}  // extern "C"

@@ -15,9 +15,19 @@
 // updates of the same state give the same bits.
 // laserCloudMapContainer (the reference's cache of transformed clouds) never changes a result and is not kept: when the selection,
 // the poses and the leaves equal those of the previous update the call does nothing at all, which is the common case at LiDAR rate.
+// Near-key-frame cloud with a device result (pcm_loam_submap_near_dev; the clouds pcm_loam_loop_verify feeds its NDT with): the
+// k_nd_* kernels below -- the same selection, transform, order and VoxelGrid as pcm_loam_submap_near's pass with its one segment,
+// bit for bit, in fewer launches: the box is derived inside the key kernel, the keys are 32 bits wide (half the radix passes; the
+// sort stays stable, so a cell's run keeps its input order and its sum its bits), the cell heads are scanned on the fly instead of
+// being stored, head positions and totals come from one kernel, and without a leaf the gather writes the result itself.
 #include "host_util.h"
 #include "loam_device.h"
 #include "loam_submap.h"
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
 
 #include <cstring>
 #include <new>
@@ -121,6 +131,143 @@ __global__ void k_sm_store_source(const float4* __restrict__ feats, const float4
   if (i < n_c) dst_c[i] = p; else dst_s[i - n_c] = p;
 }
 
+// ---- near-key-frame cloud, device result ----------------------------------------------------------------------------------------
+constexpr uint32_t kNdInvalid = 0x80000000u;   // key of a point when the index overflows (a valid box has fewer than 2^31 cells)
+constexpr int kNdSmallWords = 3;               // [0] cells, [1] valid elements, [2] index overflow
+
+__global__ void k_nd_clear(unsigned int* __restrict__ mm, uint32_t* __restrict__ small) {
+  const uint32_t t = threadIdx.x;
+  if (t < 3) { mm[t] = 0xffffffffu; mm[3 + t] = 0u; small[t] = 0u; }
+}
+
+// k_sm_gather for one segment.  kDirect (no leaf): every point is its own cell, and the mean of one value v is
+// (float)((0.0 + (double)v) / 1.0): v itself with a negative zero turned positive, which v + 0.0f is as well; the lane writes that
+// to the result and nothing else runs.
+template <bool kDirect>
+__global__ void __launch_bounds__(256) k_nd_gather(const float4* __restrict__ corner_arena, const float4* __restrict__ surf_arena, const float* __restrict__ mats,
+                                                   const SmEntry* __restrict__ ent, uint32_t n_ent, uint32_t N, float4* __restrict__ out,
+                                                   unsigned int* __restrict__ mm) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = g < N;
+  const uint32_t gg = valid ? g : N - 1;
+  uint32_t lo = 0, hi = n_ent;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (ent[mid].first <= gg) lo = mid; else hi = mid;
+  }
+  const SmEntry e = ent[lo];
+  const float4* __restrict__ arena = (e.flags & 1u) ? surf_arena : corner_arena;
+  const float4 p = arena[(size_t)e.src + (gg - e.first)];
+  const float* __restrict__ T = mats + 12 * (size_t)e.mat;
+  float4 q;
+  q.x = T[0] * p.x + T[1] * p.y + T[2] * p.z + T[3];
+  q.y = T[4] * p.x + T[5] * p.y + T[6] * p.z + T[7];
+  q.z = T[8] * p.x + T[9] * p.y + T[10] * p.z + T[11];
+  q.w = p.w;
+  if (kDirect) {
+    if (valid) out[g] = make_float4(q.x + 0.0f, q.y + 0.0f, q.z + 0.0f, q.w + 0.0f);
+  } else {
+    if (valid) out[g] = q;
+    sv_wave_minmax(valid, 0u, q, mm);
+  }
+}
+
+// k_sm_boxes + k_sm_keys: every workgroup derives the box from the finished min / max (a few dozen operations of one lane)
+__global__ void __launch_bounds__(256) k_nd_keys(const float4* __restrict__ in, uint32_t N, float leaf, const unsigned int* __restrict__ mm,
+                                                 uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ small) {
+  __shared__ long long box[6];
+  if (threadIdx.x == 0) {
+    const bool over = sv_box(mm, leaf, box);
+    if (over && blockIdx.x == 0) small[2] = 1u;
+  }
+  __syncthreads();
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= N) return;
+  keys[g] = box[5] == 2 ? (uint32_t)sv_cell(in[g], leaf, box) : kNdInvalid;
+  vals[g] = g;
+}
+
+// 1 where a cell begins in the sorted keys (k_sv_heads), evaluated by the scan itself
+struct NdHead {
+  const uint32_t* keys;
+  __host__ __device__ uint32_t operator()(uint32_t i) const {
+    const uint32_t k = keys[i];
+    return (k != kNdInvalid && (i == 0 || keys[i - 1] != k)) ? 1u : 0u;
+  }
+};
+
+// k_sv_head_pos + k_sv_count: cell c starts at sorted element pos[c]; the last valid element gives the totals
+__global__ void k_nd_pos(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ slot, uint32_t N, uint32_t* __restrict__ pos, uint32_t* __restrict__ small) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const uint32_t k = keys[i];
+  if (k == kNdInvalid) return;
+  const uint32_t head = (i == 0 || keys[i - 1] != k) ? 1u : 0u;
+  if (head) pos[slot[i]] = i;
+  if (i + 1 == N || keys[i + 1] == kNdInvalid) { small[0] = slot[i] + head; small[1] = i + 1; }
+}
+
+// k_sm_average with one output
+__global__ void __launch_bounds__(256) k_nd_average(const float4* __restrict__ in, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ pos,
+                                                    const uint32_t* __restrict__ small, float4* __restrict__ out) {
+  const uint32_t ncells = small[0], nvalid = small[1];
+  const uint32_t lane = threadIdx.x & 63;
+  for (uint32_t cell = blockIdx.x * 4 + (threadIdx.x >> 6); cell < ncells; cell += gridDim.x * 4) {
+    const uint32_t b = pos[cell], e = cell + 1 < ncells ? pos[cell + 1] : nvalid;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (uint32_t j = b + lane; j < e; j += 64) {
+      const float4 q = in[vals[j]];
+      acc[0] += (double)q.x; acc[1] += (double)q.y; acc[2] += (double)q.z; acc[3] += (double)q.w;
+    }
+    for (int k = 0; k < 4; k++) acc[k] = wave_sum_f64(acc[k]);
+    if (lane == 0) {
+      const double m = (double)(e - b);
+      out[cell] = make_float4((float)(acc[0] / m), (float)(acc[1] / m), (float)(acc[2] / m), (float)(acc[3] / m));
+    }
+  }
+}
+
+// device workspace of one such pass; two of them, so that the two clouds of a loop verification are in flight together
+struct NdWork {
+  DevBuf<char> buf;
+  size_t n_cap = 0, ent_cap = 0;
+  size_t o_in = 0, o_cells = 0, o_keys = 0, o_keys_s = 0, o_vals = 0, o_vals_s = 0, o_slot = 0, o_mm = 0, o_small = 0, o_ent = 0, o_tmp = 0, o_tmp2 = 0,
+         tmp_bytes = 0, tmp2_bytes = 0;
+  PinnedBuf<uint32_t> h_small;
+  PinnedBuf<SmEntry> h_ent;
+  bool in_flight = false;   // the last pass was left without a wait: its staging is not free yet
+
+  float4* in() const { return reinterpret_cast<float4*>(buf.p + o_in); }
+  float4* cells() const { return reinterpret_cast<float4*>(buf.p + o_cells); }
+};
+
+int nd_ensure_work(pcm_ctx* c, NdWork* W, size_t N, size_t n_ent) {
+  int rc = W->h_small.reserve(c, kNdSmallWords, kNdSmallWords);
+  if (rc != PCM_OK) return rc;
+  if (n_ent > W->h_ent.cap && (rc = W->h_ent.reserve(c, n_ent, n_ent + n_ent / 2 + 16)) != PCM_OK) return rc;
+  if (W->buf && N <= W->n_cap && n_ent <= W->ent_cap) return PCM_OK;
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
+  W->buf.release();
+  W->n_cap = W->ent_cap = 0;
+  const size_t nc = N + N / 4 + 1024, ec = W->h_ent.cap;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t r = o; o += up256(bytes); return r; };
+  W->o_in = take(16 * nc); W->o_cells = take(16 * nc);
+  W->o_keys = take(4 * nc); W->o_keys_s = take(4 * nc); W->o_vals = take(4 * nc); W->o_vals_s = take(4 * nc); W->o_slot = take(4 * nc);
+  W->o_mm = take(4 * 6); W->o_small = take(4 * kNdSmallWords);
+  W->o_ent = take(sizeof(SmEntry) * ec);
+  {
+    uint32_t* k = nullptr;
+    (void)rocprim::radix_sort_pairs(nullptr, W->tmp_bytes, k, k, k, k, nc, 0, 32, nullptr);
+    auto heads = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0u), NdHead{k});
+    (void)rocprim::exclusive_scan(nullptr, W->tmp2_bytes, heads, k, 0u, nc, rocprim::plus<uint32_t>(), nullptr);
+  }
+  W->o_tmp = take(W->tmp_bytes); W->o_tmp2 = take(W->tmp2_bytes);
+  if ((rc = W->buf.reserve(c, o, o)) != PCM_OK) return rc;
+  W->n_cap = nc; W->ent_cap = ec;
+  return PCM_OK;
+}
+
 // device workspace of one gather + VoxelGrid pass
 struct SmWork {
   DevBuf<char> buf;
@@ -180,6 +327,7 @@ struct KeyStore {
   DevBuf<float> mats{"key-frame matrices"};   // [K][12]
   uint64_t gen = 1;          // bumps whenever a key frame or a pose changes
   SmWork upd, near;
+  NdWork ndev[2];            // device-result near clouds ([0] also pcm_loam_submap_near_dev)
   // the last update
   bool last_valid = false;
   uint64_t last_gen = 0;
@@ -265,6 +413,75 @@ int check_sparams(pcm_ctx* c, const pcm_loam_submap_params& p) {
   return PCM_OK;
 }
 
+// the arguments pcm_loam_submap_near checks, for a store of K >= 1 key frames
+int nd_check_args(pcm_ctx* c, int K, int key, int search_num, int wrt_key, float leaf, const char* who) {
+  if (search_num < 0) { c->err = "search_num must be >= 0"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!(leaf >= 0.f) || !finite_f_3e38(leaf)) { c->err = "leaf must be >= 0 (0: no down-sampling)"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (key < 0 || key >= K) { c->err = std::string(who) + ": key outside [0, K)"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (wrt_key >= K) { c->err = std::string(who) + ": wrt_key outside [0, K)"; return PCM_ERR_INVALID_ARGUMENT; }
+  return PCM_OK;
+}
+
+int nd_count_points(pcm_ctx* c, const KeyStore* S, const std::vector<int32_t>& keys, uint32_t* N) {
+  uint64_t N64 = 0;
+  for (int32_t k : keys) N64 += (uint64_t)S->kf[(size_t)k].n_c + S->kf[(size_t)k].n_s;
+  if (N64 > 0x7fffffffull) { c->err = "the selected key frames hold more than 2^31 points"; return PCM_ERR_OUT_OF_RANGE; }
+  *N = (uint32_t)N64;
+  return PCM_OK;
+}
+
+// Queues the near cloud of `keys` (N >= 1 points) on the context's stream and does not wait.  leaf > 0: the cells go to `dst` (room
+// for N; null: the workspace's cell array) and the totals to W->h_small once the stream has drained.  leaf == 0: the N points go
+// to dst and W->h_small holds the count at once.  *where = the array written.
+int nd_queue(pcm_ctx* c, KeyStore* S, NdWork* W, const std::vector<int32_t>& keys, int wrt_key, float leaf, uint32_t N, float4* dst, float4** where) {
+  hipStream_t st = c->stream;
+  const size_t E = 2 * keys.size();
+  int rc = nd_ensure_work(c, W, N, E);
+  if (rc != PCM_OK) return rc;
+  if (W->in_flight) { PCM_HIPCK(c, hipStreamSynchronize(st)); W->in_flight = false; }
+  uint32_t first = 0;
+  for (size_t i = 0; i < keys.size(); i++) {
+    const KeyFrame& k = S->kf[(size_t)keys[i]];
+    const uint32_t mat = wrt_key < 0 ? (uint32_t)keys[i] : (uint32_t)wrt_key;
+    W->h_ent[2 * i] = SmEntry{(uint32_t)k.off_c, first, mat, 0u};
+    first += k.n_c;
+    W->h_ent[2 * i + 1] = SmEntry{(uint32_t)k.off_s, first, mat, 1u};
+    first += k.n_s;
+  }
+  char* b = W->buf.p;
+  SmEntry* d_ent = reinterpret_cast<SmEntry*>(b + W->o_ent);
+  if (!dst) dst = W->cells();
+  *where = dst;
+  W->in_flight = true;
+  PCM_HIPCK(c, hipMemcpyAsync(d_ent, W->h_ent, sizeof(SmEntry) * E, hipMemcpyHostToDevice, st));
+  const unsigned nb = (N + 255) / 256;
+  if (!(leaf > 0.f)) {
+    k_nd_gather<true><<<nb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, d_ent, (uint32_t)E, N, dst, nullptr);
+    PCM_HIPCK(c, hipGetLastError());
+    W->h_small[0] = N; W->h_small[1] = N; W->h_small[2] = 0u;
+    return PCM_OK;
+  }
+  unsigned int* mm = reinterpret_cast<unsigned int*>(b + W->o_mm);
+  uint32_t* small = reinterpret_cast<uint32_t*>(b + W->o_small);
+  uint32_t* keys_u = reinterpret_cast<uint32_t*>(b + W->o_keys); uint32_t* keys_s = reinterpret_cast<uint32_t*>(b + W->o_keys_s);
+  uint32_t* vals = reinterpret_cast<uint32_t*>(b + W->o_vals); uint32_t* vals_s = reinterpret_cast<uint32_t*>(b + W->o_vals_s);
+  uint32_t* slot = reinterpret_cast<uint32_t*>(b + W->o_slot);
+  k_nd_clear<<<1, 64, 0, st>>>(mm, small);
+  k_nd_gather<false><<<nb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, d_ent, (uint32_t)E, N, W->in(), mm);
+  k_nd_keys<<<nb, 256, 0, st>>>(W->in(), N, leaf, mm, keys_u, vals, small);
+  PCM_HIPCK(c, hipGetLastError());
+  size_t tb = W->tmp_bytes, tb2 = W->tmp2_bytes;
+  PCM_HIPCK(c, rocprim::radix_sort_pairs(b + W->o_tmp, tb, keys_u, keys_s, vals, vals_s, (size_t)N, 0, 32, st));
+  auto heads = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0u), NdHead{keys_s});
+  PCM_HIPCK(c, rocprim::exclusive_scan(b + W->o_tmp2, tb2, heads, slot, 0u, (size_t)N, rocprim::plus<uint32_t>(), st));
+  k_nd_pos<<<nb, 256, 0, st>>>(keys_s, slot, N, vals, small);   // vals is free after the sort: it takes the cell starts
+  const unsigned gb = std::min<unsigned>(1024u, (N + 3) / 4);
+  k_nd_average<<<gb, 256, 0, st>>>(W->in(), vals_s, vals, small, dst);
+  PCM_HIPCK(c, hipGetLastError());
+  PCM_HIPCK(c, hipMemcpyAsync(W->h_small, small, sizeof(uint32_t) * kNdSmallWords, hipMemcpyDeviceToHost, st));
+  return PCM_OK;
+}
+
 }  // namespace
 
 namespace pcm {
@@ -298,6 +515,31 @@ int loam_keyposes(pcm_ctx* c, const KeyPose** kp) {
   const KeyStore* S = slot ? static_cast<const KeyStore*>(*slot) : nullptr;
   *kp = S ? S->kp.data() : nullptr;
   return S ? (int)S->kf.size() : 0;
+}
+int loam_near_queue(pcm_ctx* c, int slot, int key, int search_num, int wrt_key, float leaf, NearCloud* out) {
+  KeyStore* S = nullptr;
+  int rc = check_ctx_sm(c, &S);
+  if (rc != PCM_OK) return rc;
+  out->pts = nullptr; out->n_in = 0; out->h_small = nullptr;
+  const int K = (int)S->kf.size();
+  if (K == 0) { c->err = "the key-frame store is empty"; return PCM_ERR_INVALID_ARGUMENT; }
+  if ((rc = nd_check_args(c, K, key, search_num, wrt_key, leaf, "pcm_loam_loop_verify")) != PCM_OK) return rc;
+  const std::vector<int32_t> keys = select_near(K, key, search_num);
+  uint32_t N = 0;
+  if ((rc = nd_count_points(c, S, keys, &N)) != PCM_OK) return rc;
+  if (N == 0) return PCM_OK;   // every selected cloud is empty
+  PCM_HIPCK(c, hipSetDevice(c->device));
+  NdWork* W = &S->ndev[slot ? 1 : 0];
+  float4* where = nullptr;
+  if ((rc = nd_queue(c, S, W, keys, wrt_key, leaf, N, nullptr, &where)) != PCM_OK) return rc;
+  out->pts = where; out->n_in = N; out->h_small = W->h_small;
+  return PCM_OK;
+}
+
+void loam_near_waited(pcm_ctx* c) {
+  void** slot = loam_keystore_slot(c);
+  KeyStore* S = slot ? static_cast<KeyStore*>(*slot) : nullptr;
+  if (S) S->ndev[0].in_flight = S->ndev[1].in_flight = false;
 }
 }  // namespace loam
 }  // namespace pcm
@@ -550,6 +792,56 @@ int pcm_loam_submap_near(pcm_ctx* c, int key, int search_num, int wrt_key, float
     PCM_HIPCK(c, hipMemcpyAsync(out, cells, sizeof(float4) * m, hipMemcpyDeviceToHost, c->stream));
     PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   }
+  return PCM_OK;
+}
+
+int pcm_loam_submap_near_dev(pcm_ctx* c, int key, int search_num, int wrt_key, float leaf, void* out, size_t cap, int memory, size_t* n_out) {
+  KeyStore* S = nullptr;
+  int rc = check_ctx_sm(c, &S);
+  if (rc != PCM_OK) return rc;
+  if (n_out) *n_out = 0;
+  if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  const int K = (int)S->kf.size();
+  if (K == 0) {   // nothing to assemble, as pcm_loam_submap_near
+    if (search_num < 0) { c->err = "search_num must be >= 0"; return PCM_ERR_INVALID_ARGUMENT; }
+    if (!(leaf >= 0.f) || !finite_f_3e38(leaf)) { c->err = "leaf must be >= 0 (0: no down-sampling)"; return PCM_ERR_INVALID_ARGUMENT; }
+    return PCM_OK;
+  }
+  if ((rc = nd_check_args(c, K, key, search_num, wrt_key, leaf, "pcm_loam_submap_near_dev")) != PCM_OK) return rc;
+  const std::vector<int32_t> keys = select_near(K, key, search_num);
+  uint32_t N = 0;
+  if ((rc = nd_count_points(c, S, keys, &N)) != PCM_OK) return rc;
+  if (N == 0) return PCM_OK;
+  const char* too_small = "pcm_loam_submap_near_dev: capacity too small (the count is set)";
+  const bool counted = !(leaf > 0.f);   // without a leaf the count is known before anything runs
+  if (counted) {
+    if (n_out) *n_out = N;
+    if (N > cap || !out) { c->err = too_small; return PCM_ERR_INVALID_ARGUMENT; }
+  }
+  PCM_HIPCK(c, hipSetDevice(c->device));
+  NdWork* W = &S->ndev[0];
+  // a device buffer with room for every input point takes the result in place
+  const bool in_place = memory == PCM_MEM_DEVICE && out && cap >= N && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
+  float4* where = nullptr;
+  if ((rc = nd_queue(c, S, W, keys, wrt_key, leaf, N, in_place ? static_cast<float4*>(out) : nullptr, &where)) != PCM_OK) return rc;
+  size_t m = N;
+  if (!counted) {
+    PCM_HIPCK(c, hipStreamSynchronize(c->stream));   // the count has to come back
+    W->in_flight = false;
+    if (W->h_small[2]) { c->err = "leaf size too small for the extent of the cloud (index overflow)"; return PCM_ERR_OUT_OF_RANGE; }
+    m = W->h_small[0];
+    if (n_out) *n_out = m;
+    if (m > cap || (!out && m)) { c->err = too_small; return PCM_ERR_INVALID_ARGUMENT; }
+  }
+  if (in_place || m == 0) return PCM_OK;
+  if (memory == PCM_MEM_DEVICE) {
+    PCM_HIPCK(c, hipMemcpyAsync(out, where, sizeof(float4) * m, hipMemcpyDeviceToDevice, c->stream));
+    W->in_flight = true;
+    return PCM_OK;
+  }
+  PCM_HIPCK(c, hipMemcpyAsync(out, where, sizeof(float4) * m, hipMemcpyDeviceToHost, c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
+  W->in_flight = false;
   return PCM_OK;
 }
 

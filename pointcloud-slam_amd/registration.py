@@ -979,6 +979,102 @@ LoamRegistration.sc_distance = _loam_sc_distance
 LoamRegistration.detect_loop_distance = _loam_detect_loop_distance
 
 
+# ---- loop verification on the device (pcm_loam_loop_*) ----
+LOOP_STATUS = {capi.PCM_LOAM_LOOP_ACCEPTED: "accepted", capi.PCM_LOAM_LOOP_REJECTED_SIZE: "rejected_size",
+               capi.PCM_LOAM_LOOP_REJECTED_NOT_CONVERGED: "rejected_not_converged", capi.PCM_LOAM_LOOP_REJECTED_FITNESS: "rejected_fitness",
+               capi.PCM_LOAM_LOOP_NONE: "no_loop"}
+
+
+@dataclasses.dataclass
+class LoamLoopFactor:
+    """pcm_loam_loop_verify / pcm_loam_loop_closure: performLoopClosure's outcome for one pair.  ``status`` is one of LOOP_STATUS's
+    names; the factor (``between`` 4x4 float64 = poseFrom.between(poseTo), ``between6`` roll pitch yaw x y z, ``noise_variance``)
+    is meaningful when ``accepted``."""
+    status: str
+    key_cur: int
+    key_pre: int
+    num_cur_points: int
+    num_prev_points: int
+    iterations: int
+    converged: bool
+    fitness: float
+    noise_variance: float
+    correction: np.ndarray
+    pose_from: np.ndarray
+    pose_to: np.ndarray
+    between: np.ndarray
+    between6: np.ndarray
+
+    @property
+    def accepted(self) -> bool:
+        return self.status == "accepted"
+
+
+def _loop_params(L, params: dict) -> capi.PcmLoamLoopParams:
+    p = capi.PcmLoamLoopParams()
+    L.pcm_loam_default_loop_params(C.byref(p))
+    for k, v in params.items():
+        if k.startswith("reserved") or not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _loop_factor(r: capi.PcmLoamLoopResult) -> LoamLoopFactor:
+    return LoamLoopFactor(LOOP_STATUS[r.status], r.key_cur, r.key_pre, r.num_cur_points, r.num_prev_points, r.ndt_iterations, bool(r.ndt_converged),
+                          r.fitness, float(np.float32(r.noise_variance)), np.array(r.correction, np.float32).reshape(4, 4), np.array(r.pose_from),
+                          np.array(r.pose_to), np.array(r.between).reshape(4, 4), np.array(r.between6))
+
+
+def _loam_submap_near_device(self, key: int, search_num: int, wrt_key: int = -1, leaf: float = 0.2, out=None):
+    """pcm_loam_submap_near_dev: the cloud of ``near_keyframes``, bit for bit, as (x, y, z, intensity) rows of ``out`` -- a
+    contiguous (cap, 4) float32 device tensor (written on the context's stream; with leaf == 0 the call does not wait) or a
+    (cap, 4) float32 host array.  Returns the number of rows written."""
+    n = C.c_size_t(0)
+    if hasattr(out, "data_ptr") and getattr(out, "is_cuda", False):
+        if out.dim() != 2 or out.shape[1] != 4 or not out.is_contiguous() or out.element_size() != 4:
+            raise ValueError("expected a contiguous (cap, 4) float32 device tensor")
+        ptr, cap, mem = out.data_ptr(), out.shape[0], capi.MEM_DEVICE
+    else:
+        if not isinstance(out, np.ndarray) or out.dtype != np.float32 or out.ndim != 2 or out.shape[1] != 4 or not out.flags.c_contiguous:
+            raise ValueError("expected a contiguous (cap, 4) float32 array or device tensor")
+        ptr, cap, mem = out.ctypes.data, out.shape[0], capi.MEM_HOST
+    rc = self._L.pcm_loam_submap_near_dev(self._h, int(key), int(search_num), int(wrt_key), float(leaf), ptr, cap, mem, C.byref(n))
+    self._near_count = n.value
+    self._check(rc)
+    return n.value
+
+
+def _loam_loop_verify(self, key_cur: int, key_pre: int, **params) -> LoamLoopFactor:
+    """performLoopClosure :645-731 for the pair (pcm_loam_loop_verify): near clouds, size gates, pclomp NDT, fitness, loop factor."""
+    p = _loop_params(self._L, params)
+    r = capi.PcmLoamLoopResult()
+    self._check(self._L.pcm_loam_loop_verify(self._h, C.byref(p), int(key_cur), int(key_pre), C.byref(r)))
+    return _loop_factor(r)
+
+
+def _loam_loop_closure(self, time_cur, radius: float = 10.0, time_diff_s: float = 30.0, **params) -> LoamLoopFactor:
+    """detectLoopClosureDistance + verification in one call (pcm_loam_loop_closure); status "no_loop" without a candidate.  The
+    loopIndexContainer bookkeeping stays with the caller."""
+    p = _loop_params(self._L, params)
+    r = capi.PcmLoamLoopResult()
+    self._check(self._L.pcm_loam_loop_closure(self._h, C.byref(p), float(radius), float(time_diff_s), float(time_cur), C.byref(r)))
+    return _loop_factor(r)
+
+
+def _loam_loop_verifier_exists(self) -> bool:
+    n = self._L.pcm_loam_loop_verifier_exists(self._h)
+    if n < 0:
+        self._check(n)
+    return bool(n)
+
+
+LoamRegistration.submap_near_device = _loam_submap_near_device
+LoamRegistration.loop_verify = _loam_loop_verify
+LoamRegistration.loop_closure = _loam_loop_closure
+LoamRegistration.loop_verifier_exists = property(_loam_loop_verifier_exists)
+
+
 def loam_extract_features(reg: LoamRegistration, cloud, **feature_params):
     """One scan to (corner (Nc,4), surf (Ns,4), info): laserCloudCornerLastDS / laserCloudSurfLastDS as (x, y, z, intensity) on
     the host (pcm_loam_extract_features; the context's LOAM source is left as it is, its cross-frame state advances)."""
