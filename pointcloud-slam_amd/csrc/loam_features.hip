@@ -579,8 +579,7 @@ __global__ void __launch_bounds__(256) k_sv_average(const LfFrame* __restrict__ 
       const float4 q = elem_of<kStage>(F, p, f, vals[j] - base, cells1).pt;
       acc[0] += (double)q.x; acc[1] += (double)q.y; acc[2] += (double)q.z; acc[3] += (double)q.w;
     }
-    for (int k = 0; k < 4; k++)
-      for (int off = 32; off >= 1; off >>= 1) acc[k] += __shfl_xor(acc[k], off, 64);
+    for (int k = 0; k < 4; k++) acc[k] = loam::wave_sum_f64(acc[k]);
     if (lane == 0) {
       const double m = (double)(e - b);
       out[cell] = make_float4((float)(acc[0] / m), (float)(acc[1] / m), (float)(acc[2] / m), (float)(acc[3] / m));

@@ -3,7 +3,7 @@
 //
 // The live verifier of that function is pclomp::NormalDistributionsTransform (:683-697; the PCL ICP block is commented out), an
 // operator this library has (pclndt.hip and its solver), so a verification is a composition: the two near-key-frame clouds are
-// queued on the context's stream into device memory (loam_submap.hip's k_nd_* pass: pcm_loam_submap_near's clouds, bit for bit),
+// queued on the context's stream into device memory (loam_submap.hip's near pass: pcm_loam_submap_near's clouds),
 // ONE wait brings their two counts back for the size gates (:652), and the clouds go as PCM_MEM_DEVICE buffers to a verifier
 // context -- a PCM_MODEL_NDT_OMP pcm_ctx the LOAM context owns, created by the first verification that gets this far, run on the
 // LOAM context's stream and released with it -- through the public pcm_set_target / pcm_set_source / pcm_align /

@@ -15,11 +15,15 @@
 // updates of the same state give the same bits.
 // laserCloudMapContainer (the reference's cache of transformed clouds) never changes a result and is not kept: when the selection,
 // the poses and the leaves equal those of the previous update the call does nothing at all, which is the common case at LiDAR rate.
-// Near-key-frame cloud with a device result (pcm_loam_submap_near_dev; the clouds pcm_loam_loop_verify feeds its NDT with): the
-// k_nd_* kernels below -- the same selection, transform, order and VoxelGrid as pcm_loam_submap_near's pass with its one segment,
-// bit for bit, in fewer launches: the box is derived inside the key kernel, the keys are 32 bits wide (half the radix passes; the
-// sort stays stable, so a cell's run keeps its input order and its sum its bits), the cell heads are scanned on the fly instead of
-// being stored, head positions and totals come from one kernel, and without a leaf the gather writes the result itself.
+// Near-key-frame cloud (pcm_loam_submap_near, pcm_loam_submap_near_dev and the clouds pcm_loam_loop_verify feeds its NDT with):
+// one path, queue_near -- pcm_loam_submap_near is pcm_loam_submap_near_dev with a host buffer.  It is the update's pass with one
+// segment, bit for bit (tests/golden/loam_near_parent.json holds the clouds of the two-segment pass it replaced), in fewer
+// launches: the box is derived inside the key kernel, the keys are 32 bits wide (half the radix passes; the sort stays stable, so
+// a cell's run keeps its input order and its sum its bits), the cell heads are scanned on the fly instead of being stored, head
+// positions and totals come from one kernel, and without a leaf the gather writes the result itself.
+// The two passes share the entry table (build_entries), the gather and the average kernel and the workspace type, and stay two
+// pipelines on purpose: the update sorts 64-bit (segment, leaf) keys through sv_sort_cells, the near pass 32-bit keys.  One
+// pipeline for both would change the number of radix passes of one of them, and with it its speed.
 #include "host_util.h"
 #include "loam_device.h"
 #include "loam_submap.h"
@@ -51,6 +55,10 @@ struct SmEntry {
 // nearly every wave reads one entry and one matrix (wave-uniform addresses, served by one cache line); the arena read and the
 // output write are contiguous 16-byte accesses per lane.  transformPointCloud :462-466: T(r,0) x + T(r,1) y + T(r,2) z + T(r,3),
 // left to right in float (built with -ffp-contract=off), intensity copied.
+// kDirect (the near pass without a leaf): every point is its own cell, and the mean of one value v is
+// (float)((0.0 + (double)v) / 1.0): v itself with a negative zero turned positive, which v + 0.0f is as well; the lane writes that
+// to the result and nothing else runs.
+template <bool kDirect>
 __global__ void __launch_bounds__(256) k_sm_gather(const float4* __restrict__ corner_arena, const float4* __restrict__ surf_arena, const float* __restrict__ mats,
                                                    const SmEntry* __restrict__ ent, uint32_t n_ent, uint32_t N, float4* __restrict__ out,
                                                    unsigned int* __restrict__ mm) {
@@ -71,8 +79,12 @@ __global__ void __launch_bounds__(256) k_sm_gather(const float4* __restrict__ co
   q.y = T[4] * p.x + T[5] * p.y + T[6] * p.z + T[7];
   q.z = T[8] * p.x + T[9] * p.y + T[10] * p.z + T[11];
   q.w = p.w;
-  if (valid) out[g] = q;
-  sv_wave_minmax(valid, (e.flags >> 1) & 1u, q, mm);
+  if (kDirect) {
+    if (valid) out[g] = make_float4(q.x + 0.0f, q.y + 0.0f, q.z + 0.0f, q.w + 0.0f);
+  } else {
+    if (valid) out[g] = q;
+    sv_wave_minmax(valid, (e.flags >> 1) & 1u, q, mm);
+  }
 }
 
 // small: [0..1] cells per segment, [2..3] first cell, [4..7] totals (sv_sort_cells' nc), [8] index overflow
@@ -98,11 +110,13 @@ __global__ void k_sm_keys(const float4* __restrict__ in, uint32_t N, uint32_t n0
   vals[g] = g;
 }
 
-// one wave per cell (grid-stride): double sums of x, y, z, intensity over the cell's run (k_sv_average's scheme); the cells of
-// segment 0 go to out0, those of segment 1 to out1, each in leaf-index order
+// one wave per cell (grid-stride): double sums of x, y, z, intensity over the cell's run (k_sv_average's scheme); the first
+// *split_p cells (segment 0) go to out0, the others (segment 1) to out1, each in leaf-index order.  split_p == nullptr: one
+// segment, every cell to out0.
 __global__ void __launch_bounds__(256) k_sm_average(const float4* __restrict__ in, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ pos,
-                                                    const uint32_t* __restrict__ small, float4* __restrict__ out0, float4* __restrict__ out1) {
-  const uint32_t ncells = small[4], nvalid = small[5], n_seg0 = small[0];
+                                                    const uint32_t* __restrict__ ncells_p, const uint32_t* __restrict__ nvalid_p,
+                                                    const uint32_t* __restrict__ split_p, float4* __restrict__ out0, float4* __restrict__ out1) {
+  const uint32_t ncells = *ncells_p, nvalid = *nvalid_p, n_seg0 = split_p ? *split_p : ncells;
   const uint32_t lane = threadIdx.x & 63;
   for (uint32_t cell = blockIdx.x * 4 + (threadIdx.x >> 6); cell < ncells; cell += gridDim.x * 4) {
     const uint32_t b = pos[cell], e = cell + 1 < ncells ? pos[cell + 1] : nvalid;
@@ -131,45 +145,13 @@ __global__ void k_sm_store_source(const float4* __restrict__ feats, const float4
   if (i < n_c) dst_c[i] = p; else dst_s[i - n_c] = p;
 }
 
-// ---- near-key-frame cloud, device result ----------------------------------------------------------------------------------------
+// ---- near-key-frame pass: one segment, 32-bit keys ------------------------------------------------------------------------------
 constexpr uint32_t kNdInvalid = 0x80000000u;   // key of a point when the index overflows (a valid box has fewer than 2^31 cells)
 constexpr int kNdSmallWords = 3;               // [0] cells, [1] valid elements, [2] index overflow
 
 __global__ void k_nd_clear(unsigned int* __restrict__ mm, uint32_t* __restrict__ small) {
   const uint32_t t = threadIdx.x;
   if (t < 3) { mm[t] = 0xffffffffu; mm[3 + t] = 0u; small[t] = 0u; }
-}
-
-// k_sm_gather for one segment.  kDirect (no leaf): every point is its own cell, and the mean of one value v is
-// (float)((0.0 + (double)v) / 1.0): v itself with a negative zero turned positive, which v + 0.0f is as well; the lane writes that
-// to the result and nothing else runs.
-template <bool kDirect>
-__global__ void __launch_bounds__(256) k_nd_gather(const float4* __restrict__ corner_arena, const float4* __restrict__ surf_arena, const float* __restrict__ mats,
-                                                   const SmEntry* __restrict__ ent, uint32_t n_ent, uint32_t N, float4* __restrict__ out,
-                                                   unsigned int* __restrict__ mm) {
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool valid = g < N;
-  const uint32_t gg = valid ? g : N - 1;
-  uint32_t lo = 0, hi = n_ent;
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (ent[mid].first <= gg) lo = mid; else hi = mid;
-  }
-  const SmEntry e = ent[lo];
-  const float4* __restrict__ arena = (e.flags & 1u) ? surf_arena : corner_arena;
-  const float4 p = arena[(size_t)e.src + (gg - e.first)];
-  const float* __restrict__ T = mats + 12 * (size_t)e.mat;
-  float4 q;
-  q.x = T[0] * p.x + T[1] * p.y + T[2] * p.z + T[3];
-  q.y = T[4] * p.x + T[5] * p.y + T[6] * p.z + T[7];
-  q.z = T[8] * p.x + T[9] * p.y + T[10] * p.z + T[11];
-  q.w = p.w;
-  if (kDirect) {
-    if (valid) out[g] = make_float4(q.x + 0.0f, q.y + 0.0f, q.z + 0.0f, q.w + 0.0f);
-  } else {
-    if (valid) out[g] = q;
-    sv_wave_minmax(valid, 0u, q, mm);
-  }
 }
 
 // k_sm_boxes + k_sm_keys: every workgroup derives the box from the finished min / max (a few dozen operations of one lane)
@@ -207,68 +189,9 @@ __global__ void k_nd_pos(const uint32_t* __restrict__ keys, const uint32_t* __re
   if (i + 1 == N || keys[i + 1] == kNdInvalid) { small[0] = slot[i] + head; small[1] = i + 1; }
 }
 
-// k_sm_average with one output
-__global__ void __launch_bounds__(256) k_nd_average(const float4* __restrict__ in, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ pos,
-                                                    const uint32_t* __restrict__ small, float4* __restrict__ out) {
-  const uint32_t ncells = small[0], nvalid = small[1];
-  const uint32_t lane = threadIdx.x & 63;
-  for (uint32_t cell = blockIdx.x * 4 + (threadIdx.x >> 6); cell < ncells; cell += gridDim.x * 4) {
-    const uint32_t b = pos[cell], e = cell + 1 < ncells ? pos[cell + 1] : nvalid;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (uint32_t j = b + lane; j < e; j += 64) {
-      const float4 q = in[vals[j]];
-      acc[0] += (double)q.x; acc[1] += (double)q.y; acc[2] += (double)q.z; acc[3] += (double)q.w;
-    }
-    for (int k = 0; k < 4; k++) acc[k] = wave_sum_f64(acc[k]);
-    if (lane == 0) {
-      const double m = (double)(e - b);
-      out[cell] = make_float4((float)(acc[0] / m), (float)(acc[1] / m), (float)(acc[2] / m), (float)(acc[3] / m));
-    }
-  }
-}
-
-// device workspace of one such pass; two of them, so that the two clouds of a loop verification are in flight together
-struct NdWork {
-  DevBuf<char> buf;
-  size_t n_cap = 0, ent_cap = 0;
-  size_t o_in = 0, o_cells = 0, o_keys = 0, o_keys_s = 0, o_vals = 0, o_vals_s = 0, o_slot = 0, o_mm = 0, o_small = 0, o_ent = 0, o_tmp = 0, o_tmp2 = 0,
-         tmp_bytes = 0, tmp2_bytes = 0;
-  PinnedBuf<uint32_t> h_small;
-  PinnedBuf<SmEntry> h_ent;
-  bool in_flight = false;   // the last pass was left without a wait: its staging is not free yet
-
-  float4* in() const { return reinterpret_cast<float4*>(buf.p + o_in); }
-  float4* cells() const { return reinterpret_cast<float4*>(buf.p + o_cells); }
-};
-
-int nd_ensure_work(pcm_ctx* c, NdWork* W, size_t N, size_t n_ent) {
-  int rc = W->h_small.reserve(c, kNdSmallWords, kNdSmallWords);
-  if (rc != PCM_OK) return rc;
-  if (n_ent > W->h_ent.cap && (rc = W->h_ent.reserve(c, n_ent, n_ent + n_ent / 2 + 16)) != PCM_OK) return rc;
-  if (W->buf && N <= W->n_cap && n_ent <= W->ent_cap) return PCM_OK;
-  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
-  W->buf.release();
-  W->n_cap = W->ent_cap = 0;
-  const size_t nc = N + N / 4 + 1024, ec = W->h_ent.cap;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t r = o; o += up256(bytes); return r; };
-  W->o_in = take(16 * nc); W->o_cells = take(16 * nc);
-  W->o_keys = take(4 * nc); W->o_keys_s = take(4 * nc); W->o_vals = take(4 * nc); W->o_vals_s = take(4 * nc); W->o_slot = take(4 * nc);
-  W->o_mm = take(4 * 6); W->o_small = take(4 * kNdSmallWords);
-  W->o_ent = take(sizeof(SmEntry) * ec);
-  {
-    uint32_t* k = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, W->tmp_bytes, k, k, k, k, nc, 0, 32, nullptr);
-    auto heads = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0u), NdHead{k});
-    (void)rocprim::exclusive_scan(nullptr, W->tmp2_bytes, heads, k, 0u, nc, rocprim::plus<uint32_t>(), nullptr);
-  }
-  W->o_tmp = take(W->tmp_bytes); W->o_tmp2 = take(W->tmp2_bytes);
-  if ((rc = W->buf.reserve(c, o, o)) != PCM_OK) return rc;
-  W->n_cap = nc; W->ent_cap = ec;
-  return PCM_OK;
-}
-
-// device workspace of one gather + VoxelGrid pass
+// device workspace of one gather + VoxelGrid pass.  The update pass (segmented) sorts 64-bit keys and keeps the cell heads, two
+// boxes and the totals of two segments; its cells go to the context's target.  The near pass sorts 32-bit keys and owns a cell
+// array.  The near pass has two workspaces, so that the two clouds of a loop verification are in flight together.
 struct SmWork {
   DevBuf<char> buf;
   size_t n_cap = 0, ent_cap = 0;
@@ -276,14 +199,18 @@ struct SmWork {
          o_tmp = 0, o_tmp2 = 0, tmp_bytes = 0, tmp2_bytes = 0;
   PinnedBuf<uint32_t> h_small;
   PinnedBuf<SmEntry> h_ent;      // staging of the entry table
+  bool in_flight = false;        // the last near pass was left without a wait: its staging is not free yet
 
-  float4* in() const { return reinterpret_cast<float4*>(buf.p + o_in); }
-  float4* cells() const { return reinterpret_cast<float4*>(buf.p + o_cells); }
-  uint32_t* small() const { return reinterpret_cast<uint32_t*>(buf.p + o_small); }
+  template <class T> T* at(size_t off) const { return reinterpret_cast<T*>(buf.p + off); }
+  float4* in() const { return at<float4>(o_in); }
+  float4* cells() const { return at<float4>(o_cells); }
 };
 
-int ensure_work(pcm_ctx* c, SmWork* W, size_t N, size_t n_ent, bool want_cells) {
-  int rc = W->h_small.reserve(c, kSmallWords, kSmallWords);
+// room for N points and n_ent entries; keys of key_bytes each.  segmented: the head and box arrays and the second segment exist
+// and the cell array does not.
+int ensure_work(pcm_ctx* c, SmWork* W, size_t N, size_t n_ent, size_t key_bytes, bool segmented) {
+  const size_t words = segmented ? kSmallWords : kNdSmallWords;
+  int rc = W->h_small.reserve(c, words, words);
   if (rc != PCM_OK) return rc;
   if (n_ent > W->h_ent.cap && (rc = W->h_ent.reserve(c, n_ent, n_ent + n_ent / 2 + 16)) != PCM_OK) return rc;
   if (W->buf && N <= W->n_cap && n_ent <= W->ent_cap) return PCM_OK;
@@ -294,12 +221,19 @@ int ensure_work(pcm_ctx* c, SmWork* W, size_t N, size_t n_ent, bool want_cells) 
   size_t o = 0;
   auto take = [&](size_t bytes) { const size_t r = o; o += up256(bytes); return r; };
   W->o_in = take(16 * nc);
-  W->o_cells = take(want_cells ? 16 * nc : 16);
-  W->o_keys = take(8 * nc); W->o_keys_s = take(8 * nc);
-  W->o_vals = take(4 * nc); W->o_vals_s = take(4 * nc); W->o_head = take(4 * nc); W->o_slot = take(4 * nc);
-  W->o_mm = take(4 * 12); W->o_box = take(8 * 12); W->o_small = take(4 * kSmallWords);
+  W->o_cells = take(segmented ? 16 : 16 * nc);
+  W->o_keys = take(key_bytes * nc); W->o_keys_s = take(key_bytes * nc);
+  W->o_vals = take(4 * nc); W->o_vals_s = take(4 * nc); W->o_head = take(segmented ? 4 * nc : 0); W->o_slot = take(4 * nc);
+  W->o_mm = take(4 * 6 * (segmented ? 2 : 1)); W->o_box = take(segmented ? 8 * 12 : 0); W->o_small = take(4 * words);
   W->o_ent = take(sizeof(SmEntry) * ec);
-  sv_temp_bytes(nc, &W->tmp_bytes, &W->tmp2_bytes);
+  if (segmented) {
+    sv_temp_bytes(nc, &W->tmp_bytes, &W->tmp2_bytes);
+  } else {
+    uint32_t* k = nullptr;
+    (void)rocprim::radix_sort_pairs(nullptr, W->tmp_bytes, k, k, k, k, nc, 0, 32, nullptr);
+    auto heads = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0u), NdHead{k});
+    (void)rocprim::exclusive_scan(nullptr, W->tmp2_bytes, heads, k, 0u, nc, rocprim::plus<uint32_t>(), nullptr);
+  }
   W->o_tmp = take(W->tmp_bytes); W->o_tmp2 = take(W->tmp2_bytes);
   if ((rc = W->buf.reserve(c, o, o)) != PCM_OK) return rc;
   W->n_cap = nc; W->ent_cap = ec;
@@ -326,8 +260,8 @@ struct KeyStore {
   Arena arena[2];            // corner, surf
   DevBuf<float> mats{"key-frame matrices"};   // [K][12]
   uint64_t gen = 1;          // bumps whenever a key frame or a pose changes
-  SmWork upd, near;
-  NdWork ndev[2];            // device-result near clouds ([0] also pcm_loam_submap_near_dev)
+  SmWork upd;                // pcm_loam_submap_update
+  SmWork ndev[2];            // near clouds: [0] pcm_loam_submap_near, pcm_loam_submap_near_dev and slot 0 of loam_near_queue, [1] slot 1
   // the last update
   bool last_valid = false;
   uint64_t last_gen = 0;
@@ -370,33 +304,55 @@ int upload_matrices(pcm_ctx* c, KeyStore* S, size_t first, size_t n) {
   return PCM_OK;
 }
 
-// gather + segmented VoxelGrid of W->h_ent[0..n_ent): N points, the first n0 of them segment 0.  Cells of segment 0 -> out0, of
-// segment 1 -> out1; the counts and the overflow flag come back through W->h_small.
+// The entry table of `keys`, two rows per key frame, into ent.  wrt_key < 0: every key frame under its own pose; else all under
+// wrt_key's.  interleaved (near): corner, surf, corner, surf, ... in one segment; else (update) all corner clouds, then all surf
+// clouds as segment 1.
+void build_entries(const KeyStore* S, const std::vector<int32_t>& keys, int wrt_key, bool interleaved, SmEntry* ent) {
+  const size_t E = keys.size();
+  for (size_t i = 0; i < E; i++) {
+    const KeyFrame& k = S->kf[(size_t)keys[i]];
+    const uint32_t mat = wrt_key < 0 ? (uint32_t)keys[i] : (uint32_t)wrt_key;
+    ent[interleaved ? 2 * i : i] = SmEntry{(uint32_t)k.off_c, k.n_c, mat, 0u};                           // first: the count for now
+    ent[interleaved ? 2 * i + 1 : E + i] = SmEntry{(uint32_t)k.off_s, k.n_s, mat, interleaved ? 1u : 3u};
+  }
+  uint32_t first = 0;
+  for (size_t r = 0; r < 2 * E; r++) { const uint32_t n = ent[r].first; ent[r].first = first; first += n; }
+}
+
+// corner and surf points of `keys`; more than 2^31 - 1 together: PCM_ERR_OUT_OF_RANGE
+int count_points(pcm_ctx* c, const KeyStore* S, const std::vector<int32_t>& keys, uint64_t* n_c, uint64_t* n_s) {
+  *n_c = *n_s = 0;
+  for (int32_t k : keys) { *n_c += S->kf[(size_t)k].n_c; *n_s += S->kf[(size_t)k].n_s; }
+  if (*n_c + *n_s > 0x7fffffffull) { c->err = "the selected key frames hold more than 2^31 points"; return PCM_ERR_OUT_OF_RANGE; }
+  return PCM_OK;
+}
+
+// the update's pass: gather + segmented VoxelGrid of W->h_ent[0..n_ent): N points, the first n0 of them segment 0.  Cells of
+// segment 0 -> out0, of segment 1 -> out1; the counts and the overflow flag come back through W->h_small.
 int run_pass(pcm_ctx* c, KeyStore* S, SmWork* W, size_t n_ent, uint32_t N, uint32_t n0, float leaf0, float leaf1, float4* out0, float4* out1) {
   hipStream_t st = c->stream;
-  char* b = W->buf.p;
-  SmEntry* d_ent = reinterpret_cast<SmEntry*>(b + W->o_ent);
-  unsigned int* mm = reinterpret_cast<unsigned int*>(b + W->o_mm);
-  long long* box = reinterpret_cast<long long*>(b + W->o_box);
-  uint32_t* small = W->small();
+  SmEntry* d_ent = W->at<SmEntry>(W->o_ent);
+  unsigned int* mm = W->at<unsigned int>(W->o_mm);
+  long long* box = W->at<long long>(W->o_box);
+  uint32_t* small = W->at<uint32_t>(W->o_small);
   SvWork V;
-  V.keys = reinterpret_cast<uint64_t*>(b + W->o_keys); V.keys_s = reinterpret_cast<uint64_t*>(b + W->o_keys_s);
-  V.vals = reinterpret_cast<uint32_t*>(b + W->o_vals); V.vals_s = reinterpret_cast<uint32_t*>(b + W->o_vals_s);
-  V.head = reinterpret_cast<uint32_t*>(b + W->o_head); V.slot = reinterpret_cast<uint32_t*>(b + W->o_slot);
+  V.keys = W->at<uint64_t>(W->o_keys); V.keys_s = W->at<uint64_t>(W->o_keys_s);
+  V.vals = W->at<uint32_t>(W->o_vals); V.vals_s = W->at<uint32_t>(W->o_vals_s);
+  V.head = W->at<uint32_t>(W->o_head); V.slot = W->at<uint32_t>(W->o_slot);
   V.scnt = small; V.sfirst = small + 2; V.nc = small + 4;
-  V.tmp = b + W->o_tmp; V.tmp_bytes = W->tmp_bytes; V.tmp2 = b + W->o_tmp2; V.tmp2_bytes = W->tmp2_bytes;
+  V.tmp = W->at<char>(W->o_tmp); V.tmp_bytes = W->tmp_bytes; V.tmp2 = W->at<char>(W->o_tmp2); V.tmp2_bytes = W->tmp2_bytes;
   PCM_HIPCK(c, hipMemcpyAsync(d_ent, W->h_ent, sizeof(SmEntry) * n_ent, hipMemcpyHostToDevice, st));
   PCM_HIPCK(c, hipMemsetAsync(small, 0, sizeof(uint32_t) * kSmallWords, st));
   sv_clear(st, mm, small, 2);
   const unsigned nb = (N + 255) / 256;
-  k_sm_gather<<<nb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, d_ent, (uint32_t)n_ent, N, W->in(), mm);
+  k_sm_gather<false><<<nb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, d_ent, (uint32_t)n_ent, N, W->in(), mm);
   k_sm_boxes<<<1, 64, 0, st>>>(mm, leaf0, leaf1, box, small);
   k_sm_keys<<<nb, 256, 0, st>>>(W->in(), N, n0, leaf0, leaf1, box, V.keys, V.vals);
   PCM_HIPCK(c, hipGetLastError());
   int rc = sv_sort_cells(c, st, V, N, 2);
   if (rc != PCM_OK) return rc;
   const unsigned gb = std::min<unsigned>(1024u, (N + 3) / 4);
-  k_sm_average<<<gb, 256, 0, st>>>(W->in(), V.vals_s, V.vals, small, out0, out1);
+  k_sm_average<<<gb, 256, 0, st>>>(W->in(), V.vals_s, V.vals, V.nc, V.nc + 1, V.scnt, out0, out1);
   PCM_HIPCK(c, hipGetLastError());
   PCM_HIPCK(c, hipMemcpyAsync(W->h_small, small, sizeof(uint32_t) * kSmallWords, hipMemcpyDeviceToHost, st));
   PCM_HIPCK(c, hipStreamSynchronize(st));
@@ -413,72 +369,105 @@ int check_sparams(pcm_ctx* c, const pcm_loam_submap_params& p) {
   return PCM_OK;
 }
 
-// the arguments pcm_loam_submap_near checks, for a store of K >= 1 key frames
-int nd_check_args(pcm_ctx* c, int K, int key, int search_num, int wrt_key, float leaf, const char* who) {
+// the arguments of a near cloud for a store of K key frames; K == 0 passes once search_num and leaf are sound (the entries then
+// decide what an empty store means)
+int check_near_args(pcm_ctx* c, int K, int key, int search_num, int wrt_key, float leaf, const char* who) {
   if (search_num < 0) { c->err = "search_num must be >= 0"; return PCM_ERR_INVALID_ARGUMENT; }
   if (!(leaf >= 0.f) || !finite_f_3e38(leaf)) { c->err = "leaf must be >= 0 (0: no down-sampling)"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (K == 0) return PCM_OK;
   if (key < 0 || key >= K) { c->err = std::string(who) + ": key outside [0, K)"; return PCM_ERR_INVALID_ARGUMENT; }
   if (wrt_key >= K) { c->err = std::string(who) + ": wrt_key outside [0, K)"; return PCM_ERR_INVALID_ARGUMENT; }
-  return PCM_OK;
-}
-
-int nd_count_points(pcm_ctx* c, const KeyStore* S, const std::vector<int32_t>& keys, uint32_t* N) {
-  uint64_t N64 = 0;
-  for (int32_t k : keys) N64 += (uint64_t)S->kf[(size_t)k].n_c + S->kf[(size_t)k].n_s;
-  if (N64 > 0x7fffffffull) { c->err = "the selected key frames hold more than 2^31 points"; return PCM_ERR_OUT_OF_RANGE; }
-  *N = (uint32_t)N64;
   return PCM_OK;
 }
 
 // Queues the near cloud of `keys` (N >= 1 points) on the context's stream and does not wait.  leaf > 0: the cells go to `dst` (room
 // for N; null: the workspace's cell array) and the totals to W->h_small once the stream has drained.  leaf == 0: the N points go
 // to dst and W->h_small holds the count at once.  *where = the array written.
-int nd_queue(pcm_ctx* c, KeyStore* S, NdWork* W, const std::vector<int32_t>& keys, int wrt_key, float leaf, uint32_t N, float4* dst, float4** where) {
+int queue_near(pcm_ctx* c, KeyStore* S, SmWork* W, const std::vector<int32_t>& keys, int wrt_key, float leaf, uint32_t N, float4* dst, float4** where) {
   hipStream_t st = c->stream;
   const size_t E = 2 * keys.size();
-  int rc = nd_ensure_work(c, W, N, E);
+  int rc = ensure_work(c, W, N, E, sizeof(uint32_t), false);
   if (rc != PCM_OK) return rc;
   if (W->in_flight) { PCM_HIPCK(c, hipStreamSynchronize(st)); W->in_flight = false; }
-  uint32_t first = 0;
-  for (size_t i = 0; i < keys.size(); i++) {
-    const KeyFrame& k = S->kf[(size_t)keys[i]];
-    const uint32_t mat = wrt_key < 0 ? (uint32_t)keys[i] : (uint32_t)wrt_key;
-    W->h_ent[2 * i] = SmEntry{(uint32_t)k.off_c, first, mat, 0u};
-    first += k.n_c;
-    W->h_ent[2 * i + 1] = SmEntry{(uint32_t)k.off_s, first, mat, 1u};
-    first += k.n_s;
-  }
-  char* b = W->buf.p;
-  SmEntry* d_ent = reinterpret_cast<SmEntry*>(b + W->o_ent);
+  build_entries(S, keys, wrt_key, true, W->h_ent);
+  SmEntry* d_ent = W->at<SmEntry>(W->o_ent);
   if (!dst) dst = W->cells();
   *where = dst;
   W->in_flight = true;
   PCM_HIPCK(c, hipMemcpyAsync(d_ent, W->h_ent, sizeof(SmEntry) * E, hipMemcpyHostToDevice, st));
   const unsigned nb = (N + 255) / 256;
   if (!(leaf > 0.f)) {
-    k_nd_gather<true><<<nb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, d_ent, (uint32_t)E, N, dst, nullptr);
+    k_sm_gather<true><<<nb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, d_ent, (uint32_t)E, N, dst, nullptr);
     PCM_HIPCK(c, hipGetLastError());
     W->h_small[0] = N; W->h_small[1] = N; W->h_small[2] = 0u;
     return PCM_OK;
   }
-  unsigned int* mm = reinterpret_cast<unsigned int*>(b + W->o_mm);
-  uint32_t* small = reinterpret_cast<uint32_t*>(b + W->o_small);
-  uint32_t* keys_u = reinterpret_cast<uint32_t*>(b + W->o_keys); uint32_t* keys_s = reinterpret_cast<uint32_t*>(b + W->o_keys_s);
-  uint32_t* vals = reinterpret_cast<uint32_t*>(b + W->o_vals); uint32_t* vals_s = reinterpret_cast<uint32_t*>(b + W->o_vals_s);
-  uint32_t* slot = reinterpret_cast<uint32_t*>(b + W->o_slot);
+  unsigned int* mm = W->at<unsigned int>(W->o_mm);
+  uint32_t* small = W->at<uint32_t>(W->o_small);
+  uint32_t* keys_u = W->at<uint32_t>(W->o_keys); uint32_t* keys_s = W->at<uint32_t>(W->o_keys_s);
+  uint32_t* vals = W->at<uint32_t>(W->o_vals); uint32_t* vals_s = W->at<uint32_t>(W->o_vals_s);
+  uint32_t* slot = W->at<uint32_t>(W->o_slot);
   k_nd_clear<<<1, 64, 0, st>>>(mm, small);
-  k_nd_gather<false><<<nb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, d_ent, (uint32_t)E, N, W->in(), mm);
+  k_sm_gather<false><<<nb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, d_ent, (uint32_t)E, N, W->in(), mm);
   k_nd_keys<<<nb, 256, 0, st>>>(W->in(), N, leaf, mm, keys_u, vals, small);
   PCM_HIPCK(c, hipGetLastError());
   size_t tb = W->tmp_bytes, tb2 = W->tmp2_bytes;
-  PCM_HIPCK(c, rocprim::radix_sort_pairs(b + W->o_tmp, tb, keys_u, keys_s, vals, vals_s, (size_t)N, 0, 32, st));
+  PCM_HIPCK(c, rocprim::radix_sort_pairs(W->at<char>(W->o_tmp), tb, keys_u, keys_s, vals, vals_s, (size_t)N, 0, 32, st));
   auto heads = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0u), NdHead{keys_s});
-  PCM_HIPCK(c, rocprim::exclusive_scan(b + W->o_tmp2, tb2, heads, slot, 0u, (size_t)N, rocprim::plus<uint32_t>(), st));
+  PCM_HIPCK(c, rocprim::exclusive_scan(W->at<char>(W->o_tmp2), tb2, heads, slot, 0u, (size_t)N, rocprim::plus<uint32_t>(), st));
   k_nd_pos<<<nb, 256, 0, st>>>(keys_s, slot, N, vals, small);   // vals is free after the sort: it takes the cell starts
   const unsigned gb = std::min<unsigned>(1024u, (N + 3) / 4);
-  k_nd_average<<<gb, 256, 0, st>>>(W->in(), vals_s, vals, small, dst);
+  k_sm_average<<<gb, 256, 0, st>>>(W->in(), vals_s, vals, small, small + 1, nullptr, dst, nullptr);
   PCM_HIPCK(c, hipGetLastError());
   PCM_HIPCK(c, hipMemcpyAsync(W->h_small, small, sizeof(uint32_t) * kNdSmallWords, hipMemcpyDeviceToHost, st));
+  return PCM_OK;
+}
+
+// pcm_loam_submap_near (memory = PCM_MEM_HOST) and pcm_loam_submap_near_dev, `who` in the error texts
+int near_cloud(pcm_ctx* c, const char* who, int key, int search_num, int wrt_key, float leaf, void* out, size_t cap, int memory, size_t* n_out) {
+  KeyStore* S = nullptr;
+  int rc = check_ctx_sm(c, &S);
+  if (rc != PCM_OK) return rc;
+  if (n_out) *n_out = 0;
+  if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  const int K = (int)S->kf.size();
+  if ((rc = check_near_args(c, K, key, search_num, wrt_key, leaf, who)) != PCM_OK) return rc;
+  if (K == 0) return PCM_OK;   // nothing to assemble
+  const std::vector<int32_t> keys = select_near(K, key, search_num);
+  uint64_t n_c = 0, n_s = 0;
+  if ((rc = count_points(c, S, keys, &n_c, &n_s)) != PCM_OK) return rc;
+  const uint32_t N = (uint32_t)(n_c + n_s);
+  if (N == 0) return PCM_OK;
+  const std::string too_small = std::string(who) + ": capacity too small (the count is set)";
+  const bool counted = !(leaf > 0.f);   // without a leaf the count is known before anything runs
+  if (counted) {
+    if (n_out) *n_out = N;
+    if (N > cap || !out) { c->err = too_small; return PCM_ERR_INVALID_ARGUMENT; }
+  }
+  PCM_HIPCK(c, hipSetDevice(c->device));
+  SmWork* W = &S->ndev[0];
+  // a device buffer with room for every input point takes the result in place
+  const bool in_place = memory == PCM_MEM_DEVICE && out && cap >= N && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
+  float4* where = nullptr;
+  if ((rc = queue_near(c, S, W, keys, wrt_key, leaf, N, in_place ? static_cast<float4*>(out) : nullptr, &where)) != PCM_OK) return rc;
+  size_t m = N;
+  if (!counted) {
+    PCM_HIPCK(c, hipStreamSynchronize(c->stream));   // the count has to come back
+    W->in_flight = false;
+    if (W->h_small[2]) { c->err = "leaf size too small for the extent of the cloud (index overflow)"; return PCM_ERR_OUT_OF_RANGE; }
+    m = W->h_small[0];
+    if (n_out) *n_out = m;
+    if (m > cap || (!out && m)) { c->err = too_small; return PCM_ERR_INVALID_ARGUMENT; }
+  }
+  if (in_place || m == 0) return PCM_OK;
+  if (memory == PCM_MEM_DEVICE) {
+    PCM_HIPCK(c, hipMemcpyAsync(out, where, sizeof(float4) * m, hipMemcpyDeviceToDevice, c->stream));
+    W->in_flight = true;
+    return PCM_OK;
+  }
+  PCM_HIPCK(c, hipMemcpyAsync(out, where, sizeof(float4) * m, hipMemcpyDeviceToHost, c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
+  W->in_flight = false;
   return PCM_OK;
 }
 
@@ -523,15 +512,16 @@ int loam_near_queue(pcm_ctx* c, int slot, int key, int search_num, int wrt_key, 
   out->pts = nullptr; out->n_in = 0; out->h_small = nullptr;
   const int K = (int)S->kf.size();
   if (K == 0) { c->err = "the key-frame store is empty"; return PCM_ERR_INVALID_ARGUMENT; }
-  if ((rc = nd_check_args(c, K, key, search_num, wrt_key, leaf, "pcm_loam_loop_verify")) != PCM_OK) return rc;
+  if ((rc = check_near_args(c, K, key, search_num, wrt_key, leaf, "pcm_loam_loop_verify")) != PCM_OK) return rc;
   const std::vector<int32_t> keys = select_near(K, key, search_num);
-  uint32_t N = 0;
-  if ((rc = nd_count_points(c, S, keys, &N)) != PCM_OK) return rc;
+  uint64_t n_c = 0, n_s = 0;
+  if ((rc = count_points(c, S, keys, &n_c, &n_s)) != PCM_OK) return rc;
+  const uint32_t N = (uint32_t)(n_c + n_s);
   if (N == 0) return PCM_OK;   // every selected cloud is empty
   PCM_HIPCK(c, hipSetDevice(c->device));
-  NdWork* W = &S->ndev[slot ? 1 : 0];
+  SmWork* W = &S->ndev[slot ? 1 : 0];
   float4* where = nullptr;
-  if ((rc = nd_queue(c, S, W, keys, wrt_key, leaf, N, nullptr, &where)) != PCM_OK) return rc;
+  if ((rc = queue_near(c, S, W, keys, wrt_key, leaf, N, nullptr, &where)) != PCM_OK) return rc;
   out->pts = where; out->n_in = N; out->h_small = W->h_small;
   return PCM_OK;
 }
@@ -710,26 +700,15 @@ int pcm_loam_submap_update(pcm_ctx* c, const pcm_loam_submap_params* params, dou
   S->last_valid = false;
   const size_t E = sel.keys.size();
   uint64_t n_c = 0, n_s = 0;
-  for (int32_t k : sel.keys) { n_c += S->kf[(size_t)k].n_c; n_s += S->kf[(size_t)k].n_s; }
-  if (n_c + n_s > 0x7fffffffull) { c->err = "the selected key frames hold more than 2^31 points"; return PCM_ERR_OUT_OF_RANGE; }
+  if ((rc = count_points(c, S, sel.keys, &n_c, &n_s)) != PCM_OK) return rc;
   float4 *out_c = nullptr, *out_s = nullptr;
   if ((rc = loam_target_reserve(c, (size_t)n_c, (size_t)n_s, &out_c, &out_s)) != PCM_OK) return rc;
   r.num_corner_in = (int32_t)n_c; r.num_surf_in = (int32_t)n_s;
   const uint32_t N = (uint32_t)(n_c + n_s);
-  if ((rc = ensure_work(c, &S->upd, N, 2 * E, false)) != PCM_OK) return rc;
+  if ((rc = ensure_work(c, &S->upd, N, 2 * E, sizeof(uint64_t), true)) != PCM_OK) return rc;
   if (N > 0) {
     PCM_HIPCK(c, hipStreamSynchronize(c->stream));   // the pinned staging of an earlier pass is free again
-    uint32_t first = 0;
-    for (size_t i = 0; i < E; i++) {
-      const KeyFrame& k = S->kf[(size_t)sel.keys[i]];
-      S->upd.h_ent[i] = SmEntry{(uint32_t)k.off_c, first, (uint32_t)sel.keys[i], 0u};
-      first += k.n_c;
-    }
-    for (size_t i = 0; i < E; i++) {
-      const KeyFrame& k = S->kf[(size_t)sel.keys[i]];
-      S->upd.h_ent[E + i] = SmEntry{(uint32_t)k.off_s, first, (uint32_t)sel.keys[i], 3u};
-      first += k.n_s;
-    }
+    build_entries(S, sel.keys, -1, false, S->upd.h_ent);
     if ((rc = run_pass(c, S, &S->upd, 2 * E, N, (uint32_t)n_c, p.corner_leaf, p.surf_leaf, out_c, out_s)) != PCM_OK) return rc;
     if (S->upd.h_small[8]) {
       r.status = PCM_ERR_OUT_OF_RANGE;
@@ -753,96 +732,11 @@ int pcm_loam_submap_update(pcm_ctx* c, const pcm_loam_submap_params* params, dou
 }
 
 int pcm_loam_submap_near(pcm_ctx* c, int key, int search_num, int wrt_key, float leaf, float* out, size_t cap, size_t* n_out) {
-  KeyStore* S = nullptr;
-  int rc = check_ctx_sm(c, &S);
-  if (rc != PCM_OK) return rc;
-  if (n_out) *n_out = 0;
-  const int K = (int)S->kf.size();
-  if (search_num < 0) { c->err = "search_num must be >= 0"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (!(leaf >= 0.f) || !finite_f_3e38(leaf)) { c->err = "leaf must be >= 0 (0: no down-sampling)"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (K == 0) return PCM_OK;   // nothing to assemble
-  if (key < 0 || key >= K) { c->err = "pcm_loam_submap_near: key outside [0, K)"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (wrt_key >= K) { c->err = "pcm_loam_submap_near: wrt_key outside [0, K)"; return PCM_ERR_INVALID_ARGUMENT; }
-  const std::vector<int32_t> keys = select_near(K, key, search_num);
-  uint64_t N64 = 0;
-  for (int32_t k : keys) N64 += (uint64_t)S->kf[(size_t)k].n_c + S->kf[(size_t)k].n_s;
-  if (N64 > 0x7fffffffull) { c->err = "the selected key frames hold more than 2^31 points"; return PCM_ERR_OUT_OF_RANGE; }
-  if (N64 == 0) return PCM_OK;
-  const uint32_t N = (uint32_t)N64;
-  PCM_HIPCK(c, hipSetDevice(c->device));
-  const size_t E = 2 * keys.size();
-  if ((rc = ensure_work(c, &S->near, N, E, true)) != PCM_OK) return rc;
-  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
-  uint32_t first = 0;
-  for (size_t i = 0; i < keys.size(); i++) {
-    const KeyFrame& k = S->kf[(size_t)keys[i]];
-    const uint32_t mat = wrt_key < 0 ? (uint32_t)keys[i] : (uint32_t)wrt_key;
-    S->near.h_ent[2 * i] = SmEntry{(uint32_t)k.off_c, first, mat, 0u};
-    first += k.n_c;
-    S->near.h_ent[2 * i + 1] = SmEntry{(uint32_t)k.off_s, first, mat, 1u};
-    first += k.n_s;
-  }
-  float4* cells = S->near.cells();
-  if ((rc = run_pass(c, S, &S->near, E, N, N, leaf, leaf, cells, cells)) != PCM_OK) return rc;
-  if (S->near.h_small[8]) { c->err = "leaf size too small for the extent of the cloud (index overflow)"; return PCM_ERR_OUT_OF_RANGE; }
-  const size_t m = S->near.h_small[0];
-  if (n_out) *n_out = m;
-  if (m > cap || (!out && m)) { c->err = "pcm_loam_submap_near: capacity too small (the count is set)"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (m) {
-    PCM_HIPCK(c, hipMemcpyAsync(out, cells, sizeof(float4) * m, hipMemcpyDeviceToHost, c->stream));
-    PCM_HIPCK(c, hipStreamSynchronize(c->stream));
-  }
-  return PCM_OK;
+  return near_cloud(c, "pcm_loam_submap_near", key, search_num, wrt_key, leaf, out, cap, PCM_MEM_HOST, n_out);
 }
 
 int pcm_loam_submap_near_dev(pcm_ctx* c, int key, int search_num, int wrt_key, float leaf, void* out, size_t cap, int memory, size_t* n_out) {
-  KeyStore* S = nullptr;
-  int rc = check_ctx_sm(c, &S);
-  if (rc != PCM_OK) return rc;
-  if (n_out) *n_out = 0;
-  if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
-  const int K = (int)S->kf.size();
-  if (K == 0) {   // nothing to assemble, as pcm_loam_submap_near
-    if (search_num < 0) { c->err = "search_num must be >= 0"; return PCM_ERR_INVALID_ARGUMENT; }
-    if (!(leaf >= 0.f) || !finite_f_3e38(leaf)) { c->err = "leaf must be >= 0 (0: no down-sampling)"; return PCM_ERR_INVALID_ARGUMENT; }
-    return PCM_OK;
-  }
-  if ((rc = nd_check_args(c, K, key, search_num, wrt_key, leaf, "pcm_loam_submap_near_dev")) != PCM_OK) return rc;
-  const std::vector<int32_t> keys = select_near(K, key, search_num);
-  uint32_t N = 0;
-  if ((rc = nd_count_points(c, S, keys, &N)) != PCM_OK) return rc;
-  if (N == 0) return PCM_OK;
-  const char* too_small = "pcm_loam_submap_near_dev: capacity too small (the count is set)";
-  const bool counted = !(leaf > 0.f);   // without a leaf the count is known before anything runs
-  if (counted) {
-    if (n_out) *n_out = N;
-    if (N > cap || !out) { c->err = too_small; return PCM_ERR_INVALID_ARGUMENT; }
-  }
-  PCM_HIPCK(c, hipSetDevice(c->device));
-  NdWork* W = &S->ndev[0];
-  // a device buffer with room for every input point takes the result in place
-  const bool in_place = memory == PCM_MEM_DEVICE && out && cap >= N && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
-  float4* where = nullptr;
-  if ((rc = nd_queue(c, S, W, keys, wrt_key, leaf, N, in_place ? static_cast<float4*>(out) : nullptr, &where)) != PCM_OK) return rc;
-  size_t m = N;
-  if (!counted) {
-    PCM_HIPCK(c, hipStreamSynchronize(c->stream));   // the count has to come back
-    W->in_flight = false;
-    if (W->h_small[2]) { c->err = "leaf size too small for the extent of the cloud (index overflow)"; return PCM_ERR_OUT_OF_RANGE; }
-    m = W->h_small[0];
-    if (n_out) *n_out = m;
-    if (m > cap || (!out && m)) { c->err = too_small; return PCM_ERR_INVALID_ARGUMENT; }
-  }
-  if (in_place || m == 0) return PCM_OK;
-  if (memory == PCM_MEM_DEVICE) {
-    PCM_HIPCK(c, hipMemcpyAsync(out, where, sizeof(float4) * m, hipMemcpyDeviceToDevice, c->stream));
-    W->in_flight = true;
-    return PCM_OK;
-  }
-  PCM_HIPCK(c, hipMemcpyAsync(out, where, sizeof(float4) * m, hipMemcpyDeviceToHost, c->stream));
-  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
-  W->in_flight = false;
-  return PCM_OK;
+  return near_cloud(c, "pcm_loam_submap_near_dev", key, search_num, wrt_key, leaf, out, cap, memory, n_out);
 }
 
 int pcm_loam_submap_info(pcm_ctx* c, int32_t* keys, float* corner_in, float* surf_in, float* corner_map, float* surf_map) {

@@ -1,6 +1,8 @@
 """GPU checks of loop verification on the device (pcm_loam_submap_near_dev, pcm_loam_loop_verify, pcm_loam_loop_closure):
 
-* the device near cloud equals pcm_loam_submap_near's host cloud bit for bit;
+* the near cloud -- pcm_loam_submap_near's host cloud and pcm_loam_submap_near_dev's, which are one device pass -- equals, bit for
+  bit, the cloud of the two-segment pass that pcm_loam_submap_near ran before the two became one (the digests recorded in
+  tests/golden/loam_near_parent.json; tests/make_golden_loam_near.py);
 * a verification equals the composition it replaces on the same context state -- near_keyframes x 2 -> a fresh PclNdtRegistration
   with the same settings -> align -> get_fitness_score -> the numpy restatement of performLoopClosure (tests/loam_loop_ref.py):
   correction, fitness and iterations as equalities, and `between` with the CPU tolerance of tests/test_loam_loop.py, which is 0
@@ -18,6 +20,7 @@ import numpy as np
 import pytest
 
 import loam_loop_ref as R
+import make_golden_loam_near as G
 
 pytestmark = pytest.mark.gpu
 
@@ -31,13 +34,13 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def near_keyframes(K):
-    """K key frames of synth_keyframes (150 + 600 points each); key frame 1 -- or the only one -- has an empty corner cloud"""
-    if ("near", K) not in _CACHE:
-        kf = synth_keyframes.make_keyframes(3, K)
-        kf.corner[min(1, K - 1)] = np.zeros((0, 4), np.float32)
-        _CACHE[("near", K)] = kf
-    return _CACHE[("near", K)]
+near_keyframes = G.near_keyframes
+_CACHE["golden"] = G.load()
+
+
+def recorded(K, case, cloud):
+    """whether `cloud` is the cloud recorded for the case: same rows, same SHA-256 of its float32 bytes"""
+    return G.digest(cloud) == _CACHE["golden"]["near"][G.case_id(K, *case)]
 
 
 def filled(pcm, kf):
@@ -57,40 +60,60 @@ def window_points(kf, key, search_num):
 def test_device_near_cloud_equals_host_near_cloud(pcm, K):
     import torch
     kf = near_keyframes(K)
+    G.check_inputs(_CACHE["golden"], K)
     g = filled(pcm, kf)
     n_checked = 0
-    for key in sorted({0, K // 2, K - 1}):
-        for search_num in (0, 1, 25):
-            for wrt_key in (-1, 0):
-                for leaf in (0.0, 0.4):
-                    want = g.near_keyframes(key, search_num, wrt_key, leaf)
-                    N, m = window_points(kf, key, search_num), len(want)
-                    assert m <= N and (leaf > 0 or m == N)
-                    # host buffer
-                    out = np.full((N + 1, 4), np.nan, np.float32)
-                    assert g.submap_near_device(key, search_num, wrt_key, leaf, out) == m
-                    assert np.array_equal(bits(out[:m]), bits(want)) and np.all(np.isnan(out[m:]))
-                    # device buffers: room for every input point (written in place), and exactly the result's size
-                    for cap in sorted({N, m}):
-                        if cap == 0:
-                            continue
-                        dev = torch.full((cap, 4), float("nan"), dtype=torch.float32, device="cuda:0")
-                        assert g.submap_near_device(key, search_num, wrt_key, leaf, dev) == m
-                        torch.cuda.synchronize()
-                        got = dev.cpu().numpy()
-                        assert np.array_equal(bits(got[:m]), bits(want)), (key, search_num, wrt_key, leaf, cap)
-                        if leaf == 0.0 or cap == m:
-                            assert np.all(np.isnan(got[m:]))
-                    # one short: PCM_ERR_INVALID_ARGUMENT with the count set
-                    if m > 0:
-                        for short in (np.zeros((m - 1, 4), np.float32), torch.zeros((max(m - 1, 1), 4), dtype=torch.float32, device="cuda:0")[:m - 1]):
-                            with pytest.raises(pcm.capi.PcmError) as e:
-                                g.submap_near_device(key, search_num, wrt_key, leaf, short)
-                            assert e.value.code == -1 and g._near_count == m
-                    n_checked += 1
-    assert n_checked == len({0, K // 2, K - 1}) * 12
+    for case in G.near_cases(K):
+        key, search_num, wrt_key, leaf = case
+        want = g.near_keyframes(key, search_num, wrt_key, leaf)
+        assert recorded(K, case, want), case
+        N, m = window_points(kf, key, search_num), len(want)
+        assert m <= N and (leaf > 0 or m == N)
+        # host buffer
+        out = np.full((N + 1, 4), np.nan, np.float32)
+        assert g.submap_near_device(key, search_num, wrt_key, leaf, out) == m
+        assert recorded(K, case, out[:m]) and np.array_equal(bits(out[:m]), bits(want)) and np.all(np.isnan(out[m:]))
+        # device buffers: room for every input point (written in place), and exactly the result's size
+        for cap in sorted({N, m}):
+            if cap == 0:
+                continue
+            dev = torch.full((cap, 4), float("nan"), dtype=torch.float32, device="cuda:0")
+            assert g.submap_near_device(key, search_num, wrt_key, leaf, dev) == m
+            torch.cuda.synchronize()
+            got = dev.cpu().numpy()
+            assert recorded(K, case, got[:m]) and np.array_equal(bits(got[:m]), bits(want)), (case, cap)
+            if leaf == 0.0 or cap == m:
+                assert np.all(np.isnan(got[m:]))
+        # one short: PCM_ERR_INVALID_ARGUMENT with the count set
+        if m > 0:
+            for short in (np.zeros((m - 1, 4), np.float32), torch.zeros((max(m - 1, 1), 4), dtype=torch.float32, device="cuda:0")[:m - 1]):
+                with pytest.raises(pcm.capi.PcmError) as e:
+                    g.submap_near_device(key, search_num, wrt_key, leaf, short)
+                assert e.value.code == -1 and g._near_count == m
+        n_checked += 1
+    assert n_checked == len({0, K // 2, K - 1}) * (14 if K == 7 else 12)
     # the host entry still gives what it gave, after all the device passes
-    assert np.array_equal(bits(g.near_keyframes(K - 1, 25, -1, 0.4)), bits(g.near_keyframes(K - 1, 25, -1, 0.4)))
+    assert recorded(K, (K - 1, 25, -1, 0.4), g.near_keyframes(K - 1, 25, -1, 0.4))
+
+
+def test_near_entries_share_a_workspace(pcm):
+    """pcm_loam_submap_near runs in the workspace of pcm_loam_submap_near_dev: a device result left un-waited -- in place without
+    a leaf, and as a queued copy out of the workspace's cell array with one -- survives a host call with other arguments."""
+    import torch
+    K = 7
+    kf = near_keyframes(K)
+    G.check_inputs(_CACHE["golden"], K)
+    g = filled(pcm, kf)
+    # the first result is written in place (no leaf: as many rows as input points); the other two are fewer rows than points
+    for first, second in (((3, 25, -1, 0.0), (6, 1, 0, 0.4)), ((3, 25, -1, 0.4), (0, 25, 0, 0.0)), ((6, 25, 0, G.BIG_LEAF), (3, 1, -1, 0.4))):
+        rows = _CACHE["golden"]["near"][G.case_id(K, *first)]["rows"]
+        assert (rows == window_points(kf, first[0], first[1])) == (first[3] == 0.0)
+        dev = torch.full((rows, 4), float("nan"), dtype=torch.float32, device="cuda:0")
+        assert g.submap_near_device(*first, dev) == rows   # not waited for
+        host = g.near_keyframes(*second)
+        torch.cuda.synchronize()
+        assert recorded(K, second, host), (first, second)
+        assert recorded(K, first, dev.cpu().numpy()), (first, second)
 
 
 def test_device_near_cloud_errors_and_empty_store(pcm):

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import loam_submap_ref as R
+import make_golden_loam_near as G
 from test_gpu_loam_features import close_ulp
 
 pytestmark = pytest.mark.gpu
@@ -57,6 +58,21 @@ def test_update_matches_restatement(pcm, K, seed, radius):
     assert g.num_keyframes == K
     r, _, _ = check_update(g, kf, radius)
     assert r.rebuilt
+
+
+@pytest.mark.parametrize("name", sorted(G.UPDATE_CASES))
+def test_update_equals_recorded_maps(pcm, name):
+    """The two maps equal, bit for bit, the maps recorded before the update and the near pass came to share their gather and
+    average kernels (tests/golden/loam_near_parent.json); and the restatement agrees as in every other update test."""
+    K, params = G.UPDATE_CASES[name]
+    golden = G.load()
+    G.check_inputs(golden, K)
+    kf = G.near_keyframes(K)
+    g = filled(pcm, kf)
+    r, info, _ = check_update(g, kf, 50.0, **params)
+    assert r.rebuilt
+    for k in ("corner_map", "surf_map"):
+        assert G.digest(info[k]) == golden["update"][name][k], k
 
 
 def test_growth_of_the_matrices_keeps_the_earlier_key_frames(pcm):

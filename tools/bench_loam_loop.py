@@ -4,7 +4,9 @@ on the same context, alternating the two paths run by run:
   (i)   verify_ms               loop_verify (both near clouds, gates, NDT, fitness, pose algebra; one call)
   (ii)  host_composition_ms     the path it replaces: near_keyframes x 2 (host) -> PclNdtRegistration.set_input_target / source ->
                                 align -> get_fitness_score -> the restatement's pose algebra
-  (iii) near_dev_ms / near_host_ms   submap_near_device into a device tensor against near_keyframes, for the previous cloud
+  (iii) near_dev_ms / near_host_ms   submap_near_device into a device tensor against near_keyframes, for the previous cloud; both
+                                are the same device pass, so near_host_ms is that pass plus the copy of the result to the host
+                                (and near_keyframes' count queries)
 Every timed call ends in a wait on the device (the count read-back, the NDT result or the fitness score), so the host clock is
 the call's time.  Medians of --runs after a warm-up of every path.  Also checks that both paths give the same correction and
 fitness.  Prints one JSON line.
