@@ -779,6 +779,57 @@ int pcm_loam_loop_closure(pcm_ctx *ctx, const pcm_loam_loop_params *params, floa
 int pcm_loam_loop_verifier_exists(pcm_ctx *ctx);
 
 /*
+ * The two clouds a mapping run of jueying_slam exists to produce, from the key frames on the device: publishGlobalMap
+ * (mapOptmization.cpp:547-590, every five seconds) and the saved map (:524-542, jueying.pcd).  DESIGN.md section 20.
+ * Both read the key-frame store and write nothing of the context: not its target or source, the key frames, the Scan Context
+ * store or the workspaces of the near clouds.  Their per-point device workspace (up to about 44 bytes per selected point) is
+ * allocated by the call and released before it returns; a table of 32 bytes per selected key frame stays.
+ */
+typedef struct pcm_loam_global_params {
+  float search_radius;           /* 1000.0 utility.h:293 globalMapVisualizationSearchRadius */
+  float keypose_density;         /* 10.0   utility.h:294 globalMapVisualizationPoseDensity: leaf of the VoxelGrid over the key poses, > 0 */
+  float leaf;                    /* 1.0    utility.h:295 globalMapVisualizationLeafSize; 0 = no down-sampling */
+} pcm_loam_global_params;
+
+typedef struct pcm_loam_global_result {
+  int32_t num_near;              /* key poses inside the radius of the last one */
+  int32_t num_pose_leaves;       /* leaves of the VoxelGrid over them */
+  int32_t num_skipped;           /* leaves whose centroid is farther than the radius from the last key pose (:578) */
+  int32_t num_used;              /* leaves used; each names one key frame (the truncated mean of the key indices in it) */
+  uint64_t points_in;            /* points of the selected clouds */
+  uint64_t points_out;           /* cells written */
+} pcm_loam_global_result;
+
+void pcm_loam_default_global_params(pcm_loam_global_params *params);
+/* the selection alone, on the host: the key frame of every used leaf in list order; capacity in keys, *n always set
+ * (PCM_ERR_INVALID_ARGUMENT when the capacity is too small).  An overflow of the pose grid: PCM_ERR_OUT_OF_RANGE. */
+int pcm_loam_global_keys(pcm_ctx *ctx, const pcm_loam_global_params *params, int32_t *keys, size_t cap, size_t *n);
+/* publishGlobalMap: corner then surf cloud of every selected key frame under its pose, one VoxelGrid(leaf): (x, y, z, intensity)
+ * float4 cells in leaf-index order into a host or DEVICE buffer (`memory`; capacity in points).  It is pcm_loam_submap_near_dev's
+ * pass on this selection and follows its rules: result->points_out is set before a "capacity too small" error
+ * (PCM_ERR_INVALID_ARGUMENT); a 16-byte-aligned device buffer with room for points_in points is written in place; with leaf == 0
+ * the count (= points_in) is known before anything runs -- so leaf == 0 with capacity 0 is a host-only query of points_in -- and
+ * a device result is queued on the context's stream without a wait; with leaf > 0 the call waits once, for the count.  More than
+ * 2^31 - 1 selected points and a VoxelGrid index overflow: PCM_ERR_OUT_OF_RANGE.  An empty store: PCM_OK, zero points.  A bad
+ * argument: nothing written.  params NULL = defaults; result may be NULL. */
+int pcm_loam_global_map(pcm_ctx *ctx, const pcm_loam_global_params *params, void *out, size_t cap, int memory, pcm_loam_global_result *result);
+/* The saved map (:530-541) of key frames [first, first + n): which 0 = their corner clouds (globalCornerCloud), 1 = their surf
+ * clouds (globalSurfCloud), 2 = all corner clouds, then all surf clouds (globalMapCloud).  Every point is transformPointCloud's
+ * value under its key frame's pose, bit for bit (a negative zero stays negative); no VoxelGrid.  Buffer rules as above; *n_out is
+ * known before anything runs and always set, and a device result is not waited for.  More than 2^31 - 1 points in one call:
+ * PCM_ERR_OUT_OF_RANGE.  A whole session through a bounded buffer is a loop over [first, first + n) with which = 0, then the
+ * same loop with which = 1: the pieces concatenate to globalCornerCloud and globalSurfCloud, and those two to jueying.pcd.
+ * which = 2 equals jueying.pcd over the full range [0, K) only: its pieces over sub-ranges do not concatenate to it. */
+int pcm_loam_map_export(pcm_ctx *ctx, int which, int first, int n, void *out, size_t cap, int memory, size_t *n_out);
+/* measurement hook (tools/bench_loam_global.py): one timed run, device events around it, of the gather of pcm_loam_global_map's
+ * selection -- variant 0: the near pass's gather (per-wave atomics on the box), 1: the global pass's (partial boxes) -- with the
+ * box either leaves (6 ordered words), the bytes of the workspace pcm_loam_global_map allocates for that selection with
+ * leaf > 0 and an in-place buffer, and the host time (ms) its allocation and its release took in this call on an idle stream.
+ * box6, workspace_bytes and workspace_ms may be NULL. */
+int pcm_loam_global_gather_ms(pcm_ctx *ctx, const pcm_loam_global_params *params, int variant, float *ms, uint32_t *box6, size_t *workspace_bytes,
+                              float *workspace_ms);
+
+/*
  * Localisation map of jueying_slam on the device: the saved global map cut into area tiles (include/dynamic_map.h:16-156), the
  * reload of the tiles around the robot (dynamic_load_map_run, localization.cpp:281-315) and the per-frame crop of the loaded
  * tiles (dynamic_load_map, :256-280).  A PCM_MODEL_LOAM context keeps every tile of the corner list and of the surf list (map

@@ -431,6 +431,8 @@ private:
 //     keyframes.loopFindNearKeyframes(cureKeyframeCloud, loopKeyCur, 0);     // :972
 //     keyframes.loopFindNearKeyframesWithRespectTo(prevKeyframeCloud, loopKeyPre, historyKeyframeSearchNum, loopKeyCur);
 //     if (keyframes.performLoopClosure(timeLaserInfoCur, &factor)) { ... }   // :619-733 on the device
+//     keyframes.publishGlobalMap(globalMapKeyFramesDS);                      // :547-590
+//     keyframes.exportMap(globalMapCloud);                                   // :524-542, what jueying.pcd holds
 // Poses are transformTobeMapped vectors (roll, pitch, yaw, x, y, z).  The object does not own the context: it must not outlive `loam`.
 template <typename PointT>
 class LoamKeyFrameMap {
@@ -506,7 +508,57 @@ public:
     return take_factor(out);
   }
 
+  void setGlobalMapVisualizationSearchRadius(float v) { globalParams().search_radius = v; }   // globalMapVisualizationSearchRadius
+  void setGlobalMapVisualizationPoseDensity(float v) { globalParams().keypose_density = v; }   // globalMapVisualizationPoseDensity
+  void setGlobalMapVisualizationLeafSize(float v) { globalParams().leaf = v; }                 // globalMapVisualizationLeafSize
+  // the reference's values on first use
+  pcm_loam_global_params& globalParams() {
+    if (!global_params_set_) { pcm_loam_default_global_params(&global_params_); global_params_set_ = true; }
+    return global_params_;
+  }
+  const pcm_loam_global_result& globalResult() const { return global_last_; }
+  // publishGlobalMap :555-588: globalMapKeyFramesDS (pcm_loam_global_map)
+  void publishGlobalMap(Cloud& globalMapKeyFramesDS) {
+    pcm_loam_global_params count = globalParams();
+    count.leaf = 0.f;   // without a leaf and a buffer: the host-only query of points_in
+    pcm_loam_global_result r{};
+    const int rc = pcm_loam_global_map(ctx_, &count, nullptr, 0, PCM_MEM_HOST, &r);
+    if (rc != PCM_OK && r.points_in == 0) check(rc, "pcm_loam_global_map");
+    if (buf_.size() < 4 * r.points_in) buf_.resize(4 * r.points_in);
+    check(pcm_loam_global_map(ctx_, &global_params_, buf_.data(), buf_.size() / 4, PCM_MEM_HOST, &global_last_), "pcm_loam_global_map");
+    unpack(globalMapKeyFramesDS, global_last_.points_out);
+  }
+  // the same into a device buffer of `capacity` float4 (x, y, z, intensity) records, on the context's stream; returns the count
+  size_t publishGlobalMap(void* device_out, size_t capacity) {
+    check(pcm_loam_global_map(ctx_, &globalParams(), device_out, capacity, PCM_MEM_DEVICE, &global_last_), "pcm_loam_global_map");
+    return global_last_.points_out;
+  }
+  // the saved map :530-541 of key frames [first, first + n) (n < 0: all from first): which 0 = globalCornerCloud, 1 =
+  // globalSurfCloud, 2 = globalMapCloud (jueying.pcd when the range is the whole store)
+  void exportMap(Cloud& out, int which = 2, int first = 0, int n = -1) {
+    if (n < 0) n = size() - first;
+    size_t total = 0;
+    const int rc = pcm_loam_map_export(ctx_, which, first, n, nullptr, 0, PCM_MEM_HOST, &total);
+    if (rc != PCM_OK && total == 0) check(rc, "pcm_loam_map_export");
+    if (buf_.size() < 4 * total) buf_.resize(4 * total);
+    check(pcm_loam_map_export(ctx_, which, first, n, buf_.data(), buf_.size() / 4, PCM_MEM_HOST, &total), "pcm_loam_map_export");
+    unpack(out, total);
+  }
+  size_t exportMap(void* device_out, size_t capacity, int which, int first, int n) {
+    size_t total = 0;
+    check(pcm_loam_map_export(ctx_, which, first, n, device_out, capacity, PCM_MEM_DEVICE, &total), "pcm_loam_map_export");
+    return total;
+  }
+
 private:
+  // n (x, y, z, intensity) records of buf_ into a cloud, member by member
+  void unpack(Cloud& out, size_t n) const {
+    out.points.resize(n);
+    for (size_t i = 0; i < n; i++) {
+      PointT& q = out.points[i];
+      q.x = buf_[4 * i]; q.y = buf_[4 * i + 1]; q.z = buf_[4 * i + 2]; q.intensity = buf_[4 * i + 3];
+    }
+  }
   bool take_factor(LoopFactor* out) const {
     if (loop_last_.status != PCM_LOAM_LOOP_ACCEPTED) return false;
     if (out) {
@@ -531,11 +583,7 @@ private:
     size_t n = 0;
     const int rc = pcm_loam_submap_near(ctx_, key, searchNum, wrt, loop_leaf_, buf_.data(), buf_.size() / 4, &n);
     check(rc, "pcm_loam_submap_near");
-    out.points.resize(n);
-    for (size_t i = 0; i < n; i++) {
-      PointT& q = out.points[i];
-      q.x = buf_[4 * i]; q.y = buf_[4 * i + 1]; q.z = buf_[4 * i + 2]; q.intensity = buf_[4 * i + 3];
-    }
+    unpack(out, n);
   }
   void check(int rc, const char* what) const {
     if (rc != PCM_OK) throw std::runtime_error(std::string(what) + ": " + pcm_last_error(ctx_));
@@ -547,6 +595,9 @@ private:
   bool loop_params_set_ = false;
   pcm_loam_loop_result loop_last_{};
   float loop_leaf_ = 0.2f;
+  pcm_loam_global_params global_params_{};
+  bool global_params_set_ = false;
+  pcm_loam_global_result global_last_{};
   std::vector<float> buf_, buf2_;
 };
 

@@ -24,6 +24,7 @@ SYMBOLS = [
     "pcm_loam_default_sc_params", "pcm_loam_sc_add", "pcm_loam_sc_put", "pcm_loam_sc_get", "pcm_loam_sc_count", "pcm_loam_sc_shape", "pcm_loam_sc_clear",
     "pcm_loam_sc_detect", "pcm_loam_sc_distance", "pcm_loam_loop_detect_distance",
     "pcm_loam_submap_near_dev", "pcm_loam_default_loop_params", "pcm_loam_loop_verify", "pcm_loam_loop_closure", "pcm_loam_loop_verifier_exists",
+    "pcm_loam_default_global_params", "pcm_loam_global_keys", "pcm_loam_global_map", "pcm_loam_map_export", "pcm_loam_global_gather_ms",
     "pcm_loam_default_dynmap_params", "pcm_loam_tile_add", "pcm_loam_tile_count", "pcm_loam_tile_clear", "pcm_loam_dynmap_need_load",
     "pcm_loam_dynmap_load", "pcm_loam_dynmap_crop", "pcm_loam_dynmap_info", "pcm_loam_dynmap_global",
     "pcm_occ_default_params", "pcm_occ_reset", "pcm_occ_insert_scans", "pcm_occ_insert_keyframes", "pcm_occ_get_scan", "pcm_occ_status",
@@ -198,6 +199,15 @@ class PcmLoamLoopResult(C.Structure):
                 ("ndt_iterations", C.c_int32), ("ndt_converged", C.c_int32), ("noise_variance", C.c_float), ("fitness", C.c_double),
                 ("correction", C.c_float * 16), ("pose_from", C.c_double * 6), ("pose_to", C.c_double * 6), ("between", C.c_double * 16),
                 ("between6", C.c_double * 6), ("reserved", C.c_int32 * 8)]
+
+
+class PcmLoamGlobalParams(C.Structure):
+    _fields_ = [("search_radius", C.c_float), ("keypose_density", C.c_float), ("leaf", C.c_float)]
+
+
+class PcmLoamGlobalResult(C.Structure):
+    _fields_ = [("num_near", C.c_int32), ("num_pose_leaves", C.c_int32), ("num_skipped", C.c_int32), ("num_used", C.c_int32),
+                ("points_in", C.c_uint64), ("points_out", C.c_uint64)]
 
 
 class PcmLoamDynmapParams(C.Structure):
@@ -387,6 +397,12 @@ def load_library():
     L.pcm_loam_loop_verify.argtypes = [vp, C.POINTER(PcmLoamLoopParams), i32, i32, C.POINTER(PcmLoamLoopResult)]
     L.pcm_loam_loop_closure.argtypes = [vp, C.POINTER(PcmLoamLoopParams), C.c_float, C.c_double, C.c_double, C.POINTER(PcmLoamLoopResult)]
     L.pcm_loam_loop_verifier_exists.argtypes = [vp]
+    L.pcm_loam_default_global_params.argtypes = [C.POINTER(PcmLoamGlobalParams)]
+    L.pcm_loam_default_global_params.restype = None
+    L.pcm_loam_global_keys.argtypes = [vp, C.POINTER(PcmLoamGlobalParams), vp, sz, C.POINTER(sz)]
+    L.pcm_loam_global_map.argtypes = [vp, C.POINTER(PcmLoamGlobalParams), vp, sz, i32, C.POINTER(PcmLoamGlobalResult)]
+    L.pcm_loam_map_export.argtypes = [vp, i32, i32, i32, vp, sz, i32, C.POINTER(sz)]
+    L.pcm_loam_global_gather_ms.argtypes = [vp, C.POINTER(PcmLoamGlobalParams), i32, C.POINTER(C.c_float), vp, C.POINTER(sz), C.POINTER(C.c_float)]
     L.pcm_loam_default_dynmap_params.argtypes = [C.POINTER(PcmLoamDynmapParams)]
     L.pcm_loam_default_dynmap_params.restype = None
     L.pcm_loam_tile_add.argtypes = [vp, i32, vp, vp, sz, sz, i32]

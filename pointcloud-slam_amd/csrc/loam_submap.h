@@ -1,5 +1,5 @@
 // loam_submap.h -- which key frames make the surrounding submap: jueying_slam's extractNearby / extractCloud selection
-// (mapOptmization.cpp:1153-1222) and the key window of loopFindNearKeyframes (:972-1018), as plain C++ over the host mirror of
+// (mapOptmization.cpp:1153-1222), publishGlobalMap's (:555-583) and the key window of loopFindNearKeyframes (:972-1018), as plain C++ over the host mirror of
 // the key poses.  K is at most some ten thousand and the work is microseconds, so it runs on the host in the API layer
 // (loam_submap.hip); tests/test_loam_submap.py compiles this header with g++ and checks it against the numpy restatement
 // (tests/loam_submap_ref.py).  Every float operation below is one IEEE operation in the order written (-ffp-contract=off).
@@ -34,8 +34,9 @@ struct SubmapSelection {
   int32_t status = 0;          // 0, or -1: the pose VoxelGrid's index overflows (leaf too small)
 };
 
-// extractNearby + the skip test of extractCloud.  K >= 1.
-inline SubmapSelection select_surrounding(const KeyPose* kp, int K, float radius, float density, double time_cur, double window) {
+// Parts (a) and (b), part (c) when recent (the key frames of the last `window` seconds before time_cur) and the skip test: the
+// body the two selections below share.  K >= 1.
+inline SubmapSelection select_entries(const KeyPose* kp, int K, float radius, float density, bool recent, double time_cur, double window) {
   SubmapSelection S;
   if (K <= 0) return S;
   const KeyPose& last = kp[K - 1];
@@ -94,11 +95,11 @@ inline SubmapSelection select_surrounding(const KeyPose* kp, int K, float radius
   }
   S.num_pose_leaves = (int32_t)list.size();
   // (c) every key frame of the last `window` seconds, newest first, with its exact index
-  for (int i = K - 1; i >= 0; --i) {
+  for (int i = K - 1; recent && i >= 0; --i) {
     if (time_cur - kp[i].time < window) list.push_back({kp[i].x, kp[i].y, kp[i].z, (float)i});
     else break;
   }
-  // extractCloud: pointDistance(entry, last) > radius skips the entry
+  // extractCloud / publishGlobalMap :578: pointDistance(entry, last) > radius skips the entry
   for (const Entry& e : list) {
     const float dx = e.x - last.x, dy = e.y - last.y, dz = e.z - last.z;
     const float dist = sqrtf(dx * dx + dy * dy + dz * dz);
@@ -106,6 +107,16 @@ inline SubmapSelection select_surrounding(const KeyPose* kp, int K, float radius
     S.keys.push_back((int32_t)e.intensity);
   }
   return S;
+}
+
+// extractNearby + the skip test of extractCloud
+inline SubmapSelection select_surrounding(const KeyPose* kp, int K, float radius, float density, double time_cur, double window) {
+  return select_entries(kp, K, radius, density, true, time_cur, window);
+}
+
+// publishGlobalMap's selection (mapOptmization.cpp:555-583): extractNearby without the window of recent key frames
+inline SubmapSelection select_global(const KeyPose* kp, int K, float radius, float density) {
+  return select_entries(kp, K, radius, density, false, 0.0, 0.0);
 }
 
 // loopFindNearKeyframes: key - search_num .. key + search_num inside [0, K)

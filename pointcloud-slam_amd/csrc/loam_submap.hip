@@ -1,5 +1,5 @@
-// loam_submap.hip -- LOAM key-frame store and surrounding-key-frame submap on the device (include/pcm_amd.h, pcm_loam_keyframe_*
-// and pcm_loam_submap_*): jueying_slam's saveKeyFramesAndFactor clouds (mapOptmization.cpp:1779-1846), correctPoses (:1886-1917),
+// loam_submap.hip -- LOAM key-frame store and surrounding-key-frame submap on the device (include/pcm_amd.h, pcm_loam_keyframe_*,
+// pcm_loam_submap_*, pcm_loam_global_* and pcm_loam_map_export): jueying_slam's saveKeyFramesAndFactor clouds (mapOptmization.cpp:1779-1846), correctPoses (:1886-1917),
 // extractSurroundingKeyFrames (:1153-1230), transformPointCloud (:447-470) and loopFindNearKeyframes (:972-1018).
 //
 // Store: one growing float4 arena (x, y, z, intensity; body frame) for the corner clouds of all key frames and one for the surf
@@ -21,6 +21,10 @@
 // launches: the box is derived inside the key kernel, the keys are 32 bits wide (half the radix passes; the sort stays stable, so
 // a cell's run keeps its input order and its sum its bits), the cell heads are scanned on the fly instead of being stored, head
 // positions and totals come from one kernel, and without a leaf the gather writes the result itself.
+// Global map and saved map (pcm_loam_global_map, pcm_loam_map_export; publishGlobalMap :547-590 and the clouds of :524-542): the
+// near pass on publishGlobalMap's selection (select_global) in a workspace of its own whose per-point arrays live for one call,
+// with a gather that leaves one partial bounding box per workgroup instead of atomics per wave (k_gm_gather, k_gm_box; the same
+// bits); the export is that gather alone, writing transformPointCloud's values as they are.  DESIGN.md section 20.
 // The two passes share the entry table (build_entries), the gather and the average kernel and the workspace type, and stay two
 // pipelines on purpose: the update sorts 64-bit (segment, leaf) keys through sv_sort_cells, the near pass 32-bit keys.  One
 // pipeline for both would change the number of radix passes of one of them, and with it its speed.
@@ -33,6 +37,7 @@
 #include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
+#include <chrono>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -58,13 +63,9 @@ struct SmEntry {
 // kDirect (the near pass without a leaf): every point is its own cell, and the mean of one value v is
 // (float)((0.0 + (double)v) / 1.0): v itself with a negative zero turned positive, which v + 0.0f is as well; the lane writes that
 // to the result and nothing else runs.
-template <bool kDirect>
-__global__ void __launch_bounds__(256) k_sm_gather(const float4* __restrict__ corner_arena, const float4* __restrict__ surf_arena, const float* __restrict__ mats,
-                                                   const SmEntry* __restrict__ ent, uint32_t n_ent, uint32_t N, float4* __restrict__ out,
-                                                   unsigned int* __restrict__ mm) {
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool valid = g < N;
-  const uint32_t gg = valid ? g : N - 1;
+// point gg < N of the concatenated selection under its key frame's matrix; *flags = its entry's
+__device__ __forceinline__ float4 sm_point(const float4* __restrict__ corner_arena, const float4* __restrict__ surf_arena, const float* __restrict__ mats,
+                                           const SmEntry* __restrict__ ent, uint32_t n_ent, uint32_t gg, uint32_t* flags) {
   uint32_t lo = 0, hi = n_ent;   // ent[lo].first <= gg < ent[hi].first (ent[n_ent].first taken as N)
   while (hi - lo > 1) {
     const uint32_t mid = (lo + hi) >> 1;
@@ -79,12 +80,68 @@ __global__ void __launch_bounds__(256) k_sm_gather(const float4* __restrict__ co
   q.y = T[4] * p.x + T[5] * p.y + T[6] * p.z + T[7];
   q.z = T[8] * p.x + T[9] * p.y + T[10] * p.z + T[11];
   q.w = p.w;
+  *flags = e.flags;
+  return q;
+}
+
+template <bool kDirect>
+__global__ void __launch_bounds__(256) k_sm_gather(const float4* __restrict__ corner_arena, const float4* __restrict__ surf_arena, const float* __restrict__ mats,
+                                                   const SmEntry* __restrict__ ent, uint32_t n_ent, uint32_t N, float4* __restrict__ out,
+                                                   unsigned int* __restrict__ mm) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = g < N;
+  uint32_t flags;
+  const float4 q = sm_point(corner_arena, surf_arena, mats, ent, n_ent, valid ? g : N - 1, &flags);
   if (kDirect) {
     if (valid) out[g] = make_float4(q.x + 0.0f, q.y + 0.0f, q.z + 0.0f, q.w + 0.0f);
   } else {
     if (valid) out[g] = q;
-    sv_wave_minmax(valid, (e.flags >> 1) & 1u, q, mm);
+    sv_wave_minmax(valid, (flags >> 1) & 1u, q, mm);
   }
+}
+
+// the box of a workgroup of 256 lanes from its lanes' boxes (ordered words), into box[0..6): a butterfly per wave, then the four
+// waves through LDS; lanes 0..5 store
+__device__ __forceinline__ void gm_fold(unsigned int lo[3], unsigned int hi[3], unsigned int* __restrict__ box) {
+  __shared__ unsigned int wave_box[4][6];
+  for (int a = 0; a < 3; a++) { lo[a] = wave_min_u32(lo[a]); hi[a] = wave_max_u32(hi[a]); }
+  if ((threadIdx.x & 63) == 0)
+    for (int a = 0; a < 3; a++) { wave_box[threadIdx.x >> 6][a] = lo[a]; wave_box[threadIdx.x >> 6][3 + a] = hi[a]; }
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    const uint32_t a = threadIdx.x;
+    unsigned int v = wave_box[0][a];
+    for (int w = 1; w < 4; w++) v = a < 3 ? min(v, wave_box[w][a]) : max(v, wave_box[w][a]);
+    box[a] = v;
+  }
+}
+
+// The gather of the global pass (pcm_loam_global_map, pcm_loam_map_export): k_sm_gather's points, at most kGmBlocks workgroups
+// striding over them.  kBox: no atomics -- every lane keeps the box of its points in registers, a butterfly folds the wave's, LDS
+// the workgroup's four, and the workgroup stores one partial box (6 ordered words, min then max) that k_gm_box folds into the
+// words k_nd_keys reads.  Min and max are exact in any order, so box, keys and cells are k_sm_gather<false>'s bit for bit.
+// !kBox (the export): transformPointCloud's value as it is -- no + 0.0f, a negative zero stays negative -- and nothing else.
+constexpr unsigned kGmBlocks = 2048;
+
+template <bool kBox>
+__global__ void __launch_bounds__(256) k_gm_gather(const float4* __restrict__ corner_arena, const float4* __restrict__ surf_arena, const float* __restrict__ mats,
+                                                   const SmEntry* __restrict__ ent, uint32_t n_ent, uint32_t N, float4* __restrict__ out,
+                                                   unsigned int* __restrict__ part) {
+  unsigned int lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
+  // N < 2^31 and a stride of at most 2^19: base does not wrap
+  for (uint32_t base = blockIdx.x * 256u; base < N; base += gridDim.x * 256u) {
+    const uint32_t g = base + threadIdx.x;
+    if (g >= N) continue;
+    uint32_t flags;
+    const float4 q = sm_point(corner_arena, surf_arena, mats, ent, n_ent, g, &flags);
+    out[g] = q;
+    if (kBox) {
+      const float c[3] = {q.x, q.y, q.z};
+      for (int a = 0; a < 3; a++) { const unsigned int o = f2ord(c[a]); lo[a] = min(lo[a], o); hi[a] = max(hi[a], o); }
+    }
+  }
+  if (!kBox) return;
+  gm_fold(lo, hi, part + 6 * blockIdx.x);
 }
 
 // small: [0..1] cells per segment, [2..3] first cell, [4..7] totals (sv_sort_cells' nc), [8] index overflow
@@ -154,6 +211,15 @@ __global__ void k_nd_clear(unsigned int* __restrict__ mm, uint32_t* __restrict__
   if (t < 3) { mm[t] = 0xffffffffu; mm[3 + t] = 0u; small[t] = 0u; }
 }
 
+// the global pass: n_part partial boxes of k_gm_gather -> mm, and k_nd_clear's zeros; one workgroup
+__global__ void __launch_bounds__(256) k_gm_box(const unsigned int* __restrict__ part, uint32_t n_part, unsigned int* __restrict__ mm, uint32_t* __restrict__ small) {
+  unsigned int lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
+  for (uint32_t i = threadIdx.x; i < n_part; i += 256u)
+    for (int a = 0; a < 3; a++) { lo[a] = min(lo[a], part[6 * i + a]); hi[a] = max(hi[a], part[6 * i + 3 + a]); }
+  gm_fold(lo, hi, mm);
+  if (threadIdx.x < kNdSmallWords) small[threadIdx.x] = 0u;
+}
+
 // k_sm_boxes + k_sm_keys: every workgroup derives the box from the finished min / max (a few dozen operations of one lane)
 __global__ void __launch_bounds__(256) k_nd_keys(const float4* __restrict__ in, uint32_t N, float leaf, const unsigned int* __restrict__ mm,
                                                  uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ small) {
@@ -192,41 +258,51 @@ __global__ void k_nd_pos(const uint32_t* __restrict__ keys, const uint32_t* __re
 // device workspace of one gather + VoxelGrid pass.  The update pass (segmented) sorts 64-bit keys and keeps the cell heads, two
 // boxes and the totals of two segments; its cells go to the context's target.  The near pass sorts 32-bit keys and owns a cell
 // array.  The near pass has two workspaces, so that the two clouds of a loop verification are in flight together.
+// The global pass (one_shot) is the near pass on a selection of up to 2^31 points: its per-point arrays are sized exactly, hold
+// only what the call at hand needs and are released when it returns; the entry table and the partial boxes of its gather (a few
+// bytes per key frame) stay.
 struct SmWork {
   DevBuf<char> buf;
-  size_t n_cap = 0, ent_cap = 0;
-  size_t o_in = 0, o_cells = 0, o_keys = 0, o_keys_s = 0, o_vals = 0, o_vals_s = 0, o_head = 0, o_slot = 0, o_mm = 0, o_box = 0, o_small = 0, o_ent = 0,
+  DevBuf<SmEntry> ent{"key-frame entry table"};
+  DevBuf<unsigned int> part{"partial boxes"};   // one_shot: [kGmBlocks][6]
+  size_t n_cap = 0;
+  size_t o_in = 0, o_cells = 0, o_keys = 0, o_keys_s = 0, o_vals = 0, o_vals_s = 0, o_head = 0, o_slot = 0, o_mm = 0, o_box = 0, o_small = 0,
          o_tmp = 0, o_tmp2 = 0, tmp_bytes = 0, tmp2_bytes = 0;
   PinnedBuf<uint32_t> h_small;
   PinnedBuf<SmEntry> h_ent;      // staging of the entry table
   bool in_flight = false;        // the last near pass was left without a wait: its staging is not free yet
+  bool one_shot = false;
 
   template <class T> T* at(size_t off) const { return reinterpret_cast<T*>(buf.p + off); }
   float4* in() const { return at<float4>(o_in); }
   float4* cells() const { return at<float4>(o_cells); }
 };
 
-// room for N points and n_ent entries; keys of key_bytes each.  segmented: the head and box arrays and the second segment exist
-// and the cell array does not.
-int ensure_work(pcm_ctx* c, SmWork* W, size_t N, size_t n_ent, size_t key_bytes, bool segmented) {
+// room for N points and n_ent entries; keys of key_bytes each.  segmented: the head and box arrays and the second segment exist.
+// sorted: the arrays of the VoxelGrid exist (a one-shot pass without a leaf has none); own_cells: the cell array does.
+int ensure_work(pcm_ctx* c, SmWork* W, size_t N, size_t n_ent, size_t key_bytes, bool segmented, bool sorted, bool own_cells) {
   const size_t words = segmented ? kSmallWords : kNdSmallWords;
   int rc = W->h_small.reserve(c, words, words);
   if (rc != PCM_OK) return rc;
   if (n_ent > W->h_ent.cap && (rc = W->h_ent.reserve(c, n_ent, n_ent + n_ent / 2 + 16)) != PCM_OK) return rc;
-  if (W->buf && N <= W->n_cap && n_ent <= W->ent_cap) return PCM_OK;
+  if ((rc = W->ent.reserve(c, n_ent, W->h_ent.cap)) != PCM_OK) return rc;
+  if (W->one_shot && (rc = W->part.reserve(c, 6 * kGmBlocks, 6 * kGmBlocks)) != PCM_OK) return rc;
+  if (W->buf && N <= W->n_cap) return PCM_OK;
+  if (!sorted && !own_cells) return PCM_OK;   // nothing per point
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   W->buf.release();   // the layout below is for the new sizes alone
-  W->n_cap = W->ent_cap = 0;
-  const size_t nc = N + N / 4 + 1024, ec = W->h_ent.cap;
+  W->n_cap = 0;
+  const size_t nc = W->one_shot ? N : N + N / 4 + 1024, ns = sorted ? nc : 0;
   size_t o = 0;
   auto take = [&](size_t bytes) { const size_t r = o; o += up256(bytes); return r; };
-  W->o_in = take(16 * nc);
-  W->o_cells = take(segmented ? 16 : 16 * nc);
-  W->o_keys = take(key_bytes * nc); W->o_keys_s = take(key_bytes * nc);
-  W->o_vals = take(4 * nc); W->o_vals_s = take(4 * nc); W->o_head = take(segmented ? 4 * nc : 0); W->o_slot = take(4 * nc);
+  W->o_in = take(16 * ns);
+  W->o_cells = take(own_cells ? 16 * nc : 16);
+  W->o_keys = take(key_bytes * ns); W->o_keys_s = take(key_bytes * ns);
+  W->o_vals = take(4 * ns); W->o_vals_s = take(4 * ns); W->o_head = take(segmented ? 4 * ns : 0); W->o_slot = take(4 * ns);
   W->o_mm = take(4 * 6 * (segmented ? 2 : 1)); W->o_box = take(segmented ? 8 * 12 : 0); W->o_small = take(4 * words);
-  W->o_ent = take(sizeof(SmEntry) * ec);
-  if (segmented) {
+  if (!sorted) {
+    W->tmp_bytes = W->tmp2_bytes = 0;
+  } else if (segmented) {
     sv_temp_bytes(nc, &W->tmp_bytes, &W->tmp2_bytes);
   } else {
     uint32_t* k = nullptr;
@@ -236,9 +312,15 @@ int ensure_work(pcm_ctx* c, SmWork* W, size_t N, size_t n_ent, size_t key_bytes,
   }
   W->o_tmp = take(W->tmp_bytes); W->o_tmp2 = take(W->tmp2_bytes);
   if ((rc = W->buf.reserve(c, o, o)) != PCM_OK) return rc;
-  W->n_cap = nc; W->ent_cap = ec;
+  W->n_cap = nc;
   return PCM_OK;
 }
+
+// the per-point arrays of a one-shot workspace go when the call returns (hipFree waits for what is queued on them)
+struct OneShot {
+  SmWork* W;
+  ~OneShot() { W->buf.release(); W->n_cap = 0; }
+};
 
 struct Arena {
   DevBuf<float4> d{"key-frame arena"};
@@ -262,6 +344,8 @@ struct KeyStore {
   uint64_t gen = 1;          // bumps whenever a key frame or a pose changes
   SmWork upd;                // pcm_loam_submap_update
   SmWork ndev[2];            // near clouds: [0] pcm_loam_submap_near, pcm_loam_submap_near_dev and slot 0 of loam_near_queue, [1] slot 1
+  SmWork glob;               // pcm_loam_global_map, pcm_loam_map_export: one_shot
+  KeyStore() { glob.one_shot = true; }
   // the last update
   bool last_valid = false;
   uint64_t last_gen = 0;
@@ -304,6 +388,12 @@ int upload_matrices(pcm_ctx* c, KeyStore* S, size_t first, size_t n) {
   return PCM_OK;
 }
 
+// rows whose `first` holds their count get their first output position
+void entry_positions(SmEntry* ent, size_t rows) {
+  uint32_t first = 0;
+  for (size_t r = 0; r < rows; r++) { const uint32_t n = ent[r].first; ent[r].first = first; first += n; }
+}
+
 // The entry table of `keys`, two rows per key frame, into ent.  wrt_key < 0: every key frame under its own pose; else all under
 // wrt_key's.  interleaved (near): corner, surf, corner, surf, ... in one segment; else (update) all corner clouds, then all surf
 // clouds as segment 1.
@@ -315,8 +405,7 @@ void build_entries(const KeyStore* S, const std::vector<int32_t>& keys, int wrt_
     ent[interleaved ? 2 * i : i] = SmEntry{(uint32_t)k.off_c, k.n_c, mat, 0u};                           // first: the count for now
     ent[interleaved ? 2 * i + 1 : E + i] = SmEntry{(uint32_t)k.off_s, k.n_s, mat, interleaved ? 1u : 3u};
   }
-  uint32_t first = 0;
-  for (size_t r = 0; r < 2 * E; r++) { const uint32_t n = ent[r].first; ent[r].first = first; first += n; }
+  entry_positions(ent, 2 * E);
 }
 
 // corner and surf points of `keys`; more than 2^31 - 1 together: PCM_ERR_OUT_OF_RANGE
@@ -331,7 +420,7 @@ int count_points(pcm_ctx* c, const KeyStore* S, const std::vector<int32_t>& keys
 // segment 0 -> out0, of segment 1 -> out1; the counts and the overflow flag come back through W->h_small.
 int run_pass(pcm_ctx* c, KeyStore* S, SmWork* W, size_t n_ent, uint32_t N, uint32_t n0, float leaf0, float leaf1, float4* out0, float4* out1) {
   hipStream_t st = c->stream;
-  SmEntry* d_ent = W->at<SmEntry>(W->o_ent);
+  SmEntry* d_ent = W->ent;
   unsigned int* mm = W->at<unsigned int>(W->o_mm);
   long long* box = W->at<long long>(W->o_box);
   uint32_t* small = W->at<uint32_t>(W->o_small);
@@ -386,11 +475,11 @@ int check_near_args(pcm_ctx* c, int K, int key, int search_num, int wrt_key, flo
 int queue_near(pcm_ctx* c, KeyStore* S, SmWork* W, const std::vector<int32_t>& keys, int wrt_key, float leaf, uint32_t N, float4* dst, float4** where) {
   hipStream_t st = c->stream;
   const size_t E = 2 * keys.size();
-  int rc = ensure_work(c, W, N, E, sizeof(uint32_t), false);
+  int rc = ensure_work(c, W, N, E, sizeof(uint32_t), false, !W->one_shot || leaf > 0.f, !W->one_shot || !dst);
   if (rc != PCM_OK) return rc;
   if (W->in_flight) { PCM_HIPCK(c, hipStreamSynchronize(st)); W->in_flight = false; }
   build_entries(S, keys, wrt_key, true, W->h_ent);
-  SmEntry* d_ent = W->at<SmEntry>(W->o_ent);
+  SmEntry* d_ent = W->ent;
   if (!dst) dst = W->cells();
   *where = dst;
   W->in_flight = true;
@@ -407,8 +496,14 @@ int queue_near(pcm_ctx* c, KeyStore* S, SmWork* W, const std::vector<int32_t>& k
   uint32_t* keys_u = W->at<uint32_t>(W->o_keys); uint32_t* keys_s = W->at<uint32_t>(W->o_keys_s);
   uint32_t* vals = W->at<uint32_t>(W->o_vals); uint32_t* vals_s = W->at<uint32_t>(W->o_vals_s);
   uint32_t* slot = W->at<uint32_t>(W->o_slot);
-  k_nd_clear<<<1, 64, 0, st>>>(mm, small);
-  k_sm_gather<false><<<nb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, d_ent, (uint32_t)E, N, W->in(), mm);
+  if (W->one_shot) {
+    const unsigned gb = std::min(nb, kGmBlocks);
+    k_gm_gather<true><<<gb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, d_ent, (uint32_t)E, N, W->in(), W->part);
+    k_gm_box<<<1, 256, 0, st>>>(W->part, gb, mm, small);
+  } else {
+    k_nd_clear<<<1, 64, 0, st>>>(mm, small);
+    k_sm_gather<false><<<nb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, d_ent, (uint32_t)E, N, W->in(), mm);
+  }
   k_nd_keys<<<nb, 256, 0, st>>>(W->in(), N, leaf, mm, keys_u, vals, small);
   PCM_HIPCK(c, hipGetLastError());
   size_t tb = W->tmp_bytes, tb2 = W->tmp2_bytes;
@@ -423,21 +518,11 @@ int queue_near(pcm_ctx* c, KeyStore* S, SmWork* W, const std::vector<int32_t>& k
   return PCM_OK;
 }
 
-// pcm_loam_submap_near (memory = PCM_MEM_HOST) and pcm_loam_submap_near_dev, `who` in the error texts
-int near_cloud(pcm_ctx* c, const char* who, int key, int search_num, int wrt_key, float leaf, void* out, size_t cap, int memory, size_t* n_out) {
-  KeyStore* S = nullptr;
-  int rc = check_ctx_sm(c, &S);
-  if (rc != PCM_OK) return rc;
-  if (n_out) *n_out = 0;
-  if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
-  const int K = (int)S->kf.size();
-  if ((rc = check_near_args(c, K, key, search_num, wrt_key, leaf, who)) != PCM_OK) return rc;
-  if (K == 0) return PCM_OK;   // nothing to assemble
-  const std::vector<int32_t> keys = select_near(K, key, search_num);
-  uint64_t n_c = 0, n_s = 0;
-  if ((rc = count_points(c, S, keys, &n_c, &n_s)) != PCM_OK) return rc;
-  const uint32_t N = (uint32_t)(n_c + n_s);
-  if (N == 0) return PCM_OK;
+// The near cloud of `keys` (N >= 1 points) through workspace W into the caller's host or device buffer of cap points; `who` in
+// the error texts.  *n_out is set before a "capacity too small" error.
+int emit_near(pcm_ctx* c, KeyStore* S, SmWork* W, const char* who, const std::vector<int32_t>& keys, int wrt_key, float leaf, uint32_t N, void* out, size_t cap,
+              int memory, size_t* n_out) {
+  int rc = PCM_OK;
   const std::string too_small = std::string(who) + ": capacity too small (the count is set)";
   const bool counted = !(leaf > 0.f);   // without a leaf the count is known before anything runs
   if (counted) {
@@ -445,7 +530,6 @@ int near_cloud(pcm_ctx* c, const char* who, int key, int search_num, int wrt_key
     if (N > cap || !out) { c->err = too_small; return PCM_ERR_INVALID_ARGUMENT; }
   }
   PCM_HIPCK(c, hipSetDevice(c->device));
-  SmWork* W = &S->ndev[0];
   // a device buffer with room for every input point takes the result in place
   const bool in_place = memory == PCM_MEM_DEVICE && out && cap >= N && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
   float4* where = nullptr;
@@ -469,6 +553,51 @@ int near_cloud(pcm_ctx* c, const char* who, int key, int search_num, int wrt_key
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   W->in_flight = false;
   return PCM_OK;
+}
+
+// pcm_loam_submap_near (memory = PCM_MEM_HOST) and pcm_loam_submap_near_dev, `who` in the error texts
+int near_cloud(pcm_ctx* c, const char* who, int key, int search_num, int wrt_key, float leaf, void* out, size_t cap, int memory, size_t* n_out) {
+  KeyStore* S = nullptr;
+  int rc = check_ctx_sm(c, &S);
+  if (rc != PCM_OK) return rc;
+  if (n_out) *n_out = 0;
+  if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  const int K = (int)S->kf.size();
+  if ((rc = check_near_args(c, K, key, search_num, wrt_key, leaf, who)) != PCM_OK) return rc;
+  if (K == 0) return PCM_OK;   // nothing to assemble
+  const std::vector<int32_t> keys = select_near(K, key, search_num);
+  uint64_t n_c = 0, n_s = 0;
+  if ((rc = count_points(c, S, keys, &n_c, &n_s)) != PCM_OK) return rc;
+  const uint32_t N = (uint32_t)(n_c + n_s);
+  if (N == 0) return PCM_OK;
+  return emit_near(c, S, &S->ndev[0], who, keys, wrt_key, leaf, N, out, cap, memory, n_out);
+}
+
+int check_gparams(pcm_ctx* c, const pcm_loam_global_params& p) {
+  if (!(p.search_radius > 0.f) || !finite_f_3e38(p.search_radius)) { c->err = "search_radius must be a positive number"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!(p.keypose_density > 0.f) || !finite_f_3e38(p.keypose_density)) { c->err = "keypose_density must be a positive number"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!(p.leaf >= 0.f) || !finite_f_3e38(p.leaf)) { c->err = "leaf must be >= 0 (0: no down-sampling)"; return PCM_ERR_INVALID_ARGUMENT; }
+  return PCM_OK;
+}
+
+// publishGlobalMap's selection on the store (K >= 1); an overflow of the pose grid: PCM_ERR_OUT_OF_RANGE
+int global_selection(pcm_ctx* c, const KeyStore* S, const pcm_loam_global_params& p, SubmapSelection* sel) {
+  *sel = select_global(S->kp.data(), (int)S->kf.size(), p.search_radius, p.keypose_density);
+  if (sel->status == 0) return PCM_OK;
+  c->err = "keypose_density too small for the extent of the key poses (index overflow)";
+  return PCM_ERR_OUT_OF_RANGE;
+}
+
+// the entry table of pcm_loam_map_export: one row per cloud, in the order the reference concatenates them
+size_t export_entries(const KeyStore* S, int which, int first, int n, SmEntry* ent) {
+  size_t r = 0;
+  for (int arena = which == 1 ? 1 : 0; arena <= (which == 0 ? 0 : 1); arena++)
+    for (int i = first; i < first + n; i++) {
+      const KeyFrame& k = S->kf[(size_t)i];
+      ent[r++] = arena ? SmEntry{(uint32_t)k.off_s, k.n_s, (uint32_t)i, 1u} : SmEntry{(uint32_t)k.off_c, k.n_c, (uint32_t)i, 0u};   // first: the count for now
+    }
+  entry_positions(ent, r);
+  return r;
 }
 
 }  // namespace
@@ -705,7 +834,7 @@ int pcm_loam_submap_update(pcm_ctx* c, const pcm_loam_submap_params* params, dou
   if ((rc = loam_target_reserve(c, (size_t)n_c, (size_t)n_s, &out_c, &out_s)) != PCM_OK) return rc;
   r.num_corner_in = (int32_t)n_c; r.num_surf_in = (int32_t)n_s;
   const uint32_t N = (uint32_t)(n_c + n_s);
-  if ((rc = ensure_work(c, &S->upd, N, 2 * E, sizeof(uint64_t), true)) != PCM_OK) return rc;
+  if ((rc = ensure_work(c, &S->upd, N, 2 * E, sizeof(uint64_t), true, true, false)) != PCM_OK) return rc;
   if (N > 0) {
     PCM_HIPCK(c, hipStreamSynchronize(c->stream));   // the pinned staging of an earlier pass is free again
     build_entries(S, sel.keys, -1, false, S->upd.h_ent);
@@ -737,6 +866,149 @@ int pcm_loam_submap_near(pcm_ctx* c, int key, int search_num, int wrt_key, float
 
 int pcm_loam_submap_near_dev(pcm_ctx* c, int key, int search_num, int wrt_key, float leaf, void* out, size_t cap, int memory, size_t* n_out) {
   return near_cloud(c, "pcm_loam_submap_near_dev", key, search_num, wrt_key, leaf, out, cap, memory, n_out);
+}
+
+void pcm_loam_default_global_params(pcm_loam_global_params* p) {
+  if (!p) return;
+  p->search_radius = 1000.0f;   // utility.h:293
+  p->keypose_density = 10.0f;   // utility.h:294
+  p->leaf = 1.0f;               // utility.h:295
+}
+
+int pcm_loam_global_keys(pcm_ctx* c, const pcm_loam_global_params* params, int32_t* keys, size_t cap, size_t* n) {
+  KeyStore* S = nullptr;
+  int rc = check_ctx_sm(c, &S);
+  if (rc != PCM_OK) return rc;
+  pcm_loam_global_params p;
+  if (params) p = *params; else pcm_loam_default_global_params(&p);
+  if ((rc = check_gparams(c, p)) != PCM_OK) return rc;
+  if (n) *n = 0;
+  if (S->kf.empty()) return PCM_OK;
+  SubmapSelection sel;
+  if ((rc = global_selection(c, S, p, &sel)) != PCM_OK) return rc;
+  if (n) *n = sel.keys.size();
+  if (sel.keys.size() > cap || (!keys && !sel.keys.empty())) { c->err = "pcm_loam_global_keys: capacity too small (the count is set)"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!sel.keys.empty()) std::memcpy(keys, sel.keys.data(), sizeof(int32_t) * sel.keys.size());
+  return PCM_OK;
+}
+
+int pcm_loam_global_map(pcm_ctx* c, const pcm_loam_global_params* params, void* out, size_t cap, int memory, pcm_loam_global_result* result) {
+  KeyStore* S = nullptr;
+  int rc = check_ctx_sm(c, &S);
+  if (rc != PCM_OK) return rc;
+  pcm_loam_global_params p;
+  if (params) p = *params; else pcm_loam_default_global_params(&p);
+  if ((rc = check_gparams(c, p)) != PCM_OK) return rc;
+  if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  pcm_loam_global_result r{};
+  if (result) *result = r;
+  if (S->kf.empty()) return PCM_OK;   // publishGlobalMap :552
+  SubmapSelection sel;
+  if ((rc = global_selection(c, S, p, &sel)) != PCM_OK) return rc;
+  r.num_near = sel.num_near; r.num_pose_leaves = sel.num_pose_leaves; r.num_skipped = sel.num_skipped; r.num_used = (int32_t)sel.keys.size();
+  if (result) *result = r;
+  uint64_t n_c = 0, n_s = 0;
+  if ((rc = count_points(c, S, sel.keys, &n_c, &n_s)) != PCM_OK) return rc;
+  r.points_in = n_c + n_s;
+  if (result) *result = r;
+  if (r.points_in == 0) return PCM_OK;
+  OneShot release{&S->glob};
+  size_t m = 0;
+  rc = emit_near(c, S, &S->glob, "pcm_loam_global_map", sel.keys, -1, p.leaf, (uint32_t)r.points_in, out, cap, memory, &m);
+  r.points_out = m;
+  if (result) *result = r;
+  return rc;
+}
+
+int pcm_loam_map_export(pcm_ctx* c, int which, int first, int n, void* out, size_t cap, int memory, size_t* n_out) {
+  KeyStore* S = nullptr;
+  int rc = check_ctx_sm(c, &S);
+  if (rc != PCM_OK) return rc;
+  if (which < 0 || which > 2) { c->err = "pcm_loam_map_export: which must be 0 (corner), 1 (surf) or 2 (corner then surf)"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (first < 0 || n < 0 || (long long)first + n > (long long)S->kf.size()) { c->err = "pcm_loam_map_export: first + n exceeds the number of key frames"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (n_out) *n_out = 0;
+  uint64_t total = 0;
+  for (int i = first; i < first + n; i++) total += (which != 1 ? S->kf[(size_t)i].n_c : 0u) + (uint64_t)(which != 0 ? S->kf[(size_t)i].n_s : 0u);
+  if (total > 0x7fffffffull) { c->err = "the key frames hold more than 2^31 points: export them in parts"; return PCM_ERR_OUT_OF_RANGE; }
+  const uint32_t N = (uint32_t)total;
+  if (n_out) *n_out = N;
+  if (N == 0) return PCM_OK;
+  if (N > cap || !out) { c->err = "pcm_loam_map_export: capacity too small (the count is set)"; return PCM_ERR_INVALID_ARGUMENT; }
+  PCM_HIPCK(c, hipSetDevice(c->device));
+  SmWork* W = &S->glob;
+  OneShot release{W};
+  const bool in_place = memory == PCM_MEM_DEVICE && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
+  const size_t E = (size_t)n * (which == 2 ? 2 : 1);
+  if ((rc = ensure_work(c, W, N, E, sizeof(uint32_t), false, false, !in_place)) != PCM_OK) return rc;
+  if (W->in_flight) { PCM_HIPCK(c, hipStreamSynchronize(c->stream)); W->in_flight = false; }
+  export_entries(S, which, first, n, W->h_ent);
+  float4* dst = in_place ? static_cast<float4*>(out) : W->cells();
+  W->in_flight = true;
+  PCM_HIPCK(c, hipMemcpyAsync(W->ent, W->h_ent, sizeof(SmEntry) * E, hipMemcpyHostToDevice, c->stream));
+  k_gm_gather<false><<<std::min((N + 255) / 256, kGmBlocks), 256, 0, c->stream>>>(S->arena[0].d, S->arena[1].d, S->mats, W->ent, (uint32_t)E, N, dst, nullptr);
+  PCM_HIPCK(c, hipGetLastError());
+  if (in_place) return PCM_OK;
+  PCM_HIPCK(c, hipMemcpyAsync(out, dst, sizeof(float4) * N, memory == PCM_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+  if (memory == PCM_MEM_HOST) { PCM_HIPCK(c, hipStreamSynchronize(c->stream)); W->in_flight = false; }
+  return PCM_OK;
+}
+
+int pcm_loam_global_gather_ms(pcm_ctx* c, const pcm_loam_global_params* params, int variant, float* ms, uint32_t* box6, size_t* workspace_bytes,
+                              float* workspace_ms) {
+  KeyStore* S = nullptr;
+  int rc = check_ctx_sm(c, &S);
+  if (rc != PCM_OK) return rc;
+  pcm_loam_global_params p;
+  if (params) p = *params; else pcm_loam_default_global_params(&p);
+  if ((rc = check_gparams(c, p)) != PCM_OK) return rc;
+  if ((variant != 0 && variant != 1) || !ms) { c->err = "pcm_loam_global_gather_ms: variant must be 0 or 1 and ms not null"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (S->kf.empty()) { c->err = "the key-frame store is empty"; return PCM_ERR_INVALID_ARGUMENT; }
+  SubmapSelection sel;
+  if ((rc = global_selection(c, S, p, &sel)) != PCM_OK) return rc;
+  uint64_t n_c = 0, n_s = 0;
+  if ((rc = count_points(c, S, sel.keys, &n_c, &n_s)) != PCM_OK) return rc;
+  const uint32_t N = (uint32_t)(n_c + n_s);
+  if (N == 0) { c->err = "the selected key frames are empty"; return PCM_ERR_INVALID_ARGUMENT; }
+  PCM_HIPCK(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  SmWork* W = &S->glob;
+  OneShot release{W};
+  const size_t E = 2 * sel.keys.size();
+  using Clock = std::chrono::steady_clock;
+  const Clock::time_point t0 = Clock::now();
+  if ((rc = ensure_work(c, W, N, E, sizeof(uint32_t), false, true, false)) != PCM_OK) return rc;
+  const Clock::time_point t1 = Clock::now();
+  if (workspace_bytes) *workspace_bytes = W->buf.cap;
+  PCM_HIPCK(c, hipStreamSynchronize(st));
+  W->in_flight = false;
+  build_entries(S, sel.keys, -1, true, W->h_ent);
+  PCM_HIPCK(c, hipMemcpyAsync(W->ent, W->h_ent, sizeof(SmEntry) * E, hipMemcpyHostToDevice, st));
+  unsigned int* mm = W->at<unsigned int>(W->o_mm);
+  uint32_t* small = W->at<uint32_t>(W->o_small);
+  const unsigned nb = (N + 255) / 256, gb = std::min(nb, kGmBlocks);
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  PCM_HIPCK(c, hipEventCreate(&e0));
+  if (hipEventCreate(&e1) != hipSuccess) { hipEventDestroy(e0); c->err = "hipEventCreate failed"; return PCM_ERR_HIP; }
+  hipError_t e = hipEventRecord(e0, st);
+  if (variant == 0) {
+    k_nd_clear<<<1, 64, 0, st>>>(mm, small);
+    k_sm_gather<false><<<nb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, W->ent, (uint32_t)E, N, W->in(), mm);
+  } else {
+    k_gm_gather<true><<<gb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, W->ent, (uint32_t)E, N, W->in(), W->part);
+    k_gm_box<<<1, 256, 0, st>>>(W->part, gb, mm, small);
+  }
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = hipEventRecord(e1, st);
+  if (e == hipSuccess && box6) e = hipMemcpyAsync(box6, mm, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = hipEventElapsedTime(ms, e0, e1);
+  hipEventDestroy(e0); hipEventDestroy(e1);
+  PCM_HIPCK(c, e);
+  const Clock::time_point t2 = Clock::now();
+  W->buf.release();   // the stream is idle: what OneShot would do, timed
+  if (workspace_ms) *workspace_ms = std::chrono::duration<float, std::milli>((t1 - t0) + (Clock::now() - t2)).count();
+  return PCM_OK;
 }
 
 int pcm_loam_submap_info(pcm_ctx* c, int32_t* keys, float* corner_in, float* surf_in, float* corner_map, float* surf_map) {

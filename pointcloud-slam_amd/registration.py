@@ -770,6 +770,17 @@ def _xyzi(a):
     return b
 
 
+def _cloud_buffer(out):
+    """(pointer, capacity, memory) of a contiguous (cap, 4) float32 device tensor or host array."""
+    if hasattr(out, "data_ptr") and getattr(out, "is_cuda", False):
+        if out.dim() != 2 or out.shape[1] != 4 or not out.is_contiguous() or out.element_size() != 4:
+            raise ValueError("expected a contiguous (cap, 4) float32 device tensor")
+        return out.data_ptr(), out.shape[0], capi.MEM_DEVICE
+    if not isinstance(out, np.ndarray) or out.dtype != np.float32 or out.ndim != 2 or out.shape[1] != 4 or not out.flags.c_contiguous:
+        raise ValueError("expected a contiguous (cap, 4) float32 array or device tensor")
+    return out.ctypes.data, out.shape[0], capi.MEM_HOST
+
+
 def _loam_add_keyframe(self, pose6, time, corner=None, surf=None) -> int:
     """saveKeyFramesAndFactor: a key frame with pose6 (roll, pitch, yaw, x, y, z), its time and its (N,4) x y z intensity clouds in
     the body frame.  Without clouds the context's current LOAM source is copied on the device.  Returns the key frame's index."""
@@ -1031,14 +1042,7 @@ def _loam_submap_near_device(self, key: int, search_num: int, wrt_key: int = -1,
     contiguous (cap, 4) float32 device tensor (written on the context's stream; with leaf == 0 the call does not wait) or a
     (cap, 4) float32 host array.  Returns the number of rows written."""
     n = C.c_size_t(0)
-    if hasattr(out, "data_ptr") and getattr(out, "is_cuda", False):
-        if out.dim() != 2 or out.shape[1] != 4 or not out.is_contiguous() or out.element_size() != 4:
-            raise ValueError("expected a contiguous (cap, 4) float32 device tensor")
-        ptr, cap, mem = out.data_ptr(), out.shape[0], capi.MEM_DEVICE
-    else:
-        if not isinstance(out, np.ndarray) or out.dtype != np.float32 or out.ndim != 2 or out.shape[1] != 4 or not out.flags.c_contiguous:
-            raise ValueError("expected a contiguous (cap, 4) float32 array or device tensor")
-        ptr, cap, mem = out.ctypes.data, out.shape[0], capi.MEM_HOST
+    ptr, cap, mem = _cloud_buffer(out)
     rc = self._L.pcm_loam_submap_near_dev(self._h, int(key), int(search_num), int(wrt_key), float(leaf), ptr, cap, mem, C.byref(n))
     self._near_count = n.value
     self._check(rc)
@@ -1410,6 +1414,99 @@ def _loam_global_map(self, out=None):
     a = np.zeros((cr.num_corner + cr.num_surf, 4), np.float32)
     self._check(self._L.pcm_loam_dynmap_global(self._h, a.ctypes.data, a.shape[0], C.byref(n), capi.MEM_HOST))
     return a[:n.value]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# LOAM global map and saved map from the key frames on the device
+# ---------------------------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class LoamGlobalMapResult:
+    num_near: int
+    num_pose_leaves: int
+    num_skipped: int
+    num_used: int
+    points_in: int
+    points_out: int
+
+
+def _global_params(L, params: dict) -> capi.PcmLoamGlobalParams:
+    p = capi.PcmLoamGlobalParams()
+    L.pcm_loam_default_global_params(C.byref(p))
+    for k, v in params.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _loam_keyframe_global_keys(self, **params) -> np.ndarray:
+    """publishGlobalMap's selection (pcm_loam_global_keys): the key frame of every used pose leaf, in list order.  ``leaf`` plays
+    no part in it."""
+    p = _global_params(self._L, params)
+    keys = np.zeros(max(1, self.num_keyframes), np.int32)
+    n = C.c_size_t(0)
+    self._check(self._L.pcm_loam_global_keys(self._h, C.byref(p), keys.ctypes.data, keys.size, C.byref(n)))
+    return keys[:n.value].copy()
+
+
+def _loam_keyframe_global_map(self, out=None, **params):
+    """publishGlobalMap (pcm_loam_global_map; search_radius, keypose_density, leaf).  Without ``out``: the (n, 4) x y z intensity
+    cells on the host.  With a contiguous (cap, 4) float32 device tensor or host array: written there, returns the number of
+    rows.  ``keyframe_global_result`` holds the counts of the last call."""
+    p = _global_params(self._L, params)
+    r = capi.PcmLoamGlobalResult()
+    self._global_result = r
+    if out is not None:
+        ptr, cap, mem = _cloud_buffer(out)
+        rc = self._L.pcm_loam_global_map(self._h, C.byref(p), ptr, cap, mem, C.byref(r))
+        self._check(rc)
+        return int(r.points_out)
+    q = capi.PcmLoamGlobalParams(p.search_radius, p.keypose_density, 0.0)   # without a leaf and a buffer: the host-only query of points_in
+    rc = self._L.pcm_loam_global_map(self._h, C.byref(q), None, 0, capi.MEM_HOST, C.byref(r))
+    if rc != capi.PCM_OK and r.points_in == 0:
+        self._check(rc)
+    a = np.zeros((int(r.points_in), 4), np.float32)
+    self._check(self._L.pcm_loam_global_map(self._h, C.byref(p), a.ctypes.data, a.shape[0], capi.MEM_HOST, C.byref(r)))
+    return a[:int(r.points_out)]
+
+
+def _loam_keyframe_global_result(self) -> LoamGlobalMapResult:
+    r = getattr(self, "_global_result", None)
+    if r is None:
+        raise capi.PcmError(-2, "keyframe_global_result before keyframe_global_map")
+    return LoamGlobalMapResult(r.num_near, r.num_pose_leaves, r.num_skipped, r.num_used, int(r.points_in), int(r.points_out))
+
+
+_EXPORT_WHICH = {0: 0, 1: 1, 2: 2, "corner": 0, "surf": 1, "both": 2}
+
+
+def _loam_export_map(self, which="both", first: int = 0, n: int = None, out=None):
+    """The saved map (pcm_loam_map_export) of key frames first .. first + n - 1 (default: all from ``first``): "corner" = their
+    corner clouds under their poses, "surf" = their surf clouds, "both" = all corner clouds, then all surf clouds (jueying.pcd when
+    the range is the whole store); no VoxelGrid.  Without ``out``: an (N, 4) host array.  With a (cap, 4) float32 device tensor or
+    host array: written there (a device tensor without a wait), returns N."""
+    if n is None:
+        n = self.num_keyframes - first
+    w = _EXPORT_WHICH[which]
+    cnt = C.c_size_t(0)
+    if out is not None:
+        ptr, cap, mem = _cloud_buffer(out)
+        rc = self._L.pcm_loam_map_export(self._h, w, int(first), int(n), ptr, cap, mem, C.byref(cnt))
+        self._export_count = cnt.value
+        self._check(rc)
+        return cnt.value
+    rc = self._L.pcm_loam_map_export(self._h, w, int(first), int(n), None, 0, capi.MEM_HOST, C.byref(cnt))   # the count
+    if rc != capi.PCM_OK and cnt.value == 0:
+        self._check(rc)
+    a = np.zeros((cnt.value, 4), np.float32)
+    self._check(self._L.pcm_loam_map_export(self._h, w, int(first), int(n), a.ctypes.data, a.shape[0], capi.MEM_HOST, C.byref(cnt)))
+    return a
+
+
+LoamRegistration.keyframe_global_keys = _loam_keyframe_global_keys
+LoamRegistration.keyframe_global_map = _loam_keyframe_global_map
+LoamRegistration.keyframe_global_result = property(_loam_keyframe_global_result)
+LoamRegistration.export_map = _loam_export_map
 
 
 def write_arealist(path, areas):
