@@ -230,6 +230,13 @@ int pcm_compute_error(pcm_ctx *ctx, const double T[16], double *cost);
  * holds 4*n floats. */
 int pcm_get_planes(pcm_ctx *ctx, float *out, size_t n);
 
+/* parity hook: the per-voxel candidate lists of a static P2PLANE target (PCM_FLAG_NEIGHBOUR_LISTS) as the device holds them.
+ * info[0] = number of list voxels L, info[1] = number of entries E (pad entries included).  Each of the other arguments may be
+ * NULL: `centres` 4*L floats (the centre of list voxel r in xyz), `starts` L+1 entries (run r = entries starts[r] .. starts[r+1];
+ * every start is a multiple of 4 and a run ends with 0..3 pad entries), `entries` 4*E floats (x, y, z, bit pattern of the point's
+ * index in the map's own array; a pad entry is +inf, +inf, +inf, 0xffffffff).  Fails unless the context holds such lists. */
+int pcm_get_neighbour_lists(pcm_ctx *ctx, uint64_t info[2], float *centres, uint32_t *starts, float *entries);
+
 /* parity hook for PCM_FLAG_LIO_REFERENCE_SEMANTICS: residuals_[i] and point_selected_surf_[i]
  * (jueying_lio/src/laser_mapping.cc:337-338, 619-635) as the last pcm_obs_model left them, in the order of the
  * caller's scan; n must equal the source size. */

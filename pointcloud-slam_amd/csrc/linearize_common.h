@@ -80,9 +80,9 @@ __device__ inline void best_finish(Best& b) {
 // (ivox3d_node.hpp:162) without a double-precision compare per candidate.
 // Sorted insert with strict '<' (an equal distance goes behind the entries
 // already there = visit order); new d[j] = median(d2, d[j-1], d[j]).
-__device__ inline void best_offer(Best& b, const float4& mp, const float (&q)[3], uint32_t id, float max_r2f) {
-  const float dx = mp.x - q[0], dy = mp.y - q[1], dz = mp.z - q[2];
-  const float d2 = dx * dx + dy * dy + dz * dz;  // distance2()  ivox3d_node.hpp:13-16
+// best_offer_d2 takes the squared distance ready-made (a caller that forms the distances of several candidates before the first
+// insert: k_linearize_lists); +inf is never inserted (thr <= max_r2f <= +inf and the compare is strict).
+__device__ inline void best_offer_d2(Best& b, float d2, uint32_t id, float max_r2f) {
   if (d2 < b.thr) {   // in range (d2 < max_r2f) and ahead of the current K-th (strict: an equal distance stays behind)
     {
       const bool c0 = d2 < b.d[0], c1 = d2 < b.d[1], c2 = d2 < b.d[2], c3 = d2 < b.d[3];
@@ -101,6 +101,12 @@ __device__ inline void best_offer(Best& b, const float4& mp, const float (&q)[3]
       b.thr = __uint_as_float(min(__float_as_uint(b.d[4]), __float_as_uint(max_r2f)));
     }
   }
+}
+
+__device__ inline void best_offer(Best& b, const float4& mp, const float (&q)[3], uint32_t id, float max_r2f) {
+  const float dx = mp.x - q[0], dy = mp.y - q[1], dz = mp.z - q[2];
+  const float d2 = dx * dx + dy * dy + dz * dz;  // distance2()  ivox3d_node.hpp:13-16
+  best_offer_d2(b, d2, id, max_r2f);
 }
 
 __device__ inline uint64_t slot_key(const uint4& s) { return ((uint64_t)s.y << 32) | s.x; }

@@ -33,6 +33,12 @@ namespace pcm {
 namespace {
 
 constexpr int kKeyBias = 1 << 20;
+// A run of candidate points (kind 0) is padded to a multiple of kListTrip entries, so with the array's base aligned (hipMalloc: 256
+// bytes) every run starts on a 64-byte boundary and the walk of k_linearize_lists takes whole trips of four 16-byte loads without
+// a bounds test.  A pad entry is (+inf, +inf, +inf, id 0xffffffff): for every finite query pad - q = +inf, its square and the sum
+// of the squares are +inf (with and without FMA contraction), and best_offer's `d2 < thr` with thr <= max_r2f <= +inf is false.
+constexpr uint32_t kListTrip = 4;
+constexpr uint32_t kListPadId = 0xffffffffu;
 
 __device__ inline uint64_t nl_pack(int x, int y, int z) { return ((uint64_t)(uint32_t)(x + kKeyBias) << 42) | ((uint64_t)(uint32_t)(y + kKeyBias) << 21) | (uint64_t)(uint32_t)(z + kKeyBias); }
 
@@ -87,7 +93,8 @@ __device__ inline bool nl_voxel_run(const TargetView& tg, BrickCursor& c, int vx
   return true;
 }
 
-// FILL = false: len[r] = candidates of list voxel r; FILL = true: copy them.  One lane per list voxel.
+// FILL = false: len[r] = candidates of list voxel r, rounded up to a multiple of kListTrip (0 stays 0); FILL = true: copy them and
+// fill the rest of the run with kListPad entries.  One lane per list voxel.
 template <bool FILL>
 __global__ void k_nl_lists(const float4* __restrict__ centres, uint32_t nd, TargetView tg, int nn, uint32_t* __restrict__ len, const uint32_t* __restrict__ start, float4* __restrict__ out) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -109,7 +116,13 @@ __global__ void k_nl_lists(const float4* __restrict__ centres, uint32_t nd, Targ
     }
     n += e - s;
   }
-  if (!FILL) len[r] = n;
+  const uint32_t padded = (n + (kListTrip - 1u)) & ~(kListTrip - 1u);
+  if (FILL) {
+    const float inf = __builtin_inff();
+    for (uint32_t k = n; k < padded; k++) out[o + k] = make_float4(inf, inf, inf, __uint_as_float(kListPadId));
+  } else {
+    len[r] = padded;
+  }
 }
 
 // pclomp NDT: the neighbour LEAVES of every list voxel in the order getNeighborhoodAtPoint{,7,1} / the radius search visit them
@@ -204,15 +217,20 @@ int build_neighbour_lists(hipStream_t stream, const TargetMap& map, int nn, Neig
   const uint32_t nvox = map.num_voxels;
   const size_t nk = (size_t)nvox * nset;
   if (nk >= (1ull << 31) || (size_t)map.num_points * nset >= (1ull << 32)) { *err = "neighbour lists: map too large"; return PCM_ERR_UNSUPPORTED; }
-  {   // room for them?  27 x 16 B per map point for the lists, ~56 B per (voxel, offset) key while they are built; a quarter of the
-      // free memory stays untouched (the caller's next targets, the scratch of the passes)
+  const bool point_lists = !ndt_leaves && !voxel_slots;   // kind 0: runs padded to whole trips (kListTrip)
+  // room for them?  27 x 16 B per map point for the lists (the pad entries of the point lists come on top: checked below, once the
+  // number of lists is known), ~56 B per (voxel, offset) key while they are built; a quarter of the free memory stays untouched
+  // (the caller's next targets, the scratch of the passes)
+  const auto room_for = [&](size_t need) -> int {
     size_t free_b = 0, total_b = 0;
-    const size_t need = ((ndt_leaves || voxel_slots) ? (size_t)nvox : (size_t)map.num_points) * nset * sizeof(float4) + nk * 56 + ((size_t)64 << 20);
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b - free_b / 4) {
       *err = "neighbour lists: " + std::to_string(need >> 20) + " MiB needed, " + std::to_string(free_b >> 20) + " MiB of device memory free";
       return PCM_ERR_HIP;
     }
-  }
+    return PCM_OK;
+  };
+  const size_t list_entries = (point_lists ? (size_t)map.num_points : (size_t)nvox) * nset;
+  if (const int rc = room_for(list_entries * sizeof(float4) + nk * 56 + ((size_t)64 << 20)); rc != PCM_OK) return rc;
   uint64_t *keys = nullptr, *keys_s = nullptr;
   uint32_t *flag = nullptr, *pos = nullptr, *d_cnt = nullptr, *len = nullptr;
   float4* centres = nullptr;
@@ -261,7 +279,11 @@ int build_neighbour_lists(hipStream_t stream, const TargetMap& map, int nn, Neig
       out->valid = true;
       return PCM_OK;
     }
-    // list lengths -> starts -> candidates
+    // list lengths -> starts -> candidates.  A point list ends with at most kListTrip - 1 pad entries: the 32-bit starts and the
+    // memory must hold them too (the temporaries of the build are still allocated here, so only the lists themselves are asked for)
+    const size_t pad_max = point_lists ? (size_t)nd * (kListTrip - 1) : 0;
+    if (list_entries + pad_max >= (1ull << 32)) { *err = "neighbour lists: map too large"; return PCM_ERR_UNSUPPORTED; }
+    if (pad_max && (rc = room_for((list_entries + pad_max) * sizeof(float4) + ((size_t)64 << 20))) != PCM_OK) return rc;
     if ((rc = out->start.reserve(stream, err, (size_t)nd + 1, (size_t)nd + 1)) != PCM_OK) return rc;
     PCM_HIPCK_ERR(err, hipMallocAsync(reinterpret_cast<void**>(&len), sizeof(uint32_t) * ((size_t)nd + 1), stream));
     PCM_HIPCK_ERR(err, hipMemsetAsync(len, 0, sizeof(uint32_t) * ((size_t)nd + 1), stream));
@@ -274,7 +296,9 @@ int build_neighbour_lists(hipStream_t stream, const TargetMap& map, int nn, Neig
     PCM_HIPCK_ERR(err, hipMemcpyAsync(&h_cnt[1], out->start + nd, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
     const size_t total = h_cnt[1];
-    // + 4: the walk of k_linearize_lists reads (never uses) up to three entries past a run
+    // The starts of the point lists are multiples of kListTrip entries = 64 bytes and DevBuf's hipMalloc returns at least 256-byte
+    // aligned memory, so every run starts on a 64-byte boundary; `total` counts the pad entries, so the last trip of the last run
+    // ends inside the array.  + 4: the walk of the leaf lists (pclndt.hip) reads (never uses) up to three entries past a run.
     if ((rc = out->pts.reserve(stream, err, total + 4, total + 4)) != PCM_OK) return rc;
     PCM_HIPCK_ERR(err, hipMemsetAsync(out->pts + total, 0, sizeof(float4) * 4, stream));
     if (ndt_leaves) k_nl_leaf_lists<true><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of_map(map), mode, ndt_leaves, nn, nullptr, out->start, out->pts);
@@ -300,6 +324,12 @@ int build_neighbour_lists(hipStream_t stream, const TargetMap& map, int nn, Neig
   if (tmp3) (void)hipFreeAsync(tmp3, stream);
   if (rc != PCM_OK) out->valid = false;
   return rc;
+}
+
+// distance2() of ivox3d_node.hpp:13-16, the operations of best_offer in its order
+__device__ inline float list_d2(const float4& mp, const float (&q)[3]) {
+  const float dx = mp.x - q[0], dy = mp.y - q[1], dz = mp.z - q[2];
+  return dx * dx + dy * dy + dz * dz;
 }
 
 // ---------------------------------------------------------------------------
@@ -344,14 +374,17 @@ __global__ void __launch_bounds__(256) k_linearize_lists(const PairDesc* __restr
           const uint32_t s = gload_u(&nl.vox_start[r]), e = gload_u(&nl.vox_start[r + 1]);
           Best best;
           best_init(best, kp.max_range_sq);
-          // the voxel's candidates in the reference's visit order, four per trip (all four loads under way before the first offer;
-          // the array is padded, a load past the run is never offered)
-          for (uint32_t k = s; k < e; k += 4) {
+          // the voxel's candidates in the reference's visit order, four per trip.  The run is padded to whole trips and starts on a
+          // 64-byte boundary (build_neighbour_lists), so e - s is a multiple of four: no bounds test, all four loads under way and all
+          // four distances formed before the first offer.  A load past the run's true end is a pad entry (d2 = +inf) and is never
+          // inserted; the offers go in visit order, each against the thr the earlier ones left.
+          for (uint32_t k = s; k < e; k += kListTrip) {
             const float4 c0 = gload4(nl.pts + k), c1 = gload4(nl.pts + k + 1), c2 = gload4(nl.pts + k + 2), c3 = gload4(nl.pts + k + 3);
-            best_offer(best, c0, q, k, kp.max_range_sq);
-            if (k + 1 < e) best_offer(best, c1, q, k + 1, kp.max_range_sq);
-            if (k + 2 < e) best_offer(best, c2, q, k + 2, kp.max_range_sq);
-            if (k + 3 < e) best_offer(best, c3, q, k + 3, kp.max_range_sq);
+            const float d0 = list_d2(c0, q), d1 = list_d2(c1, q), d2 = list_d2(c2, q), d3 = list_d2(c3, q);
+            best_offer_d2(best, d0, k, kp.max_range_sq);
+            best_offer_d2(best, d1, k + 1, kp.max_range_sq);
+            best_offer_d2(best, d2, k + 2, kp.max_range_sq);
+            best_offer_d2(best, d3, k + 3, kp.max_range_sq);
           }
           best_finish(best);
           if (best.m >= KMIN) {   // laser_mapping.cc:619-623

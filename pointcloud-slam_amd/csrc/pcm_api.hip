@@ -1159,6 +1159,19 @@ int pcm_get_planes(pcm_ctx* c, float* out, size_t n) {
   return PCM_OK;
 }
 
+int pcm_get_neighbour_lists(pcm_ctx* c, uint64_t info[2], float* centres, uint32_t* starts, float* entries) {
+  CHECK_CTX(c);
+  const pcm::NeighbourLists& nl = c->nlists;
+  if (!info || !nl.valid || nl.kind != 0) { c->err = "pcm_get_neighbour_lists: the context holds no candidate lists of points (P2PLANE, static target, lists built)"; return PCM_ERR_INVALID_ARGUMENT; }
+  info[0] = nl.num_lists;
+  info[1] = nl.num_candidates;
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
+  if (centres) PCM_HIPCK(c, hipMemcpy(centres, nl.index.pts.p, sizeof(float4) * nl.num_lists, hipMemcpyDeviceToHost));
+  if (starts) PCM_HIPCK(c, hipMemcpy(starts, nl.start.p, sizeof(uint32_t) * ((size_t)nl.num_lists + 1), hipMemcpyDeviceToHost));
+  if (entries && nl.num_candidates) PCM_HIPCK(c, hipMemcpy(entries, nl.pts.p, sizeof(float4) * nl.num_candidates, hipMemcpyDeviceToHost));
+  return PCM_OK;
+}
+
 int pcm_get_lio_members(pcm_ctx* c, float* residuals, uint8_t* selected, size_t n) {
   CHECK_CTX(c);
   if (!(c->cfg.flags & PCM_FLAG_LIO_REFERENCE_SEMANTICS) || !c->lio_aux || n != c->lio_aux_n || n != c->src.n) {

@@ -401,6 +401,16 @@ class Registration:
             self._check(self._L.pcm_get_target(self._h, out.ctypes.data, n.value, C.byref(n)))
         return out
 
+    def get_neighbour_lists(self):
+        """The target's per-voxel candidate lists as the device holds them (pcm_get_neighbour_lists): the list voxels' centres (L,3),
+        the starts (L+1,) and the entries as xyz (E,3) and point index (E,) -- a pad entry is +inf with index 0xffffffff."""
+        info = np.zeros(2, np.uint64)
+        self._check(self._L.pcm_get_neighbour_lists(self._h, info.ctypes.data, None, None, None))
+        nl, ne = int(info[0]), int(info[1])
+        centres, starts, entries = np.zeros((nl, 4), np.float32), np.zeros(nl + 1, np.uint32), np.zeros((ne, 4), np.float32)
+        self._check(self._L.pcm_get_neighbour_lists(self._h, info.ctypes.data, centres.ctypes.data, starts.ctypes.data, entries.ctypes.data))
+        return centres[:, :3].copy(), starts, entries[:, :3].copy(), entries[:, 3].copy().view(np.uint32)
+
     def get_planes(self, n: int) -> np.ndarray:
         """(n,4) planes fitted by the last evaluate_cost (NaN row = point not selected)."""
         out = np.zeros((n, 4), np.float32)
