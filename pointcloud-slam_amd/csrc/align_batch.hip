@@ -15,7 +15,6 @@
 #include <atomic>
 #include <chrono>
 #include <cstring>
-#include <new>
 #include <thread>
 
 namespace pcm {
@@ -76,9 +75,9 @@ bool same_solver_config(const pcm_config& a, const pcm_config& b) {
 // objects), so independent batches may run concurrently from different host threads
 // on their own streams -- e.g. the stragglers of one batch under the bulk of the next.
 int ensure_ws(pcm_ctx* c, Workspace** out, int npairs, size_t partial_doubles, int rounds) {
-  if (!c->ws) c->ws = new (std::nothrow) Workspace();
-  if (!c->ws) { c->err = "out of host memory"; return PCM_ERR_HIP; }
-  Workspace& w = *static_cast<Workspace*>(c->ws);
+  Workspace* wp = c->ws.get_or_create<Workspace>();
+  if (!wp) { c->err = "out of host memory"; return PCM_ERR_HIP; }
+  Workspace& w = *wp;
   w.device = c->device;
   const size_t np = (size_t)npairs, cap = (size_t)std::max(npairs, 64);
   int rc = w.d_descs.reserve(c, np, cap);
@@ -108,15 +107,6 @@ int ensure_ws(pcm_ctx* c, Workspace** out, int npairs, size_t partial_doubles, i
   }
   *out = &w;
   return PCM_OK;
-}
-
-void free_ws(pcm_ctx* c) {
-  Workspace* w = static_cast<Workspace*>(c->ws);
-  if (!w) return;
-  for (hipEvent_t e : w->ev_round) hipEventDestroy(e);
-  for (hipEvent_t e : w->ev_prof) hipEventDestroy(e);
-  delete w;
-  c->ws = nullptr;
 }
 
 int align_batch_impl(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_result* host_out, void* device_out) {
@@ -390,16 +380,10 @@ struct NdtBatchWs {
   PinnedBuf<unsigned char> h_flags{"h_flags"};   // mapped pinned: [round][object] status bytes of k_pclndt_batch_step
   unsigned char* d_flags = nullptr;              // device view of h_flags
   hipStream_t gst[4] = {nullptr, nullptr, nullptr, nullptr};   // streams of the lock-step groups, created back to back
+  ~NdtBatchWs() { for (hipStream_t st : gst) if (st) (void)hipStreamDestroy(st); }
 };
 
 }  // namespace
-
-void free_ndt_batch_ws(void* p) {
-  NdtBatchWs* w = static_cast<NdtBatchWs*>(p);
-  if (!w) return;
-  for (hipStream_t st : w->gst) if (st) (void)hipStreamDestroy(st);
-  delete w;
-}
 
 // pclomp::NormalDistributionsTransform::computeTransformation (ndt_omp_impl.hpp:69-156) for n objects: their solvers run on the
 // device (ndtomp::NdtMachine, pclndt_host.h), one derivatives launch + one step launch per round for all of them
@@ -410,9 +394,9 @@ int pclndt_align_batch(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_re
     if (rc != PCM_OK) { if (i) c0->err = ctxs[i]->err; return rc; }
     if (ctxs[i]->stream != c0->stream) PCM_HIPCK(c0, hipStreamSynchronize(ctxs[i]->stream));   // its map / leaves were built on its own stream
   }
-  if (!c0->ndt_ws) c0->ndt_ws = new (std::nothrow) NdtBatchWs();
-  if (!c0->ndt_ws) { c0->err = "out of host memory"; return PCM_ERR_HIP; }
-  NdtBatchWs& w = *static_cast<NdtBatchWs*>(c0->ndt_ws);
+  NdtBatchWs* wp = c0->ndt_ws.get_or_create<NdtBatchWs>();
+  if (!wp) { c0->err = "out of host memory"; return PCM_ERR_HIP; }
+  NdtBatchWs& w = *wp;
   {
     const size_t cap = (size_t)std::max(n, 16);
     int rc = w.d_objs.reserve(c0, (size_t)n, cap);

@@ -10,7 +10,6 @@
 #include <algorithm>
 #include <cfloat>
 #include <cstring>
-#include <new>
 #include <vector>
 
 using namespace pcm;
@@ -30,12 +29,8 @@ struct LoamCtx {
   bool src_has_int = false;    // src_int is current
   bool src_from_fe = false;    // the source came from the front end (its intensity lives in loam_features.hip's output)
   uint64_t src_fe_gen = 0;     // generation of that output when the source was committed
-  bool tgt_from_submap = false;   // the target clouds are what loam_target_commit left
-  void* keystore = nullptr;    // key frames and submap workspace (loam_submap.hip)
-  void* scstore = nullptr;     // Scan Context descriptors and loop-detection workspace (loam_sc.hip)
-  bool tgt_from_dynmap = false;   // the target clouds are what loam_target_commit_dynmap left
-  void* dynstore = nullptr;    // localisation map tiles and crop workspace (loam_dynmap.hip)
-  void* loopstore = nullptr;   // loop verifier: the pclomp NDT context of pcm_loam_loop_verify (loam_loop.hip)
+  TargetOwner tgt_owner = TargetOwner::caller;   // who wrote the target clouds (loam_target_commit)
+  SubState store[4];           // by LoamStore
   uint32_t n_c = 0, n_s = 0;
   DevBuf<double> partials;
   DevBuf<LoamState> st;
@@ -44,15 +39,11 @@ struct LoamCtx {
   PinnedBuf<LoamDesc> h_desc;  // staging of the same
 };
 
-LoamCtx* loam_of(pcm_ctx* c) {
-  if (!c->loam) c->loam = new (std::nothrow) LoamCtx();
-  return static_cast<LoamCtx*>(c->loam);
-}
+LoamCtx* loam_of(pcm_ctx* c) { return c->loam.get_or_create<LoamCtx>(); }
 
 int check_ctx(pcm_ctx* c) {
-  if (!c) return PCM_ERR_INVALID_ARGUMENT;
-  if (c->device < 0) return PCM_ERR_HIP;
-  if (c->cfg.model != PCM_MODEL_LOAM) { c->err = "pcm_loam_* needs a context created with PCM_MODEL_LOAM"; return PCM_ERR_UNSUPPORTED; }
+  const int rc = loam_check_ctx(c, PCM_ERR_UNSUPPORTED, "pcm_loam_* needs a context created with PCM_MODEL_LOAM");
+  if (rc != PCM_OK) return rc;
   if (!loam_of(c)) { c->err = "out of host memory"; return PCM_ERR_INTERNAL; }
   return PCM_OK;
 }
@@ -336,18 +327,6 @@ int probe(pcm_ctx* c, const float* x6, float* corner_out, float* surf_out, doubl
 }  // namespace
 
 namespace pcm {
-void loam_release(pcm_ctx* c) {
-  loam_features_release(c);
-  LoamCtx* L = static_cast<LoamCtx*>(c->loam);
-  if (!L) return;
-  for (int m = 0; m < 2; m++) L->map[m].release();
-  if (L->keystore) loam::loam_keystore_release(L->keystore);
-  if (L->scstore) loam::loam_scstore_release(L->scstore);
-  if (L->dynstore) loam::loam_dynstore_release(L->dynstore);
-  if (L->loopstore) loam::loam_loopstore_release(L->loopstore);
-  delete L;
-  c->loam = nullptr;
-}
 namespace loam {
 int loam_source_reserve(pcm_ctx* c, size_t n, float4** feats) {
   int rc = check_ctx(c);
@@ -378,8 +357,7 @@ int loam_target_reserve(pcm_ctx* c, size_t n_corner, size_t n_surf, float4** cor
   if (rc != PCM_OK) return rc;
   LoamCtx* L = loam_of(c);
   L->have_tgt = false;
-  L->tgt_from_submap = false;
-  L->tgt_from_dynmap = false;
+  L->tgt_owner = TargetOwner::caller;
   L->built_cell = 0.f;
   L->map[0].valid = L->map[1].valid = false;
   L->map_n[0] = L->map_n[1] = 0;
@@ -390,18 +368,18 @@ int loam_target_reserve(pcm_ctx* c, size_t n_corner, size_t n_surf, float4** cor
   return PCM_OK;
 }
 
-void loam_target_commit(pcm_ctx* c, uint32_t n_corner, uint32_t n_surf) {
+void loam_target_commit(pcm_ctx* c, uint32_t n_corner, uint32_t n_surf, TargetOwner owner) {
   LoamCtx* L = loam_of(c);
   L->map_n[0] = n_corner;
   L->map_n[1] = n_surf;
   L->tgt_tag = 0;
   L->have_tgt = true;
-  L->tgt_from_submap = true;
+  L->tgt_owner = owner;
 }
 
-bool loam_target_view(pcm_ctx* c, const float4** corner, uint32_t* n_corner, const float4** surf, uint32_t* n_surf) {
+bool loam_target_view(pcm_ctx* c, TargetOwner owner, const float4** corner, uint32_t* n_corner, const float4** surf, uint32_t* n_surf) {
   LoamCtx* L = loam_of(c);
-  if (!L || !L->have_tgt || !L->tgt_from_submap) return false;
+  if (!L || !L->have_tgt || L->tgt_owner != owner) return false;
   *corner = L->map_pts[0]; *n_corner = (uint32_t)L->map_n[0];
   *surf = L->map_pts[1]; *n_surf = (uint32_t)L->map_n[1];
   return true;
@@ -423,39 +401,9 @@ int loam_source_view(pcm_ctx* c, const float4** feats, uint32_t* n_c, uint32_t* 
   return 0;
 }
 
-void** loam_keystore_slot(pcm_ctx* c) {
+SubState* loam_store_holder(pcm_ctx* c, LoamStore which) {
   LoamCtx* L = loam_of(c);
-  return L ? &L->keystore : nullptr;
-}
-
-void** loam_scstore_slot(pcm_ctx* c) {
-  LoamCtx* L = loam_of(c);
-  return L ? &L->scstore : nullptr;
-}
-
-void loam_target_commit_dynmap(pcm_ctx* c, uint32_t n_corner, uint32_t n_surf) {
-  loam_target_commit(c, n_corner, n_surf);
-  LoamCtx* L = loam_of(c);
-  L->tgt_from_submap = false;   // not the submap's: pcm_loam_submap_update must rebuild
-  L->tgt_from_dynmap = true;
-}
-
-bool loam_target_view_dynmap(pcm_ctx* c, const float4** corner, uint32_t* n_corner, const float4** surf, uint32_t* n_surf) {
-  LoamCtx* L = loam_of(c);
-  if (!L || !L->have_tgt || !L->tgt_from_dynmap) return false;
-  *corner = L->map_pts[0]; *n_corner = (uint32_t)L->map_n[0];
-  *surf = L->map_pts[1]; *n_surf = (uint32_t)L->map_n[1];
-  return true;
-}
-
-void** loam_dynstore_slot(pcm_ctx* c) {
-  LoamCtx* L = loam_of(c);
-  return L ? &L->dynstore : nullptr;
-}
-
-void** loam_loopstore_slot(pcm_ctx* c) {
-  LoamCtx* L = loam_of(c);
-  return L ? &L->loopstore : nullptr;
+  return L ? &L->store[(int)which] : nullptr;
 }
 }  // namespace loam
 }  // namespace pcm
@@ -482,8 +430,7 @@ int pcm_loam_set_target(pcm_ctx* c, const void* corner, size_t n_c, const void* 
   if ((rc = check_cloud(c, corner, n_c, stride)) != PCM_OK || (rc = check_cloud(c, surf, n_s, stride)) != PCM_OK) return rc;
   PCM_HIPCK(c, hipSetDevice(c->device));
   L->have_tgt = false;
-  L->tgt_from_submap = false;
-  L->tgt_from_dynmap = false;
+  L->tgt_owner = TargetOwner::caller;
   L->built_cell = 0.f;
   L->map[0].valid = L->map[1].valid = false;
   if ((rc = load_cloud(c, L, 0, corner, n_c, stride, memory)) != PCM_OK) return rc;

@@ -1,10 +1,12 @@
-// loam_device.h -- what the LOAM scan-to-map kernels (loam.hip) and their host side (loam_api.hip) share.
+// loam_device.h -- what the LOAM scan-to-map kernels (loam.hip) and their host side (loam_api.hip) share, and what the LOAM
+// operators share among themselves: the context check, the stores, the target's owner, the point arena.
 #pragma once
 
+#include <algorithm>
+
+#include "host_util.h"
 #include "loam_step.h"
 #include "pcm_device.h"
-
-struct pcm_ctx;
 
 namespace pcm {
 namespace loam {
@@ -36,20 +38,58 @@ void launch_round(hipStream_t stream, const LoamDesc* d_descs, int n, uint32_t m
 int loam_source_reserve(pcm_ctx* c, size_t n, float4** feats);
 void loam_source_commit(pcm_ctx* c, uint32_t n_c, uint32_t n_s);
 
+// what every pcm_loam_* entry point asks first: a context, a usable device, PCM_MODEL_LOAM.  The operators answer another model
+// with different codes and texts, and callers may depend on them: each passes its own.
+inline int loam_check_ctx(pcm_ctx* c, int not_loam, const char* not_loam_msg) {
+  if (!c) return PCM_ERR_INVALID_ARGUMENT;
+  if (c->device < 0) return PCM_ERR_HIP;
+  if (c->cfg.model != PCM_MODEL_LOAM) { c->err = not_loam_msg; return not_loam; }
+  return PCM_OK;
+}
 
-// loam_api.hip: the key-frame submap (loam_submap.hip) writes the context's two target clouds in place: room for the clouds, then
-// their sizes once they are known (the state pcm_loam_set_target leaves, grids not built yet: the next align builds them)
+// loam_api.hip: who wrote the context's two target clouds.  The key-frame submap (loam_submap.hip) and the map-tile crop
+// (loam_dynmap.hip) write them in place: room for the clouds (the owner falls back to the caller, as after a real
+// pcm_loam_set_target), then their sizes and the writer once they are known (the state pcm_loam_set_target leaves, grids not built
+// yet: the next align builds them).  Each keeps its result only while loam_target_view still names it the owner, so neither
+// mistakes the other's target for the one it left.
+enum class TargetOwner { caller, submap, dynmap };
 int loam_target_reserve(pcm_ctx* c, size_t n_corner, size_t n_surf, float4** corner, float4** surf);
-void loam_target_commit(pcm_ctx* c, uint32_t n_corner, uint32_t n_surf);
-// the target clouds in caller order, and whether they are still what the last loam_target_commit left
-bool loam_target_view(pcm_ctx* c, const float4** corner, uint32_t* n_corner, const float4** surf, uint32_t* n_surf);
+void loam_target_commit(pcm_ctx* c, uint32_t n_corner, uint32_t n_surf, TargetOwner owner);
+// the target clouds in caller order; false: there is no target, or `owner` did not write it
+bool loam_target_view(pcm_ctx* c, TargetOwner owner, const float4** corner, uint32_t* n_corner, const float4** surf, uint32_t* n_surf);
 // the current source as PointXYZI pieces: feats (xyz, w = index), and the intensity either as whole records (xyzi, the front
 // end's output) or as one float per feature (inten); both null: intensity 0.  Returns 0, 1 without a source, 2 when the source
 // came from the front end and its output has been rewritten since (pcm_loam_extract_features on the same context, a failed frame).
 int loam_source_view(pcm_ctx* c, const float4** feats, uint32_t* n_c, uint32_t* n_s, const float4** xyzi, const float** inten);
-// the key-frame store of a context (pcm_ctx::loam owns the pointer, loam_submap.hip the type)
-void** loam_keystore_slot(pcm_ctx* c);
-void loam_keystore_release(void* store);
+// The stores of a context: the key frames and submap workspace (loam_submap.hip), the Scan Context descriptors (loam_sc.hip), the
+// map tiles and crop workspace (loam_dynmap.hip), the loop verifier (loam_loop.hip).  The context's LOAM state owns the holders,
+// each of those files its type.  loam_store: the store, made on first use when `create`; null: none yet, or out of host memory.
+enum class LoamStore { key, sc, dyn, loop };
+SubState* loam_store_holder(pcm_ctx* c, LoamStore which);   // null: the LOAM state itself could not be allocated
+template <class T> T* loam_store(pcm_ctx* c, LoamStore which, bool create) {
+  SubState* h = loam_store_holder(c, which);
+  return !h ? nullptr : create ? h->get_or_create<T>() : h->get<T>();
+}
+// loam_check_ctx, then the store (the texts: no LOAM state, no store; both for want of host memory)
+template <class T> int loam_check_store(pcm_ctx* c, const char* not_loam_msg, LoamStore which, T** out, bool create = true, const char* oom_msg = "out of host memory",
+                                        const char* store_oom_msg = "out of host memory") {
+  *out = nullptr;
+  const int rc = loam_check_ctx(c, PCM_ERR_INVALID_ARGUMENT, not_loam_msg);
+  if (rc != PCM_OK) return rc;
+  SubState* h = loam_store_holder(c, which);
+  if (!h) { c->err = oom_msg; return PCM_ERR_INTERNAL; }
+  *out = create ? h->get_or_create<T>() : h->get<T>();
+  if (!*out && create) { c->err = store_oom_msg; return PCM_ERR_INTERNAL; }
+  return PCM_OK;
+}
+// a grow-only array of points a store appends to (what: its name in an error text)
+struct Arena {
+  DevBuf<float4> d;
+  size_t n = 0;
+  explicit Arena(const char* what) : d(what) {}
+  // room for `extra` more points; growth copies device to device.  The first allocation holds at least 65 536 points.
+  int reserve(pcm_ctx* c, size_t extra) { return d.reserve_keep(c, n + extra, std::max<size_t>(n + extra, d.cap + d.cap / 2 + 65536), n); }
+};
 // loam_submap.hip: one stored cloud of a key frame on the device (which: 0 corner, 1 surf; false: no such key frame), and the host
 // mirror of the key poses (returns K)
 bool loam_keyframe_cloud(pcm_ctx* c, int key, int which, const float4** pts, uint32_t* n);
@@ -63,19 +103,6 @@ int loam_keyposes(pcm_ctx* c, const KeyPose** kp);
 struct NearCloud { const float4* pts; uint32_t n_in; const uint32_t* h_small; };
 int loam_near_queue(pcm_ctx* c, int slot, int key, int search_num, int wrt_key, float leaf, NearCloud* out);
 void loam_near_waited(pcm_ctx* c);
-// the loop verifier of a context (pcm_ctx::loam owns the pointer, loam_loop.hip the type)
-void** loam_loopstore_slot(pcm_ctx* c);
-void loam_loopstore_release(void* store);
-// the Scan Context store of a context (pcm_ctx::loam owns the pointer, loam_sc.hip the type)
-void** loam_scstore_slot(pcm_ctx* c);
-void loam_scstore_release(void* store);
-// the localisation map tiles of a context (pcm_ctx::loam owns the pointer, loam_dynmap.hip the type); its crop writes the target
-// in place through loam_target_reserve and commits it as its own, so that neither it nor the submap mistakes the other's target
-// for the one it left
-void** loam_dynstore_slot(pcm_ctx* c);
-void loam_dynstore_release(void* store);
-void loam_target_commit_dynmap(pcm_ctx* c, uint32_t n_corner, uint32_t n_surf);
-bool loam_target_view_dynmap(pcm_ctx* c, const float4** corner, uint32_t* n_corner, const float4** surf, uint32_t* n_surf);
 
 // loam_features.hip: pieces of the segmented VoxelGrid that do not depend on where the elements live
 struct SvWork {
@@ -92,9 +119,7 @@ int sv_sort_cells(pcm_ctx* c0, hipStream_t st, const SvWork& W, uint32_t N, uint
 bool loam_features_last_out(pcm_ctx* c, const float4** out, uint32_t* n_c, uint32_t* n_s, uint64_t* gen);
 
 #if defined(__HIPCC__)
-// floats as unsigned integers of the same order (atomicMin / atomicMax on bounding boxes)
-__device__ inline unsigned int f2ord(float f) { const unsigned int u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-// inverse of f2ord, branch-free (the select form crashes this compiler's instruction selection when followed by float arithmetic)
+// inverse of pcm_device.h's f2ord, branch-free (the select form crashes this compiler's instruction selection when followed by float arithmetic)
 __device__ inline float ord2f(unsigned int o) { const unsigned int m = (unsigned int)((int)o >> 31); return __uint_as_float(o ^ (~m | 0x80000000u)); }
 
 // 64-lane butterfly reductions (every lane ends with the result).  The double sum adds in this fixed order, so its bits do not

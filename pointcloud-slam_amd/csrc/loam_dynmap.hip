@@ -10,7 +10,7 @@
 //                 ballot and a popcount per wave, one count per workgroup;
 //   k_dm_scan_*   exclusive scan of the workgroup counts: 256 counts per scan block, then the block totals in one workgroup;
 //   k_dm_scatter  the predicate again, the lane's rank from the ballot, the whole 16-byte record to its place in the context's
-//                 corner or surf target cloud (loam_target_reserve / loam_target_commit_dynmap).
+//                 corner or surf target cloud (loam_target_reserve / loam_target_commit).
 // The only atomic is the integer counter of dropped non-finite points: no output position depends on the schedule, so two crops
 // of one state give the same bits.  When selection, limits and crop_x equal those of the last crop and the target is still its
 // result, the call does nothing at all (a standing robot, the relocalisation branch's second scan2MapOptimization).
@@ -20,7 +20,6 @@
 
 #include <algorithm>
 #include <cstring>
-#include <new>
 #include <vector>
 
 using namespace pcm;
@@ -151,13 +150,6 @@ __global__ void __launch_bounds__(kDmBlock) k_dm_scatter(const float4* __restric
   if (seg1) out1[off - small[0]] = p; else out0[off] = p;
 }
 
-struct Arena {
-  DevBuf<float4> d{"map-tile arena"};
-  size_t n = 0;
-  // room for `extra` more points; growth copies device to device.  The first allocation holds at least 65 536 points.
-  int reserve(pcm_ctx* c, size_t extra) { return d.reserve_keep(c, n + extra, std::max<size_t>(n + extra, d.cap + d.cap / 2 + 65536), n); }
-};
-
 struct Tile {
   Area box;
   size_t off;
@@ -166,7 +158,7 @@ struct Tile {
 
 struct DynStore {
   std::vector<Tile> tiles[2];   // corner list, surf list
-  Arena arena[2];
+  Arena arena[2] = {Arena("map-tile arena"), Arena("map-tile arena")};
   // the selection of the last load
   bool loaded = false;
   std::vector<int32_t> sel[2];
@@ -186,15 +178,7 @@ struct DynStore {
 };
 
 int check_ctx_dm(pcm_ctx* c, DynStore** ds) {
-  if (!c) return PCM_ERR_INVALID_ARGUMENT;
-  if (c->device < 0) return PCM_ERR_HIP;
-  if (c->cfg.model != PCM_MODEL_LOAM) { c->err = "pcm_loam_tile_* / pcm_loam_dynmap_* need a context created with PCM_MODEL_LOAM"; return PCM_ERR_INVALID_ARGUMENT; }
-  void** slot = loam_dynstore_slot(c);
-  if (!slot) { c->err = "out of host memory"; return PCM_ERR_INTERNAL; }
-  if (!*slot) *slot = new (std::nothrow) DynStore();
-  if (!*slot) { c->err = "out of host memory"; return PCM_ERR_INTERNAL; }
-  *ds = static_cast<DynStore*>(*slot);
-  return PCM_OK;
+  return loam_check_store(c, "pcm_loam_tile_* / pcm_loam_dynmap_* need a context created with PCM_MODEL_LOAM", LoamStore::dyn, ds);
 }
 
 int check_dparams(pcm_ctx* c, const pcm_loam_dynmap_params* params, const float* pose6, pcm_loam_dynmap_params* p) {
@@ -232,16 +216,6 @@ bool same_window(const CropWindow& a, const CropWindow& b) {
 }
 
 }  // namespace
-
-namespace pcm {
-namespace loam {
-void loam_dynstore_release(void* store) {
-  DynStore* S = static_cast<DynStore*>(store);
-  if (!S) return;
-  delete S;
-}
-}  // namespace loam
-}  // namespace pcm
 
 extern "C" {
 
@@ -354,7 +328,7 @@ int pcm_loam_dynmap_crop(pcm_ctx* c, const pcm_loam_dynmap_params* params, const
   const CropWindow w = crop_window(pose6, p.max_range, p.margin, p.crop_x);
   const float4 *tc = nullptr, *ts = nullptr;
   uint32_t tnc = 0, tns = 0;
-  if (S->last_valid && S->last_gen == S->sel_gen && same_window(S->last_w, w) && loam_target_view_dynmap(c, &tc, &tnc, &ts, &tns)) {
+  if (S->last_valid && S->last_gen == S->sel_gen && same_window(S->last_w, w) && loam_target_view(c, TargetOwner::dynmap, &tc, &tnc, &ts, &tns)) {
     // the same tiles through the same window: the target is the one the context already holds
     *result = S->last;
     result->rebuilt = 0;
@@ -410,7 +384,7 @@ int pcm_loam_dynmap_crop(pcm_ctx* c, const pcm_loam_dynmap_params* params, const
     r.num_surf = (int32_t)(k - k0);
     r.num_nonfinite = (int32_t)S->h_small[2];
   }
-  loam_target_commit_dynmap(c, (uint32_t)r.num_corner, (uint32_t)r.num_surf);
+  loam_target_commit(c, (uint32_t)r.num_corner, (uint32_t)r.num_surf, TargetOwner::dynmap);
   r.rebuilt = 1;
   r.status = PCM_OK;
   S->last_valid = true;
@@ -431,7 +405,7 @@ int pcm_loam_dynmap_info(pcm_ctx* c, int32_t* corner_tiles, int32_t* surf_tiles,
   if (!corner && !surf) return PCM_OK;
   const float4 *tc = nullptr, *ts = nullptr;
   uint32_t tnc = 0, tns = 0;
-  if (!S->last_valid || !loam_target_view_dynmap(c, &tc, &tnc, &ts, &tns)) { c->err = "pcm_loam_dynmap_info: the context's target is not the result of pcm_loam_dynmap_crop"; return PCM_ERR_NO_INPUT; }
+  if (!S->last_valid || !loam_target_view(c, TargetOwner::dynmap, &tc, &tnc, &ts, &tns)) { c->err = "pcm_loam_dynmap_info: the context's target is not the result of pcm_loam_dynmap_crop"; return PCM_ERR_NO_INPUT; }
   PCM_HIPCK(c, hipSetDevice(c->device));
   if (corner && tnc) PCM_HIPCK(c, hipMemcpyAsync(corner, tc, sizeof(float4) * tnc, hipMemcpyDeviceToHost, c->stream));
   if (surf && tns) PCM_HIPCK(c, hipMemcpyAsync(surf, ts, sizeof(float4) * tns, hipMemcpyDeviceToHost, c->stream));
@@ -447,7 +421,7 @@ int pcm_loam_dynmap_global(pcm_ctx* c, void* out, size_t capacity, size_t* n, in
   if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
   const float4 *tc = nullptr, *ts = nullptr;
   uint32_t tnc = 0, tns = 0;
-  if (!S->last_valid || !loam_target_view_dynmap(c, &tc, &tnc, &ts, &tns)) { c->err = "pcm_loam_dynmap_global: the context's target is not the result of pcm_loam_dynmap_crop"; return PCM_ERR_NO_INPUT; }
+  if (!S->last_valid || !loam_target_view(c, TargetOwner::dynmap, &tc, &tnc, &ts, &tns)) { c->err = "pcm_loam_dynmap_global: the context's target is not the result of pcm_loam_dynmap_crop"; return PCM_ERR_NO_INPUT; }
   const size_t m = (size_t)tnc + tns;
   if (n) *n = m;
   if (m > capacity || (!out && m)) { c->err = "pcm_loam_dynmap_global: capacity too small (the count is set)"; return PCM_ERR_INVALID_ARGUMENT; }

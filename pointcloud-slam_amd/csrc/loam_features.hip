@@ -22,7 +22,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <new>
 #include <vector>
 
 using namespace pcm;
@@ -647,10 +646,7 @@ struct FeatState {
   DevBuf<char> ws;
 };
 
-FeatState* fe_of(pcm_ctx* c) {
-  if (!c->loam_fe) c->loam_fe = new (std::nothrow) FeatState();
-  return static_cast<FeatState*>(c->loam_fe);
-}
+FeatState* fe_of(pcm_ctx* c) { return c->loam_fe.get_or_create<FeatState>(); }
 
 int check_fparams(pcm_ctx* c, const pcm_loam_feature_params& p) {
   if (p.n_scan < 1 || p.horizon_scan < 2) { c->err = "n_scan must be >= 1 and horizon_scan >= 2"; return PCM_ERR_INVALID_ARGUMENT; }
@@ -800,7 +796,7 @@ void sv_temp_bytes(size_t n, size_t* sort_bytes, size_t* scan_bytes) {
 
 // the context's last front-end features with their averaged intensity (k_lf_finish's F.out), alive until the next frame
 bool loam_features_last_out(pcm_ctx* c, const float4** out, uint32_t* n_c, uint32_t* n_s, uint64_t* gen) {
-  FeatState* S = static_cast<FeatState*>(c->loam_fe);
+  const FeatState* S = c->loam_fe.get<FeatState>();
   if (!S || !S->have_last || !S->out) return false;
   *gen = S->out_gen;
   *out = S->out; *n_c = S->last.n_corner; *n_s = S->last.n_surf;
@@ -832,9 +828,8 @@ LfParams dev_params(const pcm_loam_feature_params& q) {
 }
 
 int check_ctx_fe(pcm_ctx* c) {
-  if (!c) return PCM_ERR_INVALID_ARGUMENT;
-  if (c->device < 0) return PCM_ERR_HIP;
-  if (c->cfg.model != PCM_MODEL_LOAM) { c->err = "pcm_loam_* needs a context created with PCM_MODEL_LOAM"; return PCM_ERR_UNSUPPORTED; }
+  const int rc = loam::loam_check_ctx(c, PCM_ERR_UNSUPPORTED, "pcm_loam_* needs a context created with PCM_MODEL_LOAM");
+  if (rc != PCM_OK) return rc;
   if (!fe_of(c)) { c->err = "out of host memory"; return PCM_ERR_INTERNAL; }
   return PCM_OK;
 }
@@ -986,15 +981,6 @@ int run_frames(pcm_ctx* const* ctxs, int B, const void* const* points, const siz
 void copy_xyzi(const float4* d, size_t n, float* host) { for (size_t i = 0; i < n; i++) { host[4 * i] = d[i].x; host[4 * i + 1] = d[i].y; host[4 * i + 2] = d[i].z; host[4 * i + 3] = d[i].w; } }
 
 }  // namespace
-
-namespace pcm {
-void loam_features_release(pcm_ctx* c) {
-  FeatState* S = static_cast<FeatState*>(c->loam_fe);
-  if (!S) return;
-  delete S;
-  c->loam_fe = nullptr;
-}
-}  // namespace pcm
 
 extern "C" {
 

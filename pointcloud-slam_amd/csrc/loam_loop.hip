@@ -17,7 +17,6 @@
 
 #include <cfloat>
 #include <cstring>
-#include <new>
 
 using namespace pcm;
 using namespace pcm::loam;
@@ -26,18 +25,11 @@ namespace {
 
 struct LoopStore {
   pcm_ctx* verifier = nullptr;
+  ~LoopStore() { if (verifier) pcm_destroy(verifier); }
 };
 
 int check_ctx_loop(pcm_ctx* c, LoopStore** ls) {
-  if (!c) return PCM_ERR_INVALID_ARGUMENT;
-  if (c->device < 0) return PCM_ERR_HIP;
-  if (c->cfg.model != PCM_MODEL_LOAM) { c->err = "pcm_loam_loop_* needs a context created with PCM_MODEL_LOAM"; return PCM_ERR_INVALID_ARGUMENT; }
-  void** slot = loam_loopstore_slot(c);
-  if (!slot) { c->err = "out of host memory"; return PCM_ERR_INTERNAL; }
-  if (!*slot) *slot = new (std::nothrow) LoopStore();
-  if (!*slot) { c->err = "out of host memory"; return PCM_ERR_INTERNAL; }
-  *ls = static_cast<LoopStore*>(*slot);
-  return PCM_OK;
+  return loam_check_store(c, "pcm_loam_loop_* needs a context created with PCM_MODEL_LOAM", LoamStore::loop, ls);
 }
 
 int check_lparams(pcm_ctx* c, const pcm_loam_loop_params& p) {
@@ -148,17 +140,6 @@ static_assert(PCM_LOAM_LOOP_ACCEPTED == loop::kAccepted && PCM_LOAM_LOOP_REJECTE
               "status codes");
 
 }  // namespace
-
-namespace pcm {
-namespace loam {
-void loam_loopstore_release(void* store) {
-  LoopStore* S = static_cast<LoopStore*>(store);
-  if (!S) return;
-  if (S->verifier) pcm_destroy(S->verifier);
-  delete S;
-}
-}  // namespace loam
-}  // namespace pcm
 
 extern "C" {
 

@@ -17,7 +17,6 @@
 
 #include <algorithm>
 #include <cstring>
-#include <new>
 #include <vector>
 
 using namespace pcm;
@@ -243,18 +242,8 @@ struct ScStore {
 
 // create = false (queries): *out stays null when the context has no store yet, and none is made
 int check_ctx_sc(pcm_ctx* c, ScStore** out, bool create = true) {
-  *out = nullptr;
-  if (!c) return PCM_ERR_INVALID_ARGUMENT;
-  if (c->device < 0) return PCM_ERR_HIP;
-  if (c->cfg.model != PCM_MODEL_LOAM) { c->err = "pcm_loam_sc_* / pcm_loam_loop_detect_distance need a context created with PCM_MODEL_LOAM"; return PCM_ERR_INVALID_ARGUMENT; }
-  void** slot = loam_scstore_slot(c);
-  if (!slot) { c->err = "the context's LOAM state could not be allocated (out of host memory)"; return PCM_ERR_INTERNAL; }
-  if (!*slot && create) {
-    *slot = new (std::nothrow) ScStore();
-    if (!*slot) { c->err = "the Scan Context store could not be allocated (out of host memory)"; return PCM_ERR_INTERNAL; }
-  }
-  *out = static_cast<ScStore*>(*slot);
-  return PCM_OK;
+  return loam_check_store(c, "pcm_loam_sc_* / pcm_loam_loop_detect_distance need a context created with PCM_MODEL_LOAM", LoamStore::sc, out, create,
+                          "the context's LOAM state could not be allocated (out of host memory)", "the Scan Context store could not be allocated (out of host memory)");
 }
 
 int check_scparams(pcm_ctx* c, const ScStore* S, const pcm_loam_sc_params& p) {
@@ -318,16 +307,6 @@ void launch_distance(pcm_ctx* c, ScStore* S, uint32_t q, const int32_t* cand, ui
 }
 
 }  // namespace
-
-namespace pcm {
-namespace loam {
-void loam_scstore_release(void* store) {
-  ScStore* S = static_cast<ScStore*>(store);
-  if (!S) return;
-  delete S;
-}
-}  // namespace loam
-}  // namespace pcm
 
 extern "C" {
 

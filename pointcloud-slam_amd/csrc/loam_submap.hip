@@ -39,7 +39,6 @@
 
 #include <chrono>
 #include <cstring>
-#include <new>
 #include <vector>
 
 using namespace pcm;
@@ -322,13 +321,6 @@ struct OneShot {
   ~OneShot() { W->buf.release(); W->n_cap = 0; }
 };
 
-struct Arena {
-  DevBuf<float4> d{"key-frame arena"};
-  size_t n = 0;
-  // room for `extra` more points; growth copies device to device
-  int reserve(pcm_ctx* c, size_t extra) { return d.reserve_keep(c, n + extra, std::max<size_t>(n + extra, d.cap + d.cap / 2 + 65536), n); }
-};
-
 struct KeyFrame {
   float pose[6];   // roll, pitch, yaw, x, y, z
   double time;
@@ -339,7 +331,7 @@ struct KeyFrame {
 struct KeyStore {
   std::vector<KeyFrame> kf;
   std::vector<KeyPose> kp;   // what the selection reads
-  Arena arena[2];            // corner, surf
+  Arena arena[2] = {Arena("key-frame arena"), Arena("key-frame arena")};   // corner, surf
   DevBuf<float> mats{"key-frame matrices"};   // [K][12]
   uint64_t gen = 1;          // bumps whenever a key frame or a pose changes
   SmWork upd;                // pcm_loam_submap_update
@@ -355,15 +347,7 @@ struct KeyStore {
 };
 
 int check_ctx_sm(pcm_ctx* c, KeyStore** ks) {
-  if (!c) return PCM_ERR_INVALID_ARGUMENT;
-  if (c->device < 0) return PCM_ERR_HIP;
-  if (c->cfg.model != PCM_MODEL_LOAM) { c->err = "pcm_loam_keyframe_* / pcm_loam_submap_* need a context created with PCM_MODEL_LOAM"; return PCM_ERR_INVALID_ARGUMENT; }
-  void** slot = loam_keystore_slot(c);
-  if (!slot) { c->err = "out of host memory"; return PCM_ERR_INTERNAL; }
-  if (!*slot) *slot = new (std::nothrow) KeyStore();
-  if (!*slot) { c->err = "out of host memory"; return PCM_ERR_INTERNAL; }
-  *ks = static_cast<KeyStore*>(*slot);
-  return PCM_OK;
+  return loam_check_store(c, "pcm_loam_keyframe_* / pcm_loam_submap_* need a context created with PCM_MODEL_LOAM", LoamStore::key, ks);
 }
 
 void host_matrix(const float* pose6, float* T12) {
@@ -604,15 +588,8 @@ size_t export_entries(const KeyStore* S, int which, int first, int n, SmEntry* e
 
 namespace pcm {
 namespace loam {
-void loam_keystore_release(void* store) {
-  KeyStore* S = static_cast<KeyStore*>(store);
-  if (!S) return;
-  delete S;
-}
-
 bool loam_keyframe_cloud(pcm_ctx* c, int key, int which, const float4** pts, uint32_t* n) {
-  void** slot = loam_keystore_slot(c);
-  const KeyStore* S = slot ? static_cast<const KeyStore*>(*slot) : nullptr;
+  const KeyStore* S = loam_store<KeyStore>(c, LoamStore::key, false);
   if (!S || key < 0 || (size_t)key >= S->kf.size()) return false;
   const KeyFrame& k = S->kf[(size_t)key];
   *pts = S->arena[which ? 1 : 0].d + (which ? k.off_s : k.off_c);
@@ -621,16 +598,14 @@ bool loam_keyframe_cloud(pcm_ctx* c, int key, int which, const float4** pts, uin
 }
 
 bool loam_keyframe_pose(pcm_ctx* c, int key, float pose6[6]) {
-  void** slot = loam_keystore_slot(c);
-  const KeyStore* S = slot ? static_cast<const KeyStore*>(*slot) : nullptr;
+  const KeyStore* S = loam_store<KeyStore>(c, LoamStore::key, false);
   if (!S || key < 0 || (size_t)key >= S->kf.size()) return false;
   for (int a = 0; a < 6; a++) pose6[a] = S->kf[(size_t)key].pose[a];
   return true;
 }
 
 int loam_keyposes(pcm_ctx* c, const KeyPose** kp) {
-  void** slot = loam_keystore_slot(c);
-  const KeyStore* S = slot ? static_cast<const KeyStore*>(*slot) : nullptr;
+  const KeyStore* S = loam_store<KeyStore>(c, LoamStore::key, false);
   *kp = S ? S->kp.data() : nullptr;
   return S ? (int)S->kf.size() : 0;
 }
@@ -656,8 +631,7 @@ int loam_near_queue(pcm_ctx* c, int slot, int key, int search_num, int wrt_key, 
 }
 
 void loam_near_waited(pcm_ctx* c) {
-  void** slot = loam_keystore_slot(c);
-  KeyStore* S = slot ? static_cast<KeyStore*>(*slot) : nullptr;
+  KeyStore* S = loam_store<KeyStore>(c, LoamStore::key, false);
   if (S) S->ndev[0].in_flight = S->ndev[1].in_flight = false;
 }
 }  // namespace loam
@@ -816,7 +790,7 @@ int pcm_loam_submap_update(pcm_ctx* c, const pcm_loam_submap_params* params, dou
   const float4 *tc = nullptr, *ts = nullptr;
   uint32_t tnc = 0, tns = 0;
   if (S->last_valid && S->last_gen == S->gen && S->last_leaf[0] == p.corner_leaf && S->last_leaf[1] == p.surf_leaf && S->last_keys == sel.keys &&
-      loam_target_view(c, &tc, &tnc, &ts, &tns)) {
+      loam_target_view(c, TargetOwner::submap, &tc, &tnc, &ts, &tns)) {
     // same key frames in the same order under the same poses and leaves: the maps are the ones the context already holds
     r.num_corner_in = S->last.num_corner_in; r.num_surf_in = S->last.num_surf_in;
     r.num_corner_map = S->last.num_corner_map; r.num_surf_map = S->last.num_surf_map;
@@ -848,7 +822,7 @@ int pcm_loam_submap_update(pcm_ctx* c, const pcm_loam_submap_params* params, dou
     r.num_corner_map = (int32_t)S->upd.h_small[0];
     r.num_surf_map = (int32_t)S->upd.h_small[1];
   }
-  loam_target_commit(c, (uint32_t)r.num_corner_map, (uint32_t)r.num_surf_map);
+  loam_target_commit(c, (uint32_t)r.num_corner_map, (uint32_t)r.num_surf_map, TargetOwner::submap);
   r.rebuilt = 1;
   r.status = PCM_OK;
   S->last_valid = true;
@@ -1017,7 +991,7 @@ int pcm_loam_submap_info(pcm_ctx* c, int32_t* keys, float* corner_in, float* sur
   if (rc != PCM_OK) return rc;
   const float4 *tc = nullptr, *ts = nullptr;
   uint32_t tnc = 0, tns = 0;
-  if (!S->last_valid || !loam_target_view(c, &tc, &tnc, &ts, &tns)) { c->err = "pcm_loam_submap_info: the context's target is not the result of pcm_loam_submap_update"; return PCM_ERR_NO_INPUT; }
+  if (!S->last_valid || !loam_target_view(c, TargetOwner::submap, &tc, &tnc, &ts, &tns)) { c->err = "pcm_loam_submap_info: the context's target is not the result of pcm_loam_submap_update"; return PCM_ERR_NO_INPUT; }
   PCM_HIPCK(c, hipSetDevice(c->device));
   if (keys && !S->last_keys.empty()) std::memcpy(keys, S->last_keys.data(), sizeof(int32_t) * S->last_keys.size());
   const size_t n_c = (size_t)S->last.num_corner_in, n_s = (size_t)S->last.num_surf_in;

@@ -15,7 +15,6 @@
 
 #include <algorithm>
 #include <cstring>
-#include <new>
 #include <vector>
 
 using namespace pcm;
@@ -161,11 +160,8 @@ int check_ctx_occ(pcm_ctx* c, OccMap** out, bool need_params) {
   *out = nullptr;
   if (!c) return PCM_ERR_INVALID_ARGUMENT;
   if (c->device < 0) return PCM_ERR_HIP;
-  if (!c->occ) {
-    c->occ = new (std::nothrow) OccMap();
-    if (!c->occ) { c->err = "the occupancy map could not be allocated (out of host memory)"; return PCM_ERR_INTERNAL; }
-  }
-  *out = static_cast<OccMap*>(c->occ);
+  *out = c->occ.get_or_create<OccMap>();
+  if (!*out) { c->err = "the occupancy map could not be allocated (out of host memory)"; return PCM_ERR_INTERNAL; }
   if (need_params && (*out)->beams == 0) { c->err = "no occupancy map yet: call pcm_occ_reset first"; return PCM_ERR_NO_INPUT; }
   return PCM_OK;
 }
@@ -374,15 +370,6 @@ int read_back(pcm_ctx* c, OccMap* M, void* dst, const void* src, size_t bytes, s
 }
 
 }  // namespace
-
-namespace pcm {
-void occ_release(pcm_ctx* c) {
-  OccMap* M = static_cast<OccMap*>(c->occ);
-  if (!M) return;
-  delete M;
-  c->occ = nullptr;
-}
-}  // namespace pcm
 
 extern "C" {
 

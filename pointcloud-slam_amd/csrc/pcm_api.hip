@@ -162,14 +162,9 @@ void pcm_destroy(pcm_ctx* c) {
   if (c->device >= 0) {
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
-    free_ndt_batch_ws(c->ndt_ws);
-    c->ndt_ws = nullptr;
-    free_ws(c);
-    loam_release(c);
-    occ_release(c);
   }
-  // The context's own buffers (the DevBuf / PinnedBuf members of pcm_ctx, its clouds, maps and lists) free themselves here:
-  // `delete c` runs with the device current and before the context's stream is destroyed.
+  // The context's own buffers (the DevBuf / PinnedBuf members of pcm_ctx, its clouds, maps and lists) and its sub-states (the
+  // SubState members) free themselves here: `delete c` runs with the device current and before the context's stream is destroyed.
   hipStream_t own = (c->device >= 0 && c->own_stream) ? c->stream : nullptr;
   delete c;
   if (own) hipStreamDestroy(own);

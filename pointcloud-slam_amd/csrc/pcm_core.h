@@ -51,10 +51,12 @@ struct Workspace {
   SortScratch sort;
   std::vector<hipEvent_t> ev_round;
   std::vector<hipEvent_t> ev_prof;
+  ~Workspace() {
+    for (hipEvent_t e : ev_round) hipEventDestroy(e);
+    for (hipEvent_t e : ev_prof) hipEventDestroy(e);
+  }
 };
 int ensure_ws(pcm_ctx* c, Workspace** out, int npairs, size_t partial_doubles, int rounds);
-void free_ws(pcm_ctx* c);
-void free_ndt_batch_ws(void* p);   // pcm_ctx::ndt_ws
 
 int align_batch_impl(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_result* host_out, void* device_out);
 // one LINEARIZE or TRIAL pass at a caller-supplied pose (parity hook)

@@ -155,6 +155,8 @@ __device__ inline void gstore4(float4* p, const float4& v) { *(PCM_GLOBAL pcm_v4
 __device__ inline void gstore_f(float* p, float v) { *(PCM_GLOBAL float*)p = v; }
 __device__ inline void gstore_d(double* p, double v) { *(PCM_GLOBAL double*)p = v; }
 __device__ inline double gload_d(const double* p) { return *(const PCM_GLOBAL double*)p; }
+// floats as unsigned integers of the same order (atomicMin / atomicMax on bounding boxes)
+__device__ inline unsigned int f2ord(float f) { const unsigned int u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 #endif
 
 // pose-dependent constants of one pclomp NDT derivatives pass (kernel argument, filled on the host by pclndt_host.h)

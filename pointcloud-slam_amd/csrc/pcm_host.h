@@ -12,6 +12,7 @@
 #include "lio_iekf.h"
 #include "lsq_step.h"
 #include "pcm_device.h"
+#include "sub_state.h"
 
 namespace pcm {
 
@@ -174,17 +175,16 @@ void launch_pclndt_pass(hipStream_t stream, const TargetMap& map, const PclLeaf*
                         double gauss_d3 = 0.0);   // pass 3: calculateScore (needs gauss_d3)
 void launch_init_states(hipStream_t stream, PairState* d_states, const float* d_guesses, int npairs, int max_iterations, int window, unsigned int* d_queue);
 void launch_pack_results(hipStream_t stream, const PairState* d_states, pcm_result* d_results, int npairs);
-// loam_api.hip: the maps, scan and device state of a PCM_MODEL_LOAM context (pcm_ctx::loam)
-void loam_release(pcm_ctx* c);
-// loam_features.hip: the front end's cross-frame state of a PCM_MODEL_LOAM context (pcm_ctx::loam_fe)
-void loam_features_release(pcm_ctx* c);
-// occ_map.hip: the 2D occupancy map of a context (pcm_ctx::occ)
-void occ_release(pcm_ctx* c);
 
 }  // namespace pcm
 
 // A device array of the context is a DevBuf member (pinned host memory: a PinnedBuf): it frees itself when pcm_destroy deletes the
 // context, with the device current and before the stream goes.  Nothing is added to pcm_destroy for it.
+// State whose type one translation unit keeps to itself is a SubState member (sub_state.h), made on first use by that unit and
+// deleted at the same point under the same guarantee: device current, stream synchronised, stream still alive.  What such a
+// state must undo beyond its own members (events, streams, an inner context) is its destructor's business, and a new one needs
+// nothing but its member here.  A context with device < 0 never makes one -- every creator tests the device first (CHECK_CTX,
+// check_ctx_occ, loam_check_ctx) -- so deleting it touches no HIP call.
 struct pcm_ctx {
   int device = 0;
   pcm_config cfg{};
@@ -231,17 +231,17 @@ struct pcm_ctx {
   int lio_upd_calls = 0;                    // ObsModel calls the trace of the last update holds
   pcm::DevBuf<char> lio_prop{"lio_prop"};    // pcm_lio_propagate: the uploaded frame block and the downloaded result block (lio_predict.hip)
   pcm::PinnedBuf<char> lio_prop_host{"lio_prop_host"};   // their pinned host image
-  void* ws = nullptr;   // batch workspace owned by this context (align_batch.hip)
-  void* ndt_ws = nullptr;   // pclomp NDT: objects + solver machines of a batch (align_batch.hip)
+  pcm::SubState ws;       // pcm::Workspace: batch workspace owned by this context (align_batch.hip)
+  pcm::SubState ndt_ws;   // pclomp NDT: objects + solver machines of a batch (align_batch.hip)
   pcm::DevBuf<char> pre_arena{"pre_arena"};   // grow-only device scratch of the pre-processing operators
   pcm::DevBuf<char> bfgs{"bfgs"};             // GICP-BFGS functor: packed correspondence records + partial sums (gicp_bfgs.hip)
   size_t bfgs_m = 0;
   std::vector<double> user_cov[2];   // [0] source, [1] target: covariances handed in by the caller (6 per point, input order); empty = compute
   pcm::DevBuf<int32_t> bfgs_idx{"bfgs_idx"};   // source indices of the packed pairs in the first half, target indices in the second (device-side correspondence step)
   pcm::PinnedBuf<double> bfgs_host{"bfgs_host"};   // pinned, device-visible: the 14 sums land here without a copy command
-  void* loam = nullptr;   // PCM_MODEL_LOAM: maps, features and device state (loam_api.hip)
-  void* loam_fe = nullptr;   // PCM_MODEL_LOAM: the front end's cross-frame state and last-frame outputs (loam_features.hip)
-  void* occ = nullptr;   // any model: the 2D occupancy map (occ_map.hip)
+  pcm::SubState loam;      // PCM_MODEL_LOAM: maps, features, device state and the stores (loam_api.hip)
+  pcm::SubState loam_fe;   // PCM_MODEL_LOAM: the front end's cross-frame state and last-frame outputs (loam_features.hip)
+  pcm::SubState occ;       // any model: the 2D occupancy map (occ_map.hip)
   // any model: scan fusion (scan_fuse.hip): staged host segments, the fused records (pcm_scan_fused), counters + tables + scan scratch
   pcm::DevBuf<char> scan_in{"scan_in"}, scan_out{"scan_out"}, scan_tmp{"scan_tmp"};
   size_t scan_n = 0;     // records of the last pcm_scan_fuse with out = NULL that scan_out still holds

@@ -111,7 +111,7 @@ int undistort_device(hipStream_t stream, void* d_points, size_t n, size_t stride
 // ---------------------------------------------------------------------------
 namespace {
 
-__device__ inline unsigned int f2ord(float f) { const unsigned int u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }   // order-preserving
+// inverse of pcm_device.h's f2ord on the host
 inline float ord2f(unsigned int o) { const unsigned int u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o; float f; std::memcpy(&f, &u, 4); return f; }
 
 __global__ void k_vg_minmax(const char* __restrict__ base, size_t stride, uint32_t n, unsigned int* __restrict__ mm /* min xyz, max xyz (ordered ints), count */) {
