@@ -104,104 +104,8 @@ struct NearCloud { const float4* pts; uint32_t n_in; const uint32_t* h_small; };
 int loam_near_queue(pcm_ctx* c, int slot, int key, int search_num, int wrt_key, float leaf, NearCloud* out);
 void loam_near_waited(pcm_ctx* c);
 
-// loam_features.hip: pieces of the segmented VoxelGrid that do not depend on where the elements live
-struct SvWork {
-  uint64_t* keys; uint64_t* keys_s; uint32_t* vals; uint32_t* vals_s;   // [N]; after sv_sort_cells vals holds the first sorted element of every cell
-  uint32_t* head; uint32_t* slot;                                      // [N]
-  uint32_t* scnt; uint32_t* sfirst;                                    // [nseg] cells per segment, first cell of the segment
-  uint32_t* nc;                                                        // [0] cells, [1] valid elements (zeroed by the caller)
-  void* tmp; size_t tmp_bytes; void* tmp2; size_t tmp2_bytes;          // rocprim scratch (sv_temp_bytes)
-};
-void sv_temp_bytes(size_t n, size_t* sort_bytes, size_t* scan_bytes);
-void sv_clear(hipStream_t st, unsigned int* mm, uint32_t* scnt, uint32_t nseg);
-int sv_sort_cells(pcm_ctx* c0, hipStream_t st, const SvWork& W, uint32_t N, uint32_t nseg);
-// gen: bumps whenever the output array is rewritten
+// loam_features.hip: the context's last front-end features.  gen: bumps whenever the output array is rewritten
 bool loam_features_last_out(pcm_ctx* c, const float4** out, uint32_t* n_c, uint32_t* n_s, uint64_t* gen);
-
-#if defined(__HIPCC__)
-// inverse of pcm_device.h's f2ord, branch-free (the select form crashes this compiler's instruction selection when followed by float arithmetic)
-__device__ inline float ord2f(unsigned int o) { const unsigned int m = (unsigned int)((int)o >> 31); return __uint_as_float(o ^ (~m | 0x80000000u)); }
-
-// 64-lane butterfly reductions (every lane ends with the result).  The double sum adds in this fixed order, so its bits do not
-// depend on the schedule; linearize_common.h's DPP reductions are another order and stay apart.
-__device__ inline uint32_t wave_min_u32(uint32_t v) {
-  for (int off = 32; off >= 1; off >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, off, 64));
-  return v;
-}
-__device__ inline uint32_t wave_max_u32(uint32_t v) {
-  for (int off = 32; off >= 1; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off, 64));
-  return v;
-}
-__device__ inline uint32_t wave_sum_u32(uint32_t v) {
-  for (int off = 32; off >= 1; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, 64);
-  return v;
-}
-__device__ inline uint64_t wave_min_u64(uint64_t v) {
-  for (int off = 32; off >= 1; off >>= 1) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off, 64);
-    const uint64_t o = ((uint64_t)hi << 32) | lo;
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ inline double wave_sum_f64(double v) {
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// a lane's point into the bounding box of its segment (mm: 6 ordered-int words per segment, min then max)
-__device__ inline void sv_wave_minmax(bool valid, uint32_t seg, const float4& pt, unsigned int* __restrict__ mm) {
-  unsigned int lo[3], hi[3];
-  const float c[3] = {pt.x, pt.y, pt.z};
-  for (int a = 0; a < 3; a++) { lo[a] = valid ? f2ord(c[a]) : 0xffffffffu; hi[a] = valid ? f2ord(c[a]) : 0u; }
-  // one atomic per wave when every valid lane shares the segment
-  const uint64_t vm = __ballot(valid);
-  if (vm == 0) return;
-  const int l0 = __ffsll((unsigned long long)vm) - 1;
-  const uint32_t s0 = (uint32_t)__shfl((int)seg, l0, 64);
-  const bool same = __ballot(valid && seg != s0) == 0;
-  if (same) {
-    for (int off = 32; off >= 1; off >>= 1)
-      for (int a = 0; a < 3; a++) { lo[a] = min(lo[a], (unsigned int)__shfl_xor((int)lo[a], off, 64)); hi[a] = max(hi[a], (unsigned int)__shfl_xor((int)hi[a], off, 64)); }
-    if ((threadIdx.x & 63) == 0)
-      for (int a = 0; a < 3; a++) { atomicMin(&mm[6 * s0 + a], lo[a]); atomicMax(&mm[6 * s0 + 3 + a], hi[a]); }
-  } else if (valid) {
-    for (int a = 0; a < 3; a++) { atomicMin(&mm[6 * seg + a], lo[a]); atomicMax(&mm[6 * seg + 3 + a], hi[a]); }
-  }
-}
-
-// the box of pcl::VoxelGrid from a segment's min / max: b = {min_b x, y, z, divb_mul[1], divb_mul[2], state} (state 0: empty or no
-// leaf, 1: index overflow, 2: valid).  The products are formed in double: exact, as a valid box has fewer than 2^31 cells.
-// Returns whether the index overflows.
-__device__ inline bool sv_box(const unsigned int* __restrict__ mm, float leaf, long long* __restrict__ b) {
-  b[5] = 0;
-  if (mm[0] == 0xffffffffu) return false;   // empty segment
-  if (!(leaf > 0.f)) return false;
-  const float inv = 1.0f / leaf;
-  float mn[3], mx[3];
-  for (int a = 0; a < 3; a++) { mn[a] = ord2f(mm[a]); mx[a] = ord2f(mm[3 + a]); }
-  double cells = 1.0;
-  for (int a = 0; a < 3; a++) cells *= trunc((double)((mx[a] - mn[a]) * inv)) + 1.0;   // int64_t((max - min) * inv) + 1, max >= min
-  const bool over = cells > 2147483647.0;
-  int mb[3], xb[3];
-  for (int a = 0; a < 3; a++) { mb[a] = (int)floorf(mn[a] * inv); xb[a] = (int)floorf(mx[a] * inv); }
-  const double div0 = (double)xb[0] - (double)mb[0] + 1.0, div1 = (double)xb[1] - (double)mb[1] + 1.0;
-  b[0] = mb[0]; b[1] = mb[1]; b[2] = mb[2];
-  b[3] = over ? 0 : (long long)div0;
-  b[4] = over ? 0 : (long long)(div0 * div1);
-  b[5] = over ? 1 : 2;
-  return over;
-}
-
-// linear leaf index of a point in a valid box
-__device__ inline uint64_t sv_cell(const float4& pt, float leaf, const long long* __restrict__ b) {
-  const float inv = 1.0f / leaf;
-  const int mb0 = (int)b[0], mb1 = (int)b[1], mb2 = (int)b[2];
-  const long long i0 = (long long)(floorf(pt.x * inv) - (float)mb0), i1 = (long long)(floorf(pt.y * inv) - (float)mb1),
-                  i2 = (long long)(floorf(pt.z * inv) - (float)mb2);
-  return (uint64_t)(i0 + i1 * b[3] + i2 * b[4]);
-}
-#endif
 
 }  // namespace loam
 }  // namespace pcm

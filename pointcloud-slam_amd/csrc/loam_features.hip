@@ -15,9 +15,7 @@
 #include "host_util.h"
 #include "intro_sort.h"
 #include "loam_device.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
+#include "voxel_grid.h"
 
 #include <algorithm>
 #include <cmath>
@@ -454,17 +452,15 @@ __global__ void __launch_bounds__(256) k_lf_corner_compact(const LfFrame* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// segmented pcl::VoxelGrid (same arithmetic as preprocess.hip's voxel_downsample_device, one box per segment):
+// segmented pcl::VoxelGrid (voxel_grid.h's segmented pipeline, one box per segment):
 //   stage 1: segment = frame * n_scan + ring, the ring's surfaceCloudScan, leaf odometrySurfLeafSize (:243-245)
 //   stage 2: segment = 2 frame (corner) / 2 frame + 1 (surf), leaf mappingCornerLeafSize / mappingSurfLeafSize
 //            (downsampleCurrentScan, mapOptmization.cpp:1238-1246); leaf 0 = no down-sampling (one cell per element, in order)
 // keys (segment << 32 | cell index) are radix-sorted once for all segments of all frames; double centroid sums.
 // ---------------------------------------------------------------------------------------------------------------------------
-struct Elem { bool valid; uint32_t seg, ord; float4 pt; };
-
 template <int kStage>
-__device__ inline Elem elem_of(const LfFrame& F, const LfParams& p, uint32_t f, uint32_t j, const float4* cells1) {
-  Elem e{false, 0u, 0u, make_float4(0.f, 0.f, 0.f, 0.f)};
+__device__ inline vg::Elem elem_of(const LfFrame& F, const LfParams& p, uint32_t f, uint32_t j, const float4* cells1) {
+  vg::Elem e{false, 0u, 0u, make_float4(0.f, 0.f, 0.f, 0.f)};
   if (kStage == 1) {
     if (j < F.info->count && F.member[j] >= 0) {
       e.valid = true; e.seg = f * (uint32_t)p.n_scan + (uint32_t)F.member[j]; e.ord = j; e.pt = F.cloud[j];
@@ -485,106 +481,29 @@ __device__ inline float seg_leaf(int stage, const LfParams& p, uint32_t seg) {
   return stage == 1 ? p.leaf_odo : ((seg & 1u) ? p.leaf_surf : p.leaf_corner);
 }
 
-__global__ void k_sv_clear(unsigned int* __restrict__ mm, uint32_t* __restrict__ scnt, uint32_t nseg) {
-  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= nseg) return;
-  for (int a = 0; a < 3; a++) { mm[6 * s + a] = 0xffffffffu; mm[6 * s + 3 + a] = 0u; }
-  scnt[s] = 0u;
-}
-
+// a stage's elements as the pipeline reads them: row = frame, slot j of the frame's range; the cells of all frames go to `out`
 template <int kStage>
-__global__ void k_sv_minmax(const LfFrame* __restrict__ fr, LfParams p, uint32_t size_per_frame, const float4* __restrict__ cells1, unsigned int* __restrict__ mm) {
-  const uint32_t f = blockIdx.y;
-  const LfFrame& F = fr[f];
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  const Elem e = j < size_per_frame ? elem_of<kStage>(F, p, f, j, cells1) : Elem{false, 0u, 0u, make_float4(0.f, 0.f, 0.f, 0.f)};
-  loam::sv_wave_minmax(e.valid, e.seg, e.pt, mm);
-}
-
-// per segment: the box of pcl::VoxelGrid from the segment's min / max: box = {min_b x, y, z, divb_mul[1], divb_mul[2], state}
-// (state 0: empty or no leaf, 1: index overflow, 2: valid).  The products are formed in double: exact, as a valid box has fewer
-// than 2^31 cells.
-__global__ void k_sv_boxes(const LfFrame* __restrict__ fr, const unsigned int* __restrict__ mm, uint32_t nseg, int stage, LfParams p, long long* __restrict__ box) {
-  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= nseg) return;
-  const bool over = loam::sv_box(mm + 6 * (size_t)s, seg_leaf(stage, p, s), box + 6 * (size_t)s);
-  if (over) fr[s / (stage == 1 ? (uint32_t)p.n_scan : 2u)].info->overflow = 1u;   // every writer stores 1
-}
-
-template <int kStage>
-__global__ void k_sv_keys(const LfFrame* __restrict__ fr, LfParams p, uint32_t size_per_frame, const float4* __restrict__ cells1, const long long* __restrict__ box,
-                          uint32_t nseg, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
-  const uint32_t f = blockIdx.y;
-  const LfFrame& F = fr[f];
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  // the frame's own element range (size_per_frame is the largest of the batch)
-  const uint32_t own = kStage == 1 ? F.cap1 : (uint32_t)p.n_scan * (uint32_t)p.ppr + F.cap1;
-  if (j >= size_per_frame || j >= own) return;
-  const uint32_t g = (kStage == 1 ? F.base1 : F.base2) + j;
-  const Elem e = elem_of<kStage>(F, p, f, j, cells1);
-  uint64_t key = (uint64_t)nseg << 32;   // invalid: behind every segment
-  if (e.valid) {
-    const float leaf = seg_leaf(kStage, p, e.seg);
-    const long long* b = box + 6 * (size_t)e.seg;
-    if (!(leaf > 0.f)) key = ((uint64_t)e.seg << 32) | e.ord;
-    else if (b[5] == 2) key = ((uint64_t)e.seg << 32) | loam::sv_cell(e.pt, leaf, b);
-  }
-  keys[g] = key;
-  vals[g] = g;
-}
-
-__global__ void k_sv_heads(const uint64_t* __restrict__ keys, uint32_t n, uint32_t nseg, uint32_t* __restrict__ head, uint32_t* __restrict__ scnt) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint64_t k = keys[i];
-  const bool h = (k >> 32) < nseg && (i == 0 || keys[i - 1] != k);
-  head[i] = h ? 1u : 0u;
-  if (h) atomicAdd(&scnt[k >> 32], 1u);
-}
-
-// cell c starts at sorted element pos[c]; the first cell of every segment -> sfirst[segment]
-__global__ void k_sv_head_pos(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ head, const uint32_t* __restrict__ slot, uint32_t n,
-                              uint32_t* __restrict__ pos, uint32_t* __restrict__ sfirst) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || !head[i]) return;
-  pos[slot[i]] = i;
-  const uint32_t s = (uint32_t)(keys[i] >> 32);
-  if (i == 0 || (uint32_t)(keys[i - 1] >> 32) != s) sfirst[s] = slot[i];
-}
-
-// the last valid element: valid count and cell count
-__global__ void k_sv_count(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ head, const uint32_t* __restrict__ slot, uint32_t n, uint32_t nseg,
-                           uint32_t* __restrict__ nc) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || (keys[i] >> 32) >= nseg) return;
-  if (i + 1 == n || (keys[i + 1] >> 32) >= nseg) { nc[0] = slot[i] + head[i]; nc[1] = i + 1; }
-}
-
-// one wave per cell (grid-stride): double sums of x, y, z, intensity over the cell's run (k_vg_average's scheme)
-template <int kStage>
-__global__ void __launch_bounds__(256) k_sv_average(const LfFrame* __restrict__ fr, LfParams p, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
-                                                    const uint32_t* __restrict__ pos, const uint32_t* __restrict__ ncells_p, const uint32_t* __restrict__ nvalid_p,
-                                                    const float4* __restrict__ cells1, float4* __restrict__ out) {
-  const uint32_t ncells = *ncells_p, nvalid = *nvalid_p;
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t spf = kStage == 1 ? (uint32_t)p.n_scan : 2u;
-  for (uint32_t cell = blockIdx.x * 4 + (threadIdx.x >> 6); cell < ncells; cell += gridDim.x * 4) {
-    const uint32_t b = pos[cell], e = cell + 1 < ncells ? pos[cell + 1] : nvalid;
-    const uint32_t seg = (uint32_t)(keys[b] >> 32), f = seg / spf;
+struct LfElems {
+  static constexpr int kFields = 4;
+  const LfFrame* fr; LfParams p; const float4* cells1; float4* out;
+  __device__ uint32_t segs_per_frame() const { return kStage == 1 ? (uint32_t)p.n_scan : 2u; }
+  __device__ uint32_t base(const LfFrame& F) const { return kStage == 1 ? F.base1 : F.base2; }
+  __device__ int fields() const { return 4; }
+  __device__ bool slot(uint32_t f, uint32_t j, uint32_t* g) const {
     const LfFrame& F = fr[f];
-    const uint32_t base = kStage == 1 ? F.base1 : F.base2;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (uint32_t j = b + lane; j < e; j += 64) {
-      const float4 q = elem_of<kStage>(F, p, f, vals[j] - base, cells1).pt;
-      acc[0] += (double)q.x; acc[1] += (double)q.y; acc[2] += (double)q.z; acc[3] += (double)q.w;
-    }
-    for (int k = 0; k < 4; k++) acc[k] = loam::wave_sum_f64(acc[k]);
-    if (lane == 0) {
-      const double m = (double)(e - b);
-      out[cell] = make_float4((float)(acc[0] / m), (float)(acc[1] / m), (float)(acc[2] / m), (float)(acc[3] / m));
-    }
+    *g = base(F) + j;
+    return j < (kStage == 1 ? F.cap1 : (uint32_t)p.n_scan * (uint32_t)p.ppr + F.cap1);   // the frame's own range (a row is the largest of the batch)
   }
-}
+  __device__ vg::Elem elem(uint32_t f, uint32_t j) const { return elem_of<kStage>(fr[f], p, f, j, cells1); }
+  __device__ float4 fetch(uint32_t g, uint32_t seg) const {
+    const uint32_t f = seg / segs_per_frame();
+    const LfFrame& F = fr[f];
+    return elem_of<kStage>(F, p, f, g - base(F), cells1).pt;
+  }
+  __device__ float leaf(uint32_t seg) const { return seg_leaf(kStage, p, seg); }
+  __device__ void overflow(uint32_t seg) const { fr[seg / segs_per_frame()].info->overflow = 1u; }   // every writer stores 1
+  __device__ void put(uint32_t cell, const float (&m)[kFields]) const { out[cell] = make_float4(m[0], m[1], m[2], m[3]); }
+};
 
 // per-frame totals of a stage from the segment counts (one block of 256 per frame)
 template <int kStage>
@@ -680,14 +599,11 @@ int ensure_state(pcm_ctx* c, FeatState* S, const pcm_loam_feature_params& p) {
 }
 
 int next_pow2(int x) { int p = 1; while (p < x) p <<= 1; return p; }
-int bit_len(uint64_t x) { int b = 0; while (x) { b++; x >>= 1; } return b; }
 
 struct BatchLayout {
-  size_t o_in, o_owner, o_rowcnt, o_roff, o_member, o_cpick, o_ccnt;
-  size_t o_k1, o_k1s, o_v1, o_v1s, o_head1, o_slot1, o_cells1;
-  size_t o_k2, o_k2s, o_v2, o_v2s, o_head2, o_slot2, o_cells2;
-  size_t o_mm, o_box, o_scnt, o_sfirst, o_nc, o_tmp, o_tmp2, total;
-  size_t tmp_bytes, tmp2_bytes;
+  size_t o_in, o_owner, o_rowcnt, o_roff, o_member, o_cpick, o_ccnt, o_cells1, o_cells2;
+  size_t o_vg, n_vg, nseg_vg;   // the VoxelGrid's arrays (vg::work_layout): shared by the two stages
+  size_t total;
 };
 
 BatchLayout layout(int B, size_t in_bytes, size_t cap, int n_scan, int ppr, size_t N1, size_t N2, size_t nseg_max) {
@@ -701,67 +617,28 @@ BatchLayout layout(int B, size_t in_bytes, size_t cap, int n_scan, int ppr, size
   L.o_member = take(4 * cap * B);
   L.o_cpick = take(4 * (size_t)n_scan * ppr * B);
   L.o_ccnt = take(4 * (size_t)n_scan * B);
-  const size_t NM = std::max(N1, N2);
-  L.o_k1 = take(8 * NM); L.o_k1s = take(8 * NM); L.o_v1 = take(4 * NM); L.o_v1s = take(4 * NM);
-  L.o_head1 = take(4 * NM); L.o_slot1 = take(4 * NM);
   L.o_cells1 = take(16 * N1);
   L.o_cells2 = take(16 * N2);
-  L.o_mm = take(4 * 6 * nseg_max); L.o_box = take(8 * 6 * nseg_max); L.o_scnt = take(4 * nseg_max); L.o_sfirst = take(4 * nseg_max);
-  L.o_nc = take(16);
-  size_t t1 = 0, t2 = 0;
-  {
-    uint64_t* k = nullptr; uint32_t* v = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, t1, k, k, v, v, NM, 0, 64, nullptr);
-    (void)rocprim::exclusive_scan(nullptr, t2, v, v, 0u, NM, rocprim::plus<uint32_t>(), nullptr);
-  }
-  L.tmp_bytes = t1; L.tmp2_bytes = t2;
-  L.o_tmp = take(t1);
-  L.o_tmp2 = take(t2);
+  L.n_vg = std::max(N1, N2); L.nseg_vg = nseg_max;
+  size_t vg_bytes = 0;
+  (void)vg::work_layout(nullptr, L.n_vg, sizeof(uint64_t), L.nseg_vg, &vg_bytes);
+  L.o_vg = take(vg_bytes);
   L.total = o;
   return L;
 }
 
-int run_vg(pcm_ctx* c0, hipStream_t st, int stage, const LfFrame* d_fr, const LfParams& P, int B, uint32_t size_per_frame, uint32_t N, uint32_t nseg,
-           char* ws, const BatchLayout& Lw, const float4* cells1, float4* cells_out) {
-  uint64_t* keys = reinterpret_cast<uint64_t*>(ws + Lw.o_k1);
-  uint64_t* keys_s = reinterpret_cast<uint64_t*>(ws + Lw.o_k1s);
-  uint32_t* vals = reinterpret_cast<uint32_t*>(ws + Lw.o_v1);
-  uint32_t* vals_s = reinterpret_cast<uint32_t*>(ws + Lw.o_v1s);
-  uint32_t* head = reinterpret_cast<uint32_t*>(ws + Lw.o_head1);
-  uint32_t* slot = reinterpret_cast<uint32_t*>(ws + Lw.o_slot1);
-  unsigned int* mm = reinterpret_cast<unsigned int*>(ws + Lw.o_mm);
-  uint32_t* scnt = reinterpret_cast<uint32_t*>(ws + Lw.o_scnt);
-  uint32_t* sfirst = reinterpret_cast<uint32_t*>(ws + Lw.o_sfirst);
-  uint32_t* nc = reinterpret_cast<uint32_t*>(ws + Lw.o_nc);   // [0] cells, [1] valid elements
-  long long* box = reinterpret_cast<long long*>(ws + Lw.o_box);
+// one stage: N element slots in B rows of up to size_per_frame, nseg segments; the cells of all frames go to cells_out
+template <int kStage>
+int run_vg(pcm_ctx* c0, hipStream_t st, const LfFrame* d_fr, const LfParams& P, int B, uint32_t size_per_frame, uint32_t N, uint32_t nseg, vg::Work W,
+           const float4* cells1, float4* cells_out) {
   if (N == 0 || size_per_frame == 0) return PCM_OK;
-  const dim3 g((size_per_frame + 255) / 256, (unsigned)B);
-  k_sv_clear<<<(nseg + 255) / 256, 256, 0, st>>>(mm, scnt, nseg);
-  PCM_HIPCK(c0, hipMemsetAsync(nc, 0, 16, st));
-  if (stage == 1) {
-    k_sv_minmax<1><<<g, 256, 0, st>>>(d_fr, P, size_per_frame, cells1, mm);
-    k_sv_boxes<<<(nseg + 255) / 256, 256, 0, st>>>(d_fr, mm, nseg, 1, P, box);
-    k_sv_keys<1><<<g, 256, 0, st>>>(d_fr, P, size_per_frame, cells1, box, nseg, keys, vals);
-  } else {
-    k_sv_minmax<2><<<g, 256, 0, st>>>(d_fr, P, size_per_frame, cells1, mm);
-    k_sv_boxes<<<(nseg + 255) / 256, 256, 0, st>>>(d_fr, mm, nseg, 2, P, box);
-    k_sv_keys<2><<<g, 256, 0, st>>>(d_fr, P, size_per_frame, cells1, box, nseg, keys, vals);
-  }
-  PCM_HIPCK(c0, hipGetLastError());
-  loam::SvWork W;
-  W.keys = keys; W.keys_s = keys_s; W.vals = vals; W.vals_s = vals_s; W.head = head; W.slot = slot; W.scnt = scnt; W.sfirst = sfirst; W.nc = nc;
-  W.tmp = ws + Lw.o_tmp; W.tmp_bytes = Lw.tmp_bytes; W.tmp2 = ws + Lw.o_tmp2; W.tmp2_bytes = Lw.tmp2_bytes;
-  int rc = loam::sv_sort_cells(c0, st, W, N, nseg);
+  W.nseg = nseg;
+  const LfElems<kStage> E{d_fr, P, cells1, cells_out};
+  vg::clear(st, W);
+  vg::seg_minmax(st, E, (uint32_t)B, size_per_frame, W);
+  const int rc = vg::seg_cells(&c0->err, st, E, (uint32_t)B, size_per_frame, N, W);
   if (rc != PCM_OK) return rc;
-  uint32_t* pos = vals;   // free after the sort
-  const unsigned gb = std::min<unsigned>(1024u, (N + 3) / 4);
-  if (stage == 1) {
-    k_sv_average<1><<<gb, 256, 0, st>>>(d_fr, P, keys_s, vals_s, pos, nc, nc + 1, cells1, cells_out);
-    k_sv_frames<1><<<B, 256, 0, st>>>(d_fr, P, scnt, sfirst);
-  } else {
-    k_sv_average<2><<<gb, 256, 0, st>>>(d_fr, P, keys_s, vals_s, pos, nc, nc + 1, cells1, cells_out);
-    k_sv_frames<2><<<B, 256, 0, st>>>(d_fr, P, scnt, sfirst);
-  }
+  k_sv_frames<kStage><<<B, 256, 0, st>>>(d_fr, P, W.scnt(), W.sfirst());
   PCM_HIPCK(c0, hipGetLastError());
   return PCM_OK;
 }
@@ -770,30 +647,6 @@ int run_vg(pcm_ctx* c0, hipStream_t st, int stage, const LfFrame* d_fr, const Lf
 
 namespace pcm {
 namespace loam {
-// the middle of the segmented VoxelGrid, independent of where the elements live: keys -> sorted keys, cell heads, the start of
-// every cell in W.vals (free after the sort), per-segment cell counts and first cells, totals in W.nc
-int sv_sort_cells(pcm_ctx* c0, hipStream_t st, const SvWork& W, uint32_t N, uint32_t nseg) {
-  size_t tb = W.tmp_bytes, tb2 = W.tmp2_bytes;
-  const int end_bit = 32 + bit_len(nseg);
-  PCM_HIPCK(c0, rocprim::radix_sort_pairs(W.tmp, tb, W.keys, W.keys_s, W.vals, W.vals_s, (size_t)N, 0, end_bit, st));
-  const unsigned nb = (N + 255) / 256;
-  k_sv_heads<<<nb, 256, 0, st>>>(W.keys_s, N, nseg, W.head, W.scnt);
-  PCM_HIPCK(c0, hipGetLastError());
-  PCM_HIPCK(c0, rocprim::exclusive_scan(W.tmp2, tb2, W.head, W.slot, 0u, (size_t)N, rocprim::plus<uint32_t>(), st));
-  k_sv_head_pos<<<nb, 256, 0, st>>>(W.keys_s, W.head, W.slot, N, W.vals, W.sfirst);
-  k_sv_count<<<nb, 256, 0, st>>>(W.keys_s, W.head, W.slot, N, nseg, W.nc);   // invalid keys sort behind every valid one
-  PCM_HIPCK(c0, hipGetLastError());
-  return PCM_OK;
-}
-
-void sv_clear(hipStream_t st, unsigned int* mm, uint32_t* scnt, uint32_t nseg) { k_sv_clear<<<(nseg + 255) / 256, 256, 0, st>>>(mm, scnt, nseg); }
-
-void sv_temp_bytes(size_t n, size_t* sort_bytes, size_t* scan_bytes) {
-  uint64_t* k = nullptr; uint32_t* v = nullptr;
-  (void)rocprim::radix_sort_pairs(nullptr, *sort_bytes, k, k, v, v, n, 0, 64, nullptr);
-  (void)rocprim::exclusive_scan(nullptr, *scan_bytes, v, v, 0u, n, rocprim::plus<uint32_t>(), nullptr);
-}
-
 // the context's last front-end features with their averaged intensity (k_lf_finish's F.out), alive until the next frame
 bool loam_features_last_out(pcm_ctx* c, const float4** out, uint32_t* n_c, uint32_t* n_s, uint64_t* gen) {
   const FeatState* S = c->loam_fe.get<FeatState>();
@@ -947,9 +800,11 @@ int run_frames(pcm_ctx* const* ctxs, int B, const void* const* points, const siz
   PCM_HIPCK(c0, hipGetLastError());
   float4* cells1 = reinterpret_cast<float4*>(ws + Lw.o_cells1);
   float4* cells2 = reinterpret_cast<float4*>(ws + Lw.o_cells2);
-  if ((rc = run_vg(c0, st, 1, d_fr, P, B, max1, (uint32_t)N1, (uint32_t)(B * q.n_scan), ws, Lw, cells1, cells1)) != PCM_OK) return rc;
+  size_t vg_bytes = 0;
+  const vg::Work W = vg::work_layout(ws + Lw.o_vg, Lw.n_vg, sizeof(uint64_t), Lw.nseg_vg, &vg_bytes);
+  if ((rc = run_vg<1>(c0, st, d_fr, P, B, max1, (uint32_t)N1, (uint32_t)(B * q.n_scan), W, cells1, cells1)) != PCM_OK) return rc;
   const uint32_t size2 = (uint32_t)(ncs + max1);
-  if ((rc = run_vg(c0, st, 2, d_fr, P, B, size2, (uint32_t)N2, (uint32_t)(2 * B), ws, Lw, cells1, cells2)) != PCM_OK) return rc;
+  if ((rc = run_vg<2>(c0, st, d_fr, P, B, size2, (uint32_t)N2, (uint32_t)(2 * B), W, cells1, cells2)) != PCM_OK) return rc;
   k_lf_finish<<<dim3((size2 + 255) / 256, B), 256, 0, st>>>(d_fr, P, cells1, cells2);
   PCM_HIPCK(c0, hipGetLastError());
   PCM_HIPCK(c0, hipMemcpyAsync(S0->h_info, S0->d_info, sizeof(LfInfo) * (size_t)B, hipMemcpyDeviceToHost, st));

@@ -14,6 +14,7 @@
 #include "host_util.h"
 #include "loam_device.h"
 #include "loam_sc.h"
+#include "voxel_grid.h"
 
 #include <algorithm>
 #include <cstring>
@@ -66,7 +67,7 @@ __global__ void __launch_bounds__(256) k_sc_bins(const float4* __restrict__ pts,
 __global__ void __launch_bounds__(256) k_sc_finish(const uint32_t* __restrict__ table, const double* __restrict__ ready, int R, int S, float* desc, float* __restrict__ rkey,
                                                    double* __restrict__ skey, double* __restrict__ norm) {
   const int nb = R * S;
-  for (int i = threadIdx.x; i < nb; i += blockDim.x) desc[i] = table ? sc_bin_value(ord2f(table[i])) : (float)ready[i];
+  for (int i = threadIdx.x; i < nb; i += blockDim.x) desc[i] = table ? sc_bin_value(vg::ord2f(table[i])) : (float)ready[i];
   __threadfence_block();
   __syncthreads();
   for (int r = threadIdx.x; r < R; r += blockDim.x) rkey[r] = sc_ring_key(desc, R, S, r);
@@ -98,7 +99,7 @@ __global__ void __launch_bounds__(1024) k_sc_select(const uint64_t* __restrict__
       const uint64_t key = keys[i];
       if ((t == 0 || key > prev) && key < best) best = key;
     }
-    best = wave_min_u64(best);
+    best = vg::wave_min_u64(best);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
     __syncthreads();
     if (threadIdx.x == 0) {

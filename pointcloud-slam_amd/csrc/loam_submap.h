@@ -61,7 +61,7 @@ inline SubmapSelection select_entries(const KeyPose* kp, int K, float radius, fl
       const float p[3] = {kp[n.id].x, kp[n.id].y, kp[n.id].z};
       for (int a = 0; a < 3; a++) { if (p[a] < mn[a]) mn[a] = p[a]; if (p[a] > mx[a]) mx[a] = p[a]; }
     }
-    // the cell count in double against 2^31, as sv_box does on the device (a NaN or infinite product fails the test too), and
+    // the cell count in double against 2^31, as vg::box (voxel_grid.h) does on the device (a NaN or infinite product fails the test too), and
     // the leaf coordinates inside the int range before they are converted
     double cells = 1.0;
     for (int a = 0; a < 3; a++) cells *= trunc((double)((mx[a] - mn[a]) * inv)) + 1.0;

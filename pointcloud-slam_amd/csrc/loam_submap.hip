@@ -9,33 +9,28 @@
 // libm in the last bit.
 // Submap: the selection runs on the host (loam_submap.h; microseconds); its entry table (arena offset, first output position,
 // matrix) is uploaded, k_sm_gather transforms and concatenates the selected clouds and reduces their bounding boxes, and the two
-// VoxelGrids run as one segmented pass (segment 0 corner, 1 surf) through the (segment, leaf) key -> radix sort -> heads ->
-// average chain of loam_features.hip (sv_sort_cells and the sv_* device helpers of loam_device.h).  The averaged cells are written
+// VoxelGrids run as one segmented pass (segment 0 corner, 1 surf) through voxel_grid.h's segmented pipeline, the one the front end
+// (loam_features.hip) runs.  The averaged cells are written
 // straight into the context's two target clouds (loam_target_reserve / loam_target_commit); no float atomics anywhere, so two
 // updates of the same state give the same bits.
 // laserCloudMapContainer (the reference's cache of transformed clouds) never changes a result and is not kept: when the selection,
 // the poses and the leaves equal those of the previous update the call does nothing at all, which is the common case at LiDAR rate.
 // Near-key-frame cloud (pcm_loam_submap_near, pcm_loam_submap_near_dev and the clouds pcm_loam_loop_verify feeds its NDT with):
 // one path, queue_near -- pcm_loam_submap_near is pcm_loam_submap_near_dev with a host buffer.  It is the update's pass with one
-// segment, bit for bit (tests/golden/loam_near_parent.json holds the clouds of the two-segment pass it replaced), in fewer
-// launches: the box is derived inside the key kernel, the keys are 32 bits wide (half the radix passes; the sort stays stable, so
-// a cell's run keeps its input order and its sum its bits), the cell heads are scanned on the fly instead of being stored, head
-// positions and totals come from one kernel, and without a leaf the gather writes the result itself.
+// segment, bit for bit (tests/golden/loam_near_parent.json holds the clouds of the two-segment pass it replaced), through
+// voxel_grid.h's single-segment pipeline: 32-bit keys (half the radix passes; the sort stays stable, so a cell's run keeps its
+// input order and its sum its bits), fewer launches; without a leaf the gather writes the result itself.
 // Global map and saved map (pcm_loam_global_map, pcm_loam_map_export; publishGlobalMap :547-590 and the clouds of :524-542): the
 // near pass on publishGlobalMap's selection (select_global) in a workspace of its own whose per-point arrays live for one call,
-// with a gather that leaves one partial bounding box per workgroup instead of atomics per wave (k_gm_gather, k_gm_box; the same
-// bits); the export is that gather alone, writing transformPointCloud's values as they are.  DESIGN.md section 20.
-// The two passes share the entry table (build_entries), the gather and the average kernel and the workspace type, and stay two
-// pipelines on purpose: the update sorts 64-bit (segment, leaf) keys through sv_sort_cells, the near pass 32-bit keys.  One
-// pipeline for both would change the number of radix passes of one of them, and with it its speed.
+// with a gather that leaves one partial bounding box per workgroup instead of atomics per wave (k_gm_gather, vg::fold_boxes; the
+// same bits); the export is that gather alone, writing transformPointCloud's values as they are.  DESIGN.md section 20.
+// The two passes share the entry table (build_entries), the gather and the workspace type, and run voxel_grid.h's two pipelines
+// on purpose: the update sorts 64-bit (segment, leaf) keys, the near pass 32-bit keys.  One pipeline for both would change the
+// number of radix passes of one of them, and with it its speed.
 #include "host_util.h"
 #include "loam_device.h"
 #include "loam_submap.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
+#include "voxel_grid.h"
 
 #include <chrono>
 #include <cstring>
@@ -95,30 +90,14 @@ __global__ void __launch_bounds__(256) k_sm_gather(const float4* __restrict__ co
     if (valid) out[g] = make_float4(q.x + 0.0f, q.y + 0.0f, q.z + 0.0f, q.w + 0.0f);
   } else {
     if (valid) out[g] = q;
-    sv_wave_minmax(valid, (flags >> 1) & 1u, q, mm);
-  }
-}
-
-// the box of a workgroup of 256 lanes from its lanes' boxes (ordered words), into box[0..6): a butterfly per wave, then the four
-// waves through LDS; lanes 0..5 store
-__device__ __forceinline__ void gm_fold(unsigned int lo[3], unsigned int hi[3], unsigned int* __restrict__ box) {
-  __shared__ unsigned int wave_box[4][6];
-  for (int a = 0; a < 3; a++) { lo[a] = wave_min_u32(lo[a]); hi[a] = wave_max_u32(hi[a]); }
-  if ((threadIdx.x & 63) == 0)
-    for (int a = 0; a < 3; a++) { wave_box[threadIdx.x >> 6][a] = lo[a]; wave_box[threadIdx.x >> 6][3 + a] = hi[a]; }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    const uint32_t a = threadIdx.x;
-    unsigned int v = wave_box[0][a];
-    for (int w = 1; w < 4; w++) v = a < 3 ? min(v, wave_box[w][a]) : max(v, wave_box[w][a]);
-    box[a] = v;
+    vg::wave_minmax(valid, (flags >> 1) & 1u, q, mm);
   }
 }
 
 // The gather of the global pass (pcm_loam_global_map, pcm_loam_map_export): k_sm_gather's points, at most kGmBlocks workgroups
 // striding over them.  kBox: no atomics -- every lane keeps the box of its points in registers, a butterfly folds the wave's, LDS
-// the workgroup's four, and the workgroup stores one partial box (6 ordered words, min then max) that k_gm_box folds into the
-// words k_nd_keys reads.  Min and max are exact in any order, so box, keys and cells are k_sm_gather<false>'s bit for bit.
+// the workgroup's four, and the workgroup stores one partial box (6 ordered words, min then max) that vg::fold_boxes folds into
+// the words the key kernel reads.  Min and max are exact in any order, so box, keys and cells are k_sm_gather<false>'s bit for bit.
 // !kBox (the export): transformPointCloud's value as it is -- no + 0.0f, a negative zero stays negative -- and nothing else.
 constexpr unsigned kGmBlocks = 2048;
 
@@ -140,55 +119,41 @@ __global__ void __launch_bounds__(256) k_gm_gather(const float4* __restrict__ co
     }
   }
   if (!kBox) return;
-  gm_fold(lo, hi, part + 6 * blockIdx.x);
+  vg::fold_block_box(lo, hi, part + 6 * blockIdx.x);
 }
 
-// small: [0..1] cells per segment, [2..3] first cell, [4..7] totals (sv_sort_cells' nc), [8] index overflow
-constexpr int kSmallWords = 9;
+// What the totals of a pass look like on the host (vg::Work::small): [0] cells, [1] valid elements, [2] index overflow; the update
+// reads on: [4..5] cells per segment, [6..7] first cell of the segment.
+constexpr int kNearWords = 3, kUpdateWords = vg::Work::kSmallWords + 4;
 
-__global__ void k_sm_boxes(const unsigned int* __restrict__ mm, float leaf0, float leaf1, long long* __restrict__ box, uint32_t* __restrict__ small) {
-  const uint32_t s = threadIdx.x;
-  if (s >= 2) return;
-  if (sv_box(mm + 6 * s, s ? leaf1 : leaf0, box + 6 * s)) small[8] = 1u;   // every writer stores 1
-}
-
-__global__ void k_sm_keys(const float4* __restrict__ in, uint32_t N, uint32_t n0, float leaf0, float leaf1, const long long* __restrict__ box,
-                          uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= N) return;
-  const uint32_t seg = g >= n0 ? 1u : 0u;
-  const float leaf = seg ? leaf1 : leaf0;
-  const long long* b = box + 6 * seg;
-  uint64_t key = 2ull << 32;   // invalid (index overflow): behind both segments
-  if (!(leaf > 0.f)) key = ((uint64_t)seg << 32) | g;   // no down-sampling: one cell per point, in order
-  else if (b[5] == 2) key = ((uint64_t)seg << 32) | sv_cell(in[g], leaf, b);
-  keys[g] = key;
-  vals[g] = g;
-}
-
-// one wave per cell (grid-stride): double sums of x, y, z, intensity over the cell's run (k_sv_average's scheme); the first
-// *split_p cells (segment 0) go to out0, the others (segment 1) to out1, each in leaf-index order.  split_p == nullptr: one
-// segment, every cell to out0.
-__global__ void __launch_bounds__(256) k_sm_average(const float4* __restrict__ in, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ pos,
-                                                    const uint32_t* __restrict__ ncells_p, const uint32_t* __restrict__ nvalid_p,
-                                                    const uint32_t* __restrict__ split_p, float4* __restrict__ out0, float4* __restrict__ out1) {
-  const uint32_t ncells = *ncells_p, nvalid = *nvalid_p, n_seg0 = split_p ? *split_p : ncells;
-  const uint32_t lane = threadIdx.x & 63;
-  for (uint32_t cell = blockIdx.x * 4 + (threadIdx.x >> 6); cell < ncells; cell += gridDim.x * 4) {
-    const uint32_t b = pos[cell], e = cell + 1 < ncells ? pos[cell + 1] : nvalid;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (uint32_t j = b + lane; j < e; j += 64) {
-      const float4 q = in[vals[j]];
-      acc[0] += (double)q.x; acc[1] += (double)q.y; acc[2] += (double)q.z; acc[3] += (double)q.w;
-    }
-    for (int k = 0; k < 4; k++) acc[k] = wave_sum_f64(acc[k]);
-    if (lane == 0) {
-      const double m = (double)(e - b);
-      const float4 r = make_float4((float)(acc[0] / m), (float)(acc[1] / m), (float)(acc[2] / m), (float)(acc[3] / m));
-      if (cell < n_seg0) out0[cell] = r; else out1[cell - n_seg0] = r;
-    }
+// the update's elements: N gathered points, the first n0 of them segment 0 (corner), the others segment 1 (surf).  The cells of
+// segment 0 go to out0, those of segment 1 to out1, each in leaf-index order.
+struct UpdateElems {
+  static constexpr int kFields = 4;
+  const float4* in; uint32_t N, n0; float leaf0, leaf1;
+  uint32_t* small; float4* out0; float4* out1;
+  __device__ int fields() const { return 4; }
+  __device__ float4 fetch(uint32_t g, uint32_t) const { return in[g]; }
+  __device__ bool slot(uint32_t, uint32_t j, uint32_t* g) const { *g = j; return j < N; }
+  __device__ vg::Elem elem(uint32_t, uint32_t j) const { return vg::Elem{true, j >= n0 ? 1u : 0u, j, in[j]}; }
+  __device__ float leaf(uint32_t seg) const { return seg ? leaf1 : leaf0; }
+  __device__ void overflow(uint32_t) const { small[2] = 1u; }   // every writer stores 1
+  __device__ void put(uint32_t cell, const float (&m)[kFields]) const {
+    const uint32_t n_seg0 = small[vg::Work::kSmallWords];
+    const float4 r = make_float4(m[0], m[1], m[2], m[3]);
+    if (cell < n_seg0) out0[cell] = r; else out1[cell - n_seg0] = r;
   }
-}
+};
+
+// the near and global passes' elements: one segment, every point counts, the cells go to one array
+struct NearElems {
+  static constexpr int kFields = 4;
+  const float4* in; float4* out;
+  __device__ int fields() const { return 4; }
+  __device__ float4 fetch(uint32_t g, uint32_t) const { return in[g]; }
+  __device__ bool point(uint32_t g, float4* pt) const { *pt = in[g]; return true; }
+  __device__ void put(uint32_t cell, const float (&m)[kFields]) const { out[cell] = make_float4(m[0], m[1], m[2], m[3]); }
+};
 
 // the context's LOAM source as PointXYZI: corner features to dst_c, surf features to dst_s
 __global__ void k_sm_store_source(const float4* __restrict__ feats, const float4* __restrict__ xyzi, const float* __restrict__ inten, uint32_t n_c, uint32_t n_s,
@@ -199,59 +164,6 @@ __global__ void k_sm_store_source(const float4* __restrict__ feats, const float4
   if (xyzi) p = xyzi[i];
   else { p = feats[i]; p.w = inten ? inten[i] : 0.f; }
   if (i < n_c) dst_c[i] = p; else dst_s[i - n_c] = p;
-}
-
-// ---- near-key-frame pass: one segment, 32-bit keys ------------------------------------------------------------------------------
-constexpr uint32_t kNdInvalid = 0x80000000u;   // key of a point when the index overflows (a valid box has fewer than 2^31 cells)
-constexpr int kNdSmallWords = 3;               // [0] cells, [1] valid elements, [2] index overflow
-
-__global__ void k_nd_clear(unsigned int* __restrict__ mm, uint32_t* __restrict__ small) {
-  const uint32_t t = threadIdx.x;
-  if (t < 3) { mm[t] = 0xffffffffu; mm[3 + t] = 0u; small[t] = 0u; }
-}
-
-// the global pass: n_part partial boxes of k_gm_gather -> mm, and k_nd_clear's zeros; one workgroup
-__global__ void __launch_bounds__(256) k_gm_box(const unsigned int* __restrict__ part, uint32_t n_part, unsigned int* __restrict__ mm, uint32_t* __restrict__ small) {
-  unsigned int lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-  for (uint32_t i = threadIdx.x; i < n_part; i += 256u)
-    for (int a = 0; a < 3; a++) { lo[a] = min(lo[a], part[6 * i + a]); hi[a] = max(hi[a], part[6 * i + 3 + a]); }
-  gm_fold(lo, hi, mm);
-  if (threadIdx.x < kNdSmallWords) small[threadIdx.x] = 0u;
-}
-
-// k_sm_boxes + k_sm_keys: every workgroup derives the box from the finished min / max (a few dozen operations of one lane)
-__global__ void __launch_bounds__(256) k_nd_keys(const float4* __restrict__ in, uint32_t N, float leaf, const unsigned int* __restrict__ mm,
-                                                 uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ small) {
-  __shared__ long long box[6];
-  if (threadIdx.x == 0) {
-    const bool over = sv_box(mm, leaf, box);
-    if (over && blockIdx.x == 0) small[2] = 1u;
-  }
-  __syncthreads();
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= N) return;
-  keys[g] = box[5] == 2 ? (uint32_t)sv_cell(in[g], leaf, box) : kNdInvalid;
-  vals[g] = g;
-}
-
-// 1 where a cell begins in the sorted keys (k_sv_heads), evaluated by the scan itself
-struct NdHead {
-  const uint32_t* keys;
-  __host__ __device__ uint32_t operator()(uint32_t i) const {
-    const uint32_t k = keys[i];
-    return (k != kNdInvalid && (i == 0 || keys[i - 1] != k)) ? 1u : 0u;
-  }
-};
-
-// k_sv_head_pos + k_sv_count: cell c starts at sorted element pos[c]; the last valid element gives the totals
-__global__ void k_nd_pos(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ slot, uint32_t N, uint32_t* __restrict__ pos, uint32_t* __restrict__ small) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  const uint32_t k = keys[i];
-  if (k == kNdInvalid) return;
-  const uint32_t head = (i == 0 || keys[i - 1] != k) ? 1u : 0u;
-  if (head) pos[slot[i]] = i;
-  if (i + 1 == N || keys[i + 1] == kNdInvalid) { small[0] = slot[i] + head; small[1] = i + 1; }
 }
 
 // device workspace of one gather + VoxelGrid pass.  The update pass (segmented) sorts 64-bit keys and keeps the cell heads, two
@@ -265,8 +177,8 @@ struct SmWork {
   DevBuf<SmEntry> ent{"key-frame entry table"};
   DevBuf<unsigned int> part{"partial boxes"};   // one_shot: [kGmBlocks][6]
   size_t n_cap = 0;
-  size_t o_in = 0, o_cells = 0, o_keys = 0, o_keys_s = 0, o_vals = 0, o_vals_s = 0, o_head = 0, o_slot = 0, o_mm = 0, o_box = 0, o_small = 0,
-         o_tmp = 0, o_tmp2 = 0, tmp_bytes = 0, tmp2_bytes = 0;
+  size_t o_in = 0, o_cells = 0;
+  vg::Work grid{};               // the VoxelGrid's arrays, inside buf
   PinnedBuf<uint32_t> h_small;
   PinnedBuf<SmEntry> h_ent;      // staging of the entry table
   bool in_flight = false;        // the last near pass was left without a wait: its staging is not free yet
@@ -280,7 +192,7 @@ struct SmWork {
 // room for N points and n_ent entries; keys of key_bytes each.  segmented: the head and box arrays and the second segment exist.
 // sorted: the arrays of the VoxelGrid exist (a one-shot pass without a leaf has none); own_cells: the cell array does.
 int ensure_work(pcm_ctx* c, SmWork* W, size_t N, size_t n_ent, size_t key_bytes, bool segmented, bool sorted, bool own_cells) {
-  const size_t words = segmented ? kSmallWords : kNdSmallWords;
+  const size_t words = segmented ? kUpdateWords : kNearWords;
   int rc = W->h_small.reserve(c, words, words);
   if (rc != PCM_OK) return rc;
   if (n_ent > W->h_ent.cap && (rc = W->h_ent.reserve(c, n_ent, n_ent + n_ent / 2 + 16)) != PCM_OK) return rc;
@@ -296,21 +208,12 @@ int ensure_work(pcm_ctx* c, SmWork* W, size_t N, size_t n_ent, size_t key_bytes,
   auto take = [&](size_t bytes) { const size_t r = o; o += up256(bytes); return r; };
   W->o_in = take(16 * ns);
   W->o_cells = take(own_cells ? 16 * nc : 16);
-  W->o_keys = take(key_bytes * ns); W->o_keys_s = take(key_bytes * ns);
-  W->o_vals = take(4 * ns); W->o_vals_s = take(4 * ns); W->o_head = take(segmented ? 4 * ns : 0); W->o_slot = take(4 * ns);
-  W->o_mm = take(4 * 6 * (segmented ? 2 : 1)); W->o_box = take(segmented ? 8 * 12 : 0); W->o_small = take(4 * words);
-  if (!sorted) {
-    W->tmp_bytes = W->tmp2_bytes = 0;
-  } else if (segmented) {
-    sv_temp_bytes(nc, &W->tmp_bytes, &W->tmp2_bytes);
-  } else {
-    uint32_t* k = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, W->tmp_bytes, k, k, k, k, nc, 0, 32, nullptr);
-    auto heads = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0u), NdHead{k});
-    (void)rocprim::exclusive_scan(nullptr, W->tmp2_bytes, heads, k, 0u, nc, rocprim::plus<uint32_t>(), nullptr);
-  }
-  W->o_tmp = take(W->tmp_bytes); W->o_tmp2 = take(W->tmp2_bytes);
+  const size_t nseg = segmented ? 2 : 0;
+  size_t vg_bytes = 0;
+  (void)vg::work_layout(nullptr, ns, key_bytes, nseg, &vg_bytes);
+  const size_t o_vg = take(vg_bytes);
   if ((rc = W->buf.reserve(c, o, o)) != PCM_OK) return rc;
+  W->grid = vg::work_layout(W->buf.p + o_vg, ns, key_bytes, nseg, &vg_bytes);
   W->n_cap = nc;
   return PCM_OK;
 }
@@ -405,29 +308,14 @@ int count_points(pcm_ctx* c, const KeyStore* S, const std::vector<int32_t>& keys
 int run_pass(pcm_ctx* c, KeyStore* S, SmWork* W, size_t n_ent, uint32_t N, uint32_t n0, float leaf0, float leaf1, float4* out0, float4* out1) {
   hipStream_t st = c->stream;
   SmEntry* d_ent = W->ent;
-  unsigned int* mm = W->at<unsigned int>(W->o_mm);
-  long long* box = W->at<long long>(W->o_box);
-  uint32_t* small = W->at<uint32_t>(W->o_small);
-  SvWork V;
-  V.keys = W->at<uint64_t>(W->o_keys); V.keys_s = W->at<uint64_t>(W->o_keys_s);
-  V.vals = W->at<uint32_t>(W->o_vals); V.vals_s = W->at<uint32_t>(W->o_vals_s);
-  V.head = W->at<uint32_t>(W->o_head); V.slot = W->at<uint32_t>(W->o_slot);
-  V.scnt = small; V.sfirst = small + 2; V.nc = small + 4;
-  V.tmp = W->at<char>(W->o_tmp); V.tmp_bytes = W->tmp_bytes; V.tmp2 = W->at<char>(W->o_tmp2); V.tmp2_bytes = W->tmp2_bytes;
+  const vg::Work& V = W->grid;
   PCM_HIPCK(c, hipMemcpyAsync(d_ent, W->h_ent, sizeof(SmEntry) * n_ent, hipMemcpyHostToDevice, st));
-  PCM_HIPCK(c, hipMemsetAsync(small, 0, sizeof(uint32_t) * kSmallWords, st));
-  sv_clear(st, mm, small, 2);
-  const unsigned nb = (N + 255) / 256;
-  k_sm_gather<false><<<nb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, d_ent, (uint32_t)n_ent, N, W->in(), mm);
-  k_sm_boxes<<<1, 64, 0, st>>>(mm, leaf0, leaf1, box, small);
-  k_sm_keys<<<nb, 256, 0, st>>>(W->in(), N, n0, leaf0, leaf1, box, V.keys, V.vals);
+  vg::clear(st, V);
+  k_sm_gather<false><<<(N + 255) / 256, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, d_ent, (uint32_t)n_ent, N, W->in(), V.mm);
   PCM_HIPCK(c, hipGetLastError());
-  int rc = sv_sort_cells(c, st, V, N, 2);
+  const int rc = vg::seg_cells(&c->err, st, UpdateElems{W->in(), N, n0, leaf0, leaf1, V.small, out0, out1}, 1u, N, N, V);
   if (rc != PCM_OK) return rc;
-  const unsigned gb = std::min<unsigned>(1024u, (N + 3) / 4);
-  k_sm_average<<<gb, 256, 0, st>>>(W->in(), V.vals_s, V.vals, V.nc, V.nc + 1, V.scnt, out0, out1);
-  PCM_HIPCK(c, hipGetLastError());
-  PCM_HIPCK(c, hipMemcpyAsync(W->h_small, small, sizeof(uint32_t) * kSmallWords, hipMemcpyDeviceToHost, st));
+  PCM_HIPCK(c, hipMemcpyAsync(W->h_small, V.small, sizeof(uint32_t) * kUpdateWords, hipMemcpyDeviceToHost, st));
   PCM_HIPCK(c, hipStreamSynchronize(st));
   return PCM_OK;
 }
@@ -475,30 +363,17 @@ int queue_near(pcm_ctx* c, KeyStore* S, SmWork* W, const std::vector<int32_t>& k
     W->h_small[0] = N; W->h_small[1] = N; W->h_small[2] = 0u;
     return PCM_OK;
   }
-  unsigned int* mm = W->at<unsigned int>(W->o_mm);
-  uint32_t* small = W->at<uint32_t>(W->o_small);
-  uint32_t* keys_u = W->at<uint32_t>(W->o_keys); uint32_t* keys_s = W->at<uint32_t>(W->o_keys_s);
-  uint32_t* vals = W->at<uint32_t>(W->o_vals); uint32_t* vals_s = W->at<uint32_t>(W->o_vals_s);
-  uint32_t* slot = W->at<uint32_t>(W->o_slot);
+  const vg::Work& V = W->grid;
   if (W->one_shot) {
     const unsigned gb = std::min(nb, kGmBlocks);
     k_gm_gather<true><<<gb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, d_ent, (uint32_t)E, N, W->in(), W->part);
-    k_gm_box<<<1, 256, 0, st>>>(W->part, gb, mm, small);
+    vg::fold_boxes(st, W->part, gb, V);
   } else {
-    k_nd_clear<<<1, 64, 0, st>>>(mm, small);
-    k_sm_gather<false><<<nb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, d_ent, (uint32_t)E, N, W->in(), mm);
+    vg::clear(st, V);
+    k_sm_gather<false><<<nb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, d_ent, (uint32_t)E, N, W->in(), V.mm);
   }
-  k_nd_keys<<<nb, 256, 0, st>>>(W->in(), N, leaf, mm, keys_u, vals, small);
-  PCM_HIPCK(c, hipGetLastError());
-  size_t tb = W->tmp_bytes, tb2 = W->tmp2_bytes;
-  PCM_HIPCK(c, rocprim::radix_sort_pairs(W->at<char>(W->o_tmp), tb, keys_u, keys_s, vals, vals_s, (size_t)N, 0, 32, st));
-  auto heads = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0u), NdHead{keys_s});
-  PCM_HIPCK(c, rocprim::exclusive_scan(W->at<char>(W->o_tmp2), tb2, heads, slot, 0u, (size_t)N, rocprim::plus<uint32_t>(), st));
-  k_nd_pos<<<nb, 256, 0, st>>>(keys_s, slot, N, vals, small);   // vals is free after the sort: it takes the cell starts
-  const unsigned gb = std::min<unsigned>(1024u, (N + 3) / 4);
-  k_sm_average<<<gb, 256, 0, st>>>(W->in(), vals_s, vals, small, small + 1, nullptr, dst, nullptr);
-  PCM_HIPCK(c, hipGetLastError());
-  PCM_HIPCK(c, hipMemcpyAsync(W->h_small, small, sizeof(uint32_t) * kNdSmallWords, hipMemcpyDeviceToHost, st));
+  if ((rc = vg::single_cells(&c->err, st, NearElems{W->in(), dst}, N, leaf, V)) != PCM_OK) return rc;
+  PCM_HIPCK(c, hipMemcpyAsync(W->h_small, V.small, sizeof(uint32_t) * kNearWords, hipMemcpyDeviceToHost, st));
   return PCM_OK;
 }
 
@@ -813,14 +688,14 @@ int pcm_loam_submap_update(pcm_ctx* c, const pcm_loam_submap_params* params, dou
     PCM_HIPCK(c, hipStreamSynchronize(c->stream));   // the pinned staging of an earlier pass is free again
     build_entries(S, sel.keys, -1, false, S->upd.h_ent);
     if ((rc = run_pass(c, S, &S->upd, 2 * E, N, (uint32_t)n_c, p.corner_leaf, p.surf_leaf, out_c, out_s)) != PCM_OK) return rc;
-    if (S->upd.h_small[8]) {
+    if (S->upd.h_small[2]) {
       r.status = PCM_ERR_OUT_OF_RANGE;
       *result = r;
       c->err = "leaf size too small for the extent of the submap (index overflow)";
       return PCM_ERR_OUT_OF_RANGE;
     }
-    r.num_corner_map = (int32_t)S->upd.h_small[0];
-    r.num_surf_map = (int32_t)S->upd.h_small[1];
+    r.num_corner_map = (int32_t)S->upd.h_small[vg::Work::kSmallWords];
+    r.num_surf_map = (int32_t)S->upd.h_small[vg::Work::kSmallWords + 1];
   }
   loam_target_commit(c, (uint32_t)r.num_corner_map, (uint32_t)r.num_surf_map, TargetOwner::submap);
   r.rebuilt = 1;
@@ -958,19 +833,18 @@ int pcm_loam_global_gather_ms(pcm_ctx* c, const pcm_loam_global_params* params, 
   W->in_flight = false;
   build_entries(S, sel.keys, -1, true, W->h_ent);
   PCM_HIPCK(c, hipMemcpyAsync(W->ent, W->h_ent, sizeof(SmEntry) * E, hipMemcpyHostToDevice, st));
-  unsigned int* mm = W->at<unsigned int>(W->o_mm);
-  uint32_t* small = W->at<uint32_t>(W->o_small);
+  unsigned int* mm = W->grid.mm;
   const unsigned nb = (N + 255) / 256, gb = std::min(nb, kGmBlocks);
   hipEvent_t e0 = nullptr, e1 = nullptr;
   PCM_HIPCK(c, hipEventCreate(&e0));
   if (hipEventCreate(&e1) != hipSuccess) { hipEventDestroy(e0); c->err = "hipEventCreate failed"; return PCM_ERR_HIP; }
   hipError_t e = hipEventRecord(e0, st);
   if (variant == 0) {
-    k_nd_clear<<<1, 64, 0, st>>>(mm, small);
+    vg::clear(st, W->grid);
     k_sm_gather<false><<<nb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, W->ent, (uint32_t)E, N, W->in(), mm);
   } else {
     k_gm_gather<true><<<gb, 256, 0, st>>>(S->arena[0].d, S->arena[1].d, S->mats, W->ent, (uint32_t)E, N, W->in(), W->part);
-    k_gm_box<<<1, 256, 0, st>>>(W->part, gb, mm, small);
+    vg::fold_boxes(st, W->part, gb, W->grid);
   }
   if (e == hipSuccess) e = hipGetLastError();
   if (e == hipSuccess) e = hipEventRecord(e1, st);

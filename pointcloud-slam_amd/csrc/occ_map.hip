@@ -12,6 +12,7 @@
 #include "host_util.h"
 #include "loam_device.h"
 #include "occ_map.h"
+#include "voxel_grid.h"
 
 #include <algorithm>
 #include <cstring>
@@ -103,9 +104,9 @@ __global__ void __launch_bounds__(256) k_occ_bounds(const uint2* __restrict__ ce
     mny = min(mny, (uint32_t)cy); mxy = max(mxy, (uint32_t)cy);
     cnt++;
   }
-  cnt = loam::wave_sum_u32(cnt);
+  cnt = vg::wave_sum_u32(cnt);
   if (cnt == 0u) return;   // the same in every lane of the wave
-  mnx = loam::wave_min_u32(mnx); mxx = loam::wave_max_u32(mxx); mny = loam::wave_min_u32(mny); mxy = loam::wave_max_u32(mxy);
+  mnx = vg::wave_min_u32(mnx); mxx = vg::wave_max_u32(mxx); mny = vg::wave_min_u32(mny); mxy = vg::wave_max_u32(mxy);
   if ((threadIdx.x & 63) == 0) {
     atomicMin(&small[kMinX], mnx); atomicMax(&small[kMaxX], mxx);
     atomicMin(&small[kMinY], mny); atomicMax(&small[kMaxY], mxy);

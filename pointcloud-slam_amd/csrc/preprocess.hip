@@ -10,9 +10,8 @@
 // lane 0 reproduces that chain.
 #include "pcm_device.h"
 #include "pcm_host.h"
+#include "voxel_grid.h"
 
-#include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 namespace pcm {
@@ -104,153 +103,60 @@ int undistort_device(hipStream_t stream, void* d_points, size_t n, size_t stride
 
 
 // ---------------------------------------------------------------------------
-// pcl::VoxelGrid down-sampling of the scan (jueying_lio/src/laser_mapping.cc:323-328; pcl/filters/impl/voxel_grid.hpp):
-// cell = floor(p * inverse_leaf_size) - min_b, linear index ijk . (1, dx, dx dy), one centroid per occupied cell in
-// increasing index order, every float field of the record averaged.  PCL sorts (index, point) pairs with std::sort and
-// sums in float; here: radix sort (stable), one wave per cell, double sums (64 interleaved partial sums + a fixed tree).
+// pcl::VoxelGrid down-sampling of the scan (jueying_lio/src/laser_mapping.cc:323-328): voxel_grid.h's single-segment pipeline over
+// records of 3..16 floats, every float field averaged; a point with a non-finite coordinate does not count.
 // ---------------------------------------------------------------------------
 namespace {
 
-// inverse of pcm_device.h's f2ord on the host
-inline float ord2f(unsigned int o) { const unsigned int u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o; float f; std::memcpy(&f, &u, 4); return f; }
-
-__global__ void k_vg_minmax(const char* __restrict__ base, size_t stride, uint32_t n, unsigned int* __restrict__ mm /* min xyz, max xyz (ordered ints), count */) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  unsigned int lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u}, cnt = 0u;
-  if (i < n) {
-    const float* p = reinterpret_cast<const float*>(base + (size_t)i * stride);
-    if (isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2])) {
-      for (int a = 0; a < 3; a++) { lo[a] = hi[a] = f2ord(p[a]); }
-      cnt = 1u;
-    }
+struct RecordElems {
+  static constexpr int kFields = 16;
+  const char* base; size_t stride; int nfields;
+  float* out;
+  __device__ int fields() const { return nfields; }
+  __device__ const float* fetch(uint32_t g, uint32_t) const { return reinterpret_cast<const float*>(base + (size_t)g * stride); }
+  __device__ bool point(uint32_t g, float4* pt) const {
+    const float* p = fetch(g, 0u);
+    *pt = make_float4(p[0], p[1], p[2], 0.f);
+    return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);
   }
-  for (int off = 32; off >= 1; off >>= 1) {   // one atomic per wave, not per point
-    for (int a = 0; a < 3; a++) { lo[a] = min(lo[a], (unsigned int)__shfl_xor((int)lo[a], off, 64)); hi[a] = max(hi[a], (unsigned int)__shfl_xor((int)hi[a], off, 64)); }
-    cnt += (unsigned int)__shfl_xor((int)cnt, off, 64);
+  __device__ void put(uint32_t cell, const float (&mean)[kFields]) const {
+#pragma unroll
+    for (int f = 0; f < kFields; f++)
+      if (f < nfields) out[(size_t)cell * nfields + f] = mean[f];
   }
-  if ((threadIdx.x & 63) == 0 && cnt) {
-    for (int a = 0; a < 3; a++) { atomicMin(&mm[a], lo[a]); atomicMax(&mm[3 + a], hi[a]); }
-    atomicAdd(&mm[6], cnt);
-  }
-}
-
-__global__ void k_vg_keys(const char* __restrict__ base, size_t stride, uint32_t n, float inv, int mb0, int mb1, int mb2, long long div0, long long div01, uint64_t* __restrict__ keys,
-                          uint32_t* __restrict__ vals) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float* p = reinterpret_cast<const float*>(base + (size_t)i * stride);
-  uint64_t key = 1ull << 32;   // non-finite points sort behind every cell
-  if (isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2])) {
-    const long long i0 = (long long)(floorf(p[0] * inv) - (float)mb0), i1 = (long long)(floorf(p[1] * inv) - (float)mb1), i2 = (long long)(floorf(p[2] * inv) - (float)mb2);
-    key = (uint64_t)(i0 + i1 * div0 + i2 * div01);
-  }
-  keys[i] = key;
-  vals[i] = i;
-}
-
-__global__ void k_vg_heads(const uint64_t* __restrict__ keys, uint32_t n, uint32_t* __restrict__ head) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint64_t k = keys[i];
-  head[i] = (k < (1ull << 32) && (i == 0 || keys[i - 1] != k)) ? 1u : 0u;
-}
-
-// position of every cell's first element in the sorted order
-__global__ void k_vg_head_pos(const uint32_t* __restrict__ head, const uint32_t* __restrict__ slot, uint32_t n, uint32_t* __restrict__ pos) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n && head[i]) pos[slot[i]] = i;
-}
-
-// one wave per cell: lane l sums elements l, l + 64, ... of the cell's run in double, then a fixed shuffle tree
-// (deterministic; a dense leaf near the sensor holds thousands of points, which one lane alone would walk serially)
-__global__ void __launch_bounds__(256) k_vg_average(const char* __restrict__ base, size_t stride, int nfields, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ pos,
-                                                    uint32_t ncells, uint32_t nvalid, float* __restrict__ out) {
-  const uint32_t cell = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (cell >= ncells) return;
-  const uint32_t b = pos[cell], e = cell + 1 < ncells ? pos[cell + 1] : nvalid;
-  double acc[16];
-  for (int f = 0; f < 16; f++) acc[f] = 0.0;
-  for (uint32_t j = b + lane; j < e; j += 64) {
-    const float* p = reinterpret_cast<const float*>(base + (size_t)vals[j] * stride);
-    for (int f = 0; f < nfields; f++) acc[f] += (double)p[f];
-  }
-  for (int f = 0; f < nfields; f++) {
-    double v = acc[f];
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (lane == 0) out[(size_t)cell * nfields + f] = (float)(v / (double)(e - b));
-  }
-}
+};
 
 }  // namespace
 
-// scratch bytes voxel_downsample_device needs for n points (keys, values, flags, rocPRIM temporaries)
+// scratch bytes voxel_downsample_device needs for n points (keys, values, rocPRIM temporaries)
 size_t voxel_downsample_scratch_bytes(size_t n) {
-  size_t t1 = 0, t2 = 0;
-  uint64_t* k = nullptr; uint32_t* v = nullptr;
-  (void)rocprim::radix_sort_pairs(nullptr, t1, k, k, v, v, n, 0, 33, nullptr);
-  (void)rocprim::exclusive_scan(nullptr, t2, v, v, 0u, n, rocprim::plus<uint32_t>(), nullptr);
-  return up256(64) + 2 * up256(8 * n) + 4 * up256(4 * n) + up256(t1) + up256(t2);
+  size_t bytes = 0;
+  (void)vg::work_layout(nullptr, n, sizeof(uint32_t), 0, &bytes);
+  return bytes;
 }
 
 // d_in: n records of `stride` bytes (nfields = stride / 4 floats, x y z first); d_out: room for n records.  *n_out receives
 // the count.  `scratch`: voxel_downsample_scratch_bytes(n) bytes of device memory owned by the caller (no allocation here).
+// One wait, for the totals.
 int voxel_downsample_device(hipStream_t stream, const void* d_in, size_t n, size_t stride, float leaf, float* d_out, size_t* n_out, void* scratch, std::string* err) {
   *n_out = 0;
   if (n == 0) return PCM_OK;
   const int nfields = (int)(stride / 4);
   if (nfields < 3 || nfields > 16 || (stride % 4) != 0) { *err = "records must be 3..16 floats"; return PCM_ERR_INVALID_ARGUMENT; }
   if (!(leaf > 0.f)) { *err = "leaf size must be > 0"; return PCM_ERR_INVALID_ARGUMENT; }
-  const float inv = 1.0f / leaf;
-  size_t tmp_bytes = 0, tmp2_bytes = 0;
-  {
-    uint64_t* k = nullptr; uint32_t* v = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, tmp_bytes, k, k, v, v, n, 0, 33, stream);
-    (void)rocprim::exclusive_scan(nullptr, tmp2_bytes, v, v, 0u, n, rocprim::plus<uint32_t>(), stream);
-  }
-  char* cur = static_cast<char*>(scratch);
-  unsigned int* d_mm = reinterpret_cast<unsigned int*>(cur); cur += up256(64);
-  uint64_t* keys = reinterpret_cast<uint64_t*>(cur); cur += up256(8 * n);
-  uint64_t* keys_s = reinterpret_cast<uint64_t*>(cur); cur += up256(8 * n);
-  uint32_t* vals = reinterpret_cast<uint32_t*>(cur); cur += up256(4 * n);
-  uint32_t* vals_s = reinterpret_cast<uint32_t*>(cur); cur += up256(4 * n);
-  uint32_t* head = reinterpret_cast<uint32_t*>(cur); cur += up256(4 * n);
-  uint32_t* slot = reinterpret_cast<uint32_t*>(cur); cur += up256(4 * n);
-  void* tmp = cur; cur += up256(tmp_bytes);
-  void* tmp2 = cur;
-  int rc = PCM_OK;
-  const unsigned nb = (unsigned)((n + 255) / 256);
-  const char* base = static_cast<const char*>(d_in);
-  unsigned int h_mm[7] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u};
-  PCM_HIPCK_ERR(err, hipMemcpyAsync(d_mm, h_mm, sizeof(h_mm), hipMemcpyHostToDevice, stream));
-  k_vg_minmax<<<nb, 256, 0, stream>>>(base, stride, (uint32_t)n, d_mm);
-  PCM_HIPCK_ERR(err, hipMemcpyAsync(h_mm, d_mm, sizeof(h_mm), hipMemcpyDeviceToHost, stream));
+  size_t bytes = 0;
+  const vg::Work W = vg::work_layout(static_cast<char*>(scratch), n, sizeof(uint32_t), 0, &bytes);
+  const RecordElems E{static_cast<const char*>(d_in), stride, nfields, d_out};
+  vg::clear(stream, W);
+  vg::single_minmax(stream, E, (uint32_t)n, W);
+  const int rc = vg::single_cells(err, stream, E, (uint32_t)n, leaf, W);
+  if (rc != PCM_OK) return rc;
+  uint32_t totals[3] = {0u, 0u, 0u};   // cells, finite points, index overflow
+  PCM_HIPCK_ERR(err, hipMemcpyAsync(totals, W.small, sizeof(totals), hipMemcpyDeviceToHost, stream));
   PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
-  if (h_mm[6] == 0) return PCM_OK;   // no finite point
-  float mn[3], mx[3];
-  for (int a = 0; a < 3; a++) { mn[a] = ord2f(h_mm[a]); mx[a] = ord2f(h_mm[3 + a]); }
-  const long long dx = (long long)((mx[0] - mn[0]) * inv) + 1, dy = (long long)((mx[1] - mn[1]) * inv) + 1, dz = (long long)((mx[2] - mn[2]) * inv) + 1;
-  if (dx * dy * dz > 2147483647ll) { *err = "leaf size too small for the extent of the cloud (index overflow)"; return PCM_ERR_OUT_OF_RANGE; }
-  int min_b[3], max_b[3];
-  for (int a = 0; a < 3; a++) { min_b[a] = (int)floorf(mn[a] * inv); max_b[a] = (int)floorf(mx[a] * inv); }
-  const long long div0 = (long long)max_b[0] - min_b[0] + 1, div1 = (long long)max_b[1] - min_b[1] + 1;
-  k_vg_keys<<<nb, 256, 0, stream>>>(base, stride, (uint32_t)n, inv, min_b[0], min_b[1], min_b[2], div0, div0 * div1, keys, vals);
-  PCM_HIPCK_ERR(err, hipGetLastError());
-  PCM_HIPCK_ERR(err, rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_s, vals, vals_s, n, 0, 33, stream));
-  k_vg_heads<<<nb, 256, 0, stream>>>(keys_s, (uint32_t)n, head);
-  PCM_HIPCK_ERR(err, hipGetLastError());
-  PCM_HIPCK_ERR(err, rocprim::exclusive_scan(tmp2, tmp2_bytes, head, slot, 0u, n, rocprim::plus<uint32_t>(), stream));
-  uint32_t last[2];
-  PCM_HIPCK_ERR(err, hipMemcpyAsync(&last[0], slot + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  PCM_HIPCK_ERR(err, hipMemcpyAsync(&last[1], head + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
-  const uint32_t ncells = last[0] + last[1];
-  uint32_t* pos = vals;   // the unsorted value array is free after the sort
-  k_vg_head_pos<<<nb, 256, 0, stream>>>(head, slot, (uint32_t)n, pos);
-  k_vg_average<<<(ncells + 3) / 4, 256, 0, stream>>>(base, stride, nfields, vals_s, pos, ncells, h_mm[6], d_out);
-  PCM_HIPCK_ERR(err, hipGetLastError());
-  PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
-  *n_out = (size_t)ncells;
-  return rc;
+  if (totals[2]) { *err = "leaf size too small for the extent of the cloud (index overflow)"; return PCM_ERR_OUT_OF_RANGE; }
+  *n_out = (size_t)totals[0];
+  return PCM_OK;
 }
 
 // ---------------------------------------------------------------------------
