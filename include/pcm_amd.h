@@ -332,6 +332,30 @@ int pcm_undistort(pcm_ctx *ctx, void *points, size_t n, size_t stride_bytes, siz
  * Replaces voxel_scan_.filter() of LaserMapping::Run (jueying_lio/src/laser_mapping.cc:323-328). */
 int pcm_voxel_downsample(pcm_ctx *ctx, const void *points, size_t n, size_t stride_bytes, int memory, float leaf_size, void *out, size_t capacity_points, size_t *n_out);
 
+/* pcl::VoxelGridLarge (jueying_slam/include/voxel_grid_large.cpp:23-255): pcm_voxel_downsample past 2^31 - 1 leaves.  While the
+ * leaf index of a piece of the cloud overflows, the piece is cut in two along its longest axis (x where dx is strictly the
+ * largest, else y where dy is, else z -- ties go to z) at mid = min + (max - min) / 2 in float: the first half keeps v <= mid, the
+ * second v > mid, both in input order.  Every piece that does not overflow is filtered by the plain VoxelGrid in its own box, and
+ * the results are concatenated in depth-first order, first half first.  A lattice cell that a cut plane crosses therefore gives
+ * one centroid per piece.  Without an overflow the result is pcm_voxel_downsample's bit for bit.
+ * A cut that would leave a piece whole (mid >= max: a flat axis chosen by the tie rule, adjacent floats) and a piece that still
+ * overflows after PCM_VOXEL_LARGE_MAX_DEPTH cuts are PCM_ERR_OUT_OF_RANGE; pcm_last_error names the piece's extent and the axis.
+ * Records of 3..16 floats, n <= 2^31 - 1, host or device buffers.  `out` must hold result->cells records: when capacity_points
+ * is smaller, PCM_ERR_INVALID_ARGUMENT is returned with the needed count in result->cells.  An error writes nothing to `out`. */
+#define PCM_VOXEL_LARGE_MAX_DEPTH 64
+typedef struct pcm_voxel_large_result {
+  uint64_t cells;            /* centroids written (needed, when capacity_points was too small) */
+  uint64_t finite_points;    /* points with finite x, y, z: the others count nowhere */
+  uint64_t pieces;           /* non-empty leaf pieces */
+  uint32_t depth;            /* cuts above the deepest piece */
+  uint32_t levels;           /* box passes run: depth + 1 */
+  uint32_t host_waits;       /* times the call waited for the device */
+  uint32_t reserved;
+  uint64_t workspace_bytes;  /* device memory allocated for the call and released before it returned */
+} pcm_voxel_large_result;
+int pcm_voxel_downsample_large(pcm_ctx *ctx, const void *points, size_t n, size_t stride_bytes, int memory, float leaf_size, void *out, size_t capacity_points,
+                               pcm_voxel_large_result *result);
+
 /* PointCloudPreprocess::AviaHandler (jueying_lio/src/pointcloud_preprocess.cc:44-88): the n points of a livox_ros_driver::CustomMsg
  * (20-byte records {uint32 offset_time; float x, y, z; uint8 reflectivity, tag, line; pad} -- msg->points.data()) filtered by line, tag,
  * point_filter_num, the duplicate test against the previous copied point and the blind radius, with the reference's own operator

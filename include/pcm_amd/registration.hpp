@@ -756,6 +756,49 @@ private:
   std::vector<double> recent_;
 };
 
+// pcl::VoxelGridLarge (jueying_slam/include/voxel_grid_large.h: the VoxelGrid that cuts a cloud whose leaf index overflows along its
+// longest axis and filters the halves on their own) on the device, with the call surface its users have (setLeafSize,
+// setInputCloud, filter; pcd2map's and the map server's VoxelGrid take the same three calls).  A point is handed over as the
+// record of floats it is -- x y z first, every float of it averaged, padding included -- so PointT holds 3..16 floats and
+// nothing else (PointXYZ, PointXYZI, PointXYZINormal).  One leaf size for the three axes, as every call site of the reference
+// sets it; a leaf index that cannot be resolved (pcm_amd.h) throws.
+template <typename PointT>
+class VoxelGridLarge {
+public:
+  using Cloud = pcl::PointCloud<PointT>;
+  static_assert(sizeof(PointT) % sizeof(float) == 0 && sizeof(PointT) >= 3 * sizeof(float) && sizeof(PointT) <= 16 * sizeof(float), "a point of 3..16 floats");
+
+  explicit VoxelGridLarge(int device = 0) : ctx_(pcm_create(device, nullptr)) {
+    if (!ctx_) throw std::runtime_error("pcm_create failed");
+  }
+  ~VoxelGridLarge() { if (ctx_) pcm_destroy(ctx_); }
+  VoxelGridLarge(const VoxelGridLarge&) = delete;
+  VoxelGridLarge& operator=(const VoxelGridLarge&) = delete;
+
+  void setLeafSize(float lx, float ly, float lz) {
+    if (lx != ly || lx != lz) throw std::invalid_argument("pcm_amd::VoxelGridLarge: one leaf size for the three axes");
+    leaf_ = lx;
+  }
+  void setInputCloud(const typename Cloud::ConstPtr& cloud) { input_ = cloud; }
+  void filter(Cloud& output) {
+    output.points.clear();
+    if (!input_ || input_->points.empty()) return;     // "No input dataset given!": an empty output
+    const size_t n = input_->points.size();
+    std::vector<PointT> cells(n);
+    const int rc = pcm_voxel_downsample_large(ctx_, input_->points.data(), n, sizeof(PointT), PCM_MEM_HOST, leaf_, cells.data(), n, &result_);
+    if (rc != PCM_OK) throw std::runtime_error(std::string("pcm_voxel_downsample_large: ") + pcm_last_error(ctx_));
+    cells.resize((size_t)result_.cells);
+    output.points.assign(cells.begin(), cells.end());
+  }
+  const pcm_voxel_large_result& result() const { return result_; }   // pieces, depth, levels of the last filter()
+
+private:
+  pcm_ctx* ctx_ = nullptr;
+  float leaf_ = 0.f;
+  typename Cloud::ConstPtr input_;
+  pcm_voxel_large_result result_{};
+};
+
 // jueying_slam's 2D occupancy mapping tool (src/tool/occupancy_mapping) on the device: OccupancyServer's getScan + processScan per
 // cloud, getGridMap and saveMap's image.  Constructed alone it owns a context (the online node, OccupancyServerRealTime: tf lookups
 // and the sensor-tilt pre-rotation stay with the caller); constructed over a LoamScanToMap it maps that context's key frames in

@@ -15,6 +15,7 @@ from .registration import LoamRegistration, LoamResult, LoamSubmapResult, LoamLo
 from .registration import loam_extract_features, loam_frame_begin_batch, pack_xyzirt  # noqa: F401
 from .registration import OccupancyGrid, OccupancyMap2D, save_map  # noqa: F401
 from .registration import LoamGlobalMapResult  # noqa: F401
+from .registration import VoxelLargeResult  # noqa: F401
 from .registration import LoamMapLoadResult, LoamMapCropResult, read_arealist, write_arealist  # noqa: F401
 from .registration import (ScanSegment, lidar_xyzirt_segment, lidar_xyzi_segment, depth_segment, rs_to_velodyne, hesai_to_velodyne,  # noqa: F401
                            fuse_lidar_cameras)

@@ -7,6 +7,8 @@
 // header is read then.  Everything else is device code and the launchers of the two pipelines of voxel_grid.hip:
 //   single segment, 32-bit keys:  clear | fold_boxes, [single_minmax], single_cells  -> {cells, valid elements, overflow}, no wait
 //   segmented, 64-bit keys:       clear, [seg_minmax], seg_cells                     -> the same, and cells per segment
+// vg::split is pcl::VoxelGridLarge's decision for a piece whose index overflows (voxel_grid_large.hip cuts the cloud with it and runs
+// the segmented pipeline with segment = piece); it compiles for the host as well (tests/voxel_grid_large_hooks.cpp).
 // A caller hands its elements over as a functor (Elems below): where a point lives, whether it counts, which segment and leaf
 // it has, where a cell's mean goes.  Both pipelines run on a Work, which work_layout sizes and places in memory the caller owns.
 #pragma once
@@ -67,6 +69,26 @@ PCM_VG_HD inline uint64_t cell(float x, float y, float z, float leaf, const long
   const long long i0 = (long long)(::floorf(x * inv) - (float)mb0), i1 = (long long)(::floorf(y * inv) - (float)mb1),
                   i2 = (long long)(::floorf(z * inv) - (float)mb2);
   return (uint64_t)(i0 + i1 * b[3] + i2 * b[4]);
+}
+
+// pcl::VoxelGridLarge::applyFilter's decision for a piece from its min / max (mm as for box()): a piece whose index does not
+// overflow -- box()'s own test -- is a leaf piece, as is an empty one; any other is cut at *mid along *axis, x where dx is
+// strictly the largest, else y where dy is, else z (ties go to z, the reference's rule).  mid = min + (max - min) / 2 in float:
+// the first piece keeps v <= mid, the second v > mid.  A cut with mid >= max would leave the piece whole (a degenerate axis
+// chosen by the tie rule, adjacent floats, an extent that overflows float): kPieceStuck, where the reference recurses for ever.
+enum { kPieceLeaf = 0, kPieceSplit = 1, kPieceStuck = 2 };
+PCM_VG_HD inline int split(const unsigned int* __restrict__ mm, float leaf, int* __restrict__ axis, float* __restrict__ mid) {
+  *axis = -1; *mid = 0.f;
+  if (mm[0] == 0xffffffffu || !(leaf > 0.f)) return kPieceLeaf;
+  const float inv = 1.0f / leaf;
+  float mn[3], mx[3];
+  double d[3];
+  for (int a = 0; a < 3; a++) { mn[a] = ord2f(mm[a]); mx[a] = ord2f(mm[3 + a]); d[a] = ::trunc((double)((mx[a] - mn[a]) * inv)) + 1.0; }
+  if (!(d[0] * d[1] * d[2] > 2147483647.0)) return kPieceLeaf;
+  const int ax = (d[0] > d[1] && d[0] > d[2]) ? 0 : (d[1] > d[0] && d[1] > d[2]) ? 1 : 2;
+  const float m = mn[ax] + (mx[ax] - mn[ax]) / 2;
+  *axis = ax; *mid = m;
+  return m < mx[ax] ? kPieceSplit : kPieceStuck;
 }
 
 #if defined(__HIPCC__)
@@ -290,16 +312,25 @@ template <class Elems> void seg_minmax(hipStream_t st, const Elems& E, uint32_t 
   k_seg_minmax<<<dim3((per_row + 255) / 256, rows), 256, 0, st>>>(E, per_row, W.mm);
 }
 
-// boxes and keys from the finished min / max, one sort for all segments, cell starts and counts, means; queues and does not wait
-template <class Elems> int seg_cells(std::string* err, hipStream_t st, const Elems& E, uint32_t rows, uint32_t per_row, uint32_t N, const Work& W) {
+// the two halves of seg_cells, for a caller that has to see the totals before a mean is written: boxes and keys from the
+// finished min / max, one sort for all segments, cell starts and counts ...
+template <class Elems> int seg_sort(std::string* err, hipStream_t st, const Elems& E, uint32_t rows, uint32_t per_row, uint32_t N, const Work& W) {
   k_seg_boxes<<<(W.nseg + 255) / 256, 256, 0, st>>>(E, W.mm, W.nseg, W.box);
   k_seg_keys<<<dim3((per_row + 255) / 256, rows), 256, 0, st>>>(E, per_row, W.box, W.nseg, static_cast<uint64_t*>(W.keys), W.vals);
   PCM_HIPCK_ERR(err, hipGetLastError());
-  const int rc = sort_cells64(err, st, W, N);
-  if (rc != PCM_OK) return rc;
+  return sort_cells64(err, st, W, N);
+}
+// ... and the means
+template <class Elems> int seg_average(std::string* err, hipStream_t st, const Elems& E, uint32_t N, const Work& W) {
   k_average<uint64_t><<<std::min<unsigned>(1024u, (N + 3) / 4), 256, 0, st>>>(E, static_cast<const uint64_t*>(W.keys_s), W.vals_s, W.vals, W.small);
   PCM_HIPCK_ERR(err, hipGetLastError());
   return PCM_OK;
+}
+
+// boxes and keys from the finished min / max, one sort for all segments, cell starts and counts, means; queues and does not wait
+template <class Elems> int seg_cells(std::string* err, hipStream_t st, const Elems& E, uint32_t rows, uint32_t per_row, uint32_t N, const Work& W) {
+  const int rc = seg_sort(err, st, E, rows, per_row, N, W);
+  return rc != PCM_OK ? rc : seg_average(err, st, E, N, W);
 }
 #endif   // __HIPCC__
 

@@ -1513,6 +1513,75 @@ def _loam_export_map(self, which="both", first: int = 0, n: int = None, out=None
     return a
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# pcl::VoxelGridLarge on the device
+# ---------------------------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class VoxelLargeResult:
+    cells: int
+    finite_points: int
+    pieces: int
+    depth: int
+    levels: int
+    host_waits: int
+    workspace_bytes: int
+
+
+def _record_buffer(a, what):
+    """(pointer, rows, row bytes, memory) of a contiguous (rows, 3..16) float32 device tensor or host array."""
+    if hasattr(a, "data_ptr") and getattr(a, "is_cuda", False):
+        if a.dim() != 2 or not 3 <= a.shape[1] <= 16 or not a.is_contiguous() or a.element_size() != 4:
+            raise ValueError(what + ": expected a contiguous (rows, 3..16) float32 device tensor")
+        return a.data_ptr(), a.shape[0], 4 * a.shape[1], capi.MEM_DEVICE
+    if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.ndim != 2 or not 3 <= a.shape[1] <= 16 or not a.flags.c_contiguous:
+        raise ValueError(what + ": expected a contiguous (rows, 3..16) float32 array or device tensor")
+    return a.ctypes.data, a.shape[0], 4 * a.shape[1], capi.MEM_HOST
+
+
+def _voxel_downsample_large(self, points, leaf_size, out=None, rows=None):
+    """pcl::VoxelGridLarge (pcm_voxel_downsample_large): the VoxelGrid of ``voxel_downsample`` for clouds whose leaf index
+    overflows -- the cloud is cut along its longest axis until every piece fits, the pieces' cells follow one another in
+    depth-first order.  points: (N, 3..16) float32 host array or device tensor (``rows``: only its first rows).  Without ``out``
+    a host cloud returns (cells, VoxelLargeResult); with ``out`` (same memory and record width as the points) the cells are
+    written there and (count, VoxelLargeResult) returns.  On an error ``voxel_large_result`` still holds the counts."""
+    if not (hasattr(points, "data_ptr") and getattr(points, "is_cuda", False)):
+        points = np.ascontiguousarray(points, dtype=np.float32)
+    ptr, n, stride, mem = _record_buffer(points, "points")
+    if rows is not None:
+        if not 0 <= int(rows) <= n:
+            raise ValueError("rows exceeds the cloud")
+        n = int(rows)
+    r = capi.PcmVoxelLargeResult()
+    self._voxel_large_result = r
+
+    def result():
+        return VoxelLargeResult(int(r.cells), int(r.finite_points), int(r.pieces), int(r.depth), int(r.levels), int(r.host_waits), int(r.workspace_bytes))
+
+    if out is not None:
+        optr, cap, ostride, omem = _record_buffer(out, "out")
+        if ostride != stride or omem != mem:
+            raise ValueError("out must have the record width and the memory of the points")
+        self._check(self._L.pcm_voxel_downsample_large(self._h, ptr, n, stride, mem, float(leaf_size), optr, cap, C.byref(r)))
+        return int(r.cells), result()
+    if mem != capi.MEM_HOST:
+        raise ValueError("a device cloud needs a device tensor for the cells (out=)")
+    a = np.zeros((n, points.shape[1]), np.float32)
+    self._check(self._L.pcm_voxel_downsample_large(self._h, ptr, n, stride, mem, float(leaf_size), a.ctypes.data, a.shape[0], C.byref(r)))
+    return a[:int(r.cells)].copy(), result()
+
+
+def _voxel_large_result(self) -> VoxelLargeResult:
+    r = getattr(self, "_voxel_large_result", None)
+    if r is None:
+        raise capi.PcmError(-2, "voxel_large_result before voxel_downsample_large")
+    return VoxelLargeResult(int(r.cells), int(r.finite_points), int(r.pieces), int(r.depth), int(r.levels), int(r.host_waits), int(r.workspace_bytes))
+
+
+Registration.voxel_downsample_large = _voxel_downsample_large
+Registration.voxel_large_result = property(_voxel_large_result)
+LoamRegistration.voxel_downsample_large = _voxel_downsample_large
+LoamRegistration.voxel_large_result = property(_voxel_large_result)
+
 LoamRegistration.keyframe_global_keys = _loam_keyframe_global_keys
 LoamRegistration.keyframe_global_map = _loam_keyframe_global_map
 LoamRegistration.keyframe_global_result = property(_loam_keyframe_global_result)
