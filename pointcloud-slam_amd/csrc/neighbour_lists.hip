@@ -23,6 +23,7 @@
 #include "pcm_host.h"
 #include "plane_fit.h"
 #include "linearize_common.h"
+#include "keyed_best.h"
 
 #include <cstring>
 #include <string>
@@ -372,31 +373,60 @@ __global__ void __launch_bounds__(256) k_linearize_lists(const PairDesc* __restr
         if ((m >> bit) & 1u) {
           const uint32_t r = vox_base + gload_u16(&nl.bpref[(size_t)slot * 16 + w]) + (uint32_t)__popc(m & ((1u << bit) - 1u));
           const uint32_t s = gload_u(&nl.vox_start[r]), e = gload_u(&nl.vox_start[r + 1]);
-          Best best;
-          best_init(best, kp.max_range_sq);
           // the voxel's candidates in the reference's visit order, four per trip.  The run is padded to whole trips and starts on a
           // 64-byte boundary (build_neighbour_lists), so e - s is a multiple of four: no bounds test, all four loads under way and all
           // four distances formed before the first offer.  A load past the run's true end is a pad entry (d2 = +inf) and is never
-          // inserted; the offers go in visit order, each against the thr the earlier ones left.
-          for (uint32_t k = s; k < e; k += kListTrip) {
-            const float4 c0 = gload4(nl.pts + k), c1 = gload4(nl.pts + k + 1), c2 = gload4(nl.pts + k + 2), c3 = gload4(nl.pts + k + 3);
+          // among the in-range entries.
+          //
+          // Keyed walk (keyed_best.h): a run of at most kKeyedMaxRun entries keeps the six smallest (distance, position) keys by a
+          // branch-free min / med3 network.  The position `pos` is the same in every lane that is still walking, a scalar.
+          uint32_t bi[K];
+          int bm = 0;
+          const uint32_t len = e - s;
+          const bool keyed = len <= kKeyedMaxRun;
+          KeyedBest kb;
+          keyed_init(kb);
+          const float4* run = nl.pts + s;
+          for (uint32_t pos = 0; pos < (keyed ? len : 0u); pos += kListTrip) {
+            const float4 c0 = gload4(run + pos), c1 = gload4(run + pos + 1), c2 = gload4(run + pos + 2), c3 = gload4(run + pos + 3);
             const float d0 = list_d2(c0, q), d1 = list_d2(c1, q), d2 = list_d2(c2, q), d3 = list_d2(c3, q);
-            best_offer_d2(best, d0, k, kp.max_range_sq);
-            best_offer_d2(best, d1, k + 1, kp.max_range_sq);
-            best_offer_d2(best, d2, k + 2, kp.max_range_sq);
-            best_offer_d2(best, d3, k + 3, kp.max_range_sq);
+            keyed_offer(kb, keyed_pack(d0, pos));
+            keyed_offer(kb, keyed_pack(d1, pos + 1));
+            keyed_offer(kb, keyed_pack(d2, pos + 2));
+            keyed_offer(kb, keyed_pack(d3, pos + 3));
           }
-          best_finish(best);
-          if (best.m >= KMIN) {   // laser_mapping.cc:619-623
+          uint32_t kpos[kKeyedBest];
+          const bool decided = keyed_decode(kb, kp.max_range_sq, kpos, bm) && keyed;
+#pragma unroll
+          for (int j = 0; j < K; j++) bi[j] = s + kpos[j];
+          // An ambiguous lane (ties, near-ties, the range boundary, a run longer than kKeyedMaxRun) repeats its walk with the running
+          // list of the other kernels: the same offers in the same visit order.  The wave branches over this when no lane needs it.
+          if (!decided) {
+            Best best;
+            best_init(best, kp.max_range_sq);
+            for (uint32_t k = s; k < e; k += kListTrip) {
+              const float4 c0 = gload4(nl.pts + k), c1 = gload4(nl.pts + k + 1), c2 = gload4(nl.pts + k + 2), c3 = gload4(nl.pts + k + 3);
+              const float d0 = list_d2(c0, q), d1 = list_d2(c1, q), d2 = list_d2(c2, q), d3 = list_d2(c3, q);
+              best_offer_d2(best, d0, k, kp.max_range_sq);
+              best_offer_d2(best, d1, k + 1, kp.max_range_sq);
+              best_offer_d2(best, d2, k + 2, kp.max_range_sq);
+              best_offer_d2(best, d3, k + 3, kp.max_range_sq);
+            }
+            best_finish(best);
+            bm = best.m;
+#pragma unroll
+            for (int j = 0; j < K; j++) bi[j] = best.i[j];
+          }
+          if (bm >= KMIN) {   // laser_mapping.cc:619-623
             float px[K], py[K], pz[K];
 #pragma unroll
             for (int j = 0; j < K; j++) {
               float4 mp = make_float4(0.f, 0.f, 0.f, 0.f);
-              if (j < best.m) mp = gload4(nl.pts + best.i[j]);
+              if (j < bm) mp = gload4(nl.pts + bi[j]);
               px[j] = mp.x; py[j] = mp.y; pz[j] = mp.z;
             }
             float4 fit;
-            if (esti_plane<true>(px, py, pz, best.m, kp.plane_threshold, &fit)) pl = fit;
+            if (esti_plane<true>(px, py, pz, bm, kp.plane_threshold, &fit)) pl = fit;
           }
         }
       }
