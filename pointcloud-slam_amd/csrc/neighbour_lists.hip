@@ -40,6 +40,8 @@ constexpr int kKeyBias = 1 << 20;
 // of the squares are +inf (with and without FMA contraction), and best_offer's `d2 < thr` with thr <= max_r2f <= +inf is false.
 constexpr uint32_t kListTrip = 4;
 constexpr uint32_t kListPadId = 0xffffffffu;
+// Trips the keyed walk of k_linearize_lists loads ahead of the one it consumes; the point lists end with as many zeroed trips.
+constexpr uint32_t kWalkAhead = 1;
 
 __device__ inline uint64_t nl_pack(int x, int y, int z) { return ((uint64_t)(uint32_t)(x + kKeyBias) << 42) | ((uint64_t)(uint32_t)(y + kKeyBias) << 21) | (uint64_t)(uint32_t)(z + kKeyBias); }
 
@@ -299,9 +301,12 @@ int build_neighbour_lists(hipStream_t stream, const TargetMap& map, int nn, Neig
     const size_t total = h_cnt[1];
     // The starts of the point lists are multiples of kListTrip entries = 64 bytes and DevBuf's hipMalloc returns at least 256-byte
     // aligned memory, so every run starts on a 64-byte boundary; `total` counts the pad entries, so the last trip of the last run
-    // ends inside the array.  + 4: the walk of the leaf lists (pclndt.hip) reads (never uses) up to three entries past a run.
-    if ((rc = out->pts.reserve(stream, err, total + 4, total + 4)) != PCM_OK) return rc;
-    PCM_HIPCK_ERR(err, hipMemsetAsync(out->pts + total, 0, sizeof(float4) * 4, stream));
+    // ends inside the array.  Zeroed tail: the walk of the leaf lists (pclndt.hip) reads (never uses) up to three entries past a
+    // run, the keyed walk of k_linearize_lists loads (never offers) kWalkAhead trips past one.
+    const size_t tail = point_lists ? (size_t)kListTrip * kWalkAhead : 4;
+    static_assert(kListTrip * kWalkAhead >= 4, "the tail of the point lists is no shorter than that of the leaf lists");
+    if ((rc = out->pts.reserve(stream, err, total + tail, total + tail)) != PCM_OK) return rc;
+    PCM_HIPCK_ERR(err, hipMemsetAsync(out->pts + total, 0, sizeof(float4) * tail, stream));
     if (ndt_leaves) k_nl_leaf_lists<true><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of_map(map), mode, ndt_leaves, nn, nullptr, out->start, out->pts);
     else k_nl_lists<true><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of_map(map), nn, nullptr, out->start, out->pts);
     PCM_HIPCK_ERR(err, hipGetLastError());
@@ -331,6 +336,24 @@ int build_neighbour_lists(hipStream_t stream, const TargetMap& map, int nn, Neig
 __device__ inline float list_d2(const float4& mp, const float (&q)[3]) {
   const float dx = mp.x - q[0], dy = mp.y - q[1], dz = mp.z - q[2];
   return dx * dx + dy * dy + dz * dz;
+}
+
+// one trip of the keyed walk: its four loads, and its four candidates into the key network in list order
+__device__ inline void walk_load(float4 (&c)[kListTrip], const float4* p) {
+#pragma unroll
+  for (uint32_t j = 0; j < kListTrip; j++) c[j] = gload4(p + j);
+}
+__device__ inline void walk_offer(KeyedBest& kb, const float4 (&c)[kListTrip], const float (&q)[3], uint32_t pos) {
+  // An empty statement that reads the four w components (the candidates' indices, which the keyed walk does not need): it issues
+  // nothing.  Without it the register allocator treats the w register of a load that is still in flight as free, parks a
+  // temporary of the running trip in it, and the compiler must then wait for that load before the temporary is written -- a full
+  // wait in the middle of the trip the load was issued ahead of.
+  asm volatile("" ::"v"(c[0].w), "v"(c[1].w), "v"(c[2].w), "v"(c[3].w));
+  const float d0 = list_d2(c[0], q), d1 = list_d2(c[1], q), d2 = list_d2(c[2], q), d3 = list_d2(c[3], q);
+  keyed_offer(kb, keyed_pack(d0, pos));
+  keyed_offer(kb, keyed_pack(d1, pos + 1));
+  keyed_offer(kb, keyed_pack(d2, pos + 2));
+  keyed_offer(kb, keyed_pack(d3, pos + 3));
 }
 
 // ---------------------------------------------------------------------------
@@ -387,13 +410,33 @@ __global__ void __launch_bounds__(256) k_linearize_lists(const PairDesc* __restr
           KeyedBest kb;
           keyed_init(kb);
           const float4* run = nl.pts + s;
-          for (uint32_t pos = 0; pos < (keyed ? len : 0u); pos += kListTrip) {
-            const float4 c0 = gload4(run + pos), c1 = gload4(run + pos + 1), c2 = gload4(run + pos + 2), c3 = gload4(run + pos + 3);
-            const float d0 = list_d2(c0, q), d1 = list_d2(c1, q), d2 = list_d2(c2, q), d3 = list_d2(c3, q);
-            keyed_offer(kb, keyed_pack(d0, pos));
-            keyed_offer(kb, keyed_pack(d1, pos + 1));
-            keyed_offer(kb, keyed_pack(d2, pos + 2));
-            keyed_offer(kb, keyed_pack(d3, pos + 3));
+          // Pipelined: the loads of trip pos + kWalkAhead * kListTrip are issued before trip pos is consumed, so they are in flight
+          // while the distances and the network of trip pos issue.  No bounds test on them: a trip consumed at pos < len starts at
+          // most kWalkAhead trips behind the run's last one, so the furthest entry read is s + len - kListTrip + kWalkAhead * kListTrip
+          // + (kListTrip - 1) < e + kWalkAhead * kListTrip <= num_candidates + kWalkAhead * kListTrip, inside the array
+          // (build_neighbour_lists keeps kWalkAhead zeroed trips behind the last run; for an empty run s <= num_candidates and the
+          // same bound holds for the prologue).  What a load past e brings -- the head of the next run, or the zeroed tail -- belongs
+          // to a trip at a position >= len: the loop ends before that trip is consumed, its registers are dropped, nothing of it is
+          // offered.  A lane whose run is longer than kKeyedMaxRun loads nothing here: no prologue, and it never enters the loop.
+          float4 buf[kWalkAhead + 1][kListTrip];
+          if (keyed) {
+#pragma unroll
+            for (uint32_t u = 0; u < kWalkAhead; u++) walk_load(buf[u], run + u * kListTrip);
+          }
+          // kWalkAhead + 1 trips per turn, the buffers in fixed roles (no copies): at the top buf[u] holds trip pos + u * kListTrip
+          // for u < kWalkAhead; step u loads trip u + kWalkAhead into the buffer that step u - 1 emptied and consumes buf[u].  The
+          // turn runs while all its trips are inside the run; the at most kWalkAhead trips left are loaded already.
+          uint32_t pos = 0;
+          for (; pos + kWalkAhead * kListTrip < (keyed ? len : 0u); pos += (kWalkAhead + 1) * kListTrip) {
+#pragma unroll
+            for (uint32_t u = 0; u <= kWalkAhead; u++) {
+              walk_load(buf[(u + kWalkAhead) % (kWalkAhead + 1)], run + pos + (u + kWalkAhead) * kListTrip);
+              walk_offer(kb, buf[u], q, pos + u * kListTrip);
+            }
+          }
+#pragma unroll
+          for (uint32_t u = 0; u < kWalkAhead; u++) {
+            if (pos + u * kListTrip < (keyed ? len : 0u)) walk_offer(kb, buf[u], q, pos + u * kListTrip);
           }
           uint32_t kpos[kKeyedBest];
           const bool decided = keyed_decode(kb, kp.max_range_sq, kpos, bm) && keyed;
@@ -417,13 +460,20 @@ __global__ void __launch_bounds__(256) k_linearize_lists(const PairDesc* __restr
 #pragma unroll
             for (int j = 0; j < K; j++) bi[j] = best.i[j];
           }
+          // The five chosen candidates again, by index, for the fit: all five loads issued back to back ahead of the bm >= KMIN
+          // test, one round trip.  (Guarded by `if (j < bm)` the fourth and the fifth load each sat in a branch of its own behind a
+          // full wait: three round trips.)  Every lane loads five entries: entry j < bm is its j-th best, any other load reads the
+          // run's first entry (address s: inside the array, see above) and its value is replaced by zero -- an index that bm
+          // excludes is never formed into an address.
+          float4 fp[K];
+#pragma unroll
+          for (int j = 0; j < K; j++) fp[j] = gload4(nl.pts + (j < bm ? bi[j] : s));
           if (bm >= KMIN) {   // laser_mapping.cc:619-623
             float px[K], py[K], pz[K];
 #pragma unroll
             for (int j = 0; j < K; j++) {
-              float4 mp = make_float4(0.f, 0.f, 0.f, 0.f);
-              if (j < bm) mp = gload4(nl.pts + bi[j]);
-              px[j] = mp.x; py[j] = mp.y; pz[j] = mp.z;
+              asm volatile("" ::"v"(fp[j].w));   // see walk_offer
+              px[j] = j < bm ? fp[j].x : 0.f; py[j] = j < bm ? fp[j].y : 0.f; pz[j] = j < bm ? fp[j].z : 0.f;
             }
             float4 fit;
             if (esti_plane<true>(px, py, pz, bm, kp.plane_threshold, &fit)) pl = fit;
