@@ -214,6 +214,33 @@ int pcm_swap_source_and_target(pcm_ctx *ctx);              /* impl/fast_gicp_imp
 int pcm_clear_source(pcm_ctx *ctx);                        /* :60-64 */
 int pcm_clear_target(pcm_ctx *ctx);                        /* :66-69 */
 
+/* One built target for several contexts.  The reference's registration objects take one PointCloud::ConstPtr and cache by
+ * pointer identity (impl/fast_gicp_impl.hpp:72-90), so N objects against one map hold the map once; here a context owns its
+ * target, and pcm_share_target makes `dst` register against the target `src` holds from now on: the cloud, its voxel map and
+ * what the model derives from them (candidate / neighbour lists, pclomp NDT leaves, GICP-family covariances and voxel
+ * distributions) exist once, however many contexts hold them.
+ *   - Both contexts live on one device, are of the same model (not PCM_MODEL_LOAM: PCM_ERR_UNSUPPORTED) and agree in every
+ *     configuration field that decides how a target is built: model, voxel_resolution, num_neighbors, neighbor_search_radius,
+ *     the flags NEIGHBOUR_LISTS / NO_NEIGHBOUR_LISTS / REFERENCE_KNN_ORDER / COUNTED_SEARCH / NO_LDS_STAGING / FUSED_STEP,
+ *     map_capacity (P2PLANE), and for the GICP family k_correspondences, regularization, voxel_mode, covariance_method and the
+ *     RBF parameters.  A difference, a `src` without a target or dst == src: PCM_ERR_INVALID_ARGUMENT, and pcm_last_error(dst)
+ *     names the first field that differs.  Solver settings may differ.
+ *   - The call completes the target in `src` on src's stream -- everything a registration would otherwise build lazily,
+ *     the lists included unless the configuration rules them out (sharing is the repeated use their policy waits for) -- and
+ *     waits for that stream.  From then on the target is immutable while more than one context holds it, and any stream reads it.
+ *   - `dst` lets go of the target it had.  pcm_set_target, pcm_clear_target and pcm_destroy on a holder detach that holder only;
+ *     the memory goes with the last holder, so `src` may be destroyed first.
+ *   - What would change a target that has more than one holder returns PCM_ERR_UNSUPPORTED and changes nothing:
+ *     pcm_target_insert, pcm_map_incremental, pcm_lio_frame_end, pcm_set_covariances(target), pcm_swap_source_and_target, and a
+ *     pcm_set_config that changes one of the fields above.  There is no copy-on-write.
+ *   - A target that aliases a caller's device buffer (it arrived as a zero-copy source and was swapped into the target's place)
+ *     stays the caller's to keep alive and unchanged, now for as long as any holder registers against it.
+ *   - Neither context may be in another call while pcm_share_target runs.  Afterwards the holders are as independent as any
+ *     two contexts: each on its own stream and thread, or together in one pcm_align_batch.
+ * pcm_target_share_count: the contexts holding ctx's target (1 = not shared), or a negative pcm_status. */
+int pcm_share_target(pcm_ctx *dst, pcm_ctx *src);
+int pcm_target_share_count(pcm_ctx *ctx);
+
 /* pcl::Registration::align(out, guess) -> computeTransformation
  * (impl/lsq_registration_impl.hpp:52-79).  Transforming the output cloud is
  * left to the adapter (pcl::transformPointCloud, :78). */

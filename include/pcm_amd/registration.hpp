@@ -130,6 +130,23 @@ public:
     check(pcm_set_target(ctx_, cloud->points.data(), cloud->size(), sizeof(PointTarget), PCM_MEM_HOST, reinterpret_cast<uint64_t>(cloud.get())), "pcm_set_target");
   }
 
+  // One built target for several objects (pcm_share_target): this object registers against the target `other` holds from now on --
+  // the cloud, its voxel map and what the model derives from them exist once on the device -- as the reference's objects do when they
+  // are handed one PointCloud::ConstPtr.  Both are of one class with the settings that decide how a target is built equal (the
+  // exception names the first that differs).  setInputTarget(cloud) keeps its meaning: with the shared cloud it is the reference's
+  // no-op, with another it gives this object a target of its own again; the other holders are not touched either way.
+  void shareTargetWith(LsqRegistration& other) {
+    other.push_config();
+    push_config();
+    check(pcm_share_target(ctx_, other.ctx_), "pcm_share_target");
+    target_ = other.target_;
+  }
+  int targetShareCount() const {
+    const int n = pcm_target_share_count(ctx_);
+    if (n < 0) check(n, "pcm_target_share_count");
+    return n;
+  }
+
 protected:
   // pcl::Registration::align() calls this (lsq_registration_impl.hpp:52-79)
   void computeTransformation(PointCloudSource& output, const Matrix4& guess) override {

@@ -33,6 +33,7 @@ SYMBOLS = [
     "pcm_lidar_default_desc", "pcm_lidar_filter", "pcm_lio_frame_begin_cloud",
     "pcm_lio_default_update_params", "pcm_lio_update", "pcm_lio_update_trace",
     "pcm_lio_default_imu_state", "pcm_lio_imu_init", "pcm_lio_propagate",
+    "pcm_share_target", "pcm_target_share_count",
 ]
 
 PCM_ABI_VERSION = 3   # include/pcm_amd.h
@@ -332,6 +333,8 @@ def load_library():
         f.argtypes = [vp, vp, sz, sz, i32, u64]
     for f in (L.pcm_swap_source_and_target, L.pcm_clear_source, L.pcm_clear_target, L.pcm_reset_stats):
         f.argtypes = [vp]
+    L.pcm_share_target.argtypes = [vp, vp]
+    L.pcm_target_share_count.argtypes = [vp]
     L.pcm_align.argtypes = [vp, vp, C.POINTER(PcmResult)]
     L.pcm_linearize.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     L.pcm_compute_error.argtypes = [vp, vp, C.POINTER(C.c_double)]

@@ -210,8 +210,8 @@ int align_batch_impl(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_resu
   for (int i = 0; i < n && lists; i++) lists = lists_view_for(ctxs[i]).pts != nullptr;
   if (ref_order) {
     for (int i = 0; i < n; i++) {
-      if (ctxs[i]->map.max_voxel_points > (uint32_t)kRefMaxVoxelPoints) {
-        c0->err = "PCM_FLAG_REFERENCE_KNN_ORDER supports at most " + std::to_string(kRefMaxVoxelPoints) + " points per voxel (this map: " + std::to_string(ctxs[i]->map.max_voxel_points) + ")";
+      if (ctxs[i]->tg->map.max_voxel_points > (uint32_t)kRefMaxVoxelPoints) {
+        c0->err = "PCM_FLAG_REFERENCE_KNN_ORDER supports at most " + std::to_string(kRefMaxVoxelPoints) + " points per voxel (this map: " + std::to_string(ctxs[i]->tg->map.max_voxel_points) + ")";
         return PCM_ERR_UNSUPPORTED;
       }
     }
@@ -338,7 +338,7 @@ int single_pass(pcm_ctx* c, const double T[16], bool linearize, double sums[kPar
   if (ndt) launch_ndt(c->stream, w->d_descs, w->d_states, kp1, 1, ndt_kind(c->cfg.model), !linearize);
   else if (is_gicp(c->cfg.model)) launch_gicp(c->stream, w->d_descs, w->d_states, kp1, 1, c->cfg.model == PCM_MODEL_VGICP, !linearize);
   else if (linearize && (c->cfg.flags & PCM_FLAG_REFERENCE_KNN_ORDER)) {
-    if (c->map.max_voxel_points > (uint32_t)kRefMaxVoxelPoints) { c->err = "PCM_FLAG_REFERENCE_KNN_ORDER supports at most " + std::to_string(kRefMaxVoxelPoints) + " points per voxel"; return PCM_ERR_UNSUPPORTED; }
+    if (c->tg->map.max_voxel_points > (uint32_t)kRefMaxVoxelPoints) { c->err = "PCM_FLAG_REFERENCE_KNN_ORDER supports at most " + std::to_string(kRefMaxVoxelPoints) + " points per voxel"; return PCM_ERR_UNSUPPORTED; }
     launch_linearize_reforder(c->stream, w->d_descs, w->d_states, kp1, 1, true);
   }
   else if (linearize && lists_view_for(c).pts != nullptr) launch_linearize_lists(c->stream, w->d_descs, w->d_states, kp1, 1, true);
@@ -354,7 +354,7 @@ int single_pass(pcm_ctx* c, const double T[16], bool linearize, double sums[kPar
 
 // one pclomp NDT pass on the device: launch, read the 48-double row back (pass 0/1: H, g, score; pass 2: H)
 int pclndt_eval(pcm_ctx* c, int pass, const NdtOmpParams& P, ndtomp::Eval* e, double gauss_d3) {
-  launch_pclndt_pass(c->stream, c->map, c->pleaf, c->pleaf_f, ndt_lists_view(c), c->src.d_pts, (uint32_t)c->src.n, P, pass, c->ndt_partials, c->ndt_out, gauss_d3);
+  launch_pclndt_pass(c->stream, c->tg->map, c->tg->pleaf, c->tg->pleaf_f, ndt_lists_view(c), c->src.d_pts, (uint32_t)c->src.n, P, pass, c->ndt_partials, c->ndt_out, gauss_d3);
   PCM_HIPCK(c, hipGetLastError());
   PCM_HIPCK(c, hipMemcpyAsync(c->ndt_out_host, c->ndt_out, sizeof(double) * 48, hipMemcpyDeviceToHost, c->stream));
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));
@@ -409,7 +409,7 @@ int pclndt_align_batch(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_re
   int max_blocks = 1;
   for (int i = 0; i < n; i++) {
     pcm_ctx* c = ctxs[i];
-    w.h_objs[i] = make_ndt_object(c->map, c->pleaf, c->pleaf_f, ndt_lists_view(c), c->src.d_pts, (uint32_t)c->src.n, c->ndt_partials);
+    w.h_objs[i] = make_ndt_object(c->tg->map, c->tg->pleaf, c->tg->pleaf_f, ndt_lists_view(c), c->src.d_pts, (uint32_t)c->src.n, c->ndt_partials);
     max_blocks = std::max(max_blocks, (int)w.h_objs[i].nblocks);
     ndtomp::ndt_machine_start(w.h_ms[i], guesses + 16 * (size_t)i, (double)c->cfg.ndt_step_size, c->cfg.translation_eps, (double)c->cfg.ndt_outlier_ratio,
                               c->cfg.voxel_resolution, c->cfg.max_iterations, c->cfg.num_neighbors);

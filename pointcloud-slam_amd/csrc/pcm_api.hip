@@ -83,6 +83,41 @@ int set_cloud(pcm_ctx* c, Cloud* cl, const void* points, size_t n, size_t stride
   return PCM_OK;
 }
 
+// ---- the context's reference to its target (target_share.h) ---------------------------------------------------------------------
+// What runs before the last reference frees a target: the device current and this context's stream drained (dev_buf.h).  The
+// other contexts that held it drained their own streams when they let go (drain_before_letting_go), so nothing queued reads it.
+auto target_release_hook(pcm_ctx* c) {
+  return [c] {
+    if (c->device < 0) return;
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+  };
+}
+
+// this context's queued work may read the target it is about to let go of
+void drain_before_letting_go(pcm_ctx* c) {
+  if (c->device < 0 || !c->tg.shared()) return;
+  (void)hipSetDevice(c->device);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+}
+
+// a holder of a shared target that sets or clears its target leaves the others alone: it goes on with an empty target of its own
+int own_target_again(pcm_ctx* c) {
+  if (!c->tg.shared()) return PCM_OK;
+  drain_before_letting_go(c);
+  if (!c->tg.renew(target_release_hook(c))) { c->err = "out of host memory"; return PCM_ERR_HIP; }
+  c->src_cov_valid = false;   // computed with the parameters the old target recorded
+  c->lio_planes_valid = false;
+  return PCM_OK;
+}
+
+// the answer of every call that would change a target other contexts read
+int refuse_shared(pcm_ctx* c, const char* call) {
+  c->err = std::string(call) + ": the target is shared by " + std::to_string(c->tg.holders()) +
+           " contexts and cannot be changed (pcm_set_target or pcm_clear_target gives this context a target of its own)";
+  return PCM_ERR_UNSUPPORTED;
+}
+
 auto make_ndt_solver(pcm_ctx* c) {
   auto ev = [c](int pass, const NdtOmpParams& P, ndtomp::Eval* e) { return pclndt_eval(c, pass, P, e); };
   ndtomp::Solver<decltype(ev)> s{ev};
@@ -132,6 +167,7 @@ void pcm_default_config(pcm_config* cfg) {
 pcm_ctx* pcm_create(int device, const pcm_config* cfg) {
   pcm_ctx* c = new (std::nothrow) pcm_ctx();
   if (!c) return nullptr;
+  if (!c->tg.create()) { delete c; return nullptr; }
   c->device = device;
   if (cfg) c->cfg = *cfg; else pcm_default_config(&c->cfg);
   int ndev = 0;
@@ -165,7 +201,9 @@ void pcm_destroy(pcm_ctx* c) {
   }
   // The context's own buffers (the DevBuf / PinnedBuf members of pcm_ctx, its clouds, maps and lists) and its sub-states (the
   // SubState members) free themselves here: `delete c` runs with the device current and before the context's stream is destroyed.
+  // The target goes with its last holder, under the same guarantee (target_release_hook).
   hipStream_t own = (c->device >= 0 && c->own_stream) ? c->stream : nullptr;
+  c->tg.detach(target_release_hook(c));
   delete c;
   if (own) hipStreamDestroy(own);
 }
@@ -189,6 +227,12 @@ int pcm_set_config(pcm_ctx* c, const pcm_config* cfg) {
   if (!cfg) return PCM_ERR_INVALID_ARGUMENT;
   int rc = validate_config(c, *cfg);
   if (rc != PCM_OK) return rc;
+  if (c->tg.shared()) {
+    if (const char* field = target_config_difference(c->cfg, *cfg)) {
+      c->err = std::string("pcm_set_config: ") + field + " decides how the target is built, and the target is shared by " + std::to_string(c->tg.holders()) + " contexts";
+      return PCM_ERR_UNSUPPORTED;
+    }
+  }
   c->cfg = *cfg;
   return PCM_OK;
 }
@@ -203,13 +247,15 @@ int pcm_set_stream(pcm_ctx* c, void* hip_stream) {
 
 int pcm_set_target(pcm_ctx* c, const void* points, size_t n, size_t stride_bytes, int memory, uint64_t tag) {
   CHECK_CTX(c);
-  if (tag != 0 && tag == c->tgt.tag && c->tgt.n == n) return PCM_OK;  // `if (target_ == cloud) return;`  fast_gicp_impl.hpp:83-85
-  int rc = set_cloud(c, &c->tgt, points, n, stride_bytes, memory, tag, false);
-  c->user_cov[1].clear();   // target_covs_.clear()  fast_gicp_impl.hpp:89
-  c->map.valid = false;
-  c->map.index_n = 0;   // another log: the sorted index of the old one is of no use
-  c->tgt_dynamic = false;
-  c->next_seq = (uint32_t)n;
+  if (tag != 0 && tag == c->tg->tgt.tag && c->tg->tgt.n == n) return PCM_OK;  // `if (target_ == cloud) return;`  fast_gicp_impl.hpp:83-85
+  int rc = own_target_again(c);
+  if (rc != PCM_OK) return rc;
+  rc = set_cloud(c, &c->tg->tgt, points, n, stride_bytes, memory, tag, false);
+  c->tg->user_cov.clear();   // target_covs_.clear()  fast_gicp_impl.hpp:89
+  c->tg->map.valid = false;
+  c->tg->map.index_n = 0;   // another log: the sorted index of the old one is of no use
+  c->tg->tgt_dynamic = false;
+  c->tg->next_seq = (uint32_t)n;
   c->lio_planes_valid = false;
   return rc;
 }
@@ -233,7 +279,7 @@ int pcm_set_source(pcm_ctx* c, const void* points, size_t n, size_t stride_bytes
   CHECK_CTX(c);
   if (tag != 0 && tag == c->src.tag && c->src.n == n) return PCM_OK;  // fast_gicp_impl.hpp:72-74
   int rc = set_cloud(c, &c->src, points, n, stride_bytes, memory, tag, true);
-  c->user_cov[0].clear();   // source_covs_.clear()  fast_gicp_impl.hpp:78
+  c->user_cov_src.clear();   // source_covs_.clear()  fast_gicp_impl.hpp:78
   c->src_sorted = false;
   c->lio_planes_valid = false;
   c->srcmap.valid = false;
@@ -243,14 +289,56 @@ int pcm_set_source(pcm_ctx* c, const void* points, size_t n, size_t stride_bytes
 
 int pcm_swap_source_and_target(pcm_ctx* c) {
   CHECK_CTX(c);
+  if (c->tg.shared()) return refuse_shared(c, "pcm_swap_source_and_target");
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));
-  c->src.swap(c->tgt);
-  std::swap(c->user_cov[0], c->user_cov[1]);   // source_covs_.swap(target_covs_)  fast_gicp_impl.hpp:55
-  c->map.valid = false;
+  c->src.swap(c->tg->tgt);
+  std::swap(c->user_cov_src, c->tg->user_cov);   // source_covs_.swap(target_covs_)  fast_gicp_impl.hpp:55
+  c->tg->map.valid = false;
   c->srcmap.valid = false;
-  c->map.index_n = 0; c->srcmap.index_n = 0;
+  c->tg->map.index_n = 0; c->srcmap.index_n = 0;
   c->src_sorted = false;
   return PCM_OK;
+}
+
+// dst registers against src's target from now on (pcm_amd.h).  The target is completed in src, on src's stream, which is then
+// drained: what dst -- and any later holder -- reads through its own stream was finished before this call returned, and nothing
+// writes to it while it has more than one holder.
+int pcm_share_target(pcm_ctx* dst, pcm_ctx* src) {
+  CHECK_CTX(dst);
+  if (!src) { dst->err = "pcm_share_target: null source context"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (src->device < 0) { dst->err = "pcm_share_target: the source context has no device"; return PCM_ERR_HIP; }
+  if (dst == src) { dst->err = "pcm_share_target: a context cannot share its target with itself"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (dst->cfg.model == PCM_MODEL_LOAM || src->cfg.model == PCM_MODEL_LOAM) {
+    dst->err = "pcm_share_target: the maps of a PCM_MODEL_LOAM context live in its own state and are not shared";
+    return PCM_ERR_UNSUPPORTED;
+  }
+  int rc = validate_config(dst, dst->cfg);
+  if (rc != PCM_OK) return rc;
+  if (dst->device != src->device) { dst->err = "pcm_share_target: the contexts live on different devices (device)"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (const char* field = target_config_difference(src->cfg, dst->cfg)) {
+    dst->err = std::string("pcm_share_target: the configurations differ in ") + field + ", which decides how the target is built";
+    return PCM_ERR_INVALID_ARGUMENT;
+  }
+  if (dst->tg.same_as(src->tg)) return PCM_OK;
+  if (src->tg->tgt.n == 0) { dst->err = "pcm_share_target: the source context has no target"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!src->tg.shared()) {   // a target that is shared already was completed when it was first shared
+    rc = validate_config(src, src->cfg);
+    if (rc == PCM_OK) rc = build_target_for_sharing(src);
+    if (rc != PCM_OK) { dst->err = "pcm_share_target: " + src->err; return rc; }
+    PCM_HIPCK(dst, hipStreamSynchronize(src->stream));
+  }
+  PCM_HIPCK(dst, hipStreamSynchronize(dst->stream));   // its queued work may read the target it lets go of
+  dst->tg.attach(src->tg, target_release_hook(dst));
+  dst->src_cov_valid = false;   // computed with the parameters the old target recorded
+  dst->lio_planes_valid = false;
+  dst->stats.target_voxels = dst->tg->map.num_voxels;
+  dst->stats.target_slots = dst->tg->map.cap;
+  return PCM_OK;
+}
+
+int pcm_target_share_count(pcm_ctx* c) {
+  CHECK_CTX(c);
+  return c->tg.holders();
 }
 
 int pcm_clear_source(pcm_ctx* c) {
@@ -261,7 +349,8 @@ int pcm_clear_source(pcm_ctx* c) {
 
 int pcm_clear_target(pcm_ctx* c) {
   CHECK_CTX(c);
-  c->tgt.n = 0; c->tgt.tag = 0; c->map.valid = false; c->map.index_n = 0;
+  if (c->tg.shared()) return own_target_again(c);
+  c->tg->tgt.n = 0; c->tg->tgt.tag = 0; c->tg->map.valid = false; c->tg->map.index_n = 0;
   return PCM_OK;
 }
 
@@ -294,7 +383,7 @@ int pcm_fitness_score(pcm_ctx* c, const float T[16], double max_range, double* s
   if (rc != PCM_OK) return rc;
   rc = prepare(c);
   if (rc != PCM_OK) return rc;
-  if (!c->map.valid || !c->map.pts || c->src.n == 0) { c->err = "pcm_fitness_score: set a source and a target first"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!c->tg->map.valid || !c->tg->map.pts || c->src.n == 0) { c->err = "pcm_fitness_score: set a source and a target first"; return PCM_ERR_INVALID_ARGUMENT; }
   PairDesc d;
   fill_desc(c, &d, nullptr);
   const uint32_t n = (uint32_t)c->src.n;
@@ -458,7 +547,7 @@ int pcm_gicp_bfgs_update_correspondences(pcm_ctx* c, const float* transformation
   if (rc == PCM_OK) rc = c->bfgs_idx.reserve(c, 2 * n, 2 * (n + n / 4 + 64));
   if (rc != PCM_OK) return rc;
   uint32_t m = 0;
-  rc = gicp_bfgs_correspond_device(c->stream, c->map, coord_mode_for(c->cfg.model), c->srcmap, c->src_cov, c->tgt_cov, guess, transformation, (double)c->cfg.max_corr_dist,
+  rc = gicp_bfgs_correspond_device(c->stream, c->tg->map, coord_mode_for(c->cfg.model), c->srcmap, c->src_cov, c->tg->tgt_cov, guess, transformation, (double)c->cfg.max_corr_dist,
                                    reinterpret_cast<float4*>(c->bfgs.p), c->bfgs_idx, c->bfgs_idx + c->bfgs_idx.cap / 2, &m, &c->err);
   if (rc != PCM_OK) return rc;
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));
@@ -522,7 +611,8 @@ int pcm_set_covariances(pcm_ctx* c, int target, const double* covs, size_t n, in
   CHECK_CTX(c);
   if ((!covs && n) || (elems != 9 && elems != 16)) return PCM_ERR_INVALID_ARGUMENT;
   if (!is_gicp(c->cfg.model) || c->cfg.model == PCM_MODEL_VGICP_CUDA) { c->err = "covariances can be set for the GICP / VGICP models"; return PCM_ERR_UNSUPPORTED; }
-  std::vector<double>& u = c->user_cov[target ? 1 : 0];
+  if (target && c->tg.shared()) return refuse_shared(c, "pcm_set_covariances(target)");
+  std::vector<double>& u = target ? c->tg->user_cov : c->user_cov_src;
   u.resize(n * 6);
   const int ld = elems == 9 ? 3 : 4;
   for (size_t i = 0; i < n; i++) {
@@ -530,7 +620,7 @@ int pcm_set_covariances(pcm_ctx* c, int target, const double* covs, size_t n, in
     double* o = &u[i * 6];
     o[0] = m[0]; o[1] = m[1]; o[2] = m[2]; o[3] = m[ld + 1]; o[4] = m[ld + 2]; o[5] = m[2 * ld + 2];
   }
-  if (target) c->tgt_cov_valid = false; else c->src_cov_valid = false;
+  if (target) c->tg->tgt_cov_valid = false; else c->src_cov_valid = false;
   return PCM_OK;
 }
 
@@ -571,8 +661,8 @@ int pcm_get_covariances(pcm_ctx* c, int target, double* out, size_t capacity_poi
   if (!is_gicp(c->cfg.model)) { c->err = "covariances exist for the GICP / VGICP models only"; return PCM_ERR_UNSUPPORTED; }
   rc = prepare(c);
   if (rc != PCM_OK) return rc;
-  const TargetMap& m = target ? c->map : c->srcmap;
-  const double* d_cov = target ? c->tgt_cov : c->src_cov;
+  const TargetMap& m = target ? c->tg->map : c->srcmap;
+  const double* d_cov = target ? c->tg->tgt_cov : c->src_cov;
   if (n) *n = m.num_points;
   if (!out) return PCM_OK;
   if (capacity_points < m.num_points) { c->err = "output buffer too small"; return PCM_ERR_INVALID_ARGUMENT; }
@@ -917,7 +1007,7 @@ int pcm_lio_update_trace(pcm_ctx* c, int call, pcm_lio_filter_state* x, int32_t*
 namespace {
 // grow the target point log to hold `need` points (keeps the content)
 int reserve_target(pcm_ctx* c, size_t need) {
-  Cloud& t = c->tgt;
+  Cloud& t = c->tg->tgt;
   if (need <= t.own.cap && !t.borrowed) return PCM_OK;
   const size_t cap = std::max(need, t.own.cap + t.own.cap / 2 + 1024);
   if (t.borrowed) {   // the caller's buffer is copied into an owned log on the first insert (own is empty until then)
@@ -940,43 +1030,45 @@ int pcm_target_insert(pcm_ctx* c, const void* points, size_t n, size_t stride_by
   CHECK_CTX(c);
   if (!points && n) { c->err = "null point buffer"; return PCM_ERR_INVALID_ARGUMENT; }
   if (stride_bytes < 3 * sizeof(float) || (stride_bytes % sizeof(float)) != 0) { c->err = "stride must be a multiple of 4 and >= 12 bytes"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (c->tg.shared()) return refuse_shared(c, "pcm_target_insert");
   if (n == 0) return PCM_OK;
   PCM_HIPCK(c, hipSetDevice(c->device));
-  int rc = reserve_target(c, c->tgt.n + n);
+  int rc = reserve_target(c, c->tg->tgt.n + n);
   if (rc != PCM_OK) return rc;
-  rc = load_points_to_device(c->stream, points, n, stride_bytes, memory, c->next_seq, c->tgt.d_pts + c->tgt.n, &c->err);
+  rc = load_points_to_device(c->stream, points, n, stride_bytes, memory, c->tg->next_seq, c->tg->tgt.d_pts + c->tg->tgt.n, &c->err);
   if (rc != PCM_OK) return rc;
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));
-  c->tgt.n += n;
-  c->next_seq += (uint32_t)n;
-  c->tgt.tag = 0;
-  c->map.valid = false;
-  c->tgt_dynamic = true;
+  c->tg->tgt.n += n;
+  c->tg->next_seq += (uint32_t)n;
+  c->tg->tgt.tag = 0;
+  c->tg->map.valid = false;
+  c->tg->tgt_dynamic = true;
   return PCM_OK;
 }
 
 int pcm_map_incremental(pcm_ctx* c, const pcm_lio_state* s, float filter_size_map, int ekf_inited, size_t* num_added) {
   CHECK_CTX(c);
   if (!s) return PCM_ERR_INVALID_ARGUMENT;
+  if (c->tg.shared()) return refuse_shared(c, "pcm_map_incremental");
   if (c->src.n == 0) { c->err = "pcm_map_incremental without a source scan"; return PCM_ERR_NO_INPUT; }
   PCM_HIPCK(c, hipSetDevice(c->device));
   const uint32_t n = (uint32_t)c->src.n;
-  int rc = reserve_target(c, c->tgt.n + n);
+  int rc = reserve_target(c, c->tg->tgt.n + n);
   if (rc != PCM_OK) return rc;
-  const bool have_nn = c->lio_planes_valid && c->nn != nullptr && c->map.valid && ekf_inited;
+  const bool have_nn = c->lio_planes_valid && c->nn != nullptr && c->tg->map.valid && ekf_inited;
   LioStateD L;
   for (int a = 0; a < 4; a++) { L.rot[a] = s->rot[a]; L.off_R[a] = s->off_R[a]; }
   for (int a = 0; a < 3; a++) { L.pos[a] = s->pos[a]; L.off_T[a] = s->off_T[a]; }
   const bool reordered = c->cfg.sort_source && c->src_sorted;
   const float4* scan = reordered ? c->src_order : c->src.d_pts;
   uint32_t added = 0;
-  rc = map_incremental_device(c->stream, scan, reordered, n, L, filter_size_map, have_nn ? c->nn : nullptr, have_nn ? c->map.pts : nullptr, c->next_seq,
-                              c->tgt.d_pts + c->tgt.n, &added, &c->err);
+  rc = map_incremental_device(c->stream, scan, reordered, n, L, filter_size_map, have_nn ? c->nn : nullptr, have_nn ? c->tg->map.pts : nullptr, c->tg->next_seq,
+                              c->tg->tgt.d_pts + c->tg->tgt.n, &added, &c->err);
   if (rc != PCM_OK) return rc;
-  c->tgt.n += added;
-  c->next_seq += added;
-  c->tgt.tag = 0;
-  if (added) { c->map.valid = false; c->tgt_dynamic = true; }
+  c->tg->tgt.n += added;
+  c->tg->next_seq += added;
+  c->tg->tgt.tag = 0;
+  if (added) { c->tg->map.valid = false; c->tg->tgt_dynamic = true; }
   if (num_added) *num_added = added;
   return PCM_OK;
 }
@@ -1042,7 +1134,7 @@ int pcm_lio_frame_begin(pcm_ctx* c, const void* custom_points, size_t n, int mem
   c->lio_planes_valid = false;
   c->srcmap.valid = false;
   c->src_cov_valid = false;
-  c->user_cov[0].clear();
+  c->user_cov_src.clear();
   *n_scan = n_ds;
   return PCM_OK;
 }
@@ -1111,12 +1203,16 @@ int pcm_lio_frame_begin_cloud(pcm_ctx* c, const void* points, size_t n, int memo
   c->lio_planes_valid = false;
   c->srcmap.valid = false;
   c->src_cov_valid = false;
-  c->user_cov[0].clear();
+  c->user_cov_src.clear();
   *n_scan = n_ds;
   return PCM_OK;
 }
 
-int pcm_lio_frame_end(pcm_ctx* c, const pcm_lio_state* s, float filter_size_map, int ekf_inited, size_t* num_added) { return pcm_map_incremental(c, s, filter_size_map, ekf_inited, num_added); }
+int pcm_lio_frame_end(pcm_ctx* c, const pcm_lio_state* s, float filter_size_map, int ekf_inited, size_t* num_added) {
+  CHECK_CTX(c);
+  if (c->tg.shared()) return refuse_shared(c, "pcm_lio_frame_end");
+  return pcm_map_incremental(c, s, filter_size_map, ekf_inited, num_added);
+}
 
 int pcm_get_source(pcm_ctx* c, float* out_xyz, size_t capacity_points, size_t* n) {
   CHECK_CTX(c);
@@ -1134,16 +1230,16 @@ int pcm_get_source(pcm_ctx* c, float* out_xyz, size_t capacity_points, size_t* n
 int pcm_get_target(pcm_ctx* c, float* out_xyz, size_t capacity_points, size_t* n) {
   CHECK_CTX(c);
   if (!n) return PCM_ERR_INVALID_ARGUMENT;
-  if (c->tgt.n && c->cfg.map_capacity > 0 && !c->map.valid && c->src.n) {
+  if (c->tg->tgt.n && c->cfg.map_capacity > 0 && !c->tg->map.valid && c->src.n) {
     int rc = prepare(c);   // apply a pending LRU eviction so the log is the current map
     if (rc != PCM_OK) return rc;
   }
-  *n = c->tgt.n;
+  *n = c->tg->tgt.n;
   if (!out_xyz) return PCM_OK;
-  if (capacity_points < c->tgt.n) { c->err = "pcm_get_target: buffer too small"; return PCM_ERR_INVALID_ARGUMENT; }
-  std::vector<float4> tmp(c->tgt.n);
-  PCM_HIPCK(c, hipMemcpy(tmp.data(), c->tgt.d_pts, sizeof(float4) * c->tgt.n, hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < c->tgt.n; i++) { out_xyz[3 * i] = tmp[i].x; out_xyz[3 * i + 1] = tmp[i].y; out_xyz[3 * i + 2] = tmp[i].z; }
+  if (capacity_points < c->tg->tgt.n) { c->err = "pcm_get_target: buffer too small"; return PCM_ERR_INVALID_ARGUMENT; }
+  std::vector<float4> tmp(c->tg->tgt.n);
+  PCM_HIPCK(c, hipMemcpy(tmp.data(), c->tg->tgt.d_pts, sizeof(float4) * c->tg->tgt.n, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < c->tg->tgt.n; i++) { out_xyz[3 * i] = tmp[i].x; out_xyz[3 * i + 1] = tmp[i].y; out_xyz[3 * i + 2] = tmp[i].z; }
   return PCM_OK;
 }
 
@@ -1156,7 +1252,7 @@ int pcm_get_planes(pcm_ctx* c, float* out, size_t n) {
 
 int pcm_get_neighbour_lists(pcm_ctx* c, uint64_t info[2], float* centres, uint32_t* starts, float* entries) {
   CHECK_CTX(c);
-  const pcm::NeighbourLists& nl = c->nlists;
+  const pcm::NeighbourLists& nl = c->tg->nlists;
   if (!info || !nl.valid || nl.kind != 0) { c->err = "pcm_get_neighbour_lists: the context holds no candidate lists of points (P2PLANE, static target, lists built)"; return PCM_ERR_INVALID_ARGUMENT; }
   info[0] = nl.num_lists;
   info[1] = nl.num_candidates;

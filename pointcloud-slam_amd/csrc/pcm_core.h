@@ -18,6 +18,10 @@ size_t num_elements(const pcm_ctx* c);   // source elements of a pass: points, o
 
 // lazy (re)build of everything the residual kernel needs
 int prepare(pcm_ctx* c);
+// sharing a target (pcm_share_target): the first configuration field that decides how a target is built and differs, or null;
+// the eager build of everything prepare() derives from the target alone, on c's stream
+const char* target_config_difference(const pcm_config& a, const pcm_config& b);
+int build_target_for_sharing(pcm_ctx* c);
 // the lists the context's residual kernel reads (kind 0 or 2), or an empty view: they exist and the policy still wants them
 TargetView lists_view_for(const pcm_ctx* c);
 // pclomp NDT: the neighbour-leaf lists of the context's grid, or an empty view (the cells are then looked up one by one)

@@ -13,6 +13,7 @@
 #include "lsq_step.h"
 #include "pcm_device.h"
 #include "sub_state.h"
+#include "target_share.h"
 
 namespace pcm {
 
@@ -176,6 +177,31 @@ void launch_pclndt_pass(hipStream_t stream, const TargetMap& map, const PclLeaf*
 void launch_init_states(hipStream_t stream, PairState* d_states, const float* d_guesses, int npairs, int max_iterations, int window, unsigned int* d_queue);
 void launch_pack_results(hipStream_t stream, const PairState* d_states, pcm_result* d_results, int npairs);
 
+// The target of a registration context and everything built from it.  A context holds it through a counted reference
+// (pcm_ctx::tg, target_share.h); contexts that pcm_share_target joined hold the same one, which nothing changes while more than
+// one of them does.  Per-context scratch (correspondences, planes, the source and its index, workspaces) stays in pcm_ctx.
+struct TargetState {
+  Cloud tgt;
+  TargetMap map;
+  bool tgt_dynamic = false;       // the target grew since pcm_set_target (pcm_target_insert / pcm_map_incremental)
+  bool nlists_failed = false;     // the lists of this map could not be built (memory): not tried again
+  int map_uses = 0;               // prepare() calls since the map was (re)built; stands still while the target is shared
+  NeighbourLists nlists;          // candidate lists of `map` (static targets; NeighbourLists::kind)
+  // GICP / VGICP: per-point covariances in MAP order, voxel distributions
+  DevBuf<double> tgt_cov{"tgt_cov"};   // 6 doubles per point
+  bool tgt_cov_valid = false;
+  int cov_k = 0, cov_reg = -1, cov_vmode = -1;   // what the cached covariances (these and every holder's src_cov) were computed with
+  float cov_rbf_w = -1.f, cov_rbf_d = -1.f;   // RBF parameters the cached covariances were computed with (-1: kNN covariances)
+  DevBuf<VgVoxel> vvox{"vvox"};
+  DevBuf<VgcVoxel> cvox{"cvox"};   // VGICP_CUDA
+  // pclomp NDT: leaf payload of the map
+  DevBuf<PclLeaf> pleaf{"pleaf"};
+  DevBuf<PclLeafF> pleaf_f{"pleaf_f"};   // the float passes' 64-byte view of the same leaves
+  bool pleaf_valid = false;
+  std::vector<double> user_cov;   // target covariances handed in by the caller (6 per point, input order); empty = compute
+  uint32_t next_seq = 0;          // next insertion sequence number of the target point log
+};
+
 }  // namespace pcm
 
 // A device array of the context is a DevBuf member (pinned host memory: a PinnedBuf): it frees itself when pcm_destroy deletes the
@@ -190,27 +216,16 @@ struct pcm_ctx {
   pcm_config cfg{};
   hipStream_t stream = nullptr;
   bool own_stream = false;
-  pcm::Cloud src, tgt;
-  pcm::TargetMap map;
+  pcm::Cloud src;
+  pcm::SharedTarget<pcm::TargetState> tg;   // the target and what is built from it (TargetState); made by pcm_create, shared by pcm_share_target
   pcm::TargetMap srcmap;          // NDT D2D: the source's own voxel distributions
-  bool tgt_dynamic = false;       // the target grew since pcm_set_target (pcm_target_insert / pcm_map_incremental)
-  bool nlists_failed = false;     // the lists of this map could not be built (memory): not tried again
-  int map_uses = 0;               // prepare() calls since the map was (re)built
-  pcm::NeighbourLists nlists;     // P2PLANE, PCM_FLAG_NEIGHBOUR_LISTS: candidate lists of `map` (static targets)
   pcm::TargetMap covfine;         // GICP: the cloud whose covariances are being computed, on a grid 8x finer (kNN index of dense neighbourhoods only)
   pcm::DevBuf<int32_t> corr{"corr"};   // NDT: matched voxel per (element, offset) of the last linearize
-  // GICP / VGICP: per-point covariances in MAP order (the source elements are srcmap.pts), voxel distributions, Mahalanobis cache
-  pcm::DevBuf<double> src_cov{"src_cov"}, tgt_cov{"tgt_cov"};   // 6 doubles per point
-  bool src_cov_valid = false, tgt_cov_valid = false;
-  int cov_k = 0, cov_reg = -1, cov_vmode = -1;
-  float cov_rbf_w = -1.f, cov_rbf_d = -1.f;   // RBF parameters the cached covariances were computed with (-1: kNN covariances)
-  pcm::DevBuf<pcm::VgVoxel> vvox{"vvox"};
-  pcm::DevBuf<pcm::VgcVoxel> cvox{"cvox"};   // VGICP_CUDA
+  // GICP / VGICP: per-point covariances of the source in the order of srcmap.pts (6 doubles per point), Mahalanobis cache
+  pcm::DevBuf<double> src_cov{"src_cov"};
+  bool src_cov_valid = false;   // computed with the parameters tg->cov_* name
   pcm::DevBuf<double> maha{"maha"};          // 6 doubles per correspondence
-  // pclomp NDT: leaf payload of the map, partial rows, result row (device + pinned host)
-  pcm::DevBuf<pcm::PclLeaf> pleaf{"pleaf"};
-  pcm::DevBuf<pcm::PclLeafF> pleaf_f{"pleaf_f"};   // the float passes' 64-byte view of the same leaves
-  bool pleaf_valid = false;
+  // pclomp NDT: partial rows, result row (device + pinned host)
   pcm::DevBuf<double> ndt_partials{"ndt_partials"};
   pcm::DevBuf<double> ndt_out{"ndt_out"};
   pcm::PinnedBuf<double> ndt_out_host{"ndt_out_host"};
@@ -222,7 +237,6 @@ struct pcm_ctx {
   pcm_stats stats{};
   uint64_t phase_cycles[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // diagnostic (profiling bit2)
   pcm::DevBuf<uint32_t> nn{"nn"};  // LIO: the <= 5 neighbours (indices into map.pts) of every scan point from the last matching call
-  uint32_t next_seq = 0;           // next insertion sequence number of the target point log
   bool lio_planes_valid = false;   // planes of the last pcm_obs_model(rematch=1) belong to the current scan
   pcm::DevBuf<float2> lio_aux{"lio_aux"};   // PCM_FLAG_LIO_REFERENCE_SEMANTICS: residuals_ / point_selected_surf_ of LaserMapping, in the caller's scan order;
   size_t lio_aux_n = 0;                     // they outlive the scan (std::vector::resize semantics, laser_mapping.cc:337-338)
@@ -236,7 +250,7 @@ struct pcm_ctx {
   pcm::DevBuf<char> pre_arena{"pre_arena"};   // grow-only device scratch of the pre-processing operators
   pcm::DevBuf<char> bfgs{"bfgs"};             // GICP-BFGS functor: packed correspondence records + partial sums (gicp_bfgs.hip)
   size_t bfgs_m = 0;
-  std::vector<double> user_cov[2];   // [0] source, [1] target: covariances handed in by the caller (6 per point, input order); empty = compute
+  std::vector<double> user_cov_src;   // source covariances handed in by the caller (6 per point, input order); empty = compute
   pcm::DevBuf<int32_t> bfgs_idx{"bfgs_idx"};   // source indices of the packed pairs in the first half, target indices in the second (device-side correspondence step)
   pcm::PinnedBuf<double> bfgs_host{"bfgs_host"};   // pinned, device-visible: the 14 sums land here without a copy command
   pcm::SubState loam;      // PCM_MODEL_LOAM: maps, features, device state and the stores (loam_api.hip)

@@ -63,30 +63,38 @@ int wanted_list_kind(const pcm_ctx* c) {
   int kind = -1;
   if (g.model == PCM_MODEL_P2PLANE) {
     const int other_kernel = PCM_FLAG_REFERENCE_KNN_ORDER | PCM_FLAG_COUNTED_SEARCH | PCM_FLAG_NO_LDS_STAGING | PCM_FLAG_FUSED_STEP;
-    if (!c->tgt_dynamic && !(g.flags & other_kernel)) kind = 0;
+    if (!c->tg->tgt_dynamic && !(g.flags & other_kernel)) kind = 0;
   } else if (g.model == PCM_MODEL_NDT_OMP) {
     kind = 1;
   } else if (radius_model(g.model)) {
-    if (!(g.neighbor_search_radius > 0.f) && c->map.coord_mode == COORD_FLOOR_HALF) kind = 2;
+    if (!(g.neighbor_search_radius > 0.f) && c->tg->map.coord_mode == COORD_FLOOR_HALF) kind = 2;
   }
-  if (kind < 0 || c->nlists_failed || (g.flags & PCM_FLAG_NO_NEIGHBOUR_LISTS)) return -1;
-  return ((g.flags & PCM_FLAG_NEIGHBOUR_LISTS) != 0 || c->map_uses >= 2) ? kind : -1;
+  if (kind < 0 || c->tg->nlists_failed || (g.flags & PCM_FLAG_NO_NEIGHBOUR_LISTS)) return -1;
+  if (c->tg.shared()) return c->tg->nlists.valid ? kind : -1;   // nothing is built for a shared target: the lists pcm_share_target left, or none
+  return ((g.flags & PCM_FLAG_NEIGHBOUR_LISTS) != 0 || c->tg->map_uses >= 2) ? kind : -1;
 }
 
-bool has_lists_of_kind(const pcm_ctx* c, int kind) { return c->nlists.valid && c->nlists.kind == kind && c->nlists.num_neighbors == c->cfg.num_neighbors; }
+bool has_lists_of_kind(const pcm_ctx* c, int kind) { return c->tg->nlists.valid && c->tg->nlists.kind == kind && c->tg->nlists.num_neighbors == c->cfg.num_neighbors; }
 
 // builds the lists of `kind` (wanted_list_kind; -1: nothing to do) unless the context holds them, once per (static) target
 int ensure_neighbour_lists(pcm_ctx* c, int kind) {
-  if (kind < 0 || has_lists_of_kind(c, kind)) return PCM_OK;
-  const int rc = build_neighbour_lists(c->stream, c->map, c->cfg.num_neighbors, &c->nlists, &c->err, kind == 1 ? c->pleaf.p : nullptr, kind == 2);
+  if (kind < 0 || has_lists_of_kind(c, kind) || c->tg.shared()) return PCM_OK;
+  const int rc = build_neighbour_lists(c->stream, c->tg->map, c->cfg.num_neighbors, &c->tg->nlists, &c->err, kind == 1 ? c->tg->pleaf.p : nullptr, kind == 2);
   if (rc != PCM_OK) {
     if (c->cfg.flags & PCM_FLAG_NEIGHBOUR_LISTS) return rc;   // asked for explicitly
-    c->nlists_failed = true;                                   // e.g. no memory for them: the kernel without lists serves this target
-    c->nlists.release();
+    c->tg->nlists_failed = true;                                   // e.g. no memory for them: the kernel without lists serves this target
+    c->tg->nlists.release();
     c->err.clear();
     (void)hipGetLastError();
   }
   return PCM_OK;
+}
+
+// A shared target is complete when pcm_share_target returns and pcm_set_config refuses what would rebuild it, so no step below
+// finds anything to build for one.  Should one do, it says so instead of writing to memory other contexts are reading.
+int shared_target_stale(pcm_ctx* c) {
+  c->err = "the shared target was not built for this configuration (library bug: pcm_share_target / pcm_set_config let it through)";
+  return PCM_ERR_INTERNAL;
 }
 
 // ---- the steps of prepare() --------------------------------------------------------------------------------------------------------
@@ -95,39 +103,50 @@ int ensure_target_map(pcm_ctx* c) {
   const int mode = coord_mode_for(c->cfg.model);
   const bool gauss = is_ndt(c->cfg.model);
   const bool gicp = is_gicp(c->cfg.model);
-  if (!c->map.valid || c->map.res != c->cfg.voxel_resolution || c->map.coord_mode != mode || (gauss && !c->map.gvox) || (gicp && !c->map.order)) {
-    uint32_t n_log = (uint32_t)c->tgt.n;
+  if (c->tg.shared()) {   // built by pcm_share_target for this very configuration (target_config_difference), and read-only since
+    if (!c->tg->map.valid || c->tg->map.res != c->cfg.voxel_resolution || c->tg->map.coord_mode != mode) return shared_target_stale(c);
+    return PCM_OK;
+  }
+  if (!c->tg->map.valid || c->tg->map.res != c->cfg.voxel_resolution || c->tg->map.coord_mode != mode || (gauss && !c->tg->map.gvox) || (gicp && !c->tg->map.order)) {
+    uint32_t n_log = (uint32_t)c->tg->tgt.n;
     // the sliding-map capacity belongs to the iVox of the P2PLANE / LIO path; fast_gicp keeps every target point
     const uint32_t capacity = c->cfg.model == PCM_MODEL_P2PLANE ? (uint32_t)std::max(0, c->cfg.map_capacity) : 0u;
     // a map whose log only grew since its last build (pcm_target_insert / pcm_map_incremental) is updated: the new points are merged
     // into the sorted index it kept (voxel_hash.hip); anything else is built from scratch
     uint32_t hazards = 0;
-    int rc = build_target_map(c->stream, c->tgt.d_pts, &n_log, c->cfg.voxel_resolution, mode, gauss, capacity, &c->map, &c->err, gicp, c->map.index_n, &hazards);
+    int rc = build_target_map(c->stream, c->tg->tgt.d_pts, &n_log, c->cfg.voxel_resolution, mode, gauss, capacity, &c->tg->map, &c->err, gicp, c->tg->map.index_n, &hazards);
     c->stats.lru_batch_hazards += hazards;
-    c->tgt.n = n_log;   // LRU eviction compacts the point log
+    c->tg->tgt.n = n_log;   // LRU eviction compacts the point log
     if (rc != PCM_OK) return rc;
-    c->stats.target_voxels = c->map.num_voxels;
-    c->stats.target_slots = c->map.cap;
-    c->tgt_cov_valid = false;
-    c->pleaf_valid = false;
-    c->nlists.valid = false;
-    c->nlists_failed = false;
-    c->map_uses = 0;
+    c->stats.target_voxels = c->tg->map.num_voxels;
+    c->stats.target_slots = c->tg->map.cap;
+    c->tg->tgt_cov_valid = false;
+    c->tg->pleaf_valid = false;
+    c->tg->nlists.valid = false;
+    c->tg->nlists_failed = false;
+    c->tg->map_uses = 0;
   }
-  if (c->map_uses < 1000000) c->map_uses++;
+  if (c->tg->map_uses < 1000000) c->tg->map_uses++;
   return PCM_OK;
 }
 
 // pclomp NDT: VoxelGridCovariance leaves (NormalDistributionsTransform::init, ndt_omp.h:300-306), their lists, the pass buffers
+int build_leaves(pcm_ctx* c) {
+  int rc = c->tg->pleaf.reserve(c, c->tg->map.num_voxels, c->tg->map.num_voxels);
+  if (rc == PCM_OK) rc = c->tg->pleaf_f.reserve(c, c->tg->map.num_voxels, c->tg->map.num_voxels);
+  if (rc != PCM_OK) return rc;
+  rc = build_pclndt_leaves(c->stream, c->tg->map, c->tg->pleaf, c->tg->pleaf_f, &c->err);
+  if (rc != PCM_OK) return rc;
+  c->tg->pleaf_valid = true;
+  c->tg->nlists.valid = false;
+  return PCM_OK;
+}
+
 int prepare_pclndt(pcm_ctx* c) {
-  if (!c->pleaf_valid) {
-    int rc = c->pleaf.reserve(c, c->map.num_voxels, c->map.num_voxels);
-    if (rc == PCM_OK) rc = c->pleaf_f.reserve(c, c->map.num_voxels, c->map.num_voxels);
+  if (c->tg.shared() && !c->tg->pleaf_valid) return shared_target_stale(c);
+  if (!c->tg->pleaf_valid) {
+    const int rc = build_leaves(c);
     if (rc != PCM_OK) return rc;
-    rc = build_pclndt_leaves(c->stream, c->map, c->pleaf, c->pleaf_f, &c->err);
-    if (rc != PCM_OK) return rc;
-    c->pleaf_valid = true;
-    c->nlists.valid = false;
   }
   // neighbour-leaf lists of the grid (neighbour_lists.hip), after the leaves they are made of
   int rc = ensure_neighbour_lists(c, wanted_list_kind(c));
@@ -140,17 +159,18 @@ int prepare_pclndt(pcm_ctx* c) {
   return rc;
 }
 
-// Covariances of one cloud of the GICP family, in the order of its map: side 1 = target (c->map), 0 = source (c->srcmap).
+// Covariances of one cloud of the GICP family, in the order of its map: side 1 = target (c->tg->map), 0 = source (c->srcmap).
 // `if (target_covs_.size() != target_->size()) calculate_covariances(...)`  fast_gicp_impl.hpp:104-109: covariances the caller
 // handed in for every point are uploaded, else RBF or kNN.  The sides differ in three places, each a visible branch below.
 int ensure_covariances(pcm_ctx* c, int side) {
   const bool target = side == 1;
-  bool& valid = target ? c->tgt_cov_valid : c->src_cov_valid;
+  bool& valid = target ? c->tg->tgt_cov_valid : c->src_cov_valid;
   if (valid) return PCM_OK;
-  const TargetMap& map = target ? c->map : c->srcmap;
-  const Cloud& cloud = target ? c->tgt : c->src;
-  DevBuf<double>& cov = target ? c->tgt_cov : c->src_cov;
-  const std::vector<double>& user = c->user_cov[side];
+  if (target && c->tg.shared()) return shared_target_stale(c);
+  const TargetMap& map = target ? c->tg->map : c->srcmap;
+  const Cloud& cloud = target ? c->tg->tgt : c->src;
+  DevBuf<double>& cov = target ? c->tg->tgt_cov : c->src_cov;
+  const std::vector<double>& user = target ? c->tg->user_cov : c->user_cov_src;
   const bool cuda_core = c->cfg.model == PCM_MODEL_VGICP_CUDA;
   int rc = cov.reserve(c, 6 * (size_t)map.num_points, 6 * (size_t)map.num_points);
   if (rc != PCM_OK) return rc;
@@ -173,33 +193,41 @@ int ensure_covariances(pcm_ctx* c, int side) {
   if (rc != PCM_OK) return rc;
   if (target) {   // side difference 2: the voxel distributions of the target are made of its covariances
     if (cuda_core) {
-      rc = c->cvox.reserve(c, c->map.num_voxels, c->map.num_voxels);
+      rc = c->tg->cvox.reserve(c, c->tg->map.num_voxels, c->tg->map.num_voxels);
       if (rc != PCM_OK) return rc;
-      rc = build_vgc_voxels(c->stream, c->map, c->tgt_cov, c->cvox, &c->err);
+      rc = build_vgc_voxels(c->stream, c->tg->map, c->tg->tgt_cov, c->tg->cvox, &c->err);
       if (rc != PCM_OK) return rc;
     }
     if (c->cfg.model == PCM_MODEL_VGICP) {
-      rc = c->vvox.reserve(c, c->map.num_voxels, c->map.num_voxels);
+      rc = c->tg->vvox.reserve(c, c->tg->map.num_voxels, c->tg->map.num_voxels);
       if (rc != PCM_OK) return rc;
-      rc = build_vgicp_voxels(c->stream, c->map, c->tgt_cov, c->cfg.voxel_mode, c->vvox, &c->err);
+      rc = build_vgicp_voxels(c->stream, c->tg->map, c->tg->tgt_cov, c->cfg.voxel_mode, c->tg->vvox, &c->err);
       if (rc != PCM_OK) return rc;
     }
   }
-  valid = true;   // (side difference 3 is user_cov[side] above)
+  valid = true;   // (side difference 3 is the user covariances above)
+  return PCM_OK;
+}
+
+// the parameters the cached covariances of both clouds were computed with follow the configuration: a change drops the caches
+int sync_covariance_parameters(pcm_ctx* c) {
+  const bool rbf = c->cfg.model == PCM_MODEL_VGICP_CUDA && c->cfg.covariance_method == PCM_COV_RBF_KERNEL;
+  const float rbf_w = rbf ? c->cfg.rbf_kernel_width : -1.f, rbf_d = rbf ? c->cfg.rbf_max_dist : -1.f;
+  if (c->tg->cov_k != c->cfg.k_correspondences || c->tg->cov_reg != c->cfg.regularization + 100 * c->cfg.model || c->tg->cov_vmode != c->cfg.voxel_mode || c->tg->cov_rbf_w != rbf_w ||
+      c->tg->cov_rbf_d != rbf_d) {
+    if (c->tg.shared()) return shared_target_stale(c);
+    c->src_cov_valid = false; c->tg->tgt_cov_valid = false;
+    c->tg->cov_k = c->cfg.k_correspondences; c->tg->cov_reg = c->cfg.regularization + 100 * c->cfg.model; c->tg->cov_vmode = c->cfg.voxel_mode;
+    c->tg->cov_rbf_w = rbf_w; c->tg->cov_rbf_d = rbf_d;
+  }
   return PCM_OK;
 }
 
 // FastGICP::computeTransformation: the scan's kNN index, covariances of both clouds, lazily   fast_gicp_impl.hpp:102-110
 int prepare_gicp(pcm_ctx* c) {
   const int mode = coord_mode_for(c->cfg.model);
-  const bool rbf = c->cfg.model == PCM_MODEL_VGICP_CUDA && c->cfg.covariance_method == PCM_COV_RBF_KERNEL;
-  const float rbf_w = rbf ? c->cfg.rbf_kernel_width : -1.f, rbf_d = rbf ? c->cfg.rbf_max_dist : -1.f;
-  if (c->cov_k != c->cfg.k_correspondences || c->cov_reg != c->cfg.regularization + 100 * c->cfg.model || c->cov_vmode != c->cfg.voxel_mode || c->cov_rbf_w != rbf_w ||
-      c->cov_rbf_d != rbf_d) {
-    c->src_cov_valid = false; c->tgt_cov_valid = false;
-    c->cov_k = c->cfg.k_correspondences; c->cov_reg = c->cfg.regularization + 100 * c->cfg.model; c->cov_vmode = c->cfg.voxel_mode;
-    c->cov_rbf_w = rbf_w; c->cov_rbf_d = rbf_d;
-  }
+  int rc = sync_covariance_parameters(c);
+  if (rc != PCM_OK) return rc;
   // the scan's own grid is only the index of its kNN search: a finer cell keeps the candidate lists short where a
   // LiDAR scan is dense (near the sensor one 0.5 m voxel holds thousands of points)
   // (measured on Livox-shaped 100 k-point scans: 0.5 m cells are the optimum; 1.0 m costs 25 %, 0.25 m 15-40 %)
@@ -207,11 +235,11 @@ int prepare_gicp(pcm_ctx* c) {
   if (!c->srcmap.valid || c->srcmap.res != src_res || c->srcmap.coord_mode != mode) {
     uint32_t n_src = (uint32_t)c->src.n;
     // sub-voxel order: 64 consecutive points of the brick-major scan are one patch (k_covariances; k_gicp reads it point by point)
-    int rc = build_target_map(c->stream, c->src.d_pts, &n_src, src_res, mode, false, 0u, &c->srcmap, &c->err, true, 0u, nullptr, cov_subsort_enabled());
+    rc = build_target_map(c->stream, c->src.d_pts, &n_src, src_res, mode, false, 0u, &c->srcmap, &c->err, true, 0u, nullptr, cov_subsort_enabled());
     if (rc != PCM_OK) return rc;
     c->src_cov_valid = false;
   }
-  int rc = ensure_covariances(c, 1);
+  rc = ensure_covariances(c, 1);
   if (rc == PCM_OK) rc = ensure_covariances(c, 0);
   if (rc != PCM_OK) return rc;
   const size_t ncorr = c->cfg.model == PCM_MODEL_VGICP_CUDA ? 0 : c->src.n * (size_t)(c->cfg.model == PCM_MODEL_VGICP ? c->cfg.num_neighbors : 1);
@@ -248,18 +276,18 @@ int ensure_pair_buffers(pcm_ctx* c) {
 TargetView lists_view_for(const pcm_ctx* c) {
   const int kind = wanted_list_kind(c);
   const bool on = (kind == 0 || kind == 2) && has_lists_of_kind(c, kind);   // kind 1 is read through ndt_lists_view
-  return on ? view_of_lists(c->nlists) : TargetView{};
+  return on ? view_of_lists(c->tg->nlists) : TargetView{};
 }
 
 // pclomp NDT: the neighbour-leaf lists of the context's grid, or an empty view (the cells are then looked up one by one)
 TargetView ndt_lists_view(const pcm_ctx* c) {
-  const bool on = c->cfg.model == PCM_MODEL_NDT_OMP && c->nlists.valid && c->nlists.kind == 1 && c->nlists.num_neighbors == c->cfg.num_neighbors &&
+  const bool on = c->cfg.model == PCM_MODEL_NDT_OMP && c->tg->nlists.valid && c->tg->nlists.kind == 1 && c->tg->nlists.num_neighbors == c->cfg.num_neighbors &&
                   !(c->cfg.flags & PCM_FLAG_NO_NEIGHBOUR_LISTS);
-  return on ? view_of_lists(c->nlists) : TargetView{};
+  return on ? view_of_lists(c->tg->nlists) : TargetView{};
 }
 
 int prepare(pcm_ctx* c) {
-  if (c->src.n == 0 || c->tgt.n == 0) { c->err = "align before setInputSource/setInputTarget"; return PCM_ERR_NO_INPUT; }
+  if (c->src.n == 0 || c->tg->tgt.n == 0) { c->err = "align before setInputSource/setInputTarget"; return PCM_ERR_NO_INPUT; }
   PCM_HIPCK(c, hipSetDevice(c->device));
   int rc = ensure_target_map(c);
   if (rc != PCM_OK) return rc;
@@ -268,6 +296,64 @@ int prepare(pcm_ctx* c) {
   if (rc == PCM_OK && is_gicp(c->cfg.model)) rc = prepare_gicp(c);
   if (rc == PCM_OK) rc = ensure_d2d_source_map(c);
   if (rc == PCM_OK) rc = ensure_pair_buffers(c);
+  return rc;
+}
+
+// ---- sharing a target --------------------------------------------------------------------------------------------------------
+// The fields of a configuration that decide what the target-side structures hold, i.e. everything the steps of prepare() above
+// compare or pass to a build of TargetState's members:
+//   model                   coord_mode_for, gauss voxels, the kept input order, the kind of lists (ensure_target_map, wanted_list_kind)
+//   voxel_resolution        the map's cell size (ensure_target_map); the pclomp NDT leaves are a function of the map alone
+//   num_neighbors, neighbor_search_radius
+//                           the neighbourhood the lists are built for, and whether kind-2 lists exist (has_lists_of_kind, wanted_list_kind)
+//   flags & kTargetFlags    PCM_FLAG_NEIGHBOUR_LISTS / PCM_FLAG_NO_NEIGHBOUR_LISTS and the kernel flags next to which no lists are made
+//   map_capacity            P2PLANE: the LRU capacity the map was built under (ensure_target_map)
+//   k_correspondences, regularization, voxel_mode, covariance_method, rbf_kernel_width, rbf_max_dist
+//                           GICP family: the covariances and the voxel distributions made of them (prepare_gicp, ensure_covariances)
+// Solver settings (optimizer, iteration limits, epsilons, max_range, plane_threshold, max_corr_dist, the pclomp NDT step size and
+// outlier ratio, sort_source, batch_window) are read per registration and may differ between holders.
+// Returns the name of the first field that differs, or null.
+const char* target_config_difference(const pcm_config& a, const pcm_config& b) {
+  constexpr int kTargetFlags = PCM_FLAG_NEIGHBOUR_LISTS | PCM_FLAG_NO_NEIGHBOUR_LISTS | PCM_FLAG_REFERENCE_KNN_ORDER | PCM_FLAG_COUNTED_SEARCH | PCM_FLAG_NO_LDS_STAGING |
+                               PCM_FLAG_FUSED_STEP;
+  if (a.model != b.model) return "model";
+  if (a.voxel_resolution != b.voxel_resolution) return "voxel_resolution";
+  if (a.num_neighbors != b.num_neighbors) return "num_neighbors";
+  if (a.neighbor_search_radius != b.neighbor_search_radius) return "neighbor_search_radius";
+  if ((a.flags & kTargetFlags) != (b.flags & kTargetFlags)) return "flags";
+  if (a.model == PCM_MODEL_P2PLANE && a.map_capacity != b.map_capacity) return "map_capacity";
+  if (is_gicp(a.model)) {
+    if (a.k_correspondences != b.k_correspondences) return "k_correspondences";
+    if (a.regularization != b.regularization) return "regularization";
+    if (a.voxel_mode != b.voxel_mode) return "voxel_mode";
+    if (a.covariance_method != b.covariance_method) return "covariance_method";
+    if (a.covariance_method == PCM_COV_RBF_KERNEL && a.rbf_kernel_width != b.rbf_kernel_width) return "rbf_kernel_width";
+    if (a.covariance_method == PCM_COV_RBF_KERNEL && a.rbf_max_dist != b.rbf_max_dist) return "rbf_max_dist";
+  }
+  return nullptr;
+}
+
+// Everything prepare() would build lazily from the target alone, now, on c's stream: the map, the lists the model's kernel reads
+// (sharing a target is the repeated use the list policy waits for, so they are made unless the configuration rules them out),
+// the pclomp NDT leaves, the target covariances and voxel distributions of the GICP family.  The caller synchronises the stream.
+int build_target_for_sharing(pcm_ctx* c) {
+  if (c->tg->tgt.n == 0) { c->err = "pcm_share_target: the source context has no target"; return PCM_ERR_INVALID_ARGUMENT; }
+  PCM_HIPCK(c, hipSetDevice(c->device));
+  int rc = ensure_target_map(c);
+  if (rc != PCM_OK) return rc;
+  if (c->tg->map_uses < 2) c->tg->map_uses = 2;
+  if (c->cfg.model == PCM_MODEL_NDT_OMP) {
+    if (!c->tg->pleaf_valid) {
+      rc = build_leaves(c);
+      if (rc != PCM_OK) return rc;
+    }
+    return ensure_neighbour_lists(c, wanted_list_kind(c));
+  }
+  rc = ensure_neighbour_lists(c, wanted_list_kind(c));
+  if (rc == PCM_OK && is_gicp(c->cfg.model)) {
+    rc = sync_covariance_parameters(c);
+    if (rc == PCM_OK) rc = ensure_covariances(c, 1);
+  }
   return rc;
 }
 
@@ -285,23 +371,23 @@ Geom pick_geom(size_t max_n, int npairs, bool ndt) {
 }
 
 void fill_desc(const pcm_ctx* c, PairDesc* d, double* partials) {
-  d->tgt.pts = c->map.pts;
-  d->tgt.vox_start = c->map.vox_start;
-  d->tgt.bricks = c->map.bricks;
-  d->tgt.bmask = c->map.bmask;
-  d->tgt.bpref = c->map.bpref;
-  d->tgt.mask = c->map.cap - 1;
-  d->tgt.num_points = c->map.num_points;
-  d->tgt.inv_res = c->map.inv_res;
-  d->tgt.res = c->map.res;
-  d->tgt.gvox = c->map.gvox;
+  d->tgt.pts = c->tg->map.pts;
+  d->tgt.vox_start = c->tg->map.vox_start;
+  d->tgt.bricks = c->tg->map.bricks;
+  d->tgt.bmask = c->tg->map.bmask;
+  d->tgt.bpref = c->tg->map.bpref;
+  d->tgt.mask = c->tg->map.cap - 1;
+  d->tgt.num_points = c->tg->map.num_points;
+  d->tgt.inv_res = c->tg->map.inv_res;
+  d->tgt.res = c->tg->map.res;
+  d->tgt.gvox = c->tg->map.gvox;
   d->nl = lists_view_for(c);
   d->src.pts = (c->cfg.sort_source && c->src_sorted) ? c->src_order : c->src.d_pts;
   if (is_gicp(c->cfg.model)) d->src.pts = c->srcmap.pts;   // brick-major copy of the scan: its covariances are in that order
   d->src_cov = c->src_cov;
-  d->tgt_cov = c->tgt_cov;
-  d->vvox = c->vvox;
-  d->cvox = c->cvox;
+  d->tgt_cov = c->tg->tgt_cov;
+  d->vvox = c->tg->vvox;
+  d->cvox = c->tg->cvox;
   d->maha = c->maha;
   d->src.gvox = c->srcmap.gvox;
   d->src.num_points = (uint32_t)num_elements(c);

@@ -102,7 +102,10 @@ class Registration:
             if not hasattr(self._cfg, k):
                 raise KeyError(k)
             setattr(self._cfg, k, v)
-        self._check(self._L.pcm_set_config(self._h, C.byref(self._cfg)))
+        rc = self._L.pcm_set_config(self._h, C.byref(self._cfg))
+        if rc != capi.PCM_OK:   # refused (e.g. it would rebuild a shared target): the view follows the object, which is unchanged
+            self._L.pcm_get_config(self._h, C.byref(self._cfg))
+        self._check(rc)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -153,6 +156,23 @@ class Registration:
     def swap_source_and_target(self): self._check(self._L.pcm_swap_source_and_target(self._h))
     def clear_source(self): self._check(self._L.pcm_clear_source(self._h))
     def clear_target(self): self._check(self._L.pcm_clear_target(self._h))
+
+    def share_target(self, other: "Registration"):
+        """Register against the target ``other`` holds from now on (pcm_share_target): the cloud, its voxel map and everything the
+        model derives from them exist once on the device, however many objects hold them -- what the reference's objects get from
+        one PointCloud::ConstPtr.  Both objects are of one model on one device and agree in the settings that decide how a target
+        is built (the error names the first that differs).  While more than one object holds the target nothing may change it
+        (target_insert, map_incremental, lio_frame_end, set_covariances(target=True), swap_source_and_target and such setters raise);
+        set_input_target / clear_target / deleting an object detach that object only."""
+        self._check(self._L.pcm_share_target(self._h, other._h))
+
+    @property
+    def target_share_count(self) -> int:
+        """Objects holding this object's target (1 = not shared)."""
+        n = self._L.pcm_target_share_count(self._h)
+        if n < 0:
+            self._check(n)
+        return n
 
     # -- compute ------------------------------------------------------------
     def align(self, initial_guess=None) -> RegistrationResult:
