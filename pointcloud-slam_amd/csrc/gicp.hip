@@ -21,7 +21,7 @@
 #include "dev_linalg.h"
 
 #include <cstring>
-#include <rocprim/rocprim.hpp>
+#include "dev_scratch.h"
 
 namespace pcm {
 
@@ -912,16 +912,6 @@ __global__ void __launch_bounds__(256) k_gicp(const PairDesc* __restrict__ descs
   }
 }
 
-TargetView view_of(const TargetMap& m) {
-  TargetView v{};
-  v.pts = m.pts; v.vox_start = m.vox_start; v.bricks = m.bricks; v.bmask = m.bmask; v.bpref = m.bpref; v.gvox = m.gvox;
-  v.mask = m.cap - 1; v.num_points = m.num_points; v.inv_res = m.inv_res; v.res = m.res;
-  return v;
-}
-
-}  // namespace
-
-namespace {
 __global__ void k_invert_order(const uint32_t* __restrict__ order, uint32_t n, uint32_t* __restrict__ inv) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) inv[order[i]] = i;
@@ -935,10 +925,11 @@ int compute_covariances(hipStream_t stream, const TargetMap& map, int k, int reg
   const dim3 grid((map.num_points + 63) / 64);   // 64 queries per workgroup
   const dim3 grid256((map.num_points + 255) / 256);
   TargetView tf{};
+  DevScratch sc(stream);
   uint32_t* c_inv = nullptr;
   const uint32_t* f_order = nullptr;
   if (fine && fine->valid && fine->order && map.order && fine->num_points == map.num_points) {
-    if (hipMallocAsync(reinterpret_cast<void**>(&c_inv), sizeof(uint32_t) * (size_t)map.num_points, stream) != hipSuccess) { *err = "hipMallocAsync(c_inv)"; return PCM_ERR_HIP; }
+    if (const int rc = sc.take(&c_inv, map.num_points, err, "inverse map order"); rc != PCM_OK) return rc;
     k_invert_order<<<grid256, 256, 0, stream>>>(map.order, map.num_points, c_inv);
     tf = view_of(*fine);
     f_order = fine->order;
@@ -962,7 +953,6 @@ int compute_covariances(hipStream_t stream, const TargetMap& map, int k, int reg
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_cov_stats), z, sizeof(z));
   }
 #endif
-  if (c_inv) (void)hipFreeAsync(c_inv, stream);
   if (e != hipSuccess) { *err = std::string("k_covariances: ") + hipGetErrorString(e); return PCM_ERR_HIP; }
   return PCM_OK;
 }
@@ -1078,13 +1068,13 @@ int compute_covariances_rbf(hipStream_t stream, const TargetMap& map, const floa
                             std::string* err) {
   if (!(kernel_width > 0.0) || !(max_dist > 0.0)) { *err = "rbf_kernel_width and rbf_max_dist must be > 0"; return PCM_ERR_INVALID_ARGUMENT; }
   const uint32_t nblocks = (n + kRbfBlock - 1) / kRbfBlock;
+  DevScratch sc(stream);
   float* bounds = nullptr;
-  if (hipMallocAsync(reinterpret_cast<void**>(&bounds), sizeof(float) * 6 * nblocks, stream) != hipSuccess) { *err = "hipMallocAsync(rbf block bounds)"; return PCM_ERR_HIP; }
+  if (const int rc = sc.take(&bounds, 6 * (size_t)nblocks, err, "rbf block bounds"); rc != PCM_OK) return rc;
   k_rbf_block_bounds<<<nblocks, 64, 0, stream>>>(d_input_order, n, bounds);
   // thrust::device_vector<float> constants: the doubles are narrowed once  :118-121
   k_covariances_rbf<<<(map.num_points + 255) / 256, 256, 0, stream>>>(map.pts, map.num_points, d_input_order, n, bounds, nblocks, (float)kernel_width, (float)max_dist, regularization, d_out);
   const hipError_t e = hipGetLastError();
-  (void)hipFreeAsync(bounds, stream);
   if (e != hipSuccess) { *err = std::string("k_covariances_rbf: ") + hipGetErrorString(e); return PCM_ERR_HIP; }
   return PCM_OK;
 }
@@ -1188,12 +1178,12 @@ __global__ void __launch_bounds__(256) k_scatter_cov(const uint32_t* __restrict_
 int upload_covariances(hipStream_t stream, const TargetMap& map, const double* h_cov6, double* d_cov, std::string* err) {
   const uint32_t n = map.num_points;
   if (n == 0) return PCM_OK;
+  DevScratch sc(stream);
   double* tmp = nullptr;
-  hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&tmp), sizeof(double) * 6 * (size_t)n, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(tmp, h_cov6, sizeof(double) * 6 * (size_t)n, hipMemcpyHostToDevice, stream);
+  if (const int rc = sc.take(&tmp, 6 * (size_t)n, err, "upload_covariances"); rc != PCM_OK) return rc;
+  hipError_t e = hipMemcpyAsync(tmp, h_cov6, sizeof(double) * 6 * (size_t)n, hipMemcpyHostToDevice, stream);
   if (e == hipSuccess) { k_scatter_cov<<<(n + 255u) / 256u, 256, 0, stream>>>(map.order, tmp, n, d_cov); e = hipGetLastError(); }
   if (e == hipSuccess) e = hipStreamSynchronize(stream);   // h_cov6 is the caller's
-  if (tmp) (void)hipFreeAsync(tmp, stream);
   if (e != hipSuccess) { *err = std::string("upload_covariances: ") + hipGetErrorString(e); return PCM_ERR_HIP; }
   return PCM_OK;
 }
@@ -1274,39 +1264,28 @@ int gicp_bfgs_correspond_device(hipStream_t stream, const TargetMap& tmap, int c
       X.R[a * 3 + b] = v;
     }
   X.max_sq = max_corr_dist * max_corr_dist;
+  DevScratch sc(stream);
   char* tmp = nullptr;
-  void* scan_tmp = nullptr;
-  size_t scan_bytes = 0;
   uint32_t tails[2] = {0, 0};
-  TargetView tg{};
-  tg.pts = tmap.pts; tg.vox_start = tmap.vox_start; tg.bricks = tmap.bricks; tg.bmask = tmap.bmask; tg.bpref = tmap.bpref; tg.gvox = tmap.gvox;
-  tg.mask = tmap.cap - 1; tg.num_points = tmap.num_points; tg.inv_res = tmap.inv_res; tg.res = tmap.res;
-  const int rc = [&]() -> int {
-    const size_t b_flag = ((size_t)n * 4 + 255) & ~(size_t)255, b_rec = (size_t)n * 64, b_idx = b_flag;
-    PCM_HIPCK_ERR(err, hipMallocAsync(reinterpret_cast<void**>(&tmp), 2 * b_flag + b_rec + b_idx, stream));
-    uint32_t* flag = reinterpret_cast<uint32_t*>(tmp);
-    uint32_t* pos = reinterpret_cast<uint32_t*>(tmp + b_flag);
-    float4* rec = reinterpret_cast<float4*>(tmp + 2 * b_flag);
-    int32_t* tidx = reinterpret_cast<int32_t*>(tmp + 2 * b_flag + b_rec);
-    k_bfgs_correspond<<<(n + 255u) / 256u, 256, 0, stream>>>(tg, coord_mode, smap.pts, smap.order, n, src_cov, tgt_cov, tmap.order, X, flag, rec, tidx);
+  const size_t b_flag = up256((size_t)n * 4), b_rec = (size_t)n * 64, b_idx = b_flag;
+  if (const int rc = sc.take(&tmp, 2 * b_flag + b_rec + b_idx, err, "correspondence records"); rc != PCM_OK) return rc;
+  uint32_t* flag = reinterpret_cast<uint32_t*>(tmp);
+  uint32_t* pos = reinterpret_cast<uint32_t*>(tmp + b_flag);
+  float4* rec = reinterpret_cast<float4*>(tmp + 2 * b_flag);
+  int32_t* tidx = reinterpret_cast<int32_t*>(tmp + 2 * b_flag + b_rec);
+  k_bfgs_correspond<<<(n + 255u) / 256u, 256, 0, stream>>>(view_of(tmap), coord_mode, smap.pts, smap.order, n, src_cov, tgt_cov, tmap.order, X, flag, rec, tidx);
+  PCM_HIPCK_ERR(err, hipGetLastError());
+  if (const int rc = scratch_exclusive_scan(sc, err, flag, pos, (size_t)n); rc != PCM_OK) return rc;
+  PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[0], flag + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+  PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[1], pos + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+  PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
+  const uint32_t m = tails[0] + tails[1];
+  if (m) {
+    k_bfgs_compact<<<(n + 255u) / 256u, 256, 0, stream>>>(flag, pos, rec, tidx, n, m, d_records, d_idx_src, d_idx_tgt);
     PCM_HIPCK_ERR(err, hipGetLastError());
-    PCM_HIPCK_ERR(err, rocprim::exclusive_scan(nullptr, scan_bytes, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-    PCM_HIPCK_ERR(err, hipMallocAsync(&scan_tmp, scan_bytes, stream));
-    PCM_HIPCK_ERR(err, rocprim::exclusive_scan(scan_tmp, scan_bytes, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-    PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[0], flag + (n - 1), 4, hipMemcpyDeviceToHost, stream));
-    PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[1], pos + (n - 1), 4, hipMemcpyDeviceToHost, stream));
-    PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
-    const uint32_t m = tails[0] + tails[1];
-    if (m) {
-      k_bfgs_compact<<<(n + 255u) / 256u, 256, 0, stream>>>(flag, pos, rec, tidx, n, m, d_records, d_idx_src, d_idx_tgt);
-      PCM_HIPCK_ERR(err, hipGetLastError());
-    }
-    *m_out = m;
-    return PCM_OK;
-  }();
-  if (tmp) (void)hipFreeAsync(tmp, stream);
-  if (scan_tmp) (void)hipFreeAsync(scan_tmp, stream);
-  return rc;
+  }
+  *m_out = m;
+  return PCM_OK;
 }
 
 void launch_fitness(hipStream_t stream, const TargetView& tg, int coord_mode, const float4* src, uint32_t n, const float* T, double max_range, double* d_out) {

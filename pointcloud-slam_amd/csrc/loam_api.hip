@@ -100,7 +100,8 @@ int ensure_maps(pcm_ctx* c, LoamCtx* L, float cell, int* built) {
   for (int m = 0; m < 2; m++) {
     uint32_t n = (uint32_t)L->map_n[m];
     if (n == 0) { L->map[m].release(); continue; }
-    int rc = build_target_map(c->stream, L->map_pts[m], &n, cell, COORD_FLOOR_MUL, false, 0u, &L->map[m], &c->err, true);
+    MapBuildOptions opt; opt.keep_order = true;
+    int rc = build_target_map(c->stream, L->map_pts[m], &n, cell, COORD_FLOOR_MUL, &L->map[m], &c->err, opt);
     if (rc != PCM_OK) return rc;
     launch_tag_input_index(c->stream, L->map[m].pts, L->map[m].order, n);
     PCM_HIPCK(c, hipGetLastError());
@@ -113,13 +114,8 @@ int ensure_maps(pcm_ctx* c, LoamCtx* L, float cell, int* built) {
   return PCM_OK;
 }
 
-TargetView view_of_loam_map(const TargetMap& m) {
-  TargetView v{};
-  if (!m.valid) return v;
-  v.pts = m.pts; v.vox_start = m.vox_start; v.bricks = m.bricks; v.bmask = m.bmask; v.bpref = m.bpref; v.gvox = nullptr;
-  v.mask = m.cap - 1; v.num_points = m.num_points; v.inv_res = m.inv_res; v.res = m.res;
-  return v;
-}
+// an empty map has no grid; a built one has no Gauss voxels (ensure_maps never asks for them, so m.gvox is null)
+TargetView view_of_loam_map(const TargetMap& m) { return m.valid ? view_of(m) : TargetView{}; }
 
 int ensure_state(pcm_ctx* c, LoamCtx* L) {
   const size_t need = (size_t)num_blocks(L->n_c + L->n_s) * kSums;

@@ -24,10 +24,10 @@
 #include "plane_fit.h"
 #include "linearize_common.h"
 #include "keyed_best.h"
+#include "dev_scratch.h"
 
 #include <cstring>
 #include <string>
-#include <rocprim/rocprim.hpp>
 
 namespace pcm {
 
@@ -191,143 +191,159 @@ __global__ void k_nl_voxel_slots(const float4* __restrict__ centres, uint32_t nd
   }
 }
 
-TargetView view_of_map(const TargetMap& m) {
-  TargetView v{};
-  v.pts = m.pts; v.vox_start = m.vox_start; v.bricks = m.bricks; v.bmask = m.bmask; v.bpref = m.bpref; v.gvox = m.gvox;
-  v.mask = m.cap - 1; v.num_points = m.num_points; v.inv_res = m.inv_res; v.res = m.res;
-  return v;
-}
-
 }  // namespace
 
 TargetView view_of_lists(const NeighbourLists& l) {
-  TargetView v = view_of_map(l.index);
+  TargetView v = view_of(l.index);
   v.pts = l.pts;
   v.vox_start = l.start;
   v.num_points = (uint32_t)l.num_candidates;
   return v;
 }
 
-// Build the candidate lists of `map` for the neighbourhood `nn` (7 / 19 / 27 cells); with `ndt_leaves` (pclomp NDT: nn = 0 for the
-// KDTREE search, 1 / 7 / 27) the lists hold neighbour LEAVES instead of points.  Host syncs: the number of dilated voxels, the index
-// build's own, the total list length.
+// ---------------------------------------------------------------------------
+// build_neighbour_lists in stages over one ListBuild (DESIGN.md "Build stages"; as build_target_map, voxel_hash.hip)
+// ---------------------------------------------------------------------------
+struct ListBuild {
+  hipStream_t stream;
+  std::string* err;
+  const TargetMap& map;
+  NeighbourLists* out;
+  DevScratch sc;
+  int nn;        // the neighbourhood asked for (0: the KDTREE search of pclomp NDT)
+  int nset;      // its cells (the SET is the same in the iVox and the pcl order: c_nearby's prefixes)
+  size_t nk;     // (voxel, offset) keys
+  float4* centres = nullptr;   // a stand-in point per dilated voxel, in key order
+  uint32_t nd = 0;             // dilated voxels = lists
+};
+
+// room for `need` bytes?  a quarter of the free memory stays untouched (the caller's next targets, the scratch of the passes)
+static int room_for(size_t need, std::string* err) {
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b - free_b / 4) {
+    *err = "neighbour lists: " + std::to_string(need >> 20) + " MiB needed, " + std::to_string(free_b >> 20) + " MiB of device memory free";
+    return PCM_ERR_HIP;
+  }
+  return PCM_OK;
+}
+
+// the dilated occupied set: keys of every (voxel, offset), sorted, their heads flagged and ranked, one centre per head; the
+// number of heads to the host (one read-back)
+static int dilated_voxels(ListBuild& b) {
+  const TargetMap& map = b.map;
+  const int mode = map.coord_mode;
+  const size_t nk = b.nk;
+  const unsigned nb = (unsigned)((nk + 255) / 256);
+  uint64_t *keys = nullptr, *keys_s = nullptr;
+  uint32_t *flag = nullptr, *pos = nullptr, *d_cnt = nullptr, h_cnt = 0;
+  if (b.sc.take(&keys, nk, b.err, "dilation keys") || b.sc.take(&keys_s, nk, b.err, "dilation keys, sorted")) return PCM_ERR_HIP;
+  if (b.sc.take(&flag, nk, b.err, "dilation heads") || b.sc.take(&pos, nk, b.err, "dilation ranks")) return PCM_ERR_HIP;
+  if (b.sc.take(&d_cnt, 2, b.err, "dilation count")) return PCM_ERR_HIP;
+  k_nl_keys<<<(map.num_voxels + 255) / 256, 256, 0, b.stream>>>(map.pts, map.vox_start, map.num_voxels, map.res, map.inv_res, mode, b.nset, keys);
+  PCM_HIPCK_ERR(b.err, hipGetLastError());
+  if (const int rc = scratch_sort_keys(b.sc, b.err, keys, keys_s, nk, 0, 64); rc != PCM_OK) return rc;
+  k_nl_flags<<<nb, 256, 0, b.stream>>>(keys_s, (uint32_t)nk, flag);
+  PCM_HIPCK_ERR(b.err, hipGetLastError());
+  if (const int rc = scratch_exclusive_scan(b.sc, b.err, flag, pos, nk); rc != PCM_OK) return rc;
+  if (const int rc = b.sc.take(&b.centres, nk, b.err, "dilated voxel centres"); rc != PCM_OK) return rc;   // at most one per key
+  k_nl_centres<<<nb, 256, 0, b.stream>>>(keys_s, flag, pos, (uint32_t)nk, map.res, mode == COORD_ROUND ? 0.f : mode == COORD_FLOOR_MUL ? 0.5f : 1.0f, b.centres, d_cnt);
+  PCM_HIPCK_ERR(b.err, hipGetLastError());
+  PCM_HIPCK_ERR(b.err, hipMemcpyAsync(&h_cnt, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream));
+  PCM_HIPCK_ERR(b.err, hipStreamSynchronize(b.stream));
+  b.nd = h_cnt;
+  if (b.nd == 0) { *b.err = "neighbour lists: empty map"; return PCM_ERR_NO_INPUT; }
+  return PCM_OK;
+}
+
+// the list index: a brick hash over the stand-in points (one per dilated voxel); its own host syncs
+static int list_index(ListBuild& b) {
+  if (const int rc = build_target_map(b.stream, b.centres, &b.nd, b.map.res, b.map.coord_mode, &b.out->index, b.err); rc != PCM_OK) return rc;
+  if (b.out->index.num_voxels != b.nd || b.out->index.num_points != b.nd) { *b.err = "neighbour lists: index does not hold one voxel per list"; return PCM_ERR_INTERNAL; }
+  return PCM_OK;
+}
+
+// kind 2: a fixed row of nn voxel indices per list voxel, kept in the `pts` allocation
+static int voxel_slot_rows(ListBuild& b) {
+  NeighbourLists* out = b.out;
+  const uint32_t nd = b.nd;
+  const size_t words = (size_t)nd * b.nn, cells = (words + 3) / 4 + 4;
+  if (const int rc = out->pts.reserve(b.stream, b.err, cells, cells); rc != PCM_OK) return rc;
+  k_nl_voxel_slots<<<(nd + 127) / 128, 128, 0, b.stream>>>(out->index.pts, nd, view_of(b.map), b.map.coord_mode, b.nn, reinterpret_cast<int32_t*>(out->pts.p));
+  PCM_HIPCK_ERR(b.err, hipGetLastError());
+  PCM_HIPCK_ERR(b.err, hipStreamSynchronize(b.stream));
+  out->num_lists = nd;
+  out->num_candidates = words;
+  out->num_neighbors = b.nn;
+  out->kind = 2;
+  out->valid = true;
+  return PCM_OK;
+}
+
+// kinds 0 (points) and 1 (`ndt_leaves`): list lengths -> starts -> candidates; the total length to the host (one read-back)
+static int fill_lists(ListBuild& b, const PclLeaf* ndt_leaves, size_t list_entries) {
+  NeighbourLists* out = b.out;
+  hipStream_t stream = b.stream;
+  const TargetMap& map = b.map;
+  const uint32_t nd = b.nd;
+  const int nn = b.nn, mode = map.coord_mode;
+  const bool point_lists = !ndt_leaves;   // runs padded to whole trips (kListTrip)
+  // A point list ends with at most kListTrip - 1 pad entries: the 32-bit starts and the memory must hold them too (the scratch of
+  // the build is still taken here, so only the lists themselves are asked for)
+  const size_t pad_max = point_lists ? (size_t)nd * (kListTrip - 1) : 0;
+  if (list_entries + pad_max >= (1ull << 32)) { *b.err = "neighbour lists: map too large"; return PCM_ERR_UNSUPPORTED; }
+  if (pad_max)
+    if (const int rc = room_for((list_entries + pad_max) * sizeof(float4) + ((size_t)64 << 20), b.err); rc != PCM_OK) return rc;
+  if (const int rc = out->start.reserve(stream, b.err, (size_t)nd + 1, (size_t)nd + 1); rc != PCM_OK) return rc;
+  uint32_t *len = nullptr, h_total = 0;
+  if (b.sc.take(&len, (size_t)nd + 1, b.err, "list lengths")) return PCM_ERR_HIP;
+  PCM_HIPCK_ERR(b.err, hipMemsetAsync(len, 0, sizeof(uint32_t) * ((size_t)nd + 1), stream));
+  if (ndt_leaves) k_nl_leaf_lists<false><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of(map), mode, ndt_leaves, nn, len, nullptr, nullptr);
+  else k_nl_lists<false><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of(map), nn, len, nullptr, nullptr);
+  PCM_HIPCK_ERR(b.err, hipGetLastError());
+  if (const int rc = scratch_exclusive_scan(b.sc, b.err, len, out->start.p, (size_t)nd + 1); rc != PCM_OK) return rc;
+  PCM_HIPCK_ERR(b.err, hipMemcpyAsync(&h_total, out->start + nd, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  PCM_HIPCK_ERR(b.err, hipStreamSynchronize(stream));
+  const size_t total = h_total;
+  // The starts of the point lists are multiples of kListTrip entries = 64 bytes and DevBuf's hipMalloc returns at least 256-byte
+  // aligned memory, so every run starts on a 64-byte boundary; `total` counts the pad entries, so the last trip of the last run
+  // ends inside the array.  Zeroed tail: the walk of the leaf lists (pclndt.hip) reads (never uses) up to three entries past a
+  // run, the keyed walk of k_linearize_lists loads (never offers) kWalkAhead trips past one.
+  const size_t tail = point_lists ? (size_t)kListTrip * kWalkAhead : 4;
+  static_assert(kListTrip * kWalkAhead >= 4, "the tail of the point lists is no shorter than that of the leaf lists");
+  if (const int rc = out->pts.reserve(stream, b.err, total + tail, total + tail); rc != PCM_OK) return rc;
+  PCM_HIPCK_ERR(b.err, hipMemsetAsync(out->pts + total, 0, sizeof(float4) * tail, stream));
+  if (ndt_leaves) k_nl_leaf_lists<true><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of(map), mode, ndt_leaves, nn, nullptr, out->start, out->pts);
+  else k_nl_lists<true><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of(map), nn, nullptr, out->start, out->pts);
+  PCM_HIPCK_ERR(b.err, hipGetLastError());
+  PCM_HIPCK_ERR(b.err, hipStreamSynchronize(stream));
+  out->num_lists = nd;
+  out->num_candidates = total;
+  out->num_neighbors = nn;
+  out->kind = ndt_leaves ? 1 : 0;
+  out->valid = true;
+  return PCM_OK;
+}
+
+// Build the lists of `map` for the neighbourhood `nn`, of one of three kinds (NeighbourLists::kind):
+//   0  neither `ndt_leaves` nor `voxel_slots`: candidate POINTS of the nn = 1 / 7 / 19 / 27 cells, runs padded to whole trips;
+//   1  `ndt_leaves` (pclomp NDT): neighbour LEAVES, nn = 0 for the KDTREE search, else 1 / 7 / 27;
+//   2  `voxel_slots` (k_ndt): a fixed row of nn = 1 / 7 / 27 neighbour voxel indices per list voxel.
+// Host syncs: the number of dilated voxels, the index build's own, the total list length (kind 2: the end of its one kernel).
 int build_neighbour_lists(hipStream_t stream, const TargetMap& map, int nn, NeighbourLists* out, std::string* err, const PclLeaf* ndt_leaves, bool voxel_slots) {
   out->valid = false;
   const int mode = map.coord_mode;
   if (!map.valid || (mode != COORD_ROUND && mode != COORD_FLOOR_MUL && mode != COORD_FLOOR_HALF)) { *err = "neighbour lists: unsupported voxel convention"; return PCM_ERR_UNSUPPORTED; }
   if (voxel_slots ? (nn != 1 && nn != 7 && nn != 27) : ndt_leaves ? (nn != 0 && nn != 1 && nn != 7 && nn != 27) : (nn != 1 && nn != 7 && nn != 19 && nn != 27)) { *err = "neighbour lists: unsupported neighbourhood"; return PCM_ERR_INVALID_ARGUMENT; }
-  const int nset = nn == 0 ? 27 : nn;   // cells of the neighbourhood (the SET is the same in the iVox and the pcl order: c_nearby's prefixes)
-  const uint32_t nvox = map.num_voxels;
-  const size_t nk = (size_t)nvox * nset;
-  if (nk >= (1ull << 31) || (size_t)map.num_points * nset >= (1ull << 32)) { *err = "neighbour lists: map too large"; return PCM_ERR_UNSUPPORTED; }
-  const bool point_lists = !ndt_leaves && !voxel_slots;   // kind 0: runs padded to whole trips (kListTrip)
-  // room for them?  27 x 16 B per map point for the lists (the pad entries of the point lists come on top: checked below, once the
-  // number of lists is known), ~56 B per (voxel, offset) key while they are built; a quarter of the free memory stays untouched
-  // (the caller's next targets, the scratch of the passes)
-  const auto room_for = [&](size_t need) -> int {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b - free_b / 4) {
-      *err = "neighbour lists: " + std::to_string(need >> 20) + " MiB needed, " + std::to_string(free_b >> 20) + " MiB of device memory free";
-      return PCM_ERR_HIP;
-    }
-    return PCM_OK;
-  };
-  const size_t list_entries = (point_lists ? (size_t)map.num_points : (size_t)nvox) * nset;
-  if (const int rc = room_for(list_entries * sizeof(float4) + nk * 56 + ((size_t)64 << 20)); rc != PCM_OK) return rc;
-  uint64_t *keys = nullptr, *keys_s = nullptr;
-  uint32_t *flag = nullptr, *pos = nullptr, *d_cnt = nullptr, *len = nullptr;
-  float4* centres = nullptr;
-  void *tmp = nullptr, *tmp2 = nullptr, *tmp3 = nullptr;
-  size_t tmp_bytes = 0, tmp2_bytes = 0, tmp3_bytes = 0;
-  uint32_t h_cnt[2] = {0, 0};
-  // the build proper; its temporaries go back to the stream's pool behind it
-  const int rc = [&]() -> int {
-    const unsigned nb = (unsigned)((nk + 255) / 256);
-    PCM_HIPCK_ERR(err, hipMallocAsync(reinterpret_cast<void**>(&keys), sizeof(uint64_t) * nk, stream));
-    PCM_HIPCK_ERR(err, hipMallocAsync(reinterpret_cast<void**>(&keys_s), sizeof(uint64_t) * nk, stream));
-    PCM_HIPCK_ERR(err, hipMallocAsync(reinterpret_cast<void**>(&flag), sizeof(uint32_t) * nk, stream));
-    PCM_HIPCK_ERR(err, hipMallocAsync(reinterpret_cast<void**>(&pos), sizeof(uint32_t) * nk, stream));
-    PCM_HIPCK_ERR(err, hipMallocAsync(reinterpret_cast<void**>(&d_cnt), sizeof(uint32_t) * 2, stream));
-    k_nl_keys<<<(nvox + 255) / 256, 256, 0, stream>>>(map.pts, map.vox_start, nvox, map.res, map.inv_res, mode, nset, keys);
-    PCM_HIPCK_ERR(err, hipGetLastError());
-    PCM_HIPCK_ERR(err, rocprim::radix_sort_keys(nullptr, tmp_bytes, keys, keys_s, nk, 0, 64, stream));
-    PCM_HIPCK_ERR(err, hipMallocAsync(&tmp, tmp_bytes, stream));
-    PCM_HIPCK_ERR(err, rocprim::radix_sort_keys(tmp, tmp_bytes, keys, keys_s, nk, 0, 64, stream));
-    k_nl_flags<<<nb, 256, 0, stream>>>(keys_s, (uint32_t)nk, flag);
-    PCM_HIPCK_ERR(err, hipGetLastError());
-    PCM_HIPCK_ERR(err, rocprim::exclusive_scan(nullptr, tmp2_bytes, flag, pos, 0u, nk, rocprim::plus<uint32_t>(), stream));
-    PCM_HIPCK_ERR(err, hipMallocAsync(&tmp2, tmp2_bytes, stream));
-    PCM_HIPCK_ERR(err, rocprim::exclusive_scan(tmp2, tmp2_bytes, flag, pos, 0u, nk, rocprim::plus<uint32_t>(), stream));
-    PCM_HIPCK_ERR(err, hipMallocAsync(reinterpret_cast<void**>(&centres), sizeof(float4) * nk, stream));   // at most one per key
-    k_nl_centres<<<nb, 256, 0, stream>>>(keys_s, flag, pos, (uint32_t)nk, map.res, mode == COORD_ROUND ? 0.f : mode == COORD_FLOOR_MUL ? 0.5f : 1.0f, centres, d_cnt);
-    PCM_HIPCK_ERR(err, hipGetLastError());
-    PCM_HIPCK_ERR(err, hipMemcpyAsync(&h_cnt[0], d_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
-    uint32_t nd = h_cnt[0];
-    if (nd == 0) { *err = "neighbour lists: empty map"; return PCM_ERR_NO_INPUT; }
-    // the list index: a brick hash over the stand-in points (one per dilated voxel)
-    int rc = build_target_map(stream, centres, &nd, map.res, mode, false, 0u, &out->index, err);
-    if (rc != PCM_OK) return rc;
-    if (out->index.num_voxels != nd || out->index.num_points != nd) { *err = "neighbour lists: index does not hold one voxel per list"; return PCM_ERR_INTERNAL; }
-    if (voxel_slots) {   // a fixed row of nn voxel indices per list voxel, kept in the `pts` allocation
-      const size_t words = (size_t)nd * nn, cells = (words + 3) / 4 + 4;
-      if ((rc = out->pts.reserve(stream, err, cells, cells)) != PCM_OK) return rc;
-      k_nl_voxel_slots<<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of_map(map), mode, nn, reinterpret_cast<int32_t*>(out->pts.p));
-      PCM_HIPCK_ERR(err, hipGetLastError());
-      PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
-      out->num_lists = nd;
-      out->num_candidates = words;
-      out->num_neighbors = nn;
-      out->kind = 2;
-      out->valid = true;
-      return PCM_OK;
-    }
-    // list lengths -> starts -> candidates.  A point list ends with at most kListTrip - 1 pad entries: the 32-bit starts and the
-    // memory must hold them too (the temporaries of the build are still allocated here, so only the lists themselves are asked for)
-    const size_t pad_max = point_lists ? (size_t)nd * (kListTrip - 1) : 0;
-    if (list_entries + pad_max >= (1ull << 32)) { *err = "neighbour lists: map too large"; return PCM_ERR_UNSUPPORTED; }
-    if (pad_max && (rc = room_for((list_entries + pad_max) * sizeof(float4) + ((size_t)64 << 20))) != PCM_OK) return rc;
-    if ((rc = out->start.reserve(stream, err, (size_t)nd + 1, (size_t)nd + 1)) != PCM_OK) return rc;
-    PCM_HIPCK_ERR(err, hipMallocAsync(reinterpret_cast<void**>(&len), sizeof(uint32_t) * ((size_t)nd + 1), stream));
-    PCM_HIPCK_ERR(err, hipMemsetAsync(len, 0, sizeof(uint32_t) * ((size_t)nd + 1), stream));
-    if (ndt_leaves) k_nl_leaf_lists<false><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of_map(map), mode, ndt_leaves, nn, len, nullptr, nullptr);
-    else k_nl_lists<false><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of_map(map), nn, len, nullptr, nullptr);
-    PCM_HIPCK_ERR(err, hipGetLastError());
-    PCM_HIPCK_ERR(err, rocprim::exclusive_scan(nullptr, tmp3_bytes, len, out->start.p, 0u, (size_t)nd + 1, rocprim::plus<uint32_t>(), stream));
-    PCM_HIPCK_ERR(err, hipMallocAsync(&tmp3, tmp3_bytes, stream));
-    PCM_HIPCK_ERR(err, rocprim::exclusive_scan(tmp3, tmp3_bytes, len, out->start.p, 0u, (size_t)nd + 1, rocprim::plus<uint32_t>(), stream));
-    PCM_HIPCK_ERR(err, hipMemcpyAsync(&h_cnt[1], out->start + nd, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
-    const size_t total = h_cnt[1];
-    // The starts of the point lists are multiples of kListTrip entries = 64 bytes and DevBuf's hipMalloc returns at least 256-byte
-    // aligned memory, so every run starts on a 64-byte boundary; `total` counts the pad entries, so the last trip of the last run
-    // ends inside the array.  Zeroed tail: the walk of the leaf lists (pclndt.hip) reads (never uses) up to three entries past a
-    // run, the keyed walk of k_linearize_lists loads (never offers) kWalkAhead trips past one.
-    const size_t tail = point_lists ? (size_t)kListTrip * kWalkAhead : 4;
-    static_assert(kListTrip * kWalkAhead >= 4, "the tail of the point lists is no shorter than that of the leaf lists");
-    if ((rc = out->pts.reserve(stream, err, total + tail, total + tail)) != PCM_OK) return rc;
-    PCM_HIPCK_ERR(err, hipMemsetAsync(out->pts + total, 0, sizeof(float4) * tail, stream));
-    if (ndt_leaves) k_nl_leaf_lists<true><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of_map(map), mode, ndt_leaves, nn, nullptr, out->start, out->pts);
-    else k_nl_lists<true><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of_map(map), nn, nullptr, out->start, out->pts);
-    PCM_HIPCK_ERR(err, hipGetLastError());
-    PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
-    out->num_lists = nd;
-    out->num_candidates = total;
-    out->num_neighbors = nn;
-    out->kind = ndt_leaves ? 1 : 0;
-    out->valid = true;
-    return PCM_OK;
-  }();
-  if (keys) (void)hipFreeAsync(keys, stream);
-  if (keys_s) (void)hipFreeAsync(keys_s, stream);
-  if (flag) (void)hipFreeAsync(flag, stream);
-  if (pos) (void)hipFreeAsync(pos, stream);
-  if (d_cnt) (void)hipFreeAsync(d_cnt, stream);
-  if (len) (void)hipFreeAsync(len, stream);
-  if (centres) (void)hipFreeAsync(centres, stream);
-  if (tmp) (void)hipFreeAsync(tmp, stream);
-  if (tmp2) (void)hipFreeAsync(tmp2, stream);
-  if (tmp3) (void)hipFreeAsync(tmp3, stream);
+  ListBuild b{stream, err, map, out, DevScratch(stream), nn, nn == 0 ? 27 : nn, 0};
+  b.nk = (size_t)map.num_voxels * b.nset;
+  if (b.nk >= (1ull << 31) || (size_t)map.num_points * b.nset >= (1ull << 32)) { *err = "neighbour lists: map too large"; return PCM_ERR_UNSUPPORTED; }
+  // room for them?  27 x 16 B per map point for the lists (the pad entries of the point lists come on top: fill_lists, once the
+  // number of lists is known), ~56 B per (voxel, offset) key while they are built
+  const size_t list_entries = (!ndt_leaves && !voxel_slots ? (size_t)map.num_points : (size_t)map.num_voxels) * b.nset;
+  int rc = room_for(list_entries * sizeof(float4) + b.nk * 56 + ((size_t)64 << 20), err);
+  if (rc == PCM_OK) rc = dilated_voxels(b);
+  if (rc == PCM_OK) rc = list_index(b);
+  if (rc == PCM_OK) rc = voxel_slots ? voxel_slot_rows(b) : fill_lists(b, ndt_leaves, list_entries);
   if (rc != PCM_OK) out->valid = false;
   return rc;
 }

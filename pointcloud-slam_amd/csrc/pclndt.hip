@@ -728,13 +728,6 @@ __global__ void __launch_bounds__(1024) k_pclndt_reduce(const double* __restrict
   }
 }
 
-TargetView view_of2(const TargetMap& m) {
-  TargetView v{};
-  v.pts = m.pts; v.vox_start = m.vox_start; v.bricks = m.bricks; v.bmask = m.bmask; v.bpref = m.bpref; v.gvox = m.gvox;
-  v.mask = m.cap - 1; v.num_points = m.num_points; v.inv_res = m.inv_res; v.res = m.res;
-  return v;
-}
-
 }  // namespace
 
 int build_pclndt_leaves(hipStream_t stream, const TargetMap& map, PclLeaf* d_out, PclLeafF* d_out_f, std::string* err) {
@@ -751,7 +744,7 @@ void launch_pclndt_batch_round(hipStream_t stream, const NdtObject* d_objs, ndto
 
 NdtObject make_ndt_object(const TargetMap& map, const PclLeaf* leaves, const PclLeafF* leaves_f, const TargetView& nl, const float4* src, uint32_t n, double* d_partials) {
   NdtObject ob{};
-  ob.tg = view_of2(map); ob.leaves = leaves; ob.leaves_f = leaves_f; ob.nl = nl; ob.src = src; ob.n = n;
+  ob.tg = view_of(map); ob.leaves = leaves; ob.leaves_f = leaves_f; ob.nl = nl; ob.src = src; ob.n = n;
   ob.nblocks = pclndt_workgroups(n, &ob.per);
   ob.partials = d_partials;
   return ob;
@@ -772,10 +765,10 @@ void launch_pclndt_pass(hipStream_t stream, const TargetMap& map, const PclLeaf*
                         double gauss_d3) {
   uint32_t per = 0;
   const int nb = pclndt_workgroups(n, &per);
-  if (pass == 0) k_pclndt_derivatives<true><<<nb, 256, 0, stream>>>(view_of2(map), leaves, leaves_f, nl, src, n, per, P, d_partials);
-  else if (pass == 1) k_pclndt_derivatives<false><<<nb, 256, 0, stream>>>(view_of2(map), leaves, leaves_f, nl, src, n, per, P, d_partials);
-  else if (pass == 2) k_pclndt_hessian<<<nb, 256, 0, stream>>>(view_of2(map), leaves, leaves_f, nl, src, n, per, P, d_partials);
-  else k_pclndt_score<<<nb, 256, 0, stream>>>(view_of2(map), leaves, src, n, per, P, gauss_d3, d_partials);
+  if (pass == 0) k_pclndt_derivatives<true><<<nb, 256, 0, stream>>>(view_of(map), leaves, leaves_f, nl, src, n, per, P, d_partials);
+  else if (pass == 1) k_pclndt_derivatives<false><<<nb, 256, 0, stream>>>(view_of(map), leaves, leaves_f, nl, src, n, per, P, d_partials);
+  else if (pass == 2) k_pclndt_hessian<<<nb, 256, 0, stream>>>(view_of(map), leaves, leaves_f, nl, src, n, per, P, d_partials);
+  else k_pclndt_score<<<nb, 256, 0, stream>>>(view_of(map), leaves, src, n, per, P, gauss_d3, d_partials);
   k_pclndt_reduce<<<1, 1024, 0, stream>>>(d_partials, nb, d_out);
 }
 

@@ -2,6 +2,7 @@
 // (configuration check, cloud upload, the GICP-BFGS functor, the LIO frame).  What a registration reads is built in prepare.hip;
 // the batched device-resident GN/LM loop and the parity hooks (linearize / compute_error) run in align_batch.hip.
 #include "pcm_core.h"
+#include "dev_scratch.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -487,11 +488,11 @@ int pcm_gicp_bfgs_set_correspondences(pcm_ctx* c, const void* src, size_t n_src,
   const void *d_src = src, *d_tgt = tgt;
   const int32_t *d_is = idx_src, *d_it = idx_tgt;
   const float* d_maha = maha;
-  char* tmp = nullptr;
+  DevScratch sc(c->stream);
   if (memory == PCM_MEM_HOST) {   // staged once per correspondence set; the evaluations then read the packed records only
     const size_t b_src = up256(n_src * stride), b_tgt = up256(n_tgt * stride), b_idx = up256(m * 4), b_maha = up256(n_src * 64);
-    PCM_HIPCK(c, hipMallocAsync(reinterpret_cast<void**>(&tmp), b_src + b_tgt + 2 * b_idx + b_maha, c->stream));
-    char* q = tmp;
+    char* q = nullptr;
+    if ((rc = sc.take(&q, b_src + b_tgt + 2 * b_idx + b_maha, &c->err, "correspondence staging")) != PCM_OK) return rc;
     PCM_HIPCK(c, hipMemcpyAsync(q, src, n_src * stride, hipMemcpyHostToDevice, c->stream)); d_src = q; q += b_src;
     PCM_HIPCK(c, hipMemcpyAsync(q, tgt, n_tgt * stride, hipMemcpyHostToDevice, c->stream)); d_tgt = q; q += b_tgt;
     PCM_HIPCK(c, hipMemcpyAsync(q, idx_src, m * 4, hipMemcpyHostToDevice, c->stream)); d_is = reinterpret_cast<const int32_t*>(q); q += b_idx;
@@ -499,7 +500,7 @@ int pcm_gicp_bfgs_set_correspondences(pcm_ctx* c, const void* src, size_t n_src,
     PCM_HIPCK(c, hipMemcpyAsync(q, maha, n_src * 64, hipMemcpyHostToDevice, c->stream)); d_maha = reinterpret_cast<const float*>(q);
   }
   rc = gicp_bfgs_pack_device(c->stream, d_src, d_tgt, stride, d_is, d_it, d_maha, m, c->bfgs, &c->err);
-  if (tmp) PCM_HIPCK(c, hipFreeAsync(tmp, c->stream));
+  sc.release();   // behind the pack, on the stream
   if (rc != PCM_OK) return rc;
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));   // the caller's buffers are free again
   c->bfgs_m = m;

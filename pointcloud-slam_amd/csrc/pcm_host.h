@@ -51,7 +51,7 @@ struct TargetMap {   // layout: pcm_device.h
   DevBuf<uint64_t> keys_s{"keys_s"}, keys_t{"keys_t"};
   DevBuf<uint32_t> idx_s{"idx_s"}, idx_t{"idx_t"};
   uint32_t index_n = 0;         // log points keys_s / idx_s cover (0: no usable index)
-  DevBuf<char> arena{"map update arena"};   // scratch of the incremental updates (grow-only; voxel_hash.hip BuildScratch)
+  DevBuf<char> arena{"map update arena"};   // scratch of the incremental updates (grow-only; the build's DevScratch carves it)
   PinnedBuf<int> h_ctr{"counters"};         // pinned host copy of the build's counter record (one read-back per synchronisation point)
   uint32_t cap = 0, num_voxels = 0, num_bricks = 0, num_points = 0;
   uint32_t max_voxel_points = 0;   // most points in one voxel
@@ -62,9 +62,28 @@ struct TargetMap {   // layout: pcm_device.h
   void release() { this->~TargetMap(); new (this) TargetMap(); }
 };
 
-// n_indexed > 0: the first n_indexed points of the log are what map->keys_s / idx_s index; only the points behind them are new
-int build_target_map(hipStream_t stream, float4* d_pts, uint32_t* n_inout, float res, int coord_mode, bool want_gauss, uint32_t capacity_voxels, TargetMap* map,
-                     std::string* err, bool keep_order = false, uint32_t n_indexed = 0, uint32_t* lru_hazards = nullptr, bool subsort = false);
+// the kernels' view of a built map
+inline TargetView view_of(const TargetMap& m) {
+  TargetView v{};
+  v.pts = m.pts; v.vox_start = m.vox_start; v.bricks = m.bricks; v.bmask = m.bmask; v.bpref = m.bpref; v.gvox = m.gvox;
+  v.mask = m.cap - 1; v.num_points = m.num_points; v.inv_res = m.inv_res; v.res = m.res;
+  return v;
+}
+
+// What a build of a TargetMap is asked for beyond the plain brick hash; a call site names the fields it sets.
+struct MapBuildOptions {
+  bool gauss = false;        // the Gauss voxels (TargetMap::gvox: NDT models)
+  bool keep_order = false;   // keep the input index of every map point (TargetMap::order)
+  bool subsort = false;      // a voxel's points along a Morton curve of a grid 8x finer, not in input order (full builds only)
+  uint32_t capacity_voxels = 0;   // > 1: LRU eviction down to capacity - 1 voxels; log and *n_inout shrink with it
+  uint32_t n_indexed = 0;    // > 0: the first n_indexed log points are what map->keys_s / idx_s index; only the points behind are new
+  uint32_t* lru_hazards = nullptr;   // out: voxels the batch rule of the eviction kept whole (pcm_stats.lru_batch_hazards)
+};
+// Builds `map` from the point log d_pts[0 .. *n_inout): the sorted (key, log position) index, the voxel heads, the brick table,
+// the points gathered brick-major.  A run of named stages over one scoped scratch (voxel_hash.hip, DESIGN.md "Build stages"); an
+// incremental build (n_indexed, no gauss, no keep_order, same grid) sorts the new points only and merges, over map->arena.  After
+// a failure the map is empty.
+int build_target_map(hipStream_t stream, float4* d_pts, uint32_t* n_inout, float res, int coord_mode, TargetMap* map, std::string* err, const MapBuildOptions& opt = {});
 int load_points_to_device(hipStream_t stream, const void* points, size_t n, size_t stride, int memory, uint32_t seq0, float4* d_out, std::string* err);
 // batched scan re-ordering (voxel_hash.hip)
 struct SortJob {

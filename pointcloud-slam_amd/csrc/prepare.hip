@@ -114,7 +114,8 @@ int ensure_target_map(pcm_ctx* c) {
     // a map whose log only grew since its last build (pcm_target_insert / pcm_map_incremental) is updated: the new points are merged
     // into the sorted index it kept (voxel_hash.hip); anything else is built from scratch
     uint32_t hazards = 0;
-    int rc = build_target_map(c->stream, c->tg->tgt.d_pts, &n_log, c->cfg.voxel_resolution, mode, gauss, capacity, &c->tg->map, &c->err, gicp, c->tg->map.index_n, &hazards);
+    MapBuildOptions opt; opt.gauss = gauss; opt.keep_order = gicp; opt.capacity_voxels = capacity; opt.n_indexed = c->tg->map.index_n; opt.lru_hazards = &hazards;
+    int rc = build_target_map(c->stream, c->tg->tgt.d_pts, &n_log, c->cfg.voxel_resolution, mode, &c->tg->map, &c->err, opt);
     c->stats.lru_batch_hazards += hazards;
     c->tg->tgt.n = n_log;   // LRU eviction compacts the point log
     if (rc != PCM_OK) return rc;
@@ -185,8 +186,9 @@ int ensure_covariances(pcm_ctx* c, int side) {
     // Side difference 1: the target's only when its map holds the whole log; the source's is not asked.
     uint32_t n_fine = (uint32_t)cloud.n;
     const float fine_res = std::min(c->cfg.voxel_resolution, 0.5f) * 0.125f;   // 1/8 of the scan's own grid (prepare_gicp)
+    MapBuildOptions opt; opt.keep_order = true;
     const bool fine = cov_fine_index_enabled() && (!target || whole_log) &&
-                      build_target_map(c->stream, cloud.d_pts, &n_fine, fine_res, coord_mode_for(c->cfg.model), false, 0u, &c->covfine, &c->err, true) == PCM_OK;
+                      build_target_map(c->stream, cloud.d_pts, &n_fine, fine_res, coord_mode_for(c->cfg.model), &c->covfine, &c->err, opt) == PCM_OK;
     const int reg_code = c->cfg.regularization + (cuda_core ? 16 : 0);   // + 16: float CUDA-core semantics
     rc = compute_covariances(c->stream, map, c->cfg.k_correspondences, reg_code, cov, &c->err, fine ? &c->covfine : nullptr);
   }
@@ -235,7 +237,8 @@ int prepare_gicp(pcm_ctx* c) {
   if (!c->srcmap.valid || c->srcmap.res != src_res || c->srcmap.coord_mode != mode) {
     uint32_t n_src = (uint32_t)c->src.n;
     // sub-voxel order: 64 consecutive points of the brick-major scan are one patch (k_covariances; k_gicp reads it point by point)
-    rc = build_target_map(c->stream, c->src.d_pts, &n_src, src_res, mode, false, 0u, &c->srcmap, &c->err, true, 0u, nullptr, cov_subsort_enabled());
+    MapBuildOptions opt; opt.keep_order = true; opt.subsort = cov_subsort_enabled();
+    rc = build_target_map(c->stream, c->src.d_pts, &n_src, src_res, mode, &c->srcmap, &c->err, opt);
     if (rc != PCM_OK) return rc;
     c->src_cov_valid = false;
   }
@@ -250,7 +253,8 @@ int prepare_gicp(pcm_ctx* c) {
 int ensure_d2d_source_map(pcm_ctx* c) {
   if (c->cfg.model != PCM_MODEL_NDT_D2D || (c->srcmap.valid && c->srcmap.res == c->cfg.voxel_resolution)) return PCM_OK;
   uint32_t n_src = (uint32_t)c->src.n;
-  return build_target_map(c->stream, c->src.d_pts, &n_src, c->cfg.voxel_resolution, coord_mode_for(c->cfg.model), true, 0u, &c->srcmap, &c->err);
+  MapBuildOptions opt; opt.gauss = true;
+  return build_target_map(c->stream, c->src.d_pts, &n_src, c->cfg.voxel_resolution, coord_mode_for(c->cfg.model), &c->srcmap, &c->err, opt);
 }
 
 // what a pair of the batch loop writes per source element, and its round ticket
@@ -371,16 +375,7 @@ Geom pick_geom(size_t max_n, int npairs, bool ndt) {
 }
 
 void fill_desc(const pcm_ctx* c, PairDesc* d, double* partials) {
-  d->tgt.pts = c->tg->map.pts;
-  d->tgt.vox_start = c->tg->map.vox_start;
-  d->tgt.bricks = c->tg->map.bricks;
-  d->tgt.bmask = c->tg->map.bmask;
-  d->tgt.bpref = c->tg->map.bpref;
-  d->tgt.mask = c->tg->map.cap - 1;
-  d->tgt.num_points = c->tg->map.num_points;
-  d->tgt.inv_res = c->tg->map.inv_res;
-  d->tgt.res = c->tg->map.res;
-  d->tgt.gvox = c->tg->map.gvox;
+  d->tgt = view_of(c->tg->map);
   d->nl = lists_view_for(c);
   d->src.pts = (c->cfg.sort_source && c->src_sorted) ? c->src_order : c->src.d_pts;
   if (is_gicp(c->cfg.model)) d->src.pts = c->srcmap.pts;   // brick-major copy of the scan: its covariances are in that order

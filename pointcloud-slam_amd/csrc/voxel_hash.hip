@@ -16,10 +16,9 @@
 #include "pcm_device.h"
 #include "host_util.h"
 #include "dev_linalg.h"
+#include "dev_scratch.h"
 
 #include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 namespace pcm {
 
@@ -151,9 +150,6 @@ __global__ void __launch_bounds__(256) k_max_voxel_points(const uint32_t* __rest
 }
 
 static inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
-// scratch arrays come from the device's stream-ordered memory pool (hipMallocAsync): after the first frames an allocation
-// is a pool hit, no driver call and no implicit device synchronisation -- the sliding map rebuilds every frame
-static inline void sfree(hipStream_t stream, void* p) { if (p) (void)hipFreeAsync(p, stream); }
 
 // ---------------------------------------------------------------------------
 // Sliding-map eviction: IVox keeps its voxels in a least-recently-touched list and
@@ -360,227 +356,232 @@ __global__ void k_subvoxel_keys(const float4* __restrict__ pts, const uint32_t* 
   keys[i] = ((uint64_t)(vrank[i] + vflag[i] - 1u) << 9) | m;   // vrank is the EXCLUSIVE scan of the head flags: a head holds its voxel's index, the rest of the run one more
 }
 
-// Scratch of one build: a sliding map keeps a grow-only arena (an update then makes no allocation call at all: two dozen
-// hipMallocAsync / hipFreeAsync pairs were a third of an update's wall time); any other build takes from the stream-ordered pool.
-struct BuildScratch {
-  char* base = nullptr;
-  size_t cap = 0, used = 0;
-  std::vector<void*> pooled;
-  hipError_t get(void** p, size_t bytes, hipStream_t stream) {
-    const size_t b = (bytes + 255) & ~(size_t)255;
-    if (base && used + b <= cap) { *p = base + used; used += b; return hipSuccess; }
-    const hipError_t e = hipMallocAsync(p, bytes ? bytes : 1, stream);
-    if (e == hipSuccess) pooled.push_back(*p);
-    return e;
-  }
-  void release(hipStream_t stream) {
-    for (void* q : pooled) (void)hipFreeAsync(q, stream);
-    pooled.clear();
-    used = 0;
-  }
-};
-
 // capacity of a grow-only array of a TargetMap that must hold `need` elements: a quarter of headroom
 static inline size_t headroom(size_t need) { return need + need / 4 + 1024; }
 
-// Build the voxel hash of the point log `d_pts` into `map`, or -- `n_indexed` > 0: the first n_indexed log points are what
-// map->keys_s / idx_s index -- merge the points appended since.  Host syncs: voxel / brick counts (array sizes), once more after
-// an eviction.
-int build_target_map(hipStream_t stream, float4* d_pts, uint32_t* n_inout, float res, int coord_mode, bool want_gauss, uint32_t capacity_voxels, TargetMap* map,
-                     std::string* err, bool keep_order, uint32_t n_indexed, uint32_t* lru_hazards, bool subsort) {
-  uint32_t n = *n_inout;
-  if (n == 0) { map->release(); *err = "empty target cloud"; return PCM_ERR_NO_INPUT; }
-  const bool incremental = n_indexed > 0 && n_indexed <= n && map->keys_s && map->idx_s && map->index_n == n_indexed && map->res == res && map->coord_mode == coord_mode && !want_gauss && !keep_order;
-  uint64_t *keys_b = nullptr, *keys_bs = nullptr;
-  uint32_t *idx_b = nullptr, *idx_bs = nullptr, *vflag = nullptr, *vrank = nullptr;
-  int* d_flags = nullptr;  // [0] out-of-range flag, [1] brick count, [2] most points in one voxel, [3] LRU hazards, [4] voxels, [5] log points alive
-  void *tmp = nullptr, *tmp2 = nullptr;
-  size_t tmp_bytes = 0, tmp2_bytes = 0;
-  uint32_t hazards = 0;
-  BuildScratch sc;
-  // ivox3d.h:67  inv_resolution_ = 1.0 / resolution_ (float);  pcl::VoxelGrid: inverse_leaf_size_ = 1 / leaf_size_ in float
-  const float inv_res = coord_mode == COORD_FLOOR_MUL ? 1.0f / res : (float)(1.0 / res);
-#define RC(x) do { const int rc_ = (x); if (rc_ != PCM_OK) return rc_; } while (0)
-  map->valid = false;
-  if (map->h_ctr.reserve(stream, err, kCtrInts, kCtrInts) != PCM_OK) return PCM_ERR_HIP;
-  // the build proper; its scratch and, after a failure, the map are released behind it
-  const int rc = [&]() -> int {
-    if (incremental) {   // everything an update with eviction takes, rounded up: 24 B per new point, 52 B per log point, sort / scan temporaries
-      const size_t need = 24 * (size_t)(n - n_indexed) + 56 * (size_t)n + ((size_t)16 << 20);
-      RC(map->arena.reserve(stream, err, need, need + need / 4));
-      sc.base = map->arena; sc.cap = map->arena.cap;
-    }
-    PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&d_flags), kCtrInts * sizeof(int), stream));
-    PCM_HIPCK_ERR(err, hipMemsetAsync(d_flags, 0, kCtrInts * sizeof(int), stream));
-    // ---- 1. the sorted index (key, log position) of all n log points in map->keys_s / idx_s ------------------------------
-    const uint32_t first = incremental ? n_indexed : 0u, m = n - first;
-    RC(map->keys_s.reserve_keep(stream, err, n, headroom(n), first));   // an update keeps the index it merges into
-    RC(map->idx_s.reserve_keep(stream, err, n, headroom(n), first));
-    RC(map->keys_t.reserve_keep(stream, err, n, headroom(n), 0));
-    RC(map->idx_t.reserve_keep(stream, err, n, headroom(n), 0));
-    if (m > 0) {
-      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&keys_b), sizeof(uint64_t) * m, stream));
-      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&keys_bs), sizeof(uint64_t) * m, stream));
-      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&idx_b), sizeof(uint32_t) * m, stream));
-      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&idx_bs), sizeof(uint32_t) * m, stream));
-      k_point_keys_at<<<cdiv(m, 256), 256, 0, stream>>>(d_pts, first, m, res, inv_res, coord_mode, keys_b, idx_b, d_flags);
-      PCM_HIPCK_ERR(err, hipGetLastError());
-      uint64_t* ks = incremental ? keys_bs : map->keys_s;   // a full build sorts straight into the persistent index
-      uint32_t* is = incremental ? idx_bs : map->idx_s;
-      PCM_HIPCK_ERR(err, rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys_b, ks, idx_b, is, m, 0, 63, stream));
-      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&tmp), tmp_bytes, stream));
-      PCM_HIPCK_ERR(err, rocprim::radix_sort_pairs(tmp, tmp_bytes, keys_b, ks, idx_b, is, m, 0, 63, stream));
-      if (incremental) {
-        k_merge_old<<<cdiv(n_indexed, 256), 256, 0, stream>>>(map->keys_s, map->idx_s, n_indexed, keys_bs, m, map->keys_t, map->idx_t);
-        k_merge_new<<<cdiv(m, 256), 256, 0, stream>>>(map->keys_s, n_indexed, keys_bs, idx_bs, m, map->keys_t, map->idx_t);
-        PCM_HIPCK_ERR(err, hipGetLastError());
-        map->keys_s.swap(map->keys_t);
-        map->idx_s.swap(map->idx_t);
-      }
-    }
-    map->index_n = 0;   // until this build is through
-    // ---- 2. voxel heads, ranks; counts to the host -----------------------------------------------------------------------
-    PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&vflag), sizeof(uint32_t) * n, stream));
-    PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&vrank), sizeof(uint32_t) * n, stream));
-    uint32_t nvox = 0, nbricks = 0;
-    auto heads = [&](uint32_t cnt) -> int {
-      PCM_HIPCK_ERR(err, hipMemsetAsync(d_flags + 8, 0, kBrickCountShards * sizeof(int), stream));
-      k_head_flags<<<cdiv(cnt, 256), 256, 0, stream>>>(map->keys_s, cnt, vflag, reinterpret_cast<unsigned int*>(d_flags + 8));
-      PCM_HIPCK_ERR(err, hipGetLastError());
-      if (!tmp2) {
-        PCM_HIPCK_ERR(err, rocprim::exclusive_scan(nullptr, tmp2_bytes, vflag, vrank, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-        PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&tmp2), tmp2_bytes, stream));
-      }
-      {
-        size_t tb = tmp2_bytes;
-        PCM_HIPCK_ERR(err, rocprim::exclusive_scan(tmp2, tb, vflag, vrank, 0u, (size_t)cnt, rocprim::plus<uint32_t>(), stream));
-      }
-      k_count_voxels<<<1, 1, 0, stream>>>(vflag, vrank, cnt, d_flags);
-      PCM_HIPCK_ERR(err, hipMemcpyAsync(map->h_ctr, d_flags, kCtrInts * sizeof(int), hipMemcpyDeviceToHost, stream));   // one copy into pinned memory
-      PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
-      if (map->h_ctr[0]) { *err = "target point outside the +-2^20 voxel range (or not finite)"; return PCM_ERR_OUT_OF_RANGE; }
-      nvox = (uint32_t)map->h_ctr[4];
-      nbricks = 0;
-      for (int k = 0; k < kBrickCountShards; k++) nbricks += (uint32_t)map->h_ctr[8 + k];
-      return PCM_OK;
-    };
-    RC(heads(n));
-    if (subsort && !incremental) {   // permute the index inside the voxels (the heads and ranks above stay valid: same keys at the same places)
-      uint64_t *k2 = nullptr, *k2s = nullptr;
-      void* tmp5 = nullptr;
-      size_t tmp5_bytes = 0;
-      int bits = 9;
-      while (bits < 41 && (1ull << (bits - 9)) < (unsigned long long)nvox) bits++;
-      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&k2), sizeof(uint64_t) * n, stream));
-      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&k2s), sizeof(uint64_t) * n, stream));
-      k_subvoxel_keys<<<cdiv(n, 256), 256, 0, stream>>>(d_pts, map->idx_s, vflag, vrank, n, inv_res, k2);
-      PCM_HIPCK_ERR(err, hipGetLastError());
-      PCM_HIPCK_ERR(err, rocprim::radix_sort_pairs(nullptr, tmp5_bytes, k2, k2s, map->idx_s.p, map->idx_t.p, n, 0, bits, stream));
-      PCM_HIPCK_ERR(err, sc.get(&tmp5, tmp5_bytes, stream));
-      PCM_HIPCK_ERR(err, rocprim::radix_sort_pairs(tmp5, tmp5_bytes, k2, k2s, map->idx_s.p, map->idx_t.p, n, 0, bits, stream));
-      map->idx_s.swap(map->idx_t);
-    }
-    if (capacity_voxels > 1 && nvox > capacity_voxels - 1) {
-      // ---- 3. LRU eviction: keep the (capacity - 1) most recently touched voxels; log and index are compacted in place ------
-      const uint32_t keep = capacity_voxels - 1;
-      uint32_t *vlast = nullptr, *vsorted = nullptr, *alive = nullptr, *pos = nullptr, *alive_s = nullptr, *pos_s = nullptr, *vfirst = nullptr;
-      float4* tmp_log = nullptr;
-      void *tmp3 = nullptr, *tmp4 = nullptr;
-      size_t tmp3_bytes = 0, tmp4_bytes = 0;
-      const uint32_t* d_cutoff = nullptr;
-      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&vlast), sizeof(uint32_t) * nvox, stream));
-      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&vsorted), sizeof(uint32_t) * nvox, stream));
-      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&vfirst), sizeof(uint32_t) * nvox, stream));
-      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&alive), sizeof(uint32_t) * n, stream));
-      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&pos), sizeof(uint32_t) * n, stream));
-      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&alive_s), sizeof(uint32_t) * n, stream));
-      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&pos_s), sizeof(uint32_t) * n, stream));
-      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&tmp_log), sizeof(float4) * n, stream));
-      k_voxel_firsts<<<cdiv(n, 256), 256, 0, stream>>>(vflag, vrank, n, vfirst);
-      k_voxel_last_from_firsts<<<cdiv(nvox, 256), 256, 0, stream>>>(d_pts, map->idx_s, vfirst, nvox, n, vlast);
-      PCM_HIPCK_ERR(err, hipGetLastError());
-      PCM_HIPCK_ERR(err, rocprim::radix_sort_keys(nullptr, tmp3_bytes, vlast, vsorted, nvox, 0, 32, stream));
-      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&tmp3), tmp3_bytes, stream));
-      PCM_HIPCK_ERR(err, rocprim::radix_sort_keys(tmp3, tmp3_bytes, vlast, vsorted, nvox, 0, 32, stream));
-      d_cutoff = vsorted + (nvox - keep);   // the smallest surviving last-touch stamp, read on the device
-      if (incremental && n_indexed < n) {   // the batch = the log points from n_indexed on
-        k_lru_hazards<<<cdiv(nvox, 256), 256, 0, stream>>>(d_pts, map->idx_s, vfirst, vlast, nvox, n, d_pts + n_indexed, d_cutoff, reinterpret_cast<unsigned int*>(d_flags + 3));
-        PCM_HIPCK_ERR(err, hipGetLastError());
-      }
-      k_mark_alive_dev<<<cdiv(n, 256), 256, 0, stream>>>(map->idx_s, vflag, vrank, vlast, d_cutoff, n, alive);
-      PCM_HIPCK_ERR(err, hipGetLastError());
-      PCM_HIPCK_ERR(err, rocprim::exclusive_scan(nullptr, tmp4_bytes, alive, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-      PCM_HIPCK_ERR(err, sc.get(reinterpret_cast<void**>(&tmp4), tmp4_bytes, stream));
-      { size_t tb = tmp4_bytes; PCM_HIPCK_ERR(err, rocprim::exclusive_scan(tmp4, tb, alive, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream)); }
-      k_alive_sorted<<<cdiv(n, 256), 256, 0, stream>>>(map->idx_s, alive, n, alive_s);
-      { size_t tb = tmp4_bytes; PCM_HIPCK_ERR(err, rocprim::exclusive_scan(tmp4, tb, alive_s, pos_s, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream)); }
-      k_compact_log<<<cdiv(n, 256), 256, 0, stream>>>(d_pts, alive, pos, n, tmp_log);
-      k_compact_index<<<cdiv(n, 256), 256, 0, stream>>>(map->keys_s, map->idx_s, alive, pos, pos_s, n, map->keys_t, map->idx_t);
-      k_count_alive<<<1, 1, 0, stream>>>(alive, pos, n, d_flags);
-      PCM_HIPCK_ERR(err, hipGetLastError());
-      PCM_HIPCK_ERR(err, hipMemcpyAsync(map->h_ctr, d_flags, kCtrInts * sizeof(int), hipMemcpyDeviceToHost, stream));
-      PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
-      n = (uint32_t)map->h_ctr[5];
-      hazards = (uint32_t)map->h_ctr[3];
-      PCM_HIPCK_ERR(err, hipMemcpyAsync(d_pts, tmp_log, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, stream));
+// ---------------------------------------------------------------------------
+// build_target_map in stages (DESIGN.md "Build stages").  A stage is a static function over the build's MapBuild: it queues its
+// kernels on b.stream, takes what it needs until the build ends from b.sc, and returns PCM_OK or the error with its text in
+// *b.err.  Nothing is freed by hand.
+// ---------------------------------------------------------------------------
+struct MapBuild {
+  hipStream_t stream;
+  std::string* err;
+  TargetMap* map;
+  float4* d_pts;          // the point log
+  uint32_t* n_log;        // its owner's count of it: follows an eviction's compaction
+  DevScratch sc;          // a sliding map's update: over its grow-only arena (no allocation call at all: two dozen pool calls were
+                          // a third of an update's wall time); any other build: the stream-ordered pool
+  int* d_flags = nullptr;   // [0] out-of-range flag, [1] brick count, [2] most points in one voxel, [3] LRU hazards, [4] voxels, [5] log points alive
+  uint32_t *vflag = nullptr, *vrank = nullptr;   // voxel head flag of every sorted key, and its exclusive scan
+  uint32_t n = 0, n_indexed = 0, nvox = 0, nbricks = 0, cap = 0, hazards = 0;
+  float res = 0.f, inv_res = 0.f;
+  int coord_mode = 0;
+  bool incremental = false;
+  MapBuild(hipStream_t s, std::string* e, TargetMap* m, float4* pts, uint32_t* np, char* arena, size_t arena_bytes) : stream(s), err(e), map(m), d_pts(pts), n_log(np), sc(s, arena, arena_bytes) {}
+};
+
+static int clear_counters(MapBuild& b) {
+  if (b.sc.take(&b.d_flags, kCtrInts, b.err, "build counters")) return PCM_ERR_HIP;
+  PCM_HIPCK_ERR(b.err, hipMemsetAsync(b.d_flags, 0, kCtrInts * sizeof(int), b.stream));
+  return PCM_OK;
+}
+
+// the sorted index (key, log position) of all n log points in map->keys_s / idx_s: a full sort, or the new points sorted and merged
+static int sort_index(MapBuild& b) {
+  TargetMap* map = b.map;
+  const uint32_t n = b.n, first = b.incremental ? b.n_indexed : 0u, m = n - first;
+  if (const int rc = map->keys_s.reserve_keep(b.stream, b.err, n, headroom(n), first); rc != PCM_OK) return rc;   // an update keeps the index it merges into
+  if (const int rc = map->idx_s.reserve_keep(b.stream, b.err, n, headroom(n), first); rc != PCM_OK) return rc;
+  if (const int rc = map->keys_t.reserve_keep(b.stream, b.err, n, headroom(n), 0); rc != PCM_OK) return rc;
+  if (const int rc = map->idx_t.reserve_keep(b.stream, b.err, n, headroom(n), 0); rc != PCM_OK) return rc;
+  if (m > 0) {
+    uint64_t *keys_b = nullptr, *keys_bs = nullptr;
+    uint32_t *idx_b = nullptr, *idx_bs = nullptr;
+    if (b.sc.take(&keys_b, m, b.err, "new keys") || b.sc.take(&keys_bs, m, b.err, "new keys, sorted")) return PCM_ERR_HIP;
+    if (b.sc.take(&idx_b, m, b.err, "new positions") || b.sc.take(&idx_bs, m, b.err, "new positions, sorted")) return PCM_ERR_HIP;
+    k_point_keys_at<<<cdiv(m, 256), 256, 0, b.stream>>>(b.d_pts, first, m, b.res, b.inv_res, b.coord_mode, keys_b, idx_b, b.d_flags);
+    PCM_HIPCK_ERR(b.err, hipGetLastError());
+    uint64_t* ks = b.incremental ? keys_bs : map->keys_s;   // a full build sorts straight into the persistent index
+    uint32_t* is = b.incremental ? idx_bs : map->idx_s;
+    if (const int rc = scratch_sort_pairs(b.sc, b.err, keys_b, ks, idx_b, is, m, 0, 63); rc != PCM_OK) return rc;
+    if (b.incremental) {
+      k_merge_old<<<cdiv(b.n_indexed, 256), 256, 0, b.stream>>>(map->keys_s, map->idx_s, b.n_indexed, keys_bs, m, map->keys_t, map->idx_t);
+      k_merge_new<<<cdiv(m, 256), 256, 0, b.stream>>>(map->keys_s, b.n_indexed, keys_bs, idx_bs, m, map->keys_t, map->idx_t);
+      PCM_HIPCK_ERR(b.err, hipGetLastError());
       map->keys_s.swap(map->keys_t);
       map->idx_s.swap(map->idx_t);
-      *n_inout = n;
-      RC(heads(n));   // the survivors' voxel heads and ranks
     }
-    // ---- 4. tables from the sorted index (capacity-managed arrays: a sliding map allocates nothing in the steady state) ----
-    uint32_t cap = 1024;
-    while (cap < 4ull * nbricks) cap <<= 1;
-    if (cap > kMaxBrickSlots) { *err = "too many occupied bricks"; return PCM_ERR_OUT_OF_RANGE; }
-    // the table only grows; a smaller table uses the front of the allocations
-    RC(map->bricks.reserve(stream, err, cap, cap));
-    RC(map->bmask.reserve(stream, err, 16 * (size_t)cap, 16 * (size_t)cap));
-    RC(map->bpref.reserve(stream, err, 16 * (size_t)cap, 16 * (size_t)cap));
-    RC(map->vox_start.reserve_keep(stream, err, (size_t)nvox + 1, headroom((size_t)nvox + 1), 0));
-    RC(map->pts.reserve_keep(stream, err, (size_t)n, headroom((size_t)n), 0));
-    PCM_HIPCK_ERR(err, hipMemsetAsync(map->bricks, 0xFF, sizeof(BrickSlot) * (size_t)cap, stream));
-    PCM_HIPCK_ERR(err, hipMemsetAsync(map->bmask, 0, sizeof(uint32_t) * 16 * (size_t)cap, stream));
-    PCM_HIPCK_ERR(err, hipMemsetAsync(map->bpref, 0, sizeof(uint16_t) * 16 * (size_t)cap, stream));
-    k_insert_bricks<<<cdiv(n, 256), 256, 0, stream>>>(map->keys_s, vrank, n, map->bricks, cap - 1);
-    PCM_HIPCK_ERR(err, hipGetLastError());
-    k_fill_voxels<<<cdiv(n, 256), 256, 0, stream>>>(map->keys_s, vflag, vrank, n, nvox, map->vox_start, map->bricks, map->bmask, cap - 1);
-    PCM_HIPCK_ERR(err, hipGetLastError());
-    k_finalize_bricks<<<cdiv(cap, 256), 256, 0, stream>>>(map->bricks, map->bmask, map->bpref, map->vox_start, cap);
-    PCM_HIPCK_ERR(err, hipGetLastError());
-    k_gather_points<<<cdiv(n, 256), 256, 0, stream>>>(d_pts, map->idx_s, map->keys_s, vrank, map->vox_start, n, map->pts);
-    PCM_HIPCK_ERR(err, hipGetLastError());
-    k_max_voxel_points<<<cdiv(nvox, 1024), 256, 0, stream>>>(map->vox_start, nvox, reinterpret_cast<unsigned int*>(d_flags + 2));
-    PCM_HIPCK_ERR(err, hipGetLastError());
-    PCM_HIPCK_ERR(err, hipMemcpyAsync(map->h_ctr, d_flags, kCtrInts * sizeof(int), hipMemcpyDeviceToHost, stream));   // complete at the synchronize below
-    if (map->gvox) { (void)hipStreamSynchronize(stream); map->gvox.release(); }   // rebuilt at its exact size below, when asked for
-    if (map->order && !keep_order) { (void)hipStreamSynchronize(stream); map->order.release(); }
-    if (keep_order) {   // a persistent copy of the input index of every map point (capacity-managed: a scan per registration re-uses it)
-      RC(map->order.reserve_keep(stream, err, (size_t)n, headroom((size_t)n), 0));
-      PCM_HIPCK_ERR(err, hipMemcpyAsync(map->order, map->idx_s, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice, stream));
-    }
-    if (want_gauss) {
-      RC(map->gvox.reserve(stream, err, (size_t)nvox + 1, (size_t)nvox + 1));
-      k_gauss_voxels<<<cdiv(nvox, 128), 128, 0, stream>>>(map->pts, map->vox_start, nvox, map->gvox);
-      PCM_HIPCK_ERR(err, hipGetLastError());
-    }
-    PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
-    map->max_voxel_points = (uint32_t)map->h_ctr[2];
-    map->cap = cap;
-    map->num_voxels = nvox;
-    map->num_bricks = nbricks;
-    map->num_points = n;
-    map->res = res;
-    map->inv_res = inv_res;
-    map->coord_mode = coord_mode;
-    map->index_n = n;
-    map->valid = true;
-    return PCM_OK;
-  }();
-  sc.release(stream);
-  if (lru_hazards) *lru_hazards = hazards;
+  }
+  map->index_n = 0;   // until this build is through
+  return PCM_OK;
+}
+
+// voxel heads and ranks of the first cnt sorted keys; the voxel and brick counts to the host (one read-back)
+static int voxel_heads(MapBuild& b, uint32_t cnt) {
+  TargetMap* map = b.map;
+  if (!b.vflag) {
+    if (b.sc.take(&b.vflag, b.n, b.err, "voxel head flags") || b.sc.take(&b.vrank, b.n, b.err, "voxel ranks")) return PCM_ERR_HIP;
+  }
+  PCM_HIPCK_ERR(b.err, hipMemsetAsync(b.d_flags + 8, 0, kBrickCountShards * sizeof(int), b.stream));
+  k_head_flags<<<cdiv(cnt, 256), 256, 0, b.stream>>>(map->keys_s, cnt, b.vflag, reinterpret_cast<unsigned int*>(b.d_flags + 8));
+  PCM_HIPCK_ERR(b.err, hipGetLastError());
+  if (const int rc = scratch_exclusive_scan(b.sc, b.err, b.vflag, b.vrank, (size_t)cnt); rc != PCM_OK) return rc;
+  k_count_voxels<<<1, 1, 0, b.stream>>>(b.vflag, b.vrank, cnt, b.d_flags);
+  PCM_HIPCK_ERR(b.err, hipMemcpyAsync(map->h_ctr, b.d_flags, kCtrInts * sizeof(int), hipMemcpyDeviceToHost, b.stream));   // one copy into pinned memory
+  PCM_HIPCK_ERR(b.err, hipStreamSynchronize(b.stream));
+  if (map->h_ctr[0]) { *b.err = "target point outside the +-2^20 voxel range (or not finite)"; return PCM_ERR_OUT_OF_RANGE; }
+  b.nvox = (uint32_t)map->h_ctr[4];
+  b.nbricks = 0;
+  for (int k = 0; k < kBrickCountShards; k++) b.nbricks += (uint32_t)map->h_ctr[8 + k];
+  return PCM_OK;
+}
+
+// permute the index inside the voxels (the heads and ranks stay valid: same keys at the same places)
+static int subvoxel_order(MapBuild& b) {
+  TargetMap* map = b.map;
+  uint64_t *k2 = nullptr, *k2s = nullptr;
+  int bits = 9;
+  while (bits < 41 && (1ull << (bits - 9)) < (unsigned long long)b.nvox) bits++;
+  if (b.sc.take(&k2, b.n, b.err, "sub-voxel keys") || b.sc.take(&k2s, b.n, b.err, "sub-voxel keys, sorted")) return PCM_ERR_HIP;
+  k_subvoxel_keys<<<cdiv(b.n, 256), 256, 0, b.stream>>>(b.d_pts, map->idx_s, b.vflag, b.vrank, b.n, b.inv_res, k2);
+  PCM_HIPCK_ERR(b.err, hipGetLastError());
+  if (const int rc = scratch_sort_pairs(b.sc, b.err, k2, k2s, map->idx_s.p, map->idx_t.p, b.n, 0, bits); rc != PCM_OK) return rc;
+  map->idx_s.swap(map->idx_t);
+  return PCM_OK;
+}
+
+// LRU eviction: keep the `keep` most recently touched voxels; log and index are compacted in place, b.n follows, and the
+// survivors get their voxel heads and ranks (a second read-back)
+static int evict_lru(MapBuild& b, uint32_t keep) {
+  TargetMap* map = b.map;
+  const uint32_t n = b.n, nvox = b.nvox;
+  uint32_t *vlast = nullptr, *vsorted = nullptr, *alive = nullptr, *pos = nullptr, *alive_s = nullptr, *pos_s = nullptr, *vfirst = nullptr;
+  float4* tmp_log = nullptr;
+  if (b.sc.take(&vlast, nvox, b.err, "voxel last-touch stamps") || b.sc.take(&vsorted, nvox, b.err, "sorted stamps")) return PCM_ERR_HIP;
+  if (b.sc.take(&vfirst, nvox, b.err, "voxel first points") || b.sc.take(&alive, n, b.err, "alive flags")) return PCM_ERR_HIP;
+  if (b.sc.take(&pos, n, b.err, "alive positions") || b.sc.take(&alive_s, n, b.err, "alive flags, index order")) return PCM_ERR_HIP;
+  if (b.sc.take(&pos_s, n, b.err, "alive positions, index order") || b.sc.take(&tmp_log, n, b.err, "compacted log")) return PCM_ERR_HIP;
+  k_voxel_firsts<<<cdiv(n, 256), 256, 0, b.stream>>>(b.vflag, b.vrank, n, vfirst);
+  k_voxel_last_from_firsts<<<cdiv(nvox, 256), 256, 0, b.stream>>>(b.d_pts, map->idx_s, vfirst, nvox, n, vlast);
+  PCM_HIPCK_ERR(b.err, hipGetLastError());
+  if (const int rc = scratch_sort_keys(b.sc, b.err, vlast, vsorted, nvox, 0, 32); rc != PCM_OK) return rc;
+  const uint32_t* d_cutoff = vsorted + (nvox - keep);   // the smallest surviving last-touch stamp, read on the device
+  if (b.incremental && b.n_indexed < n) {   // the batch = the log points from n_indexed on
+    k_lru_hazards<<<cdiv(nvox, 256), 256, 0, b.stream>>>(b.d_pts, map->idx_s, vfirst, vlast, nvox, n, b.d_pts + b.n_indexed, d_cutoff, reinterpret_cast<unsigned int*>(b.d_flags + 3));
+    PCM_HIPCK_ERR(b.err, hipGetLastError());
+  }
+  k_mark_alive_dev<<<cdiv(n, 256), 256, 0, b.stream>>>(map->idx_s, b.vflag, b.vrank, vlast, d_cutoff, n, alive);
+  PCM_HIPCK_ERR(b.err, hipGetLastError());
+  if (const int rc = scratch_exclusive_scan(b.sc, b.err, alive, pos, (size_t)n); rc != PCM_OK) return rc;
+  k_alive_sorted<<<cdiv(n, 256), 256, 0, b.stream>>>(map->idx_s, alive, n, alive_s);
+  if (const int rc = scratch_exclusive_scan(b.sc, b.err, alive_s, pos_s, (size_t)n); rc != PCM_OK) return rc;
+  k_compact_log<<<cdiv(n, 256), 256, 0, b.stream>>>(b.d_pts, alive, pos, n, tmp_log);
+  k_compact_index<<<cdiv(n, 256), 256, 0, b.stream>>>(map->keys_s, map->idx_s, alive, pos, pos_s, n, map->keys_t, map->idx_t);
+  k_count_alive<<<1, 1, 0, b.stream>>>(alive, pos, n, b.d_flags);
+  PCM_HIPCK_ERR(b.err, hipGetLastError());
+  PCM_HIPCK_ERR(b.err, hipMemcpyAsync(map->h_ctr, b.d_flags, kCtrInts * sizeof(int), hipMemcpyDeviceToHost, b.stream));
+  PCM_HIPCK_ERR(b.err, hipStreamSynchronize(b.stream));
+  b.n = (uint32_t)map->h_ctr[5];
+  b.hazards = (uint32_t)map->h_ctr[3];
+  PCM_HIPCK_ERR(b.err, hipMemcpyAsync(b.d_pts, tmp_log, sizeof(float4) * (size_t)b.n, hipMemcpyDeviceToDevice, b.stream));
+  map->keys_s.swap(map->keys_t);
+  map->idx_s.swap(map->idx_t);
+  *b.n_log = b.n;   // the log is compacted: its owner's count follows, whatever becomes of the rest of the build
+  return voxel_heads(b, b.n);
+}
+
+// tables from the sorted index (capacity-managed arrays: a sliding map allocates nothing in the steady state), the kept input
+// order and the Gauss voxels on request; ends with the build's last synchronisation
+static int fill_tables(MapBuild& b, bool keep_order, bool gauss) {
+  TargetMap* map = b.map;
+  hipStream_t stream = b.stream;
+  const uint32_t n = b.n, nvox = b.nvox;
+  uint32_t cap = 1024;
+  while (cap < 4ull * b.nbricks) cap <<= 1;
+  if (cap > kMaxBrickSlots) { *b.err = "too many occupied bricks"; return PCM_ERR_OUT_OF_RANGE; }
+  b.cap = cap;
+  // the table only grows; a smaller table uses the front of the allocations
+  if (const int rc = map->bricks.reserve(stream, b.err, cap, cap); rc != PCM_OK) return rc;
+  if (const int rc = map->bmask.reserve(stream, b.err, 16 * (size_t)cap, 16 * (size_t)cap); rc != PCM_OK) return rc;
+  if (const int rc = map->bpref.reserve(stream, b.err, 16 * (size_t)cap, 16 * (size_t)cap); rc != PCM_OK) return rc;
+  if (const int rc = map->vox_start.reserve_keep(stream, b.err, (size_t)nvox + 1, headroom((size_t)nvox + 1), 0); rc != PCM_OK) return rc;
+  if (const int rc = map->pts.reserve_keep(stream, b.err, (size_t)n, headroom((size_t)n), 0); rc != PCM_OK) return rc;
+  PCM_HIPCK_ERR(b.err, hipMemsetAsync(map->bricks, 0xFF, sizeof(BrickSlot) * (size_t)cap, stream));
+  PCM_HIPCK_ERR(b.err, hipMemsetAsync(map->bmask, 0, sizeof(uint32_t) * 16 * (size_t)cap, stream));
+  PCM_HIPCK_ERR(b.err, hipMemsetAsync(map->bpref, 0, sizeof(uint16_t) * 16 * (size_t)cap, stream));
+  k_insert_bricks<<<cdiv(n, 256), 256, 0, stream>>>(map->keys_s, b.vrank, n, map->bricks, cap - 1);
+  PCM_HIPCK_ERR(b.err, hipGetLastError());
+  k_fill_voxels<<<cdiv(n, 256), 256, 0, stream>>>(map->keys_s, b.vflag, b.vrank, n, nvox, map->vox_start, map->bricks, map->bmask, cap - 1);
+  PCM_HIPCK_ERR(b.err, hipGetLastError());
+  k_finalize_bricks<<<cdiv(cap, 256), 256, 0, stream>>>(map->bricks, map->bmask, map->bpref, map->vox_start, cap);
+  PCM_HIPCK_ERR(b.err, hipGetLastError());
+  k_gather_points<<<cdiv(n, 256), 256, 0, stream>>>(b.d_pts, map->idx_s, map->keys_s, b.vrank, map->vox_start, n, map->pts);
+  PCM_HIPCK_ERR(b.err, hipGetLastError());
+  k_max_voxel_points<<<cdiv(nvox, 1024), 256, 0, stream>>>(map->vox_start, nvox, reinterpret_cast<unsigned int*>(b.d_flags + 2));
+  PCM_HIPCK_ERR(b.err, hipGetLastError());
+  PCM_HIPCK_ERR(b.err, hipMemcpyAsync(map->h_ctr, b.d_flags, kCtrInts * sizeof(int), hipMemcpyDeviceToHost, stream));   // complete at the synchronize below
+  if (map->gvox) { (void)hipStreamSynchronize(stream); map->gvox.release(); }   // rebuilt at its exact size below, when asked for
+  if (map->order && !keep_order) { (void)hipStreamSynchronize(stream); map->order.release(); }
+  if (keep_order) {   // a persistent copy of the input index of every map point (capacity-managed: a scan per registration re-uses it)
+    if (const int rc = map->order.reserve_keep(stream, b.err, (size_t)n, headroom((size_t)n), 0); rc != PCM_OK) return rc;
+    PCM_HIPCK_ERR(b.err, hipMemcpyAsync(map->order, map->idx_s, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice, stream));
+  }
+  if (gauss) {
+    if (const int rc = map->gvox.reserve(stream, b.err, (size_t)nvox + 1, (size_t)nvox + 1); rc != PCM_OK) return rc;
+    k_gauss_voxels<<<cdiv(nvox, 128), 128, 0, stream>>>(map->pts, map->vox_start, nvox, map->gvox);
+    PCM_HIPCK_ERR(b.err, hipGetLastError());
+  }
+  PCM_HIPCK_ERR(b.err, hipStreamSynchronize(stream));
+  return PCM_OK;
+}
+
+// the map's scalar fields; from here on it is valid
+static int publish(const MapBuild& b) {
+  TargetMap* map = b.map;
+  map->max_voxel_points = (uint32_t)map->h_ctr[2];
+  map->cap = b.cap;
+  map->num_voxels = b.nvox;
+  map->num_bricks = b.nbricks;
+  map->num_points = b.n;
+  map->res = b.res;
+  map->inv_res = b.inv_res;
+  map->coord_mode = b.coord_mode;
+  map->index_n = b.n;
+  map->valid = true;
+  return PCM_OK;
+}
+
+// Build the voxel hash of the point log `d_pts` into `map`, or -- opt.n_indexed > 0: the first n_indexed log points are what
+// map->keys_s / idx_s index -- merge the points appended since.  Host syncs: voxel / brick counts (array sizes), once more after
+// an eviction, and the build's last.  After a failure the map is empty.
+int build_target_map(hipStream_t stream, float4* d_pts, uint32_t* n_inout, float res, int coord_mode, TargetMap* map, std::string* err, const MapBuildOptions& opt) {
+  const uint32_t n = *n_inout;
+  if (n == 0) { map->release(); *err = "empty target cloud"; return PCM_ERR_NO_INPUT; }
+  const bool incremental = opt.n_indexed > 0 && opt.n_indexed <= n && map->keys_s && map->idx_s && map->index_n == opt.n_indexed && map->res == res && map->coord_mode == coord_mode &&
+                           !opt.gauss && !opt.keep_order;
+  map->valid = false;
+  if (map->h_ctr.reserve(stream, err, kCtrInts, kCtrInts) != PCM_OK) return PCM_ERR_HIP;
+  int rc = PCM_OK;
+  if (incremental) {   // everything an update with eviction takes, rounded up: 24 B per new point, 52 B per log point, sort / scan temporaries
+    const size_t need = 24 * (size_t)(n - opt.n_indexed) + 56 * (size_t)n + ((size_t)16 << 20);
+    rc = map->arena.reserve(stream, err, need, need + need / 4);
+  }
+  MapBuild b(stream, err, map, d_pts, n_inout, incremental ? map->arena.p : nullptr, incremental ? map->arena.cap : 0);
+  b.n = n; b.n_indexed = opt.n_indexed; b.incremental = incremental; b.res = res; b.coord_mode = coord_mode;
+  // ivox3d.h:67  inv_resolution_ = 1.0 / resolution_ (float);  pcl::VoxelGrid: inverse_leaf_size_ = 1 / leaf_size_ in float
+  b.inv_res = coord_mode == COORD_FLOOR_MUL ? 1.0f / res : (float)(1.0 / res);
+  if (rc == PCM_OK) rc = clear_counters(b);
+  if (rc == PCM_OK) rc = sort_index(b);
+  if (rc == PCM_OK) rc = voxel_heads(b, b.n);
+  if (rc == PCM_OK && opt.subsort && !incremental) rc = subvoxel_order(b);
+  if (rc == PCM_OK && opt.capacity_voxels > 1 && b.nvox > opt.capacity_voxels - 1) rc = evict_lru(b, opt.capacity_voxels - 1);
+  if (rc == PCM_OK) rc = fill_tables(b, opt.keep_order, opt.gauss);
+  if (rc == PCM_OK) rc = publish(b);
+  b.sc.release();
+  if (opt.lru_hazards) *opt.lru_hazards = b.hazards;
   if (rc != PCM_OK) map->release();
   return rc;
-#undef RC
 }
 
 // Re-order the scans of a whole batch along a Morton (Z-order) curve of their WORLD
@@ -778,35 +779,27 @@ __global__ void k_map_append(const float4* __restrict__ world, const uint32_t* _
 
 int map_incremental_device(hipStream_t stream, const float4* scan, bool scan_reordered, uint32_t n, const LioStateD& s, float filter_size_map, const uint32_t* nn,
                            const float4* map_pts, uint32_t seq0, float4* out_append, uint32_t* num_added, std::string* err) {
+  DevScratch sc(stream);
   float4* world = nullptr;
   uint32_t* buf = nullptr;   // f1, f2, p1, p2
-  void* tmp = nullptr;
-  size_t tmp_bytes = 0;
   uint32_t tails[4] = {0, 0, 0, 0};
-  const int rc = [&]() -> int {
-    PCM_HIPCK_ERR(err, hipMallocAsync(&world, sizeof(float4) * n, stream));
-    PCM_HIPCK_ERR(err, hipMallocAsync(&buf, sizeof(uint32_t) * 4 * (size_t)n, stream));
-    uint32_t *f1 = buf, *f2 = buf + n, *p1 = buf + 2 * (size_t)n, *p2 = buf + 3 * (size_t)n;
-    k_map_filter<<<cdiv(n, 256), 256, 0, stream>>>(scan, n, s, filter_size_map, nn, map_pts, world, f1, f2, scan_reordered ? 1 : 0);
-    PCM_HIPCK_ERR(err, hipGetLastError());
-    PCM_HIPCK_ERR(err, rocprim::exclusive_scan(nullptr, tmp_bytes, f1, p1, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-    PCM_HIPCK_ERR(err, hipMallocAsync(&tmp, tmp_bytes, stream));
-    PCM_HIPCK_ERR(err, rocprim::exclusive_scan(tmp, tmp_bytes, f1, p1, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-    PCM_HIPCK_ERR(err, rocprim::exclusive_scan(tmp, tmp_bytes, f2, p2, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-    PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[0], f1 + (n - 1), 4, hipMemcpyDeviceToHost, stream));
-    PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[1], p1 + (n - 1), 4, hipMemcpyDeviceToHost, stream));
-    PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[2], f2 + (n - 1), 4, hipMemcpyDeviceToHost, stream));
-    PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[3], p2 + (n - 1), 4, hipMemcpyDeviceToHost, stream));
-    PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
-    const uint32_t n1 = tails[0] + tails[1], n2 = tails[2] + tails[3];
-    k_map_append<<<cdiv(n, 256), 256, 0, stream>>>(world, f1, f2, p1, p2, n, n1, seq0, out_append);
-    PCM_HIPCK_ERR(err, hipGetLastError());
-    PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
-    *num_added = n1 + n2;
-    return PCM_OK;
-  }();
-  sfree(stream, world); sfree(stream, buf); sfree(stream, tmp);
-  return rc;
+  if (sc.take(&world, n, err, "world points") || sc.take(&buf, 4 * (size_t)n, err, "verdicts")) return PCM_ERR_HIP;
+  uint32_t *f1 = buf, *f2 = buf + n, *p1 = buf + 2 * (size_t)n, *p2 = buf + 3 * (size_t)n;
+  k_map_filter<<<cdiv(n, 256), 256, 0, stream>>>(scan, n, s, filter_size_map, nn, map_pts, world, f1, f2, scan_reordered ? 1 : 0);
+  PCM_HIPCK_ERR(err, hipGetLastError());
+  if (const int rc = scratch_exclusive_scan(sc, err, f1, p1, (size_t)n); rc != PCM_OK) return rc;
+  if (const int rc = scratch_exclusive_scan(sc, err, f2, p2, (size_t)n); rc != PCM_OK) return rc;
+  PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[0], f1 + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+  PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[1], p1 + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+  PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[2], f2 + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+  PCM_HIPCK_ERR(err, hipMemcpyAsync(&tails[3], p2 + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+  PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
+  const uint32_t n1 = tails[0] + tails[1], n2 = tails[2] + tails[3];
+  k_map_append<<<cdiv(n, 256), 256, 0, stream>>>(world, f1, f2, p1, p2, n, n1, seq0, out_append);
+  PCM_HIPCK_ERR(err, hipGetLastError());
+  PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
+  *num_added = n1 + n2;
+  return PCM_OK;
 }
 
 int load_points_to_device(hipStream_t stream, const void* points, size_t n, size_t stride, int memory, uint32_t seq0, float4* d_out, std::string* err) {
