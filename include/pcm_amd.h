@@ -438,6 +438,52 @@ int pcm_lio_frame_end(pcm_ctx *ctx, const pcm_lio_state *state, float filter_siz
 /* the current source scan, x y z per point in its stored order (tests: the scan pcm_lio_frame_begin produced); out may be NULL */
 int pcm_get_source(pcm_ctx *ctx, float *out_xyz, size_t capacity_points, size_t *n);
 
+/* The outputs of a frame and the saved map: the last block of LaserMapping::Run (jueying_lio/src/laser_mapping.cc:361-385) and
+ * Finish (:887-900), on the records pcm_lio_frame_begin / pcm_lio_frame_begin_cloud left on the device.  Every output record is
+ * 16 bytes, (x, y, z, intensity) as floats; every transform runs in double in Eigen's operation order and each coordinate is cast
+ * to float (`po->x = p_global(0)`, :860-862).  `state`: the state the reference would publish with (state_point_).
+ *   pcm_lio_frame_world   PublishFrameWorld's cloud (:747-762): dense = 1 every record of scan_undistort_ through
+ *                         PointBodyToWorld(const PointType*, ...) (:855-864); dense = 0 scan_down_world_ as MapIncremental leaves it
+ *                         (:540), in the order of the caller's scan (pcm_get_source's), whatever cfg.sort_source does inside
+ *   pcm_lio_frame_body    PublishFrameBody (:794-808): PointBodyLidarToIMU (:877-885) over scan_undistort_
+ *   pcm_lio_frame_effect  PublishFrameEffectWorld (:810-823): the points that gave a row to the LAST ObsModel call (corr_pts_,
+ *                         :641-655), in scan order, through PointBodyToWorld(const V3F&, ...) (:866-875): intensity = |z| of the
+ *                         float written.  *n equals that call's n_eff (pcm_obs_result.n_eff, pcm_lio_update_result.n_eff_last).
+ *                         Under PCM_FLAG_LIO_REFERENCE_SEMANTICS the points are those with point_selected_surf_ set; otherwise
+ *                         those with a plane and |p_body| > 81 pd2^2 at the state of that call.  No such call on this frame's
+ *                         scan: PCM_ERR_NO_INPUT.
+ *   pcm_lio_map_append    `*pcl_wait_save_ += *laserCloudWorld` (:777) straight into a grow-only device log (capacity x 1.5), and
+ *                         the chunk counter of :779-790: scan_wait_num goes up by one; when pcd_save_interval > 0, the log is not
+ *                         empty and scan_wait_num >= pcd_save_interval, chunk_ready = 1 and pcd_index is the k of the reference's
+ *                         jueying_<k>.pcd: the caller fetches the log (pcm_lio_map_get / _export), writes the file and calls
+ *                         pcm_lio_map_clear, as :787-789 do.  pcd_save_interval <= 0 never reports a chunk (:781).  The call
+ *                         queues its work and returns; info may be NULL.
+ *   pcm_lio_map_get       records [first, first + count) of the log
+ *   pcm_lio_map_clear     pcl_wait_save_->clear(); scan_wait_num = 0 (:788-789); pcd_index and the buffer stay
+ *   pcm_lio_map_export    Finish followed by the consumer of jueying.pcd (src/tool/pcd2map/src/pcd2map.cpp:60-72): leaf_size > 0
+ *                         runs pcm_voxel_downsample_large over the log (more than 2^31 - 1 points: PCM_ERR_OUT_OF_RANGE);
+ *                         z_min <= z_max then keeps, in order, the records with finite x, y, z and z_min <= z <= z_max
+ *                         (pcl::PassThrough, setFilterLimitsNegative(false); at most 2^32 - 1 records enter it).  leaf_size 0 with
+ *                         z_min > z_max: the log as it is.  No file is written.
+ * Validity: the frame's records live in the context's pre-processing scratch.  Any later call on the context that takes that
+ * scratch (pcm_voxel_downsample, pcm_livox_filter, pcm_lidar_filter, pcm_undistort, a frame that fails) or replaces the source
+ * (pcm_set_source, pcm_clear_source, pcm_swap_source_and_target) ends them: the three frame clouds and the append then return
+ * PCM_ERR_NO_INPUT and pcm_last_error names that call.  The log is not affected.
+ * Buffers: `out` in host or device memory (`memory`); NULL returns the count in *n only; a capacity below the count returns
+ * PCM_ERR_INVALID_ARGUMENT with the count in *n and writes nothing.  The calls with `out` wait for the stream. */
+typedef struct pcm_lio_map_info {
+  uint64_t points, capacity, frames_appended, growths;   /* growths: allocations of the log, the first included */
+  int32_t scan_wait_num, pcd_index, chunk_ready, reserved;
+} pcm_lio_map_info;
+int pcm_lio_frame_world(pcm_ctx *ctx, const pcm_lio_state *state, int dense, void *out, size_t capacity_points, int memory, size_t *n);
+int pcm_lio_frame_body(pcm_ctx *ctx, const pcm_lio_state *state, void *out, size_t capacity_points, int memory, size_t *n);
+int pcm_lio_frame_effect(pcm_ctx *ctx, const pcm_lio_state *state, void *out, size_t capacity_points, int memory, size_t *n);
+int pcm_lio_map_append(pcm_ctx *ctx, const pcm_lio_state *state, int dense, int pcd_save_interval, pcm_lio_map_info *info);
+int pcm_lio_map_info_get(pcm_ctx *ctx, pcm_lio_map_info *info);
+int pcm_lio_map_get(pcm_ctx *ctx, size_t first, size_t count, void *out, int memory);
+int pcm_lio_map_clear(pcm_ctx *ctx);
+int pcm_lio_map_export(pcm_ctx *ctx, float leaf_size, double z_min, double z_max, void *out, size_t capacity_points, int memory, size_t *n);
+
 /* esekf::update_iterated_dyn_share_modified of jueying_lio (IKFoM_toolkit/esekfom/esekfom.hpp:1526-1834, called at
  * laser_mapping.cc:347) for state_ikfom, on the device: every ObsModel call of the loop, the manifold algebra (SO3 / S2 boxplus and
  * boxminus, A_matrix, S2_Nx_yy, S2_Mx), the two 23 x 23 inverses per iteration and the closing covariance re-projection.  One call per

@@ -1174,7 +1174,63 @@ public:
   }
   bool EkfInited() const { return ekf_inited_; }
 
+  // ---- the last block of Run (laser_mapping.cc:361-385) and Finish (:887-900) ----------------------------------------------------------
+  // PointT: pcl::PointXYZINormal (PointType of jueying_lio).  The other fields are what the reference leaves in a fresh cloud:
+  // data[3] = 1, normals and curvature 0.  x: the state the reference publishes with (state_point_ = kf_.get_x()).
+  // PublishFrameWorld (:747-792): the cloud (dense_pub_en: scan_undistort_, else scan_down_world_); with pcd_save_en it is also appended
+  // to the saved map on the device.  Returns true when the reference would write jueying_<*pcd_index>.pcd now: fetch the map with
+  // finish(), write it, then clearSavedMap().
+  template <typename PointT>
+  bool publishFrameWorld(const pcm_lio_filter_state& x, bool dense_pub_en, pcl::PointCloud<PointT>* cloud, bool pcd_save_en = false, int pcd_save_interval = -1,
+                         int* pcd_index = nullptr) {
+    const pcm_lio_state st = poseOf(x);
+    if (cloud) fetch(cloud, [&](void* out, size_t cap, size_t* n) { return pcm_lio_frame_world(ctx_, &st, dense_pub_en ? 1 : 0, out, cap, PCM_MEM_HOST, n); }, "pcm_lio_frame_world");
+    if (!pcd_save_en) return false;
+    pcm_lio_map_info info{};
+    if (pcm_lio_map_append(ctx_, &st, dense_pub_en ? 1 : 0, pcd_save_interval, &info) != PCM_OK) throw std::runtime_error(std::string("pcm_lio_map_append: ") + pcm_last_error(ctx_));
+    if (pcd_index) *pcd_index = info.pcd_index;
+    return info.chunk_ready != 0;
+  }
+  // PublishFrameBody (:794-808)
+  template <typename PointT>
+  void publishFrameBody(const pcm_lio_filter_state& x, pcl::PointCloud<PointT>* cloud) {
+    const pcm_lio_state st = poseOf(x);
+    fetch(cloud, [&](void* out, size_t cap, size_t* n) { return pcm_lio_frame_body(ctx_, &st, out, cap, PCM_MEM_HOST, n); }, "pcm_lio_frame_body");
+  }
+  // PublishFrameEffectWorld (:810-823): the points of the last ObsModel call's rows, intensity = |z|
+  template <typename PointT>
+  void publishFrameEffectWorld(const pcm_lio_filter_state& x, pcl::PointCloud<PointT>* cloud) {
+    const pcm_lio_state st = poseOf(x);
+    fetch(cloud, [&](void* out, size_t cap, size_t* n) { return pcm_lio_frame_effect(ctx_, &st, out, cap, PCM_MEM_HOST, n); }, "pcm_lio_frame_effect");
+  }
+  // Finish: the cloud of jueying.pcd (false: the saved map is empty, the reference writes no file).  leaf_size > 0 and
+  // z_min <= z_max add the filters of src/tool/pcd2map (VoxelGrid, then PassThrough on z).
+  template <typename PointT>
+  bool finish(pcl::PointCloud<PointT>* cloud, float leaf_size = 0.f, double z_min = 1.0, double z_max = 0.0) {
+    fetch(cloud, [&](void* out, size_t cap, size_t* n) { return pcm_lio_map_export(ctx_, leaf_size, z_min, z_max, out, cap, PCM_MEM_HOST, n); }, "pcm_lio_map_export");
+    pcm_lio_map_info info{};
+    return pcm_lio_map_info_get(ctx_, &info) == PCM_OK && info.points > 0;
+  }
+  void clearSavedMap() { pcm_lio_map_clear(ctx_); }   // pcl_wait_save_->clear(); scan_wait_num = 0  (:788-789)
+
 private:
+  // count, then the (x, y, z, intensity) records into a cloud of PointT
+  template <typename PointT, typename Call>
+  void fetch(pcl::PointCloud<PointT>* cloud, Call call, const char* what) {
+    size_t n = 0;
+    int rc = call(nullptr, 0, &n);
+    std::vector<float> rec(4 * n);
+    if (rc == PCM_OK && n) rc = call(rec.data(), n, &n);
+    if (rc != PCM_OK) throw std::runtime_error(std::string(what) + ": " + pcm_last_error(ctx_));
+    cloud->points.resize(n);
+    for (size_t i = 0; i < n; i++) {
+      PointT p{};
+      p.x = rec[4 * i]; p.y = rec[4 * i + 1]; p.z = rec[4 * i + 2]; p.data[3] = 1.f;
+      p.intensity = rec[4 * i + 3];
+      p.normal_x = p.normal_y = p.normal_z = 0.f; p.curvature = 0.f;
+      cloud->points[i] = p;
+    }
+  }
   static pcm_lio_state poseOf(const pcm_lio_filter_state& x) {
     pcm_lio_state st{};
     for (int a = 0; a < 4; a++) { st.rot[a] = x.rot[a]; st.off_R[a] = x.off_R[a]; }

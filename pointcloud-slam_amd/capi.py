@@ -34,6 +34,8 @@ SYMBOLS = [
     "pcm_lio_default_update_params", "pcm_lio_update", "pcm_lio_update_trace",
     "pcm_lio_default_imu_state", "pcm_lio_imu_init", "pcm_lio_propagate",
     "pcm_share_target", "pcm_target_share_count",
+    "pcm_lio_frame_world", "pcm_lio_frame_body", "pcm_lio_frame_effect", "pcm_lio_map_append", "pcm_lio_map_info_get", "pcm_lio_map_get",
+    "pcm_lio_map_clear", "pcm_lio_map_export",
 ]
 
 PCM_ABI_VERSION = 3   # include/pcm_amd.h
@@ -45,6 +47,9 @@ PCM_FLAG_NEIGHBOUR_LISTS = 16           # static targets: per-voxel candidate li
 PCM_FLAG_NO_NEIGHBOUR_LISTS = 64        # never: the tile kernel serves every pass
 PCM_FLAG_REFERENCE_KNN_ORDER = 32      # neighbours in the order of libstdc++'s std::nth_element (the reference's), slower kernel
 PCM_FLAG_LIO_REFERENCE_SEMANTICS = 4   # pcm_obs_model keeps LaserMapping's per-point members across calls and scans
+PCM_ERR_INVALID_ARGUMENT = -1
+PCM_ERR_NO_INPUT = -2
+PCM_ERR_OUT_OF_RANGE = -5
 PCM_ERR_NOT_CONVERGED = -6
 PCM_ERR_INTERNAL = -7
 PCM_ERR_TOO_FEW_FEATURES = -8          # LOAM: not enough corner / surf features, pose left as given
@@ -82,6 +87,11 @@ class PcmResult(C.Structure):
 
 class PcmLioState(C.Structure):
     _fields_ = [("rot", C.c_double * 4), ("pos", C.c_double * 3), ("off_R", C.c_double * 4), ("off_T", C.c_double * 3)]
+
+
+class PcmLioMapInfo(C.Structure):   # pcm_lio_map_info
+    _fields_ = [("points", C.c_uint64), ("capacity", C.c_uint64), ("frames_appended", C.c_uint64), ("growths", C.c_uint64),
+                ("scan_wait_num", C.c_int32), ("pcd_index", C.c_int32), ("chunk_ready", C.c_int32), ("reserved", C.c_int32)]
 
 
 class PcmObsResult(C.Structure):
@@ -450,5 +460,13 @@ def load_library():
     L.pcm_lio_default_imu_state.restype = None
     L.pcm_lio_imu_init.argtypes = [C.POINTER(PcmLioImuState), vp, i32, C.POINTER(PcmLioFilterState), vp]
     L.pcm_lio_propagate.argtypes = [vp, C.POINTER(PcmLioImuState), vp, i32, C.c_double, C.c_double, C.POINTER(PcmLioFilterState), vp, vp, i32, C.POINTER(C.c_int32)]
+    L.pcm_lio_frame_world.argtypes = [vp, C.POINTER(PcmLioState), i32, vp, sz, i32, C.POINTER(sz)]
+    L.pcm_lio_frame_body.argtypes = [vp, C.POINTER(PcmLioState), vp, sz, i32, C.POINTER(sz)]
+    L.pcm_lio_frame_effect.argtypes = [vp, C.POINTER(PcmLioState), vp, sz, i32, C.POINTER(sz)]
+    L.pcm_lio_map_append.argtypes = [vp, C.POINTER(PcmLioState), i32, i32, C.POINTER(PcmLioMapInfo)]
+    L.pcm_lio_map_info_get.argtypes = [vp, C.POINTER(PcmLioMapInfo)]
+    L.pcm_lio_map_get.argtypes = [vp, sz, sz, vp, i32]
+    L.pcm_lio_map_clear.argtypes = [vp]
+    L.pcm_lio_map_export.argtypes = [vp, C.c_float, C.c_double, C.c_double, vp, sz, i32, C.POINTER(sz)]
     _LIB = L
     return L

@@ -296,15 +296,9 @@ __global__ void __launch_bounds__(256, 5) k_linearize(const PairDesc* __restrict
   bool search = false;  // lanes whose query voxel lies inside the key range of the table
   if (live) {
     p = gload4(d.src.pts + i);
-    pn_body = pcm_sqrtf_rn(p.x * p.x + p.y * p.y + p.z * p.z);   // p_body.norm() of the 81 pd2^2 test (:631), kept instead of the point
+    pn_body = lio_body_norm(p);   // p_body.norm() of the 81 pd2^2 test (:631), kept instead of the point
     if (LIO) {   // p_w = R_wl * p_body + t_wl with R_wl a float quaternion (Eigen _transformVector)  laser_mapping.cc:602-612
-      const float qx = d.lio.q_wl[0], qy = d.lio.q_wl[1], qz = d.lio.q_wl[2], qw = d.lio.q_wl[3];
-      float uv[3] = {qy * p.z - qz * p.y, qz * p.x - qx * p.z, qx * p.y - qy * p.x};
-      uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-      const float c3[3] = {qy * uv[2] - qz * uv[1], qz * uv[0] - qx * uv[2], qx * uv[1] - qy * uv[0]};
-      q[0] = (p.x + qw * uv[0] + c3[0]) + d.lio.t_wl[0];
-      q[1] = (p.y + qw * uv[1] + c3[1]) + d.lio.t_wl[1];
-      q[2] = (p.z + qw * uv[2] + c3[2]) + d.lio.t_wl[2];
+      lio_world_point(d.lio.q_wl, d.lio.t_wl, p, q);
     } else {
       transform(P, p, q);
     }
@@ -601,13 +595,8 @@ __global__ void __launch_bounds__(256, 5) k_linearize(const PairDesc* __restrict
           aux[0] = res;
           aux[1] = sel ? 1.f : 0.f;
         } else {
-          sel = !(pl.x != pl.x);
           if (do_search) gstore4(d.planes + i, pl);                        // plane_coef_[i]; the residual test is re-evaluated every call
-          if (sel) {
-            res = pl.x * q[0] + pl.y * q[1] + pl.z * q[2] + pl.w;
-            const float pn = pn_body;
-            sel = pn > 81.f * res * res;
-          }
+          sel = lio_row_selected(pl, q, pn_body, res);
         }
         {
           const float pd2 = res;

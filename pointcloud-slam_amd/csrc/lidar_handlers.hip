@@ -334,7 +334,7 @@ int pcm_lidar_filter(pcm_ctx* c, const void* points, size_t n, int memory, const
   const size_t cap = capacity_points < n ? capacity_points : n;
   const size_t o_out = memory == PCM_MEM_HOST ? up256(n * desc->stride_bytes) : 0, o_scr = o_out + (out_memory == PCM_MEM_HOST ? up256(48 * (cap ? cap : 1)) : 0);
   const size_t need = o_scr + lidar_filter_scratch_bytes(n);
-  rc = c->pre_arena.reserve(c, need, need + need / 4);
+  rc = take_pre_arena(c, need, "pcm_lidar_filter");
   if (rc != PCM_OK) return rc;
   char* A = c->pre_arena;
   const void* d_in = points;

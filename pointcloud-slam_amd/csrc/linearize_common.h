@@ -51,6 +51,29 @@ __device__ inline void transform(const PoseF& P, const float4& p, float (&q)[3])
   for (int a = 0; a < 3; a++) q[a] = (P.r[a * 3 + 0] * p.x + P.r[a * 3 + 1] * p.y) + P.r[a * 3 + 2] * p.z + P.t[a];
 }
 
+// ---- the LIO ObsModel's view of one scan point, shared by the search kernel (kernels.hip) and the effect cloud (lio_outputs.hip)
+// p_body.norm() of the 81 pd2^2 test  laser_mapping.cc:631
+__device__ inline float lio_body_norm(const float4& p) { return pcm_sqrtf_rn(p.x * p.x + p.y * p.y + p.z * p.z); }
+// p_w = R_wl * p_body + t_wl with R_wl a float quaternion (Eigen _transformVector)  laser_mapping.cc:602-612
+__device__ inline void lio_world_point(const float* q_wl, const float* t_wl, const float4& p, float (&q)[3]) {
+  const float qx = q_wl[0], qy = q_wl[1], qz = q_wl[2], qw = q_wl[3];
+  float uv[3] = {qy * p.z - qz * p.y, qz * p.x - qx * p.z, qx * p.y - qy * p.x};
+  uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
+  const float c3[3] = {qy * uv[2] - qz * uv[1], qz * uv[0] - qx * uv[2], qx * uv[1] - qy * uv[0]};
+  q[0] = (p.x + qw * uv[0] + c3[0]) + t_wl[0];
+  q[1] = (p.y + qw * uv[1] + c3[1]) + t_wl[1];
+  q[2] = (p.z + qw * uv[2] + c3[2]) + t_wl[2];
+}
+// the default semantics' row test: a plane was found (x not NaN) and |p_body| > 81 pd2^2 at the world point q (:627-631); res = pd2
+__device__ inline bool lio_row_selected(const float4& pl, const float (&q)[3], float pn_body, float& res) {
+  bool sel = !(pl.x != pl.x);
+  if (sel) {
+    res = pl.x * q[0] + pl.y * q[1] + pl.z * q[2] + pl.w;
+    sel = pn_body > 81.f * res * res;
+  }
+  return sel;
+}
+
 // running 5-best list: ascending distance, equal distances keep visit order
 struct Best {
   float d[K];

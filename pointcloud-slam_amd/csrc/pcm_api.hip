@@ -14,9 +14,8 @@ using namespace pcm;
 
 namespace {
 
-// room for `bytes` in the grow-only device scratch the pre-processing operators share (a quarter of headroom: no allocation per
-// frame in the steady state); the contents do not survive a growth
-int pre_scratch(pcm_ctx* c, size_t bytes) { return c->pre_arena.reserve(c, bytes, bytes + bytes / 4); }
+// the scratch the pre-processing operators share (pcm_host.h: take_pre_arena)
+int pre_scratch(pcm_ctx* c, size_t bytes, const char* who) { return take_pre_arena(c, bytes, who); }
 
 // the same for the records + partial sums of a GICP-BFGS correspondence set of m pairs
 int bfgs_scratch(pcm_ctx* c, size_t m) {
@@ -280,6 +279,8 @@ int pcm_set_source(pcm_ctx* c, const void* points, size_t n, size_t stride_bytes
   CHECK_CTX(c);
   if (tag != 0 && tag == c->src.tag && c->src.n == n) return PCM_OK;  // fast_gicp_impl.hpp:72-74
   int rc = set_cloud(c, &c->src, points, n, stride_bytes, memory, tag, true);
+  c->lio_frame.take("pcm_set_source");   // the source is no frame's scan any more
+  c->lio_last_obs.valid = false;
   c->user_cov_src.clear();   // source_covs_.clear()  fast_gicp_impl.hpp:78
   c->src_sorted = false;
   c->lio_planes_valid = false;
@@ -293,6 +294,8 @@ int pcm_swap_source_and_target(pcm_ctx* c) {
   if (c->tg.shared()) return refuse_shared(c, "pcm_swap_source_and_target");
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   c->src.swap(c->tg->tgt);
+  c->lio_frame.take("pcm_swap_source_and_target");
+  c->lio_last_obs.valid = false;
   std::swap(c->user_cov_src, c->tg->user_cov);   // source_covs_.swap(target_covs_)  fast_gicp_impl.hpp:55
   c->tg->map.valid = false;
   c->srcmap.valid = false;
@@ -345,6 +348,8 @@ int pcm_target_share_count(pcm_ctx* c) {
 int pcm_clear_source(pcm_ctx* c) {
   CHECK_CTX(c);
   c->src.n = 0; c->src.tag = 0; c->src_sorted = false; c->srcmap.valid = false;
+  c->lio_frame.take("pcm_clear_source");
+  c->lio_last_obs.valid = false;
   return PCM_OK;
 }
 
@@ -414,7 +419,7 @@ int pcm_undistort(pcm_ctx* c, void* points, size_t n, size_t stride, size_t time
   for (int a = 0; a < 4; a++) { s.rot[a] = st->rot[a]; s.off_R[a] = st->off_R[a]; }
   for (int a = 0; a < 3; a++) { s.pos[a] = st->pos[a]; s.off_T[a] = st->off_T[a]; }
   const size_t need = up256(sizeof(pcm_imu_pose) * (size_t)npose) + (memory == PCM_MEM_HOST ? up256(n * stride) : 0);
-  int rc = pre_scratch(c, need);
+  int rc = pre_scratch(c, need, "pcm_undistort");
   if (rc != PCM_OK) return rc;
   pcm_imu_pose* d_poses = reinterpret_cast<pcm_imu_pose*>(c->pre_arena.p);
   PCM_HIPCK(c, hipMemcpyAsync(d_poses, poses, sizeof(pcm_imu_pose) * (size_t)npose, hipMemcpyHostToDevice, c->stream));
@@ -585,7 +590,7 @@ int pcm_voxel_downsample(pcm_ctx* c, const void* points, size_t n, size_t stride
   if (n == 0) return PCM_OK;
   PCM_HIPCK(c, hipSetDevice(c->device));
   const size_t io = memory == PCM_MEM_HOST ? 2 * up256(n * stride) : 0;
-  int rc = pre_scratch(c, voxel_downsample_scratch_bytes(n) + io);
+  int rc = pre_scratch(c, voxel_downsample_scratch_bytes(n) + io, "pcm_voxel_downsample");
   if (rc != PCM_OK) return rc;
   const void* src = points;
   void* dst = out;
@@ -635,7 +640,7 @@ int pcm_livox_filter(pcm_ctx* c, const void* custom_points, size_t n, int memory
   if (n == 0) return PCM_OK;
   PCM_HIPCK(c, hipSetDevice(c->device));
   const size_t io = memory == PCM_MEM_HOST ? up256(n * 20) + up256(n * 48) : 0;
-  int rc = pre_scratch(c, livox_filter_scratch_bytes(n) + io);
+  int rc = pre_scratch(c, livox_filter_scratch_bytes(n) + io, "pcm_livox_filter");
   if (rc != PCM_OK) return rc;
   const void* src = custom_points;
   void* dst = out;
@@ -864,6 +869,7 @@ int pcm_obs_model(pcm_ctx* c, const pcm_lio_state* s, int extrinsic_est_en, int 
   PCM_HIPCK(c, hipMemcpyAsync(sums, w->d_sums, sizeof(double) * kLioStride, hipMemcpyDeviceToHost, st));
   PCM_HIPCK(c, hipStreamSynchronize(st));
   if (rematch) c->lio_planes_valid = true;
+  c->lio_last_obs.set(L.q_wl, L.t_wl);   // the state of this call: what the effect cloud's 81 pd2^2 test is evaluated at
   int t = 0;
   for (int a = 0; a < 12; a++) for (int b = a; b < 12; b++) { out->HTH[a * 12 + b] = sums[t]; out->HTH[b * 12 + a] = sums[t]; t++; }
   for (int a = 0; a < 12; a++) out->HTh[a] = sums[78 + a];
@@ -970,6 +976,12 @@ int pcm_lio_update(pcm_ctx* c, const pcm_lio_update_params* prm, pcm_lio_filter_
   const iekf::Ctl& ctl = h->b.ctl;
   c->lio_planes_valid = true;   // the first call of the loop always matches
   c->lio_upd_calls = ctl.iterations;
+  c->lio_last_obs.valid = false;
+  if (ctl.iterations >= 1 && ctl.iterations <= iekf::kMaxCalls) {   // the state of the last executed ObsModel call
+    iekf::PoseF Ll{};
+    iekf::pose_of(h->b.tr[ctl.iterations - 1].x, &Ll);
+    c->lio_last_obs.set(Ll.q_wl, Ll.t_wl);
+  }
   std::memcpy(x, &h->b.x, sizeof(iekf::State));
   std::memcpy(P, h->b.P, sizeof(double) * iekf::NN);
   std::memset(res, 0, sizeof(*res));
@@ -1091,7 +1103,7 @@ int pcm_lio_frame_begin(pcm_ctx* c, const void* custom_points, size_t n, int mem
   // steady state makes no allocation.  The raw message is the only host -> device copy of the frame.
   const size_t o_raw = 0, o_flt = o_raw + up256(n * 20), o_ds = o_flt + up256(n * 48), o_pose = o_ds + up256(n * 48);
   const size_t o_scr = o_pose + up256(sizeof(pcm_imu_pose) * (size_t)std::max(npose, 1));
-  int rc = pre_scratch(c, o_scr + std::max(livox_filter_scratch_bytes(n), voxel_downsample_scratch_bytes(n)));
+  int rc = pre_scratch(c, o_scr + std::max(livox_filter_scratch_bytes(n), voxel_downsample_scratch_bytes(n)), "pcm_lio_frame_begin");
   if (rc != PCM_OK) return rc;
   char* A = c->pre_arena;
   const void* d_raw = custom_points;
@@ -1136,6 +1148,8 @@ int pcm_lio_frame_begin(pcm_ctx* c, const void* custom_points, size_t n, int mem
   c->srcmap.valid = false;
   c->src_cov_valid = false;
   c->user_cov_src.clear();
+  c->lio_frame.set(A + o_flt, n_flt, d_scan, n_ds);   // scan_undistort_ and scan_down_body_, for the frame outputs (lio_outputs.hip)
+  c->lio_last_obs.valid = false;
   *n_scan = n_ds;
   return PCM_OK;
 }
@@ -1156,7 +1170,7 @@ int pcm_lio_frame_begin_cloud(pcm_ctx* c, const void* points, size_t n, int memo
   // frame arena: [raw cloud | filtered records, later the down-sampled ones | time-sorted records | IMU poses | scratch of the operators]
   const size_t o_raw = 0, o_flt = o_raw + (memory == PCM_MEM_HOST ? up256(n * desc->stride_bytes) : 0), o_srt = o_flt + up256(n * 48), o_pose = o_srt + up256(n * 48);
   const size_t o_scr = o_pose + up256(sizeof(pcm_imu_pose) * (size_t)std::max(npose, 1));
-  rc = pre_scratch(c, o_scr + std::max({lidar_filter_scratch_bytes(n), lidar_time_sort_scratch_bytes(n), voxel_downsample_scratch_bytes(n)}));
+  rc = pre_scratch(c, o_scr + std::max({lidar_filter_scratch_bytes(n), lidar_time_sort_scratch_bytes(n), voxel_downsample_scratch_bytes(n)}), "pcm_lio_frame_begin_cloud");
   if (rc != PCM_OK) return rc;
   char* A = c->pre_arena;
   const void* d_raw = points;
@@ -1205,6 +1219,8 @@ int pcm_lio_frame_begin_cloud(pcm_ctx* c, const void* points, size_t n, int memo
   c->srcmap.valid = false;
   c->src_cov_valid = false;
   c->user_cov_src.clear();
+  c->lio_frame.set(A + o_srt, n_flt, d_scan, n_ds);
+  c->lio_last_obs.valid = false;
   *n_scan = n_ds;
   return PCM_OK;
 }

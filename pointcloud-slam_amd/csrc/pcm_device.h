@@ -155,6 +155,14 @@ __device__ inline void gstore4(float4* p, const float4& v) { *(PCM_GLOBAL pcm_v4
 __device__ inline void gstore_f(float* p, float v) { *(PCM_GLOBAL float*)p = v; }
 __device__ inline void gstore_d(double* p, double v) { *(PCM_GLOBAL double*)p = v; }
 __device__ inline double gload_d(const double* p) { return *(const PCM_GLOBAL double*)p; }
+// r = q * v in double: Eigen's Quaternion::_transformVector, coefficients (x,y,z,w) -- the rotation of every double-precision
+// body -> world transform of jueying_lio (MapIncremental in voxel_hash.hip, the frame outputs in lio_outputs.hip)
+__device__ inline void qrot_d(const double* q, const double* v, double* r) {
+  double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
+  uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
+  const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
+  for (int a = 0; a < 3; a++) r[a] = v[a] + q[3] * uv[a] + c[a];
+}
 // floats as unsigned integers of the same order (atomicMin / atomicMax on bounding boxes)
 __device__ inline unsigned int f2ord(float f) { const unsigned int u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 #endif

@@ -10,6 +10,7 @@
 #include "../../include/pcm_amd.h"
 #include "dev_buf.h"
 #include "lio_iekf.h"
+#include "lio_outputs.h"
 #include "lsq_step.h"
 #include "pcm_device.h"
 #include "sub_state.h"
@@ -267,6 +268,11 @@ struct pcm_ctx {
   pcm::SubState ws;       // pcm::Workspace: batch workspace owned by this context (align_batch.hip)
   pcm::SubState ndt_ws;   // pclomp NDT: objects + solver machines of a batch (align_batch.hip)
   pcm::DevBuf<char> pre_arena{"pre_arena"};   // grow-only device scratch of the pre-processing operators
+  // jueying_lio frame outputs (lio_outputs.hip): where the current frame's records lie in pre_arena (gone with the next call that
+  // takes the arena: take_pre_arena), the pose of the last ObsModel call, and the saved-map log (lio_out::MapLog)
+  pcm::lio_out::FrameRecord lio_frame;
+  pcm::lio_out::LastObs lio_last_obs;
+  pcm::SubState lio_map;
   pcm::DevBuf<char> bfgs{"bfgs"};             // GICP-BFGS functor: packed correspondence records + partial sums (gicp_bfgs.hip)
   size_t bfgs_m = 0;
   std::vector<double> user_cov_src;   // source covariances handed in by the caller (6 per point, input order); empty = compute
@@ -282,6 +288,13 @@ struct pcm_ctx {
 };
 
 namespace pcm {
+// room for `bytes` in the grow-only device scratch the pre-processing operators share (a quarter of headroom: no allocation per
+// frame in the steady state); the contents do not survive the call, so the frame record of the LIO outputs goes, and `who` (a
+// string literal, the entry point) is what their refusal names
+inline int take_pre_arena(pcm_ctx* c, size_t bytes, const char* who) {
+  c->lio_frame.take(who);
+  return c->pre_arena.reserve(c->stream, &c->err, bytes, bytes + bytes / 4);
+}
 template <typename T> int DevBuf<T>::reserve(pcm_ctx* c, size_t need, size_t new_cap, bool zero) { return reserve(c->stream, &c->err, need, new_cap, zero); }
 template <typename T> int DevBuf<T>::reserve_keep(pcm_ctx* c, size_t need, size_t new_cap, size_t keep) { return reserve_keep(c->stream, &c->err, need, new_cap, keep); }
 template <typename T> int PinnedBuf<T>::reserve(pcm_ctx* c, size_t need, size_t new_cap, unsigned flags) { return reserve(c->stream, &c->err, need, new_cap, flags); }

@@ -718,13 +718,6 @@ int sort_sources_batched(hipStream_t stream, const SortJob* d_jobs, int njobs, u
 // ---------------------------------------------------------------------------
 // LaserMapping::MapIncremental (/root/reference/src/jueying_lio/src/laser_mapping.cc:525-583)
 // ---------------------------------------------------------------------------
-__device__ inline void qrot_d(const double* q, const double* v, double* r) {   // Eigen _transformVector, (x,y,z,w)
-  double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
-  uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-  const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
-  for (int a = 0; a < 3; a++) r[a] = v[a] + q[3] * uv[a] + c[a];
-}
-
 // flag[i]: 0 = not added, 1 = points_to_add, 2 = point_no_need_downsample; world[i] = PointBodyToWorld(scan[i])
 __global__ void k_map_filter(const float4* __restrict__ scan, uint32_t n, LioStateD s, float fs, const uint32_t* __restrict__ nn, const float4* __restrict__ map_pts,
                              float4* __restrict__ world, uint32_t* __restrict__ f1, uint32_t* __restrict__ f2, int scan_reordered) {

@@ -1949,6 +1949,113 @@ Registration.lio_imu_init = _lio_imu_init
 Registration.lio_propagate = _lio_propagate
 
 
+# ---- the frame outputs and the saved map of jueying_lio (pcm_lio_frame_world .. pcm_lio_map_export) --------
+def _lio_state(rot_xyzw, pos, off_R_xyzw, off_T) -> capi.PcmLioState:
+    st = capi.PcmLioState()
+    st.rot[:] = list(map(float, rot_xyzw)); st.pos[:] = list(map(float, pos)); st.off_R[:] = list(map(float, off_R_xyzw)); st.off_T[:] = list(map(float, off_T))
+    return st
+
+
+def _xyzi_out(out):
+    """(pointer, capacity in records, memory) of a caller's buffer of 16-byte records: a float32 numpy array or CUDA tensor."""
+    if hasattr(out, "data_ptr"):
+        assert out.is_cuda and out.is_contiguous() and out.element_size() == 4
+        return out.data_ptr(), out.numel() // 4, capi.MEM_DEVICE
+    assert isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.flags.writeable
+    return out.ctypes.data, out.size // 4, capi.MEM_HOST
+
+
+def _xyzi_call(self, call, out):
+    """call(ptr, capacity, memory, byref(n)) -> rc.  out None: a new (n, 4) float32 host array; else the caller's buffer is filled and
+    the count returned (a buffer that is too small raises, with the needed count in the message)."""
+    n = C.c_size_t()
+    if out is not None:
+        ptr, cap, mem = _xyzi_out(out)
+        self._check(call(C.c_void_p(ptr), cap, mem, C.byref(n)))
+        return n.value
+    self._check(call(None, 0, capi.MEM_HOST, C.byref(n)))
+    res = np.zeros((n.value, 4), np.float32)
+    if n.value:
+        self._check(call(C.c_void_p(res.ctypes.data), n.value, capi.MEM_HOST, C.byref(n)))
+    return res
+
+
+def _lio_frame_world(self, rot_xyzw, pos, off_R_xyzw, off_T, dense: bool = False, out=None):
+    """PublishFrameWorld's cloud of the current frame (pcm_lio_frame_world; laser_mapping.cc:747-762): (x, y, z, intensity) rows in the
+    world frame; dense = every undistorted point, else the down-sampled scan in the order of get_source()."""
+    st = _lio_state(rot_xyzw, pos, off_R_xyzw, off_T)
+    return _xyzi_call(self, lambda p, cap, mem, n: self._L.pcm_lio_frame_world(self._h, C.byref(st), int(bool(dense)), p, cap, mem, n), out)
+
+
+def _lio_frame_body(self, rot_xyzw, pos, off_R_xyzw, off_T, out=None):
+    """PublishFrameBody's cloud (pcm_lio_frame_body; :794-808): the undistorted scan in the IMU body frame."""
+    st = _lio_state(rot_xyzw, pos, off_R_xyzw, off_T)
+    return _xyzi_call(self, lambda p, cap, mem, n: self._L.pcm_lio_frame_body(self._h, C.byref(st), p, cap, mem, n), out)
+
+
+def _lio_frame_effect(self, rot_xyzw, pos, off_R_xyzw, off_T, out=None):
+    """PublishFrameEffectWorld's cloud (pcm_lio_frame_effect; :810-823): the points that gave a row to the last ObsModel call, in scan
+    order, in the world frame, intensity = |z|."""
+    st = _lio_state(rot_xyzw, pos, off_R_xyzw, off_T)
+    return _xyzi_call(self, lambda p, cap, mem, n: self._L.pcm_lio_frame_effect(self._h, C.byref(st), p, cap, mem, n), out)
+
+
+def _map_info_dict(info) -> dict:
+    return dict(points=int(info.points), capacity=int(info.capacity), frames_appended=int(info.frames_appended), growths=int(info.growths),
+                scan_wait_num=int(info.scan_wait_num), pcd_index=int(info.pcd_index), chunk_ready=bool(info.chunk_ready))
+
+
+def _lio_map_append(self, rot_xyzw, pos, off_R_xyzw, off_T, dense: bool = False, pcd_save_interval: int = -1) -> dict:
+    """`*pcl_wait_save_ += *laserCloudWorld` on the device (pcm_lio_map_append; :776-791) -> lio_map_info(); chunk_ready / pcd_index say
+    when the reference would write jueying_<pcd_index>.pcd and clear the cloud (fetch the log, then lio_map_clear)."""
+    st = _lio_state(rot_xyzw, pos, off_R_xyzw, off_T)
+    info = capi.PcmLioMapInfo()
+    self._check(self._L.pcm_lio_map_append(self._h, C.byref(st), int(bool(dense)), int(pcd_save_interval), C.byref(info)))
+    return _map_info_dict(info)
+
+
+def _lio_map_info(self) -> dict:
+    info = capi.PcmLioMapInfo()
+    self._check(self._L.pcm_lio_map_info_get(self._h, C.byref(info)))
+    return _map_info_dict(info)
+
+
+def _lio_map_get(self, first: int = 0, count: int = None, out=None):
+    """Records [first, first + count) of the saved-map log (count None: to its end) as (count, 4) float32 rows, or into `out`."""
+    if count is None:
+        count = max(self.lio_map_info()["points"] - int(first), 0)
+    if out is not None:
+        ptr, cap, mem = _xyzi_out(out)
+        if cap < count:
+            raise ValueError("lio_map_get: the buffer holds %d records, the slice has %d" % (cap, count))
+        self._check(self._L.pcm_lio_map_get(self._h, int(first), int(count), C.c_void_p(ptr), mem))
+        return int(count)
+    res = np.zeros((int(count), 4), np.float32)
+    self._check(self._L.pcm_lio_map_get(self._h, int(first), int(count), C.c_void_p(res.ctypes.data), capi.MEM_HOST))
+    return res
+
+
+def _lio_map_clear(self):
+    """pcl_wait_save_->clear(); scan_wait_num = 0 (pcm_lio_map_clear)."""
+    self._check(self._L.pcm_lio_map_clear(self._h))
+
+
+def _lio_map_export(self, leaf_size: float = 0.0, z_min: float = 1.0, z_max: float = 0.0, out=None):
+    """LaserMapping::Finish's cloud, optionally through pcd2map's filters (pcm_lio_map_export): VoxelGrid of leaf_size (> 0), then
+    the records with z_min <= z <= z_max (applied when z_min <= z_max).  Defaults: the log as it is."""
+    return _xyzi_call(self, lambda p, cap, mem, n: self._L.pcm_lio_map_export(self._h, C.c_float(leaf_size), float(z_min), float(z_max), p, cap, mem, n), out)
+
+
+Registration.lio_frame_world = _lio_frame_world
+Registration.lio_frame_body = _lio_frame_body
+Registration.lio_frame_effect = _lio_frame_effect
+Registration.lio_map_append = _lio_map_append
+Registration.lio_map_info = _lio_map_info
+Registration.lio_map_get = _lio_map_get
+Registration.lio_map_clear = _lio_map_clear
+Registration.lio_map_export = _lio_map_export
+
+
 class LioOdometry:
     """LaserMapping::Run (laser_mapping.cc:301-356) over one Registration (P2PLANE): ImuProcess::Process, the first-scan branch, the
     down-sampled frame, the iterated Kalman update and the map update, every step one of the object's existing calls.
@@ -1958,8 +2065,13 @@ class LioOdometry:
     MIN_POINTS = 5           # laser_mapping.cc:331
 
     def __init__(self, reg: Registration, imu_state: capi.PcmLioImuState = None, x=None, P=None, filter_size_map: float = 0.5, propagate=None,
-                 update_params: dict = None, **frame_params):
+                 update_params: dict = None, pcd_save_en: bool = False, dense_pub_en: bool = False, pcd_save_interval: int = -1, **frame_params):
         self.reg = reg
+        # the offline branch of Run's last block (laser_mapping.cc:362-365): PublishFrameWorld into the saved map
+        self.pcd_save_en = bool(pcd_save_en)
+        self.dense_pub_en = bool(dense_pub_en)
+        self.pcd_save_interval = int(pcd_save_interval)
+        self.chunks = []         # (pcd_index, (n, 4) records) of every jueying_<k>.pcd the reference would have written
         self.imu_state = imu_state if imu_state is not None else lio_imu_state()
         self.x = _filter_dict(_filter_state(x)) if x is not None else _filter_dict(_filter_state([0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 1] + [0] * 12 + [9.809, 0, 0]))
         self.P = np.eye(23) if P is None else np.array(P, np.float64).reshape(23, 23).copy()
@@ -2009,4 +2121,16 @@ class LioOdometry:
         self.last_update = self.reg.lio_update(self.x, self.P, **self.update_params)
         self.x, self.P = self.last_update.x, self.last_update.P
         self.reg.lio_frame_end(*self._pose_args(), self.filter_size_map, self.ekf_inited)
+        if self.pcd_save_en:                                   # PublishFrameWorld  :363-365, 776-791
+            info = self.reg.lio_map_append(*self._pose_args(), dense=self.dense_pub_en, pcd_save_interval=self.pcd_save_interval)
+            if info["chunk_ready"]:
+                self.chunks.append((info["pcd_index"], self.reg.lio_map_get()))
+                self.reg.lio_map_clear()
         return "updated"
+
+    def finish(self, leaf_size: float = 0.0, z_min: float = 1.0, z_max: float = 0.0):
+        """LaserMapping::Finish (:887-900): the cloud of jueying.pcd as (n, 4) float32 rows, or None where the reference writes no
+        file (pcd_save_en off, or an empty cloud); leaf_size / z_min / z_max: pcd2map's filters on top (lio_map_export)."""
+        if not self.pcd_save_en or self.reg.lio_map_info()["points"] == 0:
+            return None
+        return self.reg.lio_map_export(leaf_size, z_min, z_max)
