@@ -135,6 +135,16 @@ typedef struct pcm_config {
                                        * target that has grown (pcm_target_insert / pcm_map_incremental), the LIO model, or next to another kernel flag.
                                        * pclomp NDT (PCM_MODEL_NDT_OMP): the same policy for the grid's neighbour-LEAF lists (the leaves a point's search
                                        * visits, in visiting order; 16 B per (voxel, neighbour leaf)). */
+#define PCM_FLAG_FOLLOWING_LISTS 128  /* P2PLANE: candidate lists that follow a growing target.  Built with the map as under PCM_FLAG_NEIGHBOUR_LISTS; when the
+                                       * target grows through pcm_target_insert / pcm_map_incremental, the lists within one neighbourhood of a voxel the batch
+                                       * added points to (or the LRU eviction removed) are rewritten at the next registration -- in place where the run's
+                                       * capacity holds them, else at the end of a pool with reserved room (pcm_neighbour_list_headroom) -- instead of
+                                       * being dropped, and every linearize pass keeps running k_linearize_lists.  Same candidates in the same order as the
+                                       * tile kernel finds: bit-identical results.  A full build replaces the update when the pool is full, when the holes
+                                       * left by moved runs exceed the live entries, or when more than half the lists are empty.  No lists next to
+                                       * PCM_FLAG_NO_NEIGHBOUR_LISTS or another kernel flag (REFERENCE_KNN_ORDER, COUNTED_SEARCH, NO_LDS_STAGING, FUSED_STEP);
+                                       * pcm_obs_model stays on the tile kernel.  Measured (DESIGN section 26, 1 M-point map, 7 000-point batches): pays from one
+                                       * align per insert on; an update costs about 13 ms of device time, the pool 2.5 x the lists' memory.  Fails loudly when the lists cannot be kept (no memory). */
 #define PCM_FLAG_NO_NEIGHBOUR_LISTS 64 /* never build them: the tile kernel (kernels.hip) serves every pass */
 #define PCM_FLAG_REFERENCE_KNN_ORDER 32
 /* P2PLANE align / linearize: hand esti_plane its neighbours in the row order the reference's IVox::GetClosestPoint leaves -- the
@@ -262,7 +272,28 @@ int pcm_get_planes(pcm_ctx *ctx, float *out, size_t n);
  * NULL: `centres` 4*L floats (the centre of list voxel r in xyz), `starts` L+1 entries (run r = entries starts[r] .. starts[r+1];
  * every start is a multiple of 4 and a run ends with 0..3 pad entries), `entries` 4*E floats (x, y, z, bit pattern of the point's
  * index in the map's own array; a pad entry is +inf, +inf, +inf, 0xffffffff).  Fails unless the context holds such lists. */
+/* Following lists (PCM_FLAG_FOLLOWING_LISTS) are brought up to date first (a source must be set if the target grew since the last
+ * registration) and their pooled runs are gathered into this contiguous form, list voxels in the index's current order.  After an
+ * update the fourth component of a real entry is NOT maintained: the map's point array is renumbered by every merge and the walk
+ * never reads it; only a pad entry's 0xffffffff is kept.  A list voxel all of whose neighbours were evicted stays, with an empty run. */
 int pcm_get_neighbour_lists(pcm_ctx *ctx, uint64_t info[2], float *centres, uint32_t *starts, float *entries);
+
+/* The candidate lists the context's linearize pass reads: info[0] lists, [1] live entries (pad entries included), [2] capacity of
+ * the allocation in entries, and for following lists [3] wasted entries (holes left by moved runs), [4] updates since the last
+ * full build, [5] runs rewritten in place, [6] runs relocated, [7] full builds the pool's policy asked for ([5]-[7] since the
+ * lists were first built).  All zero when the context holds no lists or its configuration reads none. */
+int pcm_neighbour_list_info(pcm_ctx *ctx, uint64_t info[8]);
+
+/* Diagnostic: the device time of the last update of following lists that ran while pcm_set_profiling bit 0 was on, from HIP events
+ * (they cost the update one more synchronisation): ms[0] dirty lists (dilation, sort, distinct), [1] classify + the read-back,
+ * [2] rewrite, [3] index merge (only with new list voxels) + rank table, [4] the whole update.  Zeros when none was timed or a full
+ * build took the update's place. */
+int pcm_neighbour_list_update_ms(pcm_ctx *ctx, double ms[5]);
+
+/* Following lists: the free room a full build reserves behind the runs -- max(fraction * entries, min_entries) entries of 16
+ * bytes.  Default: one and a half times the entries, at least 65536 (1 MiB).  A minimum, applied when a full build has to
+ * allocate: the allocation only grows (by a quarter more than asked) and the pool uses all of it. */
+int pcm_neighbour_list_headroom(pcm_ctx *ctx, float fraction, uint64_t min_entries);
 
 /* parity hook for PCM_FLAG_LIO_REFERENCE_SEMANTICS: residuals_[i] and point_selected_surf_[i]
  * (jueying_lio/src/laser_mapping.cc:337-338, 619-635) as the last pcm_obs_model left them, in the order of the

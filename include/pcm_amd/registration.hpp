@@ -111,6 +111,8 @@ public:
   void setMaxRange(double r) { cfg_.max_range = static_cast<float>(r); }   // IVox::GetClosestPoint max_range
   void setResolution(double r) { cfg_.voxel_resolution = static_cast<float>(r); }      // fast_vgicp_impl.hpp:28-30
   void setNumNeighborCells(int n) { cfg_.num_neighbors = n; }            // ivox_nearby_type 0/6/18/26 -> 1/7/19/27
+  // P2PLANE scan-to-submap mapping: the candidate lists follow a target that grows (PCM_FLAG_FOLLOWING_LISTS)
+  void setFollowingLists(bool on) { cfg_.flags = on ? (cfg_.flags | PCM_FLAG_FOLLOWING_LISTS) : (cfg_.flags & ~PCM_FLAG_FOLLOWING_LISTS); }
 
   virtual void swapSourceAndTarget() {
     input_.swap(target_);

@@ -34,6 +34,7 @@ SYMBOLS = [
     "pcm_lio_default_update_params", "pcm_lio_update", "pcm_lio_update_trace",
     "pcm_lio_default_imu_state", "pcm_lio_imu_init", "pcm_lio_propagate",
     "pcm_share_target", "pcm_target_share_count",
+    "pcm_neighbour_list_info", "pcm_neighbour_list_headroom", "pcm_neighbour_list_update_ms",
     "pcm_lio_frame_world", "pcm_lio_frame_body", "pcm_lio_frame_effect", "pcm_lio_map_append", "pcm_lio_map_info_get", "pcm_lio_map_get",
     "pcm_lio_map_clear", "pcm_lio_map_export",
 ]
@@ -44,6 +45,7 @@ PCM_FLAG_NO_LDS_STAGING = 1
 PCM_FLAG_FUSED_STEP = 2
 PCM_FLAG_COUNTED_SEARCH = 8           # k_linearize_counted instead of k_linearize (A/B; same results, measured slower)
 PCM_FLAG_NEIGHBOUR_LISTS = 16           # static targets: per-voxel candidate lists built with the map (default: from the 2nd registration on), same results
+PCM_FLAG_FOLLOWING_LISTS = 128          # P2PLANE: the lists follow a target that grows (target_insert / map_incremental): touched runs are rewritten, same results
 PCM_FLAG_NO_NEIGHBOUR_LISTS = 64        # never: the tile kernel serves every pass
 PCM_FLAG_REFERENCE_KNN_ORDER = 32      # neighbours in the order of libstdc++'s std::nth_element (the reference's), slower kernel
 PCM_FLAG_LIO_REFERENCE_SEMANTICS = 4   # pcm_obs_model keeps LaserMapping's per-point members across calls and scans
@@ -350,6 +352,9 @@ def load_library():
     L.pcm_compute_error.argtypes = [vp, vp, C.POINTER(C.c_double)]
     L.pcm_get_planes.argtypes = [vp, vp, sz]
     L.pcm_get_neighbour_lists.argtypes = [vp, vp, vp, vp, vp]
+    L.pcm_neighbour_list_info.argtypes = [vp, vp]
+    L.pcm_neighbour_list_update_ms.argtypes = [vp, vp]
+    L.pcm_neighbour_list_headroom.argtypes = [vp, C.c_float, u64]
     L.pcm_get_lio_members.argtypes = [vp, vp, vp, sz]
     L.pcm_obs_model.argtypes = [vp, C.POINTER(PcmLioState), i32, i32, C.POINTER(PcmObsResult)]
     L.pcm_target_insert.argtypes = [vp, vp, sz, sz, i32]

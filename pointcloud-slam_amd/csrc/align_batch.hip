@@ -208,6 +208,8 @@ int align_batch_impl(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_resu
   const bool ref_order = g.model == PCM_MODEL_P2PLANE && (g.flags & PCM_FLAG_REFERENCE_KNN_ORDER) != 0;   // neighbours in libstdc++'s nth_element order
   bool lists = g.model == PCM_MODEL_P2PLANE && !ref_order;   // k_linearize_lists: every context of the batch holds its map's candidate lists
   for (int i = 0; i < n && lists; i++) lists = lists_view_for(ctxs[i]).pts != nullptr;
+  const bool pooled = lists && lists_pooled_for(ctxs[0]);   // one kernel per launch: a batch that mixes pooled and contiguous lists takes the tile kernel
+  for (int i = 0; i < n && lists; i++) lists = lists_pooled_for(ctxs[i]) == pooled;
   if (ref_order) {
     for (int i = 0; i < n; i++) {
       if (ctxs[i]->tg->map.max_voxel_points > (uint32_t)kRefMaxVoxelPoints) {
@@ -245,7 +247,7 @@ int align_batch_impl(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_resu
     else if (gicp) launch_gicp(st, w->d_descs, w->d_states, kpr, nl, g.model == PCM_MODEL_VGICP, false);
     else if (fuse) launch_linearize_fused(st, w->d_descs, w->d_states, kpr, lp, nl, w->d_flags + (size_t)r * n);
     else if (ref_order) launch_linearize_reforder(st, w->d_descs, w->d_states, kpr, nl, write_sel);
-    else if (lists && !counters_on && !timing_on) launch_linearize_lists(st, w->d_descs, w->d_states, kpr, nl, write_sel);
+    else if (lists && !counters_on && !timing_on) launch_linearize_lists(st, w->d_descs, w->d_states, kpr, nl, write_sel, pooled);
     else if (counted_search) launch_linearize_counted(st, w->d_descs, w->d_states, kpr, nl, write_sel, counters_on ? w->d_stats : nullptr, timing_on);
     else launch_linearize(st, w->d_descs, w->d_states, kpr, nl, write_sel, counters_on ? w->d_stats : nullptr, timing_on);
     if (timed) PCM_HIPCK(c0, hipEventRecord(w->ev_prof[prof_used + 1], st));
@@ -341,7 +343,7 @@ int single_pass(pcm_ctx* c, const double T[16], bool linearize, double sums[kPar
     if (c->tg->map.max_voxel_points > (uint32_t)kRefMaxVoxelPoints) { c->err = "PCM_FLAG_REFERENCE_KNN_ORDER supports at most " + std::to_string(kRefMaxVoxelPoints) + " points per voxel"; return PCM_ERR_UNSUPPORTED; }
     launch_linearize_reforder(c->stream, w->d_descs, w->d_states, kp1, 1, true);
   }
-  else if (linearize && lists_view_for(c).pts != nullptr) launch_linearize_lists(c->stream, w->d_descs, w->d_states, kp1, 1, true);
+  else if (linearize && lists_view_for(c).pts != nullptr) launch_linearize_lists(c->stream, w->d_descs, w->d_states, kp1, 1, true, lists_pooled_for(c));
   else if (linearize && (c->cfg.flags & PCM_FLAG_COUNTED_SEARCH)) launch_linearize_counted(c->stream, w->d_descs, w->d_states, kp1, 1, true, nullptr);
   else if (linearize) launch_linearize(c->stream, w->d_descs, w->d_states, kp1, 1, true, nullptr, false);
   else launch_trial(c->stream, w->d_descs, w->d_states, kp1, 1);

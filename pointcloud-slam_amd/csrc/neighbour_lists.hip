@@ -26,6 +26,7 @@
 #include "keyed_best.h"
 #include "dev_scratch.h"
 
+#include <algorithm>
 #include <cstring>
 #include <string>
 
@@ -98,15 +99,12 @@ __device__ inline bool nl_voxel_run(const TargetView& tg, BrickCursor& c, int vx
 
 // FILL = false: len[r] = candidates of list voxel r, rounded up to a multiple of kListTrip (0 stays 0); FILL = true: copy them and
 // fill the rest of the run with kListPad entries.  One lane per list voxel.
+// The candidates of list voxel (cx, cy, cz) and their padded number: the build (k_nl_lists) and the update of following lists
+// (k_fl_classify / k_fl_rewrite) share it.  FILL: they are written to out[0 ..), pad entries behind them.
 template <bool FILL>
-__global__ void k_nl_lists(const float4* __restrict__ centres, uint32_t nd, TargetView tg, int nn, uint32_t* __restrict__ len, const uint32_t* __restrict__ start, float4* __restrict__ out) {
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= nd) return;
-  const float4 c = centres[r];
-  const int cx = (int)roundf(c.x * tg.inv_res), cy = (int)roundf(c.y * tg.inv_res), cz = (int)roundf(c.z * tg.inv_res);
+__device__ inline uint32_t nl_gather(const TargetView& tg, int nn, int cx, int cy, int cz, float4* __restrict__ out) {
   BrickCursor cur;
   uint32_t n = 0;
-  const uint32_t o = FILL ? start[r] : 0u;
   for (int g = 0; g < nn; g++) {   // nearby_grids_ order  ivox3d.h:211-235
     uint32_t s, e;
     if (!nl_voxel_run(tg, cur, cx + c_nearby[g][0], cy + c_nearby[g][1], cz + c_nearby[g][2], s, e)) continue;
@@ -114,7 +112,7 @@ __global__ void k_nl_lists(const float4* __restrict__ centres, uint32_t nd, Targ
       for (uint32_t k = s; k < e; k++) {   // the voxel's points in insertion order (points_)  ivox3d_node.hpp:158-166
         float4 p = gload4(tg.pts + k);
         p.w = __uint_as_float(k);
-        out[o + n + (k - s)] = p;
+        out[n + (k - s)] = p;
       }
     }
     n += e - s;
@@ -122,10 +120,18 @@ __global__ void k_nl_lists(const float4* __restrict__ centres, uint32_t nd, Targ
   const uint32_t padded = (n + (kListTrip - 1u)) & ~(kListTrip - 1u);
   if (FILL) {
     const float inf = __builtin_inff();
-    for (uint32_t k = n; k < padded; k++) out[o + k] = make_float4(inf, inf, inf, __uint_as_float(kListPadId));
-  } else {
-    len[r] = padded;
+    for (uint32_t k = n; k < padded; k++) out[k] = make_float4(inf, inf, inf, __uint_as_float(kListPadId));
   }
+  return padded;
+}
+template <bool FILL>
+__global__ void k_nl_lists(const float4* __restrict__ centres, uint32_t nd, TargetView tg, int nn, uint32_t* __restrict__ len, const uint32_t* __restrict__ start, float4* __restrict__ out) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= nd) return;
+  const float4 c = centres[r];
+  const int cx = (int)roundf(c.x * tg.inv_res), cy = (int)roundf(c.y * tg.inv_res), cz = (int)roundf(c.z * tg.inv_res);
+  const uint32_t padded = nl_gather<FILL>(tg, nn, cx, cy, cz, FILL ? out + start[r] : nullptr);
+  if (!FILL) len[r] = padded;
 }
 
 // pclomp NDT: the neighbour LEAVES of every list voxel in the order getNeighborhoodAtPoint{,7,1} / the radius search visit them
@@ -196,7 +202,7 @@ __global__ void k_nl_voxel_slots(const float4* __restrict__ centres, uint32_t nd
 TargetView view_of_lists(const NeighbourLists& l) {
   TargetView v = view_of(l.index);
   v.pts = l.pts;
-  v.vox_start = l.start;
+  v.vox_start = l.pooled ? reinterpret_cast<const uint32_t*>(l.rank_rec.p) : l.start.p;   // pooled: (start, length) records, read by k_linearize_lists<.., true> only
   v.num_points = (uint32_t)l.num_candidates;
   return v;
 }
@@ -215,6 +221,7 @@ struct ListBuild {
   size_t nk;     // (voxel, offset) keys
   float4* centres = nullptr;   // a stand-in point per dilated voxel, in key order
   uint32_t nd = 0;             // dilated voxels = lists
+  const ListFollow* follow = nullptr;   // the pooled form of following lists
 };
 
 // room for `need` bytes?  a quarter of the free memory stays untouched (the caller's next targets, the scratch of the passes)
@@ -257,6 +264,11 @@ static int dilated_voxels(ListBuild& b) {
 
 // the list index: a brick hash over the stand-in points (one per dilated voxel); its own host syncs
 static int list_index(ListBuild& b) {
+  if (b.follow) {   // the index of following lists is merged into later (update_neighbour_lists): its point log stays
+    if (const int rc = b.out->centres.reserve(b.stream, b.err, b.nd, (size_t)b.nd + b.nd / 4 + 1024); rc != PCM_OK) return rc;
+    PCM_HIPCK_ERR(b.err, hipMemcpyAsync(b.out->centres, b.centres, sizeof(float4) * (size_t)b.nd, hipMemcpyDeviceToDevice, b.stream));
+    b.centres = b.out->centres;
+  }
   if (const int rc = build_target_map(b.stream, b.centres, &b.nd, b.map.res, b.map.coord_mode, &b.out->index, b.err); rc != PCM_OK) return rc;
   if (b.out->index.num_voxels != b.nd || b.out->index.num_points != b.nd) { *b.err = "neighbour lists: index does not hold one voxel per list"; return PCM_ERR_INTERNAL; }
   return PCM_OK;
@@ -276,6 +288,160 @@ static int voxel_slot_rows(ListBuild& b) {
   out->num_neighbors = b.nn;
   out->kind = 2;
   out->valid = true;
+  return PCM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Following lists (PCM_FLAG_FOLLOWING_LISTS): the runs in a pool, a (start, length) record per list
+// ---------------------------------------------------------------------------
+static_assert(list_pool::kTrip == kListTrip && list_pool::kTailTrips == kWalkAhead, "list_pool.h lays the pool out for this walk");
+
+namespace {
+
+// the records of a full build: run r of the contiguous layout belongs to the list whose stand-in point is log entry idx_s[r]
+__global__ void k_fl_records(const uint32_t* __restrict__ idx_s, const uint32_t* __restrict__ start, const uint32_t* __restrict__ len, uint32_t nd, uint2* __restrict__ rec,
+                             uint32_t* __restrict__ rec_cap, uint2* __restrict__ rank_rec) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= nd) return;
+  const uint32_t id = idx_s[r];
+  const uint2 v = make_uint2(start[r], len[r]);
+  rec[id] = v;
+  rec_cap[id] = v.y;
+  rank_rec[r] = v;
+}
+// rank -> record, after the ranks or the records changed
+__global__ void k_fl_rank_records(const uint32_t* __restrict__ idx_s, const uint2* __restrict__ rec, uint32_t nd, uint2* __restrict__ rank_rec) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < nd) rank_rec[r] = rec[idx_s[r]];
+}
+
+__device__ inline void fl_unpack_point_key(uint64_t k, int& x, int& y, int& z) {   // point_key (pcm_device.h) back to the voxel
+  const uint64_t bkey = k >> 9;
+  const uint32_t li = (uint32_t)(k & 511u);
+  x = (((int)(bkey >> 36) - kBrickBias) << kBrickShift) + (int)(li >> 6);
+  y = (((int)((bkey >> 18) & 0x3ffff) - kBrickBias) << kBrickShift) + (int)((li >> 3) & 7u);
+  z = (((int)(bkey & 0x3ffff) - kBrickBias) << kBrickShift) + (int)(li & 7u);
+}
+__device__ inline void fl_unpack_list_key(uint64_t k, int& x, int& y, int& z) {
+  x = (int)((k >> 42) & 0x1fffffu) - kKeyBias; y = (int)((k >> 21) & 0x1fffffu) - kKeyBias; z = (int)(k & 0x1fffffu) - kKeyBias;
+}
+
+// the dilation of k_nl_keys over the touched voxels: one key per (touched voxel, offset); a touched key equal to its predecessor
+// (the batch's keys are sorted: a voxel's points follow one another) or ~0 gives none.  grid = ceil(nt / 256)
+__global__ void k_fl_dirty_keys(const uint64_t* __restrict__ touched, uint32_t nt, int nn, uint64_t* __restrict__ keys) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nt) return;
+  const uint64_t t = touched[i];
+  const bool skip = t == ~0ull || (i > 0 && touched[i - 1] == t);
+  int cx = 0, cy = 0, cz = 0;
+  fl_unpack_point_key(t, cx, cy, cz);
+  const int lim = kKeyBias - 64;
+  for (int g = 0; g < nn; g++) {
+    const int x = cx - c_nearby[g][0], y = cy - c_nearby[g][1], z = cz - c_nearby[g][2];
+    const bool ok = !skip && x > -lim && x < lim && y > -lim && y < lim && z > -lim && z < lim;
+    keys[(size_t)i * nn + g] = ok ? nl_pack(x, y, z) : ~0ull;
+  }
+}
+// distinct keys to the front; their number to ctr[kTotDirty]
+enum { kTotDirty = 0, kTotNew, kTotRelocEntries, kTotRelocated, kTotInPlace, kTotWasted, kTotLiveAdded, kTotLiveRemoved, kTotBecameEmpty, kTotLeftEmpty, kTotWords = 16 };
+__global__ void k_fl_compact(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos, uint32_t n, uint64_t* __restrict__ out, unsigned long long* __restrict__ ctr) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (i == n - 1) ctr[kTotDirty] = pos[i] + flag[i];
+  if (flag[i]) out[pos[i]] = keys[i];
+}
+
+// What becomes of every dirty list: its new padded length from the updated map, its record in the index as it was before the
+// update (none: a new list voxel), and from the two whether it is rewritten in place or placed at the bump pointer (list_pool.h).
+// Entries past the dirty count are cleared, so the scans over the whole arrays are the scans over the dirty lists.
+struct DirtyList { uint32_t id, start, cap, len; };   // id: ~0 = new; start / cap: the old run; len: the new padded length
+__global__ void k_fl_classify(const uint64_t* __restrict__ dirty, uint32_t nk, TargetView tg, int nn, TargetView index, const uint32_t* __restrict__ index_idx, const uint2* __restrict__ rec,
+                              const uint32_t* __restrict__ rec_cap, DirtyList* __restrict__ out, uint32_t* __restrict__ newcap, uint32_t* __restrict__ isnew, unsigned long long* __restrict__ ctr) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nk) return;
+  if (i >= ctr[kTotDirty]) { newcap[i] = 0; isnew[i] = 0; return; }
+  int cx, cy, cz;
+  fl_unpack_list_key(dirty[i], cx, cy, cz);
+  DirtyList d;
+  d.len = nl_gather<false>(tg, nn, cx, cy, cz, nullptr);
+  BrickCursor cur;
+  const int rank = nl_voxel_rank(index, cur, cx, cy, cz);
+  d.id = ~0u; d.start = 0; d.cap = 0;
+  uint32_t old_len = 0;
+  if (rank >= 0) {
+    d.id = index_idx[rank];
+    const uint2 r = rec[d.id];
+    d.start = r.x; old_len = r.y; d.cap = rec_cap[d.id];
+  }
+  const bool fresh = rank < 0, stay = list_pool::rewrite_in_place(d.len, d.cap);
+  const uint32_t cap_new = stay ? 0u : list_pool::grown_capacity(d.len);
+  out[i] = d;
+  newcap[i] = cap_new;
+  isnew[i] = fresh ? 1u : 0u;
+  if (fresh) atomicAdd(&ctr[kTotNew], 1ull);
+  else if (stay) atomicAdd(&ctr[kTotInPlace], 1ull);
+  else { atomicAdd(&ctr[kTotRelocated], 1ull); atomicAdd(&ctr[kTotWasted], (unsigned long long)d.cap); }
+  if (cap_new) atomicAdd(&ctr[kTotRelocEntries], (unsigned long long)cap_new);
+  if (d.len) atomicAdd(&ctr[kTotLiveAdded], (unsigned long long)d.len);
+  if (old_len) atomicAdd(&ctr[kTotLiveRemoved], (unsigned long long)old_len);
+  if (d.len == 0 && (fresh || old_len != 0)) atomicAdd(&ctr[kTotBecameEmpty], 1ull);
+  if (d.len != 0 && !fresh && old_len == 0) atomicAdd(&ctr[kTotLeftEmpty], 1ull);
+}
+
+// The rewrite: a new list voxel gets the next id and its centre goes to the log; a run that does not stay gets its place behind
+// the bump pointer; every dirty run is gathered again as k_nl_lists gathers it.  One lane per dirty list.
+__global__ void k_fl_rewrite(const uint64_t* __restrict__ dirty, uint32_t nd, TargetView tg, int nn, const DirtyList* __restrict__ lists, const uint32_t* __restrict__ newcap,
+                             const uint32_t* __restrict__ reloc_off, const uint32_t* __restrict__ isnew, const uint32_t* __restrict__ new_off, uint32_t first_new_id, uint32_t bump, float res,
+                             float4* __restrict__ centres, uint2* __restrict__ rec, uint32_t* __restrict__ rec_cap, float4* __restrict__ pool) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nd) return;
+  int cx, cy, cz;
+  fl_unpack_list_key(dirty[i], cx, cy, cz);
+  const DirtyList d = lists[i];
+  uint32_t id = d.id, start = d.start, cap = d.cap;
+  if (isnew[i]) {
+    id = first_new_id + new_off[i];
+    centres[id] = make_float4((float)cx * res, (float)cy * res, (float)cz * res, 0.f);   // COORD_ROUND: k_nl_centres with shift 0
+  }
+  if (!list_pool::rewrite_in_place(d.len, d.cap)) { start = bump + reloc_off[i]; cap = newcap[i]; }
+  rec[id] = make_uint2(start, d.len);
+  rec_cap[id] = cap;
+  if (d.len) nl_gather<true>(tg, nn, cx, cy, cz, pool + start);
+}
+
+// parity hook: the pooled runs into contiguous order by rank
+__global__ void k_fl_lengths(const uint2* __restrict__ rank_rec, uint32_t nd, uint32_t* __restrict__ len) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r <= nd) len[r] = r < nd ? rank_rec[r].y : 0u;
+}
+__global__ void k_fl_export(const uint2* __restrict__ rank_rec, const uint32_t* __restrict__ start, uint32_t nd, const float4* __restrict__ pool, float4* __restrict__ out) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= nd) return;
+  const uint2 v = rank_rec[r];
+  for (uint32_t k = 0; k < v.y; k++) out[start[r] + k] = pool[v.x + k];
+}
+
+}  // namespace
+
+// a list's records hold `n` lists (growth keeps the first `keep`)
+static int reserve_records(hipStream_t stream, std::string* err, NeighbourLists* nl, size_t n, size_t keep) {
+  const size_t cap = n + n / 4 + 1024;
+  if (const int rc = nl->rec.reserve_keep(stream, err, n, cap, keep); rc != PCM_OK) return rc;
+  if (const int rc = nl->rec_cap.reserve_keep(stream, err, n, cap, keep); rc != PCM_OK) return rc;
+  return nl->rank_rec.reserve(stream, err, n, cap);
+}
+
+// the contiguous runs of a full build become the pool's first entries (capacity = length); `len`: their padded lengths by rank
+static int pool_the_lists(ListBuild& b, const uint32_t* len) {
+  NeighbourLists* out = b.out;
+  const uint32_t nd = b.nd;
+  if (const int rc = reserve_records(b.stream, b.err, out, nd, 0); rc != PCM_OK) return rc;
+  k_fl_records<<<(nd + 255) / 256, 256, 0, b.stream>>>(out->index.idx_s, out->start, len, nd, out->rec, out->rec_cap, out->rank_rec);
+  PCM_HIPCK_ERR(b.err, hipGetLastError());
+  const size_t tail = (size_t)list_pool::Pool::tail();
+  PCM_HIPCK_ERR(b.err, hipMemsetAsync(out->pts + (out->pts.cap - tail), 0, sizeof(float4) * tail, b.stream));   // the kWalkAhead zeroed trips behind the pool's end
+  out->pool.built(out->pts.cap, out->num_candidates, nd, 0, b.follow->by_policy);   // no list of a full build is empty: a dilated voxel has an occupied neighbour
+  out->pooled = true;
   return PCM_OK;
 }
 
@@ -310,7 +476,9 @@ static int fill_lists(ListBuild& b, const PclLeaf* ndt_leaves, size_t list_entri
   // run, the keyed walk of k_linearize_lists loads (never offers) kWalkAhead trips past one.
   const size_t tail = point_lists ? (size_t)kListTrip * kWalkAhead : 4;
   static_assert(kListTrip * kWalkAhead >= 4, "the tail of the point lists is no shorter than that of the leaf lists");
-  if (const int rc = out->pts.reserve(stream, b.err, total + tail, total + tail); rc != PCM_OK) return rc;
+  const size_t alloc = b.follow ? (size_t)list_pool::Pool::capacity_for(total, b.follow->headroom_fraction, b.follow->headroom_min) : total + tail;
+  if (alloc >= (1ull << 32)) { *b.err = "neighbour lists: map too large"; return PCM_ERR_UNSUPPORTED; }
+  if (const int rc = out->pts.reserve(stream, b.err, alloc, b.follow ? std::min<size_t>(alloc + alloc / 4, 0xfffffff0u) : alloc); rc != PCM_OK) return rc;
   PCM_HIPCK_ERR(b.err, hipMemsetAsync(out->pts + total, 0, sizeof(float4) * tail, stream));
   if (ndt_leaves) k_nl_leaf_lists<true><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of(map), mode, ndt_leaves, nn, nullptr, out->start, out->pts);
   else k_nl_lists<true><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of(map), nn, nullptr, out->start, out->pts);
@@ -320,6 +488,10 @@ static int fill_lists(ListBuild& b, const PclLeaf* ndt_leaves, size_t list_entri
   out->num_candidates = total;
   out->num_neighbors = nn;
   out->kind = ndt_leaves ? 1 : 0;
+  out->pooled = false;
+  out->stale = false;
+  if (b.follow)
+    if (const int rc = pool_the_lists(b, len); rc != PCM_OK) return rc;
   out->valid = true;
   return PCM_OK;
 }
@@ -329,12 +501,16 @@ static int fill_lists(ListBuild& b, const PclLeaf* ndt_leaves, size_t list_entri
 //   1  `ndt_leaves` (pclomp NDT): neighbour LEAVES, nn = 0 for the KDTREE search, else 1 / 7 / 27;
 //   2  `voxel_slots` (k_ndt): a fixed row of nn = 1 / 7 / 27 neighbour voxel indices per list voxel.
 // Host syncs: the number of dilated voxels, the index build's own, the total list length (kind 2: the end of its one kernel).
-int build_neighbour_lists(hipStream_t stream, const TargetMap& map, int nn, NeighbourLists* out, std::string* err, const PclLeaf* ndt_leaves, bool voxel_slots) {
+int build_neighbour_lists(hipStream_t stream, const TargetMap& map, int nn, NeighbourLists* out, std::string* err, const PclLeaf* ndt_leaves, bool voxel_slots, const ListFollow* follow) {
   out->valid = false;
+  out->pooled = false;
+  out->stale = false;
+  if (follow && (ndt_leaves || voxel_slots)) { *err = "neighbour lists: only candidate lists of points follow a target"; return PCM_ERR_INTERNAL; }
   const int mode = map.coord_mode;
   if (!map.valid || (mode != COORD_ROUND && mode != COORD_FLOOR_MUL && mode != COORD_FLOOR_HALF)) { *err = "neighbour lists: unsupported voxel convention"; return PCM_ERR_UNSUPPORTED; }
   if (voxel_slots ? (nn != 1 && nn != 7 && nn != 27) : ndt_leaves ? (nn != 0 && nn != 1 && nn != 7 && nn != 27) : (nn != 1 && nn != 7 && nn != 19 && nn != 27)) { *err = "neighbour lists: unsupported neighbourhood"; return PCM_ERR_INVALID_ARGUMENT; }
   ListBuild b{stream, err, map, out, DevScratch(stream), nn, nn == 0 ? 27 : nn, 0};
+  b.follow = follow;
   b.nk = (size_t)map.num_voxels * b.nset;
   if (b.nk >= (1ull << 31) || (size_t)map.num_points * b.nset >= (1ull << 32)) { *err = "neighbour lists: map too large"; return PCM_ERR_UNSUPPORTED; }
   // room for them?  27 x 16 B per map point for the lists (the pad entries of the point lists come on top: fill_lists, once the
@@ -346,6 +522,149 @@ int build_neighbour_lists(hipStream_t stream, const TargetMap& map, int nn, Neig
   if (rc == PCM_OK) rc = voxel_slots ? voxel_slot_rows(b) : fill_lists(b, ndt_leaves, list_entries);
   if (rc != PCM_OK) out->valid = false;
   return rc;
+}
+
+// ---------------------------------------------------------------------------
+// update_neighbour_lists in stages over one ListUpdate
+// ---------------------------------------------------------------------------
+struct ListUpdate {
+  hipStream_t stream;
+  std::string* err;
+  const TargetMap& map;
+  NeighbourLists* nl;
+  DevScratch sc;
+  int nn;
+  uint32_t nk;                    // (touched voxel, offset) keys: the most lists an update can dirty
+  uint64_t* dirty = nullptr;      // the dirty lists' keys, distinct, ascending; their number is ctr[kTotDirty]
+  unsigned long long* ctr = nullptr;   // the update's totals (kTot*), 64-bit sums
+  DirtyList* lists = nullptr;
+  uint32_t *newcap = nullptr, *reloc_off = nullptr, *isnew = nullptr, *new_off = nullptr;
+  list_pool::Totals tot;
+};
+
+// stage 1 + 2: the touched voxels dilated by the neighbourhood, sorted, duplicates removed
+static int dirty_lists(ListUpdate& u) {
+  const uint32_t nt = u.map.touched_n, nk = u.nk;
+  uint64_t *keys = nullptr, *keys_s = nullptr;
+  uint32_t *flag = nullptr, *pos = nullptr;
+  if (u.sc.take(&keys, nk, u.err, "dirty keys") || u.sc.take(&keys_s, nk, u.err, "dirty keys, sorted") || u.sc.take(&u.dirty, nk, u.err, "dirty lists")) return PCM_ERR_HIP;
+  if (u.sc.take(&flag, nk, u.err, "dirty heads") || u.sc.take(&pos, nk, u.err, "dirty ranks") || u.sc.take(&u.ctr, kTotWords, u.err, "update totals")) return PCM_ERR_HIP;
+  PCM_HIPCK_ERR(u.err, hipMemsetAsync(u.ctr, 0, sizeof(unsigned long long) * kTotWords, u.stream));
+  k_fl_dirty_keys<<<(nt + 255) / 256, 256, 0, u.stream>>>(u.map.touched, nt, u.nn, keys);
+  PCM_HIPCK_ERR(u.err, hipGetLastError());
+  if (const int rc = scratch_sort_keys(u.sc, u.err, keys, keys_s, nk, 0, 64); rc != PCM_OK) return rc;
+  k_nl_flags<<<(nk + 255) / 256, 256, 0, u.stream>>>(keys_s, nk, flag);
+  PCM_HIPCK_ERR(u.err, hipGetLastError());
+  if (const int rc = scratch_exclusive_scan(u.sc, u.err, flag, pos, nk); rc != PCM_OK) return rc;
+  k_fl_compact<<<(nk + 255) / 256, 256, 0, u.stream>>>(keys_s, flag, pos, nk, u.dirty, u.ctr);
+  PCM_HIPCK_ERR(u.err, hipGetLastError());
+  return PCM_OK;
+}
+
+// stage 3 + the first half of 4: new length, old record and the way of every dirty list; where the relocated runs and the new
+// lists go (two scans); the totals to the host -- the update's one read-back
+static int classify(ListUpdate& u) {
+  NeighbourLists* nl = u.nl;
+  const uint32_t nk = u.nk;
+  if (u.sc.take(&u.lists, nk, u.err, "dirty list records") || u.sc.take(&u.newcap, nk, u.err, "relocated capacities") || u.sc.take(&u.reloc_off, nk, u.err, "relocation offsets")) return PCM_ERR_HIP;
+  if (u.sc.take(&u.isnew, nk, u.err, "new list flags") || u.sc.take(&u.new_off, nk, u.err, "new list ids")) return PCM_ERR_HIP;
+  if (const int rc = nl->h_totals.reserve(u.stream, u.err, kTotWords, kTotWords); rc != PCM_OK) return rc;
+  k_fl_classify<<<(nk + 127) / 128, 128, 0, u.stream>>>(u.dirty, nk, view_of(u.map), u.nn, view_of(nl->index), nl->index.idx_s, nl->rec, nl->rec_cap, u.lists, u.newcap, u.isnew, u.ctr);
+  PCM_HIPCK_ERR(u.err, hipGetLastError());
+  if (const int rc = scratch_exclusive_scan(u.sc, u.err, u.newcap, u.reloc_off, nk); rc != PCM_OK) return rc;
+  if (const int rc = scratch_exclusive_scan(u.sc, u.err, u.isnew, u.new_off, nk); rc != PCM_OK) return rc;
+  PCM_HIPCK_ERR(u.err, hipMemcpyAsync(nl->h_totals.p, u.ctr, sizeof(unsigned long long) * kTotWords, hipMemcpyDeviceToHost, u.stream));
+  PCM_HIPCK_ERR(u.err, hipStreamSynchronize(u.stream));
+  const unsigned long long* h = nl->h_totals.p;
+  list_pool::Totals& t = u.tot;
+  t.dirty = h[kTotDirty]; t.new_lists = h[kTotNew]; t.reloc_entries = h[kTotRelocEntries]; t.relocated = h[kTotRelocated]; t.in_place = h[kTotInPlace];
+  t.wasted_added = h[kTotWasted]; t.live_added = h[kTotLiveAdded]; t.live_removed = h[kTotLiveRemoved]; t.became_empty = h[kTotBecameEmpty]; t.left_empty = h[kTotLeftEmpty];
+  return PCM_OK;
+}
+
+// stage 4: the dirty runs again from the updated map, in place or behind the bump pointer; the centres of new list voxels to the log
+static int rewrite(ListUpdate& u) {
+  NeighbourLists* nl = u.nl;
+  const size_t n_old = nl->num_lists, n_new = n_old + u.tot.new_lists;
+  if (u.tot.new_lists) {
+    if (const int rc = nl->centres.reserve_keep(u.stream, u.err, n_new, n_new + n_new / 4 + 1024, n_old); rc != PCM_OK) return rc;
+    if (const int rc = reserve_records(u.stream, u.err, nl, n_new, n_old); rc != PCM_OK) return rc;
+  }
+  if (u.tot.dirty) {
+    k_fl_rewrite<<<((uint32_t)u.tot.dirty + 127) / 128, 128, 0, u.stream>>>(u.dirty, (uint32_t)u.tot.dirty, view_of(u.map), u.nn, u.lists, u.newcap, u.reloc_off, u.isnew, u.new_off, (uint32_t)n_old,
+                                                                 (uint32_t)nl->pool.bump, u.map.res, nl->centres, nl->rec, nl->rec_cap, nl->pts);
+    PCM_HIPCK_ERR(u.err, hipGetLastError());
+  }
+  return PCM_OK;
+}
+
+// stage 3, second half: the new list voxels' stand-in points, appended to the log, are merged into the index (build_target_map's
+// incremental path; its own host syncs); the ranks shift, so the kernel's rank -> record table is derived again either way
+static int merge_index(ListUpdate& u) {
+  NeighbourLists* nl = u.nl;
+  if (u.tot.new_lists) {
+    uint32_t n = nl->num_lists + (uint32_t)u.tot.new_lists;   // <= dirty <= nk < 2^31
+    MapBuildOptions opt; opt.n_indexed = nl->index.index_n;
+    if (const int rc = build_target_map(u.stream, nl->centres, &n, u.map.res, u.map.coord_mode, &nl->index, u.err, opt); rc != PCM_OK) return rc;
+    if (nl->index.num_voxels != n || nl->index.num_points != n) { *u.err = "neighbour lists: index does not hold one voxel per list"; return PCM_ERR_INTERNAL; }
+    nl->num_lists = n;
+  }
+  k_fl_rank_records<<<(nl->num_lists + 255) / 256, 256, 0, u.stream>>>(nl->index.idx_s, nl->rec, nl->num_lists, nl->rank_rec);
+  PCM_HIPCK_ERR(u.err, hipGetLastError());
+  return PCM_OK;
+}
+
+int update_neighbour_lists(hipStream_t stream, const TargetMap& map, NeighbourLists* nl, std::string* err, bool* rebuild) {
+  *rebuild = false;
+  if (!nl->valid || !nl->pooled || nl->kind != 0 || !map.valid || !map.touched_valid || map.coord_mode != COORD_ROUND) { *rebuild = true; return PCM_OK; }
+  if ((size_t)map.touched_n * nl->num_neighbors >= (1ull << 31)) { *rebuild = true; return PCM_OK; }
+  if (map.touched_n == 0) { nl->stale = false; return PCM_OK; }
+  ListUpdate u{stream, err, map, nl, DevScratch(stream), nl->num_neighbors, map.touched_n * (uint32_t)nl->num_neighbors};
+  // nl->time_stages (pcm_set_profiling bit 0): HIP events around the stages, read after the update (one more synchronisation)
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  int nev = 0;
+  auto mark = [&]() { if (nl->time_stages && nev < 5 && hipEventCreate(&ev[nev]) == hipSuccess) { (void)hipEventRecord(ev[nev], stream); nev++; } };
+  for (float& m : nl->stage_ms) m = 0.f;
+  mark();
+  int rc = dirty_lists(u);
+  mark();
+  if (rc == PCM_OK) rc = classify(u);
+  mark();
+  const bool apply = rc == PCM_OK && nl->pool.decide(u.tot) == list_pool::kApply;   // stage 5: nothing was written yet
+  if (apply) rc = rewrite(u);
+  mark();
+  if (apply && rc == PCM_OK) rc = merge_index(u);
+  mark();
+  if (nev == 5 && rc == PCM_OK && hipEventSynchronize(ev[4]) == hipSuccess) {
+    for (int k = 0; k < 4; k++) (void)hipEventElapsedTime(&nl->stage_ms[k], ev[k], ev[k + 1]);
+    (void)hipEventElapsedTime(&nl->stage_ms[4], ev[0], ev[4]);
+  }
+  for (int k = 0; k < nev; k++) (void)hipEventDestroy(ev[k]);
+  if (rc == PCM_OK && !apply) { *rebuild = true; return PCM_OK; }
+  if (rc != PCM_OK) { nl->valid = false; return rc; }
+  nl->pool.apply(u.tot);
+  nl->num_candidates = (size_t)nl->pool.bump;
+  nl->stale = false;
+  return PCM_OK;
+}
+
+int export_pooled_lists(hipStream_t stream, const NeighbourLists& nl, std::vector<uint32_t>* starts, DevBuf<float4>* entries, std::string* err) {
+  const uint32_t nd = nl.num_lists;
+  DevScratch sc(stream);
+  uint32_t *len = nullptr, *start = nullptr;
+  if (sc.take(&len, (size_t)nd + 1, err, "list lengths") || sc.take(&start, (size_t)nd + 1, err, "list starts")) return PCM_ERR_HIP;
+  k_fl_lengths<<<(nd + 256) / 256, 256, 0, stream>>>(nl.rank_rec, nd, len);
+  PCM_HIPCK_ERR(err, hipGetLastError());
+  if (const int rc = scratch_exclusive_scan(sc, err, len, start, (size_t)nd + 1); rc != PCM_OK) return rc;
+  starts->resize((size_t)nd + 1);
+  PCM_HIPCK_ERR(err, hipMemcpyAsync(starts->data(), start, sizeof(uint32_t) * ((size_t)nd + 1), hipMemcpyDeviceToHost, stream));
+  PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
+  const size_t total = starts->back();
+  if (const int rc = entries->reserve(stream, err, total, total); rc != PCM_OK) return rc;
+  k_fl_export<<<(nd + 127) / 128, 128, 0, stream>>>(nl.rank_rec, start, nd, nl.pts, entries->p);
+  PCM_HIPCK_ERR(err, hipGetLastError());
+  PCM_HIPCK_ERR(err, hipStreamSynchronize(stream));
+  return PCM_OK;
 }
 
 // distance2() of ivox3d_node.hpp:13-16, the operations of best_offer in its order
@@ -375,7 +694,9 @@ __device__ inline void walk_offer(KeyedBest& kb, const float4 (&c)[kListTrip], c
 // ---------------------------------------------------------------------------
 // k_linearize_lists: grid (ceil(N / 256), pairs), one scan point per lane
 // ---------------------------------------------------------------------------
-template <bool WRITE_PLANES>
+// POOLED: following lists -- the run of list r is the 8-byte record rank_rec[r] = (start, length) in the pool (the view's vox_start
+// points at the records); the walk is the same code.
+template <bool WRITE_PLANES, bool POOLED = false>
 __global__ void __launch_bounds__(256) k_linearize_lists(const PairDesc* __restrict__ descs, const PairState* __restrict__ states, KernelParams kp) {
   // the tile placement of k_linearize (kernels.hip): neighbouring tiles of a pair share an XCD (they read the same lists)
   uint32_t tile_x = blockIdx.x;
@@ -411,7 +732,13 @@ __global__ void __launch_bounds__(256) k_linearize_lists(const PairDesc* __restr
         const uint32_t m = gload_u(&nl.bmask[(size_t)slot * 16 + w]);
         if ((m >> bit) & 1u) {
           const uint32_t r = vox_base + gload_u16(&nl.bpref[(size_t)slot * 16 + w]) + (uint32_t)__popc(m & ((1u << bit) - 1u));
-          const uint32_t s = gload_u(&nl.vox_start[r]), e = gload_u(&nl.vox_start[r + 1]);
+          uint32_t s, e;
+          if constexpr (POOLED) {
+            const unsigned long long run_rec = *(const PCM_GLOBAL unsigned long long*)(reinterpret_cast<const unsigned long long*>(nl.vox_start) + r);   // one 8-byte load
+            s = (uint32_t)run_rec; e = s + (uint32_t)(run_rec >> 32);
+          } else {
+            s = gload_u(&nl.vox_start[r]); e = gload_u(&nl.vox_start[r + 1]);
+          }
           // the voxel's candidates in the reference's visit order, four per trip.  The run is padded to whole trips and starts on a
           // 64-byte boundary (build_neighbour_lists), so e - s is a multiple of four: no bounds test, all four loads under way and all
           // four distances formed before the first offer.  A load past the run's true end is a pad entry (d2 = +inf) and is never
@@ -501,9 +828,11 @@ __global__ void __launch_bounds__(256) k_linearize_lists(const PairDesc* __restr
   residual_and_reduce<WRITE_PLANES>(d, i, tile_x, live, pl, q, pn_body, s_mem);
 }
 
-void launch_linearize_lists(hipStream_t stream, const PairDesc* d_descs, const PairState* d_states, const KernelParams& kp, int npairs, bool write_planes) {
+void launch_linearize_lists(hipStream_t stream, const PairDesc* d_descs, const PairState* d_states, const KernelParams& kp, int npairs, bool write_planes, bool pooled) {
   dim3 grid((unsigned)kp.tiles_per_pair, (unsigned)npairs);
-  if (write_planes) k_linearize_lists<true><<<grid, 256, 0, stream>>>(d_descs, d_states, kp);
+  if (pooled && write_planes) k_linearize_lists<true, true><<<grid, 256, 0, stream>>>(d_descs, d_states, kp);
+  else if (pooled) k_linearize_lists<false, true><<<grid, 256, 0, stream>>>(d_descs, d_states, kp);
+  else if (write_planes) k_linearize_lists<true><<<grid, 256, 0, stream>>>(d_descs, d_states, kp);
   else k_linearize_lists<false><<<grid, 256, 0, stream>>>(d_descs, d_states, kp);
 }
 

@@ -1271,12 +1271,58 @@ int pcm_get_neighbour_lists(pcm_ctx* c, uint64_t info[2], float* centres, uint32
   CHECK_CTX(c);
   const pcm::NeighbourLists& nl = c->tg->nlists;
   if (!info || !nl.valid || nl.kind != 0) { c->err = "pcm_get_neighbour_lists: the context holds no candidate lists of points (P2PLANE, static target, lists built)"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (nl.pooled) {   // following lists: brought up to date first, then the pooled runs gathered into contiguous order
+    if (!c->tg->map.valid && c->src.n) {
+      const int rc = prepare(c);
+      if (rc != PCM_OK) return rc;
+    }
+    if (!nl.valid || nl.stale || !c->tg->map.valid) { c->err = "pcm_get_neighbour_lists: the following lists are behind the target (set a source, or register once)"; return PCM_ERR_INVALID_ARGUMENT; }
+    std::vector<uint32_t> h_starts;
+    pcm::DevBuf<float4> gathered{"gathered lists"};
+    const int rc = pcm::export_pooled_lists(c->stream, nl, &h_starts, &gathered, &c->err);
+    if (rc != PCM_OK) return rc;
+    info[0] = nl.num_lists;
+    info[1] = h_starts.back();
+    if (centres) PCM_HIPCK(c, hipMemcpy(centres, nl.index.pts.p, sizeof(float4) * nl.num_lists, hipMemcpyDeviceToHost));
+    if (starts) std::memcpy(starts, h_starts.data(), sizeof(uint32_t) * h_starts.size());
+    if (entries && info[1]) PCM_HIPCK(c, hipMemcpy(entries, gathered.p, sizeof(float4) * info[1], hipMemcpyDeviceToHost));
+    return PCM_OK;
+  }
   info[0] = nl.num_lists;
   info[1] = nl.num_candidates;
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   if (centres) PCM_HIPCK(c, hipMemcpy(centres, nl.index.pts.p, sizeof(float4) * nl.num_lists, hipMemcpyDeviceToHost));
   if (starts) PCM_HIPCK(c, hipMemcpy(starts, nl.start.p, sizeof(uint32_t) * ((size_t)nl.num_lists + 1), hipMemcpyDeviceToHost));
   if (entries && nl.num_candidates) PCM_HIPCK(c, hipMemcpy(entries, nl.pts.p, sizeof(float4) * nl.num_candidates, hipMemcpyDeviceToHost));
+  return PCM_OK;
+}
+
+int pcm_neighbour_list_info(pcm_ctx* c, uint64_t info[8]) {
+  CHECK_CTX(c);
+  if (!info) { c->err = "pcm_neighbour_list_info: null info"; return PCM_ERR_INVALID_ARGUMENT; }
+  for (int k = 0; k < 8; k++) info[k] = 0;
+  const pcm::NeighbourLists& nl = c->tg->nlists;
+  if (!nl.valid || nl.kind != 0 || pcm::lists_view_for(c).pts == nullptr) return PCM_OK;   // no candidate lists, or none this configuration reads
+  info[0] = nl.num_lists;
+  if (!nl.pooled) { info[1] = nl.num_candidates; info[2] = nl.pts.cap; return PCM_OK; }
+  const pcm::list_pool::Pool& p = nl.pool;
+  info[1] = p.live; info[2] = p.capacity; info[3] = p.wasted; info[4] = p.updates; info[5] = p.in_place; info[6] = p.relocated; info[7] = p.rebuilds;
+  return PCM_OK;
+}
+
+int pcm_neighbour_list_update_ms(pcm_ctx* c, double ms[5]) {
+  CHECK_CTX(c);
+  if (!ms) { c->err = "pcm_neighbour_list_update_ms: null ms"; return PCM_ERR_INVALID_ARGUMENT; }
+  for (int k = 0; k < 5; k++) ms[k] = (double)c->tg->nlists.stage_ms[k];
+  return PCM_OK;
+}
+
+int pcm_neighbour_list_headroom(pcm_ctx* c, float fraction, uint64_t min_entries) {
+  CHECK_CTX(c);
+  if (!(fraction >= 0.f) || fraction > 16.f || min_entries >= (1ull << 31)) { c->err = "pcm_neighbour_list_headroom: fraction in [0, 16], min_entries below 2^31"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (c->tg.shared()) return refuse_shared(c, "pcm_neighbour_list_headroom");
+  c->tg->nl_follow.headroom_fraction = fraction;
+  c->tg->nl_follow.headroom_min = min_entries;
   return PCM_OK;
 }
 

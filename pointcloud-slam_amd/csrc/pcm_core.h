@@ -24,6 +24,8 @@ const char* target_config_difference(const pcm_config& a, const pcm_config& b);
 int build_target_for_sharing(pcm_ctx* c);
 // the lists the context's residual kernel reads (kind 0 or 2), or an empty view: they exist and the policy still wants them
 TargetView lists_view_for(const pcm_ctx* c);
+// ... and whether they are the pooled form of following lists (k_linearize_lists' second template argument)
+bool lists_pooled_for(const pcm_ctx* c);
 // pclomp NDT: the neighbour-leaf lists of the context's grid, or an empty view (the cells are then looked up one by one)
 TargetView ndt_lists_view(const pcm_ctx* c);
 

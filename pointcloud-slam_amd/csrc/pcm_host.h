@@ -9,6 +9,7 @@
 
 #include "../../include/pcm_amd.h"
 #include "dev_buf.h"
+#include "list_pool.h"
 #include "lio_iekf.h"
 #include "lio_outputs.h"
 #include "lsq_step.h"
@@ -54,6 +55,11 @@ struct TargetMap {   // layout: pcm_device.h
   uint32_t index_n = 0;         // log points keys_s / idx_s cover (0: no usable index)
   DevBuf<char> arena{"map update arena"};   // scratch of the incremental updates (grow-only; the build's DevScratch carves it)
   PinnedBuf<int> h_ctr{"counters"};         // pinned host copy of the build's counter record (one read-back per synchronisation point)
+  // MapBuildOptions::collect_touched, after an incremental build: the point keys (point_key) of the batch's points, sorted, then
+  // of the voxels the LRU eviction removed; touched_n entries, ~0 where there is none.  What following lists are updated from.
+  DevBuf<uint64_t> touched{"touched voxel keys"};
+  uint32_t touched_n = 0;
+  bool touched_valid = false;   // the last build was an update and left them
   uint32_t cap = 0, num_voxels = 0, num_bricks = 0, num_points = 0;
   uint32_t max_voxel_points = 0;   // most points in one voxel
   float res = 0.f, inv_res = 0.f;
@@ -79,6 +85,7 @@ struct MapBuildOptions {
   uint32_t capacity_voxels = 0;   // > 1: LRU eviction down to capacity - 1 voxels; log and *n_inout shrink with it
   uint32_t n_indexed = 0;    // > 0: the first n_indexed log points are what map->keys_s / idx_s index; only the points behind are new
   uint32_t* lru_hazards = nullptr;   // out: voxels the batch rule of the eviction kept whole (pcm_stats.lru_batch_hazards)
+  bool collect_touched = false;      // an update leaves the voxels it added points to or evicted in TargetMap::touched
 };
 // Builds `map` from the point log d_pts[0 .. *n_inout): the sorted (key, log position) index, the voxel heads, the brick table,
 // the points gathered brick-major.  A run of named stages over one scoped scratch (voxel_hash.hip, DESIGN.md "Build stages"); an
@@ -153,11 +160,37 @@ struct NeighbourLists {
   int num_neighbors = 0;      // the neighbourhood the lists were built for
   int kind = 0;               // 0: candidate points (P2PLANE); 1: neighbour leaves of a pclomp NDT grid (centroid, leaf index); 2: rows of neighbour voxel indices (k_ndt)
   bool valid = false;
+  // Following lists (PCM_FLAG_FOLLOWING_LISTS; kind 0): the runs live in a pool -- `pts` with room behind the runs -- and a list
+  // is a (start, length) record.  A list's id is the position of its stand-in point in `centres`, the log `index` is built from and
+  // merged into, so it survives the renumbering of the ranks; `rec` / `rec_cap` are kept by id, `rank_rec` is what the kernel reads.
+  bool pooled = false;
+  bool stale = false;         // the map was updated since the lists were: update_neighbour_lists is due
+  DevBuf<float4> centres{"list voxel centres"};
+  DevBuf<uint2> rec{"list records"};
+  DevBuf<uint32_t> rec_cap{"list capacities"};
+  DevBuf<uint2> rank_rec{"list records by rank"};
+  PinnedBuf<unsigned long long> h_totals{"list update totals"};
+  bool time_stages = false;   // HIP events around the update's stages (pcm_set_profiling bit 0)
+  float stage_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};   // the last timed update: dirty lists, classify + read-back, rewrite, index merge + rank table, all
+  list_pool::Pool pool;
   void release() { this->~NeighbourLists(); new (this) NeighbourLists(); }   // as TargetMap::release
 };
-int build_neighbour_lists(hipStream_t stream, const TargetMap& map, int num_neighbors, NeighbourLists* out, std::string* err, const PclLeaf* ndt_leaves = nullptr, bool voxel_slots = false);
+// follow != nullptr (kind 0 only): the pooled form, with the room behind the runs that *follow asks for
+struct ListFollow {
+  float headroom_fraction = list_pool::kDefaultHeadroomFraction;
+  uint64_t headroom_min = list_pool::kDefaultHeadroomMin;
+  bool by_policy = false;   // this build replaces an update (counted as a full rebuild)
+};
+int build_neighbour_lists(hipStream_t stream, const TargetMap& map, int num_neighbors, NeighbourLists* out, std::string* err, const PclLeaf* ndt_leaves = nullptr, bool voxel_slots = false,
+                          const ListFollow* follow = nullptr);
+// Following lists after an update of `map` that left map.touched: the lists within the neighbourhood of a touched voxel are
+// rewritten (in place, or at the pool's bump pointer), new list voxels are merged into the index.  *rebuild: the pool's policy
+// (list_pool.h) asks for a full build instead, nothing was changed.  One read-back, plus the index merge's own when there are new list voxels.
+int update_neighbour_lists(hipStream_t stream, const TargetMap& map, NeighbourLists* nl, std::string* err, bool* rebuild);
+// the pooled runs gathered into contiguous order by rank (parity hook): starts [num_lists + 1] on the host, the entries on the device
+int export_pooled_lists(hipStream_t stream, const NeighbourLists& nl, std::vector<uint32_t>* starts, DevBuf<float4>* entries, std::string* err);
 TargetView view_of_lists(const NeighbourLists& l);
-void launch_linearize_lists(hipStream_t stream, const PairDesc* d_descs, const PairState* d_states, const KernelParams& kp, int npairs, bool write_planes);
+void launch_linearize_lists(hipStream_t stream, const PairDesc* d_descs, const PairState* d_states, const KernelParams& kp, int npairs, bool write_planes, bool pooled = false);
 void launch_linearize_reforder(hipStream_t stream, const PairDesc* d_descs, const PairState* d_states, const KernelParams& kp, int npairs, bool write_planes);
 void launch_linearize_fused(hipStream_t stream, const PairDesc* d_descs, PairState* d_states, const KernelParams& kp, const LsqParams& lp, int npairs, unsigned char* d_flags_row);
 void launch_lio_obs(hipStream_t stream, const PairDesc* d_descs, const PairState* d_states, const KernelParams& kp);
@@ -206,7 +239,8 @@ struct TargetState {
   bool tgt_dynamic = false;       // the target grew since pcm_set_target (pcm_target_insert / pcm_map_incremental)
   bool nlists_failed = false;     // the lists of this map could not be built (memory): not tried again
   int map_uses = 0;               // prepare() calls since the map was (re)built; stands still while the target is shared
-  NeighbourLists nlists;          // candidate lists of `map` (static targets; NeighbourLists::kind)
+  NeighbourLists nlists;          // candidate lists of `map` (static targets, or following ones; NeighbourLists::kind)
+  ListFollow nl_follow;           // pcm_neighbour_list_headroom: the room a full build of following lists reserves
   // GICP / VGICP: per-point covariances in MAP order, voxel distributions
   DevBuf<double> tgt_cov{"tgt_cov"};   // 6 doubles per point
   bool tgt_cov_valid = false;

@@ -54,16 +54,20 @@ size_t neighbor_slots(const pcm_config& g) {
 // map; fast_gicp/src/align.cpp:51-104 is no such protocol: it clears the target on every iteration and its reuse loop swaps source
 // and target); PCM_FLAG_NEIGHBOUR_LISTS builds them with the map, PCM_FLAG_NO_NEIGHBOUR_LISTS never, and a build that failed is
 // not tried again for this map.  Which kind (NeighbourLists::kind) the context wants now, -1 for none:
-//   0  P2PLANE against a static target: k_linearize_lists runs on per-voxel candidate lists.  A target that grows through
-//      pcm_target_insert / pcm_map_incremental would rebuild them with every batch: it keeps the tile kernel.
+//   0  P2PLANE: k_linearize_lists runs on per-voxel candidate lists.  Against a target that grows through pcm_target_insert /
+//      pcm_map_incremental only under PCM_FLAG_FOLLOWING_LISTS, which keeps the lists of the touched neighbourhoods up to date
+//      with every batch (update_following_lists below); without it such a target keeps the tile kernel.
 //   1  pclomp NDT: neighbour leaves of the grid (whether the target grew is not looked at)
 //   2  fast_gicp NDTCuda (P2D / D2D) and VGICP of the CUDA core with a DIRECT neighbourhood: k_ndt reads rows of neighbour voxel indices
+// the pooled form is what a P2PLANE context with PCM_FLAG_FOLLOWING_LISTS builds and reads; the flag means nothing to another model
+bool wants_following(const pcm_ctx* c) { return c->cfg.model == PCM_MODEL_P2PLANE && (c->cfg.flags & PCM_FLAG_FOLLOWING_LISTS) != 0; }
+
 int wanted_list_kind(const pcm_ctx* c) {
   const pcm_config& g = c->cfg;
   int kind = -1;
   if (g.model == PCM_MODEL_P2PLANE) {
     const int other_kernel = PCM_FLAG_REFERENCE_KNN_ORDER | PCM_FLAG_COUNTED_SEARCH | PCM_FLAG_NO_LDS_STAGING | PCM_FLAG_FUSED_STEP;
-    if (!c->tg->tgt_dynamic && !(g.flags & other_kernel)) kind = 0;
+    if ((!c->tg->tgt_dynamic || wants_following(c)) && !(g.flags & other_kernel)) kind = 0;
   } else if (g.model == PCM_MODEL_NDT_OMP) {
     kind = 1;
   } else if (radius_model(g.model)) {
@@ -71,17 +75,36 @@ int wanted_list_kind(const pcm_ctx* c) {
   }
   if (kind < 0 || c->tg->nlists_failed || (g.flags & PCM_FLAG_NO_NEIGHBOUR_LISTS)) return -1;
   if (c->tg.shared()) return c->tg->nlists.valid ? kind : -1;   // nothing is built for a shared target: the lists pcm_share_target left, or none
-  return ((g.flags & PCM_FLAG_NEIGHBOUR_LISTS) != 0 || c->tg->map_uses >= 2) ? kind : -1;
+  return ((g.flags & PCM_FLAG_NEIGHBOUR_LISTS) != 0 || wants_following(c) || c->tg->map_uses >= 2) ? kind : -1;
 }
 
-bool has_lists_of_kind(const pcm_ctx* c, int kind) { return c->tg->nlists.valid && c->tg->nlists.kind == kind && c->tg->nlists.num_neighbors == c->cfg.num_neighbors; }
+bool has_lists_of_kind(const pcm_ctx* c, int kind) {
+  const NeighbourLists& l = c->tg->nlists;
+  return l.valid && l.kind == kind && l.num_neighbors == c->cfg.num_neighbors && (kind != 0 || c->tg.shared() || l.pooled == wants_following(c));
+}
+
+// Following lists after the map's update (merge and LRU eviction done): the lists around the touched voxels are rewritten, or --
+// the pool's policy, list_pool.h -- everything is built again.  A failure is the caller's: the flag asked for lists.
+int update_following_lists(pcm_ctx* c) {
+  NeighbourLists& l = c->tg->nlists;
+  bool rebuild = false;
+  l.time_stages = (c->profiling & 1) != 0;
+  int rc = update_neighbour_lists(c->stream, c->tg->map, &l, &c->err, &rebuild);
+  if (rc == PCM_OK && rebuild) {
+    ListFollow f = c->tg->nl_follow; f.by_policy = true;
+    rc = build_neighbour_lists(c->stream, c->tg->map, c->cfg.num_neighbors, &l, &c->err, nullptr, false, &f);
+  }
+  return rc;
+}
 
 // builds the lists of `kind` (wanted_list_kind; -1: nothing to do) unless the context holds them, once per (static) target
 int ensure_neighbour_lists(pcm_ctx* c, int kind) {
-  if (kind < 0 || has_lists_of_kind(c, kind) || c->tg.shared()) return PCM_OK;
-  const int rc = build_neighbour_lists(c->stream, c->tg->map, c->cfg.num_neighbors, &c->tg->nlists, &c->err, kind == 1 ? c->tg->pleaf.p : nullptr, kind == 2);
+  if (kind < 0 || c->tg.shared()) return PCM_OK;
+  if (has_lists_of_kind(c, kind)) return c->tg->nlists.stale ? update_following_lists(c) : PCM_OK;
+  const bool follow = kind == 0 && wants_following(c);
+  const int rc = build_neighbour_lists(c->stream, c->tg->map, c->cfg.num_neighbors, &c->tg->nlists, &c->err, kind == 1 ? c->tg->pleaf.p : nullptr, kind == 2, follow ? &c->tg->nl_follow : nullptr);
   if (rc != PCM_OK) {
-    if (c->cfg.flags & PCM_FLAG_NEIGHBOUR_LISTS) return rc;   // asked for explicitly
+    if ((c->cfg.flags & PCM_FLAG_NEIGHBOUR_LISTS) || wants_following(c)) return rc;   // asked for explicitly
     c->tg->nlists_failed = true;                                   // e.g. no memory for them: the kernel without lists serves this target
     c->tg->nlists.release();
     c->err.clear();
@@ -115,6 +138,9 @@ int ensure_target_map(pcm_ctx* c) {
     // into the sorted index it kept (voxel_hash.hip); anything else is built from scratch
     uint32_t hazards = 0;
     MapBuildOptions opt; opt.gauss = gauss; opt.keep_order = gicp; opt.capacity_voxels = capacity; opt.n_indexed = c->tg->map.index_n; opt.lru_hazards = &hazards;
+    // following lists that are up to date with the map as it is: the update leaves them the voxels it touched
+    const NeighbourLists& fl = c->tg->nlists;
+    opt.collect_touched = wants_following(c) && fl.valid && fl.pooled && !fl.stale && fl.kind == 0;
     int rc = build_target_map(c->stream, c->tg->tgt.d_pts, &n_log, c->cfg.voxel_resolution, mode, &c->tg->map, &c->err, opt);
     c->stats.lru_batch_hazards += hazards;
     c->tg->tgt.n = n_log;   // LRU eviction compacts the point log
@@ -123,7 +149,8 @@ int ensure_target_map(pcm_ctx* c) {
     c->stats.target_slots = c->tg->map.cap;
     c->tg->tgt_cov_valid = false;
     c->tg->pleaf_valid = false;
-    c->tg->nlists.valid = false;
+    if (opt.collect_touched && c->tg->map.touched_valid) c->tg->nlists.stale = true;   // brought up to date by ensure_neighbour_lists
+    else c->tg->nlists.valid = false;
     c->tg->nlists_failed = false;
     c->tg->map_uses = 0;
   }
@@ -277,6 +304,8 @@ int ensure_pair_buffers(pcm_ctx* c) {
 
 }  // namespace
 
+bool lists_pooled_for(const pcm_ctx* c) { return c->tg->nlists.valid && c->tg->nlists.kind == 0 && c->tg->nlists.pooled; }
+
 TargetView lists_view_for(const pcm_ctx* c) {
   const int kind = wanted_list_kind(c);
   const bool on = (kind == 0 || kind == 2) && has_lists_of_kind(c, kind);   // kind 1 is read through ndt_lists_view
@@ -310,7 +339,7 @@ int prepare(pcm_ctx* c) {
 //   voxel_resolution        the map's cell size (ensure_target_map); the pclomp NDT leaves are a function of the map alone
 //   num_neighbors, neighbor_search_radius
 //                           the neighbourhood the lists are built for, and whether kind-2 lists exist (has_lists_of_kind, wanted_list_kind)
-//   flags & kTargetFlags    PCM_FLAG_NEIGHBOUR_LISTS / PCM_FLAG_NO_NEIGHBOUR_LISTS and the kernel flags next to which no lists are made
+//   flags & kTargetFlags    PCM_FLAG_NEIGHBOUR_LISTS / PCM_FLAG_FOLLOWING_LISTS / PCM_FLAG_NO_NEIGHBOUR_LISTS and the kernel flags next to which no lists are made
 //   map_capacity            P2PLANE: the LRU capacity the map was built under (ensure_target_map)
 //   k_correspondences, regularization, voxel_mode, covariance_method, rbf_kernel_width, rbf_max_dist
 //                           GICP family: the covariances and the voxel distributions made of them (prepare_gicp, ensure_covariances)
@@ -318,7 +347,7 @@ int prepare(pcm_ctx* c) {
 // outlier ratio, sort_source, batch_window) are read per registration and may differ between holders.
 // Returns the name of the first field that differs, or null.
 const char* target_config_difference(const pcm_config& a, const pcm_config& b) {
-  constexpr int kTargetFlags = PCM_FLAG_NEIGHBOUR_LISTS | PCM_FLAG_NO_NEIGHBOUR_LISTS | PCM_FLAG_REFERENCE_KNN_ORDER | PCM_FLAG_COUNTED_SEARCH | PCM_FLAG_NO_LDS_STAGING |
+  constexpr int kTargetFlags = PCM_FLAG_NEIGHBOUR_LISTS | PCM_FLAG_FOLLOWING_LISTS | PCM_FLAG_NO_NEIGHBOUR_LISTS | PCM_FLAG_REFERENCE_KNN_ORDER | PCM_FLAG_COUNTED_SEARCH | PCM_FLAG_NO_LDS_STAGING |
                                PCM_FLAG_FUSED_STEP;
   if (a.model != b.model) return "model";
   if (a.voxel_resolution != b.voxel_resolution) return "voxel_resolution";

@@ -336,6 +336,15 @@ __global__ void k_lru_hazards(const float4* __restrict__ log, const uint32_t* __
   const uint32_t before = __float_as_uint(log[idx_s[k]].w);
   if (before < seq0 && before < cutoff) atomicAdd(out, 1u);
 }
+// MapBuildOptions::collect_touched: the key of every voxel none of whose points survives the eviction, appended behind the batch's
+// keys in any order (the consumer sorts them); at most `room` of them (the eviction removes exactly nvox - keep voxels)
+__global__ void k_evicted_voxels(const uint64_t* __restrict__ keys_s, const uint32_t* __restrict__ idx_s, const uint32_t* __restrict__ vflag, const uint32_t* __restrict__ alive_log, uint32_t n,
+                                 uint64_t* __restrict__ out, uint32_t room, unsigned int* __restrict__ count) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || !vflag[i] || alive_log[idx_s[i]]) return;   // a voxel lives or dies whole: its head speaks for it
+  const uint32_t at = atomicAdd(count, 1u);
+  if (at < room) out[at] = keys_s[i];
+}
 __global__ void k_voxel_firsts(const uint32_t* __restrict__ vflag, const uint32_t* __restrict__ vrank, uint32_t n, uint32_t* __restrict__ vox_first) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n && vflag[i]) vox_first[vrank[i]] = i;
@@ -372,12 +381,14 @@ struct MapBuild {
   uint32_t* n_log;        // its owner's count of it: follows an eviction's compaction
   DevScratch sc;          // a sliding map's update: over its grow-only arena (no allocation call at all: two dozen pool calls were
                           // a third of an update's wall time); any other build: the stream-ordered pool
-  int* d_flags = nullptr;   // [0] out-of-range flag, [1] brick count, [2] most points in one voxel, [3] LRU hazards, [4] voxels, [5] log points alive
+  int* d_flags = nullptr;   // [0] out-of-range flag, [1] brick count, [2] most points in one voxel, [3] LRU hazards, [4] voxels, [5] log points alive, [6] evicted voxels collected
   uint32_t *vflag = nullptr, *vrank = nullptr;   // voxel head flag of every sorted key, and its exclusive scan
   uint32_t n = 0, n_indexed = 0, nvox = 0, nbricks = 0, cap = 0, hazards = 0;
   float res = 0.f, inv_res = 0.f;
   int coord_mode = 0;
   bool incremental = false;
+  bool collect = false;     // MapBuildOptions::collect_touched of an incremental build
+  uint32_t touched_n = 0;   // entries of map->touched
   MapBuild(hipStream_t s, std::string* e, TargetMap* m, float4* pts, uint32_t* np, char* arena, size_t arena_bytes) : stream(s), err(e), map(m), d_pts(pts), n_log(np), sc(s, arena, arena_bytes) {}
 };
 
@@ -411,6 +422,11 @@ static int sort_index(MapBuild& b) {
       PCM_HIPCK_ERR(b.err, hipGetLastError());
       map->keys_s.swap(map->keys_t);
       map->idx_s.swap(map->idx_t);
+      if (b.collect) {   // the voxels the batch added points to: its sorted keys as they are (duplicates are the consumer's business)
+        if (const int rc = map->touched.reserve(b.stream, b.err, m, headroom(m)); rc != PCM_OK) return rc;
+        PCM_HIPCK_ERR(b.err, hipMemcpyAsync(map->touched, keys_bs, sizeof(uint64_t) * (size_t)m, hipMemcpyDeviceToDevice, b.stream));
+        b.touched_n = m;
+      }
     }
   }
   map->index_n = 0;   // until this build is through
@@ -476,6 +492,14 @@ static int evict_lru(MapBuild& b, uint32_t keep) {
   if (const int rc = scratch_exclusive_scan(b.sc, b.err, alive, pos, (size_t)n); rc != PCM_OK) return rc;
   k_alive_sorted<<<cdiv(n, 256), 256, 0, b.stream>>>(map->idx_s, alive, n, alive_s);
   if (const int rc = scratch_exclusive_scan(b.sc, b.err, alive_s, pos_s, (size_t)n); rc != PCM_OK) return rc;
+  if (b.collect) {   // the voxels that go, behind the batch's keys
+    const uint32_t gone = nvox - keep, have = b.touched_n;
+    if (const int rc = map->touched.reserve_keep(b.stream, b.err, (size_t)have + gone, headroom((size_t)have + gone), have); rc != PCM_OK) return rc;
+    PCM_HIPCK_ERR(b.err, hipMemsetAsync(map->touched + have, 0xFF, sizeof(uint64_t) * (size_t)gone, b.stream));
+    k_evicted_voxels<<<cdiv(n, 256), 256, 0, b.stream>>>(map->keys_s, map->idx_s, b.vflag, alive, n, map->touched + have, gone, reinterpret_cast<unsigned int*>(b.d_flags + 6));
+    PCM_HIPCK_ERR(b.err, hipGetLastError());
+    b.touched_n = have + gone;
+  }
   k_compact_log<<<cdiv(n, 256), 256, 0, b.stream>>>(b.d_pts, alive, pos, n, tmp_log);
   k_compact_index<<<cdiv(n, 256), 256, 0, b.stream>>>(map->keys_s, map->idx_s, alive, pos, pos_s, n, map->keys_t, map->idx_t);
   k_count_alive<<<1, 1, 0, b.stream>>>(alive, pos, n, b.d_flags);
@@ -548,6 +572,8 @@ static int publish(const MapBuild& b) {
   map->inv_res = b.inv_res;
   map->coord_mode = b.coord_mode;
   map->index_n = b.n;
+  map->touched_n = b.touched_n;
+  map->touched_valid = b.collect;
   map->valid = true;
   return PCM_OK;
 }
@@ -561,6 +587,8 @@ int build_target_map(hipStream_t stream, float4* d_pts, uint32_t* n_inout, float
   const bool incremental = opt.n_indexed > 0 && opt.n_indexed <= n && map->keys_s && map->idx_s && map->index_n == opt.n_indexed && map->res == res && map->coord_mode == coord_mode &&
                            !opt.gauss && !opt.keep_order;
   map->valid = false;
+  map->touched_valid = false;
+  map->touched_n = 0;
   if (map->h_ctr.reserve(stream, err, kCtrInts, kCtrInts) != PCM_OK) return PCM_ERR_HIP;
   int rc = PCM_OK;
   if (incremental) {   // everything an update with eviction takes, rounded up: 24 B per new point, 52 B per log point, sort / scan temporaries
@@ -568,7 +596,7 @@ int build_target_map(hipStream_t stream, float4* d_pts, uint32_t* n_inout, float
     rc = map->arena.reserve(stream, err, need, need + need / 4);
   }
   MapBuild b(stream, err, map, d_pts, n_inout, incremental ? map->arena.p : nullptr, incremental ? map->arena.cap : 0);
-  b.n = n; b.n_indexed = opt.n_indexed; b.incremental = incremental; b.res = res; b.coord_mode = coord_mode;
+  b.n = n; b.n_indexed = opt.n_indexed; b.incremental = incremental; b.collect = incremental && opt.collect_touched; b.res = res; b.coord_mode = coord_mode;
   // ivox3d.h:67  inv_resolution_ = 1.0 / resolution_ (float);  pcl::VoxelGrid: inverse_leaf_size_ = 1 / leaf_size_ in float
   b.inv_res = coord_mode == COORD_FLOOR_MUL ? 1.0f / res : (float)(1.0 / res);
   if (rc == PCM_OK) rc = clear_counters(b);

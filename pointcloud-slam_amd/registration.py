@@ -431,6 +431,28 @@ class Registration:
         self._check(self._L.pcm_get_neighbour_lists(self._h, info.ctypes.data, centres.ctypes.data, starts.ctypes.data, entries.ctypes.data))
         return centres[:, :3].copy(), starts, entries[:, :3].copy(), entries[:, 3].copy().view(np.uint32)
 
+    following_lists = capi.PCM_FLAG_FOLLOWING_LISTS   # flags=...: candidate lists that follow a growing P2PLANE target
+
+    def neighbour_list_info(self) -> dict:
+        """The candidate lists the linearize pass reads (pcm_neighbour_list_info); all zero without lists.  For following lists:
+        the pool's wasted entries, the updates since the last full build, and -- since the lists were first built -- the runs
+        rewritten in place, the runs relocated and the full builds the pool's policy asked for."""
+        info = np.zeros(8, np.uint64)
+        self._check(self._L.pcm_neighbour_list_info(self._h, info.ctypes.data))
+        names = ("lists", "live_entries", "capacity", "wasted_entries", "updates", "in_place", "relocated", "rebuilds")
+        return {k: int(v) for k, v in zip(names, info)}
+
+    def neighbour_list_update_ms(self) -> dict:
+        """Device time of the last following-lists update timed under set_profiling(1) (pcm_neighbour_list_update_ms), by stage."""
+        ms = np.zeros(5)
+        self._check(self._L.pcm_neighbour_list_update_ms(self._h, ms.ctypes.data))
+        return dict(zip(("dirty_lists", "classify", "rewrite", "index_merge", "total"), (float(v) for v in ms)))
+
+    def set_neighbour_list_headroom(self, fraction: float, min_entries: int):
+        """Room a full build of following lists reserves behind the runs: max(fraction * entries, min_entries) entries
+        (pcm_neighbour_list_headroom; default one and a half times the entries, at least 65536)."""
+        self._check(self._L.pcm_neighbour_list_headroom(self._h, C.c_float(fraction), int(min_entries)))
+
     def get_planes(self, n: int) -> np.ndarray:
         """(n,4) planes fitted by the last evaluate_cost (NaN row = point not selected)."""
         out = np.zeros((n, 4), np.float32)
