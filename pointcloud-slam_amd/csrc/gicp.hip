@@ -17,6 +17,7 @@
 // All covariance / Mahalanobis / normal-equation arithmetic is double, as in the reference.
 // Compiled with -ffp-contract=off (see kernels.hip).
 #include "pcm_device.h"
+#include "brick_table.h"
 #include "pcm_host.h"
 #include "dev_linalg.h"
 
@@ -26,8 +27,6 @@
 namespace pcm {
 
 namespace {
-
-__device__ inline uint64_t slot_key(const uint4& s) { return ((uint64_t)s.y << 32) | s.x; }
 
 // Visit every map point whose voxel lies under the box q +- rb.  A point p with |p - q|_inf <= rb is
 // visited: the voxel coordinate is monotone in the position.  Inside a brick the voxels of one (x, y)
@@ -739,12 +738,6 @@ __device__ inline int vg_lookup(const TargetView& tg, int vx, int vy, int vz) {
   const uint32_t m = gload_u(&tg.bmask[(size_t)h * 16 + w]);
   if (!((m >> bit) & 1u)) return -1;
   return (int)(s.z + gload_u16(&tg.bpref[(size_t)h * 16 + w]) + (uint32_t)__popc(m & ((1u << bit) - 1u)));
-}
-
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 __device__ inline void load6(const double* p, double (&C)[9]) {

@@ -373,17 +373,7 @@ __global__ void __launch_bounds__(256, 5) k_linearize(const PairDesc* __restrict
         uint32_t npts = 0, ps = 0;
         if (lane < nb) {
           const int z = lane % nbz, xy = lane / nbz, y = xy % nby, x = xy / nby;
-          const uint64_t key = pack_brick(bx0 + x, by0 + y, bz0 + z);
-          uint32_t h = hash_coord(bx0 + x, by0 + y, bz0 + z) & tg.mask;
-          for (;;) {   // both halves of the 32-byte slot in flight together
-            const uint4 s0 = gload4u(&tg.bricks[h]);
-            const uint4 s1 = gload4u(reinterpret_cast<const char*>(&tg.bricks[h]) + 16);
-            if (STATS) n_probe++;
-            const uint64_t sk = slot_key(s0);
-            if (sk == key) { ps = s1.x; npts = s1.y; break; }
-            if (sk == kEmptyKey) break;
-            h = (h + 1) & tg.mask;
-          }
+          brick_find_points<STATS>(tg, bx0 + x, by0 + y, bz0 + z, ps, npts, n_probe);
           // voxel coordinates of the brick's corner relative to the tile box
           s_borg[lane] = make_int4(((bx0 + x) << kBrickShift) - ox0, ((by0 + y) << kBrickShift) - oy0, ((bz0 + z) << kBrickShift) - oz0, 0);
         }

@@ -7,6 +7,7 @@
 #pragma once
 
 #include "pcm_device.h"
+#include "brick_table.h"
 #include "plane_fit.h"
 
 namespace pcm {
@@ -132,56 +133,24 @@ __device__ inline void best_offer(Best& b, const float4& mp, const float (&q)[3]
   best_offer_d2(b, d2, id, max_r2f);
 }
 
-__device__ inline uint64_t slot_key(const uint4& s) { return ((uint64_t)s.y << 32) | s.x; }
-
-// find a brick in the linear-probed brick table: slot index (or ~0u) and its first voxel
-template <bool STATS>
-__device__ inline uint32_t brick_find(const TargetView& tg, int bx, int by, int bz, uint32_t& vox_base, uint32_t& n_probe) {
-  const uint64_t key = pack_brick(bx, by, bz);
-  uint32_t h = hash_coord(bx, by, bz) & tg.mask;
-  for (;;) {
-    const uint4 s = gload4u(&tg.bricks[h]);
-    if (STATS) n_probe++;
-    const uint64_t sk = slot_key(s);
-    if (sk == key) { vox_base = s.z; return h; }
-    if (sk == kEmptyKey) { vox_base = 0; return ~0u; }
-    h = (h + 1) & tg.mask;
-  }
-}
-
 // Per-lane search straight against the global structures (tiles whose voxel box
 // does not fit the LDS grid): brick probe (re-used while consecutive cells stay in
 // one brick) -> occupancy bit -> rank -> vox_start -> the voxel's points.
 template <bool STATS>
 __device__ inline void knn_global(const TargetView& tg, const float (&q)[3], int cx, int cy, int cz, int num_neighbors, float max_range_sq, Best& best,
                                   uint32_t& n_cand, uint32_t& n_probe) {
-  int cbx = 0x7fffffff, cby = 0, cbz = 0;
-  uint32_t slot = ~0u, vox_base = 0;
+  BrickCursor cur;
   for (int g = 0; g < num_neighbors; g++) {
-    const int vx = cx + c_nearby[g][0], vy = cy + c_nearby[g][1], vz = cz + c_nearby[g][2];
-    const int bx = vx >> kBrickShift, by = vy >> kBrickShift, bz = vz >> kBrickShift;
-    if (bx != cbx || by != cby || bz != cbz) {
-      slot = brick_find<STATS>(tg, bx, by, bz, vox_base, n_probe);
-      cbx = bx; cby = by; cbz = bz;
-    }
-    if (slot == ~0u) continue;
-    const uint32_t li = local_index(vx, vy, vz), w = li >> 5, bit = li & 31;
-    const uint32_t m = gload_u(&tg.bmask[(size_t)slot * 16 + w]);
-    if (!((m >> bit) & 1u)) continue;
-    const uint32_t v = vox_base + gload_u16(&tg.bpref[(size_t)slot * 16 + w]) + (uint32_t)__popc(m & ((1u << bit) - 1u));
-    const uint32_t start = gload_u(&tg.vox_start[v]), end = gload_u(&tg.vox_start[v + 1]);
+    const int v = voxel_rank<STATS>(tg, cur, cx + c_nearby[g][0], cy + c_nearby[g][1], cz + c_nearby[g][2], n_probe);
+    if (v < 0) continue;
+    uint32_t start, end;
+    voxel_run(tg, (uint32_t)v, start, end);
     for (uint32_t k = start; k < end; k++) {
       const float4 mp = gload4(tg.pts + k);
       if (STATS) n_cand++;
       best_offer(best, mp, q, k, max_range_sq);
     }
   }
-}
-
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 // ---- wave64 data-parallel primitives on the DPP path (no LDS round trip: __shfl_* compiles to ds_bpermute_b32, one LDS-latency

@@ -55,21 +55,14 @@ __global__ void __launch_bounds__(256) k_linearize_reforder(const PairDesc* __re
       const int cx = (int)fx, cy = (int)fy, cz = (int)fz;
       DistId cand[kRefCap];
       int n = 0;
-      int cbx = 0x7fffffff, cby = 0, cbz = 0;
-      uint32_t slot = ~0u, vox_base = 0, n_probe = 0;
+      BrickCursor cur;
       for (int g = 0; g < kp.num_neighbors; g++) {   // nearby_grids_ order  ivox3d.h:211-235
         const int vx = cx + c_nearby[g][0], vy = cy + c_nearby[g][1], vz = cz + c_nearby[g][2];
-        const int bx = vx >> kBrickShift, by = vy >> kBrickShift, bz = vz >> kBrickShift;
-        if (bx != cbx || by != cby || bz != cbz) {
-          slot = brick_find<false>(tg, bx, by, bz, vox_base, n_probe);
-          cbx = bx; cby = by; cbz = bz;
-        }
-        if (slot == ~0u) continue;
-        const uint32_t li = local_index(vx, vy, vz), w = li >> 5, bit = li & 31;
-        const uint32_t m = gload_u(&tg.bmask[(size_t)slot * 16 + w]);
-        if (!((m >> bit) & 1u)) continue;
-        const uint32_t v = vox_base + gload_u16(&tg.bpref[(size_t)slot * 16 + w]) + (uint32_t)__popc(m & ((1u << bit) - 1u));
-        const uint32_t start = gload_u(&tg.vox_start[v]), end = gload_u(&tg.vox_start[v + 1]);
+        if (brick_seek(tg, cur, vx, vy, vz) == ~0u) continue;   // voxel_rank in its two steps
+        const int v = rank_in_brick(tg, cur.slot, cur.base, vx, vy, vz);
+        if (v < 0) continue;
+        uint32_t start, end;
+        voxel_run(tg, (uint32_t)v, start, end);
         const int old = n;
         for (uint32_t k = start; k < end && n < kRefCap; k++) {   // the voxel's points in insertion order (points_)  ivox3d_node.hpp:158-166
           const float4 mp = gload4(tg.pts + k);

@@ -57,22 +57,14 @@ __device__ inline void knn_walk(const TargetView& tg, const float (&q)[3], Knn5&
     lo[a] = cell_lo(q[a] - r, inv);
     hi[a] = min(cell_lo(q[a] + r, inv), lo[a] + 3);
   }
-  int cbx = 0x7fffffff, cby = 0, cbz = 0;
-  uint32_t slot = ~0u, vox_base = 0, n_probe = 0;
+  BrickCursor cur;
   for (int x = lo[0]; x <= hi[0]; x++) {
     for (int y = lo[1]; y <= hi[1]; y++) {
       for (int z = lo[2]; z <= hi[2]; z++) {
-        const int bx = x >> kBrickShift, by = y >> kBrickShift, bz = z >> kBrickShift;
-        if (bx != cbx || by != cby || bz != cbz) {
-          slot = brick_find<false>(tg, bx, by, bz, vox_base, n_probe);
-          cbx = bx; cby = by; cbz = bz;
-        }
-        if (slot == ~0u) continue;
-        const uint32_t li = local_index(x, y, z), w = li >> 5, bit = li & 31;
-        const uint32_t m = gload_u(&tg.bmask[(size_t)slot * 16 + w]);
-        if (!((m >> bit) & 1u)) continue;
-        const uint32_t v = vox_base + gload_u16(&tg.bpref[(size_t)slot * 16 + w]) + (uint32_t)__popc(m & ((1u << bit) - 1u));
-        const uint32_t start = gload_u(&tg.vox_start[v]), end = gload_u(&tg.vox_start[v + 1]);
+        const int v = voxel_rank(tg, cur, x, y, z);
+        if (v < 0) continue;
+        uint32_t start, end;
+        voxel_run(tg, (uint32_t)v, start, end);
         for (uint32_t k = start; k < end; k++) {
           const float4 mp = gload4(tg.pts + k);
           const float d2 = dist2(mp.x, mp.y, mp.z, q);

@@ -17,6 +17,7 @@
 // must re-use the correspondences of the last linearize.
 // Compiled with -ffp-contract=off (see kernels.hip).
 #include "pcm_device.h"
+#include "brick_table.h"
 #include "dev_linalg.h"
 #include "pcm_host.h"
 
@@ -37,8 +38,6 @@ __device__ inline void ndt_offset(int nO, int k, int& ox, int& oy, int& oz) {
   else { ox = c_direct7[k][0]; oy = c_direct7[k][1]; oz = c_direct7[k][2]; }
 }
 
-__device__ inline uint64_t slot_key2(const uint4& s) { return ((uint64_t)s.y << 32) | s.x; }
-
 // voxel index of cell (vx,vy,vz) or -1; (cbx..,slot,vox_base) cache the last brick
 __device__ inline int voxel_lookup(const TargetView& tg, int vx, int vy, int vz, int& cbx, int& cby, int& cbz, uint32_t& slot, uint32_t& vox_base) {
   const int bx = vx >> kBrickShift, by = vy >> kBrickShift, bz = vz >> kBrickShift;
@@ -48,7 +47,7 @@ __device__ inline int voxel_lookup(const TargetView& tg, int vx, int vy, int vz,
     slot = ~0u;
     for (;;) {
       const uint4 s = gload4u(&tg.bricks[h]);
-      const uint64_t sk = slot_key2(s);
+      const uint64_t sk = slot_key(s);
       if (sk == key) { slot = h; vox_base = s.z; break; }
       if (sk == kEmptyKey) break;
       h = (h + 1) & tg.mask;
@@ -71,12 +70,6 @@ __device__ inline void load_gvox(const GaussVoxel* g, float (&mean)[3], float (&
 
 // Matrix3f::inverse(): Eigen's fixed-size 3x3 inverse (dev_linalg.h: cofactors of column 0, det along that column)
 __device__ inline void inv3f(const float (&m)[9], float (&inv)[9]) { inv3<float>(m, inv); }
-
-__device__ inline double wave_sum_d(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // ---------------------------------------------------------------------------
 // k_ndt: TRIAL = false -> correspondences at x0 + H, b, cost (linearize)
@@ -237,7 +230,7 @@ __global__ void __launch_bounds__(256, 3) k_ndt(const PairDesc* __restrict__ des
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int j = 0; j < kNumSums; j++) {
-    const double v = wave_sum_d(acc[j]);
+    const double v = wave_sum(acc[j]);
     if (lane == 0) s_part[wave][j] = v;
   }
   __syncthreads();

@@ -44,7 +44,11 @@ constexpr uint32_t kListPadId = 0xffffffffu;
 // Trips the keyed walk of k_linearize_lists loads ahead of the one it consumes; the point lists end with as many zeroed trips.
 constexpr uint32_t kWalkAhead = 1;
 
+// the key of a list voxel: 3 x 21 bits, biased
 __device__ inline uint64_t nl_pack(int x, int y, int z) { return ((uint64_t)(uint32_t)(x + kKeyBias) << 42) | ((uint64_t)(uint32_t)(y + kKeyBias) << 21) | (uint64_t)(uint32_t)(z + kKeyBias); }
+__device__ inline void nl_unpack(uint64_t k, int& x, int& y, int& z) {
+  x = (int)((k >> 42) & 0x1fffffu) - kKeyBias; y = (int)((k >> 21) & 0x1fffffu) - kKeyBias; z = (int)(k & 0x1fffffu) - kKeyBias;
+}
 
 // one key per (occupied voxel, neighbour offset): the voxels a query can sit in and see this voxel.  grid = ceil(nvox / 256)
 __global__ void k_nl_keys(const float4* __restrict__ pts, const uint32_t* __restrict__ vox_start, uint32_t nvox, float res, float inv_res, int mode, int nn, uint64_t* __restrict__ keys) {
@@ -73,28 +77,9 @@ __global__ void k_nl_centres(const uint64_t* __restrict__ keys, const uint32_t* 
   if (i >= n) return;
   if (i == n - 1) *count = pos[i] + flag[i];
   if (!flag[i]) return;
-  const uint64_t k = keys[i];
-  const int x = (int)((k >> 42) & 0x1fffffu) - kKeyBias, y = (int)((k >> 21) & 0x1fffffu) - kKeyBias, z = (int)(k & 0x1fffffu) - kKeyBias;
+  int x, y, z;
+  nl_unpack(keys[i], x, y, z);
   out[pos[i]] = make_float4(((float)x + shift) * res, ((float)y + shift) * res, ((float)z + shift) * res, 0.f);   // shift: 0 (round) or 0.5 (floor): the voxel's centre
-}
-
-// the run of voxel (vx, vy, vz) in the map's point array (brick probe re-used while consecutive cells stay in one brick)
-struct BrickCursor { int bx = 0x7fffffff, by = 0, bz = 0; uint32_t slot = ~0u, base = 0; };
-__device__ inline bool nl_voxel_run(const TargetView& tg, BrickCursor& c, int vx, int vy, int vz, uint32_t& s, uint32_t& e) {
-  const int bx = vx >> kBrickShift, by = vy >> kBrickShift, bz = vz >> kBrickShift;
-  if (bx != c.bx || by != c.by || bz != c.bz) {
-    uint32_t np = 0;
-    c.slot = brick_find<false>(tg, bx, by, bz, c.base, np);
-    c.bx = bx; c.by = by; c.bz = bz;
-  }
-  if (c.slot == ~0u) return false;
-  const uint32_t li = local_index(vx, vy, vz), w = li >> 5, bit = li & 31;
-  const uint32_t m = gload_u(&tg.bmask[(size_t)c.slot * 16 + w]);
-  if (!((m >> bit) & 1u)) return false;
-  const uint32_t v = c.base + gload_u16(&tg.bpref[(size_t)c.slot * 16 + w]) + (uint32_t)__popc(m & ((1u << bit) - 1u));
-  s = gload_u(&tg.vox_start[v]);
-  e = gload_u(&tg.vox_start[v + 1]);
-  return true;
 }
 
 // FILL = false: len[r] = candidates of list voxel r, rounded up to a multiple of kListTrip (0 stays 0); FILL = true: copy them and
@@ -106,8 +91,10 @@ __device__ inline uint32_t nl_gather(const TargetView& tg, int nn, int cx, int c
   BrickCursor cur;
   uint32_t n = 0;
   for (int g = 0; g < nn; g++) {   // nearby_grids_ order  ivox3d.h:211-235
+    const int v = voxel_rank(tg, cur, cx + c_nearby[g][0], cy + c_nearby[g][1], cz + c_nearby[g][2]);
+    if (v < 0) continue;
     uint32_t s, e;
-    if (!nl_voxel_run(tg, cur, cx + c_nearby[g][0], cy + c_nearby[g][1], cz + c_nearby[g][2], s, e)) continue;
+    voxel_run(tg, (uint32_t)v, s, e);
     if (FILL) {
       for (uint32_t k = s; k < e; k++) {   // the voxel's points in insertion order (points_)  ivox3d_node.hpp:158-166
         float4 p = gload4(tg.pts + k);
@@ -125,37 +112,19 @@ __device__ inline uint32_t nl_gather(const TargetView& tg, int nn, int cx, int c
   return padded;
 }
 template <bool FILL>
-__global__ void k_nl_lists(const float4* __restrict__ centres, uint32_t nd, TargetView tg, int nn, uint32_t* __restrict__ len, const uint32_t* __restrict__ start, float4* __restrict__ out) {
+__global__ void k_nl_lists(const float4* __restrict__ centres, uint32_t nd, TargetView tg, int mode, int nn, uint32_t* __restrict__ len, const uint32_t* __restrict__ start, float4* __restrict__ out) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= nd) return;
   const float4 c = centres[r];
-  const int cx = (int)roundf(c.x * tg.inv_res), cy = (int)roundf(c.y * tg.inv_res), cz = (int)roundf(c.z * tg.inv_res);
+  const int cx = voxel_coord(c.x, tg.res, tg.inv_res, mode), cy = voxel_coord(c.y, tg.res, tg.inv_res, mode), cz = voxel_coord(c.z, tg.res, tg.inv_res, mode);
   const uint32_t padded = nl_gather<FILL>(tg, nn, cx, cy, cz, FILL ? out + start[r] : nullptr);
   if (!FILL) len[r] = padded;
 }
 
 // pclomp NDT: the neighbour LEAVES of every list voxel in the order getNeighborhoodAtPoint{,7,1} / the radius search visit them
-// (voxel_grid_covariance_omp_impl.hpp:373-442; pcl::getAllNeighborCellIndices order for the 27 cells), filtered as far as the filter
+// (voxel_grid_covariance_omp_impl.hpp:373-442; the 27 cells as direct_offset orders them, brick_table.h), filtered as far as the filter
 // does not depend on the query: DIRECT1/7/27 keep a leaf with >= 6 points; KDTREE (nn = 0) keeps a leaf of the centroid cloud and
 // stores its float centroid for the radius test the pass applies per point.  Entry = (centroid xyz or 0, leaf index).
-__device__ inline void nl_ndt_offset(int nO, int k, int& ox, int& oy, int& oz) {
-  if (nO == 27) { ox = k / 9 - 1; oy = (k / 3) % 3 - 1; oz = k % 3 - 1; return; }
-  ox = oy = oz = 0;
-  if (k == 1) ox = 1; else if (k == 2) ox = -1; else if (k == 3) oy = 1; else if (k == 4) oy = -1; else if (k == 5) oz = 1; else if (k == 6) oz = -1;
-}
-__device__ inline int nl_voxel_rank(const TargetView& tg, BrickCursor& c, int vx, int vy, int vz) {
-  const int bx = vx >> kBrickShift, by = vy >> kBrickShift, bz = vz >> kBrickShift;
-  if (bx != c.bx || by != c.by || bz != c.bz) {
-    uint32_t np = 0;
-    c.slot = brick_find<false>(tg, bx, by, bz, c.base, np);
-    c.bx = bx; c.by = by; c.bz = bz;
-  }
-  if (c.slot == ~0u) return -1;
-  const uint32_t li = local_index(vx, vy, vz), w = li >> 5, bit = li & 31;
-  const uint32_t m = gload_u(&tg.bmask[(size_t)c.slot * 16 + w]);
-  if (!((m >> bit) & 1u)) return -1;
-  return (int)(c.base + gload_u16(&tg.bpref[(size_t)c.slot * 16 + w]) + (uint32_t)__popc(m & ((1u << bit) - 1u)));
-}
 template <bool FILL>
 __global__ void k_nl_leaf_lists(const float4* __restrict__ centres, uint32_t nd, TargetView tg, int mode, const PclLeaf* __restrict__ leaves, int nn, uint32_t* __restrict__ len,
                                 const uint32_t* __restrict__ start, float4* __restrict__ out) {
@@ -169,8 +138,8 @@ __global__ void k_nl_leaf_lists(const float4* __restrict__ centres, uint32_t nd,
   const uint32_t o = FILL ? start[r] : 0u;
   for (int k = 0; k < nk; k++) {
     int ox, oy, oz;
-    nl_ndt_offset(nk, k, ox, oy, oz);
-    const int v = nl_voxel_rank(tg, cur, cx + ox, cy + oy, cz + oz);
+    direct_offset(nk, k, ox, oy, oz);
+    const int v = voxel_rank(tg, cur, cx + ox, cy + oy, cz + oz);
     if (v < 0) continue;
     const PclLeaf* L = leaves + v;
     const bool keep = nn == 0 ? L->in_centroids != 0 : L->n >= 6;
@@ -192,8 +161,8 @@ __global__ void k_nl_voxel_slots(const float4* __restrict__ centres, uint32_t nd
   BrickCursor cur;
   for (int k = 0; k < nO; k++) {
     int ox, oy, oz;
-    nl_ndt_offset(nO, k, ox, oy, oz);   // 7: {0, +x, -x, +y, -y, +z, -z}; 27: i, j, k loops -- the order of both references
-    out[(size_t)r * nO + k] = nl_voxel_rank(tg, cur, cx + ox, cy + oy, cz + oz);
+    direct_offset(nO, k, ox, oy, oz);
+    out[(size_t)r * nO + k] = voxel_rank(tg, cur, cx + ox, cy + oy, cz + oz);
   }
 }
 
@@ -234,26 +203,32 @@ static int room_for(size_t need, std::string* err) {
   return PCM_OK;
 }
 
-// the dilated occupied set: keys of every (voxel, offset), sorted, their heads flagged and ranked, one centre per head; the
-// number of heads to the host (one read-back)
+// The sorted distinct keys of keys[0 .. n) (~0: no key), as far as the build and the update share them: the keys sorted, a flag on
+// the first of every run of equal keys, and the flags' exclusive scan = the place of each head among the distinct keys.  The
+// caller compacts the heads its own way: into centres (dilated_voxels), into the keys themselves and their number (dirty_lists).
+struct DistinctKeys { uint64_t* sorted = nullptr; uint32_t *flag = nullptr, *pos = nullptr; };
+static int distinct_keys(DevScratch& sc, std::string* err, const uint64_t* keys, size_t n, DistinctKeys* out) {
+  if (sc.take(&out->sorted, n, err, "list keys, sorted") || sc.take(&out->flag, n, err, "list key heads") || sc.take(&out->pos, n, err, "list key ranks")) return PCM_ERR_HIP;
+  if (const int rc = scratch_sort_keys(sc, err, keys, out->sorted, n, 0, 64); rc != PCM_OK) return rc;
+  k_nl_flags<<<(unsigned)((n + 255) / 256), 256, 0, sc.stream()>>>(out->sorted, (uint32_t)n, out->flag);
+  PCM_HIPCK_ERR(err, hipGetLastError());
+  return scratch_exclusive_scan(sc, err, out->flag, out->pos, n);
+}
+
+// the dilated occupied set: the distinct keys of every (voxel, offset), one centre per key; their number to the host (one read-back)
 static int dilated_voxels(ListBuild& b) {
   const TargetMap& map = b.map;
   const int mode = map.coord_mode;
   const size_t nk = b.nk;
-  const unsigned nb = (unsigned)((nk + 255) / 256);
-  uint64_t *keys = nullptr, *keys_s = nullptr;
-  uint32_t *flag = nullptr, *pos = nullptr, *d_cnt = nullptr, h_cnt = 0;
-  if (b.sc.take(&keys, nk, b.err, "dilation keys") || b.sc.take(&keys_s, nk, b.err, "dilation keys, sorted")) return PCM_ERR_HIP;
-  if (b.sc.take(&flag, nk, b.err, "dilation heads") || b.sc.take(&pos, nk, b.err, "dilation ranks")) return PCM_ERR_HIP;
-  if (b.sc.take(&d_cnt, 2, b.err, "dilation count")) return PCM_ERR_HIP;
+  uint64_t* keys = nullptr;
+  uint32_t *d_cnt = nullptr, h_cnt = 0;
+  DistinctKeys dk;
+  if (b.sc.take(&keys, nk, b.err, "dilation keys") || b.sc.take(&d_cnt, 2, b.err, "dilation count")) return PCM_ERR_HIP;
   k_nl_keys<<<(map.num_voxels + 255) / 256, 256, 0, b.stream>>>(map.pts, map.vox_start, map.num_voxels, map.res, map.inv_res, mode, b.nset, keys);
   PCM_HIPCK_ERR(b.err, hipGetLastError());
-  if (const int rc = scratch_sort_keys(b.sc, b.err, keys, keys_s, nk, 0, 64); rc != PCM_OK) return rc;
-  k_nl_flags<<<nb, 256, 0, b.stream>>>(keys_s, (uint32_t)nk, flag);
-  PCM_HIPCK_ERR(b.err, hipGetLastError());
-  if (const int rc = scratch_exclusive_scan(b.sc, b.err, flag, pos, nk); rc != PCM_OK) return rc;
+  if (const int rc = distinct_keys(b.sc, b.err, keys, nk, &dk); rc != PCM_OK) return rc;
   if (const int rc = b.sc.take(&b.centres, nk, b.err, "dilated voxel centres"); rc != PCM_OK) return rc;   // at most one per key
-  k_nl_centres<<<nb, 256, 0, b.stream>>>(keys_s, flag, pos, (uint32_t)nk, map.res, mode == COORD_ROUND ? 0.f : mode == COORD_FLOOR_MUL ? 0.5f : 1.0f, b.centres, d_cnt);
+  k_nl_centres<<<(unsigned)((nk + 255) / 256), 256, 0, b.stream>>>(dk.sorted, dk.flag, dk.pos, (uint32_t)nk, map.res, mode == COORD_ROUND ? 0.f : mode == COORD_FLOOR_MUL ? 0.5f : 1.0f, b.centres, d_cnt);
   PCM_HIPCK_ERR(b.err, hipGetLastError());
   PCM_HIPCK_ERR(b.err, hipMemcpyAsync(&h_cnt, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream));
   PCM_HIPCK_ERR(b.err, hipStreamSynchronize(b.stream));
@@ -322,9 +297,6 @@ __device__ inline void fl_unpack_point_key(uint64_t k, int& x, int& y, int& z) {
   y = (((int)((bkey >> 18) & 0x3ffff) - kBrickBias) << kBrickShift) + (int)((li >> 3) & 7u);
   z = (((int)(bkey & 0x3ffff) - kBrickBias) << kBrickShift) + (int)(li & 7u);
 }
-__device__ inline void fl_unpack_list_key(uint64_t k, int& x, int& y, int& z) {
-  x = (int)((k >> 42) & 0x1fffffu) - kKeyBias; y = (int)((k >> 21) & 0x1fffffu) - kKeyBias; z = (int)(k & 0x1fffffu) - kKeyBias;
-}
 
 // the dilation of k_nl_keys over the touched voxels: one key per (touched voxel, offset); a touched key equal to its predecessor
 // (the batch's keys are sorted: a voxel's points follow one another) or ~0 gives none.  grid = ceil(nt / 256)
@@ -361,11 +333,10 @@ __global__ void k_fl_classify(const uint64_t* __restrict__ dirty, uint32_t nk, T
   if (i >= nk) return;
   if (i >= ctr[kTotDirty]) { newcap[i] = 0; isnew[i] = 0; return; }
   int cx, cy, cz;
-  fl_unpack_list_key(dirty[i], cx, cy, cz);
+  nl_unpack(dirty[i], cx, cy, cz);
   DirtyList d;
   d.len = nl_gather<false>(tg, nn, cx, cy, cz, nullptr);
-  BrickCursor cur;
-  const int rank = nl_voxel_rank(index, cur, cx, cy, cz);
+  const int rank = voxel_rank(index, cx, cy, cz);
   d.id = ~0u; d.start = 0; d.cap = 0;
   uint32_t old_len = 0;
   if (rank >= 0) {
@@ -396,7 +367,7 @@ __global__ void k_fl_rewrite(const uint64_t* __restrict__ dirty, uint32_t nd, Ta
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nd) return;
   int cx, cy, cz;
-  fl_unpack_list_key(dirty[i], cx, cy, cz);
+  nl_unpack(dirty[i], cx, cy, cz);
   const DirtyList d = lists[i];
   uint32_t id = d.id, start = d.start, cap = d.cap;
   if (isnew[i]) {
@@ -464,7 +435,7 @@ static int fill_lists(ListBuild& b, const PclLeaf* ndt_leaves, size_t list_entri
   if (b.sc.take(&len, (size_t)nd + 1, b.err, "list lengths")) return PCM_ERR_HIP;
   PCM_HIPCK_ERR(b.err, hipMemsetAsync(len, 0, sizeof(uint32_t) * ((size_t)nd + 1), stream));
   if (ndt_leaves) k_nl_leaf_lists<false><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of(map), mode, ndt_leaves, nn, len, nullptr, nullptr);
-  else k_nl_lists<false><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of(map), nn, len, nullptr, nullptr);
+  else k_nl_lists<false><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of(map), mode, nn, len, nullptr, nullptr);
   PCM_HIPCK_ERR(b.err, hipGetLastError());
   if (const int rc = scratch_exclusive_scan(b.sc, b.err, len, out->start.p, (size_t)nd + 1); rc != PCM_OK) return rc;
   PCM_HIPCK_ERR(b.err, hipMemcpyAsync(&h_total, out->start + nd, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -481,7 +452,7 @@ static int fill_lists(ListBuild& b, const PclLeaf* ndt_leaves, size_t list_entri
   if (const int rc = out->pts.reserve(stream, b.err, alloc, b.follow ? std::min<size_t>(alloc + alloc / 4, 0xfffffff0u) : alloc); rc != PCM_OK) return rc;
   PCM_HIPCK_ERR(b.err, hipMemsetAsync(out->pts + total, 0, sizeof(float4) * tail, stream));
   if (ndt_leaves) k_nl_leaf_lists<true><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of(map), mode, ndt_leaves, nn, nullptr, out->start, out->pts);
-  else k_nl_lists<true><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of(map), nn, nullptr, out->start, out->pts);
+  else k_nl_lists<true><<<(nd + 127) / 128, 128, 0, stream>>>(out->index.pts, nd, view_of(map), mode, nn, nullptr, out->start, out->pts);
   PCM_HIPCK_ERR(b.err, hipGetLastError());
   PCM_HIPCK_ERR(b.err, hipStreamSynchronize(stream));
   out->num_lists = nd;
@@ -545,18 +516,14 @@ struct ListUpdate {
 // stage 1 + 2: the touched voxels dilated by the neighbourhood, sorted, duplicates removed
 static int dirty_lists(ListUpdate& u) {
   const uint32_t nt = u.map.touched_n, nk = u.nk;
-  uint64_t *keys = nullptr, *keys_s = nullptr;
-  uint32_t *flag = nullptr, *pos = nullptr;
-  if (u.sc.take(&keys, nk, u.err, "dirty keys") || u.sc.take(&keys_s, nk, u.err, "dirty keys, sorted") || u.sc.take(&u.dirty, nk, u.err, "dirty lists")) return PCM_ERR_HIP;
-  if (u.sc.take(&flag, nk, u.err, "dirty heads") || u.sc.take(&pos, nk, u.err, "dirty ranks") || u.sc.take(&u.ctr, kTotWords, u.err, "update totals")) return PCM_ERR_HIP;
+  uint64_t* keys = nullptr;
+  DistinctKeys dk;
+  if (u.sc.take(&keys, nk, u.err, "dirty keys") || u.sc.take(&u.dirty, nk, u.err, "dirty lists") || u.sc.take(&u.ctr, kTotWords, u.err, "update totals")) return PCM_ERR_HIP;
   PCM_HIPCK_ERR(u.err, hipMemsetAsync(u.ctr, 0, sizeof(unsigned long long) * kTotWords, u.stream));
   k_fl_dirty_keys<<<(nt + 255) / 256, 256, 0, u.stream>>>(u.map.touched, nt, u.nn, keys);
   PCM_HIPCK_ERR(u.err, hipGetLastError());
-  if (const int rc = scratch_sort_keys(u.sc, u.err, keys, keys_s, nk, 0, 64); rc != PCM_OK) return rc;
-  k_nl_flags<<<(nk + 255) / 256, 256, 0, u.stream>>>(keys_s, nk, flag);
-  PCM_HIPCK_ERR(u.err, hipGetLastError());
-  if (const int rc = scratch_exclusive_scan(u.sc, u.err, flag, pos, nk); rc != PCM_OK) return rc;
-  k_fl_compact<<<(nk + 255) / 256, 256, 0, u.stream>>>(keys_s, flag, pos, nk, u.dirty, u.ctr);
+  if (const int rc = distinct_keys(u.sc, u.err, keys, nk, &dk); rc != PCM_OK) return rc;
+  k_fl_compact<<<(nk + 255) / 256, 256, 0, u.stream>>>(dk.sorted, dk.flag, dk.pos, nk, u.dirty, u.ctr);
   PCM_HIPCK_ERR(u.err, hipGetLastError());
   return PCM_OK;
 }
@@ -725,102 +692,97 @@ __global__ void __launch_bounds__(256) k_linearize_lists(const PairDesc* __restr
     const float lim = (float)(kCoordBias - 32);
     if (fabsf(fx) < lim && fabsf(fy) < lim && fabsf(fz) < lim) {   // also false for NaN
       const int cx = (int)fx, cy = (int)fy, cz = (int)fz;
-      uint32_t vox_base = 0, n_probe = 0;
-      const uint32_t slot = brick_find<false>(nl, cx >> kBrickShift, cy >> kBrickShift, cz >> kBrickShift, vox_base, n_probe);
-      if (slot != ~0u) {
-        const uint32_t li = local_index(cx, cy, cz), w = li >> 5, bit = li & 31;
-        const uint32_t m = gload_u(&nl.bmask[(size_t)slot * 16 + w]);
-        if ((m >> bit) & 1u) {
-          const uint32_t r = vox_base + gload_u16(&nl.bpref[(size_t)slot * 16 + w]) + (uint32_t)__popc(m & ((1u << bit) - 1u));
-          uint32_t s, e;
-          if constexpr (POOLED) {
-            const unsigned long long run_rec = *(const PCM_GLOBAL unsigned long long*)(reinterpret_cast<const unsigned long long*>(nl.vox_start) + r);   // one 8-byte load
-            s = (uint32_t)run_rec; e = s + (uint32_t)(run_rec >> 32);
-          } else {
-            s = gload_u(&nl.vox_start[r]); e = gload_u(&nl.vox_start[r + 1]);
+      const int rank = voxel_rank(nl, cx, cy, cz);   // the list index: voxel -> rank of its list
+      if (rank >= 0) {
+        const uint32_t r = (uint32_t)rank;
+        uint32_t s, e;
+        if constexpr (POOLED) {
+          const unsigned long long run_rec = *(const PCM_GLOBAL unsigned long long*)(reinterpret_cast<const unsigned long long*>(nl.vox_start) + r);   // one 8-byte load
+          s = (uint32_t)run_rec; e = s + (uint32_t)(run_rec >> 32);
+        } else {
+          voxel_run(nl, r, s, e);
+        }
+        // the voxel's candidates in the reference's visit order, four per trip.  The run is padded to whole trips and starts on a
+        // 64-byte boundary (build_neighbour_lists), so e - s is a multiple of four: no bounds test, all four loads under way and all
+        // four distances formed before the first offer.  A load past the run's true end is a pad entry (d2 = +inf) and is never
+        // among the in-range entries.
+        //
+        // Keyed walk (keyed_best.h): a run of at most kKeyedMaxRun entries keeps the six smallest (distance, position) keys by a
+        // branch-free min / med3 network.  The position `pos` is the same in every lane that is still walking, a scalar.
+        uint32_t bi[K];
+        int bm = 0;
+        const uint32_t len = e - s;
+        const bool keyed = len <= kKeyedMaxRun;
+        KeyedBest kb;
+        keyed_init(kb);
+        const float4* run = nl.pts + s;
+        // Pipelined: the loads of trip pos + kWalkAhead * kListTrip are issued before trip pos is consumed, so they are in flight
+        // while the distances and the network of trip pos issue.  No bounds test on them: a trip consumed at pos < len starts at
+        // most kWalkAhead trips behind the run's last one, so the furthest entry read is s + len - kListTrip + kWalkAhead * kListTrip
+        // + (kListTrip - 1) < e + kWalkAhead * kListTrip <= num_candidates + kWalkAhead * kListTrip, inside the array
+        // (build_neighbour_lists keeps kWalkAhead zeroed trips behind the last run; for an empty run s <= num_candidates and the
+        // same bound holds for the prologue).  What a load past e brings -- the head of the next run, or the zeroed tail -- belongs
+        // to a trip at a position >= len: the loop ends before that trip is consumed, its registers are dropped, nothing of it is
+        // offered.  A lane whose run is longer than kKeyedMaxRun loads nothing here: no prologue, and it never enters the loop.
+        float4 buf[kWalkAhead + 1][kListTrip];
+        if (keyed) {
+#pragma unroll
+          for (uint32_t u = 0; u < kWalkAhead; u++) walk_load(buf[u], run + u * kListTrip);
+        }
+        // kWalkAhead + 1 trips per turn, the buffers in fixed roles (no copies): at the top buf[u] holds trip pos + u * kListTrip
+        // for u < kWalkAhead; step u loads trip u + kWalkAhead into the buffer that step u - 1 emptied and consumes buf[u].  The
+        // turn runs while all its trips are inside the run; the at most kWalkAhead trips left are loaded already.
+        uint32_t pos = 0;
+        for (; pos + kWalkAhead * kListTrip < (keyed ? len : 0u); pos += (kWalkAhead + 1) * kListTrip) {
+#pragma unroll
+          for (uint32_t u = 0; u <= kWalkAhead; u++) {
+            walk_load(buf[(u + kWalkAhead) % (kWalkAhead + 1)], run + pos + (u + kWalkAhead) * kListTrip);
+            walk_offer(kb, buf[u], q, pos + u * kListTrip);
           }
-          // the voxel's candidates in the reference's visit order, four per trip.  The run is padded to whole trips and starts on a
-          // 64-byte boundary (build_neighbour_lists), so e - s is a multiple of four: no bounds test, all four loads under way and all
-          // four distances formed before the first offer.  A load past the run's true end is a pad entry (d2 = +inf) and is never
-          // among the in-range entries.
-          //
-          // Keyed walk (keyed_best.h): a run of at most kKeyedMaxRun entries keeps the six smallest (distance, position) keys by a
-          // branch-free min / med3 network.  The position `pos` is the same in every lane that is still walking, a scalar.
-          uint32_t bi[K];
-          int bm = 0;
-          const uint32_t len = e - s;
-          const bool keyed = len <= kKeyedMaxRun;
-          KeyedBest kb;
-          keyed_init(kb);
-          const float4* run = nl.pts + s;
-          // Pipelined: the loads of trip pos + kWalkAhead * kListTrip are issued before trip pos is consumed, so they are in flight
-          // while the distances and the network of trip pos issue.  No bounds test on them: a trip consumed at pos < len starts at
-          // most kWalkAhead trips behind the run's last one, so the furthest entry read is s + len - kListTrip + kWalkAhead * kListTrip
-          // + (kListTrip - 1) < e + kWalkAhead * kListTrip <= num_candidates + kWalkAhead * kListTrip, inside the array
-          // (build_neighbour_lists keeps kWalkAhead zeroed trips behind the last run; for an empty run s <= num_candidates and the
-          // same bound holds for the prologue).  What a load past e brings -- the head of the next run, or the zeroed tail -- belongs
-          // to a trip at a position >= len: the loop ends before that trip is consumed, its registers are dropped, nothing of it is
-          // offered.  A lane whose run is longer than kKeyedMaxRun loads nothing here: no prologue, and it never enters the loop.
-          float4 buf[kWalkAhead + 1][kListTrip];
-          if (keyed) {
+        }
 #pragma unroll
-            for (uint32_t u = 0; u < kWalkAhead; u++) walk_load(buf[u], run + u * kListTrip);
+        for (uint32_t u = 0; u < kWalkAhead; u++) {
+          if (pos + u * kListTrip < (keyed ? len : 0u)) walk_offer(kb, buf[u], q, pos + u * kListTrip);
+        }
+        uint32_t kpos[kKeyedBest];
+        const bool decided = keyed_decode(kb, kp.max_range_sq, kpos, bm) && keyed;
+#pragma unroll
+        for (int j = 0; j < K; j++) bi[j] = s + kpos[j];
+        // An ambiguous lane (ties, near-ties, the range boundary, a run longer than kKeyedMaxRun) repeats its walk with the running
+        // list of the other kernels: the same offers in the same visit order.  The wave branches over this when no lane needs it.
+        if (!decided) {
+          Best best;
+          best_init(best, kp.max_range_sq);
+          for (uint32_t k = s; k < e; k += kListTrip) {
+            const float4 c0 = gload4(nl.pts + k), c1 = gload4(nl.pts + k + 1), c2 = gload4(nl.pts + k + 2), c3 = gload4(nl.pts + k + 3);
+            const float d0 = list_d2(c0, q), d1 = list_d2(c1, q), d2 = list_d2(c2, q), d3 = list_d2(c3, q);
+            best_offer_d2(best, d0, k, kp.max_range_sq);
+            best_offer_d2(best, d1, k + 1, kp.max_range_sq);
+            best_offer_d2(best, d2, k + 2, kp.max_range_sq);
+            best_offer_d2(best, d3, k + 3, kp.max_range_sq);
           }
-          // kWalkAhead + 1 trips per turn, the buffers in fixed roles (no copies): at the top buf[u] holds trip pos + u * kListTrip
-          // for u < kWalkAhead; step u loads trip u + kWalkAhead into the buffer that step u - 1 emptied and consumes buf[u].  The
-          // turn runs while all its trips are inside the run; the at most kWalkAhead trips left are loaded already.
-          uint32_t pos = 0;
-          for (; pos + kWalkAhead * kListTrip < (keyed ? len : 0u); pos += (kWalkAhead + 1) * kListTrip) {
+          best_finish(best);
+          bm = best.m;
 #pragma unroll
-            for (uint32_t u = 0; u <= kWalkAhead; u++) {
-              walk_load(buf[(u + kWalkAhead) % (kWalkAhead + 1)], run + pos + (u + kWalkAhead) * kListTrip);
-              walk_offer(kb, buf[u], q, pos + u * kListTrip);
-            }
+          for (int j = 0; j < K; j++) bi[j] = best.i[j];
+        }
+        // The five chosen candidates again, by index, for the fit: all five loads issued back to back ahead of the bm >= KMIN
+        // test, one round trip.  (Guarded by `if (j < bm)` the fourth and the fifth load each sat in a branch of its own behind a
+        // full wait: three round trips.)  Every lane loads five entries: entry j < bm is its j-th best, any other load reads the
+        // run's first entry (address s: inside the array, see above) and its value is replaced by zero -- an index that bm
+        // excludes is never formed into an address.
+        float4 fp[K];
+#pragma unroll
+        for (int j = 0; j < K; j++) fp[j] = gload4(nl.pts + (j < bm ? bi[j] : s));
+        if (bm >= KMIN) {   // laser_mapping.cc:619-623
+          float px[K], py[K], pz[K];
+#pragma unroll
+          for (int j = 0; j < K; j++) {
+            asm volatile("" ::"v"(fp[j].w));   // see walk_offer
+            px[j] = j < bm ? fp[j].x : 0.f; py[j] = j < bm ? fp[j].y : 0.f; pz[j] = j < bm ? fp[j].z : 0.f;
           }
-#pragma unroll
-          for (uint32_t u = 0; u < kWalkAhead; u++) {
-            if (pos + u * kListTrip < (keyed ? len : 0u)) walk_offer(kb, buf[u], q, pos + u * kListTrip);
-          }
-          uint32_t kpos[kKeyedBest];
-          const bool decided = keyed_decode(kb, kp.max_range_sq, kpos, bm) && keyed;
-#pragma unroll
-          for (int j = 0; j < K; j++) bi[j] = s + kpos[j];
-          // An ambiguous lane (ties, near-ties, the range boundary, a run longer than kKeyedMaxRun) repeats its walk with the running
-          // list of the other kernels: the same offers in the same visit order.  The wave branches over this when no lane needs it.
-          if (!decided) {
-            Best best;
-            best_init(best, kp.max_range_sq);
-            for (uint32_t k = s; k < e; k += kListTrip) {
-              const float4 c0 = gload4(nl.pts + k), c1 = gload4(nl.pts + k + 1), c2 = gload4(nl.pts + k + 2), c3 = gload4(nl.pts + k + 3);
-              const float d0 = list_d2(c0, q), d1 = list_d2(c1, q), d2 = list_d2(c2, q), d3 = list_d2(c3, q);
-              best_offer_d2(best, d0, k, kp.max_range_sq);
-              best_offer_d2(best, d1, k + 1, kp.max_range_sq);
-              best_offer_d2(best, d2, k + 2, kp.max_range_sq);
-              best_offer_d2(best, d3, k + 3, kp.max_range_sq);
-            }
-            best_finish(best);
-            bm = best.m;
-#pragma unroll
-            for (int j = 0; j < K; j++) bi[j] = best.i[j];
-          }
-          // The five chosen candidates again, by index, for the fit: all five loads issued back to back ahead of the bm >= KMIN
-          // test, one round trip.  (Guarded by `if (j < bm)` the fourth and the fifth load each sat in a branch of its own behind a
-          // full wait: three round trips.)  Every lane loads five entries: entry j < bm is its j-th best, any other load reads the
-          // run's first entry (address s: inside the array, see above) and its value is replaced by zero -- an index that bm
-          // excludes is never formed into an address.
-          float4 fp[K];
-#pragma unroll
-          for (int j = 0; j < K; j++) fp[j] = gload4(nl.pts + (j < bm ? bi[j] : s));
-          if (bm >= KMIN) {   // laser_mapping.cc:619-623
-            float px[K], py[K], pz[K];
-#pragma unroll
-            for (int j = 0; j < K; j++) {
-              asm volatile("" ::"v"(fp[j].w));   // see walk_offer
-              px[j] = j < bm ? fp[j].x : 0.f; py[j] = j < bm ? fp[j].y : 0.f; pz[j] = j < bm ? fp[j].z : 0.f;
-            }
-            float4 fit;
-            if (esti_plane<true>(px, py, pz, bm, kp.plane_threshold, &fit)) pl = fit;
-          }
+          float4 fit;
+          if (esti_plane<true>(px, py, pz, bm, kp.plane_threshold, &fit)) pl = fit;
         }
       }
     }

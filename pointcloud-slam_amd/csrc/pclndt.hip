@@ -18,6 +18,7 @@
 // (pclndt_host.h): it is a serial decision per evaluation, one 48-double read-back each.
 // Compiled with -ffp-contract=off.
 #include "pcm_device.h"
+#include "brick_table.h"
 #include "pcm_host.h"
 #include "dev_linalg.h"
 #include "pclndt_host.h"
@@ -28,27 +29,6 @@ namespace {
 
 constexpr int kNdtSums = 43;       // 36 H (row-major), 6 gradient, score
 constexpr int kNdtStride = 48;
-
-__device__ inline uint64_t slot_key3(const uint4& s) { return ((uint64_t)s.y << 32) | s.x; }
-
-// leaf index of cell (vx,vy,vz) or -1
-__device__ inline int leaf_lookup(const TargetView& tg, int vx, int vy, int vz) {
-  const int bx = vx >> kBrickShift, by = vy >> kBrickShift, bz = vz >> kBrickShift;
-  const uint64_t key = pack_brick(bx, by, bz);
-  uint32_t h = hash_coord(bx, by, bz) & tg.mask;
-  uint4 s;
-  for (;;) {
-    s = gload4u(&tg.bricks[h]);
-    const uint64_t sk = slot_key3(s);
-    if (sk == key) break;
-    if (sk == kEmptyKey) return -1;
-    h = (h + 1) & tg.mask;
-  }
-  const uint32_t li = local_index(vx, vy, vz), w = li >> 5, bit = li & 31;
-  const uint32_t m = gload_u(&tg.bmask[(size_t)h * 16 + w]);
-  if (!((m >> bit) & 1u)) return -1;
-  return (int)(s.z + gload_u16(&tg.bpref[(size_t)h * 16 + w]) + (uint32_t)__popc(m & ((1u << bit) - 1u)));
-}
 
 // second pass of applyFilter: one lane per voxel, its points in input order   :206-259, 262-366
 __global__ void __launch_bounds__(128) k_pclndt_leaves(const float4* __restrict__ pts, const uint32_t* __restrict__ vox_start, uint32_t nvox, PclLeaf* __restrict__ out,
@@ -134,19 +114,13 @@ __global__ void __launch_bounds__(128) k_pclndt_leaves(const float4* __restrict_
   out_f[v] = F;
 }
 
-__device__ inline void ndt_offset3(int nO, int k, int& ox, int& oy, int& oz) {
-  if (nO == 27) { ox = k / 9 - 1; oy = (k / 3) % 3 - 1; oz = k % 3 - 1; return; }   // pcl::getAllNeighborCellIndices order
-  ox = oy = oz = 0;                                                                  // getNeighborhoodAtPoint7  :414-428
-  if (k == 1) ox = 1; else if (k == 2) ox = -1; else if (k == 3) oy = 1; else if (k == 4) oy = -1; else if (k == 5) oz = 1; else if (k == 6) oz = -1;
-}
-
 // k-th neighbour leaf of the transformed point xt whose cell is (cx,cy,cz), or -1.  num_neighbors 1 / 7 / 27: the DIRECT
 // lookups (leaf must hold >= 6 points); 0: KDTREE = radiusSearch(point, resolution) over the centroid cloud
 // (voxel_grid_covariance_omp.h:476-505): float squared distance to the leaf's float centroid strictly below radius^2.
 __device__ inline int neighbour_leaf(const TargetView& tg, const PclLeaf* leaves, int nn, int k, int cx, int cy, int cz, const float (&xt)[3]) {
   int ox, oy, oz;
-  ndt_offset3(nn == 0 ? 27 : nn, k, ox, oy, oz);
-  const int v = leaf_lookup(tg, cx + ox, cy + oy, cz + oz);
+  direct_offset(nn == 0 ? 27 : nn, k, ox, oy, oz);
+  const int v = voxel_rank(tg, cx + ox, cy + oy, cz + oz);
   if (v < 0) return -1;
   const PclLeaf* L = leaves + v;
   if (nn == 0) {
@@ -166,17 +140,6 @@ __device__ inline int neighbour_leaf(const TargetView& tg, const PclLeaf* leaves
 // share it unless the cell lies on a brick face), then every cell's mask word, prefix and leaf header are loaded by straight-line
 // code -- independent loads, in flight together.  v[0 .. count) = the leaves that take part, in the reference's cell order.
 constexpr int kNdtMaxCells = 27;
-__device__ inline uint32_t brick_find_ndt(const TargetView& tg, int bx, int by, int bz, uint32_t& vox_base) {
-  const uint64_t key = pack_brick(bx, by, bz);
-  uint32_t h = hash_coord(bx, by, bz) & tg.mask;
-  for (;;) {
-    const uint4 s = gload4u(&tg.bricks[h]);
-    const uint64_t sk = slot_key3(s);
-    if (sk == key) { vox_base = s.z; return h; }
-    if (sk == kEmptyKey) { vox_base = 0; return ~0u; }
-    h = (h + 1) & tg.mask;
-  }
-}
 __device__ inline int neighbour_leaves(const TargetView& tg, const PclLeaf* __restrict__ leaves, const PclLeafF* __restrict__ leaves_f, const TargetView& nl, int nn, int cx, int cy, int cz,
                                        const float (&xt)[3], int* __restrict__ v /* LDS, stride 256 */) {
   if (nl.pts) {
@@ -184,15 +147,10 @@ __device__ inline int neighbour_leaves(const TargetView& tg, const PclLeaf* __re
     // list index, then one contiguous run of (centroid, leaf) entries in the order the cells would have been visited -- the 27-cell
     // searches no longer cost 27 mask words, prefixes and leaf headers per point
     int cnt = 0;
-    uint32_t base = 0, np = 0;
-    const uint32_t slot = brick_find_ndt(nl, cx >> kBrickShift, cy >> kBrickShift, cz >> kBrickShift, base);
-    (void)np;
-    if (slot == ~0u) return 0;
-    const uint32_t li = local_index(cx, cy, cz), w = li >> 5, bit = li & 31;
-    const uint32_t m = gload_u(&nl.bmask[(size_t)slot * 16 + w]);
-    if (!((m >> bit) & 1u)) return 0;
-    const uint32_t r = base + gload_u16(&nl.bpref[(size_t)slot * 16 + w]) + (uint32_t)__popc(m & ((1u << bit) - 1u));
-    const uint32_t s = gload_u(&nl.vox_start[r]), e = gload_u(&nl.vox_start[r + 1]);
+    const int r = voxel_rank(nl, cx, cy, cz);
+    if (r < 0) return 0;
+    uint32_t s, e;
+    voxel_run(nl, (uint32_t)r, s, e);
     const float r2 = (float)((double)tg.res * (double)tg.res);
     for (uint32_t k = s; k < e; k += 4) {   // padded array: a load past the run is never used
       const float4 e0 = gload4(nl.pts + k), e1 = gload4(nl.pts + k + 1), e2 = gload4(nl.pts + k + 2), e3 = gload4(nl.pts + k + 3);
@@ -215,45 +173,23 @@ __device__ inline int neighbour_leaves(const TargetView& tg, const PclLeaf* __re
   }
   const int nk = nn == 0 ? 27 : nn;
   const int cbx = cx >> kBrickShift, cby = cy >> kBrickShift, cbz = cz >> kBrickShift;
-  int ch = -1;
-  uint32_t cbase = 0;
-  {
-    const uint64_t key = pack_brick(cbx, cby, cbz);
-    uint32_t h = hash_coord(cbx, cby, cbz) & tg.mask;
-    for (;;) {
-      const uint4 s = gload4u(&tg.bricks[h]);
-      const uint64_t sk = slot_key3(s);
-      if (sk == key) { ch = (int)h; cbase = s.z; break; }
-      if (sk == kEmptyKey) break;
-      h = (h + 1) & tg.mask;
-    }
-  }
+  uint32_t cbase;
+  const int ch = (int)brick_find(tg, cbx, cby, cbz, cbase);   // -1: no such brick
   const float r2 = (float)((double)tg.res * (double)tg.res);
   auto one = [&](int k) {
     int ox, oy, oz;
-    ndt_offset3(nk, k, ox, oy, oz);
+    direct_offset(nk, k, ox, oy, oz);
     const int vx = cx + ox, vy = cy + oy, vz = cz + oz;
     int h = ch;
     uint32_t base = cbase;
-    if ((vx >> kBrickShift) != cbx || (vy >> kBrickShift) != cby || (vz >> kBrickShift) != cbz) {   // a cell across a brick face
-      const int bx = vx >> kBrickShift, by = vy >> kBrickShift, bz = vz >> kBrickShift;
-      const uint64_t key = pack_brick(bx, by, bz);
-      uint32_t hh = hash_coord(bx, by, bz) & tg.mask;
-      h = -1;
-      for (;;) {
-        const uint4 s = gload4u(&tg.bricks[hh]);
-        const uint64_t sk = slot_key3(s);
-        if (sk == key) { h = (int)hh; base = s.z; break; }
-        if (sk == kEmptyKey) break;
-        hh = (hh + 1) & tg.mask;
-      }
-    }
+    if ((vx >> kBrickShift) != cbx || (vy >> kBrickShift) != cby || (vz >> kBrickShift) != cbz)   // a cell across a brick face
+      h = (int)brick_find(tg, vx >> kBrickShift, vy >> kBrickShift, vz >> kBrickShift, base);
     const uint32_t li = local_index(vx, vy, vz), w = li >> 5, bit = li & 31;
     const size_t word = (size_t)(h < 0 ? 0 : h) * 16 + w;   // a valid address either way: the loads below carry no branch
     const uint32_t m = gload_u(&tg.bmask[word]);
     const uint32_t pref = gload_u16(&tg.bpref[word]);
     const bool present = h >= 0 && ((m >> bit) & 1u);
-    const uint32_t leaf = present ? base + pref + (uint32_t)__popc(m & ((1u << bit) - 1u)) : 0u;
+    const uint32_t leaf = present ? base + pref + bit_rank(m, bit) : 0u;
     const PclLeaf* L = leaves + leaf;
     bool ok;
     if (nn == 0) {   // KDTREE = radiusSearch(point, resolution) over the centroid cloud
@@ -287,19 +223,13 @@ __device__ inline int neighbour_leaves(const TargetView& tg, const PclLeaf* __re
   return cnt;
 }
 
-__device__ inline double wave_sum3(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 template <int NS>
 __device__ inline void block_reduce_store(double (&acc)[NS], double* dst) {
   __shared__ double s_part[4][kNdtStride];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int j = 0; j < NS; j++) {
-    const double v = wave_sum3(acc[j]);
+    const double v = wave_sum(acc[j]);
     if (lane == 0) s_part[wave][j] = v;
   }
   __syncthreads();

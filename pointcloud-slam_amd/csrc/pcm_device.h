@@ -12,8 +12,8 @@
 //                             pair<Vector3i,int> per VOXEL (gaussian_voxelmap.cuh:33)
 //   bmask      uint32[cap*16] 512-bit voxel occupancy of the brick in that slot
 //   bpref      uint16[cap*16] occupied voxels before each mask word (rank prefix)
-// A voxel lookup = one brick probe (shared by up to 512 cells), one mask bit, one
-// popcount and two adjacent vox_start words.  For a LiDAR surface map the whole index
+// A voxel lookup (brick_table.h; ndt.hip and gicp.hip have copies) = one brick probe (shared by up to 512 cells), one mask bit,
+// one popcount and two adjacent vox_start words.  For a LiDAR surface map the whole index
 // (bricks + masks + vox_start) is a few MB per 1 M points and stays in L2 / Infinity
 // Cache; only the map points themselves stream from HBM.
 // One source (scan): float4[N] (re-ordered along the voxel grid for locality).
@@ -162,6 +162,12 @@ __device__ inline void qrot_d(const double* q, const double* v, double* r) {
   uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
   const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
   for (int a = 0; a < 3; a++) r[a] = v[a] + q[3] * uv[a] + c[a];
+}
+// 64-lane butterfly sum of doubles, every lane ends with the result: a fixed order, so the bits do not depend on the schedule
+__device__ inline double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
 }
 // floats as unsigned integers of the same order (atomicMin / atomicMax on bounding boxes)
 __device__ inline unsigned int f2ord(float f) { const unsigned int u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }

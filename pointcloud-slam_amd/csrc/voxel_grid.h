@@ -121,8 +121,8 @@ void fold_boxes(hipStream_t st, const unsigned int* part, uint32_t n_part, const
 int sort_cells32(std::string* err, hipStream_t st, const Work& W, uint32_t N);
 int sort_cells64(std::string* err, hipStream_t st, const Work& W, uint32_t N);
 
-// 64-lane butterfly reductions (every lane ends with the result).  The double sum adds in this fixed order, so its bits do not
-// depend on the schedule; linearize_common.h's DPP reductions are another order and stay apart.
+// 64-lane butterfly reductions (every lane ends with the result); the double sum in the same fixed order is wave_sum
+// (pcm_device.h).  linearize_common.h's DPP reductions are another order and stay apart.
 __device__ inline uint32_t wave_min_u32(uint32_t v) {
   for (int off = 32; off >= 1; off >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, off, 64));
   return v;
@@ -141,10 +141,6 @@ __device__ inline uint64_t wave_min_u64(uint64_t v) {
     const uint64_t o = ((uint64_t)hi << 32) | lo;
     v = o < v ? o : v;
   }
-  return v;
-}
-__device__ inline double wave_sum_f64(double v) {
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
 
@@ -216,7 +212,7 @@ __device__ inline void cell_mean(const Elems& E, uint32_t seg, const uint32_t* _
   const double m = (double)(e - b);
 #pragma unroll
   for (int f = 0; f < Elems::kFields; f++)
-    if (f < nfields) mean[f] = (float)(wave_sum_f64(acc[f]) / m);
+    if (f < nfields) mean[f] = (float)(wave_sum(acc[f]) / m);
 }
 
 // one wave per cell (grid-stride) of either pipeline; the totals are read on the device
