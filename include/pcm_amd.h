@@ -132,7 +132,10 @@ typedef struct pcm_config {
                                        * on the device (neighbour_lists.hip) -- instead of re-deriving the candidates per pass through LDS.  Same candidates
                                        * in the same order: bit-identical results, 1.8x the kernel speed.  DEFAULT: the lists are built when a target is
                                        * registered against the second time; this flag builds them with the map (first registration already).  Never for a
-                                       * target that has grown (pcm_target_insert / pcm_map_incremental), the LIO model, or next to another kernel flag.
+                                       * target that has grown (pcm_target_insert / pcm_map_incremental) or next to another kernel flag.  A context that
+                                       * sets this flag (or PCM_FLAG_FOLLOWING_LISTS) itself also runs the LIO model -- pcm_obs_model, pcm_lio_update,
+                                       * the frame calls -- on the lists (k_lio_lists, same bits as the tile kernel; pcm_lio_search_path tells which
+                                       * ran); lists made by the second-use default alone leave the LIO calls on the tile kernel.
                                        * pclomp NDT (PCM_MODEL_NDT_OMP): the same policy for the grid's neighbour-LEAF lists (the leaves a point's search
                                        * visits, in visiting order; 16 B per (voxel, neighbour leaf)). */
 #define PCM_FLAG_FOLLOWING_LISTS 128  /* P2PLANE: candidate lists that follow a growing target.  Built with the map as under PCM_FLAG_NEIGHBOUR_LISTS; when the
@@ -143,8 +146,13 @@ typedef struct pcm_config {
                                        * tile kernel finds: bit-identical results.  A full build replaces the update when the pool is full, when the holes
                                        * left by moved runs exceed the live entries, or when more than half the lists are empty.  No lists next to
                                        * PCM_FLAG_NO_NEIGHBOUR_LISTS or another kernel flag (REFERENCE_KNN_ORDER, COUNTED_SEARCH, NO_LDS_STAGING, FUSED_STEP);
-                                       * pcm_obs_model stays on the tile kernel.  Measured (DESIGN section 26, 1 M-point map, 7 000-point batches): pays from one
-                                       * align per insert on; an update costs about 13 ms of device time, the pool 2.5 x the lists' memory.  Fails loudly when the lists cannot be kept (no memory). */
+                                       * pcm_obs_model, pcm_lio_update and the frame calls run the lists kernel too (k_lio_lists; bit-identical
+                                       * to the tile kernel, pcm_lio_search_path tells which ran).  Measured (DESIGN section 26, 1 M-point map, 7 000-point
+                                       * batches): pays from one align per insert on; the pool takes 2.5 x the lists' memory.  The update rewrites a run per
+                                       * wave (0.07-0.14 ms of a 0.65-1.7 ms update, section 28).  Measured on the LIO frame loop (1 M-point map, 14 frames): the
+                                       * flag LOSES in all three settings tried -- 1.4 -> 2.3 ms per frame with the 0.5 m scan filter, 4.6 -> 5.8-6.4 ms unfiltered,
+                                       * 1.2 -> 4.0-4.2 ms at 0.2 m voxels -- because the per-frame list update and its synchronisations cost more than the
+                                       * search saves on a map of that size.  Fails loudly when the lists cannot be kept (no memory). */
 #define PCM_FLAG_NO_NEIGHBOUR_LISTS 64 /* never build them: the tile kernel (kernels.hip) serves every pass */
 #define PCM_FLAG_REFERENCE_KNN_ORDER 32
 /* P2PLANE align / linearize: hand esti_plane its neighbours in the row order the reference's IVox::GetClosestPoint leaves -- the
@@ -289,6 +297,13 @@ int pcm_neighbour_list_info(pcm_ctx *ctx, uint64_t info[8]);
  * [2] rewrite, [3] index merge (only with new list voxels) + rank table, [4] the whole update.  Zeros when none was timed or a full
  * build took the update's place. */
 int pcm_neighbour_list_update_ms(pcm_ctx *ctx, double ms[5]);
+
+/* Which search served the jueying_lio measurement model: counts[0] = matching ObsModel launches (pcm_obs_model with rematch != 0,
+ * the matching rounds of pcm_lio_update) that ran the lists kernel (k_lio_lists), counts[1] = those that ran the tile kernel, since
+ * pcm_create or pcm_reset_stats.  The lists kernel serves a context that set PCM_FLAG_FOLLOWING_LISTS or PCM_FLAG_NEIGHBOUR_LISTS
+ * itself and whose configuration reads lists (no other kernel flag; on a shared target, the lists its owner left); lists that
+ * exist through the second-use default alone leave these calls on the tile kernel.  Both kernels give the same bits. */
+int pcm_lio_search_path(pcm_ctx *ctx, uint64_t counts[2]);
 
 /* Following lists: the free room a full build reserves behind the runs -- max(fraction * entries, min_entries) entries of 16
  * bytes.  Default: one and a half times the entries, at least 65536 (1 MiB).  A minimum, applied when a full build has to

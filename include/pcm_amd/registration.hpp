@@ -1120,6 +1120,13 @@ public:
     return last_;
   }
   const pcm_lio_update_result& last() const { return last_; }
+  // matching ObsModel launches since the context was made (or pcm_reset_stats): served by the lists kernel / by the tile kernel
+  // (pcm_lio_search_path; the lists serve a context that set PCM_FLAG_FOLLOWING_LISTS or PCM_FLAG_NEIGHBOUR_LISTS)
+  std::pair<uint64_t, uint64_t> searchPath() const {
+    uint64_t n[2] = {0, 0};
+    if (pcm_lio_search_path(ctx_, n) != PCM_OK) throw std::runtime_error("pcm_lio_search_path: bad argument");
+    return {n[0], n[1]};
+  }
   // the state ObsModel call `call` of the last update was evaluated at, its converge flag and n_eff
   bool Trace(int call, pcm_lio_filter_state* x, int32_t* converge, int32_t* n_eff, double* dx23 = nullptr) const {
     return pcm_lio_update_trace(ctx_, call, x, converge, n_eff, nullptr, dx23) == PCM_OK;

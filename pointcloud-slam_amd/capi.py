@@ -37,6 +37,7 @@ SYMBOLS = [
     "pcm_neighbour_list_info", "pcm_neighbour_list_headroom", "pcm_neighbour_list_update_ms",
     "pcm_lio_frame_world", "pcm_lio_frame_body", "pcm_lio_frame_effect", "pcm_lio_map_append", "pcm_lio_map_info_get", "pcm_lio_map_get",
     "pcm_lio_map_clear", "pcm_lio_map_export",
+    "pcm_lio_search_path",
 ]
 
 PCM_ABI_VERSION = 3   # include/pcm_amd.h
@@ -354,6 +355,7 @@ def load_library():
     L.pcm_get_neighbour_lists.argtypes = [vp, vp, vp, vp, vp]
     L.pcm_neighbour_list_info.argtypes = [vp, vp]
     L.pcm_neighbour_list_update_ms.argtypes = [vp, vp]
+    L.pcm_lio_search_path.argtypes = [vp, vp]
     L.pcm_neighbour_list_headroom.argtypes = [vp, C.c_float, u64]
     L.pcm_get_lio_members.argtypes = [vp, vp, vp, sz]
     L.pcm_obs_model.argtypes = [vp, C.POINTER(PcmLioState), i32, i32, C.POINTER(PcmObsResult)]

@@ -248,4 +248,107 @@ __device__ inline void residual_and_reduce(const PairDesc& d, uint32_t i, uint32
   }
 }
 
+// ---- tail of a jueying_lio measurement tile (laser_mapping.cc:674-698): the 16-float row of every lane (12 Jacobian columns, h,
+// selected) -> the IEKF's HTH = h_x^T h_x and h_x^T h (esekfom.hpp:1687,1706): 92 sums per tile, formed in double, 8 groups of 32
+// rows each summed in row order, then the groups in order, one partial row per tile for k_lio_finish.  The tail of k_lio_lists
+// (neighbour_lists.hip).  Its TWIN is the `if constexpr (LIO)` block at the end of k_linearize (kernels.hip), statement for
+// statement: called from there this function left that kernel its 96 VGPRs, 31 664 B of LDS and 5 waves but changed its scratch
+// (56 -> 44 bytes per lane, another spill schedule), and the tile kernel is the yardstick of the LIO path, so it keeps its own
+// text.  A change of the row or of the order of the sums goes to both.  `do_search`: this call matched (pl is the plane just
+// fitted, ref_fit / ref_ok what esti_plane did under the reference semantics), else pl is the stored plane.  All 256 threads
+// call it; `smem` is 16-byte aligned LDS of at least kLioReduceLdsBytes that nobody else touches any more; two barriers inside.
+constexpr int kLioReduceLdsBytes = 256 * 16 * 4 + 8 * kLioStride * 8;
+__device__ inline void lio_row_and_reduce(const PairDesc& d, const KernelParams& kp, uint32_t i, uint32_t tile_x, bool live, bool do_search, const float4& p, const float (&q)[3],
+                                          float pn_body, const float4& pl, bool ref_fit, bool ref_ok, void* smem) {
+  float* s_row = reinterpret_cast<float*>(smem);                      // [256][16]: 12 columns, h, selected
+  double* s_grp = reinterpret_cast<double*>(s_row + 256 * 16);        // [8][96] group partials
+  {
+    float row[16];
+#pragma unroll
+    for (int a = 0; a < 16; a++) row[a] = 0.f;
+    if (live) {
+      bool sel;
+      float res = 0.f;
+      if (kp.lio_ref) {
+        // the members of LaserMapping as they are: the flag and the plane of a point change only when a matching call
+        // reaches them, and a selected point that fails the 81 pd2^2 test keeps its flag and the residual stored for its
+        // index by an earlier call -- of this frame or of an older one (laser_mapping.cc:335-339, 616-636, 646-650)
+        const uint32_t oi = kp.lio_ref == 2 ? __float_as_uint(p.w) : i;
+        PCM_GLOBAL float* aux = (PCM_GLOBAL float*)d.lio_aux + 2 * (size_t)oi;
+        res = aux[0];
+        sel = aux[1] != 0.f;
+        if (do_search) {
+          sel = ref_fit && ref_ok;
+          if (ref_fit) gstore4(d.planes + oi, pl);
+        }
+        if (sel) {
+          const float pd2 = pl.x * q[0] + pl.y * q[1] + pl.z * q[2] + pl.w;
+          const float pn = pn_body;
+          if (pn > 81.f * pd2 * pd2) res = pd2;
+        }
+        aux[0] = res;
+        aux[1] = sel ? 1.f : 0.f;
+      } else {
+        if (do_search) gstore4(d.planes + i, pl);                        // plane_coef_[i]; the residual test is re-evaluated every call
+        sel = lio_row_selected(pl, q, pn_body, res);
+      }
+      {
+        const float pd2 = res;
+        if (sel) {
+          const float* oR = d.lio.off_R;
+          const float* Rt = d.lio.Rt;
+          float pt[3], C[3];
+#pragma unroll
+          for (int a = 0; a < 3; a++) pt[a] = (oR[a * 3 + 0] * p.x + oR[a * 3 + 1] * p.y) + oR[a * 3 + 2] * p.z + d.lio.off_t[a];   // point_this
+#pragma unroll
+          for (int a = 0; a < 3; a++) C[a] = (Rt[a * 3 + 0] * pl.x + Rt[a * 3 + 1] * pl.y) + Rt[a * 3 + 2] * pl.z;               // C = R^T n
+          row[0] = pl.x; row[1] = pl.y; row[2] = pl.z;
+          row[3] = (0.f * C[0] + -pt[2] * C[1]) + pt[1] * C[2];                                                                 // A = skew(point_this) C
+          row[4] = (pt[2] * C[0] + 0.f * C[1]) + -pt[0] * C[2];
+          row[5] = (-pt[1] * C[0] + pt[0] * C[1]) + 0.f * C[2];
+          if (kp.lio_extrinsic) {   // B = (skew(p_body) off_R^T) C ; then C
+            const float S[9] = {0.f, -p.z, p.y, p.z, 0.f, -p.x, -p.y, p.x, 0.f};
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+              float sm[3];
+#pragma unroll
+              for (int b = 0; b < 3; b++) sm[b] = (S[a * 3 + 0] * oR[b * 3 + 0] + S[a * 3 + 1] * oR[b * 3 + 1]) + S[a * 3 + 2] * oR[b * 3 + 2];
+              row[6 + a] = (sm[0] * C[0] + sm[1] * C[1]) + sm[2] * C[2];
+              row[9 + a] = C[a];
+            }
+          }
+          row[12] = -pd2;    // ekfom_data.h(i) = -residual
+          row[13] = 1.f;
+        }
+      }
+    }
+    float4* dst = reinterpret_cast<float4*>(s_row + threadIdx.x * 16);
+#pragma unroll
+    for (int a = 0; a < 4; a++) dst[a] = make_float4(row[4 * a], row[4 * a + 1], row[4 * a + 2], row[4 * a + 3]);
+  }
+  __syncthreads();
+  {
+    const int j = threadIdx.x & 31, g = threadIdx.x >> 5;
+    const float* r0 = s_row + (g * 32) * 16;
+#pragma unroll
+    for (int tt = 0; tt < 3; tt++) {
+      const int term = j + 32 * tt;
+      if (term < kLioSums) {
+        const int ia = c_lio_a[term], ib = c_lio_b[term];
+        double v = 0.0;
+#pragma unroll 8
+        for (int k = 0; k < 32; k++) v = fma((double)r0[k * 16 + ia], (double)r0[k * 16 + ib], v);
+        s_grp[g * kLioStride + term] = v;
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < kLioSums) {
+    double v = 0.0;
+#pragma unroll
+    for (int g = 0; g < 8; g++) v += s_grp[g * kLioStride + threadIdx.x];
+    gstore_d(d.partials + (size_t)tile_x * kLioStride + threadIdx.x, v);
+  }
+}
+
 }  // namespace pcm

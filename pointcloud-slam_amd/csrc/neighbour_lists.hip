@@ -360,24 +360,57 @@ __global__ void k_fl_classify(const uint64_t* __restrict__ dirty, uint32_t nk, T
 }
 
 // The rewrite: a new list voxel gets the next id and its centre goes to the log; a run that does not stay gets its place behind
-// the bump pointer; every dirty run is gathered again as k_nl_lists gathers it.  One lane per dirty list.
-__global__ void k_fl_rewrite(const uint64_t* __restrict__ dirty, uint32_t nd, TargetView tg, int nn, const DirtyList* __restrict__ lists, const uint32_t* __restrict__ newcap,
-                             const uint32_t* __restrict__ reloc_off, const uint32_t* __restrict__ isnew, const uint32_t* __restrict__ new_off, uint32_t first_new_id, uint32_t bump, float res,
-                             float4* __restrict__ centres, uint2* __restrict__ rec, uint32_t* __restrict__ rec_cap, float4* __restrict__ pool) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+// the bump pointer; every dirty run is gathered again, the bytes nl_gather<true> would write (k_nl_lists).  One WAVE per dirty list
+// (block = kRewriteWaves waves): lane g < nn resolves neighbourhood offset g (c_nearby order) to its voxel's run in the map, a wave
+// prefix sum over the run lengths in offset order gives every cell its place, and the 64 lanes copy cell after cell with
+// coalesced 16-byte loads and stores (w = the point's index in the map array), then the +inf pad entries up to the whole trip.
+// The record, the capacity and a new list voxel's centre are lane 0's.  Every condition in front of the prefix sum is
+// wave-uniform, so all 64 lanes take part in it.  A write never passes d.len, the padded length classify reserved room for.
+constexpr uint32_t kRewriteWaves = 4;
+__global__ void __launch_bounds__(64 * kRewriteWaves) k_fl_rewrite(const uint64_t* __restrict__ dirty, uint32_t nd, TargetView tg, int nn, const DirtyList* __restrict__ lists,
+                             const uint32_t* __restrict__ newcap, const uint32_t* __restrict__ reloc_off, const uint32_t* __restrict__ isnew, const uint32_t* __restrict__ new_off,
+                             uint32_t first_new_id, uint32_t bump, float res, float4* __restrict__ centres, uint2* __restrict__ rec, uint32_t* __restrict__ rec_cap,
+                             float4* __restrict__ pool) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t i = blockIdx.x * kRewriteWaves + (threadIdx.x >> 6);   // the same in every lane of a wave
   if (i >= nd) return;
   int cx, cy, cz;
   nl_unpack(dirty[i], cx, cy, cz);
   const DirtyList d = lists[i];
   uint32_t id = d.id, start = d.start, cap = d.cap;
-  if (isnew[i]) {
-    id = first_new_id + new_off[i];
-    centres[id] = make_float4((float)cx * res, (float)cy * res, (float)cz * res, 0.f);   // COORD_ROUND: k_nl_centres with shift 0
-  }
+  const bool fresh = isnew[i] != 0;
+  if (fresh) id = first_new_id + new_off[i];
   if (!list_pool::rewrite_in_place(d.len, d.cap)) { start = bump + reloc_off[i]; cap = newcap[i]; }
-  rec[id] = make_uint2(start, d.len);
-  rec_cap[id] = cap;
-  if (d.len) nl_gather<true>(tg, nn, cx, cy, cz, pool + start);
+  if (lane == 0) {
+    if (fresh) centres[id] = make_float4((float)cx * res, (float)cy * res, (float)cz * res, 0.f);   // COORD_ROUND: k_nl_centres with shift 0
+    rec[id] = make_uint2(start, d.len);
+    rec_cap[id] = cap;
+  }
+  if (d.len == 0) return;
+  uint32_t s = 0, n = 0;
+  if ((int)lane < nn) {   // nearby_grids_ order  ivox3d.h:211-235
+    const int v = voxel_rank(tg, cx + c_nearby[lane][0], cy + c_nearby[lane][1], cz + c_nearby[lane][2]);
+    if (v >= 0) {
+      uint32_t e;
+      voxel_run(tg, (uint32_t)v, s, e);
+      n = e - s;
+    }
+  }
+  const uint32_t incl = scan_add_wave(n), excl = incl - n;
+  const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+  float4* const out = pool + start;
+  for (int g = 0; g < nn; g++) {
+    const uint32_t sg = (uint32_t)__builtin_amdgcn_readlane((int)s, g), ng = (uint32_t)__builtin_amdgcn_readlane((int)n, g), og = (uint32_t)__builtin_amdgcn_readlane((int)excl, g);
+    for (uint32_t k = lane; k < ng; k += 64u) {   // the voxel's points in insertion order (points_)  ivox3d_node.hpp:158-166
+      float4 p = gload4(tg.pts + sg + k);
+      p.w = __uint_as_float(sg + k);
+      if (og + k < d.len) out[og + k] = p;
+    }
+  }
+  const uint32_t padded = (total + (kListTrip - 1u)) & ~(kListTrip - 1u);
+  const float inf = __builtin_inff();
+  const uint32_t k = total + lane;
+  if (lane < kListTrip && k < padded && k < d.len) out[k] = make_float4(inf, inf, inf, __uint_as_float(kListPadId));
 }
 
 // parity hook: the pooled runs into contiguous order by rank
@@ -476,6 +509,7 @@ int build_neighbour_lists(hipStream_t stream, const TargetMap& map, int nn, Neig
   out->valid = false;
   out->pooled = false;
   out->stale = false;
+  out->generation++;
   if (follow && (ndt_leaves || voxel_slots)) { *err = "neighbour lists: only candidate lists of points follow a target"; return PCM_ERR_INTERNAL; }
   const int mode = map.coord_mode;
   if (!map.valid || (mode != COORD_ROUND && mode != COORD_FLOOR_MUL && mode != COORD_FLOOR_HALF)) { *err = "neighbour lists: unsupported voxel convention"; return PCM_ERR_UNSUPPORTED; }
@@ -558,7 +592,7 @@ static int rewrite(ListUpdate& u) {
     if (const int rc = reserve_records(u.stream, u.err, nl, n_new, n_old); rc != PCM_OK) return rc;
   }
   if (u.tot.dirty) {
-    k_fl_rewrite<<<((uint32_t)u.tot.dirty + 127) / 128, 128, 0, u.stream>>>(u.dirty, (uint32_t)u.tot.dirty, view_of(u.map), u.nn, u.lists, u.newcap, u.reloc_off, u.isnew, u.new_off, (uint32_t)n_old,
+    k_fl_rewrite<<<((uint32_t)u.tot.dirty + kRewriteWaves - 1u) / kRewriteWaves, 64 * kRewriteWaves, 0, u.stream>>>(u.dirty, (uint32_t)u.tot.dirty, view_of(u.map), u.nn, u.lists, u.newcap, u.reloc_off, u.isnew, u.new_off, (uint32_t)n_old,
                                                                  (uint32_t)nl->pool.bump, u.map.res, nl->centres, nl->rec, nl->rec_cap, nl->pts);
     PCM_HIPCK_ERR(u.err, hipGetLastError());
   }
@@ -587,6 +621,7 @@ int update_neighbour_lists(hipStream_t stream, const TargetMap& map, NeighbourLi
   if ((size_t)map.touched_n * nl->num_neighbors >= (1ull << 31)) { *rebuild = true; return PCM_OK; }
   if (map.touched_n == 0) { nl->stale = false; return PCM_OK; }
   ListUpdate u{stream, err, map, nl, DevScratch(stream), nl->num_neighbors, map.touched_n * (uint32_t)nl->num_neighbors};
+  nl->generation++;
   // nl->time_stages (pcm_set_profiling bit 0): HIP events around the stages, read after the update (one more synchronisation)
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   int nev = 0;
@@ -656,6 +691,92 @@ __device__ inline void walk_offer(KeyedBest& kb, const float4 (&c)[kListTrip], c
   keyed_offer(kb, keyed_pack(d1, pos + 1));
   keyed_offer(kb, keyed_pack(d2, pos + 2));
   keyed_offer(kb, keyed_pack(d3, pos + 3));
+}
+
+// The 5-NN of query q among the candidates of list r, and those candidates again for the fit: bi[j] = index of the j-th best in
+// nl.pts (j < bm), bm = min(K, #in range), fp[j] = its entry (the run's first entry beyond bm, never used).  The search of
+// k_lio_lists.  It is a copy of the walk inside k_linearize_lists below, statement for statement: called from there it changed that
+// kernel's register allocation (88 -> 86 VGPRs, another schedule), and that kernel is the measured one, so the twin stays written
+// out.  A change of the walk goes to both.
+template <bool POOLED>
+__device__ inline void lists_knn(const TargetView& nl, uint32_t r, const float (&q)[3], float max_range_sq, uint32_t (&bi)[K], int& bm, float4 (&fp)[K]) {
+  uint32_t s, e;
+  if constexpr (POOLED) {
+    const unsigned long long run_rec = *(const PCM_GLOBAL unsigned long long*)(reinterpret_cast<const unsigned long long*>(nl.vox_start) + r);   // one 8-byte load
+    s = (uint32_t)run_rec; e = s + (uint32_t)(run_rec >> 32);
+  } else {
+    voxel_run(nl, r, s, e);
+  }
+  // the voxel's candidates in the reference's visit order, four per trip.  The run is padded to whole trips and starts on a
+  // 64-byte boundary (build_neighbour_lists), so e - s is a multiple of four: no bounds test, all four loads under way and all
+  // four distances formed before the first offer.  A load past the run's true end is a pad entry (d2 = +inf) and is never
+  // among the in-range entries.
+  //
+  // Keyed walk (keyed_best.h): a run of at most kKeyedMaxRun entries keeps the six smallest (distance, position) keys by a
+  // branch-free min / med3 network.  The position `pos` is the same in every lane that is still walking, a scalar.
+  bm = 0;
+  const uint32_t len = e - s;
+  const bool keyed = len <= kKeyedMaxRun;
+  KeyedBest kb;
+  keyed_init(kb);
+  const float4* run = nl.pts + s;
+  // Pipelined: the loads of trip pos + kWalkAhead * kListTrip are issued before trip pos is consumed, so they are in flight
+  // while the distances and the network of trip pos issue.  No bounds test on them: a trip consumed at pos < len starts at
+  // most kWalkAhead trips behind the run's last one, so the furthest entry read is s + len - kListTrip + kWalkAhead * kListTrip
+  // + (kListTrip - 1) < e + kWalkAhead * kListTrip <= num_candidates + kWalkAhead * kListTrip, inside the array
+  // (build_neighbour_lists keeps kWalkAhead zeroed trips behind the last run; for an empty run s <= num_candidates and the
+  // same bound holds for the prologue).  What a load past e brings -- the head of the next run, or the zeroed tail -- belongs
+  // to a trip at a position >= len: the loop ends before that trip is consumed, its registers are dropped, nothing of it is
+  // offered.  A lane whose run is longer than kKeyedMaxRun loads nothing here: no prologue, and it never enters the loop.
+  float4 buf[kWalkAhead + 1][kListTrip];
+  if (keyed) {
+#pragma unroll
+    for (uint32_t u = 0; u < kWalkAhead; u++) walk_load(buf[u], run + u * kListTrip);
+  }
+  // kWalkAhead + 1 trips per turn, the buffers in fixed roles (no copies): at the top buf[u] holds trip pos + u * kListTrip
+  // for u < kWalkAhead; step u loads trip u + kWalkAhead into the buffer that step u - 1 emptied and consumes buf[u].  The
+  // turn runs while all its trips are inside the run; the at most kWalkAhead trips left are loaded already.
+  uint32_t pos = 0;
+  for (; pos + kWalkAhead * kListTrip < (keyed ? len : 0u); pos += (kWalkAhead + 1) * kListTrip) {
+#pragma unroll
+    for (uint32_t u = 0; u <= kWalkAhead; u++) {
+      walk_load(buf[(u + kWalkAhead) % (kWalkAhead + 1)], run + pos + (u + kWalkAhead) * kListTrip);
+      walk_offer(kb, buf[u], q, pos + u * kListTrip);
+    }
+  }
+#pragma unroll
+  for (uint32_t u = 0; u < kWalkAhead; u++) {
+    if (pos + u * kListTrip < (keyed ? len : 0u)) walk_offer(kb, buf[u], q, pos + u * kListTrip);
+  }
+  uint32_t kpos[kKeyedBest];
+  const bool decided = keyed_decode(kb, max_range_sq, kpos, bm) && keyed;
+#pragma unroll
+  for (int j = 0; j < K; j++) bi[j] = s + kpos[j];
+  // An ambiguous lane (ties, near-ties, the range boundary, a run longer than kKeyedMaxRun) repeats its walk with the running
+  // list of the other kernels: the same offers in the same visit order.  The wave branches over this when no lane needs it.
+  if (!decided) {
+    Best best;
+    best_init(best, max_range_sq);
+    for (uint32_t k = s; k < e; k += kListTrip) {
+      const float4 c0 = gload4(nl.pts + k), c1 = gload4(nl.pts + k + 1), c2 = gload4(nl.pts + k + 2), c3 = gload4(nl.pts + k + 3);
+      const float d0 = list_d2(c0, q), d1 = list_d2(c1, q), d2 = list_d2(c2, q), d3 = list_d2(c3, q);
+      best_offer_d2(best, d0, k, max_range_sq);
+      best_offer_d2(best, d1, k + 1, max_range_sq);
+      best_offer_d2(best, d2, k + 2, max_range_sq);
+      best_offer_d2(best, d3, k + 3, max_range_sq);
+    }
+    best_finish(best);
+    bm = best.m;
+#pragma unroll
+    for (int j = 0; j < K; j++) bi[j] = best.i[j];
+  }
+  // The five chosen candidates again, by index, for the fit: all five loads issued back to back ahead of the bm >= KMIN
+  // test, one round trip.  (Guarded by `if (j < bm)` the fourth and the fifth load each sat in a branch of its own behind a
+  // full wait: three round trips.)  Every lane loads five entries: entry j < bm is its j-th best, any other load reads the
+  // run's first entry (address s: inside the array, see above) and its value is replaced by zero -- an index that bm
+  // excludes is never formed into an address.
+#pragma unroll
+  for (int j = 0; j < K; j++) fp[j] = gload4(nl.pts + (j < bm ? bi[j] : s));
 }
 
 // ---------------------------------------------------------------------------
@@ -796,6 +917,86 @@ void launch_linearize_lists(hipStream_t stream, const PairDesc* d_descs, const P
   else if (pooled) k_linearize_lists<false, true><<<grid, 256, 0, stream>>>(d_descs, d_states, kp);
   else if (write_planes) k_linearize_lists<true><<<grid, 256, 0, stream>>>(d_descs, d_states, kp);
   else k_linearize_lists<false><<<grid, 256, 0, stream>>>(d_descs, d_states, kp);
+}
+
+// ---------------------------------------------------------------------------
+// k_lio_lists: the jueying_lio measurement model (LaserMapping::ObsModel) on candidate lists -- what k_linearize<.., LIO>
+// (kernels.hip) computes, bit for bit, with the search of k_linearize_lists.  grid (ceil(N / 256), 1), one scan point per lane.
+//   world point   lio_world_point / lio_body_norm with the float pose of the descriptor, as the tile kernel
+//   search        Pos2Grid -> list index -> lists_knn (keyed walk, running-list fallback); a call that does not match
+//                 (converge == false, laser_mapping.cc:616) reads the stored plane and walks nothing
+//   fit           esti_plane<true> on the bm >= KMIN neighbours, verdict kept apart for the reference semantics
+//   nearest_points_ (d.nn)   positions in the list entry array nl.pts, nearest first, ~0u beyond bm: the entries hold the xyz of
+//                 the map's points, so k_map_filter reads them through that array (pcm_map_incremental)
+//   tail          lio_row_and_reduce (linearize_common.h)
+// POOLED as in k_linearize_lists; LIO_DEV: a round of pcm_lio_update, the converge flag k_iekf_step left in the descriptor.
+// ---------------------------------------------------------------------------
+template <bool POOLED, bool LIO_DEV>
+__global__ void __launch_bounds__(256) k_lio_lists(const PairDesc* __restrict__ descs, const PairState* __restrict__ states, KernelParams kp) {
+  uint32_t tile_x = blockIdx.x;
+  {
+    const uint32_t base = blockIdx.x & ~63u, w = blockIdx.x & 63u;
+    if (base + 64u <= gridDim.x) tile_x = base + (w & 7u) * 8u + (w >> 3);
+  }
+  const int pair = PCM_PAIR_OF(kp, blockIdx.y);
+  if (states[pair].mode != MODE_LINEARIZE) return;
+  const PairDesc d = descs[pair];
+  const uint32_t i = tile_x * 256u + threadIdx.x;
+  if (tile_x * 256u >= d.src.num_points) return;
+  const bool live = i < d.src.num_points;
+  const TargetView nl = d.nl;
+  const bool do_search = LIO_DEV ? d.lio.rematch != 0 : kp.lio_rematch != 0;
+  __shared__ __align__(16) unsigned char s_mem[kLioReduceLdsBytes];
+
+  float4 p = make_float4(0.f, 0.f, 0.f, 1.f);
+  float4 pl = make_float4(__builtin_nanf(""), 0.f, 0.f, 0.f);
+  float q[3] = {0.f, 0.f, 0.f};
+  float pn_body = 0.f;
+  bool ref_fit = false, ref_ok = false;
+  if (live) {
+    p = gload4(d.src.pts + i);
+    pn_body = lio_body_norm(p);
+    lio_world_point(d.lio.q_wl, d.lio.t_wl, p, q);
+    if (do_search) {
+      uint32_t bi[K];
+      int bm = 0;
+      const float fx = roundf(q[0] * nl.inv_res), fy = roundf(q[1] * nl.inv_res), fz = roundf(q[2] * nl.inv_res);  // Pos2Grid  ivox3d.h:283-286
+      const float lim = (float)(kCoordBias - 32);
+      if (fabsf(fx) < lim && fabsf(fy) < lim && fabsf(fz) < lim) {   // also false for NaN
+        const int rank = voxel_rank(nl, (int)fx, (int)fy, (int)fz);
+        if (rank >= 0) {
+          float4 fp[K];
+          lists_knn<POOLED>(nl, (uint32_t)rank, q, kp.max_range_sq, bi, bm, fp);
+          if (bm >= KMIN) {   // laser_mapping.cc:619-623
+            float px[K], py[K], pz[K];
+#pragma unroll
+            for (int j = 0; j < K; j++) {
+              asm volatile("" ::"v"(fp[j].w));   // see walk_offer
+              px[j] = j < bm ? fp[j].x : 0.f; py[j] = j < bm ? fp[j].y : 0.f; pz[j] = j < bm ? fp[j].z : 0.f;
+            }
+            float4 fit;
+            const bool ok = esti_plane<true>(px, py, pz, bm, kp.plane_threshold, &fit);
+            if (kp.lio_ref) { pl = fit; ref_fit = true; ref_ok = ok; }   // plane_coef_[i] is written whatever the verdict (common_lib.h:229-233)
+            else if (ok) pl = fit;
+            else if (bm < K) { pl.y = fit.y; pl.z = fit.z; pl.w = fit.w; }   // the tile kernel's queued 3- / 4-neighbour fits hand back (NaN, y, z, w)
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < K; j++) *(PCM_GLOBAL uint32_t*)(d.nn + (size_t)i * K + j) = j < bm ? bi[j] : ~0u;
+    } else {
+      pl = gload4(d.planes + (kp.lio_ref == 2 ? __float_as_uint(p.w) : i));   // plane of the previous ObsModel call
+    }
+  }
+  lio_row_and_reduce(d, kp, i, tile_x, live, do_search, p, q, pn_body, pl, ref_fit, ref_ok, s_mem);
+}
+
+void launch_lio_lists(hipStream_t stream, const PairDesc* d_descs, const PairState* d_states, const KernelParams& kp, bool pooled, bool dev) {
+  dim3 grid((unsigned)kp.tiles_per_pair, 1u);
+  if (pooled && dev) k_lio_lists<true, true><<<grid, 256, 0, stream>>>(d_descs, d_states, kp);
+  else if (pooled) k_lio_lists<true, false><<<grid, 256, 0, stream>>>(d_descs, d_states, kp);
+  else if (dev) k_lio_lists<false, true><<<grid, 256, 0, stream>>>(d_descs, d_states, kp);
+  else k_lio_lists<false, false><<<grid, 256, 0, stream>>>(d_descs, d_states, kp);
 }
 
 }  // namespace pcm

@@ -862,13 +862,20 @@ int pcm_obs_model(pcm_ctx* c, const pcm_lio_state* s, int extrinsic_est_en, int 
   init_state(ps, ident);
   PCM_HIPCK(c, hipMemcpyAsync(w->d_descs, &d, sizeof(d), hipMemcpyHostToDevice, st));
   PCM_HIPCK(c, hipMemcpyAsync(w->d_states, &ps, sizeof(ps), hipMemcpyHostToDevice, st));
-  launch_lio_obs(st, w->d_descs, w->d_states, kp);
+  const bool on_lists = lio_on_lists(c);   // d.nl is their view then
+  if (on_lists) launch_lio_lists(st, w->d_descs, w->d_states, kp, lists_pooled_for(c), false);
+  else launch_lio_obs(st, w->d_descs, w->d_states, kp);
   launch_lio_finish(st, w->d_partials, tiles, w->d_sums);
   PCM_HIPCK(c, hipGetLastError());
   double sums[kLioStride];
   PCM_HIPCK(c, hipMemcpyAsync(sums, w->d_sums, sizeof(double) * kLioStride, hipMemcpyDeviceToHost, st));
   PCM_HIPCK(c, hipStreamSynchronize(st));
-  if (rematch) c->lio_planes_valid = true;
+  if (rematch) {
+    c->lio_planes_valid = true;
+    c->nn_in_lists = on_lists;
+    c->nn_lists_generation = c->tg->nlists.generation;
+    c->lio_search_path[on_lists ? 0 : 1] += 1;
+  }
   c->lio_last_obs.set(L.q_wl, L.t_wl);   // the state of this call: what the effect cloud's 81 pd2^2 test is evaluated at
   int t = 0;
   for (int a = 0; a < 12; a++) for (int b = a; b < 12; b++) { out->HTH[a * 12 + b] = sums[t]; out->HTH[b * 12 + a] = sums[t]; t++; }
@@ -963,8 +970,11 @@ int pcm_lio_update(pcm_ctx* c, const pcm_lio_update_params* prm, pcm_lio_filter_
   init_state(h->ps, ident);
   const int rounds = prm->max_iter + 1;
   PCM_HIPCK(c, hipMemcpyAsync(dv, h, offsetof(LioUpdateRecord, b) + offsetof(iekf::Block, tr), hipMemcpyHostToDevice, st));
+  const bool on_lists = lio_on_lists(c);   // desc.nl is their view then
+  const bool pooled = on_lists && lists_pooled_for(c);
   for (int r = 0; r < rounds; r++) {
-    launch_lio_obs_dev(st, &dv->desc, &dv->ps, kp);
+    if (on_lists) launch_lio_lists(st, &dv->desc, &dv->ps, kp, pooled, true);
+    else launch_lio_obs_dev(st, &dv->desc, &dv->ps, kp);
     launch_lio_finish_gated(st, dv, w->d_partials, tiles, w->d_sums);
     launch_iekf_step(st, dv, w->d_sums);
   }
@@ -975,6 +985,9 @@ int pcm_lio_update(pcm_ctx* c, const pcm_lio_update_params* prm, pcm_lio_filter_
   PCM_HIPCK(c, hipStreamSynchronize(st));
   const iekf::Ctl& ctl = h->b.ctl;
   c->lio_planes_valid = true;   // the first call of the loop always matches
+  c->nn_in_lists = on_lists;
+  c->nn_lists_generation = c->tg->nlists.generation;
+  if (ctl.rematches > 0) c->lio_search_path[on_lists ? 0 : 1] += (uint64_t)ctl.rematches;
   c->lio_upd_calls = ctl.iterations;
   c->lio_last_obs.valid = false;
   if (ctl.iterations >= 1 && ctl.iterations <= iekf::kMaxCalls) {   // the state of the last executed ObsModel call
@@ -1068,14 +1081,19 @@ int pcm_map_incremental(pcm_ctx* c, const pcm_lio_state* s, float filter_size_ma
   const uint32_t n = (uint32_t)c->src.n;
   int rc = reserve_target(c, c->tg->tgt.n + n);
   if (rc != PCM_OK) return rc;
-  const bool have_nn = c->lio_planes_valid && c->nn != nullptr && c->tg->map.valid && ekf_inited;
+  // nearest_points_ of the last matching call: positions in the map's point array (the tile kernel) or in the list entries
+  // (k_lio_lists), the latter only while no update or rebuild has moved them since
+  const pcm::NeighbourLists& nl = c->tg->nlists;
+  const bool nn_current = !c->nn_in_lists || (nl.valid && nl.kind == 0 && !nl.stale && nl.generation == c->nn_lists_generation);
+  const bool have_nn = c->lio_planes_valid && c->nn != nullptr && c->tg->map.valid && ekf_inited && nn_current;
+  const float4* nn_pts = c->nn_in_lists ? nl.pts.p : c->tg->map.pts.p;
   LioStateD L;
   for (int a = 0; a < 4; a++) { L.rot[a] = s->rot[a]; L.off_R[a] = s->off_R[a]; }
   for (int a = 0; a < 3; a++) { L.pos[a] = s->pos[a]; L.off_T[a] = s->off_T[a]; }
   const bool reordered = c->cfg.sort_source && c->src_sorted;
   const float4* scan = reordered ? c->src_order : c->src.d_pts;
   uint32_t added = 0;
-  rc = map_incremental_device(c->stream, scan, reordered, n, L, filter_size_map, have_nn ? c->nn : nullptr, have_nn ? c->tg->map.pts : nullptr, c->tg->next_seq,
+  rc = map_incremental_device(c->stream, scan, reordered, n, L, filter_size_map, have_nn ? c->nn : nullptr, have_nn ? nn_pts : nullptr, c->tg->next_seq,
                               c->tg->tgt.d_pts + c->tg->tgt.n, &added, &c->err);
   if (rc != PCM_OK) return rc;
   c->tg->tgt.n += added;
@@ -1348,6 +1366,13 @@ int pcm_debug_phase_cycles(pcm_ctx* c, uint64_t out[8]) {
   return PCM_OK;
 }
 
+int pcm_lio_search_path(pcm_ctx* c, uint64_t counts[2]) {
+  if (!c || !counts) return PCM_ERR_INVALID_ARGUMENT;
+  counts[0] = c->lio_search_path[0];
+  counts[1] = c->lio_search_path[1];
+  return PCM_OK;
+}
+
 int pcm_get_stats(pcm_ctx* c, pcm_stats* out) {
   if (!c || !out) return PCM_ERR_INVALID_ARGUMENT;
   *out = c->stats;
@@ -1360,6 +1385,7 @@ int pcm_reset_stats(pcm_ctx* c) {
   c->stats = pcm_stats{};
   c->stats.target_voxels = v;
   c->stats.target_slots = s;
+  c->lio_search_path[0] = c->lio_search_path[1] = 0;
   return PCM_OK;
 }
 

@@ -26,6 +26,8 @@ int build_target_for_sharing(pcm_ctx* c);
 TargetView lists_view_for(const pcm_ctx* c);
 // ... and whether they are the pooled form of following lists (k_linearize_lists' second template argument)
 bool lists_pooled_for(const pcm_ctx* c);
+// the LIO calls take k_lio_lists: the context set PCM_FLAG_FOLLOWING_LISTS or PCM_FLAG_NEIGHBOUR_LISTS and lists_view_for is not empty
+bool lio_on_lists(const pcm_ctx* c);
 // pclomp NDT: the neighbour-leaf lists of the context's grid, or an empty view (the cells are then looked up one by one)
 TargetView ndt_lists_view(const pcm_ctx* c);
 

@@ -173,7 +173,10 @@ struct NeighbourLists {
   bool time_stages = false;   // HIP events around the update's stages (pcm_set_profiling bit 0)
   float stage_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};   // the last timed update: dirty lists, classify + read-back, rewrite, index merge + rank table, all
   list_pool::Pool pool;
-  void release() { this->~NeighbourLists(); new (this) NeighbourLists(); }   // as TargetMap::release
+  // counts every build and every update that wrote entries: whoever keeps positions in `pts` (pcm_ctx::nn after a matching LIO call
+  // on the lists) remembers the value they belong to.  It survives release().
+  uint64_t generation = 0;
+  void release() { const uint64_t g = generation; this->~NeighbourLists(); new (this) NeighbourLists(); generation = g + 1; }   // as TargetMap::release
 };
 // follow != nullptr (kind 0 only): the pooled form, with the room behind the runs that *follow asks for
 struct ListFollow {
@@ -191,6 +194,9 @@ int update_neighbour_lists(hipStream_t stream, const TargetMap& map, NeighbourLi
 int export_pooled_lists(hipStream_t stream, const NeighbourLists& nl, std::vector<uint32_t>* starts, DevBuf<float4>* entries, std::string* err);
 TargetView view_of_lists(const NeighbourLists& l);
 void launch_linearize_lists(hipStream_t stream, const PairDesc* d_descs, const PairState* d_states, const KernelParams& kp, int npairs, bool write_planes, bool pooled = false);
+// the jueying_lio measurement model on candidate lists (k_lio_lists, neighbour_lists.hip): what launch_lio_obs (dev: launch_lio_obs_dev)
+// computes, through the lists of the descriptor's `nl`
+void launch_lio_lists(hipStream_t stream, const PairDesc* d_descs, const PairState* d_states, const KernelParams& kp, bool pooled, bool dev);
 void launch_linearize_reforder(hipStream_t stream, const PairDesc* d_descs, const PairState* d_states, const KernelParams& kp, int npairs, bool write_planes);
 void launch_linearize_fused(hipStream_t stream, const PairDesc* d_descs, PairState* d_states, const KernelParams& kp, const LsqParams& lp, int npairs, unsigned char* d_flags_row);
 void launch_lio_obs(hipStream_t stream, const PairDesc* d_descs, const PairState* d_states, const KernelParams& kp);
@@ -292,6 +298,11 @@ struct pcm_ctx {
   uint64_t phase_cycles[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // diagnostic (profiling bit2)
   pcm::DevBuf<uint32_t> nn{"nn"};  // LIO: the <= 5 neighbours (indices into map.pts) of every scan point from the last matching call
   bool lio_planes_valid = false;   // planes of the last pcm_obs_model(rematch=1) belong to the current scan
+  // which array `nn` indexes: the map's points (the tile kernel) or the list entries (k_lio_lists), and for the latter the
+  // generation of the lists at that call -- an update or a rebuild since moves the entries, and `nn` then serves nobody
+  bool nn_in_lists = false;
+  uint64_t nn_lists_generation = 0;
+  uint64_t lio_search_path[2] = {0, 0};   // matching ObsModel launches served by k_lio_lists / by the tile kernel (pcm_lio_search_path)
   pcm::DevBuf<float2> lio_aux{"lio_aux"};   // PCM_FLAG_LIO_REFERENCE_SEMANTICS: residuals_ / point_selected_surf_ of LaserMapping, in the caller's scan order;
   size_t lio_aux_n = 0;                     // they outlive the scan (std::vector::resize semantics, laser_mapping.cc:337-338)
   pcm::DevBuf<char> lio_upd{"lio_upd"};      // pcm_lio_update: descriptor, pair state, filter record and trace of the last update (lio_iekf.hip)

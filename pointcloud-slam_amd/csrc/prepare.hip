@@ -312,6 +312,12 @@ TargetView lists_view_for(const pcm_ctx* c) {
   return on ? view_of_lists(c->tg->nlists) : TargetView{};
 }
 
+// The LIO calls (pcm_obs_model, pcm_lio_update, the frame calls) run k_lio_lists when the context asked for lists by a flag and
+// reads them now; lists that exist through the second-use policy alone leave an LIO call on the tile kernel.
+bool lio_on_lists(const pcm_ctx* c) {
+  return c->cfg.model == PCM_MODEL_P2PLANE && (c->cfg.flags & (PCM_FLAG_FOLLOWING_LISTS | PCM_FLAG_NEIGHBOUR_LISTS)) != 0 && lists_view_for(c).pts != nullptr;
+}
+
 // pclomp NDT: the neighbour-leaf lists of the context's grid, or an empty view (the cells are then looked up one by one)
 TargetView ndt_lists_view(const pcm_ctx* c) {
   const bool on = c->cfg.model == PCM_MODEL_NDT_OMP && c->tg->nlists.valid && c->tg->nlists.kind == 1 && c->tg->nlists.num_neighbors == c->cfg.num_neighbors &&

@@ -442,6 +442,13 @@ class Registration:
         names = ("lists", "live_entries", "capacity", "wasted_entries", "updates", "in_place", "relocated", "rebuilds")
         return {k: int(v) for k, v in zip(names, info)}
 
+    def lio_search_path(self) -> tuple:
+        """(lists, tile): matching ObsModel launches (obs_model with rematch, the matching rounds of lio_update) served by the lists
+        kernel and by the tile kernel since the context was made or reset_stats (pcm_lio_search_path)."""
+        n = np.zeros(2, np.uint64)
+        self._check(self._L.pcm_lio_search_path(self._h, n.ctypes.data))
+        return int(n[0]), int(n[1])
+
     def neighbour_list_update_ms(self) -> dict:
         """Device time of the last following-lists update timed under set_profiling(1) (pcm_neighbour_list_update_ms), by stage."""
         ms = np.zeros(5)
