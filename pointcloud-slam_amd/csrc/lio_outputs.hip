@@ -122,13 +122,6 @@ __global__ void __launch_bounds__(256) k_compact(const float4* __restrict__ pts,
 
 inline unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
 
-LioStateD state_of(const pcm_lio_state* st) {
-  LioStateD s;
-  for (int a = 0; a < 4; a++) { s.rot[a] = st->rot[a]; s.off_R[a] = st->off_R[a]; }
-  for (int a = 0; a < 3; a++) { s.pos[a] = st->pos[a]; s.off_T[a] = st->off_T[a]; }
-  return s;
-}
-
 // the frame's records, or the refusal: PCM_ERR_NO_INPUT and the call that took them
 int need_frame(pcm_ctx* c, const char* who) {
   if (c->lio_frame.valid) return PCM_OK;

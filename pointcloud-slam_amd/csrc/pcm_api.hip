@@ -1,6 +1,7 @@
 // pcm_api.hip -- the C ABI of include/pcm_amd.h: the extern "C" entry points of the registration objects and their small helpers
-// (configuration check, cloud upload, the GICP-BFGS functor, the LIO frame).  What a registration reads is built in prepare.hip;
-// the batched device-resident GN/LM loop and the parity hooks (linearize / compute_error) run in align_batch.hip.
+// (configuration check, cloud upload, the target log, the GICP-BFGS functor).  What a registration reads is built in prepare.hip;
+// the batched device-resident GN/LM loop and the parity hooks (linearize / compute_error) run in align_batch.hip; the jueying_lio
+// entry points are in lio_api.hip and use the helpers pcm_core.h declares from here.
 #include "pcm_core.h"
 #include "dev_scratch.h"
 
@@ -23,7 +24,9 @@ int bfgs_scratch(pcm_ctx* c, size_t m) {
   return c->bfgs.reserve(c, need, need + need / 4);
 }
 
-int validate_config(pcm_ctx* c, const pcm_config& g) {
+}  // namespace
+
+int pcm::validate_config(pcm_ctx* c, const pcm_config& g) {
   if (g.model == PCM_MODEL_LOAM) { c->err = "PCM_MODEL_LOAM contexts run through the pcm_loam_* entry points"; return PCM_ERR_UNSUPPORTED; }
   if (g.model != PCM_MODEL_P2PLANE && !is_ndt(g.model) && !is_gicp(g.model) && g.model != PCM_MODEL_NDT_OMP) { c->err = "unknown registration model"; return PCM_ERR_UNSUPPORTED; }
   if (g.model == PCM_MODEL_NDT_OMP) {
@@ -57,7 +60,7 @@ int validate_config(pcm_ctx* c, const pcm_config& g) {
   return PCM_OK;
 }
 
-int set_cloud(pcm_ctx* c, Cloud* cl, const void* points, size_t n, size_t stride, int memory, uint64_t tag, bool allow_borrow) {
+int pcm::set_cloud(pcm_ctx* c, Cloud* cl, const void* points, size_t n, size_t stride, int memory, uint64_t tag, bool allow_borrow) {
   int rc = check_point_records(c, points, n, stride, memory, 0x7fffffffull, false);
   if (rc != PCM_OK) return rc;
   PCM_HIPCK(c, hipSetDevice(c->device));
@@ -82,6 +85,35 @@ int set_cloud(pcm_ctx* c, Cloud* cl, const void* points, size_t n, size_t stride
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));  // the caller may free/reuse its buffer on return
   return PCM_OK;
 }
+
+// the answer of every call that would change a target other contexts read
+int pcm::refuse_shared(pcm_ctx* c, const char* call) {
+  c->err = std::string(call) + ": the target is shared by " + std::to_string(c->tg.holders()) +
+           " contexts and cannot be changed (pcm_set_target or pcm_clear_target gives this context a target of its own)";
+  return PCM_ERR_UNSUPPORTED;
+}
+
+// grow the target point log to hold `need` points (keeps the content)
+int pcm::reserve_target(pcm_ctx* c, size_t need) {
+  Cloud& t = c->tg->tgt;
+  if (need <= t.own.cap && !t.borrowed) return PCM_OK;
+  const size_t cap = std::max(need, t.own.cap + t.own.cap / 2 + 1024);
+  if (t.borrowed) {   // the caller's buffer is copied into an owned log on the first insert (own is empty until then)
+    const int rc = t.own.reserve(c, need, cap);
+    if (rc != PCM_OK) return rc;
+    hipError_t e = t.n ? hipMemcpyAsync(t.own, t.d_pts, sizeof(float4) * t.n, hipMemcpyDeviceToDevice, c->stream) : hipSuccess;
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { t.own.release(); return hip_failure(&c->err, "copy", t.own.what, e); }
+    t.borrowed = false;
+  } else {
+    const int rc = t.own.reserve_keep(c, need, cap, t.n);
+    if (rc != PCM_OK) return rc;
+  }
+  t.d_pts = t.own;
+  return PCM_OK;
+}
+
+namespace {
 
 // ---- the context's reference to its target (target_share.h) ---------------------------------------------------------------------
 // What runs before the last reference frees a target: the device current and this context's stream drained (dev_buf.h).  The
@@ -109,13 +141,6 @@ int own_target_again(pcm_ctx* c) {
   c->src_cov_valid = false;   // computed with the parameters the old target recorded
   c->lio_planes_valid = false;
   return PCM_OK;
-}
-
-// the answer of every call that would change a target other contexts read
-int refuse_shared(pcm_ctx* c, const char* call) {
-  c->err = std::string(call) + ": the target is shared by " + std::to_string(c->tg.holders()) +
-           " contexts and cannot be changed (pcm_set_target or pcm_clear_target gives this context a target of its own)";
-  return PCM_ERR_UNSUPPORTED;
 }
 
 auto make_ndt_solver(pcm_ctx* c) {
@@ -260,31 +285,12 @@ int pcm_set_target(pcm_ctx* c, const void* points, size_t n, size_t stride_bytes
   return rc;
 }
 
-namespace {
-// residuals_.resize(cur_pts, 0); point_selected_surf_.resize(cur_pts, true)  (laser_mapping.cc:337-338): the first
-// min(old, new) entries survive a new scan, appended ones take the default.  plane_coef_ (:339) needs no such care: the
-// IEKF's first ObsModel call of a frame always matches (esekfom.hpp:1529) and rewrites every plane it may read later.
-static int lio_members_resize(pcm_ctx* c, size_t n) {
-  if (n > c->lio_aux.cap) {
-    const int rc = c->lio_aux.reserve_keep(c, n, n + n / 2 + 1024, c->lio_aux_n);
-    if (rc != PCM_OK) return rc;
-  }
-  if (n > c->lio_aux_n) launch_lio_members_init(c->stream, c->lio_aux, (uint32_t)c->lio_aux_n, (uint32_t)n);
-  c->lio_aux_n = n;
-  return PCM_OK;
-}
-}  // namespace
-
 int pcm_set_source(pcm_ctx* c, const void* points, size_t n, size_t stride_bytes, int memory, uint64_t tag) {
   CHECK_CTX(c);
   if (tag != 0 && tag == c->src.tag && c->src.n == n) return PCM_OK;  // fast_gicp_impl.hpp:72-74
   int rc = set_cloud(c, &c->src, points, n, stride_bytes, memory, tag, true);
-  c->lio_frame.take("pcm_set_source");   // the source is no frame's scan any more
-  c->lio_last_obs.valid = false;
+  source_replaced(c, "pcm_set_source");
   c->user_cov_src.clear();   // source_covs_.clear()  fast_gicp_impl.hpp:78
-  c->src_sorted = false;
-  c->lio_planes_valid = false;
-  c->srcmap.valid = false;
   if (rc == PCM_OK && (c->cfg.flags & PCM_FLAG_LIO_REFERENCE_SEMANTICS)) rc = lio_members_resize(c, n);   // one resize per frame
   return rc;
 }
@@ -294,13 +300,10 @@ int pcm_swap_source_and_target(pcm_ctx* c) {
   if (c->tg.shared()) return refuse_shared(c, "pcm_swap_source_and_target");
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   c->src.swap(c->tg->tgt);
-  c->lio_frame.take("pcm_swap_source_and_target");
-  c->lio_last_obs.valid = false;
+  source_replaced(c, "pcm_swap_source_and_target");
   std::swap(c->user_cov_src, c->tg->user_cov);   // source_covs_.swap(target_covs_)  fast_gicp_impl.hpp:55
   c->tg->map.valid = false;
-  c->srcmap.valid = false;
   c->tg->map.index_n = 0; c->srcmap.index_n = 0;
-  c->src_sorted = false;
   return PCM_OK;
 }
 
@@ -347,9 +350,8 @@ int pcm_target_share_count(pcm_ctx* c) {
 
 int pcm_clear_source(pcm_ctx* c) {
   CHECK_CTX(c);
-  c->src.n = 0; c->src.tag = 0; c->src_sorted = false; c->srcmap.valid = false;
-  c->lio_frame.take("pcm_clear_source");
-  c->lio_last_obs.valid = false;
+  c->src.n = 0; c->src.tag = 0;
+  source_replaced(c, "pcm_clear_source");
   return PCM_OK;
 }
 
@@ -405,33 +407,6 @@ int pcm_fitness_score(pcm_ctx* c, const float T[16], double max_range, double* s
   double sum = 0.0, cnt = 0.0;
   for (uint32_t b = 0; b < nblocks; b++) { sum += rows[2 * b]; cnt += rows[2 * b + 1]; }
   *score = cnt > 0.0 ? sum / cnt : DBL_MAX;
-  return PCM_OK;
-}
-
-// ImuProcess::UndistortPcl backward propagation  (jueying_lio/include/imu_processing.hpp:245-285)
-int pcm_undistort(pcm_ctx* c, void* points, size_t n, size_t stride, size_t time_off, int memory, const pcm_imu_pose* poses, int npose, const pcm_lio_state* st) {
-  CHECK_CTX(c);
-  if ((!points && n) || !poses || !st || npose < 0) return PCM_ERR_INVALID_ARGUMENT;
-  if (stride < 16 || (stride % 4) != 0 || time_off + 4 > stride || (time_off % 4) != 0) { c->err = "bad record layout"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (n == 0 || npose < 2) return PCM_OK;
-  PCM_HIPCK(c, hipSetDevice(c->device));
-  LioStateD s;
-  for (int a = 0; a < 4; a++) { s.rot[a] = st->rot[a]; s.off_R[a] = st->off_R[a]; }
-  for (int a = 0; a < 3; a++) { s.pos[a] = st->pos[a]; s.off_T[a] = st->off_T[a]; }
-  const size_t need = up256(sizeof(pcm_imu_pose) * (size_t)npose) + (memory == PCM_MEM_HOST ? up256(n * stride) : 0);
-  int rc = pre_scratch(c, need, "pcm_undistort");
-  if (rc != PCM_OK) return rc;
-  pcm_imu_pose* d_poses = reinterpret_cast<pcm_imu_pose*>(c->pre_arena.p);
-  PCM_HIPCK(c, hipMemcpyAsync(d_poses, poses, sizeof(pcm_imu_pose) * (size_t)npose, hipMemcpyHostToDevice, c->stream));
-  void* d_pts = points;
-  if (memory == PCM_MEM_HOST) {
-    d_pts = c->pre_arena + up256(sizeof(pcm_imu_pose) * (size_t)npose);
-    PCM_HIPCK(c, hipMemcpyAsync(d_pts, points, n * stride, hipMemcpyHostToDevice, c->stream));
-  }
-  rc = undistort_device(c->stream, d_pts, n, stride, time_off, d_poses, npose, s, &c->err);
-  if (rc != PCM_OK) return rc;
-  if (memory == PCM_MEM_HOST) PCM_HIPCK(c, hipMemcpyAsync(points, d_pts, n * stride, hipMemcpyDeviceToHost, c->stream));
-  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   return PCM_OK;
 }
 
@@ -780,278 +755,6 @@ int pcm_compute_error(pcm_ctx* c, const double T[16], double* cost) {
   return PCM_OK;
 }
 
-namespace {
-void quat_mul_d(const double* a, const double* b, double* r) {   // Eigen quaternion product, (x,y,z,w)
-  r[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-  r[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-  r[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-  r[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
-}
-void quat_rot_d(const double* q, const double* v, double* r) {   // Eigen _transformVector
-  double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
-  uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-  const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
-  for (int a = 0; a < 3; a++) r[a] = v[a] + q[3] * uv[a] + c[a];
-}
-void quat_to_rot_d(const double* q, double* R) {   // Eigen Quaternion::toRotationMatrix, row-major
-  const double x = q[0], y = q[1], z = q[2], w = q[3];
-  const double tx = 2 * x, ty = 2 * y, tz = 2 * z, twx = tx * w, twy = ty * w, twz = tz * w;
-  const double txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-  R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-  R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-  R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
-}
-}  // namespace
-
-int pcm_obs_model(pcm_ctx* c, const pcm_lio_state* s, int extrinsic_est_en, int rematch, pcm_obs_result* out) {
-  CHECK_CTX(c);
-  if (!s || !out) return PCM_ERR_INVALID_ARGUMENT;
-  if (c->cfg.model != PCM_MODEL_P2PLANE) { c->err = "pcm_obs_model needs the P2PLANE model"; return PCM_ERR_INVALID_ARGUMENT; }
-  int rc = validate_config(c, c->cfg);
-  if (rc != PCM_OK) return rc;
-  rc = prepare(c);
-  if (rc != PCM_OK) return rc;
-  if (!rematch && !c->lio_planes_valid) { c->err = "pcm_obs_model(rematch=0) before any matching call"; return PCM_ERR_INVALID_ARGUMENT; }
-  // the float state exactly as the reference casts it (laser_mapping.cc:602-603,669-671)
-  LioPose L{};
-  double qwl[4], twl[3], Rd[9], ORd[9];
-  quat_mul_d(s->rot, s->off_R, qwl);
-  quat_rot_d(s->rot, s->off_T, twl);
-  quat_to_rot_d(s->rot, Rd);
-  quat_to_rot_d(s->off_R, ORd);
-  for (int a = 0; a < 4; a++) L.q_wl[a] = (float)qwl[a];
-  for (int a = 0; a < 3; a++) { L.t_wl[a] = (float)(twl[a] + s->pos[a]); L.off_t[a] = (float)s->off_T[a]; }
-  for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { L.Rt[i * 3 + j] = (float)Rd[j * 3 + i]; L.off_R[i * 3 + j] = (float)ORd[i * 3 + j]; }
-
-  const uint32_t n = (uint32_t)c->src.n;
-  const int tiles = (int)((n + 255u) / 256u);
-  Workspace* w = nullptr;
-  rc = ensure_ws(c, &w, 1, (size_t)tiles * kLioStride, 2);
-  if (rc != PCM_OK) return rc;
-  hipStream_t st = c->stream;
-  if (c->cfg.sort_source && !c->src_sorted) {   // new scan: order it along the world grid at this state's pose
-    double Rwl[9];
-    quat_to_rot_d(qwl, Rwl);
-    float g[16] = {(float)Rwl[0], (float)Rwl[1], (float)Rwl[2], L.t_wl[0], (float)Rwl[3], (float)Rwl[4], (float)Rwl[5], L.t_wl[1],
-                   (float)Rwl[6], (float)Rwl[7], (float)Rwl[8], L.t_wl[2], 0.f, 0.f, 0.f, 1.f};
-    SortJob j{c->src.d_pts, c->src_order, n, 0, 0, 0};
-    PCM_HIPCK(c, hipMemcpyAsync(w->d_guesses, g, sizeof(g), hipMemcpyHostToDevice, st));
-    PCM_HIPCK(c, hipMemcpyAsync(w->d_jobs, &j, sizeof(j), hipMemcpyHostToDevice, st));
-    rc = sort_sources_batched(st, w->d_jobs, 1, n, n, w->d_guesses, c->cfg.voxel_resolution, &w->sort, &c->err);
-    if (rc != PCM_OK) return rc;
-    c->src_sorted = true;
-    c->lio_planes_valid = false;
-    if (!rematch) { c->err = "pcm_obs_model(rematch=0) on a new scan"; return PCM_ERR_INVALID_ARGUMENT; }
-  }
-  const bool ref = (c->cfg.flags & PCM_FLAG_LIO_REFERENCE_SEMANTICS) != 0;
-  if (ref) {
-    rc = lio_members_resize(c, n);
-    if (rc != PCM_OK) return rc;
-  }
-  Geom geom = pick_geom(n, 1);
-  KernelParams kp = kernel_params(c->cfg, geom);
-  kp.lio_rematch = rematch ? 1 : 0;
-  kp.lio_extrinsic = extrinsic_est_en ? 1 : 0;
-  kp.lio_ref = !ref ? 0 : ((c->cfg.sort_source && c->src_sorted) ? 2 : 1);
-  PairDesc d;
-  fill_desc(c, &d, w->d_partials);
-  d.lio = L;
-  d.lio_aux = c->lio_aux;
-  PairState ps;
-  const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  init_state(ps, ident);
-  PCM_HIPCK(c, hipMemcpyAsync(w->d_descs, &d, sizeof(d), hipMemcpyHostToDevice, st));
-  PCM_HIPCK(c, hipMemcpyAsync(w->d_states, &ps, sizeof(ps), hipMemcpyHostToDevice, st));
-  const bool on_lists = lio_on_lists(c);   // d.nl is their view then
-  if (on_lists) launch_lio_lists(st, w->d_descs, w->d_states, kp, lists_pooled_for(c), false);
-  else launch_lio_obs(st, w->d_descs, w->d_states, kp);
-  launch_lio_finish(st, w->d_partials, tiles, w->d_sums);
-  PCM_HIPCK(c, hipGetLastError());
-  double sums[kLioStride];
-  PCM_HIPCK(c, hipMemcpyAsync(sums, w->d_sums, sizeof(double) * kLioStride, hipMemcpyDeviceToHost, st));
-  PCM_HIPCK(c, hipStreamSynchronize(st));
-  if (rematch) {
-    c->lio_planes_valid = true;
-    c->nn_in_lists = on_lists;
-    c->nn_lists_generation = c->tg->nlists.generation;
-    c->lio_search_path[on_lists ? 0 : 1] += 1;
-  }
-  c->lio_last_obs.set(L.q_wl, L.t_wl);   // the state of this call: what the effect cloud's 81 pd2^2 test is evaluated at
-  int t = 0;
-  for (int a = 0; a < 12; a++) for (int b = a; b < 12; b++) { out->HTH[a * 12 + b] = sums[t]; out->HTH[b * 12 + a] = sums[t]; t++; }
-  for (int a = 0; a < 12; a++) out->HTh[a] = sums[78 + a];
-  out->sum_h2 = sums[90];
-  out->n_eff = (int32_t)sums[91];
-  out->valid = out->n_eff >= 1 ? 1 : 0;
-  c->stats.linearize_launches += 1;
-  c->stats.point_passes += n;
-  return PCM_OK;
-}
-
-void pcm_lio_default_update_params(pcm_lio_update_params* p) {
-  if (!p) return;
-  std::memset(p, 0, sizeof(*p));
-  p->R = 0.001;        // options.h:12 LASER_POINT_COV
-  p->max_iter = 4;     // laser_mapping.cc:89
-  for (int k = 0; k < 23; k++) p->limit[k] = 0.001;   // laser_mapping.cc:19
-}
-
-// esekf::update_iterated_dyn_share_modified on the device (lio_iekf.h, lio_iekf.hip): the rounds are queued up front, the host waits once
-int pcm_lio_update(pcm_ctx* c, const pcm_lio_update_params* prm, pcm_lio_filter_state* x, double* P, pcm_lio_update_result* res) {
-  CHECK_CTX(c);
-  if (!prm || !x || !P || !res) { c->err = "pcm_lio_update: null argument"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (c->cfg.model != PCM_MODEL_P2PLANE) { c->err = "pcm_lio_update needs the P2PLANE model"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (prm->max_iter < 1 || prm->max_iter + 1 > iekf::kMaxCalls) { c->err = "pcm_lio_update: max_iter must be in 1 .. 15"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (!(prm->R > 0.0) || !std::isfinite(prm->R)) { c->err = "pcm_lio_update: R must be positive and finite"; return PCM_ERR_INVALID_ARGUMENT; }
-  for (int k = 0; k < iekf::N; k++)
-    if (!(prm->limit[k] >= 0.0)) { c->err = "pcm_lio_update: limit must not be negative or NaN"; return PCM_ERR_INVALID_ARGUMENT; }
-  for (int k = 0; k < iekf::NN; k++)
-    if (!std::isfinite(P[k])) { c->err = "pcm_lio_update: P is not finite"; return PCM_ERR_INVALID_ARGUMENT; }
-  {
-    const double* xs = reinterpret_cast<const double*>(x);
-    for (size_t k = 0; k < sizeof(*x) / sizeof(double); k++)
-      if (!std::isfinite(xs[k])) { c->err = "pcm_lio_update: the state is not finite"; return PCM_ERR_INVALID_ARGUMENT; }
-  }
-  int rc = validate_config(c, c->cfg);
-  if (rc != PCM_OK) return rc;
-  rc = prepare(c);
-  if (rc != PCM_OK) return rc;
-  const uint32_t n = (uint32_t)c->src.n;
-  const int tiles = (int)((n + 255u) / 256u);
-  Workspace* w = nullptr;
-  rc = ensure_ws(c, &w, 1, (size_t)tiles * kLioStride, 2);
-  if (rc != PCM_OK) return rc;
-  rc = c->lio_upd.reserve(c, sizeof(LioUpdateRecord), sizeof(LioUpdateRecord));
-  if (rc != PCM_OK) return rc;
-  rc = c->lio_upd_host.reserve(c, sizeof(LioUpdateRecord), sizeof(LioUpdateRecord));
-  if (rc != PCM_OK) return rc;
-  c->lio_upd_calls = 0;
-  LioUpdateRecord* h = reinterpret_cast<LioUpdateRecord*>(c->lio_upd_host.p);
-  LioUpdateRecord* dv = reinterpret_cast<LioUpdateRecord*>(c->lio_upd.p);
-  std::memcpy(&h->b.x_prop, x, sizeof(iekf::State));
-  std::memcpy(h->b.P_prop, P, sizeof(double) * iekf::NN);
-  h->b.prm.R = prm->R;
-  h->b.prm.max_iter = prm->max_iter;
-  h->b.prm.extrinsic = prm->extrinsic_est_en ? 1 : 0;
-  for (int k = 0; k < iekf::N; k++) h->b.prm.limit[k] = prm->limit[k];
-  iekf::begin(h->b);
-  iekf::PoseF L0{};
-  iekf::pose_of(h->b.x, &L0);
-  L0.rematch = 1;   // dyn_share.converge = true  esekfom.hpp:1529
-  hipStream_t st = c->stream;
-  if (c->cfg.sort_source && !c->src_sorted) {   // new scan: order it along the world grid at the propagated state's pose (as pcm_obs_model)
-    double qwl[4], Rwl[9];
-    quat_mul_d(x->rot, x->off_R, qwl);
-    quat_to_rot_d(qwl, Rwl);
-    float g[16] = {(float)Rwl[0], (float)Rwl[1], (float)Rwl[2], L0.t_wl[0], (float)Rwl[3], (float)Rwl[4], (float)Rwl[5], L0.t_wl[1],
-                   (float)Rwl[6], (float)Rwl[7], (float)Rwl[8], L0.t_wl[2], 0.f, 0.f, 0.f, 1.f};
-    SortJob j{c->src.d_pts, c->src_order, n, 0, 0, 0};
-    PCM_HIPCK(c, hipMemcpyAsync(w->d_guesses, g, sizeof(g), hipMemcpyHostToDevice, st));
-    PCM_HIPCK(c, hipMemcpyAsync(w->d_jobs, &j, sizeof(j), hipMemcpyHostToDevice, st));
-    rc = sort_sources_batched(st, w->d_jobs, 1, n, n, w->d_guesses, c->cfg.voxel_resolution, &w->sort, &c->err);
-    if (rc != PCM_OK) return rc;
-    c->src_sorted = true;
-  }
-  c->lio_planes_valid = false;
-  const bool ref = (c->cfg.flags & PCM_FLAG_LIO_REFERENCE_SEMANTICS) != 0;
-  if (ref) {
-    rc = lio_members_resize(c, n);
-    if (rc != PCM_OK) return rc;
-  }
-  Geom geom = pick_geom(n, 1);
-  KernelParams kp = kernel_params(c->cfg, geom);
-  kp.lio_rematch = 1;   // not read by the device-flag instance
-  kp.lio_extrinsic = prm->extrinsic_est_en ? 1 : 0;
-  kp.lio_ref = !ref ? 0 : ((c->cfg.sort_source && c->src_sorted) ? 2 : 1);
-  fill_desc(c, &h->desc, w->d_partials);
-  std::memcpy(&h->desc.lio, &L0, sizeof(L0));
-  h->desc.lio_aux = c->lio_aux;
-  const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  init_state(h->ps, ident);
-  const int rounds = prm->max_iter + 1;
-  PCM_HIPCK(c, hipMemcpyAsync(dv, h, offsetof(LioUpdateRecord, b) + offsetof(iekf::Block, tr), hipMemcpyHostToDevice, st));
-  const bool on_lists = lio_on_lists(c);   // desc.nl is their view then
-  const bool pooled = on_lists && lists_pooled_for(c);
-  for (int r = 0; r < rounds; r++) {
-    if (on_lists) launch_lio_lists(st, &dv->desc, &dv->ps, kp, pooled, true);
-    else launch_lio_obs_dev(st, &dv->desc, &dv->ps, kp);
-    launch_lio_finish_gated(st, dv, w->d_partials, tiles, w->d_sums);
-    launch_iekf_step(st, dv, w->d_sums);
-  }
-  PCM_HIPCK(c, hipGetLastError());
-  const size_t back0 = offsetof(LioUpdateRecord, b) + offsetof(iekf::Block, x);
-  const size_t back1 = offsetof(LioUpdateRecord, b) + offsetof(iekf::Block, tr) + sizeof(iekf::Trace) * (size_t)rounds;
-  PCM_HIPCK(c, hipMemcpyAsync(reinterpret_cast<char*>(h) + back0, reinterpret_cast<const char*>(dv) + back0, back1 - back0, hipMemcpyDeviceToHost, st));
-  PCM_HIPCK(c, hipStreamSynchronize(st));
-  const iekf::Ctl& ctl = h->b.ctl;
-  c->lio_planes_valid = true;   // the first call of the loop always matches
-  c->nn_in_lists = on_lists;
-  c->nn_lists_generation = c->tg->nlists.generation;
-  if (ctl.rematches > 0) c->lio_search_path[on_lists ? 0 : 1] += (uint64_t)ctl.rematches;
-  c->lio_upd_calls = ctl.iterations;
-  c->lio_last_obs.valid = false;
-  if (ctl.iterations >= 1 && ctl.iterations <= iekf::kMaxCalls) {   // the state of the last executed ObsModel call
-    iekf::PoseF Ll{};
-    iekf::pose_of(h->b.tr[ctl.iterations - 1].x, &Ll);
-    c->lio_last_obs.set(Ll.q_wl, Ll.t_wl);
-  }
-  std::memcpy(x, &h->b.x, sizeof(iekf::State));
-  std::memcpy(P, h->b.P, sizeof(double) * iekf::NN);
-  std::memset(res, 0, sizeof(*res));
-  res->iterations = ctl.iterations;
-  res->rematches = ctl.rematches;
-  res->valid_calls = ctl.valid_calls;
-  res->t = ctl.t;
-  res->n_eff_last = ctl.n_eff_last;
-  res->sum_h2_last = ctl.sum_h2_last;
-  res->status = PCM_OK;
-  c->stats.linearize_launches += (uint64_t)ctl.iterations;
-  c->stats.point_passes += (uint64_t)n * (uint64_t)ctl.iterations;
-  bool finite = true;
-  for (int k = 0; k < iekf::NN; k++) finite = finite && std::isfinite(P[k]);
-  for (size_t k = 0; k < sizeof(*x) / sizeof(double); k++) finite = finite && std::isfinite(reinterpret_cast<const double*>(x)[k]);
-  if (!finite || !ctl.done) {
-    c->err = !ctl.done ? "pcm_lio_update: the loop did not reach its end" : "pcm_lio_update: the updated state or covariance is not finite";
-    res->status = PCM_ERR_INTERNAL;
-    return PCM_ERR_INTERNAL;
-  }
-  return PCM_OK;
-}
-
-int pcm_lio_update_trace(pcm_ctx* c, int call, pcm_lio_filter_state* x, int32_t* converge, int32_t* n_eff, double* sums90, double* dx23) {
-  CHECK_CTX(c);
-  if (call < 0 || call >= c->lio_upd_calls || !c->lio_upd_host.p) { c->err = "pcm_lio_update_trace: no such call of the last pcm_lio_update"; return PCM_ERR_INVALID_ARGUMENT; }
-  const iekf::Trace& t = reinterpret_cast<const LioUpdateRecord*>(c->lio_upd_host.p)->b.tr[call];
-  if (x) std::memcpy(x, &t.x, sizeof(iekf::State));
-  if (converge) *converge = t.converge;
-  if (n_eff) *n_eff = t.n_eff;
-  if (sums90) std::memcpy(sums90, t.sums, sizeof(t.sums));
-  if (dx23) std::memcpy(dx23, t.dx, sizeof(t.dx));
-  return PCM_OK;
-}
-
-namespace {
-// grow the target point log to hold `need` points (keeps the content)
-int reserve_target(pcm_ctx* c, size_t need) {
-  Cloud& t = c->tg->tgt;
-  if (need <= t.own.cap && !t.borrowed) return PCM_OK;
-  const size_t cap = std::max(need, t.own.cap + t.own.cap / 2 + 1024);
-  if (t.borrowed) {   // the caller's buffer is copied into an owned log on the first insert (own is empty until then)
-    const int rc = t.own.reserve(c, need, cap);
-    if (rc != PCM_OK) return rc;
-    hipError_t e = t.n ? hipMemcpyAsync(t.own, t.d_pts, sizeof(float4) * t.n, hipMemcpyDeviceToDevice, c->stream) : hipSuccess;
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { t.own.release(); return hip_failure(&c->err, "copy", t.own.what, e); }
-    t.borrowed = false;
-  } else {
-    const int rc = t.own.reserve_keep(c, need, cap, t.n);
-    if (rc != PCM_OK) return rc;
-  }
-  t.d_pts = t.own;
-  return PCM_OK;
-}
-}  // namespace
-
 int pcm_target_insert(pcm_ctx* c, const void* points, size_t n, size_t stride_bytes, int memory) {
   CHECK_CTX(c);
   if (!points && n) { c->err = "null point buffer"; return PCM_ERR_INVALID_ARGUMENT; }
@@ -1070,183 +773,6 @@ int pcm_target_insert(pcm_ctx* c, const void* points, size_t n, size_t stride_by
   c->tg->map.valid = false;
   c->tg->tgt_dynamic = true;
   return PCM_OK;
-}
-
-int pcm_map_incremental(pcm_ctx* c, const pcm_lio_state* s, float filter_size_map, int ekf_inited, size_t* num_added) {
-  CHECK_CTX(c);
-  if (!s) return PCM_ERR_INVALID_ARGUMENT;
-  if (c->tg.shared()) return refuse_shared(c, "pcm_map_incremental");
-  if (c->src.n == 0) { c->err = "pcm_map_incremental without a source scan"; return PCM_ERR_NO_INPUT; }
-  PCM_HIPCK(c, hipSetDevice(c->device));
-  const uint32_t n = (uint32_t)c->src.n;
-  int rc = reserve_target(c, c->tg->tgt.n + n);
-  if (rc != PCM_OK) return rc;
-  // nearest_points_ of the last matching call: positions in the map's point array (the tile kernel) or in the list entries
-  // (k_lio_lists), the latter only while no update or rebuild has moved them since
-  const pcm::NeighbourLists& nl = c->tg->nlists;
-  const bool nn_current = !c->nn_in_lists || (nl.valid && nl.kind == 0 && !nl.stale && nl.generation == c->nn_lists_generation);
-  const bool have_nn = c->lio_planes_valid && c->nn != nullptr && c->tg->map.valid && ekf_inited && nn_current;
-  const float4* nn_pts = c->nn_in_lists ? nl.pts.p : c->tg->map.pts.p;
-  LioStateD L;
-  for (int a = 0; a < 4; a++) { L.rot[a] = s->rot[a]; L.off_R[a] = s->off_R[a]; }
-  for (int a = 0; a < 3; a++) { L.pos[a] = s->pos[a]; L.off_T[a] = s->off_T[a]; }
-  const bool reordered = c->cfg.sort_source && c->src_sorted;
-  const float4* scan = reordered ? c->src_order : c->src.d_pts;
-  uint32_t added = 0;
-  rc = map_incremental_device(c->stream, scan, reordered, n, L, filter_size_map, have_nn ? c->nn : nullptr, have_nn ? nn_pts : nullptr, c->tg->next_seq,
-                              c->tg->tgt.d_pts + c->tg->tgt.n, &added, &c->err);
-  if (rc != PCM_OK) return rc;
-  c->tg->tgt.n += added;
-  c->tg->next_seq += added;
-  c->tg->tgt.tag = 0;
-  if (added) { c->tg->map.valid = false; c->tg->tgt_dynamic = true; }
-  if (num_added) *num_added = added;
-  return PCM_OK;
-}
-
-// ---------------------------------------------------------------------------
-// One LiDAR frame of LaserMapping::Run on device buffers (jueying_lio/src/laser_mapping.cc:323-347 front end, :525-583 back end).
-// ---------------------------------------------------------------------------
-int pcm_lio_frame_begin(pcm_ctx* c, const void* custom_points, size_t n, int memory, const pcm_lio_frame_params* prm, const pcm_imu_pose* poses, int npose,
-                        const pcm_lio_state* end_state, size_t* n_scan) {
-  CHECK_CTX(c);
-  if ((!custom_points && n) || !prm || !n_scan || (npose >= 2 && (!poses || !end_state))) return PCM_ERR_INVALID_ARGUMENT;
-  if (n > 0xffffffffull) { c->err = "too many points"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (!(prm->leaf_size >= 0.f)) { c->err = "leaf_size must be >= 0"; return PCM_ERR_INVALID_ARGUMENT; }
-  *n_scan = 0;
-  if (n == 0) { c->err = "empty frame"; return PCM_ERR_NO_INPUT; }
-  PCM_HIPCK(c, hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  // frame arena: [raw message | filtered records | down-sampled records | IMU poses | scratch of the operators]; grow-only, so the
-  // steady state makes no allocation.  The raw message is the only host -> device copy of the frame.
-  const size_t o_raw = 0, o_flt = o_raw + up256(n * 20), o_ds = o_flt + up256(n * 48), o_pose = o_ds + up256(n * 48);
-  const size_t o_scr = o_pose + up256(sizeof(pcm_imu_pose) * (size_t)std::max(npose, 1));
-  int rc = pre_scratch(c, o_scr + std::max(livox_filter_scratch_bytes(n), voxel_downsample_scratch_bytes(n)), "pcm_lio_frame_begin");
-  if (rc != PCM_OK) return rc;
-  char* A = c->pre_arena;
-  const void* d_raw = custom_points;
-  if (memory == PCM_MEM_HOST) {
-    PCM_HIPCK(c, hipMemcpyAsync(A + o_raw, custom_points, n * 20, hipMemcpyHostToDevice, st));
-    d_raw = A + o_raw;
-  }
-  // 1. PointCloudPreprocess::AviaHandler  (pointcloud_preprocess.cc:44-88)
-  size_t n_flt = 0;
-  rc = livox_filter_device(st, d_raw, n, prm->num_scans, prm->point_filter_num, prm->blind, A + o_flt, &n_flt, A + o_scr, &c->err);
-  if (rc != PCM_OK) return rc;
-  if (n_flt == 0) { c->err = "no point of the frame passed the driver-message filter"; return PCM_ERR_NO_INPUT; }
-  // 2. ImuProcess::UndistortPcl backward loop  (imu_processing.hpp:245-285): in place on the filtered records (time stamp = curvature).
-  //    The reference sorts the scan by time first (:177-178); a Livox message is time-ordered, and the compensation of a point
-  //    depends on its own stamp only, so the message order is kept.
-  if (npose >= 2) {
-    LioStateD s;
-    for (int a = 0; a < 4; a++) { s.rot[a] = end_state->rot[a]; s.off_R[a] = end_state->off_R[a]; }
-    for (int a = 0; a < 3; a++) { s.pos[a] = end_state->pos[a]; s.off_T[a] = end_state->off_T[a]; }
-    PCM_HIPCK(c, hipMemcpyAsync(A + o_pose, poses, sizeof(pcm_imu_pose) * (size_t)npose, hipMemcpyHostToDevice, st));
-    rc = undistort_device(st, A + o_flt, n_flt, 48, 36, reinterpret_cast<const pcm_imu_pose*>(A + o_pose), npose, s, &c->err);   // PointXYZINormal::curvature: byte 36
-    if (rc != PCM_OK) return rc;
-  }
-  // 3. voxel_scan_.filter()  (laser_mapping.cc:323-328); leaf 0 = no down-sampling
-  const char* d_scan = A + o_flt;
-  size_t n_ds = n_flt;
-  if (prm->leaf_size > 0.f) {
-    rc = voxel_downsample_device(st, A + o_flt, n_flt, 48, prm->leaf_size, reinterpret_cast<float*>(A + o_ds), &n_ds, A + o_scr, &c->err);
-    if (rc != PCM_OK) return rc;
-    d_scan = A + o_ds;
-  }
-  if (n_ds == 0) { c->err = "empty scan after down-sampling"; return PCM_ERR_NO_INPUT; }
-  // 4. the down-sampled scan (scan_down_body_) becomes the source of this object: device -> device, no host copy
-  if (c->cfg.flags & PCM_FLAG_LIO_REFERENCE_SEMANTICS) {   // one resize of residuals_ / point_selected_surf_ per frame  laser_mapping.cc:335-339
-    rc = lio_members_resize(c, n_ds);
-    if (rc != PCM_OK) return rc;
-  }
-  rc = set_cloud(c, &c->src, d_scan, n_ds, 48, PCM_MEM_DEVICE, 0, false);
-  if (rc != PCM_OK) return rc;
-  c->src_sorted = false;
-  c->lio_planes_valid = false;
-  c->srcmap.valid = false;
-  c->src_cov_valid = false;
-  c->user_cov_src.clear();
-  c->lio_frame.set(A + o_flt, n_flt, d_scan, n_ds);   // scan_undistort_ and scan_down_body_, for the frame outputs (lio_outputs.hip)
-  c->lio_last_obs.valid = false;
-  *n_scan = n_ds;
-  return PCM_OK;
-}
-
-// The same frame for a sensor_msgs::PointCloud2 cloud: the handler of its LiDAR type (pointcloud_preprocess.cc:89-305) in front, and
-// the time sort of ImuProcess::UndistortPcl (imu_processing.hpp:177-178) made definite: (curvature, input index).
-int pcm_lio_frame_begin_cloud(pcm_ctx* c, const void* points, size_t n, int memory, const pcm_lidar_desc* desc, float leaf_size, const pcm_imu_pose* poses, int npose,
-                              const pcm_lio_state* end_state, size_t* n_scan) {
-  CHECK_CTX(c);
-  if (!n_scan || (npose >= 2 && (!poses || !end_state))) return PCM_ERR_INVALID_ARGUMENT;
-  *n_scan = 0;
-  int rc = lidar_check_cloud(c, points, n, memory, desc);
-  if (rc != PCM_OK) return rc;
-  if (!(leaf_size >= 0.f)) { c->err = "leaf_size must be >= 0"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (n == 0) { c->err = "empty frame"; return PCM_ERR_NO_INPUT; }
-  PCM_HIPCK(c, hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  // frame arena: [raw cloud | filtered records, later the down-sampled ones | time-sorted records | IMU poses | scratch of the operators]
-  const size_t o_raw = 0, o_flt = o_raw + (memory == PCM_MEM_HOST ? up256(n * desc->stride_bytes) : 0), o_srt = o_flt + up256(n * 48), o_pose = o_srt + up256(n * 48);
-  const size_t o_scr = o_pose + up256(sizeof(pcm_imu_pose) * (size_t)std::max(npose, 1));
-  rc = pre_scratch(c, o_scr + std::max({lidar_filter_scratch_bytes(n), lidar_time_sort_scratch_bytes(n), voxel_downsample_scratch_bytes(n)}), "pcm_lio_frame_begin_cloud");
-  if (rc != PCM_OK) return rc;
-  char* A = c->pre_arena;
-  const void* d_raw = points;
-  int hint = -1;
-  if (memory == PCM_MEM_HOST) {
-    PCM_HIPCK(c, hipMemcpyAsync(A + o_raw, points, n * desc->stride_bytes, hipMemcpyHostToDevice, st));
-    d_raw = A + o_raw;
-    hint = lidar_given_on_host(points, n, *desc);
-  }
-  // 1. the handler: kept points in input order
-  size_t n_flt = 0;
-  int given = 1;
-  rc = lidar_filter_device(st, d_raw, n, *desc, hint, A + o_flt, n, &n_flt, &given, A + o_scr, &c->err);
-  if (rc != PCM_OK) return rc;
-  if (n_flt == 0) { c->err = "no point of the frame passed the handler"; return PCM_ERR_NO_INPUT; }
-  // 2. sort by time; the radix sort is stable, so equal stamps keep their input order
-  rc = lidar_time_sort_device(st, A + o_flt, n_flt, A + o_srt, A + o_scr, &c->err);
-  if (rc != PCM_OK) return rc;
-  // 3. ImuProcess::UndistortPcl backward loop, in place on the sorted records
-  if (npose >= 2) {
-    LioStateD s;
-    for (int a = 0; a < 4; a++) { s.rot[a] = end_state->rot[a]; s.off_R[a] = end_state->off_R[a]; }
-    for (int a = 0; a < 3; a++) { s.pos[a] = end_state->pos[a]; s.off_T[a] = end_state->off_T[a]; }
-    PCM_HIPCK(c, hipMemcpyAsync(A + o_pose, poses, sizeof(pcm_imu_pose) * (size_t)npose, hipMemcpyHostToDevice, st));
-    rc = undistort_device(st, A + o_srt, n_flt, 48, 36, reinterpret_cast<const pcm_imu_pose*>(A + o_pose), npose, s, &c->err);
-    if (rc != PCM_OK) return rc;
-  }
-  // 4. voxel_scan_.filter(); leaf 0 = the sorted scan as it is.  The filtered records are free again: the centroids go there.
-  const char* d_scan = A + o_srt;
-  size_t n_ds = n_flt;
-  if (leaf_size > 0.f) {
-    rc = voxel_downsample_device(st, A + o_srt, n_flt, 48, leaf_size, reinterpret_cast<float*>(A + o_flt), &n_ds, A + o_scr, &c->err);
-    if (rc != PCM_OK) return rc;
-    d_scan = A + o_flt;
-  }
-  if (n_ds == 0) { c->err = "empty scan after down-sampling"; return PCM_ERR_NO_INPUT; }
-  // 5. the scan becomes the source of this object: device -> device
-  if (c->cfg.flags & PCM_FLAG_LIO_REFERENCE_SEMANTICS) {
-    rc = lio_members_resize(c, n_ds);
-    if (rc != PCM_OK) return rc;
-  }
-  rc = set_cloud(c, &c->src, d_scan, n_ds, 48, PCM_MEM_DEVICE, 0, false);
-  if (rc != PCM_OK) return rc;
-  c->src_sorted = false;
-  c->lio_planes_valid = false;
-  c->srcmap.valid = false;
-  c->src_cov_valid = false;
-  c->user_cov_src.clear();
-  c->lio_frame.set(A + o_srt, n_flt, d_scan, n_ds);
-  c->lio_last_obs.valid = false;
-  *n_scan = n_ds;
-  return PCM_OK;
-}
-
-int pcm_lio_frame_end(pcm_ctx* c, const pcm_lio_state* s, float filter_size_map, int ekf_inited, size_t* num_added) {
-  CHECK_CTX(c);
-  if (c->tg.shared()) return refuse_shared(c, "pcm_lio_frame_end");
-  return pcm_map_incremental(c, s, filter_size_map, ekf_inited, num_added);
 }
 
 int pcm_get_source(pcm_ctx* c, float* out_xyz, size_t capacity_points, size_t* n) {
@@ -1344,32 +870,9 @@ int pcm_neighbour_list_headroom(pcm_ctx* c, float fraction, uint64_t min_entries
   return PCM_OK;
 }
 
-int pcm_get_lio_members(pcm_ctx* c, float* residuals, uint8_t* selected, size_t n) {
-  CHECK_CTX(c);
-  if (!(c->cfg.flags & PCM_FLAG_LIO_REFERENCE_SEMANTICS) || !c->lio_aux || n != c->lio_aux_n || n != c->src.n) {
-    c->err = "pcm_get_lio_members: needs PCM_FLAG_LIO_REFERENCE_SEMANTICS and n equal to the source size";
-    return PCM_ERR_INVALID_ARGUMENT;
-  }
-  std::vector<float2> tmp(n);
-  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
-  if (n) PCM_HIPCK(c, hipMemcpy(tmp.data(), c->lio_aux, sizeof(float2) * n, hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < n; i++) {
-    if (residuals) residuals[i] = tmp[i].x;
-    if (selected) selected[i] = tmp[i].y != 0.f ? 1 : 0;
-  }
-  return PCM_OK;
-}
-
 int pcm_debug_phase_cycles(pcm_ctx* c, uint64_t out[8]) {
   if (!c || !out) return PCM_ERR_INVALID_ARGUMENT;
   for (int k = 0; k < 8; k++) { out[k] = c->phase_cycles[k]; c->phase_cycles[k] = 0; }
-  return PCM_OK;
-}
-
-int pcm_lio_search_path(pcm_ctx* c, uint64_t counts[2]) {
-  if (!c || !counts) return PCM_ERR_INVALID_ARGUMENT;
-  counts[0] = c->lio_search_path[0];
-  counts[1] = c->lio_search_path[1];
   return PCM_OK;
 }
 

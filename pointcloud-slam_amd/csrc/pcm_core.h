@@ -1,12 +1,21 @@
-// pcm_core.h -- what the three translation units behind the core C ABI share: pcm_api.hip (the extern "C" entry points),
-// prepare.hip (lazy build of everything a registration reads, the pair descriptor and the kernel parameters) and
-// align_batch.hip (the batch workspace and the round loops).  Internal: nothing here is exported (exports.map).
+// pcm_core.h -- what the four translation units behind the core C ABI share: pcm_api.hip (the extern "C" entry points of the
+// registration objects), lio_api.hip (those of jueying_lio: measurement model, IEKF update, map growth, the frame), prepare.hip
+// (lazy build of everything a registration reads, the pair descriptor and the kernel parameters) and align_batch.hip (the
+// batch workspace and the round loops).  Internal: nothing here is exported (exports.map).
 #pragma once
 
 #include "host_util.h"
 #include "pclndt_host.h"
 
 namespace pcm {
+
+// ---- pcm_api.hip: what the LIO entry points (lio_api.hip) use of it -------------------------------------------------------------
+int validate_config(pcm_ctx* c, const pcm_config& g);
+int set_cloud(pcm_ctx* c, Cloud* cl, const void* points, size_t n, size_t stride, int memory, uint64_t tag, bool allow_borrow);
+int refuse_shared(pcm_ctx* c, const char* call);   // the answer of every call that would change a target other contexts read
+int reserve_target(pcm_ctx* c, size_t need);       // grow the target point log to hold `need` points (keeps the content)
+// ---- lio_api.hip ---------------------------------------------------------------------------------------------------------------
+int lio_members_resize(pcm_ctx* c, size_t n);      // residuals_ / point_selected_surf_ follow the scan size (pcm_set_source)
 
 // ---- prepare.hip -------------------------------------------------------------------------------------------------------------
 bool is_ndt(int model);         // fast_gicp NDTCuda P2D / D2D

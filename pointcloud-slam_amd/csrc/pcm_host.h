@@ -110,6 +110,12 @@ struct SortScratch {
 };
 // MapIncremental on the device (voxel_hash.hip)
 struct LioStateD { double rot[4], pos[3], off_R[4], off_T[3]; };
+inline LioStateD state_of(const pcm_lio_state* st) {
+  LioStateD s;
+  for (int a = 0; a < 4; a++) { s.rot[a] = st->rot[a]; s.off_R[a] = st->off_R[a]; }
+  for (int a = 0; a < 3; a++) { s.pos[a] = st->pos[a]; s.off_T[a] = st->off_T[a]; }
+  return s;
+}
 int map_incremental_device(hipStream_t stream, const float4* scan, bool scan_reordered, uint32_t n, const LioStateD& s, float filter_size_map, const uint32_t* nn,
                            const float4* map_pts, uint32_t seq0, float4* out_append, uint32_t* num_added, std::string* err);
 // preprocess.hip
@@ -339,6 +345,18 @@ namespace pcm {
 inline int take_pre_arena(pcm_ctx* c, size_t bytes, const char* who) {
   c->lio_frame.take(who);
   return c->pre_arena.reserve(c->stream, &c->err, bytes, bytes + bytes / 4);
+}
+// the source is another cloud from now on (set, swapped, cleared, or a frame's scan adopted by the entry point `who`): nothing
+// derived from the old one serves it -- the frame record, the pose of the last ObsModel call, the re-ordered copy, the planes
+// and neighbours of the last matching call, the source's voxel map and its covariances.  Every call that replaces the source
+// comes here; covariances the caller handed in (user_cov_src) are its own business
+inline void source_replaced(pcm_ctx* c, const char* who) {
+  c->lio_frame.take(who);
+  c->lio_last_obs.valid = false;
+  c->src_sorted = false;
+  c->lio_planes_valid = false;
+  c->srcmap.valid = false;
+  c->src_cov_valid = false;
 }
 template <typename T> int DevBuf<T>::reserve(pcm_ctx* c, size_t need, size_t new_cap, bool zero) { return reserve(c->stream, &c->err, need, new_cap, zero); }
 template <typename T> int DevBuf<T>::reserve_keep(pcm_ctx* c, size_t need, size_t new_cap, size_t keep) { return reserve_keep(c->stream, &c->err, need, new_cap, keep); }

@@ -1,6 +1,6 @@
 // target_share.h -- how registration contexts hold a built target: a counted reference to one holder object.  A context that
 // never shares is the only holder of its own; pcm_share_target makes a second context hold the same one.  The rules, which the
-// callers in pcm_api.hip keep and tests/target_share_check.cpp walks through:
+// callers in pcm_api.hip and lio_api.hip keep and tests/target_share_check.cpp walks through:
 //   * a holder with more than one reference is immutable: whoever would change it asks mutable_by_me() first and refuses;
 //   * attach / detach change one reference only: the other holders never notice;
 //   * the last reference to go runs the release hook (device current, stream synchronised: the DevBuf rule of dev_buf.h) and

@@ -1,6 +1,6 @@
 // target_share_check.cpp -- the attach / detach / last-release rules of csrc/target_share.h, walked through on the host: plain
 // g++, no GPU, own main, so that it is also built with -fsanitize=address,undefined (tests/test_shared_target_capi.py).  A
-// "context" here is the reference plus the calls pcm_api.hip makes on it; the payload counts its constructions and destructions,
+// "context" here is the reference plus the calls pcm_api.hip and lio_api.hip make on it; the payload counts its constructions and destructions,
 // and the release hook counts its runs, so a double release, a leak or a use after the release shows as a wrong count or as a
 // sanitizer report.
 #include <cstdio>
