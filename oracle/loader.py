@@ -145,6 +145,7 @@ class Oracle:
 
     def swap_source_and_target(self):
         lib().orc_swap_source_and_target(self._h)
+        self._keep["s"], self._keep["t"] = self._keep.get("t"), self._keep.get("s")   # covariances() sizes its buffer by these
 
     def linearize(self, T):
         T = np.ascontiguousarray(T, dtype=np.float64)

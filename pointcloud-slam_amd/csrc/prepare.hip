@@ -298,7 +298,9 @@ int ensure_pair_buffers(pcm_ctx* c) {
   }
   int rc = c->counter.reserve(c, 1, 1, true);
   if (rc == PCM_OK) rc = c->nn.reserve(c, 5 * c->src.n, 5 * c->src.n);
-  if (rc == PCM_OK) rc = c->planes.reserve(c, c->src.n, c->src.n);
+  // a new plane array is cleared: with PCM_FLAG_LIO_REFERENCE rows no fit has written are read back (get_planes), and the reference's
+  // plane_coef_ starts as a value-initialised vector, not as whatever the allocator handed out
+  if (rc == PCM_OK) rc = c->planes.reserve(c, c->src.n, c->src.n, true);
   return rc;
 }
 
