@@ -1,5 +1,5 @@
-// dev_buf.h -- the project's one way to hold device and pinned host memory: the HIP error checks, grow-only owned buffers and
-// the 256-byte round-up.  Knows nothing of the context (pcm_host.h holds these buffers as members and adds the pcm_ctx forms).
+// dev_buf.h -- the project's one way to hold device and pinned host memory: the HIP error checks, grow-only owned buffers
+// (the 256-byte round-up is arena_carver.h's).  Knows nothing of the context (pcm_host.h holds these buffers as members and adds the pcm_ctx forms).
 // Host code only.
 #pragma once
 
@@ -9,6 +9,7 @@
 #include <utility>
 
 #include "../../include/pcm_amd.h"
+#include "arena_carver.h"
 
 // a failed HIP call: its text and the runtime's message into *errptr, PCM_ERR_HIP to the caller
 #define PCM_HIPCK_ERR(errptr, x)                                                     \
@@ -25,8 +26,6 @@
 struct pcm_ctx;
 
 namespace pcm {
-
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 inline int hip_failure(std::string* err, const char* call, const char* what, hipError_t e) {
   *err = std::string(call) + "(" + what + "): " + hipGetErrorString(e);

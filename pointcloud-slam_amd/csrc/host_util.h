@@ -17,7 +17,7 @@ inline bool finite_d(double v) { return v == v && v <= 1.7976931348623157e308 &&
 inline int check_point_records(pcm_ctx* c, const void* pts, size_t n, size_t stride, int memory, size_t max_n, bool check_memory = true) {
   if (!pts && n) { c->err = "null point buffer"; return PCM_ERR_INVALID_ARGUMENT; }
   if (stride < 3 * sizeof(float) || (stride % sizeof(float)) != 0) { c->err = "stride must be a multiple of 4 and >= 12 bytes"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (check_memory && memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (check_memory && pcm::check_memory(c, memory, "memory") != PCM_OK) return PCM_ERR_INVALID_ARGUMENT;
   if (n > max_n) { c->err = "cloud too large"; return PCM_ERR_INVALID_ARGUMENT; }
   return PCM_OK;
 }

@@ -16,6 +16,7 @@
 // past the end carries the constant function, which sits behind every real point.
 #include "host_util.h"
 #include "lidar_handlers.h"
+#include "pre_layouts.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -160,44 +161,12 @@ __global__ void __launch_bounds__(kLhBlock) k_lh_gather(const float4* __restrict
   o[0] = s[0]; o[1] = s[1]; o[2] = s[2];
 }
 
-struct LhScratch {
-  uint32_t *small, *first_idx, *flag, *pos, *val, *val_s;
-  double* yaw;
-  uint8_t *key, *key_s;
-  float *curv, *after;
-  LhFn* tot;
-  void *scan_tmp, *sort_tmp;
-  size_t scan_bytes, sort_bytes, total;
-};
-
-// the arrays of one call of n points laid out from `base` (nullptr: the size alone)
-LhScratch lh_scratch(char* base, size_t n) {
-  LhScratch S;
-  const size_t n1 = n ? n : 1, nb = (n1 + kLhBlock - 1) / kLhBlock;
-  S.scan_bytes = 0; S.sort_bytes = 0;
-  {
-    uint32_t* v = nullptr; uint8_t* k = nullptr;
-    (void)rocprim::exclusive_scan(nullptr, S.scan_bytes, v, v, 0u, n1, rocprim::plus<uint32_t>(), nullptr);
-    (void)rocprim::radix_sort_pairs(nullptr, S.sort_bytes, k, k, v, v, n1, 0, 8, nullptr);
-  }
-  size_t at = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + at : nullptr; at += up256(bytes); return p; };
-  S.small = reinterpret_cast<uint32_t*>(take(256));
-  S.first_idx = reinterpret_cast<uint32_t*>(take(4 * PCM_LIDAR_MAX_SCANS));
-  S.flag = reinterpret_cast<uint32_t*>(take(4 * n1));
-  S.pos = reinterpret_cast<uint32_t*>(take(4 * n1));
-  S.scan_tmp = take(S.scan_bytes);
-  S.yaw = reinterpret_cast<double*>(take(8 * n1));
-  S.val = reinterpret_cast<uint32_t*>(take(4 * n1));
-  S.val_s = reinterpret_cast<uint32_t*>(take(4 * n1));
-  S.key = reinterpret_cast<uint8_t*>(take(n1));
-  S.key_s = reinterpret_cast<uint8_t*>(take(n1));
-  S.curv = reinterpret_cast<float*>(take(4 * n1));
-  S.tot = reinterpret_cast<LhFn*>(take(sizeof(LhFn) * nb));
-  S.after = reinterpret_cast<float*>(take(4 * nb));
-  S.sort_tmp = take(S.sort_bytes);
-  S.total = at;
-  return S;
+// rocPRIM's temporaries for one handler call of n points
+void lh_tmp_bytes(size_t n, size_t* scan_bytes, size_t* sort_bytes) {
+  uint32_t* v = nullptr; uint8_t* k = nullptr;
+  *scan_bytes = 0; *sort_bytes = 0;
+  (void)rocprim::exclusive_scan(nullptr, *scan_bytes, v, v, 0u, n ? n : 1, rocprim::plus<uint32_t>(), nullptr);
+  (void)rocprim::radix_sort_pairs(nullptr, *sort_bytes, k, k, v, v, n ? n : 1, 0, 8, nullptr);
 }
 
 #define CHECK_CTX(c)                                                   \
@@ -208,7 +177,13 @@ LhScratch lh_scratch(char* base, size_t n) {
 
 }  // namespace
 
-size_t lidar_filter_scratch_bytes(size_t n) { return lh_scratch(nullptr, n).total; }
+size_t lidar_filter_scratch_bytes(size_t n) {
+  size_t scan_bytes, sort_bytes;
+  lh_tmp_bytes(n, &scan_bytes, &sort_bytes);
+  ArenaCarver a;
+  (void)lidar_filter_layout(a, n, kLhBlock, scan_bytes, sort_bytes);
+  return a.used();
+}
 
 // d_pts: n >= 1 records on the device (the descriptor has passed lh_check_desc); d_out: room for `capacity` records, 16-byte
 // aligned.  given_hint: what lh_given_time says when the caller could read the cloud on the host, -1 to read the last point's
@@ -231,14 +206,16 @@ int lidar_filter_device(hipStream_t stream, const void* d_pts, size_t n, const p
     }
   }
   *given_out = given;
-  const LhScratch S = lh_scratch(static_cast<char*>(scratch), n);
+  size_t scan_bytes, sort_bytes;
+  lh_tmp_bytes(n, &scan_bytes, &sort_bytes);
+  ArenaCarver a(scratch);
+  const LhScratch S = lidar_filter_layout(a, n, kLhBlock, scan_bytes, sort_bytes);
   const unsigned nb = (unsigned)((n + kLhBlock - 1) / kLhBlock);
   PCM_HIPCK_ERR(err, hipMemsetAsync(S.small, 0, 256, stream));
   if (!given) {
     PCM_HIPCK_ERR(err, hipMemsetAsync(S.first_idx, 0xff, 4 * PCM_LIDAR_MAX_SCANS, stream));
     k_lh_yaw<<<nb, kLhBlock, 0, stream>>>(V, S.yaw, S.key, S.val, S.small);
     PCM_HIPCK_ERR(err, hipGetLastError());
-    size_t sort_bytes = S.sort_bytes;
     PCM_HIPCK_ERR(err, rocprim::radix_sort_pairs(S.sort_tmp, sort_bytes, S.key, S.key_s, S.val, S.val_s, n, 0, 8, stream));
     k_lh_heads<<<nb, kLhBlock, 0, stream>>>(S.key_s, S.val_s, (uint32_t)n, S.first_idx);
     k_lh_block_totals<<<nb, kLhBlock, 0, stream>>>((uint32_t)n, S.key_s, S.val_s, S.yaw, S.first_idx, S.tot);
@@ -248,7 +225,6 @@ int lidar_filter_device(hipStream_t stream, const void* d_pts, size_t n, const p
   }
   k_lh_flags<<<nb, kLhBlock, 0, stream>>>(V, given, S.first_idx, S.flag);
   PCM_HIPCK_ERR(err, hipGetLastError());
-  size_t scan_bytes = S.scan_bytes;
   PCM_HIPCK_ERR(err, rocprim::exclusive_scan(S.scan_tmp, scan_bytes, S.flag, S.pos, 0u, n, rocprim::plus<uint32_t>(), stream));
   k_lh_write<<<nb, kLhBlock, 0, stream>>>(V, given, S.curv, S.flag, S.pos, (uint32_t)(capacity < n ? capacity : n), static_cast<float4*>(d_out));
   PCM_HIPCK_ERR(err, hipGetLastError());
@@ -267,27 +243,31 @@ int lidar_filter_device(hipStream_t stream, const void* d_pts, size_t n, const p
   return PCM_OK;
 }
 
-size_t lidar_time_sort_scratch_bytes(size_t m) {
+// rocPRIM's temporary for the time sort of m records
+static size_t lh_time_sort_tmp_bytes(size_t m) {
   size_t t = 0;
   uint32_t* v = nullptr;
   (void)rocprim::radix_sort_pairs(nullptr, t, v, v, v, v, m ? m : 1, 0, 32, nullptr);
-  return 4 * up256(4 * (m ? m : 1)) + up256(t);
+  return t;
+}
+
+size_t lidar_time_sort_scratch_bytes(size_t m) {
+  ArenaCarver a;
+  (void)lidar_time_sort_layout(a, m, lh_time_sort_tmp_bytes(m));
+  return a.used();
 }
 
 // d_in: m 48-byte records; d_out: the same records in (curvature, input index) order (lh_time_key; the radix sort is stable)
 int lidar_time_sort_device(hipStream_t stream, const void* d_in, size_t m, void* d_out, void* scratch, std::string* err) {
   if (m == 0) return PCM_OK;
-  char* cur = static_cast<char*>(scratch);
-  uint32_t* key = reinterpret_cast<uint32_t*>(cur); cur += up256(4 * m);
-  uint32_t* key_s = reinterpret_cast<uint32_t*>(cur); cur += up256(4 * m);
-  uint32_t* val = reinterpret_cast<uint32_t*>(cur); cur += up256(4 * m);
-  uint32_t* val_s = reinterpret_cast<uint32_t*>(cur); cur += up256(4 * m);
-  size_t t = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, t, key, key_s, val, val_s, m, 0, 32, stream);
+  size_t t = lh_time_sort_tmp_bytes(m);
+  ArenaCarver a(scratch);
+  const TimeSortScratch S = lidar_time_sort_layout(a, m, t);
+  uint32_t *key = S.key, *key_s = S.key_s, *val = S.val, *val_s = S.val_s;
   const unsigned nb = (unsigned)((m + kLhBlock - 1) / kLhBlock);
   k_lh_time_keys<<<nb, kLhBlock, 0, stream>>>(static_cast<const float*>(d_in), (uint32_t)m, key, val);
   PCM_HIPCK_ERR(err, hipGetLastError());
-  PCM_HIPCK_ERR(err, rocprim::radix_sort_pairs(cur, t, key, key_s, val, val_s, m, 0, 32, stream));
+  PCM_HIPCK_ERR(err, rocprim::radix_sort_pairs(S.tmp, t, key, key_s, val, val_s, m, 0, 32, stream));
   k_lh_gather<<<nb, kLhBlock, 0, stream>>>(static_cast<const float4*>(d_in), val_s, (uint32_t)m, static_cast<float4*>(d_out));
   PCM_HIPCK_ERR(err, hipGetLastError());
   return PCM_OK;
@@ -297,7 +277,7 @@ int lidar_time_sort_device(hipStream_t stream, const void* d_in, size_t m, void*
 int lidar_check_cloud(pcm_ctx* c, const void* points, size_t n, int memory, const pcm_lidar_desc* desc) {
   if (const char* why = lh_check_desc(desc)) { c->err = why; return PCM_ERR_INVALID_ARGUMENT; }
   if (!points && n) { c->err = "null point buffer"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (check_memory(c, memory, "memory") != PCM_OK) return PCM_ERR_INVALID_ARGUMENT;
   if (n > kLhMaxPoints) { c->err = "cloud too large"; return PCM_ERR_INVALID_ARGUMENT; }
   if (((uintptr_t)points % 4) != 0) { c->err = "the point buffer must be 4-byte aligned"; return PCM_ERR_INVALID_ARGUMENT; }
   return PCM_OK;
@@ -325,35 +305,26 @@ int pcm_lidar_filter(pcm_ctx* c, const void* points, size_t n, int memory, const
   int rc = lidar_check_cloud(c, points, n, memory, desc);
   if (rc != PCM_OK) return rc;
   if (!out && capacity_points) { c->err = "null output buffer"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (out_memory != PCM_MEM_HOST && out_memory != PCM_MEM_DEVICE) { c->err = "out_memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (check_memory(c, out_memory, "out_memory") != PCM_OK) return PCM_ERR_INVALID_ARGUMENT;
   if (out_memory == PCM_MEM_DEVICE && ((uintptr_t)out % 16) != 0) { c->err = "a device output buffer must be 16-byte aligned"; return PCM_ERR_INVALID_ARGUMENT; }
   if (given_offset_time) *given_offset_time = 1;
   if (n == 0) return PCM_OK;
   PCM_HIPCK(c, hipSetDevice(c->device));
-  // arena: [staged input | staged output | scratch]
   const size_t cap = capacity_points < n ? capacity_points : n;
-  const size_t o_out = memory == PCM_MEM_HOST ? up256(n * desc->stride_bytes) : 0, o_scr = o_out + (out_memory == PCM_MEM_HOST ? up256(48 * (cap ? cap : 1)) : 0);
-  const size_t need = o_scr + lidar_filter_scratch_bytes(n);
-  rc = take_pre_arena(c, need, "pcm_lidar_filter");
+  const size_t scratch_bytes = lidar_filter_scratch_bytes(n);
+  FilterArena F;
+  rc = carve_pre_arena(c, "pcm_lidar_filter", [&](ArenaStage& a) { F = filter_layout(a, memory, points, n * desc->stride_bytes, out_memory, out, 48 * (cap ? cap : 1), scratch_bytes); });
   if (rc != PCM_OK) return rc;
-  char* A = c->pre_arena;
-  const void* d_in = points;
-  int hint = -1;
-  if (memory == PCM_MEM_HOST) {
-    PCM_HIPCK(c, hipMemcpyAsync(A, points, n * desc->stride_bytes, hipMemcpyHostToDevice, c->stream));
-    d_in = A;
-    hint = lidar_given_on_host(points, n, *desc);
-  }
-  void* d_out = out_memory == PCM_MEM_HOST ? static_cast<void*>(A + o_out) : out;
+  const int hint = memory == PCM_MEM_HOST ? lidar_given_on_host(points, n, *desc) : -1;
   size_t m = 0;
   int given = 1;
-  rc = lidar_filter_device(c->stream, d_in, n, *desc, hint, d_out, cap, &m, &given, A + o_scr, &c->err);
+  rc = lidar_filter_device(c->stream, F.src, n, *desc, hint, F.dst, cap, &m, &given, F.scratch, &c->err);
   if (given_offset_time) *given_offset_time = given;
   if (rc != PCM_OK) return rc;
   *n_out = m;
   if (m > capacity_points) { c->err = "output buffer too small"; return PCM_ERR_INVALID_ARGUMENT; }
   if (out_memory == PCM_MEM_HOST && m) {
-    PCM_HIPCK(c, hipMemcpyAsync(out, d_out, 48 * m, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = stage_back(c, out_memory, out, F.dst, 48 * m)) != PCM_OK) return rc;
     PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   }
   return PCM_OK;

@@ -4,6 +4,7 @@
 // frame entries through frame_tail, and whatever replaces the source through source_replaced (pcm_host.h): a new LIO call uses
 // them instead of a copy of its neighbour.  The frame outputs are in lio_outputs.hip, the propagation in lio_predict.hip.
 #include "pcm_core.h"
+#include "pre_layouts.h"
 
 #include <algorithm>
 #include <cmath>
@@ -121,12 +122,12 @@ void match_record(pcm_ctx* c, const Match& m, bool matched, uint64_t rematches, 
 // ---- the part of a frame both entries share ----------------------------------------------------------------------------------------
 // `recs`: the n_flt 48-byte records of the frame after the entry's own front steps, `spare`: a second record array of that size.
 int frame_tail(pcm_ctx* c, const char* who, char* recs, size_t n_flt, char* spare, float leaf_size, const pcm_imu_pose* poses, int npose, const pcm_lio_state* end_state,
-               char* d_poses, char* scratch, size_t* n_scan) {
+               pcm_imu_pose* d_poses, void* scratch, size_t* n_scan) {
   hipStream_t st = c->stream;
   // ImuProcess::UndistortPcl backward loop  (imu_processing.hpp:245-285): in place on the records (time stamp = curvature)
   if (npose >= 2) {
     PCM_HIPCK(c, hipMemcpyAsync(d_poses, poses, sizeof(pcm_imu_pose) * (size_t)npose, hipMemcpyHostToDevice, st));
-    int rc = undistort_device(st, recs, n_flt, 48, 36, reinterpret_cast<const pcm_imu_pose*>(d_poses), npose, state_of(end_state), &c->err);   // PointXYZINormal::curvature: byte 36
+    int rc = undistort_device(st, recs, n_flt, 48, 36, d_poses, npose, state_of(end_state), &c->err);   // PointXYZINormal::curvature: byte 36
     if (rc != PCM_OK) return rc;
   }
   // voxel_scan_.filter()  (laser_mapping.cc:323-328); leaf 0 = no down-sampling.  The centroids go to the spare array.
@@ -163,19 +164,12 @@ int pcm_undistort(pcm_ctx* c, void* points, size_t n, size_t stride, size_t time
   if (stride < 16 || (stride % 4) != 0 || time_off + 4 > stride || (time_off % 4) != 0) { c->err = "bad record layout"; return PCM_ERR_INVALID_ARGUMENT; }
   if (n == 0 || npose < 2) return PCM_OK;
   PCM_HIPCK(c, hipSetDevice(c->device));
-  const size_t need = up256(sizeof(pcm_imu_pose) * (size_t)npose) + (memory == PCM_MEM_HOST ? up256(n * stride) : 0);
-  int rc = take_pre_arena(c, need, "pcm_undistort");
+  UndistortArena U;   // arena: [IMU poses | staged points]
+  int rc = carve_pre_arena(c, "pcm_undistort", [&](ArenaStage& a) { U = undistort_layout(a, poses, npose, memory, points, n * stride); });
   if (rc != PCM_OK) return rc;
-  pcm_imu_pose* d_poses = reinterpret_cast<pcm_imu_pose*>(c->pre_arena.p);
-  PCM_HIPCK(c, hipMemcpyAsync(d_poses, poses, sizeof(pcm_imu_pose) * (size_t)npose, hipMemcpyHostToDevice, c->stream));
-  void* d_pts = points;
-  if (memory == PCM_MEM_HOST) {
-    d_pts = c->pre_arena + up256(sizeof(pcm_imu_pose) * (size_t)npose);
-    PCM_HIPCK(c, hipMemcpyAsync(d_pts, points, n * stride, hipMemcpyHostToDevice, c->stream));
-  }
-  rc = undistort_device(c->stream, d_pts, n, stride, time_off, d_poses, npose, state_of(st), &c->err);
+  rc = undistort_device(c->stream, U.pts, n, stride, time_off, U.poses, npose, state_of(st), &c->err);
   if (rc != PCM_OK) return rc;
-  if (memory == PCM_MEM_HOST) PCM_HIPCK(c, hipMemcpyAsync(points, d_pts, n * stride, hipMemcpyDeviceToHost, c->stream));
+  if ((rc = stage_back(c, memory, points, U.pts, n * stride)) != PCM_OK) return rc;
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   return PCM_OK;
 }
@@ -363,27 +357,21 @@ int pcm_lio_frame_begin(pcm_ctx* c, const void* custom_points, size_t n, int mem
   if (n == 0) { c->err = "empty frame"; return PCM_ERR_NO_INPUT; }
   PCM_HIPCK(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
-  // frame arena: [raw message | filtered records | down-sampled records | IMU poses | scratch of the operators]; grow-only, so the
-  // steady state makes no allocation.  The raw message is the only host -> device copy of the frame.
-  const size_t o_raw = 0, o_flt = o_raw + up256(n * 20), o_ds = o_flt + up256(n * 48), o_pose = o_ds + up256(n * 48);
-  const size_t o_scr = o_pose + up256(sizeof(pcm_imu_pose) * (size_t)std::max(npose, 1));
-  int rc = take_pre_arena(c, o_scr + std::max(livox_filter_scratch_bytes(n), voxel_downsample_scratch_bytes(n)), "pcm_lio_frame_begin");
+  // grow-only, so the steady state makes no allocation
+  const size_t livox_bytes = livox_filter_scratch_bytes(n), vg_bytes = voxel_downsample_scratch_bytes(n);
+  FrameArena F;
+  int rc = carve_pre_arena(c, "pcm_lio_frame_begin", [&](ArenaStage& a) { F = frame_layout(a, memory, custom_points, n * 20, true, n, npose, {livox_bytes, vg_bytes}); });
   if (rc != PCM_OK) return rc;
-  char* A = c->pre_arena;
-  const void* d_raw = custom_points;
-  if (memory == PCM_MEM_HOST) {
-    PCM_HIPCK(c, hipMemcpyAsync(A + o_raw, custom_points, n * 20, hipMemcpyHostToDevice, st));
-    d_raw = A + o_raw;
-  }
+  char *flt = F.rec[0], *ds = F.rec[1];
   // 1. PointCloudPreprocess::AviaHandler  (pointcloud_preprocess.cc:44-88)
   size_t n_flt = 0;
-  rc = livox_filter_device(st, d_raw, n, prm->num_scans, prm->point_filter_num, prm->blind, A + o_flt, &n_flt, A + o_scr, &c->err);
+  rc = livox_filter_device(st, F.raw, n, prm->num_scans, prm->point_filter_num, prm->blind, flt, &n_flt, F.scratch, &c->err);
   if (rc != PCM_OK) return rc;
   if (n_flt == 0) { c->err = "no point of the frame passed the driver-message filter"; return PCM_ERR_NO_INPUT; }
   // 2.-4. motion compensation, down-sampling, the scan becomes the source.  The reference sorts the scan by time first
   //    (imu_processing.hpp:177-178); a Livox message is time-ordered, and the compensation of a point depends on its own stamp
   //    only, so the message order is kept.
-  return frame_tail(c, "pcm_lio_frame_begin", A + o_flt, n_flt, A + o_ds, prm->leaf_size, poses, npose, end_state, A + o_pose, A + o_scr, n_scan);
+  return frame_tail(c, "pcm_lio_frame_begin", flt, n_flt, ds, prm->leaf_size, poses, npose, end_state, F.poses, F.scratch, n_scan);
 }
 
 // The same frame for a sensor_msgs::PointCloud2 cloud: the handler of its LiDAR type (pointcloud_preprocess.cc:89-305) in front, and
@@ -399,31 +387,24 @@ int pcm_lio_frame_begin_cloud(pcm_ctx* c, const void* points, size_t n, int memo
   if (n == 0) { c->err = "empty frame"; return PCM_ERR_NO_INPUT; }
   PCM_HIPCK(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
-  // frame arena: [raw cloud | filtered records, later the down-sampled ones | time-sorted records | IMU poses | scratch of the operators]
-  const size_t o_raw = 0, o_flt = o_raw + (memory == PCM_MEM_HOST ? up256(n * desc->stride_bytes) : 0), o_srt = o_flt + up256(n * 48), o_pose = o_srt + up256(n * 48);
-  const size_t o_scr = o_pose + up256(sizeof(pcm_imu_pose) * (size_t)std::max(npose, 1));
-  rc = take_pre_arena(c, o_scr + std::max({lidar_filter_scratch_bytes(n), lidar_time_sort_scratch_bytes(n), voxel_downsample_scratch_bytes(n)}), "pcm_lio_frame_begin_cloud");
+  const size_t filter_bytes = lidar_filter_scratch_bytes(n), sort_bytes = lidar_time_sort_scratch_bytes(n), vg_bytes = voxel_downsample_scratch_bytes(n);
+  FrameArena F;
+  rc = carve_pre_arena(c, "pcm_lio_frame_begin_cloud", [&](ArenaStage& a) { F = frame_layout(a, memory, points, n * desc->stride_bytes, false, n, npose, {filter_bytes, sort_bytes, vg_bytes}); });
   if (rc != PCM_OK) return rc;
-  char* A = c->pre_arena;
-  const void* d_raw = points;
-  int hint = -1;
-  if (memory == PCM_MEM_HOST) {
-    PCM_HIPCK(c, hipMemcpyAsync(A + o_raw, points, n * desc->stride_bytes, hipMemcpyHostToDevice, st));
-    d_raw = A + o_raw;
-    hint = lidar_given_on_host(points, n, *desc);
-  }
+  char *flt = F.rec[0], *srt = F.rec[1];   // the filtered records, later the down-sampled ones; the time-sorted records
+  const int hint = memory == PCM_MEM_HOST ? lidar_given_on_host(points, n, *desc) : -1;
   // 1. the handler: kept points in input order
   size_t n_flt = 0;
   int given = 1;
-  rc = lidar_filter_device(st, d_raw, n, *desc, hint, A + o_flt, n, &n_flt, &given, A + o_scr, &c->err);
+  rc = lidar_filter_device(st, F.raw, n, *desc, hint, flt, n, &n_flt, &given, F.scratch, &c->err);
   if (rc != PCM_OK) return rc;
   if (n_flt == 0) { c->err = "no point of the frame passed the handler"; return PCM_ERR_NO_INPUT; }
   // 2. sort by time; the radix sort is stable, so equal stamps keep their input order
-  rc = lidar_time_sort_device(st, A + o_flt, n_flt, A + o_srt, A + o_scr, &c->err);
+  rc = lidar_time_sort_device(st, flt, n_flt, srt, F.scratch, &c->err);
   if (rc != PCM_OK) return rc;
   // 3.-5. motion compensation in place on the sorted records, down-sampling (the filtered records are free again: the centroids go
   //    there), the scan becomes the source
-  return frame_tail(c, "pcm_lio_frame_begin_cloud", A + o_srt, n_flt, A + o_flt, leaf_size, poses, npose, end_state, A + o_pose, A + o_scr, n_scan);
+  return frame_tail(c, "pcm_lio_frame_begin_cloud", srt, n_flt, flt, leaf_size, poses, npose, end_state, F.poses, F.scratch, n_scan);
 }
 
 int pcm_lio_frame_end(pcm_ctx* c, const pcm_lio_state* s, float filter_size_map, int ekf_inited, size_t* num_added) {

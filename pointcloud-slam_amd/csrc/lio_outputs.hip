@@ -135,7 +135,7 @@ bool direct_out(void* out, int memory) { return memory == PCM_MEM_DEVICE && (rei
 int check_out(pcm_ctx* c, const char* who, int memory, size_t* n) {
   if (!n) { c->err = std::string(who) + ": null count"; return PCM_ERR_INVALID_ARGUMENT; }
   *n = 0;
-  if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (check_memory(c, memory, "memory") != PCM_OK) return PCM_ERR_INVALID_ARGUMENT;
   return PCM_OK;
 }
 int too_small(pcm_ctx* c, const char* who, size_t cap, size_t need) {
@@ -280,7 +280,7 @@ int pcm_lio_map_info_get(pcm_ctx* c, pcm_lio_map_info* info) {
 
 int pcm_lio_map_get(pcm_ctx* c, size_t first, size_t count, void* out, int memory) {
   CHECK_CTX(c);
-  if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (check_memory(c, memory, "memory") != PCM_OK) return PCM_ERR_INVALID_ARGUMENT;
   const MapLog* M = log_of(c);
   if (!lio_out::slice_ok(M ? M->n : 0, first, count)) { c->err = "pcm_lio_map_get: the slice does not lie inside the log"; return PCM_ERR_INVALID_ARGUMENT; }
   if (count == 0) return PCM_OK;

@@ -418,7 +418,7 @@ int pcm_loam_dynmap_global(pcm_ctx* c, void* out, size_t capacity, size_t* n, in
   int rc = check_ctx_dm(c, &S);
   if (rc != PCM_OK) return rc;
   if (n) *n = 0;
-  if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (check_memory(c, memory, "memory") != PCM_OK) return PCM_ERR_INVALID_ARGUMENT;
   const float4 *tc = nullptr, *ts = nullptr;
   uint32_t tnc = 0, tns = 0;
   if (!S->last_valid || !loam_target_view(c, TargetOwner::dynmap, &tc, &tnc, &ts, &tns)) { c->err = "pcm_loam_dynmap_global: the context's target is not the result of pcm_loam_dynmap_crop"; return PCM_ERR_NO_INPUT; }

@@ -15,6 +15,7 @@
 #include "host_util.h"
 #include "intro_sort.h"
 #include "loam_device.h"
+#include "pre_layouts.h"
 #include "voxel_grid.h"
 
 #include <algorithm>
@@ -600,33 +601,6 @@ int ensure_state(pcm_ctx* c, FeatState* S, const pcm_loam_feature_params& p) {
 
 int next_pow2(int x) { int p = 1; while (p < x) p <<= 1; return p; }
 
-struct BatchLayout {
-  size_t o_in, o_owner, o_rowcnt, o_roff, o_member, o_cpick, o_ccnt, o_cells1, o_cells2;
-  size_t o_vg, n_vg, nseg_vg;   // the VoxelGrid's arrays (vg::work_layout): shared by the two stages
-  size_t total;
-};
-
-BatchLayout layout(int B, size_t in_bytes, size_t cap, int n_scan, int ppr, size_t N1, size_t N2, size_t nseg_max) {
-  BatchLayout L{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t r = o; o += up256(bytes); return r; };
-  L.o_in = take(in_bytes);
-  L.o_owner = take(4 * cap * B);
-  L.o_rowcnt = take(4 * (size_t)n_scan * B);
-  L.o_roff = take(4 * (size_t)(n_scan + 1) * B);
-  L.o_member = take(4 * cap * B);
-  L.o_cpick = take(4 * (size_t)n_scan * ppr * B);
-  L.o_ccnt = take(4 * (size_t)n_scan * B);
-  L.o_cells1 = take(16 * N1);
-  L.o_cells2 = take(16 * N2);
-  L.n_vg = std::max(N1, N2); L.nseg_vg = nseg_max;
-  size_t vg_bytes = 0;
-  (void)vg::work_layout(nullptr, L.n_vg, sizeof(uint64_t), L.nseg_vg, &vg_bytes);
-  L.o_vg = take(vg_bytes);
-  L.total = o;
-  return L;
-}
-
 // one stage: N element slots in B rows of up to size_per_frame, nseg segments; the cells of all frames go to cells_out
 template <int kStage>
 int run_vg(pcm_ctx* c0, hipStream_t st, const LfFrame* d_fr, const LfParams& P, int B, uint32_t size_per_frame, uint32_t N, uint32_t nseg, vg::Work W,
@@ -700,7 +674,7 @@ int run_frames(pcm_ctx* const* ctxs, int B, const void* const* points, const siz
     c0->err = "stride must be a multiple of 4 >= 12 holding the 1-byte intensity and the 2-byte aligned ring";
     return PCM_ERR_INVALID_ARGUMENT;
   }
-  if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c0->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (check_memory(c0, memory, "memory") != PCM_OK) return PCM_ERR_INVALID_ARGUMENT;
   for (int i = 0; i < B; i++) {
     if ((rc = check_ctx_fe(ctxs[i])) != PCM_OK) { if (ctxs[i] && ctxs[i] != c0) c0->err = ctxs[i]->err; return rc; }
     if (ctxs[i]->device != c0->device) { c0->err = "all contexts of a batch must live on one device"; return PCM_ERR_INVALID_ARGUMENT; }
@@ -718,7 +692,7 @@ int run_frames(pcm_ctx* const* ctxs, int B, const void* const* points, const siz
   if (lds > 65536) { c0->err = "k_lf_select's LDS exceeds 64 KiB (library bug: the caps keep it below 48.1 KiB)"; return PCM_ERR_INTERNAL; }
   // per-context state and outputs
   std::vector<size_t> cap1((size_t)B), base1((size_t)B), base2((size_t)B);
-  size_t N1 = 0, N2 = 0, in_bytes = 0;
+  size_t N1 = 0, N2 = 0;
   uint32_t max1 = 1;
   for (int i = 0; i < B; i++) {
     pcm_ctx* c = ctxs[i];
@@ -738,7 +712,6 @@ int run_frames(pcm_ctx* const* ctxs, int B, const void* const* points, const siz
     S->end = S->start + q.n_scan;
     S->A = q.area_num;
     S->out_gen++;
-    if (memory == PCM_MEM_HOST) in_bytes += up256(n_points[i] * stride);
   }
   std::vector<float4*> src((size_t)B, nullptr);
   if (to_source)
@@ -747,38 +720,40 @@ int run_frames(pcm_ctx* const* ctxs, int B, const void* const* points, const siz
   // batch workspace of the leading context
   FeatState* S0 = fe_of(c0);
   const size_t nseg_max = std::max<size_t>((size_t)B * q.n_scan, 2 * (size_t)B);
-  const BatchLayout Lw = layout(B, in_bytes, cap, q.n_scan, P.ppr, N1, N2, nseg_max);
+  const size_t n_vg = std::max(N1, N2);   // the VoxelGrid's arrays are shared by the two stages
+  size_t vg_bytes = 0;
+  (void)vg::work_layout(nullptr, n_vg, sizeof(uint64_t), nseg_max, &vg_bytes);
+  std::vector<const void*> pts((size_t)B, nullptr);
+  LfBatch Lw;
+  auto layout = [&](ArenaStage& a) { Lw = loam_batch_layout(a, B, memory, points, n_points, stride, pts.data(), cap, q.n_scan, P.ppr, N1, N2, vg_bytes); };
+  ArenaStage ws_size = arena_stage(c0, nullptr);
+  layout(ws_size);
   hipStream_t st = c0->stream;
   PCM_HIPCK(c0, hipStreamSynchronize(st));   // the pinned staging of an earlier batch is free again
-  if ((rc = S0->ws.reserve(c0, Lw.total, Lw.total)) != PCM_OK) return rc;
+  if ((rc = S0->ws.reserve(c0, ws_size.used(), ws_size.used())) != PCM_OK) return rc;
   if ((rc = S0->d_fr.reserve(c0, (size_t)B, (size_t)B)) != PCM_OK || (rc = S0->h_fr.reserve(c0, (size_t)B, (size_t)B)) != PCM_OK ||
       (rc = S0->d_info.reserve(c0, (size_t)B, (size_t)B)) != PCM_OK || (rc = S0->h_info.reserve(c0, (size_t)B, (size_t)B)) != PCM_OK)
     return rc;
-  char* ws = S0->ws;
-  size_t in_off = Lw.o_in;
+  ArenaStage ws = arena_stage(c0, S0->ws.p);   // the clouds in host memory are staged here
+  layout(ws);
+  if (ws.rc != PCM_OK) return ws.rc;
   uint32_t maxn = 1;
   for (int i = 0; i < B; i++) {
     FeatState* S = fe_of(ctxs[i]);
     LfFrame& F = S0->h_fr[i];
     std::memset(&F, 0, sizeof(F));
-    if (memory == PCM_MEM_HOST) {
-      F.pts = ws + in_off;
-      if (n_points[i]) PCM_HIPCK(c0, hipMemcpyAsync(ws + in_off, points[i], n_points[i] * stride, hipMemcpyHostToDevice, st));
-      in_off += up256(n_points[i] * stride);
-    } else {
-      F.pts = static_cast<const char*>(points[i]);
-    }
+    F.pts = static_cast<const char*>(pts[(size_t)i]);
     F.n = (uint32_t)n_points[i]; F.stride = (uint32_t)stride; F.ioff = (uint32_t)ioff; F.roff = (uint32_t)roff;
     F.cap1 = (uint32_t)cap1[(size_t)i]; F.base1 = (uint32_t)base1[(size_t)i]; F.base2 = (uint32_t)base2[(size_t)i];
     F.col_ind = S->col_ind; F.range = S->range; F.cloud = S->cloud; F.curv = S->curv; F.picked = S->picked; F.label = S->label; F.smooth = S->smooth;
     F.start = S->start; F.end = S->end; F.picked_occ = S->picked_occ; F.corner_scan = S->corner_scan; F.surf_scan = S->surf_scan; F.out = S->out;
     F.src = src[(size_t)i];
-    F.owner = reinterpret_cast<uint32_t*>(ws + Lw.o_owner) + (size_t)i * cap;
-    F.rowcnt = reinterpret_cast<uint32_t*>(ws + Lw.o_rowcnt) + (size_t)i * q.n_scan;
-    F.roff_arr = reinterpret_cast<uint32_t*>(ws + Lw.o_roff) + (size_t)i * (q.n_scan + 1);
-    F.member = reinterpret_cast<int32_t*>(ws + Lw.o_member) + (size_t)i * cap;
-    F.cpick = reinterpret_cast<int32_t*>(ws + Lw.o_cpick) + (size_t)i * ncs;
-    F.ccnt = reinterpret_cast<int32_t*>(ws + Lw.o_ccnt) + (size_t)i * q.n_scan;
+    F.owner = Lw.owner + (size_t)i * cap;
+    F.rowcnt = Lw.rowcnt + (size_t)i * q.n_scan;
+    F.roff_arr = Lw.roff + (size_t)i * (q.n_scan + 1);
+    F.member = Lw.member + (size_t)i * cap;
+    F.cpick = Lw.cpick + (size_t)i * ncs;
+    F.ccnt = Lw.ccnt + (size_t)i * q.n_scan;
     F.info = S0->d_info + i;
     maxn = std::max<uint32_t>(maxn, F.n);
   }
@@ -798,10 +773,9 @@ int run_frames(pcm_ctx* const* ctxs, int B, const void* const* points, const siz
   k_lf_select<false><<<dim3(q.n_scan, B), 64, lds, st>>>(d_fr, P);
   k_lf_corner_compact<<<B, 256, 0, st>>>(d_fr, P);
   PCM_HIPCK(c0, hipGetLastError());
-  float4* cells1 = reinterpret_cast<float4*>(ws + Lw.o_cells1);
-  float4* cells2 = reinterpret_cast<float4*>(ws + Lw.o_cells2);
-  size_t vg_bytes = 0;
-  const vg::Work W = vg::work_layout(ws + Lw.o_vg, Lw.n_vg, sizeof(uint64_t), Lw.nseg_vg, &vg_bytes);
+  float4* cells1 = static_cast<float4*>(Lw.cells1);
+  float4* cells2 = static_cast<float4*>(Lw.cells2);
+  const vg::Work W = vg::work_layout(Lw.vg, n_vg, sizeof(uint64_t), nseg_max, &vg_bytes);
   if ((rc = run_vg<1>(c0, st, d_fr, P, B, max1, (uint32_t)N1, (uint32_t)(B * q.n_scan), W, cells1, cells1)) != PCM_OK) return rc;
   const uint32_t size2 = (uint32_t)(ncs + max1);
   if ((rc = run_vg<2>(c0, st, d_fr, P, B, size2, (uint32_t)N2, (uint32_t)(2 * B), W, cells1, cells2)) != PCM_OK) return rc;

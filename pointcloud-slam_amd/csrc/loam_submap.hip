@@ -420,7 +420,7 @@ int near_cloud(pcm_ctx* c, const char* who, int key, int search_num, int wrt_key
   int rc = check_ctx_sm(c, &S);
   if (rc != PCM_OK) return rc;
   if (n_out) *n_out = 0;
-  if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (check_memory(c, memory, "memory") != PCM_OK) return PCM_ERR_INVALID_ARGUMENT;
   const int K = (int)S->kf.size();
   if ((rc = check_near_args(c, K, key, search_num, wrt_key, leaf, who)) != PCM_OK) return rc;
   if (K == 0) return PCM_OK;   // nothing to assemble
@@ -547,7 +547,7 @@ int pcm_loam_keyframe_add(pcm_ctx* c, const float pose6[6], double time, const v
   } else {
     if ((!corner && n_corner) || (!surf && n_surf)) { c->err = "null point buffer"; return PCM_ERR_INVALID_ARGUMENT; }
     if (stride < 3 * sizeof(float) || (stride % sizeof(float)) != 0) { c->err = "stride must be a multiple of 4 and >= 12 bytes"; return PCM_ERR_INVALID_ARGUMENT; }
-    if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+    if (check_memory(c, memory, "memory") != PCM_OK) return PCM_ERR_INVALID_ARGUMENT;
   }
   if (n_corner > 0x3fffffffull || n_surf > 0x3fffffffull || S->arena[0].n + n_corner > 0xffffffffull || S->arena[1].n + n_surf > 0xffffffffull) {
     c->err = "key-frame store too large"; return PCM_ERR_INVALID_ARGUMENT;
@@ -748,7 +748,7 @@ int pcm_loam_global_map(pcm_ctx* c, const pcm_loam_global_params* params, void* 
   pcm_loam_global_params p;
   if (params) p = *params; else pcm_loam_default_global_params(&p);
   if ((rc = check_gparams(c, p)) != PCM_OK) return rc;
-  if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (check_memory(c, memory, "memory") != PCM_OK) return PCM_ERR_INVALID_ARGUMENT;
   pcm_loam_global_result r{};
   if (result) *result = r;
   if (S->kf.empty()) return PCM_OK;   // publishGlobalMap :552
@@ -774,7 +774,7 @@ int pcm_loam_map_export(pcm_ctx* c, int which, int first, int n, void* out, size
   int rc = check_ctx_sm(c, &S);
   if (rc != PCM_OK) return rc;
   if (which < 0 || which > 2) { c->err = "pcm_loam_map_export: which must be 0 (corner), 1 (surf) or 2 (corner then surf)"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (check_memory(c, memory, "memory") != PCM_OK) return PCM_ERR_INVALID_ARGUMENT;
   if (first < 0 || n < 0 || (long long)first + n > (long long)S->kf.size()) { c->err = "pcm_loam_map_export: first + n exceeds the number of key frames"; return PCM_ERR_INVALID_ARGUMENT; }
   if (n_out) *n_out = 0;
   uint64_t total = 0;

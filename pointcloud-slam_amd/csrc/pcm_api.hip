@@ -4,6 +4,7 @@
 // entry points are in lio_api.hip and use the helpers pcm_core.h declares from here.
 #include "pcm_core.h"
 #include "dev_scratch.h"
+#include "pre_layouts.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -15,8 +16,6 @@ using namespace pcm;
 
 namespace {
 
-// the scratch the pre-processing operators share (pcm_host.h: take_pre_arena)
-int pre_scratch(pcm_ctx* c, size_t bytes, const char* who) { return take_pre_arena(c, bytes, who); }
 
 // the same for the records + partial sums of a GICP-BFGS correspondence set of m pairs
 int bfgs_scratch(pcm_ctx* c, size_t m) {
@@ -465,21 +464,17 @@ int pcm_gicp_bfgs_set_correspondences(pcm_ctx* c, const void* src, size_t n_src,
   int rc = bfgs_scratch(c, m);
   if (rc != PCM_OK) return rc;
   if (m == 0) return PCM_OK;
-  const void *d_src = src, *d_tgt = tgt;
-  const int32_t *d_is = idx_src, *d_it = idx_tgt;
-  const float* d_maha = maha;
   DevScratch sc(c->stream);
-  if (memory == PCM_MEM_HOST) {   // staged once per correspondence set; the evaluations then read the packed records only
-    const size_t b_src = up256(n_src * stride), b_tgt = up256(n_tgt * stride), b_idx = up256(m * 4), b_maha = up256(n_src * 64);
-    char* q = nullptr;
-    if ((rc = sc.take(&q, b_src + b_tgt + 2 * b_idx + b_maha, &c->err, "correspondence staging")) != PCM_OK) return rc;
-    PCM_HIPCK(c, hipMemcpyAsync(q, src, n_src * stride, hipMemcpyHostToDevice, c->stream)); d_src = q; q += b_src;
-    PCM_HIPCK(c, hipMemcpyAsync(q, tgt, n_tgt * stride, hipMemcpyHostToDevice, c->stream)); d_tgt = q; q += b_tgt;
-    PCM_HIPCK(c, hipMemcpyAsync(q, idx_src, m * 4, hipMemcpyHostToDevice, c->stream)); d_is = reinterpret_cast<const int32_t*>(q); q += b_idx;
-    PCM_HIPCK(c, hipMemcpyAsync(q, idx_tgt, m * 4, hipMemcpyHostToDevice, c->stream)); d_it = reinterpret_cast<const int32_t*>(q); q += b_idx;
-    PCM_HIPCK(c, hipMemcpyAsync(q, maha, n_src * 64, hipMemcpyHostToDevice, c->stream)); d_maha = reinterpret_cast<const float*>(q);
-  }
-  rc = gicp_bfgs_pack_device(c->stream, d_src, d_tgt, stride, d_is, d_it, d_maha, m, c->bfgs, &c->err);
+  BfgsStaging G;   // staged once per correspondence set; the evaluations then read the packed records only
+  auto layout = [&](ArenaStage& a) { G = bfgs_staging_layout(a, memory, src, n_src, tgt, n_tgt, stride, idx_src, idx_tgt, m, maha); };
+  ArenaStage size = arena_stage(c, nullptr);
+  layout(size);
+  char* q = nullptr;
+  if (size.used() && (rc = sc.take(&q, size.used(), &c->err, "correspondence staging")) != PCM_OK) return rc;
+  ArenaStage S = arena_stage(c, q);
+  layout(S);
+  if (S.rc != PCM_OK) return S.rc;
+  rc = gicp_bfgs_pack_device(c->stream, G.src, G.tgt, stride, G.idx_src, G.idx_tgt, G.maha, m, c->bfgs, &c->err);
   sc.release();   // behind the pack, on the stream
   if (rc != PCM_OK) return rc;
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));   // the caller's buffers are free again
@@ -564,23 +559,14 @@ int pcm_voxel_downsample(pcm_ctx* c, const void* points, size_t n, size_t stride
   *n_out = 0;
   if (n == 0) return PCM_OK;
   PCM_HIPCK(c, hipSetDevice(c->device));
-  const size_t io = memory == PCM_MEM_HOST ? 2 * up256(n * stride) : 0;
-  int rc = pre_scratch(c, voxel_downsample_scratch_bytes(n) + io, "pcm_voxel_downsample");
+  const size_t scratch_bytes = voxel_downsample_scratch_bytes(n);
+  FilterArena F;
+  int rc = carve_pre_arena(c, "pcm_voxel_downsample", [&](ArenaStage& a) { F = filter_layout(a, memory, points, n * stride, memory, out, n * stride, scratch_bytes); });
   if (rc != PCM_OK) return rc;
-  const void* src = points;
-  void* dst = out;
-  char* scratch = c->pre_arena;
-  if (memory == PCM_MEM_HOST) {
-    char* d_in = c->pre_arena;
-    char* d_out = c->pre_arena + up256(n * stride);
-    scratch = c->pre_arena + io;
-    PCM_HIPCK(c, hipMemcpyAsync(d_in, points, n * stride, hipMemcpyHostToDevice, c->stream));
-    src = d_in; dst = d_out;
-  }
-  rc = voxel_downsample_device(c->stream, src, n, stride, leaf, static_cast<float*>(dst), n_out, scratch, &c->err);
+  rc = voxel_downsample_device(c->stream, F.src, n, stride, leaf, static_cast<float*>(F.dst), n_out, F.scratch, &c->err);
   if (rc != PCM_OK) return rc;
   if (memory == PCM_MEM_HOST && *n_out) {
-    PCM_HIPCK(c, hipMemcpyAsync(out, dst, *n_out * stride, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = stage_back(c, memory, out, F.dst, *n_out * stride)) != PCM_OK) return rc;
     PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   }
   return PCM_OK;
@@ -614,22 +600,13 @@ int pcm_livox_filter(pcm_ctx* c, const void* custom_points, size_t n, int memory
   *n_out = 0;
   if (n == 0) return PCM_OK;
   PCM_HIPCK(c, hipSetDevice(c->device));
-  const size_t io = memory == PCM_MEM_HOST ? up256(n * 20) + up256(n * 48) : 0;
-  int rc = pre_scratch(c, livox_filter_scratch_bytes(n) + io, "pcm_livox_filter");
+  const size_t scratch_bytes = livox_filter_scratch_bytes(n);
+  FilterArena F;
+  int rc = carve_pre_arena(c, "pcm_livox_filter", [&](ArenaStage& a) { F = filter_layout(a, memory, custom_points, n * 20, memory, out, n * 48, scratch_bytes); });
   if (rc != PCM_OK) return rc;
-  const void* src = custom_points;
-  void* dst = out;
-  char* scratch = c->pre_arena;
-  if (memory == PCM_MEM_HOST) {
-    char* d_in = c->pre_arena;
-    char* d_out = c->pre_arena + up256(n * 20);
-    scratch = c->pre_arena + io;
-    PCM_HIPCK(c, hipMemcpyAsync(d_in, custom_points, n * 20, hipMemcpyHostToDevice, c->stream));
-    src = d_in; dst = d_out;
-  }
-  rc = livox_filter_device(c->stream, src, n, num_scans, point_filter_num, blind, dst, n_out, scratch, &c->err);
+  rc = livox_filter_device(c->stream, F.src, n, num_scans, point_filter_num, blind, F.dst, n_out, F.scratch, &c->err);
   if (rc != PCM_OK) return rc;
-  if (memory == PCM_MEM_HOST && *n_out) PCM_HIPCK(c, hipMemcpyAsync(out, dst, *n_out * 48, hipMemcpyDeviceToHost, c->stream));
+  if ((rc = stage_back(c, memory, out, F.dst, *n_out * 48)) != PCM_OK) return rc;
   PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   return PCM_OK;
 }

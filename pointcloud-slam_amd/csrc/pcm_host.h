@@ -358,6 +358,33 @@ inline void source_replaced(pcm_ctx* c, const char* who) {
   c->srcmap.valid = false;
   c->src_cov_valid = false;
 }
+// the copies of a Stage (arena_carver.h) on a stream
+struct StreamCopy {
+  hipStream_t st;
+  std::string* err;
+  int h2d(void* dst, const void* src, size_t bytes) const { PCM_HIPCK_ERR(err, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st)); return PCM_OK; }
+  int d2h(void* dst, const void* src, size_t bytes) const { PCM_HIPCK_ERR(err, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st)); return PCM_OK; }
+};
+using ArenaStage = Stage<StreamCopy>;
+inline ArenaStage arena_stage(pcm_ctx* c, void* base) { return ArenaStage(base, StreamCopy{c->stream, &c->err}); }
+// The two passes of an entry point over the pre-processing arena: `layout(ArenaStage&)` run over a null base is the size
+// take_pre_arena makes room for; run again over the arena it carves the blocks and queues the staged input.
+template <class Layout> int carve_pre_arena(pcm_ctx* c, const char* who, Layout&& layout) {
+  ArenaStage size = arena_stage(c, nullptr);
+  layout(size);
+  const int rc = take_pre_arena(c, size.used(), who);
+  if (rc != PCM_OK) return rc;
+  ArenaStage S = arena_stage(c, c->pre_arena.p);
+  layout(S);
+  return S.rc;
+}
+inline int stage_back(pcm_ctx* c, int memory, void* user, const void* dev, size_t bytes) { return stage_back(StreamCopy{c->stream, &c->err}, memory, user, dev, bytes); }
+// `name`: "memory" or "out_memory", the argument
+inline int check_memory(pcm_ctx* c, int memory, const char* name) {
+  if (memory == PCM_MEM_HOST || memory == PCM_MEM_DEVICE) return PCM_OK;
+  c->err = std::string(name) + " must be PCM_MEM_HOST or PCM_MEM_DEVICE";
+  return PCM_ERR_INVALID_ARGUMENT;
+}
 template <typename T> int DevBuf<T>::reserve(pcm_ctx* c, size_t need, size_t new_cap, bool zero) { return reserve(c->stream, &c->err, need, new_cap, zero); }
 template <typename T> int DevBuf<T>::reserve_keep(pcm_ctx* c, size_t need, size_t new_cap, size_t keep) { return reserve_keep(c->stream, &c->err, need, new_cap, keep); }
 template <typename T> int PinnedBuf<T>::reserve(pcm_ctx* c, size_t need, size_t new_cap, unsigned flags) { return reserve(c->stream, &c->err, need, new_cap, flags); }

@@ -10,6 +10,7 @@
 // lane 0 reproduces that chain.
 #include "pcm_device.h"
 #include "pcm_host.h"
+#include "pre_layouts.h"
 #include "voxel_grid.h"
 
 #include <rocprim/device/device_scan.hpp>
@@ -207,19 +208,24 @@ size_t livox_filter_scratch_bytes(size_t n) {
   size_t t = 0;
   uint32_t* v = nullptr;
   (void)rocprim::exclusive_scan(nullptr, t, v, v, 0u, n, rocprim::plus<uint32_t>(), nullptr);
-  return 2 * up256(4 * n) + up256(t);
+  ArenaCarver a;
+  (void)livox_layout(a, n, t);
+  return a.used();
 }
 
 int livox_filter_device(hipStream_t stream, const void* d_msg, size_t n, int num_scans, int point_filter_num, double blind, void* d_out, size_t* n_out, void* scratch, std::string* err) {
   *n_out = 0;
   if (n < 2) return PCM_OK;
   if (point_filter_num < 1 || num_scans < 0) { *err = "point_filter_num must be >= 1"; return PCM_ERR_INVALID_ARGUMENT; }
-  char* cur = static_cast<char*>(scratch);
-  uint32_t* flag = reinterpret_cast<uint32_t*>(cur); cur += up256(4 * n);
-  uint32_t* pos = reinterpret_cast<uint32_t*>(cur); cur += up256(4 * n);
-  void* tmp = cur;
   size_t tmp_bytes = 0;
-  (void)rocprim::exclusive_scan(nullptr, tmp_bytes, flag, pos, 0u, n, rocprim::plus<uint32_t>(), stream);
+  {
+    uint32_t* v = nullptr;
+    (void)rocprim::exclusive_scan(nullptr, tmp_bytes, v, v, 0u, n, rocprim::plus<uint32_t>(), stream);
+  }
+  ArenaCarver a(scratch);
+  const LivoxScratch S = livox_layout(a, n, tmp_bytes);
+  uint32_t *flag = S.flag, *pos = S.pos;
+  void* tmp = S.tmp;
   const unsigned nb = (unsigned)((n + 255) / 256);
   const LivoxRaw* msg = static_cast<const LivoxRaw*>(d_msg);
   k_livox_flags<<<nb, 256, 0, stream>>>(msg, (uint32_t)n, num_scans, (uint32_t)point_filter_num, blind * blind, flag);

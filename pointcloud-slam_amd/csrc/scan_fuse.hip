@@ -11,6 +11,7 @@
 // first time) instead of writing and reading a flag and a position per point.  The segment table (at most 8 entries) travels
 // in the kernel arguments; a lane finds its segment by a fixed-trip walk over the 8 start indices.
 #include "host_util.h"
+#include "pre_layouts.h"
 #include "scan_fuse.h"
 
 #include <rocprim/device/device_scan.hpp>
@@ -131,15 +132,13 @@ int pcm_scan_fuse(pcm_ctx* c, const pcm_scan_segment* segs, int n_segs, const pc
   pcm_scan_fuse_params P;
   if (params) P = *params; else scan::scan_default_params(&P);
   if (const char* why = scan::scan_check_args(segs, n_segs, &P)) { c->err = why; return PCM_ERR_INVALID_ARGUMENT; }
-  if (out && out_memory != PCM_MEM_HOST && out_memory != PCM_MEM_DEVICE) { c->err = "out_memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (out && check_memory(c, out_memory, "out_memory") != PCM_OK) return PCM_ERR_INVALID_ARGUMENT;
   if (out && out_memory == PCM_MEM_DEVICE && ((uintptr_t)out % 16) != 0) { c->err = "a device output buffer must be 16-byte aligned"; return PCM_ERR_INVALID_ARGUMENT; }
-  size_t total = 0, in_bytes = 0, table_bytes = up256(2 * (size_t)(P.pitch_ring_table ? P.pitch_ring_table_len : 0));
+  size_t total = 0;
   for (int s = 0; s < n_segs; s++) {
     int rc = check_point_records(c, segs[s].points, segs[s].n, segs[s].stride_bytes, segs[s].memory, scan::kScanMaxPoints);
     if (rc != PCM_OK) return rc;
     total += segs[s].n;
-    if (segs[s].memory == PCM_MEM_HOST) in_bytes += up256(segs[s].n * segs[s].stride_bytes);
-    if (segs[s].kind == PCM_SCAN_LIDAR_XYZI) table_bytes += up256(2 * (size_t)segs[s].ring_table_len);
   }
   PCM_HIPCK(c, hipSetDevice(c->device));
   const bool own_out = !out || out_memory == PCM_MEM_HOST;   // the records are written to the context's buffer
@@ -150,58 +149,50 @@ int pcm_scan_fuse(pcm_ctx* c, const pcm_scan_segment* segs, int n_segs, const pc
     uint32_t* v = nullptr;
     (void)rocprim::exclusive_scan(nullptr, scan_tmp_bytes, v, v, 0u, nb ? nb : 1, rocprim::plus<uint32_t>(), c->stream);
   }
-  // scratch: counters | tables | workgroup counts | workgroup offsets | rocPRIM's temporary
-  const size_t off_tab = up256(4 * kCtrCount), off_kept = off_tab + table_bytes, off_off = off_kept + up256(4 * (nb + 1)), off_tmp = off_off + up256(4 * (nb + 1));
-  const size_t tmp_need = off_tmp + up256(scan_tmp_bytes);
+  const void* seg_base[PCM_SCAN_MAX_SEGMENTS] = {nullptr};
+  ArenaCarver tmp_size;
+  ArenaStage in_size = arena_stage(c, nullptr);
+  (void)scan_scratch_layout(tmp_size, kCtrCount, segs, n_segs, P, nb, scan_tmp_bytes);
+  scan_input_layout(in_size, segs, n_segs, seg_base);
+  const size_t tmp_need = tmp_size.used(), in_bytes = in_size.used();
   int rc = c->scan_tmp.reserve(c, tmp_need, tmp_need + tmp_need / 4);
   if (rc != PCM_OK) return rc;
   if (in_bytes && (rc = c->scan_in.reserve(c, in_bytes, in_bytes + in_bytes / 4)) != PCM_OK) return rc;
   if (own_out && total && (rc = c->scan_out.reserve(c, 32 * total, 32 * total + 8 * total)) != PCM_OK) return rc;
+  ArenaCarver tmp_carver(c->scan_tmp.p);
+  const ScanScratch T = scan_scratch_layout(tmp_carver, kCtrCount, segs, n_segs, P, nb, scan_tmp_bytes);
+  ArenaStage in_stage = arena_stage(c, c->scan_in.p);   // every host segment staged, one upload each
+  scan_input_layout(in_stage, segs, n_segs, seg_base);
+  if (in_stage.rc != PCM_OK) return in_stage.rc;
 
   // tables: cast to uint16 as the reference's assignment to `ring` does, one upload
-  std::vector<uint16_t> h_tab(table_bytes / 2, 0);
+  std::vector<uint16_t> h_tab((size_t)(reinterpret_cast<uint16_t*>(T.kept) - T.pitch_tab), 0);
   ScanArgs A;
   std::memset(&A, 0, sizeof(A));
-  const uint16_t* d_tab = reinterpret_cast<const uint16_t*>(c->scan_tmp.p + off_tab);
-  size_t tab_at = 0, in_at = 0;
-  if (P.pitch_ring_table) {
+  if (P.pitch_ring_table)
     for (int k = 0; k < P.pitch_ring_table_len; k++) h_tab[k] = (uint16_t)P.pitch_ring_table[k];
-    tab_at = up256(2 * (size_t)P.pitch_ring_table_len) / 2;
-  }
-  A.R = scan::scan_rule(P, d_tab);
+  A.R = scan::scan_rule(P, T.pitch_tab);
   uint32_t start = 0;
   for (int s = 0; s < PCM_SCAN_MAX_SEGMENTS; s++) {
     if (s >= n_segs) { A.seg[s].start = (uint32_t)total; A.seg[s].stride = 16; A.seg[s].divisor = 1; continue; }
     const pcm_scan_segment& g = segs[s];
-    const char* base = static_cast<const char*>(g.points);
-    if (g.memory == PCM_MEM_HOST) {   // staged in one upload
-      base = c->scan_in.p + in_at;
-      if (g.n) PCM_HIPCK(c, hipMemcpyAsync(c->scan_in.p + in_at, g.points, g.n * g.stride_bytes, hipMemcpyHostToDevice, c->stream));
-      in_at += up256(g.n * g.stride_bytes);
-    }
-    const uint16_t* tab = nullptr;
-    if (g.kind == PCM_SCAN_LIDAR_XYZI) {
-      for (int k = 0; k < g.ring_table_len; k++) h_tab[tab_at + k] = (uint16_t)g.ring_table[k];
-      tab = d_tab + tab_at;
-      tab_at += up256(2 * (size_t)g.ring_table_len) / 2;
-    }
-    A.seg[s] = scan::scan_view(g, base, tab, start);
+    if (g.kind == PCM_SCAN_LIDAR_XYZI)
+      for (int k = 0; k < g.ring_table_len; k++) h_tab[(size_t)(T.seg_tab[s] - T.pitch_tab) + k] = (uint16_t)g.ring_table[k];
+    A.seg[s] = scan::scan_view(g, static_cast<const char*>(seg_base[s]), T.seg_tab[s], start);
     start += (uint32_t)g.n;
   }
   A.total = (uint32_t)total;
   A.capacity = (uint32_t)(out ? (capacity_points < total ? capacity_points : total) : total);
 
   uint32_t h_ctr[kCtrCount] = {0};
-  uint32_t* d_ctr = reinterpret_cast<uint32_t*>(c->scan_tmp.p);
-  uint32_t* d_kept = reinterpret_cast<uint32_t*>(c->scan_tmp.p + off_kept);
-  uint32_t* d_off = reinterpret_cast<uint32_t*>(c->scan_tmp.p + off_off);
+  uint32_t *d_ctr = T.ctr, *d_kept = T.kept, *d_off = T.off;
   if (total) {
     PCM_HIPCK(c, hipMemsetAsync(d_ctr, 0, 4 * kCtrCount, c->stream));
-    if (!h_tab.empty()) PCM_HIPCK(c, hipMemcpyAsync(c->scan_tmp.p + off_tab, h_tab.data(), 2 * h_tab.size(), hipMemcpyHostToDevice, c->stream));
+    if (!h_tab.empty()) PCM_HIPCK(c, hipMemcpyAsync(T.pitch_tab, h_tab.data(), 2 * h_tab.size(), hipMemcpyHostToDevice, c->stream));
     uint4* d_out = reinterpret_cast<uint4*>(own_out ? c->scan_out.p : static_cast<char*>(out));
     k_scan_count<<<(unsigned)nb, 256, 0, c->stream>>>(A, d_kept, d_ctr);
     PCM_HIPCK(c, hipGetLastError());
-    PCM_HIPCK(c, rocprim::exclusive_scan(c->scan_tmp.p + off_tmp, scan_tmp_bytes, d_kept, d_off, 0u, nb, rocprim::plus<uint32_t>(), c->stream));
+    PCM_HIPCK(c, rocprim::exclusive_scan(T.tmp, scan_tmp_bytes, d_kept, d_off, 0u, nb, rocprim::plus<uint32_t>(), c->stream));
     k_scan_write<<<(unsigned)nb, 256, 0, c->stream>>>(A, d_off, d_out, d_ctr);
     PCM_HIPCK(c, hipGetLastError());
     PCM_HIPCK(c, hipMemcpyAsync(h_ctr, d_ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, c->stream));

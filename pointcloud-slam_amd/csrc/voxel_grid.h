@@ -3,7 +3,7 @@
 // index order, every float field averaged.  PCL sorts (index, point) pairs with std::sort and sums in float; here: a stable radix
 // sort, one wave per cell, double sums (64 interleaved partial sums + a fixed tree), so a result does not depend on the schedule.
 //
-// The box and the cell index compile for the host as well -- with a host compiler alone (tests/voxel_grid_hooks.cpp), no HIP
+// The box, the cell index and the layout of a Work compile for the host as well -- with a host compiler alone (tests/voxel_grid_hooks.cpp), no HIP
 // header is read then.  Everything else is device code and the launchers of the two pipelines of voxel_grid.hip:
 //   single segment, 32-bit keys:  clear | fold_boxes, [single_minmax], single_cells  -> {cells, valid elements, overflow}, no wait
 //   segmented, 64-bit keys:       clear, [seg_minmax], seg_cells                     -> the same, and cells per segment
@@ -16,6 +16,8 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+
+#include "arena_carver.h"
 
 #if defined(__HIPCC__)
 #include <algorithm>
@@ -91,9 +93,6 @@ PCM_VG_HD inline int split(const unsigned int* __restrict__ mm, float leaf, int*
   return m < mx[ax] ? kPieceSplit : kPieceStuck;
 }
 
-#if defined(__HIPCC__)
-constexpr uint32_t kInvalid32 = 0x80000000u;   // 32-bit key of an element without a cell (a valid box has fewer than 2^31 cells)
-
 // The arrays of one pass over N elements with keys of key_bytes (4: single segment; 8: (segment << 32 | cell), nseg segments).
 struct Work {
   void* keys; void* keys_s;          // [N]
@@ -109,6 +108,25 @@ struct Work {
   uint32_t* sfirst() const { return small + kSmallWords + nseg; }
   static constexpr int kSmallWords = 4;
 };
+// the Work of N elements carved from `a`; nseg == 0: the single pass.  sort_tmp_bytes, scan_tmp_bytes: rocPRIM's sizes (work_layout asks)
+inline Work work_carve(ArenaCarver& a, size_t N, size_t key_bytes, size_t nseg, size_t sort_tmp_bytes, size_t scan_tmp_bytes) {
+  Work W{};
+  W.keys = a.take<char>(key_bytes * N); W.keys_s = a.take<char>(key_bytes * N);
+  W.vals = a.take<uint32_t>(N); W.vals_s = a.take<uint32_t>(N);
+  W.slot = a.take<uint32_t>(N);
+  W.head = a.take<uint32_t>(nseg ? N : 0);
+  W.mm = a.take<unsigned int>(6 * (nseg ? nseg : 1));
+  W.box = a.take<long long>(6 * nseg);
+  W.small = a.take<uint32_t>(Work::kSmallWords + 2 * nseg);
+  W.nseg = (uint32_t)nseg;
+  W.tmp_bytes = sort_tmp_bytes; W.tmp2_bytes = scan_tmp_bytes;
+  W.tmp = a.take<char>(sort_tmp_bytes); W.tmp2 = a.take<char>(scan_tmp_bytes);
+  return W;
+}
+
+#if defined(__HIPCC__)
+constexpr uint32_t kInvalid32 = 0x80000000u;   // 32-bit key of an element without a cell (a valid box has fewer than 2^31 cells)
+
 // The Work of N elements at `base` (256-byte aligned; null: sizes only), *bytes = what it occupies.  nseg == 0: the single pass.
 // A pass may run on fewer elements and segments than its Work was laid out for (set nseg to the pass's).
 Work work_layout(char* base, size_t N, size_t key_bytes, size_t nseg, size_t* bytes);

@@ -80,29 +80,20 @@ __global__ void k_count64(const uint64_t* __restrict__ keys, const uint32_t* __r
 }  // namespace
 
 Work work_layout(char* base, size_t N, size_t key_bytes, size_t nseg, size_t* bytes) {
-  Work W{};
-  size_t o = 0;
-  auto take = [&](size_t b) { char* p = base ? base + o : nullptr; o += up256(b); return p; };
-  W.keys = take(key_bytes * N); W.keys_s = take(key_bytes * N);
-  W.vals = reinterpret_cast<uint32_t*>(take(4 * N)); W.vals_s = reinterpret_cast<uint32_t*>(take(4 * N));
-  W.slot = reinterpret_cast<uint32_t*>(take(4 * N));
-  W.head = reinterpret_cast<uint32_t*>(take(nseg ? 4 * N : 0));
-  W.mm = reinterpret_cast<unsigned int*>(take(4 * 6 * (nseg ? nseg : 1)));
-  W.box = reinterpret_cast<long long*>(take(8 * 6 * nseg));
-  W.small = reinterpret_cast<uint32_t*>(take(4 * (Work::kSmallWords + 2 * nseg)));
-  W.nseg = (uint32_t)nseg;
+  size_t sort_tmp = 0, scan_tmp = 0;
   uint32_t* v = nullptr;
   if (nseg) {
     uint64_t* k = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, W.tmp_bytes, k, k, v, v, N, 0, 64, nullptr);
-    (void)rocprim::exclusive_scan(nullptr, W.tmp2_bytes, v, v, 0u, N, rocprim::plus<uint32_t>(), nullptr);
+    (void)rocprim::radix_sort_pairs(nullptr, sort_tmp, k, k, v, v, N, 0, 64, nullptr);
+    (void)rocprim::exclusive_scan(nullptr, scan_tmp, v, v, 0u, N, rocprim::plus<uint32_t>(), nullptr);
   } else {
-    (void)rocprim::radix_sort_pairs(nullptr, W.tmp_bytes, v, v, v, v, N, 0, 32, nullptr);
+    (void)rocprim::radix_sort_pairs(nullptr, sort_tmp, v, v, v, v, N, 0, 32, nullptr);
     auto heads = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0u), Head32{v});
-    (void)rocprim::exclusive_scan(nullptr, W.tmp2_bytes, heads, v, 0u, N, rocprim::plus<uint32_t>(), nullptr);
+    (void)rocprim::exclusive_scan(nullptr, scan_tmp, heads, v, 0u, N, rocprim::plus<uint32_t>(), nullptr);
   }
-  W.tmp = take(W.tmp_bytes); W.tmp2 = take(W.tmp2_bytes);
-  *bytes = o;
+  ArenaCarver a(base);
+  const Work W = work_carve(a, N, key_bytes, nseg, sort_tmp, scan_tmp);
+  *bytes = a.used();
   return W;
 }
 

@@ -13,6 +13,7 @@
 // per cell.  The boxes of the leaf pieces are the ones the levels left, so no min / max pass follows.  gfx950.
 #include "pcm_device.h"
 #include "pcm_host.h"
+#include "pre_layouts.h"
 #include "voxel_grid.h"
 
 #include <rocprim/device/device_scan.hpp>
@@ -25,7 +26,6 @@ namespace pcm {
 namespace {
 
 constexpr uint32_t kNoPiece = 0xffffffffu;   // the id of a point with a non-finite coordinate: it counts nowhere
-constexpr uint32_t kBoxBlocks = 2048;        // workgroups of a box pass (they stride over the points)
 constexpr uint32_t kSlots = 128;             // pieces a workgroup keeps in LDS during a box pass (direct mapped by id)
 
 struct Cloud {
@@ -33,35 +33,17 @@ struct Cloud {
   __device__ const float* rec(uint32_t g) const { return reinterpret_cast<const float*>(base + (size_t)g * stride); }
 };
 
-// the tables of a level, for up to cap pieces; [2]: this level's and the next one's
-struct Tables {
-  unsigned int* mm[2];   // [cap][6] ordered-int boxes, min then max
-  uint32_t* fin[2];      // [cap] 1: a leaf piece, its box is final
-  uint32_t* flag;        // [cap] 1: cut at this level (what the scan reads)
-  uint32_t* before;      // [cap] cuts before the piece
-  int32_t* axis;         // [cap]
-  float* mid;            // [cap]
-  unsigned int* part;    // [kBoxBlocks][6] partial boxes of the first level
-  uint32_t* status;      // [0] cuts, [1] first stuck piece, [2] first piece that would pass the depth cap, [3] free; [4..8) fold_boxes' zeros
-  void* tmp; size_t tmp_bytes;
-};
+using Tables = VlTables;
+constexpr uint32_t kBoxBlocks = kVlBoxBlocks;
 
+// the tables of up to cap pieces (pre_layouts.h) at `base` (null: the size alone), *bytes = what they occupy
 Tables tables_layout(char* base, size_t cap, size_t* bytes) {
-  Tables T{};
-  size_t o = 0;
-  auto take = [&](size_t b) { char* p = base ? base + o : nullptr; o += up256(b); return p; };
-  for (int b = 0; b < 2; b++) T.mm[b] = reinterpret_cast<unsigned int*>(take(24 * cap));
-  for (int b = 0; b < 2; b++) T.fin[b] = reinterpret_cast<uint32_t*>(take(4 * cap));
-  T.flag = reinterpret_cast<uint32_t*>(take(4 * cap));
-  T.before = reinterpret_cast<uint32_t*>(take(4 * cap));
-  T.axis = reinterpret_cast<int32_t*>(take(4 * cap));
-  T.mid = reinterpret_cast<float*>(take(4 * cap));
-  T.part = reinterpret_cast<unsigned int*>(take(24 * kBoxBlocks));
-  T.status = reinterpret_cast<uint32_t*>(take(4 * 8));
+  size_t scan_tmp = 0;
   uint32_t* v = nullptr;
-  (void)rocprim::exclusive_scan(nullptr, T.tmp_bytes, v, v, 0u, cap, rocprim::plus<uint32_t>(), nullptr);
-  T.tmp = take(T.tmp_bytes);
-  *bytes = o;
+  (void)rocprim::exclusive_scan(nullptr, scan_tmp, v, v, 0u, cap, rocprim::plus<uint32_t>(), nullptr);
+  ArenaCarver a(base);
+  const Tables T = vl_tables_layout(a, cap, scan_tmp);
+  *bytes = a.used();
   return T;
 }
 
@@ -219,15 +201,18 @@ int run_large(pcm_ctx* c, const void* points, size_t n, size_t stride, int memor
   const int nfields = (int)(stride / 4);
   // per-point memory: the ids, and a copy of a host cloud.  Everything here goes when the call returns (hipFree waits).
   DevBuf<char> pts("VoxelGridLarge points"), tab("VoxelGridLarge piece tables"), work("VoxelGridLarge sort arrays"), cells("VoxelGridLarge cells");
-  const size_t o_in = up256(4 * n), in_bytes = memory == PCM_MEM_HOST ? up256(n * stride) : 0;
-  int rc = pts.reserve(c, o_in + in_bytes, o_in + in_bytes);
+  VlPoints L;
+  auto layout = [&](ArenaStage& a) { L = vl_points_layout(a, n, memory, points, stride); };
+  ArenaStage size = arena_stage(c, nullptr);
+  layout(size);
+  const size_t pts_bytes = size.used();
+  int rc = pts.reserve(c, pts_bytes, pts_bytes);
   if (rc != PCM_OK) return rc;
-  uint32_t* id = reinterpret_cast<uint32_t*>(pts.p);
-  Cloud C{static_cast<const char*>(points), stride};
-  if (memory == PCM_MEM_HOST) {
-    PCM_HIPCK(c, hipMemcpyAsync(pts.p + o_in, points, n * stride, hipMemcpyHostToDevice, st));
-    C.base = pts.p + o_in;
-  }
+  ArenaStage S = arena_stage(c, pts.p);
+  layout(S);
+  if (S.rc != PCM_OK) return S.rc;
+  uint32_t* id = L.id;
+  const Cloud C{static_cast<const char*>(L.cloud), stride};
   size_t cap = std::min<size_t>(4096, n), tab_bytes = 0;
   (void)tables_layout(nullptr, cap, &tab_bytes);
   if ((rc = tab.reserve(c, tab_bytes, tab_bytes)) != PCM_OK) return rc;
@@ -311,7 +296,7 @@ int run_large(pcm_ctx* c, const void* points, size_t n, size_t stride, int memor
   waits++;
   r->cells = totals[0]; r->finite_points = totals[1]; r->pieces = totals[1] ? P : 0;
   r->depth = depth; r->levels = levels; r->host_waits = waits;
-  r->workspace_bytes = o_in + in_bytes + peak_tab + work_bytes;
+  r->workspace_bytes = pts_bytes + peak_tab + work_bytes;
   if (totals[2]) { c->err = "pcm_voxel_downsample_large: a leaf piece overflows the leaf index"; return PCM_ERR_INTERNAL; }
   const size_t m = totals[0];
   if (capacity_points < m) {
@@ -321,14 +306,13 @@ int run_large(pcm_ctx* c, const void* points, size_t n, size_t stride, int memor
     return PCM_ERR_INVALID_ARGUMENT;
   }
   if (m == 0) return PCM_OK;
-  E.out = static_cast<float*>(out);
-  if (memory == PCM_MEM_HOST) {
-    if ((rc = cells.reserve(c, m * stride, m * stride)) != PCM_OK) return rc;
-    E.out = reinterpret_cast<float*>(cells.p);
-    r->workspace_bytes += up256(m * stride);
-  }
+  ArenaStage cells_size = arena_stage(c, nullptr);   // the cells of a host call: a staged output in a block of its own
+  (void)cells_size.out(memory, out, m * stride);
+  if (cells_size.used() && (rc = cells.reserve(c, m * stride, m * stride)) != PCM_OK) return rc;
+  r->workspace_bytes += cells_size.used();
+  E.out = static_cast<float*>(arena_stage(c, cells.p).out(memory, out, m * stride));
   if ((rc = vg::seg_average(&c->err, st, E, N, W)) != PCM_OK) return rc;
-  if (memory == PCM_MEM_HOST) PCM_HIPCK(c, hipMemcpyAsync(out, cells.p, m * stride, hipMemcpyDeviceToHost, st));
+  if ((rc = stage_back(c, memory, out, E.out, m * stride)) != PCM_OK) return rc;
   PCM_HIPCK(c, hipStreamSynchronize(st));   // the workspace is released on return
   r->host_waits = ++waits;
   return PCM_OK;
@@ -349,7 +333,7 @@ int pcm_voxel_downsample_large(pcm_ctx* c, const void* points, size_t n, size_t 
   if (!result) { c->err = "pcm_voxel_downsample_large: result is null"; return PCM_ERR_INVALID_ARGUMENT; }
   *result = pcm_voxel_large_result{};
   if ((!points && n) || (!out && capacity_points)) { c->err = "pcm_voxel_downsample_large: null buffer"; return PCM_ERR_INVALID_ARGUMENT; }
-  if (memory != PCM_MEM_HOST && memory != PCM_MEM_DEVICE) { c->err = "memory must be PCM_MEM_HOST or PCM_MEM_DEVICE"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (check_memory(c, memory, "memory") != PCM_OK) return PCM_ERR_INVALID_ARGUMENT;
   if (stride < 12 || stride > 64 || (stride % 4) != 0) { c->err = "records must be 3..16 floats"; return PCM_ERR_INVALID_ARGUMENT; }
   if (!(leaf > 0.f)) { c->err = "leaf size must be > 0"; return PCM_ERR_INVALID_ARGUMENT; }
   if (n > 0x7fffffffull) { c->err = "pcm_voxel_downsample_large: more than 2^31 - 1 points"; return PCM_ERR_OUT_OF_RANGE; }
