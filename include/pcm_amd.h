@@ -265,7 +265,10 @@ int pcm_target_share_count(pcm_ctx *ctx);
 int pcm_align(pcm_ctx *ctx, const float guess[16], pcm_result *out);
 
 /* LsqRegistration::evaluateCost -> linearize (lsq_registration_impl.hpp:46-49)
- * and compute_error (impl/fast_gicp_impl.hpp:213-237). H,b may be NULL. */
+ * and compute_error (impl/fast_gicp_impl.hpp:213-237). H,b may be NULL.
+ * pcm_compute_error evaluates the correspondences of the last pcm_linearize; for NDT D2D and VGICP_CUDA it keeps R cov_A R^T at
+ * the pose of that pcm_linearize (linearized_x, ndt_cuda.cu:149). pcm_align keeps its own linearisation pose and does not
+ * change the one pcm_compute_error uses: call pcm_linearize first. */
 int pcm_linearize(pcm_ctx *ctx, const double T[16], double H[36], double b[6], double *cost, int32_t *num_inliers);
 int pcm_compute_error(pcm_ctx *ctx, const double T[16], double *cost);
 

@@ -331,7 +331,10 @@ int single_pass(pcm_ctx* c, const double T[16], bool linearize, double sums[kPar
   PairState s;
   float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   init_state(s, ident);
-  for (int i = 0; i < 16; i++) { s.x0[i] = T[i]; s.xi[i] = T[i]; }
+  // k_ndt<., true> builds R cov_A R^T of D2D / VGICP_CUDA from x0 = the pose of the last linearize, not from the trial pose (with
+  // x0 = T here, pcm_compute_error at a ROTATED pose used the trial pose's rotation: 2.4e-4 / 1.3e-2 off at 0.02 rad)
+  if (linearize) std::memcpy(c->lin_T, T, sizeof(double) * 16);
+  for (int i = 0; i < 16; i++) { s.x0[i] = (ndt && !linearize) ? c->lin_T[i] : T[i]; s.xi[i] = T[i]; }
   s.mode = linearize ? MODE_LINEARIZE : MODE_TRIAL;
   PCM_HIPCK(c, hipMemcpyAsync(w->d_descs, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
   PCM_HIPCK(c, hipMemcpyAsync(w->d_states, &s, sizeof(s), hipMemcpyHostToDevice, c->stream));

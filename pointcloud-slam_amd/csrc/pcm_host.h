@@ -295,6 +295,8 @@ struct pcm_ctx {
   pcm::DevBuf<double> ndt_partials{"ndt_partials"};
   pcm::DevBuf<double> ndt_out{"ndt_out"};
   pcm::PinnedBuf<double> ndt_out_host{"ndt_out_host"};
+  // pose of the last pcm_linearize: linearized_x of the CUDA-core models (ndt_cuda.cu:149), whose trial passes keep R cov_A R^T at it
+  double lin_T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   pcm::DevBuf<float4> src_order{"src_order"};   // the scan re-ordered along the world-grid Morton curve (speed only)
   bool src_sorted = false;       // src_order holds the current source
   pcm::DevBuf<float4> planes{"planes"};
