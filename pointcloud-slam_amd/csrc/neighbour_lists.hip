@@ -675,18 +675,38 @@ __device__ inline float list_d2(const float4& mp, const float (&q)[3]) {
   return dx * dx + dy * dy + dz * dz;
 }
 
+// list_d2 for the keyed walk, the same operations in the same order on plain f32 instructions.  Left alone, the SLP vectoriser
+// pairs the z and x squares of a candidate (v_pk_add_f32 / v_pk_mul_f32 on (z, x) against (q.z, q.x)): x has to be copied next to z
+// first, into the dead w register of its load, one v_mov per candidate and for the carried buffer a second one, behind a wait for
+// loads the turn does not need yet; and a packed f32 instruction costs more issue time than the two plain ones it replaces
+// ("Padded runs").  An empty statement that takes a square and hands it back issues nothing, and a value
+// that comes out of it is no multiply the vectoriser could pair with another.  With contraction off a packed instruction rounds
+// each half as the plain one does: same bits.
+__device__ inline float walk_plain(float v) {
+  asm("" : "+v"(v));
+  return v;
+}
+__device__ inline float walk_d2(const float4& mp, const float (&q)[3]) {
+  const float dx = mp.x - q[0], dy = mp.y - q[1], dz = mp.z - q[2];
+  return walk_plain(dx * dx) + walk_plain(dy * dy) + walk_plain(dz * dz);
+}
+
 // one trip of the keyed walk: its four loads, and its four candidates into the key network in list order
 __device__ inline void walk_load(float4 (&c)[kListTrip], const float4* p) {
 #pragma unroll
   for (uint32_t j = 0; j < kListTrip; j++) c[j] = gload4(p + j);
 }
+// PLAIN: the distances by walk_d2 (k_linearize_lists) or by list_d2 as the compiler packs it (lists_knn, see there).
+template <bool PLAIN>
 __device__ inline void walk_offer(KeyedBest& kb, const float4 (&c)[kListTrip], const float (&q)[3], uint32_t pos) {
   // An empty statement that reads the four w components (the candidates' indices, which the keyed walk does not need): it issues
   // nothing.  Without it the register allocator treats the w register of a load that is still in flight as free, parks a
   // temporary of the running trip in it, and the compiler must then wait for that load before the temporary is written -- a full
   // wait in the middle of the trip the load was issued ahead of.
   asm volatile("" ::"v"(c[0].w), "v"(c[1].w), "v"(c[2].w), "v"(c[3].w));
-  const float d0 = list_d2(c[0], q), d1 = list_d2(c[1], q), d2 = list_d2(c[2], q), d3 = list_d2(c[3], q);
+  float d0, d1, d2, d3;
+  if constexpr (PLAIN) { d0 = walk_d2(c[0], q); d1 = walk_d2(c[1], q); d2 = walk_d2(c[2], q); d3 = walk_d2(c[3], q); }
+  else { d0 = list_d2(c[0], q); d1 = list_d2(c[1], q); d2 = list_d2(c[2], q); d3 = list_d2(c[3], q); }
   keyed_offer(kb, keyed_pack(d0, pos));
   keyed_offer(kb, keyed_pack(d1, pos + 1));
   keyed_offer(kb, keyed_pack(d2, pos + 2));
@@ -697,7 +717,10 @@ __device__ inline void walk_offer(KeyedBest& kb, const float4 (&c)[kListTrip], c
 // nl.pts (j < bm), bm = min(K, #in range), fp[j] = its entry (the run's first entry beyond bm, never used).  The search of
 // k_lio_lists.  It is a copy of the walk inside k_linearize_lists below, statement for statement: called from there it changed that
 // kernel's register allocation (88 -> 86 VGPRs, another schedule), and that kernel is the measured one, so the twin stays written
-// out.  A change of the walk goes to both.
+// out.  A change of the walk goes to both -- but for the plain-f32 distances (walk_d2): with them this kernel's allocation goes from
+// 96 to 98 registers, four waves per SIMD instead of five, for every placement of the barriers that was built (the peak is in the
+// fit and the tail, which keep bi[] and the body point live; held to five waves it spills three dwords).  So the twin walks on
+// list_d2 and compiles to the instructions it had.
 template <bool POOLED>
 __device__ inline void lists_knn(const TargetView& nl, uint32_t r, const float (&q)[3], float max_range_sq, uint32_t (&bi)[K], int& bm, float4 (&fp)[K]) {
   uint32_t s, e;
@@ -741,12 +764,12 @@ __device__ inline void lists_knn(const TargetView& nl, uint32_t r, const float (
 #pragma unroll
     for (uint32_t u = 0; u <= kWalkAhead; u++) {
       walk_load(buf[(u + kWalkAhead) % (kWalkAhead + 1)], run + pos + (u + kWalkAhead) * kListTrip);
-      walk_offer(kb, buf[u], q, pos + u * kListTrip);
+      walk_offer<false>(kb, buf[u], q, pos + u * kListTrip);
     }
   }
 #pragma unroll
   for (uint32_t u = 0; u < kWalkAhead; u++) {
-    if (pos + u * kListTrip < (keyed ? len : 0u)) walk_offer(kb, buf[u], q, pos + u * kListTrip);
+    if (pos + u * kListTrip < (keyed ? len : 0u)) walk_offer<false>(kb, buf[u], q, pos + u * kListTrip);
   }
   uint32_t kpos[kKeyedBest];
   const bool decided = keyed_decode(kb, max_range_sq, kpos, bm) && keyed;
@@ -858,12 +881,12 @@ __global__ void __launch_bounds__(256) k_linearize_lists(const PairDesc* __restr
 #pragma unroll
           for (uint32_t u = 0; u <= kWalkAhead; u++) {
             walk_load(buf[(u + kWalkAhead) % (kWalkAhead + 1)], run + pos + (u + kWalkAhead) * kListTrip);
-            walk_offer(kb, buf[u], q, pos + u * kListTrip);
+            walk_offer<true>(kb, buf[u], q, pos + u * kListTrip);
           }
         }
 #pragma unroll
         for (uint32_t u = 0; u < kWalkAhead; u++) {
-          if (pos + u * kListTrip < (keyed ? len : 0u)) walk_offer(kb, buf[u], q, pos + u * kListTrip);
+          if (pos + u * kListTrip < (keyed ? len : 0u)) walk_offer<true>(kb, buf[u], q, pos + u * kListTrip);
         }
         uint32_t kpos[kKeyedBest];
         const bool decided = keyed_decode(kb, kp.max_range_sq, kpos, bm) && keyed;
