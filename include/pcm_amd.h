@@ -792,7 +792,7 @@ int pcm_loam_submap_info(pcm_ctx *ctx, int32_t *keys, float *corner_in, float *s
  */
 #define PCM_LOAM_SC_POINTS 0          /* the given cloud (SINGLE_SCAN_FULL), through the VoxelGrid of `leaf` */
 #define PCM_LOAM_SC_KEYFRAME_SURF 1   /* the stored surf cloud of key frame `key`, no VoxelGrid (SINGLE_SCAN_FEAT) */
-#define PCM_LOAM_SC_KEYFRAME_NEAR 2   /* MULTI_SCAN_FEAT: not built, PCM_ERR_UNSUPPORTED */
+#define PCM_LOAM_SC_KEYFRAME_NEAR 2   /* MULTI_SCAN_FEAT: pcm_loam_sc_add_near (it needs search_num and leaf; pcm_loam_sc_add: PCM_ERR_UNSUPPORTED) */
 
 typedef struct pcm_loam_sc_params {
   double lidar_height;           /* 0.3   Scancontext.h:80 LIDAR_HEIGHT */
@@ -842,6 +842,12 @@ void pcm_loam_default_sc_params(pcm_loam_sc_params *params);
  * A point with a non-finite coordinate is skipped.  params NULL = defaults; result may be NULL. */
 int pcm_loam_sc_add(pcm_ctx *ctx, const pcm_loam_sc_params *params, int input, int key, const void *points, size_t n, size_t stride_bytes, int memory,
                     pcm_loam_sc_add_result *result);
+/* MULTI_SCAN_FEAT (input PCM_LOAM_SC_KEYFRAME_NEAR): the descriptor of the near-key-frame cloud of `key` -- pcm_loam_submap_near's
+ * cloud for (key, search_num, wrt_key, leaf), built in device memory and read where it lies.  Descriptor and keys equal, bit for
+ * bit, pcm_loam_submap_near followed by pcm_loam_sc_add(PCM_LOAM_SC_POINTS) with params->leaf = 0 (params->leaf is not read here).
+ * An empty key-frame store, a key outside [0, K) and a bad search_num / leaf: PCM_ERR_INVALID_ARGUMENT; a VoxelGrid index
+ * overflow: PCM_ERR_OUT_OF_RANGE; nothing is stored then.  params NULL = defaults; result may be NULL. */
+int pcm_loam_sc_add_near(pcm_ctx *ctx, const pcm_loam_sc_params *params, int key, int search_num, int wrt_key, float leaf, pcm_loam_sc_add_result *result);
 /* a ready descriptor (column-major doubles, ring fastest: the reference's Eigen::MatrixXd; every value must be representable as a
  * float): the keys are derived on the device.  This is how the descriptors of a saved map are loaded. */
 int pcm_loam_sc_put(pcm_ctx *ctx, const double *desc, int num_ring, int num_sector);
@@ -990,7 +996,8 @@ int pcm_loam_global_gather_ms(pcm_ctx *ctx, const pcm_loam_global_params *params
  * compacts the selected tiles through the frame's window, in order, straight into the context's LOAM target
  * (laserCloudCornerFromMapDS / laserCloudSurfFromMapDS), so a localisation frame is
  *   pcm_loam_frame_begin -> pcm_loam_dynmap_crop -> pcm_loam_align
- * with the scan as the only bulk upload.  DESIGN.md section 14.
+ * with the scan as the only bulk upload.  DESIGN.md section 14.  A mapping context can hand its map over without the host:
+ * pcm_loam_tiles_build (below) cuts its key frames into these tiles on the device.
  */
 typedef struct pcm_loam_dynmap_params {
   float max_range;               /* 150.0 utility.h:224: the window is pose -/+ max_range * 1.1 */
@@ -1054,6 +1061,61 @@ int pcm_loam_dynmap_info(pcm_ctx *ctx, int32_t *corner_tiles, int32_t *surf_tile
  * a host buffer or a caller's device buffer (memory) of `capacity` points; *n is always set, PCM_ERR_INVALID_ARGUMENT when the
  * capacity is too small.  The Matching_method == "ndt" branch feeds it to an NDT context with PCM_MEM_DEVICE. */
 int pcm_loam_dynmap_global(pcm_ctx *ctx, void *out, size_t capacity, size_t *n, int memory);
+
+/*
+ * The key-frame map cut into area tiles on the device: what a mapping session leaves a localisation session, with no host copy
+ * of the map in between (mapping context -> pcm_loam_tiles_build -> pcm_loam_dynmap_load / _crop -> pcm_loam_align).  The reference
+ * reads area lists (dynamic_map.h:37-88) and holds no program that writes them, so the rules of the cut are this library's:
+ *   tile index  ix = (int32)floorf(x / tile_size), iy likewise, on transformPointCloud's float values: -0.0f lies in tile 0,
+ *               -1e-7f in tile -1, a point exactly on k * tile_size in tile k
+ *   order       a list holds the tiles that have a point of it, by ascending (iy, ix); the two lists are independent
+ *   cloud       leaf == 0: the tile's points in export order (key frame, then point; the values are the segmented VoxelGrid
+ *               pass's one-point means, so a negative zero is stored as zero); leaf > 0: the pcl::VoxelGrid of the tile's points
+ *               alone -- the bits pcm_voxel_downsample(those points, leaf) returns
+ *   box         x_min = (double)ix * (double)tile_size, x_max = (double)(ix + 1) * (double)tile_size, the same for y (what
+ *               is_in_area selects by); z_min / z_max: the stored points' range
+ * DESIGN.md section 31.
+ */
+typedef struct pcm_loam_tiles_params {
+  float tile_size;     /* 50.0  edge of a square tile in x and y, metres; finite, > 0 */
+  float leaf_corner;   /* 0.2   utility.h:271 mappingCornerLeafSize; 0 = no down-sampling */
+  float leaf_surf;     /* 0.2   utility.h:272 mappingSurfLeafSize;   0 = no down-sampling */
+  int32_t reserved[9];
+} pcm_loam_tiles_params;
+
+typedef struct pcm_loam_tiles_result {
+  int32_t  num_corner_tiles, num_surf_tiles;
+  uint64_t corner_points_in, surf_points_in;      /* points of key frames [first, first+n) */
+  uint64_t corner_points_out, surf_points_out;    /* points stored in the tiles */
+  uint64_t num_nonfinite;                         /* dropped: non-finite x, y or z */
+  int32_t  reserved[6];
+} pcm_loam_tiles_result;
+
+void pcm_loam_default_tiles_params(pcm_loam_tiles_params *params);
+/* Replaces both tile lists of the context (and clears the selection, as pcm_loam_tile_clear followed by adds would) with the tiles
+ * of key frames [first, first + n) under their current poses.  Only counts and the per-tile table (16 bytes per tile) leave the
+ * device; the call waits twice -- for the number of tiles, then for the table (a third time when the two lists together hold more
+ * than 2^31 - 1 points and are exported one after the other).  The key-frame store, the context's target and source, the Scan
+ * Context store and the occupancy map are not touched.  The workspace (88 bytes per point plus the sort's temporaries, both lists
+ * alive together) is released before the call returns.  A bad argument (tile_size not finite or <= 0, a negative leaf, a range outside
+ * [0, K]): PCM_ERR_INVALID_ARGUMENT; |ix| or |iy| >= 32768, a tile whose VoxelGrid index overflows (tiles are not cut as
+ * pcm_voxel_downsample_large cuts) and more than 2^31 - 1 points in one list: PCM_ERR_OUT_OF_RANGE; every error leaves the tiles
+ * as they were.  An empty range or store: PCM_OK, zero tiles.  params NULL = defaults; result may be NULL. */
+int pcm_loam_tiles_build(pcm_ctx *ctx, const pcm_loam_tiles_params *params, int first, int n, pcm_loam_tiles_result *result);
+/* measurement hook (tools/bench_loam_tiles.py): pcm_loam_tiles_build with device events at its stage boundaries.  stage_ms takes
+ * PCM_LOAM_TILES_STAGES floats per list (corner, then surf): host ms of the workspace requests, then device ms of the tile keys,
+ * the key sort, the distinct keys, rank + table init, the per-tile min / max, boxes + cell keys + cell sort, the means (the
+ * scatter), the per-tile count and z range; then two more: the gather of both lists and the copies into the arenas.  The timed
+ * call waits once more than the untimed one. */
+#define PCM_LOAM_TILES_STAGES 9
+int pcm_loam_tiles_build_ms(pcm_ctx *ctx, const pcm_loam_tiles_params *params, int first, int n, pcm_loam_tiles_result *result, float *stage_ms);
+/* tile `index` of list `which`, from pcm_loam_tile_add or pcm_loam_tiles_build: its box (x_min, y_min, z_min, x_max, y_max,
+ * z_max), its index pair (0, 0 for a tile the caller added) and its number of points; any pointer may be NULL */
+int pcm_loam_tile_info(pcm_ctx *ctx, int which, int index, double box[6], int32_t ixy[2], size_t *n_points);
+/* the tile's (x, y, z, intensity) records into a host or device buffer of capacity_points; *n is always set,
+ * PCM_ERR_INVALID_ARGUMENT when the capacity is too small (the rules of pcm_loam_dynmap_global).  With pcm_loam_tile_info this is
+ * what a caller writes the PCD files and the area list from. */
+int pcm_loam_tile_get(pcm_ctx *ctx, int which, int index, void *out, size_t capacity_points, int memory, size_t *n);
 
 /*
  * 2D occupancy grid mapping of jueying_slam's map tool (src/tool/occupancy_mapping) on the device: getScan (cloud -> virtual

@@ -670,6 +670,39 @@ public:
   int laserCloudCornerFromMapDSNum() const { return crop_.num_corner; }
   int laserCloudSurfFromMapDSNum() const { return crop_.num_surf; }
 
+  // The hand-over from a mapping session on the same LoamScanToMap: the key frames of `keyframes` [first, first + n) (n < 0: all
+  // from first), cut into area tiles on the device under their current poses (pcm_loam_tiles_build).  Replaces both area lists;
+  // the map never visits the host.  params NULL: tile_size 50, leaves 0.2.
+  const pcm_loam_tiles_result& buildFromKeyFrames(LoamKeyFrameMap<PointT>& keyframes, const pcm_loam_tiles_params* params = nullptr, int first = 0, int n = -1) {
+    if (n < 0) n = keyframes.size() - first;
+    check(pcm_loam_tiles_build(ctx_, params, first, n, &tiles_), "pcm_loam_tiles_build");
+    return tiles_;
+  }
+  // area `index` of a list (0 corner, 1 surf): its box (the area list's columns), its index pair and its number of points
+  size_t tileInfo(int which, int index, double box[6], int32_t ixy[2] = nullptr) const {
+    size_t n = 0;
+    check(pcm_loam_tile_info(ctx_, which, index, box, ixy, &n), "pcm_loam_tile_info");
+    return n;
+  }
+  // the area's cloud on the host: what the caller writes to the PCD file the area list names
+  void getTile(int which, int index, Cloud& out) {
+    const size_t cap = tileInfo(which, index, nullptr);
+    if (buf_.size() < 4 * cap) buf_.resize(4 * cap);
+    size_t n = 0;
+    check(pcm_loam_tile_get(ctx_, which, index, buf_.data(), buf_.size() / 4, PCM_MEM_HOST, &n), "pcm_loam_tile_get");
+    out.points.resize(n);
+    for (size_t i = 0; i < n; i++) {
+      PointT& q = out.points[i];
+      q.x = buf_[4 * i]; q.y = buf_[4 * i + 1]; q.z = buf_[4 * i + 2]; q.intensity = buf_[4 * i + 3];
+    }
+  }
+  // ... or into a device buffer of `capacity` points; returns the number of points
+  size_t getTile(int which, int index, void* device_out, size_t capacity) {
+    size_t n = 0;
+    check(pcm_loam_tile_get(ctx_, which, index, device_out, capacity, PCM_MEM_DEVICE, &n), "pcm_loam_tile_get");
+    return n;
+  }
+
   // globalMap as (x, y, z, intensity) records into a device buffer of `capacity` points (e.g. the target of an NDT context,
   // then pcm_set_target with PCM_MEM_DEVICE and a stride of 16); returns the number of points
   size_t globalMap(void* device_out, size_t capacity) {
@@ -704,6 +737,7 @@ private:
   pcm_loam_dynmap_params params_;
   pcm_loam_dynmap_load_result load_{};
   pcm_loam_dynmap_crop_result crop_{};
+  pcm_loam_tiles_result tiles_{};
   std::vector<float> buf_;
 };
 

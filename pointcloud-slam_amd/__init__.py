@@ -17,6 +17,7 @@ from .registration import OccupancyGrid, OccupancyMap2D, save_map  # noqa: F401
 from .registration import LoamGlobalMapResult  # noqa: F401
 from .registration import VoxelLargeResult  # noqa: F401
 from .registration import LoamMapLoadResult, LoamMapCropResult, read_arealist, write_arealist  # noqa: F401
+from .registration import LoamTilesResult  # noqa: F401
 from .registration import (ScanSegment, lidar_xyzirt_segment, lidar_xyzi_segment, depth_segment, rs_to_velodyne, hesai_to_velodyne,  # noqa: F401
                            fuse_lidar_cameras)
 from .registration import lidar_desc  # noqa: F401

@@ -22,11 +22,12 @@ SYMBOLS = [
     "pcm_loam_default_submap_params", "pcm_loam_keyframe_add", "pcm_loam_keyframe_set_poses", "pcm_loam_keyframe_count", "pcm_loam_keyframe_clear",
     "pcm_loam_keyframe_get", "pcm_loam_submap_update", "pcm_loam_submap_near", "pcm_loam_submap_info",
     "pcm_loam_default_sc_params", "pcm_loam_sc_add", "pcm_loam_sc_put", "pcm_loam_sc_get", "pcm_loam_sc_count", "pcm_loam_sc_shape", "pcm_loam_sc_clear",
-    "pcm_loam_sc_detect", "pcm_loam_sc_distance", "pcm_loam_loop_detect_distance",
+    "pcm_loam_sc_detect", "pcm_loam_sc_distance", "pcm_loam_loop_detect_distance", "pcm_loam_sc_add_near",
     "pcm_loam_submap_near_dev", "pcm_loam_default_loop_params", "pcm_loam_loop_verify", "pcm_loam_loop_closure", "pcm_loam_loop_verifier_exists",
     "pcm_loam_default_global_params", "pcm_loam_global_keys", "pcm_loam_global_map", "pcm_loam_map_export", "pcm_loam_global_gather_ms",
     "pcm_loam_default_dynmap_params", "pcm_loam_tile_add", "pcm_loam_tile_count", "pcm_loam_tile_clear", "pcm_loam_dynmap_need_load",
     "pcm_loam_dynmap_load", "pcm_loam_dynmap_crop", "pcm_loam_dynmap_info", "pcm_loam_dynmap_global",
+    "pcm_loam_default_tiles_params", "pcm_loam_tiles_build", "pcm_loam_tile_info", "pcm_loam_tile_get", "pcm_loam_tiles_build_ms",
     "pcm_occ_default_params", "pcm_occ_reset", "pcm_occ_insert_scans", "pcm_occ_insert_keyframes", "pcm_occ_get_scan", "pcm_occ_status",
     "pcm_occ_info", "pcm_occ_get_map", "pcm_occ_get_pgm", "pcm_occ_get_counts",
     "pcm_scan_default_fuse_params", "pcm_scan_fuse", "pcm_scan_fused",
@@ -245,6 +246,19 @@ class PcmLoamDynmapCropResult(C.Structure):
                 ("y_hi", C.c_float), ("status", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
+PCM_LOAM_TILES_STAGES = 9
+TILES_STAGE_NAMES = ("workspace_host", "tile_keys", "key_sort", "distinct_keys", "rank", "tile_minmax", "cell_sort", "means_scatter", "tile_stats")
+
+
+class PcmLoamTilesParams(C.Structure):
+    _fields_ = [("tile_size", C.c_float), ("leaf_corner", C.c_float), ("leaf_surf", C.c_float), ("reserved", C.c_int32 * 9)]
+
+
+class PcmLoamTilesResult(C.Structure):
+    _fields_ = [("num_corner_tiles", C.c_int32), ("num_surf_tiles", C.c_int32), ("corner_points_in", C.c_uint64), ("surf_points_in", C.c_uint64),
+                ("corner_points_out", C.c_uint64), ("surf_points_out", C.c_uint64), ("num_nonfinite", C.c_uint64), ("reserved", C.c_int32 * 6)]
+
+
 class PcmOccParams(C.Structure):
     _fields_ = [("min_z", C.c_double), ("max_z", C.c_double), ("angle_increment", C.c_double), ("min_range", C.c_double),
                 ("max_range", C.c_double), ("log_occ", C.c_double), ("log_free", C.c_double), ("resolution", C.c_double),
@@ -410,6 +424,7 @@ def load_library():
     L.pcm_loam_default_sc_params.argtypes = [C.POINTER(PcmLoamScParams)]
     L.pcm_loam_default_sc_params.restype = None
     L.pcm_loam_sc_add.argtypes = [vp, C.POINTER(PcmLoamScParams), i32, i32, vp, sz, sz, i32, C.POINTER(PcmLoamScAddResult)]
+    L.pcm_loam_sc_add_near.argtypes = [vp, C.POINTER(PcmLoamScParams), i32, i32, i32, C.c_float, C.POINTER(PcmLoamScAddResult)]
     L.pcm_loam_sc_put.argtypes = [vp, vp, i32, i32]
     L.pcm_loam_sc_get.argtypes = [vp, i32, vp, vp, vp]
     L.pcm_loam_sc_count.argtypes = [vp]
@@ -440,6 +455,12 @@ def load_library():
     L.pcm_loam_dynmap_crop.argtypes = [vp, C.POINTER(PcmLoamDynmapParams), vp, C.POINTER(PcmLoamDynmapCropResult)]
     L.pcm_loam_dynmap_info.argtypes = [vp] * 5
     L.pcm_loam_dynmap_global.argtypes = [vp, vp, sz, C.POINTER(sz), i32]
+    L.pcm_loam_default_tiles_params.argtypes = [C.POINTER(PcmLoamTilesParams)]
+    L.pcm_loam_default_tiles_params.restype = None
+    L.pcm_loam_tiles_build.argtypes = [vp, C.POINTER(PcmLoamTilesParams), i32, i32, C.POINTER(PcmLoamTilesResult)]
+    L.pcm_loam_tiles_build_ms.argtypes = [vp, C.POINTER(PcmLoamTilesParams), i32, i32, C.POINTER(PcmLoamTilesResult), vp]
+    L.pcm_loam_tile_info.argtypes = [vp, i32, i32, vp, vp, C.POINTER(sz)]
+    L.pcm_loam_tile_get.argtypes = [vp, i32, i32, vp, sz, i32, C.POINTER(sz)]
     L.pcm_occ_default_params.argtypes = [C.POINTER(PcmOccParams)]
     L.pcm_occ_default_params.restype = None
     L.pcm_occ_reset.argtypes = [vp, C.POINTER(PcmOccParams)]

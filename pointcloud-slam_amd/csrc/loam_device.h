@@ -103,6 +103,15 @@ int loam_keyposes(pcm_ctx* c, const KeyPose** kp);
 struct NearCloud { const float4* pts; uint32_t n_in; const uint32_t* h_small; };
 int loam_near_queue(pcm_ctx* c, int slot, int key, int search_num, int wrt_key, float leaf, NearCloud* out);
 void loam_near_waited(pcm_ctx* c);
+// loam_submap.hip: the caller of pcm_loam_map_export / pcm_loam_global_map with a device buffer has drained the stream
+void loam_export_waited(pcm_ctx* c);
+
+// loam_dynmap.hip: what the tile builder (loam_tiles.hip) hands the map-tile store.  One tile: its box, its index pair and its
+// points, which are cells [first, first + n) of its list's cloud.  loam_tiles_replace empties both lists and the selection as
+// pcm_loam_tile_clear does and stores the new tiles; the clouds (device memory, n_cells[m] points) are copied into the arenas on the
+// context's stream, device to device, and may be released in stream order on return.  A failure leaves the store as it was.
+struct BuiltTile { double box[6]; int32_t ix, iy; uint32_t first, n; };
+int loam_tiles_replace(pcm_ctx* c, const BuiltTile* const tiles[2], const size_t n_tiles[2], const float4* const cells[2], const size_t n_cells[2]);
 
 // loam_features.hip: the context's last front-end features.  gen: bumps whenever the output array is rewritten
 bool loam_features_last_out(pcm_ctx* c, const float4** out, uint32_t* n_c, uint32_t* n_s, uint64_t* gen);

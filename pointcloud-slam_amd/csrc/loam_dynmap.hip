@@ -154,6 +154,7 @@ struct Tile {
   Area box;
   size_t off;
   uint32_t n;
+  int32_t ix = 0, iy = 0;   // the index pair of a tile pcm_loam_tiles_build cut; 0, 0 for one the caller added
 };
 
 struct DynStore {
@@ -210,12 +211,58 @@ int ensure_work(pcm_ctx* c, DynStore* S, size_t nb, size_t n_ent) {
   return PCM_OK;
 }
 
+// both lists and the selection; the arenas keep their memory
+void clear_tiles(DynStore* S) {
+  for (int m = 0; m < 2; m++) {
+    S->tiles[m].clear();
+    S->sel[m].clear();
+    S->arena[m].n = 0;
+  }
+  S->loaded = false;
+  S->sel_gen++;
+  S->last_valid = false;
+  for (int k = 0; k < 6; k++) S->last_load[k] = kNeverLoaded;
+}
+
 bool same_window(const CropWindow& a, const CropWindow& b) {
   // float equality: the limits are finite or the two infinities of margin < 0, never NaN
   return a.x_lo == b.x_lo && a.x_hi == b.x_hi && a.y_lo == b.y_lo && a.y_hi == b.y_hi && a.crop_x == b.crop_x;
 }
 
 }  // namespace
+
+namespace pcm {
+namespace loam {
+int loam_tiles_replace(pcm_ctx* c, const BuiltTile* const tiles[2], const size_t n_tiles[2], const float4* const cells[2], const size_t n_cells[2]) {
+  DynStore* S = nullptr;
+  int rc = check_ctx_dm(c, &S);
+  if (rc != PCM_OK) return rc;
+  for (int m = 0; m < 2; m++) {
+    if (n_cells[m] > 0xffffffffull || n_tiles[m] > 0x7fffffffull) { c->err = "map-tile store too large"; return PCM_ERR_OUT_OF_RANGE; }
+    // room first, so that a failed allocation leaves both lists whole (growth keeps the stored points)
+    Arena& A = S->arena[m];
+    if (n_cells[m] > A.n && (rc = A.reserve(c, n_cells[m] - A.n)) != PCM_OK) return rc;
+  }
+  for (int m = 0; m < 2; m++) {
+    try { S->tiles[m].reserve(n_tiles[m]); } catch (...) { c->err = "out of host memory"; return PCM_ERR_INTERNAL; }
+  }
+  clear_tiles(S);
+  for (int m = 0; m < 2; m++) {
+    Arena& A = S->arena[m];
+    if (n_cells[m]) PCM_HIPCK(c, hipMemcpyAsync(A.d.p, cells[m], sizeof(float4) * n_cells[m], hipMemcpyDeviceToDevice, c->stream));
+    for (size_t t = 0; t < n_tiles[m]; t++) {
+      const BuiltTile& b = tiles[m][t];
+      Tile T;
+      T.box = Area{b.box[0], b.box[1], b.box[2], b.box[3], b.box[4], b.box[5]};
+      T.off = b.first; T.n = b.n; T.ix = b.ix; T.iy = b.iy;
+      S->tiles[m].push_back(T);
+    }
+    A.n = n_cells[m];
+  }
+  return PCM_OK;
+}
+}  // namespace loam
+}  // namespace pcm
 
 extern "C" {
 
@@ -263,15 +310,38 @@ int pcm_loam_tile_clear(pcm_ctx* c) {
   DynStore* S = nullptr;
   int rc = check_ctx_dm(c, &S);
   if (rc != PCM_OK) return rc;
-  for (int m = 0; m < 2; m++) {
-    S->tiles[m].clear();
-    S->sel[m].clear();
-    S->arena[m].n = 0;   // the arenas keep their memory
-  }
-  S->loaded = false;
-  S->sel_gen++;
-  S->last_valid = false;
-  for (int k = 0; k < 6; k++) S->last_load[k] = kNeverLoaded;
+  clear_tiles(S);
+  return PCM_OK;
+}
+
+int pcm_loam_tile_info(pcm_ctx* c, int which, int index, double box[6], int32_t ixy[2], size_t* n_points) {
+  DynStore* S = nullptr;
+  int rc = check_ctx_dm(c, &S);
+  if (rc != PCM_OK) return rc;
+  if (which != 0 && which != 1) { c->err = "which must be 0 (corner list) or 1 (surf list)"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (index < 0 || (size_t)index >= S->tiles[which].size()) { c->err = "pcm_loam_tile_info: index outside [0, tiles of the list)"; return PCM_ERR_INVALID_ARGUMENT; }
+  const Tile& T = S->tiles[which][(size_t)index];
+  if (box) { box[0] = T.box.x_min; box[1] = T.box.y_min; box[2] = T.box.z_min; box[3] = T.box.x_max; box[4] = T.box.y_max; box[5] = T.box.z_max; }
+  if (ixy) { ixy[0] = T.ix; ixy[1] = T.iy; }
+  if (n_points) *n_points = T.n;
+  return PCM_OK;
+}
+
+int pcm_loam_tile_get(pcm_ctx* c, int which, int index, void* out, size_t capacity, int memory, size_t* n) {
+  DynStore* S = nullptr;
+  int rc = check_ctx_dm(c, &S);
+  if (rc != PCM_OK) return rc;
+  if (n) *n = 0;
+  if (which != 0 && which != 1) { c->err = "which must be 0 (corner list) or 1 (surf list)"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (check_memory(c, memory, "memory") != PCM_OK) return PCM_ERR_INVALID_ARGUMENT;
+  if (index < 0 || (size_t)index >= S->tiles[which].size()) { c->err = "pcm_loam_tile_get: index outside [0, tiles of the list)"; return PCM_ERR_INVALID_ARGUMENT; }
+  const Tile& T = S->tiles[which][(size_t)index];
+  if (n) *n = T.n;
+  if (T.n > capacity || (!out && T.n)) { c->err = "pcm_loam_tile_get: capacity too small (the count is set)"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (T.n == 0) return PCM_OK;
+  PCM_HIPCK(c, hipSetDevice(c->device));
+  PCM_HIPCK(c, hipMemcpyAsync(out, S->arena[which].d + T.off, sizeof(float4) * T.n, memory == PCM_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
   return PCM_OK;
 }
 

@@ -307,6 +307,31 @@ void launch_distance(pcm_ctx* c, ScStore* S, uint32_t q, const int32_t* cand, ui
   k_sc_distance<<<n, block, lds, c->stream>>>(S->desc, S->skey, S->norm, S->R, S->S, q, cand, first, sc_search_radius(search_ratio, S->S), S->dist, S->shift);
 }
 
+// the descriptor of `cloud` (n_cloud points on the device; may be empty) becomes row S->count of the store; waits, so the caller may
+// reuse its buffers on return
+int add_descriptor(pcm_ctx* c, ScStore* S, const pcm_loam_sc_params& p, const float4* cloud, uint32_t n_cloud, size_t n_in, pcm_loam_sc_add_result* result) {
+  hipStream_t st = c->stream;
+  const uint32_t nb = (uint32_t)(S->R * S->S);
+  k_sc_table_init<<<(nb + 255) / 256, 256, 0, st>>>(S->table, nb);
+  if (n_cloud > 0) {
+    const ScShape sh{S->R, S->S, p.lidar_height, p.max_radius};
+    const unsigned grid = std::min<unsigned>(1024u, (n_cloud + 255) / 256);
+    const int use_lds = nb <= kScLdsWords ? 1 : 0;
+    k_sc_bins<<<grid, 256, use_lds ? sizeof(uint32_t) * nb : 0, st>>>(cloud, n_cloud, sh, S->table, use_lds);
+  }
+  launch_finish(c, S, true);
+  PCM_HIPCK(c, hipGetLastError());
+  PCM_HIPCK(c, hipStreamSynchronize(st));
+  S->count++;
+  if (result) {
+    result->index = (int32_t)(S->count - 1);
+    result->num_points_in = (int32_t)n_in;
+    result->num_points = (int32_t)n_cloud;
+    result->status = PCM_OK;
+  }
+  return PCM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -339,7 +364,7 @@ int pcm_loam_sc_add(pcm_ctx* c, const pcm_loam_sc_params* params, int input, int
   uint32_t n_cloud = 0;
   size_t n_in = 0;
   if (input == PCM_LOAM_SC_KEYFRAME_NEAR) {
-    c->err = "PCM_LOAM_SC_KEYFRAME_NEAR is not built: assemble the cloud with pcm_loam_submap_near and pass it as PCM_LOAM_SC_POINTS";
+    c->err = "PCM_LOAM_SC_KEYFRAME_NEAR needs search_num and leaf, which this entry point has no room for: call pcm_loam_sc_add_near";
     return PCM_ERR_UNSUPPORTED;
   }
   if (input == PCM_LOAM_SC_KEYFRAME_SURF) {
@@ -373,25 +398,31 @@ int pcm_loam_sc_add(pcm_ctx* c, const pcm_loam_sc_params* params, int input, int
       n_cloud = (uint32_t)m;
     }
   }
-  const uint32_t nb = (uint32_t)(S->R * S->S);
-  k_sc_table_init<<<(nb + 255) / 256, 256, 0, st>>>(S->table, nb);
-  if (n_cloud > 0) {
-    const ScShape sh{S->R, S->S, p.lidar_height, p.max_radius};
-    const unsigned grid = std::min<unsigned>(1024u, (n_cloud + 255) / 256);
-    const int use_lds = nb <= kScLdsWords ? 1 : 0;
-    k_sc_bins<<<grid, 256, use_lds ? sizeof(uint32_t) * nb : 0, st>>>(cloud, n_cloud, sh, S->table, use_lds);
+  return add_descriptor(c, S, p, cloud, n_cloud, n_in, result);
+}
+
+int pcm_loam_sc_add_near(pcm_ctx* c, const pcm_loam_sc_params* params, int key, int search_num, int wrt_key, float leaf, pcm_loam_sc_add_result* result) {
+  ScStore* S = nullptr;
+  int rc = check_ctx_sc(c, &S);
+  if (rc != PCM_OK) return rc;
+  pcm_loam_sc_params p;
+  if (params) p = *params; else pcm_loam_default_sc_params(&p);
+  if ((rc = check_scparams(c, S, p)) != PCM_OK) return rc;
+  if (result) std::memset(result, 0, sizeof(*result));
+  // pcm_loam_submap_near's cloud, queued in the near workspace of the key-frame store and read where it lies
+  NearCloud near{};
+  if ((rc = loam_near_queue(c, 0, key, search_num, wrt_key, leaf, &near)) != PCM_OK) return rc;
+  PCM_HIPCK(c, hipSetDevice(c->device));
+  uint32_t n_cloud = 0;
+  if (near.pts) {
+    PCM_HIPCK(c, hipStreamSynchronize(c->stream));   // the count of the cells
+    loam_near_waited(c);
+    if (near.h_small[2]) { c->err = "leaf size too small for the extent of the cloud (index overflow)"; return PCM_ERR_OUT_OF_RANGE; }
+    n_cloud = near.h_small[0];
+    if (n_cloud > near.n_in) { c->err = "pcm_loam_sc_add_near: inconsistent counts"; return PCM_ERR_INTERNAL; }
   }
-  launch_finish(c, S, true);
-  PCM_HIPCK(c, hipGetLastError());
-  PCM_HIPCK(c, hipStreamSynchronize(st));   // the caller may reuse its buffers on return
-  S->count++;
-  if (result) {
-    result->index = (int32_t)(S->count - 1);
-    result->num_points_in = (int32_t)n_in;
-    result->num_points = (int32_t)n_cloud;
-    result->status = PCM_OK;
-  }
-  return PCM_OK;
+  if ((rc = ensure_store(c, S, p.num_ring, p.num_sector)) != PCM_OK) return rc;
+  return add_descriptor(c, S, p, near.pts, n_cloud, near.n_in, result);
 }
 
 int pcm_loam_sc_put(pcm_ctx* c, const double* desc, int num_ring, int num_sector) {

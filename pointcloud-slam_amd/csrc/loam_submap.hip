@@ -509,6 +509,11 @@ void loam_near_waited(pcm_ctx* c) {
   KeyStore* S = loam_store<KeyStore>(c, LoamStore::key, false);
   if (S) S->ndev[0].in_flight = S->ndev[1].in_flight = false;
 }
+
+void loam_export_waited(pcm_ctx* c) {
+  KeyStore* S = loam_store<KeyStore>(c, LoamStore::key, false);
+  if (S) S->glob.in_flight = false;
+}
 }  // namespace loam
 }  // namespace pcm
 

@@ -980,6 +980,16 @@ def _loam_sc_add(self, points=None, keyframe=None, near=None, **params) -> int:
     return r.index
 
 
+def _loam_sc_add_near(self, key: int, search_num: int, wrt_key: int = -1, leaf: float = 0.2, **params) -> int:
+    """MULTI_SCAN_FEAT: the descriptor of the near-key-frame cloud ``near_keyframes(key, search_num, wrt_key, leaf)``, built on the
+    device and read in place (pcm_loam_sc_add_near); equals ``sc_add(points=that cloud, leaf=0.0)``.  Returns its index."""
+    p = _sc_params(self._L, params)
+    r = capi.PcmLoamScAddResult()
+    self._check(self._L.pcm_loam_sc_add_near(self._h, C.byref(p), int(key), int(search_num), int(wrt_key), float(leaf), C.byref(r)))
+    self._sc_last_add = r
+    return r.index
+
+
 def _loam_sc_put(self, desc):
     """A ready (num_ring, num_sector) descriptor (e.g. of a saved map); its keys are derived on the device."""
     d = np.asarray(desc, dtype=np.float64)
@@ -1041,6 +1051,7 @@ def _loam_detect_loop_distance(self, time_cur, radius: float = 10.0, time_diff_s
 
 LoamRegistration.sc_add = _loam_sc_add
 LoamRegistration.sc_put = _loam_sc_put
+LoamRegistration.sc_add_near = _loam_sc_add_near
 LoamRegistration.sc_get = _loam_sc_get
 LoamRegistration.sc_count = property(_loam_sc_count)
 LoamRegistration.sc_clear = _loam_sc_clear
@@ -1390,6 +1401,7 @@ def _loam_add_tile(self, which, box, points) -> int:
     idx = self._L.pcm_loam_tile_add(self._h, _TILE_LIST[which], b.ctypes.data, pts.ctypes.data, pts.shape[0], 16, capi.MEM_HOST)
     if idx < 0:
         self._check(idx)
+    self._tile_size = None   # the list now holds a tile that build_tiles did not name
     return idx
 
 
@@ -1403,6 +1415,7 @@ def _loam_num_tiles(self, which) -> int:
 def _loam_clear_tiles(self):
     self._check(self._L.pcm_loam_tile_clear(self._h))
     self._dm_load = self._dm_crop = None
+    self._tile_size = None
 
 
 def _pose6(pose6):
@@ -1666,6 +1679,105 @@ LoamRegistration.load_map = _loam_load_map
 LoamRegistration.crop_map = _loam_crop_map
 LoamRegistration.dynmap_info = _loam_dynmap_info
 LoamRegistration.global_map = _loam_global_map
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The key-frame map cut into localisation area tiles on the device
+# ---------------------------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class LoamTilesResult:
+    num_corner_tiles: int
+    num_surf_tiles: int
+    corner_points_in: int
+    surf_points_in: int
+    corner_points_out: int
+    surf_points_out: int
+    num_nonfinite: int
+
+
+def _tiles_params(L, params: dict) -> capi.PcmLoamTilesParams:
+    p = capi.PcmLoamTilesParams()
+    L.pcm_loam_default_tiles_params(C.byref(p))
+    for k, v in params.items():
+        if k.startswith("reserved") or not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _loam_build_tiles(self, first: int = 0, n: int = None, **params) -> LoamTilesResult:
+    """pcm_loam_tiles_build: replaces both tile lists with the tiles of key frames first .. first + n - 1 (default: all from
+    ``first``) under their current poses (tile_size, leaf_corner, leaf_surf); the map does not leave the device.  ``load_map`` /
+    ``crop_map`` then run on them as on tiles from ``add_tile``."""
+    if n is None:
+        n = self.num_keyframes - first
+    p = _tiles_params(self._L, params)
+    r = capi.PcmLoamTilesResult()
+    self._check(self._L.pcm_loam_tiles_build(self._h, C.byref(p), int(first), int(n), C.byref(r)))
+    self._dm_load = self._dm_crop = None
+    self._tile_size = float(p.tile_size)
+    return LoamTilesResult(r.num_corner_tiles, r.num_surf_tiles, int(r.corner_points_in), int(r.surf_points_in), int(r.corner_points_out),
+                           int(r.surf_points_out), int(r.num_nonfinite))
+
+
+def _loam_build_tiles_ms(self, first: int = 0, n: int = None, **params) -> dict:
+    """Measurement hook (pcm_loam_tiles_build_ms): build_tiles with device events at its stage boundaries.  Returns the stage
+    times in ms: {"corner": {stage: ms}, "surf": {stage: ms}, "gather": ms, "arena_copy": ms}; ``workspace_host`` is host time."""
+    if n is None:
+        n = self.num_keyframes - first
+    p = _tiles_params(self._L, params)
+    r = capi.PcmLoamTilesResult()
+    ms = np.zeros(2 * capi.PCM_LOAM_TILES_STAGES + 2, np.float32)
+    self._check(self._L.pcm_loam_tiles_build_ms(self._h, C.byref(p), int(first), int(n), C.byref(r), ms.ctypes.data))
+    self._dm_load = self._dm_crop = None
+    self._tile_size = float(p.tile_size)
+    S = capi.PCM_LOAM_TILES_STAGES
+    out = {name: {k: float(v) for k, v in zip(capi.TILES_STAGE_NAMES, ms[m * S:(m + 1) * S])} for m, name in enumerate(("corner", "surf"))}
+    out["gather"], out["arena_copy"] = float(ms[2 * S]), float(ms[2 * S + 1])
+    return out
+
+
+def _loam_tile_info(self, which, i: int) -> dict:
+    """Tile ``i`` of a list, from ``add_tile`` or ``build_tiles``: box (x_min, y_min, z_min, x_max, y_max, z_max) float64, ixy (the
+    index pair; (0, 0) for a tile added by hand) and its number of points (pcm_loam_tile_info)."""
+    box = np.zeros(6, np.float64)
+    ixy = np.zeros(2, np.int32)
+    n = C.c_size_t(0)
+    self._check(self._L.pcm_loam_tile_info(self._h, _TILE_LIST[which], int(i), box.ctypes.data, ixy.ctypes.data, C.byref(n)))
+    return {"box": box, "ixy": (int(ixy[0]), int(ixy[1])), "n": int(n.value)}
+
+
+def _loam_get_tile(self, which, i: int, out=None):
+    """The (n, 4) x y z intensity points of tile ``i`` (pcm_loam_tile_get).  Without ``out``: a host array.  With a contiguous
+    (cap, 4) float32 device tensor or host array: written there, returns n."""
+    n = C.c_size_t(0)
+    if out is not None:
+        ptr, cap, mem = _cloud_buffer(out)
+        self._check(self._L.pcm_loam_tile_get(self._h, _TILE_LIST[which], int(i), ptr, cap, mem, C.byref(n)))
+        return int(n.value)
+    a = np.zeros((self.tile_info(which, i)["n"], 4), np.float32)
+    self._check(self._L.pcm_loam_tile_get(self._h, _TILE_LIST[which], int(i), a.ctypes.data, a.shape[0], capi.MEM_HOST, C.byref(n)))
+    return a[:n.value]
+
+
+def _loam_tiles_arealist(self, which, prefix: str = ""):
+    """The rows ``write_arealist`` takes for the tiles ``build_tiles`` left in a list: (path, box) with path
+    ``f"{prefix}{tile_size:g}_{ix}_{iy}.pcd"``.  There is no PCD writer here: the caller writes ``get_tile(which, i)`` to each path."""
+    ts = getattr(self, "_tile_size", None)
+    if ts is None:
+        raise capi.PcmError(-2, "tiles_arealist needs the lists as build_tiles left them (no build yet, or add_tile / clear_tiles since)")
+    rows = []
+    for i in range(self.num_tiles(which)):
+        t = self.tile_info(which, i)
+        rows.append(("%s%g_%d_%d.pcd" % (prefix, ts, t["ixy"][0], t["ixy"][1]), t["box"]))
+    return rows
+
+
+LoamRegistration.build_tiles = _loam_build_tiles
+LoamRegistration.build_tiles_ms = _loam_build_tiles_ms
+LoamRegistration.tile_info = _loam_tile_info
+LoamRegistration.get_tile = _loam_get_tile
+LoamRegistration.tiles_arealist = _loam_tiles_arealist
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
