@@ -2,7 +2,8 @@
 
 Holds only what the path needs: ``csrc/`` (hand-written HIP kernels + the C ABI
 of ``include/pcm_amd.h``, built into ``libpcm_amd.so``), the host-side mirror
-of the reference's registration interface (``registration.py``), the synthetic
+of the reference's registration interface (``registration.py``, with its subsystems in
+``lio.py``, ``loam.py``, ``occ.py`` and ``scan.py`` over the shared ``_binding.py``), the synthetic
 Livox-shaped input generator (``synth.py``) and the batch sharding helper
 (``sharding.py``).  There is no CPU fallback: loading fails loudly when the HIP
 library is missing, and contexts fail when no HIP device is present.

@@ -28,23 +28,41 @@ def test_library_exports_every_declared_symbol(pcm):
     assert L.pcm_abi_version() == 3
 
 
+STRUCTS_WITHOUT_A_CLASS = {"pcm_imu_pose"}   # the binding passes Pose6D rows as a (K,22) float64 numpy array
+
+
 def test_struct_layouts_match_header(pcm, tmp_path):
+    """Every ctypes.Structure of capi.py against include/pcm_amd.h as gcc lays it out: the struct's sizeof, and every field's
+    offsetof and sizeof; as many fields as the header's struct body declares; and no struct typedef of the header without a class."""
     from pointcloud_slam_amd import capi
-    src = r'''
-    #include <stdio.h>
-    #include <stddef.h>
-    #include "pcm_amd.h"
-    int main(void) {
-      printf("%zu %zu %zu %zu %zu %zu %zu\n", sizeof(pcm_config), sizeof(pcm_result), sizeof(pcm_stats),
-             offsetof(pcm_config, voxel_resolution), offsetof(pcm_config, flags), offsetof(pcm_result, H), offsetof(pcm_result, status));
-      return 0;
-    }'''
+    hdr = open(os.path.join(ROOT, "include", "pcm_amd.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    bodies = {m.group(2): m.group(1) for m in re.finditer(r"typedef\s+struct\s+\w*\s*\{([^{}]*)\}\s*(pcm_\w+)\s*;", hdr)}
+    classes = {re.sub(r"(?<!^)([A-Z])", r"_\1", c.__name__).lower(): c for c in vars(capi).values()
+               if isinstance(c, type) and issubclass(c, C.Structure) and c is not C.Structure}
+    assert len(classes) >= 37 and set(classes) <= set(bodies), set(classes) - set(bodies)
+    assert set(bodies) - set(classes) == STRUCTS_WITHOUT_A_CLASS
+    lines, want = [], []
+    for name, cls in sorted(classes.items()):
+        declarators = sum(len(d.split(",")) for d in bodies[name].split(";") if d.strip())
+        assert declarators == len(cls._fields_), (name, declarators, len(cls._fields_))
+        lines.append('printf("%%zu\\n", sizeof(%s));' % name)
+        want.append(C.sizeof(cls))
+        for field, _ in cls._fields_:
+            lines.append('printf("%%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (name, field, name, field))
+            want += [getattr(cls, field).offset, getattr(cls, field).size]
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "pcm_amd.h"\nint main(void) {\n%s\nreturn 0;\n}\n' % "\n".join(lines)
     exe = str(tmp_path / "pcm_layout_check")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src.encode(), check=True)
     got = [int(x) for x in subprocess.check_output([exe]).split()]
-    want = [C.sizeof(capi.PcmConfig), C.sizeof(capi.PcmResult), C.sizeof(capi.PcmStats), capi.PcmConfig.voxel_resolution.offset,
-            capi.PcmConfig.flags.offset, capi.PcmResult.H.offset, capi.PcmResult.status.offset]
-    assert got == want
+    assert len(got) == len(want) >= 700
+    values = iter(zip(got, want))
+    for name, cls in sorted(classes.items()):
+        assert next(values) == (C.sizeof(cls),) * 2, "sizeof(%s)" % name
+        for field, _ in cls._fields_:
+            for what in ("offsetof", "sizeof"):
+                g, w = next(values)
+                assert g == w, "%s(%s.%s): header %d, capi.py %d" % (what, name, field, g, w)
 
 
 def test_flag_constants_match_header(pcm):
