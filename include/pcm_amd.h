@@ -1062,6 +1062,37 @@ int pcm_loam_dynmap_info(pcm_ctx *ctx, int32_t *corner_tiles, int32_t *surf_tile
  * capacity is too small.  The Matching_method == "ndt" branch feeds it to an NDT context with PCM_MEM_DEVICE. */
 int pcm_loam_dynmap_global(pcm_ctx *ctx, void *out, size_t capacity, size_t *n, int memory);
 
+/* One tile store for several localisation contexts (a fleet of robots on one site map).  The store -- both tile lists and their
+ * points on the device -- exists once however many contexts hold it; the selection of the last load, the crop workspace and the
+ * record of the last crop stay per context: each robot has its own pose and its own window.  DESIGN.md section 33.
+ *   - pcm_loam_tile_share: `dst` reads the store `src` holds from now on.  Both are PCM_MODEL_LOAM contexts on one device and
+ *     dst != src, else PCM_ERR_INVALID_ARGUMENT (pcm_last_error(dst) names the reason).  The call waits for src's stream (every
+ *     upload of pcm_loam_tile_add and the copies of pcm_loam_tiles_build are complete before any holder reads) and for dst's,
+ *     lets go of the store dst had and resets dst's selection: a crop needs a new pcm_loam_dynmap_load (PCM_ERR_NO_INPUT before).
+ *     dst's LOAM target and search grids are not touched.  An empty store may be shared.
+ *   - While a store has more than one holder nothing writes to it: pcm_loam_tile_add and pcm_loam_tiles_build on any holder return
+ *     PCM_ERR_UNSUPPORTED (the build before any device work) and change nothing.  pcm_loam_tile_clear on a holder of a shared
+ *     store detaches that holder only and gives it an empty store of its own.  There is no copy-on-write.
+ *   - The reading calls work on every holder: pcm_loam_tile_count / _info / _get, pcm_loam_dynmap_need_load / _load / _crop /
+ *     _crop_batch / _info / _global.
+ *   - pcm_destroy detaches; the memory goes with the last holder, so `src` may be destroyed first.
+ *   - Neither context may be in another call while pcm_loam_tile_share runs.
+ * pcm_loam_tile_share_count: the contexts holding ctx's store (1 = not shared), or a negative pcm_status. */
+int pcm_loam_tile_share(pcm_ctx *dst, pcm_ctx *src);
+int pcm_loam_tile_share_count(pcm_ctx *ctx);
+
+/* pcm_loam_dynmap_crop for n contexts in one round of launches on the stream of ctxs[0]: one upload, four launches, one read-back
+ * and one wait for the whole batch instead of one of each per context.  Context i is cropped at poses6[6 i .. 6 i + 5] with the
+ * one params (NULL = defaults); results[i] is the record a single pcm_loam_dynmap_crop would have written, bit for bit, and so
+ * is the context's target.  The contexts may hold one store, different stores, or a mix; they are distinct and live on one device.
+ * A context whose crop is unchanged reports rebuilt = 0 and takes no part in the launches.  A context that cannot be cropped (no
+ * load yet, a pose that is not finite, a duplicate, another device, more than 2^31 - 1 points selected, no room for its target)
+ * gets its status in results[i].status and is left out; the others run.  Returns the first status that is not PCM_OK (the text
+ * is pcm_last_error(ctxs[0])).  n <= 0 or a null array: PCM_ERR_INVALID_ARGUMENT; more workgroups than one grid holds:
+ * PCM_ERR_OUT_OF_RANGE, nothing done.  A fleet frame is
+ *   pcm_loam_frame_begin_batch -> pcm_loam_dynmap_crop_batch -> pcm_loam_align_batch */
+int pcm_loam_dynmap_crop_batch(pcm_ctx *const *ctxs, int n, const pcm_loam_dynmap_params *params, const float *poses6, pcm_loam_dynmap_crop_result *results);
+
 /*
  * The key-frame map cut into area tiles on the device: what a mapping session leaves a localisation session, with no host copy
  * of the map in between (mapping context -> pcm_loam_tiles_build -> pcm_loam_dynmap_load / _crop -> pcm_loam_align).  The reference

@@ -670,6 +670,33 @@ public:
   int laserCloudCornerFromMapDSNum() const { return crop_.num_corner; }
   int laserCloudSurfFromMapDSNum() const { return crop_.num_surf; }
 
+  // A fleet on one site map: this map reads the areas `other` holds from now on (pcm_loam_tile_share); they exist once on the
+  // device.  load() before the next dynamic_load_map.  While areas are shared, add*Area and buildFromKeyFrames throw on every
+  // holder, and clear() detaches this map alone.
+  void shareTilesWith(LoamDynamicMap& other) { check(pcm_loam_tile_share(ctx_, other.ctx_), "pcm_loam_tile_share"); }
+  int tileShareCount() const {
+    const int rc = pcm_loam_tile_share_count(ctx_);
+    if (rc < 0) check(rc, "pcm_loam_tile_share_count");
+    return rc;
+  }
+  // dynamic_load_map of several maps in one round of launches (pcm_loam_dynmap_crop_batch) with the parameters of maps[0]:
+  // poses holds 6 floats per map; results (may be null) takes one record per map, and each map keeps its own as result().  A map
+  // that could not be cropped carries its code in its record's status while the others complete; returns the first such code.
+  static int cropBatch(const std::vector<LoamDynamicMap*>& maps, const float* poses, pcm_loam_dynmap_crop_result* results = nullptr) {
+    if (maps.empty()) return PCM_ERR_INVALID_ARGUMENT;
+    std::vector<pcm_ctx*> ctxs(maps.size());
+    for (size_t i = 0; i < maps.size(); i++) ctxs[i] = maps[i]->ctx_;
+    std::vector<pcm_loam_dynmap_crop_result> rec(maps.size());
+    const int rc = pcm_loam_dynmap_crop_batch(ctxs.data(), (int)maps.size(), &maps[0]->params_, poses, rec.data());
+    bool any = false;
+    for (size_t i = 0; i < maps.size(); i++) {
+      if (rec[i].status == PCM_OK) maps[i]->crop_ = rec[i]; else any = true;
+      if (results) results[i] = rec[i];
+    }
+    if (rc != PCM_OK && !any) maps[0]->check(rc, "pcm_loam_dynmap_crop_batch");   // the call as a whole failed
+    return rc;
+  }
+
   // The hand-over from a mapping session on the same LoamScanToMap: the key frames of `keyframes` [first, first + n) (n < 0: all
   // from first), cut into area tiles on the device under their current poses (pcm_loam_tiles_build).  Replaces both area lists;
   // the map never visits the host.  params NULL: tile_size 50, leaves 0.2.

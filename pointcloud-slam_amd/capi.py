@@ -28,6 +28,7 @@ SYMBOLS = [
     "pcm_loam_default_dynmap_params", "pcm_loam_tile_add", "pcm_loam_tile_count", "pcm_loam_tile_clear", "pcm_loam_dynmap_need_load",
     "pcm_loam_dynmap_load", "pcm_loam_dynmap_crop", "pcm_loam_dynmap_info", "pcm_loam_dynmap_global",
     "pcm_loam_default_tiles_params", "pcm_loam_tiles_build", "pcm_loam_tile_info", "pcm_loam_tile_get", "pcm_loam_tiles_build_ms",
+    "pcm_loam_tile_share", "pcm_loam_tile_share_count", "pcm_loam_dynmap_crop_batch",
     "pcm_occ_default_params", "pcm_occ_reset", "pcm_occ_insert_scans", "pcm_occ_insert_keyframes", "pcm_occ_get_scan", "pcm_occ_status",
     "pcm_occ_info", "pcm_occ_get_map", "pcm_occ_get_pgm", "pcm_occ_get_counts",
     "pcm_scan_default_fuse_params", "pcm_scan_fuse", "pcm_scan_fused",
@@ -453,6 +454,9 @@ def load_library():
     L.pcm_loam_dynmap_need_load.argtypes = [vp, C.POINTER(PcmLoamDynmapParams), vp]
     L.pcm_loam_dynmap_load.argtypes = [vp, C.POINTER(PcmLoamDynmapParams), vp, C.POINTER(PcmLoamDynmapLoadResult)]
     L.pcm_loam_dynmap_crop.argtypes = [vp, C.POINTER(PcmLoamDynmapParams), vp, C.POINTER(PcmLoamDynmapCropResult)]
+    L.pcm_loam_dynmap_crop_batch.argtypes = [C.POINTER(vp), i32, C.POINTER(PcmLoamDynmapParams), vp, C.POINTER(PcmLoamDynmapCropResult)]
+    L.pcm_loam_tile_share.argtypes = [vp, vp]
+    L.pcm_loam_tile_share_count.argtypes = [vp]
     L.pcm_loam_dynmap_info.argtypes = [vp] * 5
     L.pcm_loam_dynmap_global.argtypes = [vp, vp, sz, C.POINTER(sz), i32]
     L.pcm_loam_default_tiles_params.argtypes = [C.POINTER(PcmLoamTilesParams)]

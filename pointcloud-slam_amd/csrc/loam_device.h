@@ -110,7 +110,10 @@ void loam_export_waited(pcm_ctx* c);
 // points, which are cells [first, first + n) of its list's cloud.  loam_tiles_replace empties both lists and the selection as
 // pcm_loam_tile_clear does and stores the new tiles; the clouds (device memory, n_cells[m] points) are copied into the arenas on the
 // context's stream, device to device, and may be released in stream order on return.  A failure leaves the store as it was.
+// loam_tiles_writable: PCM_OK when the context is the only holder of its tile store, else PCM_ERR_UNSUPPORTED with a text that names
+// `call` (pcm_loam_tile_share; a shared store is immutable).  The builder asks before any device work; loam_tiles_replace asks again.
 struct BuiltTile { double box[6]; int32_t ix, iy; uint32_t first, n; };
+int loam_tiles_writable(pcm_ctx* c, const char* call);
 int loam_tiles_replace(pcm_ctx* c, const BuiltTile* const tiles[2], const size_t n_tiles[2], const float4* const cells[2], const size_t n_cells[2]);
 
 // loam_features.hip: the context's last front-end features.  gen: bumps whenever the output array is rewritten

@@ -16,6 +16,8 @@
 
 #include <vector>
 
+#include "target_share.h"
+
 #if defined(__HIPCC__)
 #define PCM_DM_HD __host__ __device__
 #else
@@ -95,6 +97,101 @@ PCM_DM_HD inline int crop_class(float x, float y, float z, const CropWindow& w) 
   if (!(w.y_lo <= y && y <= w.y_hi)) return 0;
   if (w.crop_x && !(w.x_lo <= x && x <= w.x_hi)) return 0;
   return 1;
+}
+
+// ---- one tile store for several contexts -------------------------------------------------------------------
+// What a context keeps of the localisation map for itself: the selection of its last load and whether its last crop still stands.
+// Each robot has its own pose, so this is never shared.
+struct TileSelection {
+  bool loaded = false;
+  std::vector<int32_t> sel[2];
+  uint64_t sel_gen = 0;
+  float last_load[6] = {kNeverLoaded, kNeverLoaded, kNeverLoaded, kNeverLoaded, kNeverLoaded, kNeverLoaded};
+  bool last_valid = false;   // the record of the last crop is current
+  // back to "never loaded"; the generation moves on, so a crop record of the old selection can never match again
+  void reset() {
+    sel[0].clear(); sel[1].clear();
+    loaded = false;
+    sel_gen++;
+    last_valid = false;
+    for (int k = 0; k < 6; k++) last_load[k] = kNeverLoaded;
+  }
+};
+
+// A context's reference to a tile store (the tile tables and the two arenas: Store) and its selection.  The rules are those of
+// target_share.h: a store with more than one holder is immutable (writable() first), share_from / clear_or_detach / let_go change
+// this holder alone, and the last holder to go runs the hook (device current, its stream drained) before the store is freed.
+// tests/tile_share_check.cpp walks through them on the host.
+template <class Store>
+struct TileHolder {
+  SharedTarget<Store> ts;
+  TileSelection s;
+  TileHolder() { (void)ts.create(); }   // an empty reference after a failed allocation: ready() says so
+  bool ready() { return !ts.empty() || ts.create(); }
+  int holders() const { return ts.holders(); }
+  bool writable() const { return ts.mutable_by_me(); }
+  // pcm_loam_tile_share: lets go of the store it had and holds src's; the selection starts over (the caller has drained both streams)
+  template <class Hook>
+  void share_from(const TileHolder& src, Hook&& before_free) {
+    if (!ts.same_as(src.ts)) ts.attach(src.ts, std::forward<Hook>(before_free));
+    s.reset();
+  }
+  // pcm_loam_tile_clear: the sole holder empties its store (empty_store(Store&)), a sharer detaches and goes on with an empty store
+  // of its own; false: out of host memory, nothing changed
+  template <class Hook, class Empty>
+  bool clear_or_detach(Hook&& before_free, Empty&& empty_store) {
+    if (ts.shared()) {
+      if (!ts.renew(std::forward<Hook>(before_free))) return false;
+    } else {
+      empty_store(*ts);
+    }
+    s.reset();
+    return true;
+  }
+  template <class Hook>
+  void let_go(Hook&& before_free) { ts.detach(std::forward<Hook>(before_free)); }
+};
+
+// ---- the layout of a batched crop (pcm_loam_dynmap_crop_batch) --------------------------------------------------------------------
+constexpr uint32_t kDmBlock = 256;   // points per workgroup of k_dm_count / k_dm_scatter
+constexpr uint32_t kDmChunk = 256;   // workgroup counts per scan block
+
+// Context i of a batch runs nb[i] workgroups.  The workgroups of all contexts form one 1-D grid, context after context; every
+// context owns a slice of the count array padded to whole scan blocks, so that the chunk scan runs over the concatenation and no scan
+// block straddles two contexts.  A context without workgroups owns no slot and no chunk.
+struct BatchSlice {
+  uint32_t block0;   // its first workgroup in the grid
+  uint32_t slot0;    // its first count slot (= chunk0 * kDmChunk)
+  uint32_t chunk0;   // its first scan block
+  uint32_t nchunks;  // ceil(nb / kDmChunk)
+};
+struct BatchLayout {
+  uint32_t blocks = 0, slots = 0, chunks = 0;
+};
+// false: the grid or the count array does not fit 31 bits (a 1-D grid holds 2^31 - 1 workgroups)
+inline bool batch_layout(const uint32_t* nb, int n, BatchSlice* out, BatchLayout* total) {
+  uint64_t blocks = 0, chunks = 0;
+  for (int i = 0; i < n; i++) {
+    const uint64_t c = ((uint64_t)nb[i] + kDmChunk - 1) / kDmChunk;
+    if (blocks > 0x7fffffffull || chunks * kDmChunk > 0x7fffffffull) return false;
+    out[i] = BatchSlice{(uint32_t)blocks, (uint32_t)(chunks * kDmChunk), (uint32_t)chunks, (uint32_t)c};
+    blocks += nb[i];
+    chunks += c;
+  }
+  if (blocks > 0x7fffffffull || chunks * kDmChunk > 0x7fffffffull) return false;
+  total->blocks = (uint32_t)blocks; total->slots = (uint32_t)(chunks * kDmChunk); total->chunks = (uint32_t)chunks;
+  return true;
+}
+// workgroup b of the grid -> its context: the last i with block0[i] <= b (block0: n ascending first workgroups, n >= 1, b below
+// the grid size).  A context without workgroups shares its block0 with the next one and is never the last.  The trip count depends
+// on n alone, and b is the same in every lane of a workgroup, so the result is uniform.
+PCM_DM_HD inline uint32_t batch_context_of(const uint32_t* block0, uint32_t n, uint32_t b) {
+  uint32_t lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (block0[mid] <= b) lo = mid; else hi = mid;
+  }
+  return lo;
 }
 
 }  // namespace loam

@@ -384,6 +384,7 @@ int run_build(pcm_ctx* c, DevScratch& sc, ListJob (&job)[2], StageClock (&clk)[2
 int build(pcm_ctx* c, const pcm_loam_tiles_params* params, int first, int n, pcm_loam_tiles_result* result, float* stage_ms) {
   int rc = loam_check_ctx(c, PCM_ERR_INVALID_ARGUMENT, "pcm_loam_tiles_build needs a context created with PCM_MODEL_LOAM");
   if (rc != PCM_OK) return rc;
+  if ((rc = loam_tiles_writable(c, "pcm_loam_tiles_build")) != PCM_OK) return rc;   // a shared store: refused before any device work
   pcm_loam_tiles_params p;
   if (params) p = *params; else pcm_loam_default_tiles_params(&p);
   if ((rc = check_tparams(c, p)) != PCM_OK) return rc;

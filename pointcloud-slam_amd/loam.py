@@ -533,6 +533,48 @@ class LoamTilesResult:
 _TILE_LIST = {0: 0, 1: 1, "corner": 0, "surf": 1}
 
 
+def _crop_result(r: capi.PcmLoamDynmapCropResult) -> LoamMapCropResult:
+    return LoamMapCropResult(r.num_corner_in, r.num_surf_in, r.num_corner, r.num_surf, r.num_nonfinite, bool(r.rebuilt), np.float32(r.x_lo),
+                             np.float32(r.x_hi), np.float32(r.y_lo), np.float32(r.y_hi), r.status)
+
+
+def loam_share_tiles(reg, other):
+    """``reg`` reads the tile store ``other`` holds from now on (pcm_loam_tile_share): the tiles exist once on the device however many
+    LoamRegistration objects hold them.  ``reg``'s selection starts over: ``load_map`` before its next ``crop_map``.  While a store is
+    shared, ``add_tile`` and ``build_tiles`` on any holder raise PcmError (UNSUPPORTED); ``clear_tiles`` detaches that object alone."""
+    reg._check(reg._L.pcm_loam_tile_share(reg.handle, other.handle))
+    reg._dm_load = reg._dm_crop = None
+    reg._tile_size = getattr(other, "_tile_size", None)
+
+
+def loam_tile_share_count(reg) -> int:
+    """LoamRegistration objects holding ``reg``'s tile store (1 = not shared) (pcm_loam_tile_share_count)."""
+    n = reg._L.pcm_loam_tile_share_count(reg.handle)
+    if n < 0:
+        reg._check(n)
+    return n
+
+
+def loam_crop_map_batch(regs, poses6, **params):
+    """crop_map of several LoamRegistration objects in one round of launches (pcm_loam_dynmap_crop_batch): object i is cropped at
+    poses6[i]; its target and its LoamMapCropResult are those of a single ``crop_map``, bit for bit.  The objects may share one tile
+    store (``loam_share_tiles``) or hold their own.  An object that cannot be cropped carries its code in ``status`` while the others
+    complete; PcmError when the call as a whole fails."""
+    L = capi.load_library()
+    n = len(regs)
+    p = fill_params(capi.PcmLoamDynmapParams, L.pcm_loam_default_dynmap_params, params)
+    x = np.ascontiguousarray(poses6, dtype=np.float32).reshape(n, 6)
+    arr = (C.c_void_p * n)(*[r.handle for r in regs])
+    out = (capi.PcmLoamDynmapCropResult * n)()
+    rc = L.pcm_loam_dynmap_crop_batch(arr, n, C.byref(p), x.ctypes.data, out)
+    if rc != capi.PCM_OK and all(out[i].status == capi.PCM_OK for i in range(n)):
+        raise capi.PcmError(rc, (L.pcm_last_error(regs[0].handle) or b"").decode())
+    for i, reg in enumerate(regs):
+        if out[i].status == capi.PCM_OK:
+            reg._dm_crop = capi.PcmLoamDynmapCropResult.from_buffer_copy(out[i])
+    return [_crop_result(out[i]) for i in range(n)]
+
+
 def write_arealist(path, areas):
     """dynamic_map.h:90-106: one line per area, ``path,x_min,y_min,z_min,x_max,y_max,z_max``, the numbers as std::to_string writes
     doubles (``%f``: 6 decimals).  areas: (path, (6 numbers)) pairs."""
@@ -661,8 +703,7 @@ class _LocalisationTiles:
         r = capi.PcmLoamDynmapCropResult()
         self._check(self._L.pcm_loam_dynmap_crop(self._h, C.byref(p), x.ctypes.data, C.byref(r)))
         self._dm_crop = r
-        return LoamMapCropResult(r.num_corner_in, r.num_surf_in, r.num_corner, r.num_surf, r.num_nonfinite, bool(r.rebuilt), np.float32(r.x_lo),
-                                 np.float32(r.x_hi), np.float32(r.y_lo), np.float32(r.y_hi), r.status)
+        return _crop_result(r)
 
     def dynmap_info(self) -> dict:
         """Parity hook: the selected tile indices of both lists and, after crop_map, the two cropped clouds (pcm_loam_dynmap_info)."""
