@@ -664,6 +664,7 @@ int pcm_loam_neighbours(pcm_ctx *ctx, const float x6[6], int32_t *corner_nn, int
  * by default); a point with a non-finite coordinate is skipped; the timestamp is never read (the reference's deskew is the
  * identity as written).  The context keeps the nodes' cross-frame arrays (zero at creation), so a stream of
  * frames through one context reproduces the nodes frame for frame.  Needs a PCM_MODEL_LOAM context.
+ * The *_deskew entry points below take IMU / odometry tables and run the live deskewPoint in front of the features.
  */
 #define PCM_LOAM_FEATURES_FORCE_SERIAL_SORT 1u   /* flags: every sector through the serial std::sort restatement (tests) */
 
@@ -718,6 +719,88 @@ int pcm_loam_frame_begin_batch(pcm_ctx *const *ctxs, int n, const void *const *p
  * 4 floats per point.  Any pointer may be NULL. */
 int pcm_loam_feature_info(pcm_ctx *ctx, int32_t counts[4], int32_t *start_ring, int32_t *end_ring, int32_t *col_ind, float *range, float *cloud,
                           float *curvature, int32_t *neighbor_picked, int32_t *label, float *corner_scan, float *surf_scan);
+
+/*
+ * IMU / odometry deskew in front of the LOAM features (an option of this library, off by default).
+ * imageProjection.cpp:709 hands findRotation / findPosition a relative point time, so the reference's deskewPoint is the identity
+ * as written; new_localization.cpp:1948-1977 holds the live form, pointTime = timeScanCur + relTime, which these entry points run:
+ * pointTime = time_scan_cur + (t_i - t_0), t_0 the stamp of record 0 of the input, the difference in the field's type.  The column,
+ * the raw range test and the ownership of a cell stay the raw point's; the stored point and its range (and through it smoothness,
+ * occlusion and the features) are the deskewed point's (imageProjection.cpp:760-782).  transStartInverse comes from the first
+ * record that passes the ring, column and range tests (firstPointFlag).  pcm_loam_feature_info then returns cloud_deskewed.
+ *
+ * A table is n entries in arrival order (the times need not increase; the look-up is findRotation's linear scan, served by a
+ * binary search over the prefix maximum of the times): at most 1024 (PCM_ERR_UNSUPPORTED beyond; the reference's arrays hold
+ * imuFrequency = 500 and overflow).  n_odom = 0: no odometry table, the translation is 0.  A NULL descriptor or imu_available = 0
+ * is the call without _deskew, bit for bit.  A time field past the record, or one that is not aligned to its size in every record
+ * (device records are read where they lie): PCM_ERR_INVALID_ARGUMENT before any device work.
+ */
+#define PCM_LOAM_TIME_DOUBLE 0   /* PointXYZIRT's `double timestamp` (offset 24 of the 48-byte record) */
+#define PCM_LOAM_TIME_FLOAT 1    /* the 32-byte fused XYZIRT record's float (pcm_scan_fuse, PCM_SCAN_OUT_XYZIRT) */
+#define PCM_LOAM_DESKEW_READY 0
+#define PCM_LOAM_DESKEW_WAITING 1   /* deskewInfo's "Waiting for IMU data ...": not an error, nothing popped or written */
+
+typedef struct pcm_loam_deskew {
+  double time_scan_cur;          /* timeScanCur: the header stamp of the scan */
+  const double *imu_time;        /* imuTime, imuRotX / Y / Z: n_imu host doubles each */
+  const double *imu_rot_x;
+  const double *imu_rot_y;
+  const double *imu_rot_z;
+  const double *odom_time;       /* odomTime, odomIncreX / Y / Z: n_odom host doubles each (NULL with n_odom = 0) */
+  const double *odom_incre_x;
+  const double *odom_incre_y;
+  const double *odom_incre_z;
+  int32_t n_imu;                 /* imuPointerCur + 1 */
+  int32_t n_odom;                /* OdomPointerCur + 1, or 0 */
+  int32_t imu_available;         /* cloudInfo.imuAvailable; 0: the points stay as they are */
+  int32_t time_kind;             /* PCM_LOAM_TIME_* of the field at time_offset_bytes */
+  size_t time_offset_bytes;
+  int32_t reserved[8];
+} pcm_loam_deskew;
+
+typedef struct pcm_loam_imu_sample { double t, gyro[3]; } pcm_loam_imu_sample;     /* sensor_msgs::Imu through imuConverter: stamp, angular_velocity */
+typedef struct pcm_loam_odom_sample { double t, xyz[3]; } pcm_loam_odom_sample;   /* nav_msgs::Odometry: stamp, pose.pose.position */
+
+typedef struct pcm_loam_deskew_input {
+  double time_scan_cur;          /* timeScanCur */
+  double time_scan_next;         /* timeScanNext (imageProjection.cpp: the `back < timeScanNext` gate and the `> timeScanNext + 0.01` break);
+                                  * +inf: new_localization.cpp's form, neither */
+  const pcm_loam_imu_sample *imu;     /* imuQueue, front first */
+  const pcm_loam_odom_sample *odom;   /* odomQueue, front first */
+  int32_t n_imu;
+  int32_t n_odom;
+  int32_t reserved[4];
+} pcm_loam_deskew_input;
+
+typedef struct pcm_loam_deskew_result {
+  int32_t status;                /* PCM_LOAM_DESKEW_READY or PCM_LOAM_DESKEW_WAITING */
+  int32_t imu_skipped;           /* samples older than timeScanCur - 0.01 at the front of each queue: the reference pops them, the caller */
+  int32_t odom_skipped;          /*   pops as many from its own */
+  int32_t n_imu;                 /* table entries written */
+  int32_t n_odom;
+  int32_t imu_available;         /* cloudInfo.imuAvailable */
+  int32_t odom_available;        /* cloudInfo.odomAvailable */
+  int32_t odom_deskew;           /* odomDeskewFlag */
+  int32_t start_odom_index;      /* startOdomMsg as an index into `odom` as given (initialGuess* are the caller's: getRPY is not here); -1: none */
+  int32_t reserved[7];
+} pcm_loam_deskew_result;
+
+/* deskewInfo = the gate, imuDeskewInfo, odomDeskewInfo (imageProjection.cpp:483-642, new_localization.cpp:1733-1886); no context.
+ * imu_table / odom_table: four rows of cap_imu / cap_odom doubles (time, x, y, z), written up to the counts of *res; a capacity
+ * below a count: PCM_ERR_INVALID_ARGUMENT with the counts in *res; more than 1024 entries: PCM_ERR_UNSUPPORTED.  deskew (may be
+ * NULL) is filled to point at the two tables, with time_offset_bytes = 24 and PCM_LOAM_TIME_DOUBLE (PointXYZIRT). */
+int pcm_loam_deskew_tables(const pcm_loam_deskew_input *in, double *imu_table, size_t cap_imu, double *odom_table, size_t cap_odom, pcm_loam_deskew *deskew,
+                           pcm_loam_deskew_result *res);
+/* pcm_loam_extract_features / pcm_loam_frame_begin / pcm_loam_frame_begin_batch with the deskew in front; deskew NULL = those calls.
+ * The batch takes NULL or one descriptor per frame, any of which may be NULL. */
+int pcm_loam_extract_features_deskew(pcm_ctx *ctx, const void *points, size_t n, size_t stride_bytes, size_t intensity_offset_bytes, size_t ring_offset_bytes,
+                                     int memory, const pcm_loam_feature_params *params, float *corner, size_t cap_corner, float *surf, size_t cap_surf,
+                                     pcm_loam_features_result *res, const pcm_loam_deskew *deskew);
+int pcm_loam_frame_begin_deskew(pcm_ctx *ctx, const void *points, size_t n, size_t stride_bytes, size_t intensity_offset_bytes, size_t ring_offset_bytes,
+                                int memory, const pcm_loam_feature_params *params, pcm_loam_features_result *res, const pcm_loam_deskew *deskew);
+int pcm_loam_frame_begin_batch_deskew(pcm_ctx *const *ctxs, int n, const void *const *points, const size_t *n_points, size_t stride_bytes,
+                                      size_t intensity_offset_bytes, size_t ring_offset_bytes, int memory, const pcm_loam_feature_params *params,
+                                      pcm_loam_features_result *results, const pcm_loam_deskew *const *deskew);
 
 /*
  * LOAM key-frame store and surrounding-key-frame submap of jueying_slam on the device: saveKeyFramesAndFactor's clouds

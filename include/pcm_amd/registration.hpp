@@ -400,12 +400,13 @@ public:
   // imageProjection + featureExtraction + downsampleCurrentScan of one ring-tagged scan (PointXYZIRT-like: x y z, intensity, ring
   // members) into the features on the device (pcm_loam_frame_begin).  The context keeps the nodes'
   // cross-frame state.  fp: the feature parameters (default: utility.h's), e.g. LoamFeatureExtraction::params().
+  // deskew: LoamFeatureExtraction::deskewInfo's descriptor with its time field set (NULL: the points stay as they are).
   template <typename PointIn>
-  void setInputScan(const std::shared_ptr<const pcl::PointCloud<PointIn>>& scan, const pcm_loam_feature_params* fp = nullptr) {
+  void setInputScan(const std::shared_ptr<const pcl::PointCloud<PointIn>>& scan, const pcm_loam_feature_params* fp = nullptr, const pcm_loam_deskew* deskew = nullptr) {
     const PointIn probe{};
     const char* base = reinterpret_cast<const char*>(&probe);
     const size_t ioff = (size_t)(reinterpret_cast<const char*>(&probe.intensity) - base), roff = (size_t)(reinterpret_cast<const char*>(&probe.ring) - base);
-    check(pcm_loam_frame_begin(ctx_, scan->points.data(), scan->size(), sizeof(PointIn), ioff, roff, PCM_MEM_HOST, fp, &features_),
+    check(pcm_loam_frame_begin_deskew(ctx_, scan->points.data(), scan->size(), sizeof(PointIn), ioff, roff, PCM_MEM_HOST, fp, &features_, deskew),
           "pcm_loam_frame_begin");
   }
   // the same for ring-tagged records that already lie in device memory (ScanFusion::fuseToFrontEnd)
@@ -939,6 +940,23 @@ private:
 // device, for callers that want the features on the host.  PointIn: the driver's ring-tagged point (members x y z, intensity as
 // uint8, ring as uint16, e.g. imageProjection.cpp's PointXYZIRT); PointOut: PointType (x y z intensity).  One object per node: it
 // holds the nodes' cross-frame arrays.  The setters are named after ParamServer's members (utility.h:223-272).
+// With IMU / odometry queues the scan is motion-compensated first (an option of this library: the reference's deskewPoint is the
+// identity as written).  cloudHandler's order (imageProjection.cpp:238-262):
+//     if (!cachePointCloud(msg)) return;                                              // the caller's: timeScanCur, timeScanNext
+//     pcm_amd::LoamDeskewTables tables;
+//     if (!fe.deskewInfo(timeScanCur, timeScanNext, imu.data(), imu.size(), odom.data(), odom.size(), &tables)) return;   // "Waiting for IMU data ..."
+//     imu.erase(imu.begin(), imu.begin() + tables.info.imu_skipped);                  // the pops of imuDeskewInfo / odomDeskewInfo
+//     odom.erase(odom.begin(), odom.begin() + tables.info.odom_skipped);
+//     fe.setDeskew(tables, offsetof(PointXYZIRT, timestamp));
+//     fe.extract(laserCloudIn, corner, surf);                                         // projectPointCloud with the live deskewPoint, ...
+//     fe.clearDeskew();                                                               // resetParameters
+// imuRollInit / initialGuess* need tf's getRPY and stay with the caller (tables.info.start_odom_index names startOdomMsg).
+struct LoamDeskewTables {
+  std::vector<double> imu, odom;     // four rows each: time, x, y, z
+  pcm_loam_deskew desc{};            // points into imu / odom
+  pcm_loam_deskew_result info{};
+};
+
 template <typename PointIn, typename PointOut = pcl::PointXYZI>
 class LoamFeatureExtraction {
 public:
@@ -971,7 +989,33 @@ public:
   const pcm_loam_feature_params& params() const { return params_; }
   const pcm_loam_features_result& result() const { return last_; }
 
-  // laserCloudCornerLastDS / laserCloudSurfLastDS of one scan (pcm_loam_extract_features)
+  // deskewInfo (imageProjection.cpp:483-642; timeScanNext = +inf: new_localization.cpp:1733-1886): false while waiting for IMU data
+  static bool deskewInfo(double timeScanCur, double timeScanNext, const pcm_loam_imu_sample* imu, size_t nImu, const pcm_loam_odom_sample* odom, size_t nOdom,
+                         LoamDeskewTables* out) {
+    pcm_loam_deskew_input in{};
+    in.time_scan_cur = timeScanCur; in.time_scan_next = timeScanNext;
+    in.imu = imu; in.odom = odom; in.n_imu = (int32_t)nImu; in.n_odom = (int32_t)nOdom;
+    const size_t ci = nImu < 1 ? 1 : nImu > 1024 ? 1024 : nImu, co = nOdom < 1 ? 1 : nOdom > 1024 ? 1024 : nOdom;
+    out->imu.assign(4 * ci, 0.0);
+    out->odom.assign(4 * co, 0.0);
+    const int rc = pcm_loam_deskew_tables(&in, out->imu.data(), ci, out->odom.data(), co, &out->desc, &out->info);
+    if (rc != PCM_OK) throw std::runtime_error(rc == PCM_ERR_UNSUPPORTED ? "pcm_loam_deskew_tables: more than 1024 table entries" : "pcm_loam_deskew_tables: bad input");
+    return out->info.status == PCM_LOAM_DESKEW_READY;
+  }
+  // the tables of the next extract() calls; timeOffset / timeKind: where a point's stamp lies (PCM_LOAM_TIME_*)
+  void setDeskew(const LoamDeskewTables& t, size_t timeOffset, int timeKind = PCM_LOAM_TIME_DOUBLE) {
+    deskew_ = t;
+    const size_t ci = deskew_.imu.size() / 4, co = deskew_.odom.size() / 4;
+    pcm_loam_deskew& d = deskew_.desc;
+    if (d.n_imu) { d.imu_time = deskew_.imu.data(); d.imu_rot_x = d.imu_time + ci; d.imu_rot_y = d.imu_time + 2 * ci; d.imu_rot_z = d.imu_time + 3 * ci; }
+    if (d.n_odom) { d.odom_time = deskew_.odom.data(); d.odom_incre_x = d.odom_time + co; d.odom_incre_y = d.odom_time + 2 * co; d.odom_incre_z = d.odom_time + 3 * co; }
+    d.time_offset_bytes = timeOffset;
+    d.time_kind = timeKind;
+    have_deskew_ = true;
+  }
+  void clearDeskew() { have_deskew_ = false; }
+
+  // laserCloudCornerLastDS / laserCloudSurfLastDS of one scan (pcm_loam_extract_features[_deskew])
   void extract(const std::shared_ptr<const CloudIn>& scan, CloudOut& cornerOut, CloudOut& surfOut) {
     const PointIn probe{};
     const char* base = reinterpret_cast<const char*>(&probe);
@@ -979,8 +1023,8 @@ public:
     const size_t cap = scan->size() ? scan->size() : 1;   // both outputs hold at most one feature per input point
     corner_.resize(4 * cap);
     surf_.resize(4 * cap);
-    const int rc = pcm_loam_extract_features(ctx_, scan->points.data(), scan->size(), sizeof(PointIn), ioff, roff, PCM_MEM_HOST, &params_,
-                                             corner_.data(), cap, surf_.data(), cap, &last_);
+    const int rc = pcm_loam_extract_features_deskew(ctx_, scan->points.data(), scan->size(), sizeof(PointIn), ioff, roff, PCM_MEM_HOST, &params_,
+                                                    corner_.data(), cap, surf_.data(), cap, &last_, have_deskew_ ? &deskew_.desc : nullptr);
     if (rc != PCM_OK) throw std::runtime_error(std::string("pcm_loam_extract_features: ") + pcm_last_error(ctx_));
     fill(corner_, (size_t)last_.num_corner, cornerOut);
     fill(surf_, (size_t)last_.num_surf, surfOut);
@@ -998,6 +1042,8 @@ private:
   pcm_loam_feature_params params_;
   pcm_loam_features_result last_{};
   std::vector<float> corner_, surf_;
+  LoamDeskewTables deskew_;
+  bool have_deskew_ = false;
 };
 
 // jueying_slam's fusion_lidar_camera node (src/tool/integrate_points/src/fusion_lidar_camera.cpp) on the device: the node's

@@ -19,6 +19,7 @@ SYMBOLS = [
     "pcm_loam_coefficients", "pcm_loam_neighbours",
     "pcm_loam_default_feature_params", "pcm_loam_extract_features", "pcm_loam_frame_begin", "pcm_loam_frame_begin_batch",
     "pcm_loam_feature_info",
+    "pcm_loam_deskew_tables", "pcm_loam_extract_features_deskew", "pcm_loam_frame_begin_deskew", "pcm_loam_frame_begin_batch_deskew",
     "pcm_loam_default_submap_params", "pcm_loam_keyframe_add", "pcm_loam_keyframe_set_poses", "pcm_loam_keyframe_count", "pcm_loam_keyframe_clear",
     "pcm_loam_keyframe_get", "pcm_loam_submap_update", "pcm_loam_submap_near", "pcm_loam_submap_info",
     "pcm_loam_default_sc_params", "pcm_loam_sc_add", "pcm_loam_sc_put", "pcm_loam_sc_get", "pcm_loam_sc_count", "pcm_loam_sc_shape", "pcm_loam_sc_clear",
@@ -54,6 +55,7 @@ PCM_FLAG_REFERENCE_KNN_ORDER = 32      # neighbours in the order of libstdc++'s 
 PCM_FLAG_LIO_REFERENCE_SEMANTICS = 4   # pcm_obs_model keeps LaserMapping's per-point members across calls and scans
 PCM_ERR_INVALID_ARGUMENT = -1
 PCM_ERR_NO_INPUT = -2
+PCM_ERR_UNSUPPORTED = -4
 PCM_ERR_OUT_OF_RANGE = -5
 PCM_ERR_NOT_CONVERGED = -6
 PCM_ERR_INTERNAL = -7
@@ -168,6 +170,36 @@ class PcmLoamFeaturesResult(C.Structure):
     _fields_ = [("num_extracted", C.c_int32), ("num_corner_scan", C.c_int32), ("num_surf_scan", C.c_int32), ("num_corner", C.c_int32),
                 ("num_surf", C.c_int32), ("sectors", C.c_int32), ("sectors_serial", C.c_int32), ("status", C.c_int32),
                 ("reserved", C.c_int32 * 8)]
+
+
+PCM_LOAM_TIME_DOUBLE, PCM_LOAM_TIME_FLOAT = 0, 1
+PCM_LOAM_DESKEW_READY, PCM_LOAM_DESKEW_WAITING = 0, 1
+
+
+class PcmLoamDeskew(C.Structure):
+    _fields_ = [("time_scan_cur", C.c_double), ("imu_time", C.c_void_p), ("imu_rot_x", C.c_void_p), ("imu_rot_y", C.c_void_p), ("imu_rot_z", C.c_void_p),
+                ("odom_time", C.c_void_p), ("odom_incre_x", C.c_void_p), ("odom_incre_y", C.c_void_p), ("odom_incre_z", C.c_void_p),
+                ("n_imu", C.c_int32), ("n_odom", C.c_int32), ("imu_available", C.c_int32), ("time_kind", C.c_int32),
+                ("time_offset_bytes", C.c_size_t), ("reserved", C.c_int32 * 8)]
+
+
+class PcmLoamImuSample(C.Structure):   # sensor_msgs::Imu through imuConverter: stamp, angular_velocity
+    _fields_ = [("t", C.c_double), ("gyro", C.c_double * 3)]
+
+
+class PcmLoamOdomSample(C.Structure):   # nav_msgs::Odometry: stamp, pose.pose.position
+    _fields_ = [("t", C.c_double), ("xyz", C.c_double * 3)]
+
+
+class PcmLoamDeskewInput(C.Structure):
+    _fields_ = [("time_scan_cur", C.c_double), ("time_scan_next", C.c_double), ("imu", C.c_void_p), ("odom", C.c_void_p),
+                ("n_imu", C.c_int32), ("n_odom", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class PcmLoamDeskewResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("imu_skipped", C.c_int32), ("odom_skipped", C.c_int32), ("n_imu", C.c_int32), ("n_odom", C.c_int32),
+                ("imu_available", C.c_int32), ("odom_available", C.c_int32), ("odom_deskew", C.c_int32), ("start_odom_index", C.c_int32),
+                ("reserved", C.c_int32 * 7)]
 
 
 class PcmLoamSubmapParams(C.Structure):
@@ -412,6 +444,10 @@ def load_library():
     L.pcm_loam_frame_begin_batch.argtypes = [C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(sz), sz, sz, sz, i32, C.POINTER(PcmLoamFeatureParams),
                                              C.POINTER(PcmLoamFeaturesResult)]
     L.pcm_loam_feature_info.argtypes = [vp] * 12
+    L.pcm_loam_deskew_tables.argtypes = [C.POINTER(PcmLoamDeskewInput), vp, sz, vp, sz, C.POINTER(PcmLoamDeskew), C.POINTER(PcmLoamDeskewResult)]
+    L.pcm_loam_extract_features_deskew.argtypes = L.pcm_loam_extract_features.argtypes + [C.POINTER(PcmLoamDeskew)]
+    L.pcm_loam_frame_begin_deskew.argtypes = L.pcm_loam_frame_begin.argtypes + [C.POINTER(PcmLoamDeskew)]
+    L.pcm_loam_frame_begin_batch_deskew.argtypes = L.pcm_loam_frame_begin_batch.argtypes + [C.POINTER(C.POINTER(PcmLoamDeskew))]
     L.pcm_loam_default_submap_params.argtypes = [C.POINTER(PcmLoamSubmapParams)]
     L.pcm_loam_default_submap_params.restype = None
     L.pcm_loam_keyframe_add.argtypes = [vp, vp, C.c_double, vp, sz, vp, sz, sz, i32]

@@ -6,6 +6,8 @@
 // Reference: jueying_slam/src/imageProjection.cpp:736-823, featureExtraction.cpp:84-247,
 // mapOptmization.cpp:1232-1247.  Deskew (imageProjection.cpp:704-733) is the identity as written (relative point time compared
 // against absolute IMU / odometry stamps, :535/:548/:624/:632/:777): no IMU input, the timestamp field is never read.
+// The *_deskew entry points run the live form instead (new_localization.cpp:1948-1977, loam_deskew.h):
+// the <true> instantiations of k_lf_clear / k_lf_project / k_lf_extract and k_lf_dk_start between the last two.
 //
 // Launches of one batch (grid.y = frame), all on the stream of the first context, one read-back at the end:
 //   k_lf_clear, k_lf_project (atomicMin cell owner = first point wins), k_lf_rowcount, k_lf_rings (ring prefix, start/end),
@@ -14,6 +16,7 @@
 //   k_lf_corner_compact, segmented VoxelGrid stage 1 (per ring, odometry leaf), stage 2 (corner / surf, mapping leaves), k_lf_finish.
 #include "host_util.h"
 #include "intro_sort.h"
+#include "loam_deskew.h"
 #include "loam_device.h"
 #include "pre_layouts.h"
 #include "voxel_grid.h"
@@ -44,6 +47,17 @@ struct LfInfo {
   uint32_t first2;         // first stage-2 cell of the frame
 };
 
+// deskew of one frame (pcm_loam_deskew on the device); enabled == 0: the frame's points stay as they are
+struct LfDeskew {
+  loam::DeskewTable imu, odo;   // odo.n == 0: no odometry table
+  double time_scan_cur;
+  uint32_t toff;           // offset of the time field in a record
+  int32_t tkind;           // PCM_LOAM_TIME_*
+  int32_t enabled;
+  uint32_t* first;         // smallest record index that passed the ring, column and range tests (0xffffffff: none)
+  float* start_inv;        // transStartInverse, 12 floats
+};
+
 struct LfFrame {
   const char* pts;         // input records (device)
   uint32_t n, stride, ioff, roff;
@@ -57,6 +71,7 @@ struct LfFrame {
   // batch scratch
   uint32_t* owner; uint32_t* rowcnt; uint32_t* roff_arr; int32_t* member; int32_t* cpick; int32_t* ccnt;
   LfInfo* info;
+  LfDeskew dk;
 };
 
 struct LfParams {
@@ -73,11 +88,13 @@ __device__ inline uint32_t cap_of(const LfParams& p) { return (uint32_t)p.n_scan
 // ---------------------------------------------------------------------------------------------------------------------------
 // projection (imageProjection.cpp:736-797)
 // ---------------------------------------------------------------------------------------------------------------------------
+template <bool kDeskew>
 __global__ void k_lf_clear(const LfFrame* __restrict__ fr, LfParams p) {
   const LfFrame& F = fr[blockIdx.y];
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < cap_of(p)) F.owner[i] = 0xffffffffu;
   if (i < (uint32_t)p.n_scan) { F.rowcnt[i] = 0u; F.ccnt[i] = 0; }
+  if (kDeskew && i == 0 && F.dk.enabled) *F.dk.first = 0xffffffffu;
   if (i == 0) {
     LfInfo z;
     memset(&z, 0, sizeof(z));
@@ -108,13 +125,45 @@ __device__ inline bool project_point(const LfFrame& F, const LfParams& p, uint32
   return true;
 }
 
+// kDeskew: the smallest passing record index of the frame as well (one atomicMin per wave).  It owns its cell, so it is the first
+// point that reaches deskewPoint (firstPointFlag, new_localization.cpp:1961-1965).
+template <bool kDeskew>
 __global__ void k_lf_project(const LfFrame* __restrict__ fr, LfParams p) {
   const LfFrame& F = fr[blockIdx.y];
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= F.n) return;
   Proj q;
-  if (!project_point(F, p, i, &q, nullptr)) return;
-  atomicMin(&F.owner[(uint32_t)q.row * (uint32_t)p.H + (uint32_t)q.col], i);   // rangeMat != FLT_MAX -> skip (:774): first point wins
+  const bool ok = i < F.n && project_point(F, p, i, &q, nullptr);
+  if (ok) atomicMin(&F.owner[(uint32_t)q.row * (uint32_t)p.H + (uint32_t)q.col], i);   // rangeMat != FLT_MAX -> skip (:774): first point wins
+  if constexpr (kDeskew) {
+    if (!F.dk.enabled) return;   // the same in every lane of the block
+    uint32_t m = ok ? i : 0xffffffffu;
+    for (int off = 32; off >= 1; off >>= 1) m = min(m, (uint32_t)__shfl_xor((int)m, off, 64));
+    if ((threadIdx.x & 63) == 0 && m != 0xffffffffu) atomicMin(F.dk.first, m);
+  }
+}
+
+// pointTime = timeScanCur + (timestamp[i] - timestamp[0]) (imageProjection.cpp:777, new_localization.cpp:1953): the difference
+// in the field's type, the sum in double.  Record 0 is the input's, whether or not it passes the tests.
+__device__ inline double point_time(const LfFrame& F, uint32_t i) {
+  const char* r0 = F.pts + F.dk.toff;
+  const char* ri = r0 + (size_t)i * F.stride;
+  const double rel = F.dk.tkind == PCM_LOAM_TIME_FLOAT ? (double)(*reinterpret_cast<const float*>(ri) - *reinterpret_cast<const float*>(r0))
+                                                       : *reinterpret_cast<const double*>(ri) - *reinterpret_cast<const double*>(r0);
+  return F.dk.time_scan_cur + rel;
+}
+
+// one lane per frame: transStartInverse from the first point
+__global__ void __launch_bounds__(64) k_lf_dk_start(const LfFrame* __restrict__ fr) {
+  const LfFrame& F = fr[blockIdx.x];
+  if (threadIdx.x != 0 || !F.dk.enabled) return;
+  const uint32_t first = *F.dk.first;
+  if (first == 0xffffffffu) return;   // no point passed: nothing reads the transform
+  const double t = point_time(F, first);
+  float rot[3], pos[3], inv[12];
+  loam::deskew_find(F.dk.imu, t, rot);
+  loam::deskew_find(F.dk.odo, t, pos);
+  loam::deskew_start(rot, pos, inv);
+  for (int k = 0; k < 12; k++) F.dk.start_inv[k] = inv[k];
 }
 
 // one block of 256 per (row, frame): occupied cells of the row
@@ -159,7 +208,9 @@ __global__ void __launch_bounds__(256) k_lf_rings(const LfFrame* __restrict__ fr
   }
 }
 
-// one block of 256 per (row, frame): the row's occupied cells in column order
+// one block of 256 per (row, frame): the row's occupied cells in column order.  kDeskew: the stored point and its range are the
+// deskewed point's (imageProjection.cpp:777-782); the column stays the raw point's.
+template <bool kDeskew>
 __global__ void __launch_bounds__(256) k_lf_extract(const LfFrame* __restrict__ fr, LfParams p) {
   const LfFrame& F = fr[blockIdx.y];
   const uint32_t row = blockIdx.x;
@@ -189,6 +240,18 @@ __global__ void __launch_bounds__(256) k_lf_extract(const LfFrame* __restrict__ 
     Proj q;
     float4 pt;
     project_point(F, p, i, &q, &pt);   // the owner passed every test in k_lf_project
+    if constexpr (kDeskew) {
+      if (F.dk.enabled) {
+        const double t = point_time(F, i);
+        float rot[3], tr[3], inv[12], d[3];
+        loam::deskew_find(F.dk.imu, t, rot);
+        loam::deskew_find(F.dk.odo, t, tr);
+        for (int k = 0; k < 12; k++) inv[k] = F.dk.start_inv[k];
+        loam::deskew_point(inv, rot, tr, pt.x, pt.y, pt.z, d);
+        pt.x = d[0]; pt.y = d[1]; pt.z = d[2];
+        q.range = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);   // pointDistance(thisPoint) :779
+      }
+    }
     F.col_ind[pos] = j;
     F.range[pos] = q.range;
     F.cloud[pos] = pt;
@@ -564,6 +627,7 @@ struct FeatState {
   DevBuf<LfFrame> d_fr; PinnedBuf<LfFrame> h_fr;
   DevBuf<LfInfo> d_info; PinnedBuf<LfInfo> h_info;
   DevBuf<char> ws;
+  std::vector<double> dk_host;   // the deskew tables of a batch as the device reads them (staging of their upload)
 };
 
 FeatState* fe_of(pcm_ctx* c) { return c->loam_fe.get_or_create<FeatState>(); }
@@ -661,9 +725,41 @@ int check_ctx_fe(pcm_ctx* c) {
   return PCM_OK;
 }
 
-// the whole front end for n frames (one context each) in one set of launches on the first context's stream
+constexpr size_t kDkStateWords = 16;   // per frame: the first-point word, then transStartInverse (12 floats)
+
+// a live descriptor (non-null, imu_available != 0) against the record layout, before any device work
+int check_deskew(pcm_ctx* c0, const pcm_loam_deskew& d, const void* pts, size_t stride, int memory) {
+  if (d.n_imu > loam::kDeskewMaxEntries || d.n_odom > loam::kDeskewMaxEntries) { c0->err = "a deskew table holds at most 1024 entries"; return PCM_ERR_UNSUPPORTED; }
+  if (d.n_imu < 1 || d.n_odom < 0 || !d.imu_time || !d.imu_rot_x || !d.imu_rot_y || !d.imu_rot_z ||
+      (d.n_odom > 0 && (!d.odom_time || !d.odom_incre_x || !d.odom_incre_y || !d.odom_incre_z))) {
+    c0->err = "deskew: imu_available needs an IMU table of >= 1 entries; a table with entries needs its four arrays";
+    return PCM_ERR_INVALID_ARGUMENT;
+  }
+  if (d.time_kind != PCM_LOAM_TIME_DOUBLE && d.time_kind != PCM_LOAM_TIME_FLOAT) { c0->err = "deskew: time_kind must be PCM_LOAM_TIME_DOUBLE or PCM_LOAM_TIME_FLOAT"; return PCM_ERR_INVALID_ARGUMENT; }
+  const size_t w = d.time_kind == PCM_LOAM_TIME_DOUBLE ? 8 : 4;
+  if (d.time_offset_bytes + w > stride) { c0->err = "deskew: the time field lies past the record"; return PCM_ERR_INVALID_ARGUMENT; }
+  // host records are staged at a 256-byte boundary; device records are read where they lie
+  const size_t base = memory == PCM_MEM_DEVICE ? (size_t)reinterpret_cast<uintptr_t>(pts) : 0;
+  if ((stride % w) != 0 || ((base + d.time_offset_bytes) % w) != 0) { c0->err = "deskew: the time field is not aligned to its size in every record"; return PCM_ERR_INVALID_ARGUMENT; }
+  return PCM_OK;
+}
+
+// rows of one table behind `out`: prefix maximum, time, x, y, z
+void pack_table(std::vector<double>& out, const double* t, const double* x, const double* y, const double* z, int n) {
+  const size_t at = out.size();
+  out.resize(at + 5 * (size_t)n);
+  if (n == 0) return;
+  loam::deskew_prefix_max(t, n, out.data() + at);
+  std::memcpy(out.data() + at + (size_t)n, t, sizeof(double) * (size_t)n);
+  std::memcpy(out.data() + at + 2 * (size_t)n, x, sizeof(double) * (size_t)n);
+  std::memcpy(out.data() + at + 3 * (size_t)n, y, sizeof(double) * (size_t)n);
+  std::memcpy(out.data() + at + 4 * (size_t)n, z, sizeof(double) * (size_t)n);
+}
+
+// the whole front end for n frames (one context each) in one set of launches on the first context's stream.  dks: null, or one
+// descriptor per frame (any may be null); a frame is deskewed when its descriptor says imu_available (deskewPoint's own test)
 int run_frames(pcm_ctx* const* ctxs, int B, const void* const* points, const size_t* n_points, size_t stride, size_t ioff, size_t roff, int memory,
-               const pcm_loam_feature_params* params, bool to_source, pcm_loam_features_result* results) {
+               const pcm_loam_feature_params* params, bool to_source, pcm_loam_features_result* results, const pcm_loam_deskew* const* dks = nullptr) {
   if (!ctxs || B <= 0 || !points || !n_points || !results) return PCM_ERR_INVALID_ARGUMENT;
   pcm_ctx* c0 = ctxs[0];
   int rc = check_ctx_fe(c0);
@@ -681,6 +777,14 @@ int run_frames(pcm_ctx* const* ctxs, int B, const void* const* points, const siz
     for (int j = 0; j < i; j++) if (ctxs[j] == ctxs[i]) { c0->err = "a context appears twice in the batch"; return PCM_ERR_INVALID_ARGUMENT; }
     if (!points[i] && n_points[i]) { c0->err = "null point buffer"; return PCM_ERR_INVALID_ARGUMENT; }
     if (n_points[i] > 0x3fffffffull) { c0->err = "cloud too large"; return PCM_ERR_INVALID_ARGUMENT; }
+  }
+  std::vector<const pcm_loam_deskew*> live((size_t)B, nullptr);
+  bool any_dk = false;
+  for (int i = 0; i < B && dks; i++) {
+    if (!dks[i] || !dks[i]->imu_available) continue;
+    if ((rc = check_deskew(c0, *dks[i], points[i], stride, memory)) != PCM_OK) return rc;
+    live[(size_t)i] = dks[i];
+    any_dk = true;
   }
   PCM_HIPCK(c0, hipSetDevice(c0->device));
   const LfParams P = dev_params(q);
@@ -725,11 +829,30 @@ int run_frames(pcm_ctx* const* ctxs, int B, const void* const* points, const siz
   (void)vg::work_layout(nullptr, n_vg, sizeof(uint64_t), nseg_max, &vg_bytes);
   std::vector<const void*> pts((size_t)B, nullptr);
   LfBatch Lw;
-  auto layout = [&](ArenaStage& a) { Lw = loam_batch_layout(a, B, memory, points, n_points, stride, pts.data(), cap, q.n_scan, P.ppr, N1, N2, vg_bytes); };
+  // the deskew tables of the batch, frame after frame (IMU rows, then odometry rows), and one state block per frame
+  std::vector<size_t> dk_at((size_t)B, 0);
+  size_t dk_total = 0;
+  for (int i = 0; i < B; i++)
+    if (const pcm_loam_deskew* d = live[(size_t)i]) { dk_at[(size_t)i] = dk_total; dk_total += 5 * ((size_t)d->n_imu + (size_t)d->n_odom); }
+  const double* dk_tab = nullptr;
+  uint32_t* dk_state = nullptr;
+  auto layout = [&](ArenaStage& a) {
+    Lw = loam_batch_layout(a, B, memory, points, n_points, stride, pts.data(), cap, q.n_scan, P.ppr, N1, N2, vg_bytes);
+    if (any_dk) {
+      dk_tab = a.upload(a.take<double>(dk_total), S0->dk_host.data(), sizeof(double) * dk_total);
+      dk_state = a.take<uint32_t>(kDkStateWords * (size_t)B);
+    }
+  };
   ArenaStage ws_size = arena_stage(c0, nullptr);
   layout(ws_size);
   hipStream_t st = c0->stream;
-  PCM_HIPCK(c0, hipStreamSynchronize(st));   // the pinned staging of an earlier batch is free again
+  PCM_HIPCK(c0, hipStreamSynchronize(st));   // the pinned staging of an earlier batch, and dk_host, are free again
+  S0->dk_host.clear();
+  for (int i = 0; i < B; i++)
+    if (const pcm_loam_deskew* d = live[(size_t)i]) {
+      pack_table(S0->dk_host, d->imu_time, d->imu_rot_x, d->imu_rot_y, d->imu_rot_z, d->n_imu);
+      pack_table(S0->dk_host, d->odom_time, d->odom_incre_x, d->odom_incre_y, d->odom_incre_z, d->n_odom);
+    }
   if ((rc = S0->ws.reserve(c0, ws_size.used(), ws_size.used())) != PCM_OK) return rc;
   if ((rc = S0->d_fr.reserve(c0, (size_t)B, (size_t)B)) != PCM_OK || (rc = S0->h_fr.reserve(c0, (size_t)B, (size_t)B)) != PCM_OK ||
       (rc = S0->d_info.reserve(c0, (size_t)B, (size_t)B)) != PCM_OK || (rc = S0->h_info.reserve(c0, (size_t)B, (size_t)B)) != PCM_OK)
@@ -755,16 +878,34 @@ int run_frames(pcm_ctx* const* ctxs, int B, const void* const* points, const siz
     F.cpick = Lw.cpick + (size_t)i * ncs;
     F.ccnt = Lw.ccnt + (size_t)i * q.n_scan;
     F.info = S0->d_info + i;
+    if (const pcm_loam_deskew* d = live[(size_t)i]) {
+      const double* tab = dk_tab + dk_at[(size_t)i];
+      F.dk.imu = loam::DeskewTable{tab, d->n_imu};
+      F.dk.odo = loam::DeskewTable{tab + 5 * (size_t)d->n_imu, d->n_odom};
+      F.dk.time_scan_cur = d->time_scan_cur;
+      F.dk.toff = (uint32_t)d->time_offset_bytes;
+      F.dk.tkind = d->time_kind;
+      F.dk.enabled = 1;
+      F.dk.first = dk_state + kDkStateWords * (size_t)i;
+      F.dk.start_inv = reinterpret_cast<float*>(F.dk.first + 1);
+    }
     maxn = std::max<uint32_t>(maxn, F.n);
   }
   PCM_HIPCK(c0, hipMemcpyAsync(S0->d_fr, S0->h_fr, sizeof(LfFrame) * (size_t)B, hipMemcpyHostToDevice, st));
   const LfFrame* d_fr = S0->d_fr;
   const unsigned gcap = (unsigned)((std::max<size_t>(cap, (size_t)q.n_scan) + 255) / 256);
-  k_lf_clear<<<dim3(gcap, B), 256, 0, st>>>(d_fr, P);
-  k_lf_project<<<dim3((maxn + 255) / 256, B), 256, 0, st>>>(d_fr, P);
+  if (any_dk) {
+    k_lf_clear<true><<<dim3(gcap, B), 256, 0, st>>>(d_fr, P);
+    k_lf_project<true><<<dim3((maxn + 255) / 256, B), 256, 0, st>>>(d_fr, P);
+    k_lf_dk_start<<<B, 64, 0, st>>>(d_fr);
+  } else {
+    k_lf_clear<false><<<dim3(gcap, B), 256, 0, st>>>(d_fr, P);
+    k_lf_project<false><<<dim3((maxn + 255) / 256, B), 256, 0, st>>>(d_fr, P);
+  }
   k_lf_rowcount<<<dim3(q.n_scan, B), 256, 0, st>>>(d_fr, P);
   k_lf_rings<<<B, 256, 0, st>>>(d_fr, P);
-  k_lf_extract<<<dim3(q.n_scan, B), 256, 0, st>>>(d_fr, P);
+  if (any_dk) k_lf_extract<true><<<dim3(q.n_scan, B), 256, 0, st>>>(d_fr, P);
+  else k_lf_extract<false><<<dim3(q.n_scan, B), 256, 0, st>>>(d_fr, P);
   const unsigned g1 = (max1 + 255) / 256;
   k_lf_smooth<<<dim3(g1, B), 256, 0, st>>>(d_fr, P);
   k_lf_occlude<<<dim3(g1, B), 256, 0, st>>>(d_fr, P);
@@ -831,11 +972,18 @@ void pcm_loam_default_feature_params(pcm_loam_feature_params* p) {
 
 int pcm_loam_extract_features(pcm_ctx* c, const void* points, size_t n, size_t stride_bytes, size_t intensity_offset_bytes, size_t ring_offset_bytes, int memory,
                               const pcm_loam_feature_params* params, float* corner, size_t cap_corner, float* surf, size_t cap_surf, pcm_loam_features_result* res) {
+  return pcm_loam_extract_features_deskew(c, points, n, stride_bytes, intensity_offset_bytes, ring_offset_bytes, memory, params, corner, cap_corner, surf, cap_surf, res, nullptr);
+}
+
+int pcm_loam_extract_features_deskew(pcm_ctx* c, const void* points, size_t n, size_t stride_bytes, size_t intensity_offset_bytes, size_t ring_offset_bytes, int memory,
+                                     const pcm_loam_feature_params* params, float* corner, size_t cap_corner, float* surf, size_t cap_surf, pcm_loam_features_result* res,
+                                     const pcm_loam_deskew* deskew) {
   if (!c || !res) return PCM_ERR_INVALID_ARGUMENT;
   pcm_ctx* arr[1] = {c};
   const void* pts[1] = {points};
   size_t ns[1] = {n};
-  int rc = run_frames(arr, 1, pts, ns, stride_bytes, intensity_offset_bytes, ring_offset_bytes, memory, params, false, res);
+  const pcm_loam_deskew* dks[1] = {deskew};
+  int rc = run_frames(arr, 1, pts, ns, stride_bytes, intensity_offset_bytes, ring_offset_bytes, memory, params, false, res, dks);
   if (rc != PCM_OK) return rc;
   const size_t nc = (size_t)res->num_corner, nsf = (size_t)res->num_surf;
   if ((nc && !corner) || (nsf && !surf) || nc > cap_corner || nsf > cap_surf) { c->err = "output capacity too small (counts are in the result)"; return PCM_ERR_INVALID_ARGUMENT; }
@@ -860,6 +1008,57 @@ int pcm_loam_frame_begin(pcm_ctx* c, const void* points, size_t n, size_t stride
 int pcm_loam_frame_begin_batch(pcm_ctx* const* ctxs, int n, const void* const* points, const size_t* n_points, size_t stride_bytes, size_t intensity_offset_bytes,
                                size_t ring_offset_bytes, int memory, const pcm_loam_feature_params* params, pcm_loam_features_result* results) {
   return run_frames(ctxs, n, points, n_points, stride_bytes, intensity_offset_bytes, ring_offset_bytes, memory, params, true, results);
+}
+
+int pcm_loam_frame_begin_deskew(pcm_ctx* c, const void* points, size_t n, size_t stride_bytes, size_t intensity_offset_bytes, size_t ring_offset_bytes, int memory,
+                                const pcm_loam_feature_params* params, pcm_loam_features_result* res, const pcm_loam_deskew* deskew) {
+  pcm_ctx* arr[1] = {c};
+  const void* pts[1] = {points};
+  size_t ns[1] = {n};
+  const pcm_loam_deskew* dks[1] = {deskew};
+  return run_frames(arr, 1, pts, ns, stride_bytes, intensity_offset_bytes, ring_offset_bytes, memory, params, true, res, dks);
+}
+
+int pcm_loam_frame_begin_batch_deskew(pcm_ctx* const* ctxs, int n, const void* const* points, const size_t* n_points, size_t stride_bytes, size_t intensity_offset_bytes,
+                                      size_t ring_offset_bytes, int memory, const pcm_loam_feature_params* params, pcm_loam_features_result* results,
+                                      const pcm_loam_deskew* const* deskew) {
+  return run_frames(ctxs, n, points, n_points, stride_bytes, intensity_offset_bytes, ring_offset_bytes, memory, params, true, results, deskew);
+}
+
+int pcm_loam_deskew_tables(const pcm_loam_deskew_input* in, double* imu_table, size_t cap_imu, double* odom_table, size_t cap_odom, pcm_loam_deskew* deskew,
+                           pcm_loam_deskew_result* res) {
+  if (!in || !res || in->n_imu < 0 || in->n_odom < 0 || (in->n_imu && !in->imu) || (in->n_odom && !in->odom)) return PCM_ERR_INVALID_ARGUMENT;
+  static_assert(sizeof(pcm_loam_imu_sample) == sizeof(loam::DeskewImu) && sizeof(pcm_loam_odom_sample) == sizeof(loam::DeskewOdom), "sample layouts");
+  std::memset(res, 0, sizeof(*res));
+  res->start_odom_index = -1;
+  constexpr int K = loam::kDeskewMaxEntries;
+  std::vector<double> imu(4 * (size_t)K), odo(4 * (size_t)K);
+  loam::DeskewTables t;
+  const loam::DeskewBuild b = loam::deskew_tables(in->time_scan_cur, in->time_scan_next, reinterpret_cast<const loam::DeskewImu*>(in->imu), in->n_imu,
+                                                  reinterpret_cast<const loam::DeskewOdom*>(in->odom), in->n_odom, imu.data(), odo.data(), K, &t);
+  if (b == loam::kDeskewTooMany) return PCM_ERR_UNSUPPORTED;
+  if (b == loam::kDeskewWaiting) { res->status = PCM_LOAM_DESKEW_WAITING; return PCM_OK; }
+  res->status = PCM_LOAM_DESKEW_READY;
+  res->imu_skipped = t.imu_skipped; res->odom_skipped = t.odom_skipped;
+  res->n_imu = t.n_imu; res->n_odom = t.n_odom;
+  res->imu_available = t.imu_available; res->odom_available = t.odom_available; res->odom_deskew = t.odom_deskew;
+  res->start_odom_index = t.start_odom;
+  if ((size_t)t.n_imu > cap_imu || (size_t)t.n_odom > cap_odom || (t.n_imu && !imu_table) || (t.n_odom && !odom_table)) return PCM_ERR_INVALID_ARGUMENT;
+  for (int r = 0; r < 4; r++) {
+    if (t.n_imu) std::memcpy(imu_table + (size_t)r * cap_imu, imu.data() + (size_t)r * K, sizeof(double) * (size_t)t.n_imu);
+    if (t.n_odom) std::memcpy(odom_table + (size_t)r * cap_odom, odo.data() + (size_t)r * K, sizeof(double) * (size_t)t.n_odom);
+  }
+  if (deskew) {
+    std::memset(deskew, 0, sizeof(*deskew));
+    deskew->time_scan_cur = in->time_scan_cur;
+    if (t.n_imu) { deskew->imu_time = imu_table; deskew->imu_rot_x = imu_table + cap_imu; deskew->imu_rot_y = imu_table + 2 * cap_imu; deskew->imu_rot_z = imu_table + 3 * cap_imu; }
+    if (t.n_odom) { deskew->odom_time = odom_table; deskew->odom_incre_x = odom_table + cap_odom; deskew->odom_incre_y = odom_table + 2 * cap_odom; deskew->odom_incre_z = odom_table + 3 * cap_odom; }
+    deskew->n_imu = t.n_imu; deskew->n_odom = t.n_odom;
+    deskew->imu_available = t.imu_available;
+    deskew->time_offset_bytes = 24;   // PointXYZIRT's double timestamp
+    deskew->time_kind = PCM_LOAM_TIME_DOUBLE;
+  }
+  return PCM_OK;
 }
 
 int pcm_loam_feature_info(pcm_ctx* c, int32_t counts[4], int32_t* start_ring, int32_t* end_ring, int32_t* col_ind, float* range, float* cloud, float* curvature,

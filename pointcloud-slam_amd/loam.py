@@ -226,6 +226,100 @@ def loam_frame_begin_batch(regs, clouds, **feature_params):
     return res
 
 
+# ---- IMU / odometry deskew in front of the features -----------------------------------------------------
+def loam_deskew_tables(time_scan_cur, imu, odom=None, time_scan_next=float("inf")):
+    """deskewInfo (pcm_loam_deskew_tables): ``imu`` (N,4) rows of (stamp, gyro x y z) after imuConverter, ``odom`` (M,4) rows of
+    (stamp, x, y, z), both front first.  ``time_scan_next`` = inf is new_localization.cpp's form (no upper gate, no break).
+    Returns None while waiting for IMU data, else a dict: the descriptor fields ``time_scan_cur``, ``imu`` (n_imu,4) rows of
+    (time, rot x y z), ``odom`` (n_odom,4) rows of (time, increment x y z), ``imu_available``, and the builder's ``imu_skipped``,
+    ``odom_skipped``, ``odom_available``, ``odom_deskew``, ``start_odom_index``.  It is what the *_deskew calls take."""
+    L = capi.load_library()
+    im = np.ascontiguousarray(imu, dtype=np.float64).reshape(-1, 4)
+    od = np.ascontiguousarray(odom if odom is not None else np.zeros((0, 4)), dtype=np.float64).reshape(-1, 4)
+    inp = capi.PcmLoamDeskewInput(time_scan_cur=time_scan_cur, time_scan_next=time_scan_next, imu=im.ctypes.data, odom=od.ctypes.data,
+                                  n_imu=im.shape[0], n_odom=od.shape[0])
+    ci, co = max(1, min(im.shape[0], 1024)), max(1, min(od.shape[0], 1024))
+    it, ot = np.zeros((4, ci)), np.zeros((4, co))
+    r = capi.PcmLoamDeskewResult()
+    rc = L.pcm_loam_deskew_tables(C.byref(inp), it.ctypes.data, ci, ot.ctypes.data, co, None, C.byref(r))
+    if rc != capi.PCM_OK:
+        raise capi.PcmError(rc, "pcm_loam_deskew_tables: more than 1024 table entries" if rc == capi.PCM_ERR_UNSUPPORTED else "pcm_loam_deskew_tables")
+    if r.status == capi.PCM_LOAM_DESKEW_WAITING:
+        return None
+    out = {k: getattr(r, k) for k, _ in r._fields_ if k not in ("reserved", "status", "n_imu", "n_odom")}
+    out.update(time_scan_cur=float(time_scan_cur), imu=it[:, :r.n_imu].T.copy(), odom=ot[:, :r.n_odom].T.copy())
+    return out
+
+
+def _deskew_arg(deskew):
+    """``deskew`` (None, or a dict with time_scan_cur, imu (n,4), optional odom (m,4), imu_available, optional time_offset and
+    time_kind) as a pcm_loam_deskew -> (struct or None, keep-alive)."""
+    if deskew is None:
+        return None, None
+    im = np.ascontiguousarray(np.asarray(deskew["imu"], dtype=np.float64).reshape(-1, 4).T)
+    odom = deskew.get("odom")
+    od = np.ascontiguousarray(np.asarray(odom if odom is not None else np.zeros((0, 4)), dtype=np.float64).reshape(-1, 4).T)
+    d = capi.PcmLoamDeskew(time_scan_cur=deskew["time_scan_cur"], n_imu=im.shape[1], n_odom=od.shape[1],
+                           imu_available=int(deskew.get("imu_available", 1)), time_kind=deskew.get("time_kind", capi.PCM_LOAM_TIME_DOUBLE),
+                           time_offset_bytes=deskew.get("time_offset", 24))
+    if im.shape[1]:
+        d.imu_time, d.imu_rot_x, d.imu_rot_y, d.imu_rot_z = (im[k].ctypes.data for k in range(4))
+    if od.shape[1]:
+        d.odom_time, d.odom_incre_x, d.odom_incre_y, d.odom_incre_z = (od[k].ctypes.data for k in range(4))
+    return d, (im, od)
+
+
+def loam_extract_features_deskew(reg: LoamRegistration, cloud, deskew=None, **feature_params):
+    """loam_extract_features with deskewPoint in front (pcm_loam_extract_features_deskew); ``deskew``: loam_deskew_tables' dict."""
+    (stride, ioff, roff), p = _feature_args(reg._L, feature_params)
+    ptr, n, _, mem, keep = buffer_arg(cloud, record=stride, f32=False, convert=True, what="scan:")
+    d, keep_d = _deskew_arg(deskew)
+    r = capi.PcmLoamFeaturesResult()
+    cap = max(1, n)
+    corner = np.zeros((cap, 4), np.float32)
+    surf = np.zeros((cap, 4), np.float32)
+    reg._check(reg._L.pcm_loam_extract_features_deskew(reg.handle, ptr, n, stride, ioff, roff, mem, C.byref(p), corner.ctypes.data, cap,
+                                                       surf.ctypes.data, cap, C.byref(r), C.byref(d) if d is not None else None))
+    del keep, keep_d
+    return corner[:r.num_corner].copy(), surf[:r.num_surf].copy(), _features_result(r)
+
+
+def loam_frame_begin_deskew(reg: LoamRegistration, cloud, deskew=None, **feature_params) -> dict:
+    """LoamRegistration.set_input_scan with deskewPoint in front (pcm_loam_frame_begin_deskew)."""
+    (stride, ioff, roff), p = _feature_args(reg._L, feature_params)
+    ptr, n, _, mem, keep = buffer_arg(cloud, record=stride, f32=False, convert=True, what="scan:")
+    d, keep_d = _deskew_arg(deskew)
+    r = capi.PcmLoamFeaturesResult()
+    reg._check(reg._L.pcm_loam_frame_begin_deskew(reg.handle, ptr, n, stride, ioff, roff, mem, C.byref(p), C.byref(r), C.byref(d) if d is not None else None))
+    del keep, keep_d
+    reg.n_corner, reg.n_surf = r.num_corner, r.num_surf
+    return _features_result(r)
+
+
+def loam_frame_begin_batch_deskew(regs, clouds, deskews, **feature_params):
+    """loam_frame_begin_batch with one ``deskew`` (or None) per frame (pcm_loam_frame_begin_batch_deskew)."""
+    L = capi.load_library()
+    (stride, ioff, roff), p = _feature_args(L, feature_params)
+    n = len(regs)
+    if len(clouds) != n or len(deskews) != n:
+        raise ValueError("one scan and one deskew (or None) per context")
+    args = [buffer_arg(c, record=stride, f32=False, convert=True, what="scan:") for c in clouds]
+    mems = {a[3] for a in args}
+    if len(mems) != 1:
+        raise ValueError("all scans of a batch must be host arrays or all device tensors")
+    ds = [_deskew_arg(d) for d in deskews]
+    hs = (C.c_void_p * n)(*[r.handle for r in regs])
+    ptrs = (C.c_void_p * n)(*[a[0] for a in args])
+    ns = (C.c_size_t * n)(*[a[1] for a in args])
+    dp = (C.POINTER(capi.PcmLoamDeskew) * n)(*[C.pointer(d) if d is not None else C.POINTER(capi.PcmLoamDeskew)() for d, _ in ds])
+    out = (capi.PcmLoamFeaturesResult * n)()
+    regs[0]._check(L.pcm_loam_frame_begin_batch_deskew(hs, n, ptrs, ns, stride, ioff, roff, mems.pop(), C.byref(p), out, dp))
+    res = [_features_result(out[i]) for i in range(n)]
+    for reg, r in zip(regs, res):
+        reg.n_corner, reg.n_surf = r["num_corner"], r["num_surf"]
+    return res
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # LOAM key-frame store and surrounding-key-frame submap on the device (DESIGN.md section 11)
 # ---------------------------------------------------------------------------------------------------------------------------
