@@ -432,6 +432,20 @@ typedef struct pcm_voxel_large_result {
 int pcm_voxel_downsample_large(pcm_ctx *ctx, const void *points, size_t n, size_t stride_bytes, int memory, float leaf_size, void *out, size_t capacity_points,
                                pcm_voxel_large_result *result);
 
+/* pcl::ApproximateVoxelGrid (fast_gicp/src/align.cpp:136-147, kitti.cpp:81, src/python/main.cpp:46-92), one leaf for the three
+ * axes.  In input order a point has the voxel (ix, iy, iz) = floorf(v * (1.0f / leaf_size)) and the history entry
+ * h = (ix * 7171 + iy * 3079 + iz * 4231) & 511 (32-bit wrapping); an entry that holds another voxel is flushed -- its mean is
+ * the next output record -- before the point joins it, and after the last point the entries in use are flushed in increasing h.
+ * The result depends on the input order, and a voxel can come out more than once; count, membership and order are PCL's.
+ * Every float of a record is averaged (records of 3..16 floats, x y z first); a mean is a double sum in a fixed order divided
+ * in double and cast to float (pcm_voxel_downsample's rule; PCL keeps a running float sum).  A point with a non-finite x, y or z,
+ * or with |floorf(v / leaf)| >= 2^31, is dropped, counted in *n_dropped (may be NULL) and neither joins nor breaks a run.
+ * leaf_size <= 0 or not finite: PCM_ERR_INVALID_ARGUMENT; n <= 2^31 - 1.  `memory` holds for `points` and `out` alike, which do
+ * not overlap.  *n_out = records of the result; when capacity_points is smaller, PCM_ERR_INVALID_ARGUMENT is returned with the
+ * needed count in *n_out and nothing is written to `out`.  Two calls on one input give the same bytes. */
+int pcm_approx_voxel_downsample(pcm_ctx *ctx, const void *points, size_t n, size_t stride_bytes, int memory, float leaf_size, void *out, size_t capacity_points,
+                                size_t *n_out, size_t *n_dropped);
+
 /* PointCloudPreprocess::AviaHandler (jueying_lio/src/pointcloud_preprocess.cc:44-88): the n points of a livox_ros_driver::CustomMsg
  * (20-byte records {uint32 offset_time; float x, y, z; uint8 reflectivity, tag, line; pad} -- msg->points.data()) filtered by line, tag,
  * point_filter_num, the duplicate test against the previous copied point and the blind radius, with the reference's own operator
@@ -515,7 +529,7 @@ int pcm_get_source(pcm_ctx *ctx, float *out_xyz, size_t capacity_points, size_t 
  *                         (pcl::PassThrough, setFilterLimitsNegative(false); at most 2^32 - 1 records enter it).  leaf_size 0 with
  *                         z_min > z_max: the log as it is.  No file is written.
  * Validity: the frame's records live in the context's pre-processing scratch.  Any later call on the context that takes that
- * scratch (pcm_voxel_downsample, pcm_livox_filter, pcm_lidar_filter, pcm_undistort, a frame that fails) or replaces the source
+ * scratch (pcm_voxel_downsample, pcm_approx_voxel_downsample, pcm_livox_filter, pcm_lidar_filter, pcm_undistort, a frame that fails) or replaces the source
  * (pcm_set_source, pcm_clear_source, pcm_swap_source_and_target) ends them: the three frame clouds and the append then return
  * PCM_ERR_NO_INPUT and pcm_last_error names that call.  The log is not affected.
  * Buffers: `out` in host or device memory (`memory`); NULL returns the count in *n only; a capacity below the count returns

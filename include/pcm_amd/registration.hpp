@@ -880,6 +880,49 @@ private:
   pcm_voxel_large_result result_{};
 };
 
+// pcl::ApproximateVoxelGrid on the device (pcm_approx_voxel_downsample; the rules are in pcm_amd.h), with the call surface
+// fast_gicp/src/align.cpp:136-147 and kitti.cpp:81 use: setLeafSize, setInputCloud, filter.  A point is the record of floats it
+// is, as for VoxelGridLarge; one leaf size for the three axes, as every call site sets it -- unequal leaves throw.
+template <typename PointT>
+class ApproximateVoxelGrid {
+public:
+  using Cloud = pcl::PointCloud<PointT>;
+  static_assert(sizeof(PointT) % sizeof(float) == 0 && sizeof(PointT) >= 3 * sizeof(float) && sizeof(PointT) <= 16 * sizeof(float), "a point of 3..16 floats");
+
+  explicit ApproximateVoxelGrid(int device = 0) : ctx_(pcm_create(device, nullptr)) {
+    if (!ctx_) throw std::runtime_error("pcm_create failed");
+  }
+  ~ApproximateVoxelGrid() { if (ctx_) pcm_destroy(ctx_); }
+  ApproximateVoxelGrid(const ApproximateVoxelGrid&) = delete;
+  ApproximateVoxelGrid& operator=(const ApproximateVoxelGrid&) = delete;
+
+  void setLeafSize(float lx, float ly, float lz) {
+    if (lx != ly || lx != lz) throw std::invalid_argument("pcm_amd::ApproximateVoxelGrid: one leaf size for the three axes");
+    leaf_ = lx;
+  }
+  // a cloud of any pointer type that reaches a const cloud (align.cpp hands a PointCloud::Ptr over)
+  void setInputCloud(const typename Cloud::ConstPtr& cloud) { input_ = cloud; }
+  void filter(Cloud& output) {
+    output.points.clear();
+    dropped_ = 0;
+    if (!input_ || input_->points.empty()) return;     // "No input dataset given!": an empty output
+    const size_t n = input_->points.size();
+    std::vector<PointT> records(n);
+    size_t m = 0;
+    const int rc = pcm_approx_voxel_downsample(ctx_, input_->points.data(), n, sizeof(PointT), PCM_MEM_HOST, leaf_, records.data(), n, &m, &dropped_);
+    if (rc != PCM_OK) throw std::runtime_error(std::string("pcm_approx_voxel_downsample: ") + pcm_last_error(ctx_));
+    records.resize(m);
+    output.points.assign(records.begin(), records.end());
+  }
+  size_t dropped() const { return dropped_; }   // points of the last filter() without a voxel (non-finite, or beyond the index range)
+
+private:
+  pcm_ctx* ctx_ = nullptr;
+  float leaf_ = 0.f;
+  typename Cloud::ConstPtr input_;
+  size_t dropped_ = 0;
+};
+
 // jueying_slam's 2D occupancy mapping tool (src/tool/occupancy_mapping) on the device: OccupancyServer's getScan + processScan per
 // cloud, getGridMap and saveMap's image.  Constructed alone it owns a context (the online node, OccupancyServerRealTime: tf lookups
 // and the sensor-tilt pre-rotation stay with the caller); constructed over a LoamScanToMap it maps that context's key frames in

@@ -13,7 +13,7 @@ SYMBOLS = [
     "pcm_abi_version", "pcm_default_config", "pcm_create", "pcm_destroy", "pcm_last_error",
     "pcm_get_config", "pcm_set_config", "pcm_set_stream", "pcm_set_target", "pcm_set_source",
     "pcm_swap_source_and_target", "pcm_clear_source", "pcm_clear_target", "pcm_align",
-    "pcm_linearize", "pcm_compute_error", "pcm_get_planes", "pcm_get_neighbour_lists", "pcm_get_lio_members", "pcm_obs_model", "pcm_target_insert", "pcm_map_incremental", "pcm_get_target", "pcm_get_covariances", "pcm_set_covariances", "pcm_ndt_derivatives", "pcm_ndt_score", "pcm_fitness_score", "pcm_undistort", "pcm_voxel_downsample", "pcm_voxel_downsample_large", "pcm_livox_filter", "pcm_gicp_bfgs_set_correspondences", "pcm_gicp_bfgs_fdf", "pcm_gicp_bfgs_update_correspondences", "pcm_gicp_bfgs_get_correspondences", "pcm_align_batch", "pcm_set_profiling", "pcm_debug_phase_cycles",
+    "pcm_linearize", "pcm_compute_error", "pcm_get_planes", "pcm_get_neighbour_lists", "pcm_get_lio_members", "pcm_obs_model", "pcm_target_insert", "pcm_map_incremental", "pcm_get_target", "pcm_get_covariances", "pcm_set_covariances", "pcm_ndt_derivatives", "pcm_ndt_score", "pcm_fitness_score", "pcm_undistort", "pcm_voxel_downsample", "pcm_voxel_downsample_large", "pcm_approx_voxel_downsample", "pcm_livox_filter", "pcm_gicp_bfgs_set_correspondences", "pcm_gicp_bfgs_fdf", "pcm_gicp_bfgs_update_correspondences", "pcm_gicp_bfgs_get_correspondences", "pcm_align_batch", "pcm_set_profiling", "pcm_debug_phase_cycles",
     "pcm_get_stats", "pcm_reset_stats", "pcm_lio_frame_begin", "pcm_lio_frame_end", "pcm_get_source",
     "pcm_loam_default_params", "pcm_loam_set_target", "pcm_loam_set_source", "pcm_loam_align", "pcm_loam_align_batch",
     "pcm_loam_coefficients", "pcm_loam_neighbours",
@@ -417,6 +417,7 @@ def load_library():
     L.pcm_fitness_score.argtypes = [vp, vp, C.c_double, C.POINTER(C.c_double)]
     L.pcm_voxel_downsample.argtypes = [vp, vp, sz, sz, C.c_int, C.c_float, vp, sz, C.POINTER(sz)]
     L.pcm_voxel_downsample_large.argtypes = [vp, vp, sz, sz, C.c_int, C.c_float, vp, sz, C.POINTER(PcmVoxelLargeResult)]
+    L.pcm_approx_voxel_downsample.argtypes = [vp, vp, sz, sz, C.c_int, C.c_float, vp, sz, C.POINTER(sz), C.POINTER(sz)]
     L.pcm_gicp_bfgs_set_correspondences.argtypes = [vp, vp, sz, vp, sz, sz, vp, vp, sz, vp, C.c_int]
     L.pcm_gicp_bfgs_fdf.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_double), vp]
     L.pcm_gicp_bfgs_update_correspondences.argtypes = [vp, vp, vp, C.POINTER(sz)]

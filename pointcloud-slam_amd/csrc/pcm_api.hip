@@ -572,6 +572,43 @@ int pcm_voxel_downsample(pcm_ctx* c, const void* points, size_t n, size_t stride
   return PCM_OK;
 }
 
+// pcl::ApproximateVoxelGrid::filter (fast_gicp/src/align.cpp:136-147, src/python/main.cpp:46-92); the rules: approx_voxel.h
+int pcm_approx_voxel_downsample(pcm_ctx* c, const void* points, size_t n, size_t stride, int memory, float leaf, void* out, size_t capacity_points, size_t* n_out,
+                                size_t* n_dropped) {
+  CHECK_CTX(c);
+  if (!n_out) { c->err = "pcm_approx_voxel_downsample: n_out is null"; return PCM_ERR_INVALID_ARGUMENT; }
+  *n_out = 0;
+  if (n_dropped) *n_dropped = 0;
+  if ((!points && n) || (!out && capacity_points)) { c->err = "pcm_approx_voxel_downsample: null buffer"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (check_memory(c, memory, "memory") != PCM_OK) return PCM_ERR_INVALID_ARGUMENT;
+  if (stride < 12 || stride > 64 || (stride % 4) != 0) { c->err = "records must be 3..16 floats"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (!(leaf > 0.f) || !std::isfinite(leaf)) { c->err = "leaf size must be finite and > 0"; return PCM_ERR_INVALID_ARGUMENT; }
+  if (n > 0x7fffffffull) { c->err = "pcm_approx_voxel_downsample: more than 2^31 - 1 points"; return PCM_ERR_OUT_OF_RANGE; }
+  if (n == 0) return PCM_OK;
+  PCM_HIPCK(c, hipSetDevice(c->device));
+  const size_t scratch_bytes = approx_voxel_scratch_bytes(n), room = std::min(n, capacity_points);   // a result has at most n records
+  FilterArena F;
+  int rc = carve_pre_arena(c, "pcm_approx_voxel_downsample", [&](ArenaStage& a) { F = filter_layout(a, memory, points, n * stride, memory, out, room * stride, scratch_bytes); });
+  if (rc != PCM_OK) return rc;
+  uint32_t totals[2] = {0u, 0u};   // runs, valid points
+  rc = approx_voxel_downsample_device(c->stream, F.src, n, stride, leaf, static_cast<float*>(F.dst), room, totals, F.scratch, &c->err);
+  if (rc != PCM_OK) return rc;
+  PCM_HIPCK(c, hipStreamSynchronize(c->stream));   // the one wait
+  *n_out = (size_t)totals[0];
+  if (n_dropped) *n_dropped = n - (size_t)totals[1];
+  if (*n_out > capacity_points) {
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "pcm_approx_voxel_downsample: the output buffer holds %zu records, the result has %zu", capacity_points, *n_out);
+    c->err = buf;
+    return PCM_ERR_INVALID_ARGUMENT;
+  }
+  if (memory == PCM_MEM_HOST && *n_out) {
+    if ((rc = stage_back(c, memory, out, F.dst, *n_out * stride)) != PCM_OK) return rc;
+    PCM_HIPCK(c, hipStreamSynchronize(c->stream));   // the staged records reach the caller's memory
+  }
+  return PCM_OK;
+}
+
 // setSourceCovariances / setTargetCovariances  fast_gicp_impl.hpp:93-100: `covs` = n matrices of `elems` doubles each (9: 3x3, 16: the
 // reference's Matrix4d -- its top-left 3x3 block; symmetric, so row- and column-major read the same), input order
 int pcm_set_covariances(pcm_ctx* c, int target, const double* covs, size_t n, int elems) {

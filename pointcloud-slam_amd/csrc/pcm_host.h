@@ -124,6 +124,10 @@ size_t voxel_downsample_scratch_bytes(size_t n);
 size_t livox_filter_scratch_bytes(size_t n);
 int livox_filter_device(hipStream_t stream, const void* d_msg, size_t n, int num_scans, int point_filter_num, double blind, void* d_out, size_t* n_out, void* scratch, std::string* err);
 int voxel_downsample_device(hipStream_t stream, const void* d_in, size_t n, size_t stride, float leaf, float* d_out, size_t* n_out, void* scratch, std::string* err);
+// approx_voxel.hip: pcl::ApproximateVoxelGrid; queues everything, totals = {runs, valid points} after the caller's wait
+size_t approx_voxel_scratch_bytes(size_t n);
+int approx_voxel_downsample_device(hipStream_t stream, const void* d_in, size_t n, size_t stride, float leaf, float* d_out, size_t capacity, uint32_t* totals, void* scratch,
+                                   std::string* err);
 // lidar_handlers.hip: the PointCloud2 handlers (the descriptor has passed lidar_check_cloud; n >= 1) and the stable time sort
 size_t lidar_filter_scratch_bytes(size_t n);
 int lidar_check_cloud(pcm_ctx* c, const void* points, size_t n, int memory, const pcm_lidar_desc* desc);
