@@ -675,10 +675,12 @@ int pcm_loam_neighbours(pcm_ctx *ctx, const float x6[6], int32_t *corner_nn, int
  * featureExtraction (calculateSmoothness / markOccludedPoints / extractFeatures with one pcl::VoxelGrid per ring,
  * featureExtraction.cpp:84-247) and downsampleCurrentScan's two mapping VoxelGrids (mapOptmization.cpp:1232-1247), on the device.
  * Input: ring-tagged records (PointXYZIRT, imageProjection.cpp:7-19: x y z floats at 0, uint8 intensity, uint16 ring; 48 / 16 / 32
- * by default); a point with a non-finite coordinate is skipped; the timestamp is never read (the reference's deskew is the
- * identity as written).  The context keeps the nodes' cross-frame arrays (zero at creation), so a stream of
- * frames through one context reproduces the nodes frame for frame.  Needs a PCM_MODEL_LOAM context.
- * The *_deskew entry points below take IMU / odometry tables and run the live deskewPoint in front of the features.
+ * by default); a point with a non-finite coordinate is skipped.  The entry points without a deskew descriptor never read the
+ * timestamp (the reference's deskew is the identity as written); the *_deskew entry points below take IMU /
+ * odometry tables, read every record's time field and run the live deskewPoint in front of the features (section 34), and the
+ * *_cloud entry points further down make the records themselves, ring and time included, from a raw organised cloud (section 36).
+ * The context keeps the nodes' cross-frame arrays (zero at creation), so a stream of frames through one context reproduces the
+ * nodes frame for frame.  Needs a PCM_MODEL_LOAM context.
  */
 #define PCM_LOAM_FEATURES_FORCE_SERIAL_SORT 1u   /* flags: every sector through the serial std::sort restatement (tests) */
 
@@ -815,6 +817,107 @@ int pcm_loam_frame_begin_deskew(pcm_ctx *ctx, const void *points, size_t n, size
 int pcm_loam_frame_begin_batch_deskew(pcm_ctx *const *ctxs, int n, const void *const *points, const size_t *n_points, size_t stride_bytes,
                                       size_t intensity_offset_bytes, size_t ring_offset_bytes, int memory, const pcm_loam_feature_params *params,
                                       pcm_loam_features_result *results, const pcm_loam_deskew *const *deskew);
+
+/*
+ * cachePointCloud on the device: from the driver's organised cloud to the node's laserCloudIn (DESIGN.md section 36;
+ * imageProjection.cpp:258-479, new_localization.cpp:1560-1731, myremoveNaNFromPointCloud :211-256).  For the three RoboSense
+ * types the reference makes the ring, the per-point time (when the message has none) and the NaN removal there, in per-point host
+ * loops; here raw message bytes go in and the records pcm_loam_frame_begin[_deskew] reads come out, in a buffer of the context.
+ *
+ * Input: height x width records of point_step bytes, record (w, h) at index h * width + w, in host or device memory at a 4-byte
+ * aligned address.  point_step is a multiple of 2; the offsets of x (y, z behind it), of a float intensity and of the time field
+ * are multiples of 4 inside the record, the ring's a multiple of 2; device records are read where they lie.  The intensity, the
+ * ring and the time are copied in their own kind: a kind that is not the output record's is PCM_ERR_INVALID_ARGUMENT (PCL's field
+ * matching is not in the reference tree, so no conversion is defined).  An absent ring or time field leaves 0 in the record.
+ *
+ * Output (record_kind), padding bytes zero:
+ *   PCM_LOAM_CLOUD_MAPPING       48 bytes (imageProjection.cpp:7-19): x y z 1.0f, uint8 intensity @16, double timestamp @24, uint16 ring @32
+ *   PCM_LOAM_CLOUD_LOCALIZATION  32 bytes (new_localization.cpp:26-38, the layout pcm_scan_fuse writes): float intensity @16,
+ *                                uint16 ring @20, float time @24
+ *
+ * synth_ring (RoboSense types): for h in [0, height-1) and w in [0, width-1) -- the last row and the last column are NOT written
+ * (:326-327) and keep the message's ring, or 0 -- ring = h < 8 ? h : 15 - (h - 8) (RSLIDAR_16, :328) or h (RUBY :369, RSLIDAR_32
+ * :444), converted to uint16.  When it runs is the caller's: the node's static ringFlag, and the difference between
+ * imageProjection.cpp:437 and new_localization.cpp:1692, stay with the caller.
+ * synth_time (RoboSense types): the same bounds; evaluated as written, in double, rounded once to float for the 32-byte record:
+ *   RSLIDAR_16    h*2.8*1e-6 + w*55.5*1e-6                                                  (:349)
+ *   RSLIDAR_RUBY  3.236*((((h+1)%64==0?64:(h+1)%64)-1)/4.f)*1e-6 + w*55.552*1e-6            (:386, the division in float)
+ *   RSLIDAR_32    (w*55.52 + h%16*2.88 + 1.44*float(h/16))*1e-6                             (:461)
+ * The reference synthesises on the first frame only (deskewFlag becomes 1); whether a later frame does is this flag, per call.
+ * is_dense == 0 on a RoboSense type: records with a non-finite x, y or z are dropped, the rest keep their order; is_dense == 1:
+ * every record is copied, NaN or not.  So record 0 of the prepared cloud -- whose time is the deskew's t_0 -- is the first finite
+ * record of a non-dense cloud.  VELODYNE: the records are copied; is_dense == 0, an absent ring field (the node shuts down,
+ * :280-303) or a synth flag is PCM_ERR_INVALID_ARGUMENT; an absent time field is reported (time_available = 0).
+ * This library's definitions: height == 0 or width == 0 is an empty cloud and PCM_OK (the reference's unsigned height-1 is
+ * undefined there); a ring beyond n_scan is no error here (the projection skips the point).  myPassThrough (:182-209) has no
+ * call site and is not built.
+ */
+#define PCM_LOAM_LIDAR_VELODYNE 0        /* utility.h:116-121, elidar_type */
+#define PCM_LOAM_LIDAR_RSLIDAR_RUBY 1
+#define PCM_LOAM_LIDAR_RSLIDAR_16 2
+#define PCM_LOAM_LIDAR_RSLIDAR_32 3
+#define PCM_LOAM_CLOUD_MAPPING 0
+#define PCM_LOAM_CLOUD_LOCALIZATION 1
+#define PCM_LOAM_INTENSITY_UINT8 0
+#define PCM_LOAM_INTENSITY_FLOAT 1
+#define PCM_LOAM_RING_UINT16 0
+#define PCM_LOAM_FIELD_ABSENT ((size_t)-1)   /* ring_offset_bytes / time_offset_bytes: the message has no such field */
+
+typedef struct pcm_loam_cloud_desc {
+  uint32_t height;
+  uint32_t width;
+  size_t point_step;
+  size_t xyz_offset_bytes;
+  size_t intensity_offset_bytes;
+  size_t ring_offset_bytes;      /* or PCM_LOAM_FIELD_ABSENT */
+  size_t time_offset_bytes;      /* or PCM_LOAM_FIELD_ABSENT */
+  int32_t intensity_kind;        /* PCM_LOAM_INTENSITY_*: must be the record's (UINT8 mapping, FLOAT localisation) */
+  int32_t ring_kind;             /* PCM_LOAM_RING_UINT16 */
+  int32_t time_kind;             /* PCM_LOAM_TIME_*: must be the record's (DOUBLE mapping, FLOAT localisation) when the field is there */
+  int32_t is_dense;
+  int32_t lidar_type;            /* PCM_LOAM_LIDAR_* */
+  int32_t record_kind;           /* PCM_LOAM_CLOUD_* */
+  int32_t synth_ring;
+  int32_t synth_time;
+  int32_t reserved[8];
+} pcm_loam_cloud_desc;
+
+typedef struct pcm_loam_cloud_result {
+  uint64_t n_in;                 /* height * width */
+  uint64_t n_out;                /* records of the prepared cloud */
+  uint64_t n_nonfinite;          /* records dropped for a non-finite x, y or z (a dense cloud is not examined: 0) */
+  int32_t ring_synthesised;
+  int32_t time_synthesised;
+  int32_t time_available;        /* the records carry a time: the message's field or the synthesised one */
+  int32_t status;
+  int32_t reserved[8];
+} pcm_loam_cloud_result;
+
+/* the descriptor of the reference's own struct of that node (the record kind's layout as the message's: point_step 48 or 32, both
+ * fields present), height = width = 0, is_dense = 1; the RoboSense types with synth_ring = 1, and synth_time = 0 (a time field is there) */
+int pcm_loam_cloud_default_desc(int lidar_type, int record_kind, pcm_loam_cloud_desc *desc);
+/* out NULL: the prepared cloud stays in a buffer of the context (pcm_loam_cloud_cached).  Else `out` takes up to capacity_points
+ * records (device memory: 16-byte aligned); a capacity below n_out returns the counts in *result and PCM_ERR_INVALID_ARGUMENT, and
+ * nothing is written past the capacity.  One synchronisation (the kept count of a non-dense cloud).  Needs a PCM_MODEL_LOAM
+ * context.  Every misuse -- an offset past point_step, a misaligned field, an unknown type or kind, another model's context --
+ * returns its status with a readable pcm_last_error before any device work. */
+int pcm_loam_cloud_prepare(pcm_ctx *ctx, const void *data, const pcm_loam_cloud_desc *desc, int memory, void *out, size_t capacity_points, int out_memory,
+                           pcm_loam_cloud_result *result);
+/* the records of the last pcm_loam_cloud_prepare with out = NULL (or pcm_loam_frame_begin_cloud) on the device, alive until the
+ * next such call; *n = 0 and a null pointer when there are none */
+int pcm_loam_cloud_cached(pcm_ctx *ctx, const void **device_records, size_t *n, size_t *stride_bytes);
+/* pcm_loam_cloud_prepare into the context's buffer, then pcm_loam_frame_begin_deskew on it where it lies: the raw cloud is the only
+ * bulk upload of the frame.  The front end reads the record kind's layout (intensity @16: of a float intensity its low byte, as
+ * with pcm_scan_fuse's records).  deskew may be NULL; its time_offset_bytes and time_kind are overridden by the record kind's, and
+ * it is ignored when time_available == 0. */
+int pcm_loam_frame_begin_cloud(pcm_ctx *ctx, const void *data, const pcm_loam_cloud_desc *desc, int memory, const pcm_loam_feature_params *feature_params,
+                               pcm_loam_features_result *features_result, const pcm_loam_deskew *deskew, pcm_loam_cloud_result *cloud_result);
+/* n clouds of n distinct contexts on one device: one round of launches prepares them all (one read-back), then
+ * pcm_loam_frame_begin_batch_deskew.  The descriptors may differ in everything but record_kind.  deskews: NULL, or one per frame
+ * (any may be NULL). */
+int pcm_loam_frame_begin_cloud_batch(pcm_ctx *const *ctxs, int n, const void *const *data, const pcm_loam_cloud_desc *descs, int memory,
+                                     const pcm_loam_feature_params *feature_params, pcm_loam_features_result *results, const pcm_loam_deskew *const *deskews,
+                                     pcm_loam_cloud_result *cloud_results);
 
 /*
  * LOAM key-frame store and surrounding-key-frame submap of jueying_slam on the device: saveKeyFramesAndFactor's clouds

@@ -985,7 +985,10 @@ private:
 // holds the nodes' cross-frame arrays.  The setters are named after ParamServer's members (utility.h:223-272).
 // With IMU / odometry queues the scan is motion-compensated first (an option of this library: the reference's deskewPoint is the
 // identity as written).  cloudHandler's order (imageProjection.cpp:238-262):
-//     if (!cachePointCloud(msg)) return;                                              // the caller's: timeScanCur, timeScanNext
+//     // cachePointCloud: the queueing (cloudQueue, timeScanCur, timeScanNext) is the caller's; the per-point part -- the ring, the
+//     // time and the NaN removal of the RoboSense types -- runs on the device from the message's bytes:
+//     fe.setLidarType(PCM_LOAM_LIDAR_RSLIDAR_16); fe.setTimeField(timeField);          // utility.h:227-243, once
+//     fe.cachePointCloud(currentCloudMsg);     // laserCloudIn on the device; or, with the tables set, fe.frameBegin(currentCloudMsg)
 //     pcm_amd::LoamDeskewTables tables;
 //     if (!fe.deskewInfo(timeScanCur, timeScanNext, imu.data(), imu.size(), odom.data(), odom.size(), &tables)) return;   // "Waiting for IMU data ..."
 //     imu.erase(imu.begin(), imu.begin() + tables.info.imu_skipped);                  // the pops of imuDeskewInfo / odomDeskewInfo
@@ -1058,6 +1061,62 @@ public:
   }
   void clearDeskew() { have_deskew_ = false; }
 
+  // cachePointCloud's per-point part on the device (imageProjection.cpp:258-479, new_localization.cpp:1560-1731; DESIGN.md section
+  // 36).  Msg: sensor_msgs::PointCloud2 or anything with its members (fields[].name / .offset / .datatype, height, width, point_step,
+  // is_dense, data); no ROS header enters here.
+  void setLidarType(int v) { lidar_type_ = v; }                        // mlidar_type: PCM_LOAM_LIDAR_* (utility.h:116-121, default rslidar_ruby :227)
+  void setRecordKind(int v) { record_kind_ = v; }                      // PCM_LOAM_CLOUD_MAPPING (imageProjection's struct) or _LOCALIZATION
+  void setTimeField(const std::string& v) { time_field_ = v; }         // timeField (utility.h:243, default "time")
+  // The descriptor of a message.  The ring of rslidar_16 / rslidar_ruby is synthesised on every frame (:328, :369); rslidar_32's
+  // when the message lacks the ring or the time field (imageProjection.cpp:437) or always (new_localization.cpp:1692), by record
+  // kind.  The time of a RoboSense message without a time field is synthesised ON EVERY FRAME: the reference does it on the first
+  // frame only (deskewFlag turns 1) and leaves later frames with whatever fromROSMsg left in the re-used cloud; a caller that
+  // wants that sets synth_time = 0 in the descriptor of later frames and calls pcm_loam_frame_begin_cloud itself.
+  template <typename Msg>
+  pcm_loam_cloud_desc cloudDesc(const Msg& msg) const {
+    pcm_loam_cloud_desc d{};
+    d.height = msg.height; d.width = msg.width; d.point_step = msg.point_step;
+    d.ring_offset_bytes = PCM_LOAM_FIELD_ABSENT; d.time_offset_bytes = PCM_LOAM_FIELD_ABSENT;
+    d.intensity_kind = record_kind_ == PCM_LOAM_CLOUD_MAPPING ? PCM_LOAM_INTENSITY_UINT8 : PCM_LOAM_INTENSITY_FLOAT;
+    d.ring_kind = PCM_LOAM_RING_UINT16;
+    d.time_kind = record_kind_ == PCM_LOAM_CLOUD_MAPPING ? PCM_LOAM_TIME_DOUBLE : PCM_LOAM_TIME_FLOAT;
+    bool have_x = false, have_i = false;
+    for (const auto& f : msg.fields) {
+      if (f.name == "x") { d.xyz_offset_bytes = f.offset; have_x = true; }
+      else if (f.name == "intensity") { d.intensity_offset_bytes = f.offset; d.intensity_kind = f.datatype == 7 ? PCM_LOAM_INTENSITY_FLOAT : f.datatype == 2 ? PCM_LOAM_INTENSITY_UINT8 : -1; have_i = true; }
+      else if (f.name == "ring") { d.ring_offset_bytes = f.offset; d.ring_kind = f.datatype == 4 ? PCM_LOAM_RING_UINT16 : -1; }
+      else if (f.name == time_field_) { d.time_offset_bytes = f.offset; d.time_kind = f.datatype == 8 ? PCM_LOAM_TIME_DOUBLE : f.datatype == 7 ? PCM_LOAM_TIME_FLOAT : -1; }
+    }
+    if (!have_x || !have_i) throw std::runtime_error("cachePointCloud: the message has no x or no intensity field");
+    d.is_dense = msg.is_dense ? 1 : 0;
+    d.lidar_type = lidar_type_; d.record_kind = record_kind_;
+    const bool has_ring = d.ring_offset_bytes != PCM_LOAM_FIELD_ABSENT, has_time = d.time_offset_bytes != PCM_LOAM_FIELD_ABSENT;
+    if (lidar_type_ == PCM_LOAM_LIDAR_RSLIDAR_16 || lidar_type_ == PCM_LOAM_LIDAR_RSLIDAR_RUBY) d.synth_ring = 1;
+    if (lidar_type_ == PCM_LOAM_LIDAR_RSLIDAR_32) d.synth_ring = (record_kind_ == PCM_LOAM_CLOUD_LOCALIZATION || !has_ring || !has_time) ? 1 : 0;
+    if (lidar_type_ != PCM_LOAM_LIDAR_VELODYNE) d.synth_time = has_time ? 0 : 1;
+    return d;
+  }
+  // laserCloudIn of the message, prepared in this object's context (pcm_loam_cloud_cached).  Throws where the node shuts down
+  // (Velodyne: not dense, no ring field) and for a field type that is not the record's.
+  template <typename Msg>
+  const pcm_loam_cloud_result& cachePointCloud(const Msg& msg) {
+    const pcm_loam_cloud_desc d = cloudDesc(msg);
+    const int rc = pcm_loam_cloud_prepare(ctx_, msg.data.data(), &d, PCM_MEM_HOST, nullptr, 0, PCM_MEM_DEVICE, &cloud_);
+    if (rc != PCM_OK) throw std::runtime_error(std::string("pcm_loam_cloud_prepare: ") + pcm_last_error(ctx_));
+    return cloud_;
+  }
+  // cachePointCloud + projectPointCloud ... downsampleCurrentScan of the message: the features become this context's LOAM source
+  // (pcm_loam_frame_begin_cloud); the tables of setDeskew apply when the cloud has a time.  result() / cloudResult() hold the counts.
+  template <typename Msg>
+  const pcm_loam_features_result& frameBegin(const Msg& msg) {
+    const pcm_loam_cloud_desc d = cloudDesc(msg);
+    const int rc = pcm_loam_frame_begin_cloud(ctx_, msg.data.data(), &d, PCM_MEM_HOST, &params_, &last_, have_deskew_ ? &deskew_.desc : nullptr, &cloud_);
+    if (rc != PCM_OK) throw std::runtime_error(std::string("pcm_loam_frame_begin_cloud: ") + pcm_last_error(ctx_));
+    return last_;
+  }
+  const pcm_loam_cloud_result& cloudResult() const { return cloud_; }
+  pcm_ctx* context() const { return ctx_; }
+
   // laserCloudCornerLastDS / laserCloudSurfLastDS of one scan (pcm_loam_extract_features[_deskew])
   void extract(const std::shared_ptr<const CloudIn>& scan, CloudOut& cornerOut, CloudOut& surfOut) {
     const PointIn probe{};
@@ -1087,6 +1146,9 @@ private:
   std::vector<float> corner_, surf_;
   LoamDeskewTables deskew_;
   bool have_deskew_ = false;
+  int lidar_type_ = PCM_LOAM_LIDAR_RSLIDAR_RUBY, record_kind_ = PCM_LOAM_CLOUD_MAPPING;
+  std::string time_field_ = "time";
+  pcm_loam_cloud_result cloud_{};
 };
 
 // jueying_slam's fusion_lidar_camera node (src/tool/integrate_points/src/fusion_lidar_camera.cpp) on the device: the node's

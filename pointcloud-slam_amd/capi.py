@@ -20,6 +20,7 @@ SYMBOLS = [
     "pcm_loam_default_feature_params", "pcm_loam_extract_features", "pcm_loam_frame_begin", "pcm_loam_frame_begin_batch",
     "pcm_loam_feature_info",
     "pcm_loam_deskew_tables", "pcm_loam_extract_features_deskew", "pcm_loam_frame_begin_deskew", "pcm_loam_frame_begin_batch_deskew",
+    "pcm_loam_cloud_default_desc", "pcm_loam_cloud_prepare", "pcm_loam_cloud_cached", "pcm_loam_frame_begin_cloud", "pcm_loam_frame_begin_cloud_batch",
     "pcm_loam_default_submap_params", "pcm_loam_keyframe_add", "pcm_loam_keyframe_set_poses", "pcm_loam_keyframe_count", "pcm_loam_keyframe_clear",
     "pcm_loam_keyframe_get", "pcm_loam_submap_update", "pcm_loam_submap_near", "pcm_loam_submap_info",
     "pcm_loam_default_sc_params", "pcm_loam_sc_add", "pcm_loam_sc_put", "pcm_loam_sc_get", "pcm_loam_sc_count", "pcm_loam_sc_shape", "pcm_loam_sc_clear",
@@ -200,6 +201,26 @@ class PcmLoamDeskewResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("imu_skipped", C.c_int32), ("odom_skipped", C.c_int32), ("n_imu", C.c_int32), ("n_odom", C.c_int32),
                 ("imu_available", C.c_int32), ("odom_available", C.c_int32), ("odom_deskew", C.c_int32), ("start_odom_index", C.c_int32),
                 ("reserved", C.c_int32 * 7)]
+
+
+PCM_LOAM_LIDAR_VELODYNE, PCM_LOAM_LIDAR_RSLIDAR_RUBY, PCM_LOAM_LIDAR_RSLIDAR_16, PCM_LOAM_LIDAR_RSLIDAR_32 = 0, 1, 2, 3   # utility.h:116-121
+PCM_LOAM_CLOUD_MAPPING, PCM_LOAM_CLOUD_LOCALIZATION = 0, 1
+PCM_LOAM_INTENSITY_UINT8, PCM_LOAM_INTENSITY_FLOAT = 0, 1
+PCM_LOAM_RING_UINT16 = 0
+PCM_LOAM_FIELD_ABSENT = C.c_size_t(-1).value
+
+
+class PcmLoamCloudDesc(C.Structure):
+    _fields_ = [("height", C.c_uint32), ("width", C.c_uint32), ("point_step", C.c_size_t), ("xyz_offset_bytes", C.c_size_t),
+                ("intensity_offset_bytes", C.c_size_t), ("ring_offset_bytes", C.c_size_t), ("time_offset_bytes", C.c_size_t),
+                ("intensity_kind", C.c_int32), ("ring_kind", C.c_int32), ("time_kind", C.c_int32), ("is_dense", C.c_int32),
+                ("lidar_type", C.c_int32), ("record_kind", C.c_int32), ("synth_ring", C.c_int32), ("synth_time", C.c_int32),
+                ("reserved", C.c_int32 * 8)]
+
+
+class PcmLoamCloudResult(C.Structure):
+    _fields_ = [("n_in", C.c_uint64), ("n_out", C.c_uint64), ("n_nonfinite", C.c_uint64), ("ring_synthesised", C.c_int32),
+                ("time_synthesised", C.c_int32), ("time_available", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32 * 8)]
 
 
 class PcmLoamSubmapParams(C.Structure):
@@ -449,6 +470,13 @@ def load_library():
     L.pcm_loam_extract_features_deskew.argtypes = L.pcm_loam_extract_features.argtypes + [C.POINTER(PcmLoamDeskew)]
     L.pcm_loam_frame_begin_deskew.argtypes = L.pcm_loam_frame_begin.argtypes + [C.POINTER(PcmLoamDeskew)]
     L.pcm_loam_frame_begin_batch_deskew.argtypes = L.pcm_loam_frame_begin_batch.argtypes + [C.POINTER(C.POINTER(PcmLoamDeskew))]
+    L.pcm_loam_cloud_default_desc.argtypes = [i32, i32, C.POINTER(PcmLoamCloudDesc)]
+    L.pcm_loam_cloud_prepare.argtypes = [vp, vp, C.POINTER(PcmLoamCloudDesc), i32, vp, sz, i32, C.POINTER(PcmLoamCloudResult)]
+    L.pcm_loam_cloud_cached.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]
+    L.pcm_loam_frame_begin_cloud.argtypes = [vp, vp, C.POINTER(PcmLoamCloudDesc), i32, C.POINTER(PcmLoamFeatureParams), C.POINTER(PcmLoamFeaturesResult),
+                                             C.POINTER(PcmLoamDeskew), C.POINTER(PcmLoamCloudResult)]
+    L.pcm_loam_frame_begin_cloud_batch.argtypes = [C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(PcmLoamCloudDesc), i32, C.POINTER(PcmLoamFeatureParams),
+                                                   C.POINTER(PcmLoamFeaturesResult), C.POINTER(C.POINTER(PcmLoamDeskew)), C.POINTER(PcmLoamCloudResult)]
     L.pcm_loam_default_submap_params.argtypes = [C.POINTER(PcmLoamSubmapParams)]
     L.pcm_loam_default_submap_params.restype = None
     L.pcm_loam_keyframe_add.argtypes = [vp, vp, C.c_double, vp, sz, vp, sz, sz, i32]

@@ -337,6 +337,7 @@ struct pcm_ctx {
   pcm::PinnedBuf<double> bfgs_host{"bfgs_host"};   // pinned, device-visible: the 14 sums land here without a copy command
   pcm::SubState loam;      // PCM_MODEL_LOAM: maps, features, device state and the stores (loam_api.hip)
   pcm::SubState loam_fe;   // PCM_MODEL_LOAM: the front end's cross-frame state and last-frame outputs (loam_features.hip)
+  pcm::SubState loam_cloud;   // PCM_MODEL_LOAM: the staged raw cloud and the prepared records of cachePointCloud (loam_cloud.hip)
   pcm::SubState occ;       // any model: the 2D occupancy map (occ_map.hip)
   // any model: scan fusion (scan_fuse.hip): staged host segments, the fused records (pcm_scan_fused), counters + tables + scan scratch
   pcm::DevBuf<char> scan_in{"scan_in"}, scan_out{"scan_out"}, scan_tmp{"scan_tmp"};

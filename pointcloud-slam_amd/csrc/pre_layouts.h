@@ -179,6 +179,22 @@ template <class S> void scan_input_layout(S& a, const pcm_scan_segment* segs, in
   for (int s = 0; s < n_segs; s++) base[s] = a.in(segs[s].memory, segs[s].points, segs[s].n * segs[s].stride_bytes);
 }
 
+// pcm_loam_cloud_prepare / pcm_loam_frame_begin_cloud[_batch]'s scratch for the B clouds of a call, nb workgroups of non-dense
+// clouds together: [workgroup counts | workgroup offsets (one more than counts: the total) | kept count per cloud | rocPRIM's temporary]
+struct LoamCloudScratch { uint32_t *kept, *off, *info; void* tmp; };
+inline LoamCloudScratch loam_cloud_scratch_layout(ArenaCarver& a, size_t nb, size_t B, size_t scan_tmp_bytes) {
+  LoamCloudScratch L;
+  L.kept = a.take<uint32_t>(nb + 1);
+  L.off = a.take<uint32_t>(nb + 1);
+  L.info = a.take<uint32_t>(B);
+  L.tmp = a.take<char>(scan_tmp_bytes);
+  return L;
+}
+// ... and its staged host clouds: base[i] = where cloud i is read
+template <class S> void loam_cloud_input_layout(S& a, int B, int memory, const void* const* data, const size_t* bytes, const void** base) {
+  for (int i = 0; i < B; i++) base[i] = a.in(memory, data[i], bytes[i]);
+}
+
 // pcm_gicp_bfgs_set_correspondences: [source | target | source indices | target indices | Mahalanobis rows]
 struct BfgsStaging { const void *src, *tgt; const int32_t *idx_src, *idx_tgt; const float* maha; };
 template <class S> BfgsStaging bfgs_staging_layout(S& a, int memory, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride, const int32_t* idx_src, const int32_t* idx_tgt,

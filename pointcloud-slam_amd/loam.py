@@ -320,6 +320,108 @@ def loam_frame_begin_batch_deskew(regs, clouds, deskews, **feature_params):
     return res
 
 
+# ---- cachePointCloud: the driver's organised cloud to the front end's records ---------------------------
+LOAM_LIDAR_TYPE = {"velodyne": capi.PCM_LOAM_LIDAR_VELODYNE, "rslidar_ruby": capi.PCM_LOAM_LIDAR_RSLIDAR_RUBY,
+                   "rslidar_16": capi.PCM_LOAM_LIDAR_RSLIDAR_16, "rslidar_32": capi.PCM_LOAM_LIDAR_RSLIDAR_32}
+LOAM_CLOUD_KIND = {"mapping": capi.PCM_LOAM_CLOUD_MAPPING, "localization": capi.PCM_LOAM_CLOUD_LOCALIZATION}
+LOAM_CLOUD_STRIDE = {capi.PCM_LOAM_CLOUD_MAPPING: 48, capi.PCM_LOAM_CLOUD_LOCALIZATION: 32}
+
+
+def _cloud_desc_key(p, k, v):
+    if k in ("ring_offset_bytes", "time_offset_bytes") and v is None:   # the message has no such field
+        setattr(p, k, capi.PCM_LOAM_FIELD_ABSENT)
+        return True
+    return False
+
+
+def loam_cloud_desc(lidar_type, record_kind="mapping", **overrides) -> capi.PcmLoamCloudDesc:
+    """pcm_loam_cloud_default_desc of a lidar type ("velodyne" | "rslidar_ruby" | "rslidar_16" | "rslidar_32", or the
+    reference's elidar_type number) and a record kind ("mapping" | "localization"), with any field of pcm_loam_cloud_desc
+    overridden (height, width, point_step, the offsets -- ``ring_offset_bytes`` / ``time_offset_bytes`` None: the message has
+    no such field --, is_dense, synth_ring, synth_time)."""
+    t = LOAM_LIDAR_TYPE.get(lidar_type, lidar_type) if isinstance(lidar_type, str) else int(lidar_type)
+    k = LOAM_CLOUD_KIND.get(record_kind, record_kind) if isinstance(record_kind, str) else int(record_kind)
+    default = capi.load_library().pcm_loam_cloud_default_desc
+    return fill_params(capi.PcmLoamCloudDesc, lambda d: default(t, k, d), overrides, _cloud_desc_key)
+
+
+def _cloud_result(r: capi.PcmLoamCloudResult) -> dict:
+    return {k: getattr(r, k) for k, _ in r._fields_ if k != "reserved"}
+
+
+def _cloud_arg(data, desc):
+    """The raw bytes of ``desc.height x desc.width`` records of ``desc.point_step`` bytes -> (pointer, memory, keep-alive)."""
+    ptr, n, _, mem, keep = buffer_arg(data, record=max(1, desc.point_step), f32=False, convert=True, what="cloud:")
+    if n != desc.height * desc.width:
+        raise ValueError("cloud: %d records of %d bytes, the descriptor says %d x %d" % (n, desc.point_step, desc.height, desc.width))
+    return (ptr if n else None), mem, keep
+
+
+def loam_cloud_prepare(reg: LoamRegistration, data, desc, out=None):
+    """cachePointCloud on the device (pcm_loam_cloud_prepare): ``data`` the organised cloud's raw bytes (host array or device
+    tensor), ``desc`` from loam_cloud_desc.  out None: the records stay in the context's device buffer -> (None, result); out
+    "host": -> ((n_out, 48 | 32) uint8 array, result); out a device tensor or a host array of capacity x (48 | 32) bytes:
+    filled -> (out, result).  A capacity below n_out raises PcmError; nothing past the capacity is written."""
+    stride = LOAM_CLOUD_STRIDE.get(desc.record_kind, 48)   # an unknown kind is the library's to refuse
+    ptr, mem, keep = _cloud_arg(data, desc)
+    r = capi.PcmLoamCloudResult()
+    optr, cap, omem, ret, keep_o = None, 0, capi.MEM_HOST, None, None
+    if isinstance(out, str) and out == "host":
+        ret = np.zeros((max(desc.height * desc.width, 1), stride), np.uint8)
+        optr, cap = ret.ctypes.data, ret.shape[0]
+    elif out is not None:
+        optr, cap, _, omem, keep_o = buffer_arg(out, record=stride, f32=False, write=True, what="out:")
+        ret = out
+    reg._check(reg._L.pcm_loam_cloud_prepare(reg.handle, ptr, C.byref(desc), mem, optr, cap, omem, C.byref(r)))
+    del keep, keep_o
+    if isinstance(out, str):
+        ret = ret[:r.n_out].copy()
+    return ret, _cloud_result(r)
+
+
+def loam_frame_begin_cloud(reg: LoamRegistration, data, desc, deskew=None, **feature_params):
+    """The raw organised cloud through cachePointCloud and the front end into the context's LOAM source
+    (pcm_loam_frame_begin_cloud) -> (features result, cloud result).  ``deskew``: loam_deskew_tables' dict or None; its time
+    field is the prepared record's, and it is ignored when the cloud has no time (``time_available`` 0).  The record layout
+    keywords of the other front-end calls do not apply."""
+    _, p = _feature_args(reg._L, feature_params)
+    ptr, mem, keep = _cloud_arg(data, desc)
+    d, keep_d = _deskew_arg(deskew)
+    r, cr = capi.PcmLoamFeaturesResult(), capi.PcmLoamCloudResult()
+    reg._check(reg._L.pcm_loam_frame_begin_cloud(reg.handle, ptr, C.byref(desc), mem, C.byref(p), C.byref(r), C.byref(d) if d is not None else None, C.byref(cr)))
+    del keep, keep_d
+    reg.n_corner, reg.n_surf = r.num_corner, r.num_surf
+    return _features_result(r), _cloud_result(cr)
+
+
+def loam_frame_begin_cloud_batch(regs, datas, descs, deskews=None, **feature_params):
+    """loam_frame_begin_cloud of n clouds into n LoamRegistration contexts in one round of launches
+    (pcm_loam_frame_begin_cloud_batch) -> (n features results, n cloud results).  One record kind per batch."""
+    L = capi.load_library()
+    _, p = _feature_args(L, feature_params)
+    n = len(regs)
+    deskews = [None] * n if deskews is None else deskews
+    if len(datas) != n or len(descs) != n or len(deskews) != n:
+        raise ValueError("one cloud, one descriptor and one deskew (or None) per context")
+    args = [_cloud_arg(a, d) for a, d in zip(datas, descs)]
+    mems = {a[1] for a in args}
+    if len(mems) != 1:
+        raise ValueError("all clouds of a batch must be host arrays or all device tensors")
+    ds = [_deskew_arg(d) for d in deskews]
+    hs = (C.c_void_p * n)(*[r.handle for r in regs])
+    ptrs = (C.c_void_p * n)(*[a[0] for a in args])
+    da = (capi.PcmLoamCloudDesc * n)()
+    for i, d in enumerate(descs):
+        C.memmove(C.byref(da[i]), C.byref(d), C.sizeof(capi.PcmLoamCloudDesc))
+    dp = (C.POINTER(capi.PcmLoamDeskew) * n)(*[C.pointer(d) if d is not None else C.POINTER(capi.PcmLoamDeskew)() for d, _ in ds])
+    out, cout = (capi.PcmLoamFeaturesResult * n)(), (capi.PcmLoamCloudResult * n)()
+    regs[0]._check(L.pcm_loam_frame_begin_cloud_batch(hs, n, ptrs, da, mems.pop(), C.byref(p), out, dp, cout))
+    res = [_features_result(out[i]) for i in range(n)]
+    for reg, r in zip(regs, res):
+        reg.n_corner, reg.n_surf = r["num_corner"], r["num_surf"]
+    return res, [_cloud_result(cout[i]) for i in range(n)]
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # LOAM key-frame store and surrounding-key-frame submap on the device (DESIGN.md section 11)
 # ---------------------------------------------------------------------------------------------------------------------------
