@@ -55,6 +55,7 @@ typedef enum pcm_model {
   PCM_MODEL_VGICP_CUDA = 6, /* FastVGICPCuda's float core: src/fast_gicp/cuda/{covariance_estimation,covariance_regularization,gaussian_voxelmap,
                              * find_voxel_correspondences,compute_derivatives}.cu (resolution 1.0, DIRECT1, PLANE: impl/fast_vgicp_cuda_impl.hpp:24-27) */
   PCM_MODEL_LOAM = 7,    /* jueying_slam LOAM edge / plane scan-to-map optimisation (mapOptmization.cpp:1255-1586): pcm_loam_* entry points only */
+  PCM_MODEL_ICP = 8,     /* point-to-point ICP, pcl::IterativeClosestPoint as jueying_slam/src/mapOptmization.cpp:768-779 uses it: pcm_icp_* below */
   PCM_MODEL_NDT_OMP = 5  /* pclomp::NormalDistributionsTransform: pointcloud_match/ndt_omp/include/pclomp/ndt_omp_impl.hpp:69-880
                           * (Newton step + More-Thuente line search; max_iterations 35, translation_eps 0.1 = transformation_epsilon_,
                           *  voxel_resolution 1.0, num_neighbors 7 = DIRECT7 are that class's defaults) */
@@ -378,6 +379,64 @@ int pcm_fitness_score(pcm_ctx *ctx, const float T[16], double max_range, double 
 
 /* pclomp NDT: calculateScore (ndt_omp_impl.hpp:835-880) of the source cloud transformed by T (row-major float 4x4) */
 int pcm_ndt_score(pcm_ctx *ctx, const float T[16], double *score);
+
+/*
+ * Point-to-point ICP (PCM_MODEL_ICP): pcl::IterativeClosestPoint, the verifier of jueying_slam's performSCLoopClosure
+ * (mapOptmization.cpp:768-779).  PCL is not in the reference tree: the rules are restated from PCL 1.10's IterativeClosestPoint /
+ * DefaultConvergenceCriteria and are this library's definition (csrc/icp.h); the closed-form step is Eigen's
+ * umeyama without scaling (fast_gicp/thirdparty/Eigen/Eigen/src/Geometry/Umeyama.h:118-158).  A context of this model goes through
+ * pcm_set_target / pcm_set_source (a PCM_MEM_DEVICE source of 16-byte records is read in place) / pcm_align / pcm_fitness_score;
+ * of pcm_config it reads voxel_resolution (the cell of the search grid: speed only, the nearest neighbour is exact).  One align(guess):
+ *   F = double(guess); per iteration every source point goes through float(F) (the cloud itself is never rewritten: PCL transforms
+ *   the cloud and composes increments in float), pairs with its exact nearest target point when the float squared distance is
+ *   <= max_correspondence_distance^2 (inclusive; non-finite points have no pair); fewer than 3 pairs stop the loop unconverged
+ *   with the pose as it was; else the SVD step of the pairs is composed onto F in double and the criteria run in this order:
+ *   iteration count >= max_iterations (converged = 1: PCL counts the cap as convergence), cos(angle) >= rotation threshold and
+ *   |t|^2 <= transformation_epsilon (the epsilon meets the squared translation, as in PCL), |mse - previous mse| < mse_absolute,
+ *   |mse - previous mse| / previous mse < euclidean_fitness_epsilon.
+ * pcm_result: T = float(F), T64 = F, iterations, converged, cost = the last mean squared pair distance, num_inliers = the last
+ * pair count, num_linearize = iterations that ran; pcm_align returns PCM_OK also when converged = 0.  Sums are taken in a fixed
+ * order without atomics: two runs give the same bytes.  The loop is device-resident; the host waits once per
+ * PCM_ICP_CHUNK_ITERATIONS iterations.
+ */
+#define PCM_ICP_STOP_NONE 0                 /* no align() yet */
+#define PCM_ICP_STOP_ITERATIONS 1           /* the iteration cap (converged = 1) */
+#define PCM_ICP_STOP_TRANSFORM 2            /* rotation and translation of the last step below their thresholds */
+#define PCM_ICP_STOP_ABS_MSE 3              /* |mse - previous mse| < mse_absolute */
+#define PCM_ICP_STOP_REL_MSE 4              /* |mse - previous mse| / previous mse < euclidean_fitness_epsilon */
+#define PCM_ICP_STOP_NO_CORRESPONDENCES 5   /* fewer than 3 pairs (converged = 0) */
+#define PCM_ICP_CHUNK_ITERATIONS 8
+
+typedef struct pcm_icp_params {
+  int32_t max_iterations;                /* 10            setMaximumIterations */
+  double max_correspondence_distance;    /* sqrt(DBL_MAX) setMaxCorrespondenceDistance */
+  double transformation_epsilon;         /* 0             setTransformationEpsilon */
+  double rotation_epsilon;               /* 0             setTransformationRotationEpsilon: a cosine; <= 0 means 1 - transformation_epsilon */
+  double euclidean_fitness_epsilon;      /* -DBL_MAX      setEuclideanFitnessEpsilon: the relative-MSE threshold */
+  double mse_absolute;                   /* 1e-12         DefaultConvergenceCriteria's absolute MSE threshold */
+  int32_t reserved[8];
+} pcm_icp_params;
+
+typedef struct pcm_icp_info {
+  int32_t stop_reason;           /* PCM_ICP_STOP_* of the last pcm_align */
+  int32_t iterations;            /* completed iterations */
+  int32_t converged;
+  int32_t reserved0;
+  uint64_t num_pairs;            /* N of the last iteration that ran */
+  double mse;                    /* sum d2 / N of the last iteration that had >= 3 pairs */
+  int32_t reserved[8];
+} pcm_icp_info;
+
+void pcm_icp_default_params(pcm_icp_params *params);
+/* PCM_MODEL_ICP contexts only (PCM_ERR_UNSUPPORTED otherwise).  max_iterations in [1, 2^20], max_correspondence_distance > 0, no
+ * NaN: PCM_ERR_INVALID_ARGUMENT, nothing changed.  A context that never set any runs with the defaults. */
+int pcm_icp_set_params(pcm_ctx *ctx, const pcm_icp_params *params);
+int pcm_icp_get_params(pcm_ctx *ctx, pcm_icp_params *params);
+/* stop reason, iterations, last pair count and mse of the last pcm_align (zeros before one) */
+int pcm_icp_last(pcm_ctx *ctx, pcm_icp_info *info);
+/* parity hook: pair count and mse of every iteration that ran in the last pcm_align (*n entries; an iteration stopped for
+ * fewer than 3 pairs has mse 0); num_pairs / mse may be NULL to ask for the count */
+int pcm_icp_trace(pcm_ctx *ctx, int32_t capacity, uint64_t *num_pairs, double *mse, int32_t *n);
 
 /* GICP / VGICP: regularised per-point covariances (row-major 3x3 doubles, INPUT order) of the source
  * (target = 0) or target (target = 1) cloud; computes them if needed.  Query the count with out = NULL.
@@ -1094,7 +1153,7 @@ typedef struct pcm_loam_loop_params {
   int32_t min_prev_points;       /* 1000  mapOptmization.cpp:652 */
   int32_t wrt_key;               /* -1    every key frame under its own pose, as performLoopClosure (:650-651).  >= 0: both clouds
                                   *       under the pose of that key frame (loopFindNearKeyframesWithRespectTo) -- an option of this
-                                  *       library, NOT performSCLoopClosure, which verifies with PCL ICP and stays with the caller */
+                                  *       library, NOT performSCLoopClosure, which verifies with PCL ICP: pcm_loam_sc_loop_verify */
   float fitness_threshold;       /* 0.3   utility.h:291 historyKeyframeFitnessScore */
   float near_leaf;               /* 0.2   mapOptmization.cpp:243 downSizeFilterICP = mappingSurfLeafSize (utility.h:272); 0 = none */
   double ndt_epsilon;            /* 0.01  mapOptmization.cpp:684 setTransformationEpsilon */
@@ -1136,6 +1195,62 @@ int pcm_loam_loop_verify(pcm_ctx *ctx, const pcm_loam_loop_params *params, int k
 int pcm_loam_loop_closure(pcm_ctx *ctx, const pcm_loam_loop_params *params, float radius, double time_diff_s, double time_cur, pcm_loam_loop_result *result);
 /* 1 when the context holds a verifier context, 0 when none has been created yet, or a negative pcm_status */
 int pcm_loam_loop_verifier_exists(pcm_ctx *ctx);
+
+/*
+ * performSCLoopClosure (mapOptmization.cpp:735-841), the Scan Context half of the loop thread, on the device: both near clouds
+ * under the pose of key frame 0 (base_key, :757-759; cur = key_cur +- 0, prev = key_pre +- history_search_num, each through the
+ * VoxelGrid of near_leaf), the size gates (:761), pcl::IterativeClosestPoint from the identity (:768-779: PCM_MODEL_ICP in a second
+ * verifier context the LOAM context owns, created by the first verification that passes the gates, run on the LOAM context's
+ * stream, released with the context), pcm_fitness_score(..., DBL_MAX), the acceptance test (:783) and -- on the host -- the factor
+ * of :817-834: poseFrom = getTranslationAndEulerAngles(correction), poseTo = the identity, between = poseFrom.between(poseTo).
+ * Nothing of the LOAM context's target, source, key frames or Scan Context store is written, and the NDT verifier of
+ * pcm_loam_loop_verify is neither created nor used.  GTSAM's factor and the loopIndexContainer insert (:833-840) stay with the caller.
+ */
+typedef struct pcm_loam_sc_loop_params {
+  int32_t history_search_num;        /* 25    utility.h:290 */
+  int32_t min_cur_points;            /* 300   mapOptmization.cpp:761 */
+  int32_t min_prev_points;           /* 1000  mapOptmization.cpp:761 */
+  int32_t icp_max_iterations;        /* 100   :770 */
+  float fitness_threshold;           /* 0.3   :783 historyKeyframeFitnessScore */
+  float near_leaf;                   /* 0.2   downSizeFilterICP (mapOptmization.cpp:243); 0 = none */
+  double icp_max_correspondence_distance;   /* 150   :769 */
+  double icp_transformation_epsilon;        /* 1e-6  :771 */
+  double icp_euclidean_fitness_epsilon;     /* 1e-6  :772 */
+  float icp_voxel_resolution;        /* 1.0   cell of the verifier's search grid (speed only) */
+  int32_t reserved[9];
+} pcm_loam_sc_loop_params;
+
+typedef struct pcm_loam_sc_loop_result {
+  int32_t status;                /* PCM_LOAM_LOOP_* */
+  int32_t key_cur, key_pre;      /* the pair (pcm_loam_sc_loop_closure: as detected; -1, -1 without one) */
+  int32_t num_cur_points;
+  int32_t num_prev_points;
+  int32_t icp_iterations;        /* 0 when ICP did not run */
+  int32_t icp_converged;
+  int32_t icp_stop_reason;       /* PCM_ICP_STOP_* */
+  float yaw_diff_rad;            /* :744 detectResult.second (pcm_loam_sc_loop_closure; unused by the reference); 0 from pcm_loam_sc_loop_verify */
+  float noise_variance;          /* 0.5   :822 robustNoiseScore: the six variances */
+  double cauchy_k;               /* 1     :827 mEstimator::Cauchy::Create(1) */
+  double fitness;                /* icp.getFitnessScore(); 0 when ICP did not run */
+  float correction[16];          /* icp.getFinalTransformation(), row-major; identity when ICP did not run */
+  /* the loop factor, written when the status is ACCEPTED (zero otherwise); poses as (roll, pitch, yaw, x, y, z) */
+  double pose_from[6];           /* :817-818 */
+  double pose_to[6];             /* :819 the identity */
+  double between[16];            /* :834 poseFrom.between(poseTo), row-major 4 x 4 */
+  double between6[6];
+  int32_t reserved[8];
+} pcm_loam_sc_loop_result;
+
+void pcm_loam_default_sc_loop_params(pcm_loam_sc_loop_params *params);
+/* performSCLoopClosure :750-834 for the pair (key_cur, key_pre).  Returns PCM_OK with the outcome in result->status.  An empty
+ * store, a key outside [0, K) and bad parameters: PCM_ERR_INVALID_ARGUMENT, nothing changed.  params NULL = defaults. */
+int pcm_loam_sc_loop_verify(pcm_ctx *ctx, const pcm_loam_sc_loop_params *params, int key_cur, int key_pre, pcm_loam_sc_loop_result *result);
+/* pcm_loam_sc_detect of the last descriptor with its default parameters (:741) and key_cur = K - 1 (:742), then
+ * pcm_loam_sc_loop_verify of the pair.  No loop (:745): PCM_OK with status PCM_LOAM_LOOP_NONE and no further device work.  A caller
+ * with other detection parameters calls pcm_loam_sc_detect and pcm_loam_sc_loop_verify itself. */
+int pcm_loam_sc_loop_closure(pcm_ctx *ctx, const pcm_loam_sc_loop_params *params, pcm_loam_sc_loop_result *result);
+/* 1 when the context holds an ICP verifier context, 0 when none has been created yet, or a negative pcm_status */
+int pcm_loam_sc_loop_verifier_exists(pcm_ctx *ctx);
 
 /*
  * The two clouds a mapping run of jueying_slam exists to produce, from the key frames on the device: publishGlobalMap

@@ -293,6 +293,47 @@ public:
 // pclomp::NormalDistributionsTransform (ndt_omp/include/pclomp/ndt_omp.h:77-310): the operator jueying_slam's
 // localization constructs (jueying_slam/src/localization.cpp:162-189).  Defaults of that class (ndt_omp_impl.hpp:48,60-63).
 enum NeighborSearchMethodOmp { KDTREE, DIRECT26, DIRECT7, DIRECT1 };   // ndt_omp.h:60
+// pcl::IterativeClosestPoint (PCM_MODEL_ICP), as jueying_slam's performSCLoopClosure uses it (mapOptmization.cpp:768-779): point-to-point
+// ICP with PCL's defaults and setter names; setMaximumIterations / setTransformationEpsilon are pcl::Registration's own.  The rules
+// (PCL's, restated; one deliberate departure) are in include/pcm_amd.h and DESIGN.md section 37.  getFitnessScore is the base's.
+template <typename PointSource, typename PointTarget>
+class IterativeClosestPoint : public LsqRegistration<PointSource, PointTarget> {
+  using Lsq = LsqRegistration<PointSource, PointTarget>;
+
+public:
+  explicit IterativeClosestPoint(int device = 0) : Lsq(PCM_MODEL_ICP, device) {
+    this->reg_name_ = "pcm_amd::IterativeClosestPoint";
+    pcm_icp_default_params(&icp_);
+    this->max_iterations_ = icp_.max_iterations;                     // 10
+    this->transformation_epsilon_ = icp_.transformation_epsilon;     // 0
+  }
+  void setMaxCorrespondenceDistance(double d) { Lsq::Base::setMaxCorrespondenceDistance(d); icp_.max_correspondence_distance = d; }
+  void setEuclideanFitnessEpsilon(double e) { icp_.euclidean_fitness_epsilon = e; }
+  void setTransformationRotationEpsilon(double e) { icp_.rotation_epsilon = e; }
+  void setRANSACIterations(int) {}   // :773 sets 0: there is no RANSAC rejection here
+  const pcm_icp_info& lastInfo() const { return info_; }   // stop reason (PCM_ICP_STOP_*), pair count and mse of the last align()
+
+protected:
+  void computeTransformation(typename Lsq::PointCloudSource& output, const typename Lsq::Matrix4& guess) override {
+    icp_.max_iterations = this->max_iterations_;
+    icp_.transformation_epsilon = this->transformation_epsilon_;
+    this->check(pcm_set_config(this->ctx_, &this->cfg_), "pcm_set_config");   // setResolution: the cell of the search grid
+    this->check(pcm_icp_set_params(this->ctx_, &icp_), "pcm_icp_set_params");
+    float g[16];
+    for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) g[i * 4 + j] = guess(i, j);
+    pcm_result r;
+    this->check(pcm_align(this->ctx_, g, &r), "pcm_align");
+    this->check(pcm_icp_last(this->ctx_, &info_), "pcm_icp_last");
+    for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) this->final_transformation_(i, j) = r.T[i * 4 + j];
+    this->nr_iterations_ = r.iterations;
+    this->converged_ = r.converged != 0;
+    this->last_cost_ = r.cost;
+    pcl::transformPointCloud(*this->input_, output, this->final_transformation_);
+  }
+  pcm_icp_params icp_;
+  pcm_icp_info info_{};
+};
+
 template <typename PointSource, typename PointTarget>
 class PclNdtRegistration : public LsqRegistration<PointSource, PointTarget> {
 public:
@@ -528,6 +569,27 @@ public:
     return take_factor(out);
   }
 
+  // performSCLoopClosure :750-834 for a pair Scan Context found, on the device (pcm_loam_sc_loop_verify): both near clouds under
+  // key frame 0, point-to-point ICP (150 / 100 / 1e-6 / 1e-6), the fitness test; true = the factor is in *out (noise 0.5, to go under
+  // mEstimator::Cauchy::Create(scLoopResult().cauchy_k)).  historyKeyframeSearchNum / FitnessScore / the leaf are the setters' above.
+  pcm_loam_sc_loop_params& scLoopParams() {
+    if (!sc_loop_params_set_) { pcm_loam_default_sc_loop_params(&sc_loop_params_); sc_loop_params_set_ = true; }
+    return sc_loop_params_;
+  }
+  const pcm_loam_sc_loop_result& scLoopResult() const { return sc_loop_last_; }
+  bool performSCLoopClosure(int loopKeyCur, int loopKeyPre, LoopFactor* out) {
+    sync_sc_params();
+    check(pcm_loam_sc_loop_verify(ctx_, &sc_loop_params_, loopKeyCur, loopKeyPre, &sc_loop_last_), "pcm_loam_sc_loop_verify");
+    return take_sc_factor(out);
+  }
+  // detectLoopClosureID of the last descriptor (:741) and the verification in one call (pcm_loam_sc_loop_closure); false also
+  // when there is no loop.  The loopIndexContainer insert (:840) stays with the caller.
+  bool performSCLoopClosure(LoopFactor* out) {
+    sync_sc_params();
+    check(pcm_loam_sc_loop_closure(ctx_, &sc_loop_params_, &sc_loop_last_), "pcm_loam_sc_loop_closure");
+    return take_sc_factor(out);
+  }
+
   void setGlobalMapVisualizationSearchRadius(float v) { globalParams().search_radius = v; }   // globalMapVisualizationSearchRadius
   void setGlobalMapVisualizationPoseDensity(float v) { globalParams().keypose_density = v; }   // globalMapVisualizationPoseDensity
   void setGlobalMapVisualizationLeafSize(float v) { globalParams().leaf = v; }                 // globalMapVisualizationLeafSize
@@ -579,6 +641,21 @@ private:
       q.x = buf_[4 * i]; q.y = buf_[4 * i + 1]; q.z = buf_[4 * i + 2]; q.intensity = buf_[4 * i + 3];
     }
   }
+  void sync_sc_params() {
+    scLoopParams().near_leaf = loop_leaf_;
+    sc_loop_params_.history_search_num = loopParams().history_search_num;
+    sc_loop_params_.fitness_threshold = loopParams().fitness_threshold;
+  }
+  bool take_sc_factor(LoopFactor* out) const {
+    if (sc_loop_last_.status != PCM_LOAM_LOOP_ACCEPTED) return false;
+    if (out) {
+      out->index = std::make_pair((int)sc_loop_last_.key_cur, (int)sc_loop_last_.key_pre);
+      for (int k = 0; k < 16; k++) out->between[k] = sc_loop_last_.between[k];
+      for (int k = 0; k < 6; k++) out->between6[k] = sc_loop_last_.between6[k];
+      out->noise = sc_loop_last_.noise_variance;
+    }
+    return true;
+  }
   bool take_factor(LoopFactor* out) const {
     if (loop_last_.status != PCM_LOAM_LOOP_ACCEPTED) return false;
     if (out) {
@@ -614,6 +691,9 @@ private:
   pcm_loam_loop_params loop_params_{};
   bool loop_params_set_ = false;
   pcm_loam_loop_result loop_last_{};
+  pcm_loam_sc_loop_params sc_loop_params_{};
+  bool sc_loop_params_set_ = false;
+  pcm_loam_sc_loop_result sc_loop_last_{};
   float loop_leaf_ = 0.2f;
   pcm_loam_global_params global_params_{};
   bool global_params_set_ = false;

@@ -42,6 +42,8 @@ SYMBOLS = [
     "pcm_lio_frame_world", "pcm_lio_frame_body", "pcm_lio_frame_effect", "pcm_lio_map_append", "pcm_lio_map_info_get", "pcm_lio_map_get",
     "pcm_lio_map_clear", "pcm_lio_map_export",
     "pcm_lio_search_path",
+    "pcm_icp_default_params", "pcm_icp_set_params", "pcm_icp_get_params", "pcm_icp_last", "pcm_icp_trace",
+    "pcm_loam_default_sc_loop_params", "pcm_loam_sc_loop_verify", "pcm_loam_sc_loop_closure", "pcm_loam_sc_loop_verifier_exists",
 ]
 
 PCM_ABI_VERSION = 3   # include/pcm_amd.h
@@ -62,7 +64,7 @@ PCM_ERR_NOT_CONVERGED = -6
 PCM_ERR_INTERNAL = -7
 PCM_ERR_TOO_FEW_FEATURES = -8          # LOAM: not enough corner / surf features, pose left as given
 MEM_HOST, MEM_DEVICE = 0, 1
-MODEL = {"P2PLANE": 0, "GICP": 1, "VGICP": 2, "NDT_P2D": 3, "NDT_D2D": 4, "NDT_OMP": 5, "VGICP_CUDA": 6, "LOAM": 7}
+MODEL = {"P2PLANE": 0, "GICP": 1, "VGICP": 2, "NDT_P2D": 3, "NDT_D2D": 4, "NDT_OMP": 5, "VGICP_CUDA": 6, "LOAM": 7, "ICP": 8}
 OPTIMIZER = {"GN": 0, "LM": 1}
 REGULARIZATION = {"NONE": 0, "MIN_EIG": 1, "NORMALIZED_MIN_EIG": 2, "PLANE": 3, "FROBENIUS": 4, "PCLOMP": 5}
 
@@ -268,6 +270,36 @@ class PcmLoamLoopResult(C.Structure):
                 ("ndt_iterations", C.c_int32), ("ndt_converged", C.c_int32), ("noise_variance", C.c_float), ("fitness", C.c_double),
                 ("correction", C.c_float * 16), ("pose_from", C.c_double * 6), ("pose_to", C.c_double * 6), ("between", C.c_double * 16),
                 ("between6", C.c_double * 6), ("reserved", C.c_int32 * 8)]
+
+
+class PcmLoamScLoopParams(C.Structure):
+    _fields_ = [("history_search_num", C.c_int32), ("min_cur_points", C.c_int32), ("min_prev_points", C.c_int32), ("icp_max_iterations", C.c_int32),
+                ("fitness_threshold", C.c_float), ("near_leaf", C.c_float), ("icp_max_correspondence_distance", C.c_double),
+                ("icp_transformation_epsilon", C.c_double), ("icp_euclidean_fitness_epsilon", C.c_double), ("icp_voxel_resolution", C.c_float),
+                ("reserved", C.c_int32 * 9)]
+
+
+class PcmLoamScLoopResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("key_cur", C.c_int32), ("key_pre", C.c_int32), ("num_cur_points", C.c_int32), ("num_prev_points", C.c_int32),
+                ("icp_iterations", C.c_int32), ("icp_converged", C.c_int32), ("icp_stop_reason", C.c_int32), ("yaw_diff_rad", C.c_float),
+                ("noise_variance", C.c_float), ("cauchy_k", C.c_double), ("fitness", C.c_double), ("correction", C.c_float * 16),
+                ("pose_from", C.c_double * 6), ("pose_to", C.c_double * 6), ("between", C.c_double * 16), ("between6", C.c_double * 6),
+                ("reserved", C.c_int32 * 8)]
+
+
+PCM_MODEL_ICP = 8
+PCM_ICP_STOP_NONE, PCM_ICP_STOP_ITERATIONS, PCM_ICP_STOP_TRANSFORM, PCM_ICP_STOP_ABS_MSE, PCM_ICP_STOP_REL_MSE, PCM_ICP_STOP_NO_CORRESPONDENCES = 0, 1, 2, 3, 4, 5
+PCM_ICP_CHUNK_ITERATIONS = 8
+
+
+class PcmIcpParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("max_correspondence_distance", C.c_double), ("transformation_epsilon", C.c_double),
+                ("rotation_epsilon", C.c_double), ("euclidean_fitness_epsilon", C.c_double), ("mse_absolute", C.c_double), ("reserved", C.c_int32 * 8)]
+
+
+class PcmIcpInfo(C.Structure):
+    _fields_ = [("stop_reason", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32), ("reserved0", C.c_int32), ("num_pairs", C.c_uint64),
+                ("mse", C.c_double), ("reserved", C.c_int32 * 8)]
 
 
 class PcmLoamGlobalParams(C.Structure):
@@ -565,5 +597,16 @@ def load_library():
     L.pcm_lio_map_get.argtypes = [vp, sz, sz, vp, i32]
     L.pcm_lio_map_clear.argtypes = [vp]
     L.pcm_lio_map_export.argtypes = [vp, C.c_float, C.c_double, C.c_double, vp, sz, i32, C.POINTER(sz)]
+    L.pcm_icp_default_params.argtypes = [C.POINTER(PcmIcpParams)]
+    L.pcm_icp_default_params.restype = None
+    L.pcm_icp_set_params.argtypes = [vp, C.POINTER(PcmIcpParams)]
+    L.pcm_icp_get_params.argtypes = [vp, C.POINTER(PcmIcpParams)]
+    L.pcm_icp_last.argtypes = [vp, C.POINTER(PcmIcpInfo)]
+    L.pcm_icp_trace.argtypes = [vp, i32, vp, vp, C.POINTER(C.c_int32)]
+    L.pcm_loam_default_sc_loop_params.argtypes = [C.POINTER(PcmLoamScLoopParams)]
+    L.pcm_loam_default_sc_loop_params.restype = None
+    L.pcm_loam_sc_loop_verify.argtypes = [vp, C.POINTER(PcmLoamScLoopParams), i32, i32, C.POINTER(PcmLoamScLoopResult)]
+    L.pcm_loam_sc_loop_closure.argtypes = [vp, C.POINTER(PcmLoamScLoopParams), C.POINTER(PcmLoamScLoopResult)]
+    L.pcm_loam_sc_loop_verifier_exists.argtypes = [vp]
     _LIB = L
     return L

@@ -112,6 +112,15 @@ LOOP_HD void loop_factor(const float* correction, const float* pose_cur, const f
   between(from6, to6, B16, b6);
 }
 
+// performSCLoopClosure :817-834 for one accepted pair.  correction: icp.getFinalTransformation() row-major.  out: its six numbers
+// promoted (poseFrom, :817-818), poseTo = the identity (:819: Rot3::RzRyRx(0, 0, 0), Point3(0, 0, 0)), between (:834).
+LOOP_HD void sc_loop_factor(const float* correction, double* from6, double* to6, double* B16, double* b6) {
+  float pc[6];
+  pose_from_affine(correction, pc);
+  for (int k = 0; k < 6; k++) { from6[k] = (double)pc[k]; to6[k] = 0.0; }
+  between(from6, to6, B16, b6);
+}
+
 }  // namespace loop
 }  // namespace loam
 }  // namespace pcm

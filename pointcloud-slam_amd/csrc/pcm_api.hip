@@ -27,7 +27,7 @@ int bfgs_scratch(pcm_ctx* c, size_t m) {
 
 int pcm::validate_config(pcm_ctx* c, const pcm_config& g) {
   if (g.model == PCM_MODEL_LOAM) { c->err = "PCM_MODEL_LOAM contexts run through the pcm_loam_* entry points"; return PCM_ERR_UNSUPPORTED; }
-  if (g.model != PCM_MODEL_P2PLANE && !is_ndt(g.model) && !is_gicp(g.model) && g.model != PCM_MODEL_NDT_OMP) { c->err = "unknown registration model"; return PCM_ERR_UNSUPPORTED; }
+  if (g.model != PCM_MODEL_P2PLANE && !is_ndt(g.model) && !is_gicp(g.model) && g.model != PCM_MODEL_NDT_OMP && g.model != PCM_MODEL_ICP) { c->err = "unknown registration model"; return PCM_ERR_UNSUPPORTED; }
   if (g.model == PCM_MODEL_NDT_OMP) {
     if (g.num_neighbors == 19) { c->err = "pclomp NDT neighbourhoods are KDTREE / DIRECT1 / DIRECT7 / DIRECT26 (num_neighbors 0, 1, 7, 27)"; return PCM_ERR_INVALID_ARGUMENT; }
     if (!(g.ndt_step_size > 0.f) || !(g.ndt_outlier_ratio > 0.f) || !(g.ndt_outlier_ratio < 1.f)) { c->err = "bad ndt_step_size / ndt_outlier_ratio"; return PCM_ERR_INVALID_ARGUMENT; }
@@ -686,6 +686,7 @@ int pcm_align(pcm_ctx* c, const float guess[16], pcm_result* out) {
   if (rc != PCM_OK) return rc;
   pcm_ctx* arr[1] = {c};
   if (c->cfg.model == PCM_MODEL_NDT_OMP) return pclndt_align_batch(arr, 1, guess, out);
+  if (c->cfg.model == PCM_MODEL_ICP) return icp_align(c, guess, out);
   return align_batch_impl(arr, 1, guess, out, nullptr);
 }
 
@@ -735,6 +736,8 @@ int pcm_align_batch(pcm_ctx* const* ctxs, int n, const float* guesses, pcm_resul
     if (device_out && hipMemcpy(device_out, res.data(), sizeof(pcm_result) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) return PCM_ERR_HIP;
     return worst;
   }
+  for (int i = 0; i < n; i++)
+    if (ctxs[i]->cfg.model == PCM_MODEL_ICP) { ctxs[0]->err = "pcm_align_batch: PCM_MODEL_ICP contexts register one at a time (pcm_align)"; return PCM_ERR_UNSUPPORTED; }
   return align_batch_impl(ctxs, n, guesses, host_out, device_out);
 }
 
@@ -743,6 +746,7 @@ int pcm_linearize(pcm_ctx* c, const double T[16], double H[36], double b[6], dou
   if (!T) return PCM_ERR_INVALID_ARGUMENT;
   int rc = validate_config(c, c->cfg);
   if (rc != PCM_OK) return rc;
+  if (c->cfg.model == PCM_MODEL_ICP) { c->err = "pcm_linearize: PCM_MODEL_ICP has no normal equations (its step is closed-form)"; return PCM_ERR_UNSUPPORTED; }
   double s[kPartialStride];
   rc = single_pass(c, T, true, s);
   if (rc != PCM_OK) return rc;
@@ -762,6 +766,7 @@ int pcm_linearize(pcm_ctx* c, const double T[16], double H[36], double b[6], dou
 int pcm_compute_error(pcm_ctx* c, const double T[16], double* cost) {
   CHECK_CTX(c);
   if (!T || !cost) return PCM_ERR_INVALID_ARGUMENT;
+  if (c->cfg.model == PCM_MODEL_ICP) { c->err = "pcm_compute_error: not a call of PCM_MODEL_ICP (pcm_fitness_score is its error)"; return PCM_ERR_UNSUPPORTED; }
   double s[kPartialStride];
   int rc = single_pass(c, T, false, s);
   if (rc != PCM_OK) return rc;

@@ -50,6 +50,10 @@ void fill_desc(const pcm_ctx* c, PairDesc* d, double* partials);
 KernelParams kernel_params(const pcm_config& g, const Geom& geom);
 LsqParams lsq_params(const pcm_config& g);
 
+// ---- icp.hip -------------------------------------------------------------------------------------------------------------------
+// one point-to-point ICP registration of a PCM_MODEL_ICP context (the configuration has passed validate_config)
+int icp_align(pcm_ctx* c, const float* guess, pcm_result* out);
+
 // ---- align_batch.hip ---------------------------------------------------------------------------------------------------------
 // grow-only device workspace shared by the batch launches of one device
 struct Workspace {

@@ -12,7 +12,7 @@
 namespace pcm {
 
 int coord_mode_for(int model) {
-  if (model == PCM_MODEL_P2PLANE || model == PCM_MODEL_GICP) return COORD_ROUND;   // GICP: the grid is only the kNN index, any convention serves
+  if (model == PCM_MODEL_P2PLANE || model == PCM_MODEL_GICP || model == PCM_MODEL_ICP) return COORD_ROUND;   // GICP, ICP: the grid is only the NN index, any convention serves
   if (model == PCM_MODEL_NDT_OMP) return COORD_FLOOR_MUL;
   return model == PCM_MODEL_VGICP ? COORD_FLOOR_HALF_D : COORD_FLOOR_HALF;
 }
@@ -333,6 +333,7 @@ int prepare(pcm_ctx* c) {
   int rc = ensure_target_map(c);
   if (rc != PCM_OK) return rc;
   if (c->cfg.model == PCM_MODEL_NDT_OMP) return prepare_pclndt(c);   // nothing of the pair loop is touched
+  if (c->cfg.model == PCM_MODEL_ICP) return PCM_OK;                  // the cloud in map order and the brick table are all ICP reads (icp.hip)
   rc = ensure_neighbour_lists(c, wanted_list_kind(c));
   if (rc == PCM_OK && is_gicp(c->cfg.model)) rc = prepare_gicp(c);
   if (rc == PCM_OK) rc = ensure_d2d_source_map(c);

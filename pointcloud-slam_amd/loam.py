@@ -684,6 +684,66 @@ class _LoopDetection:
         return bool(n)
 
 
+@dataclasses.dataclass
+class LoamScLoopFactor:
+    """pcm_loam_sc_loop_verify / pcm_loam_sc_loop_closure: performSCLoopClosure's outcome for one pair.  ``status`` is one of
+    LOOP_STATUS's names; the factor (``between`` = poseFrom.between(identity), ``noise_variance`` 0.5 under a Cauchy kernel of
+    ``cauchy_k``) is meaningful when ``accepted``."""
+    status: str
+    key_cur: int
+    key_pre: int
+    num_cur_points: int
+    num_prev_points: int
+    icp_iterations: int
+    icp_converged: bool
+    icp_stop_reason: int
+    yaw_diff_rad: float
+    fitness: float
+    noise_variance: float
+    cauchy_k: float
+    correction: np.ndarray
+    pose_from: np.ndarray
+    pose_to: np.ndarray
+    between: np.ndarray
+    between6: np.ndarray
+
+    @property
+    def accepted(self) -> bool:
+        return self.status == "accepted"
+
+
+def _sc_loop_factor(r: capi.PcmLoamScLoopResult) -> LoamScLoopFactor:
+    return LoamScLoopFactor(LOOP_STATUS[r.status], r.key_cur, r.key_pre, r.num_cur_points, r.num_prev_points, r.icp_iterations, bool(r.icp_converged),
+                            r.icp_stop_reason, float(np.float32(r.yaw_diff_rad)), r.fitness, float(np.float32(r.noise_variance)), r.cauchy_k,
+                            np.array(r.correction, np.float32).reshape(4, 4), np.array(r.pose_from), np.array(r.pose_to),
+                            np.array(r.between).reshape(4, 4), np.array(r.between6))
+
+
+def loam_sc_loop_verify(reg, key_cur: int, key_pre: int, **params) -> LoamScLoopFactor:
+    """performSCLoopClosure :750-834 for the pair (pcm_loam_sc_loop_verify): both near clouds under key frame 0, size gates,
+    point-to-point ICP from the identity, fitness, loop factor."""
+    p = fill_params(capi.PcmLoamScLoopParams, reg._L.pcm_loam_default_sc_loop_params, params)
+    r = capi.PcmLoamScLoopResult()
+    reg._check(reg._L.pcm_loam_sc_loop_verify(reg._h, C.byref(p), int(key_cur), int(key_pre), C.byref(r)))
+    return _sc_loop_factor(r)
+
+
+def loam_sc_loop_closure(reg, **params) -> LoamScLoopFactor:
+    """Scan Context detection of the last key frame + verification in one call (pcm_loam_sc_loop_closure); status "no_loop"
+    without a candidate.  The loopIndexContainer bookkeeping stays with the caller."""
+    p = fill_params(capi.PcmLoamScLoopParams, reg._L.pcm_loam_default_sc_loop_params, params)
+    r = capi.PcmLoamScLoopResult()
+    reg._check(reg._L.pcm_loam_sc_loop_closure(reg._h, C.byref(p), C.byref(r)))
+    return _sc_loop_factor(r)
+
+
+def loam_sc_loop_verifier_exists(reg) -> bool:
+    n = reg._L.pcm_loam_sc_loop_verifier_exists(reg._h)
+    if n < 0:
+        reg._check(n)
+    return bool(n)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # LOAM localisation map: area tiles and the per-frame crop on the device (DESIGN.md section 14); the key-frame map cut into
 # tiles (section 31)
