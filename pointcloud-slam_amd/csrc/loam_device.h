@@ -7,6 +7,7 @@
 #include "host_util.h"
 #include "loam_step.h"
 #include "pcm_device.h"
+#include "table_search.h"
 
 namespace pcm {
 namespace loam {

@@ -16,6 +16,8 @@
 
 #include <vector>
 
+#include "arena_carver.h"
+#include "table_search.h"
 #include "target_share.h"
 
 #if defined(__HIPCC__)
@@ -152,8 +154,8 @@ struct TileHolder {
   void let_go(Hook&& before_free) { ts.detach(std::forward<Hook>(before_free)); }
 };
 
-// ---- the layout of a batched crop (pcm_loam_dynmap_crop_batch) --------------------------------------------------------------------
-constexpr uint32_t kDmBlock = 256;   // points per workgroup of k_dm_count / k_dm_scatter
+// ---- the layout of a crop (one context or a batch: loam_dynmap.hip) -----------------------------------------------------------------
+constexpr uint32_t kDmBlock = 256;   // points per workgroup of k_dm_count_batch / k_dm_scatter_batch
 constexpr uint32_t kDmChunk = 256;   // workgroup counts per scan block
 
 // Context i of a batch runs nb[i] workgroups.  The workgroups of all contexts form one 1-D grid, context after context; every
@@ -185,13 +187,40 @@ inline bool batch_layout(const uint32_t* nb, int n, BatchSlice* out, BatchLayout
 // workgroup b of the grid -> its context: the last i with block0[i] <= b (block0: n ascending first workgroups, n >= 1, b below
 // the grid size).  A context without workgroups shares its block0 with the next one and is never the last.  The trip count depends
 // on n alone, and b is the same in every lane of a workgroup, so the result is uniform.
-PCM_DM_HD inline uint32_t batch_context_of(const uint32_t* block0, uint32_t n, uint32_t b) {
-  uint32_t lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (block0[mid] <= b) lo = mid; else hi = mid;
-  }
-  return lo;
+PCM_DM_HD inline uint32_t batch_context_of(const uint32_t* block0, uint32_t n, uint32_t b) { return table_row_of(block0, 1u, n, b); }
+
+// The workspace of a crop of m contexts with E entry-table rows in all: [descriptors | block prefix | entry tables] is the upload
+// range, filled by one copy from a pinned block carved the same way; [counters | count slices] is the zero range, cleared by one
+// memset (the padding of a count slice must scan as zeros); then the scan-block totals and offsets.  Run over a null base it is the
+// size query (bytes), run over the device or the pinned block the carve.  Desc and Entry are the kernels' types (loam_dynmap.hip).
+template <class Desc, class Entry>
+struct CropCarve {
+  Desc* desc;            // [m]
+  uint32_t* block0;      // [m]
+  Entry* ent;            // [E]
+  uint32_t* small;       // [m][small_words]
+  uint32_t* counts;      // [lay.slots]
+  uint32_t* chunk_tot;   // [lay.chunks]
+  uint32_t* chunk_off;   // [lay.chunks]
+  size_t up_bytes;       // the upload range, from desc
+  size_t zero_bytes;     // the zero range, from small
+  size_t bytes;          // everything
+};
+template <class Desc, class Entry>
+inline CropCarve<Desc, Entry> crop_carve(void* base, size_t m, size_t E, size_t small_words, const BatchLayout& lay) {
+  ArenaCarver a(base);
+  CropCarve<Desc, Entry> c;
+  c.desc = a.take<Desc>(m);
+  c.block0 = a.take<uint32_t>(m);
+  c.ent = a.take<Entry>(E);
+  c.up_bytes = a.used();
+  c.small = a.take<uint32_t>(small_words * m);
+  c.counts = a.take<uint32_t>(lay.slots);
+  c.zero_bytes = a.used() - c.up_bytes;
+  c.chunk_tot = a.take<uint32_t>(lay.chunks);
+  c.chunk_off = a.take<uint32_t>(lay.chunks);
+  c.bytes = a.used();
+  return c;
 }
 
 }  // namespace loam

@@ -6,29 +6,31 @@
 // list, per-tile offset, count and Area on the host.  Load: the selection runs on the host (loam_dynmap.h; microseconds) and
 // moves no points.  Crop: the selected tiles' entry table (arena offset, first position in the concatenation) is uploaded and
 // the concatenation is compacted through the frame's window in three steps that keep the order:
-//   k_dm_count    one lane per point, 256 points per workgroup (a workgroup never straddles the two lists): the predicate, a
-//                 ballot and a popcount per wave, one count per workgroup;
-//   k_dm_scan_*   exclusive scan of the workgroup counts: 256 counts per scan block, then the block totals in one workgroup;
-//   k_dm_scatter  the predicate again, the lane's rank from the ballot, the whole 16-byte record to its place in the context's
-//                 corner or surf target cloud (loam_target_reserve / loam_target_commit).
+//   count    one lane per point, 256 points per workgroup (a workgroup never straddles the two lists): the predicate, a ballot
+//            and a popcount per wave, one count per workgroup;
+//   scan     exclusive scan of the workgroup counts: 256 counts per scan block, then the block totals in one workgroup;
+//   scatter  the predicate again, the lane's rank from the ballot, the whole 16-byte record to its place in the context's corner
+//            or surf target cloud (loam_target_reserve / loam_target_commit).
 // The only atomic is the integer counter of dropped non-finite points: no output position depends on the schedule, so two crops
 // of one state give the same bits.  When selection, limits and crop_x equal those of the last crop and the target is still its
 // result, the call does nothing at all (a standing robot, the relocalisation branch's second scan2MapOptimization).
 //
 // The store proper (tile tables and arenas: TileStore) is held through a counted reference (loam_dynmap.h, TileHolder): after
 // pcm_loam_tile_share several contexts read one store, which is then immutable; the selection, the crop workspace and the record of
-// the last crop stay per context.  pcm_loam_dynmap_crop_batch runs the crops of B contexts in one round of launches:
+// the last crop stay per context.  There is one host path and one kernel set (crop_contexts): the crops of B contexts run in one
+// round of launches, and pcm_loam_dynmap_crop is that round with B = 1:
 //   k_dm_count_batch / k_dm_scatter_batch   the workgroups of all contexts in one grid; a workgroup finds its context in the
-//                 block-prefix table and reads that context's DmBatchDesc, then runs the single-context body;
-//   k_dm_scan_chunks                        unchanged, over the count slices of all contexts, each padded to whole scan blocks;
+//                 block-prefix table and reads that context's DmBatchDesc, then runs the body of one context;
+//   k_dm_scan_chunks                        over the count slices of all contexts, each padded to whole scan blocks;
 //   k_dm_scan_tops_batch                    one workgroup per context.
-// The bodies are shared with the single-context kernels, so a batched crop gives the bits of a single one.  DESIGN.md section 33.
+// A context's bits do not depend on who else is in the round.  DESIGN.md sections 14 and 33.
 #include "host_util.h"
 #include "loam_device.h"
 #include "loam_dynmap.h"
 
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 using namespace pcm;
@@ -48,8 +50,8 @@ struct DmEntry {
 constexpr int kSmallWords = 4;
 
 // lane threadIdx.x of a context's workgroup b -> its position g in the concatenation (corner workgroups first: b < nb0 covers
-// [0, n0), the rest [n0, N)), its record and the record's class.  The entry is found by a binary search over the first positions
-// whose trip count depends on the table size alone; a tile holds thousands of points, so nearly every wave reads one entry.  An idle
+// [0, n0), the rest [n0, N)), its record and the record's class.  The entry is found by the search of table_search.h, whose trip
+// count depends on the table size alone; a tile holds thousands of points, so nearly every wave reads one entry.  An idle
 // lane reads the last record of its own list (in bounds) and is class 0.
 __device__ inline int dm_fetch(const float4* __restrict__ corner_arena, const float4* __restrict__ surf_arena, const DmEntry* __restrict__ ent, uint32_t n_ent,
                                uint32_t b, uint32_t nb0, uint32_t n0, uint32_t N, const CropWindow& w, float4* p, bool* seg1) {
@@ -58,12 +60,7 @@ __device__ inline int dm_fetch(const float4* __restrict__ corner_arena, const fl
   const uint32_t end = *seg1 ? N : n0;
   const bool valid = g < end;
   const uint32_t gg = valid ? g : end - 1;
-  uint32_t lo = 0, hi = n_ent;   // ent[lo].first <= gg < ent[hi].first (ent[n_ent].first taken as N)
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (ent[mid].first <= gg) lo = mid; else hi = mid;
-  }
-  const DmEntry e = ent[lo];
+  const DmEntry e = ent[table_row_of(&ent->first, sizeof(DmEntry) / 4, n_ent, gg)];
   const float4* __restrict__ arena = (e.flags & 1u) ? surf_arena : corner_arena;
   *p = arena[(size_t)e.src + (gg - e.first)];
   return valid ? crop_class(p->x, p->y, p->z, w) : 0;
@@ -86,12 +83,6 @@ __device__ inline void dm_count_body(const float4* __restrict__ corner_arena, co
     counts[b] = k;
     if (n) atomicAdd(&small[2], n);   // an integer sum: the same in every order
   }
-}
-
-__global__ void __launch_bounds__(kDmBlock) k_dm_count(const float4* __restrict__ corner_arena, const float4* __restrict__ surf_arena,
-                                                       const DmEntry* __restrict__ ent, uint32_t n_ent, uint32_t nb0, uint32_t n0, uint32_t N, CropWindow w,
-                                                       uint32_t* __restrict__ counts, uint32_t* __restrict__ small) {
-  dm_count_body(corner_arena, surf_arena, ent, n_ent, blockIdx.x, nb0, n0, N, w, counts, small);
 }
 
 // exclusive scan of one value per lane over a workgroup of kDmChunk lanes; *total: the sum, in every lane
@@ -143,11 +134,6 @@ __device__ inline void dm_scan_tops_body(const uint32_t* __restrict__ counts, co
   }
 }
 
-__global__ void __launch_bounds__(kDmChunk) k_dm_scan_tops(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ chunk_tot, uint32_t nchunks, uint32_t nb,
-                                                           uint32_t nb0, uint32_t* __restrict__ chunk_off, uint32_t* __restrict__ small) {
-  dm_scan_tops_body(counts, chunk_tot, nchunks, nb, nb0, chunk_off, small);
-}
-
 // workgroup b of one context: its kept records to their places in the context's two output clouds
 __device__ inline void dm_scatter_body(const float4* __restrict__ corner_arena, const float4* __restrict__ surf_arena, const DmEntry* __restrict__ ent, uint32_t n_ent,
                                        uint32_t b, uint32_t nb0, uint32_t n0, uint32_t N, const CropWindow& w, const uint32_t* __restrict__ counts,
@@ -168,15 +154,8 @@ __device__ inline void dm_scatter_body(const float4* __restrict__ corner_arena, 
   if (seg1) out1[off - small[0]] = p; else out0[off] = p;
 }
 
-__global__ void __launch_bounds__(kDmBlock) k_dm_scatter(const float4* __restrict__ corner_arena, const float4* __restrict__ surf_arena,
-                                                         const DmEntry* __restrict__ ent, uint32_t n_ent, uint32_t nb0, uint32_t n0, uint32_t N, CropWindow w,
-                                                         const uint32_t* __restrict__ counts, const uint32_t* __restrict__ chunk_off,
-                                                         const uint32_t* __restrict__ small, float4* __restrict__ out0, float4* __restrict__ out1) {
-  dm_scatter_body(corner_arena, surf_arena, ent, n_ent, blockIdx.x, nb0, n0, N, w, counts, chunk_off, small, out0, out1);
-}
-
-// ---- the batched crop ---------------------------------------------------------------------------------------------------------
-// one context of a batch as the kernels read it; counts, chunk_tot, chunk_off and small point at its own slices (BatchSlice)
+// ---- the launches: the contexts of one round (a single crop is a round of one) -------------------------------------------------
+// one context as the kernels read it; counts, chunk_tot, chunk_off and small point at its own slices (BatchSlice)
 struct DmBatchDesc {
   const float4* arena[2];   // the store this context holds
   const DmEntry* ent;       // its entry table
@@ -191,23 +170,41 @@ struct DmBatchDesc {
 };
 static_assert(sizeof(DmBatchDesc) % 8 == 0, "descriptors lie in an array");
 
-// grid: the workgroups of all contexts; block0[i] = the first workgroup of context i
-__global__ void __launch_bounds__(kDmBlock) k_dm_count_batch(const DmBatchDesc* __restrict__ descs, const uint32_t* __restrict__ block0, uint32_t n_ctx) {
+// Each of the three kernels below exists twice (Descs): with the round's descriptors in memory (DescArray), and for a round of one
+// with the descriptor in the kernel arguments (DmBatchDesc), where the workgroup needs neither the block prefix nor a load before
+// its first instruction.  The single crop was measured slower than its own earlier kernels without this.
+using DescArray = const DmBatchDesc* __restrict__;
+__device__ inline const DmBatchDesc& dm_desc(DescArray descs, uint32_t i) { return descs[i]; }
+__device__ inline const DmBatchDesc& dm_desc(const DmBatchDesc& one, uint32_t) { return one; }
+// workgroup blockIdx.x of the grid -> its context i and its place *b among that context's workgroups
+template <class Descs>
+__device__ inline uint32_t dm_context(const uint32_t* __restrict__ block0, uint32_t n_ctx, uint32_t* b) {
+  if (std::is_same<Descs, DmBatchDesc>::value) { *b = blockIdx.x; return 0u; }
   const uint32_t i = batch_context_of(block0, n_ctx, blockIdx.x);
-  const DmBatchDesc& D = descs[i];
-  dm_count_body(D.arena[0], D.arena[1], D.ent, D.n_ent, blockIdx.x - block0[i], D.nb0, D.n0, D.N, D.w, D.counts, D.small);
+  *b = blockIdx.x - block0[i];
+  return i;
+}
+
+// grid: the workgroups of all contexts; block0[i] = the first workgroup of context i
+template <class Descs>
+__global__ void __launch_bounds__(kDmBlock) k_dm_count_batch(const Descs descs, const uint32_t* __restrict__ block0, uint32_t n_ctx) {
+  uint32_t b;
+  const DmBatchDesc& D = dm_desc(descs, dm_context<Descs>(block0, n_ctx, &b));
+  dm_count_body(D.arena[0], D.arena[1], D.ent, D.n_ent, b, D.nb0, D.n0, D.N, D.w, D.counts, D.small);
 }
 
 // grid: one workgroup per context
-__global__ void __launch_bounds__(kDmChunk) k_dm_scan_tops_batch(const DmBatchDesc* __restrict__ descs) {
-  const DmBatchDesc& D = descs[blockIdx.x];
+template <class Descs>
+__global__ void __launch_bounds__(kDmChunk) k_dm_scan_tops_batch(const Descs descs) {
+  const DmBatchDesc& D = dm_desc(descs, blockIdx.x);
   dm_scan_tops_body(D.counts, D.chunk_tot, D.nchunks, D.nb, D.nb0, D.chunk_off, D.small);
 }
 
-__global__ void __launch_bounds__(kDmBlock) k_dm_scatter_batch(const DmBatchDesc* __restrict__ descs, const uint32_t* __restrict__ block0, uint32_t n_ctx) {
-  const uint32_t i = batch_context_of(block0, n_ctx, blockIdx.x);
-  const DmBatchDesc& D = descs[i];
-  dm_scatter_body(D.arena[0], D.arena[1], D.ent, D.n_ent, blockIdx.x - block0[i], D.nb0, D.n0, D.N, D.w, D.counts, D.chunk_off, D.small, D.out[0], D.out[1]);
+template <class Descs>
+__global__ void __launch_bounds__(kDmBlock) k_dm_scatter_batch(const Descs descs, const uint32_t* __restrict__ block0, uint32_t n_ctx) {
+  uint32_t b;
+  const DmBatchDesc& D = dm_desc(descs, dm_context<Descs>(block0, n_ctx, &b));
+  dm_scatter_body(D.arena[0], D.arena[1], D.ent, D.n_ent, b, D.nb0, D.n0, D.N, D.w, D.counts, D.chunk_off, D.small, D.out[0], D.out[1]);
 }
 
 struct Tile {
@@ -230,13 +227,7 @@ struct TileStore {
 struct DynStore {
   TileHolder<TileStore> h;      // the reference to the store, and the selection of the last load
   int device = -1;              // of the context (the last holder frees the arenas with it current)
-  // crop workspace
-  DevBuf<char> buf{"map-crop workspace"};
-  size_t nb_cap = 0, ent_cap = 0;
-  size_t o_counts = 0, o_tot = 0, o_off = 0, o_small = 0, o_ent = 0;
-  PinnedBuf<uint32_t> h_small;
-  PinnedBuf<DmEntry> h_ent;
-  // workspace and staging of the batches this context leads
+  // workspace and staging of the rounds this context leads (its own crops among them): crop_carve
   DevBuf<char> bbuf{"map-crop batch workspace"};
   PinnedBuf<char> h_up{"map-crop batch staging"};
   PinnedBuf<uint32_t> h_bsmall{"map-crop batch counters"};
@@ -280,27 +271,6 @@ int check_dparams(pcm_ctx* c, const pcm_loam_dynmap_params* params, const float*
   if (!(p->max_range >= 0.f) || !finite_f(p->max_range)) { c->err = "max_range must be a number >= 0"; return PCM_ERR_INVALID_ARGUMENT; }
   if (!pose6) { c->err = "null pose"; return PCM_ERR_INVALID_ARGUMENT; }
   for (int k = 0; k < 6; k++) if (!finite_f(pose6[k])) { c->err = "the pose must be finite"; return PCM_ERR_INVALID_ARGUMENT; }
-  return PCM_OK;
-}
-
-int ensure_work(pcm_ctx* c, DynStore* S, size_t nb, size_t n_ent) {
-  int rc = S->h_small.reserve(c, kSmallWords, kSmallWords);
-  if (rc != PCM_OK) return rc;
-  if (n_ent > S->h_ent.cap && (rc = S->h_ent.reserve(c, n_ent, n_ent + n_ent / 2 + 16)) != PCM_OK) return rc;
-  if (S->buf && nb <= S->nb_cap && n_ent <= S->ent_cap) return PCM_OK;
-  PCM_HIPCK(c, hipStreamSynchronize(c->stream));
-  S->buf.release();   // the layout below is for the new sizes alone
-  S->nb_cap = S->ent_cap = 0;
-  const size_t bc = nb + nb / 4 + 256, ec = S->h_ent.cap, cc = (bc + kDmChunk - 1) / kDmChunk;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t r = o; o += up256(bytes); return r; };
-  S->o_counts = take(4 * bc);
-  S->o_tot = take(4 * cc);
-  S->o_off = take(4 * cc);
-  S->o_small = take(4 * kSmallWords);
-  S->o_ent = take(sizeof(DmEntry) * ec);
-  if ((rc = S->buf.reserve(c, o, o)) != PCM_OK) return rc;
-  S->nb_cap = bc; S->ent_cap = ec;
   return PCM_OK;
 }
 
@@ -388,6 +358,154 @@ struct BatchJob {
   float4* out[2];
   pcm_loam_dynmap_crop_result r;
 };
+
+using Carve = CropCarve<DmBatchDesc, DmEntry>;
+
+// the four launches of a round of m contexts over the workspace d
+template <class Descs>
+void launch_round(hipStream_t st, const Descs descs, const Carve& d, uint32_t m, const BatchLayout& lay) {
+  k_dm_count_batch<Descs><<<lay.blocks, kDmBlock, 0, st>>>(descs, d.block0, m);
+  k_dm_scan_chunks<<<lay.chunks, kDmChunk, 0, st>>>(d.counts, lay.slots, d.chunk_tot);
+  k_dm_scan_tops_batch<Descs><<<m, kDmChunk, 0, st>>>(descs);
+  k_dm_scatter_batch<Descs><<<lay.blocks, kDmBlock, 0, st>>>(descs, d.block0, m);
+}
+
+// The crops of n contexts in one round of launches on the stream of the first context: the one path of pcm_loam_dynmap_crop
+// (n = 1; `one`) and pcm_loam_dynmap_crop_batch.  Host: per context the window and the unchanged short-cut, the target's room, the
+// entry table into one pinned block; one upload (descriptors, block prefix, entry tables), one clear (counters and count slices),
+// four launches, one read-back of all counters, one wait.  results[i].status and the return value (the first failure's status) are
+// the batched call's; a failed allocation names the buffer as the entry point at hand always has.
+int crop_contexts(pcm_ctx* const* ctxs, int n, const pcm_loam_dynmap_params* params, const float* poses6, pcm_loam_dynmap_crop_result* results, bool one) {
+  pcm_ctx* c0 = ctxs[0];
+  DynStore* S0 = nullptr;
+  int rc = check_ctx_dm(c0, &S0);
+  if (rc != PCM_OK) return rc;
+  std::memset(results, 0, sizeof(pcm_loam_dynmap_crop_result) * (size_t)n);
+  int worst = PCM_OK;
+  auto fail = [&](int i, int status, pcm_ctx* c) {
+    results[i].status = status;
+    if (c && c != c0) c0->err = c->err;
+    if (worst == PCM_OK) worst = status;
+  };
+  // what every context asks for; nothing is changed yet
+  std::vector<BatchJob> jobs;
+  std::vector<uint32_t> nbs;
+  jobs.reserve((size_t)n); nbs.reserve((size_t)n);
+  for (int i = 0; i < n; i++) {
+    pcm_ctx* c = ctxs[i];
+    DynStore* S = nullptr;
+    if ((rc = check_ctx_dm(c, &S)) != PCM_OK) {
+      if (!c) c0->err = "pcm_loam_dynmap_crop_batch: null context";
+      fail(i, rc, c);
+      continue;
+    }
+    if (c->device != c0->device) { c0->err = "all contexts of a batch must live on one device"; fail(i, PCM_ERR_INVALID_ARGUMENT, nullptr); continue; }
+    bool twice = false;
+    for (int j = 0; j < i; j++) twice = twice || ctxs[j] == c;
+    if (twice) { c0->err = "a context appears twice in the batch"; fail(i, PCM_ERR_INVALID_ARGUMENT, nullptr); continue; }
+    pcm_loam_dynmap_params p;
+    const float* pose6 = poses6 + 6 * (size_t)i;
+    if ((rc = check_dparams(c, params, pose6, &p)) != PCM_OK) { fail(i, rc, c); continue; }
+    if (!S->h.s.loaded) { c->err = "pcm_loam_dynmap_crop before pcm_loam_dynmap_load"; fail(i, PCM_ERR_NO_INPUT, c); continue; }
+    BatchJob J{};
+    J.i = i; J.c = c; J.S = S;
+    J.w = crop_window(pose6, p.max_range, p.margin, p.crop_x);
+    if (crop_unchanged(c, S, J.w)) {
+      // the same tiles through the same window: the target is the one the context already holds
+      results[i] = S->last;
+      results[i].rebuilt = 0;
+      continue;
+    }
+    selection_size(S, &J.n0, &J.n1, &J.E);
+    if (J.n0 + J.n1 > 0x7fffffffull) { c->err = "the selected tiles hold more than 2^31 points"; fail(i, PCM_ERR_OUT_OF_RANGE, c); continue; }
+    J.nb0 = (uint32_t)((J.n0 + kDmBlock - 1) / kDmBlock);
+    J.nb = J.nb0 + (uint32_t)((J.n1 + kDmBlock - 1) / kDmBlock);
+    jobs.push_back(J);
+    nbs.push_back(J.nb);
+  }
+  if (jobs.empty()) return worst;   // nothing for the device: the short-cut does not touch it
+  std::vector<BatchSlice> slices(jobs.size());
+  BatchLayout lay;
+  if (!batch_layout(nbs.data(), (int)nbs.size(), slices.data(), &lay)) {
+    c0->err = "pcm_loam_dynmap_crop_batch: the workgroups of the batch do not fit one grid: crop in smaller batches";
+    return PCM_ERR_OUT_OF_RANGE;
+  }
+  PCM_HIPCK(c0, hipSetDevice(c0->device));
+  // room for the targets; a context without points is done here.  Those that go on to the device move to the front of jobs.
+  uint32_t m = 0;
+  size_t E_all = 0;
+  for (size_t k = 0; k < jobs.size(); k++) {
+    BatchJob& J = jobs[k];
+    J.S->h.s.last_valid = false;
+    if ((rc = loam_target_reserve(J.c, (size_t)J.n0, (size_t)J.n1, &J.out[0], &J.out[1])) != PCM_OK) { fail(J.i, rc, J.c); continue; }
+    J.r = crop_record(J.n0, J.n1, J.w);
+    if (J.nb == 0) {
+      commit_crop(J.c, J.S, J.w, &J.r);
+      results[J.i] = J.r;
+      continue;
+    }
+    if (J.S->h.ts->fill_queued && J.c != c0) {   // copies into this store are queued on its sole holder's stream
+      if (hipStreamSynchronize(J.c->stream) != hipSuccess) { J.c->err = "pcm_loam_dynmap_crop_batch: hipStreamSynchronize failed"; fail(J.i, PCM_ERR_HIP, J.c); continue; }
+      J.S->h.ts->fill_queued = false;
+    }
+    E_all += J.E;
+    nbs[m] = J.nb;
+    jobs[m++] = J;
+  }
+  if (m == 0) return worst;
+  (void)batch_layout(nbs.data(), (int)m, slices.data(), &lay);   // a failed reservation took a context out: a subset of what fitted
+  const Carve size = crop_carve<DmBatchDesc, DmEntry>(nullptr, m, E_all, kSmallWords, lay);
+  const size_t bytes = size.bytes, up_bytes = size.up_bytes;
+  hipStream_t st = c0->stream;
+  S0->bbuf.what = one ? "map-crop workspace" : "map-crop batch workspace";
+  S0->h_up.what = one ? "pinned buffer" : "map-crop batch staging";
+  S0->h_bsmall.what = one ? "pinned buffer" : "map-crop batch counters";
+  if ((rc = S0->bbuf.reserve(c0, bytes, bytes + bytes / 2)) != PCM_OK) return rc;
+  if ((rc = S0->h_up.reserve(c0, up_bytes, up_bytes + up_bytes / 2)) != PCM_OK) return rc;
+  if ((rc = S0->h_bsmall.reserve(c0, (size_t)kSmallWords * m, (size_t)kSmallWords * m)) != PCM_OK) return rc;
+  PCM_HIPCK(c0, hipStreamSynchronize(st));   // the pinned staging of an earlier round is free again
+  const Carve d = crop_carve<DmBatchDesc, DmEntry>(S0->bbuf.p, m, E_all, kSmallWords, lay);
+  const Carve h = crop_carve<DmBatchDesc, DmEntry>(S0->h_up.p, m, E_all, kSmallWords, lay);   // its upload range mirrors d's
+  size_t e0 = 0;
+  for (uint32_t k = 0; k < m; k++) {
+    const BatchJob& J = jobs[k];
+    const BatchSlice& sl = slices[k];
+    const TileStore& T = *J.S->h.ts;
+    DmBatchDesc D;
+    std::memset(&D, 0, sizeof(D));
+    D.arena[0] = T.arena[0].d; D.arena[1] = T.arena[1].d;
+    D.ent = d.ent + e0;
+    D.counts = d.counts + sl.slot0;
+    D.chunk_tot = d.chunk_tot + sl.chunk0;
+    D.chunk_off = d.chunk_off + sl.chunk0;
+    D.small = d.small + (size_t)kSmallWords * k;
+    D.out[0] = J.out[0]; D.out[1] = J.out[1];
+    D.n_ent = (uint32_t)J.E; D.nb0 = J.nb0; D.nb = J.nb; D.n0 = (uint32_t)J.n0; D.N = (uint32_t)(J.n0 + J.n1); D.nchunks = sl.nchunks;
+    D.w = J.w;
+    h.desc[k] = D;
+    h.block0[k] = sl.block0;
+    e0 += write_entries(J.S, h.ent + e0);
+  }
+  PCM_HIPCK(c0, hipMemcpyAsync(d.desc, h.desc, d.up_bytes, hipMemcpyHostToDevice, st));
+  PCM_HIPCK(c0, hipMemsetAsync(d.small, 0, d.zero_bytes, st));
+  if (m == 1) launch_round<DmBatchDesc>(st, h.desc[0], d, m, lay);   // the descriptor in the kernel arguments
+  else launch_round<DescArray>(st, d.desc, d, m, lay);
+  PCM_HIPCK(c0, hipGetLastError());
+  PCM_HIPCK(c0, hipMemcpyAsync(S0->h_bsmall, d.small, sizeof(uint32_t) * kSmallWords * m, hipMemcpyDeviceToHost, st));
+  PCM_HIPCK(c0, hipStreamSynchronize(st));
+  S0->h.ts->fill_queued = false;
+  for (uint32_t k = 0; k < m; k++) {
+    BatchJob& J = jobs[k];
+    if (!take_counters(S0->h_bsmall + (size_t)kSmallWords * k, J.n0, J.n1, &J.r)) {
+      J.c->err = "pcm_loam_dynmap_crop: inconsistent counts";
+      fail(J.i, PCM_ERR_INTERNAL, J.c);
+      continue;
+    }
+    commit_crop(J.c, J.S, J.w, &J.r);
+    results[J.i] = J.r;
+  }
+  return worst;
+}
 
 }  // namespace
 
@@ -603,6 +721,8 @@ int pcm_loam_dynmap_load(pcm_ctx* c, const pcm_loam_dynmap_params* params, const
   return PCM_OK;
 }
 
+// A round of one.  What this call always answered stays: bad arguments leave *result as it was, every later failure leaves it
+// zeroed (the per-context status is the batched call's), the unchanged short-cut returns the last record with rebuilt = 0.
 int pcm_loam_dynmap_crop(pcm_ctx* c, const pcm_loam_dynmap_params* params, const float pose6[6], pcm_loam_dynmap_crop_result* result) {
   DynStore* S = nullptr;
   int rc = check_ctx_dm(c, &S);
@@ -610,201 +730,13 @@ int pcm_loam_dynmap_crop(pcm_ctx* c, const pcm_loam_dynmap_params* params, const
   if (!result) { c->err = "null result"; return PCM_ERR_INVALID_ARGUMENT; }
   pcm_loam_dynmap_params p;
   if ((rc = check_dparams(c, params, pose6, &p)) != PCM_OK) return rc;
-  std::memset(result, 0, sizeof(*result));
-  if (!S->h.s.loaded) { c->err = "pcm_loam_dynmap_crop before pcm_loam_dynmap_load"; return PCM_ERR_NO_INPUT; }
-  const CropWindow w = crop_window(pose6, p.max_range, p.margin, p.crop_x);
-  if (crop_unchanged(c, S, w)) {
-    // the same tiles through the same window: the target is the one the context already holds
-    *result = S->last;
-    result->rebuilt = 0;
-    return PCM_OK;
-  }
-  PCM_HIPCK(c, hipSetDevice(c->device));
-  S->h.s.last_valid = false;
-  uint64_t n0 = 0, n1 = 0;
-  size_t E = 0;
-  selection_size(S, &n0, &n1, &E);
-  if (n0 + n1 > 0x7fffffffull) { c->err = "the selected tiles hold more than 2^31 points"; return PCM_ERR_OUT_OF_RANGE; }
-  float4 *out_c = nullptr, *out_s = nullptr;
-  if ((rc = loam_target_reserve(c, (size_t)n0, (size_t)n1, &out_c, &out_s)) != PCM_OK) return rc;
-  pcm_loam_dynmap_crop_result r = crop_record(n0, n1, w);
-  const uint32_t N = (uint32_t)(n0 + n1);
-  if (N > 0) {
-    const uint32_t nb0 = (uint32_t)((n0 + kDmBlock - 1) / kDmBlock), nb = nb0 + (uint32_t)((n1 + kDmBlock - 1) / kDmBlock);
-    const uint32_t nchunks = (nb + kDmChunk - 1) / kDmChunk;
-    if ((rc = ensure_work(c, S, nb, E)) != PCM_OK) return rc;
-    PCM_HIPCK(c, hipStreamSynchronize(c->stream));   // the pinned staging of an earlier crop is free again
-    write_entries(S, S->h_ent);
-    const TileStore& T = *S->h.ts;
-    hipStream_t st = c->stream;
-    char* b = S->buf.p;
-    uint32_t* counts = reinterpret_cast<uint32_t*>(b + S->o_counts);
-    uint32_t* chunk_tot = reinterpret_cast<uint32_t*>(b + S->o_tot);
-    uint32_t* chunk_off = reinterpret_cast<uint32_t*>(b + S->o_off);
-    uint32_t* small = reinterpret_cast<uint32_t*>(b + S->o_small);
-    DmEntry* d_ent = reinterpret_cast<DmEntry*>(b + S->o_ent);
-    PCM_HIPCK(c, hipMemcpyAsync(d_ent, S->h_ent, sizeof(DmEntry) * E, hipMemcpyHostToDevice, st));
-    PCM_HIPCK(c, hipMemsetAsync(small, 0, sizeof(uint32_t) * kSmallWords, st));
-    k_dm_count<<<nb, kDmBlock, 0, st>>>(T.arena[0].d, T.arena[1].d, d_ent, (uint32_t)E, nb0, (uint32_t)n0, N, w, counts, small);
-    k_dm_scan_chunks<<<nchunks, kDmChunk, 0, st>>>(counts, nb, chunk_tot);
-    k_dm_scan_tops<<<1, kDmChunk, 0, st>>>(counts, chunk_tot, nchunks, nb, nb0, chunk_off, small);
-    k_dm_scatter<<<nb, kDmBlock, 0, st>>>(T.arena[0].d, T.arena[1].d, d_ent, (uint32_t)E, nb0, (uint32_t)n0, N, w, counts, chunk_off, small, out_c, out_s);
-    PCM_HIPCK(c, hipGetLastError());
-    PCM_HIPCK(c, hipMemcpyAsync(S->h_small, small, sizeof(uint32_t) * kSmallWords, hipMemcpyDeviceToHost, st));
-    PCM_HIPCK(c, hipStreamSynchronize(st));
-    if (!take_counters(S->h_small, n0, n1, &r)) { c->err = "pcm_loam_dynmap_crop: inconsistent counts"; return PCM_ERR_INTERNAL; }
-  }
-  commit_crop(c, S, w, &r);
-  *result = r;
-  return PCM_OK;
+  if ((rc = crop_contexts(&c, 1, params, pose6, result, true)) != PCM_OK) std::memset(result, 0, sizeof(*result));
+  return rc;
 }
 
-// The crops of n contexts in one round of launches on the stream of the first context.  Host: per context the window and the
-// unchanged short-cut, the target's room, the entry table into one pinned block; one upload (descriptors, block prefix, entry
-// tables), one clear (counters and count slices), four launches, one read-back of all counters, one wait.
 int pcm_loam_dynmap_crop_batch(pcm_ctx* const* ctxs, int n, const pcm_loam_dynmap_params* params, const float* poses6, pcm_loam_dynmap_crop_result* results) {
   if (!ctxs || n <= 0 || !poses6 || !results) return PCM_ERR_INVALID_ARGUMENT;
-  pcm_ctx* c0 = ctxs[0];
-  DynStore* S0 = nullptr;
-  int rc = check_ctx_dm(c0, &S0);
-  if (rc != PCM_OK) return rc;
-  std::memset(results, 0, sizeof(pcm_loam_dynmap_crop_result) * (size_t)n);
-  int worst = PCM_OK;
-  auto fail = [&](int i, int status, pcm_ctx* c) {
-    results[i].status = status;
-    if (c && c != c0) c0->err = c->err;
-    if (worst == PCM_OK) worst = status;
-  };
-  PCM_HIPCK(c0, hipSetDevice(c0->device));
-  // what every context asks for; nothing is changed yet
-  std::vector<BatchJob> jobs;
-  std::vector<uint32_t> nbs;
-  jobs.reserve((size_t)n); nbs.reserve((size_t)n);
-  for (int i = 0; i < n; i++) {
-    pcm_ctx* c = ctxs[i];
-    DynStore* S = nullptr;
-    if ((rc = check_ctx_dm(c, &S)) != PCM_OK) {
-      if (!c) c0->err = "pcm_loam_dynmap_crop_batch: null context";
-      fail(i, rc, c);
-      continue;
-    }
-    if (c->device != c0->device) { c0->err = "all contexts of a batch must live on one device"; fail(i, PCM_ERR_INVALID_ARGUMENT, nullptr); continue; }
-    bool twice = false;
-    for (int j = 0; j < i; j++) twice = twice || ctxs[j] == c;
-    if (twice) { c0->err = "a context appears twice in the batch"; fail(i, PCM_ERR_INVALID_ARGUMENT, nullptr); continue; }
-    pcm_loam_dynmap_params p;
-    const float* pose6 = poses6 + 6 * (size_t)i;
-    if ((rc = check_dparams(c, params, pose6, &p)) != PCM_OK) { fail(i, rc, c); continue; }
-    if (!S->h.s.loaded) { c->err = "pcm_loam_dynmap_crop before pcm_loam_dynmap_load"; fail(i, PCM_ERR_NO_INPUT, c); continue; }
-    BatchJob J{};
-    J.i = i; J.c = c; J.S = S;
-    J.w = crop_window(pose6, p.max_range, p.margin, p.crop_x);
-    if (crop_unchanged(c, S, J.w)) {
-      results[i] = S->last;
-      results[i].rebuilt = 0;
-      continue;
-    }
-    selection_size(S, &J.n0, &J.n1, &J.E);
-    if (J.n0 + J.n1 > 0x7fffffffull) { c->err = "the selected tiles hold more than 2^31 points"; fail(i, PCM_ERR_OUT_OF_RANGE, c); continue; }
-    J.nb0 = (uint32_t)((J.n0 + kDmBlock - 1) / kDmBlock);
-    J.nb = J.nb0 + (uint32_t)((J.n1 + kDmBlock - 1) / kDmBlock);
-    jobs.push_back(J);
-    nbs.push_back(J.nb);
-  }
-  std::vector<BatchSlice> slices(jobs.size());
-  BatchLayout lay;
-  if (!batch_layout(nbs.data(), (int)nbs.size(), slices.data(), &lay)) {
-    c0->err = "pcm_loam_dynmap_crop_batch: the workgroups of the batch do not fit one grid: crop in smaller batches";
-    return PCM_ERR_OUT_OF_RANGE;
-  }
-  // room for the targets; a context without points is done here, as in the single call
-  std::vector<BatchJob> live;
-  std::vector<BatchSlice> lsl;
-  size_t E_all = 0;
-  for (size_t k = 0; k < jobs.size(); k++) {
-    BatchJob& J = jobs[k];
-    J.S->h.s.last_valid = false;
-    if ((rc = loam_target_reserve(J.c, (size_t)J.n0, (size_t)J.n1, &J.out[0], &J.out[1])) != PCM_OK) { fail(J.i, rc, J.c); continue; }
-    J.r = crop_record(J.n0, J.n1, J.w);
-    if (J.nb == 0) {
-      commit_crop(J.c, J.S, J.w, &J.r);
-      results[J.i] = J.r;
-      continue;
-    }
-    if (J.S->h.ts->fill_queued && J.c != c0) {   // copies into this store are queued on its sole holder's stream
-      if (hipStreamSynchronize(J.c->stream) != hipSuccess) { J.c->err = "pcm_loam_dynmap_crop_batch: hipStreamSynchronize failed"; fail(J.i, PCM_ERR_HIP, J.c); continue; }
-      J.S->h.ts->fill_queued = false;
-    }
-    live.push_back(J);
-    E_all += J.E;
-  }
-  if (live.empty()) return worst;
-  // a failed reservation took a context out: the slices of those that run
-  const uint32_t m = (uint32_t)live.size();
-  nbs.clear();
-  for (const BatchJob& J : live) nbs.push_back(J.nb);
-  lsl.resize(m);
-  (void)batch_layout(nbs.data(), (int)m, lsl.data(), &lay);   // a subset of what fitted
-  // device block: [descriptors | block prefix | entry tables] uploaded in one copy, [counters | count slices] cleared in one
-  // memset, then the scan-block totals and offsets; the pinned block mirrors the first part
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t r = o; o += up256(bytes); return r; };
-  const size_t o_desc = take(sizeof(DmBatchDesc) * m), o_blk = take(4 * (size_t)m), o_ent = take(sizeof(DmEntry) * E_all), up_bytes = o;
-  const size_t o_small = take(4 * (size_t)kSmallWords * m), o_counts = take(4 * (size_t)lay.slots), zero_bytes = o - o_small;
-  const size_t o_tot = take(4 * (size_t)lay.chunks), o_off = take(4 * (size_t)lay.chunks);
-  hipStream_t st = c0->stream;
-  if ((rc = S0->bbuf.reserve(c0, o, o + o / 2)) != PCM_OK) return rc;
-  if ((rc = S0->h_up.reserve(c0, up_bytes, up_bytes + up_bytes / 2)) != PCM_OK) return rc;
-  if ((rc = S0->h_bsmall.reserve(c0, (size_t)kSmallWords * m, (size_t)kSmallWords * m)) != PCM_OK) return rc;
-  PCM_HIPCK(c0, hipStreamSynchronize(st));   // the pinned staging of an earlier batch is free again
-  char* d = S0->bbuf.p;
-  DmBatchDesc* h_desc = reinterpret_cast<DmBatchDesc*>(S0->h_up.p + o_desc);
-  uint32_t* h_blk = reinterpret_cast<uint32_t*>(S0->h_up.p + o_blk);
-  DmEntry* h_ent = reinterpret_cast<DmEntry*>(S0->h_up.p + o_ent);
-  uint32_t* d_small = reinterpret_cast<uint32_t*>(d + o_small);
-  size_t e0 = 0;
-  for (uint32_t k = 0; k < m; k++) {
-    const BatchJob& J = live[k];
-    const BatchSlice& sl = lsl[k];
-    const TileStore& T = *J.S->h.ts;
-    DmBatchDesc D;
-    std::memset(&D, 0, sizeof(D));
-    D.arena[0] = T.arena[0].d; D.arena[1] = T.arena[1].d;
-    D.ent = reinterpret_cast<const DmEntry*>(d + o_ent) + e0;
-    D.counts = reinterpret_cast<uint32_t*>(d + o_counts) + sl.slot0;
-    D.chunk_tot = reinterpret_cast<uint32_t*>(d + o_tot) + sl.chunk0;
-    D.chunk_off = reinterpret_cast<uint32_t*>(d + o_off) + sl.chunk0;
-    D.small = d_small + (size_t)kSmallWords * k;
-    D.out[0] = J.out[0]; D.out[1] = J.out[1];
-    D.n_ent = (uint32_t)J.E; D.nb0 = J.nb0; D.nb = J.nb; D.n0 = (uint32_t)J.n0; D.N = (uint32_t)(J.n0 + J.n1); D.nchunks = sl.nchunks;
-    D.w = J.w;
-    h_desc[k] = D;
-    h_blk[k] = sl.block0;
-    e0 += write_entries(J.S, h_ent + e0);
-  }
-  const DmBatchDesc* d_desc = reinterpret_cast<const DmBatchDesc*>(d + o_desc);
-  const uint32_t* d_blk = reinterpret_cast<const uint32_t*>(d + o_blk);
-  PCM_HIPCK(c0, hipMemcpyAsync(d, S0->h_up.p, up_bytes, hipMemcpyHostToDevice, st));
-  PCM_HIPCK(c0, hipMemsetAsync(d_small, 0, zero_bytes, st));   // the padding of a count slice must scan as zeros
-  k_dm_count_batch<<<lay.blocks, kDmBlock, 0, st>>>(d_desc, d_blk, m);
-  k_dm_scan_chunks<<<lay.chunks, kDmChunk, 0, st>>>(reinterpret_cast<uint32_t*>(d + o_counts), lay.slots, reinterpret_cast<uint32_t*>(d + o_tot));
-  k_dm_scan_tops_batch<<<m, kDmChunk, 0, st>>>(d_desc);
-  k_dm_scatter_batch<<<lay.blocks, kDmBlock, 0, st>>>(d_desc, d_blk, m);
-  PCM_HIPCK(c0, hipGetLastError());
-  PCM_HIPCK(c0, hipMemcpyAsync(S0->h_bsmall, d_small, sizeof(uint32_t) * kSmallWords * m, hipMemcpyDeviceToHost, st));
-  PCM_HIPCK(c0, hipStreamSynchronize(st));
-  S0->h.ts->fill_queued = false;
-  for (uint32_t k = 0; k < m; k++) {
-    BatchJob& J = live[k];
-    if (!take_counters(S0->h_bsmall + (size_t)kSmallWords * k, J.n0, J.n1, &J.r)) {
-      J.c->err = "pcm_loam_dynmap_crop: inconsistent counts";
-      fail(J.i, PCM_ERR_INTERNAL, J.c);
-      continue;
-    }
-    commit_crop(J.c, J.S, J.w, &J.r);
-    results[J.i] = J.r;
-  }
-  return worst;
+  return crop_contexts(ctxs, n, params, poses6, results, false);
 }
 
 int pcm_loam_dynmap_info(pcm_ctx* c, int32_t* corner_tiles, int32_t* surf_tiles, float* corner, float* surf) {

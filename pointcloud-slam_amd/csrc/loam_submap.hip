@@ -60,12 +60,7 @@ struct SmEntry {
 // point gg < N of the concatenated selection under its key frame's matrix; *flags = its entry's
 __device__ __forceinline__ float4 sm_point(const float4* __restrict__ corner_arena, const float4* __restrict__ surf_arena, const float* __restrict__ mats,
                                            const SmEntry* __restrict__ ent, uint32_t n_ent, uint32_t gg, uint32_t* flags) {
-  uint32_t lo = 0, hi = n_ent;   // ent[lo].first <= gg < ent[hi].first (ent[n_ent].first taken as N)
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (ent[mid].first <= gg) lo = mid; else hi = mid;
-  }
-  const SmEntry e = ent[lo];
+  const SmEntry e = ent[table_row_of(&ent->first, sizeof(SmEntry) / 4, n_ent, gg)];   // never an empty entry: the last row at or before gg
   const float4* __restrict__ arena = (e.flags & 1u) ? surf_arena : corner_arena;
   const float4 p = arena[(size_t)e.src + (gg - e.first)];
   const float* __restrict__ T = mats + 12 * (size_t)e.mat;
@@ -177,17 +172,29 @@ struct SmWork {
   DevBuf<SmEntry> ent{"key-frame entry table"};
   DevBuf<unsigned int> part{"partial boxes"};   // one_shot: [kGmBlocks][6]
   size_t n_cap = 0;
-  size_t o_in = 0, o_cells = 0;
+  float4* d_in = nullptr;        // inside buf (sm_carve): the gathered points
+  float4* d_cells = nullptr;     //                          the pass's own cells
   vg::Work grid{};               // the VoxelGrid's arrays, inside buf
   PinnedBuf<uint32_t> h_small;
   PinnedBuf<SmEntry> h_ent;      // staging of the entry table
   bool in_flight = false;        // the last near pass was left without a wait: its staging is not free yet
   bool one_shot = false;
 
-  template <class T> T* at(size_t off) const { return reinterpret_cast<T*>(buf.p + off); }
-  float4* in() const { return at<float4>(o_in); }
-  float4* cells() const { return at<float4>(o_cells); }
+  float4* in() const { return d_in; }
+  float4* cells() const { return d_cells; }
 };
+
+// buf's layout: [gathered points | own cells | the VoxelGrid's Work].  Over a null base the size query, over buf.p the carve.
+struct SmCarve { float4* in; float4* cells; char* grid; size_t bytes; };
+SmCarve sm_carve(char* base, size_t n_in, size_t n_cells, size_t grid_bytes) {
+  ArenaCarver a(base);
+  SmCarve c;
+  c.in = a.take<float4>(n_in);
+  c.cells = a.take<float4>(n_cells);
+  c.grid = a.take<char>(grid_bytes);
+  c.bytes = a.used();
+  return c;
+}
 
 // room for N points and n_ent entries; keys of key_bytes each.  segmented: the head and box arrays and the second segment exist.
 // sorted: the arrays of the VoxelGrid exist (a one-shot pass without a leaf has none); own_cells: the cell array does.
@@ -204,16 +211,14 @@ int ensure_work(pcm_ctx* c, SmWork* W, size_t N, size_t n_ent, size_t key_bytes,
   W->buf.release();   // the layout below is for the new sizes alone
   W->n_cap = 0;
   const size_t nc = W->one_shot ? N : N + N / 4 + 1024, ns = sorted ? nc : 0;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t r = o; o += up256(bytes); return r; };
-  W->o_in = take(16 * ns);
-  W->o_cells = take(own_cells ? 16 * nc : 16);
-  const size_t nseg = segmented ? 2 : 0;
+  const size_t nseg = segmented ? 2 : 0, n_cells = own_cells ? nc : 1;
   size_t vg_bytes = 0;
   (void)vg::work_layout(nullptr, ns, key_bytes, nseg, &vg_bytes);
-  const size_t o_vg = take(vg_bytes);
-  if ((rc = W->buf.reserve(c, o, o)) != PCM_OK) return rc;
-  W->grid = vg::work_layout(W->buf.p + o_vg, ns, key_bytes, nseg, &vg_bytes);
+  const size_t bytes = sm_carve(nullptr, ns, n_cells, vg_bytes).bytes;
+  if ((rc = W->buf.reserve(c, bytes, bytes)) != PCM_OK) return rc;
+  const SmCarve at = sm_carve(W->buf.p, ns, n_cells, vg_bytes);
+  W->d_in = at.in; W->d_cells = at.cells;
+  W->grid = vg::work_layout(at.grid, ns, key_bytes, nseg, &vg_bytes);
   W->n_cap = nc;
   return PCM_OK;
 }

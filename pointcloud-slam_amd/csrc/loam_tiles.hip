@@ -86,11 +86,7 @@ __global__ void __launch_bounds__(256) k_tile_rank(const uint32_t* __restrict__ 
   const uint32_t g = blockIdx.x * 256u + threadIdx.x;
   const bool in = g < N;
   const uint32_t k = in ? keys[g] : kNoTileKey;
-  uint32_t lo = 0, hi = T;   // T >= 1; distinct[lo] <= k < distinct[hi] (distinct[T] taken as infinite) once distinct[0] <= k
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (distinct[mid] <= k) lo = mid; else hi = mid;
-  }
+  const uint32_t lo = table_row_of(distinct, 1u, T, k);   // T >= 1; row 0 when k lies before the table: the comparison below says so
   const bool found = k != kNoTileKey && distinct[lo] == k;
   if (in) seg[g] = found ? lo : kNoTile;
   const uint64_t lost = __ballot(in && k != kNoTileKey && !found);

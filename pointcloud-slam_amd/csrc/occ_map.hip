@@ -54,11 +54,7 @@ __global__ void k_occ_move(const uint2* __restrict__ src, OccRect a, uint2* __re
 __global__ void __launch_bounds__(256) k_occ_scan(const OccSeg* __restrict__ segs, const uint32_t* __restrict__ off, uint32_t nseg, uint32_t total, OccParams P,
                                                   uint32_t beams, uint32_t* __restrict__ table) {
   for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < total; g += gridDim.x * blockDim.x) {
-    uint32_t lo = 0, hi = nseg;
-    while (hi - lo > 1) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (off[mid] <= g) lo = mid; else hi = mid;
-    }
+    const uint32_t lo = table_row_of(off, 1u, nseg, g);
     const OccSeg sg = segs[lo];
     const uint32_t k = g - off[lo];
     if (k >= sg.n) continue;

@@ -1,6 +1,8 @@
 """GPU checks of the localisation map tiles and the per-frame crop (pcm_loam_tile_*, pcm_loam_dynmap_*) against the CPU restatement of
 tests/loam_dynmap_ref.py.  The crop kernels take 256 points per workgroup and scan 256 workgroup counts per scan block; an arena's
-first allocation holds 65 536 points."""
+first allocation holds 65 536 points.  pcm_loam_dynmap_crop runs the batched path with one context; test_single_call_contract pins
+what its caller sees."""
+import ctypes as C
 import importlib
 
 import numpy as np
@@ -414,6 +416,72 @@ def test_run_to_run(pcm):
     c = h.dynmap_info()
     for k in ("corner", "surf"):
         assert len(a[k]) > 1000 and np.array_equal(bits(a[k]), bits(b[k])) and np.array_equal(bits(a[k]), bits(c[k])), k
+
+
+HAND = [0, 1, 63, 64, 65, 255, 256, 257, 1023, 1025, 3000]
+
+
+def hand():
+    """Both lists hold tiles of the HAND sizes (the surf list reversed), four records with a non-finite coordinate and one with a
+    non-finite intensity among them."""
+    if "hand" not in _CACHE:
+        ts = synth_tiles.make_sized_tiles(5, HAND, HAND[::-1])
+        for lst, (t, i, col, v) in ((ts.corner_tiles, (10, 7, 0, np.nan)), (ts.corner_tiles, (8, 1000, 2, np.inf)), (ts.surf_tiles, (0, 2999, 1, -np.inf)),
+                                    (ts.surf_tiles, (2, 5, 1, np.nan)), (ts.corner_tiles, (4, 64, 3, np.nan))):   # the last: an intensity, kept
+            lst[t][i, col] = v
+        _CACHE["hand"] = ts
+    return _CACHE["hand"]
+
+
+def raw_crop(pcm, g, x6, margin=1000, max_range=6.0, crop_x=0):
+    """pcm_loam_dynmap_crop itself on a zeroed record: its return value, pcm_last_error's text and the 64 bytes of the record."""
+    p = pcm.capi.PcmLoamDynmapParams()
+    g._L.pcm_loam_default_dynmap_params(C.byref(p))
+    p.margin, p.max_range, p.crop_x = margin, max_range, crop_x
+    x = np.ascontiguousarray(x6, F)
+    r = pcm.capi.PcmLoamDynmapCropResult()
+    rc = g._L.pcm_loam_dynmap_crop(g.handle, C.byref(p), x.ctypes.data, C.byref(r))
+    if rc == 0:
+        g._dm_crop = r   # what crop_map keeps for dynmap_info
+    return rc, (g._L.pcm_last_error(g.handle) or b"").decode(), bytes(r)
+
+
+def test_single_call_contract(pcm):
+    """What the caller of pcm_loam_dynmap_crop sees, whatever runs underneath (a round of one context): the codes and texts of its
+    failures (literals: what the call answered before it shared the batched path) with the record left all zero, the short-cut's
+    record, and two fresh contexts agreeing with each other and with the restatement bit for bit."""
+    ts = hand()
+    x6 = pose(100.0, 10.0)
+    zero = bytes(64)
+    g = filled(pcm, ts)
+    assert raw_crop(pcm, g, x6) == (-2, "pcm_loam_dynmap_crop before pcm_loam_dynmap_load", zero)
+    _, sels = check_load(g, ts, x6, 1000)
+    assert raw_crop(pcm, g, pose(np.nan, 10.0)) == (-1, "the pose must be finite", zero)
+    other = pcm.P2PlaneRegistration(0)
+    assert raw_crop(pcm, other, x6) == (-1, "pcm_loam_tile_* / pcm_loam_dynmap_* need a context created with PCM_MODEL_LOAM", zero)
+    # a forced crop, then the same crop: the same record but for `rebuilt` (bytes 20..23)
+    rc, _, first = raw_crop(pcm, g, x6)
+    assert rc == 0 and np.frombuffer(first, np.int32)[5] == 1 and np.frombuffer(first, np.int32)[10] == 0
+    rc, _, again = raw_crop(pcm, g, x6)
+    assert rc == 0 and np.frombuffer(again, np.int32)[5] == 0
+    assert again[:20] + again[24:] == first[:20] + first[24:]
+    # a failure in between changes neither the target nor the short-cut
+    assert raw_crop(pcm, g, pose(100.0, np.inf))[0] == -1
+    assert raw_crop(pcm, g, x6)[2] == again
+    # two fresh contexts, the same tiles and pose: identical records, identical target bits, and the restatement's
+    h = filled(pcm, ts)
+    h.load_map(x6, margin=1000)
+    rc, _, second = raw_crop(pcm, h, x6)
+    assert rc == 0 and second == first
+    ref = R.crop(ts.lists(), sels, x6, 6.0, 1000, 0)
+    rec = np.frombuffer(first, np.int32)
+    print("in %d + %d, kept %d + %d, non-finite %d" % tuple(rec[:5]))
+    assert tuple(rec[:5]) == (ref["corner_in"], ref["surf_in"], len(ref["corner"]), len(ref["surf"]), ref["nonfinite"]) and rec[4] == 4
+    assert 0 < rec[2] < rec[0] and 0 < rec[3] < rec[1]
+    assert np.array_equal(np.frombuffer(first, np.uint32)[6:10], bits(np.array(ref["window"])))
+    ig, ih = g.dynmap_info(), h.dynmap_info()
+    for k in ("corner", "surf"):
+        assert ig[k].shape == ref[k].shape and np.array_equal(bits(ig[k]), bits(ref[k])) and np.array_equal(bits(ih[k]), bits(ig[k])), k
 
 
 def test_errors(pcm):

@@ -281,6 +281,9 @@ def fleet(pcm):
 @pytest.mark.parametrize("names", [("big",), ("empty", "hand"), ("no_corner", "still", "nothing"), ("hand", "big", "empty", "still", "nothing_no_corner")],
                          ids=["B1", "B2", "B3", "B5"])
 def test_batch_equals_single_crops(pcm, names, params):
+    # The single crop is the batched path with one context (crop_contexts in csrc/loam_dynmap.hip), so "the batch equals a context
+    # cropped alone" compares one path with itself: it shows that a context's bits do not depend on its company in the round.  The
+    # independent check of every case is check_against_ref, against the numpy restatement (tests/loam_dynmap_ref.py), and stays.
     plan, _keep = fleet(pcm)
     if "nothing_no_corner" in names:   # B = 5 holds all six cases: the window that keeps nothing falls on the store without corner tiles
         g, ts_name, x_load, margin, _ = plan["no_corner"]

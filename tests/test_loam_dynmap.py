@@ -1,7 +1,9 @@
 """CPU checks of the localisation map's host logic (pointcloud-slam_amd/csrc/loam_dynmap.h, compiled with g++ through
 tests/loam_dynmap_hooks.cpp) against the numpy restatement (tests/loam_dynmap_ref.py): tile selection, reload trigger, window
 limits and the crop predicate; of the synthetic tile layouts (asserted on the restatement alone); of read_arealist /
-write_arealist; and of the pcm_loam_dynmap_* struct layouts against the ctypes binding.  No GPU."""
+write_arealist; of the pcm_loam_dynmap_* struct layouts against the ctypes binding; and, through tests/loam_dynmap_batch_hooks.cpp,
+of the crop's workspace layout (crop_carve) and of the table search every concatenation kernel uses (csrc/table_search.h) against
+numpy.searchsorted.  No GPU."""
 import ctypes as C
 import importlib
 import os
@@ -240,6 +242,79 @@ def test_arealist_round_trip(tmp_path, pcm):
     path2 = str(tmp_path / "again.csv")
     pcm.write_arealist(path2, back)
     assert open(path2).read() == open(path).read()
+
+
+@pytest.fixture(scope="module")
+def BH(tmp_path_factory):
+    """csrc/loam_dynmap.h's crop_carve and csrc/table_search.h's table_row_of (tests/loam_dynmap_batch_hooks.cpp)."""
+    so = str(tmp_path_factory.mktemp("dynmap_carve_hooks") / "loam_dynmap_batch_hooks.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-fPIC", "-shared", "-I",
+                    os.path.join(ROOT, "pointcloud-slam_amd", "csrc"), os.path.join(ROOT, "tests", "loam_dynmap_batch_hooks.cpp"), "-o", so], check=True)
+    L = C.CDLL(so)
+    L.dynmap_batch_hook_carve.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
+    L.dynmap_batch_hook_row_of.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+    L.dynmap_batch_hook_row_of.restype = C.c_uint32
+    return L
+
+
+def up256(x):
+    return (x + 255) // 256 * 256
+
+
+@pytest.mark.parametrize("nb, n_ent", [([1], [1]), ([0, 257], [0, 3]), ([256, 0, 1, 300, 2], [2, 0, 1, 7, 1])])
+def test_crop_workspace_carve(BH, nb, n_ent):
+    """One layout function gives the size (null base) and the carve: 256-byte blocks that do not overlap, the upload range
+    [descriptors | block prefix | entry tables] and the zero range [counters | count slices] each contiguous and nothing else."""
+    small_words = 4
+    nb_a, ne_a = np.asarray(nb, np.uint32), np.asarray(n_ent, np.uint32)
+    out = np.zeros(16, np.uint64)
+    assert BH.dynmap_batch_hook_carve(nb_a.ctypes.data, len(nb), ne_a.ctypes.data, small_words, out.ctypes.data) == 1
+    out = [int(v) for v in out]
+    off, (up_bytes, zero_bytes, used, used_null, null_ok, sz_desc, sz_ent, slots, chunks) = out[:7], out[7:]
+    m, E = len(nb), sum(n_ent)
+    assert (sz_desc, sz_ent) == (120, 16) and chunks == sum(-(-b // 256) for b in nb) and slots == 256 * chunks
+    # desc, block0, ent, small, counts, chunk_tot, chunk_off
+    size = [sz_desc * m, 4 * m, sz_ent * E, 4 * small_words * m, 4 * slots, 4 * chunks, 4 * chunks]
+    assert all(o % 256 == 0 for o in off)
+    assert off == sorted(off)   # in this order
+    for k in range(6):
+        assert off[k] + size[k] <= off[k + 1]   # no overlap
+    # the upload range: starts at the base, holds the three blocks back to back (each padded to 256) and ends where the zero range begins
+    assert off[0] == 0 and off[1] == up256(size[0]) and off[2] == off[1] + up256(size[1])
+    assert up_bytes == off[2] + up256(size[2]) == off[3]
+    # the zero range: counters, then count slices, and ends where the scan-block totals begin
+    assert off[4] == off[3] + up256(size[3]) and zero_bytes == off[5] - off[3] == up256(size[3]) + up256(size[4])
+    # the size query is the extent of the carve
+    assert off[6] == off[5] + up256(size[5]) and used == off[6] + up256(size[6])
+    assert used_null == used and null_ok == 1
+
+
+def _row_of(BH, first, stride, g):
+    table = np.zeros((len(first), stride), np.uint32)
+    table[:, 1 if stride > 1 else 0] = first   # the entry tables keep the first position in their second word
+    field = table.ctypes.data + (4 if stride > 1 else 0)
+    return BH.dynmap_batch_hook_row_of(field, stride, len(first), int(g))
+
+
+@pytest.mark.parametrize("rows", [1, 2, 3, 64, 65])
+def test_table_search_matches_searchsorted(BH, rows):
+    """The last row whose first position is <= g, as numpy.searchsorted(first, g, side="right") - 1 says; equal neighbours (an
+    empty row shares its position with its successor) included: an empty row is never the answer where the next row holds g."""
+    rng = np.random.default_rng(rows)
+    tables = [np.arange(rows, dtype=np.uint32) * 7, np.zeros(rows, np.uint32)]
+    for _ in range(6):
+        lens = rng.choice([0, 0, 1, 2, 5, 300], rows)   # many empty rows, runs of them too
+        tables.append(np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint32))
+    big = (np.arange(rows, dtype=np.uint64) * (0x7fffffff // rows)).astype(np.uint32)   # positions up to 2^31
+    tables.append(big)
+    for first in tables:
+        assert np.all(np.diff(first.astype(np.int64)) >= 0) and first[0] == 0
+        probes = set(int(v) for v in first) | set(int(v) + 1 for v in first) | set(max(int(v), 1) - 1 for v in first) | {int(first[-1]) + 1000}
+        for stride in (1, 4):
+            for g in sorted(probes):
+                r = _row_of(BH, first, stride, g)
+                assert r == int(np.searchsorted(first, g, side="right")) - 1, (list(first), stride, g)
+                assert r == rows - 1 or first[r + 1] > g   # row r is not empty at g
 
 
 def test_struct_layouts(H, pcm):

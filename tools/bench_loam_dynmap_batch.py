@@ -5,8 +5,9 @@ one a tenth of that.  For B in 1, 8, 32, in one process:
   set-up   B owners (each uploads the whole map: what a fleet pays without sharing) against 1 owner + B - 1 sharers: wall time and
            device memory in use afterwards (hipMemGetInfo through torch);
   crop     B forced-rebuild crops (every robot at its own pose, moved by a centimetre per sample, which moves the windows and changes
-           no work) as a loop of single crop_map calls -- the code path without the batch call -- against one loam_crop_map_batch,
-           on the same shared fleet, samples interleaved: median, minimum and maximum of --runs after a warm-up;
+           no work) as a loop of single crop_map calls against one loam_crop_map_batch, on the same shared fleet, samples
+           interleaved: median, minimum and maximum of --runs after a warm-up.  Both are one code path (a single crop is a round of
+           one context): the loop pays the round's upload, four launches, read-back and wait once per context, the batch once;
   identity every target of the two ways at one pose, compared on the device bit for bit; a difference fails the run.
 Prints one JSON line (and writes it to --out).  --trace runs nothing but batched crops of --trace-size at B = 32, for a kernel trace
 whose rows all belong to this path."""
