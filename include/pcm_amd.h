@@ -1518,6 +1518,111 @@ int pcm_occ_get_pgm(pcm_ctx *ctx, uint8_t *data, size_t capacity);
 int pcm_occ_get_counts(pcm_ctx *ctx, uint32_t *n_occ, uint32_t *n_free, size_t capacity);
 
 /*
+ * octomap_server's 3D occupancy map and its projected 2D map on the device (src/tool/octomap_server: insertCloudCallback,
+ * insertScan, publishAll's projected_map and octomap_point_cloud_centers) with map_saver's files: the cloud_to_map route of the
+ * reference (pcd2map -> octomap_server -> map_saver).  A sparse set of finest-level cells, each a float log-odds, in a hash table
+ * on the device that grows by doubling up to max_cells.  A scan updates a cell at most once (a hit when an end point fell into
+ * it, else a miss), so the map does not depend on the order of rays.  The map belongs to a context of any model; a PCM_MODEL_LOAM
+ * context can also feed it from its key-frame store in place.  Not built: filter_ground (the caller passes a ground cloud of its
+ * own), colour, markers, the octomap messages, clearBBX, the incremental projection.  DESIGN.md section 38.
+ */
+typedef struct pcm_octo_params {
+  double resolution;             /* 0.05   metres per cell; keys are 16 bit per axis, so the map spans +-32768 cells */
+  double prob_hit;               /* 0.7    sensor_model/hit: a cell's update is (float)log(p / (1 - p)) */
+  double prob_miss;              /* 0.4    sensor_model/miss */
+  double clamp_min;              /* 0.12   sensor_model/min */
+  double clamp_max;              /* 0.97   sensor_model/max */
+  double max_range;              /* -1     sensor_model/max_range: longer rays are cut there and clear only; < 0: off */
+  double min_range;              /* -1     closer points are skipped; <= 0: off */
+  double pointcloud_min_x;       /* -DBL_MAX  the three PassThrough windows of insertCloudCallback (world frame), applied as floats */
+  double pointcloud_max_x;       /* DBL_MAX */
+  double pointcloud_min_y;
+  double pointcloud_max_y;
+  double pointcloud_min_z;
+  double pointcloud_max_z;
+  double occupancy_min_z;        /* -DBL_MAX  cells whose z extent meets (occupancy_min_z, occupancy_max_z) enter the projection */
+  double occupancy_max_z;        /* DBL_MAX */
+  double min_x_size;             /* 0      the projected map covers at least [-min_x_size / 2, min_x_size / 2] */
+  double min_y_size;             /* 0 */
+  int32_t filter_speckles;       /* 0      occupied cells without an occupied cell among their 26 neighbours are left out */
+  int32_t reserved0;
+  uint64_t initial_cells;        /* 65536  cells the first table has room for */
+  uint64_t max_cells;            /* 2^28   the table never grows beyond room for this many cells */
+  int32_t reserved[8];
+} pcm_octo_params;
+
+typedef struct pcm_octo_insert_result {
+  uint64_t points_in;            /* ground + non-ground */
+  uint64_t dropped_nonfinite;    /* a non-finite coordinate (after sensor_to_world) */
+  uint64_t skipped_window;       /* outside a pointcloud_min / max window */
+  uint64_t skipped_min_range;
+  uint64_t truncated;            /* rays cut at max_range */
+  uint64_t rejected_rays;        /* origin or end outside the key range, or the walk left it: the ray clears nothing */
+  uint64_t cells_touched;        /* cells that received their one update */
+  uint64_t new_cells;            /* of those, cells that were unknown before */
+  uint32_t table_growths;        /* rehashes into a larger table during this call */
+  int32_t status;                /* the call's return value */
+  int32_t reserved[8];
+} pcm_octo_insert_result;
+
+typedef struct pcm_octo_map_info {
+  uint64_t cells;                /* known cells */
+  uint64_t occupied;             /* log-odds >= 0 */
+  uint64_t free_cells;
+  uint64_t capacity;             /* cells the table has room for */
+  uint64_t epoch;                /* mark passes since the reset */
+  int32_t key_min[3];            /* key box of the known cells; cells == 0: 0, 0, 0 */
+  int32_t key_max[3];
+  double metric_min[3];          /* keyToCoord(key_min) - res / 2 */
+  double metric_max[3];          /* keyToCoord(key_max) + res / 2 */
+  double resolution;
+  float hit, miss, clamp_min, clamp_max;   /* the four log-odds constants in use */
+  int32_t reserved[8];
+} pcm_octo_map_info;
+
+typedef struct pcm_octo_grid_info {
+  int32_t width, height;         /* 0, 0: at most one known cell, nothing is produced (publishAll :501) */
+  int32_t min_key_x, min_key_y;  /* key of column 0 / row 0 */
+  double resolution;
+  double origin_x, origin_y;     /* nav_msgs/MapMetaData origin.position */
+  int32_t reserved[8];
+} pcm_octo_grid_info;
+
+void pcm_octo_default_params(pcm_octo_params *params);
+/* an empty map with these parameters (NULL = defaults); they hold until the next reset.  Device memory is kept when the first
+ * table is no larger than the one in place. */
+int pcm_octo_reset(pcm_ctx *ctx, const pcm_octo_params *params);
+/* insertCloudCallback + insertScan of one cloud, given as its ground part (clears only) and its non-ground part: records of
+ * stride_bytes, x y z first, host or device memory (device, stride 16, 16-byte aligned: read in place); either may be empty.
+ * origin: the sensor origin in the world frame; sensor_to_world: row-major float 4x4 applied to every point first, or NULL.  One
+ * stream synchronisation when the table does not grow.  A table that would exceed max_cells: PCM_ERR_OUT_OF_RANGE, and every
+ * log-odds is as it was before the call.  result may be NULL. */
+int pcm_octo_insert_scan(pcm_ctx *ctx, const void *ground, size_t n_ground, const void *nonground, size_t n_nonground, size_t stride_bytes,
+                         int memory, const float origin[3], const float *sensor_to_world, pcm_octo_insert_result *result);
+/* PCM_MODEL_LOAM: key frames first .. first + n - 1 of the context's store, one scan each: the corner and surf cloud where they lie
+ * on the device, moved by the stored pose, every point non-ground, the origin the pose's translation.  Stops at the first error. */
+int pcm_octo_insert_keyframes(pcm_ctx *ctx, int first, int n);
+int pcm_octo_info(pcm_ctx *ctx, pcm_octo_map_info *info);
+/* the known cells as 16-byte records (int32 key x, y, z; float log-odds) sorted by the packed key (x << 32 | y << 16 | z) into a
+ * host or device buffer of capacity records; *n is always set; out NULL with capacity 0 asks for the count */
+int pcm_octo_get_cells(pcm_ctx *ctx, void *out, size_t capacity, int memory, size_t *n);
+/* octomap_point_cloud_centers: (x, y, z, log-odds) floats of the occupied cells inside the occupancy z window (and past the
+ * speckle filter), in the same order and under the same buffer rules */
+int pcm_octo_get_occupied(pcm_ctx *ctx, void *out, size_t capacity, int memory, size_t *n);
+/* projected_map rebuilt completely at full depth: the geometry, and width x height values (row-major, i + j * width: -1 unknown,
+ * 0 free, 100 occupied) into a host or device buffer of capacity cells when grid is not NULL */
+int pcm_octo_project(pcm_ctx *ctx, pcm_octo_grid_info *info, int8_t *grid, size_t capacity, int memory);
+/* the body of map_saver's P5 image of that map: width x height bytes, rows top-down (205 unknown, 254 free, 0 occupied) */
+int pcm_octo_get_pgm(pcm_ctx *ctx, uint8_t *data, size_t capacity, int memory);
+/* measurement hooks (tools/bench_octo_map.py).  mark_variant: 0 one ray per lane (the default), 1 one ray per wave (the same map,
+ * bit for bit), + 2: without the dry walk in front of the marking walk -- a measurement only: a rejected ray then leaves its marks.
+ * timed: device events around the mark pass and around apply + fold of every insert (one more wait per insert).  The phases of
+ * the context's last insert: ms[0] mark, ms[1] apply + fold (both summed over the passes of a call that grew the table; zero
+ * unless timed), ms[2] host ms spent rehashing, ms[3] mark passes timed. */
+int pcm_octo_debug(pcm_ctx *ctx, int mark_variant, int timed);
+int pcm_octo_phase_ms(pcm_ctx *ctx, float ms[4]);
+
+/*
  * The ring-tagged scan the LOAM front end reads, made on the device from the sensors' own buffers: jueying_slam's
  * fusion_lidar_camera node (src/tool/integrate_points/src/fusion_lidar_camera.cpp: the LiDAR cloud, then 1-3 depth-camera clouds
  * moved into the LiDAR frame with a ring from their pitch angle) and its rs_to_velodyne / hesai_to_velodyne converters

@@ -23,6 +23,7 @@
 #include <Eigen/Eigenvalues>
 #include <Eigen/Geometry>
 #include <cfloat>
+#include <cstdio>
 #include <iostream>
 #include <memory>
 #include <stdexcept>
@@ -1057,6 +1058,114 @@ private:
   bool own_ = false;
   pcm_occ_params params_;
   std::vector<float> buf_;
+};
+
+// octomap_server's node (src/tool/octomap_server) on the device: insertCloudCallback + insertScan per cloud, the projected 2D map
+// and map_saver's files.  The setters carry the node's parameter names; they are read by the next reset(),
+// which the first insertCloud() runs when nothing did.  Constructed alone it owns a context; constructed over a LoamScanToMap it
+// maps that context's key frames in place.  tf lookups and the ground segmentation (filter_ground) stay with the caller.
+template <typename PointT>
+class OccupancyMap3D {
+public:
+  using Cloud = pcl::PointCloud<PointT>;
+  struct ProjectedMap {   // nav_msgs/OccupancyGrid
+    std::vector<int8_t> data;
+    int width = 0, height = 0;
+    double resolution = 0, origin_x = 0, origin_y = 0;
+  };
+
+  explicit OccupancyMap3D(int device = 0) : ctx_(pcm_create(device, nullptr)), own_(true) {
+    if (!ctx_) throw std::runtime_error("pcm_create failed");
+    pcm_octo_default_params(&params_);
+  }
+  explicit OccupancyMap3D(LoamScanToMap<PointT>& loam) : ctx_(loam.context()), own_(false) { pcm_octo_default_params(&params_); }
+  ~OccupancyMap3D() { if (own_ && ctx_) pcm_destroy(ctx_); }
+  OccupancyMap3D(const OccupancyMap3D&) = delete;
+  OccupancyMap3D& operator=(const OccupancyMap3D&) = delete;
+
+  pcm_octo_params& params() { return params_; }
+  void setResolution(double res) { params_.resolution = res; }
+  void setSensorModel(double hit, double miss, double min, double max) { params_.prob_hit = hit; params_.prob_miss = miss; params_.clamp_min = min; params_.clamp_max = max; }
+  void setMaxRange(double max_range) { params_.max_range = max_range; }
+  void setMinRange(double min_range) { params_.min_range = min_range; }
+  void setPointcloudZ(double min_z, double max_z) { params_.pointcloud_min_z = min_z; params_.pointcloud_max_z = max_z; }
+  void setOccupancyZ(double min_z, double max_z) { params_.occupancy_min_z = min_z; params_.occupancy_max_z = max_z; }
+  void setFilterSpeckles(bool on) { params_.filter_speckles = on ? 1 : 0; }
+  void setMinSize(double min_x_size, double min_y_size) { params_.min_x_size = min_x_size; params_.min_y_size = min_y_size; }
+  void reset() { check(pcm_octo_reset(ctx_, &params_), "pcm_octo_reset"); ready_ = true; }
+
+  // insertCloudCallback: the cloud in the sensor frame, sensor_to_world as the tf lookup gave it; every point non-ground
+  pcm_octo_insert_result insertCloud(const Cloud& cloud, const Eigen::Matrix4f& sensor_to_world) { return insertCloud(Cloud(), cloud, sensor_to_world); }
+  // the same with the caller's own ground / non-ground split
+  pcm_octo_insert_result insertCloud(const Cloud& ground, const Cloud& nonground, const Eigen::Matrix4f& sensor_to_world) {
+    if (!ready_) reset();
+    detail::pack_xyzi(ground, gbuf_);
+    detail::pack_xyzi(nonground, buf_);
+    float T[16], origin[3];
+    for (int r = 0; r < 4; r++)
+      for (int c = 0; c < 4; c++) T[4 * r + c] = sensor_to_world(r, c);
+    for (int r = 0; r < 3; r++) origin[r] = sensor_to_world(r, 3);
+    pcm_octo_insert_result res;
+    check(pcm_octo_insert_scan(ctx_, gbuf_.data(), ground.points.size(), buf_.data(), nonground.points.size(), 4 * sizeof(float), PCM_MEM_HOST, origin, T, &res),
+          "pcm_octo_insert_scan");
+    return res;
+  }
+  // key frames first .. first + n - 1 of LoamKeyFrameMap, one scan each, without leaving the device
+  void insertKeyFrames(int first, int n) {
+    if (!ready_) reset();
+    check(pcm_octo_insert_keyframes(ctx_, first, n), "pcm_octo_insert_keyframes");
+  }
+  pcm_octo_map_info info() {
+    pcm_octo_map_info i;
+    check(pcm_octo_info(ctx_, &i), "pcm_octo_info");
+    return i;
+  }
+  // projected_map
+  ProjectedMap projectedMap() {
+    ProjectedMap m;
+    pcm_octo_grid_info g;
+    check(pcm_octo_project(ctx_, &g, nullptr, 0, PCM_MEM_HOST), "pcm_octo_project");
+    m.width = g.width; m.height = g.height; m.resolution = g.resolution; m.origin_x = g.origin_x; m.origin_y = g.origin_y;
+    m.data.assign((size_t)g.width * (size_t)g.height, (int8_t)-1);
+    if (!m.data.empty()) check(pcm_octo_project(ctx_, &g, m.data.data(), m.data.size(), PCM_MEM_HOST), "pcm_octo_project");
+    return m;
+  }
+  // octomap_point_cloud_centers
+  void occupiedCenters(Cloud* out) {
+    size_t n = (size_t)info().occupied;   // an upper bound: the z window and the speckle filter only take away
+    buf_.assign(4 * n, 0.f);
+    if (n) check(pcm_octo_get_occupied(ctx_, buf_.data(), n, PCM_MEM_HOST, &n), "pcm_octo_get_occupied");
+    out->points.resize(n);
+    for (size_t i = 0; i < n; i++) { out->points[i].x = buf_[4 * i]; out->points[i].y = buf_[4 * i + 1]; out->points[i].z = buf_[4 * i + 2]; }
+  }
+  // map_saver: <mapname>.pgm and <mapname>.yaml; false when there is no map yet or a file cannot be written
+  bool saveMap(const std::string& mapname) {
+    const ProjectedMap m = projectedMap();
+    if (m.data.empty()) return false;
+    std::vector<uint8_t> bytes(m.data.size(), (uint8_t)205);
+    check(pcm_octo_get_pgm(ctx_, bytes.data(), bytes.size(), PCM_MEM_HOST), "pcm_octo_get_pgm");
+    const std::string pgm = mapname + ".pgm", yaml = mapname + ".yaml";
+    FILE* out = fopen(pgm.c_str(), "w");
+    if (!out) return false;
+    fprintf(out, "P5\n# CREATOR: map_saver.cpp %.3f m/pix\n%d %d\n255\n", m.resolution, m.width, m.height);
+    fwrite(bytes.data(), 1, bytes.size(), out);
+    fclose(out);
+    FILE* y = fopen(yaml.c_str(), "w");
+    if (!y) return false;
+    fprintf(y, "image: %s\nresolution: %f\norigin: [%f, %f, 0.00]\nnegate: 0\noccupied_thresh: 0.65\nfree_thresh: 0.196\n\n", pgm.c_str(), m.resolution, m.origin_x,
+            m.origin_y);
+    fclose(y);
+    return true;
+  }
+
+private:
+  void check(int rc, const char* what) const {
+    if (rc != PCM_OK) throw std::runtime_error(std::string(what) + ": " + pcm_last_error(ctx_));
+  }
+  pcm_ctx* ctx_ = nullptr;
+  bool own_ = false, ready_ = false;
+  pcm_octo_params params_;
+  std::vector<float> buf_, gbuf_;
 };
 
 // jueying_slam's LOAM front end (imageProjection.cpp:736-823, featureExtraction.cpp:84-247, mapOptmization.cpp:1232-1247) on the

@@ -44,6 +44,8 @@ SYMBOLS = [
     "pcm_lio_search_path",
     "pcm_icp_default_params", "pcm_icp_set_params", "pcm_icp_get_params", "pcm_icp_last", "pcm_icp_trace",
     "pcm_loam_default_sc_loop_params", "pcm_loam_sc_loop_verify", "pcm_loam_sc_loop_closure", "pcm_loam_sc_loop_verifier_exists",
+    "pcm_octo_default_params", "pcm_octo_reset", "pcm_octo_insert_scan", "pcm_octo_insert_keyframes", "pcm_octo_info", "pcm_octo_get_cells",
+    "pcm_octo_get_occupied", "pcm_octo_project", "pcm_octo_get_pgm", "pcm_octo_debug", "pcm_octo_phase_ms",
 ]
 
 PCM_ABI_VERSION = 3   # include/pcm_amd.h
@@ -351,6 +353,33 @@ class PcmOccParams(C.Structure):
                 ("max_radius", C.c_double), ("fill_with_white", C.c_int32), ("use_nan", C.c_int32), ("reserved", C.c_int32 * 8)]
 
 
+class PcmOctoParams(C.Structure):
+    _fields_ = [("resolution", C.c_double), ("prob_hit", C.c_double), ("prob_miss", C.c_double), ("clamp_min", C.c_double), ("clamp_max", C.c_double),
+                ("max_range", C.c_double), ("min_range", C.c_double), ("pointcloud_min_x", C.c_double), ("pointcloud_max_x", C.c_double),
+                ("pointcloud_min_y", C.c_double), ("pointcloud_max_y", C.c_double), ("pointcloud_min_z", C.c_double), ("pointcloud_max_z", C.c_double),
+                ("occupancy_min_z", C.c_double), ("occupancy_max_z", C.c_double), ("min_x_size", C.c_double), ("min_y_size", C.c_double),
+                ("filter_speckles", C.c_int32), ("reserved0", C.c_int32), ("initial_cells", C.c_uint64), ("max_cells", C.c_uint64),
+                ("reserved", C.c_int32 * 8)]
+
+
+class PcmOctoInsertResult(C.Structure):
+    _fields_ = [("points_in", C.c_uint64), ("dropped_nonfinite", C.c_uint64), ("skipped_window", C.c_uint64), ("skipped_min_range", C.c_uint64),
+                ("truncated", C.c_uint64), ("rejected_rays", C.c_uint64), ("cells_touched", C.c_uint64), ("new_cells", C.c_uint64),
+                ("table_growths", C.c_uint32), ("status", C.c_int32), ("reserved", C.c_int32 * 8)]
+
+
+class PcmOctoMapInfo(C.Structure):
+    _fields_ = [("cells", C.c_uint64), ("occupied", C.c_uint64), ("free_cells", C.c_uint64), ("capacity", C.c_uint64), ("epoch", C.c_uint64),
+                ("key_min", C.c_int32 * 3), ("key_max", C.c_int32 * 3), ("metric_min", C.c_double * 3), ("metric_max", C.c_double * 3),
+                ("resolution", C.c_double), ("hit", C.c_float), ("miss", C.c_float), ("clamp_min", C.c_float), ("clamp_max", C.c_float),
+                ("reserved", C.c_int32 * 8)]
+
+
+class PcmOctoGridInfo(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("min_key_x", C.c_int32), ("min_key_y", C.c_int32), ("resolution", C.c_double),
+                ("origin_x", C.c_double), ("origin_y", C.c_double), ("reserved", C.c_int32 * 8)]
+
+
 PCM_SCAN_MAX_SEGMENTS = 8
 PCM_SCAN_LIDAR_XYZIRT, PCM_SCAN_LIDAR_XYZI, PCM_SCAN_DEPTH = 0, 1, 2
 PCM_SCAN_INTENSITY_FLOAT, PCM_SCAN_INTENSITY_UINT8 = 0, 1
@@ -574,6 +603,18 @@ def load_library():
     L.pcm_occ_get_map.argtypes = [vp, vp, sz]
     L.pcm_occ_get_pgm.argtypes = [vp, vp, sz]
     L.pcm_occ_get_counts.argtypes = [vp, vp, vp, sz]
+    L.pcm_octo_default_params.argtypes = [C.POINTER(PcmOctoParams)]
+    L.pcm_octo_default_params.restype = None
+    L.pcm_octo_reset.argtypes = [vp, C.POINTER(PcmOctoParams)]
+    L.pcm_octo_insert_scan.argtypes = [vp, vp, sz, vp, sz, sz, i32, vp, vp, C.POINTER(PcmOctoInsertResult)]
+    L.pcm_octo_insert_keyframes.argtypes = [vp, i32, i32]
+    L.pcm_octo_info.argtypes = [vp, C.POINTER(PcmOctoMapInfo)]
+    L.pcm_octo_get_cells.argtypes = [vp, vp, sz, i32, C.POINTER(sz)]
+    L.pcm_octo_get_occupied.argtypes = [vp, vp, sz, i32, C.POINTER(sz)]
+    L.pcm_octo_project.argtypes = [vp, C.POINTER(PcmOctoGridInfo), vp, sz, i32]
+    L.pcm_octo_get_pgm.argtypes = [vp, vp, sz, i32]
+    L.pcm_octo_debug.argtypes = [vp, i32, i32]
+    L.pcm_octo_phase_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.pcm_scan_default_fuse_params.argtypes = [C.POINTER(PcmScanFuseParams)]
     L.pcm_scan_default_fuse_params.restype = None
     L.pcm_scan_fuse.argtypes = [vp, C.POINTER(PcmScanSegment), i32, C.POINTER(PcmScanFuseParams), vp, sz, i32, C.POINTER(PcmScanFuseResult)]

@@ -339,6 +339,7 @@ struct pcm_ctx {
   pcm::SubState loam_fe;   // PCM_MODEL_LOAM: the front end's cross-frame state and last-frame outputs (loam_features.hip)
   pcm::SubState loam_cloud;   // PCM_MODEL_LOAM: the staged raw cloud and the prepared records of cachePointCloud (loam_cloud.hip)
   pcm::SubState occ;       // any model: the 2D occupancy map (occ_map.hip)
+  pcm::SubState octo;      // any model: the 3D occupancy map (octo_map.hip)
   pcm::SubState icp;       // PCM_MODEL_ICP: parameters, state block, sum rows and trace of the device loop (icp.hip)
   // any model: scan fusion (scan_fuse.hip): staged host segments, the fused records (pcm_scan_fused), counters + tables + scan scratch
   pcm::DevBuf<char> scan_in{"scan_in"}, scan_out{"scan_out"}, scan_tmp{"scan_tmp"};
